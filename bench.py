@@ -18,7 +18,8 @@ ranks, is an error.  `--dry` runs the same launcher / sharding / reduction path 
 Prints ONE JSON line on rank 0 (see the task contract): value = total env-steps / wall time,
 plus `roofline` (algorithmic HBM bytes of the dominant kernel / its HIP-event duration, per rank), at
 N=1 `cpu_baseline` (the C oracle on the host cores, bounded sample), and `parity_checked` (frames of the timed
-region's last step compared bit for bit with the CPU oracle, after the clock has stopped).
+region's last step compared bit for bit with the CPU oracle, after the clock has stopped).  `--dump-outputs DIR` also
+writes what that last step returned to DIR as .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -53,6 +54,10 @@ RASTER_PHASE = {
 ALSO = ("oneroom_rgbd", "maze", "pickup_dr")      # BASELINE.json configs[2..4], timed after the headline in the default run
 HBM_PEAK_GBPS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 PREWARM_S = 0.5             # untimed steps before the W warm-up steps: clocks and caches of a cold box (reported)
+DUMP_PREWARM_STEPS = 1536   # --dump-outputs without --prewarm-steps: a fixed pre-warm (~0.5 s of the headline), so that runs repeat
+DUMP_BYTES = 64 << 20       # --dump-outputs: everything written stays below this
+DUMP_SAMPLE_ENVS = 512      # frames of at most this many envs (a fixed, seeded sample); the per-env vectors are written whole
+DUMP_SAMPLE_SEED = 0
 
 
 def _traffic_sum(per_kernel, source, extra=None):
@@ -356,6 +361,37 @@ def parity_spot_check(vec, last_actions, config, n_check=8):
     return len(pick)
 
 
+# ------------------------------------------------------------------ outputs of the timed path (--dump-outputs)
+
+def dump_outputs(vec, out_dir):
+    """What the timed region's last step handed its caller — observations (and depth maps), rewards, terminated and
+    truncated flags — as float32 .npy files in out_dir.  Rewards and flags of every env; frames of a fixed, seeded sample
+    of envs (sample_env_index.npy) that keeps the whole below DUMP_BYTES.  Returns {file name: shape}."""
+    import numpy as np
+    import torch
+    n = vec.num_envs
+    flat = {"reward": vec.reward, "terminated": vec.terminated, "truncated": vec.truncated}
+    frames = {"obs": vec.obs}
+    if vec.depth is not None:
+        frames["depth"] = vec.depth
+    per_env = sum(t[0].numel() for t in frames.values()) * 4
+    room = DUMP_BYTES - (len(flat) + 2) * n * 8 - (1 << 16)          # (per-env vectors, the index, .npy headers)
+    m = max(0, min(n, DUMP_SAMPLE_ENVS, room // per_env))
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, m, replace=False))
+    out = {name: t.cpu().numpy().astype(np.float32) for name, t in flat.items()}
+    sel = torch.from_numpy(idx).to(vec.obs.device)
+    out.update({name: t[sel].cpu().numpy().astype(np.float32) for name, t in frames.items()})
+    out["sample_env_index"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) < DUMP_BYTES
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:       # (generated files: kept out of git wherever DIR is)
+            f.write("*\n")
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name + ".npy": list(a.shape) for name, a in out.items()}
+
+
 # ------------------------------------------------------------------ launcher
 
 def _free_port():
@@ -392,8 +428,9 @@ class _DryVec:
 
 def measure(args, ctx, config, n, steps, warmup, headline):
     """One BASELINE config through the whole protocol: engine of `n` envs per rank, pre-generated random actions, pre-warm,
-    W warm-up steps, K timed steps between barriers (MAX over ranks), HIP-event kernel times (one launch in 4 / 8), the parity
-    spot check after the clock has stopped, PMC traffic of the raster-phase kernels read by child runs (single GPU).
+    W warm-up steps, K timed steps between barriers (MAX over ranks), HIP-event kernel times (one launch in 4 / 8), the outputs
+    of the last timed step written out (--dump-outputs, headline, rank 0), the parity spot check after the clock has stopped,
+    PMC traffic of the raster-phase kernels read by child runs (single GPU).
     Returns the JSON object of the line (the headline's, or an entry of its `also` list) on rank 0, None elsewhere."""
     import torch
     from miniworld_amd.sharding import ObsAllGather, gather_objects, max_over_ranks, shard_plan
@@ -431,9 +468,11 @@ def measure(args, ctx, config, n, steps, warmup, headline):
 
     # pre-warm: a cold box (fresh lease, idle clocks, cold L2 / instruction caches) is not what the metric describes;
     # untimed and reported, separate from the W warm-up steps of the contract
+    # (a pre-warm of a fixed step count when the outputs are dumped: the timed steps then start from the same state every run)
+    prewarm_steps = args.prewarm_steps or (DUMP_PREWARM_STEPS if args.dump_outputs else 0)
     t_pre = time.perf_counter()
     k = 0
-    while not args.dry and (k < args.prewarm_steps if args.prewarm_steps else time.perf_counter() - t_pre < PREWARM_S):
+    while not args.dry and (k < prewarm_steps if prewarm_steps else time.perf_counter() - t_pre < PREWARM_S):
         for _ in range(16):
             vec.step(actions[k % total])
             k += 1
@@ -465,6 +504,9 @@ def measure(args, ctx, config, n, steps, warmup, headline):
             gath.wait()
         barrier()
         window_s.append(time.perf_counter() - tw)
+    dumped = None
+    if args.dump_outputs and headline and rank == 0:
+        dumped = dump_outputs(vec, args.dump_outputs)
     raster_ms = setup_ms = 0.0
     launches = parity = 0
     if not args.dry:
@@ -518,6 +560,7 @@ def measure(args, ctx, config, n, steps, warmup, headline):
                                "note": "env-steps/s of consecutive timed windows of K steps each (rank 0's clock); `value` is the first — the contract's — window"})(
             [world * n * steps / w for w in window_max]),
         "prewarm_s": prewarm_s,
+        "prewarm_steps": k,
         "parity_checked": sum(r["parity_checked"] for r in per_rank),
         "roofline": {
             "bound": "hbm",
@@ -545,6 +588,9 @@ def measure(args, ctx, config, n, steps, warmup, headline):
                     "under rocprofv3 (traffic_source = live) or, without the profiler, from the committed profile of the named commit",
         },
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped, "sample_seed": DUMP_SAMPLE_SEED,
+                               "note": "what the last timed step returned (float32); frames of the envs in sample_env_index.npy"}
     return out
 
 
@@ -587,7 +633,8 @@ def main():
                     help="pre-warm with exactly this many steps instead of PREWARM_S seconds (A/B runs: the timed region then "
                          "covers the same episode phases in both)")
     ap.add_argument("--no-also", action="store_true", help="skip the extra single-GPU configs timed after the headline (the `also` list)")
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of K steps each; `value` is the first one's (the contract's), the others show the spread")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="timed windows of K steps each (default: the contract's one); `value` is the first one's, more show the spread")
     ap.add_argument("--no-pmc", action="store_true", help="skip the child runs under rocprofv3 that read roofline.traffic during the run")
     ap.add_argument("--dry", action="store_true", help="CPU dry run of the multi-rank path (gloo, no engine)")
     ap.add_argument("--force-dist", action="store_true",
@@ -596,7 +643,13 @@ def main():
     ap.add_argument("--gather-obs", action="store_true",
                     help="also all-gather every rank's observations onto every rank each step (RCCL over xGMI, overlapped "
                          "with the next step; for a single-process trainer).  Not part of the headline workload")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (observations, rewards, flags; float32 .npy, "
+                         "under 64 MB: frames of a fixed, seeded sample of envs) to DIR; rank 0, headline config.  The pre-warm "
+                         "is then a fixed number of steps, so that the same arguments give the same outputs")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry or args.view800):
+        sys.exit("bench.py: --dump-outputs needs the engine's step workload (not --dry, not --view800)")
     if args.view800:
         return view800(args)
     if args.gpus < 1:

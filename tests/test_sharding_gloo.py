@@ -70,7 +70,7 @@ def _bench(*argv, env=None):
 def test_bench_launcher_dry_run_spawns_the_ranks_it_reports():
     """`bench.py --gpus 2 --dry` with no WORLD_SIZE: the script launches its own two ranks (torch.distributed.run on
     127.0.0.1), shards the envs, reduces the time, gathers per-rank entries and prints n_gpus = 2."""
-    out = _bench("--gpus", "2", "--dry", "--steps", "5", "--warmup", "1", "--config", "maze", "--gather-obs")
+    out = _bench("--gpus", "2", "--dry", "--steps", "5", "--warmup", "1", "--config", "maze", "--gather-obs", "--windows", "5")
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -80,7 +80,7 @@ def test_bench_launcher_dry_run_spawns_the_ranks_it_reports():
     assert res["config"]["obs_allgather"] is True
     assert [r["rank"] for r in res["roofline"]["per_rank"]] == [0, 1]
     assert res["value"] > 0 and "dry-run" in res["data"]
-    # five timed windows of K steps each by default, `value` the first one's (MAX over the ranks of each)
+    # five timed windows of K steps each when asked, `value` the first one's (MAX over the ranks of each)
     w = res["windows"]
     assert w["n"] == 5 and w["steps_each"] == 5 and len(w["values"]) == 5 and w["values"][0] == res["value"]
     assert w["min"] <= w["median"] <= w["max"] and min(w["values"]) > 0
@@ -97,6 +97,8 @@ def test_bench_launcher_dry_run_with_eight_ranks():
     assert res["n_gpus"] == 8 and res["scaling"] == "weak" and res["config"]["envs_per_gpu"] == 2048
     assert res["config"]["parallelism"] == "env-shard x8" and [r["rank"] for r in res["roofline"]["per_rank"]] == list(range(8))
     assert res["value"] > 0 and "cpu_baseline" not in res and "also" not in res
+    # by default --steps is the number of timed steps: one window of K
+    assert res["steps"] == 3 and res["windows"]["n"] == 1 and res["windows"]["steps_each"] == 3 and res["windows"]["values"] == [res["value"]]
 
 
 def test_bench_refuses_a_rank_count_it_was_not_asked_for():
