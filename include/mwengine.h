@@ -76,7 +76,16 @@ enum {
  * miniworld.py:677-680).  Every device generator, with and without domain_rand (the Maze's room textures exist in one
  * variant each in the reference, so Room._gen_static_data's variant draws consume nothing there, opengl.py:134-138). */
 enum { MW_RNG_PHILOX = 0, MW_RNG_PCG64 = 1 };
-enum { MW_AUTORESET_OFF = 0, MW_AUTORESET_SAME_STEP = 1 };
+/* Auto-reset of the envs whose episode ended (term | trunc), on the device, with the configured generator (none with MW_GEN_NONE):
+ *   MW_AUTORESET_OFF        never: the caller resets with mw_reset(mask, ...).
+ *   MW_AUTORESET_SAME_STEP  the step that ends an episode installs the next world before its frame is drawn: the observation returned
+ *                           with done = 1 is the first one of the next episode (the terminal frame is never drawn).
+ *   MW_AUTORESET_NEXT_STEP  the step that ends an episode is an ordinary step (its frame shows the terminal state, its reward and flags
+ *                           are the episode's last); the env's NEXT step ignores its action, installs the next world and returns that
+ *                           world's first frame with reward 0 and term = trunc = 0.  The reference's "step; if done: reset()", stream
+ *                           order included (Gymnasium's AutoresetMode.NEXT_STEP); mw_get_reset_pending tells which envs such a
+ *                           step will reset. */
+enum { MW_AUTORESET_OFF = 0, MW_AUTORESET_SAME_STEP = 1, MW_AUTORESET_NEXT_STEP = 2 };
 
 typedef struct mw_engine mw_engine;
 
@@ -103,7 +112,7 @@ typedef struct {
     int32_t max_episode_steps;  /* miniworld.py:472, per env class                 */
     int32_t domain_rand;        /* miniworld.py:478                                */
     int32_t generator;          /* MW_GEN_*                                        */
-    int32_t autoreset;          /* MW_AUTORESET_*                                  */
+    int32_t autoreset;          /* MW_AUTORESET_* (mw_create rejects other values)  */
     double agent_radius;        /* entity.py:470 (0.4)                             */
     double agent_height;        /* entity.py:471 (1.6): height of the top-view marker */
     double max_forward_step;    /* params.get_max("forward_step") miniworld.py:581 */
@@ -272,6 +281,7 @@ int mw_set_geometry(mw_engine *e, int32_t env, const mw_poly *polys, int32_t n_p
 /* state injection / inspection (synchronous) */
 /* reads one geometry set back (polys: max_polys entries, segs: max_segs*4 doubles) */
 int mw_get_geometry(mw_engine *e, int32_t env, mw_poly *polys, int32_t *n_polys, double *segs, int32_t *n_segs);
+/* (clears a pending next-step auto-reset of the envs it writes) */
 int mw_set_state(mw_engine *e, int32_t first_env, int32_t count, const mw_state_view *host);
 /* Test hook: host double[num_envs][3] = forward_step, forward_drift, turn_step to use in
  * the next steps instead of the defaults / device RNG draws (miniworld.py:678-680);
@@ -281,7 +291,8 @@ int mw_get_state(mw_engine *e, int32_t first_env, int32_t count, mw_state_view *
 /* device-side MiniWorldEnv.reset (miniworld.py:544-604) for the configured generator.
  * mask: host uint8[num_envs] or NULL (= all); seeds: host uint64[num_envs] or NULL.
  * With MW_GEN_NONE (host-generated worlds) only the re-seeding happens: seeds[i] (masked) re-seeds env i's device
- * stream, which serves the per-step domain-randomisation draws (miniworld.py:677-680); seeds == NULL is an error. */
+ * stream, which serves the per-step domain-randomisation draws (miniworld.py:677-680); seeds == NULL is an error.
+ * A pending next-step auto-reset of a reset env is dropped (the env's next step is an ordinary one). */
 int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *stream);
 
 /* ---- the hot path ------------------------------------------------------------ */
@@ -290,7 +301,9 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
  *   d_obs     uint8[N][H][W][3]   FrameBuffer.resolve() layout, row 0 = top (opengl.py:339-398)
  *   d_depth   float[N][H][W][1]   FrameBuffer.get_depth_map(0.04, 100) (opengl.py:400-435); NULL = skip
  *   d_reward  float[N], d_term uint8[N], d_trunc uint8[N]
- * All device pointers; asynchronous on `stream`. */
+ * All device pointers; asynchronous on `stream`.  Auto-reset of finished envs: mw_config.autoreset (MW_AUTORESET_*).  With
+ * MW_AUTORESET_NEXT_STEP, mw_render / mw_render_top / mw_get_state / mw_get_info between the step that ends an episode and the next
+ * step see the terminal state. */
 int mw_step(mw_engine *e, const int32_t *d_actions, uint8_t *d_obs, float *d_depth,
             float *d_reward, uint8_t *d_term, uint8_t *d_trunc, void *stream);
 /* Layout of the d_obs buffer written by mw_step / mw_render / mw_render_top — the reference's
@@ -359,14 +372,20 @@ int mw_kernel_time_ms(mw_engine *e, int32_t reset, double *raster_ms, double *se
 /* The `info` dict of the envs' step() as device arrays, asynchronous on `stream` (either pointer may be NULL):
  *   d_health  int32[N]     CollectHealth: info["health"] (collecthealth.py:100)
  *   d_ent_pos double[N][3] position of entity slot `ent_slot`: TMaze / YMaze info["goal_pos"] = box.pos (tmaze.py:89, ymaze.py:125)
- * Values are those of the state the device holds: with MW_AUTORESET_SAME_STEP an env that just finished reports its new episode.
+ * Values are those of the state the device holds: with MW_AUTORESET_SAME_STEP an env that just finished reports its new episode; with
+ * MW_AUTORESET_NEXT_STEP it reports the finished one (its next step installs the new episode).
  * d_health on an engine whose task is not MW_TASK_COLLECT is MW_E_INVALID (there is no health array). */
 int mw_get_info(mw_engine *e, int32_t *d_health, double *d_ent_pos, int32_t ent_slot, void *stream);
 /* The same two values as they stood when each env's LAST FINISHED episode ended (collecthealth.py:100: the health that ended it;
  * tmaze.py:89 / ymaze.py:125: that episode's goal_pos = position of entity slot mw_config.goal_ent) — with MW_AUTORESET_SAME_STEP the step
- * kernel keeps them before it installs the next world (Gymnasium's `final_info` of a same-step vector env).  Undefined for an env that
+ * kernel keeps them before it installs the next world (Gymnasium's `final_info` of a same-step vector env); with MW_AUTORESET_NEXT_STEP it
+ * keeps them on the step that ends the episode (mw_get_info reports the same values until the next step).  Undefined for an env that
  * has not finished an episode yet; either pointer may be NULL; d_health needs MW_TASK_COLLECT. */
 int mw_get_final_info(mw_engine *e, int32_t *d_health, double *d_goal_pos, void *stream);
+/* MW_AUTORESET_NEXT_STEP: d_out uint8[N] (device), 1 = the env's last step ended its episode and its next step will install the next world
+ * (ignoring its action; reward 0, term = trunc = 0) — what a replay buffer masks out.  Asynchronous on `stream`; all zeros in the other
+ * modes. */
+int mw_get_reset_pending(mw_engine *e, uint8_t *d_out, void *stream);
 
 /* Diagnostic (synchronises `stream`): how many triangles the last frame's display list held per env after clipping and culling —
  * what max_visible has to pay for (6 records per unit), and what decides which raster kernel an env's frame takes.

@@ -183,6 +183,9 @@ struct MwArgs {
     const MwArgs *gen_live; // device copies of this struct for the generators (live state / spare state): they index
     const MwArgs *gen_spare;//   it dynamically, which a by-value kernarg would turn into a scratch copy
     int32_t *pending_remove; // [N] entity slot that leaves the list after this step's frame (-1 none): written by K1, applied by the geometry kernel
+    // MW_AUTORESET_NEXT_STEP: 1 = the env's episode ended with the last step, whose frame showed its terminal state; the env's next
+    // step ignores its action and installs the next world instead (K1).  Cleared by that step, mw_reset and mw_set_state.
+    uint8_t *reset_pending;  // [N]
     // big scenes: what the geometry kernel's culling derives from a world's polygons alone (mw_geom.hip), kept from frame to
     // frame.  occ_valid[set]: polygon count + 1 of the world the cache belongs to, 0 after anything rewrote the polygons.
     int32_t *occ_valid;     // [sets] or null

@@ -860,6 +860,8 @@ int mw_create(const mw_config *cfg, mw_engine **out)
     if (cfg->num_envs <= 0 || cfg->max_ents < 0 || cfg->max_polys <= 0 || cfg->max_segs <= 0 || cfg->max_visible <= 0)
         return fail(nullptr, MW_E_INVALID, "bad capacities");
     if (cfg->rng_mode != MW_RNG_PHILOX && cfg->rng_mode != MW_RNG_PCG64) return fail(nullptr, MW_E_INVALID, "unknown rng_mode %d", cfg->rng_mode);
+    if (cfg->autoreset != MW_AUTORESET_OFF && cfg->autoreset != MW_AUTORESET_SAME_STEP && cfg->autoreset != MW_AUTORESET_NEXT_STEP)
+        return fail(nullptr, MW_E_INVALID, "unknown autoreset mode %d", cfg->autoreset);
     if (cfg->rng_mode == MW_RNG_PCG64 && cfg->generator == MW_GEN_NONE)
         return fail(nullptr, MW_E_INVALID, "MW_RNG_PCG64 (the reference's own numpy stream) needs a device generator");
     if (cfg->max_ents > 64) return fail(nullptr, MW_E_CAPACITY, "max_ents > 64 (one entity slot per lane of the env's wavefront)");
@@ -972,6 +974,7 @@ int mw_create(const mw_config *cfg, mw_engine **out)
         ALLOC(a.occ_cache, (size_t)e->n_sets * MW_OCC_CACHE_STRIDE(cfg->max_polys));
     }
     ALLOC(a.pending_remove, (size_t)N);
+    ALLOC(a.reset_pending, (size_t)N);      // (zeroed: nothing pending)
     if (rc == MW_OK) (void)hipMemset(a.pending_remove, 0xFF, 4 * (size_t)N);
     ALLOC(a.nvis, N); ALLOC(a.envhdr, (size_t)MW_ENVHDR * N); ALLOC(a.status, 1);
     ALLOC(e->d_reward_scratch, N); ALLOC(e->d_flag_scratch, 2 * (size_t)N); ALLOC(e->d_action_scratch, N);
@@ -1299,7 +1302,12 @@ int mw_set_state(mw_engine *e, int32_t first_env, int32_t count, const mw_state_
 {
     if (!e) return MW_E_INVALID;
     ON_DEVICE_SYNC(e);
-    return state_xfer(e, first_env, count, host, true);
+    const int rc = state_xfer(e, first_env, count, host, true);
+    if (rc != MW_OK) return rc;
+    // a world written from the host replaces whatever a pending next-step auto-reset would have installed
+    HIP_TRY(e, hipMemset(e->args.reset_pending + first_env, 0, (size_t)count));
+    HIP_TRY(e, hipDeviceSynchronize());     // (a null-stream memset: the caller's stream is not ordered against it)
+    return MW_OK;
 }
 
 int mw_get_state(mw_engine *e, int32_t first_env, int32_t count, mw_state_view *host)
@@ -1589,6 +1597,15 @@ int mw_get_final_info(mw_engine *e, int32_t *d_health, double *d_goal_pos, void 
     hipLaunchKernelGGL(mw_info_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, 1, (const int32_t *)e->args.final_health,
                        (const double *)e->args.final_goal, 0, d_health, d_goal_pos);
     HIP_TRY(e, hipGetLastError());
+    return MW_OK;
+}
+
+int mw_get_reset_pending(mw_engine *e, uint8_t *d_out, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (!d_out) return fail(e, MW_E_INVALID, "mw_get_reset_pending: d_out is null");
+    ON_DEVICE(e);
+    HIP_TRY(e, hipMemcpyAsync(d_out, e->args.reset_pending, (size_t)e->cfg.num_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MW_OK;
 }
 

@@ -13,7 +13,10 @@ extern "C" __global__ __launch_bounds__(64) void MW_RESET_KERNEL_NAME(MwArgs a, 
     if (env >= a.N) return;
     if (!force_all && !mask[env]) return;
     mw::generate_world(*a.gen_live, env, wave_per_env ? ws[0] : ws[threadIdx.x], wave_per_env ? (int)threadIdx.x : 0);
-    if (mark_refill && (!wave_per_env || threadIdx.x == 0)) a.refill_mask[env] = 1u;      // spare mode: its spare is stale now
+    if (!wave_per_env || threadIdx.x == 0) {
+        if (mark_refill) a.refill_mask[env] = 1u;      // spare mode: its spare is stale now
+        a.reset_pending[env] = 0;       // the new world replaces a pending next-step auto-reset
+    }
 }
 
 #ifndef MW_REFILL_KERNEL_NAME
@@ -49,6 +52,6 @@ extern "C" __global__ __launch_bounds__(64) void mw_take_spare_kernel(MwArgs a, 
     if (env >= a.N) return;
     if (!force_all && !mask[env]) return;
     mw::take_spare(a, env, (int)threadIdx.x);
-    if (threadIdx.x == 0) a.refill_mask[env] = 1u;
+    if (threadIdx.x == 0) { a.refill_mask[env] = 1u; a.reset_pending[env] = 0; }
 }
 #endif

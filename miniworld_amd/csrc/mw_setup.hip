@@ -50,8 +50,11 @@ extern "C" __global__ __launch_bounds__(64 * MW_K1_WAVES) __attribute__((amdgpu_
     }
     int remove_slot = -1;
     int tm = 0, tr = 0;             // terminated / truncated, uniform over the wave
+    // next-step auto-reset: the env's last step ended its episode (and drew its terminal state); this step installs the
+    // next world instead of stepping — no action, no per-step draws (miniworld.py:677-680 are step()'s, not reset()'s)
+    const bool pend = do_step && a.autoreset == MW_AUTORESET_NEXT_STEP && a.reset_pending[env] != 0;
 
-    if (do_step) {
+    if (do_step && !pend) {
         int step_count = a.step[env] + 1;
         int picked = a.picked[env];
         // the three per-step parameters (miniworld.py:677-680)
@@ -157,8 +160,7 @@ extern "C" __global__ __launch_bounds__(64 * MW_K1_WAVES) __attribute__((amdgpu_
     }
 
     // ---- state write-back (agent + carried entity) ------------------------------
-    bool regenerated = false;
-    if (do_step && writer) {
+    if (do_step && !pend && writer) {
         a.ax[env] = c.px; a.ay[env] = c.py; a.az[env] = c.pz; a.adir[env] = c.dir;
         if (c.live >= 0) {
             a.epos[((size_t)0 * a.E + c.live) * a.N + env] = c.cpos[0];
@@ -167,40 +169,47 @@ extern "C" __global__ __launch_bounds__(64 * MW_K1_WAVES) __attribute__((amdgpu_
             a.edir[(size_t)c.live * a.N + env] = c.cdir;
         }
         a.carry[env] = remove_slot >= 0 ? -1 : c.carry;
-    }
-    if (do_step && a.autoreset == MW_AUTORESET_SAME_STEP && a.generator != MW_GEN_NONE) {
-        // same-step auto-reset: the observation returned with done=1 is the first one of the
-        // next episode (the reference leaves the reset to the caller, scripts/benchmark.py:36-37)
-        regenerated = (tm | tr) != 0;
-        if (regenerated) {
-            if (writer) mw::keep_final_info(a, env);
-            if (a.spare) {
-                // the next world was generated ahead (by a refill block of an earlier launch): claim it
-                if (writer) s_cnt[0][0] = (int)atomicCAS(a.refill_mask + env, 1u, 3u);
-                __syncthreads();
-                __threadfence();        // acquire: the spare's contents (written by another block, released with its state) are read behind the claim
-                const int old = s_cnt[0][0];
-                if (old == 1) {
-                    // the previous episode lasted one step and the refill has not run yet: generate in place
-                    if (wave == 0) mw::generate_world(*a.gen_live, env, gen_ws, lane);
-                } else {
-                    if (old == 2) {     // a refill block of this very launch is on it
-                        if (writer) while (__hip_atomic_load(a.refill_mask + env, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u) __builtin_amdgcn_s_sleep(16);
-                        __syncthreads();
-                    }
-                    if (wave == 0) mw::take_spare(a, env, lane);
-                }
-                __threadfence();
-                __syncthreads();
-                if (writer) atomicExch(a.refill_mask + env, 1u);        // the spare is missing again
-            } else if (wave == 0) {
-                mw::generate_world(*a.gen_live, env, gen_ws, lane);
-            }
-            __syncthreads();
-            c.px = a.ax[env]; c.py = a.ay[env]; c.pz = a.az[env]; c.dir = a.adir[env];
-            c.carry = -1; c.live = -1;
-            remove_slot = -1;
+        if ((tm | tr) && a.autoreset != MW_AUTORESET_OFF && a.generator != MW_GEN_NONE) {
+            mw::keep_final_info(a, env);
+            if (a.autoreset == MW_AUTORESET_NEXT_STEP) a.reset_pending[env] = 1;
         }
+    }
+    if (pend && writer) {
+        reward[env] = 0.0f;
+        term[env] = 0;
+        trunc[env] = 0;
+    }
+    // The one install site of the next world.  Same-step auto-reset: on the step that ends the episode, so that the observation
+    // returned with done = 1 is the first one of the next episode.  Next-step auto-reset: on the step after it, the reference's
+    // "step; if done: reset()" (scripts/benchmark.py:36-37) — the stream is consumed in that order.
+    if (a.generator != MW_GEN_NONE && (pend || (do_step && a.autoreset == MW_AUTORESET_SAME_STEP && (tm | tr) != 0))) {
+        if (a.spare) {
+            // the next world was generated ahead (by a refill block of an earlier launch): claim it
+            if (writer) s_cnt[0][0] = (int)atomicCAS(a.refill_mask + env, 1u, 3u);
+            __syncthreads();
+            __threadfence();        // acquire: the spare's contents (written by another block, released with its state) are read behind the claim
+            const int old = s_cnt[0][0];
+            if (old == 1) {
+                // the previous episode lasted one step and the refill has not run yet: generate in place
+                if (wave == 0) mw::generate_world(*a.gen_live, env, gen_ws, lane);
+            } else {
+                if (old == 2) {     // a refill block of this very launch is on it
+                    if (writer) while (__hip_atomic_load(a.refill_mask + env, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u) __builtin_amdgcn_s_sleep(16);
+                    __syncthreads();
+                }
+                if (wave == 0) mw::take_spare(a, env, lane);
+            }
+            __threadfence();
+            __syncthreads();
+            if (writer) atomicExch(a.refill_mask + env, 1u);        // the spare is missing again
+        } else if (wave == 0) {
+            mw::generate_world(*a.gen_live, env, gen_ws, lane);
+        }
+        __syncthreads();
+        c.px = a.ax[env]; c.py = a.ay[env]; c.pz = a.az[env]; c.dir = a.adir[env];
+        c.carry = -1; c.live = -1;
+        remove_slot = -1;
+        if (pend && writer) a.reset_pending[env] = 0;
     }
 
     // The frame's vertex half — camera, lighting, transform, clipping, triangle setup under the pinned GL rules — is

@@ -23,8 +23,10 @@ __device__ inline void dense_step(const MwArgs &a, int do_step, int env, int lan
     }
     int remove_slot = -1;
     int tm = 0, tr = 0;
+    // next-step auto-reset: this step installs the next world instead of stepping (see mw_setup.hip)
+    const bool pend = do_step && a.autoreset == MW_AUTORESET_NEXT_STEP && a.reset_pending[env] != 0;
 
-    if (do_step) {
+    if (do_step && !pend) {
         const int step_count = a.step[env] + 1;
         int picked = a.picked[env];
         // the three per-step parameters (miniworld.py:677-680)
@@ -126,38 +128,46 @@ __device__ inline void dense_step(const MwArgs &a, int do_step, int env, int lan
                 a.edir[(size_t)c.live * a.N + env] = c.cdir;
             }
             a.carry[env] = remove_slot >= 0 ? -1 : c.carry;
-        }
-        if (a.autoreset == MW_AUTORESET_SAME_STEP && a.generator != MW_GEN_NONE && (tm | tr)) {
-            // same-step auto-reset: the observation returned with done = 1 is the first one of the next episode.
-            // The env's leading lane installs the next world (several envs of the wave may do so side by side); the
-            // env's other lanes then read it like the leader does.
-            if (leader) {
+            if ((tm | tr) && a.autoreset != MW_AUTORESET_OFF && a.generator != MW_GEN_NONE) {
                 mw::keep_final_info(a, env);
-                if (a.spare) {
-                    // spare mode: the next world was generated ahead by a refill block of an earlier launch (the
-                    // blocks behind the env blocks of this grid): claim it.  States of refill_mask: mw_device.h.
-                    const unsigned old = atomicCAS(a.refill_mask + env, 1u, 3u);
-                    __threadfence();        // acquire: the spare's contents are read behind the claim
-                    if (old == 1u) {
-                        // the previous episode lasted one step and the refill has not run yet: generate in place
-                        mw::generate_world(*a.gen_live, env, gen_ws, 0);
-                    } else {
-                        if (old == 2u)      // a refill block of this very launch is on it
-                            while (__hip_atomic_load(a.refill_mask + env, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u) __builtin_amdgcn_s_sleep(16);
-                        mw::take_spare_lane(a, env);
-                    }
-                    __threadfence();
-                    atomicExch(a.refill_mask + env, 1u);        // the spare is missing again
-                } else {
-                    mw::generate_world(*a.gen_live, env, gen_ws, 0);
-                }
+                if (a.autoreset == MW_AUTORESET_NEXT_STEP) a.reset_pending[env] = 1;
             }
-            __threadfence();
-            __builtin_amdgcn_wave_barrier();
-            c.px = a.ax[env]; c.py = a.ay[env]; c.pz = a.az[env]; c.dir = a.adir[env];
-            c.carry = -1; c.live = -1;
-            remove_slot = -1;
         }
+    } else if (pend && leader) {
+        reward[env] = 0.0f;
+        term[env] = 0;
+        trunc[env] = 0;
+    }
+    // The one install site of the next world (see mw_setup.hip): same-step auto-reset on the step that ends the episode, next-step
+    // auto-reset on the step after it.  The env's leading lane installs it (several envs of the wave may do so side by side); the
+    // env's other lanes then read it like the leader does.
+    if (a.generator != MW_GEN_NONE && (pend || (do_step && a.autoreset == MW_AUTORESET_SAME_STEP && (tm | tr)))) {
+        if (leader) {
+            if (a.spare) {
+                // spare mode: the next world was generated ahead by a refill block of an earlier launch (the
+                // blocks behind the env blocks of this grid): claim it.  States of refill_mask: mw_device.h.
+                const unsigned old = atomicCAS(a.refill_mask + env, 1u, 3u);
+                __threadfence();        // acquire: the spare's contents are read behind the claim
+                if (old == 1u) {
+                    // the previous episode lasted one step and the refill has not run yet: generate in place
+                    mw::generate_world(*a.gen_live, env, gen_ws, 0);
+                } else {
+                    if (old == 2u)      // a refill block of this very launch is on it
+                        while (__hip_atomic_load(a.refill_mask + env, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u) __builtin_amdgcn_s_sleep(16);
+                    mw::take_spare_lane(a, env);
+                }
+                __threadfence();
+                atomicExch(a.refill_mask + env, 1u);        // the spare is missing again
+            } else {
+                mw::generate_world(*a.gen_live, env, gen_ws, 0);
+            }
+        }
+        __threadfence();
+        __builtin_amdgcn_wave_barrier();
+        c.px = a.ax[env]; c.py = a.ay[env]; c.pz = a.az[env]; c.dir = a.adir[env];
+        c.carry = -1; c.live = -1;
+        remove_slot = -1;
+        if (pend && leader) a.reset_pending[env] = 0;
     }
 
     // the frame's vertex half is mw_geom_kernel's (mw_geom.hip); see mw_setup.hip

@@ -26,7 +26,7 @@ TASK_NONE, TASK_GOTO, TASK_PICKUP, TASK_PUTNEXT, TASK_SIDEWALK, TASK_SIGN, TASK_
 GEN_NONE, GEN_HALLWAY, GEN_ONEROOM, GEN_PICKUP, GEN_MAZE, GEN_PROGRAM = 0, 1, 2, 3, 4, 5
 OP_COIN, OP_DRAW_DIR, OP_PLACE, OP_FIXED, OP_BOX_SIZE, OP_COLOR, OP_APPEND = 1, 2, 3, 4, 5, 6, 7
 PROG_MAX_ROOMS, PROG_MAX_TEX, PROG_MAX_OPS, PROG_MAX_ENTS = 16, 8, 48, 64
-AUTORESET_OFF, AUTORESET_SAME_STEP = 0, 1
+AUTORESET_OFF, AUTORESET_SAME_STEP, AUTORESET_NEXT_STEP = 0, 1, 2
 OBS_HWC_U8, OBS_CWH_U8, OBS_GREY_F64 = 0, 1, 2
 RNG_PHILOX, RNG_PCG64 = 0, 1
 PATH_TILE, PATH_QUAD, PATH_QUAD_MESH, PATH_GENERIC = 0, 1, 2, 3
@@ -34,7 +34,7 @@ PATH_TILE, PATH_QUAD, PATH_QUAD_MESH, PATH_GENERIC = 0, 1, 2, 3
 EXPORTS = [
     "mw_create", "mw_destroy", "mw_last_error", "mw_upload_texture", "mw_upload_mesh",
     "mw_set_geometry", "mw_get_geometry", "mw_set_state", "mw_get_state", "mw_set_step_params", "mw_reset",
-    "mw_step", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
+    "mw_step", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
     "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
 ]
 
@@ -189,6 +189,7 @@ def load_library():
     L.mw_raster_path.argtypes = [vp]
     L.mw_get_info.argtypes = [vp, vp, vp, i32, vp]
     L.mw_get_final_info.argtypes = [vp, vp, vp, vp]
+    L.mw_get_reset_pending.argtypes = [vp, vp, vp]
     L.mw_get_list_lengths.argtypes = [vp, i32, i32, vp, vp]
     L.mw_debug_set_mesh_frame_seq.argtypes = [vp, C.c_uint32]
     L.mw_debug_get_slow_heads.argtypes = [vp, vp, vp]
@@ -409,6 +410,16 @@ class Engine:
                 assert t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()
         self._check(self.lib.mw_get_final_info(self.h, health.data_ptr() if health is not None else None,
                                                goal_pos.data_ptr() if goal_pos is not None else None, _stream_ptr(self.device)), "mw_get_final_info")
+
+    def get_reset_pending(self, out=None):
+        """uint8[N] on the device: 1 = the env's last step ended its episode and, under AUTORESET_NEXT_STEP, its next step installs
+        the next world instead of stepping (the action is ignored; reward 0, flags 0).  Written into `out` when given."""
+        import torch
+        if out is None:
+            out = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (self.N,) and out.is_contiguous()
+        self._check(self.lib.mw_get_reset_pending(self.h, out.data_ptr(), _stream_ptr(self.device)), "mw_get_reset_pending")
+        return out
 
     def list_lengths(self):
         """int32[N]: triangles in each env's display list of the last frame (after clipping and culling)."""

@@ -18,9 +18,9 @@ try:  # pragma: no cover - depends on the environment
     VectorEnvBase = gym.vector.VectorEnv                # miniworld_amd.vector.MiniWorldVectorEnv is one when gymnasium is there
     try:                                                # gymnasium >= 1.1: an enum; before: the plain string
         from gymnasium.vector import AutoresetMode
-        AUTORESET_SAME_STEP = AutoresetMode.SAME_STEP
+        AUTORESET_SAME_STEP, AUTORESET_NEXT_STEP = AutoresetMode.SAME_STEP, AutoresetMode.NEXT_STEP
     except ImportError:
-        AUTORESET_SAME_STEP = "same-step"
+        AUTORESET_SAME_STEP, AUTORESET_NEXT_STEP = "same-step", "next-step"
 
     def batch_action_space(single, n):
         from gymnasium.vector.utils import batch_space
@@ -28,7 +28,7 @@ try:  # pragma: no cover - depends on the environment
 except Exception:  # noqa: BLE001
     HAVE_GYMNASIUM = False
     VectorEnvBase = object
-    AUTORESET_SAME_STEP = "same-step"
+    AUTORESET_SAME_STEP, AUTORESET_NEXT_STEP = "same-step", "next-step"
 
     def batch_action_space(single, n):
         return Box(single.start, single.start + single.n - 1, (n,), dtype=np.int64)

@@ -3,9 +3,11 @@
 This is the performance path: world state lives on the device as Structure-of-Arrays, one
 ``step()`` is three kernel launches (step, geometry, raster; two more with mesh entities) that write the
 ``uint8[N,60,80,3]`` observation tensor (and optionally ``float32[N,60,80,1]`` depth) straight into torch memory.
-Episodes auto-reset on the device (same-step semantics: the observation returned together
-with ``terminated|truncated`` is the first one of the next episode; the reference leaves the
-reset to the caller, scripts/benchmark.py:36-37).
+Episodes auto-reset on the device.  ``autoreset=True`` / ``"same_step"`` (the default): the observation returned together
+with ``terminated|truncated`` is the first one of the next episode.  ``autoreset="next_step"``: the step that ends an
+episode returns its terminal frame, reward and flags, and the env's next step ignores its action and returns the next
+episode's first frame with reward 0 and no flags — the reference's own "step; if done: reset()" (it leaves the reset to the
+caller, scripts/benchmark.py:36-37), on the same random stream.  ``autoreset=False``: the caller resets.
 
 All 23 env ids are generated, ruled and auto-reset on the device, on the reference's own numpy PCG64 stream: Hallway,
 OneRoom*, Maze* and PickupObjects through their own generators, the fixed-floorplan families through placement programs
@@ -54,7 +56,7 @@ _KIND = {
 
 class MiniWorldVecEnv:
     def __init__(self, env_id: str, num_envs: int, device_id: int = 0, domain_rand: bool = False,
-                 want_depth: bool = False, seed: int = 0, autoreset: bool = True, obs_layout: str = "hwc",
+                 want_depth: bool = False, seed: int = 0, autoreset: bool | str = True, obs_layout: str = "hwc",
                  rng: str = "auto", msaa: int = 8, **env_kwargs):
         """obs_layout: "hwc" uint8[N,H,W,3] (the env's observation), "cwh" uint8[N,3,W,H]
         (PyTorchObsWrapper, wrappers.py:24) or "grey" float64[N,H,W,1] (GreyscaleWrapper, wrappers.py:44):
@@ -64,9 +66,15 @@ class MiniWorldVecEnv:
         rng: stream of the device-side resets. "pcg64" = numpy's own Generator(PCG64(SeedSequence(seed + i))) drawn in
         the reference's call order, so that env i IS the reference's env.reset(seed=seed + i) and its later episodes
         continue like env.reset(), per-step domain-randomisation draws included (every device generator);
-        "philox" = the engine's counter-based stream; "auto" = pcg64 where implemented."""
+        "philox" = the engine's counter-based stream; "auto" = pcg64 where implemented.
+        autoreset: True or "same_step", "next_step", False (see the module's docstring); the mode is `autoreset_mode`
+        ("same_step", "next_step" or "off")."""
         import torch
         self.torch = torch
+        modes = {True: "same_step", False: "off", "same_step": "same_step", "next_step": "next_step"}
+        if not isinstance(autoreset, (bool, str)) or autoreset not in modes:
+            raise ValueError(f"autoreset must be True, False, 'same_step' or 'next_step', not {autoreset!r}")
+        self.autoreset_mode = modes[autoreset]
         if obs_layout not in ("hwc", "cwh", "grey"):
             raise ValueError(f"obs_layout must be 'hwc', 'cwh' or 'grey', not {obs_layout!r}")
         self.obs_layout = obs_layout
@@ -120,8 +128,8 @@ class MiniWorldVecEnv:
         cfg.max_episode_steps = int(min(float(self.template.max_episode_steps), 2 ** 30))
         cfg.domain_rand = int(domain_rand)
         cfg.generator = generator
-        cfg.autoreset = eng.AUTORESET_SAME_STEP if autoreset else eng.AUTORESET_OFF
-        self.autoreset = bool(autoreset)
+        cfg.autoreset = {"same_step": eng.AUTORESET_SAME_STEP, "next_step": eng.AUTORESET_NEXT_STEP, "off": eng.AUTORESET_OFF}[self.autoreset_mode]
+        self.autoreset = self.autoreset_mode != "off"
         cfg.agent_radius = float(self.template.agent.radius)
         if generator in (eng.GEN_HALLWAY, eng.GEN_ONEROOM):
             room = self.template.rooms[0]
@@ -283,8 +291,8 @@ class MiniWorldVecEnv:
         """The batched `info` of the last step as device tensors: {"health": int32[N]} for CollectHealth (collecthealth.py:100),
         {"goal_pos": float64[N, 3]} for TMaze / YMaze (the box's position, tmaze.py:89, ymaze.py:125), {} for the other envs
         (miniworld.py:730 returns an empty dict).  One small gather kernel on the engine's stream; the values are those of the
-        state the device holds (with the same-step auto-reset an env that just finished reports its new episode; the finished
-        episode's own values: final_infos)."""
+        state the device holds (with the same-step auto-reset an env that just finished reports its new episode — the finished
+        episode's own values: final_infos —; with the next-step auto-reset it reports the finished one)."""
         if self._info_kind is None:
             return {}
         torch = self.torch
@@ -314,6 +322,12 @@ class MiniWorldVecEnv:
         else:
             self.engine.get_final_info(goal_pos=self._final_info_buf)
         return {self._info_kind: self._final_info_buf}
+
+    def reset_pending(self):
+        """uint8[N] device tensor: 1 = the env's last step ended its episode and its next step (autoreset="next_step") installs
+        the next world instead of stepping — its action is ignored and its transition is no transition of the env (mask it out
+        of a replay buffer).  All zeros in the other modes."""
+        return self.engine.get_reset_pending()
 
     def render_top_view(self, render_agent=True):
         """uint8[N,H,W,3] map views (render_top_view, miniworld.py:1088-1175) of every env."""

@@ -5,8 +5,8 @@
     obs, rewards, terminations, truncations, infos = envs.step(actions)
 
 follows gymnasium.vector.VectorEnv's calling convention (num_envs, single_* / batched spaces,
-reset -> (obs, infos), step -> 5-tuple, autoreset mode "same-step": the observation returned with
-a finished episode is the first one of the next episode).  Observations, rewards and flags stay
+reset -> (obs, infos), step -> 5-tuple, autoreset mode "same-step" by default: the observation returned with
+a finished episode is the first one of the next episode; or "next-step", below).  Observations, rewards and flags stay
 torch tensors on the engine's GPU by default (`to_numpy=True` copies them to the host like a
 classic VectorEnv); actions may be a torch tensor, a numpy array or a list.
 
@@ -17,12 +17,19 @@ from final_obs on truncation must take the returned observation's predecessor in
 (bool[N], for every env family, also those without info keys) and — for the families that have info keys
 (CollectHealth's health, TMaze / YMaze's goal_pos) — info["final_info"], the finished episodes' own values.  The arrays
 under final_info are copies: they stay valid after the next step.
+
+**`autoreset_mode="next-step"` gives the terminal observation** (gymnasium's AutoresetMode.NEXT_STEP, its default for vector envs
+since 1.0; `metadata["autoreset_mode"]` of the instance says so): the step that ends an episode returns that episode's last frame,
+reward, flags and info (CollectHealth's final health, TMaze / YMaze's goal_pos of that episode) — no "final_obs" / "final_info"
+keys are needed and none are emitted —, and the env's next step ignores its action and returns the next episode's first frame
+with reward 0 and both flags False.  `self.vec.reset_pending()` marks the envs whose next step is such a reset step.  Still one
+frame per env and step, drawn in the same kernels; the worlds follow the reference's "step; if done: reset()" stream order.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .gymshim import AUTORESET_SAME_STEP, VectorEnvBase, batch_action_space, spaces
+from .gymshim import AUTORESET_NEXT_STEP, AUTORESET_SAME_STEP, VectorEnvBase, batch_action_space, spaces
 from .vec_env import MiniWorldVecEnv
 
 
@@ -30,7 +37,17 @@ class MiniWorldVectorEnv(VectorEnvBase):
     """A gymnasium.vector.VectorEnv when gymnasium is importable (a plain class with the same surface otherwise)."""
     metadata = {"autoreset_mode": AUTORESET_SAME_STEP, "render_modes": ["rgb_array"]}
 
-    def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, **kwargs):
+    def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", **kwargs):
+        """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
+        are accepted too."""
+        mode = str(getattr(autoreset_mode, "name", autoreset_mode)).lower().replace("_", "-")     # (an AutoresetMode: its name)
+        if mode not in ("same-step", "next-step"):
+            raise ValueError(f"autoreset_mode must be 'same-step' or 'next-step', not {autoreset_mode!r}")
+        if mode == "next-step":
+            if kwargs.get("autoreset", True) is not True:
+                raise ValueError("autoreset_mode='next-step' and autoreset= exclude each other")
+            kwargs["autoreset"] = "next_step"
+            self.metadata = dict(type(self).metadata, autoreset_mode=AUTORESET_NEXT_STEP)
         self.vec = MiniWorldVecEnv(env_id, num_envs, **kwargs)
         self.num_envs = num_envs
         self.to_numpy = to_numpy
@@ -61,7 +78,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
         actions = actions.to(device=self.vec.engine.device, dtype=torch.int32)
         obs, rew, term, trunc = self.vec.step(actions)
         info = self._infos()
-        if self.vec.autoreset:
+        if self.vec.autoreset_mode == "same_step":
             # gymnasium's same-step convention: "_final_info" masks the envs whose episode ended with this step (every family); the
             # finished episodes' own info under "final_info" where the family has info keys — clones, the engine's buffers are
             # rewritten by the next step.  (No "final_obs": see the module's docstring.)

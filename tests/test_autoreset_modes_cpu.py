@@ -1,0 +1,56 @@
+"""The next-step auto-reset's host side, without a GPU: the C enum and the Python constants agree, mw_create rejects an unknown
+mode, and the Python layers validate the mode before anything touches the device."""
+import ctypes
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_header_enum_matches_the_python_constants():
+    from miniworld_amd import engine
+    header = open(os.path.join(ROOT, "include", "mwengine.h")).read()
+    enum = re.search(r"enum\s*\{\s*(MW_AUTORESET_OFF[^}]*)\}", header).group(1)
+    values = {k: int(v) for k, v in re.findall(r"(MW_AUTORESET_\w+)\s*=\s*(\d+)", enum)}
+    assert values == {"MW_AUTORESET_OFF": engine.AUTORESET_OFF, "MW_AUTORESET_SAME_STEP": engine.AUTORESET_SAME_STEP,
+                      "MW_AUTORESET_NEXT_STEP": engine.AUTORESET_NEXT_STEP}
+    assert engine.AUTORESET_NEXT_STEP == 2 and engine.ABI_VERSION == 4
+    assert "mw_get_reset_pending" in engine.EXPORTS
+    assert re.search(r"int mw_get_reset_pending\(mw_engine \*e, uint8_t \*d_out, void \*stream\);", header)
+
+
+def test_create_rejects_an_unknown_autoreset_mode():
+    """mw_create checks the mode before it looks for a device: MW_E_INVALID here too."""
+    from miniworld_amd import engine
+    from miniworld_amd.scene import base_config
+    engine.build_library()
+    lib = engine.load_library()
+    for mode in (3, -1):
+        cfg = base_config(4, 80, 60, 1, 6, 4, 16)
+        cfg.abi_version = engine.ABI_VERSION
+        cfg.autoreset = mode
+        h = ctypes.c_void_p()
+        assert lib.mw_create(ctypes.byref(cfg), ctypes.byref(h)) == -1 and not h.value, mode
+        assert b"autoreset" in lib.mw_last_error(None), mode
+
+
+def test_gymshim_has_both_modes():
+    from miniworld_amd import gymshim
+    norm = lambda m: str(getattr(m, "name", m)).lower().replace("_", "-")        # noqa: E731
+    assert norm(gymshim.AUTORESET_SAME_STEP) == "same-step" and norm(gymshim.AUTORESET_NEXT_STEP) == "next-step"
+
+
+@pytest.mark.parametrize("bad", ["next-step", "same-step", "off", 2, None])
+def test_vec_env_rejects_unknown_modes_before_touching_the_device(bad):
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    with pytest.raises(ValueError, match="autoreset"):
+        MiniWorldVecEnv("MiniWorld-Hallway-v0", 2, autoreset=bad)
+
+
+@pytest.mark.parametrize("bad", ["next_steps", "disabled", 1])
+def test_vector_env_rejects_unknown_modes(bad):
+    from miniworld_amd.vector import MiniWorldVectorEnv
+    with pytest.raises(ValueError, match="autoreset_mode"):
+        MiniWorldVectorEnv("MiniWorld-Hallway-v0", 2, autoreset_mode=bad)
