@@ -306,6 +306,17 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
  * step see the terminal state. */
 int mw_step(mw_engine *e, const int32_t *d_actions, uint8_t *d_obs, float *d_depth,
             float *d_reward, uint8_t *d_term, uint8_t *d_trunc, void *stream);
+/* Final observations of a MW_AUTORESET_SAME_STEP engine (Gymnasium's info["final_obs"] of a same-step vector env, SB3's
+ * info["terminal_observation"]): d_final_obs and d_final_depth are device buffers shaped like mw_step's d_obs / d_depth (N rows in
+ * the layout of mw_set_obs_layout at the time of the step).  With d_final_obs non-null, every later mw_step writes the TERMINAL
+ * frame of each env whose episode ended in that step (term | trunc) into that env's row of d_final_obs — and its depth into
+ * d_final_depth when both the step's d_depth and d_final_depth are non-null.  The rows of the other envs are not written.
+ * Everything else the step returns is what same-step returns without it: d_obs (the next episode's first frame), reward, flags,
+ * mw_get_state, mw_get_info, mw_get_final_info; mw_get_reset_pending stays all zeros.  Still asynchronous and without host
+ * synchronisation: the step draws every env, then the finished ones once more (their new worlds).  NULL turns it off again.
+ * MW_E_INVALID on MW_AUTORESET_OFF / MW_AUTORESET_NEXT_STEP engines and on MW_GEN_NONE engines (nothing is auto-reset there: the
+ * frame mw_step returns is the terminal one). */
+int mw_set_final_obs(mw_engine *e, uint8_t *d_final_obs, float *d_final_depth);
 /* Layout of the d_obs buffer written by mw_step / mw_render / mw_render_top — the reference's
  * observation wrappers (wrappers.py) folded into the raster kernel's store:
  *   MW_OBS_HWC_U8   uint8 [N][H][W][3]   the env's own observation (default)

@@ -31,13 +31,19 @@ extern "C" __global__ void mw_geom_kernel(MwArgs a, int view_flags, int S, int L
 extern "C" __global__ void mw_geom_any_kernel(MwArgs a, int view_flags, int S, int L, int n_env);
 extern "C" __global__ void mw_geom_big_kernel(MwArgs a, int view_flags, int S, int L, int n_env);
 extern "C" __global__ void mw_geom_big_any_kernel(MwArgs a, int view_flags, int S, int L, int n_env);
+extern "C" __global__ void mw_geom_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list);
+extern "C" __global__ void mw_geom_big_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list);
+extern "C" __global__ void mw_geom_any_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list);
+extern "C" __global__ void mw_geom_big_any_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list);
 #define MW_RASTER_DECL(name) \
     extern "C" __global__ void name(int N, int W, int H, int max_vis, int tiles_x, int n_tiles, int waves_per_env, int tiles_per_wave, \
                                     const float *rec_raster, const float *rec_shade, const float *rec_cull, const int32_t *nvis, \
                                     const float *envhdr, const MwTexDesc *texd, const uint32_t *texels, uint8_t *obs, float *depth, int dbg, \
                                     int texel_bytes, const uint16_t *rec_order, const float *mesh_pos, const float *mesh_nrm, \
                                     const float *mesh_rgb, const float *mesh_uv, uint32_t *mesh_keys, const float *plane_cache, int plane_cap, \
-                                    const float4 *slow_frags, const uint32_t *slow_head, const uint32_t *tile_list, int32_t *tile_n, int tile_list_cap, int n_xcc)
+                                    const float4 *slow_frags, const uint32_t *slow_head, const uint32_t *tile_list, int32_t *tile_n, int tile_list_cap, int n_xcc \
+                                    MW_RASTER_DECL_TAIL)
+#define MW_RASTER_DECL_TAIL
 MW_RASTER_DECL(mw_raster_kernel);
 MW_RASTER_DECL(mw_raster_depth_kernel);
 MW_RASTER_DECL(mw_raster_big_kernel);
@@ -50,12 +56,33 @@ MW_RASTER_DECL(mw_raster_nomesh_depth_kernel);
 MW_RASTER_DECL(mw_raster_mesh_depth_kernel);
 MW_RASTER_DECL(mw_raster_mesh_wrap_kernel);
 MW_RASTER_DECL(mw_raster_big_mesh_wrap_kernel);
+// ... the same over the envs of a list (mw_raster.hip: MW_RASTER_SUB)
+#undef MW_RASTER_DECL_TAIL
+#define MW_RASTER_DECL_TAIL , const int32_t *list
+MW_RASTER_DECL(mw_raster_sub_kernel);
+MW_RASTER_DECL(mw_raster_depth_sub_kernel);
+MW_RASTER_DECL(mw_raster_big_sub_kernel);
+MW_RASTER_DECL(mw_raster_big_depth_sub_kernel);
+MW_RASTER_DECL(mw_raster_wrap_sub_kernel);
+MW_RASTER_DECL(mw_raster_big_wrap_sub_kernel);
+MW_RASTER_DECL(mw_raster_mesh_sub_kernel);
+MW_RASTER_DECL(mw_raster_nomesh_sub_kernel);
+MW_RASTER_DECL(mw_raster_nomesh_depth_sub_kernel);
+MW_RASTER_DECL(mw_raster_mesh_depth_sub_kernel);
+MW_RASTER_DECL(mw_raster_mesh_wrap_sub_kernel);
+MW_RASTER_DECL(mw_raster_big_mesh_wrap_sub_kernel);
 #define MW_RASTERQ_DECL(name) \
     extern "C" __global__ void name(int N, int W, int H, int max_vis, int tiles_x, int n_tiles, const float *rec_raster, const float *rec_shade, \
                                     const float *rec_cull, const int32_t *nvis, const float *envhdr, const uint32_t *texels, uint8_t *obs, \
-                                    float *depth, int dbg, int texel_bytes, unsigned long long *prof)
+                                    float *depth, int dbg, int texel_bytes, unsigned long long *prof MW_RASTER_DECL_TAIL)
+#undef MW_RASTER_DECL_TAIL
+#define MW_RASTER_DECL_TAIL
 MW_RASTERQ_DECL(mw_rasterq_kernel);
 MW_RASTERQ_DECL(mw_rasterq4_kernel);
+#undef MW_RASTER_DECL_TAIL
+#define MW_RASTER_DECL_TAIL , const int32_t *list
+MW_RASTERQ_DECL(mw_rasterq_sub_kernel);
+MW_RASTERQ_DECL(mw_rasterq4_sub_kernel);
 extern "C" int mw_rasterq_lds_bytes(int S, int W, int H, int n_tiles, int depth);
 extern "C" int mw_rasterq_cap(int depth);
 #define MW_RASTERQ_THREADS 512
@@ -74,11 +101,20 @@ extern "C" __global__ void mw_collect_respawn_kernel(MwArgs a);
 extern "C" __global__ void mw_collect_respawn_pcg_kernel(MwArgs a);
 extern "C" __global__ void mw_take_spare_kernel(MwArgs a, const uint8_t *mask, int force_all);
 extern "C" __global__ void mw_view_mesh_kernel(int W, int H, int S, int first_env, const float *envhdr, const float *mesh_pos, uint32_t *keys);
-extern "C" __global__ void mw_view_raster_kernel(int env, int W, int H, int S, int max_vis, int tiles_x, const float *rec_raster,
-                                                 const float *rec_shade, const float *rec_cull, const int32_t *nvis, const float *envhdr,
-                                                 const MwTexDesc *texd, const uint32_t *texels, const float *mesh_pos,
-                                                 const float *mesh_nrm, const float *mesh_rgb, const float *mesh_uv, const uint32_t *mesh_keys,
-                                                 uint8_t *out, float *depth, int texel_bytes);
+extern "C" __global__ void mw_view_mesh_sub_kernel(int W, int H, int S, int first_env, const float *envhdr, const float *mesh_pos, uint32_t *keys,
+                                                   const int32_t *list);
+#define MW_VIEW_RASTER_DECL(name) \
+    extern "C" __global__ void name(int env, int W, int H, int S, int max_vis, int tiles_x, const float *rec_raster, \
+                                    const float *rec_shade, const float *rec_cull, const int32_t *nvis, const float *envhdr, \
+                                    const MwTexDesc *texd, const uint32_t *texels, const float *mesh_pos, \
+                                    const float *mesh_nrm, const float *mesh_rgb, const float *mesh_uv, const uint32_t *mesh_keys, \
+                                    uint8_t *out, float *depth, int texel_bytes MW_RASTER_DECL_TAIL)
+MW_VIEW_RASTER_DECL(mw_view_raster_sub_kernel);
+#undef MW_RASTER_DECL_TAIL
+#define MW_RASTER_DECL_TAIL
+MW_VIEW_RASTER_DECL(mw_view_raster_kernel);
+extern "C" __global__ void mw_final_install_kernel(MwArgs a, const int32_t *list);
+extern "C" __global__ void mw_final_install_pcg_kernel(MwArgs a, const int32_t *list);
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *rec_raster, const float *rec_cull,
                                              const int32_t *nvis, uint8_t *vis);
 
@@ -92,6 +128,58 @@ extern "C" __global__ void mw_info_kernel(int N, int E, const int32_t *health, c
     if (out_health) out_health[i] = health[i];
     if (out_pos)
         for (int c = 0; c < 3; ++c) out_pos[(size_t)i * 3 + c] = epos[((size_t)c * E + slot) * N + i];
+}
+
+// Same-step auto-reset with final observations (mw_set_final_obs), behind the first pass's step kernel: the envs whose episode
+// ended with this step — reset_pending, set by the step kernel run as the next-step mode's terminal step — in ascending order, as
+// list[0] = count, list[1 + i] = env.  One workgroup, ballot compaction, deterministic.  The finished worlds' pending removals go:
+// the same-step install drops them (a picked object's world is replaced; CollectHealth's consumed kit does not respawn).
+extern "C" __global__ __launch_bounds__(1024) void mw_final_list_kernel(int N, const uint8_t *__restrict__ pending, int32_t *__restrict__ pending_remove,
+                                                                       int32_t *__restrict__ list)
+{
+    __shared__ int s_wave[16];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < N; i0 += 1024) {
+        const int i = i0 + tid;
+        const bool p = i < N && pending[i] != 0;
+        const unsigned long long m = __ballot(p);
+        if (lane == 0) s_wave[wave] = __popcll(m);
+        __syncthreads();
+        int before = base, total = 0;
+        for (int w = 0; w < 16; ++w) {
+            const int c = s_wave[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        if (p) {
+            list[1 + before + __popcll(m & ((1ull << lane) - 1ull))] = i;
+            pending_remove[i] = -1;
+        }
+        base += total;
+        __syncthreads();        // (s_wave is rewritten by the next round)
+    }
+    if (tid == 0) list[0] = base;
+}
+
+// ... behind the first pass's frame: the listed envs' rows of the observation (and depth) into the final buffers.  Grid N, one
+// workgroup per list slot.
+extern "C" __global__ __launch_bounds__(256) void mw_final_copy_kernel(const int32_t *__restrict__ list, const uint8_t *__restrict__ obs,
+                                                                      uint8_t *__restrict__ final_obs, unsigned long long row_bytes,
+                                                                      const float *__restrict__ depth, float *__restrict__ final_depth, int depth_row)
+{
+    if ((int)blockIdx.x >= list[0]) return;
+    const size_t env = (size_t)list[1 + blockIdx.x];
+    const uint8_t *src = obs + env * row_bytes;
+    uint8_t *dst = final_obs + env * row_bytes;
+    if ((((uintptr_t)obs | (uintptr_t)final_obs | (uintptr_t)row_bytes) & 15u) == 0) {
+        for (size_t k = threadIdx.x; k < row_bytes / 16; k += blockDim.x)
+            reinterpret_cast<uint4 *>(dst)[k] = reinterpret_cast<const uint4 *>(src)[k];
+    } else {
+        for (size_t k = threadIdx.x; k < row_bytes; k += blockDim.x) dst[k] = src[k];
+    }
+    if (depth && final_depth)
+        for (int k = threadIdx.x; k < depth_row; k += blockDim.x) final_depth[env * depth_row + k] = depth[env * depth_row + k];
 }
 
 namespace {
@@ -177,6 +265,10 @@ struct mw_engine {
     static constexpr int slow_waves = 8192;      // wavefronts of the slow kernel's launch (4096: 59 us, 8192: 55)
     unsigned long long *d_ent_prof = nullptr;   // MW_ENT_PROF=<file>: the mesh entity kernel's per-env times and counts of the last frame, [N][8], dumped by mw_destroy
     unsigned long long *d_k2q_prof = nullptr;   // MW_K2Q_PROF=<file>: s_memtime stamps of the quad kernel's phases, [N][8 waves][8], dumped by mw_destroy
+    // mw_set_final_obs: the terminal frames of the envs whose episode ends in a same-step step (null: off); the list of those envs
+    uint8_t *final_obs = nullptr;
+    float *final_depth = nullptr;
+    int32_t *d_final_list = nullptr;    // [1 + N]: count, envs (mw_final_list_kernel)
 };
 
 namespace {
@@ -229,6 +321,30 @@ auto geom_kernel_of(const mw_engine *e, int L, int msaa) -> void (*)(MwArgs, int
     const bool fixed8 = msaa == 8;
     if (L == 64) return fixed8 ? mw_geom_big_kernel : mw_geom_big_any_kernel;
     return fixed8 ? mw_geom_kernel : mw_geom_any_kernel;
+}
+
+// ... its form that draws the envs of a list
+auto geom_sub_kernel_of(const mw_engine *e, int L, int msaa) -> decltype(&mw_geom_sub_kernel)
+{
+    (void)e;
+    const bool fixed8 = msaa == 8;
+    if (L == 64) return fixed8 ? mw_geom_big_sub_kernel : mw_geom_big_any_sub_kernel;
+    return fixed8 ? mw_geom_sub_kernel : mw_geom_any_sub_kernel;
+}
+
+// the tile kernel's form that draws the envs of a list
+auto raster_sub_of(decltype(&mw_raster_kernel) k) -> decltype(&mw_raster_sub_kernel)
+{
+    static const std::pair<decltype(&mw_raster_kernel), decltype(&mw_raster_sub_kernel)> map[] = {
+        {mw_raster_kernel, mw_raster_sub_kernel}, {mw_raster_depth_kernel, mw_raster_depth_sub_kernel},
+        {mw_raster_big_kernel, mw_raster_big_sub_kernel}, {mw_raster_big_depth_kernel, mw_raster_big_depth_sub_kernel},
+        {mw_raster_wrap_kernel, mw_raster_wrap_sub_kernel}, {mw_raster_big_wrap_kernel, mw_raster_big_wrap_sub_kernel},
+        {mw_raster_mesh_kernel, mw_raster_mesh_sub_kernel}, {mw_raster_nomesh_kernel, mw_raster_nomesh_sub_kernel},
+        {mw_raster_nomesh_depth_kernel, mw_raster_nomesh_depth_sub_kernel}, {mw_raster_mesh_depth_kernel, mw_raster_mesh_depth_sub_kernel},
+        {mw_raster_mesh_wrap_kernel, mw_raster_mesh_wrap_sub_kernel}, {mw_raster_big_mesh_wrap_kernel, mw_raster_big_mesh_wrap_sub_kernel},
+    };
+    for (const auto &m : map) if (m.first == k) return m.second;
+    return nullptr;
 }
 
 // The tile / quad / mesh-scatter kernels keep edge values in 32 bits: |c_k| = |dcdx X - dcdy Y| <= 2 W H 2^16 has to stay below
@@ -651,8 +767,14 @@ int ensure_mesh_buffers(mw_engine *e)
     return MW_OK;
 }
 
+// The frames of a same-step step with final observations (mw_step): FRAME_TERMINAL — the step kernel runs as the next-step mode's
+// terminal step (no install; reset_pending marks the finished envs), the list of those envs is built behind it, and the frame
+// shows every env's state after the step (terminal states for the finished envs); FRAME_LIST — no step, the frame of the listed
+// envs only (their new worlds), through the list forms of the geometry and raster kernels.
+enum { FRAME_ALL = 0, FRAME_TERMINAL = 1, FRAME_LIST = 2 };
+
 int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_actions, uint8_t *d_obs, float *d_depth,
-                 float *d_reward, uint8_t *d_term, uint8_t *d_trunc, hipStream_t st)
+                 float *d_reward, uint8_t *d_term, uint8_t *d_trunc, hipStream_t st, int frame = FRAME_ALL)
 {
     if (!d_obs) return fail(e, MW_E_INVALID, "d_obs is null");
     // (checked before anything is launched or any timing event is taken)
@@ -672,7 +794,8 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
     mw_engine::Ev ev{};
     // kernel durations are sampled: three event records on every launch cost ~4 % of the step rate,
     // on one launch in MW_TIMING_STRIDE they cost nothing measurable
-    const bool timed = e->timing && (e->frame_count++ % (uint64_t)e->timing_stride) == 0;
+    // (the second pass of a final-observation step is no frame of its own here)
+    const bool timed = frame != FRAME_LIST && e->timing && (e->frame_count++ % (uint64_t)e->timing_stride) == 0;
     if (timed) {
         ev = get_events(e);
         (void)hipEventRecord(ev.a, st);
@@ -685,6 +808,9 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
     const bool async_refill = e->spare_mode && do_step && e->cfg.generator == MW_GEN_MAZE;
     const int refill_blocks = (e->spare_mode && do_step && !async_refill) ? (N + 63) / 64 : 0;
     const int gl = geom_lanes(e);
+    const int32_t *list = e->d_final_list;
+    MwArgs ak = a;          // the step kernel's arguments: the first pass of a final-observation step runs as a next-step terminal step
+    if (frame == FRAME_TERMINAL) ak.autoreset = MW_AUTORESET_NEXT_STEP;
     if (!do_step) {
         // render only: nothing to step
     } else if (const int lanes = k1_dense_lanes(e, 0)) {
@@ -693,18 +819,23 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
         auto k1d = pcg ? mw_step_setup_dense_pcg_kernel : mw_step_setup_dense_kernel;
         // spare mode: blocks appended to the grid regenerate the spare worlds consumed in earlier steps (64 envs each)
         const int refill = (e->spare_mode && do_step) ? (N + 63) / 64 : 0;
-        hipLaunchKernelGGL(k1d, dim3((N + epw - 1) / epw + refill), dim3(64), 0, st, a, do_step ? 1 : 0, lanes, d_actions,
+        hipLaunchKernelGGL(k1d, dim3((N + epw - 1) / epw + refill), dim3(64), 0, st, ak, do_step ? 1 : 0, lanes, d_actions,
                            d_reward ? d_reward : e->d_reward_scratch, d_term ? d_term : e->d_flag_scratch,
                            d_trunc ? d_trunc : e->d_flag_scratch + N);
     } else {
-        hipLaunchKernelGGL(k1_of(e), dim3(N + refill_blocks), dim3(k1_threads(e)), 0, st, a, do_step ? 1 : 0, view_flags, d_actions,
+        hipLaunchKernelGGL(k1_of(e), dim3(N + refill_blocks), dim3(k1_threads(e)), 0, st, ak, do_step ? 1 : 0, view_flags, d_actions,
                            d_reward ? d_reward : e->d_reward_scratch, d_term ? d_term : e->d_flag_scratch,
                            d_trunc ? d_trunc : e->d_flag_scratch + N);
     }
+    if (frame == FRAME_TERMINAL)
+        hipLaunchKernelGGL(mw_final_list_kernel, dim3(1), dim3(1024), 0, st, N, (const uint8_t *)a.reset_pending, a.pending_remove, e->d_final_list);
     // the frame's vertex half: camera, lighting, transform, clipping, triangle setup (mw_geom.hip)
     {
         const int L = gl, epw = 64 / L;
-        hipLaunchKernelGGL(geom_kernel_of(e, L, e->cfg.msaa), dim3((N + epw - 1) / epw), dim3(64), 0, st, a, view_flags, e->cfg.msaa, L, N);
+        if (frame == FRAME_LIST)
+            hipLaunchKernelGGL(geom_sub_kernel_of(e, L, e->cfg.msaa), dim3((N + epw - 1) / epw), dim3(64), 0, st, a, view_flags, e->cfg.msaa, L, N, list);
+        else
+            hipLaunchKernelGGL(geom_kernel_of(e, L, e->cfg.msaa), dim3((N + epw - 1) / epw), dim3(64), 0, st, a, view_flags, e->cfg.msaa, L, N);
     }
     if (do_step && e->cfg.task == MW_TASK_COLLECT)
         hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_collect_respawn_pcg_kernel : mw_collect_respawn_kernel, dim3((N + 63) / 64), dim3(64), 0, st, a);
@@ -727,9 +858,14 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
         const int S = e->cfg.msaa;
         const int lds = mw_rasterq_lds_bytes(S, a.W, a.H, a.n_tiles, d_depth ? 1 : 0);
         const int flags = (e->dbg_flags & 0xFC8F) | (e->obs_layout << 8) | part_flags;
-        hipLaunchKernelGGL(S == 8 ? mw_rasterq_kernel : mw_rasterq4_kernel, dim3(N), dim3(MW_RASTERQ_THREADS), (size_t)lds, kq, a.N, a.W, a.H, a.max_vis,
-                           a.tiles_x, a.n_tiles, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
-                           (const int32_t *)a.nvis, (const float *)a.envhdr, a.texels, d_obs, d_depth, flags, e->texel_bytes, e->d_k2q_prof);
+        if (frame == FRAME_LIST)
+            hipLaunchKernelGGL(S == 8 ? mw_rasterq_sub_kernel : mw_rasterq4_sub_kernel, dim3(N), dim3(MW_RASTERQ_THREADS), (size_t)lds, kq, a.N, a.W, a.H, a.max_vis,
+                               a.tiles_x, a.n_tiles, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
+                               (const int32_t *)a.nvis, (const float *)a.envhdr, a.texels, d_obs, d_depth, flags, e->texel_bytes, e->d_k2q_prof, list);
+        else
+            hipLaunchKernelGGL(S == 8 ? mw_rasterq_kernel : mw_rasterq4_kernel, dim3(N), dim3(MW_RASTERQ_THREADS), (size_t)lds, kq, a.N, a.W, a.H, a.max_vis,
+                               a.tiles_x, a.n_tiles, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
+                               (const int32_t *)a.nvis, (const float *)a.envhdr, a.texels, d_obs, d_depth, flags, e->texel_bytes, e->d_k2q_prof);
     };
     if (k2q && e->cfg.msaa == 4) {
         launch_k2q(0, st);
@@ -746,12 +882,20 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
             if (need > e->view_keys_bytes) return fail(e, MW_E_INVALID, "view keys missing (mw_upload_mesh allocates them)");
             keys = e->d_view_keys;
             HIP_TRY(e, hipMemsetAsync(keys, 0xFF, need, st));
-            hipLaunchKernelGGL(mw_view_mesh_kernel, dim3(32, N), dim3(256), 0, st, a.W, a.H, S, 0, (const float *)a.envhdr, a.mesh_pos, keys);
+            if (frame == FRAME_LIST)
+                hipLaunchKernelGGL(mw_view_mesh_sub_kernel, dim3(32, N), dim3(256), 0, st, a.W, a.H, S, 0, (const float *)a.envhdr, a.mesh_pos, keys, list);
+            else
+                hipLaunchKernelGGL(mw_view_mesh_kernel, dim3(32, N), dim3(256), 0, st, a.W, a.H, S, 0, (const float *)a.envhdr, a.mesh_pos, keys);
         }
         e->last_raster_path = MW_PATH_GENERIC;
-        hipLaunchKernelGGL(mw_view_raster_kernel, dim3(a.n_tiles, N), dim3(64), 0, st, 0, a.W, a.H, S, a.max_vis, a.tiles_x,
-                           (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull, (const int32_t *)a.nvis, (const float *)a.envhdr,
-                           a.tex, a.texels, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, (const uint32_t *)keys, d_obs, d_depth, e->texel_bytes);
+        if (frame == FRAME_LIST)
+            hipLaunchKernelGGL(mw_view_raster_sub_kernel, dim3(a.n_tiles, N), dim3(64), 0, st, 0, a.W, a.H, S, a.max_vis, a.tiles_x,
+                               (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull, (const int32_t *)a.nvis, (const float *)a.envhdr,
+                               a.tex, a.texels, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, (const uint32_t *)keys, d_obs, d_depth, e->texel_bytes, list);
+        else
+            hipLaunchKernelGGL(mw_view_raster_kernel, dim3(a.n_tiles, N), dim3(64), 0, st, 0, a.W, a.H, S, a.max_vis, a.tiles_x,
+                               (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull, (const int32_t *)a.nvis, (const float *)a.envhdr,
+                               a.tex, a.texels, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, (const uint32_t *)keys, d_obs, d_depth, e->texel_bytes);
     } else {
         const bool mesh = e->have_meshes;
         uint32_t mesh_stamp = 0u;
@@ -816,13 +960,23 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
             const int wpe2 = (part_flags >> 4) == 2 ? a.n_tiles : wpe;
             const int tpw2 = (part_flags >> 4) == 2 ? 1 : tpw;
             const int grid = listed ? std::min(e->mesh_tile_waves, N * (int)a.n_tiles) : groups * 8 * wpe2;
-            hipLaunchKernelGGL((part_flags >> 4) == 1 ? k2_first : k2, dim3(grid), dim3(64), lds, ks, a.N, a.W, a.H, a.max_vis, a.tiles_x,
-                               a.n_tiles, wpe2, tpw2, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
-                               (const int32_t *)a.nvis,
-                               (const float *)a.envhdr, a.tex, a.texels, d_obs, d_depth, flags | part_flags, e->texel_bytes,
-                               (const uint16_t *)a.rec_order, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, e->d_mesh_keys,
-                               (const float *)e->d_plane_cache, e->plane_cap, (const float4 *)e->d_slow_frags, (const uint32_t *)e->d_slow_head,
-                               (const uint32_t *)a.tile_list, a.ent_list_n, a.tile_list_cap, std::max(a.n_xcc, 1));
+            const auto kk = (part_flags >> 4) == 1 ? k2_first : k2;
+            if (frame == FRAME_LIST)
+                hipLaunchKernelGGL(raster_sub_of(kk), dim3(grid), dim3(64), lds, ks, a.N, a.W, a.H, a.max_vis, a.tiles_x,
+                                   a.n_tiles, wpe2, tpw2, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
+                                   (const int32_t *)a.nvis,
+                                   (const float *)a.envhdr, a.tex, a.texels, d_obs, d_depth, flags | part_flags, e->texel_bytes,
+                                   (const uint16_t *)a.rec_order, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, e->d_mesh_keys,
+                                   (const float *)e->d_plane_cache, e->plane_cap, (const float4 *)e->d_slow_frags, (const uint32_t *)e->d_slow_head,
+                                   (const uint32_t *)a.tile_list, a.ent_list_n, a.tile_list_cap, std::max(a.n_xcc, 1), list);
+            else
+                hipLaunchKernelGGL(kk, dim3(grid), dim3(64), lds, ks, a.N, a.W, a.H, a.max_vis, a.tiles_x,
+                                   a.n_tiles, wpe2, tpw2, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
+                                   (const int32_t *)a.nvis,
+                                   (const float *)a.envhdr, a.tex, a.texels, d_obs, d_depth, flags | part_flags, e->texel_bytes,
+                                   (const uint16_t *)a.rec_order, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, e->d_mesh_keys,
+                                   (const float *)e->d_plane_cache, e->plane_cap, (const float4 *)e->d_slow_frags, (const uint32_t *)e->d_slow_head,
+                                   (const uint32_t *)a.tile_list, a.ent_list_n, a.tile_list_cap, std::max(a.n_xcc, 1));
         };
         e->last_raster_path = k2q ? (mesh ? MW_PATH_QUAD_MESH : MW_PATH_QUAD) : MW_PATH_TILE;
         if (mesh) {
@@ -978,6 +1132,7 @@ int mw_create(const mw_config *cfg, mw_engine **out)
     if (rc == MW_OK) (void)hipMemset(a.pending_remove, 0xFF, 4 * (size_t)N);
     ALLOC(a.nvis, N); ALLOC(a.envhdr, (size_t)MW_ENVHDR * N); ALLOC(a.status, 1);
     ALLOC(e->d_reward_scratch, N); ALLOC(e->d_flag_scratch, 2 * (size_t)N); ALLOC(e->d_action_scratch, N);
+    ALLOC(e->d_final_list, 1 + (size_t)N);
     ALLOC(e->d_mask, N); ALLOC(e->d_step_override, 3 * (size_t)N);
 #ifdef MW_PERF_HOOKS        // (tools/perf: make EXTRA=-DMW_PERF_HOOKS — kernel phase stamps dumped by mw_destroy; not in the product build)
     if (getenv("MW_K1_PROF")) {     // per-env cycle stamps of the geometry kernel's phases
@@ -1428,7 +1583,33 @@ int mw_step(mw_engine *e, const int32_t *d_actions, uint8_t *d_obs, float *d_dep
     if (!d_actions) return fail(e, MW_E_INVALID, "d_actions is null");
     if ((e->cfg.generator == MW_GEN_PROGRAM || e->cfg.task >= MW_TASK_SIDEWALK) && !e->args.prog)
         return fail(e, MW_E_INVALID, "no placement program installed (mw_set_gen_program)");
-    return launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, (hipStream_t)stream);
+    if (!e->final_obs) return launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, (hipStream_t)stream);
+    // Same-step auto-reset with final observations, in two passes.  1: the step as the next-step mode's terminal step — physics,
+    // rule, reward, flags, final info, per-step draws; the finished envs keep their terminal state — and the frame of every env.
+    // The finished envs' rows go to the final buffers.  2: they install their next world (the same install code and stream order
+    // as the plain same-step step: the step's draws, then the reset's), and the frame of those envs alone overwrites their rows.
+    const hipStream_t st = (hipStream_t)stream;
+    const int N = e->cfg.num_envs;
+    int rc = launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, st, FRAME_TERMINAL);
+    if (rc != MW_OK) return rc;
+    const size_t row_bytes = (size_t)e->cfg.obs_width * e->cfg.obs_height * (e->obs_layout == MW_OBS_GREY_F64 ? 8 : 3);
+    hipLaunchKernelGGL(mw_final_copy_kernel, dim3(N), dim3(256), 0, st, (const int32_t *)e->d_final_list, (const uint8_t *)d_obs, e->final_obs,
+                       (unsigned long long)row_bytes, (const float *)d_depth, e->final_depth, e->cfg.obs_width * e->cfg.obs_height);
+    hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_final_install_pcg_kernel : mw_final_install_kernel, dim3(N), dim3(64), 0, st,
+                       e->args, (const int32_t *)e->d_final_list);
+    return launch_frame(e, false, 0, e->d_action_scratch, d_obs, d_depth, nullptr, nullptr, nullptr, st, FRAME_LIST);
+}
+
+int mw_set_final_obs(mw_engine *e, uint8_t *d_final_obs, float *d_final_depth)
+{
+    if (!e) return MW_E_INVALID;
+    if (e->cfg.autoreset != MW_AUTORESET_SAME_STEP)
+        return fail(e, MW_E_INVALID, "mw_set_final_obs: final observations exist in MW_AUTORESET_SAME_STEP only (next-step returns the terminal frame itself)");
+    if (e->cfg.generator == MW_GEN_NONE)
+        return fail(e, MW_E_INVALID, "mw_set_final_obs: MW_GEN_NONE engines auto-reset nothing (the returned frame is the terminal one)");
+    e->final_obs = d_final_obs;
+    e->final_depth = d_final_obs ? d_final_depth : nullptr;
+    return MW_OK;
 }
 
 int mw_render(mw_engine *e, uint8_t *d_obs, float *d_depth, void *stream)

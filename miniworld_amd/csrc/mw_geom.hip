@@ -211,8 +211,11 @@ __device__ inline bool occluded_rmq(const float *rmq, const mwgl::Vert v[4], flo
 // small scenes' kernel, whose workgroups then fit four to a CU.
 // SFIX: the target's samples per pixel when fixed at compile time (8: the observation path — a quarter of the record
 // writer's code, 36 registers less), 0: taken from the launch
-template <bool BIG, int SFIX>
-__device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L, int n_env)
+// SUB: the frame of a subset of the batch (same-step auto-reset with final observations, mw_engine.hip): group g of the grid
+// draws env list[1 + g] while g < list[0]; the grid stays N-sized (the host does not know the count) and a workgroup without a
+// listed env exits at once
+template <bool BIG, int SFIX, bool SUB = false>
+__device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L, int n_env, const int32_t *__restrict__ list = nullptr)
 {
     const int S = SFIX ? SFIX : S_;
     // (244 dwords per slot: consecutive slots start in different LDS banks)
@@ -239,9 +242,14 @@ __device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L,
     [[maybe_unused]] unsigned long long kp_clip = 0, kp_emit = 0, kp_e_shfl = 0, kp_e_setup = 0, kp_e_write = 0;
     const int lane = threadIdx.x;
     const int epw = 64 / L, sub = lane & (L - 1), grp = lane / L;
+    if (SUB) {
+        n_env = list[0];
+        if ((int)blockIdx.x * epw >= n_env) return;     // (uniform over the workgroup: one wavefront)
+    }
     const int rel = (int)blockIdx.x * epw + grp;
     const bool live = rel < n_env;
-    const int env = a.env_base + (live ? rel : n_env - 1);      // a padding group recomputes the last env and writes nothing
+    // a padding group recomputes the last env and writes nothing
+    const int env = SUB ? list[1 + (live ? rel : n_env - 1)] : a.env_base + (live ? rel : n_env - 1);
     const int set = a.shared_geom ? 0 : env;
     const bool top = (view_flags & 1) != 0, proxy = (view_flags & 4) != 0, ms = S > 1;
     // big scenes: the per-world culling data (occ_cache: full-height walls, boxes of eight polygons) lives in HBM, one to two
@@ -1300,6 +1308,11 @@ extern "C" __global__ __launch_bounds__(64) MW_GEOM_OCC void mw_geom_big_kernel(
 // ... for frame buffers with 1, 4 or 16 samples per pixel
 extern "C" __global__ __launch_bounds__(64) void mw_geom_any_kernel(MwArgs a, int view_flags, int S, int L, int n_env) { geom_body<false, 0>(a, view_flags, S, L, n_env); }
 extern "C" __global__ __launch_bounds__(64) void mw_geom_big_any_kernel(MwArgs a, int view_flags, int S, int L, int n_env) { geom_body<true, 0>(a, view_flags, S, L, n_env); }
+// ... the same four over the envs of a list (int32 [0] count, [1 + i] env; n_env unused)
+extern "C" __global__ __launch_bounds__(64) MW_GEOM_OCC void mw_geom_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list) { geom_body<false, 8, true>(a, view_flags, S, L, n_env, list); }
+extern "C" __global__ __launch_bounds__(64) MW_GEOM_OCC void mw_geom_big_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list) { geom_body<true, 8, true>(a, view_flags, S, L, n_env, list); }
+extern "C" __global__ __launch_bounds__(64) void mw_geom_any_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list) { geom_body<false, 0, true>(a, view_flags, S, L, n_env, list); }
+extern "C" __global__ __launch_bounds__(64) void mw_geom_big_any_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list) { geom_body<true, 0, true>(a, view_flags, S, L, n_env, list); }
 
 // mw_selftest_sort: the visiting order's sort on keys of the caller's (tests/test_gpu_numerics.py): block b sorts the
 // n[b] <= 512 keys at keys + 512 b into order + 513 b (order[0] unused, then the keys' low halves in ascending key order)

@@ -24,8 +24,10 @@
 //                   visible primitives (Maze) would not leave room for enough resident waves.
 // MESHAWARE   : envs may hold mesh entities — the tiles inside a mesh entity's tile rectangle (env header) start from the
 //               sample keys the scatter kernel left (mw_raster_mesh.hip) and give them back cleared.
+// (always inlined: with the list forms below it has two callers per instantiation, and as a called function it cost the
+// kernels twice their registers)
 template <bool LDS_RECS, int FMT, int HOT = 0, int MESHAWARE = 0>
-__device__ inline void raster_env_tiles(
+__device__ __attribute__((always_inline)) inline void raster_env_tiles(
     int N, int env, int t_begin, int t_end, int part_mode, int W, int H, int max_vis, int tiles_x, int n_tiles,
     const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull,
     const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const MwTexDesc *__restrict__ texd,
@@ -166,8 +168,11 @@ __device__ inline void raster_env_tiles(
 // persistent wavefronts drawing (env, tile) items from the list the geometry kernel left (mw_geom.hip: the union of the
 // entities' tile rectangles; a grid of one wavefront per tile of every env spent most of its time starting wavefronts that
 // found no mesh in their env).
-template <bool LDS_RECS, int FMT, int HOT = 0, int MESHAWARE = 0>
-__device__ inline void raster_kernel_body(
+// SUB: the frame of a subset of the batch (mw_engine.hip, same-step auto-reset with final observations): the block's env slot e
+// draws env list[1 + e] while e < list[0], and exits otherwise (the listed mesh tiles come from the geometry kernel's list, which
+// held the listed envs only).
+template <bool LDS_RECS, int FMT, int HOT = 0, int MESHAWARE = 0, bool SUB = false>
+__device__ __attribute__((always_inline)) inline void raster_kernel_body(
     int N, int W, int H, int max_vis, int tiles_x, int n_tiles, int waves_per_env, int tiles_per_wave,
     const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull,
     const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const MwTexDesc *__restrict__ texd,
@@ -175,7 +180,7 @@ __device__ inline void raster_kernel_body(
     const uint16_t *__restrict__ rec_order, const float *__restrict__ mesh_pos, const float *__restrict__ mesh_nrm,
     const float *__restrict__ mesh_rgb, const float *__restrict__ mesh_uv, uint32_t *__restrict__ mesh_keys,
     const float *__restrict__ plane_cache, int plane_cap, const float4 *__restrict__ slow_frags, const uint32_t *__restrict__ slow_head,
-    const uint32_t *__restrict__ tile_list, int32_t *__restrict__ tile_n, int tile_list_cap, int n_xcc)
+    const uint32_t *__restrict__ tile_list, int32_t *__restrict__ tile_n, int tile_list_cap, int n_xcc, const int32_t *__restrict__ list = nullptr)
 {
     if (MESHAWARE == 1) __builtin_amdgcn_s_setprio(3);      // (the mesh tiles end the frame's critical path: ahead of the quad kernel's wavefronts)
     // (one call site for both forms: two copies of the tile code in one kernel cost it 150 registers)
@@ -199,7 +204,10 @@ __device__ inline void raster_kernel_body(
             const int b = blockIdx.x;
             const int xcd = b & 7, slot = b >> 3;
             env = (slot / waves_per_env) * 8 + xcd;
-            if (env >= N) return;
+            if (SUB) {
+                if (env >= list[0]) return;
+                env = list[1 + env];
+            } else if (env >= N) return;
             t_begin = (slot % waves_per_env) * tiles_per_wave; t_end = min(t_begin + tiles_per_wave, n_tiles);
         }
         raster_env_tiles<LDS_RECS, FMT, HOT, MESHAWARE>(N, env, t_begin, t_end, listed ? 2 : part_mode, W, H, max_vis, tiles_x, n_tiles, rec_raster, rec_shade, rec_cull, nvis_arr,
@@ -271,6 +279,23 @@ extern "C" __global__ __launch_bounds__(64, MW_MESH_TILE_OCC) void mw_raster_mes
 extern "C" __global__ __launch_bounds__(64, MW_MESH_TILE_OCC) void mw_raster_mesh_depth_kernel(MW_RASTER_ARGS) { raster_kernel_body<true, 0, 2, 1>(MW_RASTER_FWD); }
 extern "C" __global__ __launch_bounds__(64) void mw_raster_mesh_wrap_kernel(MW_RASTER_ARGS) { raster_kernel_body<true, -1, 0, 1>(MW_RASTER_FWD); }
 extern "C" __global__ __launch_bounds__(64) void mw_raster_big_mesh_wrap_kernel(MW_RASTER_ARGS) { raster_kernel_body<false, -1, 0, 1>(MW_RASTER_FWD); }
+
+// ... each of them over the envs of a list (int32 [0] count, [1 + i] env): the second pass of a same-step auto-reset step with
+// final observations (mw_engine.hip)
+#define MW_RASTER_SUB(name, occ, ...) \
+    extern "C" __global__ occ void name(MW_RASTER_ARGS, const int32_t *__restrict__ list) { raster_kernel_body<__VA_ARGS__, true>(MW_RASTER_FWD, list); }
+MW_RASTER_SUB(mw_raster_sub_kernel, __launch_bounds__(64), true, 0, 1, 0)
+MW_RASTER_SUB(mw_raster_depth_sub_kernel, __launch_bounds__(64), true, 0, 2, 0)
+MW_RASTER_SUB(mw_raster_big_sub_kernel, __launch_bounds__(64) MW_K2BIG_OCC, false, 0, 1, 0)
+MW_RASTER_SUB(mw_raster_big_depth_sub_kernel, __launch_bounds__(64), false, 0, 2, 0)
+MW_RASTER_SUB(mw_raster_wrap_sub_kernel, __launch_bounds__(64), true, -1, 0, 0)
+MW_RASTER_SUB(mw_raster_big_wrap_sub_kernel, __launch_bounds__(64), false, -1, 0, 0)
+MW_RASTER_SUB(mw_raster_nomesh_sub_kernel, __launch_bounds__(64), true, 0, 1, 2)
+MW_RASTER_SUB(mw_raster_nomesh_depth_sub_kernel, __launch_bounds__(64), true, 0, 2, 2)
+MW_RASTER_SUB(mw_raster_mesh_sub_kernel, __launch_bounds__(64, MW_MESH_TILE_OCC), true, 0, 1, 1)
+MW_RASTER_SUB(mw_raster_mesh_depth_sub_kernel, __launch_bounds__(64, MW_MESH_TILE_OCC), true, 0, 2, 1)
+MW_RASTER_SUB(mw_raster_mesh_wrap_sub_kernel, __launch_bounds__(64), true, -1, 0, 1)
+MW_RASTER_SUB(mw_raster_big_mesh_wrap_sub_kernel, __launch_bounds__(64), false, -1, 0, 1)
 
 #ifdef MW_PERF_HOOKS
 // tools/perf/k2prof.py: read (and zero) this translation unit's phase counters

@@ -3,12 +3,14 @@
 #include "mw_mesh.h"
 
 // HW_REG_XCC_ID of 256 workgroups: which XCDs does this device show (mw_create)
+#ifndef MW_VIEW_LIST_UNIT      // (the list forms of the generic-resolution kernels: mw_raster_view_list.hip)
 extern "C" __global__ void mw_xcc_probe_kernel(uint32_t *out)
 {
     uint32_t x;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
     if (threadIdx.x == 0) out[blockIdx.x] = x & 15u;
 }
+#endif
 
 namespace {
 // a workgroup barrier that orders LDS only: the global minima and plane records in flight need no other wave's attention,
@@ -35,6 +37,7 @@ __device__ inline void lds_barrier()
 // The workgroups (MW_ENT_THREADS lanes; dynamic LDS: 16 bytes x the largest uploaded vertex table — a launch of one workgroup
 // per env would queue 2 048 of them for LDS, most to find no mesh in view) are persistent: each draws envs from a counter and
 // goes through the env's mesh entities in view.
+#ifndef MW_VIEW_LIST_UNIT      // (the list forms of the generic-resolution kernels: mw_raster_view_list.hip)
 extern "C" __global__ __launch_bounds__(MW_ENT_THREADS, MW_ENT_OCC) void mw_mesh_entity_kernel(
     int N, int W, int H, const float *__restrict__ envhdr, const MwMeshDesc *__restrict__ meshes, const float4 *__restrict__ mesh_vpos,
     const uint2 *__restrict__ mesh_idx, const float *__restrict__ mesh_stream, const float *__restrict__ mesh_attr, uint32_t *__restrict__ keys_all,
@@ -172,6 +175,7 @@ extern "C" __global__ __launch_bounds__(MW_ENT_THREADS, MW_ENT_OCC) void mw_mesh
         }
     }
 }
+#endif
 
 // The mesh triangles that cross a frustum plane (a mesh at the frame's edge; the scatter kernel lists them): clipped, every
 // piece set up on its own (llvmpipe's clipper output), its keys scattered, its attribute planes left in the env's piece
@@ -230,6 +234,7 @@ __device__ inline void slow_pixel(const SlowPiece &p, int px, int gy, int W, int
 
 }  // namespace
 
+#ifndef MW_VIEW_LIST_UNIT      // (the list forms of the generic-resolution kernels: mw_raster_view_list.hip)
 extern "C" __global__ __launch_bounds__(64) void mw_mesh_slow_kernel(int W, int H, const float *__restrict__ envhdr, const float *__restrict__ mesh_pos,
                                                                     const float *__restrict__ mesh_nrm, const float *__restrict__ mesh_rgb,
                                                                     const float *__restrict__ mesh_uv, const uint32_t *__restrict__ texels, int texel_bytes,
@@ -382,6 +387,7 @@ extern "C" __global__ __launch_bounds__(64) void mw_mesh_slow_kernel(int W, int 
     }
     }
 }
+#endif
 
 // ======================================================================================
 // Generic-resolution path: render()/vis_fb 800x600 (miniworld.py:518, 1340-1362), the fallback sample counts of
@@ -405,19 +411,42 @@ __device__ inline void view_mesh_body(int W, int H, const float *hdr, const floa
     }
 }
 
-// grid (x, count): blockIdx.y = env first_env + y of the batch, its keys at keys + y * W * H * S
-extern "C" __global__ __launch_bounds__(256) MW_NO_TAIL_MARKS void mw_view_mesh_kernel(int W, int H, int S, int first_env, const float *__restrict__ envhdr,
-                                                                     const float *__restrict__ mesh_pos, uint32_t *keys)
+// grid (x, count): blockIdx.y = env first_env + y of the batch, its keys at keys + y * W * H * S.  SUB (first_env = 0, the whole
+// batch's keys): y draws env list[1 + y] while y < list[0] (same-step auto-reset with final observations, mw_engine.hip).
+template <bool SUB>
+__device__ __attribute__((always_inline)) inline void view_mesh_kernel_body(int W, int H, int S, int first_env, const float *__restrict__ envhdr,
+                                             const float *__restrict__ mesh_pos, uint32_t *keys, const int32_t *__restrict__ list)
 {
     __shared__ mwgl::Vert s_clip[4][MW_CLIP_TURN * 2 * MWGL_MAX_CLIP_VERTS];       // the clipper's work lists, MW_CLIP_TURN pairs per wavefront
     mwgl::Vert *clipbuf = s_clip[threadIdx.x >> 6];
-    const float *hdr = envhdr + (size_t)(first_env + (int)blockIdx.y) * MW_ENVHDR;
-    keys += (size_t)blockIdx.y * W * H * S;
+    int y = (int)blockIdx.y;
+    if (SUB) {
+        if (y >= list[0]) return;
+        y = list[1 + y];
+    }
+    const float *hdr = envhdr + (size_t)(first_env + y) * MW_ENVHDR;
+    keys += (size_t)y * W * H * S;
     if (S == 16) view_mesh_body<16>(W, H, hdr, mesh_pos, keys, clipbuf);
     else if (S == 4) view_mesh_body<4>(W, H, hdr, mesh_pos, keys, clipbuf);
     else if (S == 1) view_mesh_body<1>(W, H, hdr, mesh_pos, keys, clipbuf);
     else view_mesh_body<8>(W, H, hdr, mesh_pos, keys, clipbuf);
 }
+
+#ifndef MW_VIEW_LIST_UNIT      // (the list forms of the generic-resolution kernels: mw_raster_view_list.hip)
+extern "C" __global__ __launch_bounds__(256) MW_NO_TAIL_MARKS void mw_view_mesh_kernel(int W, int H, int S, int first_env, const float *__restrict__ envhdr,
+                                                                     const float *__restrict__ mesh_pos, uint32_t *keys)
+{
+    view_mesh_kernel_body<false>(W, H, S, first_env, envhdr, mesh_pos, keys, nullptr);
+}
+#endif
+
+#ifdef MW_VIEW_LIST_UNIT
+extern "C" __global__ __launch_bounds__(256) MW_NO_TAIL_MARKS void mw_view_mesh_sub_kernel(int W, int H, int S, int first_env, const float *__restrict__ envhdr,
+                                                                         const float *__restrict__ mesh_pos, uint32_t *keys, const int32_t *__restrict__ list)
+{
+    view_mesh_kernel_body<true>(W, H, S, first_env, envhdr, mesh_pos, keys, list);
+}
+#endif
 
 template <int S>
 __device__ inline void view_tile_body(TileCtx &cx, int tiles_x, const uint32_t *mesh_keys)
@@ -486,19 +515,25 @@ __device__ inline void view_tile_body(TileCtx &cx, int tiles_x, const uint32_t *
 }
 
 // grid (n_tiles, count): blockIdx.y = env first_env + y of the batch; its frame at out + y * H * W * 3, its mesh keys
-// at mesh_keys + y * W * H * S
-extern "C" __global__ __launch_bounds__(64) MW_NO_TAIL_MARKS void mw_view_raster_kernel(
-    int first_env, int W, int H, int S, int max_vis, int tiles_x, const float *__restrict__ rec_raster,
-    const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr,
-    const MwTexDesc *__restrict__ texd, const uint32_t *__restrict__ texels, const float *__restrict__ mesh_pos,
-    const float *__restrict__ mesh_nrm, const float *__restrict__ mesh_rgb, const float *__restrict__ mesh_uv, const uint32_t *mesh_keys,
-    uint8_t *__restrict__ out, float *__restrict__ depth, int texel_bytes)
+// at mesh_keys + y * W * H * S.  SUB (first_env = 0, the whole batch's buffers): y draws env list[1 + y] while y < list[0].
+#define MW_VIEW_RASTER_ARGS \
+    int first_env, int W, int H, int S, int max_vis, int tiles_x, const float *__restrict__ rec_raster, \
+    const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, \
+    const MwTexDesc *__restrict__ texd, const uint32_t *__restrict__ texels, const float *__restrict__ mesh_pos, \
+    const float *__restrict__ mesh_nrm, const float *__restrict__ mesh_rgb, const float *__restrict__ mesh_uv, const uint32_t *mesh_keys, \
+    uint8_t *__restrict__ out, float *__restrict__ depth, int texel_bytes
+#define MW_VIEW_RASTER_FWD first_env, W, H, S, max_vis, tiles_x, rec_raster, rec_shade, rec_cull, nvis_arr, envhdr, texd, texels, mesh_pos, \
+    mesh_nrm, mesh_rgb, mesh_uv, mesh_keys, out, depth, texel_bytes
+template <bool SUB>
+__device__ __attribute__((always_inline)) inline void view_raster_kernel_body(MW_VIEW_RASTER_ARGS, const int32_t *__restrict__ list)
 {
     __shared__ mwgl::Vert s_clip[MW_CLIP_TURN * 2 * MWGL_MAX_CLIP_VERTS];
-    const int env = first_env + (int)blockIdx.y;
-    out += (size_t)blockIdx.y * H * W * 3;
-    if (depth) depth += (size_t)blockIdx.y * H * W;
-    if (mesh_keys) mesh_keys += (size_t)blockIdx.y * W * H * S;
+    if (SUB && (int)blockIdx.y >= list[0]) return;
+    const unsigned y = SUB ? (unsigned)list[1 + blockIdx.y] : blockIdx.y;
+    const int env = first_env + (int)y;
+    out += (size_t)y * H * W * 3;
+    if (depth) depth += (size_t)y * H * W;
+    if (mesh_keys) mesh_keys += (size_t)y * W * H * S;
     const float *hdr = envhdr + (size_t)env * MW_ENVHDR;
     TileCtx cx;
     cx.s_shade = reinterpret_cast<const float4 *>(rec_shade + (size_t)env * max_vis * MW_SHADE_REC);
@@ -522,4 +557,18 @@ extern "C" __global__ __launch_bounds__(64) MW_NO_TAIL_MARKS void mw_view_raster
     else if (S == 1) view_tile_body<1>(cx, tiles_x, mesh_keys);
     else view_tile_body<8>(cx, tiles_x, mesh_keys);
 }
+
+#ifndef MW_VIEW_LIST_UNIT      // (the list forms of the generic-resolution kernels: mw_raster_view_list.hip)
+extern "C" __global__ __launch_bounds__(64) MW_NO_TAIL_MARKS void mw_view_raster_kernel(MW_VIEW_RASTER_ARGS)
+{
+    view_raster_kernel_body<false>(MW_VIEW_RASTER_FWD, nullptr);
+}
+#endif
+
+#ifdef MW_VIEW_LIST_UNIT
+extern "C" __global__ __launch_bounds__(64) MW_NO_TAIL_MARKS void mw_view_raster_sub_kernel(MW_VIEW_RASTER_ARGS, const int32_t *__restrict__ list)
+{
+    view_raster_kernel_body<true>(MW_VIEW_RASTER_FWD, list);
+}
+#endif
 

@@ -545,17 +545,23 @@ __device__ inline void batch_exact(const QCtx &cx, int kmax, Tri tri, RecOf recp
 }
 
 // ---- the kernel -------------------------------------------------------------------------------------------------------------
-template <int S>
+// SUB: the frame of a subset of the batch (mw_engine.hip, same-step auto-reset with final observations): workgroup e draws env
+// list[1 + e] while e < list[0] and exits at once otherwise (before any barrier: the whole workgroup)
+template <int S, bool SUB = false>
 __device__ inline void rasterq_body(
     int N, int W, int H, int max_vis, int tiles_x, int n_tiles,
     const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull,
     const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const uint32_t *__restrict__ texels,
-    uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof)
+    uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof,
+    const int32_t *__restrict__ list = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef QRec<S> R;
-    const int env = blockIdx.x;
-    if (env >= N) return;
+    int env = blockIdx.x;
+    if (SUB) {
+        if (env >= list[0]) return;
+        env = list[1 + env];
+    } else if (env >= N) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool has_depth = depth != nullptr;
     const QPlan pl = q_plan(S, W, H, n_tiles, has_depth);
@@ -978,6 +984,9 @@ __device__ inline void rasterq_body(
 
 extern "C" __global__ __launch_bounds__(MWQ_THREADS, MWQ_OCC) void mw_rasterq_kernel(MWQ_ARGS) { rasterq_body<8>(MWQ_FWD); }
 extern "C" __global__ __launch_bounds__(MWQ_THREADS) void mw_rasterq4_kernel(MWQ_ARGS) { rasterq_body<4>(MWQ_FWD); }
+// ... over the envs of a list (int32 [0] count, [1 + i] env)
+extern "C" __global__ __launch_bounds__(MWQ_THREADS, MWQ_OCC) void mw_rasterq_sub_kernel(MWQ_ARGS, const int32_t *__restrict__ list) { rasterq_body<8, true>(MWQ_FWD, list); }
+extern "C" __global__ __launch_bounds__(MWQ_THREADS) void mw_rasterq4_sub_kernel(MWQ_ARGS, const int32_t *__restrict__ list) { rasterq_body<4, true>(MWQ_FWD, list); }
 
 // bytes of dynamic LDS a launch needs (mw_engine.hip)
 extern "C" int mw_rasterq_lds_bytes(int S, int W, int H, int n_tiles, int depth) { return q_plan(S, W, H, n_tiles, depth != 0).total; }

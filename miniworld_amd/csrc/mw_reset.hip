@@ -44,6 +44,26 @@ extern "C" __global__ __launch_bounds__(64) void MW_RESPAWN_KERNEL_NAME(MwArgs a
     a.pending_remove[env] = -1;
 }
 
+#ifndef MW_INSTALL_KERNEL_NAME
+#define MW_INSTALL_KERNEL_NAME mw_final_install_kernel
+#endif
+// Same-step auto-reset with final observations, between the two passes of the step (mw_engine.hip): the listed envs (int32
+// [0] count, [1 + i] env: the ones whose episode ended with this step, whose terminal frame was drawn) install their next world
+// through the same install code as the step kernel's, and leave nothing of the finished episode behind: no pending removal (a
+// picked object, CollectHealth's consumed kit), no pending next-step reset.  One wavefront per list slot; grid N.
+extern "C" __global__ __launch_bounds__(64) void MW_INSTALL_KERNEL_NAME(MwArgs a, const int32_t *__restrict__ list)
+{
+    __shared__ unsigned char gen_ws[MW_GEN_WS_BYTES];
+    __shared__ int s_claim;
+    if ((int)blockIdx.x >= list[0]) return;
+    const int env = list[1 + blockIdx.x], lane = (int)threadIdx.x;
+    mw::install_next_world(a, env, lane, gen_ws, &s_claim);
+    if (lane == 0) {
+        a.pending_remove[env] = -1;
+        a.reset_pending[env] = 0;
+    }
+}
+
 #if MW_RNG_KIND == 0
 // mw_reset without seeds in spare mode: the masked envs take their pre-generated world (one wavefront per env)
 extern "C" __global__ __launch_bounds__(64) void mw_take_spare_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all)

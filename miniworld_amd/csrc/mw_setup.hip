@@ -34,7 +34,7 @@ extern "C" __global__ __launch_bounds__(64 * MW_K1_WAVES) __attribute__((amdgpu_
         return;
     }
     const int env = a.env_base + blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const bool writer = threadIdx.x == 0;       // the one thread that writes the env's state
     StepCtx c{a, env, lane, a.shared_geom ? 0 : env, 0, 0, 0, 0, 0, -1, -1, {0, 0, 0}, 0};
     c.px = a.ax[env]; c.py = a.ay[env]; c.pz = a.az[env]; c.dir = a.adir[env];
@@ -183,29 +183,8 @@ extern "C" __global__ __launch_bounds__(64 * MW_K1_WAVES) __attribute__((amdgpu_
     // returned with done = 1 is the first one of the next episode.  Next-step auto-reset: on the step after it, the reference's
     // "step; if done: reset()" (scripts/benchmark.py:36-37) — the stream is consumed in that order.
     if (a.generator != MW_GEN_NONE && (pend || (do_step && a.autoreset == MW_AUTORESET_SAME_STEP && (tm | tr) != 0))) {
-        if (a.spare) {
-            // the next world was generated ahead (by a refill block of an earlier launch): claim it
-            if (writer) s_cnt[0][0] = (int)atomicCAS(a.refill_mask + env, 1u, 3u);
-            __syncthreads();
-            __threadfence();        // acquire: the spare's contents (written by another block, released with its state) are read behind the claim
-            const int old = s_cnt[0][0];
-            if (old == 1) {
-                // the previous episode lasted one step and the refill has not run yet: generate in place
-                if (wave == 0) mw::generate_world(*a.gen_live, env, gen_ws, lane);
-            } else {
-                if (old == 2) {     // a refill block of this very launch is on it
-                    if (writer) while (__hip_atomic_load(a.refill_mask + env, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u) __builtin_amdgcn_s_sleep(16);
-                    __syncthreads();
-                }
-                if (wave == 0) mw::take_spare(a, env, lane);
-            }
-            __threadfence();
-            __syncthreads();
-            if (writer) atomicExch(a.refill_mask + env, 1u);        // the spare is missing again
-        } else if (wave == 0) {
-            mw::generate_world(*a.gen_live, env, gen_ws, lane);
-        }
-        __syncthreads();
+        static_assert(KW == 1, "mw::install_next_world runs on one wavefront");
+        mw::install_next_world(a, env, lane, gen_ws, &s_cnt[0][0]);
         c.px = a.ax[env]; c.py = a.ay[env]; c.pz = a.az[env]; c.dir = a.adir[env];
         c.carry = -1; c.live = -1;
         remove_slot = -1;

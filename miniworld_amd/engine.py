@@ -34,7 +34,7 @@ PATH_TILE, PATH_QUAD, PATH_QUAD_MESH, PATH_GENERIC = 0, 1, 2, 3
 EXPORTS = [
     "mw_create", "mw_destroy", "mw_last_error", "mw_upload_texture", "mw_upload_mesh",
     "mw_set_geometry", "mw_get_geometry", "mw_set_state", "mw_get_state", "mw_set_step_params", "mw_reset",
-    "mw_step", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
+    "mw_step", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
     "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
 ]
 
@@ -183,6 +183,7 @@ def load_library():
     L.mw_render_view.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
     L.mw_visible_ents.argtypes = [vp, i32, i32, vp, vp]
     L.mw_set_obs_layout.argtypes = [vp, i32]
+    L.mw_set_final_obs.argtypes = [vp, vp, vp]
     L.mw_pcg64_draws.argtypes = [C.c_uint64, i32, vp, vp]
     L.mw_check.argtypes = [vp, vp]
     L.mw_kernel_time_ms.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -342,6 +343,19 @@ class Engine:
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         self._check(self.lib.mw_step(self.h, ptr(actions), ptr(obs), ptr(depth), ptr(reward), ptr(term),
                                      ptr(trunc), _stream_ptr(self.device)), "mw_step")
+
+    def set_final_obs(self, obs=None, depth=None):
+        """Same-step auto-reset: every later step writes the terminal frame (and depth) of each env whose episode ended in it into
+        that env's row of `obs` (`depth`); the other rows are left alone.  Device tensors shaped like the step's obs / depth
+        (obs_buffer()); obs=None turns it off.  The engine keeps references to them while they are in use."""
+        import torch
+        if obs is not None:
+            obs_numel = self.N * self.H * self.W * (1 if self.obs_layout == OBS_GREY_F64 else 3)
+            self._dev_tensor(obs, "final obs", torch.float64 if self.obs_layout == OBS_GREY_F64 else torch.uint8, obs_numel)
+            self._dev_tensor(depth, "final depth", torch.float32, self.N * self.H * self.W)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.mw_set_final_obs(self.h, ptr(obs), ptr(depth if obs is not None else None)), "mw_set_final_obs")
+        self._final_bufs = (obs, depth) if obs is not None else None
 
     def render(self, obs, depth=None):
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())

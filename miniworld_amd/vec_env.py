@@ -57,7 +57,7 @@ _KIND = {
 class MiniWorldVecEnv:
     def __init__(self, env_id: str, num_envs: int, device_id: int = 0, domain_rand: bool = False,
                  want_depth: bool = False, seed: int = 0, autoreset: bool | str = True, obs_layout: str = "hwc",
-                 rng: str = "auto", msaa: int = 8, **env_kwargs):
+                 rng: str = "auto", msaa: int = 8, final_obs: bool = False, **env_kwargs):
         """obs_layout: "hwc" uint8[N,H,W,3] (the env's observation), "cwh" uint8[N,3,W,H]
         (PyTorchObsWrapper, wrappers.py:24) or "grey" float64[N,H,W,1] (GreyscaleWrapper, wrappers.py:44):
         the raster kernel stores the frame in that layout, there is no extra pass.
@@ -68,13 +68,19 @@ class MiniWorldVecEnv:
         continue like env.reset(), per-step domain-randomisation draws included (every device generator);
         "philox" = the engine's counter-based stream; "auto" = pcg64 where implemented.
         autoreset: True or "same_step", "next_step", False (see the module's docstring); the mode is `autoreset_mode`
-        ("same_step", "next_step" or "off")."""
+        ("same_step", "next_step" or "off").
+        final_obs (same-step auto-reset only): every step also writes the terminal frame of each env whose episode ended in it
+        into that env's row of `self.final_obs` (and its depth into `self.final_depth` with want_depth); the other rows keep
+        what they held.  Costs a second, small frame of the finished envs in every step."""
         import torch
         self.torch = torch
         modes = {True: "same_step", False: "off", "same_step": "same_step", "next_step": "next_step"}
         if not isinstance(autoreset, (bool, str)) or autoreset not in modes:
             raise ValueError(f"autoreset must be True, False, 'same_step' or 'next_step', not {autoreset!r}")
         self.autoreset_mode = modes[autoreset]
+        if final_obs and self.autoreset_mode != "same_step":
+            raise ValueError(f"final_obs needs the same-step auto-reset (autoreset={autoreset!r}: "
+                             + ("the terminal step returns the terminal frame itself)" if self.autoreset_mode == "next_step" else "nothing is auto-reset)"))
         if obs_layout not in ("hwc", "cwh", "grey"):
             raise ValueError(f"obs_layout must be 'hwc', 'cwh' or 'grey', not {obs_layout!r}")
         self.obs_layout = obs_layout
@@ -217,6 +223,11 @@ class MiniWorldVecEnv:
         self.reward = torch.zeros(num_envs, dtype=torch.float32, device=dev)
         self.terminated = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
         self.truncated = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
+        self.final_obs = self.final_depth = None
+        if final_obs:
+            self.final_obs = self.engine.obs_buffer()
+            self.final_depth = torch.zeros_like(self.depth) if want_depth else None
+            self.engine.set_final_obs(self.final_obs, self.final_depth)
         self._host_envs = None
         self._next_seed = seed
         # what the env's step() reports in `info` beside the observation (collecthealth.py:100, tmaze.py:89, ymaze.py:125)

@@ -10,13 +10,17 @@ a finished episode is the first one of the next episode; or "next-step", below).
 torch tensors on the engine's GPU by default (`to_numpy=True` copies them to the host like a
 classic VectorEnv); actions may be a torch tensor, a numpy array or a list.
 
-**What a same-step consumer does NOT get: `final_obs`.**  Gymnasium's SAME_STEP mode promises the finished episode's last
-observation under info["final_obs"]; the engine never draws it (the step's only frame is the next episode's first one —
-the reference leaves resets to the caller and renders once per step, miniworld.py:670-730).  Code that bootstraps a value
-from final_obs on truncation must take the returned observation's predecessor instead.  What IS there: info["_final_info"]
-(bool[N], for every env family, also those without info keys) and — for the families that have info keys
-(CollectHealth's health, TMaze / YMaze's goal_pos) — info["final_info"], the finished episodes' own values.  The arrays
-under final_info are copies: they stay valid after the next step.
+**A same-step consumer gets `final_obs` on request: `final_obs=True`.**  Gymnasium's SAME_STEP mode promises the finished
+episode's last observation under info["final_obs"].  By default the engine does not draw it (the step's only frame is the next
+episode's first one — the reference leaves resets to the caller and renders once per step, miniworld.py:670-730), and no
+"final_obs" key is emitted.  With `final_obs=True` every step draws the finished envs' terminal frames as well (a second, small
+frame of those envs in the same step, on the device) and info carries "final_obs" (the batch's observation array: the rows
+masked by info["_final_obs"] hold the terminal frames, the others are undefined; a copy, valid after the next step) and
+"_final_obs" (bool[N], the envs whose episode ended with this step).  SB3's `terminal_observation` and gymnasium 0.29's
+`final_observation` are the same rows.  Always there: info["_final_info"] (bool[N], for every env family, also those
+without info keys) and — for the families that have info keys (CollectHealth's health, TMaze / YMaze's goal_pos) —
+info["final_info"], the finished episodes' own values.  The arrays under final_info are copies: they stay valid after the
+next step.
 
 **`autoreset_mode="next-step"` gives the terminal observation** (gymnasium's AutoresetMode.NEXT_STEP, its default for vector envs
 since 1.0; `metadata["autoreset_mode"]` of the instance says so): the step that ends an episode returns that episode's last frame,
@@ -37,9 +41,10 @@ class MiniWorldVectorEnv(VectorEnvBase):
     """A gymnasium.vector.VectorEnv when gymnasium is importable (a plain class with the same surface otherwise)."""
     metadata = {"autoreset_mode": AUTORESET_SAME_STEP, "render_modes": ["rgb_array"]}
 
-    def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", **kwargs):
+    def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
+                 **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
-        are accepted too."""
+        are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring)."""
         mode = str(getattr(autoreset_mode, "name", autoreset_mode)).lower().replace("_", "-")     # (an AutoresetMode: its name)
         if mode not in ("same-step", "next-step"):
             raise ValueError(f"autoreset_mode must be 'same-step' or 'next-step', not {autoreset_mode!r}")
@@ -48,6 +53,10 @@ class MiniWorldVectorEnv(VectorEnvBase):
                 raise ValueError("autoreset_mode='next-step' and autoreset= exclude each other")
             kwargs["autoreset"] = "next_step"
             self.metadata = dict(type(self).metadata, autoreset_mode=AUTORESET_NEXT_STEP)
+        if final_obs and mode != "same-step":
+            raise ValueError("final_obs=True needs autoreset_mode='same-step' (next-step returns the terminal frame itself)")
+        if final_obs:
+            kwargs["final_obs"] = True
         self.vec = MiniWorldVecEnv(env_id, num_envs, **kwargs)
         self.num_envs = num_envs
         self.to_numpy = to_numpy
@@ -81,9 +90,12 @@ class MiniWorldVectorEnv(VectorEnvBase):
         if self.vec.autoreset_mode == "same_step":
             # gymnasium's same-step convention: "_final_info" masks the envs whose episode ended with this step (every family); the
             # finished episodes' own info under "final_info" where the family has info keys — clones, the engine's buffers are
-            # rewritten by the next step.  (No "final_obs": see the module's docstring.)
+            # rewritten by the next step.  ("final_obs" with final_obs=True: see the module's docstring.)
             done = self._out((term | trunc).bool())
             info["_final_info"] = done
+            if self.vec.final_obs is not None:
+                info["final_obs"] = self._out(self.vec.final_obs) if self.to_numpy else self.vec.final_obs.clone()
+                info["_final_obs"] = done
             if info.keys() - {"_final_info"}:
                 final = {k: (self._out(v) if self.to_numpy else v.clone()) for k, v in self.vec.final_infos().items()}
                 final.update({"_" + k: done for k in list(final)})
