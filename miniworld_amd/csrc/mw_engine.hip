@@ -18,14 +18,14 @@
 #include "mw_device.h"
 #include "mw_rng.h"
 
-extern "C" __global__ void mw_step_setup_kernel(MwArgs a, int do_step, int view_flags, const int32_t *actions,
+extern "C" __global__ void mw_step_setup_kernel(MwArgs a, int lanes_per_env, const int32_t *actions,
                                                 float *reward, uint8_t *term, uint8_t *trunc);
-extern "C" __global__ void mw_step_setup_pcg_kernel(MwArgs a, int do_step, int view_flags, const int32_t *actions,
+extern "C" __global__ void mw_step_setup_pcg_kernel(MwArgs a, int lanes_per_env, const int32_t *actions,
                                                     float *reward, uint8_t *term, uint8_t *trunc);
 extern "C" __global__ void mw_reset_pcg_kernel(MwArgs a, const uint8_t *mask, int force_all, int mark_refill);
-extern "C" __global__ void mw_step_setup_dense_kernel(MwArgs a, int do_step, int lanes_per_env, const int32_t *actions,
+extern "C" __global__ void mw_step_setup_dense_kernel(MwArgs a, int lanes_per_env, const int32_t *actions,
                                                        float *reward, uint8_t *term, uint8_t *trunc);
-extern "C" __global__ void mw_step_setup_dense_pcg_kernel(MwArgs a, int do_step, int lanes_per_env, const int32_t *actions,
+extern "C" __global__ void mw_step_setup_dense_pcg_kernel(MwArgs a, int lanes_per_env, const int32_t *actions,
                                                            float *reward, uint8_t *term, uint8_t *trunc);
 extern "C" __global__ void mw_geom_kernel(MwArgs a, int view_flags, int S, int L, int n_env);
 extern "C" __global__ void mw_geom_any_kernel(MwArgs a, int view_flags, int S, int L, int n_env);
@@ -307,13 +307,14 @@ int dev_alloc(mw_engine *e, T **out, size_t count, bool zero = true)
     return MW_OK;
 }
 
-// K1 for the engine's random stream (the device code is compiled once per stream, mw_rng.h)
-auto k1_of(const mw_engine *e) -> decltype(&mw_step_setup_kernel)
+// K1 for the engine's random stream (the device code is compiled once per stream, mw_rng.h): the dense form for
+// lanes = k1_dense_lanes(e) > 0, the wave-per-env form otherwise
+auto k1_of(const mw_engine *e, int lanes) -> decltype(&mw_step_setup_kernel)
 {
-    return e->cfg.rng_mode == MW_RNG_PCG64 ? mw_step_setup_pcg_kernel : mw_step_setup_kernel;
+    const bool pcg = e->cfg.rng_mode == MW_RNG_PCG64;
+    if (lanes) return pcg ? mw_step_setup_dense_pcg_kernel : mw_step_setup_dense_kernel;
+    return pcg ? mw_step_setup_pcg_kernel : mw_step_setup_kernel;
 }
-
-int k1_threads(const mw_engine *) { return 64; }
 
 // the geometry kernel: big scenes (one env per wavefront) or small, 8 samples per pixel (compiled in) or any
 auto geom_kernel_of(const mw_engine *e, int L, int msaa) -> void (*)(MwArgs, int, int, int, int)
@@ -373,9 +374,9 @@ int geom_lanes(const mw_engine *e)
 
 // Lanes per env of the dense K1 (mw_setup_dense.hip), or 0 when the step has to go through the wave-per-env kernel: big
 // scenes, CollectHealth, or too many slots to pack two envs into a wavefront.
-int k1_dense_lanes(const mw_engine *e, int view_flags)
+int k1_dense_lanes(const mw_engine *e)
 {
-    if (e->args.rec_order || view_flags != 0 || e->cfg.task == MW_TASK_COLLECT) return 0;
+    if (e->args.rec_order || e->cfg.task == MW_TASK_COLLECT) return 0;
     // at least two envs per wavefront: with one, every lane repeats the env's scalar work for nothing and the wave-per-env
     // kernel's lane-cooperative collision tests win (PickupObjects, 35 slots: 62 us dense against 47 us)
     const int lanes = e->cfg.max_polys + 6 * e->cfg.max_ents;
@@ -811,19 +812,9 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
     const int32_t *list = e->d_final_list;
     MwArgs ak = a;          // the step kernel's arguments: the first pass of a final-observation step runs as a next-step terminal step
     if (frame == FRAME_TERMINAL) ak.autoreset = MW_AUTORESET_NEXT_STEP;
-    if (!do_step) {
-        // render only: nothing to step
-    } else if (const int lanes = k1_dense_lanes(e, 0)) {
-        const int epw = 64 / lanes;
-        const bool pcg = e->cfg.rng_mode == MW_RNG_PCG64;
-        auto k1d = pcg ? mw_step_setup_dense_pcg_kernel : mw_step_setup_dense_kernel;
-        // spare mode: blocks appended to the grid regenerate the spare worlds consumed in earlier steps (64 envs each)
-        const int refill = (e->spare_mode && do_step) ? (N + 63) / 64 : 0;
-        hipLaunchKernelGGL(k1d, dim3((N + epw - 1) / epw + refill), dim3(64), 0, st, ak, do_step ? 1 : 0, lanes, d_actions,
-                           d_reward ? d_reward : e->d_reward_scratch, d_term ? d_term : e->d_flag_scratch,
-                           d_trunc ? d_trunc : e->d_flag_scratch + N);
-    } else {
-        hipLaunchKernelGGL(k1_of(e), dim3(N + refill_blocks), dim3(k1_threads(e)), 0, st, ak, do_step ? 1 : 0, view_flags, d_actions,
+    if (do_step) {      // (a render-only frame has nothing to step)
+        const int lanes = k1_dense_lanes(e), epw = lanes ? 64 / lanes : 1;      // envs per workgroup
+        hipLaunchKernelGGL(k1_of(e, lanes), dim3((N + epw - 1) / epw + refill_blocks), dim3(64), 0, st, ak, lanes, d_actions,
                            d_reward ? d_reward : e->d_reward_scratch, d_term ? d_term : e->d_flag_scratch,
                            d_trunc ? d_trunc : e->d_flag_scratch + N);
     }

@@ -851,35 +851,42 @@ __device__ inline void refill_spares(const MwArgs &a, int r, int tid, unsigned c
     if (lane == 0) atomicExch(a.refill_mask + env, 0u);
 }
 
-// The next world of an env whose episode ended, installed by one workgroup of ONE wavefront (lane 0 writes; s_claim: an int
-// in LDS): the generator in place, or in spare mode the claim of the env's spare under the refill_mask protocol (mw_device.h).
-// The install site of the wave-per-env K1 (mw_setup.hip) and of the final-observation step's second pass (mw_reset.hip).
+// The next world of an env whose episode ended: the generator in place, or in spare mode the claim of the env's spare under the
+// refill_mask protocol (mw_device.h).  The install site of both K1 forms (mw_setup_common.h: step_env) and of the final-observation
+// step's second pass (mw_reset.hip).
+// PER_LANE = false: one workgroup of ONE wavefront installs it; lane 0 writes, s_claim is an int in LDS.
+// PER_LANE = true: the env's leading lane alone (the dense K1: a wavefront holds several envs), lane = 0, the claim in a register.
+template <bool PER_LANE>
 __device__ inline void install_next_world(const MwArgs &a, int env, int lane, unsigned char *gen_ws, int *s_claim)
 {
-    const bool writer = lane == 0;
+    const bool writer = PER_LANE || lane == 0;
     if (a.spare) {
         // the next world was generated ahead (by a refill block of an earlier launch): claim it
-        if (writer) *s_claim = (int)atomicCAS(a.refill_mask + env, 1u, 3u);
-        __syncthreads();
+        int old = 0;
+        if (writer) old = (int)atomicCAS(a.refill_mask + env, 1u, 3u);
+        if (!PER_LANE) {
+            if (writer) *s_claim = old;
+            __syncthreads();
+        }
         __threadfence();        // acquire: the spare's contents (written by another block, released with its state) are read behind the claim
-        const int old = *s_claim;
+        if (!PER_LANE) old = *s_claim;
         if (old == 1) {
             // the previous episode lasted one step and the refill has not run yet: generate in place
             generate_world(*a.gen_live, env, gen_ws, lane);
         } else {
             if (old == 2) {     // a refill block (of this very launch, or the Maze's refill kernel on the side stream) is on it
                 if (writer) while (__hip_atomic_load(a.refill_mask + env, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u) __builtin_amdgcn_s_sleep(16);
-                __syncthreads();
+                if (!PER_LANE) __syncthreads();
             }
-            take_spare(a, env, lane);
+            if (PER_LANE) take_spare_lane(a, env); else take_spare(a, env, lane);
         }
         __threadfence();
-        __syncthreads();
+        if (!PER_LANE) __syncthreads();
         if (writer) atomicExch(a.refill_mask + env, 1u);        // the spare is missing again
     } else {
         generate_world(*a.gen_live, env, gen_ws, lane);
     }
-    __syncthreads();
+    if (!PER_LANE) __syncthreads();
 }
 
 }  // namespace mw

@@ -57,7 +57,7 @@ extern "C" __global__ __launch_bounds__(64) void MW_INSTALL_KERNEL_NAME(MwArgs a
     __shared__ int s_claim;
     if ((int)blockIdx.x >= list[0]) return;
     const int env = list[1 + blockIdx.x], lane = (int)threadIdx.x;
-    mw::install_next_world(a, env, lane, gen_ws, &s_claim);
+    mw::install_next_world<false>(a, env, lane, gen_ws, &s_claim);
     if (lane == 0) {
         a.pending_remove[env] = -1;
         a.reset_pending[env] = 0;
