@@ -96,10 +96,13 @@ typedef struct {
     int32_t abi_version;        /* MW_ABI_VERSION */
     int32_t device_id;
     int32_t num_envs;
-    int32_t obs_width, obs_height;  /* MiniWorldEnv(obs_width=80, obs_height=60) miniworld.py:473-474 */
+    int32_t obs_width, obs_height;  /* MiniWorldEnv(obs_width=80, obs_height=60) miniworld.py:473-474: any size from 1 x 1 to
+                                     * 4080 x 1020.  Frames that are not multiples of the 16 x 4 raster tile (84 x 84,
+                                     * 81 x 61, ...) take the ragged tile kernels or the generic-resolution kernels
+                                     * (mw_raster_path)                                                               */
     int32_t msaa;               /* FrameBuffer(..., num_samples=8) miniworld.py:515.  8 = the hot path; 4 or 1 = what the
                                  * reference falls back to on a driver that clamps GL_MAX_SAMPLES (opengl.py:229-231):
-                                 * same semantics through the generic-resolution kernels, plain HWC layout only       */
+                                 * same semantics through the generic-resolution kernels, every obs layout            */
     int32_t max_ents;           /* entity slots per env, agent excluded            */
     int32_t max_polys;          /* room polygons per geometry set                  */
     int32_t max_segs;           /* collision segments per geometry set             */
@@ -353,7 +356,7 @@ int mw_render(mw_engine *e, uint8_t *d_obs, float *d_depth, void *stream);
  * kind of buffers; render_agent != 0 also draws Agent.render's marker (entity.py:518-539) */
 int mw_render_top(mw_engine *e, uint8_t *d_obs, float *d_depth, int32_t render_agent, void *stream);
 /* render() / render_obs(vis_fb) / render_top_view(vis_fb) (miniworld.py:1340-1362): ONE env into a frame
- * buffer of any size (multiples of 16 x 4) with msaa = 1, 4, 8 or 16 samples (vis_fb = FrameBuffer(800, 600, 16),
+ * buffer of any size (1 x 1 to 4080 x 1020) with msaa = 1, 4, 8 or 16 samples (vis_fb = FrameBuffer(800, 600, 16),
  * miniworld.py:518).  view_flags: bit 0 top view, bit 1 draw the agent marker.
  *   d_out uint8[height][width][3], d_depth float[height][width] or NULL.  Not the hot path. */
 int mw_render_view(mw_engine *e, int32_t env, int32_t view_flags, int32_t width, int32_t height, int32_t msaa,
@@ -379,7 +382,9 @@ int mw_kernel_time_ms(mw_engine *e, int32_t reset, double *raster_ms, double *se
  * which code its fixtures exercised: MW_PATH_QUAD the quad kernel (mw_rasterq.hip: small scenes, 8 or 4 samples),
  * MW_PATH_QUAD_MESH the same for every tile no mesh entity can touch + the mesh-aware tile kernel for the others,
  * MW_PATH_TILE the tile kernels (mw_raster.hip: big scenes, MW_K2Q=0), MW_PATH_GENERIC the generic-resolution kernels
- * (other sample counts, frames beyond 128 x 96 pixels (W H > 12 288: the tile kernels' 32-bit edge sums), MW_GENERIC_RASTER=1); -1 before the first frame. */
+ * (other sample counts, frames beyond 128 x 96 pixels (W H > 12 288: the tile kernels' 32-bit edge sums), frames off the 16 x 4 grid
+ * other than the ragged tile kernels' (8 samples, even H, no meshes), MW_GENERIC_RASTER=1); -1 before the first frame.  Frames off
+ * the grid that the tile kernels draw report MW_PATH_TILE. */
 /* The `info` dict of the envs' step() as device arrays, asynchronous on `stream` (either pointer may be NULL):
  *   d_health  int32[N]     CollectHealth: info["health"] (collecthealth.py:100)
  *   d_ent_pos double[N][3] position of entity slot `ent_slot`: TMaze / YMaze info["goal_pos"] = box.pos (tmaze.py:89, ymaze.py:125)

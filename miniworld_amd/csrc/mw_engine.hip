@@ -56,6 +56,8 @@ MW_RASTER_DECL(mw_raster_nomesh_depth_kernel);
 MW_RASTER_DECL(mw_raster_mesh_depth_kernel);
 MW_RASTER_DECL(mw_raster_mesh_wrap_kernel);
 MW_RASTER_DECL(mw_raster_big_mesh_wrap_kernel);
+MW_RASTER_DECL(mw_raster_ragged_kernel);
+MW_RASTER_DECL(mw_raster_big_ragged_kernel);
 // ... the same over the envs of a list (mw_raster.hip: MW_RASTER_SUB)
 #undef MW_RASTER_DECL_TAIL
 #define MW_RASTER_DECL_TAIL , const int32_t *list
@@ -71,6 +73,8 @@ MW_RASTER_DECL(mw_raster_nomesh_depth_sub_kernel);
 MW_RASTER_DECL(mw_raster_mesh_depth_sub_kernel);
 MW_RASTER_DECL(mw_raster_mesh_wrap_sub_kernel);
 MW_RASTER_DECL(mw_raster_big_mesh_wrap_sub_kernel);
+MW_RASTER_DECL(mw_raster_ragged_sub_kernel);
+MW_RASTER_DECL(mw_raster_big_ragged_sub_kernel);
 #define MW_RASTERQ_DECL(name) \
     extern "C" __global__ void name(int N, int W, int H, int max_vis, int tiles_x, int n_tiles, const float *rec_raster, const float *rec_shade, \
                                     const float *rec_cull, const int32_t *nvis, const float *envhdr, const uint32_t *texels, uint8_t *obs, \
@@ -108,11 +112,13 @@ extern "C" __global__ void mw_view_mesh_sub_kernel(int W, int H, int S, int firs
                                     const float *rec_shade, const float *rec_cull, const int32_t *nvis, const float *envhdr, \
                                     const MwTexDesc *texd, const uint32_t *texels, const float *mesh_pos, \
                                     const float *mesh_nrm, const float *mesh_rgb, const float *mesh_uv, const uint32_t *mesh_keys, \
-                                    uint8_t *out, float *depth, int texel_bytes MW_RASTER_DECL_TAIL)
+                                    uint8_t *out, float *depth, int texel_bytes, int layout MW_RASTER_DECL_TAIL)
 MW_VIEW_RASTER_DECL(mw_view_raster_sub_kernel);
+MW_VIEW_RASTER_DECL(mw_view_raster_any_sub_kernel);
 #undef MW_RASTER_DECL_TAIL
 #define MW_RASTER_DECL_TAIL
 MW_VIEW_RASTER_DECL(mw_view_raster_kernel);
+MW_VIEW_RASTER_DECL(mw_view_raster_any_kernel);      // frames off the 16 x 4 grid, wrapper layouts
 extern "C" __global__ void mw_final_install_kernel(MwArgs a, const int32_t *list);
 extern "C" __global__ void mw_final_install_pcg_kernel(MwArgs a, const int32_t *list);
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *rec_raster, const float *rec_cull,
@@ -343,6 +349,7 @@ auto raster_sub_of(decltype(&mw_raster_kernel) k) -> decltype(&mw_raster_sub_ker
         {mw_raster_mesh_kernel, mw_raster_mesh_sub_kernel}, {mw_raster_nomesh_kernel, mw_raster_nomesh_sub_kernel},
         {mw_raster_nomesh_depth_kernel, mw_raster_nomesh_depth_sub_kernel}, {mw_raster_mesh_depth_kernel, mw_raster_mesh_depth_sub_kernel},
         {mw_raster_mesh_wrap_kernel, mw_raster_mesh_wrap_sub_kernel}, {mw_raster_big_mesh_wrap_kernel, mw_raster_big_mesh_wrap_sub_kernel},
+        {mw_raster_ragged_kernel, mw_raster_ragged_sub_kernel}, {mw_raster_big_ragged_kernel, mw_raster_big_ragged_sub_kernel},
     };
     for (const auto &m : map) if (m.first == k) return m.second;
     return nullptr;
@@ -352,6 +359,21 @@ auto raster_sub_of(decltype(&mw_raster_kernel) k) -> decltype(&mw_raster_sub_ker
 // 2^31, i.e. W H < 16384 — 128 x 96 passes, 128 x 128 does not (a wall across the whole frame lost its triangle there);
 // larger frames take the generic-resolution kernels (64-bit edge values).
 bool tile_kernels_exact(int W, int H) { return W <= 128 && H <= 128 && W * H <= 128 * 96; }
+
+// The frame is W x H, the size the caller asked for: the viewport, the projection and every output stride.  The raster grid is
+// the frame rounded up to whole 16 x 4 tiles, ceil16(W) x ceil4(H): tiles_x, tiles_y, n_tiles.  A frame that is not the grid
+// ("ragged": padding pixels right of column W - 1 or below row H - 1) takes, at 8 samples without mesh entities, with an even H
+// and a grid inside the tile kernels' edge bound, the ragged tile kernels (mw_raster.hip, FMT -2: padding masked, per-pixel stores); any
+// other ragged frame the generic-resolution kernels, which mask the padding per pixel too.  The quad kernel and the fixed-layout
+// tile kernels take frames on the grid only ("Frame sizes").
+bool frame_on_grid(int W, int H) { return W % MW_TILE_W == 0 && H % MW_TILE_H == 0; }
+bool tile_path_ok(int W, int H) { return frame_on_grid(W, H) && tile_kernels_exact(W, H); }
+// sizes mw_create and mw_render_view accept: at least one pixel, at most 255 tiles of grid in each direction (8-bit tile
+// coordinates of the records' bounding boxes)
+bool frame_size_ok(int W, int H)
+{
+    return W >= 1 && H >= 1 && W <= 255 * MW_TILE_W && H <= 255 * MW_TILE_H;
+}
 
 // lanes per env of the geometry kernel: the power of two that holds an env's triangles (two per polygon and box face, the
 // agent marker), 8 .. 64 — except that the smallest scenes get 16 lanes for their up to 32 triangles: an env's lanes go over
@@ -709,7 +731,7 @@ int ensure_mesh_buffers(mw_engine *e)
     const MwArgs &a = e->args;
     const size_t N = (size_t)e->cfg.num_envs;
     if (ensure_mesh_stream(e) != MW_OK) return MW_E_HIP;
-    if (e->cfg.msaa != 8 || !tile_kernels_exact(a.W, a.H)) {       // the generic-resolution path
+    if (e->cfg.msaa != 8 || !tile_path_ok(a.W, a.H)) {       // the generic-resolution path
         const size_t need = N * a.W * a.H * e->cfg.msaa * 4;
         if (need > e->view_keys_bytes) {
             uint32_t *nk = nullptr;
@@ -722,7 +744,7 @@ int ensure_mesh_buffers(mw_engine *e)
     }
     if (a.W > 255 * MW_TILE_W || a.H > 255 * MW_TILE_H) return fail(e, MW_E_CAPACITY, "frame too large for the mesh tile rectangles");
     // the mesh tiles' work list (mw_geom.hip): a tile index in the 8 bits above the env, and one bit of a lane's 32-bit mask per tile
-    // sub + k L.  tile_kernels_exact caps these frames at 192 tiles and the geometry kernel has at least 8 lanes per env, so this holds
+    // sub + k L.  tile_path_ok caps these frames at 192 tiles and the geometry kernel has at least 8 lanes per env, so this holds
     // today; a larger frame limit or fewer lanes must not leave mesh tiles undrawn (and their sample keys uncleared) in silence
     if (a.n_tiles > 255 || a.n_tiles > 32 * geom_lanes(e))
         return fail(e, MW_E_CAPACITY, "%d tiles per frame: the mesh tiles' work list holds 255 (8-bit tile index) and 32 per lane of the geometry kernel (%d lanes)", a.n_tiles, geom_lanes(e));
@@ -768,6 +790,16 @@ int ensure_mesh_buffers(mw_engine *e)
     return MW_OK;
 }
 
+// a ragged frame the ragged tile kernels draw: 8 samples, no mesh entities, a grid inside the tile kernels' edge bound, and an
+// even H — the tile kernels' 2x2 quads (texture lod) pair image rows from the top, GL pairs window rows from the bottom
+// (mw_frag.h): the two agree only when H is even.  Odd heights take the generic-resolution kernels.
+bool ragged_tiles_ok(const mw_engine *e)
+{
+    const MwArgs &a = e->args;
+    return e->cfg.msaa == 8 && !e->have_meshes && !frame_on_grid(a.W, a.H) && a.H % 2 == 0 &&
+           tile_kernels_exact(a.tiles_x * MW_TILE_W, a.tiles_y * MW_TILE_H);
+}
+
 // The frames of a same-step step with final observations (mw_step): FRAME_TERMINAL — the step kernel runs as the next-step mode's
 // terminal step (no install; reset_pending marks the finished envs), the list of those envs is built behind it, and the frame
 // shows every env's state after the step (terminal states for the finished envs); FRAME_LIST — no step, the frame of the listed
@@ -778,15 +810,12 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
                  float *d_reward, uint8_t *d_term, uint8_t *d_trunc, hipStream_t st, int frame = FRAME_ALL)
 {
     if (!d_obs) return fail(e, MW_E_INVALID, "d_obs is null");
-    // (checked before anything is launched or any timing event is taken)
-    if ((e->cfg.msaa != 8 || !tile_kernels_exact(e->cfg.obs_width, e->cfg.obs_height)) && e->obs_layout != MW_OBS_HWC_U8)
-        return fail(e, MW_E_INVALID, "wrapper layouts need msaa = 8 and observations up to 128 x 96");
     MwArgs a = e->args;
     a.step_override = e->use_step_override ? e->d_step_override : nullptr;
     const int N = e->cfg.num_envs;
     // a frame with mesh entities through the tile / quad kernels: the geometry kernel lists the entities in view for the mesh
     // entity kernel (lists, slow-path lists and fragment stamps alternate between two sets from frame to frame)
-    const bool mesh_obs = e->have_meshes && e->cfg.msaa == 8 && tile_kernels_exact(a.W, a.H) && e->d_ent_list && e->d_mesh_keys;
+    const bool mesh_obs = e->have_meshes && e->cfg.msaa == 8 && tile_path_ok(a.W, a.H) && e->d_ent_list && e->d_mesh_keys;
     const uint32_t mesh_seq = mesh_obs ? e->mesh_frame_seq++ : 0u;
     if (mesh_obs) {
         a.ent_list = e->d_ent_list; a.ent_list_n = e->d_ent_counter + (mesh_seq & 1u) * MW_CNT_WORDS; a.ent_list_cap = e->ent_list_cap;
@@ -861,11 +890,11 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
     if (k2q && e->cfg.msaa == 4) {
         launch_k2q(0, st);
         e->last_raster_path = MW_PATH_QUAD;
-    } else if (e->cfg.msaa != 8 || !tile_kernels_exact(a.W, a.H)) {
+    } else if (e->cfg.msaa != 8 || (!tile_path_ok(a.W, a.H) && !ragged_tiles_ok(e))) {
         // FrameBuffer's fallback sample counts (opengl.py:229-231: a driver that clamps GL_MAX_SAMPLES gets 4 or 1
-        // samples) and observations beyond 128 x 128 (the tile kernels' 24-bit edge arithmetic): not the hot path — the
-        // generic-resolution kernels, 64-bit edge values, exact packed-key resolution, the whole batch in one grid
-        // (blockIdx.y = env)
+        // samples), observations beyond 128 x 128 (the tile kernels' 24-bit edge arithmetic) and frames off the 16 x 4 grid:
+        // the generic-resolution kernels, 64-bit edge values, exact packed-key resolution, every output layout, the whole
+        // batch in one grid (blockIdx.y = env)
         const int S = e->cfg.msaa;
         uint32_t *keys = nullptr;
         if (e->have_meshes) {
@@ -879,14 +908,17 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
                 hipLaunchKernelGGL(mw_view_mesh_kernel, dim3(32, N), dim3(256), 0, st, a.W, a.H, S, 0, (const float *)a.envhdr, a.mesh_pos, keys);
         }
         e->last_raster_path = MW_PATH_GENERIC;
+        const bool any = !frame_on_grid(a.W, a.H) || e->obs_layout != MW_OBS_HWC_U8;
         if (frame == FRAME_LIST)
-            hipLaunchKernelGGL(mw_view_raster_sub_kernel, dim3(a.n_tiles, N), dim3(64), 0, st, 0, a.W, a.H, S, a.max_vis, a.tiles_x,
+            hipLaunchKernelGGL(any ? mw_view_raster_any_sub_kernel : mw_view_raster_sub_kernel, dim3(a.n_tiles, N), dim3(64), 0, st, 0, a.W, a.H, S, a.max_vis, a.tiles_x,
                                (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull, (const int32_t *)a.nvis, (const float *)a.envhdr,
-                               a.tex, a.texels, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, (const uint32_t *)keys, d_obs, d_depth, e->texel_bytes, list);
+                               a.tex, a.texels, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, (const uint32_t *)keys, d_obs, d_depth, e->texel_bytes,
+                               e->obs_layout, list);
         else
-            hipLaunchKernelGGL(mw_view_raster_kernel, dim3(a.n_tiles, N), dim3(64), 0, st, 0, a.W, a.H, S, a.max_vis, a.tiles_x,
+            hipLaunchKernelGGL(any ? mw_view_raster_any_kernel : mw_view_raster_kernel, dim3(a.n_tiles, N), dim3(64), 0, st, 0, a.W, a.H, S, a.max_vis, a.tiles_x,
                                (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull, (const int32_t *)a.nvis, (const float *)a.envhdr,
-                               a.tex, a.texels, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, (const uint32_t *)keys, d_obs, d_depth, e->texel_bytes);
+                               a.tex, a.texels, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, (const uint32_t *)keys, d_obs, d_depth, e->texel_bytes,
+                               e->obs_layout);
     } else {
         const bool mesh = e->have_meshes;
         uint32_t mesh_stamp = 0u;
@@ -936,6 +968,7 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
         const bool general = e->obs_layout != MW_OBS_HWC_U8 || e->dbg_flags != 0;
         auto k2 = big ? (d_depth ? mw_raster_big_depth_kernel : mw_raster_big_kernel) : (d_depth ? mw_raster_depth_kernel : mw_raster_kernel);
         if (general) k2 = big ? mw_raster_big_wrap_kernel : mw_raster_wrap_kernel;
+        if (!frame_on_grid(a.W, a.H)) k2 = big ? mw_raster_big_ragged_kernel : mw_raster_ragged_kernel;     // (no meshes: ragged_tiles_ok)
         if (mesh) {
             k2 = big ? mw_raster_big_mesh_wrap_kernel : (d_depth ? mw_raster_mesh_depth_kernel : mw_raster_mesh_kernel);
             if (general && !big) k2 = mw_raster_mesh_wrap_kernel;
@@ -1011,8 +1044,8 @@ int mw_create(const mw_config *cfg, mw_engine **out)
         return fail(nullptr, MW_E_INVALID, "MW_RNG_PCG64 (the reference's own numpy stream) needs a device generator");
     if (cfg->max_ents > 64) return fail(nullptr, MW_E_CAPACITY, "max_ents > 64 (one entity slot per lane of the env's wavefront)");
     if (cfg->msaa != 8 && cfg->msaa != 4 && cfg->msaa != 1) return fail(nullptr, MW_E_INVALID, "msaa must be 8, 4 or 1");
-    if (cfg->obs_width % MW_TILE_W || cfg->obs_height % MW_TILE_H || cfg->obs_width > 255 * MW_TILE_W || cfg->obs_height > 255 * MW_TILE_H)
-        return fail(nullptr, MW_E_INVALID, "obs size must be a multiple of %dx%d", MW_TILE_W, MW_TILE_H);
+    if (!frame_size_ok(cfg->obs_width, cfg->obs_height))
+        return fail(nullptr, MW_E_INVALID, "obs size %dx%d: 1 to %d x 1 to %d pixels", cfg->obs_width, cfg->obs_height, 255 * MW_TILE_W, 255 * MW_TILE_H);
     if (cfg->max_visible > 60000) return fail(nullptr, MW_E_CAPACITY, "max_visible too large (16-bit draw ids)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, MW_E_DEVICE, "no HIP device available");
@@ -1036,7 +1069,7 @@ int mw_create(const mw_config *cfg, mw_engine **out)
     a.occlusion = 1;
     if (const char *s = getenv("MW_OCCLUSION")) a.occlusion = atoi(s) != 0;
     a.domain_rand = cfg->domain_rand; a.generator = cfg->generator; a.autoreset = cfg->autoreset;
-    a.tiles_x = a.W / MW_TILE_W; a.tiles_y = a.H / MW_TILE_H; a.n_tiles = a.tiles_x * a.tiles_y;
+    a.tiles_x = (a.W + MW_TILE_W - 1) / MW_TILE_W; a.tiles_y = (a.H + MW_TILE_H - 1) / MW_TILE_H; a.n_tiles = a.tiles_x * a.tiles_y;    // the raster grid
     a.agent_radius = cfg->agent_radius; a.max_forward_step = cfg->max_forward_step;
     a.agent_height = cfg->agent_height > 0.0 ? cfg->agent_height : 1.6;
     a.fwd = cfg->forward_step; a.drift = cfg->forward_drift; a.turn = cfg->turn_step;
@@ -1178,7 +1211,7 @@ int mw_create(const mw_config *cfg, mw_engine **out)
         // the quad kernel (mw_rasterq.hip) keeps an env's frame, quad lists and triangle records in LDS: frames up to 8192 pixels
         const int S = cfg->msaa == 4 ? 4 : 8;
         const int lds = mw_rasterq_lds_bytes(S, a.W, a.H, a.n_tiles, 1);
-        e->k2q_ok = (cfg->msaa == 8 || cfg->msaa == 4) && a.W <= 128 && a.H <= 128 && a.W * a.H <= 8192 && lds <= 64 * 1024;
+        e->k2q_ok = (cfg->msaa == 8 || cfg->msaa == 4) && frame_on_grid(a.W, a.H) && a.W <= 128 && a.H <= 128 && a.W * a.H <= 8192 && lds <= 64 * 1024;
     }
     if (sync_gen_args(e) != MW_OK) { g_create_error = e->err; mw_destroy(e); return MW_E_HIP; }
     *out = e;
@@ -1625,13 +1658,13 @@ int mw_render_view(mw_engine *e, int32_t env, int32_t view_flags, int32_t width,
     ON_DEVICE(e);
     if (env < 0 || env >= e->cfg.num_envs) return fail(e, MW_E_INVALID, "env %d out of range", env);
     if (msaa != 1 && msaa != 4 && msaa != 8 && msaa != 16) return fail(e, MW_E_INVALID, "msaa must be 1, 4, 8 or 16");
-    if (width <= 0 || height <= 0 || width % MW_TILE_W || height % MW_TILE_H || width > 255 * MW_TILE_W || height > 255 * MW_TILE_H)
-        return fail(e, MW_E_INVALID, "frame buffer size must be a multiple of %dx%d", MW_TILE_W, MW_TILE_H);
+    if (!frame_size_ok(width, height))
+        return fail(e, MW_E_INVALID, "frame buffer size %dx%d: 1 to %d x 1 to %d pixels", width, height, 255 * MW_TILE_W, 255 * MW_TILE_H);
     hipStream_t st = (hipStream_t)stream;
     MwArgs b = e->args;
     b.step_override = nullptr;
     b.W = width; b.H = height;
-    b.tiles_x = width / MW_TILE_W; b.tiles_y = height / MW_TILE_H; b.n_tiles = b.tiles_x * b.tiles_y;
+    b.tiles_x = (width + MW_TILE_W - 1) / MW_TILE_W; b.tiles_y = (height + MW_TILE_H - 1) / MW_TILE_H; b.n_tiles = b.tiles_x * b.tiles_y;
     b.env_base = env;
     hipLaunchKernelGGL(geom_kernel_of(e, 64, msaa), dim3(1), dim3(64), 0, st, b, view_flags, msaa, 64, 1);
     uint32_t *keys = nullptr;
@@ -1648,9 +1681,10 @@ int mw_render_view(mw_engine *e, int32_t env, int32_t view_flags, int32_t width,
         HIP_TRY(e, hipMemsetAsync(keys, 0xFF, need, st));
         hipLaunchKernelGGL(mw_view_mesh_kernel, dim3(128), dim3(256), 0, st, width, height, msaa, env, (const float *)b.envhdr, b.mesh_pos, keys);
     }
-    hipLaunchKernelGGL(mw_view_raster_kernel, dim3(b.n_tiles), dim3(64), 0, st, env, width, height, msaa, b.max_vis, b.tiles_x,
+    hipLaunchKernelGGL(frame_on_grid(width, height) ? mw_view_raster_kernel : mw_view_raster_any_kernel, dim3(b.n_tiles), dim3(64), 0, st, env, width, height, msaa, b.max_vis, b.tiles_x,
                        (const float *)b.rec_raster, (const float *)b.rec_shade, (const float *)b.rec_cull, (const int32_t *)b.nvis, (const float *)b.envhdr,
-                       b.tex, b.texels, b.mesh_pos, b.mesh_nrm, b.mesh_rgb, b.mesh_uv, (const uint32_t *)keys, d_out, d_depth, e->texel_bytes);
+                       b.tex, b.texels, b.mesh_pos, b.mesh_nrm, b.mesh_rgb, b.mesh_uv, (const uint32_t *)keys, d_out, d_depth, e->texel_bytes,
+                       MW_OBS_HWC_U8);
     HIP_TRY(e, hipGetLastError());
     return MW_OK;
 }

@@ -267,6 +267,17 @@ extern "C" __global__ __launch_bounds__(64) void mw_raster_big_wrap_kernel(MW_RA
     raster_kernel_body<false, -1>(MW_RASTER_FWD);
 }
 
+// frames off the 16 x 4 grid (FMT -2, mw_raster_common.h): padding lanes masked, per-pixel stores in every layout; small / big scenes
+extern "C" __global__ __launch_bounds__(64) void mw_raster_ragged_kernel(MW_RASTER_ARGS)
+{
+    raster_kernel_body<true, -2>(MW_RASTER_FWD);
+}
+
+extern "C" __global__ __launch_bounds__(64) void mw_raster_big_ragged_kernel(MW_RASTER_ARGS)
+{
+    raster_kernel_body<false, -2>(MW_RASTER_FWD);
+}
+
 #ifndef MW_MESH_TILE_OCC
 #define MW_MESH_TILE_OCC 4
 #endif
@@ -296,6 +307,8 @@ MW_RASTER_SUB(mw_raster_mesh_sub_kernel, __launch_bounds__(64, MW_MESH_TILE_OCC)
 MW_RASTER_SUB(mw_raster_mesh_depth_sub_kernel, __launch_bounds__(64, MW_MESH_TILE_OCC), true, 0, 2, 1)
 MW_RASTER_SUB(mw_raster_mesh_wrap_sub_kernel, __launch_bounds__(64), true, -1, 0, 1)
 MW_RASTER_SUB(mw_raster_big_mesh_wrap_sub_kernel, __launch_bounds__(64), false, -1, 0, 1)
+MW_RASTER_SUB(mw_raster_ragged_sub_kernel, __launch_bounds__(64), true, -2, 0, 0)
+MW_RASTER_SUB(mw_raster_big_ragged_sub_kernel, __launch_bounds__(64), false, -2, 0, 0)
 
 #ifdef MW_PERF_HOOKS
 // tools/perf/k2prof.py: read (and zero) this translation unit's phase counters

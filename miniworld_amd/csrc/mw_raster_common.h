@@ -413,7 +413,10 @@ __device__ inline int mesh_entry_of(const TileCtx &cx, uint32_t id, int &rec)
     return -1;
 }
 
-// FMT: output layout fixed at compile time (0: the plain observation) or -1: read from the launch flags.
+// FMT: output layout fixed at compile time (0: the plain observation) or -1: read from the launch flags; -2: the same for a
+// frame off the 16 x 4 grid ("ragged": W or H not a multiple of the tile, mw_engine.hip).  The tiles cover the grid
+// ceil16(W) x ceil4(H); the lanes of padding pixels (px >= W, or py >= H: GL rows below 0) have their coverage masked and store
+// nothing, and the real pixels store byte by byte (a 48-byte tile row would straddle output rows, and rows start at any address).
 // SORTED: the env's triangles come with a visiting order by ascending depth bound (big scenes).
 // HOT: 0 = everything read from the launch (debug flags, depth or not); 1 / 2 = production instantiations RGB / RGB + depth.
 // PRE: 1 = the tile's classification masks come from classify_group (at most 32 triangles), 0 = classified here, -1 = cx.have_pre decides
@@ -436,6 +439,9 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
     const int gy = H - 1 - py;                              // GL row (the frame buffer's y points up, the image's down)
     const int pxlo = tx * MW_TILE_W, pxhi = pxlo + MW_TILE_W - 1;
     const int gyhi = H - 1 - ty * MW_TILE_H, gylo = gyhi - (MW_TILE_H - 1);
+    constexpr bool RAGGED = FMT == -2;
+    const bool real = !RAGGED || (px < W && py < H);
+    const uint64_t real_m = RAGGED ? __ballot(real) : ~0ull;
     RGB out = {0.0f, 0.0f, 0.0f};
     uint32_t z16 = 65535u;
 
@@ -480,6 +486,10 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
                     if (anycov_m) { exact = true; break; }
                     covbits = 0xFFu;
                     anycov_m = ~0ull;
+                    if (RAGGED) {
+#pragma unroll
+                        for (int s = 0; s < 8; ++s) in_m[s] = real_m;
+                    }
                 } else {
                     const int *__restrict__ rr = reinterpret_cast<const int *>(rr_env + (size_t)p * MW_RASTER_REC);
 #pragma unroll
@@ -489,6 +499,10 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
                         if (__all(E > rr[13 + k])) continue;        // tile strictly inside edge k
 #pragma unroll
                         for (int s = 0; s < 8; ++s) in_m[s] &= __ballot(E > rr[16 + k * 16 + s]);
+                    }
+                    if (RAGGED) {
+#pragma unroll
+                        for (int s = 0; s < 8; ++s) in_m[s] &= real_m;
                     }
                     uint64_t any_m = 0ull;
 #pragma unroll
@@ -576,6 +590,10 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
                     if (__all(E > rr[13 + k])) continue;
 #pragma unroll
                     for (int s = 0; s < 8; ++s) in_m[s] &= __ballot(E > rr[16 + k * 16 + s]);
+                }
+                if (RAGGED) {
+#pragma unroll
+                    for (int s = 0; s < 8; ++s) in_m[s] &= real_m;
                 }
                 uint64_t any_m = 0ull;
 #pragma unroll
@@ -677,7 +695,19 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
     //   1  uint8 [3][W][H]      PyTorchObsWrapper: observation.transpose(2, 1, 0)   (wrappers.py:24)
     //   2  double[H][W][1]      GreyscaleWrapper: 0.30 R + 0.59 G + 0.11 B in numpy's float64 (wrappers.py:44)
     const int fmt = FMT >= 0 ? FMT : ((dbg >> 8) & 3);
-    if (fmt == 2) {
+    if (RAGGED) {
+        if (real) {
+            if (fmt == 2) {
+                reinterpret_cast<double *>(obs)[((size_t)env * H + py) * W + px] = (0.30 * (double)R + 0.59 * (double)G) + 0.11 * (double)B;
+            } else if (fmt == 0) {
+                uint8_t *dst = obs + (((size_t)env * H + py) * W + px) * 3;
+                dst[0] = (uint8_t)R; dst[1] = (uint8_t)G; dst[2] = (uint8_t)B;
+            } else {
+                uint8_t *dst = obs + ((size_t)env * 3 * W + px) * H + py;
+                dst[0] = (uint8_t)R; dst[(size_t)W * H] = (uint8_t)G; dst[(size_t)2 * W * H] = (uint8_t)B;
+            }
+        }
+    } else if (fmt == 2) {
         const double g = (0.30 * (double)R + 0.59 * (double)G) + 0.11 * (double)B;
         reinterpret_cast<double *>(obs)[((size_t)env * H + py) * W + px] = g;
     } else {
@@ -708,7 +738,7 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         __builtin_amdgcn_wave_barrier();
     }
-    if (has_depth) {
+    if (has_depth && real) {
         // resolved depth = sample 0; get_depth_map in float32 as numpy evaluates it (opengl.py:426-431)
         const float z = (float)z16;
         const float d = z / 65535.0f;

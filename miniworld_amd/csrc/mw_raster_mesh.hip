@@ -440,7 +440,7 @@ extern "C" __global__ __launch_bounds__(256) MW_NO_TAIL_MARKS void mw_view_mesh_
 }
 #endif
 
-#ifdef MW_VIEW_LIST_UNIT
+#if defined(MW_VIEW_LIST_UNIT) && !defined(MW_VIEW_ANY_UNIT)
 extern "C" __global__ __launch_bounds__(256) MW_NO_TAIL_MARKS void mw_view_mesh_sub_kernel(int W, int H, int S, int first_env, const float *__restrict__ envhdr,
                                                                          const float *__restrict__ mesh_pos, uint32_t *keys, const int32_t *__restrict__ list)
 {
@@ -448,17 +448,23 @@ extern "C" __global__ __launch_bounds__(256) MW_NO_TAIL_MARKS void mw_view_mesh_
 }
 #endif
 
-template <int S>
-__device__ inline void view_tile_body(TileCtx &cx, int tiles_x, const uint32_t *mesh_keys)
+// The tiles cover the raster grid, ceil16(W) x ceil4(H); a frame of any other size has padding pixels right of column W - 1 and
+// below row H - 1 (GL rows below 0).  They take part in the wavefront's loops, but nothing covers them (mesh keys included) and
+// they store nothing.  ANY: frames off the grid and the wrapper layouts (mw_view_raster_any_kernel); without it the frame is on the grid
+// and the layout HWC, and the code is the plain kernel's of old (the padding and layout tests cost 800 x 600 views ~5 %).
+template <int S, bool ANY>
+__device__ inline void view_tile_body(TileCtx &cx, int tiles_x, const uint32_t *mesh_keys, int layout)
 {
     const int lane = cx.lane, W = cx.W, H = cx.H, nvis = cx.nvis;
     const int tile = blockIdx.x;
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int px = tx * MW_TILE_W + (lane & 15), py = ty * MW_TILE_H + (lane >> 4);
     const int gy = H - 1 - py;
+    const bool inside = !ANY || (px < W && py < H);
+    if (!ANY) layout = 0;
     uint32_t key[S];
 #pragma unroll
-    for (int s = 0; s < S; ++s) key[s] = mesh_keys ? mesh_keys[((size_t)py * W + px) * S + s] : 0xFFFFFFFFu;
+    for (int s = 0; s < S; ++s) key[s] = mesh_keys && inside ? mesh_keys[((size_t)py * W + px) * S + s] : 0xFFFFFFFFu;
     for (int p = 0; p < nvis; ++p) {
         const int *__restrict__ rr = reinterpret_cast<const int *>(cx.rr_env + (size_t)p * MW_RASTER_REC);
         const float4 *cr = cx.s_cull + (size_t)p * (MW_CULL_REC / 4);
@@ -477,7 +483,7 @@ __device__ inline void view_tile_body(TileCtx &cx, int tiles_x, const uint32_t *
         const uint32_t id = (uint32_t)rr[9];
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            const bool in = E[0] > (int64_t)rr[16 + s] && E[1] > (int64_t)rr[32 + s] && E[2] > (int64_t)rr[48 + s];
+            const bool in = inside && E[0] > (int64_t)rr[16 + s] && E[1] > (int64_t)rr[32 + s] && E[2] > (int64_t)rr[48 + s];
             const float xs = (float)px + samp_fx<S>(s), ys = (float)gy + samp_fy<S>(s);
             const uint32_t k = (mwgl::z_to_unorm16(mwgl::plane_at(zp, xs, ys)) << 16) | id;
             key[s] = in ? min(key[s], k) : key[s];
@@ -500,11 +506,27 @@ __device__ inline void view_tile_body(TileCtx &cx, int tiles_x, const uint32_t *
         if (s == 0) acc = last;
         else { acc.r = acc.r + last.r; acc.g = acc.g + last.g; acc.b = acc.b + last.b; }
     }
+    if (!inside) return;
     const float inv = 1.0f / (float)S;
     const float v[3] = {acc.r * inv, acc.g * inv, acc.b * inv};
-    uint8_t *dst = cx.obs + ((size_t)py * W + px) * 3;
+    // Output layouts (mw_set_obs_layout; the reference's wrappers.py folded into the store), byte and qword stores only, so
+    // any base address works:
+    //   0  uint8 [H][W][3]      the observation itself
+    //   1  uint8 [3][W][H]      PyTorchObsWrapper: observation.transpose(2, 1, 0)   (wrappers.py:24)
+    //   2  double[H][W][1]      GreyscaleWrapper: 0.30 R + 0.59 G + 0.11 B in numpy's float64 (wrappers.py:44)
+    uint32_t u8[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) dst[c] = (uint8_t)mwgl::float_to_unorm8(v[c]);
+    for (int c = 0; c < 3; ++c) u8[c] = mwgl::float_to_unorm8(v[c]);
+    if (layout == 2) {
+        reinterpret_cast<double *>(cx.obs)[(size_t)py * W + px] = (0.30 * (double)u8[0] + 0.59 * (double)u8[1]) + 0.11 * (double)u8[2];
+    } else if (layout == 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) cx.obs[((size_t)c * W + px) * H + py] = (uint8_t)u8[c];
+    } else {
+        uint8_t *dst = cx.obs + ((size_t)py * W + px) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dst[c] = (uint8_t)u8[c];
+    }
     if (cx.depth) {
         const float z = (float)z16;
         const float d = z / 65535.0f;
@@ -514,24 +536,24 @@ __device__ inline void view_tile_body(TileCtx &cx, int tiles_x, const uint32_t *
     }
 }
 
-// grid (n_tiles, count): blockIdx.y = env first_env + y of the batch; its frame at out + y * H * W * 3, its mesh keys
+// grid (n_tiles, count): blockIdx.y = env first_env + y of the batch; its frame at out + y * H * W * 3 (* 8: layout 2), its mesh keys
 // at mesh_keys + y * W * H * S.  SUB (first_env = 0, the whole batch's buffers): y draws env list[1 + y] while y < list[0].
 #define MW_VIEW_RASTER_ARGS \
     int first_env, int W, int H, int S, int max_vis, int tiles_x, const float *__restrict__ rec_raster, \
     const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, \
     const MwTexDesc *__restrict__ texd, const uint32_t *__restrict__ texels, const float *__restrict__ mesh_pos, \
     const float *__restrict__ mesh_nrm, const float *__restrict__ mesh_rgb, const float *__restrict__ mesh_uv, const uint32_t *mesh_keys, \
-    uint8_t *__restrict__ out, float *__restrict__ depth, int texel_bytes
+    uint8_t *__restrict__ out, float *__restrict__ depth, int texel_bytes, int layout
 #define MW_VIEW_RASTER_FWD first_env, W, H, S, max_vis, tiles_x, rec_raster, rec_shade, rec_cull, nvis_arr, envhdr, texd, texels, mesh_pos, \
-    mesh_nrm, mesh_rgb, mesh_uv, mesh_keys, out, depth, texel_bytes
-template <bool SUB>
+    mesh_nrm, mesh_rgb, mesh_uv, mesh_keys, out, depth, texel_bytes, layout
+template <bool SUB, bool ANY>
 __device__ __attribute__((always_inline)) inline void view_raster_kernel_body(MW_VIEW_RASTER_ARGS, const int32_t *__restrict__ list)
 {
     __shared__ mwgl::Vert s_clip[MW_CLIP_TURN * 2 * MWGL_MAX_CLIP_VERTS];
     if (SUB && (int)blockIdx.y >= list[0]) return;
     const unsigned y = SUB ? (unsigned)list[1 + blockIdx.y] : blockIdx.y;
     const int env = first_env + (int)y;
-    out += (size_t)y * H * W * 3;
+    out += (size_t)y * H * W * (ANY && layout == 2 ? 8 : 3);
     if (depth) depth += (size_t)y * H * W;
     if (mesh_keys) mesh_keys += (size_t)y * W * H * S;
     const float *hdr = envhdr + (size_t)env * MW_ENVHDR;
@@ -552,23 +574,35 @@ __device__ __attribute__((always_inline)) inline void view_raster_kernel_body(MW
     cx.env = 0; cx.nvis = nvis_arr[env]; cx.W = W; cx.H = H; cx.dbg = 0; cx.lane = threadIdx.x; cx.have_pre = 0; cx.order = nullptr;
     cx.planes = nullptr; cx.planes_xtra = nullptr; cx.clipbuf = s_clip; cx.slow_frags = nullptr; cx.slow_head = nullptr; cx.slow_stamp = 0u;
     cx.pre_touch = cx.pre_full = cx.pre_clip = cx.pre_edges = 0ull;
-    if (S == 16) view_tile_body<16>(cx, tiles_x, mesh_keys);
-    else if (S == 4) view_tile_body<4>(cx, tiles_x, mesh_keys);
-    else if (S == 1) view_tile_body<1>(cx, tiles_x, mesh_keys);
-    else view_tile_body<8>(cx, tiles_x, mesh_keys);
+    if (S == 16) view_tile_body<16, ANY>(cx, tiles_x, mesh_keys, layout);
+    else if (S == 4) view_tile_body<4, ANY>(cx, tiles_x, mesh_keys, layout);
+    else if (S == 1) view_tile_body<1, ANY>(cx, tiles_x, mesh_keys, layout);
+    else view_tile_body<8, ANY>(cx, tiles_x, mesh_keys, layout);
 }
 
 #ifndef MW_VIEW_LIST_UNIT      // (the list forms of the generic-resolution kernels: mw_raster_view_list.hip)
 extern "C" __global__ __launch_bounds__(64) MW_NO_TAIL_MARKS void mw_view_raster_kernel(MW_VIEW_RASTER_ARGS)
 {
-    view_raster_kernel_body<false>(MW_VIEW_RASTER_FWD, nullptr);
+    view_raster_kernel_body<false, false>(MW_VIEW_RASTER_FWD, nullptr);
 }
 #endif
 
-#ifdef MW_VIEW_LIST_UNIT
+#if defined(MW_VIEW_LIST_UNIT) && !defined(MW_VIEW_ANY_UNIT)
 extern "C" __global__ __launch_bounds__(64) MW_NO_TAIL_MARKS void mw_view_raster_sub_kernel(MW_VIEW_RASTER_ARGS, const int32_t *__restrict__ list)
 {
-    view_raster_kernel_body<true>(MW_VIEW_RASTER_FWD, list);
+    view_raster_kernel_body<true, false>(MW_VIEW_RASTER_FWD, list);
+}
+#endif
+
+#ifdef MW_VIEW_ANY_UNIT     // (frames off the grid and wrapper layouts: mw_raster_view_any.hip)
+extern "C" __global__ __launch_bounds__(64) MW_NO_TAIL_MARKS void mw_view_raster_any_kernel(MW_VIEW_RASTER_ARGS)
+{
+    view_raster_kernel_body<false, true>(MW_VIEW_RASTER_FWD, nullptr);
+}
+
+extern "C" __global__ __launch_bounds__(64) MW_NO_TAIL_MARKS void mw_view_raster_any_sub_kernel(MW_VIEW_RASTER_ARGS, const int32_t *__restrict__ list)
+{
+    view_raster_kernel_body<true, true>(MW_VIEW_RASTER_FWD, list);
 }
 #endif
 
