@@ -26,6 +26,7 @@
 #include <cstddef>
 #include "mw_setup_common.h"
 #include "mw_records.h"
+#include "mw_kernels.h"
 
 namespace {
 
@@ -1303,16 +1304,15 @@ __device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L,
 #ifndef MW_GEOM_OCC
 #define MW_GEOM_OCC
 #endif
-extern "C" __global__ __launch_bounds__(64) MW_GEOM_OCC void mw_geom_kernel(MwArgs a, int view_flags, int S, int L, int n_env) { geom_body<false, 8>(a, view_flags, S, L, n_env); }
-extern "C" __global__ __launch_bounds__(64) MW_GEOM_OCC void mw_geom_big_kernel(MwArgs a, int view_flags, int S, int L, int n_env) { geom_body<true, 8>(a, view_flags, S, L, n_env); }
+// each kernel and its list form over the envs of a list (int32 [0] count, [1 + i] env; n_env unused)
+#define MW_GEOM_PAIR(stem, bounds, ...)                                                                                        \
+    extern "C" __global__ bounds void stem##_kernel(MW_GEOM_ARGS) { geom_body<__VA_ARGS__, false>(a, view_flags, S, L, n_env); } \
+    extern "C" __global__ bounds void stem##_sub_kernel(MW_GEOM_ARGS, const int32_t *list) { geom_body<__VA_ARGS__, true>(a, view_flags, S, L, n_env, list); }
+MW_GEOM_PAIR(mw_geom, __launch_bounds__(64) MW_GEOM_OCC, false, 8)
+MW_GEOM_PAIR(mw_geom_big, __launch_bounds__(64) MW_GEOM_OCC, true, 8)
 // ... for frame buffers with 1, 4 or 16 samples per pixel
-extern "C" __global__ __launch_bounds__(64) void mw_geom_any_kernel(MwArgs a, int view_flags, int S, int L, int n_env) { geom_body<false, 0>(a, view_flags, S, L, n_env); }
-extern "C" __global__ __launch_bounds__(64) void mw_geom_big_any_kernel(MwArgs a, int view_flags, int S, int L, int n_env) { geom_body<true, 0>(a, view_flags, S, L, n_env); }
-// ... the same four over the envs of a list (int32 [0] count, [1 + i] env; n_env unused)
-extern "C" __global__ __launch_bounds__(64) MW_GEOM_OCC void mw_geom_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list) { geom_body<false, 8, true>(a, view_flags, S, L, n_env, list); }
-extern "C" __global__ __launch_bounds__(64) MW_GEOM_OCC void mw_geom_big_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list) { geom_body<true, 8, true>(a, view_flags, S, L, n_env, list); }
-extern "C" __global__ __launch_bounds__(64) void mw_geom_any_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list) { geom_body<false, 0, true>(a, view_flags, S, L, n_env, list); }
-extern "C" __global__ __launch_bounds__(64) void mw_geom_big_any_sub_kernel(MwArgs a, int view_flags, int S, int L, int n_env, const int32_t *list) { geom_body<true, 0, true>(a, view_flags, S, L, n_env, list); }
+MW_GEOM_PAIR(mw_geom_any, __launch_bounds__(64), false, 0)
+MW_GEOM_PAIR(mw_geom_big_any, __launch_bounds__(64), true, 0)
 
 // mw_selftest_sort: the visiting order's sort on keys of the caller's (tests/test_gpu_numerics.py): block b sorts the
 // n[b] <= 512 keys at keys + 512 b into order + 513 b (order[0] unused, then the keys' low halves in ascending key order)

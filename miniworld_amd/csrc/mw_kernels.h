@@ -1,0 +1,105 @@
+// The kernel interface: every kernel the host runtime (mw_engine.hip) launches, declared once.  The engine includes this header to
+// launch them and every translation unit that defines one includes it too, so a definition that drifts from its declaration does
+// not compile.
+#pragma once
+#include "mw_device.h"
+
+// a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
+// whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine.hip)
+#define MW_KERNEL_PAIR(stem, ...)                          \
+    extern "C" __global__ void stem##_kernel(__VA_ARGS__); \
+    extern "C" __global__ void stem##_sub_kernel(__VA_ARGS__, const int32_t *list)
+
+// K1, the step (mw_setup.hip: wave per env; mw_setup_dense.hip: several envs per wavefront), per random stream (the *_pcg units)
+#define MW_K1_ARGS MwArgs a, int lanes_per_env, const int32_t *__restrict__ actions, float *__restrict__ reward, \
+                   uint8_t *__restrict__ term, uint8_t *__restrict__ trunc
+extern "C" __global__ void mw_step_setup_kernel(MW_K1_ARGS);
+extern "C" __global__ void mw_step_setup_pcg_kernel(MW_K1_ARGS);
+extern "C" __global__ void mw_step_setup_dense_kernel(MW_K1_ARGS);
+extern "C" __global__ void mw_step_setup_dense_pcg_kernel(MW_K1_ARGS);
+
+// reset, spare refill, CollectHealth respawn, same-step install, spare take-over (mw_reset.hip, mw_reset_pcg.hip)
+extern "C" __global__ void mw_reset_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all, int mark_refill);
+extern "C" __global__ void mw_reset_pcg_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all, int mark_refill);
+extern "C" __global__ void mw_refill_kernel(MwArgs a);
+extern "C" __global__ void mw_refill_pcg_kernel(MwArgs a);
+extern "C" __global__ void mw_collect_respawn_kernel(MwArgs a);
+extern "C" __global__ void mw_collect_respawn_pcg_kernel(MwArgs a);
+extern "C" __global__ void mw_final_install_kernel(MwArgs a, const int32_t *__restrict__ list);
+extern "C" __global__ void mw_final_install_pcg_kernel(MwArgs a, const int32_t *__restrict__ list);
+extern "C" __global__ void mw_take_spare_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all);
+
+// the geometry kernel (mw_geom.hip): small / big scenes, 8 samples per pixel compiled in or any
+#define MW_GEOM_ARGS MwArgs a, int view_flags, int S, int L, int n_env
+MW_KERNEL_PAIR(mw_geom, MW_GEOM_ARGS);
+MW_KERNEL_PAIR(mw_geom_big, MW_GEOM_ARGS);
+MW_KERNEL_PAIR(mw_geom_any, MW_GEOM_ARGS);
+MW_KERNEL_PAIR(mw_geom_big_any, MW_GEOM_ARGS);
+
+// the tile kernels (mw_raster.hip)
+// (texd == texels: the descriptor table is the head of the texel block, mw_engine.hip::upload_textures; the kernels
+// use `texels` for both)
+#define MW_RASTER_ARGS \
+    int N, int W, int H, int max_vis, int tiles_x, int n_tiles, int waves_per_env, int tiles_per_wave, \
+    const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, \
+    const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const MwTexDesc *__restrict__ texd, \
+    const uint32_t *__restrict__ texels, uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, \
+    const uint16_t *__restrict__ rec_order, const float *__restrict__ mesh_pos, const float *__restrict__ mesh_nrm, \
+    const float *__restrict__ mesh_rgb, const float *__restrict__ mesh_uv, uint32_t *__restrict__ mesh_keys, \
+    const float *__restrict__ plane_cache, int plane_cap, const float4 *__restrict__ slow_frags, const uint32_t *__restrict__ slow_head, \
+    const uint32_t *__restrict__ tile_list, int32_t *__restrict__ tile_n, int tile_list_cap, int n_xcc
+MW_KERNEL_PAIR(mw_raster, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_depth, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_big, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_big_depth, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_wrap, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_big_wrap, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_ragged, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_big_ragged, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_nomesh, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_nomesh_depth, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_mesh, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_mesh_depth, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_mesh_wrap, MW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_raster_big_mesh_wrap, MW_RASTER_ARGS);
+
+// the quad kernel (mw_rasterq.hip): one workgroup of MWQ_THREADS lanes per env, 8 or 4 samples per pixel
+#define MWQ_THREADS 512
+#define MWQ_ARGS \
+    int N, int W, int H, int max_vis, int tiles_x, int n_tiles, \
+    const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, \
+    const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const uint32_t *__restrict__ texels, \
+    uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof
+MW_KERNEL_PAIR(mw_rasterq, MWQ_ARGS);
+MW_KERNEL_PAIR(mw_rasterq4, MWQ_ARGS);
+// bytes of dynamic LDS a launch needs; the longest display list the quad path draws (longer ones: the tile code)
+extern "C" int mw_rasterq_lds_bytes(int S, int W, int H, int n_tiles, int depth);
+extern "C" int mw_rasterq_cap(int depth);
+
+// the mesh entity and slow-path kernels, the XCD probe (mw_raster_mesh.hip)
+extern "C" __global__ void mw_mesh_entity_kernel(
+    int N, int W, int H, const float *__restrict__ envhdr, const MwMeshDesc *__restrict__ meshes, const float4 *__restrict__ mesh_vpos,
+    const uint2 *__restrict__ mesh_idx, const float *__restrict__ mesh_stream, const float *__restrict__ mesh_attr, uint32_t *__restrict__ keys_all,
+    float *__restrict__ plane_cache, int plane_cap, int32_t *__restrict__ slow_count, uint32_t *__restrict__ slow_tris, const uint32_t *__restrict__ ent_list,
+    int ent_list_cap, int32_t *ent_n, int32_t *ent_n_after, uint32_t *__restrict__ slow_envs, int n_xcc, unsigned long long *prof);
+extern "C" __global__ void mw_mesh_slow_kernel(int W, int H, const float *envhdr, const float *mesh_pos, const float *mesh_nrm, const float *mesh_rgb,
+                                               const float *mesh_uv, const uint32_t *texels, int texel_bytes, uint32_t *keys, int32_t *counts, int N,
+                                               int parity, const uint32_t *slow_tris, float4 *frags, uint32_t *heads, uint32_t stamp, uint32_t *status,
+                                               const uint32_t *slow_envs, const int32_t *slow_env_n);
+extern "C" __global__ void mw_xcc_probe_kernel(uint32_t *out);
+
+// the generic-resolution kernels (mw_raster_mesh.hip; the list forms in mw_raster_view_list.hip, the raster kernel for frames off
+// the grid and wrapper layouts in mw_raster_view_any.hip)
+MW_KERNEL_PAIR(mw_view_mesh, int W, int H, int S, int first_env, const float *__restrict__ envhdr, const float *__restrict__ mesh_pos, uint32_t *keys);
+#define MW_VIEW_RASTER_ARGS \
+    int first_env, int W, int H, int S, int max_vis, int tiles_x, const float *__restrict__ rec_raster, \
+    const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, \
+    const MwTexDesc *__restrict__ texd, const uint32_t *__restrict__ texels, const float *__restrict__ mesh_pos, \
+    const float *__restrict__ mesh_nrm, const float *__restrict__ mesh_rgb, const float *__restrict__ mesh_uv, const uint32_t *mesh_keys, \
+    uint8_t *__restrict__ out, float *__restrict__ depth, int texel_bytes, int layout
+MW_KERNEL_PAIR(mw_view_raster, MW_VIEW_RASTER_ARGS);
+MW_KERNEL_PAIR(mw_view_raster_any, MW_VIEW_RASTER_ARGS);
+
+// the occlusion queries of mw_visible_ents (mw_visible.hip)
+extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,
+                                             const float *__restrict__ rec_cull, const int32_t *__restrict__ nvis, uint8_t *__restrict__ vis);

@@ -18,6 +18,7 @@
 // and records are L2-resident.
 #include <cstring>
 #include "mw_mesh.h"
+#include "mw_kernels.h"
 
 // LDS_RECS = true : the env's shade / classification records are staged in LDS (small scenes);
 // LDS_RECS = false: they are read in place from global memory (L1/L2) — scenes with hundreds of
@@ -217,66 +218,29 @@ __device__ __attribute__((always_inline)) inline void raster_kernel_body(
     }
 }
 
-// (texd == texels: the descriptor table is the head of the texel block, mw_engine.hip::upload_textures; the kernels
-// use `texels` for both)
-#define MW_RASTER_ARGS \
-    int N, int W, int H, int max_vis, int tiles_x, int n_tiles, int waves_per_env, int tiles_per_wave, \
-    const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, \
-    const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const MwTexDesc *__restrict__ texd, \
-    const uint32_t *__restrict__ texels, uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, \
-    const uint16_t *__restrict__ rec_order, const float *__restrict__ mesh_pos, const float *__restrict__ mesh_nrm, \
-    const float *__restrict__ mesh_rgb, const float *__restrict__ mesh_uv, uint32_t *__restrict__ mesh_keys, \
-    const float *__restrict__ plane_cache, int plane_cap, const float4 *__restrict__ slow_frags, const uint32_t *__restrict__ slow_head, \
-    const uint32_t *__restrict__ tile_list, int32_t *__restrict__ tile_n, int tile_list_cap, int n_xcc
 #define MW_RASTER_FWD N, W, H, max_vis, tiles_x, n_tiles, waves_per_env, tiles_per_wave, rec_raster, rec_shade, rec_cull, \
     nvis_arr, envhdr, texd, texels, obs, depth, dbg, texel_bytes, rec_order, mesh_pos, mesh_nrm, mesh_rgb, mesh_uv, mesh_keys, plane_cache, plane_cap, slow_frags, slow_head, tile_list, tile_n, tile_list_cap, n_xcc
+// each kernel and its list form over the envs of a list (int32 [0] count, [1 + i] env): the second pass of a same-step auto-reset
+// step with final observations (mw_engine.hip)
+#define MW_RASTER_PAIR(stem, bounds, ...)                                                                                           \
+    extern "C" __global__ bounds void stem##_kernel(MW_RASTER_ARGS) { raster_kernel_body<__VA_ARGS__, false>(MW_RASTER_FWD); } \
+    extern "C" __global__ bounds void stem##_sub_kernel(MW_RASTER_ARGS, const int32_t *__restrict__ list) { raster_kernel_body<__VA_ARGS__, true>(MW_RASTER_FWD, list); }
 
 // the production kernels of small scenes: no debug flags (mw_engine.hip launches the general kernel below when
 // MW_DEBUG_FLAGS asks for any), RGB only / RGB + depth
-extern "C" __global__ __launch_bounds__(64) void mw_raster_kernel(MW_RASTER_ARGS)
-{
-    raster_kernel_body<true, 0, 1>(MW_RASTER_FWD);
-}
-
-extern "C" __global__ __launch_bounds__(64) void mw_raster_depth_kernel(MW_RASTER_ARGS)
-{
-    raster_kernel_body<true, 0, 2>(MW_RASTER_FWD);
-}
-
+MW_RASTER_PAIR(mw_raster, __launch_bounds__(64), true, 0, 1, 0)
+MW_RASTER_PAIR(mw_raster_depth, __launch_bounds__(64), true, 0, 2, 0)
 #ifndef MW_K2BIG_OCC
 #define MW_K2BIG_OCC
 #endif
-extern "C" __global__ __launch_bounds__(64) MW_K2BIG_OCC void mw_raster_big_kernel(MW_RASTER_ARGS)
-{
-    raster_kernel_body<false, 0, 1>(MW_RASTER_FWD);
-}
-
-extern "C" __global__ __launch_bounds__(64) void mw_raster_big_depth_kernel(MW_RASTER_ARGS)
-{
-    raster_kernel_body<false, 0, 2>(MW_RASTER_FWD);
-}
-
+MW_RASTER_PAIR(mw_raster_big, __launch_bounds__(64) MW_K2BIG_OCC, false, 0, 1, 0)
+MW_RASTER_PAIR(mw_raster_big_depth, __launch_bounds__(64), false, 0, 2, 0)
 // the general kernels: output layout (mw_set_obs_layout; dbg bits 8-9), debug flags and depth read from the launch
-extern "C" __global__ __launch_bounds__(64) void mw_raster_wrap_kernel(MW_RASTER_ARGS)
-{
-    raster_kernel_body<true, -1>(MW_RASTER_FWD);
-}
-
-extern "C" __global__ __launch_bounds__(64) void mw_raster_big_wrap_kernel(MW_RASTER_ARGS)
-{
-    raster_kernel_body<false, -1>(MW_RASTER_FWD);
-}
-
+MW_RASTER_PAIR(mw_raster_wrap, __launch_bounds__(64), true, -1, 0, 0)
+MW_RASTER_PAIR(mw_raster_big_wrap, __launch_bounds__(64), false, -1, 0, 0)
 // frames off the 16 x 4 grid (FMT -2, mw_raster_common.h): padding lanes masked, per-pixel stores in every layout; small / big scenes
-extern "C" __global__ __launch_bounds__(64) void mw_raster_ragged_kernel(MW_RASTER_ARGS)
-{
-    raster_kernel_body<true, -2>(MW_RASTER_FWD);
-}
-
-extern "C" __global__ __launch_bounds__(64) void mw_raster_big_ragged_kernel(MW_RASTER_ARGS)
-{
-    raster_kernel_body<false, -2>(MW_RASTER_FWD);
-}
+MW_RASTER_PAIR(mw_raster_ragged, __launch_bounds__(64), true, -2, 0, 0)
+MW_RASTER_PAIR(mw_raster_big_ragged, __launch_bounds__(64), false, -2, 0, 0)
 
 #ifndef MW_MESH_TILE_OCC
 #define MW_MESH_TILE_OCC 4
@@ -284,31 +248,12 @@ extern "C" __global__ __launch_bounds__(64) void mw_raster_big_ragged_kernel(MW_
 // the same for envs that may hold mesh entities (PickupObjects, Sign, CollectHealth, ...)
 // ... the tiles no mesh can touch, of envs that hold mesh entities (K2's first part, beside the mesh kernels): the plain tile code,
 // at the plain kernels' register count
-extern "C" __global__ __launch_bounds__(64) void mw_raster_nomesh_kernel(MW_RASTER_ARGS) { raster_kernel_body<true, 0, 1, 2>(MW_RASTER_FWD); }
-extern "C" __global__ __launch_bounds__(64) void mw_raster_nomesh_depth_kernel(MW_RASTER_ARGS) { raster_kernel_body<true, 0, 2, 2>(MW_RASTER_FWD); }
-extern "C" __global__ __launch_bounds__(64, MW_MESH_TILE_OCC) void mw_raster_mesh_kernel(MW_RASTER_ARGS) { raster_kernel_body<true, 0, 1, 1>(MW_RASTER_FWD); }
-extern "C" __global__ __launch_bounds__(64, MW_MESH_TILE_OCC) void mw_raster_mesh_depth_kernel(MW_RASTER_ARGS) { raster_kernel_body<true, 0, 2, 1>(MW_RASTER_FWD); }
-extern "C" __global__ __launch_bounds__(64) void mw_raster_mesh_wrap_kernel(MW_RASTER_ARGS) { raster_kernel_body<true, -1, 0, 1>(MW_RASTER_FWD); }
-extern "C" __global__ __launch_bounds__(64) void mw_raster_big_mesh_wrap_kernel(MW_RASTER_ARGS) { raster_kernel_body<false, -1, 0, 1>(MW_RASTER_FWD); }
-
-// ... each of them over the envs of a list (int32 [0] count, [1 + i] env): the second pass of a same-step auto-reset step with
-// final observations (mw_engine.hip)
-#define MW_RASTER_SUB(name, occ, ...) \
-    extern "C" __global__ occ void name(MW_RASTER_ARGS, const int32_t *__restrict__ list) { raster_kernel_body<__VA_ARGS__, true>(MW_RASTER_FWD, list); }
-MW_RASTER_SUB(mw_raster_sub_kernel, __launch_bounds__(64), true, 0, 1, 0)
-MW_RASTER_SUB(mw_raster_depth_sub_kernel, __launch_bounds__(64), true, 0, 2, 0)
-MW_RASTER_SUB(mw_raster_big_sub_kernel, __launch_bounds__(64) MW_K2BIG_OCC, false, 0, 1, 0)
-MW_RASTER_SUB(mw_raster_big_depth_sub_kernel, __launch_bounds__(64), false, 0, 2, 0)
-MW_RASTER_SUB(mw_raster_wrap_sub_kernel, __launch_bounds__(64), true, -1, 0, 0)
-MW_RASTER_SUB(mw_raster_big_wrap_sub_kernel, __launch_bounds__(64), false, -1, 0, 0)
-MW_RASTER_SUB(mw_raster_nomesh_sub_kernel, __launch_bounds__(64), true, 0, 1, 2)
-MW_RASTER_SUB(mw_raster_nomesh_depth_sub_kernel, __launch_bounds__(64), true, 0, 2, 2)
-MW_RASTER_SUB(mw_raster_mesh_sub_kernel, __launch_bounds__(64, MW_MESH_TILE_OCC), true, 0, 1, 1)
-MW_RASTER_SUB(mw_raster_mesh_depth_sub_kernel, __launch_bounds__(64, MW_MESH_TILE_OCC), true, 0, 2, 1)
-MW_RASTER_SUB(mw_raster_mesh_wrap_sub_kernel, __launch_bounds__(64), true, -1, 0, 1)
-MW_RASTER_SUB(mw_raster_big_mesh_wrap_sub_kernel, __launch_bounds__(64), false, -1, 0, 1)
-MW_RASTER_SUB(mw_raster_ragged_sub_kernel, __launch_bounds__(64), true, -2, 0, 0)
-MW_RASTER_SUB(mw_raster_big_ragged_sub_kernel, __launch_bounds__(64), false, -2, 0, 0)
+MW_RASTER_PAIR(mw_raster_nomesh, __launch_bounds__(64), true, 0, 1, 2)
+MW_RASTER_PAIR(mw_raster_nomesh_depth, __launch_bounds__(64), true, 0, 2, 2)
+MW_RASTER_PAIR(mw_raster_mesh, __launch_bounds__(64, MW_MESH_TILE_OCC), true, 0, 1, 1)
+MW_RASTER_PAIR(mw_raster_mesh_depth, __launch_bounds__(64, MW_MESH_TILE_OCC), true, 0, 2, 1)
+MW_RASTER_PAIR(mw_raster_mesh_wrap, __launch_bounds__(64), true, -1, 0, 1)
+MW_RASTER_PAIR(mw_raster_big_mesh_wrap, __launch_bounds__(64), false, -1, 0, 1)
 
 #ifdef MW_PERF_HOOKS
 // tools/perf/k2prof.py: read (and zero) this translation unit's phase counters

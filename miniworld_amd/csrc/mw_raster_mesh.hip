@@ -1,6 +1,7 @@
 // The mesh entity kernel (mesh triangles -> sample keys + attribute planes of the winners), the kernel of the triangles that
 // cross a frustum plane, and the generic-resolution view kernels.  See mw_mesh.h.
 #include "mw_mesh.h"
+#include "mw_kernels.h"
 
 // HW_REG_XCC_ID of 256 workgroups: which XCDs does this device show (mw_create)
 #ifndef MW_VIEW_LIST_UNIT      // (the list forms of the generic-resolution kernels: mw_raster_view_list.hip)
@@ -538,12 +539,6 @@ __device__ inline void view_tile_body(TileCtx &cx, int tiles_x, const uint32_t *
 
 // grid (n_tiles, count): blockIdx.y = env first_env + y of the batch; its frame at out + y * H * W * 3 (* 8: layout 2), its mesh keys
 // at mesh_keys + y * W * H * S.  SUB (first_env = 0, the whole batch's buffers): y draws env list[1 + y] while y < list[0].
-#define MW_VIEW_RASTER_ARGS \
-    int first_env, int W, int H, int S, int max_vis, int tiles_x, const float *__restrict__ rec_raster, \
-    const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, \
-    const MwTexDesc *__restrict__ texd, const uint32_t *__restrict__ texels, const float *__restrict__ mesh_pos, \
-    const float *__restrict__ mesh_nrm, const float *__restrict__ mesh_rgb, const float *__restrict__ mesh_uv, const uint32_t *mesh_keys, \
-    uint8_t *__restrict__ out, float *__restrict__ depth, int texel_bytes, int layout
 #define MW_VIEW_RASTER_FWD first_env, W, H, S, max_vis, tiles_x, rec_raster, rec_shade, rec_cull, nvis_arr, envhdr, texd, texels, mesh_pos, \
     mesh_nrm, mesh_rgb, mesh_uv, mesh_keys, out, depth, texel_bytes, layout
 template <bool SUB, bool ANY>

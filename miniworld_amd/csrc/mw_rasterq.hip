@@ -26,8 +26,8 @@
 // disjoint, the exact path is an unsigned minimum.  Instantiated for 8 samples (the hot path) and for 4 (llvmpipe's
 // GL_MAX_SAMPLES, opengl.py:229-231: the reference's own frames in tests/golden/gl_*.npz run through this very code).
 #include "mw_mesh.h"
+#include "mw_kernels.h"
 
-#define MWQ_THREADS 512
 #define MWQ_WAVES (MWQ_THREADS / 64)
 #define MWQ_CAP_MAX 48        // triangle records staged per env: 48, or 40 with a depth channel (three workgroups per CU either way)
 #define MWQ_SLOTS 16          // triangles listed per tile
@@ -975,18 +975,13 @@ __device__ inline void rasterq_body(
 
 }  // namespace
 
-#define MWQ_ARGS \
-    int N, int W, int H, int max_vis, int tiles_x, int n_tiles, \
-    const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, \
-    const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const uint32_t *__restrict__ texels, \
-    uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof
 #define MWQ_FWD N, W, H, max_vis, tiles_x, n_tiles, rec_raster, rec_shade, rec_cull, nvis_arr, envhdr, texels, obs, depth, dbg, texel_bytes, prof
-
-extern "C" __global__ __launch_bounds__(MWQ_THREADS, MWQ_OCC) void mw_rasterq_kernel(MWQ_ARGS) { rasterq_body<8>(MWQ_FWD); }
-extern "C" __global__ __launch_bounds__(MWQ_THREADS) void mw_rasterq4_kernel(MWQ_ARGS) { rasterq_body<4>(MWQ_FWD); }
-// ... over the envs of a list (int32 [0] count, [1 + i] env)
-extern "C" __global__ __launch_bounds__(MWQ_THREADS, MWQ_OCC) void mw_rasterq_sub_kernel(MWQ_ARGS, const int32_t *__restrict__ list) { rasterq_body<8, true>(MWQ_FWD, list); }
-extern "C" __global__ __launch_bounds__(MWQ_THREADS) void mw_rasterq4_sub_kernel(MWQ_ARGS, const int32_t *__restrict__ list) { rasterq_body<4, true>(MWQ_FWD, list); }
+// each kernel and its list form over the envs of a list (int32 [0] count, [1 + i] env)
+#define MWQ_PAIR(stem, bounds, ...)                                                                          \
+    extern "C" __global__ bounds void stem##_kernel(MWQ_ARGS) { rasterq_body<__VA_ARGS__, false>(MWQ_FWD); } \
+    extern "C" __global__ bounds void stem##_sub_kernel(MWQ_ARGS, const int32_t *__restrict__ list) { rasterq_body<__VA_ARGS__, true>(MWQ_FWD, list); }
+MWQ_PAIR(mw_rasterq, __launch_bounds__(MWQ_THREADS, MWQ_OCC), 8)
+MWQ_PAIR(mw_rasterq4, __launch_bounds__(MWQ_THREADS), 4)
 
 // bytes of dynamic LDS a launch needs (mw_engine.hip)
 extern "C" int mw_rasterq_lds_bytes(int S, int W, int H, int n_tiles, int depth) { return q_plan(S, W, H, n_tiles, depth != 0).total; }

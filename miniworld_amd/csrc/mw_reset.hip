@@ -1,6 +1,7 @@
 // mw_reset_kernel — batched MiniWorldEnv.reset (miniworld.py:544-604): one thread per env, or one wavefront per
 // env for the Maze generator (its 127 rooms are emitted one per lane; grid = N blocks then).
 #include "mw_gen.h"
+#include "mw_kernels.h"
 
 #ifndef MW_RESET_KERNEL_NAME
 #define MW_RESET_KERNEL_NAME mw_reset_kernel

@@ -4,6 +4,7 @@
 // Lanes cooperate: collision segments and entities are tested one per lane (ballot).
 // All double-precision dynamics follow numpy's evaluation order.
 #include "mw_setup_common.h"
+#include "mw_kernels.h"
 
 #ifndef MW_SETUP_KERNEL_NAME
 #define MW_SETUP_KERNEL_NAME mw_step_setup_kernel

@@ -6,6 +6,7 @@
 // env's step itself, and the leading lane writes its state and flags and — on an episode's end — installs the next world.
 // Not handled here (the engine launches mw_setup.hip instead): scenes whose L exceeds 32, MW_TASK_COLLECT.
 #include "mw_setup_common.h"
+#include "mw_kernels.h"
 
 #ifndef MW_DENSE_KERNEL_NAME
 #define MW_DENSE_KERNEL_NAME mw_step_setup_dense_kernel

@@ -12,6 +12,7 @@
 // Coverage and depth are the raster kernels' (mw_records.h: integer edge functions, z plane at the sample position).
 #include "mw_records.h"
 #include "mw_frag.h"
+#include "mw_kernels.h"
 
 namespace {
 
