@@ -37,6 +37,8 @@ MW_KERNEL_PAIR(mw_geom_any, MW_GEOM_ARGS);
 MW_KERNEL_PAIR(mw_geom_big_any, MW_GEOM_ARGS);
 
 // the tile kernels (mw_raster.hip)
+// (the frame kernels take parameter lists, not one struct: only __restrict__ on a kernel parameter tells the compiler that the
+// buffers do not overlap, and a by-value struct's pointers lose it — measured, tools/experiments/README.md)
 // (texd == texels: the descriptor table is the head of the texel block, mw_engine.hip::upload_textures; the kernels
 // use `texels` for both)
 #define MW_RASTER_ARGS \
