@@ -16,10 +16,15 @@ ranks, is an error.  `--dry` runs the same launcher / sharding / reduction path 
 (tests/test_sharding_gloo.py).
 
 Prints ONE JSON line on rank 0 (see the task contract): value = total env-steps / wall time,
-plus `roofline` (algorithmic HBM bytes of the dominant kernel / its HIP-event duration, per rank), at
-N=1 `cpu_baseline` (the C oracle on the host cores, bounded sample), and `parity_checked` (frames of the timed
-region's last step compared bit for bit with the CPU oracle, after the clock has stopped).  `--dump-outputs DIR` also
-writes what that last step returned to DIR as .npy files, so that two builds can be compared output for output.
+plus `roofline` (algorithmic HBM bytes of the dominant kernel / its HIP-event duration, per rank; counters from the
+committed profile).  `--dump-outputs DIR` also writes what that last step returned to DIR as .npy files, so that two
+builds can be compared output for output.
+
+A plain run does only what that line needs: set-up, pre-warm, W warm-up steps, K timed steps, the dump, the line.
+`--full` adds the legs that take runs or processes of their own, after the clock has stopped: `parity_checked` (frames of
+the timed region's last step compared bit for bit with the CPU oracle), `roofline.traffic` / `valu` read live by child
+runs under rocprofv3, `also` (the other BASELINE.json configs, hallway only) and at N=1 `cpu_baseline` (the C oracle on the
+host cores, bounded sample, and the reference itself).  Each can still be left out of a `--full` run with its --no-* option.
 """
 import argparse
 import json
@@ -51,7 +56,7 @@ RASTER_PHASE = {
     "maze": ("mw_raster_big_kernel",),
     "pickup_dr": ("mw_rasterq_kernel", "mw_mesh_entity_kernel", "mw_mesh_slow_kernel", "mw_raster_mesh_kernel"),
 }
-ALSO = ("oneroom_rgbd", "maze", "pickup_dr")      # BASELINE.json configs[2..4], timed after the headline in the default run
+ALSO = ("oneroom_rgbd", "maze", "pickup_dr")      # BASELINE.json configs[2..4], timed after the headline in a --full run
 HBM_PEAK_GBPS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 PREWARM_S = 0.5             # untimed steps before the W warm-up steps: clocks and caches of a cold box (reported)
 DUMP_PREWARM_STEPS = 1536   # --dump-outputs without --prewarm-steps: a fixed pre-warm (~0.5 s of the headline), so that runs repeat
@@ -429,8 +434,8 @@ class _DryVec:
 def measure(args, ctx, config, n, steps, warmup, headline):
     """One BASELINE config through the whole protocol: engine of `n` envs per rank, pre-generated random actions, pre-warm,
     W warm-up steps, K timed steps between barriers (MAX over ranks), HIP-event kernel times (one launch in 4 / 8), the outputs
-    of the last timed step written out (--dump-outputs, headline, rank 0), the parity spot check after the clock has stopped,
-    PMC traffic of the raster-phase kernels read by child runs (single GPU).
+    of the last timed step written out (--dump-outputs, headline, rank 0), and with --full the parity spot check after the clock
+    has stopped and PMC traffic of the raster-phase kernels read by child runs (single GPU).
     Returns the JSON object of the line (the headline's, or an entry of its `also` list) on rank 0, None elsewhere."""
     import torch
     from miniworld_amd.sharding import ObsAllGather, gather_objects, max_over_ranks, shard_plan
@@ -626,6 +631,9 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--envs-per-gpu", type=int, default=0, help="default: the BASELINE.json size of the config")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure, after the clock has stopped: the parity spot check, the PMC "
+                         "child runs, the `also` configs and the CPU baseline (each can be left out with its --no-* option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity-check", action="store_true")
     ap.add_argument("--config", default="hallway", choices=list(CONFIGS), help="hallway = the headline workload")
@@ -648,6 +656,8 @@ def main():
                          "under 64 MB: frames of a fixed, seeded sample of envs) to DIR; rank 0, headline config.  The pre-warm "
                          "is then a fixed number of steps, so that the same arguments give the same outputs")
     args = ap.parse_args()
+    if not args.full:       # a plain run: the headline line and nothing that takes runs of its own
+        args.no_cpu_baseline = args.no_parity_check = args.no_also = args.no_pmc = True
     if args.dump_outputs and (args.dry or args.view800):
         sys.exit("bench.py: --dump-outputs needs the engine's step workload (not --dry, not --view800)")
     if args.view800:
@@ -689,9 +699,9 @@ def main():
     ctx = {"rank": rank, "world": world, "local": local, "dist": dist, "device": device}
 
     head = measure(args, ctx, args.config, n, args.steps, args.warmup, headline=True)
-    # BASELINE.json configs[2..4] in the same command (same protocol, same pre-warm, their BASELINE sizes per GPU; under N
-    # ranks every rank runs its shard of each): before the CPU baseline, whose one-process-per-core storm leaves the GPU
-    # idle for ~20 s.  Never touches `value`.
+    # --full: BASELINE.json configs[2..4] in the same command (same protocol, same pre-warm, their BASELINE sizes per GPU;
+    # under N ranks every rank runs its shard of each): before the CPU baseline, whose one-process-per-core storm leaves
+    # the GPU idle for ~20 s.  Never touches `value`.
     also = []
     if not args.no_also and args.config == "hallway" and not args.envs_per_gpu:
         for name in ALSO:

@@ -70,7 +70,7 @@ def test_obs_allgather_over_rccl_world_size_one():
 def test_bench_force_dist_runs_the_rank_path_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--gather-obs", "--steps", "10", "--warmup", "2",
-                          "--envs-per-gpu", "256", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
+                          "--envs-per-gpu", "256", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["torch_distributed"] is True and line["config"]["obs_allgather"] is True

@@ -101,6 +101,26 @@ def test_bench_launcher_dry_run_with_eight_ranks():
     assert res["steps"] == 3 and res["windows"]["n"] == 1 and res["windows"]["steps_each"] == 3 and res["windows"]["values"] == [res["value"]]
 
 
+def test_bench_other_configs_only_with_full():
+    """The headline config in a dry run: a plain line carries no `also` list; `--full` adds BASELINE.json configs[2..4],
+    each with its own per-rank entries, and leaves the headline's own fields as they are."""
+    plain = _bench("--gpus", "2", "--dry", "--steps", "3", "--warmup", "1")
+    full = _bench("--gpus", "2", "--dry", "--steps", "3", "--warmup", "1", "--full")
+    res = {}
+    for name, out in (("plain", plain), ("full", full)):
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        res[name] = json.loads(lines[0])
+    assert "also" not in res["plain"] and "cpu_baseline" not in res["plain"]
+    also = res["full"]["also"]
+    assert [a["config"]["name"] for a in also] == ["oneroom_rgbd", "maze", "pickup_dr"]
+    assert all(a["n_gpus"] == 2 and [r["rank"] for r in a["roofline"]["per_rank"]] == [0, 1] for a in also)
+    for r in res.values():
+        assert r["config"]["name"] == "hallway" and r["config"]["envs_per_gpu"] == 4096 and r["steps"] == 3 and r["warmup"] == 1
+        assert r["parity_checked"] == 0 and "dry-run" in r["data"]
+
+
 def test_bench_refuses_a_rank_count_it_was_not_asked_for():
     # torch.distributed.run gave us one rank, the command line says two: no line, non-zero exit
     env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29577")

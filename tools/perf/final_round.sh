@@ -6,8 +6,8 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/final_$TAG
 mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_line_driver_command.json 2> $O/bench_line_driver_command.err
-python bench.py > $O/bench_line_default.json 2> $O/bench_line_default.err
+python bench.py --steps 20 --warmup 5 --full > $O/bench_line_driver_command.json 2> $O/bench_line_driver_command.err
+python bench.py --full > $O/bench_line_default.json 2> $O/bench_line_default.err
 python bench.py --view800 > $O/view800.json 2>/dev/null
 bash tools/perf/profile_round.sh $TAG > $O/profile_round.log 2>&1
 V=miniworld_amd/csrc/_variants
