@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -86,6 +87,15 @@ extern "C" __global__ __launch_bounds__(256) void mw_final_copy_kernel(const int
 
 namespace {
 thread_local std::string g_create_error;
+
+// Owning handles: every device buffer, stream and event of an engine has exactly one, and is released with it (mw_destroy keeps
+// the engine's device current while the members go).  The kernels keep taking raw pointers (MwArgs and the launches: .get()).
+template <typename H, hipError_t (*destroy)(H)>
+struct Destroy { void operator()(H h) const { (void)destroy(h); } };
+template <typename T>
+using DevBuf = std::unique_ptr<T, Destroy<void *, hipFree>>;
+using Stream = std::unique_ptr<ihipStream_t, Destroy<hipStream_t, hipStreamDestroy>>;
+using Event = std::unique_ptr<ihipEvent_t, Destroy<hipEvent_t, hipEventDestroy>>;
 }
 
 struct mw_engine {
@@ -98,45 +108,45 @@ struct mw_engine {
     int32_t *d_spare_dummy = nullptr;   // carry / step / picked written by the generator in spare mode go nowhere
     int n_sets = 1;
     std::string err;
-    // device allocations (freed in destroy)
-    std::vector<void *> allocs;
+    // the buffers mw_create makes for the engine's lifetime (world state, records, scratch); MwArgs and the members below point into them
+    std::vector<DevBuf<void>> fixed;
     // textures
     std::vector<MwTexDesc> tex_desc;
     std::vector<std::vector<uint32_t>> tex_data;   // per texture: every level as 32-byte footprint records (build_pyramid)
-    uint32_t *d_texels = nullptr;
-    MwTexDesc *d_texdesc = nullptr;
+    DevBuf<uint32_t> d_texels;          // the descriptor table, then the texels (upload_textures)
+    size_t texel_cap = 0;               // dwords d_texels holds
     MwMeshDesc *d_meshdesc = nullptr;
     std::vector<MwMeshDesc> mesh_desc;
     std::vector<std::vector<float>> mesh_pos, mesh_nrm, mesh_rgb, mesh_uv;   // per mesh id, [ntris][9] ([6] for uv)
-    float *d_mesh_pos = nullptr, *d_mesh_nrm = nullptr, *d_mesh_rgb = nullptr, *d_mesh_uv = nullptr;
-    float *d_mesh_stream = nullptr, *d_mesh_attr = nullptr;     // the entity kernel's triangle streams (rasterisation order): positions (meshes without a vertex table), vertex attributes
-    float4 *d_mesh_vpos = nullptr;      // the meshes' distinct positions (MwMeshDesc::vfirst, nverts)
-    uint2 *d_mesh_idx = nullptr;        // per triangle of the rasterisation order: three 16-bit indices into the mesh's table, the triangle's index
+    DevBuf<float> d_mesh_pos, d_mesh_nrm, d_mesh_rgb, d_mesh_uv;
+    DevBuf<float> d_mesh_stream, d_mesh_attr;   // the entity kernel's triangle streams (rasterisation order): positions (meshes without a vertex table), vertex attributes
+    DevBuf<float4> d_mesh_vpos;         // the meshes' distinct positions (MwMeshDesc::vfirst, nverts)
+    DevBuf<uint2> d_mesh_idx;           // per triangle of the rasterisation order: three 16-bit indices into the mesh's table, the triangle's index
     std::vector<std::vector<float>> mesh_vtab;      // per mesh id: [nverts][4]
     std::vector<std::vector<uint32_t>> mesh_itab;   // per mesh id: [ntris][2]
     int max_mesh_verts = 0;
     bool have_meshes = false;
-    uint32_t *d_view_keys = nullptr;    // sample keys of the generic-resolution path
+    DevBuf<uint32_t> d_view_keys;       // sample keys of the generic-resolution path
     bool visible_attr_set = false;
-    hipStream_t side_stream = nullptr;      // low priority: the Maze's spare-world refills beside the steps
-    hipStream_t quad_stream = nullptr;      // low priority: the raster kernel's first part (every tile no mesh can touch) beside the mesh kernels
-    hipEvent_t ev_mesh_fork = nullptr, ev_mesh_join = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    uint32_t *d_mesh_keys = nullptr;    // [N][H][W][8] sample keys of the mesh scatter kernel (all-ones between frames)
+    Stream side_stream;     // low priority: the Maze's spare-world refills beside the steps
+    Event ev_fork;
+    Stream quad_stream;     // low priority: the raster kernel's first part (every tile no mesh can touch) beside the mesh kernels
+    Event ev_mesh_fork, ev_mesh_join;
+    DevBuf<uint32_t> d_mesh_keys;       // [N][H][W][8] sample keys of the mesh scatter kernel (all-ones between frames)
     bool mesh_keys_dirty = true;
-    int32_t *d_slow_count = nullptr;    // [2 parities][2][N] listed triangles, fragments
+    DevBuf<int32_t> d_slow_count;       // [2 parities][2][N] listed triangles, fragments; then d_ent_counter
     int32_t *d_ent_counter = nullptr;   // [2][MW_CNT_WORDS] the work lists' lengths and cursors (mw_device.h: ent_list_n), this frame's and the next frame's
-    uint32_t *d_slow_envs = nullptr;    // [2][N] the envs with triangles across a frustum plane (written by the entity kernel: the slow kernel's work list)
-    uint32_t *d_tile_list = nullptr;    // [N * n_tiles] the mesh tiles' work list (written by the geometry kernel)
+    DevBuf<uint32_t> d_slow_envs;       // [2][N] the envs with triangles across a frustum plane (written by the entity kernel: the slow kernel's work list)
+    DevBuf<uint32_t> d_tile_list;       // [N * n_tiles] the mesh tiles' work list (written by the geometry kernel)
     static constexpr int mesh_tile_waves = 16384;       // wavefronts of the mesh tiles' launch, wavefront w taking the items w, w + 16384, ... of the list (4096: 139 us, 8192: 122, 16384: 112)
-    uint32_t *d_ent_list = nullptr;     // [2][N * slots] the work list itself (written by the geometry kernel)
+    DevBuf<uint32_t> d_ent_list;        // [2][N * slots] the work list itself (written by the geometry kernel)
     int ent_list_cap = 0;
     static constexpr int ent_blocks = 512;      // its persistent workgroups: two of 512 lanes per CU (768 of them, or 256 of 1024 lanes: measured slower)
     uint32_t mesh_frame_seq = 1;
-    uint32_t *d_slow_tris = nullptr;
-    float4 *d_slow_frags = nullptr;
-    uint32_t *d_slow_head = nullptr;
-    float *d_plane_cache = nullptr;     // [N][plane_cap][16] + [N][plane_cap][4] attribute planes of the mesh triangles that win samples (mw_raster_mesh.hip)
+    DevBuf<uint32_t> d_slow_tris;
+    DevBuf<float4> d_slow_frags;
+    DevBuf<uint32_t> d_slow_head;
+    DevBuf<float> d_plane_cache;        // [N][plane_cap][16] + [N][plane_cap][4] attribute planes of the mesh triangles that win samples (mw_raster_mesh.hip)
     int plane_cap = 0, max_mesh_tris = 0;
     int obs_layout = MW_OBS_HWC_U8;
     size_t view_keys_bytes = 0;
@@ -151,10 +161,13 @@ struct mw_engine {
     bool timing = false;
     int timing_stride = MW_TIMING_STRIDE;
     uint64_t frame_count = 0;
-    struct Ev { hipEvent_t a, b, c; };
+    struct Ev { Event a, b, c; };
     std::vector<Ev> ev_used, ev_free;
     int waves_per_env = 0;
-    MwProgram *d_prog = nullptr;        // placement program (mw_set_gen_program)
+    DevBuf<MwProgram> d_prog;           // placement program (mw_set_gen_program) and the tables it points at
+    DevBuf<mw_poly> d_prog_polys;
+    DevBuf<int32_t> d_prog_room, d_prog_surf;
+    DevBuf<double> d_prog_m, d_prog_segs;
     int texel_bytes = 4;
     int dbg_flags = 0;       // MW_DEBUG_FLAGS & MW_DEBUG_BITS: perf experiments only (bit0: flat shading)
     int last_raster_path = -1;  // mw_raster_path
@@ -193,20 +206,65 @@ int fail(mw_engine *e, int code, const char *fmt, ...)
             return fail(e, MW_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_st), __FILE__, __LINE__); \
     } while (0)
 
+// count elements of T (at least one), zeroed unless asked otherwise; `out` is left as it was on failure
 template <typename T>
-int dev_alloc(mw_engine *e, T **out, size_t count, bool zero = true)
+int dev_alloc(mw_engine *e, DevBuf<T> &out, size_t count, bool zero = true)
 {
     void *p = nullptr;
     const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
     hipError_t st = hipMalloc(&p, bytes);
     if (st != hipSuccess) return fail(e, MW_E_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(st));
+    DevBuf<T> buf(static_cast<T *>(p));
     if (zero) {
         st = hipMemset(p, 0, bytes);
         if (st != hipSuccess) return fail(e, MW_E_HIP, "hipMemset failed: %s", hipGetErrorString(st));
     }
-    e->allocs.push_back(p);
-    *out = static_cast<T *>(p);
+    out = std::move(buf);
     return MW_OK;
+}
+
+// ... one of mw_create's buffers: *out points into it, the engine owns it until it is destroyed
+template <typename T>
+int fixed_alloc(mw_engine *e, T **out, size_t count)
+{
+    DevBuf<T> buf;
+    if (const int rc = dev_alloc(e, buf, count)) return rc;
+    *out = buf.get();
+    e->fixed.emplace_back(std::move(buf));
+    return MW_OK;
+}
+
+// Grows a buffer to `want` units of `unit` bytes (`have`: what it holds): the new buffer is allocated beside the old one, which stays
+// in place if that fails; the device finishes whatever may still read the old one before it is released.
+template <typename T, typename C>
+int grow(mw_engine *e, DevBuf<T> &buf, C &have, C want, size_t unit)
+{
+    if (want <= have) return MW_OK;
+    DevBuf<T> fresh;
+    if (const int rc = dev_alloc(e, fresh, (size_t)want * unit / sizeof(T), false)) return rc;
+    (void)hipDeviceSynchronize();
+    buf = std::move(fresh);
+    have = want;
+    return MW_OK;
+}
+
+hipError_t make_event(Event &out, unsigned flags = hipEventDisableTiming)
+{
+    hipEvent_t ev = nullptr;
+    const hipError_t st = hipEventCreateWithFlags(&ev, flags);
+    if (st == hipSuccess) out.reset(ev);
+    return st;
+}
+
+// a low-priority stream: the filler work beside the caller's stream must not keep the main kernels' workgroups out
+hipError_t make_stream(Stream &out)
+{
+    int prio_least = 0, prio_greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+    hipStream_t s = nullptr;
+    const hipError_t st = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio_least);
+    if (st == hipSuccess) out.reset(s);
+    return st;
 }
 
 // K1 for the engine's random stream (the device code is compiled once per stream, mw_rng.h): the dense form for
@@ -448,18 +506,18 @@ int upload_textures(mw_engine *e)
         total += e->tex_data[i].size();
     }
     if (total * 4 > 0xFFFFFFF0ull) return fail(e, MW_E_CAPACITY, "texture pool of %zu bytes exceeds one buffer resource", total * 4);
-    if (e->d_texels) { (void)hipFree(e->d_texels); e->d_texels = nullptr; e->d_texdesc = nullptr; }
-    HIP_TRY(e, hipMalloc((void **)&e->d_texels, total * 4));
-    e->d_texdesc = reinterpret_cast<MwTexDesc *>(e->d_texels);
+    // (the pool is rewritten in place unless it grows: the frames that may still read it finish first)
+    HIP_TRY(e, hipDeviceSynchronize());
+    if (const int rc = grow(e, e->d_texels, e->texel_cap, total, 4)) return rc;
+    uint32_t *texels = e->d_texels.get();
+    e->args.texels = texels; e->args.tex = reinterpret_cast<MwTexDesc *>(texels);
     size_t off = table;
     for (size_t i = 0; i < descs.size(); ++i) {
         if (!e->tex_data[i].empty())
-            HIP_TRY(e, hipMemcpy(e->d_texels + off, e->tex_data[i].data(), e->tex_data[i].size() * 4, hipMemcpyHostToDevice));
+            HIP_TRY(e, hipMemcpy(texels + off, e->tex_data[i].data(), e->tex_data[i].size() * 4, hipMemcpyHostToDevice));
         off += e->tex_data[i].size();
     }
-    HIP_TRY(e, hipMemcpy(e->d_texdesc, descs.data(), descs.size() * sizeof(MwTexDesc), hipMemcpyHostToDevice));
-    e->args.texels = e->d_texels;
-    e->args.tex = e->d_texdesc;
+    HIP_TRY(e, hipMemcpy(texels, descs.data(), descs.size() * sizeof(MwTexDesc), hipMemcpyHostToDevice));
     e->texel_bytes = (int)(total * 4);
     if (e->d_gen_live && sync_gen_args(e) != MW_OK) return MW_E_HIP;
     return MW_OK;
@@ -564,20 +622,18 @@ int state_xfer(mw_engine *e, int first, int count, const mw_state_view *h, bool 
         if (sd_ != hipSuccess) return fail((e), MW_E_HIP, "hipSetDevice(%d): %s", (e)->cfg.device_id, hipGetErrorString(sd_)); } while (0)
 
 // ... and, for every entry point but the step / render ones, after the spare-world refills still running on the side stream
-#define ON_DEVICE_SYNC(e) do { ON_DEVICE(e); if ((e)->side_refill_pending) { (void)hipStreamSynchronize((e)->side_stream); \
+#define ON_DEVICE_SYNC(e) do { ON_DEVICE(e); if ((e)->side_refill_pending) { (void)hipStreamSynchronize((e)->side_stream.get()); \
         (e)->side_refill_pending = false; } } while (0)
 
 mw_engine::Ev get_events(mw_engine *e)
 {
     if (!e->ev_free.empty()) {
-        mw_engine::Ev ev = e->ev_free.back();
+        mw_engine::Ev ev = std::move(e->ev_free.back());
         e->ev_free.pop_back();
         return ev;
     }
-    mw_engine::Ev ev{};
-    (void)hipEventCreate(&ev.a);
-    (void)hipEventCreate(&ev.b);
-    (void)hipEventCreate(&ev.c);
+    mw_engine::Ev ev;
+    for (Event *x : {&ev.a, &ev.b, &ev.c}) (void)make_event(*x, hipEventDefault);
     return ev;
 }
 
@@ -586,16 +642,6 @@ mw_engine::Ev get_events(mw_engine *e)
 int sync_gen_args(mw_engine *e)
 {
     if (e->cfg.generator == MW_GEN_NONE) return MW_OK;
-    if (!e->d_gen_live) {
-        HIP_TRY(e, hipMalloc((void **)&e->d_gen_live, sizeof(MwArgs)));
-        e->allocs.push_back(e->d_gen_live);
-        e->args.gen_live = e->d_gen_live;
-        if (e->spare_mode) {
-            HIP_TRY(e, hipMalloc((void **)&e->d_gen_spare, sizeof(MwArgs)));
-            e->allocs.push_back(e->d_gen_spare);
-            e->args.gen_spare = e->d_gen_spare;
-        }
-    }
     MwArgs live = e->args;
     HIP_TRY(e, hipMemcpy(e->d_gen_live, &live, sizeof live, hipMemcpyHostToDevice));
     if (e->spare_mode) {
@@ -612,28 +658,11 @@ int sync_gen_args(mw_engine *e)
     return MW_OK;
 }
 
-// second, low-priority stream for work that runs beside the raster kernel (spare refill, K2 beside the mesh kernel)
+// second, low-priority stream for work that runs beside the raster kernel (the Maze's spare refills)
 int ensure_side_stream(mw_engine *e)
 {
-    if (e->side_stream) return MW_OK;
-    int prio_least = 0, prio_greatest = 0;      // the filler work must not keep the main kernels' workgroups out
-    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    HIP_TRY(e, hipStreamCreateWithPriority(&e->side_stream, hipStreamNonBlocking, prio_least));
-    HIP_TRY(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-    HIP_TRY(e, hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-    return MW_OK;
-}
-
-// the stream of the raster kernel's first part in a frame with meshes: LOW priority — the mesh kernels on the caller's stream are the
-// critical path, the quad kernel fills the CUs around them
-int ensure_mesh_stream(mw_engine *e)
-{
-    if (e->quad_stream) return MW_OK;
-    int prio_least = 0, prio_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    HIP_TRY(e, hipStreamCreateWithPriority(&e->quad_stream, hipStreamNonBlocking, prio_least));
-    HIP_TRY(e, hipEventCreateWithFlags(&e->ev_mesh_fork, hipEventDisableTiming));
-    HIP_TRY(e, hipEventCreateWithFlags(&e->ev_mesh_join, hipEventDisableTiming));
+    if (!e->side_stream) HIP_TRY(e, make_stream(e->side_stream));
+    if (!e->ev_fork) HIP_TRY(e, make_event(e->ev_fork));
     return MW_OK;
 }
 
@@ -645,18 +674,13 @@ int ensure_mesh_buffers(mw_engine *e)
 {
     const MwArgs &a = e->args;
     const size_t N = (size_t)e->cfg.num_envs;
-    if (ensure_mesh_stream(e) != MW_OK) return MW_E_HIP;
-    if (e->cfg.msaa != 8 || !tile_path_ok(a.W, a.H)) {       // the generic-resolution path
-        const size_t need = N * a.W * a.H * e->cfg.msaa * 4;
-        if (need > e->view_keys_bytes) {
-            uint32_t *nk = nullptr;
-            if (hipMalloc((void **)&nk, need) != hipSuccess) return fail(e, MW_E_NOMEM, "hipMalloc(%zu) for the view keys failed", need);
-            (void)hipDeviceSynchronize();
-            if (e->d_view_keys) (void)hipFree(e->d_view_keys);
-            e->d_view_keys = nk; e->view_keys_bytes = need;
-        }
-        return MW_OK;
-    }
+    // the stream of the raster kernel's first part in a frame with meshes: LOW priority — the mesh kernels on the caller's stream are the
+    // critical path, the quad kernel fills the CUs around them
+    if (!e->quad_stream) HIP_TRY(e, make_stream(e->quad_stream));
+    if (!e->ev_mesh_fork) HIP_TRY(e, make_event(e->ev_mesh_fork));
+    if (!e->ev_mesh_join) HIP_TRY(e, make_event(e->ev_mesh_join));
+    if (e->cfg.msaa != 8 || !tile_path_ok(a.W, a.H))        // the generic-resolution path
+        return grow(e, e->d_view_keys, e->view_keys_bytes, N * a.W * a.H * e->cfg.msaa * 4, 1);
     if (a.W > 255 * MW_TILE_W || a.H > 255 * MW_TILE_H) return fail(e, MW_E_CAPACITY, "frame too large for the mesh tile rectangles");
     // the mesh tiles' work list (mw_geom.hip): a tile index in the 8 bits above the env, and one bit of a lane's 32-bit mask per tile
     // sub + k L.  tile_path_ok caps these frames at 192 tiles and the geometry kernel has at least 8 lanes per env, so this holds
@@ -664,40 +688,30 @@ int ensure_mesh_buffers(mw_engine *e)
     if (a.n_tiles > 255 || a.n_tiles > 32 * geom_lanes(e))
         return fail(e, MW_E_CAPACITY, "%d tiles per frame: the mesh tiles' work list holds 255 (8-bit tile index) and 32 per lane of the geometry kernel (%d lanes)", a.n_tiles, geom_lanes(e));
     const long long want = std::min<long long>(0xC000, (long long)e->cfg.max_ents * e->max_mesh_tris);
-    if ((int)want > e->plane_cap) {
-        float *np = nullptr;
-        if (hipMalloc((void **)&np, N * (size_t)want * (MW_PLANE_REC + MW_PLANE_XTRA) * 4) != hipSuccess) return fail(e, MW_E_NOMEM, "hipMalloc for the plane cache (%lld records per env) failed", want);
-        (void)hipDeviceSynchronize();
-        if (e->d_plane_cache) (void)hipFree(e->d_plane_cache);
-        e->d_plane_cache = np; e->plane_cap = (int)want;
-    }
+    int rc;
+    if ((rc = grow(e, e->d_plane_cache, e->plane_cap, (int)want, N * (MW_PLANE_REC + MW_PLANE_XTRA) * 4))) return rc;
     if (!e->d_ent_list) {
-        // (all three work lists or none: a failed allocation leaves no pointer behind)
+        // (all three work lists or none)
         const int cap = (int)N * std::min(MW_MAX_MESH_ENTS, std::max(e->cfg.max_ents, 1));
-        void *ents = nullptr, *slow = nullptr, *tiles = nullptr;
-        const bool ok = hipMalloc(&ents, (size_t)cap * 16 * 4) == hipSuccess && hipMalloc(&slow, N * 2 * 4) == hipSuccess &&
-                        hipMalloc(&tiles, N * (size_t)a.n_tiles * 8 * 4) == hipSuccess;
-        if (!ok) {
-            for (void *p : {ents, slow, tiles}) if (p) (void)hipFree(p);
-            return fail(e, MW_E_NOMEM, "hipMalloc for the mesh path's work lists failed");
-        }
+        DevBuf<uint32_t> ents, slow, tiles;
+        if ((rc = dev_alloc(e, ents, (size_t)cap * 16, false)) || (rc = dev_alloc(e, slow, N * 2, false)) ||
+            (rc = dev_alloc(e, tiles, N * (size_t)a.n_tiles * 8, false)))
+            return rc;
         e->ent_list_cap = cap;
-        e->d_ent_list = (uint32_t *)ents; e->d_slow_envs = (uint32_t *)slow; e->d_tile_list = (uint32_t *)tiles;
+        e->d_ent_list = std::move(ents); e->d_slow_envs = std::move(slow); e->d_tile_list = std::move(tiles);
     }
     if (!e->d_mesh_keys) {
-        const size_t key_bytes = N * a.W * a.H * 8 * 4, head_bytes = N * a.W * a.H * 4;
-        void *keys = nullptr, *cnt = nullptr, *tris = nullptr, *frags = nullptr, *head = nullptr;
+        const size_t px = N * a.W * a.H;
+        DevBuf<uint32_t> keys, tris, head; DevBuf<int32_t> cnt; DevBuf<float4> frags;
         // triangles that cross a frustum plane and their fragments (mw_mesh_slow_kernel): counts, 1024 / 2048 entries per env
-        const bool ok = hipMalloc(&keys, key_bytes) == hipSuccess && hipMalloc(&cnt, N * 4 * 4 + 2 * MW_CNT_WORDS * 4) == hipSuccess && hipMalloc(&tris, N * MW_SLOW_TRIS * 4) == hipSuccess &&
-                        hipMalloc(&frags, N * MW_SLOW_STRIDE * 16) == hipSuccess && hipMalloc(&head, head_bytes) == hipSuccess &&
-                        hipMemset(cnt, 0, N * 4 * 4 + 2 * MW_CNT_WORDS * 4) == hipSuccess && hipMemset(head, 0, head_bytes) == hipSuccess && hipMemset(keys, 0xFF, key_bytes) == hipSuccess;
-        if (!ok) {
-            for (void *p : {keys, cnt, tris, frags, head}) if (p) (void)hipFree(p);
-            return fail(e, MW_E_NOMEM, "hipMalloc for the mesh path's buffers failed");
-        }
-        e->d_mesh_keys = (uint32_t *)keys; e->d_slow_count = (int32_t *)cnt; e->d_slow_tris = (uint32_t *)tris;
-        e->d_slow_frags = (float4 *)frags; e->d_slow_head = (uint32_t *)head;
-        e->d_ent_counter = (int32_t *)cnt + N * 4;       // (behind the slow path's counts)
+        if ((rc = dev_alloc(e, keys, px * 8, false)) || (rc = dev_alloc(e, cnt, N * 4 + 2 * MW_CNT_WORDS)) ||
+            (rc = dev_alloc(e, tris, N * MW_SLOW_TRIS, false)) || (rc = dev_alloc(e, frags, N * MW_SLOW_STRIDE, false)) ||
+            (rc = dev_alloc(e, head, px)))
+            return rc;
+        HIP_TRY(e, hipMemset(keys.get(), 0xFF, px * 8 * 4));
+        e->d_ent_counter = cnt.get() + N * 4;       // (behind the slow path's counts)
+        e->d_mesh_keys = std::move(keys); e->d_slow_count = std::move(cnt); e->d_slow_tris = std::move(tris);
+        e->d_slow_frags = std::move(frags); e->d_slow_head = std::move(head);
         // (the memsets above ran on the null stream, which a caller's non-blocking stream is not ordered against: finish them here)
         (void)hipDeviceSynchronize();
         e->mesh_keys_dirty = false;
@@ -744,8 +758,8 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
     const bool mesh_obs = e->have_meshes && e->cfg.msaa == 8 && tile_path_ok(a.W, a.H) && e->d_ent_list && e->d_mesh_keys;
     const uint32_t mesh_seq = mesh_obs ? e->mesh_frame_seq++ : 0u;
     if (mesh_obs) {
-        a.ent_list = e->d_ent_list; a.ent_list_n = e->d_ent_counter + (mesh_seq & 1u) * MW_CNT_WORDS; a.ent_list_cap = e->ent_list_cap;
-        a.tile_list = e->d_tile_list; a.tile_list_cap = N * a.n_tiles;
+        a.ent_list = e->d_ent_list.get(); a.ent_list_n = e->d_ent_counter + (mesh_seq & 1u) * MW_CNT_WORDS; a.ent_list_cap = e->ent_list_cap;
+        a.tile_list = e->d_tile_list.get(); a.tile_list_cap = N * a.n_tiles;
     }
     mw_engine::Ev ev{};
     // kernel durations are sampled: three event records on every launch cost ~4 % of the step rate,
@@ -754,7 +768,7 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
     const bool timed = frame != FRAME_LIST && e->timing && (e->frame_count++ % (uint64_t)e->timing_stride) == 0;
     if (timed) {
         ev = get_events(e);
-        (void)hipEventRecord(ev.a, st);
+        (void)hipEventRecord(ev.a.get(), st);
     }
     // spare mode: blocks appended to the grid regenerate the spare worlds consumed in earlier steps, beside the step itself
     // ... except for the Maze: regenerating one takes ~300 us on a single wave, four times a whole step of the batch, and
@@ -782,12 +796,12 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
     }
     if (do_step && e->cfg.task == MW_TASK_COLLECT)
         hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_collect_respawn_pcg_kernel : mw_collect_respawn_kernel, dim3((N + 63) / 64), dim3(64), 0, st, a);
-    if (timed) (void)hipEventRecord(ev.b, st);
+    if (timed) (void)hipEventRecord(ev.b.get(), st);
     if (async_refill) {
         if (ensure_side_stream(e) != MW_OK) return MW_E_HIP;
-        HIP_TRY(e, hipEventRecord(e->ev_fork, st));
-        HIP_TRY(e, hipStreamWaitEvent(e->side_stream, e->ev_fork, 0));
-        hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_refill_pcg_kernel : mw_refill_kernel, dim3(N), dim3(64), 0, e->side_stream, e->args);
+        HIP_TRY(e, hipEventRecord(e->ev_fork.get(), st));
+        HIP_TRY(e, hipStreamWaitEvent(e->side_stream.get(), e->ev_fork.get(), 0));
+        hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_refill_pcg_kernel : mw_refill_kernel, dim3(N), dim3(64), 0, e->side_stream.get(), e->args);
         e->side_refill_pending = true;
     }
     // the quad kernel (mw_rasterq.hip): small scenes without a visiting order, frames that fit its LDS plan — 8 samples (the
@@ -818,7 +832,7 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
         if (e->have_meshes) {
             const size_t need = (size_t)N * a.W * a.H * S * 4;
             if (need > e->view_keys_bytes) return fail(e, MW_E_INVALID, "view keys missing (mw_upload_mesh allocates them)");
-            keys = e->d_view_keys;
+            keys = e->d_view_keys.get();
             HIP_TRY(e, hipMemsetAsync(keys, 0xFF, need, st));
             launch(MW_PAIR(mw_view_mesh), list, dim3(32, N), dim3(256), 0, st, a.W, a.H, S, 0, (const float *)a.envhdr, a.mesh_pos, keys);
         }
@@ -832,7 +846,7 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
             // ensure_mesh_buffers, at upload time)
             if (!e->d_mesh_keys || !e->d_plane_cache || !e->quad_stream) return fail(e, MW_E_INVALID, "mesh buffers missing (mw_upload_mesh allocates them)");
             const size_t key_bytes = (size_t)N * a.W * a.H * 8 * 4;
-            if (e->mesh_keys_dirty) HIP_TRY(e, hipMemsetAsync(e->d_mesh_keys, 0xFF, key_bytes, st));
+            if (e->mesh_keys_dirty) HIP_TRY(e, hipMemsetAsync(e->d_mesh_keys.get(), 0xFF, key_bytes, st));
             e->mesh_keys_dirty = true;      // until the raster kernel that clears them again has been enqueued
             // frame stamp of the slow-fragment chains and parity of the lists.  The stamp has 16 bits: a head that no frame has
             // overwritten since frame F would read as valid again at frame F + 65536 (24 s of PickupObjects), so the heads are
@@ -840,25 +854,25 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
             // stream order (tests/test_gpu_env_api.py::test_slow_fragment_heads_survive_the_stamp_wrap)
             const uint32_t seq = mesh_seq;
             mesh_stamp = seq & 0xFFFFu;
-            if (mesh_stamp == 0u) HIP_TRY(e, hipMemsetAsync(e->d_slow_head, 0, (size_t)N * a.W * a.H * 4, st));
+            if (mesh_stamp == 0u) HIP_TRY(e, hipMemsetAsync(e->d_slow_head.get(), 0, (size_t)N * a.W * a.H * 4, st));
             const int parity = (int)(seq & 1u);
             // The mesh kernels — the frame's critical path — stay on the caller's stream, right behind the geometry kernel; the quad
             // kernel, which draws every tile no mesh can touch, goes to the low-priority quad stream beside them.  (The other way
             // round — mesh kernels on a side stream — the quad kernel started a few microseconds EARLIER, its 2 048 workgroups
             // took the CUs, and the entity kernel's workgroups waited a quad-kernel workgroup's lifetime for room: 212 instead of
             // 133 us, PickupObjects 4.55 -> 5.3 M env-steps/s.)
-            HIP_TRY(e, hipEventRecord(e->ev_mesh_fork, st));
-            HIP_TRY(e, hipStreamWaitEvent(e->quad_stream, e->ev_mesh_fork, 0));
+            HIP_TRY(e, hipEventRecord(e->ev_mesh_fork.get(), st));
+            HIP_TRY(e, hipStreamWaitEvent(e->quad_stream.get(), e->ev_mesh_fork.get(), 0));
             // persistent workgroups drawing entities from the geometry kernel's list (two sets of counters swapping places: the
             // kernel zeroes the next frame's)
             hipLaunchKernelGGL(mw_mesh_entity_kernel, dim3(std::max(a.n_xcc, std::min(e->ent_list_cap, e->ent_blocks))), dim3(MW_ENT_THREADS), (size_t)e->max_mesh_verts * 16, st, N, a.W, a.H,
-                               (const float *)a.envhdr, a.mesh, (const float4 *)e->d_mesh_vpos, (const uint2 *)e->d_mesh_idx, (const float *)e->d_mesh_stream,
-                               (const float *)e->d_mesh_attr, e->d_mesh_keys, e->d_plane_cache, e->plane_cap, e->d_slow_count + (size_t)parity * 2 * N, e->d_slow_tris,
-                               (const uint32_t *)e->d_ent_list, e->ent_list_cap, e->d_ent_counter + parity * MW_CNT_WORDS, e->d_ent_counter + (parity ^ 1) * MW_CNT_WORDS, e->d_slow_envs + (size_t)parity * N, e->args.n_xcc, e->d_ent_prof);
+                               (const float *)a.envhdr, a.mesh, (const float4 *)e->d_mesh_vpos.get(), (const uint2 *)e->d_mesh_idx.get(), (const float *)e->d_mesh_stream.get(),
+                               (const float *)e->d_mesh_attr.get(), e->d_mesh_keys.get(), e->d_plane_cache.get(), e->plane_cap, e->d_slow_count.get() + (size_t)parity * 2 * N, e->d_slow_tris.get(),
+                               (const uint32_t *)e->d_ent_list.get(), e->ent_list_cap, e->d_ent_counter + parity * MW_CNT_WORDS, e->d_ent_counter + (parity ^ 1) * MW_CNT_WORDS, e->d_slow_envs.get() + (size_t)parity * N, e->args.n_xcc, e->d_ent_prof);
             hipLaunchKernelGGL(mw_mesh_slow_kernel, dim3(std::min(N * 16, e->slow_waves)), dim3(64), 0, st, a.W, a.H, (const float *)a.envhdr, a.mesh_pos, a.mesh_nrm, a.mesh_rgb,
-                               a.mesh_uv, a.texels, e->texel_bytes, e->d_mesh_keys, e->d_slow_count, N, parity, (const uint32_t *)e->d_slow_tris,
-                               e->d_slow_frags, e->d_slow_head, mesh_stamp, a.status,
-                               (const uint32_t *)(e->d_slow_envs + (size_t)parity * N), (const int32_t *)(e->d_ent_counter + parity * MW_CNT_WORDS + MW_CNT_SLOW_ENVS));
+                               a.mesh_uv, a.texels, e->texel_bytes, e->d_mesh_keys.get(), e->d_slow_count.get(), N, parity, (const uint32_t *)e->d_slow_tris.get(),
+                               e->d_slow_frags.get(), e->d_slow_head.get(), mesh_stamp, a.status,
+                               (const uint32_t *)(e->d_slow_envs.get() + (size_t)parity * N), (const int32_t *)(e->d_ent_counter + parity * MW_CNT_WORDS + MW_CNT_SLOW_ENVS));
         }
         const int wpe = e->waves_per_env;
         const int tpw = (a.n_tiles + wpe - 1) / wpe;
@@ -881,18 +895,18 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
             launch(tile_kernel_of(big, d_depth != nullptr, general, ragged, mesh, part == 1), list, dim3(grid), dim3(64), lds, ks,
                    a.N, a.W, a.H, a.max_vis, a.tiles_x, a.n_tiles, wpe2, tpw2, (const float *)a.rec_raster, (const float *)a.rec_shade,
                    (const float *)a.rec_cull, (const int32_t *)a.nvis, (const float *)a.envhdr, a.tex, a.texels, d_obs, d_depth, raster_flags(e, part, mesh_stamp),
-                   e->texel_bytes, (const uint16_t *)a.rec_order, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, e->d_mesh_keys,
-                   (const float *)e->d_plane_cache, e->plane_cap, (const float4 *)e->d_slow_frags, (const uint32_t *)e->d_slow_head,
+                   e->texel_bytes, (const uint16_t *)a.rec_order, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, e->d_mesh_keys.get(),
+                   (const float *)e->d_plane_cache.get(), e->plane_cap, (const float4 *)e->d_slow_frags.get(), (const uint32_t *)e->d_slow_head.get(),
                    (const uint32_t *)a.tile_list, a.ent_list_n, a.tile_list_cap, std::max(a.n_xcc, 1));
         };
         e->last_raster_path = k2q ? (mesh ? MW_PATH_QUAD_MESH : MW_PATH_QUAD) : MW_PATH_TILE;
         if (mesh) {
             // the first part — every tile no mesh can touch: it needs nothing of the mesh kernels — on the quad stream beside them
             // (forked above, behind the geometry kernel); the mesh tiles end the chain on the caller's stream
-            if (k2q) launch_k2q(1, e->quad_stream); else launch_k2(1, e->quad_stream);
+            if (k2q) launch_k2q(1, e->quad_stream.get()); else launch_k2(1, e->quad_stream.get());
             launch_k2(2, st);
-            HIP_TRY(e, hipEventRecord(e->ev_mesh_join, e->quad_stream));
-            HIP_TRY(e, hipStreamWaitEvent(st, e->ev_mesh_join, 0));
+            HIP_TRY(e, hipEventRecord(e->ev_mesh_join.get(), e->quad_stream.get()));
+            HIP_TRY(e, hipStreamWaitEvent(st, e->ev_mesh_join.get(), 0));
         } else if (k2q) {
             launch_k2q(0, st);
         } else {
@@ -901,42 +915,16 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
         if (mesh) e->mesh_keys_dirty = false;
     }
     if (timed) {
-        (void)hipEventRecord(ev.c, st);
-        e->ev_used.push_back(ev);
+        (void)hipEventRecord(ev.c.get(), st);
+        e->ev_used.push_back(std::move(ev));
     }
     HIP_TRY(e, hipGetLastError());
     return MW_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-const char *mw_last_error(const mw_engine *e) { return e ? e->err.c_str() : g_create_error.c_str(); }
-
-int mw_create(const mw_config *cfg, mw_engine **out)
+// mw_create's engine for a checked configuration; on failure mw_create destroys it with whatever it holds
+int init_engine(mw_engine *e, const mw_config *cfg)
 {
-    if (!cfg || !out) return fail(nullptr, MW_E_INVALID, "null argument");
-    if (cfg->abi_version != MW_ABI_VERSION) return fail(nullptr, MW_E_INVALID, "ABI version mismatch: header %d, caller %d", MW_ABI_VERSION, cfg->abi_version);
-    if (cfg->num_envs <= 0 || cfg->max_ents < 0 || cfg->max_polys <= 0 || cfg->max_segs <= 0 || cfg->max_visible <= 0)
-        return fail(nullptr, MW_E_INVALID, "bad capacities");
-    if (cfg->rng_mode != MW_RNG_PHILOX && cfg->rng_mode != MW_RNG_PCG64) return fail(nullptr, MW_E_INVALID, "unknown rng_mode %d", cfg->rng_mode);
-    if (cfg->autoreset != MW_AUTORESET_OFF && cfg->autoreset != MW_AUTORESET_SAME_STEP && cfg->autoreset != MW_AUTORESET_NEXT_STEP)
-        return fail(nullptr, MW_E_INVALID, "unknown autoreset mode %d", cfg->autoreset);
-    if (cfg->rng_mode == MW_RNG_PCG64 && cfg->generator == MW_GEN_NONE)
-        return fail(nullptr, MW_E_INVALID, "MW_RNG_PCG64 (the reference's own numpy stream) needs a device generator");
-    if (cfg->max_ents > 64) return fail(nullptr, MW_E_CAPACITY, "max_ents > 64 (one entity slot per lane of the env's wavefront)");
-    if (cfg->msaa != 8 && cfg->msaa != 4 && cfg->msaa != 1) return fail(nullptr, MW_E_INVALID, "msaa must be 8, 4 or 1");
-    if (!frame_size_ok(cfg->obs_width, cfg->obs_height))
-        return fail(nullptr, MW_E_INVALID, "obs size %dx%d: 1 to %d x 1 to %d pixels", cfg->obs_width, cfg->obs_height, 255 * MW_TILE_W, 255 * MW_TILE_H);
-    if (cfg->max_visible > 60000) return fail(nullptr, MW_E_CAPACITY, "max_visible too large (16-bit draw ids)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, MW_E_DEVICE, "no HIP device available");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(nullptr, MW_E_DEVICE, "device %d out of range (%d devices)", cfg->device_id, ndev);
-    hipError_t st = hipSetDevice(cfg->device_id);
-    if (st != hipSuccess) return fail(nullptr, MW_E_HIP, "hipSetDevice: %s", hipGetErrorString(st));
-
-    mw_engine *e = new mw_engine();
     e->cfg = *cfg;
     const int N = cfg->num_envs, E = std::max(cfg->max_ents, 1);
     e->cfg.max_ents = E;
@@ -969,8 +957,7 @@ int mw_create(const mw_config *cfg, mw_engine **out)
         a.light_ambient[i] = cfg->light_ambient[i]; a.color_bias[i] = cfg->obj_color_bias[i];
     }
     a.cam_height = cfg->cam_height; a.cam_fwd_disp = cfg->cam_fwd_disp; a.cam_pitch = cfg->cam_pitch; a.cam_fov_y = cfg->cam_fov_y;
-    int rc = MW_OK;
-#define ALLOC(ptr, count) if (rc == MW_OK) rc = dev_alloc(e, &ptr, (size_t)(count))
+#define ALLOC(ptr, count) do { if (const int rc_ = fixed_alloc(e, &ptr, (size_t)(count))) return rc_; } while (0)
     ALLOC(a.ax, N); ALLOC(a.ay, N); ALLOC(a.az, N); ALLOC(a.adir, N);
     ALLOC(a.cam, 4 * (size_t)N); ALLOC(a.light, 12 * (size_t)N);
     ALLOC(a.carry, N); ALLOC(a.step, N); ALLOC(a.picked, N);
@@ -981,7 +968,8 @@ int mw_create(const mw_config *cfg, mw_engine **out)
     ALLOC(a.rng, 5 * (size_t)N); ALLOC(a.extent, 4 * (size_t)N);
     MwGenTables *d_gt = nullptr;
     ALLOC(d_gt, 1);
-    if (rc == MW_OK) { (void)hipMemcpy(d_gt, &gt, sizeof gt, hipMemcpyHostToDevice); a.gt = d_gt; }
+    HIP_TRY(e, hipMemcpy(d_gt, &gt, sizeof gt, hipMemcpyHostToDevice));
+    a.gt = d_gt;
     mw_poly *polys = nullptr; int32_t *npolys = nullptr; double *segs = nullptr; int32_t *nsegs = nullptr;
     ALLOC(polys, (size_t)e->n_sets * cfg->max_polys); ALLOC(npolys, e->n_sets);
     ALLOC(segs, (size_t)e->n_sets * cfg->max_segs * 4); ALLOC(nsegs, e->n_sets);
@@ -1013,11 +1001,16 @@ int mw_create(const mw_config *cfg, mw_engine **out)
         ALLOC(a.refill_mask, N);
         ALLOC(e->d_spare_dummy, 3 * (size_t)N);
         e->spare_host = sp;
-        if (rc == MW_OK) {      // every spare starts out consumed: the first reset generates it
+        {       // every spare starts out consumed: the first reset generates it
             std::vector<uint32_t> ones((size_t)N, 1u);
-            (void)hipMemcpy(a.refill_mask, ones.data(), 4 * (size_t)N, hipMemcpyHostToDevice);
+            HIP_TRY(e, hipMemcpy(a.refill_mask, ones.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
         }
-        if (rc == MW_OK) { (void)hipMemcpy(d_sp, &sp, sizeof sp, hipMemcpyHostToDevice); a.spare = d_sp; }
+        HIP_TRY(e, hipMemcpy(d_sp, &sp, sizeof sp, hipMemcpyHostToDevice));
+        a.spare = d_sp;
+    }
+    if (cfg->generator != MW_GEN_NONE) {
+        ALLOC(e->d_gen_live, 1); a.gen_live = e->d_gen_live;
+        if (e->spare_mode) { ALLOC(e->d_gen_spare, 1); a.gen_spare = e->d_gen_spare; }
     }
     ALLOC(e->d_meshdesc, MW_MAX_MESH);
     a.mesh = e->d_meshdesc;      // a.tex / a.texels: upload_textures
@@ -1025,9 +1018,8 @@ int mw_create(const mw_config *cfg, mw_engine **out)
     ALLOC(a.rec_shade, (size_t)N * a.max_vis * MW_SHADE_REC);
     ALLOC(a.rec_cull, (size_t)N * a.max_vis * MW_CULL_REC);
     if (cfg->max_visible > 64) {
-        // big scenes: the visiting order the geometry kernel leaves for K2 (mw_geom.hip)
+        // big scenes: the visiting order the geometry kernel leaves for K2 (mw_geom.hip), zeroed
         ALLOC(a.rec_order, (size_t)N * (a.max_vis + 1));
-        if (rc == MW_OK) (void)hipMemset(a.rec_order, 0, (size_t)N * (a.max_vis + 1) * 2);
     }
     if (cfg->max_polys > 64 && !(getenv("MW_OCC_CACHE") && atoi(getenv("MW_OCC_CACHE")) == 0)) {
         // big scenes: the geometry kernel's per-world culling data (mw_geom.hip), zeroed = nothing cached
@@ -1036,33 +1028,31 @@ int mw_create(const mw_config *cfg, mw_engine **out)
     }
     ALLOC(a.pending_remove, (size_t)N);
     ALLOC(a.reset_pending, (size_t)N);      // (zeroed: nothing pending)
-    if (rc == MW_OK) (void)hipMemset(a.pending_remove, 0xFF, 4 * (size_t)N);
+    HIP_TRY(e, hipMemset(a.pending_remove, 0xFF, 4 * (size_t)N));
     ALLOC(a.nvis, N); ALLOC(a.envhdr, (size_t)MW_ENVHDR * N); ALLOC(a.status, 1);
     ALLOC(e->d_reward_scratch, N); ALLOC(e->d_flag_scratch, 2 * (size_t)N); ALLOC(e->d_action_scratch, N);
     ALLOC(e->d_final_list, 1 + (size_t)N);
     ALLOC(e->d_mask, N); ALLOC(e->d_step_override, 3 * (size_t)N);
 #ifdef MW_PERF_HOOKS        // (tools/perf: make EXTRA=-DMW_PERF_HOOKS — kernel phase stamps dumped by mw_destroy; not in the product build)
-    if (getenv("MW_K1_PROF")) {     // per-env cycle stamps of the geometry kernel's phases
-        ALLOC(a.k1_prof, MW_K1_PROF_SLOTS * (size_t)N);
-        if (rc == MW_OK) (void)hipMemset(a.k1_prof, 0, 8 * MW_K1_PROF_SLOTS * (size_t)N);
-    }
+    if (getenv("MW_K1_PROF")) ALLOC(a.k1_prof, MW_K1_PROF_SLOTS * (size_t)N);     // per-env cycle stamps of the geometry kernel's phases (zeroed)
+    if (getenv("MW_ENT_PROF")) ALLOC(e->d_ent_prof, (size_t)16 * 2 * N * MW_MAX_MESH_ENTS * 8);
+    if (getenv("MW_K2Q_PROF")) ALLOC(e->d_k2q_prof, (size_t)N * 80);
 #endif
 #undef ALLOC
-    if (rc != MW_OK) { g_create_error = e->err; mw_destroy(e); return rc; }
     // carrying = -1 everywhere; default seeds = env index
     {
         std::vector<int32_t> m1((size_t)N, -1);
-        (void)hipMemcpy(a.carry, m1.data(), 4 * (size_t)N, hipMemcpyHostToDevice);
+        HIP_TRY(e, hipMemcpy(a.carry, m1.data(), 4 * (size_t)N, hipMemcpyHostToDevice));
         std::vector<uint64_t> seeds(5 * (size_t)N, 0);
         for (int i = 0; i < N; ++i) seed_env(e, seeds.data(), i, (uint64_t)i);
-        (void)hipMemcpy(a.rng, seeds.data(), 40 * (size_t)N, hipMemcpyHostToDevice);
+        HIP_TRY(e, hipMemcpy(a.rng, seeds.data(), 40 * (size_t)N, hipMemcpyHostToDevice));
     }
     e->mesh_desc.assign(MW_MAX_MESH, MwMeshDesc{});
     e->mesh_pos.assign(MW_MAX_MESH, {}); e->mesh_nrm.assign(MW_MAX_MESH, {}); e->mesh_rgb.assign(MW_MAX_MESH, {}); e->mesh_uv.assign(MW_MAX_MESH, {});
     e->mesh_vtab.assign(MW_MAX_MESH, {}); e->mesh_itab.assign(MW_MAX_MESH, {});
     e->tex_desc.assign(MW_MAX_TEX, MwTexDesc{});
     e->tex_data.assign(MW_MAX_TEX, {});
-    if (upload_textures(e) != MW_OK) { g_create_error = e->err; mw_destroy(e); return MW_E_HIP; }
+    if (const int rc = upload_textures(e)) return rc;
     e->waves_per_env = pick_waves_per_env(e);
     {
         // The XCDs of this device as workgroups see them (HW_REG_XCC_ID of 256 workgroups: 8, 4, 2 or one id per partition mode).
@@ -1070,33 +1060,61 @@ int mw_create(const mw_config *cfg, mw_engine **out)
         // draws from class b % n_xcc: where workgroup b runs on XCD b % n_xcc — every launch of a fresh process — an env's records,
         // keys and planes meet one L2 (the mesh tiles' fetch 50 -> 37 MB).  Locality only: nothing is wrong when the dispatcher's
         // round-robin starts elsewhere.
-        uint32_t *d_ids = nullptr, ids[256];
+        uint32_t *p = nullptr, ids[256];
         a.n_xcc = 0;
-        if (hipMalloc((void **)&d_ids, sizeof ids) == hipSuccess) {
-            hipLaunchKernelGGL(mw_xcc_probe_kernel, dim3(256), dim3(64), 0, 0, d_ids);
-            if (hipMemcpy(ids, d_ids, sizeof ids, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMalloc((void **)&p, sizeof ids) == hipSuccess) {
+            const DevBuf<uint32_t> d_ids(p);
+            hipLaunchKernelGGL(mw_xcc_probe_kernel, dim3(256), dim3(64), 0, 0, d_ids.get());
+            if (hipMemcpy(ids, d_ids.get(), sizeof ids, hipMemcpyDeviceToHost) == hipSuccess) {
                 uint32_t seen = 0u;
                 for (uint32_t v : ids) seen |= 1u << (v & 15u);
                 for (int n : {8, 4, 2}) if (seen == (1u << n) - 1u) a.n_xcc = n;
             }
-            (void)hipFree(d_ids);
         }
         if (a.n_xcc == 0) a.n_xcc = 1;      // (one id, or a set this code does not know: one class — the lists are about locality only)
     }
     if (const char *s = getenv("MW_DEBUG_FLAGS")) e->dbg_flags = atoi(s) & MW_DEBUG_BITS;
     if (const char *s = getenv("MW_K2Q")) e->use_k2q = atoi(s) != 0;
     if (const char *s = getenv("MW_GENERIC_RASTER")) e->generic_raster = atoi(s) != 0;
-#ifdef MW_PERF_HOOKS
-    if (getenv("MW_ENT_PROF")) { if (dev_alloc(e, &e->d_ent_prof, (size_t)16 * 2 * N * MW_MAX_MESH_ENTS * 8) != MW_OK) { g_create_error = e->err; mw_destroy(e); return MW_E_NOMEM; } }
-    if (getenv("MW_K2Q_PROF")) { if (dev_alloc(e, &e->d_k2q_prof, (size_t)N * 80) != MW_OK) { g_create_error = e->err; mw_destroy(e); return MW_E_NOMEM; } }
-#endif
     {
         // the quad kernel (mw_rasterq.hip) keeps an env's frame, quad lists and triangle records in LDS: frames up to 8192 pixels
         const int S = cfg->msaa == 4 ? 4 : 8;
         const int lds = mw_rasterq_lds_bytes(S, a.W, a.H, a.n_tiles, 1);
         e->k2q_ok = (cfg->msaa == 8 || cfg->msaa == 4) && frame_on_grid(a.W, a.H) && a.W <= 128 && a.H <= 128 && a.W * a.H <= 8192 && lds <= 64 * 1024;
     }
-    if (sync_gen_args(e) != MW_OK) { g_create_error = e->err; mw_destroy(e); return MW_E_HIP; }
+    return sync_gen_args(e);
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *mw_last_error(const mw_engine *e) { return e ? e->err.c_str() : g_create_error.c_str(); }
+
+int mw_create(const mw_config *cfg, mw_engine **out)
+{
+    if (!cfg || !out) return fail(nullptr, MW_E_INVALID, "null argument");
+    if (cfg->abi_version != MW_ABI_VERSION) return fail(nullptr, MW_E_INVALID, "ABI version mismatch: header %d, caller %d", MW_ABI_VERSION, cfg->abi_version);
+    if (cfg->num_envs <= 0 || cfg->max_ents < 0 || cfg->max_polys <= 0 || cfg->max_segs <= 0 || cfg->max_visible <= 0)
+        return fail(nullptr, MW_E_INVALID, "bad capacities");
+    if (cfg->rng_mode != MW_RNG_PHILOX && cfg->rng_mode != MW_RNG_PCG64) return fail(nullptr, MW_E_INVALID, "unknown rng_mode %d", cfg->rng_mode);
+    if (cfg->autoreset != MW_AUTORESET_OFF && cfg->autoreset != MW_AUTORESET_SAME_STEP && cfg->autoreset != MW_AUTORESET_NEXT_STEP)
+        return fail(nullptr, MW_E_INVALID, "unknown autoreset mode %d", cfg->autoreset);
+    if (cfg->rng_mode == MW_RNG_PCG64 && cfg->generator == MW_GEN_NONE)
+        return fail(nullptr, MW_E_INVALID, "MW_RNG_PCG64 (the reference's own numpy stream) needs a device generator");
+    if (cfg->max_ents > 64) return fail(nullptr, MW_E_CAPACITY, "max_ents > 64 (one entity slot per lane of the env's wavefront)");
+    if (cfg->msaa != 8 && cfg->msaa != 4 && cfg->msaa != 1) return fail(nullptr, MW_E_INVALID, "msaa must be 8, 4 or 1");
+    if (!frame_size_ok(cfg->obs_width, cfg->obs_height))
+        return fail(nullptr, MW_E_INVALID, "obs size %dx%d: 1 to %d x 1 to %d pixels", cfg->obs_width, cfg->obs_height, 255 * MW_TILE_W, 255 * MW_TILE_H);
+    if (cfg->max_visible > 60000) return fail(nullptr, MW_E_CAPACITY, "max_visible too large (16-bit draw ids)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, MW_E_DEVICE, "no HIP device available");
+    if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(nullptr, MW_E_DEVICE, "device %d out of range (%d devices)", cfg->device_id, ndev);
+    hipError_t st = hipSetDevice(cfg->device_id);
+    if (st != hipSuccess) return fail(nullptr, MW_E_HIP, "hipSetDevice: %s", hipGetErrorString(st));
+
+    mw_engine *e = new mw_engine();
+    if (const int rc = init_engine(e, cfg)) { g_create_error = e->err; mw_destroy(e); return rc; }
     *out = e;
     return MW_OK;
 }
@@ -1104,7 +1122,7 @@ int mw_create(const mw_config *cfg, mw_engine **out)
 void mw_destroy(mw_engine *e)
 {
     if (!e) return;
-    (void)hipSetDevice(e->cfg.device_id);
+    (void)hipSetDevice(e->cfg.device_id);       // (the members release their buffers, streams and events on the engine's device)
     (void)hipDeviceSynchronize();
 #ifdef MW_PERF_HOOKS
     if (e->d_k2q_prof) {
@@ -1124,7 +1142,7 @@ void mw_destroy(mw_engine *e)
     }
     if (getenv("MW_SLOW_STATS") && e->d_slow_count) {      // perf experiments only: the last frame's slow fragments per env
         std::vector<int32_t> h((size_t)e->cfg.num_envs * 4);
-        if (hipMemcpy(h.data(), e->d_slow_count, h.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(h.data(), e->d_slow_count.get(), h.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
             long long tot = 0, nz = 0, mx = 0;
             for (int i = 0; i < e->cfg.num_envs; ++i) { const int v = h[(size_t)e->cfg.num_envs + i] + h[(size_t)e->cfg.num_envs * 3 + i]; tot += v; nz += v > 0; mx = std::max<long long>(mx, v); }
             fprintf(stderr, "slow fragments: total %lld, envs with any %lld of %d, max %lld\n", tot, nz, e->cfg.num_envs, mx);
@@ -1139,22 +1157,6 @@ void mw_destroy(mw_engine *e)
         }
     }
 #endif
-    for (void *p : e->allocs) (void)hipFree(p);
-    if (e->d_texels) (void)hipFree(e->d_texels);
-    for (float *p : {e->d_mesh_pos, e->d_mesh_nrm, e->d_mesh_rgb, e->d_mesh_uv, e->d_mesh_stream, e->d_mesh_attr}) if (p) (void)hipFree(p);
-    if (e->d_mesh_vpos) (void)hipFree(e->d_mesh_vpos);
-    if (e->d_mesh_idx) (void)hipFree(e->d_mesh_idx);
-    if (e->d_view_keys) (void)hipFree(e->d_view_keys);
-    if (e->d_plane_cache) (void)hipFree(e->d_plane_cache);
-    if (e->d_mesh_keys) (void)hipFree(e->d_mesh_keys);
-    if (e->d_ent_list) (void)hipFree(e->d_ent_list);
-    if (e->d_tile_list) (void)hipFree(e->d_tile_list);
-    if (e->d_slow_envs) (void)hipFree(e->d_slow_envs);
-    for (void *q : {(void *)e->d_slow_count, (void *)e->d_slow_tris, (void *)e->d_slow_frags, (void *)e->d_slow_head}) if (q) (void)hipFree(q);
-    if (e->quad_stream) { (void)hipStreamDestroy(e->quad_stream); (void)hipEventDestroy(e->ev_mesh_fork); (void)hipEventDestroy(e->ev_mesh_join); }
-    if (e->side_stream) { (void)hipStreamDestroy(e->side_stream); (void)hipEventDestroy(e->ev_fork); (void)hipEventDestroy(e->ev_join); }
-    for (auto &ev : e->ev_used) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); (void)hipEventDestroy(ev.c); }
-    for (auto &ev : e->ev_free) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); (void)hipEventDestroy(ev.c); }
     delete e;
 }
 
@@ -1257,37 +1259,31 @@ int mw_upload_mesh(mw_engine *e, int32_t mesh_id, const float *pos, const float 
         }
         md.radius = (float)(std::sqrt(rc2) * 1.0001 + 1e-6);
     }
-    // repack all pools (uploads are rare)
+    // repack all pools (uploads are rare) into new ones: a failure leaves the installed pools, descriptors and MwArgs as they are
     size_t total = 0;
     size_t total_v = 0;
-    e->max_mesh_verts = 0;
+    int max_verts = 0;
     for (int i = 0; i < MW_MAX_MESH; ++i) {
         e->mesh_desc[i].first = (uint32_t)total; total += e->mesh_desc[i].ntris;
         e->mesh_desc[i].vfirst = (uint32_t)total_v; total_v += e->mesh_desc[i].nverts;
-        e->max_mesh_verts = std::max(e->max_mesh_verts, (int)e->mesh_desc[i].nverts);
+        max_verts = std::max(max_verts, (int)e->mesh_desc[i].nverts);
     }
-    if (e->d_mesh_vpos) { (void)hipFree(e->d_mesh_vpos); e->d_mesh_vpos = nullptr; }
-    if (e->d_mesh_idx) { (void)hipFree(e->d_mesh_idx); e->d_mesh_idx = nullptr; }
-    HIP_TRY(e, hipMalloc((void **)&e->d_mesh_vpos, std::max<size_t>(total_v, 1) * 16));
-    HIP_TRY(e, hipMalloc((void **)&e->d_mesh_idx, total * 8));
-    for (float **p : {&e->d_mesh_pos, &e->d_mesh_nrm, &e->d_mesh_rgb, &e->d_mesh_uv, &e->d_mesh_stream, &e->d_mesh_attr})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    HIP_TRY(e, hipMalloc((void **)&e->d_mesh_pos, total * 4 * MW_MESH_POS_STRIDE));
-    HIP_TRY(e, hipMalloc((void **)&e->d_mesh_nrm, total * 36));
-    HIP_TRY(e, hipMalloc((void **)&e->d_mesh_rgb, total * 36));
-    HIP_TRY(e, hipMalloc((void **)&e->d_mesh_uv, total * 24));
-    HIP_TRY(e, hipMalloc((void **)&e->d_mesh_stream, total * 48));
-    HIP_TRY(e, hipMalloc((void **)&e->d_mesh_attr, total * 96));
+    DevBuf<float> d_pos, d_nrm, d_rgb, d_uv, d_stream, d_attr; DevBuf<float4> d_vpos; DevBuf<uint2> d_idx;
+    int rc;
+    if ((rc = dev_alloc(e, d_vpos, total_v, false)) || (rc = dev_alloc(e, d_idx, total, false)) || (rc = dev_alloc(e, d_pos, total * MW_MESH_POS_STRIDE, false)) ||
+        (rc = dev_alloc(e, d_nrm, total * 9, false)) || (rc = dev_alloc(e, d_rgb, total * 9, false)) || (rc = dev_alloc(e, d_uv, total * 6, false)) ||
+        (rc = dev_alloc(e, d_stream, total * 12, false)) || (rc = dev_alloc(e, d_attr, total * 24, false)))
+        return rc;
     for (int i = 0; i < MW_MAX_MESH; ++i) {
         const size_t n = e->mesh_desc[i].ntris, off = (size_t)e->mesh_desc[i].first * 9;
         if (!n) continue;
-        HIP_TRY(e, hipMemcpy(e->d_mesh_pos + (size_t)e->mesh_desc[i].first * MW_MESH_POS_STRIDE, e->mesh_pos[i].data(), n * 4 * MW_MESH_POS_STRIDE, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(e->d_mesh_nrm + off, e->mesh_nrm[i].data(), n * 36, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(e->d_mesh_rgb + off, e->mesh_rgb[i].data(), n * 36, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(e->d_mesh_uv + (size_t)e->mesh_desc[i].first * 6, e->mesh_uv[i].data(), n * 24, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(d_pos.get() + (size_t)e->mesh_desc[i].first * MW_MESH_POS_STRIDE, e->mesh_pos[i].data(), n * 4 * MW_MESH_POS_STRIDE, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(d_nrm.get() + off, e->mesh_nrm[i].data(), n * 36, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(d_rgb.get() + off, e->mesh_rgb[i].data(), n * 36, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(d_uv.get() + (size_t)e->mesh_desc[i].first * 6, e->mesh_uv[i].data(), n * 24, hipMemcpyHostToDevice));
         if (e->mesh_desc[i].nverts)
-            HIP_TRY(e, hipMemcpy(e->d_mesh_vpos + e->mesh_desc[i].vfirst, e->mesh_vtab[i].data(), (size_t)e->mesh_desc[i].nverts * 16, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(e->d_mesh_idx + e->mesh_desc[i].first, e->mesh_itab[i].data(), n * 8, hipMemcpyHostToDevice));
+            HIP_TRY(e, hipMemcpy(d_vpos.get() + e->mesh_desc[i].vfirst, e->mesh_vtab[i].data(), (size_t)e->mesh_desc[i].nverts * 16, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(d_idx.get() + e->mesh_desc[i].first, e->mesh_itab[i].data(), n * 8, hipMemcpyHostToDevice));
         {
             // the scatter kernel's stream: the triangles in rasterisation order, 48 bytes each (9 coordinates, the triangle's index)
             std::vector<float> st(n * 12, 0.0f);
@@ -1298,7 +1294,7 @@ int mw_upload_mesh(mw_engine *e, int32_t mesh_id, const float *pos, const float 
                 memcpy(&st[k * 12], &P[(size_t)tri * MW_MESH_POS_STRIDE], 36);
                 memcpy(&st[k * 12 + 9], &tri, 4);
             }
-            HIP_TRY(e, hipMemcpy(e->d_mesh_stream + (size_t)e->mesh_desc[i].first * 12, st.data(), n * 48, hipMemcpyHostToDevice));
+            HIP_TRY(e, hipMemcpy(d_stream.get() + (size_t)e->mesh_desc[i].first * 12, st.data(), n * 48, hipMemcpyHostToDevice));
             // ... and their vertex attributes in the same order, 96 bytes each (normals, colours, texture coordinates)
             std::vector<float> at(n * 24, 0.0f);
             for (size_t k = 0; k < n; ++k) {
@@ -1308,11 +1304,16 @@ int mw_upload_mesh(mw_engine *e, int32_t mesh_id, const float *pos, const float 
                 memcpy(&at[k * 24 + 9], &e->mesh_rgb[i][(size_t)tri * 9], 36);
                 memcpy(&at[k * 24 + 18], &e->mesh_uv[i][(size_t)tri * 6], 24);
             }
-            HIP_TRY(e, hipMemcpy(e->d_mesh_attr + (size_t)e->mesh_desc[i].first * 24, at.data(), n * 96, hipMemcpyHostToDevice));
+            HIP_TRY(e, hipMemcpy(d_attr.get() + (size_t)e->mesh_desc[i].first * 24, at.data(), n * 96, hipMemcpyHostToDevice));
         }
     }
+    // install: the frames that may still read the old pools and descriptors finish first
+    HIP_TRY(e, hipDeviceSynchronize());
     HIP_TRY(e, hipMemcpy(e->d_meshdesc, e->mesh_desc.data(), sizeof(MwMeshDesc) * MW_MAX_MESH, hipMemcpyHostToDevice));
-    e->args.mesh_pos = e->d_mesh_pos; e->args.mesh_nrm = e->d_mesh_nrm; e->args.mesh_rgb = e->d_mesh_rgb; e->args.mesh_uv = e->d_mesh_uv;
+    e->args.mesh_pos = d_pos.get(); e->args.mesh_nrm = d_nrm.get(); e->args.mesh_rgb = d_rgb.get(); e->args.mesh_uv = d_uv.get();
+    e->d_mesh_pos = std::move(d_pos); e->d_mesh_nrm = std::move(d_nrm); e->d_mesh_rgb = std::move(d_rgb); e->d_mesh_uv = std::move(d_uv);
+    e->d_mesh_stream = std::move(d_stream); e->d_mesh_attr = std::move(d_attr); e->d_mesh_vpos = std::move(d_vpos); e->d_mesh_idx = std::move(d_idx);
+    e->max_mesh_verts = max_verts;
     if (e->d_gen_live && sync_gen_args(e) != MW_OK) return MW_E_HIP;
     e->have_meshes = true;
     e->max_mesh_tris = std::max(e->max_mesh_tris, (int)ntris);
@@ -1403,25 +1404,26 @@ int mw_set_gen_program(mw_engine *e, const mw_gen_program *prog, const mw_poly *
     MwProgram hp{};
     hp.p = *prog;
     hp.n_polys = n_polys; hp.n_segs = n_segs;
-    mw_poly *d_polys = nullptr; int32_t *d_room = nullptr, *d_surf = nullptr; double *d_m = nullptr, *d_segs = nullptr;
-    int rc = MW_OK;
-    if (rc == MW_OK) rc = dev_alloc(e, &d_polys, (size_t)n_polys);
-    if (rc == MW_OK) rc = dev_alloc(e, &d_room, (size_t)n_polys);
-    if (rc == MW_OK) rc = dev_alloc(e, &d_surf, (size_t)n_polys);
-    if (rc == MW_OK) rc = dev_alloc(e, &d_m, (size_t)n_polys * 8);
-    if (rc == MW_OK) rc = dev_alloc(e, &d_segs, (size_t)n_segs * 4);
-    if (rc == MW_OK && !e->d_prog) rc = dev_alloc(e, &e->d_prog, 1);
-    if (rc != MW_OK) return rc;
+    // the new tables are built beside the installed ones: a failure leaves those, the program block and MwArgs as they are
+    DevBuf<mw_poly> d_polys; DevBuf<int32_t> d_room, d_surf; DevBuf<double> d_m, d_segs;
+    int rc;
+    if ((rc = dev_alloc(e, d_polys, (size_t)n_polys)) || (rc = dev_alloc(e, d_room, (size_t)n_polys)) || (rc = dev_alloc(e, d_surf, (size_t)n_polys)) ||
+        (rc = dev_alloc(e, d_m, (size_t)n_polys * 8)) || (rc = dev_alloc(e, d_segs, (size_t)n_segs * 4)) || (!e->d_prog && (rc = dev_alloc(e, e->d_prog, 1))))
+        return rc;
     if (n_polys > 0) {
-        HIP_TRY(e, hipMemcpy(d_polys, polys, sizeof(mw_poly) * (size_t)n_polys, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(d_room, poly_room, 4 * (size_t)n_polys, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(d_surf, poly_surf, 4 * (size_t)n_polys, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(d_m, poly_m, 64 * (size_t)n_polys, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(d_polys.get(), polys, sizeof(mw_poly) * (size_t)n_polys, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(d_room.get(), poly_room, 4 * (size_t)n_polys, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(d_surf.get(), poly_surf, 4 * (size_t)n_polys, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(d_m.get(), poly_m, 64 * (size_t)n_polys, hipMemcpyHostToDevice));
     }
-    if (n_segs > 0) HIP_TRY(e, hipMemcpy(d_segs, segs, 32 * (size_t)n_segs, hipMemcpyHostToDevice));
-    hp.polys = d_polys; hp.poly_room = d_room; hp.poly_surf = d_surf; hp.poly_m = d_m; hp.segs = d_segs;
-    HIP_TRY(e, hipMemcpy(e->d_prog, &hp, sizeof hp, hipMemcpyHostToDevice));
-    e->args.prog = e->d_prog;
+    if (n_segs > 0) HIP_TRY(e, hipMemcpy(d_segs.get(), segs, 32 * (size_t)n_segs, hipMemcpyHostToDevice));
+    hp.polys = d_polys.get(); hp.poly_room = d_room.get(); hp.poly_surf = d_surf.get(); hp.poly_m = d_m.get(); hp.segs = d_segs.get();
+    // install: the device finishes whatever may still read the program block and the previous program's tables, which then go
+    HIP_TRY(e, hipDeviceSynchronize());
+    HIP_TRY(e, hipMemcpy(e->d_prog.get(), &hp, sizeof hp, hipMemcpyHostToDevice));
+    e->d_prog_polys = std::move(d_polys); e->d_prog_room = std::move(d_room); e->d_prog_surf = std::move(d_surf);
+    e->d_prog_m = std::move(d_m); e->d_prog_segs = std::move(d_segs);
+    e->args.prog = e->d_prog.get();
     if (e->cfg.shared_geometry && n_polys > 0) {        // no texture randomisation: the template IS the geometry
         const int r2 = mw_set_geometry(e, -1, polys, n_polys, segs, n_segs);
         if (r2 != MW_OK) return r2;
@@ -1553,14 +1555,8 @@ int mw_render_view(mw_engine *e, int32_t env, int32_t view_flags, int32_t width,
     uint32_t *keys = nullptr;
     if (e->have_meshes) {
         const size_t need = (size_t)width * height * msaa * 4;
-        if (need > e->view_keys_bytes) {
-            HIP_TRY(e, hipStreamSynchronize(st));
-            if (e->d_view_keys) (void)hipFree(e->d_view_keys);
-            e->d_view_keys = nullptr; e->view_keys_bytes = 0;
-            HIP_TRY(e, hipMalloc((void **)&e->d_view_keys, need));
-            e->view_keys_bytes = need;
-        }
-        keys = e->d_view_keys;
+        if (const int rc = grow(e, e->d_view_keys, e->view_keys_bytes, need, 1)) return rc;
+        keys = e->d_view_keys.get();
         HIP_TRY(e, hipMemsetAsync(keys, 0xFF, need, st));
         hipLaunchKernelGGL(mw_view_mesh_kernel, dim3(128), dim3(256), 0, st, width, height, msaa, env, (const float *)b.envhdr, b.mesh_pos, keys);
     }
@@ -1643,7 +1639,7 @@ int mw_debug_get_slow_heads(mw_engine *e, uint32_t *host_out, void *stream)
     if (!e->d_slow_head) return fail(e, MW_E_INVALID, "mw_debug_get_slow_heads: this engine has no mesh path buffers");
     ON_DEVICE(e);
     HIP_TRY(e, hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(e, hipMemcpy(host_out, e->d_slow_head, sizeof(uint32_t) * (size_t)e->cfg.num_envs * e->args.W * e->args.H, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(host_out, e->d_slow_head.get(), sizeof(uint32_t) * (size_t)e->cfg.num_envs * e->args.W * e->args.H, hipMemcpyDeviceToHost));
     return MW_OK;
 }
 
@@ -1702,12 +1698,12 @@ int mw_kernel_time_ms(mw_engine *e, int32_t reset, double *raster_ms, double *se
     double r = 0, s = 0;
     int64_t n = 0;
     for (auto &ev : e->ev_used) {
-        (void)hipEventSynchronize(ev.c);
+        (void)hipEventSynchronize(ev.c.get());
         float t1 = 0, t2 = 0;
-        (void)hipEventElapsedTime(&t1, ev.a, ev.b);
-        (void)hipEventElapsedTime(&t2, ev.b, ev.c);
+        (void)hipEventElapsedTime(&t1, ev.a.get(), ev.b.get());
+        (void)hipEventElapsedTime(&t2, ev.b.get(), ev.c.get());
         s += t1; r += t2; ++n;
-        e->ev_free.push_back(ev);
+        e->ev_free.push_back(std::move(ev));
     }
     e->ev_used.clear();
     if (raster_ms) *raster_ms = n ? r / n : 0.0;

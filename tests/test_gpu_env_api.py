@@ -1370,3 +1370,123 @@ def test_big_host_built_worlds_match_the_oracle(rows, open_plan, occlusion, monk
         want = pyoracle.render(scene_from_env(env))["rgb"]
         assert np.array_equal(o, want), (rows, t, int((o != want).any(-1).sum()))
     env.close()
+
+
+def test_set_gen_program_again_gives_the_frames_of_one_program(monkeypatch):
+    """mw_set_gen_program replaces the placement program's tables (the previous ones are released): installed again before the
+    first reset and again with frames in flight, the same program must give the frames of an engine that installed it once —
+    through the resets the program generates and Sign's step rule, which reads its tables (20-step episodes: auto-resets mid-run)."""
+    import torch
+    from miniworld_amd import engine as eng
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    installed = []
+    set_gen_program = eng.Engine.set_gen_program
+
+    def keep(self, *args):
+        installed.append(args)
+        return set_gen_program(self, *args)
+
+    monkeypatch.setattr(eng.Engine, "set_gen_program", keep)
+    n, steps = 256, 60
+    g = torch.Generator(device="cuda").manual_seed(3)
+    acts = torch.randint(0, 4, (steps, n), generator=g, device="cuda", dtype=torch.int32)
+
+    def run(again):
+        vec = MiniWorldVecEnv("MiniWorld-Sign-v0", n, seed=4)
+        prog = installed[-1]
+        for _ in range(again):
+            vec.engine.set_gen_program(*prog)
+        vec.reset()
+        frames = []
+        for t in range(steps):
+            if t == steps // 2:
+                for _ in range(again):
+                    vec.engine.set_gen_program(*prog)
+            vec.step(acts[t])
+            frames.append(vec.obs.clone())
+        vec.engine.check()
+        out = torch.stack(frames).cpu().numpy()
+        vec.close()
+        return out
+
+    a, b = run(0), run(4)
+    assert 1.0 < a.mean() < 254.0
+    bad = np.argwhere((a != b).reshape(a.shape[0], -1).any(axis=1)).ravel()
+    assert bad.size == 0, f"frames {bad.tolist()} differ after the program was installed again"
+
+
+def test_assets_replaced_after_the_first_frame_draw_like_the_final_assets():
+    """mw_upload_mesh on an existing mesh id repacks the mesh pools into new ones, mw_upload_texture after the first frame grows
+    the texture pool or rewrites it in place: once the final assets are uploaded, the frames equal those of an engine built with
+    them from the start."""
+    import torch
+    from miniworld_amd import assets
+    from miniworld_amd.entity import COLOR_NAMES
+    from miniworld_amd.objmesh import ObjMesh
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    n, steps = 256, 30
+    g = torch.Generator(device="cuda").manual_seed(5)
+    acts = torch.randint(0, 5, (steps, n), generator=g, device="cuda", dtype=torch.int32)
+
+    def run(replace):
+        vec = MiniWorldVecEnv("MiniWorld-PickupObjects-v0", n, seed=6)
+        vec.reset()                                             # the first frame
+        if replace:
+            mesh_id = vec.mesh_ids["ball_" + COLOR_NAMES[0]]
+            other, right = ObjMesh.get("key_" + COLOR_NAMES[1]), ObjMesh.get("ball_" + COLOR_NAMES[0])
+            name, tex_id = next(iter(vec.tex_ids.items()))
+            tex = assets.texture_rgb_bottom_up(name)
+            noise = np.random.default_rng(0).integers(0, 256, (2 * tex.shape[0], 2 * tex.shape[1], 3), dtype=np.uint8)
+            vec.engine.upload_mesh(mesh_id, other.verts, other.norms, other.texcs, other.colors)
+            vec.engine.upload_texture(tex_id, noise)           # a larger pool
+            vec.engine.render(vec.obs)
+            vec.engine.upload_mesh(mesh_id, right.verts, right.norms, right.texcs, right.colors)
+            vec.engine.upload_texture(tex_id, tex)             # the same pool, rewritten
+        frames = []
+        for t in range(steps):
+            vec.step(acts[t])
+            frames.append(vec.obs.clone())
+        vec.engine.check()
+        out = torch.stack(frames).cpu().numpy()
+        vec.close()
+        return out
+
+    a, b = run(False), run(True)
+    assert 1.0 < a.mean() < 254.0
+    bad = np.argwhere((a != b).reshape(a.shape[0], -1).any(axis=1)).ravel()
+    assert bad.size == 0, f"frames {bad.tolist()} differ from those of the engine built with the final assets"
+
+
+def test_engines_created_and_closed_again_and_again(monkeypatch):
+    """Every device buffer, stream and event of an engine goes with it: ten rounds of creating, stepping and closing each engine
+    shape — spare worlds on and off, mesh entities, final observations, the Maze's spare refills on the side stream — run without
+    an error.  (The device's free memory over the rounds is printed, not asserted: other work shares the device.)"""
+    import torch
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    n = 64
+    shapes = [("MiniWorld-Hallway-v0", "1", {}), ("MiniWorld-Hallway-v0", "0", {}), ("MiniWorld-PickupObjects-v0", None, {}),
+              ("MiniWorld-Hallway-v0", None, {"final_obs": True, "want_depth": True}), ("MiniWorld-MazeS3-v0", None, {})]
+    act = torch.zeros(n, dtype=torch.int32, device="cuda")
+
+    def cycle(env_id, spare, kw):
+        if spare is None:
+            monkeypatch.delenv("MW_SPARE", raising=False)
+        else:
+            monkeypatch.setenv("MW_SPARE", spare)
+        vec = MiniWorldVecEnv(env_id, n, seed=1, **kw)
+        vec.reset()
+        for _ in range(3):
+            vec.step(act)
+        vec.engine.check()
+        vec.close()
+
+    for shape in shapes:                                        # first round: code objects, torch's caching allocator
+        cycle(*shape)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(10):
+        for shape in shapes:
+            cycle(*shape)
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info()[0]
+    print(f"device free memory over 10 rounds of {len(shapes)} engine shapes: {free1 - free0:+d} bytes ({free0} -> {free1})")
