@@ -284,7 +284,10 @@ int mw_set_geometry(mw_engine *e, int32_t env, const mw_poly *polys, int32_t n_p
 /* state injection / inspection (synchronous) */
 /* reads one geometry set back (polys: max_polys entries, segs: max_segs*4 doubles) */
 int mw_get_geometry(mw_engine *e, int32_t env, mw_poly *polys, int32_t *n_polys, double *segs, int32_t *n_segs);
-/* (clears a pending next-step auto-reset of the envs it writes) */
+/* (clears a pending next-step auto-reset of the envs it writes)
+ * Domain: |agent_dir| < 1e6 radians — the agent's heading feeds the f64 sin / cos of the dynamics and the camera
+ * (mw_math.h sincos_det, within 1 ulp of libm there and no further).  An entity's dir may be any finite angle: it only
+ * feeds the float rotation of glRotatef (mw_glmath.h sincosf_glibc, glibc's bits for every float). */
 int mw_set_state(mw_engine *e, int32_t first_env, int32_t count, const mw_state_view *host);
 /* Test hook: host double[num_envs][3] = forward_step, forward_drift, turn_step to use in
  * the next steps instead of the defaults / device RNG draws (miniworld.py:678-680);
@@ -349,6 +352,11 @@ int mw_selftest_sort(const uint32_t *keys, const int32_t *n, int32_t blocks, uin
  * n_bad[1] = inputs where the lod taken from rho^2's bits differs from llvmpipe's float arithmetic (pyramids of 1 .. 12
  * levels); examples[2][32] = the first offending bit patterns of each. */
 int mw_selftest_q(unsigned long long *n_bad, uint32_t *examples);
+/* ... and the rotations' and headings' sin / cos: sums[512] = per binade (sign | exponent) of the input, the sum mod 2^64
+ * of mwcheck::hash_sincosf(x, sin, cos) (mw_selftest.h) of mwgl::sincosf_glibc over all 2^32 floats; sums64[120] = per
+ * bin of mwcheck::heading_sample, the sum of mwcheck::hash_sincos(x, sin, cos) of mw::sincos_det over inputs 0 .. n64 - 1
+ * of that stream.  The host forms the same sums from libm's sinf / cosf and the oracle's mwo_sincos. */
+int mw_selftest_sincosf(unsigned long long *sums, unsigned long long n64, unsigned long long *sums64);
 
 /* render_obs / render_depth only (miniworld.py:1177-1236) */
 int mw_render(mw_engine *e, uint8_t *d_obs, float *d_depth, void *stream);

@@ -17,18 +17,14 @@
 #include <stdint.h>
 #include <math.h>
 #include <string.h>
-
-#ifdef __HIPCC__
-#define MW_HD __host__ __device__ inline
-#else
-#define MW_HD inline
-#endif
+#include "mw_hd.h"
 
 namespace mwgl {
 
 // ---------------------------------------------------------------- glibc 2.35 sinf / cosf (FMA multiarch variant)
-// Mesa's _math_matrix_rotate calls sinf / cosf: restated (sysdeps/ieee754/flt-32/s_sinf.c, sincosf.h) so that the
-// device produces glibc's bits; checked against libm over all floats of |x| < 120 (tests/test_host_logic_cpu.py).
+// Mesa's _math_matrix_rotate calls sinf / cosf: restated (sysdeps/ieee754/flt-32/s_sinf.c, s_cosf.c, sincosf.h) so that the
+// device produces glibc's bits for every float: checked against libm over all 2^32 of them on the host
+// (tests/test_engine_math_cpu.py) and on the device (mw_selftest_sincosf, tests/test_gpu_numerics.py).
 MW_HD float sincosf_poly(double x, double x2, int tab, int n)
 {
     // tab 0 / 1: the table and its negated-cosine twin (quadrants 2, 3)
@@ -48,9 +44,33 @@ MW_HD uint32_t f2u(float x) { uint32_t u; memcpy(&u, &x, 4); return u; }
 MW_HD float u2f(uint32_t u) { float x; memcpy(&x, &u, 4); return x; }
 MW_HD uint32_t abstop12(float x) { return (f2u(x) >> 20) & 0x7ffu; }
 
+// 4 / pi in 8-bit steps: entry i = floor(4 / pi * 2^(7 + 8 i)) mod 2^32 (24 entries, 192 bits), so that any three entries
+// four apart are one 96-bit window of its bits.  Computed from 4 / pi itself; tests/test_engine_math_cpu.py recomputes it.
+constexpr uint32_t kInvPio4[24] = {
+    0x000000a2u, 0x0000a2f9u, 0x00a2f983u, 0xa2f9836eu, 0xf9836e4eu, 0x836e4e44u, 0x6e4e4415u, 0x4e441529u,
+    0x441529fcu, 0x1529fc27u, 0x29fc2757u, 0xfc2757d1u, 0x2757d1f5u, 0x57d1f534u, 0xd1f534ddu, 0xf534ddc0u,
+    0x34ddc0dbu, 0xddc0db62u, 0xc0db6295u, 0xdb629599u, 0x6295993cu, 0x95993c43u, 0x993c4390u, 0x3c439041u};
+
+// reduce_large, for 120 <= |y| < inf: the mantissa (shifted by the exponent's low 3 bits) times the 96 bits of 4 / pi the
+// exponent's next 4 bits select gives |y| * 2 / pi mod 4 in fixed point with 62 fraction bits.  n: the quadrant of |y|;
+// returns |y| - n pi / 2, in [-pi / 4, pi / 4].
+MW_HD double sincosf_reduce_large(uint32_t xi, int &n)
+{
+    const uint32_t *arr = &kInvPio4[(xi >> 26) & 15u];
+    const uint32_t m = ((xi & 0xffffffu) | 0x800000u) << ((xi >> 23) & 7u);
+    const uint64_t r0 = (uint32_t)(m * arr[0]);             // only the low 32 bits of this product reach the result
+    const uint64_t r1 = (uint64_t)m * arr[4];
+    const uint64_t r2 = (uint64_t)m * arr[8];
+    uint64_t res = ((r2 >> 32) | (r0 << 32)) + r1;
+    const uint64_t q = (res + (1ull << 61)) >> 62;
+    res -= q << 62;
+    n = (int)q;
+    return (double)(int64_t)res * 0x1.921FB54442D18p-62;
+}
+
 MW_HD void sincosf_glibc(float y, float &sn, float &cs)
 {
-    // valid for |y| < 120 (angles of a few turns); beyond that the reference's own libm takes another path
+    // every float: |y| < 120 takes the fast reduction, larger finite ones the 4 / pi table, +-inf and NaN give NaN
     double x = y;
     if (abstop12(y) < abstop12(0x1.921FB6p-1f)) {
         if (abstop12(y) < abstop12(0x1p-12f)) { sn = y; cs = 1.0f; return; }
@@ -59,11 +79,21 @@ MW_HD void sincosf_glibc(float y, float &sn, float &cs)
         cs = sincosf_poly(x, x2, 0, 1);
         return;
     }
-    const double r = x * 0x1.45F306DC9C883p+23;
-    const int n = ((int32_t)r + 0x800000) >> 24;
-    x = fma(-(double)n, 0x1.921FB54442D18p0, x);
-    const double sg = ((n & 3) == 1 || (n & 3) == 2) ? -1.0 : 1.0;
-    const int tab = (n & 2) ? 1 : 0;
+    int n, q;       // q: the quadrant with y's sign folded in (picks the sign and the table; n picks sin or cos)
+    if (abstop12(y) < abstop12(120.0f)) {
+        const double r = x * 0x1.45F306DC9C883p+23;
+        n = ((int32_t)r + 0x800000) >> 24;
+        x = fma(-(double)n, 0x1.921FB54442D18p0, x);
+        q = n;
+    } else if (abstop12(y) < abstop12(INFINITY)) {
+        x = sincosf_reduce_large(f2u(y), n);
+        q = n + (int)(f2u(y) >> 31);
+    } else {
+        sn = cs = y - y;
+        return;
+    }
+    const double sg = ((q & 3) == 1 || (q & 3) == 2) ? -1.0 : 1.0;
+    const int tab = (q & 2) ? 1 : 0;
     sn = sincosf_poly(x * sg, x * x, tab, n);
     cs = sincosf_poly(x * sg, x * x, tab, n ^ 1);
 }

@@ -5,15 +5,17 @@
 // engine evaluates the classic published algorithm instead (Sun fdlibm: two-stage
 // Cody-Waite reduction by pi/2 followed by the k_sin / k_cos minimax kernels), using only
 // IEEE-754 + - * in a fixed order.  Compiled with -ffp-contract=off the result is a pure
-// function of the input bits on any conforming target.  Accurate to < 1 ulp, |x| < 1e6.
+// function of the input bits on any conforming target.  Valid for |x| < 1e6 (the headings' domain, mw_set_state):
+// within 1 ulp of libm there and bit-identical to the oracle's mwo_sincos (tests/test_engine_math_cpu.py on the host,
+// mw_selftest_sincosf on the device); the two-stage reduction breaks down from about 1.6e6.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "mw_hd.h"
 
 namespace mw {
 
 struct SinCos { double s, c; };
 
-__host__ __device__ inline double kernel_sin(double x, double tail)
+MW_HD double kernel_sin(double x, double tail)
 {
     const double z = x * x;
     const double v = z * x;
@@ -24,7 +26,7 @@ __host__ __device__ inline double kernel_sin(double x, double tail)
     return x - ((z * (0.5 * tail - v * r) - tail) - v * -1.66666666666666324348e-01);
 }
 
-__host__ __device__ inline double kernel_cos(double x, double tail)
+MW_HD double kernel_cos(double x, double tail)
 {
     const double z = x * x;
     const double r = z * (4.16666666666666019037e-02 +
@@ -37,7 +39,7 @@ __host__ __device__ inline double kernel_cos(double x, double tail)
     return w + (((1.0 - w) - hz) + (z * r - x * tail));
 }
 
-__host__ __device__ inline SinCos sincos_det(double x)
+MW_HD SinCos sincos_det(double x)
 {
     const double t = x * 6.36619772367581382433e-01;            // x * 2/pi
     const double fn = (t >= 0.0) ? (double)(long long)(t + 0.5) : -(double)(long long)(0.5 - t);

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mw_raster_common.h"
+#include "mw_math.h"
+#include "mw_selftest.h"
 
 extern "C" __global__ void mw_selftest_rcp_kernel(unsigned long long *bad_per_exp, uint32_t *examples, unsigned int *n_examples)
 {
@@ -116,5 +118,57 @@ extern "C" int mw_selftest_q(unsigned long long *host_n_bad /*[2]*/, uint32_t *h
     (void)hipMemcpy(host_n_bad, d_n, 16, hipMemcpyDeviceToHost);
     (void)hipMemcpy(host_examples, d_ex, 64 * 4, hipMemcpyDeviceToHost);
     (void)hipFree(d_n); (void)hipFree(d_ex);
+    return 0;
+}
+
+// mw_selftest_sincosf: mwgl::sincosf_glibc (glRotatef's sinf / cosf: every Box, MeshEnt and ImageFrame) for ALL 2^32 floats,
+// and mw::sincos_det (the f64 headings) over n64 inputs of mwcheck::heading_sample.  The device holds neither libm nor the
+// oracle, so both sides reduce their results to per-binade sums of mwcheck's hash of (input, sin, cos), and the test
+// compares the sums.  Block b of the f32 grid covers 2^17 floats of binade b / 64: one global atomic per block.
+extern "C" __global__ __launch_bounds__(256) void mw_selftest_sincosf_kernel(unsigned long long *sums /*[512]*/)
+{
+    __shared__ unsigned long long acc;
+    if (threadIdx.x == 0) acc = 0ull;
+    __syncthreads();
+    const uint32_t binade = blockIdx.x >> 6, base = binade << 23 | (blockIdx.x & 63u) << 17;
+    unsigned long long h = 0ull;
+    for (uint32_t k = threadIdx.x; k < (1u << 17); k += 256u) {
+        const uint32_t b = base | k;
+        float s, c;
+        mwgl::sincosf_glibc(__uint_as_float(b), s, c);
+        h += mwcheck::hash_sincosf(b, s, c);
+    }
+    atomicAdd(&acc, h);
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(&sums[binade], acc);
+}
+
+extern "C" __global__ __launch_bounds__(256) void mw_selftest_sincos_det_kernel(unsigned long long n, unsigned long long *sums /*[120]*/)
+{
+    __shared__ unsigned long long acc[120];
+    for (int k = threadIdx.x; k < 120; k += 256) acc[k] = 0ull;
+    __syncthreads();
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256u) {
+        int bin;
+        const double x = mwcheck::heading_sample(i, bin);
+        const mw::SinCos r = mw::sincos_det(x);
+        atomicAdd(&acc[bin], (unsigned long long)mwcheck::hash_sincos(x, r.s, r.c));
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < 120; k += 256)
+        if (acc[k]) atomicAdd(&sums[k], acc[k]);
+}
+
+extern "C" int mw_selftest_sincosf(unsigned long long *host_sums /*[512]*/, unsigned long long n64, unsigned long long *host_sums64 /*[120]*/)
+{
+    unsigned long long *d = nullptr;
+    if (hipMalloc((void **)&d, (512 + 120) * 8) != hipSuccess) return -1;
+    (void)hipMemset(d, 0, (512 + 120) * 8);
+    hipLaunchKernelGGL(mw_selftest_sincosf_kernel, dim3(512 * 64), dim3(256), 0, 0, d);
+    hipLaunchKernelGGL(mw_selftest_sincos_det_kernel, dim3(256 * 32), dim3(256), 0, 0, n64, d + 512);
+    if (hipDeviceSynchronize() != hipSuccess) { (void)hipFree(d); return -2; }
+    (void)hipMemcpy(host_sums, d, 512 * 8, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(host_sums64, d + 512, 120 * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
     return 0;
 }

@@ -58,7 +58,34 @@ static inline double reduce_fast(double x, const sincosf_tab *p, int *np)
     return fma(-(double)n, p->hpi, x);
 }
 
-/* valid for |x| < 120 (the reference's angles are a few turns at most); beyond that libm's own */
+/* 4/pi to 192 bits, floor(4/pi * 2^191), most significant word first (computed from 4/pi itself; checked by
+ * tests/test_engine_math_cpu.py) */
+static const uint64_t FOUR_OVER_PI[3] = {0xa2f9836e4e441529ull, 0xfc2757d1f534ddc0ull, 0xdb6295993c439041ull};
+
+/* glibc's reduce_large, for finite |y| >= 120.  y = m 2^(E - 150), m the 24-bit significand, E the biased exponent
+ * (133 .. 254); write E - 128 = 8 i + k with 0 <= k < 8.  glibc multiplies m 2^k by the 96 bits of 4/pi that end at
+ * 2^-(71 + 8 i), W = floor(4/pi 2^(71 + 8 i)) mod 2^96, and keeps bits 32 .. 95 of the product: |y| * 2/pi mod 4 with 62
+ * fraction bits, short by what the bits of 4/pi below W would add (the higher bits give whole turns).  *quadrant: the
+ * nearest multiple of pi/2 (mod 4); returns |y| less that multiple, in [-pi/4, pi/4]. */
+static double reduce_large(float y, int *quadrant)
+{
+    uint32_t u;
+    memcpy(&u, &y, 4);
+    const unsigned e = (u >> 23) & 0xff, i = ((e - 128) >> 3) & 15, k = (e - 128) & 7;
+    const unsigned shift = 120 - 8 * i;             /* W = (4/pi 2^191 >> shift) mod 2^96 */
+    const unsigned __int128 top = ((unsigned __int128)FOUR_OVER_PI[0] << 64) | FOUR_OVER_PI[1];
+    unsigned __int128 w = shift >= 64 ? top >> (shift - 64) : (top << (64 - shift)) | (FOUR_OVER_PI[2] >> shift);
+    w &= ((unsigned __int128)1 << 96) - 1;
+    const uint64_t m = (uint64_t)((u & 0x7fffff) | 0x800000) << k;      /* < 2^31: the product fits in 127 bits */
+    const uint64_t t = (uint64_t)((m * w) >> 32);                        /* 2.62 fixed point, mod 4 */
+    const unsigned n = (unsigned)((t + (1ull << 61)) >> 62) & 3;
+    const int64_t r = (int64_t)(t - ((uint64_t)n << 62));
+    *quadrant = (int)n;
+    return (double)r * 0x1.921FB54442D18p-62;
+}
+
+/* every float, as glibc: |y| < 120 by reduce_fast, larger finite values by reduce_large with y's sign folded into the
+ * quadrant that picks the sign and the table, +-inf and NaN give NaN */
 float mwo_sinf(float y)
 {
     double x = y;
@@ -68,10 +95,17 @@ float mwo_sinf(float y)
         if (abstop12(y) < abstop12(0x1p-12f)) return y;
         return sincosf_poly(x, x * x, p, 0);
     }
-    if (!(abstop12(y) < abstop12(120.0f))) return sinf(y);
-    x = reduce_fast(x, p, &n);
-    double s = p->sign[n & 3];
-    if (n & 2) p = &SCT[1];
+    if (abstop12(y) < abstop12(120.0f)) {
+        x = reduce_fast(x, p, &n);
+        double s = p->sign[n & 3];
+        if (n & 2) p = &SCT[1];
+        return sincosf_poly(x * s, x * x, p, n);
+    }
+    if (!(abstop12(y) < abstop12(INFINITY))) return y - y;
+    x = reduce_large(y, &n);
+    const int q = n + (signbit(y) ? 1 : 0);
+    double s = p->sign[q & 3];
+    if (q & 2) p = &SCT[1];
     return sincosf_poly(x * s, x * x, p, n);
 }
 
@@ -84,10 +118,17 @@ float mwo_cosf(float y)
         if (abstop12(y) < abstop12(0x1p-12f)) return 1.0f;
         return sincosf_poly(x, x * x, p, 1);
     }
-    if (!(abstop12(y) < abstop12(120.0f))) return cosf(y);
-    x = reduce_fast(x, p, &n);
-    double s = p->sign[n & 3];
-    if (n & 2) p = &SCT[1];
+    if (abstop12(y) < abstop12(120.0f)) {
+        x = reduce_fast(x, p, &n);
+        double s = p->sign[n & 3];
+        if (n & 2) p = &SCT[1];
+        return sincosf_poly(x * s, x * x, p, n ^ 1);
+    }
+    if (!(abstop12(y) < abstop12(INFINITY))) return y - y;
+    x = reduce_large(y, &n);
+    const int q = n + (signbit(y) ? 1 : 0);
+    double s = p->sign[q & 3];
+    if (q & 2) p = &SCT[1];
     return sincosf_poly(x * s, x * x, p, n ^ 1);
 }
 

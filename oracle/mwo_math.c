@@ -8,10 +8,12 @@
  * math.py:18-19 via math.cos/math.sin).  glibc and ROCm's ocml differ by <=1 ulp on
  * some arguments, which would make "HIP engine == oracle" only approximately true.
  * Both the oracle (this file) and the engine (csrc/mw_math.h, written separately)
- * implement this same published algorithm, so their results are bit-identical, and
- * tests/test_oracle_math.py pins this function to glibc within 1 ulp.
+ * implement this same published algorithm, so their results are bit-identical
+ * (tests/test_engine_math_cpu.py on the host, mw_selftest_sincosf on the device).
  *
- * Valid for |x| < ~1e6 (agent headings stay far below that: <= 1536 steps * 20 deg).
+ * Valid for |x| < 1e6, the headings' domain (mw_set_state): within 1 ulp of glibc's sin / cos
+ * there, up to 1e6 +- 1 ulp (tests/test_engine_math_cpu.py); the two-stage reduction breaks
+ * down from about 1.6e6.
  */
 #include "mwo.h"
 

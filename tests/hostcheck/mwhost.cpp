@@ -5,7 +5,12 @@
 // Input: the oracle's scene struct (oracle/mwo.h), so that tests feed both from the same arrays.
 #include "../../miniworld_amd/csrc/mw_frag.h"
 #include "../../miniworld_amd/csrc/mw_cover.h"
+#include "../../miniworld_amd/csrc/mw_math.h"
+#include "../../miniworld_amd/csrc/mw_selftest.h"
 #include "../../oracle/mwo.h"
+#include <atomic>
+#include <cmath>
+#include <thread>
 #include <vector>
 #include <cstdlib>
 #include <cstring>
@@ -252,6 +257,136 @@ extern "C" int mwhost_list_length(const mwo_scene *sc)
 
 // glibc's sinf / cosf against the restatement the device uses (exhaustive range test in tests/)
 extern "C" void mwhost_sincosf(float x, float *s, float *c) { sincosf_glibc(x, *s, *c); }
+
+namespace {
+// libm's sinf / cosf called one at a time, as Mesa calls them (no sincosf the compiler might merge them into)
+float (*volatile libm_sinf)(float) = sinf;
+float (*volatile libm_cosf)(float) = cosf;
+double (*volatile libm_sin)(double) = sin;
+double (*volatile libm_cos)(double) = cos;
+
+// body(lo, hi, thread) over [0, n) in chunks of 2^20, on `threads` threads
+template <class F> void parallel_chunks(uint64_t n, int threads, F body)
+{
+    std::atomic<uint64_t> next{0};
+    std::vector<std::thread> pool;
+    for (int t = 0; t < threads; ++t)
+        pool.emplace_back([&, t] {
+            for (uint64_t lo; (lo = next.fetch_add(1u << 20)) < n;) body(lo, lo + (1u << 20) < n ? lo + (1u << 20) : n, t);
+        });
+    for (auto &th : pool) th.join();
+}
+
+int64_t ordered(double x) { int64_t i; memcpy(&i, &x, 8); return i < 0 ? INT64_MIN - i : i; }
+uint64_t ulps(double a, double b)
+{
+    if (a != a || b != b) return (a != a && b != b) ? 0 : UINT64_MAX;
+    const int64_t d = ordered(a) - ordered(b);
+    return d < 0 ? (uint64_t)0 - (uint64_t)d : (uint64_t)d;
+}
+}  // namespace
+
+// sinf / cosf over ALL 2^32 floats against libm's, bit for bit (NaN as NaN): the engine's header (sin_fn == NULL) or the
+// given functions (the oracle's mwo_sinf / mwo_cosf).  bad[512]: mismatches per binade (sign | exponent); first[512]: the
+// binade's smallest mismatching input bits (0xffffffff: none).  Returns the total.
+extern "C" long mwhost_sincosf_mismatches(float (*sin_fn)(float), float (*cos_fn)(float), int threads, uint64_t *bad,
+                                          uint32_t *first)
+{
+    std::vector<std::vector<uint64_t>> nb(threads, std::vector<uint64_t>(512, 0));
+    std::vector<std::vector<uint32_t>> fb(threads, std::vector<uint32_t>(512, 0xffffffffu));
+    parallel_chunks(1ull << 32, threads, [&](uint64_t lo, uint64_t hi, int t) {
+        for (uint64_t b = lo; b < hi; ++b) {
+            const float x = u2f((uint32_t)b);
+            float s, c;
+            if (sin_fn) { s = sin_fn(x); c = cos_fn(x); } else sincosf_glibc(x, s, c);
+            const float ws = libm_sinf(x), wc = libm_cosf(x);
+            if (mwcheck::float_bits(s) != mwcheck::float_bits(ws) || mwcheck::float_bits(c) != mwcheck::float_bits(wc)) {
+                const uint32_t k = (uint32_t)(b >> 23);
+                ++nb[t][k];
+                if ((uint32_t)b < fb[t][k]) fb[t][k] = (uint32_t)b;
+            }
+        }
+    });
+    long total = 0;
+    for (int k = 0; k < 512; ++k) {
+        bad[k] = 0; first[k] = 0xffffffffu;
+        for (int t = 0; t < threads; ++t) { bad[k] += nb[t][k]; if (fb[t][k] < first[k]) first[k] = fb[t][k]; }
+        total += (long)bad[k];
+    }
+    return total;
+}
+
+// mw_selftest_sincosf's per-binade sums of mwcheck::hash_sincosf, from libm's sinf / cosf over all 2^32 floats
+extern "C" void mwhost_sincosf_sums(int threads, uint64_t *sums)
+{
+    std::vector<std::vector<uint64_t>> acc(threads, std::vector<uint64_t>(512, 0));
+    parallel_chunks(1ull << 32, threads, [&](uint64_t lo, uint64_t hi, int t) {
+        for (uint64_t b = lo; b < hi; ++b) {
+            const float x = u2f((uint32_t)b);
+            acc[t][b >> 23] += mwcheck::hash_sincosf((uint32_t)b, libm_sinf(x), libm_cosf(x));
+        }
+    });
+    for (int k = 0; k < 512; ++k) { sums[k] = 0; for (int t = 0; t < threads; ++t) sums[k] += acc[t][k]; }
+}
+
+// mw_selftest_sincosf's f64 half: the per-bin sums of mwcheck::hash_sincos over inputs 0 .. n - 1 of the heading stream,
+// from the oracle's mwo_sincos
+extern "C" void mwhost_sincos_det_sums(uint64_t n, int threads, uint64_t *sums /*[120]*/)
+{
+    std::vector<std::vector<uint64_t>> acc(threads, std::vector<uint64_t>(120, 0));
+    parallel_chunks(n, threads, [&](uint64_t lo, uint64_t hi, int t) {
+        for (uint64_t i = lo; i < hi; ++i) {
+            int bin;
+            const double x = mwcheck::heading_sample(i, bin);
+            double s, c;
+            mwo_sincos(x, &s, &c);
+            acc[t][bin] += mwcheck::hash_sincos(x, s, c);
+        }
+    });
+    for (int k = 0; k < 120; ++k) { sums[k] = 0; for (int t = 0; t < threads; ++t) sums[k] += acc[t][k]; }
+}
+
+// the f64 headings: mw::sincos_det (the engine's, mw_math.h) against the oracle's mwo_sincos bit for bit, and both against
+// libm's sin / cos, over inputs 0 .. n - 1 of the heading stream and the n_extra doubles in extra.  out[0]: inputs where the
+// engine and the oracle differ; out[1], out[2]: the engine's / the oracle's largest distance from libm in ulps (sin or
+// cos); out[3]: inputs where either is more than 1 ulp from libm; ex[0..1]: the first input of each kind (as bits).
+extern "C" void mwhost_sincos_det_check(uint64_t n, const double *extra, uint64_t n_extra, int threads, uint64_t *out,
+                                        double *ex)
+{
+    struct Acc { uint64_t diff = 0, ulp_e = 0, ulp_o = 0, over = 0; double ex_diff = NAN, ex_over = NAN; uint64_t i_diff = UINT64_MAX, i_over = UINT64_MAX; };
+    std::vector<Acc> acc(threads);
+    parallel_chunks(n + n_extra, threads, [&](uint64_t lo, uint64_t hi, int t) {
+        Acc &a = acc[t];
+        for (uint64_t i = lo; i < hi; ++i) {
+            int bin;
+            const double x = i < n ? mwcheck::heading_sample(i, bin) : extra[i - n];
+            const mw::SinCos e = mw::sincos_det(x);
+            double s, c;
+            mwo_sincos(x, &s, &c);
+            const double ws = libm_sin(x), wc = libm_cos(x);
+            if (mwcheck::double_bits(e.s) != mwcheck::double_bits(s) || mwcheck::double_bits(e.c) != mwcheck::double_bits(c)) {
+                ++a.diff;
+                if (i < a.i_diff) { a.i_diff = i; a.ex_diff = x; }
+            }
+            const uint64_t ue = std::max(ulps(e.s, ws), ulps(e.c, wc)), uo = std::max(ulps(s, ws), ulps(c, wc));
+            a.ulp_e = std::max(a.ulp_e, ue);
+            a.ulp_o = std::max(a.ulp_o, uo);
+            if (ue > 1 || uo > 1) {
+                ++a.over;
+                if (i < a.i_over) { a.i_over = i; a.ex_over = x; }
+            }
+        }
+    });
+    Acc r;
+    for (const Acc &a : acc) {
+        r.diff += a.diff; r.over += a.over;
+        r.ulp_e = std::max(r.ulp_e, a.ulp_e); r.ulp_o = std::max(r.ulp_o, a.ulp_o);
+        if (a.i_diff < r.i_diff) { r.i_diff = a.i_diff; r.ex_diff = a.ex_diff; }
+        if (a.i_over < r.i_over) { r.i_over = a.i_over; r.ex_over = a.ex_over; }
+    }
+    out[0] = r.diff; out[1] = r.ulp_e; out[2] = r.ulp_o; out[3] = r.over;
+    ex[0] = r.ex_diff; ex[1] = r.ex_over;
+}
 
 // mw_frag.h: the lod from rho^2's bits (the quad kernel's form) against llvmpipe's float arithmetic, on n bit patterns;
 // returns the number of inputs where level or weight differ for some pyramid of 1 .. 12 levels

@@ -19,12 +19,14 @@ LIB = os.path.join(HERE, "hostcheck", "libmwhost.so")
 ROOT = os.path.dirname(HERE)
 
 
-@pytest.fixture(scope="module")
-def host():
-    deps = [SRC] + [os.path.join(ROOT, "miniworld_amd", "csrc", h) for h in ("mw_glmath.h", "mw_frag.h", "mw_cover.h")]
+def build_host():
+    """tests/hostcheck/libmwhost.so, (re)built when a source is newer; also used by the -m gpu selftests."""
+    deps = [SRC, os.path.join(ROOT, "oracle", "mwo_math.c")] + [
+        os.path.join(ROOT, "miniworld_amd", "csrc", h)
+        for h in ("mw_glmath.h", "mw_frag.h", "mw_cover.h", "mw_math.h", "mw_selftest.h", "mw_hd.h")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         fma = ["-mfma"] if " fma " in open("/proc/cpuinfo").read() else []
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", *fma, "-shared", SRC,
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", *fma, "-pthread", "-shared", SRC,
                                os.path.join(ROOT, "oracle", "mwo_math.c"), "-o", LIB])
     lib = C.CDLL(LIB)
     lib.mwhost_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -33,7 +35,17 @@ def host():
     lib.mwhost_lod_bits_mismatches.restype = C.c_long
     lib.mwhost_cover_mismatches.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.POINTER(C.c_long)]
     lib.mwhost_cover_mismatches.restype = C.c_long
+    lib.mwhost_sincosf_mismatches.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mwhost_sincosf_mismatches.restype = C.c_long
+    lib.mwhost_sincosf_sums.argtypes = [C.c_int, C.c_void_p]
+    lib.mwhost_sincos_det_sums.argtypes = [C.c_uint64, C.c_int, C.c_void_p]
+    lib.mwhost_sincos_det_check.argtypes = [C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
     return lib
+
+
+@pytest.fixture(scope="module")
+def host():
+    return build_host()
 
 
 @pytest.mark.parametrize("size", [(80, 60), (128, 96), (16, 4)])
@@ -114,17 +126,110 @@ def test_engine_math_equals_the_oracle_at_8_and_1_samples(host, case):
             assert np.array_equal(z16, want["z16"]) and np.array_equal(rgb, want["rgb"]), f"{case} frame {k} at {ns} samples"
 
 
+THREADS = min(16, len(os.sched_getaffinity(0)))
+
+
+def restated_libm_missing():
+    """Why this machine's libm is not the sinf / cosf that mw_glmath.h restates (glibc >= 2.28, the FMA variant), or None."""
+    name, version = os.confstr("CS_GNU_LIBC_VERSION").split() if hasattr(os, "confstr") else ("", "0")
+    if name != "glibc" or tuple(int(v) for v in version.split(".")[:2]) < (2, 28):
+        return f"libm is {name} {version}: mw_glmath.h restates the sinf / cosf of glibc >= 2.28"
+    if " fma " not in open("/proc/cpuinfo").read():
+        return "the CPU lacks FMA: libm's sinf / cosf is not the FMA variant mw_glmath.h restates"
+    return None
+
+
+def sincosf_mismatches(host, sin_fn=None, cos_fn=None):
+    bad = (C.c_uint64 * 512)()
+    first = (C.c_uint32 * 512)()
+    n = host.mwhost_sincosf_mismatches(sin_fn, cos_fn, THREADS, bad, first)
+    binades = [(k, int(bad[k]), float(np.uint32(first[k]).view(np.float32))) for k in range(512) if bad[k]]
+    return n, binades
+
+
 def test_device_sinf_cosf_restate_glibc(host):
-    """Mesa's glRotatef calls glibc's sinf / cosf; the device evaluates the same algorithm (mw_glmath.h)."""
-    libm = C.CDLL("libm.so.6")
-    libm.sinf.restype = libm.cosf.restype = C.c_float
-    libm.sinf.argtypes = libm.cosf.argtypes = [C.c_float]
-    rng = np.random.default_rng(0)
-    xs = np.concatenate([rng.uniform(-20, 20, 20000), rng.uniform(-1e-3, 1e-3, 2000), [0.0, 0.785398185253, 1.57079637051, 3.14159274101]]).astype(np.float32)
-    s, c = C.c_float(), C.c_float()
-    for x in xs:
-        host.mwhost_sincosf(float(x), C.byref(s), C.byref(c))
-        assert s.value == libm.sinf(float(x)) and c.value == libm.cosf(float(x)), float(x)
+    """Mesa's glRotatef calls glibc's sinf / cosf; the device evaluates the same algorithm (mw_glmath.h sincosf_glibc):
+    the host build of it equals libm's sinf and cosf, bit for bit, for ALL 2^32 floats (NaN as NaN) — the fast reduction
+    below 120, the 4 / pi table above (an entity's dir grows with every turn of the agent that carries it), +-inf, NaN."""
+    why = restated_libm_missing()
+    if why:
+        pytest.skip(why)
+    n, binades = sincosf_mismatches(host)
+    assert n == 0, (f"{n} floats differ; binades (sign|exponent, count, first input): {binades[:12]}")
+
+
+def test_oracle_sinf_cosf_equal_libm_for_every_float(host):
+    """The oracle's own restatement (oracle/mwo_geom.c mwo_sinf / mwo_cosf, written separately from the engine's and no
+    longer calling libm above 120): libm's bits for all 2^32 floats."""
+    why = restated_libm_missing()
+    if why:
+        pytest.skip(why)
+    mwo = pyoracle.lib()
+    n, binades = sincosf_mismatches(host, C.cast(mwo.mwo_sinf, C.c_void_p), C.cast(mwo.mwo_cosf, C.c_void_p))
+    assert n == 0, (f"{n} floats differ; binades (sign|exponent, count, first input): {binades[:12]}")
+
+
+def four_over_pi_bits(bits):
+    """floor(4 / pi * 2^bits) from Machin's formula in Python integers (pi / 4 = 4 acot 5 - acot 239), 64 guard bits."""
+    unity = 1 << (bits + 64)
+
+    def acot(x):
+        total = term = unity // x
+        n, sign = 3, -1
+        while term:
+            term //= x * x
+            total += sign * (term // n)
+            sign, n = -sign, n + 2
+        return total
+
+    pi_unity = 4 * (4 * acot(5) - acot(239))
+    return ((4 << bits) * unity) // pi_unity
+
+
+def test_four_over_pi_tables_hold_the_bits_of_four_over_pi():
+    """The large-argument reduction's 4 / pi (mw_glmath.h kInvPio4: entry i = floor(4 / pi * 2^(7 + 8 i)) mod 2^32; the
+    oracle's FOUR_OVER_PI: floor(4 / pi * 2^191) in three words) against 4 / pi computed here, independently of both."""
+    import re
+    v = four_over_pi_bits(191)
+    assert v.bit_length() == 192 and v >> 188 == 0xA                # 4 / pi = 1.27... = 0b1.0100010...
+    src = open(os.path.join(ROOT, "miniworld_amd", "csrc", "mw_glmath.h")).read()
+    table = re.search(r"kInvPio4\[24\] = \{([^}]*)\}", src).group(1)
+    engine = [int(w.rstrip("uU"), 16) for w in re.findall(r"0x[0-9a-fA-F]+u?", table)]
+    assert engine == [(v >> (184 - 8 * i)) & 0xFFFFFFFF for i in range(24)]
+    src = open(os.path.join(ROOT, "oracle", "mwo_geom.c")).read()
+    words = re.search(r"FOUR_OVER_PI\[3\] = \{([^}]*)\}", src).group(1)
+    oracle = [int(w.rstrip("ulUL"), 16) for w in re.findall(r"0x[0-9a-fA-F]+(?:ull)?", words)]
+    assert oracle == [(v >> 128) & (2 ** 64 - 1), (v >> 64) & (2 ** 64 - 1), v & (2 ** 64 - 1)]
+
+
+def test_f64_headings_engine_equals_oracle_and_libm_within_one_ulp(host):
+    """mw::sincos_det (mw_math.h, the engine's headings) against the oracle's mwo_sincos (oracle/mwo_math.c, written
+    separately) bit for bit, and both within 1 ulp of libm's sin / cos, over the headings' domain |x| < 1e6: 2^26 inputs
+    spread by exponent (2^-40 .. 2^19, both signs), the doubles nearest k pi / 4 (+-2 ulps) for every k there, zeros,
+    subnormals, tiny values and 1e6 +- 1 ulp."""
+    k = np.arange(-1273239, 1273240, dtype=np.float64)
+    near = k * (np.pi / 4)                                           # within an ulp or so of the nearest double
+    pts = [near]
+    for side in (np.inf, -np.inf):
+        x = near
+        for _ in range(2):
+            x = np.nextafter(x, side)
+            pts.append(x)
+    big = np.float64(1e6)
+    tiny = [0.0, -0.0, 5e-324, -5e-324, 2.2250738585072014e-308, -2.2250738585072014e-308, 1e-300, 1e-20, 2.0 ** -27,
+            -2.0 ** -27, 1e-8, 0.7853981633974483, 1.5707963267948966, 3.141592653589793]
+    ends = [np.nextafter(big, 0.0), np.nextafter(big, np.inf), -np.nextafter(big, 0.0), -np.nextafter(big, np.inf)]
+    extra = np.concatenate(pts + [np.array(tiny + ends)])
+    extra = np.ascontiguousarray(extra[np.abs(extra) <= np.nextafter(big, np.inf)])
+    assert len(extra) > 12_000_000
+    out = (C.c_uint64 * 4)()
+    ex = (C.c_double * 2)()
+    host.mwhost_sincos_det_check(1 << 26, extra.ctypes.data, len(extra), THREADS, out, ex)
+    assert out[0] == 0, f"{out[0]} inputs where the engine and the oracle differ, first {ex[0]!r}"
+    if os.confstr("CS_GNU_LIBC_VERSION").split()[0] != "glibc":
+        pytest.skip("libm is not glibc's: the 1-ulp bound is stated against glibc's sin / cos")
+    assert out[1] <= 1 and out[2] <= 1 and out[3] == 0, (f"{out[3]} inputs more than 1 ulp from libm (engine up to {out[1]}, "
+                                                         f"oracle up to {out[2]} ulps), first {ex[1]!r}")
 
 
 def test_compact_clip_vertices_clip_like_full_ones(host):

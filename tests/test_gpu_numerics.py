@@ -69,3 +69,29 @@ def test_visiting_order_sort_sorts():
         want = (np.sort(keys[b, :n]) & 0xFFFF).astype(np.uint16)
         assert np.array_equal(order[b, 1:1 + n], want), (n, order[b, 1:9], want[:8])
 
+
+
+def test_rotation_and_heading_sin_cos_equal_libm_and_the_oracle():
+    """mwgl::sincosf_glibc on the device (glRotatef's sinf / cosf for every Box, MeshEnt and ImageFrame) against libm's
+    sinf / cosf for ALL 2^32 floats, and mw::sincos_det (the f64 headings) against the oracle's mwo_sincos over 2^30
+    doubles of |x| < 1e6 spread by exponent: per-binade sums of a hash of the (input, sin, cos) bits (mw_selftest.h),
+    formed on the device and on the host."""
+    from miniworld_amd import engine
+    from test_engine_math_cpu import THREADS, build_host, restated_libm_missing
+    host = build_host()
+    lib = engine.load_library()
+    n64 = 1 << 30
+    got, got64 = (C.c_uint64 * 512)(), (C.c_uint64 * 120)()
+    lib.mw_selftest_sincosf.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+    assert lib.mw_selftest_sincosf(got, n64, got64) == 0
+    want64 = (C.c_uint64 * 120)()
+    host.mwhost_sincos_det_sums(n64, THREADS, want64)
+    bad64 = [k for k in range(120) if got64[k] != want64[k]]
+    assert not bad64, f"sincos_det differs from mwo_sincos in {len(bad64)} bins (sign * 60 + exponent + 40): {bad64[:24]}"
+    why = restated_libm_missing()
+    if why:
+        pytest.skip(why)
+    want = (C.c_uint64 * 512)()
+    host.mwhost_sincosf_sums(THREADS, want)
+    bad = [k for k in range(512) if got[k] != want[k]]
+    assert not bad, f"sincosf_glibc differs from libm in {len(bad)} binades (sign|exponent): {bad[:24]}"

@@ -104,6 +104,55 @@ def capture(env, out, k, stats, big=False):
 # floor and ceiling are then GL_POLYGONs of that many vertices).  A hexagon and a heptagon joined by nothing, a box, the
 # reference's own classes and methods throughout.
 EXTRA = [("ngon_s0", "NGonRooms", {}, 0, 3, 40, [0, 13, 27, 40]), ("ngon_dr_s2", "NGonRooms", {"domain_rand": True}, 2, 3, 30, [0, 17, 30])]
+# Headings past glibc's fast sinf / cosf reduction (|x| >= 120 rad): the reference never wraps agent.dir, and a carried entity
+# copies it on every turn and every step (miniworld.py:666, 714) and keeps it after a drop.  SCRIPTS drive these cases instead
+# of the random action stream; whole turns (2 pi k) added to agent.dir change nothing but the size of the angle.
+EXTRA += [("putnext_turns_s0", "PutNext", {}, 0, 0, 7, [2, 3, 4, 5, 7]),
+          ("pickup_dr_turns_s1", "PickupObjects", {"domain_rand": True}, 1, 0, 2, [1, 2])]
+
+
+def _clear_centre(env, keep):
+    """The agent to the room's centre at heading 0, `keep` just beyond the pickup's test point (miniworld.py:696-698), the
+    other entities along a wall 2 m apart: nothing in the way of a carried entity turning, nothing near anything else."""
+    cx, cz = (env.min_x + env.max_x) / 2, (env.min_z + env.max_z) / 2
+    env.agent.pos = np.array([cx, 0.0, cz])
+    others = [e for e in env.entities if e is not env.agent and e is not keep]
+    for j, e in enumerate(others):
+        e.pos = np.array([env.min_x + 1.0, 0.0, env.min_z + 1.0 + 2.0 * j])
+    keep.pos = env.agent.pos + env.agent.dir_vec * (1.5 * env.agent.radius + 0.3)
+
+
+def putnext_turns(env, t):
+    """pick up a box; turn carrying it at about 125, 250 and 1000 rad; drop it; two steps back"""
+    a = env.actions
+    if t == 0:
+        env.agent.dir = 0.0
+        _clear_centre(env, [e for e in env.entities if e is not env.agent][0])
+        return a.pickup, None
+    assert env.agent.carrying is not None or t > 4
+    if t in (1, 2, 3):
+        env.agent.dir += 2 * np.pi * {1: 20, 2: 20, 3: 119}[t]
+        return a.turn_left, None
+    return (a.drop if t == 4 else a.move_back), None
+
+
+def pickup_dr_turns(env, t):
+    """the pickup step of a ball at about 250 rad, then of a key at about 1000 rad: the frame of that step, which draws the
+    picked-up mesh at the agent's heading before PickupObjects.step removes it (pickupobjects.py:83-95) — so the base class
+    steps here, and the next call removes the entity the way PickupObjects.step would"""
+    if env.agent.carrying is not None:
+        env.entities.remove(env.agent.carrying)
+        env.agent.carrying = None
+        env.num_picked_up += 1
+    kind = ("Ball", "Key")[t]
+    ent = [e for e in env.entities if type(e).__name__ == kind][0]
+    env.agent.dir = 0.0
+    _clear_centre(env, ent)
+    env.agent.dir += 2 * np.pi * (40, 159)[t]
+    return env.actions.pickup, super(type(env), env).step
+
+
+SCRIPTS = {"putnext_turns_s0": putnext_turns, "pickup_dr_turns_s1": pickup_dr_turns}
 
 
 def make_ngon_env(**kwargs):
@@ -149,11 +198,15 @@ def run_case(name, cls, kwargs, seed, n_actions, steps, frames, totals):
     for t in range(steps):
         if name.startswith("putnext_poke") and t == 40:
             env.red_box.pos = env.yellow_box.pos + np.array([1.0, 0.0, 0.0])
-        if isinstance(n_actions, list):
+        step = env.step
+        if name in SCRIPTS:
+            a, base_step = SCRIPTS[name](env, t)
+            step = base_step or step
+        elif isinstance(n_actions, list):
             a = int(rng.choice(len(n_actions), p=n_actions))
         else:
             a = int(rng.integers(0, n_actions))
-        obs, rew, term, trunc, info = env.step(a)
+        obs, rew, term, trunc, info = step(a)
         if (t + 1) in frames or (t + 1) in BIG.get(name, []):
             capture(env, out, t + 1, stats, big=(t + 1) in BIG.get(name, []))
             done_frames.append(t + 1)
