@@ -411,6 +411,34 @@ int mw_get_final_info(mw_engine *e, int32_t *d_health, double *d_goal_pos, void 
  * modes. */
 int mw_get_reset_pending(mw_engine *e, uint8_t *d_out, void *stream);
 
+/* ---- frames that need not be drawn ------------------------------------------- */
+/* A frame is a pure function of the env's state, and a step may leave that state as it was: a forward move into a wall or an entity,
+ * a turn that the carried box blocks, a pickup or drop that finds nothing to do.  The step kernel compares the state it loaded with
+ * the state it stores and keeps one byte per env, "frame clean": agent pose, carried slot and the carried entity's pose are bit for
+ * bit the same, no entity leaves or has just left the list, no world was installed (auto-reset), the step was no next-step reset.
+ * MW_TASK_COLLECT engines never set it (kits respawn behind the step kernel).
+ *
+ * mw_set_frame_reuse(e, 1) lets mw_step leave the rows of such envs in d_obs / d_depth undrawn.  Off by default.  With it on, the
+ * caller promises exactly two things:
+ *   1. the d_obs / d_depth it passes to consecutive mw_step calls are the same buffers, and
+ *   2. it has not written to them in between.
+ * The engine checks what it can: it remembers which buffers (pointers, output layout) hold every env's current agent-view frame, and a
+ * step skips clean envs only when it is a plain step of the whole batch into exactly those.  A whole agent-view frame — mw_render, or
+ * an mw_step that drew every env — makes its buffers the remembered ones, so mw_reset + mw_render + mw_step on one buffer skips from
+ * the first step.  Every other frame draws every env and forgets the buffers: another pointer or layout, mw_render_top,
+ * mw_render_view, both passes of a step with final observations (mw_set_final_obs), frames with mesh entities (always drawn in full),
+ * and every frame of an engine created with experiment flags (MW_DEBUG_FLAGS != 0; read once by mw_create, like MW_K2Q and
+ * MW_GENERIC_RASTER, so no toggle changes the raster path under a held frame).
+ * So does every call that writes something a frame depends on: mw_reset, mw_set_state, mw_set_geometry, mw_set_gen_program,
+ * mw_upload_texture, mw_upload_mesh, mw_set_obs_layout, mw_set_final_obs, mw_debug_set_mesh_frame_seq, mw_set_frame_reuse itself.
+ * Observations, depth, rewards and flags are bit for bit what they are with reuse off.  What the engine cannot see is promise 2: a
+ * caller that scribbles into d_obs between steps (in-place normalisation, say) keeps its scribbles in the rows of clean envs. */
+int mw_set_frame_reuse(mw_engine *e, int32_t on);
+/* d_out uint8[N] (device): the frame-clean bytes of the last mw_step, whether or not reuse is on — for tests, and for consumers that
+ * want to skip their own per-frame work (an encoder need not run again on a frame that did not change).  Asynchronous on `stream`; all
+ * zeros before the first step; 0 for every env that was given a new world in the step, with and without final observations. */
+int mw_get_frame_clean(mw_engine *e, uint8_t *d_out, void *stream);
+
 /* Diagnostic (synchronises `stream`): how many triangles the last frame's display list held per env after clipping and culling —
  * what max_visible has to pay for (6 records per unit), and what decides which raster kernel an env's frame takes.
  * The stored length is clamped to the list's capacity (6 x max_visible): a value EQUAL to the capacity means "at least this

@@ -124,6 +124,10 @@ struct MwProgram {
     int32_t n_polys, n_segs;
 };
 
+// pending_remove[env] once the geometry kernel has taken the slot out of the list: not -1, so that the next step knows that its frame
+// lacks an entity the last one showed (frame_clean)
+#define MW_REMOVE_APPLIED (-2)
+
 // Everything the kernels need; passed by value (kernarg).
 struct MwArgs {
     int32_t N, W, H, E;
@@ -182,10 +186,15 @@ struct MwArgs {
     uint32_t *refill_mask;  // [N] 0 spare ready, 1 consumed (refill pending), 2 refill running, 3 env regenerating inline
     const MwArgs *gen_live; // device copies of this struct for the generators (live state / spare state): they index
     const MwArgs *gen_spare;//   it dynamically, which a by-value kernarg would turn into a scratch copy
-    int32_t *pending_remove; // [N] entity slot that leaves the list after this step's frame (-1 none): written by K1, applied by the geometry kernel
+    int32_t *pending_remove; // [N] entity slot that leaves the list after this step's frame (-1 none): written by K1, applied by the geometry kernel, which leaves MW_REMOVE_APPLIED
     // MW_AUTORESET_NEXT_STEP: 1 = the env's episode ended with the last step, whose frame showed its terminal state; the env's next
     // step ignores its action and installs the next world instead (K1).  Cleared by that step, mw_reset and mw_set_state.
     uint8_t *reset_pending;  // [N]
+    // 1 = the env's frame after the last step is bit for bit the frame before it: K1 compared the state it loaded with the state
+    // it stored (agent pose, carried slot and that entity's pose), nothing left or entered the entity list and no world was
+    // installed.  Stored by K1 for every env on every step; the raster kernels leave such an env's rows of the observation
+    // alone when the engine vouches for the buffer (mw_set_frame_reuse).
+    uint8_t *frame_clean;    // [N]
     // big scenes: what the geometry kernel's culling derives from a world's polygons alone (mw_geom.hip), kept from frame to
     // frame.  occ_valid[set]: polygon count + 1 of the world the cache belongs to, 0 after anything rewrote the polygons.
     int32_t *occ_valid;     // [sets] or null

@@ -184,6 +184,12 @@ struct mw_engine {
     uint8_t *final_obs = nullptr;
     float *final_depth = nullptr;
     int32_t *d_final_list = nullptr;    // [1 + N]: count, envs (mw_final_list_kernel)
+    // mw_set_frame_reuse: the caller's buffers keep their frames from step to step, so a step need not redraw an env whose frame
+    // did not change (MwArgs::frame_clean).  `held`: the buffers that hold every env's current agent-view frame, and their layout —
+    // set by a whole plain frame (launch_frame), dropped by every other frame and by every entry point that writes something a
+    // frame depends on (drop_held_frame).
+    bool frame_reuse = false;
+    struct { uint8_t *obs = nullptr; float *depth = nullptr; int layout = 0; bool valid = false; } held;
 };
 
 namespace {
@@ -326,7 +332,12 @@ auto tile_kernel_of(bool big, bool depth, bool general, bool ragged, bool mesh, 
 // 16-31; 0 for the quad kernel, which reads bits 13-15 as experiment bits).  mw_create keeps only MW_DEBUG_BITS of MW_DEBUG_FLAGS,
 // so that no experiment flag lands in the fields beside it.
 #define MW_DEBUG_BITS 0xFCCF
-int raster_flags(const mw_engine *e, int part, uint32_t stamp) { return e->dbg_flags | e->obs_layout << 8 | part << 4 | (int)(stamp << 16); }
+// `reuse`: MW_RASTER_REUSE (mw_kernels.h), frames without mesh entities only — it shares the stamp's field.
+int raster_flags(const mw_engine *e, int part, uint32_t stamp, bool reuse = false)
+{
+    return e->dbg_flags | e->obs_layout << 8 | part << 4 | (int)(stamp << 16) | (reuse && stamp == 0u ? MW_RASTER_REUSE : 0);
+}
+void drop_held_frame(mw_engine *e) { e->held.valid = false; }
 
 // The tile / quad / mesh-scatter kernels keep edge values in 32 bits: |c_k| = |dcdx X - dcdy Y| <= 2 W H 2^16 has to stay below
 // 2^31, i.e. W H < 16384 — 128 x 96 passes, 128 x 128 does not (a wall across the whole frame lost its triangle there);
@@ -750,6 +761,14 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
                  float *d_reward, uint8_t *d_term, uint8_t *d_trunc, hipStream_t st, int frame = FRAME_ALL)
 {
     if (!d_obs) return fail(e, MW_E_INVALID, "d_obs is null");
+    // Frame reuse: a plain step of the whole batch into the buffers that hold the frame before it leaves the envs K1 marks clean
+    // undrawn.  Any other frame — the first one, a render, a top view, the passes of a final-observation step, frames with mesh
+    // entities (their sample keys and fragment lists have a protocol of their own), other buffers or another layout, experiment
+    // flags — draws every env; a whole plain agent-view frame then makes its buffers the held ones, anything else leaves none.
+    const bool plain = frame == FRAME_ALL && view_flags == 0;
+    const bool reuse = e->frame_reuse && plain && do_step && !e->have_meshes && e->dbg_flags == 0 && e->held.valid && e->held.obs == d_obs &&
+                       e->held.depth == d_depth && e->held.layout == e->obs_layout;
+    drop_held_frame(e);
     MwArgs a = e->args;
     a.step_override = e->use_step_override ? e->d_step_override : nullptr;
     const int N = e->cfg.num_envs;
@@ -814,10 +833,11 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
     auto launch_k2q = [&](int part, hipStream_t kq) {
         const int S = e->cfg.msaa;
         const int lds = mw_rasterq_lds_bytes(S, a.W, a.H, a.n_tiles, d_depth ? 1 : 0);
-        const int flags = raster_flags(e, part, 0u);
+        const int flags = raster_flags(e, part, 0u, reuse);
         launch(S == 8 ? MW_PAIR(mw_rasterq) : MW_PAIR(mw_rasterq4), list, dim3(N), dim3(MWQ_THREADS), (size_t)lds, kq, a.N, a.W, a.H, a.max_vis,
                a.tiles_x, a.n_tiles, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
-               (const int32_t *)a.nvis, (const float *)a.envhdr, a.texels, d_obs, d_depth, flags, e->texel_bytes, e->d_k2q_prof);
+               (const int32_t *)a.nvis, (const float *)a.envhdr, a.texels, d_obs, d_depth, flags, e->texel_bytes, e->d_k2q_prof,
+               (const uint8_t *)a.frame_clean);
     };
     if (k2q && e->cfg.msaa == 4) {
         launch_k2q(0, st);
@@ -894,10 +914,10 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
             const int grid = listed ? std::min(e->mesh_tile_waves, N * (int)a.n_tiles) : groups * 8 * wpe2;
             launch(tile_kernel_of(big, d_depth != nullptr, general, ragged, mesh, part == 1), list, dim3(grid), dim3(64), lds, ks,
                    a.N, a.W, a.H, a.max_vis, a.tiles_x, a.n_tiles, wpe2, tpw2, (const float *)a.rec_raster, (const float *)a.rec_shade,
-                   (const float *)a.rec_cull, (const int32_t *)a.nvis, (const float *)a.envhdr, a.tex, a.texels, d_obs, d_depth, raster_flags(e, part, mesh_stamp),
+                   (const float *)a.rec_cull, (const int32_t *)a.nvis, (const float *)a.envhdr, a.tex, a.texels, d_obs, d_depth, raster_flags(e, part, mesh_stamp, reuse),
                    e->texel_bytes, (const uint16_t *)a.rec_order, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, e->d_mesh_keys.get(),
                    (const float *)e->d_plane_cache.get(), e->plane_cap, (const float4 *)e->d_slow_frags.get(), (const uint32_t *)e->d_slow_head.get(),
-                   (const uint32_t *)a.tile_list, a.ent_list_n, a.tile_list_cap, std::max(a.n_xcc, 1));
+                   (const uint32_t *)a.tile_list, a.ent_list_n, a.tile_list_cap, std::max(a.n_xcc, 1), (const uint8_t *)a.frame_clean);
         };
         e->last_raster_path = k2q ? (mesh ? MW_PATH_QUAD_MESH : MW_PATH_QUAD) : MW_PATH_TILE;
         if (mesh) {
@@ -919,6 +939,7 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
         e->ev_used.push_back(std::move(ev));
     }
     HIP_TRY(e, hipGetLastError());
+    if (plain) e->held = {d_obs, d_depth, e->obs_layout, true};
     return MW_OK;
 }
 
@@ -1028,6 +1049,7 @@ int init_engine(mw_engine *e, const mw_config *cfg)
     }
     ALLOC(a.pending_remove, (size_t)N);
     ALLOC(a.reset_pending, (size_t)N);      // (zeroed: nothing pending)
+    ALLOC(a.frame_clean, (size_t)N);        // (zeroed: nothing clean before the first step)
     HIP_TRY(e, hipMemset(a.pending_remove, 0xFF, 4 * (size_t)N));
     ALLOC(a.nvis, N); ALLOC(a.envhdr, (size_t)MW_ENVHDR * N); ALLOC(a.status, 1);
     ALLOC(e->d_reward_scratch, N); ALLOC(e->d_flag_scratch, 2 * (size_t)N); ALLOC(e->d_action_scratch, N);
@@ -1164,6 +1186,7 @@ int mw_upload_texture(mw_engine *e, int32_t tex_id, const uint8_t *rgb, int32_t 
 {
     if (!e || !rgb) return fail(e, MW_E_INVALID, "null argument");
     ON_DEVICE_SYNC(e);
+    drop_held_frame(e);
     if (tex_id < 0 || tex_id >= MW_MAX_TEX) return fail(e, MW_E_CAPACITY, "texture id %d out of range (max %d)", tex_id, MW_MAX_TEX);
     if (w <= 0 || h <= 0 || w > 16384 || h > 16384) return fail(e, MW_E_INVALID, "bad texture size %dx%d", w, h);
     build_pyramid(rgb, w, h, e->tex_data[tex_id], e->tex_desc[tex_id]);
@@ -1175,6 +1198,7 @@ int mw_upload_mesh(mw_engine *e, int32_t mesh_id, const float *pos, const float 
 {
     if (!e || !pos || !nrm || !rgb) return fail(e, MW_E_INVALID, "null argument");
     ON_DEVICE_SYNC(e);
+    drop_held_frame(e);
     if (tex_id >= MW_MAX_TEX || (tex_id >= 0 && !uv)) return fail(e, MW_E_INVALID, "textured mesh needs texcoords and a valid texture id");
     if (mesh_id < 0 || mesh_id >= MW_MAX_MESH) return fail(e, MW_E_CAPACITY, "mesh id %d out of range (max %d)", mesh_id, MW_MAX_MESH);
     if (ntris <= 0 || ntris > 60000) return fail(e, MW_E_CAPACITY, "mesh with %d triangles (1..60000 supported: 16-bit draw ids)", ntris);
@@ -1324,6 +1348,7 @@ int mw_set_geometry(mw_engine *e, int32_t env, const mw_poly *polys, int32_t n_p
 {
     if (!e || (n_polys > 0 && !polys) || (n_segs > 0 && !segs)) return fail(e, MW_E_INVALID, "null argument");
     ON_DEVICE_SYNC(e);
+    drop_held_frame(e);
     if (n_polys < 0 || n_polys > e->cfg.max_polys) return fail(e, MW_E_CAPACITY, "%d polygons > max_polys %d", n_polys, e->cfg.max_polys);
     if (n_segs < 0 || n_segs > e->cfg.max_segs) return fail(e, MW_E_CAPACITY, "%d segments > max_segs %d", n_segs, e->cfg.max_segs);
     int set = 0;
@@ -1365,6 +1390,7 @@ int mw_set_state(mw_engine *e, int32_t first_env, int32_t count, const mw_state_
 {
     if (!e) return MW_E_INVALID;
     ON_DEVICE_SYNC(e);
+    drop_held_frame(e);
     const int rc = state_xfer(e, first_env, count, host, true);
     if (rc != MW_OK) return rc;
     // a world written from the host replaces whatever a pending next-step auto-reset would have installed
@@ -1386,6 +1412,7 @@ int mw_set_gen_program(mw_engine *e, const mw_gen_program *prog, const mw_poly *
 {
     if (!e || !prog) return fail(e, MW_E_INVALID, "null argument");
     ON_DEVICE_SYNC(e);
+    drop_held_frame(e);
     if (prog->n_rooms < 1 || prog->n_rooms > MW_PROG_MAX_ROOMS || prog->n_tex < 0 || prog->n_tex > MW_PROG_MAX_TEX ||
         prog->n_ops < 0 || prog->n_ops > MW_PROG_MAX_OPS || prog->n_ents < 0 || prog->n_ents > MW_PROG_MAX_ENTS ||
         prog->n_ents > e->cfg.max_ents || prog->sign_n < 0 || prog->sign_n > 8)
@@ -1445,6 +1472,7 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
 {
     if (!e) return MW_E_INVALID;
     ON_DEVICE_SYNC(e);
+    drop_held_frame(e);
     if (e->cfg.generator == MW_GEN_NONE && !seeds) return fail(e, MW_E_INVALID, "engine was created without a device-side generator");
     if (e->cfg.generator == MW_GEN_PROGRAM && !e->args.prog) return fail(e, MW_E_INVALID, "MW_GEN_PROGRAM: no placement program installed (mw_set_gen_program)");
     const int N = e->cfg.num_envs;
@@ -1516,6 +1544,7 @@ int mw_set_final_obs(mw_engine *e, uint8_t *d_final_obs, float *d_final_depth)
         return fail(e, MW_E_INVALID, "mw_set_final_obs: final observations exist in MW_AUTORESET_SAME_STEP only (next-step returns the terminal frame itself)");
     if (e->cfg.generator == MW_GEN_NONE)
         return fail(e, MW_E_INVALID, "mw_set_final_obs: MW_GEN_NONE engines auto-reset nothing (the returned frame is the terminal one)");
+    drop_held_frame(e);
     e->final_obs = d_final_obs;
     e->final_depth = d_final_obs ? d_final_depth : nullptr;
     return MW_OK;
@@ -1545,6 +1574,7 @@ int mw_render_view(mw_engine *e, int32_t env, int32_t view_flags, int32_t width,
     if (msaa != 1 && msaa != 4 && msaa != 8 && msaa != 16) return fail(e, MW_E_INVALID, "msaa must be 1, 4, 8 or 16");
     if (!frame_size_ok(width, height))
         return fail(e, MW_E_INVALID, "frame buffer size %dx%d: 1 to %d x 1 to %d pixels", width, height, 255 * MW_TILE_W, 255 * MW_TILE_H);
+    drop_held_frame(e);     // (d_out may lie inside the held buffers)
     hipStream_t st = (hipStream_t)stream;
     MwArgs b = e->args;
     b.step_override = nullptr;
@@ -1580,6 +1610,7 @@ int mw_set_obs_layout(mw_engine *e, int32_t layout)
 {
     if (!e) return MW_E_INVALID;
     if (layout != MW_OBS_HWC_U8 && layout != MW_OBS_CWH_U8 && layout != MW_OBS_GREY_F64) return fail(e, MW_E_INVALID, "unknown obs layout %d", layout);
+    drop_held_frame(e);
     e->obs_layout = layout;
     return MW_OK;
 }
@@ -1629,6 +1660,7 @@ int mw_debug_set_mesh_frame_seq(mw_engine *e, uint32_t seq)
     if (!e) return MW_E_INVALID;
     // (the work lists and the slow-path counters alternate with the sequence number's parity: keep it)
     if ((seq & 1u) != (e->mesh_frame_seq & 1u)) return fail(e, MW_E_INVALID, "mw_debug_set_mesh_frame_seq: the parity of the sequence number must stay");
+    drop_held_frame(e);
     e->mesh_frame_seq = seq;
     return MW_OK;
 }
@@ -1688,6 +1720,23 @@ int mw_get_reset_pending(mw_engine *e, uint8_t *d_out, void *stream)
     if (!d_out) return fail(e, MW_E_INVALID, "mw_get_reset_pending: d_out is null");
     ON_DEVICE(e);
     HIP_TRY(e, hipMemcpyAsync(d_out, e->args.reset_pending, (size_t)e->cfg.num_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MW_OK;
+}
+
+int mw_set_frame_reuse(mw_engine *e, int32_t on)
+{
+    if (!e) return MW_E_INVALID;
+    drop_held_frame(e);     // (trust starts with the next whole frame)
+    e->frame_reuse = on != 0;
+    return MW_OK;
+}
+
+int mw_get_frame_clean(mw_engine *e, uint8_t *d_out, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (!d_out) return fail(e, MW_E_INVALID, "mw_get_frame_clean: d_out is null");
+    ON_DEVICE(e);
+    HIP_TRY(e, hipMemcpyAsync(d_out, e->args.frame_clean, (size_t)e->cfg.num_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MW_OK;
 }
 

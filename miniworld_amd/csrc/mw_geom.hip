@@ -1284,7 +1284,7 @@ __device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L,
         const int rs = a.pending_remove[env];
         if (rs >= 0 && !proxy && a.task != MW_TASK_COLLECT) {
             a.ekind[(size_t)rs * a.N + env] = MW_ENT_NONE;
-            a.pending_remove[env] = -1;
+            a.pending_remove[env] = MW_REMOVE_APPLIED;
         }
     }
     if (a.tile_list) {

@@ -36,6 +36,12 @@ MW_KERNEL_PAIR(mw_geom_big, MW_GEOM_ARGS);
 MW_KERNEL_PAIR(mw_geom_any, MW_GEOM_ARGS);
 MW_KERNEL_PAIR(mw_geom_big_any, MW_GEOM_ARGS);
 
+// Bit of the raster kernels' flag word (mw_engine.hip::raster_flags): the observation buffer still holds every env's last frame, so
+// an env whose frame_clean byte is set (MwArgs) is not drawn — the quad kernel's workgroup and the plain tile kernels' wavefronts
+// of that env leave at once.  Only frames without mesh entities carry it: the bit is the lowest of the field that holds the
+// slow-fragment stamp of a frame with meshes, and such a frame is always drawn in full.  The list forms never honour it.
+#define MW_RASTER_REUSE 0x10000
+
 // the tile kernels (mw_raster.hip)
 // (the frame kernels take parameter lists, not one struct: only __restrict__ on a kernel parameter tells the compiler that the
 // buffers do not overlap, and a by-value struct's pointers lose it — measured, tools/experiments/README.md)
@@ -49,7 +55,8 @@ MW_KERNEL_PAIR(mw_geom_big_any, MW_GEOM_ARGS);
     const uint16_t *__restrict__ rec_order, const float *__restrict__ mesh_pos, const float *__restrict__ mesh_nrm, \
     const float *__restrict__ mesh_rgb, const float *__restrict__ mesh_uv, uint32_t *__restrict__ mesh_keys, \
     const float *__restrict__ plane_cache, int plane_cap, const float4 *__restrict__ slow_frags, const uint32_t *__restrict__ slow_head, \
-    const uint32_t *__restrict__ tile_list, int32_t *__restrict__ tile_n, int tile_list_cap, int n_xcc
+    const uint32_t *__restrict__ tile_list, int32_t *__restrict__ tile_n, int tile_list_cap, int n_xcc, \
+    const uint8_t *__restrict__ frame_clean
 MW_KERNEL_PAIR(mw_raster, MW_RASTER_ARGS);
 MW_KERNEL_PAIR(mw_raster_depth, MW_RASTER_ARGS);
 MW_KERNEL_PAIR(mw_raster_big, MW_RASTER_ARGS);
@@ -71,7 +78,8 @@ MW_KERNEL_PAIR(mw_raster_big_mesh_wrap, MW_RASTER_ARGS);
     int N, int W, int H, int max_vis, int tiles_x, int n_tiles, \
     const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, \
     const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const uint32_t *__restrict__ texels, \
-    uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof
+    uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof, \
+    const uint8_t *__restrict__ frame_clean
 MW_KERNEL_PAIR(mw_rasterq, MWQ_ARGS);
 MW_KERNEL_PAIR(mw_rasterq4, MWQ_ARGS);
 // bytes of dynamic LDS a launch needs; the longest display list the quad path draws (longer ones: the tile code)

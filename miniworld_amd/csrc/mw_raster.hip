@@ -181,7 +181,8 @@ __device__ __attribute__((always_inline)) inline void raster_kernel_body(
     const uint16_t *__restrict__ rec_order, const float *__restrict__ mesh_pos, const float *__restrict__ mesh_nrm,
     const float *__restrict__ mesh_rgb, const float *__restrict__ mesh_uv, uint32_t *__restrict__ mesh_keys,
     const float *__restrict__ plane_cache, int plane_cap, const float4 *__restrict__ slow_frags, const uint32_t *__restrict__ slow_head,
-    const uint32_t *__restrict__ tile_list, int32_t *__restrict__ tile_n, int tile_list_cap, int n_xcc, const int32_t *__restrict__ list = nullptr)
+    const uint32_t *__restrict__ tile_list, int32_t *__restrict__ tile_n, int tile_list_cap, int n_xcc, const uint8_t *__restrict__ frame_clean,
+    const int32_t *__restrict__ list = nullptr)
 {
     if (MESHAWARE == 1) __builtin_amdgcn_s_setprio(3);      // (the mesh tiles end the frame's critical path: ahead of the quad kernel's wavefronts)
     // (one call site for both forms: two copies of the tile code in one kernel cost it 150 registers)
@@ -209,6 +210,8 @@ __device__ __attribute__((always_inline)) inline void raster_kernel_body(
                 if (env >= list[0]) return;
                 env = list[1 + env];
             } else if (env >= N) return;
+            // the plain kernels of frames without mesh entities: the buffer holds this env's frame already (MW_RASTER_REUSE, mw_kernels.h)
+            if (!SUB && HOT && !MESHAWARE && (dbg & MW_RASTER_REUSE) && frame_clean[env]) return;
             t_begin = (slot % waves_per_env) * tiles_per_wave; t_end = min(t_begin + tiles_per_wave, n_tiles);
         }
         raster_env_tiles<LDS_RECS, FMT, HOT, MESHAWARE>(N, env, t_begin, t_end, listed ? 2 : part_mode, W, H, max_vis, tiles_x, n_tiles, rec_raster, rec_shade, rec_cull, nvis_arr,
@@ -219,7 +222,7 @@ __device__ __attribute__((always_inline)) inline void raster_kernel_body(
 }
 
 #define MW_RASTER_FWD N, W, H, max_vis, tiles_x, n_tiles, waves_per_env, tiles_per_wave, rec_raster, rec_shade, rec_cull, \
-    nvis_arr, envhdr, texd, texels, obs, depth, dbg, texel_bytes, rec_order, mesh_pos, mesh_nrm, mesh_rgb, mesh_uv, mesh_keys, plane_cache, plane_cap, slow_frags, slow_head, tile_list, tile_n, tile_list_cap, n_xcc
+    nvis_arr, envhdr, texd, texels, obs, depth, dbg, texel_bytes, rec_order, mesh_pos, mesh_nrm, mesh_rgb, mesh_uv, mesh_keys, plane_cache, plane_cap, slow_frags, slow_head, tile_list, tile_n, tile_list_cap, n_xcc, frame_clean
 // each kernel and its list form over the envs of a list (int32 [0] count, [1 + i] env): the second pass of a same-step auto-reset
 // step with final observations (mw_engine.hip)
 #define MW_RASTER_PAIR(stem, bounds, ...)                                                                                           \

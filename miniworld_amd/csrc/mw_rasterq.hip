@@ -553,7 +553,7 @@ __device__ inline void rasterq_body(
     const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull,
     const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const uint32_t *__restrict__ texels,
     uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof,
-    const int32_t *__restrict__ list = nullptr)
+    const uint8_t *__restrict__ frame_clean, const int32_t *__restrict__ list = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef QRec<S> R;
@@ -562,6 +562,8 @@ __device__ inline void rasterq_body(
         if (env >= list[0]) return;
         env = list[1 + env];
     } else if (env >= N) return;
+    // the buffer holds this env's frame already (MW_RASTER_REUSE, mw_kernels.h): the whole workgroup, before any barrier
+    if (!SUB && (dbg & MW_RASTER_REUSE) && frame_clean[env]) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool has_depth = depth != nullptr;
     const QPlan pl = q_plan(S, W, H, n_tiles, has_depth);
@@ -975,7 +977,7 @@ __device__ inline void rasterq_body(
 
 }  // namespace
 
-#define MWQ_FWD N, W, H, max_vis, tiles_x, n_tiles, rec_raster, rec_shade, rec_cull, nvis_arr, envhdr, texels, obs, depth, dbg, texel_bytes, prof
+#define MWQ_FWD N, W, H, max_vis, tiles_x, n_tiles, rec_raster, rec_shade, rec_cull, nvis_arr, envhdr, texels, obs, depth, dbg, texel_bytes, prof, frame_clean
 // each kernel and its list form over the envs of a list (int32 [0] count, [1 + i] env)
 #define MWQ_PAIR(stem, bounds, ...)                                                                          \
     extern "C" __global__ bounds void stem##_kernel(MWQ_ARGS) { rasterq_body<__VA_ARGS__, false>(MWQ_FWD); } \

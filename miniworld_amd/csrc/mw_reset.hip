@@ -51,7 +51,7 @@ extern "C" __global__ __launch_bounds__(64) void MW_RESPAWN_KERNEL_NAME(MwArgs a
 // Same-step auto-reset with final observations, between the two passes of the step (mw_engine.hip): the listed envs (int32
 // [0] count, [1 + i] env: the ones whose episode ended with this step, whose terminal frame was drawn) install their next world
 // through the same install code as the step kernel's, and leave nothing of the finished episode behind: no pending removal (a
-// picked object, CollectHealth's consumed kit), no pending next-step reset.  One wavefront per list slot; grid N.
+// picked object, CollectHealth's consumed kit), no pending next-step reset, no frame_clean byte.  One wavefront per list slot; grid N.
 extern "C" __global__ __launch_bounds__(64) void MW_INSTALL_KERNEL_NAME(MwArgs a, const int32_t *__restrict__ list)
 {
     __shared__ unsigned char gen_ws[MW_GEN_WS_BYTES];
@@ -62,6 +62,7 @@ extern "C" __global__ __launch_bounds__(64) void MW_INSTALL_KERNEL_NAME(MwArgs a
     if (lane == 0) {
         a.pending_remove[env] = -1;
         a.reset_pending[env] = 0;
+        a.frame_clean[env] = 0;         // (K1 ran as a terminal step and may have found the finished episode's last frame unchanged)
     }
 }
 

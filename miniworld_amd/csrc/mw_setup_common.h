@@ -24,6 +24,8 @@ __device__ inline double uni(double v)
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
+__device__ inline bool same_bits(double x, double y) { return __double_as_longlong(x) == __double_as_longlong(y); }
+
 // ---------------------------------------------------------------- dynamics (f64)
 
 struct StepCtx {
@@ -225,6 +227,10 @@ __device__ inline void step_env(const MwArgs &a, int env, int lane, bool writer,
         c.cdir = a.edir[(size_t)k * a.N + env];
         c.live = k;
     }
+    // the state as loaded, for the frame_clean byte: what the frame shows of an env is its agent's pose and its entities'
+    const double o_px = c.px, o_py = c.py, o_pz = c.pz, o_dir = c.dir, o_cpos[3] = {c.cpos[0], c.cpos[1], c.cpos[2]}, o_cdir = c.cdir;
+    const int o_carry = c.carry;
+    bool same = false;              // the state this step stores is the state it loaded, bit for bit
     int remove_slot = -1;
     int tm = 0, tr = 0;             // terminated / truncated, uniform over the env's lanes
     // next-step auto-reset: the env's last step ended its episode (and drew its terminal state); this step installs the
@@ -325,6 +331,10 @@ __device__ inline void step_env(const MwArgs &a, int env, int lane, bool writer,
             }
             if (health > 0) rew = 2.0; else { rew = -100.0; tm = 1; }
         }
+        // (compared, not tracked through the code paths above: a blocked move, a turn a carried box undoes, a pickup that finds
+        // nothing all end here with the loaded values; a slot that is live now and was not carried before fails on `carry`)
+        same = same_bits(c.px, o_px) && same_bits(c.py, o_py) && same_bits(c.pz, o_pz) && same_bits(c.dir, o_dir) && c.carry == o_carry &&
+               (c.live < 0 || (same_bits(c.cpos[0], o_cpos[0]) && same_bits(c.cpos[1], o_cpos[1]) && same_bits(c.cpos[2], o_cpos[2]) && same_bits(c.cdir, o_cdir)));
         // every lane of the env has read the old state (the lanes of a wavefront run in lockstep, and each lane only reads its
         // own env's): the writer stores the new one
         if (PER_LANE) __builtin_amdgcn_wave_barrier();
@@ -358,7 +368,9 @@ __device__ inline void step_env(const MwArgs &a, int env, int lane, bool writer,
     // The one install site of the next world.  Same-step auto-reset: on the step that ends the episode, so that the observation
     // returned with done = 1 is the first one of the next episode.  Next-step auto-reset: on the step after it, the reference's
     // "step; if done: reset()" (scripts/benchmark.py:36-37) — the stream is consumed in that order.
+    bool installed = false;
     if (a.generator != MW_GEN_NONE && (pend || (a.autoreset == MW_AUTORESET_SAME_STEP && (tm | tr)))) {
+        installed = true;
         if (PER_LANE) {
             // the env's leading lane installs it (several envs of the wave may do so side by side); the env's other lanes then
             // read it like the leader does
@@ -376,7 +388,15 @@ __device__ inline void step_env(const MwArgs &a, int env, int lane, bool writer,
 
     // what this step leaves for after its frame (a picked-up object is drawn one last time, pickupobjects.py:86-88) goes with
     // the frame's vertex half, mw_geom_kernel's (mw_geom.hip)
-    if (writer) a.pending_remove[env] = remove_slot;
+    if (writer) {
+        // frame_clean: the frame after this step is the frame before it.  Not when an entity leaves the list behind this frame or
+        // left it behind the last one (the geometry kernel applied that removal after the last frame was drawn: MW_REMOVE_APPLIED;
+        // a slot still pending was never applied), not on a next-step reset, not when a world was installed.  CollectHealth never:
+        // its respawn kernel moves entities behind this kernel's back.
+        const bool clean = same && !pend && !installed && remove_slot < 0 && a.pending_remove[env] == -1 && a.task != MW_TASK_COLLECT;
+        a.frame_clean[env] = clean ? 1 : 0;
+        a.pending_remove[env] = remove_slot;
+    }
 }
 
 }  // namespace

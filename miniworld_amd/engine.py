@@ -34,7 +34,7 @@ PATH_TILE, PATH_QUAD, PATH_QUAD_MESH, PATH_GENERIC = 0, 1, 2, 3
 EXPORTS = [
     "mw_create", "mw_destroy", "mw_last_error", "mw_upload_texture", "mw_upload_mesh",
     "mw_set_geometry", "mw_get_geometry", "mw_set_state", "mw_get_state", "mw_set_step_params", "mw_reset",
-    "mw_step", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
+    "mw_step", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
     "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
     "mw_selftest_sincosf",
 ]
@@ -192,11 +192,18 @@ def load_library():
     L.mw_get_info.argtypes = [vp, vp, vp, i32, vp]
     L.mw_get_final_info.argtypes = [vp, vp, vp, vp]
     L.mw_get_reset_pending.argtypes = [vp, vp, vp]
+    L.mw_set_frame_reuse.argtypes = [vp, i32]
+    L.mw_get_frame_clean.argtypes = [vp, vp, vp]
     L.mw_get_list_lengths.argtypes = [vp, i32, i32, vp, vp]
     L.mw_debug_set_mesh_frame_seq.argtypes = [vp, C.c_uint32]
     L.mw_debug_get_slow_heads.argtypes = [vp, vp, vp]
     _lib = L
     return L
+
+
+def frame_reuse_allowed() -> bool:
+    """MW_FRAME_REUSE=0 forces frame reuse off, whatever a caller asks for: the A/B switch of an unchanged benchmark run."""
+    return os.environ.get("MW_FRAME_REUSE", "1").strip() != "0"
 
 
 def _stream_ptr(device=None):
@@ -225,6 +232,7 @@ class Engine:
         if rc != 0:
             raise EngineError(f"mw_create failed ({rc}): {self.lib.mw_last_error(None).decode()}")
         self.h = h
+        self.frame_reuse = False
 
     def _check(self, rc, what):
         if rc != 0:
@@ -434,6 +442,25 @@ class Engine:
             out = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
         assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (self.N,) and out.is_contiguous()
         self._check(self.lib.mw_get_reset_pending(self.h, out.data_ptr(), _stream_ptr(self.device)), "mw_get_reset_pending")
+        return out
+
+    def set_frame_reuse(self, on: bool):
+        """Lets step() leave the rows of envs whose frame did not change undrawn (include/mwengine.h: mw_set_frame_reuse).  With
+        it on the caller promises to pass the same obs / depth tensors to consecutive steps and not to write to them in
+        between.  MW_FRAME_REUSE=0 in the environment forces it off (the A/B switch); returns what is in effect."""
+        on = bool(on) and frame_reuse_allowed()
+        self._check(self.lib.mw_set_frame_reuse(self.h, int(on)), "mw_set_frame_reuse")
+        self.frame_reuse = on
+        return on
+
+    def get_frame_clean(self, out=None):
+        """uint8[N] on the device: 1 = the env's frame after the last step is bit for bit the frame before it (a blocked move, a
+        pickup that found nothing ...), whether or not reuse is on.  Written into `out` when given."""
+        import torch
+        if out is None:
+            out = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (self.N,) and out.is_contiguous()
+        self._check(self.lib.mw_get_frame_clean(self.h, out.data_ptr(), _stream_ptr(self.device)), "mw_get_frame_clean")
         return out
 
     def list_lengths(self):

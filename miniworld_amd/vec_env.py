@@ -57,7 +57,7 @@ _KIND = {
 class MiniWorldVecEnv:
     def __init__(self, env_id: str, num_envs: int, device_id: int = 0, domain_rand: bool = False,
                  want_depth: bool = False, seed: int = 0, autoreset: bool | str = True, obs_layout: str = "hwc",
-                 rng: str = "auto", msaa: int = 8, final_obs: bool = False, **env_kwargs):
+                 rng: str = "auto", msaa: int = 8, final_obs: bool = False, frame_reuse: bool = True, **env_kwargs):
         """obs_layout: "hwc" uint8[N,H,W,3] (the env's observation), "cwh" uint8[N,3,W,H]
         (PyTorchObsWrapper, wrappers.py:24) or "grey" float64[N,H,W,1] (GreyscaleWrapper, wrappers.py:44):
         the raster kernel stores the frame in that layout, there is no extra pass.
@@ -71,7 +71,12 @@ class MiniWorldVecEnv:
         ("same_step", "next_step" or "off").
         final_obs (same-step auto-reset only): every step also writes the terminal frame of each env whose episode ended in it
         into that env's row of `self.final_obs` (and its depth into `self.final_depth` with want_depth); the other rows keep
-        what they held.  Costs a second, small frame of the finished envs in every step."""
+        what they held.  Costs a second, small frame of the finished envs in every step.
+        frame_reuse: a step does not redraw an env whose frame did not change (a move into a wall, a pickup that finds nothing):
+        its rows of `self.obs` / `self.depth` already hold that frame.  This env owns those tensors and passes them on every
+        step, so it is on by default — TREAT THE RETURNED TENSORS AS READ-ONLY between steps (copy before normalising in
+        place).  False, or MW_FRAME_REUSE=0 in the environment, draws every env on every step; `self.frame_reuse` tells which
+        is in effect.  Results are bit for bit the same either way."""
         import torch
         self.torch = torch
         modes = {True: "same_step", False: "off", "same_step": "same_step", "next_step": "next_step"}
@@ -228,6 +233,7 @@ class MiniWorldVecEnv:
             self.final_obs = self.engine.obs_buffer()
             self.final_depth = torch.zeros_like(self.depth) if want_depth else None
             self.engine.set_final_obs(self.final_obs, self.final_depth)
+        self.frame_reuse = self.engine.set_frame_reuse(frame_reuse)
         self._host_envs = None
         self._next_seed = seed
         # what the env's step() reports in `info` beside the observation (collecthealth.py:100, tmaze.py:89, ymaze.py:125)
@@ -339,6 +345,11 @@ class MiniWorldVecEnv:
         the next world instead of stepping — its action is ignored and its transition is no transition of the env (mask it out
         of a replay buffer).  All zeros in the other modes."""
         return self.engine.get_reset_pending()
+
+    def frame_clean(self):
+        """uint8[N] device tensor: 1 = the env's observation of the last step is bit for bit the one before it (its state did not
+        change), so per-frame work of the consumer's own can be skipped for it too."""
+        return self.engine.get_frame_clean()
 
     def render_top_view(self, render_agent=True):
         """uint8[N,H,W,3] map views (render_top_view, miniworld.py:1088-1175) of every env."""

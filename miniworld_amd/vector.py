@@ -28,6 +28,13 @@ reward, flags and info (CollectHealth's final health, TMaze / YMaze's goal_pos o
 keys are needed and none are emitted —, and the env's next step ignores its action and returns the next episode's first frame
 with reward 0 and both flags False.  `self.vec.reset_pending()` marks the envs whose next step is such a reset step.  Still one
 frame per env and step, drawn in the same kernels; the worlds follow the reference's "step; if done: reset()" stream order.
+
+**The observation returned with `to_numpy=False` is the engine's own device tensor: treat it as read-only between steps.**  A
+step does not redraw an env whose state did not change (a move into a wall, a pickup that finds nothing): its rows already hold
+that frame (`MiniWorldVecEnv(frame_reuse=True)`, the default).  A wrapper that normalises or augments observations IN PLACE would
+find its own writes again in the rows of such envs — copy first (`obs.clone()`, `obs.float()`), or pass `frame_reuse=False`, which
+draws every env on every step.  `to_numpy=True` hands out host copies and is not affected.  Results are bit for bit the same
+either way; `self.vec.frame_clean()` tells a consumer which rows did not change.
 """
 from __future__ import annotations
 
@@ -42,9 +49,11 @@ class MiniWorldVectorEnv(VectorEnvBase):
     metadata = {"autoreset_mode": AUTORESET_SAME_STEP, "render_modes": ["rgb_array"]}
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
-                 **kwargs):
+                 frame_reuse: bool = True, **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
-        are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring)."""
+        are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
+        False draws every env on every step, for consumers that write into the returned observation tensor (module docstring)."""
+        kwargs["frame_reuse"] = frame_reuse
         mode = str(getattr(autoreset_mode, "name", autoreset_mode)).lower().replace("_", "-")     # (an AutoresetMode: its name)
         if mode not in ("same-step", "next-step"):
             raise ValueError(f"autoreset_mode must be 'same-step' or 'next-step', not {autoreset_mode!r}")
