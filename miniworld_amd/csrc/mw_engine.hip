@@ -5,8 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
-#include <map>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -17,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "mw_assets.h"
 #include "mw_device.h"
 #include "mw_kernels.h"
 #include "mw_rng.h"
@@ -116,40 +115,40 @@ struct mw_engine {
     DevBuf<uint32_t> d_texels;          // the descriptor table, then the texels (upload_textures)
     size_t texel_cap = 0;               // dwords d_texels holds
     MwMeshDesc *d_meshdesc = nullptr;
-    std::vector<MwMeshDesc> mesh_desc;
-    std::vector<std::vector<float>> mesh_pos, mesh_nrm, mesh_rgb, mesh_uv;   // per mesh id, [ntris][9] ([6] for uv)
-    DevBuf<float> d_mesh_pos, d_mesh_nrm, d_mesh_rgb, d_mesh_uv;
-    DevBuf<float> d_mesh_stream, d_mesh_attr;   // the entity kernel's triangle streams (rasterisation order): positions (meshes without a vertex table), vertex attributes
-    DevBuf<float4> d_mesh_vpos;         // the meshes' distinct positions (MwMeshDesc::vfirst, nverts)
-    DevBuf<uint2> d_mesh_idx;           // per triangle of the rasterisation order: three 16-bit indices into the mesh's table, the triangle's index
-    std::vector<std::vector<float>> mesh_vtab;      // per mesh id: [nverts][4]
-    std::vector<std::vector<uint32_t>> mesh_itab;   // per mesh id: [ntris][2]
-    int max_mesh_verts = 0;
-    bool have_meshes = false;
-    DevBuf<uint32_t> d_view_keys;       // sample keys of the generic-resolution path
-    bool visible_attr_set = false;
+    std::vector<mwasset::HostMesh> meshes;      // per mesh id (ntris = 0: none); the pools below are repacked from them (mw_upload_mesh)
+    struct MeshPools {
+        DevBuf<float> pos, nrm, rgb, uv;
+        DevBuf<float> stream, attr;     // the entity kernel's triangle streams (rasterisation order): positions (meshes without a vertex table), vertex attributes
+        DevBuf<float4> vpos;            // the meshes' distinct positions (MwMeshDesc::vfirst, nverts)
+        DevBuf<uint2> idx;              // per triangle of the rasterisation order: three 16-bit indices into the mesh's table, the triangle's index
+    } pools;
+    int max_mesh_verts = 0, max_mesh_tris = 0;
+    bool have_meshes = false, visible_attr_set = false;
     Stream side_stream;     // low priority: the Maze's spare-world refills beside the steps
     Event ev_fork;
-    Stream quad_stream;     // low priority: the raster kernel's first part (every tile no mesh can touch) beside the mesh kernels
-    Event ev_mesh_fork, ev_mesh_join;
-    DevBuf<uint32_t> d_mesh_keys;       // [N][H][W][8] sample keys of the mesh scatter kernel (all-ones between frames)
-    bool mesh_keys_dirty = true;
-    DevBuf<int32_t> d_slow_count;       // [2 parities][2][N] listed triangles, fragments; then d_ent_counter
-    int32_t *d_ent_counter = nullptr;   // [2][MW_CNT_WORDS] the work lists' lengths and cursors (mw_device.h: ent_list_n), this frame's and the next frame's
-    DevBuf<uint32_t> d_slow_envs;       // [2][N] the envs with triangles across a frustum plane (written by the entity kernel: the slow kernel's work list)
-    DevBuf<uint32_t> d_tile_list;       // [N * n_tiles] the mesh tiles' work list (written by the geometry kernel)
-    static constexpr int mesh_tile_waves = 16384;       // wavefronts of the mesh tiles' launch, wavefront w taking the items w, w + 16384, ... of the list (4096: 139 us, 8192: 122, 16384: 112)
-    DevBuf<uint32_t> d_ent_list;        // [2][N * slots] the work list itself (written by the geometry kernel)
-    int ent_list_cap = 0;
-    static constexpr int ent_blocks = 512;      // its persistent workgroups: two of 512 lanes per CU (768 of them, or 256 of 1024 lanes: measured slower)
-    uint32_t mesh_frame_seq = 1;
-    DevBuf<uint32_t> d_slow_tris;
-    DevBuf<float4> d_slow_frags;
-    DevBuf<uint32_t> d_slow_head;
-    DevBuf<float> d_plane_cache;        // [N][plane_cap][16] + [N][plane_cap][4] attribute planes of the mesh triangles that win samples (mw_raster_mesh.hip)
-    int plane_cap = 0, max_mesh_tris = 0;
+    // The mesh path: what a frame with mesh entities uses beside the triangle records and the pools (ensure_mesh_buffers fills it)
+    struct MeshPath {
+        Stream quad_stream;     // low priority: the raster kernel's first part (every tile no mesh can touch) beside the mesh kernels
+        Event ev_fork, ev_join;
+        DevBuf<uint32_t> view_keys;     // sample keys of the generic-resolution path
+        size_t view_keys_bytes = 0;
+        DevBuf<uint32_t> keys;          // [N][H][W][8] sample keys of the mesh scatter kernel (all-ones between frames)
+        bool keys_dirty = true;
+        DevBuf<int32_t> slow_count;     // [2 parities][2][N] listed triangles, fragments; then ent_counter
+        int32_t *ent_counter = nullptr; // [2][MW_CNT_WORDS] the work lists' lengths and cursors (mw_device.h: ent_list_n), this frame's and the next frame's
+        DevBuf<uint32_t> slow_envs;     // [2][N] the envs with triangles across a frustum plane (written by the entity kernel: the slow kernel's work list)
+        DevBuf<uint32_t> tile_list;     // [N * n_tiles] the mesh tiles' work list (written by the geometry kernel)
+        DevBuf<uint32_t> ent_list;      // [2][N * slots] the work list itself (written by the geometry kernel)
+        int ent_list_cap = 0;
+        uint32_t frame_seq = 1;         // frames drawn through the lists: the parity picks their side, the low 16 bits stamp the slow fragments (mesh_frame)
+        DevBuf<uint32_t> slow_tris; DevBuf<float4> slow_frags; DevBuf<uint32_t> slow_head;     // (mw_mesh_slow_kernel)
+        DevBuf<float> plane_cache;      // [N][plane_cap][16] + [N][plane_cap][4] attribute planes of the mesh triangles that win samples (mw_raster_mesh.hip)
+        int plane_cap = 0;
+        static constexpr int mesh_tile_waves = 16384;   // wavefronts of the mesh tiles' launch, wavefront w taking the items w, w + 16384, ... of the list (4096: 139 us, 8192: 122, 16384: 112)
+        static constexpr int ent_blocks = 512;          // the entity kernel's persistent workgroups: two of 512 lanes per CU (768 of them, or 256 of 1024 lanes: measured slower)
+        static constexpr int slow_waves = 8192;         // wavefronts of the slow kernel's launch (4096: 59 us, 8192: 55)
+    } mp;
     int obs_layout = MW_OBS_HWC_U8;
-    size_t view_keys_bytes = 0;
     // scratch for the step outputs when the caller passes none
     float *d_reward_scratch = nullptr;
     uint8_t *d_flag_scratch = nullptr;
@@ -177,7 +176,6 @@ struct mw_engine {
     bool use_k2q = true;        // MW_K2Q=0: the tile kernels of mw_raster.hip for small scenes too (the A/B baseline of the quad kernel)
     bool k2q_ok = false;        // the frame fits the quad kernel's LDS plan
     bool generic_raster = false;    // MW_GENERIC_RASTER=1: msaa = 4 frames through the generic-resolution kernel (tests run both)
-    static constexpr int slow_waves = 8192;      // wavefronts of the slow kernel's launch (4096: 59 us, 8192: 55)
     unsigned long long *d_ent_prof = nullptr;   // MW_ENT_PROF=<file>: the mesh entity kernel's per-env times and counts of the last frame, [N][8], dumped by mw_destroy
     unsigned long long *d_k2q_prof = nullptr;   // MW_K2Q_PROF=<file>: s_memtime stamps of the quad kernel's phases, [N][8 waves][8], dumped by mw_destroy
     // mw_set_final_obs: the terminal frames of the envs whose episode ends in a same-step step (null: off); the list of those envs
@@ -310,7 +308,7 @@ auto geom_kernel_of(int L, int msaa)
 
 // the tile kernel (mw_raster.hip).  big: a visiting order exists, records read in place; general: an output layout other than
 // HWC or debug flags (the small-scene production kernels carry neither, nor a run-time depth switch); ragged: a frame off the
-// 16 x 4 grid (no meshes: ragged_tiles_ok); first: K2's first part of a frame with meshes, which never enters a mesh tile — the
+// 16 x 4 grid (no meshes: raster_path); first: K2's first part of a frame with meshes, which never enters a mesh tile — the
 // plain tile code with the skip (the small-scene observation path only)
 auto tile_kernel_of(bool big, bool depth, bool general, bool ragged, bool mesh, bool first)
 {
@@ -389,116 +387,17 @@ int k1_dense_lanes(const mw_engine *e)
     return lanes <= 32 ? lanes : 0;
 }
 
-// numpy.random.SeedSequence(seed).generate_state(4, uint64) for a non-negative integer seed (the
-// published SeedSequence algorithm: 4-word pool, hashmix / mix with the constants below), then PCG64's
-// pcg_setseq_128_srandom_r — what gymnasium's np_random(seed) builds (miniworld.py:551).
-void pcg64_seed(uint64_t seed, uint64_t out[4])
-{
-    const uint32_t INIT_A = 0x43b0d7e5u, MULT_A = 0x931e8875u, INIT_B = 0x8b51f9ddu, MULT_B = 0x58f38dedu;
-    const uint32_t MIX_L = 0xca01f9ddu, MIX_R = 0x4973f715u;
-    uint32_t ent[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-    const int n_ent = ent[1] ? 2 : 1;
-    uint32_t hc = INIT_A;
-    auto hashmix = [&](uint32_t v) { v ^= hc; hc *= MULT_A; v *= hc; v ^= v >> 16; return v; };
-    auto mix = [&](uint32_t x, uint32_t y) { uint32_t r = MIX_L * x - MIX_R * y; r ^= r >> 16; return r; };
-    uint32_t pool[4];
-    for (int i = 0; i < 4; ++i) pool[i] = hashmix(i < n_ent ? ent[i] : 0u);
-    for (int s = 0; s < 4; ++s)
-        for (int d = 0; d < 4; ++d)
-            if (s != d) pool[d] = mix(pool[d], hashmix(pool[s]));
-    uint32_t hb = INIT_B, w[8];
-    for (int i = 0; i < 8; ++i) {
-        uint32_t v = pool[i & 3];
-        v ^= hb; hb *= MULT_B; v *= hb; v ^= v >> 16;
-        w[i] = v;
-    }
-    uint64_t st[4];
-    for (int i = 0; i < 4; ++i) st[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
-    // initstate = st[0]:st[1], initseq = st[2]:st[3];  inc = (initseq << 1) | 1
-    const uint64_t inc_hi = (st[2] << 1) | (st[3] >> 63), inc_lo = (st[3] << 1) | 1ull;
-    uint64_t hi = 0, lo = 0;
-    mw::pcg64_step(hi, lo, inc_hi, inc_lo);
-    const uint64_t sl = lo + st[1];
-    hi += st[0] + (sl < lo ? 1ull : 0ull);
-    lo = sl;
-    mw::pcg64_step(hi, lo, inc_hi, inc_lo);
-    out[0] = hi; out[1] = lo; out[2] = inc_hi; out[3] = inc_lo;
-}
-
 // (re)seed env i in a host copy of the uint64[4][N] rng array
 void seed_env(const mw_engine *e, uint64_t *rng, int i, uint64_t seed)
 {
     const size_t N = (size_t)e->cfg.num_envs;
     if (e->cfg.rng_mode == MW_RNG_PCG64) {
         uint64_t s[4];
-        pcg64_seed(seed, s);
+        mwasset::pcg64_seed(seed, s, mw::pcg64_step);
         for (int k = 0; k < 4; ++k) rng[(size_t)k * N + i] = s[k];
         rng[4 * N + i] = 0;
     } else {
         rng[i] = seed; rng[N + i] = 0; rng[2 * N + i] = 0; rng[3 * N + i] = 0; rng[4 * N + i] = 0;
-    }
-}
-
-// Mip pyramid as glGenerateMipmap builds it on the reference's driver (llvmpipe: a GL_LINEAR blit of the previous level):
-// destination texel i of dn reads source texels i0, i1 with an 8-bit weight — 24.8 fixed-point coordinate
-// iround((i + 0.5) n / dn * 256) - 128, CLAMP_TO_EDGE; 2i, 2i + 1 with weight 128 on an even axis — and
-// lerp a + ((w (b - a) + 128) >> 8), x first, then y.  tests/golden/gl_meta.npz holds the driver's own levels (checksums).
-struct Taps { int i0, i1, w; };
-Taps axis_taps(int n, int dn, int i)
-{
-    Taps t{0, 0, 0};
-    if (n == 1) return t;
-    const double sc = ((double)i + 0.5) * (double)n / (double)dn * 256.0;
-    const long fixed = lrint(sc) - 128;         // round half to even
-    const long ip = fixed >> 8;
-    t.w = (int)(fixed & 255);
-    t.i0 = ip < 0 ? 0 : (ip > n - 1 ? n - 1 : (int)ip);
-    t.i1 = ip + 1 < 0 ? 0 : (ip + 1 > n - 1 ? n - 1 : (int)(ip + 1));
-    return t;
-}
-inline int lerp8(int a, int b, int w) { return a + ((w * (b - a) + 128) >> 8); }
-
-void build_pyramid(const uint8_t *rgb, int w, int h, std::vector<uint32_t> &out, MwTexDesc &desc)
-{
-    std::vector<uint8_t> cur(rgb, rgb + (size_t)w * h * 3), nxt;
-    desc.w = (uint32_t)w; desc.h = (uint32_t)h; desc.nlevels = 0; desc.pad = 0;
-    out.clear();
-    for (;;) {
-        // a level is stored as one 32-byte record per texel (i, j): its GL_LINEAR footprint (i, j), (i+1, j), (i, j+1),
-        // (i+1, j+1), GL_REPEAT applied, laid out for the filter's first step.  The lerp along x of a channel's two texels
-        // a, b under the 8-bit weight w, a + ((w (b - a) + 128) >> 8), is ((a * 256 + 128) + w * (b - a)) >> 8 in 16-bit
-        // arithmetic (the sum stays in [128, 65408]); a record holds A = a * 256 + 128 and D = (b - a) mod 2^16, two
-        // channels to a dword: row j as (A_r | A_b << 16, D_r | D_b << 16, A_g, D_g), then row j + 1 the same.  A bilinear
-        // tap is two 16-byte loads, needs neither the neighbours' indices nor their wrap nor any unpacking, and its
-        // x step is one packed multiply-add and one packed shift per pair of channels (8x the memory of the texels: the
-        // coarse levels an 80x60 frame samples stay cache resident all the same).  Level::off counts records from the
-        // start of the pool.
-        desc.lvl[desc.nlevels++] = MwTexDesc::Level{(uint32_t)(out.size() / 8), (uint32_t)w, (uint32_t)w - 1u, (uint32_t)h - 1u, (float)w, (float)h, (uint32_t)h, 0u};
-        auto chan = [&](int i, int j, int c) { return (uint32_t)cur[((size_t)(j % h) * w + (size_t)(i % w)) * 3 + c]; };
-        auto A = [&](int i, int j, int c) { return chan(i, j, c) * 256u + 128u; };
-        auto D = [&](int i, int j, int c) { return (chan(i + 1, j, c) - chan(i, j, c)) & 0xFFFFu; };
-        for (int j = 0; j < h; ++j)
-            for (int i = 0; i < w; ++i)
-                for (int r = 0; r < 2; ++r) {
-                    out.push_back(A(i, j + r, 0) | (A(i, j + r, 2) << 16)); out.push_back(D(i, j + r, 0) | (D(i, j + r, 2) << 16));
-                    out.push_back(A(i, j + r, 1)); out.push_back(D(i, j + r, 1));
-                }
-        if ((w == 1 && h == 1) || desc.nlevels == MW_MAX_LEVELS) break;
-        const int nw = std::max(1, w / 2), nh = std::max(1, h / 2);
-        nxt.assign((size_t)nw * nh * 3, 0);
-        for (int j = 0; j < nh; ++j) {
-            const Taps ty = axis_taps(h, nh, j);
-            for (int i = 0; i < nw; ++i) {
-                const Taps tx = axis_taps(w, nw, i);
-                for (int c = 0; c < 3; ++c) {
-                    const int t0 = lerp8(cur[((size_t)ty.i0 * w + tx.i0) * 3 + c], cur[((size_t)ty.i0 * w + tx.i1) * 3 + c], tx.w);
-                    const int t1 = lerp8(cur[((size_t)ty.i1 * w + tx.i0) * 3 + c], cur[((size_t)ty.i1 * w + tx.i1) * 3 + c], tx.w);
-                    nxt[((size_t)j * nw + i) * 3 + c] = (uint8_t)lerp8(t0, t1, ty.w);
-                }
-            }
-        }
-        cur.swap(nxt);
-        w = nw; h = nh;
     }
 }
 
@@ -550,42 +449,21 @@ int pick_waves_per_env(const mw_engine *e)
     return best;
 }
 
-// copy host [count][inner] <-> device SoA [inner][N] (component-major), element type T
-template <typename T>
-int xfer(mw_engine *e, T *dev, T *host, int first, int count, int inner, bool to_device)
+// copy host [count][slots][inner] <-> device, element type T: component k of slot s is an array over the envs at dev_of(k, s)
+template <typename T, typename F>
+int xfer(mw_engine *e, F dev_of, T *host, int first, int count, int slots, int inner, bool to_device)
 {
     if (!host) return MW_OK;
-    const int N = e->cfg.num_envs;
-    std::vector<T> tmp((size_t)count);
-    for (int k = 0; k < inner; ++k) {
-        T *d = dev + (size_t)k * N + first;
-        if (to_device) {
-            for (int i = 0; i < count; ++i) tmp[i] = host[(size_t)i * inner + k];
-            HIP_TRY(e, hipMemcpy(d, tmp.data(), sizeof(T) * count, hipMemcpyHostToDevice));
-        } else {
-            HIP_TRY(e, hipMemcpy(tmp.data(), d, sizeof(T) * count, hipMemcpyDeviceToHost));
-            for (int i = 0; i < count; ++i) host[(size_t)i * inner + k] = tmp[i];
-        }
-    }
-    return MW_OK;
-}
-
-// host [count][E][inner] <-> device [inner][E][N]
-template <typename T>
-int xfer_ent(mw_engine *e, T *dev, T *host, int first, int count, int inner, bool to_device)
-{
-    if (!host) return MW_OK;
-    const int N = e->cfg.num_envs, E = e->cfg.max_ents;
     std::vector<T> tmp((size_t)count);
     for (int k = 0; k < inner; ++k)
-        for (int s = 0; s < E; ++s) {
-            T *d = dev + ((size_t)k * E + s) * N + first;
+        for (int s = 0; s < slots; ++s) {
+            T *d = dev_of(k, s) + first;
             if (to_device) {
-                for (int i = 0; i < count; ++i) tmp[i] = host[((size_t)i * E + s) * inner + k];
+                for (int i = 0; i < count; ++i) tmp[i] = host[((size_t)i * slots + s) * inner + k];
                 HIP_TRY(e, hipMemcpy(d, tmp.data(), sizeof(T) * count, hipMemcpyHostToDevice));
             } else {
                 HIP_TRY(e, hipMemcpy(tmp.data(), d, sizeof(T) * count, hipMemcpyDeviceToHost));
-                for (int i = 0; i < count; ++i) host[((size_t)i * E + s) * inner + k] = tmp[i];
+                for (int i = 0; i < count; ++i) host[((size_t)i * slots + s) * inner + k] = tmp[i];
             }
         }
     return MW_OK;
@@ -596,34 +474,19 @@ int state_xfer(mw_engine *e, int first, int count, const mw_state_view *h, bool 
     if (!e || !h) return fail(e, MW_E_INVALID, "null argument");
     if (first < 0 || count < 0 || first + count > e->cfg.num_envs) return fail(e, MW_E_INVALID, "env range out of bounds");
     MwArgs &a = e->args;
-    int rc;
+    const size_t N = (size_t)e->cfg.num_envs, E = (size_t)e->cfg.max_ents;
+    // per env: host [count][inner], device SoA [inner][N] (component-major); per entity slot: host [count][E][inner], device [inner][E][N]
+    auto env = [&](auto *dev, auto *host, int inner) { return xfer(e, [=](int k, int) { return dev + k * N; }, host, first, count, 1, inner, to_device); };
+    auto ent = [&](auto *dev, auto *host, int inner) { return xfer(e, [=](int k, int s) { return dev + (k * E + s) * N; }, host, first, count, (int)E, inner, to_device); };
     // agent_pos is [count][3] on the host, three separate arrays on the device
-    if (h->agent_pos) {
-        std::vector<double> tmp((size_t)count);
-        double *dev[3] = {a.ax, a.ay, a.az};
-        for (int k = 0; k < 3; ++k) {
-            if (to_device) {
-                for (int i = 0; i < count; ++i) tmp[i] = h->agent_pos[(size_t)i * 3 + k];
-                HIP_TRY(e, hipMemcpy(dev[k] + first, tmp.data(), 8 * (size_t)count, hipMemcpyHostToDevice));
-            } else {
-                HIP_TRY(e, hipMemcpy(tmp.data(), dev[k] + first, 8 * (size_t)count, hipMemcpyDeviceToHost));
-                for (int i = 0; i < count; ++i) h->agent_pos[(size_t)i * 3 + k] = tmp[i];
-            }
-        }
-    }
-    if ((rc = xfer(e, a.adir, h->agent_dir, first, count, 1, to_device))) return rc;
-    if ((rc = xfer(e, a.cam, h->cam, first, count, 4, to_device))) return rc;
-    if ((rc = xfer(e, a.light, h->light, first, count, 12, to_device))) return rc;
-    if ((rc = xfer(e, a.carry, h->carrying, first, count, 1, to_device))) return rc;
-    if ((rc = xfer(e, a.step, h->step_count, first, count, 1, to_device))) return rc;
-    if ((rc = xfer(e, a.picked, h->num_picked_up, first, count, 1, to_device))) return rc;
-    if ((rc = xfer_ent(e, a.ekind, h->ent_kind, first, count, 1, to_device))) return rc;
-    if ((rc = xfer_ent(e, a.emesh, h->ent_mesh, first, count, 1, to_device))) return rc;
-    if ((rc = xfer_ent(e, a.estatic, h->ent_static, first, count, 1, to_device))) return rc;
-    if ((rc = xfer_ent(e, a.epos, h->ent_pos, first, count, 3, to_device))) return rc;
-    if ((rc = xfer_ent(e, a.edir, h->ent_dir, first, count, 1, to_device))) return rc;
-    if ((rc = xfer_ent(e, a.egeom, h->ent_geom, first, count, 9, to_device))) return rc;
-    if ((rc = xfer(e, a.extent, h->extent, first, count, 4, to_device))) return rc;
+    double *const pos[3] = {a.ax, a.ay, a.az};
+    int rc;
+    if ((rc = xfer(e, [&](int k, int) { return pos[k]; }, h->agent_pos, first, count, 1, 3, to_device)) || (rc = env(a.adir, h->agent_dir, 1)) || (rc = env(a.cam, h->cam, 4)) || (rc = env(a.light, h->light, 12)) ||
+        (rc = env(a.carry, h->carrying, 1)) || (rc = env(a.step, h->step_count, 1)) || (rc = env(a.picked, h->num_picked_up, 1)) ||
+        (rc = ent(a.ekind, h->ent_kind, 1)) || (rc = ent(a.emesh, h->ent_mesh, 1)) || (rc = ent(a.estatic, h->ent_static, 1)) ||
+        (rc = ent(a.epos, h->ent_pos, 3)) || (rc = ent(a.edir, h->ent_dir, 1)) || (rc = ent(a.egeom, h->ent_geom, 9)) ||
+        (rc = env(a.extent, h->extent, 4)))
+        return rc;
     return MW_OK;
 }
 
@@ -669,49 +532,74 @@ int sync_gen_args(mw_engine *e)
     return MW_OK;
 }
 
-// second, low-priority stream for work that runs beside the raster kernel (the Maze's spare refills)
-int ensure_side_stream(mw_engine *e)
+// Which kernels draw a frame of the engine's size (mw_raster_path), and the forms of them the launches pick: the one statement
+// of these conditions — launch_frame, the frame's mesh lists and ensure_mesh_buffers take their answer from here.  Inputs: msaa,
+// W x H, resident meshes, a visiting order, the MW_K2Q / MW_GENERIC_RASTER switches; the frame's layout, debug flags, depth.
+struct RasterPath {
+    int path;           // MW_PATH_TILE, MW_PATH_QUAD, MW_PATH_QUAD_MESH, MW_PATH_GENERIC
+    bool mesh;          // mesh entities through the tile / quad kernels: the frame runs the mesh chain (launch_mesh_chain) on the mesh path's lists
+    bool quad4;         // the quad kernel at 4 samples
+    // big scene: a visiting order exists; an output layout other than HWC or debug flags; a frame off the 16 x 4 grid; depth asked for
+    bool big, general, ragged, depth;
+};
+RasterPath raster_path(const mw_engine *e, bool depth)
 {
-    if (!e->side_stream) HIP_TRY(e, make_stream(e->side_stream));
-    if (!e->ev_fork) HIP_TRY(e, make_event(e->ev_fork));
-    return MW_OK;
+    const MwArgs &a = e->args; const int S = e->cfg.msaa;
+    RasterPath p{MW_PATH_GENERIC, false, false, a.rec_order != nullptr, e->obs_layout != MW_OBS_HWC_U8 || e->dbg_flags != 0, !frame_on_grid(a.W, a.H), depth};
+    // the quad kernel (mw_rasterq.hip): small scenes without a visiting order, frames that fit its LDS plan — 8 samples (the
+    // hot path) and 4 (llvmpipe's GL_MAX_SAMPLES: the reference's own frames run through the same code); with mesh entities
+    // it draws the tiles no mesh can touch (8 samples only)
+    // (big scenes — a visiting order exists — keep the tile kernels: their near-to-far order with its early exit is the better fit
+    // for deep scenes; the quad kernel on the Maze was measured and lost, tools/experiments/README.md)
+    const bool k2q = e->use_k2q && e->k2q_ok && !p.big && !(S == 4 && (e->have_meshes || e->generic_raster));
+    // a ragged frame the ragged tile kernels draw (frame_on_grid).  The even H: the tile kernels' 2x2 quads (texture lod) pair image rows from
+    // the top, GL pairs window rows from the bottom (mw_frag.h), and the two agree only then.  Odd heights take the generic-resolution kernels.
+    const bool ragged_tiles = !e->have_meshes && p.ragged && a.H % 2 == 0 && tile_kernels_exact(a.tiles_x * MW_TILE_W, a.tiles_y * MW_TILE_H);
+    p.quad4 = k2q && S == 4;
+    // FrameBuffer's fallback sample counts (opengl.py:229-231: a driver that clamps GL_MAX_SAMPLES gets 4 or 1
+    // samples), observations beyond 128 x 128 (the tile kernels' 24-bit edge arithmetic) and frames off the 16 x 4 grid:
+    // the generic-resolution kernels, 64-bit edge values, exact packed-key resolution, every output layout, the whole
+    // batch in one grid (blockIdx.y = env)
+    const bool generic = S != 8 || (!tile_path_ok(a.W, a.H) && !ragged_tiles);
+    p.mesh = !p.quad4 && !generic && e->have_meshes;
+    p.path = p.quad4 ? MW_PATH_QUAD : generic ? MW_PATH_GENERIC : !k2q ? MW_PATH_TILE : p.mesh ? MW_PATH_QUAD_MESH : MW_PATH_QUAD;
+    return p;
 }
 
-// Everything a frame with mesh entities needs beyond the triangle records — the plane cache (one record per mesh triangle that
-// can be in view: the geometry kernel admits 0xC000 per env), the sample keys of the tiles a mesh can touch, the slow-path
-// lists, the mesh stream; for the generic-resolution path the view keys.  Called by mw_upload_mesh (a synchronous entry point):
-// a frame never allocates, never synchronises.  Failure-atomic: either every buffer of a group is there or none.
+// Fills mw_engine::MeshPath: everything a frame with mesh entities needs beyond the triangle records — the plane cache (one record
+// per mesh triangle that can be in view: the geometry kernel admits 0xC000 per env), the sample keys of the tiles a mesh can touch,
+// the slow-path lists, the mesh stream; for the generic-resolution path the view keys.  Called by mw_upload_mesh (a synchronous
+// entry point): a frame never allocates, never synchronises.  Failure-atomic: either every buffer of a group is there or none.
 int ensure_mesh_buffers(mw_engine *e)
 {
-    const MwArgs &a = e->args;
+    const MwArgs &a = e->args; mw_engine::MeshPath &m = e->mp;
     const size_t N = (size_t)e->cfg.num_envs;
     // the stream of the raster kernel's first part in a frame with meshes: LOW priority — the mesh kernels on the caller's stream are the
     // critical path, the quad kernel fills the CUs around them
-    if (!e->quad_stream) HIP_TRY(e, make_stream(e->quad_stream));
-    if (!e->ev_mesh_fork) HIP_TRY(e, make_event(e->ev_mesh_fork));
-    if (!e->ev_mesh_join) HIP_TRY(e, make_event(e->ev_mesh_join));
-    if (e->cfg.msaa != 8 || !tile_path_ok(a.W, a.H))        // the generic-resolution path
-        return grow(e, e->d_view_keys, e->view_keys_bytes, N * a.W * a.H * e->cfg.msaa * 4, 1);
+    if (!m.quad_stream) HIP_TRY(e, make_stream(m.quad_stream));
+    for (Event *ev : {&m.ev_fork, &m.ev_join}) if (!*ev) HIP_TRY(e, make_event(*ev));
+    if (raster_path(e, false).path == MW_PATH_GENERIC)
+        return grow(e, m.view_keys, m.view_keys_bytes, N * a.W * a.H * e->cfg.msaa * 4, 1);
     if (a.W > 255 * MW_TILE_W || a.H > 255 * MW_TILE_H) return fail(e, MW_E_CAPACITY, "frame too large for the mesh tile rectangles");
     // the mesh tiles' work list (mw_geom.hip): a tile index in the 8 bits above the env, and one bit of a lane's 32-bit mask per tile
-    // sub + k L.  tile_path_ok caps these frames at 192 tiles and the geometry kernel has at least 8 lanes per env, so this holds
-    // today; a larger frame limit or fewer lanes must not leave mesh tiles undrawn (and their sample keys uncleared) in silence
+    // sub + k L.  tile_path_ok caps these frames at 192 tiles and the geometry kernel has at least 8 lanes per env, so
+    // this holds today; a larger frame limit or fewer lanes must not leave mesh tiles undrawn (and their sample keys uncleared) in silence
     if (a.n_tiles > 255 || a.n_tiles > 32 * geom_lanes(e))
         return fail(e, MW_E_CAPACITY, "%d tiles per frame: the mesh tiles' work list holds 255 (8-bit tile index) and 32 per lane of the geometry kernel (%d lanes)", a.n_tiles, geom_lanes(e));
     const long long want = std::min<long long>(0xC000, (long long)e->cfg.max_ents * e->max_mesh_tris);
     int rc;
-    if ((rc = grow(e, e->d_plane_cache, e->plane_cap, (int)want, N * (MW_PLANE_REC + MW_PLANE_XTRA) * 4))) return rc;
-    if (!e->d_ent_list) {
+    if ((rc = grow(e, m.plane_cache, m.plane_cap, (int)want, N * (MW_PLANE_REC + MW_PLANE_XTRA) * 4))) return rc;
+    if (!m.ent_list) {
         // (all three work lists or none)
         const int cap = (int)N * std::min(MW_MAX_MESH_ENTS, std::max(e->cfg.max_ents, 1));
         DevBuf<uint32_t> ents, slow, tiles;
         if ((rc = dev_alloc(e, ents, (size_t)cap * 16, false)) || (rc = dev_alloc(e, slow, N * 2, false)) ||
             (rc = dev_alloc(e, tiles, N * (size_t)a.n_tiles * 8, false)))
             return rc;
-        e->ent_list_cap = cap;
-        e->d_ent_list = std::move(ents); e->d_slow_envs = std::move(slow); e->d_tile_list = std::move(tiles);
+        m.ent_list_cap = cap;
+        m.ent_list = std::move(ents); m.slow_envs = std::move(slow); m.tile_list = std::move(tiles);
     }
-    if (!e->d_mesh_keys) {
+    if (!m.keys) {
         const size_t px = N * a.W * a.H;
         DevBuf<uint32_t> keys, tris, head; DevBuf<int32_t> cnt; DevBuf<float4> frags;
         // triangles that cross a frustum plane and their fragments (mw_mesh_slow_kernel): counts, 1024 / 2048 entries per env
@@ -720,35 +608,30 @@ int ensure_mesh_buffers(mw_engine *e)
             (rc = dev_alloc(e, head, px)))
             return rc;
         HIP_TRY(e, hipMemset(keys.get(), 0xFF, px * 8 * 4));
-        e->d_ent_counter = cnt.get() + N * 4;       // (behind the slow path's counts)
-        e->d_mesh_keys = std::move(keys); e->d_slow_count = std::move(cnt); e->d_slow_tris = std::move(tris);
-        e->d_slow_frags = std::move(frags); e->d_slow_head = std::move(head);
+        m.ent_counter = cnt.get() + N * 4;          // (behind the slow path's counts)
+        m.keys = std::move(keys); m.slow_count = std::move(cnt); m.slow_tris = std::move(tris);
+        m.slow_frags = std::move(frags); m.slow_head = std::move(head);
         // (the memsets above ran on the null stream, which a caller's non-blocking stream is not ordered against: finish them here)
         (void)hipDeviceSynchronize();
-        e->mesh_keys_dirty = false;
+        m.keys_dirty = false;
     }
     return MW_OK;
 }
 
-// a ragged frame the ragged tile kernels draw: 8 samples, no mesh entities, a grid inside the tile kernels' edge bound, and an
-// even H — the tile kernels' 2x2 quads (texture lod) pair image rows from the top, GL pairs window rows from the bottom
-// (mw_frag.h): the two agree only when H is even.  Odd heights take the generic-resolution kernels.
-bool ragged_tiles_ok(const mw_engine *e)
+// This frame's side of the mesh path's double-buffered lists: the work lists' counters, the slow-path lists and the fragment stamps
+// alternate between two sets from frame to frame (the entity kernel zeroes the next frame's counters).  Every parity offset is here.
+struct MeshFrame {
+    uint32_t stamp;                 // frame stamp of the slow-fragment chains: the sequence number's low 16 bits
+    int parity;                     // (the slow kernel indexes slow_count itself)
+    int32_t *cnt, *cnt_next, *slow_count;   // [MW_CNT_WORDS] this frame's lengths and cursors of the work lists, the next frame's; [2][N] this frame's listed triangles, fragments
+    uint32_t *slow_envs;            // [N] this frame's envs with slow-path triangles: cnt[MW_CNT_SLOW_ENVS] of them
+};
+MeshFrame mesh_frame(mw_engine::MeshPath &m, size_t N)
 {
-    const MwArgs &a = e->args;
-    return e->cfg.msaa == 8 && !e->have_meshes && !frame_on_grid(a.W, a.H) && a.H % 2 == 0 &&
-           tile_kernels_exact(a.tiles_x * MW_TILE_W, a.tiles_y * MW_TILE_H);
-}
-
-// the generic-resolution raster kernel (mw_raster_mesh.hip) over `count` envs from first_env, or over the envs of a list: frames
-// off the 16 x 4 grid and the wrapper layouts take its "any" form (mw_raster_view_any.hip)
-void launch_view_raster(const mw_engine *e, const MwArgs &a, int first_env, int count, int S, const uint32_t *keys, uint8_t *out, float *depth,
-                        int layout, const int32_t *list, hipStream_t st)
-{
-    const bool any = !frame_on_grid(a.W, a.H) || layout != MW_OBS_HWC_U8;
-    launch(any ? MW_PAIR(mw_view_raster_any) : MW_PAIR(mw_view_raster), list, dim3(a.n_tiles, count), dim3(64), 0, st, first_env, a.W, a.H, S,
-           a.max_vis, a.tiles_x, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull, (const int32_t *)a.nvis,
-           (const float *)a.envhdr, a.tex, a.texels, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, keys, out, depth, e->texel_bytes, layout);
+    const uint32_t seq = m.frame_seq++;         // (the next frame through the lists)
+    const int parity = (int)(seq & 1u);
+    return {seq & 0xFFFFu, parity, m.ent_counter + parity * MW_CNT_WORDS, m.ent_counter + (parity ^ 1) * MW_CNT_WORDS,
+            m.slow_count.get() + (size_t)parity * 2 * N, m.slow_envs.get() + (size_t)parity * N};
 }
 
 // The frames of a same-step step with final observations (mw_step): FRAME_TERMINAL — the step kernel runs as the next-step mode's
@@ -756,6 +639,154 @@ void launch_view_raster(const mw_engine *e, const MwArgs &a, int first_env, int 
 // shows every env's state after the step (terminal states for the finished envs); FRAME_LIST — no step, the frame of the listed
 // envs only (their new worlds), through the list forms of the geometry and raster kernels.
 enum { FRAME_ALL = 0, FRAME_TERMINAL = 1, FRAME_LIST = 2 };
+
+// what the stages of one frame share (launch_frame)
+struct Frame {
+    MwArgs a;
+    int view_flags;
+    const int32_t *list;        // FRAME_LIST: the list forms draw the listed envs only
+    uint8_t *obs; float *depth; hipStream_t st; bool reuse;
+    RasterPath p;
+    MeshFrame mf;               // p.mesh only
+};
+
+// the step (a render-only frame has none), the list of a FRAME_TERMINAL step's finished envs, the frame's vertex half, CollectHealth's respawns
+void launch_step_and_geometry(mw_engine *e, const Frame &f, bool do_step, int frame, bool async_refill, const int32_t *d_actions,
+                              float *d_reward, uint8_t *d_term, uint8_t *d_trunc)
+{
+    const MwArgs &a = f.a; const int N = e->cfg.num_envs;
+    if (do_step) {
+        // spare mode: blocks appended to the grid regenerate the spare worlds consumed in earlier steps, beside the step itself
+        // (the Maze's go to the side stream: launch_side_refill)
+        const int refill_blocks = (e->spare_mode && !async_refill) ? (N + 63) / 64 : 0;
+        MwArgs ak = a;          // the step kernel's arguments: the first pass of a final-observation step runs as a next-step terminal step
+        if (frame == FRAME_TERMINAL) ak.autoreset = MW_AUTORESET_NEXT_STEP;
+        const int lanes = k1_dense_lanes(e), epw = lanes ? 64 / lanes : 1;      // envs per workgroup
+        hipLaunchKernelGGL(k1_of(e, lanes), dim3((N + epw - 1) / epw + refill_blocks), dim3(64), 0, f.st, ak, lanes, d_actions,
+                           d_reward ? d_reward : e->d_reward_scratch, d_term ? d_term : e->d_flag_scratch,
+                           d_trunc ? d_trunc : e->d_flag_scratch + N);
+    }
+    if (frame == FRAME_TERMINAL)
+        hipLaunchKernelGGL(mw_final_list_kernel, dim3(1), dim3(1024), 0, f.st, N, (const uint8_t *)a.reset_pending, a.pending_remove, e->d_final_list);
+    // the frame's vertex half: camera, lighting, transform, clipping, triangle setup (mw_geom.hip)
+    const int L = geom_lanes(e), epw = 64 / L;
+    launch(geom_kernel_of(L, e->cfg.msaa), f.list, dim3((N + epw - 1) / epw), dim3(64), 0, f.st, a, f.view_flags, e->cfg.msaa, L, N);
+    if (do_step && e->cfg.task == MW_TASK_COLLECT)
+        hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_collect_respawn_pcg_kernel : mw_collect_respawn_kernel, dim3((N + 63) / 64), dim3(64), 0, f.st, a);
+}
+
+// The Maze's spare worlds: regenerating one takes ~300 us on a single wave, four times a whole step of the batch, and any launch
+// that carries such a block lasts that long.  Its refills go to a kernel of their own on the low-priority side stream, running
+// beside this and the next steps; nothing waits for it but the entry points that touch the worlds from the host
+// (ON_DEVICE_SYNC) — an env that needs its spare earlier follows the refill_mask protocol.
+int launch_side_refill(mw_engine *e, hipStream_t st)
+{
+    if (!e->side_stream) HIP_TRY(e, make_stream(e->side_stream));
+    if (!e->ev_fork) HIP_TRY(e, make_event(e->ev_fork));
+    HIP_TRY(e, hipEventRecord(e->ev_fork.get(), st));
+    HIP_TRY(e, hipStreamWaitEvent(e->side_stream.get(), e->ev_fork.get(), 0));
+    hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_refill_pcg_kernel : mw_refill_kernel, dim3(e->cfg.num_envs), dim3(64), 0, e->side_stream.get(), e->args);
+    e->side_refill_pending = true;
+    return MW_OK;
+}
+
+// The generic-resolution path (mw_raster_mesh.hip) over `count` envs from first_env, or over the envs of a list, at a.W x a.H and
+// S samples: with meshes resident the view keys are cleared and the mesh triangles scattered into them (mesh_grid), then the
+// raster kernel — frames off the 16 x 4 grid and the wrapper layouts take its "any" form (mw_raster_view_any.hip).
+int launch_generic(mw_engine *e, const MwArgs &a, int first_env, int count, int S, dim3 mesh_grid, uint8_t *out, float *depth,
+                   int layout, const int32_t *list, hipStream_t st)
+{
+    uint32_t *keys = nullptr;
+    if (e->have_meshes) {
+        const size_t need = (size_t)count * a.W * a.H * S * 4;
+        if (need > e->mp.view_keys_bytes) return fail(e, MW_E_INVALID, "view keys missing (mw_upload_mesh allocates them)");
+        keys = e->mp.view_keys.get();
+        HIP_TRY(e, hipMemsetAsync(keys, 0xFF, need, st));
+        launch(MW_PAIR(mw_view_mesh), list, mesh_grid, dim3(256), 0, st, a.W, a.H, S, first_env, (const float *)a.envhdr, a.mesh_pos, keys);
+    }
+    const bool any = !frame_on_grid(a.W, a.H) || layout != MW_OBS_HWC_U8;
+    launch(any ? MW_PAIR(mw_view_raster_any) : MW_PAIR(mw_view_raster), list, dim3(a.n_tiles, count), dim3(64), 0, st, first_env, a.W, a.H, S,
+           a.max_vis, a.tiles_x, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull, (const int32_t *)a.nvis,
+           (const float *)a.envhdr, a.tex, a.texels, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, keys, out, depth, e->texel_bytes, layout);
+    return MW_OK;
+}
+
+// the quad kernel (mw_rasterq.hip); part: raster_flags
+void launch_quad(const mw_engine *e, const Frame &f, int part, hipStream_t st)
+{
+    const MwArgs &a = f.a;
+    const int lds = mw_rasterq_lds_bytes(e->cfg.msaa, a.W, a.H, a.n_tiles, f.depth ? 1 : 0);
+    launch(f.p.quad4 ? MW_PAIR(mw_rasterq4) : MW_PAIR(mw_rasterq), f.list, dim3(e->cfg.num_envs), dim3(MWQ_THREADS), (size_t)lds, st, a.N, a.W, a.H, a.max_vis,
+           a.tiles_x, a.n_tiles, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
+           (const int32_t *)a.nvis, (const float *)a.envhdr, a.texels, f.obs, f.depth, raster_flags(e, part, 0u, f.reuse), e->texel_bytes, e->d_k2q_prof,
+           (const uint8_t *)a.frame_clean);
+}
+
+// the tile kernels (mw_raster.hip); part: raster_flags
+void launch_tiles(const mw_engine *e, const Frame &f, int part, hipStream_t st)
+{
+    const MwArgs &a = f.a; const mw_engine::MeshPath &m = e->mp;
+    const int N = e->cfg.num_envs, wpe = e->waves_per_env;
+    // big scenes (a visiting order exists): records read in place, near to far; otherwise the env's records are staged
+    // in LDS when there are at most MW_LDS_RECS of them (a wave whose env holds more reads them in place).
+    const int lds_recs = a.max_vis < MW_LDS_RECS ? a.max_vis : MW_LDS_RECS;
+    const size_t lds = f.p.big ? 192 : (size_t)lds_recs * (MW_LDS_SHADE_Q + MW_LDS_CULL_Q) * 16 + 192;
+    // the second part (the tiles a mesh can touch: few, slow, clustered): persistent wavefronts over the geometry kernel's
+    // tile list (part 3)
+    const bool listed = part == 2 && a.tile_list != nullptr;
+    if (listed) part = 3;
+    const int wpe2 = part == 2 ? a.n_tiles : wpe;
+    const int tpw2 = part == 2 ? 1 : (a.n_tiles + wpe - 1) / wpe;
+    const int grid = listed ? std::min(m.mesh_tile_waves, N * (int)a.n_tiles) : (N + 7) / 8 * 8 * wpe2;
+    launch(tile_kernel_of(f.p.big, f.p.depth, f.p.general, f.p.ragged, f.p.mesh, part == 1), f.list, dim3(grid), dim3(64), lds, st,
+           a.N, a.W, a.H, a.max_vis, a.tiles_x, a.n_tiles, wpe2, tpw2, (const float *)a.rec_raster, (const float *)a.rec_shade,
+           (const float *)a.rec_cull, (const int32_t *)a.nvis, (const float *)a.envhdr, a.tex, a.texels, f.obs, f.depth, raster_flags(e, part, f.mf.stamp, f.reuse),
+           e->texel_bytes, (const uint16_t *)a.rec_order, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, m.keys.get(),
+           (const float *)m.plane_cache.get(), m.plane_cap, (const float4 *)m.slow_frags.get(), (const uint32_t *)m.slow_head.get(),
+           (const uint32_t *)a.tile_list, a.ent_list_n, a.tile_list_cap, std::max(a.n_xcc, 1), (const uint8_t *)a.frame_clean);
+}
+
+// A frame with mesh entities through the tile / quad kernels, behind the geometry kernel: the mesh kernels, the raster kernel's
+// first part beside them on the quad stream, its second part behind both.
+int launch_mesh_chain(mw_engine *e, const Frame &f, hipStream_t st)
+{
+    const MwArgs &a = f.a; const MeshFrame &mf = f.mf;
+    mw_engine::MeshPath &m = e->mp; const int N = e->cfg.num_envs;
+    // (plane cache, sample keys — all-ones between frames, K2 clears what it reads —, slow-path lists, mesh stream:
+    // ensure_mesh_buffers, at upload time)
+    if (!m.keys || !m.plane_cache || !m.quad_stream) return fail(e, MW_E_INVALID, "mesh buffers missing (mw_upload_mesh allocates them)");
+    if (m.keys_dirty) HIP_TRY(e, hipMemsetAsync(m.keys.get(), 0xFF, (size_t)N * a.W * a.H * 8 * 4, st));
+    m.keys_dirty = true;        // until the raster kernel that clears them again has been enqueued
+    // The stamp has 16 bits: a head that no frame has overwritten since frame F would read as valid again at frame F + 65536 (24 s
+    // of PickupObjects), so the heads are wiped on the frame whose stamp is 0 — behind the previous frame's readers, before this
+    // frame's slow-path kernel, in stream order (tests/test_gpu_env_api.py::test_slow_fragment_heads_survive_the_stamp_wrap)
+    if (mf.stamp == 0u) HIP_TRY(e, hipMemsetAsync(m.slow_head.get(), 0, (size_t)N * a.W * a.H * 4, st));
+    // The mesh kernels — the frame's critical path — stay on the caller's stream, right behind the geometry kernel; the quad
+    // kernel, which draws every tile no mesh can touch, goes to the low-priority quad stream beside them.  (The other way
+    // round — mesh kernels on a side stream — the quad kernel started a few microseconds EARLIER, its 2 048 workgroups
+    // took the CUs, and the entity kernel's workgroups waited a quad-kernel workgroup's lifetime for room: 212 instead of
+    // 133 us, PickupObjects 4.55 -> 5.3 M env-steps/s.)
+    HIP_TRY(e, hipEventRecord(m.ev_fork.get(), st));
+    HIP_TRY(e, hipStreamWaitEvent(m.quad_stream.get(), m.ev_fork.get(), 0));
+    // persistent workgroups drawing entities from the geometry kernel's list (two sets of counters swapping places: the
+    // kernel zeroes the next frame's)
+    hipLaunchKernelGGL(mw_mesh_entity_kernel, dim3(std::max(a.n_xcc, std::min(m.ent_list_cap, m.ent_blocks))), dim3(MW_ENT_THREADS), (size_t)e->max_mesh_verts * 16, st, N, a.W, a.H,
+                       (const float *)a.envhdr, a.mesh, (const float4 *)e->pools.vpos.get(), (const uint2 *)e->pools.idx.get(), (const float *)e->pools.stream.get(),
+                       (const float *)e->pools.attr.get(), m.keys.get(), m.plane_cache.get(), m.plane_cap, mf.slow_count, m.slow_tris.get(),
+                       (const uint32_t *)m.ent_list.get(), m.ent_list_cap, mf.cnt, mf.cnt_next, mf.slow_envs, e->args.n_xcc, e->d_ent_prof);
+    hipLaunchKernelGGL(mw_mesh_slow_kernel, dim3(std::min(N * 16, m.slow_waves)), dim3(64), 0, st, a.W, a.H, (const float *)a.envhdr, a.mesh_pos, a.mesh_nrm, a.mesh_rgb,
+                       a.mesh_uv, a.texels, e->texel_bytes, m.keys.get(), m.slow_count.get(), N, mf.parity, (const uint32_t *)m.slow_tris.get(),
+                       m.slow_frags.get(), m.slow_head.get(), mf.stamp, a.status,
+                       (const uint32_t *)mf.slow_envs, (const int32_t *)(mf.cnt + MW_CNT_SLOW_ENVS));
+    // the first part — every tile no mesh can touch: it needs nothing of the mesh kernels — on the quad stream beside them
+    // (forked above, behind the geometry kernel); the mesh tiles end the chain on the caller's stream
+    if (f.p.path == MW_PATH_QUAD_MESH) launch_quad(e, f, 1, m.quad_stream.get()); else launch_tiles(e, f, 1, m.quad_stream.get());
+    launch_tiles(e, f, 2, st);
+    HIP_TRY(e, hipEventRecord(m.ev_join.get(), m.quad_stream.get()));
+    HIP_TRY(e, hipStreamWaitEvent(st, m.ev_join.get(), 0));
+    m.keys_dirty = false;
+    return MW_OK;
+}
 
 int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_actions, uint8_t *d_obs, float *d_depth,
                  float *d_reward, uint8_t *d_term, uint8_t *d_trunc, hipStream_t st, int frame = FRAME_ALL)
@@ -769,16 +800,15 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
     const bool reuse = e->frame_reuse && plain && do_step && !e->have_meshes && e->dbg_flags == 0 && e->held.valid && e->held.obs == d_obs &&
                        e->held.depth == d_depth && e->held.layout == e->obs_layout;
     drop_held_frame(e);
-    MwArgs a = e->args;
-    a.step_override = e->use_step_override ? e->d_step_override : nullptr;
     const int N = e->cfg.num_envs;
+    Frame f{e->args, view_flags, frame == FRAME_LIST ? e->d_final_list : nullptr, d_obs, d_depth, st, reuse, raster_path(e, d_depth != nullptr), {}};
+    f.a.step_override = e->use_step_override ? e->d_step_override : nullptr;
     // a frame with mesh entities through the tile / quad kernels: the geometry kernel lists the entities in view for the mesh
-    // entity kernel (lists, slow-path lists and fragment stamps alternate between two sets from frame to frame)
-    const bool mesh_obs = e->have_meshes && e->cfg.msaa == 8 && tile_path_ok(a.W, a.H) && e->d_ent_list && e->d_mesh_keys;
-    const uint32_t mesh_seq = mesh_obs ? e->mesh_frame_seq++ : 0u;
-    if (mesh_obs) {
-        a.ent_list = e->d_ent_list.get(); a.ent_list_n = e->d_ent_counter + (mesh_seq & 1u) * MW_CNT_WORDS; a.ent_list_cap = e->ent_list_cap;
-        a.tile_list = e->d_tile_list.get(); a.tile_list_cap = N * a.n_tiles;
+    // entity kernel and the tiles a mesh can touch for the raster kernel's second part
+    if (f.p.mesh && e->mp.ent_list && e->mp.keys) {
+        f.mf = mesh_frame(e->mp, (size_t)N);
+        f.a.ent_list = e->mp.ent_list.get(); f.a.ent_list_n = f.mf.cnt; f.a.ent_list_cap = e->mp.ent_list_cap;
+        f.a.tile_list = e->mp.tile_list.get(); f.a.tile_list_cap = N * f.a.n_tiles;
     }
     mw_engine::Ev ev{};
     // kernel durations are sampled: three event records on every launch cost ~4 % of the step rate,
@@ -789,151 +819,17 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
         ev = get_events(e);
         (void)hipEventRecord(ev.a.get(), st);
     }
-    // spare mode: blocks appended to the grid regenerate the spare worlds consumed in earlier steps, beside the step itself
-    // ... except for the Maze: regenerating one takes ~300 us on a single wave, four times a whole step of the batch, and
-    // any launch that carries such a block lasts that long.  Its refills go to a kernel of their own on the low-priority
-    // side stream (below), running beside this and the next steps; nothing waits for it but the entry points that touch
-    // the worlds from the host (ON_DEVICE_SYNC) — an env that needs its spare earlier follows the refill_mask protocol.
     const bool async_refill = e->spare_mode && do_step && e->cfg.generator == MW_GEN_MAZE;
-    const int refill_blocks = (e->spare_mode && do_step && !async_refill) ? (N + 63) / 64 : 0;
-    const int gl = geom_lanes(e);
-    const int32_t *list = frame == FRAME_LIST ? e->d_final_list : nullptr;     // (the list forms draw the listed envs only)
-    MwArgs ak = a;          // the step kernel's arguments: the first pass of a final-observation step runs as a next-step terminal step
-    if (frame == FRAME_TERMINAL) ak.autoreset = MW_AUTORESET_NEXT_STEP;
-    if (do_step) {      // (a render-only frame has nothing to step)
-        const int lanes = k1_dense_lanes(e), epw = lanes ? 64 / lanes : 1;      // envs per workgroup
-        hipLaunchKernelGGL(k1_of(e, lanes), dim3((N + epw - 1) / epw + refill_blocks), dim3(64), 0, st, ak, lanes, d_actions,
-                           d_reward ? d_reward : e->d_reward_scratch, d_term ? d_term : e->d_flag_scratch,
-                           d_trunc ? d_trunc : e->d_flag_scratch + N);
-    }
-    if (frame == FRAME_TERMINAL)
-        hipLaunchKernelGGL(mw_final_list_kernel, dim3(1), dim3(1024), 0, st, N, (const uint8_t *)a.reset_pending, a.pending_remove, e->d_final_list);
-    // the frame's vertex half: camera, lighting, transform, clipping, triangle setup (mw_geom.hip)
-    {
-        const int L = gl, epw = 64 / L;
-        launch(geom_kernel_of(L, e->cfg.msaa), list, dim3((N + epw - 1) / epw), dim3(64), 0, st, a, view_flags, e->cfg.msaa, L, N);
-    }
-    if (do_step && e->cfg.task == MW_TASK_COLLECT)
-        hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_collect_respawn_pcg_kernel : mw_collect_respawn_kernel, dim3((N + 63) / 64), dim3(64), 0, st, a);
+    launch_step_and_geometry(e, f, do_step, frame, async_refill, d_actions, d_reward, d_term, d_trunc);
     if (timed) (void)hipEventRecord(ev.b.get(), st);
-    if (async_refill) {
-        if (ensure_side_stream(e) != MW_OK) return MW_E_HIP;
-        HIP_TRY(e, hipEventRecord(e->ev_fork.get(), st));
-        HIP_TRY(e, hipStreamWaitEvent(e->side_stream.get(), e->ev_fork.get(), 0));
-        hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_refill_pcg_kernel : mw_refill_kernel, dim3(N), dim3(64), 0, e->side_stream.get(), e->args);
-        e->side_refill_pending = true;
-    }
-    // the quad kernel (mw_rasterq.hip): small scenes without a visiting order, frames that fit its LDS plan — 8 samples (the
-    // hot path) and 4 (llvmpipe's GL_MAX_SAMPLES: the reference's own frames run through the same code); with mesh entities
-    // it draws the tiles no mesh can touch (8 samples only)
-    const bool big_scene = a.rec_order != nullptr;
-    // (big scenes — a visiting order exists — keep the tile kernels: their near-to-far order with its early exit is the better fit
-    // for deep scenes; the quad kernel on the Maze was measured and lost, tools/experiments/README.md)
-    const bool k2q = e->use_k2q && e->k2q_ok && !big_scene && !(e->cfg.msaa == 4 && (e->have_meshes || e->generic_raster));
-    auto launch_k2q = [&](int part, hipStream_t kq) {
-        const int S = e->cfg.msaa;
-        const int lds = mw_rasterq_lds_bytes(S, a.W, a.H, a.n_tiles, d_depth ? 1 : 0);
-        const int flags = raster_flags(e, part, 0u, reuse);
-        launch(S == 8 ? MW_PAIR(mw_rasterq) : MW_PAIR(mw_rasterq4), list, dim3(N), dim3(MWQ_THREADS), (size_t)lds, kq, a.N, a.W, a.H, a.max_vis,
-               a.tiles_x, a.n_tiles, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
-               (const int32_t *)a.nvis, (const float *)a.envhdr, a.texels, d_obs, d_depth, flags, e->texel_bytes, e->d_k2q_prof,
-               (const uint8_t *)a.frame_clean);
-    };
-    if (k2q && e->cfg.msaa == 4) {
-        launch_k2q(0, st);
-        e->last_raster_path = MW_PATH_QUAD;
-    } else if (e->cfg.msaa != 8 || (!tile_path_ok(a.W, a.H) && !ragged_tiles_ok(e))) {
-        // FrameBuffer's fallback sample counts (opengl.py:229-231: a driver that clamps GL_MAX_SAMPLES gets 4 or 1
-        // samples), observations beyond 128 x 128 (the tile kernels' 24-bit edge arithmetic) and frames off the 16 x 4 grid:
-        // the generic-resolution kernels, 64-bit edge values, exact packed-key resolution, every output layout, the whole
-        // batch in one grid (blockIdx.y = env)
-        const int S = e->cfg.msaa;
-        uint32_t *keys = nullptr;
-        if (e->have_meshes) {
-            const size_t need = (size_t)N * a.W * a.H * S * 4;
-            if (need > e->view_keys_bytes) return fail(e, MW_E_INVALID, "view keys missing (mw_upload_mesh allocates them)");
-            keys = e->d_view_keys.get();
-            HIP_TRY(e, hipMemsetAsync(keys, 0xFF, need, st));
-            launch(MW_PAIR(mw_view_mesh), list, dim3(32, N), dim3(256), 0, st, a.W, a.H, S, 0, (const float *)a.envhdr, a.mesh_pos, keys);
-        }
-        e->last_raster_path = MW_PATH_GENERIC;
-        launch_view_raster(e, a, 0, N, S, keys, d_obs, d_depth, e->obs_layout, list, st);
-    } else {
-        const bool mesh = e->have_meshes;
-        uint32_t mesh_stamp = 0u;
-        if (mesh) {
-            // (plane cache, sample keys — all-ones between frames, K2 clears what it reads —, slow-path lists, mesh stream:
-            // ensure_mesh_buffers, at upload time)
-            if (!e->d_mesh_keys || !e->d_plane_cache || !e->quad_stream) return fail(e, MW_E_INVALID, "mesh buffers missing (mw_upload_mesh allocates them)");
-            const size_t key_bytes = (size_t)N * a.W * a.H * 8 * 4;
-            if (e->mesh_keys_dirty) HIP_TRY(e, hipMemsetAsync(e->d_mesh_keys.get(), 0xFF, key_bytes, st));
-            e->mesh_keys_dirty = true;      // until the raster kernel that clears them again has been enqueued
-            // frame stamp of the slow-fragment chains and parity of the lists.  The stamp has 16 bits: a head that no frame has
-            // overwritten since frame F would read as valid again at frame F + 65536 (24 s of PickupObjects), so the heads are
-            // wiped on the frame whose stamp is 0 — behind the previous frame's readers, before this frame's slow-path kernel, in
-            // stream order (tests/test_gpu_env_api.py::test_slow_fragment_heads_survive_the_stamp_wrap)
-            const uint32_t seq = mesh_seq;
-            mesh_stamp = seq & 0xFFFFu;
-            if (mesh_stamp == 0u) HIP_TRY(e, hipMemsetAsync(e->d_slow_head.get(), 0, (size_t)N * a.W * a.H * 4, st));
-            const int parity = (int)(seq & 1u);
-            // The mesh kernels — the frame's critical path — stay on the caller's stream, right behind the geometry kernel; the quad
-            // kernel, which draws every tile no mesh can touch, goes to the low-priority quad stream beside them.  (The other way
-            // round — mesh kernels on a side stream — the quad kernel started a few microseconds EARLIER, its 2 048 workgroups
-            // took the CUs, and the entity kernel's workgroups waited a quad-kernel workgroup's lifetime for room: 212 instead of
-            // 133 us, PickupObjects 4.55 -> 5.3 M env-steps/s.)
-            HIP_TRY(e, hipEventRecord(e->ev_mesh_fork.get(), st));
-            HIP_TRY(e, hipStreamWaitEvent(e->quad_stream.get(), e->ev_mesh_fork.get(), 0));
-            // persistent workgroups drawing entities from the geometry kernel's list (two sets of counters swapping places: the
-            // kernel zeroes the next frame's)
-            hipLaunchKernelGGL(mw_mesh_entity_kernel, dim3(std::max(a.n_xcc, std::min(e->ent_list_cap, e->ent_blocks))), dim3(MW_ENT_THREADS), (size_t)e->max_mesh_verts * 16, st, N, a.W, a.H,
-                               (const float *)a.envhdr, a.mesh, (const float4 *)e->d_mesh_vpos.get(), (const uint2 *)e->d_mesh_idx.get(), (const float *)e->d_mesh_stream.get(),
-                               (const float *)e->d_mesh_attr.get(), e->d_mesh_keys.get(), e->d_plane_cache.get(), e->plane_cap, e->d_slow_count.get() + (size_t)parity * 2 * N, e->d_slow_tris.get(),
-                               (const uint32_t *)e->d_ent_list.get(), e->ent_list_cap, e->d_ent_counter + parity * MW_CNT_WORDS, e->d_ent_counter + (parity ^ 1) * MW_CNT_WORDS, e->d_slow_envs.get() + (size_t)parity * N, e->args.n_xcc, e->d_ent_prof);
-            hipLaunchKernelGGL(mw_mesh_slow_kernel, dim3(std::min(N * 16, e->slow_waves)), dim3(64), 0, st, a.W, a.H, (const float *)a.envhdr, a.mesh_pos, a.mesh_nrm, a.mesh_rgb,
-                               a.mesh_uv, a.texels, e->texel_bytes, e->d_mesh_keys.get(), e->d_slow_count.get(), N, parity, (const uint32_t *)e->d_slow_tris.get(),
-                               e->d_slow_frags.get(), e->d_slow_head.get(), mesh_stamp, a.status,
-                               (const uint32_t *)(e->d_slow_envs.get() + (size_t)parity * N), (const int32_t *)(e->d_ent_counter + parity * MW_CNT_WORDS + MW_CNT_SLOW_ENVS));
-        }
-        const int wpe = e->waves_per_env;
-        const int tpw = (a.n_tiles + wpe - 1) / wpe;
-        const int groups = (N + 7) / 8;
-        // big scenes (a visiting order exists): records read in place, near to far; otherwise the env's records are staged
-        // in LDS when there are at most MW_LDS_RECS of them (a wave whose env holds more reads them in place).
-        const bool big = a.rec_order != nullptr;
-        const int lds_recs = a.max_vis < MW_LDS_RECS ? a.max_vis : MW_LDS_RECS;
-        const size_t lds = big ? 192 : (size_t)lds_recs * (MW_LDS_SHADE_Q + MW_LDS_CULL_Q) * 16 + 192;
-        const bool general = e->obs_layout != MW_OBS_HWC_U8 || e->dbg_flags != 0;
-        const bool ragged = !frame_on_grid(a.W, a.H);
-        auto launch_k2 = [&](int part, hipStream_t ks) {
-            // the second part (the tiles a mesh can touch: few, slow, clustered): persistent wavefronts over the geometry kernel's
-            // tile list (part 3)
-            const bool listed = part == 2 && a.tile_list != nullptr;
-            if (listed) part = 3;
-            const int wpe2 = part == 2 ? a.n_tiles : wpe;
-            const int tpw2 = part == 2 ? 1 : tpw;
-            const int grid = listed ? std::min(e->mesh_tile_waves, N * (int)a.n_tiles) : groups * 8 * wpe2;
-            launch(tile_kernel_of(big, d_depth != nullptr, general, ragged, mesh, part == 1), list, dim3(grid), dim3(64), lds, ks,
-                   a.N, a.W, a.H, a.max_vis, a.tiles_x, a.n_tiles, wpe2, tpw2, (const float *)a.rec_raster, (const float *)a.rec_shade,
-                   (const float *)a.rec_cull, (const int32_t *)a.nvis, (const float *)a.envhdr, a.tex, a.texels, d_obs, d_depth, raster_flags(e, part, mesh_stamp, reuse),
-                   e->texel_bytes, (const uint16_t *)a.rec_order, a.mesh_pos, a.mesh_nrm, a.mesh_rgb, a.mesh_uv, e->d_mesh_keys.get(),
-                   (const float *)e->d_plane_cache.get(), e->plane_cap, (const float4 *)e->d_slow_frags.get(), (const uint32_t *)e->d_slow_head.get(),
-                   (const uint32_t *)a.tile_list, a.ent_list_n, a.tile_list_cap, std::max(a.n_xcc, 1), (const uint8_t *)a.frame_clean);
-        };
-        e->last_raster_path = k2q ? (mesh ? MW_PATH_QUAD_MESH : MW_PATH_QUAD) : MW_PATH_TILE;
-        if (mesh) {
-            // the first part — every tile no mesh can touch: it needs nothing of the mesh kernels — on the quad stream beside them
-            // (forked above, behind the geometry kernel); the mesh tiles end the chain on the caller's stream
-            if (k2q) launch_k2q(1, e->quad_stream.get()); else launch_k2(1, e->quad_stream.get());
-            launch_k2(2, st);
-            HIP_TRY(e, hipEventRecord(e->ev_mesh_join.get(), e->quad_stream.get()));
-            HIP_TRY(e, hipStreamWaitEvent(st, e->ev_mesh_join.get(), 0));
-        } else if (k2q) {
-            launch_k2q(0, st);
-        } else {
-            launch_k2(0, st);
-        }
-        if (mesh) e->mesh_keys_dirty = false;
-    }
+    int rc = MW_OK;
+    if (async_refill && (rc = launch_side_refill(e, st))) return rc;
+    if (f.p.path == MW_PATH_GENERIC) rc = launch_generic(e, f.a, 0, N, e->cfg.msaa, dim3(32, N), d_obs, d_depth, e->obs_layout, f.list, st);
+    else if (f.p.mesh) rc = launch_mesh_chain(e, f, st);
+    else if (f.p.path == MW_PATH_QUAD) launch_quad(e, f, 0, st);
+    else launch_tiles(e, f, 0, st);
+    if (rc) return rc;
+    e->last_raster_path = f.p.path;
     if (timed) {
         (void)hipEventRecord(ev.c.get(), st);
         e->ev_used.push_back(std::move(ev));
@@ -1069,11 +965,7 @@ int init_engine(mw_engine *e, const mw_config *cfg)
         for (int i = 0; i < N; ++i) seed_env(e, seeds.data(), i, (uint64_t)i);
         HIP_TRY(e, hipMemcpy(a.rng, seeds.data(), 40 * (size_t)N, hipMemcpyHostToDevice));
     }
-    e->mesh_desc.assign(MW_MAX_MESH, MwMeshDesc{});
-    e->mesh_pos.assign(MW_MAX_MESH, {}); e->mesh_nrm.assign(MW_MAX_MESH, {}); e->mesh_rgb.assign(MW_MAX_MESH, {}); e->mesh_uv.assign(MW_MAX_MESH, {});
-    e->mesh_vtab.assign(MW_MAX_MESH, {}); e->mesh_itab.assign(MW_MAX_MESH, {});
-    e->tex_desc.assign(MW_MAX_TEX, MwTexDesc{});
-    e->tex_data.assign(MW_MAX_TEX, {});
+    e->meshes.assign(MW_MAX_MESH, {}); e->tex_desc.assign(MW_MAX_TEX, MwTexDesc{}); e->tex_data.assign(MW_MAX_TEX, {});
     if (const int rc = upload_textures(e)) return rc;
     e->waves_per_env = pick_waves_per_env(e);
     {
@@ -1147,29 +1039,22 @@ void mw_destroy(mw_engine *e)
     (void)hipSetDevice(e->cfg.device_id);       // (the members release their buffers, streams and events on the engine's device)
     (void)hipDeviceSynchronize();
 #ifdef MW_PERF_HOOKS
-    if (e->d_k2q_prof) {
-        std::vector<unsigned long long> h((size_t)e->cfg.num_envs * 80);
-        if (hipMemcpy(h.data(), e->d_k2q_prof, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)
-            if (FILE *f = fopen(getenv("MW_K2Q_PROF"), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-    }
-    if (e->d_ent_prof) {
-        std::vector<unsigned long long> h((size_t)16 * 2 * e->cfg.num_envs * MW_MAX_MESH_ENTS * 8);
-        if (hipMemcpy(h.data(), e->d_ent_prof, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)
-            if (FILE *f = fopen(getenv("MW_ENT_PROF"), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-    }
-    if (e->args.k1_prof) {
-        std::vector<unsigned long long> h((size_t)e->cfg.num_envs * MW_K1_PROF_SLOTS);
-        if (hipMemcpy(h.data(), e->args.k1_prof, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)
-            if (FILE *f = fopen(getenv("MW_K1_PROF"), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-    }
-    if (getenv("MW_SLOW_STATS") && e->d_slow_count) {      // perf experiments only: the last frame's slow fragments per env
+    auto dump = [](const unsigned long long *dev, size_t count, const char *var) {      // count stamps to the file the variable names
+        std::vector<unsigned long long> h(count);
+        if (dev && hipMemcpy(h.data(), dev, count * 8, hipMemcpyDeviceToHost) == hipSuccess)
+            if (FILE *f = fopen(getenv(var), "wb")) { fwrite(h.data(), 8, count, f); fclose(f); }
+    };
+    dump(e->d_k2q_prof, (size_t)e->cfg.num_envs * 80, "MW_K2Q_PROF");
+    dump(e->d_ent_prof, (size_t)16 * 2 * e->cfg.num_envs * MW_MAX_MESH_ENTS * 8, "MW_ENT_PROF");
+    dump(e->args.k1_prof, (size_t)e->cfg.num_envs * MW_K1_PROF_SLOTS, "MW_K1_PROF");
+    if (getenv("MW_SLOW_STATS") && e->mp.slow_count) {      // perf experiments only: the last frame's slow fragments per env
         std::vector<int32_t> h((size_t)e->cfg.num_envs * 4);
-        if (hipMemcpy(h.data(), e->d_slow_count.get(), h.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(h.data(), e->mp.slow_count.get(), h.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
             long long tot = 0, nz = 0, mx = 0;
             for (int i = 0; i < e->cfg.num_envs; ++i) { const int v = h[(size_t)e->cfg.num_envs + i] + h[(size_t)e->cfg.num_envs * 3 + i]; tot += v; nz += v > 0; mx = std::max<long long>(mx, v); }
             fprintf(stderr, "slow fragments: total %lld, envs with any %lld of %d, max %lld\n", tot, nz, e->cfg.num_envs, mx);
             int32_t c[2 * MW_CNT_WORDS];
-            if (e->d_ent_counter && hipMemcpy(c, e->d_ent_counter, sizeof c, hipMemcpyDeviceToHost) == hipSuccess)
+            if (e->mp.ent_counter && hipMemcpy(c, e->mp.ent_counter, sizeof c, hipMemcpyDeviceToHost) == hipSuccess)
                 for (int p = 0; p < 2; ++p) {
                     int nl = 0, ns = 0, nt = 0;
                     for (int x = 0; x < 8; ++x) { nl += c[p * MW_CNT_WORDS + MW_CNT_LONG + x]; ns += c[p * MW_CNT_WORDS + MW_CNT_SHORT + x]; nt += c[p * MW_CNT_WORDS + MW_CNT_TILES + x]; }
@@ -1189,7 +1074,7 @@ int mw_upload_texture(mw_engine *e, int32_t tex_id, const uint8_t *rgb, int32_t 
     drop_held_frame(e);
     if (tex_id < 0 || tex_id >= MW_MAX_TEX) return fail(e, MW_E_CAPACITY, "texture id %d out of range (max %d)", tex_id, MW_MAX_TEX);
     if (w <= 0 || h <= 0 || w > 16384 || h > 16384) return fail(e, MW_E_INVALID, "bad texture size %dx%d", w, h);
-    build_pyramid(rgb, w, h, e->tex_data[tex_id], e->tex_desc[tex_id]);
+    mwasset::build_pyramid(rgb, w, h, e->tex_data[tex_id], e->tex_desc[tex_id]);
     return upload_textures(e);
 }
 
@@ -1202,142 +1087,42 @@ int mw_upload_mesh(mw_engine *e, int32_t mesh_id, const float *pos, const float 
     if (tex_id >= MW_MAX_TEX || (tex_id >= 0 && !uv)) return fail(e, MW_E_INVALID, "textured mesh needs texcoords and a valid texture id");
     if (mesh_id < 0 || mesh_id >= MW_MAX_MESH) return fail(e, MW_E_CAPACITY, "mesh id %d out of range (max %d)", mesh_id, MW_MAX_MESH);
     if (ntris <= 0 || ntris > 60000) return fail(e, MW_E_CAPACITY, "mesh with %d triangles (1..60000 supported: 16-bit draw ids)", ntris);
-    // storage order: triangles sorted by the direction of their face normal (octahedral map, 6 + 6 bit Morton code,
-    // stable), mw_device.h: MW_MESH_POS_STRIDE
-    std::vector<uint32_t> order((size_t)ntris), key((size_t)ntris);
-    for (int t = 0; t < ntris; ++t) {
-        const float *p = pos + (size_t)t * 9;
-        const double ax = p[3] - p[0], ay = p[4] - p[1], az = p[5] - p[2], bx = p[6] - p[0], by = p[7] - p[1], bz = p[8] - p[2];
-        double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
-        double l1 = std::fabs(nx) + std::fabs(ny) + std::fabs(nz);
-        if (!(l1 > 0.0)) { nx = nrm[(size_t)t * 9]; ny = nrm[(size_t)t * 9 + 1]; nz = nrm[(size_t)t * 9 + 2]; l1 = std::fabs(nx) + std::fabs(ny) + std::fabs(nz); }
-        if (!(l1 > 0.0)) { nx = 0; ny = 1; nz = 0; l1 = 1; }
-        double u = nx / l1, v = nz / l1;
-        if (ny < 0.0) {     // lower hemisphere folded outwards
-            const double uu = (1.0 - std::fabs(v)) * (u >= 0 ? 1.0 : -1.0), vv = (1.0 - std::fabs(u)) * (v >= 0 ? 1.0 : -1.0);
-            u = uu; v = vv;
-        }
-        const uint32_t qu = (uint32_t)std::min(63.0, std::max(0.0, (u * 0.5 + 0.5) * 64.0)), qv = (uint32_t)std::min(63.0, std::max(0.0, (v * 0.5 + 0.5) * 64.0));
-        uint32_t m = 0;
-        for (int b = 0; b < 6; ++b) m |= ((qu >> b) & 1u) << (2 * b) | ((qv >> b) & 1u) << (2 * b + 1);
-        key[t] = m; order[t] = (uint32_t)t;
-    }
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
-    auto &P = e->mesh_pos[mesh_id]; auto &Nn = e->mesh_nrm[mesh_id]; auto &Cc = e->mesh_rgb[mesh_id]; auto &U = e->mesh_uv[mesh_id];
-    P.assign((size_t)ntris * MW_MESH_POS_STRIDE, 0.0f);
-    Nn.assign(nrm, nrm + (size_t)ntris * 9); Cc.assign(rgb, rgb + (size_t)ntris * 9);
-    if (uv) U.assign(uv, uv + (size_t)ntris * 6); else U.assign((size_t)ntris * 6, 0.0f);
-    for (int i = 0; i < ntris; ++i) {
-        memcpy(&P[(size_t)i * MW_MESH_POS_STRIDE], pos + (size_t)i * 9, 36);
-        memcpy(&P[(size_t)i * MW_MESH_POS_STRIDE + 9], &order[i], 4);      // the i-th triangle of the rasterisation order
-    }
-    {
-        // the table of distinct positions (bit patterns: -0 and 0 stay apart) and the triangles' indices into it, in
-        // rasterisation order; a mesh with more than MW_MESH_VCAP positions keeps none (the entity kernel then takes its
-        // triangles through the vertex stage one by one)
-        std::map<std::array<uint32_t, 3>, uint32_t> seen;
-        auto &VT = e->mesh_vtab[mesh_id]; auto &IT = e->mesh_itab[mesh_id];
-        VT.clear(); IT.assign((size_t)ntris * 2, 0u);
-        bool fits = true;
-        for (int k = 0; k < ntris && fits; ++k) {
-            const uint32_t tri = order[k];
-            uint32_t ix[3];
-            for (int c = 0; c < 3; ++c) {
-                std::array<uint32_t, 3> key;
-                memcpy(key.data(), pos + ((size_t)tri * 3 + c) * 3, 12);
-                auto it = seen.find(key);
-                if (it == seen.end()) {
-                    if (seen.size() >= MW_MESH_VCAP) { fits = false; break; }
-                    it = seen.emplace(key, (uint32_t)seen.size()).first;
-                    const float *pp = pos + ((size_t)tri * 3 + c) * 3;
-                    VT.insert(VT.end(), {pp[0], pp[1], pp[2], 0.0f});
-                }
-                ix[c] = it->second;
-            }
-            IT[(size_t)k * 2] = ix[0] | (ix[1] << 16);
-            IT[(size_t)k * 2 + 1] = ix[2] | (tri << 16);
-        }
-        if (!fits) VT.clear();
-        e->mesh_desc[mesh_id].nverts = (uint32_t)(VT.size() / 4);
-    }
-    memcpy(e->mesh_desc[mesh_id].last_n, nrm + ((size_t)(ntris - 1) * 3 + 2) * 3, 12);
-    e->mesh_desc[mesh_id].ntris = (uint32_t)ntris;
-    e->mesh_desc[mesh_id].tex = tex_id;
-    {
-        float r2 = 0.0f;
-        for (size_t i = 0; i < (size_t)ntris * 3; ++i)
-            r2 = std::max(r2, pos[i * 3] * pos[i * 3] + pos[i * 3 + 1] * pos[i * 3 + 1] + pos[i * 3 + 2] * pos[i * 3 + 2]);
-        const float r = std::sqrt(r2) * 1.0001f;
-        memcpy(&e->mesh_desc[mesh_id].bound_bits, &r, 4);
-        // bounding box, its centre, the sphere about the centre (doubles: the radius rounds up)
-        MwMeshDesc &md = e->mesh_desc[mesh_id];
-        for (int c = 0; c < 3; ++c) { md.bmin[c] = pos[c]; md.bmax[c] = pos[c]; }
-        for (size_t i = 0; i < (size_t)ntris * 3; ++i)
-            for (int c = 0; c < 3; ++c) { md.bmin[c] = std::min(md.bmin[c], pos[i * 3 + c]); md.bmax[c] = std::max(md.bmax[c], pos[i * 3 + c]); }
-        for (int c = 0; c < 3; ++c) md.center[c] = 0.5f * (md.bmin[c] + md.bmax[c]);
-        double rc2 = 0.0;
-        for (size_t i = 0; i < (size_t)ntris * 3; ++i) {
-            double d2 = 0.0;
-            for (int c = 0; c < 3; ++c) { const double d = (double)pos[i * 3 + c] - (double)md.center[c]; d2 += d * d; }
-            rc2 = std::max(rc2, d2);
-        }
-        md.radius = (float)(std::sqrt(rc2) * 1.0001 + 1e-6);
-    }
+    e->meshes[mesh_id] = mwasset::prepare_mesh(pos, nrm, uv, rgb, ntris, tex_id);
     // repack all pools (uploads are rare) into new ones: a failure leaves the installed pools, descriptors and MwArgs as they are
-    size_t total = 0;
-    size_t total_v = 0;
-    int max_verts = 0;
+    std::vector<MwMeshDesc> descs(MW_MAX_MESH);
+    size_t total = 0, total_v = 0, max_verts = 0;
     for (int i = 0; i < MW_MAX_MESH; ++i) {
-        e->mesh_desc[i].first = (uint32_t)total; total += e->mesh_desc[i].ntris;
-        e->mesh_desc[i].vfirst = (uint32_t)total_v; total_v += e->mesh_desc[i].nverts;
-        max_verts = std::max(max_verts, (int)e->mesh_desc[i].nverts);
+        descs[i] = e->meshes[i].desc;
+        descs[i].first = (uint32_t)total; total += descs[i].ntris;
+        descs[i].vfirst = (uint32_t)total_v; total_v += descs[i].nverts;
+        max_verts = std::max<size_t>(max_verts, descs[i].nverts);
     }
-    DevBuf<float> d_pos, d_nrm, d_rgb, d_uv, d_stream, d_attr; DevBuf<float4> d_vpos; DevBuf<uint2> d_idx;
+    mw_engine::MeshPools p;
     int rc;
-    if ((rc = dev_alloc(e, d_vpos, total_v, false)) || (rc = dev_alloc(e, d_idx, total, false)) || (rc = dev_alloc(e, d_pos, total * MW_MESH_POS_STRIDE, false)) ||
-        (rc = dev_alloc(e, d_nrm, total * 9, false)) || (rc = dev_alloc(e, d_rgb, total * 9, false)) || (rc = dev_alloc(e, d_uv, total * 6, false)) ||
-        (rc = dev_alloc(e, d_stream, total * 12, false)) || (rc = dev_alloc(e, d_attr, total * 24, false)))
+    if ((rc = dev_alloc(e, p.vpos, total_v, false)) || (rc = dev_alloc(e, p.idx, total, false)) || (rc = dev_alloc(e, p.pos, total * MW_MESH_POS_STRIDE, false)) ||
+        (rc = dev_alloc(e, p.nrm, total * 9, false)) || (rc = dev_alloc(e, p.rgb, total * 9, false)) || (rc = dev_alloc(e, p.uv, total * 6, false)) ||
+        (rc = dev_alloc(e, p.stream, total * 12, false)) || (rc = dev_alloc(e, p.attr, total * 24, false)))
         return rc;
     for (int i = 0; i < MW_MAX_MESH; ++i) {
-        const size_t n = e->mesh_desc[i].ntris, off = (size_t)e->mesh_desc[i].first * 9;
+        const mwasset::HostMesh &m = e->meshes[i];
+        const size_t n = descs[i].ntris, first = descs[i].first;
         if (!n) continue;
-        HIP_TRY(e, hipMemcpy(d_pos.get() + (size_t)e->mesh_desc[i].first * MW_MESH_POS_STRIDE, e->mesh_pos[i].data(), n * 4 * MW_MESH_POS_STRIDE, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(d_nrm.get() + off, e->mesh_nrm[i].data(), n * 36, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(d_rgb.get() + off, e->mesh_rgb[i].data(), n * 36, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(d_uv.get() + (size_t)e->mesh_desc[i].first * 6, e->mesh_uv[i].data(), n * 24, hipMemcpyHostToDevice));
-        if (e->mesh_desc[i].nverts)
-            HIP_TRY(e, hipMemcpy(d_vpos.get() + e->mesh_desc[i].vfirst, e->mesh_vtab[i].data(), (size_t)e->mesh_desc[i].nverts * 16, hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(d_idx.get() + e->mesh_desc[i].first, e->mesh_itab[i].data(), n * 8, hipMemcpyHostToDevice));
-        {
-            // the scatter kernel's stream: the triangles in rasterisation order, 48 bytes each (9 coordinates, the triangle's index)
-            std::vector<float> st(n * 12, 0.0f);
-            const auto &P = e->mesh_pos[i];
-            for (size_t k = 0; k < n; ++k) {
-                uint32_t tri;
-                memcpy(&tri, &P[k * MW_MESH_POS_STRIDE + 9], 4);
-                memcpy(&st[k * 12], &P[(size_t)tri * MW_MESH_POS_STRIDE], 36);
-                memcpy(&st[k * 12 + 9], &tri, 4);
-            }
-            HIP_TRY(e, hipMemcpy(d_stream.get() + (size_t)e->mesh_desc[i].first * 12, st.data(), n * 48, hipMemcpyHostToDevice));
-            // ... and their vertex attributes in the same order, 96 bytes each (normals, colours, texture coordinates)
-            std::vector<float> at(n * 24, 0.0f);
-            for (size_t k = 0; k < n; ++k) {
-                uint32_t tri;
-                memcpy(&tri, &P[k * MW_MESH_POS_STRIDE + 9], 4);
-                memcpy(&at[k * 24], &e->mesh_nrm[i][(size_t)tri * 9], 36);
-                memcpy(&at[k * 24 + 9], &e->mesh_rgb[i][(size_t)tri * 9], 36);
-                memcpy(&at[k * 24 + 18], &e->mesh_uv[i][(size_t)tri * 6], 24);
-            }
-            HIP_TRY(e, hipMemcpy(d_attr.get() + (size_t)e->mesh_desc[i].first * 24, at.data(), n * 96, hipMemcpyHostToDevice));
-        }
+        HIP_TRY(e, hipMemcpy(p.pos.get() + first * MW_MESH_POS_STRIDE, m.pos.data(), n * 4 * MW_MESH_POS_STRIDE, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(p.nrm.get() + first * 9, m.nrm.data(), n * 36, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(p.rgb.get() + first * 9, m.rgb.data(), n * 36, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(p.uv.get() + first * 6, m.uv.data(), n * 24, hipMemcpyHostToDevice));
+        if (descs[i].nverts)
+            HIP_TRY(e, hipMemcpy(p.vpos.get() + descs[i].vfirst, m.vtab.data(), (size_t)descs[i].nverts * 16, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(p.idx.get() + first, m.itab.data(), n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(p.stream.get() + first * 12, m.stream.data(), n * 48, hipMemcpyHostToDevice));
+        HIP_TRY(e, hipMemcpy(p.attr.get() + first * 24, m.attr.data(), n * 96, hipMemcpyHostToDevice));
     }
     // install: the frames that may still read the old pools and descriptors finish first
     HIP_TRY(e, hipDeviceSynchronize());
-    HIP_TRY(e, hipMemcpy(e->d_meshdesc, e->mesh_desc.data(), sizeof(MwMeshDesc) * MW_MAX_MESH, hipMemcpyHostToDevice));
-    e->args.mesh_pos = d_pos.get(); e->args.mesh_nrm = d_nrm.get(); e->args.mesh_rgb = d_rgb.get(); e->args.mesh_uv = d_uv.get();
-    e->d_mesh_pos = std::move(d_pos); e->d_mesh_nrm = std::move(d_nrm); e->d_mesh_rgb = std::move(d_rgb); e->d_mesh_uv = std::move(d_uv);
-    e->d_mesh_stream = std::move(d_stream); e->d_mesh_attr = std::move(d_attr); e->d_mesh_vpos = std::move(d_vpos); e->d_mesh_idx = std::move(d_idx);
-    e->max_mesh_verts = max_verts;
+    HIP_TRY(e, hipMemcpy(e->d_meshdesc, descs.data(), sizeof(MwMeshDesc) * MW_MAX_MESH, hipMemcpyHostToDevice));
+    e->args.mesh_pos = p.pos.get(); e->args.mesh_nrm = p.nrm.get(); e->args.mesh_rgb = p.rgb.get(); e->args.mesh_uv = p.uv.get();
+    e->pools = std::move(p);
+    e->max_mesh_verts = (int)max_verts;
     if (e->d_gen_live && sync_gen_args(e) != MW_OK) return MW_E_HIP;
     e->have_meshes = true;
     e->max_mesh_tris = std::max(e->max_mesh_tris, (int)ntris);
@@ -1582,15 +1367,8 @@ int mw_render_view(mw_engine *e, int32_t env, int32_t view_flags, int32_t width,
     b.tiles_x = (width + MW_TILE_W - 1) / MW_TILE_W; b.tiles_y = (height + MW_TILE_H - 1) / MW_TILE_H; b.n_tiles = b.tiles_x * b.tiles_y;
     b.env_base = env;
     hipLaunchKernelGGL(geom_kernel_of(64, msaa).plain, dim3(1), dim3(64), 0, st, b, view_flags, msaa, 64, 1);
-    uint32_t *keys = nullptr;
-    if (e->have_meshes) {
-        const size_t need = (size_t)width * height * msaa * 4;
-        if (const int rc = grow(e, e->d_view_keys, e->view_keys_bytes, need, 1)) return rc;
-        keys = e->d_view_keys.get();
-        HIP_TRY(e, hipMemsetAsync(keys, 0xFF, need, st));
-        hipLaunchKernelGGL(mw_view_mesh_kernel, dim3(128), dim3(256), 0, st, width, height, msaa, env, (const float *)b.envhdr, b.mesh_pos, keys);
-    }
-    launch_view_raster(e, b, env, 1, msaa, keys, d_out, d_depth, MW_OBS_HWC_U8, nullptr, st);
+    if (const int rc = e->have_meshes ? grow(e, e->mp.view_keys, e->mp.view_keys_bytes, (size_t)width * height * msaa * 4, 1) : MW_OK) return rc;
+    if (const int rc = launch_generic(e, b, env, 1, msaa, dim3(128), d_out, d_depth, MW_OBS_HWC_U8, nullptr, st)) return rc;
     HIP_TRY(e, hipGetLastError());
     return MW_OK;
 }
@@ -1599,7 +1377,7 @@ int mw_pcg64_draws(uint64_t seed, int32_t n, const int32_t *bounds, double *out)
 {
     if (!out || n < 0) return MW_E_INVALID;
     uint64_t s[4];
-    pcg64_seed(seed, s);
+    mwasset::pcg64_seed(seed, s, mw::pcg64_step);
     mw::Rng r{s[0], s[1], s[2], s[3], 1, 0u, 0u};
     for (int i = 0; i < n; ++i)
         out[i] = (bounds && bounds[i] > 0) ? (double)mw::rng_below(r, (uint32_t)bounds[i]) : mw::rng_double(r);
@@ -1659,19 +1437,19 @@ int mw_debug_set_mesh_frame_seq(mw_engine *e, uint32_t seq)
 {
     if (!e) return MW_E_INVALID;
     // (the work lists and the slow-path counters alternate with the sequence number's parity: keep it)
-    if ((seq & 1u) != (e->mesh_frame_seq & 1u)) return fail(e, MW_E_INVALID, "mw_debug_set_mesh_frame_seq: the parity of the sequence number must stay");
+    if ((seq & 1u) != (e->mp.frame_seq & 1u)) return fail(e, MW_E_INVALID, "mw_debug_set_mesh_frame_seq: the parity of the sequence number must stay");
     drop_held_frame(e);
-    e->mesh_frame_seq = seq;
+    e->mp.frame_seq = seq;
     return MW_OK;
 }
 
 int mw_debug_get_slow_heads(mw_engine *e, uint32_t *host_out, void *stream)
 {
     if (!e || !host_out) return fail(e, MW_E_INVALID, "null argument");
-    if (!e->d_slow_head) return fail(e, MW_E_INVALID, "mw_debug_get_slow_heads: this engine has no mesh path buffers");
+    if (!e->mp.slow_head) return fail(e, MW_E_INVALID, "mw_debug_get_slow_heads: this engine has no mesh path buffers");
     ON_DEVICE(e);
     HIP_TRY(e, hipStreamSynchronize((hipStream_t)stream));
-    HIP_TRY(e, hipMemcpy(host_out, e->d_slow_head.get(), sizeof(uint32_t) * (size_t)e->cfg.num_envs * e->args.W * e->args.H, hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(host_out, e->mp.slow_head.get(), sizeof(uint32_t) * (size_t)e->cfg.num_envs * e->args.W * e->args.H, hipMemcpyDeviceToHost));
     return MW_OK;
 }
 

@@ -74,7 +74,7 @@ __device__ inline uint32_t lerp8_pk(uint32_t a, uint32_t b, uint32_t w, uint32_t
     return __builtin_bit_cast(uint32_t, r);
 }
 __device__ inline uint32_t weight_pk(int w) { return (uint32_t)w | ((uint32_t)w << 16); }
-// ... given A = a * 256 + 128 and D = b - a (the footprint records of mw_engine.hip::build_pyramid): (A + w D) >> 8
+// ... given A = a * 256 + 128 and D = b - a (the footprint records of mw_assets.h::build_pyramid): (A + w D) >> 8
 __device__ inline uint32_t lerp8_ad(uint32_t A, uint32_t D, uint32_t w)
 {
     const u16x2 av = __builtin_bit_cast(u16x2, A), dv = __builtin_bit_cast(u16x2, D), wv = __builtin_bit_cast(u16x2, w);
@@ -93,7 +93,7 @@ __device__ inline void bilerp_rec(const TexEnv &te, uint32_t rec, int wx8, int w
 }
 
 // GL_LINEAR lookup on mip level l of the texture whose descriptor starts at dword `desc`: one 32-byte footprint record
-// (the texel and its right / upper / diagonal neighbours, GL_REPEAT applied: mw_engine.hip::build_pyramid), 8-bit weights
+// (the texel and its right / upper / diagonal neighbours, GL_REPEAT applied: mw_assets.h::build_pyramid), 8-bit weights
 __device__ inline void fetch_level(const TexEnv &te, uint32_t desc, int l, float s, float t, int out[3])
 {
     const uint32_t rec = (desc + 4u + (uint32_t)l * 8u) << 2;

@@ -1,8 +1,10 @@
 // TEST INFRASTRUCTURE ONLY — the engine's own per-vertex / per-fragment arithmetic (miniworld_amd/csrc/mw_glmath.h,
 // mw_frag.h: the functions the HIP kernels call) compiled for the HOST and wrapped in a plain frame loop, so that
 // `-m "not gpu"` tests can compare it with the oracle and with the reference's GL frames without a GPU
-// (tests/test_engine_math_cpu.py).  Never part of the product: the engine has no CPU path.
+// (tests/test_engine_math_cpu.py); and thin entries to the engine's asset preparation (mw_assets.h: host code in the product
+// too).  Never part of the product: the engine has no CPU path.
 // Input: the oracle's scene struct (oracle/mwo.h), so that tests feed both from the same arrays.
+#include "../../miniworld_amd/csrc/mw_assets.h"
 #include "../../miniworld_amd/csrc/mw_frag.h"
 #include "../../miniworld_amd/csrc/mw_cover.h"
 #include "../../miniworld_amd/csrc/mw_math.h"
@@ -613,4 +615,27 @@ extern "C" long mwhost_cover_mismatches(const float *win, long n, int W, int H, 
     }
     if (covered) *covered = cov;
     return bad;
+}
+
+// mw_assets.h: a texture's pyramid as the engine uploads it.  Returns the number of dwords (8 per texel of every level); fills
+// out (when not null) and *desc.
+extern "C" long mwhost_build_pyramid(const uint8_t *rgb, int w, int h, uint32_t *out, MwTexDesc *desc)
+{
+    std::vector<uint32_t> recs;
+    mwasset::build_pyramid(rgb, w, h, recs, *desc);
+    if (out) memcpy(out, recs.data(), recs.size() * 4);
+    return (long)recs.size();
+}
+
+// mw_assets.h: a mesh as the engine keeps it.  pos [ntris][10], nrm / rgb [ntris][9], uv [ntris][6], vtab [MW_MESH_VCAP][4],
+// itab [ntris][2], stream [ntris][12], attr [ntris][24]; returns the number of table positions (vtab rows filled).
+extern "C" int mwhost_prepare_mesh(const float *in_pos, const float *in_nrm, const float *in_uv, const float *in_rgb, int ntris, int tex,
+                                   float *pos, float *nrm, float *rgb, float *uv, float *vtab, uint32_t *itab, float *stream, float *attr,
+                                   MwMeshDesc *desc)
+{
+    const mwasset::HostMesh m = mwasset::prepare_mesh(in_pos, in_nrm, in_uv, in_rgb, ntris, tex);
+    auto put = [](auto *dst, const auto &v) { if (!v.empty()) memcpy(dst, v.data(), v.size() * sizeof v[0]); };
+    put(pos, m.pos); put(nrm, m.nrm); put(rgb, m.rgb); put(uv, m.uv); put(vtab, m.vtab); put(itab, m.itab); put(stream, m.stream); put(attr, m.attr);
+    *desc = m.desc;
+    return (int)(m.vtab.size() / 4);
 }

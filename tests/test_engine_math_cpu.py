@@ -23,7 +23,7 @@ def build_host():
     """tests/hostcheck/libmwhost.so, (re)built when a source is newer; also used by the -m gpu selftests."""
     deps = [SRC, os.path.join(ROOT, "oracle", "mwo_math.c")] + [
         os.path.join(ROOT, "miniworld_amd", "csrc", h)
-        for h in ("mw_glmath.h", "mw_frag.h", "mw_cover.h", "mw_math.h", "mw_selftest.h", "mw_hd.h")]
+        for h in ("mw_glmath.h", "mw_frag.h", "mw_cover.h", "mw_math.h", "mw_selftest.h", "mw_hd.h", "mw_assets.h", "mw_asset_types.h")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         fma = ["-mfma"] if " fma " in open("/proc/cpuinfo").read() else []
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", *fma, "-pthread", "-shared", SRC,
@@ -40,6 +40,9 @@ def build_host():
     lib.mwhost_sincosf_sums.argtypes = [C.c_int, C.c_void_p]
     lib.mwhost_sincos_det_sums.argtypes = [C.c_uint64, C.c_int, C.c_void_p]
     lib.mwhost_sincos_det_check.argtypes = [C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mwhost_build_pyramid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mwhost_build_pyramid.restype = C.c_long
+    lib.mwhost_prepare_mesh.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 9
     return lib
 
 
@@ -325,3 +328,146 @@ def test_a_box_outside_the_frustum_holds_only_vertices_outside_it(host):
         culled += planes.value != 0
     assert 500 < culled < 2900      # both outcomes occur
 
+
+
+# ------------------------------------------------------------------ asset preparation (mw_assets.h)
+
+GL_META = np.load(os.path.join(HERE, "golden", "gl_meta.npz"))
+MIP_NAMES = [str(n) for n in GL_META["mip_names"]]
+
+
+@pytest.mark.parametrize("name", MIP_NAMES)
+def test_engine_mip_pyramid_equals_glGenerateMipmap_in_footprint_records(host, name):
+    """mwasset::build_pyramid — what mw_upload_texture uploads — for a shipped texture: every level's texels, decoded from the
+    footprint records (channel = A >> 8 of a record's first row), are the oracle's level byte for byte and carry the checksum
+    of the driver's own level (gl_meta.npz); every record holds what its layout promises — A = a * 256 + 128 and
+    D = (right neighbour - a) mod 2^16 for the texel's row and for the row above, GL_REPEAT applied, packed
+    (A_r | A_b << 16, D_r | D_b << 16, A_g, D_g); the descriptor's level table agrees with the level sizes."""
+    import zlib
+    rgb = np.ascontiguousarray(pyoracle.texture_rgb_bottom_up(name), np.uint8)
+    h, w, _ = rgb.shape
+    desc = np.zeros(4 + 16 * 8, np.uint32)
+    n = host.mwhost_build_pyramid(rgb.ctypes.data, w, h, None, desc.ctypes.data)
+    recs = np.zeros(n, np.uint32)
+    assert host.mwhost_build_pyramid(rgb.ctypes.data, w, h, recs.ctypes.data, desc.ctypes.data) == n
+    want_levels = pyoracle.mip_levels(rgb)
+    crcs = [int(x) for x in GL_META["mip_crc"][MIP_NAMES.index(name)]]
+    assert [int(x) for x in desc[:4]] == [w, h, len(want_levels), 0]
+    assert all(c == 0 for c in crcs[len(want_levels):])
+
+    def row(a, b):
+        A, D = a * np.uint32(256) + np.uint32(128), (b - a) & np.uint32(0xFFFF)
+        return np.stack([A[..., 0] | A[..., 2] << np.uint32(16), D[..., 0] | D[..., 2] << np.uint32(16), A[..., 1], D[..., 1]], -1)
+
+    off, lw, lh = 0, w, h
+    for l, want in enumerate(want_levels):
+        lv = desc[4 + 8 * l:12 + 8 * l]
+        assert [int(x) for x in lv[[0, 1, 2, 3, 6, 7]]] == [off, lw, lw - 1, lh - 1, lh, 0], f"{name} level {l}"
+        assert [float(x) for x in lv[4:6].view(np.float32)] == [float(lw), float(lh)], f"{name} level {l}"
+        R = recs[off * 8:(off + lw * lh) * 8].reshape(lh, lw, 2, 4)
+        A = np.stack([R[:, :, 0, 0] & np.uint32(0xFFFF), R[:, :, 0, 2], R[:, :, 0, 0] >> np.uint32(16)], -1)
+        assert np.all(A & np.uint32(0xFF) == 128) and np.all(A < 65536), f"{name} level {l}"
+        tex = (A >> np.uint32(8)).astype(np.uint8)
+        assert np.array_equal(tex, want), f"{name} level {l}: differs from the oracle's level"
+        assert zlib.crc32(np.ascontiguousarray(tex).tobytes()) == crcs[l], f"{name} level {l}: differs from the driver's level"
+        t = tex.astype(np.uint32)
+        up = np.roll(t, -1, axis=0)
+        assert np.array_equal(R[:, :, 0], row(t, np.roll(t, -1, axis=1))), f"{name} level {l}: the texel's row"
+        assert np.array_equal(R[:, :, 1], row(up, np.roll(up, -1, axis=1))), f"{name} level {l}: the row above"
+        off, lw, lh = off + lw * lh, max(1, lw // 2), max(1, lh // 2)
+    assert off * 8 == n
+
+
+MW_MESH_VCAP = 3568     # mw_asset_types.h
+
+
+def shipped_meshes():
+    """every mesh name ObjMesh can load from the asset pack: <base>_<colour> for the coloured ones, the rest by their own name"""
+    from miniworld_amd import assets
+    files = list(assets._pack_file().keys())
+    coloured = [k[3:] for k in files if k.startswith("kd:")]
+    bases = {n.split("_")[0] for n in coloured}
+    return sorted(coloured + [k[4:] for k in files if k.startswith("obj:") and k[4:] not in bases])
+
+
+def synthetic_mesh(kind):
+    rng = np.random.default_rng(11)
+    if kind == "over_the_cap":      # 1400 triangles of their own vertices: 4200 distinct positions
+        verts = rng.uniform(-1, 1, (1400, 3, 3)).astype(np.float32)
+        verts[::7, 0, 0] = 0.0
+        verts[3::7, 1, 2] = -0.0
+    else:                           # "signed_zeros": shared vertices that differ in the sign of a zero only, degenerate triangles
+        grid = rng.uniform(-1, 1, (40, 3)).astype(np.float32)
+        grid[:20, 1] = 0.0
+        grid[20:, :] = grid[:20, :]
+        grid[20:, 1] = -0.0
+        verts = grid[rng.integers(0, 40, (300, 3))]
+    n = len(verts)
+    norms = rng.uniform(-1, 1, (n, 3, 3)).astype(np.float32)
+    return verts, norms, rng.uniform(0, 1, (n, 3, 2)).astype(np.float32), rng.uniform(0, 1, (n, 3, 3)).astype(np.float32)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("name", shipped_meshes() + ["synthetic:over_the_cap", "synthetic:signed_zeros"])
+def test_mesh_preparation_keeps_every_triangle_and_bounds_the_mesh(host, name):
+    """mwasset::prepare_mesh — the host half of mw_upload_mesh — for every shipped mesh, a mesh with more distinct positions
+    than MW_MESH_VCAP (no vertex table) and one whose vertices differ in the sign of a zero: the rasterisation order is a
+    permutation; the entity kernel's stream and attribute rows are the input rows of that order's triangles bit for bit; the
+    index table decodes through the vertex table to the same positions bit for bit; the table exists exactly when the
+    positions fit; box, spheres and the last normal hold what the descriptor says."""
+    if name.startswith("synthetic:"):
+        verts, norms, texcs, colors = synthetic_mesh(name[10:])
+        tex = 3
+    else:
+        from miniworld_amd.objmesh import ObjMesh
+        m = ObjMesh.get(name)
+        verts, norms, texcs, colors = m.verts, m.norms, m.texcs, m.colors
+        tex = -1 if m.tex_variant is None else 5
+    verts, norms, colors = (np.ascontiguousarray(x, np.float32) for x in (verts, norms, colors))
+    texcs = np.ascontiguousarray(texcs, np.float32) if tex >= 0 else None
+    n = len(verts)
+    pos, nrm, rgb, uv = np.zeros((n, 10), np.float32), np.zeros((n, 9), np.float32), np.zeros((n, 9), np.float32), np.zeros((n, 6), np.float32)
+    vtab, itab = np.full((MW_MESH_VCAP, 4), np.nan, np.float32), np.zeros((n, 2), np.uint32)
+    stream, attr = np.zeros((n, 12), np.float32), np.zeros((n, 24), np.float32)
+    desc = np.zeros(20, np.uint32)
+    nverts = host.mwhost_prepare_mesh(verts.ctypes.data, norms.ctypes.data, texcs.ctypes.data if texcs is not None else None,
+                                      colors.ctypes.data, n, tex, *(x.ctypes.data for x in (pos, nrm, rgb, uv, vtab, itab, stream, attr, desc)))
+    want_uv = texcs.reshape(n, 6) if texcs is not None else np.zeros((n, 6), np.float32)
+    # the pools' rows, drawing order
+    order = bits(pos[:, 9]).astype(np.int64)
+    assert np.array_equal(np.sort(order), np.arange(n))
+    assert np.array_equal(bits(pos[:, :9]), bits(verts.reshape(n, 9)))
+    assert np.array_equal(bits(nrm), bits(norms.reshape(n, 9))) and np.array_equal(bits(rgb), bits(colors.reshape(n, 9)))
+    assert np.array_equal(bits(uv), bits(want_uv))
+    # the entity kernel's rows, rasterisation order
+    assert np.array_equal(bits(stream[:, :9]), bits(verts.reshape(n, 9)[order]))
+    assert np.array_equal(bits(stream[:, 9]), order) and not bits(stream[:, 10:]).any()
+    assert np.array_equal(bits(attr), bits(np.concatenate([norms.reshape(n, 9), colors.reshape(n, 9), want_uv], 1)[order]))
+    # the tables
+    distinct = len(np.unique(bits(verts.reshape(-1, 3)), axis=0))
+    d_u, d_f = desc, desc.view(np.float32)
+    assert (nverts == 0) == (distinct > MW_MESH_VCAP) and int(d_u[9]) == nverts
+    if name == "synthetic:over_the_cap":
+        assert nverts == 0
+    if name == "synthetic:signed_zeros":
+        assert distinct == 40 and len(np.unique(verts.reshape(-1, 3), axis=0)) == 20
+    if nverts:
+        assert nverts == distinct and len(np.unique(bits(vtab[:nverts, :3]), axis=0)) == distinct
+        assert not bits(vtab[:nverts, 3]).any() and np.isnan(vtab[nverts:]).all()
+        idx = np.stack([itab[:, 0] & 0xFFFF, itab[:, 0] >> 16, itab[:, 1] & 0xFFFF], 1).astype(np.int64)
+        assert np.array_equal(itab[:, 1] >> 16, order) and idx.max() < nverts
+        assert np.array_equal(bits(vtab[idx, :3]), bits(verts[order]))
+    # the descriptor: ntris, tex, first, bound_bits, last_n[3], pad, vfirst, nverts, bmin[3], bmax[3], center[3], radius
+    assert [int(d_u[0]), int(d_u[1].view(np.int32)), int(d_u[2]), int(d_u[7]), int(d_u[8])] == [n, tex, 0, 0, 0]
+    assert np.array_equal(d_u[4:7], bits(norms[n - 1, 2]))
+    v = verts.reshape(-1, 3)
+    bmin, bmax, center, radius, bound = d_f[10:13], d_f[13:16], d_f[16:19], float(d_f[19]), float(d_f[3])
+    assert np.all(v >= bmin) and np.all(v <= bmax)
+    assert np.array_equal(bmin, v.min(0)) and np.array_equal(bmax, v.max(0))        # (min and max are exact)
+    assert np.array_equal(center, np.float32(0.5) * (bmin + bmax))
+    v64 = v.astype(np.float64)
+    assert np.sqrt(((v64 - center.astype(np.float64)) ** 2).sum(1)).max() <= radius
+    assert np.sqrt((v64 ** 2).sum(1)).max() <= bound

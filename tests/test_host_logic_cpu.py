@@ -281,7 +281,7 @@ def test_rooms_with_more_than_four_corners_are_the_references():
 
 def test_footprint_record_operands_reproduce_the_8_8_lerp_for_every_input():
     """The engine's texture footprint records hold, per channel and texel pair, A = 256 a + 128 and D = (b - a) mod 2^16
-    (mw_engine.hip::build_pyramid); the raster kernel's x lerp is one packed 16-bit multiply-add and a shift,
+    (mw_assets.h::build_pyramid); the raster kernel's x lerp is one packed 16-bit multiply-add and a shift,
     (A + w D) mod 2^16 >> 8 (mw_raster_common.h::lerp8_ad).  Exhaustively over a, b, w in 0 .. 255 that is llvmpipe's
     a + ((w (b - a) + 128) >> 8) — and so is the three-instruction form of the other lerps, (a (256 - w) + (b w + 128)) >> 8,
     whose sums stay below 2^16."""
