@@ -18,13 +18,14 @@ def main():
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--repeat", type=int, default=1, help="action repeat: env steps per policy decision and frame (1 .. 256)")
     args = ap.parse_args()
 
     import torch
     from miniworld_amd.vector import MiniWorldVectorEnv
 
     # obs_layout="cwh": the kernel stores uint8[N, 3, W, H] (the reference's PyTorchObsWrapper layout) directly
-    envs = MiniWorldVectorEnv(args.env, args.envs, seed=args.seed, obs_layout="cwh")
+    envs = MiniWorldVectorEnv(args.env, args.envs, seed=args.seed, obs_layout="cwh", action_repeat=args.repeat)
     n_act = envs.single_action_space.n
     policy = torch.nn.Sequential(
         torch.nn.Conv2d(3, 16, 5, stride=2), torch.nn.ReLU(),
@@ -37,6 +38,7 @@ def main():
         for _ in range(5):
             policy(obs.half() / 255.0)
     episodes, returns = 0, torch.zeros(args.envs, device="cuda")
+    sim_steps = torch.zeros((), dtype=torch.int64, device="cuda")       # env steps simulated: the sum of info["substeps"]
     finished_returns = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -44,7 +46,8 @@ def main():
         for _ in range(args.steps):
             logits = policy(obs.half() / 255.0)
             actions = torch.distributions.Categorical(logits=logits.float()).sample().to(torch.int32)
-            obs, rew, term, trunc, _ = envs.step(actions)
+            obs, rew, term, trunc, info = envs.step(actions)
+            sim_steps += info["substeps"].sum() if args.repeat > 1 else args.envs
             returns += rew
             done = term | trunc
             if done.any():
@@ -54,7 +57,8 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     mean_ret = torch.cat(finished_returns).mean().item() if finished_returns else float("nan")
-    print(f"{args.env}: {args.envs * args.steps / dt:,.0f} env-steps/s with the policy in the loop, "
+    decisions = f" ({args.envs * args.steps / dt:,.0f} decisions/s at repeat {args.repeat})" if args.repeat > 1 else ""
+    print(f"{args.env}: {sim_steps.item() / dt:,.0f} env-steps/s with the policy in the loop{decisions}, "
           f"{episodes} episodes finished, mean return {mean_ret:.3f}")
     envs.close()
 

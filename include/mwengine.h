@@ -312,6 +312,33 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
  * step see the terminal state. */
 int mw_step(mw_engine *e, const int32_t *d_actions, uint8_t *d_obs, float *d_depth,
             float *d_reward, uint8_t *d_term, uint8_t *d_trunc, void *stream);
+/* Action repeat (gymnasium's frame skip, DMLab's action repeat): up to `repeat` consecutive MiniWorldEnv.step(action) per env with
+ * the same action, in ONE step-kernel launch, and one frame at the end.  Arguments as mw_step's, and
+ *   repeat    1 .. MW_MAX_REPEAT; anything else is MW_E_INVALID: nothing is launched, no state is touched
+ *   d_nsteps  int32[N] or NULL: the sub-steps the env executed in this call
+ * Per env and call:
+ *   - sub-steps 1, 2, ... are each exactly mw_step's step: physics, the env rule, step_count + 1 — max_episode_steps counts
+ *     sub-steps, as a frame-skip wrapper around the reference env would; with domain randomisation every executed sub-step takes its
+ *     three per-step draws from the env's stream (miniworld.py:677-680), with mw_set_step_params the override values.
+ *   - the env stops after the first sub-step that sets term | trunc; d_term / d_trunc are that last executed sub-step's flags;
+ *     d_reward is the sum of the executed sub-steps' rewards, taken in double, in order, rounded to float once.
+ *   - between two sub-steps the step kernel applies what the frame's tail applies after a rendered step: a picked-up object leaves
+ *     the entity list (pickupobjects.py:86-88), MW_TASK_COLLECT's consumed kit respawns with its draws from the env's stream (the
+ *     sub-step's draws, the respawn's, then the next sub-step's).  The last executed sub-step's removal is applied behind the frame
+ *     as after mw_step: the object is drawn one last time.
+ *   - auto-reset is applied once, after the last executed sub-step.  MW_AUTORESET_SAME_STEP: an env that finished installs its next
+ *     world, the frame is the new episode's first and the remaining repeats are dropped — an env never steps in two episodes within
+ *     one call.  MW_AUTORESET_NEXT_STEP: the call that ends an episode returns the terminal frame; the env's next call executes 0
+ *     sub-steps whatever `repeat` is — it installs the next world, reward 0, no flags, d_nsteps 0.  MW_AUTORESET_OFF or
+ *     MW_GEN_NONE: the env stops at its terminal state and the frame shows it.  With final buffers (mw_set_final_obs) the call
+ *     takes mw_step's two passes.
+ *   - mw_get_info, mw_get_final_info and mw_get_reset_pending behave as after an mw_step that ended with the call's last sub-step;
+ *     the frame-clean byte (mw_get_frame_clean) is 1 iff the env executed at least one sub-step and every executed sub-step left
+ *     its state as it was; frame reuse treats the call as a plain step of the whole batch.
+ * repeat = 1 returns what mw_step returns, bit for bit (through the repeat kernels; mw_step keeps the plain ones). */
+#define MW_MAX_REPEAT 256       /* keeps one launch bounded */
+int mw_step_repeat(mw_engine *e, const int32_t *d_actions, int32_t repeat, uint8_t *d_obs, float *d_depth,
+                   float *d_reward, uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, void *stream);
 /* Final observations of a MW_AUTORESET_SAME_STEP engine (Gymnasium's info["final_obs"] of a same-step vector env, SB3's
  * info["terminal_observation"]): d_final_obs and d_final_depth are device buffers shaped like mw_step's d_obs / d_depth (N rows in
  * the layout of mw_set_obs_layout at the time of the step).  With d_final_obs non-null, every later mw_step writes the TERMINAL

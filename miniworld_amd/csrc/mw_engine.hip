@@ -280,6 +280,14 @@ auto k1_of(const mw_engine *e, int lanes) -> decltype(&mw_step_setup_kernel)
     return pcg ? mw_step_setup_pcg_kernel : mw_step_setup_kernel;
 }
 
+// ... and mw_step_repeat's K1 (the same two forms around the sub-step loop)
+auto k1_repeat_of(const mw_engine *e, int lanes) -> decltype(&mw_step_repeat_kernel)
+{
+    const bool pcg = e->cfg.rng_mode == MW_RNG_PCG64;
+    if (lanes) return pcg ? mw_step_repeat_dense_pcg_kernel : mw_step_repeat_dense_kernel;
+    return pcg ? mw_step_repeat_pcg_kernel : mw_step_repeat_kernel;
+}
+
 // a kernel and its list form (mw_kernels.h: MW_KERNEL_PAIR)
 template <typename... A>
 struct KernelPair {
@@ -651,8 +659,9 @@ struct Frame {
 };
 
 // the step (a render-only frame has none), the list of a FRAME_TERMINAL step's finished envs, the frame's vertex half, CollectHealth's respawns
+// (repeat > 0: mw_step_repeat's step kernel, the same launch shape, up to `repeat` sub-steps per env, the executed count into d_nsteps)
 void launch_step_and_geometry(mw_engine *e, const Frame &f, bool do_step, int frame, bool async_refill, const int32_t *d_actions,
-                              float *d_reward, uint8_t *d_term, uint8_t *d_trunc)
+                              float *d_reward, uint8_t *d_term, uint8_t *d_trunc, int repeat, int32_t *d_nsteps)
 {
     const MwArgs &a = f.a; const int N = e->cfg.num_envs;
     if (do_step) {
@@ -662,9 +671,11 @@ void launch_step_and_geometry(mw_engine *e, const Frame &f, bool do_step, int fr
         MwArgs ak = a;          // the step kernel's arguments: the first pass of a final-observation step runs as a next-step terminal step
         if (frame == FRAME_TERMINAL) ak.autoreset = MW_AUTORESET_NEXT_STEP;
         const int lanes = k1_dense_lanes(e), epw = lanes ? 64 / lanes : 1;      // envs per workgroup
-        hipLaunchKernelGGL(k1_of(e, lanes), dim3((N + epw - 1) / epw + refill_blocks), dim3(64), 0, f.st, ak, lanes, d_actions,
-                           d_reward ? d_reward : e->d_reward_scratch, d_term ? d_term : e->d_flag_scratch,
-                           d_trunc ? d_trunc : e->d_flag_scratch + N);
+        const dim3 grid((N + epw - 1) / epw + refill_blocks);
+        float *reward = d_reward ? d_reward : e->d_reward_scratch;
+        uint8_t *term = d_term ? d_term : e->d_flag_scratch, *trunc = d_trunc ? d_trunc : e->d_flag_scratch + N;
+        if (repeat > 0) hipLaunchKernelGGL(k1_repeat_of(e, lanes), grid, dim3(64), 0, f.st, ak, lanes, d_actions, reward, term, trunc, repeat, d_nsteps);
+        else hipLaunchKernelGGL(k1_of(e, lanes), grid, dim3(64), 0, f.st, ak, lanes, d_actions, reward, term, trunc);
     }
     if (frame == FRAME_TERMINAL)
         hipLaunchKernelGGL(mw_final_list_kernel, dim3(1), dim3(1024), 0, f.st, N, (const uint8_t *)a.reset_pending, a.pending_remove, e->d_final_list);
@@ -789,7 +800,8 @@ int launch_mesh_chain(mw_engine *e, const Frame &f, hipStream_t st)
 }
 
 int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_actions, uint8_t *d_obs, float *d_depth,
-                 float *d_reward, uint8_t *d_term, uint8_t *d_trunc, hipStream_t st, int frame = FRAME_ALL)
+                 float *d_reward, uint8_t *d_term, uint8_t *d_trunc, hipStream_t st, int frame = FRAME_ALL, int repeat = 0,
+                 int32_t *d_nsteps = nullptr)
 {
     if (!d_obs) return fail(e, MW_E_INVALID, "d_obs is null");
     // Frame reuse: a plain step of the whole batch into the buffers that hold the frame before it leaves the envs K1 marks clean
@@ -820,7 +832,7 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
         (void)hipEventRecord(ev.a.get(), st);
     }
     const bool async_refill = e->spare_mode && do_step && e->cfg.generator == MW_GEN_MAZE;
-    launch_step_and_geometry(e, f, do_step, frame, async_refill, d_actions, d_reward, d_term, d_trunc);
+    launch_step_and_geometry(e, f, do_step, frame, async_refill, d_actions, d_reward, d_term, d_trunc, repeat, d_nsteps);
     if (timed) (void)hipEventRecord(ev.b.get(), st);
     int rc = MW_OK;
     if (async_refill && (rc = launch_side_refill(e, st))) return rc;
@@ -1297,22 +1309,23 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
     return MW_OK;
 }
 
-int mw_step(mw_engine *e, const int32_t *d_actions, uint8_t *d_obs, float *d_depth, float *d_reward,
-            uint8_t *d_term, uint8_t *d_trunc, void *stream)
+// mw_step (repeat = 0: the plain step kernels) and mw_step_repeat (1 .. MW_MAX_REPEAT: the repeat kernels)
+static int step_frames(mw_engine *e, const int32_t *d_actions, int repeat, uint8_t *d_obs, float *d_depth, float *d_reward,
+                uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, void *stream)
 {
-    if (!e) return MW_E_INVALID;
     ON_DEVICE(e);
     if (!d_actions) return fail(e, MW_E_INVALID, "d_actions is null");
     if ((e->cfg.generator == MW_GEN_PROGRAM || e->cfg.task >= MW_TASK_SIDEWALK) && !e->args.prog)
         return fail(e, MW_E_INVALID, "no placement program installed (mw_set_gen_program)");
-    if (!e->final_obs) return launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, (hipStream_t)stream);
+    if (!e->final_obs)
+        return launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, (hipStream_t)stream, FRAME_ALL, repeat, d_nsteps);
     // Same-step auto-reset with final observations, in two passes.  1: the step as the next-step mode's terminal step — physics,
     // rule, reward, flags, final info, per-step draws; the finished envs keep their terminal state — and the frame of every env.
     // The finished envs' rows go to the final buffers.  2: they install their next world (the same install code and stream order
     // as the plain same-step step: the step's draws, then the reset's), and the frame of those envs alone overwrites their rows.
     const hipStream_t st = (hipStream_t)stream;
     const int N = e->cfg.num_envs;
-    int rc = launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, st, FRAME_TERMINAL);
+    int rc = launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, st, FRAME_TERMINAL, repeat, d_nsteps);
     if (rc != MW_OK) return rc;
     const size_t row_bytes = (size_t)e->cfg.obs_width * e->cfg.obs_height * (e->obs_layout == MW_OBS_GREY_F64 ? 8 : 3);
     hipLaunchKernelGGL(mw_final_copy_kernel, dim3(N), dim3(256), 0, st, (const int32_t *)e->d_final_list, (const uint8_t *)d_obs, e->final_obs,
@@ -1320,6 +1333,21 @@ int mw_step(mw_engine *e, const int32_t *d_actions, uint8_t *d_obs, float *d_dep
     hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_final_install_pcg_kernel : mw_final_install_kernel, dim3(N), dim3(64), 0, st,
                        e->args, (const int32_t *)e->d_final_list);
     return launch_frame(e, false, 0, e->d_action_scratch, d_obs, d_depth, nullptr, nullptr, nullptr, st, FRAME_LIST);
+}
+
+int mw_step(mw_engine *e, const int32_t *d_actions, uint8_t *d_obs, float *d_depth, float *d_reward,
+            uint8_t *d_term, uint8_t *d_trunc, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    return step_frames(e, d_actions, 0, d_obs, d_depth, d_reward, d_term, d_trunc, nullptr, stream);
+}
+
+int mw_step_repeat(mw_engine *e, const int32_t *d_actions, int32_t repeat, uint8_t *d_obs, float *d_depth, float *d_reward,
+                   uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (repeat < 1 || repeat > MW_MAX_REPEAT) return fail(e, MW_E_INVALID, "mw_step_repeat: repeat %d outside 1 .. %d", (int)repeat, MW_MAX_REPEAT);
+    return step_frames(e, d_actions, repeat, d_obs, d_depth, d_reward, d_term, d_trunc, d_nsteps, stream);
 }
 
 int mw_set_final_obs(mw_engine *e, uint8_t *d_final_obs, float *d_final_depth)

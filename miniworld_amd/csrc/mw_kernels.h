@@ -17,6 +17,13 @@ extern "C" __global__ void mw_step_setup_kernel(MW_K1_ARGS);
 extern "C" __global__ void mw_step_setup_pcg_kernel(MW_K1_ARGS);
 extern "C" __global__ void mw_step_setup_dense_kernel(MW_K1_ARGS);
 extern "C" __global__ void mw_step_setup_dense_pcg_kernel(MW_K1_ARGS);
+// ... and mw_step_repeat's: the same sources around the sub-step loop (mw_setup_repeat*.hip; mw_setup_common.h: step_env_repeat),
+// up to `repeat` sub-steps per env, the executed count into nsteps (may be null)
+#define MW_K1_REPEAT_ARGS MW_K1_ARGS, int repeat, int32_t *__restrict__ nsteps
+extern "C" __global__ void mw_step_repeat_kernel(MW_K1_REPEAT_ARGS);
+extern "C" __global__ void mw_step_repeat_pcg_kernel(MW_K1_REPEAT_ARGS);
+extern "C" __global__ void mw_step_repeat_dense_kernel(MW_K1_REPEAT_ARGS);
+extern "C" __global__ void mw_step_repeat_dense_pcg_kernel(MW_K1_REPEAT_ARGS);
 
 // reset, spare refill, CollectHealth respawn, same-step install, spare take-over (mw_reset.hip, mw_reset_pcg.hip)
 extern "C" __global__ void mw_reset_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all, int mark_refill);

@@ -15,8 +15,7 @@
 
 // (lanes_per_env: the dense form's argument, 0 and unused here: one env per workgroup)
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MW_K1_OCC, 4))) void MW_SETUP_KERNEL_NAME(
-    MwArgs a, int lanes_per_env, const int32_t *__restrict__ actions, float *__restrict__ reward,
-    uint8_t *__restrict__ term, uint8_t *__restrict__ trunc)
+    MW_K1_PARAMS)
 {
     __shared__ int s_claim;
     __shared__ unsigned char gen_ws[MW_GEN_WS_BYTES];
@@ -27,5 +26,5 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(M
         return;
     }
     const int lane = threadIdx.x & 63;
-    step_env<false>(a, a.env_base + (int)blockIdx.x, lane, lane == 0, actions, reward, term, trunc, gen_ws, &s_claim);
+    MW_K1_STEP(false, a.env_base + (int)blockIdx.x, lane, lane == 0, gen_ws, &s_claim);
 }

@@ -204,6 +204,15 @@ __device__ void turn_agent(StepCtx &c, double turn_deg)
     }
 }
 
+// What one sub-step hands to the loop of a repeat call (step_env_repeat); the plain step ignores it.
+struct SubStep {
+    double rew;             // the sub-step's reward, before it is rounded to float
+    int tm, tr;
+    int remove_slot;        // what the sub-step left in pending_remove
+    bool ran;               // false: the call installed a pending next-step reset instead of stepping
+    bool clean;             // the writer lane's frame_clean value of this sub-step
+};
+
 // One env's step, the body of both K1 forms (mw_setup.hip: one wavefront per env, PER_LANE = false, the 64 lanes share the
 // collision tests; mw_setup_dense.hip: several envs per wavefront, PER_LANE = true, each lane tests alone).  Every lane of the
 // env calls it with the same env and evaluates the step; `writer`, one lane of the env, writes its state and flags.
@@ -212,8 +221,10 @@ __device__ void turn_agent(StepCtx &c, double turn_deg)
 //   MiniWorldEnv.intersect + intersect_circle_segs                 miniworld.py:937-963, math.py:30-62
 //   near / _reward + env rules                                     miniworld.py:965-975,1012-1017; hallway.py:67-74; pickupobjects.py:83-95
 // The frame itself — camera, transform, lighting, clipping, triangle setup — is the geometry kernel's (mw_geom.hip).
-template <bool PER_LANE>
-__device__ inline void step_env(const MwArgs &a, int env, int lane, bool writer, const int32_t *__restrict__ actions,
+// REPEAT: one sub-step of mw_step_repeat — the same step, except that reward, flags and the frame_clean byte are the loop's to
+// write, once per call (step_env_repeat).
+template <bool PER_LANE, bool REPEAT = false>
+__device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writer, const int32_t *__restrict__ actions,
                                 float *__restrict__ reward, uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
                                 unsigned char *gen_ws, int *s_claim)
 {
@@ -233,6 +244,8 @@ __device__ inline void step_env(const MwArgs &a, int env, int lane, bool writer,
     bool same = false;              // the state this step stores is the state it loaded, bit for bit
     int remove_slot = -1;
     int tm = 0, tr = 0;             // terminated / truncated, uniform over the env's lanes
+    double rew_out = 0.0;
+    bool clean_out = false;
     // next-step auto-reset: the env's last step ended its episode (and drew its terminal state); this step installs the
     // next world instead of stepping — no action, no per-step draws (miniworld.py:677-680 are step()'s, not reset()'s)
     const bool pend = a.autoreset == MW_AUTORESET_NEXT_STEP && a.reset_pending[env] != 0;
@@ -331,6 +344,7 @@ __device__ inline void step_env(const MwArgs &a, int env, int lane, bool writer,
             }
             if (health > 0) rew = 2.0; else { rew = -100.0; tm = 1; }
         }
+        if (REPEAT) rew_out = rew;
         // (compared, not tracked through the code paths above: a blocked move, a turn a carried box undoes, a pickup that finds
         // nothing all end here with the loaded values; a slot that is live now and was not carried before fails on `carry`)
         same = same_bits(c.px, o_px) && same_bits(c.py, o_py) && same_bits(c.pz, o_pz) && same_bits(c.dir, o_dir) && c.carry == o_carry &&
@@ -340,9 +354,11 @@ __device__ inline void step_env(const MwArgs &a, int env, int lane, bool writer,
         if (PER_LANE) __builtin_amdgcn_wave_barrier();
         if (writer) {
             if (drew) mw::rng_store(a.rng, a.N, env, rng);
-            reward[env] = (float)rew;
-            term[env] = (uint8_t)tm;
-            trunc[env] = (uint8_t)tr;
+            if (!REPEAT) {
+                reward[env] = (float)rew;
+                term[env] = (uint8_t)tm;
+                trunc[env] = (uint8_t)tr;
+            }
             a.step[env] = step_count;
             a.picked[env] = picked;
             if (!PER_LANE && a.task == MW_TASK_COLLECT) a.health[env] = health;
@@ -360,7 +376,7 @@ __device__ inline void step_env(const MwArgs &a, int env, int lane, bool writer,
                 if (a.autoreset == MW_AUTORESET_NEXT_STEP) a.reset_pending[env] = 1;
             }
         }
-    } else if (writer) {
+    } else if (writer && !REPEAT) {
         reward[env] = 0.0f;
         term[env] = 0;
         trunc[env] = 0;
@@ -394,9 +410,77 @@ __device__ inline void step_env(const MwArgs &a, int env, int lane, bool writer,
         // a slot still pending was never applied), not on a next-step reset, not when a world was installed.  CollectHealth never:
         // its respawn kernel moves entities behind this kernel's back.
         const bool clean = same && !pend && !installed && remove_slot < 0 && a.pending_remove[env] == -1 && a.task != MW_TASK_COLLECT;
-        a.frame_clean[env] = clean ? 1 : 0;
+        if (REPEAT) clean_out = clean; else a.frame_clean[env] = clean ? 1 : 0;
         a.pending_remove[env] = remove_slot;
+    }
+    return SubStep{rew_out, tm, tr, remove_slot, !pend, clean_out};
+}
+
+// mw_step_repeat's step of one env: up to `repeat` sub-steps with the same action, each one step_env, until one ends the episode;
+// the auto-reset (step_env's one install site) runs on that sub-step, or instead of the first one for a pending next-step reset,
+// so an env never steps in two episodes within one call.  Between two sub-steps the writer lane applies what the frame's tail
+// applies after a rendered step: a picked-up object leaves the list (pickupobjects.py:86-88 — the geometry kernel's part),
+// CollectHealth's consumed kit respawns with its draws from the env's stream (mw_collect_respawn_kernel's part).  The last
+// executed sub-step's removal stays in pending_remove for those two, so the object is drawn one last time.  The reward is summed
+// in double, in order, and rounded once; flags are the last executed sub-step's; frame_clean: at least one sub-step ran and every
+// one left the state as it was.
+// The envs of a dense wavefront stop at different sub-steps: the trip count is the wavefront's — the loop ends when none of its
+// envs is active — and an env that has stopped is predicated off, its lanes stay in the loop.
+template <bool PER_LANE>
+__device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool writer, const int32_t *__restrict__ actions, int repeat,
+                                       float *__restrict__ reward, uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
+                                       int32_t *__restrict__ nsteps, unsigned char *gen_ws, int *s_claim)
+{
+    double sum = 0.0;
+    int n = 0, tm = 0, tr = 0;
+    bool clean = true, active = true;
+    for (int k = 0; k < repeat; ++k) {
+        if (!ballot(active)) break;
+        if (active) {
+            const SubStep s = step_env<PER_LANE, true>(a, env, lane, writer, actions, reward, term, trunc, gen_ws, s_claim);
+            if (s.ran) {
+                sum += s.rew;
+                ++n;
+                tm = s.tm; tr = s.tr;
+                clean = clean && s.clean;
+            }
+            active = s.ran && !(tm | tr) && k + 1 < repeat;
+            if (active && writer && s.remove_slot >= 0) {
+                if (a.task == MW_TASK_COLLECT) {
+                    mw::collect_respawn(a, env, a.shared_geom ? 0 : env, s.remove_slot, a.ax[env], a.az[env]);
+                    a.pending_remove[env] = -1;
+                } else {
+                    a.ekind[(size_t)s.remove_slot * a.N + env] = MW_ENT_NONE;
+                    a.pending_remove[env] = MW_REMOVE_APPLIED;
+                }
+            }
+        }
+        // the env's lanes reload its state for the next sub-step: after the writer's stores (the install site's pattern, at
+        // workgroup scope: the lanes that reload are the writer's own wavefront, which is the whole workgroup in both forms.  The
+        // device-scope __threadfence() here, an L2 write-back and invalidate per sub-step, made the dense kernel 118 us at
+        // K = 4 where this one takes 48)
+        __threadfence_block();
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (writer) {
+        reward[env] = (float)sum;
+        term[env] = (uint8_t)tm;
+        trunc[env] = (uint8_t)tr;
+        if (nsteps) nsteps[env] = n;
+        a.frame_clean[env] = n > 0 && clean ? 1 : 0;
     }
 }
 
 }  // namespace
+
+// The two K1 sources (mw_setup.hip, mw_setup_dense.hip) compile as the plain step or, with MW_K1_REPEAT defined by the unit that
+// re-includes them (mw_setup_repeat*.hip), as mw_step_repeat's kernels: the same grid mapping and refill blocks around the
+// sub-step loop, `repeat` and `nsteps` as two more kernel parameters (mw_kernels.h).
+#ifdef MW_K1_REPEAT
+#define MW_K1_PARAMS MW_K1_REPEAT_ARGS
+#define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) \
+    step_env_repeat<PER_LANE>(a, env, lane, writer, actions, repeat, reward, term, trunc, nsteps, ws, claim)
+#else
+#define MW_K1_PARAMS MW_K1_ARGS
+#define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) step_env<PER_LANE>(a, env, lane, writer, actions, reward, term, trunc, ws, claim)
+#endif

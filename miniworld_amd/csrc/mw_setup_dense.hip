@@ -14,8 +14,7 @@
 
 
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void MW_DENSE_KERNEL_NAME(
-    MwArgs a, int lanes_per_env, const int32_t *__restrict__ actions, float *__restrict__ reward,
-    uint8_t *__restrict__ term, uint8_t *__restrict__ trunc)
+    MW_K1_PARAMS)
 {
     __shared__ unsigned char gen_ws[MW_GEN_WS_BYTES];      // generator scratch (used by the Maze generator only)
     const int lane = threadIdx.x;
@@ -31,5 +30,5 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1
     }
     const int env = (int)blockIdx.x * epw + el;
     if (el >= epw || env >= a.N) return;
-    step_env<true>(a, env, lane, slot == 0, actions, reward, term, trunc, gen_ws, nullptr);
+    MW_K1_STEP(true, env, lane, slot == 0, gen_ws, nullptr);
 }

@@ -18,6 +18,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("MW_ENGINE_LIB") or os.path.join(_CSRC, "libmwengine.so")
 
 ABI_VERSION = 4
+MAX_REPEAT = 256            # MW_MAX_REPEAT
 ENT_NONE, ENT_BOX, ENT_MESH, ENT_FRAME = 0, 1, 2, 3
 POLY_ENTITY = 0x100          # mw_poly.nv flag: quad of a static entity, not a room
 POLY_XF = 0x200              # ... drawn under its own glTranslatef / glRotatef (mw_poly.xf)
@@ -34,7 +35,7 @@ PATH_TILE, PATH_QUAD, PATH_QUAD_MESH, PATH_GENERIC = 0, 1, 2, 3
 EXPORTS = [
     "mw_create", "mw_destroy", "mw_last_error", "mw_upload_texture", "mw_upload_mesh",
     "mw_set_geometry", "mw_get_geometry", "mw_set_state", "mw_get_state", "mw_set_step_params", "mw_reset",
-    "mw_step", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
+    "mw_step", "mw_step_repeat", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
     "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
     "mw_selftest_sincosf",
 ]
@@ -179,6 +180,7 @@ def load_library():
     L.mw_set_gen_program.argtypes = [vp, C.POINTER(MwGenProgram), vp, vp, vp, vp, i32, vp, i32]
     L.mw_reset.argtypes = [vp, vp, vp, vp]
     L.mw_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mw_step_repeat.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mw_render.argtypes = [vp, vp, vp, vp]
     L.mw_render_top.argtypes = [vp, vp, vp, i32, vp]
     L.mw_render_view.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
@@ -334,10 +336,8 @@ class Engine:
                               f"{t.dtype} {tuple(t.shape)} on {t.device}{'' if t.is_contiguous() else ' (non-contiguous)'}")
         return t
 
-    def step(self, actions, obs, depth=None, reward=None, term=None, trunc=None):
-        """All arguments are torch tensors on this engine's device (depth may be None).  `actions` is converted to a
-        contiguous int32 tensor on the device if it is not one already (torch.randint / argmax / Categorical.sample
-        give int64; a column of a [N, T] tensor is strided); the output tensors are checked, never converted."""
+    def _step_tensors(self, actions, obs, depth, reward, term, trunc):
+        """The checks step() and step_repeat() share; returns the int32 actions."""
         import torch
         if actions.device != self.device or actions.dtype != torch.int32 or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
@@ -349,9 +349,29 @@ class Engine:
         self._dev_tensor(reward, "reward", torch.float32, self.N)
         self._dev_tensor(term, "terminated", torch.uint8, self.N)
         self._dev_tensor(trunc, "truncated", torch.uint8, self.N)
+        return actions
+
+    def step(self, actions, obs, depth=None, reward=None, term=None, trunc=None):
+        """All arguments are torch tensors on this engine's device (depth may be None).  `actions` is converted to a
+        contiguous int32 tensor on the device if it is not one already (torch.randint / argmax / Categorical.sample
+        give int64; a column of a [N, T] tensor is strided); the output tensors are checked, never converted."""
+        actions = self._step_tensors(actions, obs, depth, reward, term, trunc)
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         self._check(self.lib.mw_step(self.h, ptr(actions), ptr(obs), ptr(depth), ptr(reward), ptr(term),
                                      ptr(trunc), _stream_ptr(self.device)), "mw_step")
+
+    def step_repeat(self, actions, repeat, obs, depth=None, reward=None, term=None, trunc=None, nsteps=None):
+        """Action repeat (include/mwengine.h: mw_step_repeat): every env takes up to `repeat` steps with its action, stops at
+        the one that ends its episode, and one frame is drawn at the end.  Tensors as for step(); `nsteps`, int32[N] or None,
+        receives the sub-steps each env executed.  `repeat` outside 1 .. MAX_REPEAT raises before the library is called."""
+        import torch
+        if not isinstance(repeat, (int, np.integer)) or not 1 <= repeat <= MAX_REPEAT:
+            raise EngineError(f"repeat: need an integer in 1 .. {MAX_REPEAT}, got {repeat!r}")
+        actions = self._step_tensors(actions, obs, depth, reward, term, trunc)
+        self._dev_tensor(nsteps, "nsteps", torch.int32, self.N)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.mw_step_repeat(self.h, ptr(actions), int(repeat), ptr(obs), ptr(depth), ptr(reward), ptr(term),
+                                            ptr(trunc), ptr(nsteps), _stream_ptr(self.device)), "mw_step_repeat")
 
     def set_final_obs(self, obs=None, depth=None):
         """Same-step auto-reset: every later step writes the terminal frame (and depth) of each env whose episode ended in it into

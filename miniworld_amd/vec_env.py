@@ -228,6 +228,7 @@ class MiniWorldVecEnv:
         self.reward = torch.zeros(num_envs, dtype=torch.float32, device=dev)
         self.terminated = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
         self.truncated = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
+        self.substeps = None            # int32[N], made by the first step(actions, repeat > 1)
         self.final_obs = self.final_depth = None
         if final_obs:
             self.final_obs = self.engine.obs_buffer()
@@ -299,9 +300,18 @@ class MiniWorldVecEnv:
         self.engine.render(self.obs, self.depth)
         return self.obs
 
-    def step(self, actions):
-        """actions: integer torch tensor [N] (converted to contiguous int32 on the engine's device if needed)."""
-        self.engine.step(actions, self.obs, self.depth, self.reward, self.terminated, self.truncated)
+    def step(self, actions, repeat: int = 1):
+        """actions: integer torch tensor [N] (converted to contiguous int32 on the engine's device if needed).
+        repeat > 1 (action repeat, up to engine.MAX_REPEAT): every env takes up to `repeat` steps with its action in one kernel
+        launch and stops at the one that ends its episode; the observation is the frame after the last of them (after the
+        auto-reset, as for a single step), the reward their sum, the flags the last one's, and `self.substeps` (int32[N] on
+        the device) the number each env took — 0 for the reset step of autoreset="next_step".  max_episode_steps counts them."""
+        if repeat == 1:
+            self.engine.step(actions, self.obs, self.depth, self.reward, self.terminated, self.truncated)
+            return self.obs, self.reward, self.terminated, self.truncated
+        if self.substeps is None:
+            self.substeps = self.torch.zeros(self.num_envs, dtype=self.torch.int32, device=self.engine.device)
+        self.engine.step_repeat(actions, repeat, self.obs, self.depth, self.reward, self.terminated, self.truncated, self.substeps)
         return self.obs, self.reward, self.terminated, self.truncated
 
     def infos(self):

@@ -49,10 +49,15 @@ class MiniWorldVectorEnv(VectorEnvBase):
     metadata = {"autoreset_mode": AUTORESET_SAME_STEP, "render_modes": ["rgb_array"]}
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
-                 frame_reuse: bool = True, **kwargs):
+                 frame_reuse: bool = True, action_repeat: int = 1, **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
-        False draws every env on every step, for consumers that write into the returned observation tensor (module docstring)."""
+        False draws every env on every step, for consumers that write into the returned observation tensor (module docstring).
+        action_repeat > 1: every step() holds the action for up to that many env steps (MiniWorldVecEnv.step's `repeat`) and
+        info["substeps"] (int32[N]) tells how many each env took."""
+        if not isinstance(action_repeat, (int, np.integer)) or not 1 <= action_repeat <= 256:
+            raise ValueError(f"action_repeat must be an integer in 1 .. 256, not {action_repeat!r}")
+        self.action_repeat = int(action_repeat)
         kwargs["frame_reuse"] = frame_reuse
         mode = str(getattr(autoreset_mode, "name", autoreset_mode)).lower().replace("_", "-")     # (an AutoresetMode: its name)
         if mode not in ("same-step", "next-step"):
@@ -94,8 +99,10 @@ class MiniWorldVectorEnv(VectorEnvBase):
         if not torch.is_tensor(actions):
             actions = torch.as_tensor(np.asarray(actions), device=self.vec.engine.device)
         actions = actions.to(device=self.vec.engine.device, dtype=torch.int32)
-        obs, rew, term, trunc = self.vec.step(actions)
+        obs, rew, term, trunc = self.vec.step(actions, self.action_repeat)
         info = self._infos()
+        if self.action_repeat > 1:
+            info["substeps"] = self._out(self.vec.substeps) if self.to_numpy else self.vec.substeps.clone()
         if self.vec.autoreset_mode == "same_step":
             # gymnasium's same-step convention: "_final_info" masks the envs whose episode ended with this step (every family); the
             # finished episodes' own info under "final_info" where the family has info keys — clones, the engine's buffers are
