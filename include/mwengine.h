@@ -298,7 +298,9 @@ int mw_get_state(mw_engine *e, int32_t first_env, int32_t count, mw_state_view *
  * mask: host uint8[num_envs] or NULL (= all); seeds: host uint64[num_envs] or NULL.
  * With MW_GEN_NONE (host-generated worlds) only the re-seeding happens: seeds[i] (masked) re-seeds env i's device
  * stream, which serves the per-step domain-randomisation draws (miniworld.py:677-680); seeds == NULL is an error.
- * A pending next-step auto-reset of a reset env is dropped (the env's next step is an ordinary one). */
+ * A pending next-step auto-reset of a reset env is dropped (the env's next step is an ordinary one).
+ * With a frame stack (mw_set_frame_stack) the envs whose world it writes are marked: mw_stack_refresh or their next push rebuilds
+ * their stacks (a MW_GEN_NONE engine's reset writes no world and marks nothing). */
 int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *stream);
 
 /* ---- the hot path ------------------------------------------------------------ */
@@ -350,6 +352,46 @@ int mw_step_repeat(mw_engine *e, const int32_t *d_actions, int32_t repeat, uint8
  * MW_E_INVALID on MW_AUTORESET_OFF / MW_AUTORESET_NEXT_STEP engines and on MW_GEN_NONE engines (nothing is auto-reset there: the
  * frame mw_step returns is the terminal one). */
 int mw_set_final_obs(mw_engine *e, uint8_t *d_final_obs, float *d_final_depth);
+/* Frame stacking on the device (Gymnasium's FrameStackObservation, SB3's VecFrameStack, EnvPool's stack_num around the reference env):
+ * the engine keeps the last `depth` frames each env RETURNED — its rows of d_obs, in the layout of mw_set_obs_layout; depth maps are
+ * not stacked — oldest first, in the caller's ring.
+ *   depth         2 .. MW_MAX_STACK; 0 (or d_ring == NULL) turns the stack off
+ *   pad           what fills a new episode's stack: MW_STACK_PAD_RESET depth copies of its first frame (Gymnasium's
+ *                 padding_type="reset"), MW_STACK_PAD_ZERO depth - 1 all-zero frames, then the frame (SB3's VecFrameStack)
+ *   d_ring        [N][2 * depth - 1][frame bytes].  Push number j of the engine (0, 1, ...) writes an env's frame to slot
+ *                 (j mod depth) + depth - 1 and, when j mod depth >= 1, to slot (j mod depth) - 1 too; after it the ordered window of
+ *                 every env is the `depth` consecutive slots from slot j mod depth on (mw_stack_window) — nothing is ever shifted
+ *   d_final_stack [N][depth][frame bytes] or NULL; used by the steps of an engine with final buffers (mw_set_final_obs), and
+ *                 MW_E_INVALID where mw_set_final_obs is (not MW_AUTORESET_SAME_STEP, or MW_GEN_NONE)
+ * A depth outside 2 .. MW_MAX_STACK or an unknown pad is MW_E_INVALID and changes nothing.  Setting a stack marks every env "never
+ * pushed", restarts j at 0 and remembers the layout: a step or refresh under another layout is MW_E_INVALID before anything is
+ * launched (mw_render / mw_render_top under another layout push nothing and stay legal).
+ * One push ends every mw_step and every mw_step_repeat (one per call: the stack holds the frames the agent saw), asynchronous on the
+ * call's stream behind its last raster kernel; everything else the call returns is bit for bit what it returns without a stack,
+ * frame reuse included (the push reads the rows of clean envs where they lie).  Per env and push:
+ *   - an ordinary frame: the window drops its oldest frame and gains the call's; afterwards its newest frame is the env's row of d_obs.
+ *   - the first frame of an episode: the env's whole stack is rebuilt from that frame and the pad.  That is: the call installed a
+ *     world for the env through auto-reset (same-step: the call set term | trunc and a generator is configured; next-step: the env
+ *     entered the call with reset_pending); or mw_reset wrote the env's world since its last push; or the env was never pushed.  With
+ *     MW_AUTORESET_OFF or MW_GEN_NONE a finished env keeps stacking its terminal state's frames until the host resets it.
+ *   - mw_set_state is mid-episode injection and leaves stacks alone; as it clears a pending next-step reset, it also cancels the
+ *     rebuild that reset would have caused.
+ *   - final stacks (final buffers and d_final_stack both set): for every env whose episode ended in the call, its row of
+ *     d_final_stack = its depth - 1 newest frames from before this push (zeros where the zero pad still shows; the pad alone for an
+ *     env without a valid stack: reset or never pushed, and not refreshed), then its terminal frame, the row mw_set_final_obs
+ *     writes.  The rows of the other envs are not written. */
+#define MW_MAX_STACK 16
+enum { MW_STACK_PAD_RESET = 0, MW_STACK_PAD_ZERO = 1 };
+int mw_set_frame_stack(mw_engine *e, int32_t depth, int32_t pad, uint8_t *d_ring, uint8_t *d_final_stack /* [N][depth][frame] or NULL */);
+/* The reset path of a frame stack (FrameStackObservation.reset, VecFrameStack.reset): rebuilds, from their rows of d_obs, the stacks of
+ * exactly those envs that mw_reset wrote since their last push or that were never pushed; every other env and the ring position stay
+ * as they are.  The host sequence is mw_reset(mask), mw_render(d_obs), mw_stack_refresh(d_obs); an env reset without a refresh is
+ * rebuilt by its next push instead.  Asynchronous on `stream`; MW_E_INVALID without a stack or under another layout than the stack's. */
+int mw_stack_refresh(mw_engine *e, const uint8_t *d_obs, void *stream);
+/* Where the ordered window lies (the view FrameStackObservation / VecFrameStack hand out as the observation): *first_slot = the slot
+ * of every env's oldest frame — stack[env][k] = d_ring[env][*first_slot + k], k = 0 .. depth - 1 —, *pushes = the pushes since
+ * mw_set_frame_stack.  Host values, no synchronisation; either pointer may be NULL; MW_E_INVALID without a stack. */
+int mw_stack_window(const mw_engine *e, int32_t *first_slot, int64_t *pushes);   /* host values, no sync */
 /* Layout of the d_obs buffer written by mw_step / mw_render / mw_render_top — the reference's
  * observation wrappers (wrappers.py) folded into the raster kernel's store:
  *   MW_OBS_HWC_U8   uint8 [N][H][W][3]   the env's own observation (default)

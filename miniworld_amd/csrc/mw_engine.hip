@@ -188,6 +188,16 @@ struct mw_engine {
     // frame depends on (drop_held_frame).
     bool frame_reuse = false;
     struct { uint8_t *obs = nullptr; float *depth = nullptr; int layout = 0; bool valid = false; } held;
+    // mw_set_frame_stack: the caller's ring (depth = 0: off), the layout and frame size it was set under, the pushes so far — a host
+    // counter, every launch gets its phase by value — and the engine's flag bytes, [2][N] (MW_STACK_*): a push or refresh reads
+    // flags[cur] and writes the other half, which becomes the current one (mw_stack.hip); the host's marks go to flags[cur]
+    struct {
+        int depth = 0, pad = 0, layout = 0, cur = 0;
+        uint8_t *ring = nullptr, *final_stack = nullptr;
+        size_t frame_bytes = 0;
+        int64_t pushes = 0;
+        uint8_t *flags = nullptr;
+    } stack;
 };
 
 namespace {
@@ -344,6 +354,50 @@ int raster_flags(const mw_engine *e, int part, uint32_t stamp, bool reuse = fals
     return e->dbg_flags | e->obs_layout << 8 | part << 4 | (int)(stamp << 16) | (reuse && stamp == 0u ? MW_RASTER_REUSE : 0);
 }
 void drop_held_frame(mw_engine *e) { e->held.valid = false; }
+
+// bytes of one env's row of d_obs in the current output layout
+size_t obs_row_bytes(const mw_engine *e)
+{
+    return (size_t)e->cfg.obs_width * e->cfg.obs_height * (e->obs_layout == MW_OBS_GREY_F64 ? 8 : 3);
+}
+
+// Frame stacking (mw_set_frame_stack; kernels: mw_stack.hip).  phase of the last push: the window starts there (before the first push
+// every slot a refresh wrote is valid, and the same formula gives depth - 1).
+int stack_phase(const mw_engine *e) { return (int)((e->stack.pushes + e->stack.depth - 1) % e->stack.depth); }
+uint8_t *stack_flags(const mw_engine *e, int half) { return e->stack.flags + (size_t)half * e->cfg.num_envs; }
+// a push or refresh draws from rows of the layout and size the stack was set under: checked before anything is launched
+int stack_check(mw_engine *e, const char *what)
+{
+    if (e->stack.depth && (e->stack.layout != e->obs_layout || e->stack.frame_bytes != obs_row_bytes(e)))
+        return fail(e, MW_E_INVALID, "%s: the frame stack was set under obs layout %d, the engine is in layout %d now (mw_set_frame_stack again, or switch back)",
+                    what, e->stack.layout, e->obs_layout);
+    return MW_OK;
+}
+// the push behind a step's last raster kernel (term, trunc: the buffers the step kernel wrote), or the refresh (push = false)
+int launch_stack(mw_engine *e, bool push, const uint8_t *d_obs, const uint8_t *term, const uint8_t *trunc, hipStream_t st)
+{
+    auto &s = e->stack;
+    const int N = e->cfg.num_envs, phase = push ? (int)(s.pushes % s.depth) : stack_phase(e);
+    const bool installs = e->cfg.generator != MW_GEN_NONE;      // auto-reset installs worlds (none with MW_GEN_NONE)
+    const bool same = installs && e->cfg.autoreset == MW_AUTORESET_SAME_STEP, next = installs && e->cfg.autoreset == MW_AUTORESET_NEXT_STEP;
+    const uint8_t *final_obs = push && same && s.final_stack ? e->final_obs : nullptr;
+    uint8_t *final_stack = final_obs ? s.final_stack : nullptr;
+    const bool wide = (((uintptr_t)d_obs | (uintptr_t)s.ring | (uintptr_t)final_obs | (uintptr_t)final_stack | (uintptr_t)s.frame_bytes) & 15u) == 0;
+    const size_t units = s.frame_bytes / (wide ? 16 : 1), chunk = (size_t)MW_STACK_THREADS * MW_STACK_UNROLL;
+    const dim3 grid(N, (unsigned)((units + chunk - 1) / chunk));
+    const uint8_t *in = stack_flags(e, s.cur);
+    uint8_t *out = stack_flags(e, s.cur ^ 1);
+    if (push)
+        hipLaunchKernelGGL(mw_stack_push_kernel, grid, dim3(MW_STACK_THREADS), 0, st, s.depth, s.pad, phase, (unsigned long long)s.frame_bytes, (int)wide, d_obs, s.ring,
+                           in, out, same ? term : nullptr, same ? trunc : nullptr, next ? (const uint8_t *)e->args.reset_pending : nullptr, final_obs, final_stack);
+    else
+        hipLaunchKernelGGL(mw_stack_refresh_kernel, grid, dim3(MW_STACK_THREADS), 0, st, s.depth, s.pad, phase, (unsigned long long)s.frame_bytes, (int)wide, d_obs, s.ring,
+                           in, out);
+    HIP_TRY(e, hipGetLastError());
+    s.cur ^= 1;
+    if (push) ++s.pushes;
+    return MW_OK;
+}
 
 // The tile / quad / mesh-scatter kernels keep edge values in 32 bits: |c_k| = |dcdx X - dcdy Y| <= 2 W H 2^16 has to stay below
 // 2^31, i.e. W H < 16384 — 128 x 96 passes, 128 x 128 does not (a wall across the whole frame lost its triangle there);
@@ -962,6 +1016,7 @@ int init_engine(mw_engine *e, const mw_config *cfg)
     ALLOC(a.nvis, N); ALLOC(a.envhdr, (size_t)MW_ENVHDR * N); ALLOC(a.status, 1);
     ALLOC(e->d_reward_scratch, N); ALLOC(e->d_flag_scratch, 2 * (size_t)N); ALLOC(e->d_action_scratch, N);
     ALLOC(e->d_final_list, 1 + (size_t)N);
+    ALLOC(e->stack.flags, 2 * (size_t)N);
     ALLOC(e->d_mask, N); ALLOC(e->d_step_override, 3 * (size_t)N);
 #ifdef MW_PERF_HOOKS        // (tools/perf: make EXTRA=-DMW_PERF_HOOKS — kernel phase stamps dumped by mw_destroy; not in the product build)
     if (getenv("MW_K1_PROF")) ALLOC(a.k1_prof, MW_K1_PROF_SLOTS * (size_t)N);     // per-env cycle stamps of the geometry kernel's phases (zeroed)
@@ -1193,6 +1248,14 @@ int mw_set_state(mw_engine *e, int32_t first_env, int32_t count, const mw_state_
     // a world written from the host replaces whatever a pending next-step auto-reset would have installed
     HIP_TRY(e, hipMemset(e->args.reset_pending + first_env, 0, (size_t)count));
     HIP_TRY(e, hipDeviceSynchronize());     // (a null-stream memset: the caller's stream is not ordered against it)
+    if (e->stack.depth && count > 0) {
+        // ... and with it the rebuild of the env's frame stack that reset would have caused; the stacks themselves stay
+        std::vector<uint8_t> fl((size_t)count);
+        uint8_t *d = stack_flags(e, e->stack.cur) + first_env;
+        HIP_TRY(e, hipMemcpy(fl.data(), d, (size_t)count, hipMemcpyDeviceToHost));
+        for (uint8_t &f : fl) f &= (uint8_t)~MW_STACK_PENDING;
+        HIP_TRY(e, hipMemcpy(d, fl.data(), (size_t)count, hipMemcpyHostToDevice));
+    }
     return MW_OK;
 }
 
@@ -1305,8 +1368,32 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
         }
         hipLaunchKernelGGL(refill, grid, dim3(64), 0, st, e->args);
     }
+    // the envs whose world was just written start an episode: mw_stack_refresh or their next push rebuilds their frame stacks
+    if (e->stack.depth)
+        hipLaunchKernelGGL(mw_stack_mark_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, (const uint8_t *)e->d_mask, all, stack_flags(e, e->stack.cur));
     HIP_TRY(e, hipGetLastError());
     return MW_OK;
+}
+
+// the frames of one call: one, or the two passes of a same-step step with final observations
+static int step_passes(mw_engine *e, const int32_t *d_actions, int repeat, uint8_t *d_obs, float *d_depth, float *d_reward,
+                       uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, hipStream_t st)
+{
+    if (!e->final_obs)
+        return launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, st, FRAME_ALL, repeat, d_nsteps);
+    // Same-step auto-reset with final observations, in two passes.  1: the step as the next-step mode's terminal step — physics,
+    // rule, reward, flags, final info, per-step draws; the finished envs keep their terminal state — and the frame of every env.
+    // The finished envs' rows go to the final buffers.  2: they install their next world (the same install code and stream order
+    // as the plain same-step step: the step's draws, then the reset's), and the frame of those envs alone overwrites their rows.
+    const int N = e->cfg.num_envs;
+    int rc = launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, st, FRAME_TERMINAL, repeat, d_nsteps);
+    if (rc != MW_OK) return rc;
+    const size_t row_bytes = obs_row_bytes(e);
+    hipLaunchKernelGGL(mw_final_copy_kernel, dim3(N), dim3(256), 0, st, (const int32_t *)e->d_final_list, (const uint8_t *)d_obs, e->final_obs,
+                       (unsigned long long)row_bytes, (const float *)d_depth, e->final_depth, e->cfg.obs_width * e->cfg.obs_height);
+    hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_final_install_pcg_kernel : mw_final_install_kernel, dim3(N), dim3(64), 0, st,
+                       e->args, (const int32_t *)e->d_final_list);
+    return launch_frame(e, false, 0, e->d_action_scratch, d_obs, d_depth, nullptr, nullptr, nullptr, st, FRAME_LIST);
 }
 
 // mw_step (repeat = 0: the plain step kernels) and mw_step_repeat (1 .. MW_MAX_REPEAT: the repeat kernels)
@@ -1317,22 +1404,11 @@ static int step_frames(mw_engine *e, const int32_t *d_actions, int repeat, uint8
     if (!d_actions) return fail(e, MW_E_INVALID, "d_actions is null");
     if ((e->cfg.generator == MW_GEN_PROGRAM || e->cfg.task >= MW_TASK_SIDEWALK) && !e->args.prog)
         return fail(e, MW_E_INVALID, "no placement program installed (mw_set_gen_program)");
-    if (!e->final_obs)
-        return launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, (hipStream_t)stream, FRAME_ALL, repeat, d_nsteps);
-    // Same-step auto-reset with final observations, in two passes.  1: the step as the next-step mode's terminal step — physics,
-    // rule, reward, flags, final info, per-step draws; the finished envs keep their terminal state — and the frame of every env.
-    // The finished envs' rows go to the final buffers.  2: they install their next world (the same install code and stream order
-    // as the plain same-step step: the step's draws, then the reset's), and the frame of those envs alone overwrites their rows.
-    const hipStream_t st = (hipStream_t)stream;
-    const int N = e->cfg.num_envs;
-    int rc = launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, st, FRAME_TERMINAL, repeat, d_nsteps);
-    if (rc != MW_OK) return rc;
-    const size_t row_bytes = (size_t)e->cfg.obs_width * e->cfg.obs_height * (e->obs_layout == MW_OBS_GREY_F64 ? 8 : 3);
-    hipLaunchKernelGGL(mw_final_copy_kernel, dim3(N), dim3(256), 0, st, (const int32_t *)e->d_final_list, (const uint8_t *)d_obs, e->final_obs,
-                       (unsigned long long)row_bytes, (const float *)d_depth, e->final_depth, e->cfg.obs_width * e->cfg.obs_height);
-    hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_final_install_pcg_kernel : mw_final_install_kernel, dim3(N), dim3(64), 0, st,
-                       e->args, (const int32_t *)e->d_final_list);
-    return launch_frame(e, false, 0, e->d_action_scratch, d_obs, d_depth, nullptr, nullptr, nullptr, st, FRAME_LIST);
+    if (const int rc = stack_check(e, repeat ? "mw_step_repeat" : "mw_step")) return rc;
+    const int rc = step_passes(e, d_actions, repeat, d_obs, d_depth, d_reward, d_term, d_trunc, d_nsteps, (hipStream_t)stream);
+    if (rc != MW_OK || !e->stack.depth) return rc;
+    // the call's one push, behind its last raster kernel; the flags are where the step kernel wrote them (launch_step_and_geometry)
+    return launch_stack(e, true, d_obs, d_term ? d_term : e->d_flag_scratch, d_trunc ? d_trunc : e->d_flag_scratch + e->cfg.num_envs, (hipStream_t)stream);
 }
 
 int mw_step(mw_engine *e, const int32_t *d_actions, uint8_t *d_obs, float *d_depth, float *d_reward,
@@ -1360,6 +1436,48 @@ int mw_set_final_obs(mw_engine *e, uint8_t *d_final_obs, float *d_final_depth)
     drop_held_frame(e);
     e->final_obs = d_final_obs;
     e->final_depth = d_final_obs ? d_final_depth : nullptr;
+    return MW_OK;
+}
+
+int mw_set_frame_stack(mw_engine *e, int32_t depth, int32_t pad, uint8_t *d_ring, uint8_t *d_final_stack)
+{
+    if (!e) return MW_E_INVALID;
+    if (depth == 0 || !d_ring) {
+        e->stack.depth = 0;
+        e->stack.ring = e->stack.final_stack = nullptr;
+        return MW_OK;
+    }
+    if (depth < 2 || depth > MW_MAX_STACK) return fail(e, MW_E_INVALID, "mw_set_frame_stack: depth %d outside 2 .. %d", (int)depth, MW_MAX_STACK);
+    if (pad != MW_STACK_PAD_RESET && pad != MW_STACK_PAD_ZERO) return fail(e, MW_E_INVALID, "mw_set_frame_stack: unknown pad mode %d", (int)pad);
+    if (d_final_stack && (e->cfg.autoreset != MW_AUTORESET_SAME_STEP || e->cfg.generator == MW_GEN_NONE))
+        return fail(e, MW_E_INVALID, "mw_set_frame_stack: final stacks exist where final observations do (MW_AUTORESET_SAME_STEP with a generator)");
+    ON_DEVICE(e);
+    // every env "never pushed": written behind whatever still runs, and finished before the caller's stream can read it
+    HIP_TRY(e, hipDeviceSynchronize());
+    HIP_TRY(e, hipMemset(e->stack.flags, MW_STACK_FRESH, 2 * (size_t)e->cfg.num_envs));
+    HIP_TRY(e, hipDeviceSynchronize());
+    e->stack.depth = depth; e->stack.pad = pad; e->stack.layout = e->obs_layout; e->stack.cur = 0;
+    e->stack.ring = d_ring; e->stack.final_stack = d_final_stack;
+    e->stack.frame_bytes = obs_row_bytes(e);
+    e->stack.pushes = 0;
+    return MW_OK;
+}
+
+int mw_stack_refresh(mw_engine *e, const uint8_t *d_obs, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (!e->stack.depth) return fail(e, MW_E_INVALID, "mw_stack_refresh: no frame stack set (mw_set_frame_stack)");
+    if (!d_obs) return fail(e, MW_E_INVALID, "mw_stack_refresh: d_obs is null");
+    if (const int rc = stack_check(e, "mw_stack_refresh")) return rc;
+    ON_DEVICE(e);
+    return launch_stack(e, false, d_obs, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int mw_stack_window(const mw_engine *e, int32_t *first_slot, int64_t *pushes)
+{
+    if (!e || !e->stack.depth) return MW_E_INVALID;
+    if (first_slot) *first_slot = stack_phase(e);
+    if (pushes) *pushes = e->stack.pushes;
     return MW_OK;
 }
 

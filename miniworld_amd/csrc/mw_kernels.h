@@ -117,6 +117,24 @@ MW_KERNEL_PAIR(mw_view_mesh, int W, int H, int S, int first_env, const float *__
 MW_KERNEL_PAIR(mw_view_raster, MW_VIEW_RASTER_ARGS);
 MW_KERNEL_PAIR(mw_view_raster_any, MW_VIEW_RASTER_ARGS);
 
+// frame stacking (mw_stack.hip): the push behind a step's last raster kernel, mw_stack_refresh's form of the same body, mw_reset's marks.
+// Grid (N, chunks of MW_STACK_THREADS * MW_STACK_UNROLL units); a unit is 16 bytes (`wide`: obs, ring, the final buffers and the frame
+// size are all multiples of 16) or one byte.  The per-env flag byte: MW_STACK_FRESH — reset by the host or never pushed, the stack is
+// rebuilt by mw_stack_refresh or the next push; MW_STACK_PENDING — the env's next call installs a world (next-step auto-reset), the
+// push of that call rebuilds.
+#define MW_STACK_THREADS 256
+#define MW_STACK_UNROLL 4
+#define MW_STACK_FRESH 1
+#define MW_STACK_PENDING 2
+#define MW_STACK_ARGS \
+    int depth, int pad, int phase, unsigned long long frame_bytes, int wide, const uint8_t *__restrict__ obs, uint8_t *ring, \
+    const uint8_t *__restrict__ flags_in, uint8_t *__restrict__ flags_out
+extern "C" __global__ void mw_stack_push_kernel(MW_STACK_ARGS, const uint8_t *__restrict__ term, const uint8_t *__restrict__ trunc,
+                                                const uint8_t *__restrict__ pending, const uint8_t *__restrict__ final_obs,
+                                                uint8_t *__restrict__ final_stack);
+extern "C" __global__ void mw_stack_refresh_kernel(MW_STACK_ARGS);
+extern "C" __global__ void mw_stack_mark_kernel(int N, const uint8_t *__restrict__ mask, int force_all, uint8_t *__restrict__ flags);
+
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,
                                              const float *__restrict__ rec_cull, const int32_t *__restrict__ nvis, uint8_t *__restrict__ vis);

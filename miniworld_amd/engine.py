@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("MW_ENGINE_LIB") or os.path.join(_CSRC, "libmwengine.s
 
 ABI_VERSION = 4
 MAX_REPEAT = 256            # MW_MAX_REPEAT
+MAX_STACK = 16              # MW_MAX_STACK
+STACK_PAD_RESET, STACK_PAD_ZERO = 0, 1
 ENT_NONE, ENT_BOX, ENT_MESH, ENT_FRAME = 0, 1, 2, 3
 POLY_ENTITY = 0x100          # mw_poly.nv flag: quad of a static entity, not a room
 POLY_XF = 0x200              # ... drawn under its own glTranslatef / glRotatef (mw_poly.xf)
@@ -38,6 +40,7 @@ EXPORTS = [
     "mw_step", "mw_step_repeat", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
     "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
     "mw_selftest_sincosf",
+    "mw_set_frame_stack", "mw_stack_refresh", "mw_stack_window",
 ]
 
 
@@ -187,6 +190,9 @@ def load_library():
     L.mw_visible_ents.argtypes = [vp, i32, i32, vp, vp]
     L.mw_set_obs_layout.argtypes = [vp, i32]
     L.mw_set_final_obs.argtypes = [vp, vp, vp]
+    L.mw_set_frame_stack.argtypes = [vp, i32, i32, vp, vp]
+    L.mw_stack_refresh.argtypes = [vp, vp, vp]
+    L.mw_stack_window.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_int64)]
     L.mw_pcg64_draws.argtypes = [C.c_uint64, i32, vp, vp]
     L.mw_check.argtypes = [vp, vp]
     L.mw_kernel_time_ms.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -206,6 +212,14 @@ def load_library():
 def frame_reuse_allowed() -> bool:
     """MW_FRAME_REUSE=0 forces frame reuse off, whatever a caller asks for: the A/B switch of an unchanged benchmark run."""
     return os.environ.get("MW_FRAME_REUSE", "1").strip() != "0"
+
+
+def stack_slots(depth: int, push: int):
+    """The ring rule of mw_set_frame_stack, once for host code and tests: push number `push` (0, 1, ...) of a stack of `depth`
+    frames writes the frame to the slots `write_slots` of the env's 2 * depth - 1, and the ordered window after it is the `depth`
+    consecutive slots from `window_first` on.  Returns (write_slots, window_first)."""
+    p = push % depth
+    return ((p + depth - 1,) if p == 0 else (p + depth - 1, p - 1)), p
 
 
 def _stream_ptr(device=None):
@@ -385,6 +399,34 @@ class Engine:
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         self._check(self.lib.mw_set_final_obs(self.h, ptr(obs), ptr(depth if obs is not None else None)), "mw_set_final_obs")
         self._final_bufs = (obs, depth) if obs is not None else None
+
+    def set_frame_stack(self, depth: int, pad: int = STACK_PAD_RESET, ring=None, final_stack=None):
+        """Frame stacking on the device (include/mwengine.h: mw_set_frame_stack): every later step() / step_repeat() pushes its
+        frame into `ring`, a device tensor of [N, 2 * depth - 1, *frame] elements in the obs dtype, and — on an engine with final
+        buffers — completes the rows of `final_stack` ([N, depth, *frame]) of the envs whose episode ended.  depth = 0 or
+        ring=None turns it off.  The engine keeps references to the tensors while they are in use."""
+        import torch
+        if depth and ring is not None:
+            per_frame = self.H * self.W * (1 if self.obs_layout == OBS_GREY_F64 else 3)
+            dtype = torch.float64 if self.obs_layout == OBS_GREY_F64 else torch.uint8
+            self._dev_tensor(ring, "stack ring", dtype, self.N * (2 * depth - 1) * per_frame)
+            self._dev_tensor(final_stack, "final stack", dtype, self.N * depth * per_frame)
+        else:
+            depth, ring, final_stack = 0, None, None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.mw_set_frame_stack(self.h, int(depth), int(pad), ptr(ring), ptr(final_stack)), "mw_set_frame_stack")
+        self._stack_bufs = (ring, final_stack) if depth else None
+
+    def stack_refresh(self, obs):
+        """The reset path of the frame stack: after reset(mask) and render(obs), rebuilds the stacks of the envs that were reset (or
+        never pushed) from their rows of `obs`; the others and the ring position stay (mw_stack_refresh)."""
+        self._check(self.lib.mw_stack_refresh(self.h, C.c_void_p(obs.data_ptr()), _stream_ptr(self.device)), "mw_stack_refresh")
+
+    def stack_window(self):
+        """(first_slot, pushes): every env's ordered stack is ring[:, first_slot : first_slot + depth]; host values, no sync."""
+        first, pushes = C.c_int32(), C.c_int64()
+        self._check(self.lib.mw_stack_window(self.h, C.byref(first), C.byref(pushes)), "mw_stack_window")
+        return first.value, pushes.value
 
     def render(self, obs, depth=None):
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())

@@ -57,7 +57,8 @@ _KIND = {
 class MiniWorldVecEnv:
     def __init__(self, env_id: str, num_envs: int, device_id: int = 0, domain_rand: bool = False,
                  want_depth: bool = False, seed: int = 0, autoreset: bool | str = True, obs_layout: str = "hwc",
-                 rng: str = "auto", msaa: int = 8, final_obs: bool = False, frame_reuse: bool = True, **env_kwargs):
+                 rng: str = "auto", msaa: int = 8, final_obs: bool = False, frame_reuse: bool = True,
+                 frame_stack: int | None = None, stack_pad: str = "reset", **env_kwargs):
         """obs_layout: "hwc" uint8[N,H,W,3] (the env's observation), "cwh" uint8[N,3,W,H]
         (PyTorchObsWrapper, wrappers.py:24) or "grey" float64[N,H,W,1] (GreyscaleWrapper, wrappers.py:44):
         the raster kernel stores the frame in that layout, there is no extra pass.
@@ -76,9 +77,21 @@ class MiniWorldVecEnv:
         its rows of `self.obs` / `self.depth` already hold that frame.  This env owns those tensors and passes them on every
         step, so it is on by default — TREAT THE RETURNED TENSORS AS READ-ONLY between steps (copy before normalising in
         place).  False, or MW_FRAME_REUSE=0 in the environment, draws every env on every step; `self.frame_reuse` tells which
-        is in effect.  Results are bit for bit the same either way."""
+        is in effect.  Results are bit for bit the same either way.
+        frame_stack=K (2 .. engine.MAX_STACK): the engine keeps every env's last K returned frames (Gymnasium's
+        FrameStackObservation, SB3's VecFrameStack); `self.stack` is the ordered view [N, K, *obs.shape[1:]], oldest first, and with
+        final_obs `self.final_stack` holds, for the envs whose episode ended in a step, the old stack with the terminal frame
+        appended.  stack_pad: what a new episode's stack starts from, "reset" (K copies of its first frame) or "zero" (K - 1
+        all-zero frames, then the frame).  One push per step() call, whatever `repeat` is; reset() rebuilds every stack."""
         import torch
         self.torch = torch
+        if frame_stack is not None and (not isinstance(frame_stack, (int, np.integer)) or isinstance(frame_stack, bool)
+                                        or not 2 <= frame_stack <= eng.MAX_STACK):
+            raise ValueError(f"frame_stack must be an integer in 2 .. {eng.MAX_STACK} (or None), not {frame_stack!r}")
+        if stack_pad not in ("reset", "zero"):
+            raise ValueError(f"stack_pad must be 'reset' or 'zero', not {stack_pad!r}")
+        self.frame_stack = None if frame_stack is None else int(frame_stack)
+        self.stack_pad = stack_pad
         modes = {True: "same_step", False: "off", "same_step": "same_step", "next_step": "next_step"}
         if not isinstance(autoreset, (bool, str)) or autoreset not in modes:
             raise ValueError(f"autoreset must be True, False, 'same_step' or 'next_step', not {autoreset!r}")
@@ -235,6 +248,13 @@ class MiniWorldVecEnv:
             self.final_depth = torch.zeros_like(self.depth) if want_depth else None
             self.engine.set_final_obs(self.final_obs, self.final_depth)
         self.frame_reuse = self.engine.set_frame_reuse(frame_reuse)
+        self._ring = self.final_stack = None
+        if self.frame_stack:
+            K, frame = self.frame_stack, tuple(self.obs.shape[1:])
+            self._ring = torch.zeros((num_envs, 2 * K - 1) + frame, dtype=self.obs.dtype, device=dev)
+            if final_obs:
+                self.final_stack = torch.zeros((num_envs, K) + frame, dtype=self.obs.dtype, device=dev)
+            self.engine.set_frame_stack(K, {"reset": eng.STACK_PAD_RESET, "zero": eng.STACK_PAD_ZERO}[stack_pad], self._ring, self.final_stack)
         self._host_envs = None
         self._next_seed = seed
         # what the env's step() reports in `info` beside the observation (collecthealth.py:100, tmaze.py:89, ymaze.py:125)
@@ -298,14 +318,27 @@ class MiniWorldVecEnv:
         self._next_seed += self.num_envs
         self.engine.reset(None, seeds)
         self.engine.render(self.obs, self.depth)
+        if self.frame_stack:
+            self.engine.stack_refresh(self.obs)
         return self.obs
+
+    @property
+    def stack(self):
+        """[N, K, *obs.shape[1:]], oldest frame first: a VIEW of the engine's ring (no copy, no kernel), computed per access from
+        where the window lies — read-only and valid until the next step, like `self.obs`.  In the "cwh" layout
+        `stack.reshape(N, 3 * K, W, H)` is a view too (the channel-stacked input of a CNN).  None without frame_stack."""
+        if not self.frame_stack:
+            return None
+        first, _ = self.engine.stack_window()
+        return self._ring[:, first:first + self.frame_stack]
 
     def step(self, actions, repeat: int = 1):
         """actions: integer torch tensor [N] (converted to contiguous int32 on the engine's device if needed).
         repeat > 1 (action repeat, up to engine.MAX_REPEAT): every env takes up to `repeat` steps with its action in one kernel
         launch and stops at the one that ends its episode; the observation is the frame after the last of them (after the
         auto-reset, as for a single step), the reward their sum, the flags the last one's, and `self.substeps` (int32[N] on
-        the device) the number each env took — 0 for the reset step of autoreset="next_step".  max_episode_steps counts them."""
+        the device) the number each env took — 0 for the reset step of autoreset="next_step".  max_episode_steps counts them.
+        With frame_stack every call pushes its one frame; read `self.stack` afterwards."""
         if repeat == 1:
             self.engine.step(actions, self.obs, self.depth, self.reward, self.terminated, self.truncated)
             return self.obs, self.reward, self.terminated, self.truncated

@@ -49,16 +49,22 @@ class MiniWorldVectorEnv(VectorEnvBase):
     metadata = {"autoreset_mode": AUTORESET_SAME_STEP, "render_modes": ["rgb_array"]}
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
-                 frame_reuse: bool = True, action_repeat: int = 1, **kwargs):
+                 frame_reuse: bool = True, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset", **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
         False draws every env on every step, for consumers that write into the returned observation tensor (module docstring).
         action_repeat > 1: every step() holds the action for up to that many env steps (MiniWorldVecEnv.step's `repeat`) and
-        info["substeps"] (int32[N]) tells how many each env took."""
+        info["substeps"] (int32[N]) tells how many each env took.
+        frame_stack=K, stack_pad: observations (and the observation spaces) become the stacks of the last K frames, oldest first
+        (MiniWorldVecEnv's frame_stack: Gymnasium's FrameStackObservation / SB3's VecFrameStack on the device) — the engine's
+        view, read-only until the next step, or a host copy with to_numpy; with final_obs, info["final_obs"] holds the final
+        stacks (the old stack with the terminal frame appended)."""
         if not isinstance(action_repeat, (int, np.integer)) or not 1 <= action_repeat <= 256:
             raise ValueError(f"action_repeat must be an integer in 1 .. 256, not {action_repeat!r}")
         self.action_repeat = int(action_repeat)
         kwargs["frame_reuse"] = frame_reuse
+        if frame_stack is not None:
+            kwargs["frame_stack"], kwargs["stack_pad"] = frame_stack, stack_pad
         mode = str(getattr(autoreset_mode, "name", autoreset_mode)).lower().replace("_", "-")     # (an AutoresetMode: its name)
         if mode not in ("same-step", "next-step"):
             raise ValueError(f"autoreset_mode must be 'same-step' or 'next-step', not {autoreset_mode!r}")
@@ -75,6 +81,8 @@ class MiniWorldVectorEnv(VectorEnvBase):
         self.num_envs = num_envs
         self.to_numpy = to_numpy
         shape, dtype = tuple(self.vec.obs.shape[1:]), {"grey": np.float64}.get(self.vec.obs_layout, np.uint8)
+        if self.vec.frame_stack:
+            shape = (self.vec.frame_stack,) + shape
         self.single_observation_space = spaces.Box(0, 255, shape, dtype=dtype)
         self.observation_space = spaces.Box(0, 255, (num_envs,) + shape, dtype=dtype)
         self.single_action_space = spaces.Discrete(self.vec.n_actions)
@@ -85,6 +93,9 @@ class MiniWorldVectorEnv(VectorEnvBase):
     def _out(self, t):
         return t.cpu().numpy() if self.to_numpy else t
 
+    def _obs(self, obs):
+        return self.vec.stack if self.vec.frame_stack else obs
+
     def _infos(self):
         """gymnasium's batched info convention: one array per key (health / goal_pos: MiniWorldVecEnv.infos)."""
         return {k: self._out(v) for k, v in self.vec.infos().items()}
@@ -92,7 +103,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
     def reset(self, *, seed: int | None = None, options: dict | None = None):
         """Env i is seeded with seed + i (gymnasium's convention for an integer seed)."""
         obs = self.vec.reset(seed)
-        return self._out(obs), {}
+        return self._out(self._obs(obs)), {}
 
     def step(self, actions):
         torch = self.vec.torch
@@ -110,13 +121,14 @@ class MiniWorldVectorEnv(VectorEnvBase):
             done = self._out((term | trunc).bool())
             info["_final_info"] = done
             if self.vec.final_obs is not None:
-                info["final_obs"] = self._out(self.vec.final_obs) if self.to_numpy else self.vec.final_obs.clone()
+                final = self.vec.final_stack if self.vec.frame_stack else self.vec.final_obs
+                info["final_obs"] = self._out(final) if self.to_numpy else final.clone()
                 info["_final_obs"] = done
             if info.keys() - {"_final_info"}:
                 final = {k: (self._out(v) if self.to_numpy else v.clone()) for k, v in self.vec.final_infos().items()}
                 final.update({"_" + k: done for k in list(final)})
                 info["final_info"] = final
-        return self._out(obs), self._out(rew), self._out(term.bool()), self._out(trunc.bool()), info
+        return self._out(self._obs(obs)), self._out(rew), self._out(term.bool()), self._out(trunc.bool()), info
 
     def render(self):
         """Tuple-free batched render: the map view of every env (uint8[N, H, W, 3])."""
