@@ -444,7 +444,44 @@ int mw_render_view(mw_engine *e, int32_t env, int32_t view_flags, int32_t width,
  * empty slots report 0.  Needs obs_width * obs_height * 32 bytes of LDS (<= 160 KiB).  Not the hot path. */
 int mw_visible_ents(mw_engine *e, int32_t first_env, int32_t count, uint8_t *d_vis, void *stream);
 
-/* checks the device-side status word (capacity overflows); synchronises `stream` */
+/* ---- snapshots: save, restore and fork environments on the device ------------------------------------------------
+ * The reference keeps an env's state in Python attributes and its stream in env.np_random; copy.deepcopy(env) is how a user of
+ * it checkpoints or branches one env.  These three calls do that for the batched engine, on the device: a RECORD is the complete
+ * state of one env, a caller-owned device buffer holds `capacity` of them, and a restored or forked env continues exactly — bit for
+ * bit, random stream included — as the env the record was taken from would have.
+ *   record      everything that decides the env's future and is not configuration: agent pose, cam, light, extent, carry, step,
+ *               picked, health, final_health, final_goal (mw_get_final_info), the entity slabs, the random stream (all five words),
+ *               the pending removal (none, a slot, or "applied"), a pending next-step reset; with per-env geometry sets
+ *               (shared_geometry = 0) the env's polygons and segments; in spare mode (a pre-generated next world per env) the whole
+ *               spare world and its state word — the live stream has already moved past the spare's draws.
+ *   NOT in it   textures, meshes, the placement program and the shared geometry set (configuration); the mw_set_step_params
+ *               override; rendered frames and the frame-stack ring; all per-frame scratch.
+ *   the buffer  opaque.  It starts with a header that carries a layout key — a format number, max_ents, max_polys, max_segs,
+ *               shared_geometry, task, generator, rng_mode, spares on / off, capacity — and is compatible between engines of the
+ *               same configuration in one process, whatever their num_envs.  It must be 16-byte aligned.
+ * d_envs and d_recs are DEVICE arrays (a planner picks on the device which state to branch from); both calls are asynchronous on
+ * `stream` and one kernel launch each.  They wait, on `stream` (an event: the host does not block), for the spare-world refills the
+ * Maze's steps leave running on the engine's side stream.
+ * Errors.  MW_E_INVALID before anything is launched: a null engine or buffer, a misaligned buffer, count < 0, count > capacity,
+ * count > num_envs on a load or on a save with d_envs == NULL, n_recs > capacity.  On the device every env and record index is
+ * tested against its limit and a load compares the header's key: an offending item is skipped — it writes nothing — and sets a bit
+ * of the status word that mw_check reports as MW_E_INVALID. */
+/* bytes of a caller-owned device buffer that holds `capacity` records of this engine (host value, no sync; < 0 on error) */
+int64_t mw_snapshot_bytes(const mw_engine *e, int32_t capacity);
+/* record k (k < count <= capacity) := the complete state of env d_envs[k]; d_envs == NULL: env k, count <= num_envs.  Writes the header.
+ * Changes nothing in the engine. */
+int mw_snapshot_save(mw_engine *e, const int32_t *d_envs, int32_t count, uint8_t *d_snap, int32_t capacity, void *stream);
+/* env d_envs[k] := record d_recs[k] of a buffer whose first n_recs records are valid.  d_envs == NULL: env k.  d_recs == NULL: record k.
+ * The target envs must be distinct (caller's contract); records may repeat (that is a fork).
+ * Like mw_set_state it drops the frame that frame reuse holds; for every env it writes it clears the frame-clean byte, invalidates
+ * the occlusion cache of the env's geometry set and, with a frame stack, marks the env like mw_reset does: mw_stack_refresh or its next
+ * push rebuilds its stack.  d_obs is stale afterwards — the host sequence is the reset path's: mw_snapshot_load, mw_render, then
+ * mw_stack_refresh if a stack is set.  A record taken with a pending next-step reset restores an env whose next step installs its
+ * next world; a record whose spare was consumed restores an env whose spare the next step's refill regenerates. */
+int mw_snapshot_load(mw_engine *e, const int32_t *d_envs, const int32_t *d_recs, int32_t count,
+                     const uint8_t *d_snap, int32_t n_recs, int32_t capacity, void *stream);
+
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 
 /* ---- measurement ------------------------------------------------------------- */

@@ -54,6 +54,7 @@
 // status bits written by kernels, read by mw_check()
 #define MW_ST_VIS_OVERFLOW 1u
 #define MW_ST_PLACEMENT_FAIL 2u
+#define MW_ST_SNAPSHOT_BAD 4u       // mw_snapshot_save / mw_snapshot_load skipped an item: env or record index out of range, or a buffer of another layout key
 
 // Generator tables; kept in device memory because dynamic indexing into a by-value kernarg
 // struct would force a private (scratch) copy of the whole argument block.

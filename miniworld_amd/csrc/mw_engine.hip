@@ -198,6 +198,13 @@ struct mw_engine {
         int64_t pushes = 0;
         uint8_t *flags = nullptr;
     } stack;
+    // mw_snapshot_*: what of the configuration shapes a record, the layout that follows from it (mw_snapshot.h), the copy kernels'
+    // table of the engine's arrays, and the event that orders a call behind the side stream's refills
+    MwSnapConfig snap_cfg{};
+    MwSnapLayout snap_layout{};
+    MwSnapTable *d_snap_tab = nullptr;
+    int snap_chunks_per_item = 0;       // blob workgroups per item: geometry sets x (polygon chunks + segment chunks), as in the table
+    Event ev_refill_done;
 };
 
 namespace {
@@ -1063,7 +1070,89 @@ int init_engine(mw_engine *e, const mw_config *cfg)
         const int lds = mw_rasterq_lds_bytes(S, a.W, a.H, a.n_tiles, 1);
         e->k2q_ok = (cfg->msaa == 8 || cfg->msaa == 4) && frame_on_grid(a.W, a.H) && a.W <= 128 && a.H <= 128 && a.W * a.H <= 8192 && lds <= 64 * 1024;
     }
+    {
+        // snapshot records: the components this engine has, each with its array and its place in a record (mw_snapshot.h)
+        e->snap_cfg = {E, cfg->max_polys, cfg->max_segs, cfg->shared_geometry ? 1 : 0, cfg->task, cfg->generator, cfg->rng_mode, e->spare_mode ? 1 : 0,
+                       cfg->task == MW_TASK_COLLECT ? 1 : 0};
+        const MwSnapLayout &L = e->snap_layout = mw_snap_layout(e->snap_cfg);
+        void *arr[MW_SC_COUNT] = {};
+        arr[MW_SC_AX] = a.ax; arr[MW_SC_AY] = a.ay; arr[MW_SC_AZ] = a.az; arr[MW_SC_ADIR] = a.adir; arr[MW_SC_CAM] = a.cam; arr[MW_SC_LIGHT] = a.light;
+        arr[MW_SC_EXTENT] = a.extent; arr[MW_SC_CARRY] = a.carry; arr[MW_SC_STEP] = a.step; arr[MW_SC_PICKED] = a.picked; arr[MW_SC_HEALTH] = a.health;
+        arr[MW_SC_FINAL_HEALTH] = a.final_health; arr[MW_SC_FINAL_GOAL] = a.final_goal; arr[MW_SC_EKIND] = a.ekind; arr[MW_SC_EMESH] = a.emesh;
+        arr[MW_SC_ESTATIC] = a.estatic; arr[MW_SC_EPOS] = a.epos; arr[MW_SC_EDIR] = a.edir; arr[MW_SC_EGEOM] = a.egeom; arr[MW_SC_RNG] = a.rng;
+        arr[MW_SC_PENDING_REMOVE] = a.pending_remove; arr[MW_SC_RESET_PENDING] = a.reset_pending;
+        arr[MW_SC_NPOLYS] = const_cast<int32_t *>(a.npolys); arr[MW_SC_NSEGS] = const_cast<int32_t *>(a.nsegs);
+        arr[MW_SC_SP_AX] = sp.ax; arr[MW_SC_SP_AY] = sp.ay; arr[MW_SC_SP_AZ] = sp.az; arr[MW_SC_SP_ADIR] = sp.adir; arr[MW_SC_SP_CAM] = sp.cam;
+        arr[MW_SC_SP_LIGHT] = sp.light; arr[MW_SC_SP_EXTENT] = sp.extent; arr[MW_SC_SP_EKIND] = sp.ekind; arr[MW_SC_SP_EMESH] = sp.emesh;
+        arr[MW_SC_SP_ESTATIC] = sp.estatic; arr[MW_SC_SP_EPOS] = sp.epos; arr[MW_SC_SP_EDIR] = sp.edir; arr[MW_SC_SP_EGEOM] = sp.egeom;
+        arr[MW_SC_SP_NPOLYS] = sp.npolys; arr[MW_SC_SP_NSEGS] = sp.nsegs; arr[MW_SC_REFILL_MASK] = a.refill_mask;
+        MwSnapTable t{};
+        for (int id = 0; id < MW_SC_COUNT; ++id) {
+            if (!L.comp_rows[id]) continue;
+            if (!arr[id]) return fail(e, MW_E_INVALID, "snapshot layout: component %d has rows but no array", id);
+            t.comp[t.n_comps++] = {arr[id], L.comp_unit[id], L.comp_row0[id], L.comp_rows[id], L.comp_elem[id], 0};
+        }
+        t.total_rows = L.total_rows; t.n_geo = L.n_geo; t.max_polys = cfg->max_polys; t.max_segs = cfg->max_segs;
+        const int chunk = MW_SNAP_THREADS * MW_SNAP_UNROLL;
+        t.poly_chunks = (cfg->max_polys * (MW_SNAP_POLY_BYTES / 16) + chunk - 1) / chunk;
+        t.seg_chunks = (cfg->max_segs * (MW_SNAP_SEG_BYTES / 16) + chunk - 1) / chunk;
+        t.eng_polys[0] = const_cast<mw_poly *>(a.polys); t.eng_segs[0] = const_cast<double *>(a.segs);
+        t.eng_npolys[0] = const_cast<int32_t *>(a.npolys); t.eng_nsegs[0] = const_cast<int32_t *>(a.nsegs);
+        t.eng_polys[1] = sp.polys; t.eng_segs[1] = sp.segs; t.eng_npolys[1] = sp.npolys; t.eng_nsegs[1] = sp.nsegs;
+        t.polys_unit[0] = L.blob_unit[MW_SB_POLYS]; t.segs_unit[0] = L.blob_unit[MW_SB_SEGS];
+        t.polys_unit[1] = L.blob_unit[MW_SB_SP_POLYS]; t.segs_unit[1] = L.blob_unit[MW_SB_SP_SEGS];
+        t.npolys_unit[0] = L.comp_unit[MW_SC_NPOLYS]; t.nsegs_unit[0] = L.comp_unit[MW_SC_NSEGS];
+        t.npolys_unit[1] = L.comp_unit[MW_SC_SP_NPOLYS]; t.nsegs_unit[1] = L.comp_unit[MW_SC_SP_NSEGS];
+        t.reset_pending_unit = L.comp_unit[MW_SC_RESET_PENDING];
+        e->snap_chunks_per_item = t.n_geo * (t.poly_chunks + t.seg_chunks);
+        {
+            std::vector<uint16_t> row_comp((size_t)t.total_rows);
+            for (int c = 0; c < t.n_comps; ++c)
+                for (int r = 0; r < t.comp[c].rows; ++r) row_comp[(size_t)t.comp[c].row0 + r] = (uint16_t)c;
+            uint16_t *d_row_comp = nullptr;
+            if (const int rc = fixed_alloc(e, &d_row_comp, row_comp.size())) return rc;
+            HIP_TRY(e, hipMemcpy(d_row_comp, row_comp.data(), row_comp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            t.row_comp = d_row_comp;
+        }
+        if (const int rc = fixed_alloc(e, &e->d_snap_tab, 1)) return rc;
+        HIP_TRY(e, hipMemcpy(e->d_snap_tab, &t, sizeof t, hipMemcpyHostToDevice));
+    }
     return sync_gen_args(e);
+}
+
+// mw_snapshot_save / mw_snapshot_load touch worlds that the Maze's refill kernel may still be writing on the side stream (spares and
+// their refill_mask words, read behind the live stream).  The caller's stream waits for an event recorded behind those refills:
+// the host does not block — a fork loop stays asynchronous, which ON_DEVICE_SYNC would not be — and everything the engine enqueues
+// later on the side stream is ordered behind the caller's stream by launch_side_refill's own event.  The other refills are blocks
+// of the step kernel itself, in stream order.  So between launches refill_mask is 0 or 1 (mw_snapshot.hip).
+int snapshot_order(mw_engine *e, hipStream_t st)
+{
+    if (!e->side_refill_pending || !e->side_stream) return MW_OK;
+    if (!e->ev_refill_done) HIP_TRY(e, make_event(e->ev_refill_done));
+    HIP_TRY(e, hipEventRecord(e->ev_refill_done.get(), e->side_stream.get()));
+    HIP_TRY(e, hipStreamWaitEvent(st, e->ev_refill_done.get(), 0));
+    return MW_OK;
+}
+
+// the arguments both calls share, checked before anything is launched
+int snapshot_args(mw_engine *e, const char *what, const void *d_snap, int32_t count, int32_t capacity, bool whole_batch_limit)
+{
+    if (!d_snap) return fail(e, MW_E_INVALID, "%s: the record buffer is null", what);
+    if ((uintptr_t)d_snap & 15u) return fail(e, MW_E_INVALID, "%s: the record buffer is not 16-byte aligned", what);
+    if (capacity < 0) return fail(e, MW_E_INVALID, "%s: capacity %d < 0", what, (int)capacity);
+    if (count < 0 || count > capacity) return fail(e, MW_E_INVALID, "%s: count %d outside 0 .. capacity %d", what, (int)count, (int)capacity);
+    if (whole_batch_limit && count > e->cfg.num_envs) return fail(e, MW_E_INVALID, "%s: count %d > num_envs %d", what, (int)count, e->cfg.num_envs);
+    return MW_OK;
+}
+
+// the grid of a call over `count` items: component blocks, then blob blocks (mw_snapshot.hip); MW_E_INVALID past the 1-D grid limit
+int snapshot_grid(mw_engine *e, const char *what, int count, int *item_chunks, unsigned *grid)
+{
+    *item_chunks = (count + MW_SNAP_THREADS - 1) / MW_SNAP_THREADS;
+    const long long blocks = (long long)*item_chunks * e->snap_layout.total_rows + (long long)count * e->snap_chunks_per_item;
+    if (blocks > 0x7FFFFFFFll) return fail(e, MW_E_INVALID, "%s: %d items need %lld workgroups, more than one launch holds: split the call", what, count, blocks);
+    *grid = (unsigned)std::max<long long>(blocks, 1);
+    return MW_OK;
 }
 
 }  // namespace
@@ -1565,6 +1654,48 @@ int mw_visible_ents(mw_engine *e, int32_t first_env, int32_t count, uint8_t *d_v
     return MW_OK;
 }
 
+int64_t mw_snapshot_bytes(const mw_engine *e, int32_t capacity)
+{
+    if (!e || capacity < 0) return MW_E_INVALID;
+    return mw_snap_bytes(e->snap_layout, capacity);
+}
+
+int mw_snapshot_save(mw_engine *e, const int32_t *d_envs, int32_t count, uint8_t *d_snap, int32_t capacity, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (const int rc = snapshot_args(e, "mw_snapshot_save", d_snap, count, capacity, d_envs == nullptr)) return rc;
+    ON_DEVICE(e);
+    hipStream_t st = (hipStream_t)stream;
+    int item_chunks = 0;
+    unsigned grid = 1;
+    if (const int rc = snapshot_grid(e, "mw_snapshot_save", count, &item_chunks, &grid)) return rc;
+    if (const int rc = snapshot_order(e, st)) return rc;
+    hipLaunchKernelGGL(mw_snapshot_save_kernel, dim3(grid), dim3(MW_SNAP_THREADS), 0, st, (const MwSnapTable *)e->d_snap_tab, mw_snap_key(e->snap_cfg, capacity),
+                       e->cfg.num_envs, (int)capacity, (int)count, item_chunks, d_envs, e->args.status, d_snap);
+    HIP_TRY(e, hipGetLastError());
+    return MW_OK;
+}
+
+int mw_snapshot_load(mw_engine *e, const int32_t *d_envs, const int32_t *d_recs, int32_t count, const uint8_t *d_snap, int32_t n_recs,
+                     int32_t capacity, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (const int rc = snapshot_args(e, "mw_snapshot_load", d_snap, count, capacity, true)) return rc;
+    if (n_recs < 0 || n_recs > capacity) return fail(e, MW_E_INVALID, "mw_snapshot_load: n_recs %d outside 0 .. capacity %d", (int)n_recs, (int)capacity);
+    ON_DEVICE(e);
+    hipStream_t st = (hipStream_t)stream;
+    int item_chunks = 0;
+    unsigned grid = 1;
+    if (const int rc = snapshot_grid(e, "mw_snapshot_load", count, &item_chunks, &grid)) return rc;
+    if (const int rc = snapshot_order(e, st)) return rc;
+    drop_held_frame(e);     // (the frames in the caller's buffers are those of the states that are about to go)
+    hipLaunchKernelGGL(mw_snapshot_load_kernel, dim3(grid), dim3(MW_SNAP_THREADS), 0, st, (const MwSnapTable *)e->d_snap_tab, mw_snap_key(e->snap_cfg, capacity),
+                       e->cfg.num_envs, (int)capacity, (int)count, item_chunks, d_envs, e->args.status, d_snap, d_recs, (int)n_recs, e->args.frame_clean,
+                       e->cfg.shared_geometry ? nullptr : e->args.occ_valid, e->stack.depth ? stack_flags(e, e->stack.cur) : nullptr);
+    HIP_TRY(e, hipGetLastError());
+    return MW_OK;
+}
+
 int mw_check(mw_engine *e, void *stream)
 {
     if (!e) return MW_E_INVALID;
@@ -1574,6 +1705,8 @@ int mw_check(mw_engine *e, void *stream)
     HIP_TRY(e, hipMemcpy(&st, e->args.status, 4, hipMemcpyDeviceToHost));
     if (st & MW_ST_VIS_OVERFLOW) return fail(e, MW_E_OVERFLOW, "more than max_visible=%d visible primitives in some env", e->cfg.max_visible);
     if (st & MW_ST_PLACEMENT_FAIL) return fail(e, MW_E_OVERFLOW, "device-side placement did not converge in some env");
+    if (st & MW_ST_SNAPSHOT_BAD)
+        return fail(e, MW_E_INVALID, "mw_snapshot_save / mw_snapshot_load skipped an item: an env or record index out of range, or a record buffer of another layout (key mismatch)");
     return MW_OK;
 }
 

@@ -3,6 +3,7 @@
 // not compile.
 #pragma once
 #include "mw_device.h"
+#include "mw_snapshot.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine.hip)
@@ -134,6 +135,19 @@ extern "C" __global__ void mw_stack_push_kernel(MW_STACK_ARGS, const uint8_t *__
                                                 uint8_t *__restrict__ final_stack);
 extern "C" __global__ void mw_stack_refresh_kernel(MW_STACK_ARGS);
 extern "C" __global__ void mw_stack_mark_kernel(int N, const uint8_t *__restrict__ mask, int force_all, uint8_t *__restrict__ flags);
+
+// snapshot records (mw_snapshot.hip; the layout: mw_snapshot.h): one launch per save, one per load.  A 1-D grid of MW_SNAP_THREADS
+// lanes: first the component blocks — (row of a component, 256 consecutive items), a lane per item —, then, with per-env geometry
+// sets, the blob blocks — (item, geometry set, chunk of its polygons or segments), 16-byte units.  Item k is (env d_envs[k] or k,
+// record d_recs[k] or k); every index is tested against its limit, an offending item is skipped and sets MW_ST_SNAPSHOT_BAD.
+#define MW_SNAP_ARGS \
+    const MwSnapTable *__restrict__ tab, MwSnapKey key, int N, int capacity, int count, int item_chunks, const int32_t *__restrict__ d_envs, \
+    uint32_t *__restrict__ status
+extern "C" __global__ void mw_snapshot_save_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap);
+//   n_recs               the records of the buffer that are valid
+//   frame_clean, occ_valid, stack_flags  what a load resets for every env it writes (the last two may be null)
+extern "C" __global__ void mw_snapshot_load_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap, const int32_t *__restrict__ d_recs, int n_recs,
+                                                   uint8_t *__restrict__ frame_clean, int32_t *__restrict__ occ_valid, uint8_t *__restrict__ stack_flags);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -41,6 +41,7 @@ EXPORTS = [
     "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
     "mw_selftest_sincosf",
     "mw_set_frame_stack", "mw_stack_refresh", "mw_stack_window",
+    "mw_snapshot_bytes", "mw_snapshot_save", "mw_snapshot_load",
 ]
 
 
@@ -193,6 +194,10 @@ def load_library():
     L.mw_set_frame_stack.argtypes = [vp, i32, i32, vp, vp]
     L.mw_stack_refresh.argtypes = [vp, vp, vp]
     L.mw_stack_window.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_int64)]
+    L.mw_snapshot_bytes.argtypes = [vp, i32]
+    L.mw_snapshot_bytes.restype = C.c_int64
+    L.mw_snapshot_save.argtypes = [vp, vp, i32, vp, i32, vp]
+    L.mw_snapshot_load.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp]
     L.mw_pcg64_draws.argtypes = [C.c_uint64, i32, vp, vp]
     L.mw_check.argtypes = [vp, vp]
     L.mw_kernel_time_ms.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -427,6 +432,59 @@ class Engine:
         first, pushes = C.c_int32(), C.c_int64()
         self._check(self.lib.mw_stack_window(self.h, C.byref(first), C.byref(pushes)), "mw_stack_window")
         return first.value, pushes.value
+
+    # -- snapshots ---------------------------------------------------------------------
+    def snapshot_bytes(self, capacity: int) -> int:
+        """Bytes of a device buffer that holds `capacity` records of this engine (include/mwengine.h: mw_snapshot_bytes)."""
+        n = int(self.lib.mw_snapshot_bytes(self.h, int(capacity)))
+        if n < 0:
+            raise EngineError(f"mw_snapshot_bytes failed ({n}): capacity {capacity!r}")
+        return n
+
+    def _index_tensor(self, t, name, count=None):
+        """An index array of a snapshot call: None, or made a contiguous int32 tensor on the engine's device."""
+        import torch
+        if t is None:
+            return None
+        t = torch.as_tensor(t)
+        if t.device != self.device or t.dtype != torch.int32 or not t.is_contiguous():
+            t = t.to(device=self.device, dtype=torch.int32).contiguous()
+        if t.dim() != 1 or (count is not None and t.numel() != count):
+            raise EngineError(f"{name}: need a 1-D index tensor" + (f" of {count} elements" if count is not None else "") + f", got shape {tuple(t.shape)}")
+        return t
+
+    def _snapshot_buffer(self, buf, capacity):
+        import torch
+        need = self.snapshot_bytes(capacity)
+        if buf.device != self.device or buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.numel() < need:
+            raise EngineError(f"snapshot buffer: need a contiguous uint8 tensor of at least {need} bytes on {self.device} for {capacity} records, got "
+                              f"{buf.dtype} {tuple(buf.shape)} on {buf.device}")
+
+    def snapshot_save(self, buf, capacity: int, envs=None, count: int | None = None):
+        """Record k of `buf` := the complete state of env envs[k] (envs=None: env k, for k < count, default all envs); `buf` is a
+        uint8 device tensor of snapshot_bytes(capacity) bytes.  Asynchronous on the current stream, one kernel; returns the number
+        of records written (mw_snapshot_save)."""
+        envs = self._index_tensor(envs, "envs")
+        count = (self.N if envs is None else envs.numel()) if count is None else int(count)
+        self._snapshot_buffer(buf, capacity)
+        self._check(self.lib.mw_snapshot_save(self.h, None if envs is None else C.c_void_p(envs.data_ptr()), count, C.c_void_p(buf.data_ptr()),
+                                              int(capacity), _stream_ptr(self.device)), "mw_snapshot_save")
+        return count
+
+    def snapshot_load(self, buf, n_recs: int, capacity: int, envs=None, records=None, count: int | None = None):
+        """Env envs[k] := record records[k] of `buf`, whose first n_recs records are valid (envs=None: env k; records=None: record
+        k).  The target envs must be distinct; records may repeat — a fork.  The observation buffers are stale afterwards: render(),
+        then stack_refresh() with a frame stack (mw_snapshot_load).  Asynchronous on the current stream, one kernel."""
+        envs, records = self._index_tensor(envs, "envs"), self._index_tensor(records, "records")
+        if count is None:
+            count = envs.numel() if envs is not None else records.numel() if records is not None else min(int(n_recs), self.N)
+        for t, name in ((envs, "envs"), (records, "records")):
+            if t is not None and t.numel() != count:
+                raise EngineError(f"{name}: {t.numel()} indices for {count} items")
+        self._snapshot_buffer(buf, capacity)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.mw_snapshot_load(self.h, ptr(envs), ptr(records), int(count), C.c_void_p(buf.data_ptr()), int(n_recs), int(capacity),
+                                              _stream_ptr(self.device)), "mw_snapshot_load")
 
     def render(self, obs, depth=None):
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())

@@ -54,6 +54,35 @@ _KIND = {
 }
 
 
+class EnvSnapshot:
+    """Records of MiniWorldVecEnv.save_state(): `data`, the engine's opaque uint8 record buffer (a torch tensor; its header carries
+    the layout key of the configuration it was taken under), `count`, the valid records, and `capacity`, the records the buffer was
+    laid out for.  `.cpu()` / `.to(device)` move it, so `torch.save(snap.cpu().state_dict(), path)` and
+    `EnvSnapshot.from_state_dict(torch.load(path))` write a checkpoint and read it back."""
+
+    def __init__(self, data, count: int, capacity: int):
+        self.data, self.count, self.capacity = data, int(count), int(capacity)
+
+    def to(self, device):
+        return EnvSnapshot(self.data.to(device), self.count, self.capacity)
+
+    def cpu(self):
+        return self.to("cpu")
+
+    def clone(self):
+        return EnvSnapshot(self.data.clone(), self.count, self.capacity)
+
+    def state_dict(self):
+        return {"data": self.data, "count": self.count, "capacity": self.capacity}
+
+    @classmethod
+    def from_state_dict(cls, d):
+        return cls(d["data"], d["count"], d["capacity"])
+
+    def __len__(self):
+        return self.count
+
+
 class MiniWorldVecEnv:
     def __init__(self, env_id: str, num_envs: int, device_id: int = 0, domain_rand: bool = False,
                  want_depth: bool = False, seed: int = 0, autoreset: bool | str = True, obs_layout: str = "hwc",
@@ -263,6 +292,7 @@ class MiniWorldVecEnv:
         self._info_slot = int(cfg.goal_ent)
         self._info_buf = None
         self._final_info_buf = None
+        self._fork_buf = None           # fork()'s scratch records, made on first use
 
     # ------------------------------------------------------------------ assets / worlds
     def _upload_assets(self, sc):
@@ -346,6 +376,54 @@ class MiniWorldVecEnv:
             self.substeps = self.torch.zeros(self.num_envs, dtype=self.torch.int32, device=self.engine.device)
         self.engine.step_repeat(actions, repeat, self.obs, self.depth, self.reward, self.terminated, self.truncated, self.substeps)
         return self.obs, self.reward, self.terminated, self.truncated
+
+    # ------------------------------------------------------------------ save / restore / fork
+    def save_state(self, envs=None, capacity: int | None = None):
+        """The complete state of the envs `envs` (an integer sequence or tensor; None: all of them, in order) as an EnvSnapshot on
+        the device: everything that decides their future — poses, entities, step counts, the random stream, pending removals and
+        resets, the Maze's own geometry, the pre-generated next world — but no frames (include/mwengine.h: mw_snapshot_save).  One
+        kernel on the current stream; nothing in this env changes.
+        capacity: the records the buffer is laid out for (default: the number saved).  One load_state call moves at most that many
+        envs, so a snapshot of ONE state that is to be loaded into many envs at once ("reset all of them to this cell") is taken
+        with capacity=num_envs: `vec.load_state(vec.save_state([i], capacity=n), records=torch.zeros(n, dtype=torch.int32))`."""
+        torch = self.torch
+        envs = None if envs is None else torch.as_tensor(envs)
+        count = self.num_envs if envs is None else int(envs.numel())
+        capacity = count if capacity is None else int(capacity)
+        if capacity < count:
+            raise ValueError(f"capacity {capacity} < the {count} records to save")
+        data = torch.zeros(self.engine.snapshot_bytes(capacity), dtype=torch.uint8, device=self.engine.device)
+        self.engine.snapshot_save(data, capacity, envs)
+        return EnvSnapshot(data, count, capacity)
+
+    def load_state(self, snap, envs=None, records=None):
+        """Env envs[k] becomes record records[k] of `snap` (envs=None: env k; records=None: record k; the envs must be distinct,
+        records may repeat; one call moves at most `snap.capacity` envs) and continues bit for bit as the env the record was taken from would have — on this env or on another
+        one of the same configuration, whatever its num_envs.  Draws the new frames (and rebuilds the loaded envs' frame stacks as
+        reset() does) and returns `self.obs`; rewards and flags are left alone."""
+        data = snap.data
+        if data.device != self.engine.device:
+            data = data.to(self.engine.device)
+        self.engine.snapshot_load(data, snap.count, snap.capacity, envs, records)
+        return self._redraw()
+
+    def fork(self, src):
+        """src: integer tensor [N].  Env j becomes a copy of env src[j] (its stream included: copies given the same actions stay
+        identical) — a whole-batch save into scratch records of this env's own and a load through `src`, two kernels and a frame;
+        returns `self.obs`."""
+        eng_ = self.engine
+        if self._fork_buf is None:
+            self._fork_buf = self.torch.empty(eng_.snapshot_bytes(self.num_envs), dtype=self.torch.uint8, device=eng_.device)
+        src = eng_._index_tensor(src, "src", self.num_envs)
+        eng_.snapshot_save(self._fork_buf, self.num_envs)
+        eng_.snapshot_load(self._fork_buf, self.num_envs, self.num_envs, None, src)
+        return self._redraw()
+
+    def _redraw(self):
+        self.engine.render(self.obs, self.depth)
+        if self.frame_stack:
+            self.engine.stack_refresh(self.obs)
+        return self.obs
 
     def infos(self):
         """The batched `info` of the last step as device tensors: {"health": int32[N]} for CollectHealth (collecthealth.py:100),

@@ -1,0 +1,150 @@
+"""What saving, restoring and forking environments costs (mw_snapshot_save / mw_snapshot_load; MiniWorldVecEnv.save_state / load_state /
+fork), for Hallway x 4096, Maze x 1024 and PickupObjects (domain randomisation) x 2048.
+
+    python tools/perf/snapshot_cost.py                        # wall time per call, alternating windows, one JSON line per config
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o snap -- python tools/perf/snapshot_cost.py --profile maze --op fork
+                                                              # a run of its own, no counters: the two kernels' durations.  --op save_load:
+                                                              # whole-batch save and whole-batch load; --op fork: whole-batch save and a
+                                                              # load through a random index (the gather)
+    python tools/perf/snapshot_cost.py --bench <parent checkout>   # `python bench.py --windows 5` alternately in a built checkout of
+                                                              # the parent commit and in this tree
+
+Wall time: per config one env; the timed windows alternate between save_state(), load_state(snap), fork(random src), a render alone (what
+load_state and fork end with) and the only thing a user could do before: engine.get_state() + engine.set_state() through the host —
+which does NOT carry the random stream, the spare worlds, pending removals and resets, health, the kept final info or the Maze's
+geometry, so it is the price of less.  Every window is preceded and ended by a device synchronisation.  Reported beside them: the bytes
+of the records (the layout's; a save reads that much and writes it, a load the other way round); the profiled runs' kernel durations
+turn them into a rate (profiles/r10/README.md)."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+CONFIGS = {
+    "hallway": ("MiniWorld-Hallway-v0", 4096, 3, {}),
+    "maze": ("MiniWorld-Maze-v0", 1024, 3, {}),
+    "pickup_dr": ("MiniWorld-PickupObjects-v0", 2048, 5, {"domain_rand": True}),
+}
+
+
+def make(name):
+    import torch
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    env_id, n, n_act, kw = CONFIGS[name]
+    vec = MiniWorldVecEnv(env_id, n, seed=0, **kw)
+    vec.reset()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    return vec, n, n_act, g
+
+
+def profile(name, op, reps, warmup):
+    """the run a profiler wraps: untimed"""
+    import torch
+    vec, n, n_act, g = make(name)
+    for _ in range(warmup):
+        vec.step(torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32))
+    e = vec.engine
+    buf = torch.zeros(e.snapshot_bytes(n), dtype=torch.uint8, device="cuda")
+    src = torch.randint(0, n, (n,), generator=g, device="cuda", dtype=torch.int32)
+    for _ in range(reps):
+        e.snapshot_save(buf, n)
+        e.snapshot_load(buf, n, n, None, src if op == "fork" else None)
+        # (a step in between: the next save reads worlds the engine has touched, as in a search loop)
+        vec.step(torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32))
+    torch.cuda.synchronize()
+    e.check()
+    vec.close()
+
+
+def wall(name, windows, reps, warmup):
+    import torch
+    vec, n, n_act, g = make(name)
+    for _ in range(warmup):
+        vec.step(torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32))
+    e = vec.engine
+    snap = vec.save_state()
+    src = torch.randint(0, n, (n,), generator=g, device="cuda", dtype=torch.int32)
+
+    def host_round_trip():
+        e.set_state(e.get_state())
+    variants = {
+        "save_state": (lambda: vec.save_state(), reps),
+        "load_state": (lambda: vec.load_state(snap), reps),
+        "fork": (lambda: vec.fork(src), reps),
+        "render_alone": (lambda: e.render(vec.obs, vec.depth), reps),
+        "engine_save_kernel_call": (lambda: e.snapshot_save(snap.data, n), reps),
+        "engine_load_kernel_call": (lambda: e.snapshot_load(snap.data, n, n), reps),
+        "host_get_state_set_state": (host_round_trip, max(1, reps // 10)),
+    }
+    us = {k: [] for k in variants}
+    for _ in range(windows):
+        for k, (fn, r) in variants.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(r):
+                fn()
+            torch.cuda.synchronize()
+            us[k].append(1e6 * (time.perf_counter() - t0) / r)
+    record_bytes = (e.snapshot_bytes(n) - e.snapshot_bytes(0)) / n
+    # per-env geometry sets are copied up to their own counts: what a whole-batch call really moves (the spare set, where there is
+    # one, taken to be as long as the live one; a sample of 64 envs)
+    geometry = None
+    if not e.cfg.shared_geometry:
+        counts = [tuple(len(a) for a in e.get_geometry(i)) for i in range(0, n, max(1, n // 64))]
+        np_mean, ns_mean = (sum(c[k] for c in counts) / len(counts) for k in (0, 1))
+        blob_cap = e.cfg.max_polys * 128 + e.cfg.max_segs * 32
+        sets = max(1, min(2, int(record_bytes // blob_cap)))
+        used = record_bytes - sets * (blob_cap - (np_mean * 128 + ns_mean * 32))
+        geometry = {"max_polys": e.cfg.max_polys, "max_segs": e.cfg.max_segs, "polys_mean": round(np_mean, 1), "segs_mean": round(ns_mean, 1),
+                    "sets_per_record": sets, "record_bytes_moved": round(used, 1), "batch_bytes_moved": int(used * n)}
+    med = {k: sorted(v)[len(v) // 2] for k, v in us.items()}
+    out = {"config": name, "env_id": CONFIGS[name][0], "num_envs": n, "record_bytes": round(record_bytes, 1),
+           "batch_bytes": int(e.snapshot_bytes(n)), "geometry": geometry, "calls_per_window": reps,
+           "wall_us_per_call": {k: round(v, 1) for k, v in med.items()},
+           "windows_us": {k: [round(x, 1) for x in v] for k, v in us.items()},
+           "host_alternative_lacks": "rng stream, spare world, pending_remove, reset_pending, health, final info, per-env geometry"}
+    e.check()
+    vec.close()
+    print(json.dumps(out), flush=True)
+
+
+def bench_alternation(parent, rounds, windows):
+    """bench.py in the parent checkout and in this tree, alternately; prints each run's JSON result line tagged with its tree"""
+    for r in range(rounds):
+        for tag, root in (("parent", parent), ("tree", ROOT)):
+            p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--windows", str(windows), "--no-also", "--no-pmc", "--no-cpu-baseline", "--no-parity-check"],
+                               cwd=root, capture_output=True, text=True, timeout=900)
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+            if p.returncode != 0 or not line:
+                print(json.dumps({"tree": tag, "round": r, "error": (p.stdout + p.stderr)[-2000:]}), flush=True)
+                raise SystemExit(1)
+            res = json.loads(line[-1])
+            print(json.dumps({"tree": tag, "round": r, "result": res}), flush=True)
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--configs", default="hallway,maze,pickup_dr")
+    p.add_argument("--windows", type=int, default=5)
+    p.add_argument("--reps", type=int, default=50, help="calls per timed window (the host round trip: a tenth)")
+    p.add_argument("--warmup", type=int, default=100, help="steps before anything is measured")
+    p.add_argument("--profile", choices=sorted(CONFIGS), help="one config, untimed: the run a profiler wraps")
+    p.add_argument("--op", choices=["save_load", "fork"], default="save_load")
+    p.add_argument("--bench", metavar="PARENT", help="a built checkout of the parent commit: alternate bench.py between it and this tree")
+    p.add_argument("--rounds", type=int, default=2)
+    args = p.parse_args()
+    if args.bench:
+        return bench_alternation(os.path.abspath(args.bench), args.rounds, args.windows)
+    if args.profile:
+        return profile(args.profile, args.op, args.reps, args.warmup)
+    for name in args.configs.split(","):
+        wall(name, args.windows, args.reps, args.warmup)
+
+
+if __name__ == "__main__":
+    main()
