@@ -545,6 +545,29 @@ int mw_set_frame_reuse(mw_engine *e, int32_t on);
  * zeros before the first step; 0 for every env that was given a new world in the step, with and without final observations. */
 int mw_get_frame_clean(mw_engine *e, uint8_t *d_out, void *stream);
 
+/* The frame cache: the engine keeps, per env, the last `slots` distinct frames a plain mw_step / mw_step_repeat drew (0 .. 8; 0, the
+ * default, turns it off and frees the memory) and copies one of them instead of drawing when the env is back in the state that frame
+ * shows: turn left then right, a move that a later one undoes.  A cached frame matches when its key does, byte for byte: the agent's
+ * position and direction, the carried slot, the carried entity's position and direction, and a per-env epoch that the device
+ * advances whenever anything else a frame shows changes — a world installed (auto-reset, mw_reset), an entity removed behind the last
+ * frame, a pickup or a drop.  The copies are the engine's own, so unlike frame reuse nothing is promised about d_obs / d_depth: the
+ * caller may pass other buffers on every step and write to them as it likes.  A clean env that frame reuse may not skip (another
+ * buffer) is an ordinary hit.
+ * Used by plain steps of the whole batch through the quad kernel (small scenes, frames on the 16x4 grid) in the uint8 HWC layout,
+ * without mesh entities and experiment flags, never by MW_TASK_COLLECT; every other frame — renders, top views, the passes of a step
+ * with final observations, the tile kernels' frames — neither reads nor fills nor invalidates it, and an engine whose frames take
+ * another path holds the setting and no memory.  Every call that writes something a frame depends on drops every env's cached frames
+ * (one asynchronous clear of the key table in front of the next step that uses the cache): mw_reset, mw_set_state, mw_set_geometry,
+ * mw_set_gen_program, mw_upload_texture, mw_upload_mesh, mw_set_obs_layout, mw_snapshot_load, mw_set_frame_cache itself, and a
+ * change between steps with and without d_depth.
+ * Memory: num_envs x slots x H x W x 3 bytes (59 MB per slot at 4096 envs of 80x60), plus num_envs x slots x H x W x 4 for the
+ * depth maps once a step asks for depth (78 MB more per slot).  Observations, depth, rewards and flags are bit for bit what they are
+ * with the cache off.  A drawn frame costs one more store of its bytes, so a policy that never revisits a state pays without gain. */
+int mw_set_frame_cache(mw_engine *e, int32_t slots);
+/* d_out uint8[N] (device): where each env's frame of the last plain mw_step came from — 0 drawn, 1 left alone as clean (frame reuse),
+ * 2 + j copied from slot j of the frame cache.  The step kernel stores 0, the quad kernel the rest: zeros on the other raster paths.  Asynchronous on `stream`. */
+int mw_get_frame_source(mw_engine *e, uint8_t *d_out, void *stream);
+
 /* Diagnostic (synchronises `stream`): how many triangles the last frame's display list held per env after clipping and culling —
  * what max_visible has to pay for (6 records per unit), and what decides which raster kernel an env's frame takes.
  * The stored length is clamped to the list's capacity (6 x max_visible): a value EQUAL to the capacity means "at least this

@@ -95,6 +95,23 @@ struct MwProgram {
 // lacks an entity the last one showed (frame_clean)
 #define MW_REMOVE_APPLIED (-2)
 
+// the frame cache's keys: ten 64-bit words (MwArgs::fc_key), compared as five 16-byte quads; the cache's key table holds, per env,
+// a 16-byte header (word 0: the slot the next drawn frame replaces) and the slots' keys — all zero = nothing cached (a key's last
+// word is 1)
+#define MW_FC_KEY_WORDS 10
+#define MW_FC_META_WORDS(slots) (2 + MW_FC_KEY_WORDS * (slots))
+#define MW_FC_MAX_SLOTS 8
+// ... and what the quad kernel needs of the cache, in device memory: the kernel takes ONE pointer to it (null: no cache for this
+// frame) and loads the rest where it uses it — its scalar registers are spoken for, and kernel arguments stay in them from the
+// first instruction to their last use.
+struct MwFcArgs {
+    const uint64_t *key;    // MwArgs::fc_key
+    uint64_t *meta;         // [N][MW_FC_META_WORDS(slots)]
+    uint8_t *frames;        // [N][slots][H W 3]
+    float *depth;           // [N][slots][H W], or null before the first step with a depth output
+    int32_t slots, pad;
+};
+
 // Everything the kernels need; passed by value (kernarg).
 struct MwArgs {
     int32_t N, W, H, E;
@@ -162,6 +179,14 @@ struct MwArgs {
     // installed.  Stored by K1 for every env on every step; the raster kernels leave such an env's rows of the observation
     // alone when the engine vouches for the buffer (mw_set_frame_reuse).
     uint8_t *frame_clean;    // [N]
+    // The frame cache (mw_set_frame_cache; the quad kernel, mw_rasterq.hip).  fc_key[env]: the key of the env's current frame,
+    // MW_FC_KEY_WORDS words stored by K1 on every call — the bits of the agent's x, y, z and direction, the carried slot | the
+    // epoch << 32, the bits of the carried entity's x, y, z and direction (zeros when nothing is carried), 1.  fc_epoch[env]: advanced
+    // whenever anything else the frame shows changes on the device — a world installed, a removal applied behind the last frame, a
+    // change of the carried slot — so that frames from before and after it cannot match.
+    uint64_t *fc_key;        // [N][MW_FC_KEY_WORDS]
+    uint32_t *fc_epoch;      // [N]
+    uint8_t *fc_source;      // [N] where the env's frame of the last plain step came from (mw_get_frame_source): K1 stores 0, "drawn", the quad kernel 1 or 2 + j for an env it does not draw
     // big scenes: what the geometry kernel's culling derives from a world's polygons alone (mw_geom.hip), kept from frame to
     // frame.  occ_valid[set]: polygon count + 1 of the world the cache belongs to, 0 after anything rewrote the polygons.
     int32_t *occ_valid;     // [sets] or null

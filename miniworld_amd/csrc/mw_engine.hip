@@ -188,6 +188,20 @@ struct mw_engine {
     // frame depends on (drop_held_frame).
     bool frame_reuse = false;
     struct { uint8_t *obs = nullptr; float *depth = nullptr; int layout = 0; bool valid = false; } held;
+    // mw_set_frame_cache: per env the last `slots` distinct frames the quad kernel drew, with their keys (mw_kernels.h).  The engine's
+    // own copies: unlike frame reuse it needs no promise about the caller's buffers.  `dirty`: an entry point wrote something a
+    // frame depends on (drop_frame_cache) — the next frame that uses the cache clears the key table first, on its own stream.
+    struct {
+        int slots = 0;
+        DevBuf<uint8_t> frames;         // [N][slots][H W 3]
+        DevBuf<float> depth;            // [N][slots][H W], allocated by the first frame with a depth output
+        DevBuf<uint64_t> meta;          // [N][MW_FC_META_WORDS(slots)]
+        DevBuf<MwFcArgs> d_args;        // the quad kernel's view of the above (mw_device.h), rewritten with the clear when a buffer changed
+        MwFcArgs args{};
+        bool args_stale = true;
+        bool with_depth = false;        // the cached frames were drawn with a depth output
+        bool dirty = true;
+    } fc;
     // mw_set_frame_stack: the caller's ring (depth = 0: off), the layout and frame size it was set under, the pushes so far — a host
     // counter, every launch gets its phase by value — and the engine's flag bytes, [2][N] (MW_STACK_*): a push or refresh reads
     // flags[cur] and writes the other half, which becomes the current one (mw_stack.hip); the host's marks go to flags[cur]
@@ -361,6 +375,9 @@ int raster_flags(const mw_engine *e, int part, uint32_t stamp, bool reuse = fals
     return e->dbg_flags | e->obs_layout << 8 | part << 4 | (int)(stamp << 16) | (reuse && stamp == 0u ? MW_RASTER_REUSE : 0);
 }
 void drop_held_frame(mw_engine *e) { e->held.valid = false; }
+// ... and the cached frames of every env: for the entry points that change what a state's frame looks like or the states themselves
+// behind K1's back.  Not for frames (launch_frame): a render, a top view or a list pass leaves the state-to-frame function alone.
+void drop_frame_cache(mw_engine *e) { e->fc.dirty = true; }
 
 // bytes of one env's row of d_obs in the current output layout
 size_t obs_row_bytes(const mw_engine *e)
@@ -715,6 +732,8 @@ struct Frame {
     int view_flags;
     const int32_t *list;        // FRAME_LIST: the list forms draw the listed envs only
     uint8_t *obs; float *depth; hipStream_t st; bool reuse;
+    int fc_slots;               // > 0: the quad kernel consults and fills the frame cache
+    uint8_t *source;            // the per-env source byte (a plain step), or null
     RasterPath p;
     MeshFrame mf;               // p.mesh only
 };
@@ -791,7 +810,7 @@ void launch_quad(const mw_engine *e, const Frame &f, int part, hipStream_t st)
     launch(f.p.quad4 ? MW_PAIR(mw_rasterq4) : MW_PAIR(mw_rasterq), f.list, dim3(e->cfg.num_envs), dim3(MWQ_THREADS), (size_t)lds, st, a.N, a.W, a.H, a.max_vis,
            a.tiles_x, a.n_tiles, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
            (const int32_t *)a.nvis, (const float *)a.envhdr, a.texels, f.obs, f.depth, raster_flags(e, part, 0u, f.reuse), e->texel_bytes, e->d_k2q_prof,
-           (const uint8_t *)a.frame_clean);
+           (const uint8_t *)a.frame_clean, f.fc_slots ? (const MwFcArgs *)e->fc.d_args.get() : nullptr, f.source);
 }
 
 // the tile kernels (mw_raster.hip); part: raster_flags
@@ -874,7 +893,32 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
                        e->held.depth == d_depth && e->held.layout == e->obs_layout;
     drop_held_frame(e);
     const int N = e->cfg.num_envs;
-    Frame f{e->args, view_flags, frame == FRAME_LIST ? e->d_final_list : nullptr, d_obs, d_depth, st, reuse, raster_path(e, d_depth != nullptr), {}};
+    Frame f{e->args, view_flags, frame == FRAME_LIST ? e->d_final_list : nullptr, d_obs, d_depth, st, reuse, 0, nullptr, raster_path(e, d_depth != nullptr), {}};
+    // The frame cache: consulted and filled by a plain step of the whole batch through the quad kernel, in the layout it was
+    // allocated for, without mesh entities or experiment flags; whose buffers the frame goes to does not matter.  Every other frame
+    // neither reads nor writes it.  CollectHealth never: its respawn kernel moves entities behind K1's back (as for frame_clean).
+    if (plain && do_step && f.p.path == MW_PATH_QUAD) {
+        f.source = f.a.fc_source;
+        if (e->fc.slots > 0 && e->fc.frames && !e->have_meshes && e->dbg_flags == 0 && e->obs_layout == MW_OBS_HWC_U8 && e->cfg.task != MW_TASK_COLLECT) {
+            if (d_depth && !e->fc.depth) {
+                if (const int rc = dev_alloc(e, e->fc.depth, (size_t)N * e->fc.slots * f.a.W * f.a.H, false)) return rc;
+                e->fc.args_stale = true;
+            }
+            if ((d_depth != nullptr) != e->fc.with_depth) { e->fc.with_depth = d_depth != nullptr; drop_frame_cache(e); }
+            if (e->fc.args_stale) {
+                // (the buffers are new: no frame that is still running reads the block)
+                e->fc.args = MwFcArgs{f.a.fc_key, e->fc.meta.get(), e->fc.frames.get(), e->fc.depth.get(), e->fc.slots, 0};
+                HIP_TRY(e, hipMemcpyAsync(e->fc.d_args.get(), &e->fc.args, sizeof(MwFcArgs), hipMemcpyHostToDevice, st));
+                e->fc.args_stale = false;
+                drop_frame_cache(e);
+            }
+            if (e->fc.dirty) {
+                HIP_TRY(e, hipMemsetAsync(e->fc.meta.get(), 0, (size_t)N * MW_FC_META_WORDS(e->fc.slots) * 8, st));
+                e->fc.dirty = false;
+            }
+            f.fc_slots = e->fc.slots;
+        }
+    }
     f.a.step_override = e->use_step_override ? e->d_step_override : nullptr;
     // a frame with mesh entities through the tile / quad kernels: the geometry kernel lists the entities in view for the mesh
     // entity kernel and the tiles a mesh can touch for the raster kernel's second part
@@ -1019,6 +1063,7 @@ int init_engine(mw_engine *e, const mw_config *cfg)
     ALLOC(a.pending_remove, (size_t)N);
     ALLOC(a.reset_pending, (size_t)N);      // (zeroed: nothing pending)
     ALLOC(a.frame_clean, (size_t)N);        // (zeroed: nothing clean before the first step)
+    ALLOC(a.fc_key, (size_t)MW_FC_KEY_WORDS * N); ALLOC(a.fc_epoch, (size_t)N); ALLOC(a.fc_source, (size_t)N);
     HIP_TRY(e, hipMemset(a.pending_remove, 0xFF, 4 * (size_t)N));
     ALLOC(a.nvis, N); ALLOC(a.envhdr, (size_t)MW_ENVHDR * N); ALLOC(a.status, 1);
     ALLOC(e->d_reward_scratch, N); ALLOC(e->d_flag_scratch, 2 * (size_t)N); ALLOC(e->d_action_scratch, N);
@@ -1228,6 +1273,7 @@ int mw_upload_texture(mw_engine *e, int32_t tex_id, const uint8_t *rgb, int32_t 
     if (!e || !rgb) return fail(e, MW_E_INVALID, "null argument");
     ON_DEVICE_SYNC(e);
     drop_held_frame(e);
+    drop_frame_cache(e);
     if (tex_id < 0 || tex_id >= MW_MAX_TEX) return fail(e, MW_E_CAPACITY, "texture id %d out of range (max %d)", tex_id, MW_MAX_TEX);
     if (w <= 0 || h <= 0 || w > 16384 || h > 16384) return fail(e, MW_E_INVALID, "bad texture size %dx%d", w, h);
     mwasset::build_pyramid(rgb, w, h, e->tex_data[tex_id], e->tex_desc[tex_id]);
@@ -1240,6 +1286,7 @@ int mw_upload_mesh(mw_engine *e, int32_t mesh_id, const float *pos, const float 
     if (!e || !pos || !nrm || !rgb) return fail(e, MW_E_INVALID, "null argument");
     ON_DEVICE_SYNC(e);
     drop_held_frame(e);
+    drop_frame_cache(e);
     if (tex_id >= MW_MAX_TEX || (tex_id >= 0 && !uv)) return fail(e, MW_E_INVALID, "textured mesh needs texcoords and a valid texture id");
     if (mesh_id < 0 || mesh_id >= MW_MAX_MESH) return fail(e, MW_E_CAPACITY, "mesh id %d out of range (max %d)", mesh_id, MW_MAX_MESH);
     if (ntris <= 0 || ntris > 60000) return fail(e, MW_E_CAPACITY, "mesh with %d triangles (1..60000 supported: 16-bit draw ids)", ntris);
@@ -1290,6 +1337,7 @@ int mw_set_geometry(mw_engine *e, int32_t env, const mw_poly *polys, int32_t n_p
     if (!e || (n_polys > 0 && !polys) || (n_segs > 0 && !segs)) return fail(e, MW_E_INVALID, "null argument");
     ON_DEVICE_SYNC(e);
     drop_held_frame(e);
+    drop_frame_cache(e);
     if (n_polys < 0 || n_polys > e->cfg.max_polys) return fail(e, MW_E_CAPACITY, "%d polygons > max_polys %d", n_polys, e->cfg.max_polys);
     if (n_segs < 0 || n_segs > e->cfg.max_segs) return fail(e, MW_E_CAPACITY, "%d segments > max_segs %d", n_segs, e->cfg.max_segs);
     int set = 0;
@@ -1332,6 +1380,7 @@ int mw_set_state(mw_engine *e, int32_t first_env, int32_t count, const mw_state_
     if (!e) return MW_E_INVALID;
     ON_DEVICE_SYNC(e);
     drop_held_frame(e);
+    drop_frame_cache(e);
     const int rc = state_xfer(e, first_env, count, host, true);
     if (rc != MW_OK) return rc;
     // a world written from the host replaces whatever a pending next-step auto-reset would have installed
@@ -1362,6 +1411,7 @@ int mw_set_gen_program(mw_engine *e, const mw_gen_program *prog, const mw_poly *
     if (!e || !prog) return fail(e, MW_E_INVALID, "null argument");
     ON_DEVICE_SYNC(e);
     drop_held_frame(e);
+    drop_frame_cache(e);
     if (prog->n_rooms < 1 || prog->n_rooms > MW_PROG_MAX_ROOMS || prog->n_tex < 0 || prog->n_tex > MW_PROG_MAX_TEX ||
         prog->n_ops < 0 || prog->n_ops > MW_PROG_MAX_OPS || prog->n_ents < 0 || prog->n_ents > MW_PROG_MAX_ENTS ||
         prog->n_ents > e->cfg.max_ents || prog->sign_n < 0 || prog->sign_n > 8)
@@ -1422,6 +1472,7 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
     if (!e) return MW_E_INVALID;
     ON_DEVICE_SYNC(e);
     drop_held_frame(e);
+    drop_frame_cache(e);
     if (e->cfg.generator == MW_GEN_NONE && !seeds) return fail(e, MW_E_INVALID, "engine was created without a device-side generator");
     if (e->cfg.generator == MW_GEN_PROGRAM && !e->args.prog) return fail(e, MW_E_INVALID, "MW_GEN_PROGRAM: no placement program installed (mw_set_gen_program)");
     const int N = e->cfg.num_envs;
@@ -1624,6 +1675,7 @@ int mw_set_obs_layout(mw_engine *e, int32_t layout)
     if (!e) return MW_E_INVALID;
     if (layout != MW_OBS_HWC_U8 && layout != MW_OBS_CWH_U8 && layout != MW_OBS_GREY_F64) return fail(e, MW_E_INVALID, "unknown obs layout %d", layout);
     drop_held_frame(e);
+    drop_frame_cache(e);
     e->obs_layout = layout;
     return MW_OK;
 }
@@ -1689,6 +1741,7 @@ int mw_snapshot_load(mw_engine *e, const int32_t *d_envs, const int32_t *d_recs,
     if (const int rc = snapshot_grid(e, "mw_snapshot_load", count, &item_chunks, &grid)) return rc;
     if (const int rc = snapshot_order(e, st)) return rc;
     drop_held_frame(e);     // (the frames in the caller's buffers are those of the states that are about to go)
+    drop_frame_cache(e);    // (... and so are the cached ones: a loaded env's epoch is not part of its record)
     hipLaunchKernelGGL(mw_snapshot_load_kernel, dim3(grid), dim3(MW_SNAP_THREADS), 0, st, (const MwSnapTable *)e->d_snap_tab, mw_snap_key(e->snap_cfg, capacity),
                        e->cfg.num_envs, (int)capacity, (int)count, item_chunks, d_envs, e->args.status, d_snap, d_recs, (int)n_recs, e->args.frame_clean,
                        e->cfg.shared_geometry ? nullptr : e->args.occ_valid, e->stack.depth ? stack_flags(e, e->stack.cur) : nullptr);
@@ -1785,6 +1838,41 @@ int mw_set_frame_reuse(mw_engine *e, int32_t on)
     if (!e) return MW_E_INVALID;
     drop_held_frame(e);     // (trust starts with the next whole frame)
     e->frame_reuse = on != 0;
+    return MW_OK;
+}
+
+int mw_set_frame_cache(mw_engine *e, int32_t slots)
+{
+    if (!e) return MW_E_INVALID;
+    if (slots < 0 || slots > MW_FC_MAX_SLOTS) return fail(e, MW_E_INVALID, "mw_set_frame_cache: %d slots outside 0 .. %d", (int)slots, MW_FC_MAX_SLOTS);
+    ON_DEVICE(e);
+    drop_frame_cache(e);
+    if (slots == e->fc.slots) return MW_OK;
+    // the frames that may still read or write the old buffers finish first
+    HIP_TRY(e, hipDeviceSynchronize());
+    e->fc.slots = 0;
+    e->fc.frames.reset(); e->fc.depth.reset(); e->fc.meta.reset();
+    // (only the quad kernel uses the cache: an engine whose frames take another path holds the setting and no memory)
+    if (slots > 0 && e->use_k2q && e->k2q_ok) {
+        const size_t N = (size_t)e->cfg.num_envs;
+        DevBuf<uint8_t> frames; DevBuf<uint64_t> meta;
+        int rc;
+        if ((rc = dev_alloc(e, frames, N * slots * e->cfg.obs_width * e->cfg.obs_height * 3, false)) || (rc = dev_alloc(e, meta, N * MW_FC_META_WORDS(slots))) ||
+            (!e->fc.d_args && (rc = dev_alloc(e, e->fc.d_args, 1))))
+            return rc;
+        e->fc.frames = std::move(frames); e->fc.meta = std::move(meta);
+        e->fc.args_stale = true;
+    }
+    e->fc.slots = slots;
+    return MW_OK;
+}
+
+int mw_get_frame_source(mw_engine *e, uint8_t *d_out, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (!d_out) return fail(e, MW_E_INVALID, "mw_get_frame_source: d_out is null");
+    ON_DEVICE(e);
+    HIP_TRY(e, hipMemcpyAsync(d_out, e->args.fc_source, (size_t)e->cfg.num_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MW_OK;
 }
 

@@ -81,13 +81,18 @@ MW_KERNEL_PAIR(mw_raster_mesh_wrap, MW_RASTER_ARGS);
 MW_KERNEL_PAIR(mw_raster_big_mesh_wrap, MW_RASTER_ARGS);
 
 // the quad kernel (mw_rasterq.hip): one workgroup of MWQ_THREADS lanes per env, 8 or 4 samples per pixel
+// The frame cache (mw_set_frame_cache), fc != null (MwFcArgs, mw_device.h) — uint8 HWC frames without mesh entities only, never the
+// list forms: the env's workgroup compares the key K1 stored for this frame (MwArgs::fc_key) with the keys of the env's slots and
+// copies the matching slot's frame and depth map instead of drawing; a frame it draws also goes to the slot the env's header names,
+// with its key.  frame_source (may be null; MwArgs::fc_source): per env 0 drawn — K1's store, a drawing workgroup writes nothing —, 1 left
+// alone as clean, 2 + j copied from slot j.
 #define MWQ_THREADS 512
 #define MWQ_ARGS \
     int N, int W, int H, int max_vis, int tiles_x, int n_tiles, \
     const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, \
     const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const uint32_t *__restrict__ texels, \
     uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof, \
-    const uint8_t *__restrict__ frame_clean
+    const uint8_t *__restrict__ frame_clean, const MwFcArgs *__restrict__ fc, uint8_t *__restrict__ frame_source
 MW_KERNEL_PAIR(mw_rasterq, MWQ_ARGS);
 MW_KERNEL_PAIR(mw_rasterq4, MWQ_ARGS);
 // bytes of dynamic LDS a launch needs; the longest display list the quad path draws (longer ones: the tile code)

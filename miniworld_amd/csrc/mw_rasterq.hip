@@ -553,7 +553,8 @@ __device__ inline void rasterq_body(
     const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull,
     const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const uint32_t *__restrict__ texels,
     uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof,
-    const uint8_t *__restrict__ frame_clean, const int32_t *__restrict__ list = nullptr)
+    const uint8_t *__restrict__ frame_clean, const MwFcArgs *__restrict__ fc, uint8_t *__restrict__ frame_source,
+    const int32_t *__restrict__ list = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef QRec<S> R;
@@ -563,9 +564,55 @@ __device__ inline void rasterq_body(
         env = list[1 + env];
     } else if (env >= N) return;
     // the buffer holds this env's frame already (MW_RASTER_REUSE, mw_kernels.h): the whole workgroup, before any barrier
-    if (!SUB && (dbg & MW_RASTER_REUSE) && frame_clean[env]) return;
+    if (!SUB && (dbg & MW_RASTER_REUSE) && frame_clean[env]) {
+        if (frame_source && threadIdx.x == 0) frame_source[env] = 1;
+        return;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool has_depth = depth != nullptr;
+    // The frame cache (mw_kernels.h): every wavefront compares the env's key with the slots' keys, a 16-byte quad per lane, and
+    // reaches the same verdict from the same bytes — nothing writes them before phase E, behind the barriers every wavefront of a
+    // drawing workgroup passes.  A hit copies the slot's frame and leaves, the whole workgroup, before any barrier.
+    uint32_t fc_victim = 0u;        // the slot this frame goes to when it is drawn: kept in LDS from phase 0 on (s_misc[20])
+    if (!SUB && fc) {
+        const int fc_slots = fc->slots;
+        const uint64_t *meta = fc->meta + (size_t)env * MW_FC_META_WORDS(fc_slots);
+        const uint4 *cur = reinterpret_cast<const uint4 *>(fc->key + (size_t)env * MW_FC_KEY_WORDS);
+        // (lane 63 fetches the env's header beside the keys: one round trip to memory for both)
+        bool eq = false;
+        uint4 k = make_uint4(0u, 0u, 0u, 0u);
+        if (lane < fc_slots * (MW_FC_KEY_WORDS / 2)) {
+            const uint4 c = cur[lane % (MW_FC_KEY_WORDS / 2)];
+            k = reinterpret_cast<const uint4 *>(meta + 2)[lane];
+            eq = k.x == c.x && k.y == c.y && k.z == c.z && k.w == c.w;
+        } else if (lane == 63) k = reinterpret_cast<const uint4 *>(meta)[0];
+        const uint64_t m = __builtin_amdgcn_ballot_w64(eq);
+        int hit = -1;
+        for (int j = fc_slots - 1; j >= 0; --j)
+            if (((m >> (j * (MW_FC_KEY_WORDS / 2))) & 31ull) == 31ull) hit = j;
+        if (hit >= 0) {
+            const int fbytes = W * H * 3;           // (a multiple of 64 bytes: the quad path draws frames on the 16x4 grid only)
+            const uint8_t *src = fc->frames + ((size_t)env * fc_slots + hit) * fbytes;
+            uint8_t *dst = obs + (size_t)env * fbytes;
+            if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0u)
+                for (int i = tid; i < fbytes / 16; i += MWQ_THREADS) reinterpret_cast<uint4 *>(dst)[i] = reinterpret_cast<const uint4 *>(src)[i];
+            else if ((reinterpret_cast<uintptr_t>(dst) & 3u) == 0u)
+                for (int i = tid; i < fbytes / 4; i += MWQ_THREADS) reinterpret_cast<uint32_t *>(dst)[i] = reinterpret_cast<const uint32_t *>(src)[i];
+            else
+                for (int i = tid; i < fbytes; i += MWQ_THREADS) dst[i] = src[i];
+            if (has_depth) {
+                const float *zs = fc->depth + ((size_t)env * fc_slots + hit) * (W * H);
+                float *zd = depth + (size_t)env * (W * H);
+                if ((reinterpret_cast<uintptr_t>(zd) & 15u) == 0u)
+                    for (int i = tid; i < W * H / 4; i += MWQ_THREADS) reinterpret_cast<float4 *>(zd)[i] = reinterpret_cast<const float4 *>(zs)[i];
+                else
+                    for (int i = tid; i < W * H; i += MWQ_THREADS) zd[i] = zs[i];
+            }
+            if (frame_source && tid == 0) frame_source[env] = (uint8_t)(2 + hit);
+            return;
+        }
+        fc_victim = min((uint32_t)__builtin_amdgcn_readlane((int)k.x, 63), (uint32_t)(fc_slots - 1));
+    }
     const QPlan pl = q_plan(S, W, H, n_tiles, has_depth);
     float4 *s_rec = reinterpret_cast<float4 *>(smem + pl.rec);
     uint8_t *s_frame = smem + pl.frame;
@@ -578,7 +625,7 @@ __device__ inline void rasterq_body(
     uint8_t *s_tlist = smem + pl.tlist;
     uint32_t *s_tmask = reinterpret_cast<uint32_t *>(smem + pl.tmask);
     uint32_t *s_pe = reinterpret_cast<uint32_t *>(smem + pl.pe);
-    uint32_t *s_misc = reinterpret_cast<uint32_t *>(smem + pl.misc);     // [0..8] class counts, [16] partial events, [17] next batch, [18] exact list, [19] next exact batch
+    uint32_t *s_misc = reinterpret_cast<uint32_t *>(smem + pl.misc);     // [0..8] class counts, [16] partial events, [17] next batch, [18] exact list, [19] next exact batch, [20] the frame cache's slot for this frame
     uint16_t *s_rank = reinterpret_cast<uint16_t *>(s_frame);            // phase C only (the partial events are done with, the frame is not written before phase D)
     uint32_t *s_btab = reinterpret_cast<uint32_t *>(smem + pl.btab);
     const int QW = W / 2, QH = H / 2, nquads = QW * QH;
@@ -668,6 +715,7 @@ __device__ inline void rasterq_body(
         // wavefront's scratch
         float4 *scr = reinterpret_cast<float4 *>(smem + pl.scratch) + wave * R::NQ;
         cx.s_rec = scr;
+        if (tid == 20) s_misc[20] = fc_victim;
         for (int b = wave; b * 16 < nquads; b += MWQ_WAVES) {
             const int Q = b * 16 + (lane >> 2);
             const bool on = Q < nquads;
@@ -701,7 +749,7 @@ __device__ inline void rasterq_body(
         for (int i = tid; i < nvis * 3; i += MWQ_THREADS) { const int p = i / 3, j = i - p * 3; stage_quad(p, R::CT + j, s_rec + p * R::NQ + R::CT + j, false); }
         for (int i = tid; i < n_tiles; i += MWQ_THREADS) { s_tcnt[i] = 0u; s_tfull[i] = 0u; }
         for (int i = tid; i < nquads; i += MWQ_THREADS) s_qids[i] = 0u;
-        if (tid < 64) s_misc[tid] = 0u;
+        if (tid < 64) s_misc[tid] = tid == 20 ? fc_victim : 0u;
         __syncthreads();
         stamp(1);
         if ((dbg >> 13) == 1) return;       // (bits 13-15: leave after phase 0 / A / B / C1 — instruction counts per phase, frames invalid)
@@ -961,23 +1009,42 @@ __device__ inline void rasterq_body(
         }
     }
     stamp(7);
+    // get_depth_map in float32 as numpy evaluates it (opengl.py:426-431)
+    auto depth_of = [&](int i) {
+        const float z = (float)s_z[i];
+        const float d = z / 65535.0f;
+        const float clip = (d - 0.5f) * 2.0f;
+        const float den = clip * (float)(100.0 - 0.04) - (float)(100.0 + 0.04);
+        return (float)(-2.0 * 100.0 * 0.04) / den;
+    };
     if (has_depth) {
-        // get_depth_map in float32 as numpy evaluates it (opengl.py:426-431)
         float *dst = depth + (size_t)env * npix;
         for (int i = tid; i < npix; i += MWQ_THREADS) {
             if (in_mesh_tile(i % W, i / W)) continue;
-            const float z = (float)s_z[i];
-            const float d = z / 65535.0f;
-            const float clip = (d - 0.5f) * 2.0f;
-            const float den = clip * (float)(100.0 - 0.04) - (float)(100.0 + 0.04);
-            dst[i] = (float)(-2.0 * 100.0 * 0.04) / den;
+            dst[i] = depth_of(i);
         }
+    }
+    // the frame cache: the drawn frame, its depth map and its key into the slot the header named (round-robin; a hit changes nothing)
+    if (!SUB && fc) {
+        const int fc_slots = fc->slots;
+        const uint32_t victim = s_misc[20];
+        uint64_t *meta = fc->meta + (size_t)env * MW_FC_META_WORDS(fc_slots);
+        uint4 *fd = reinterpret_cast<uint4 *>(fc->frames + ((size_t)env * fc_slots + victim) * (npix * 3));
+        const uint4 *src = reinterpret_cast<const uint4 *>(s_frame);
+        for (int i = tid; i < npix * 3 / 16; i += MWQ_THREADS) fd[i] = src[i];
+        if (has_depth) {
+            float *fz = fc->depth + ((size_t)env * fc_slots + victim) * npix;
+            for (int i = tid; i < npix; i += MWQ_THREADS) fz[i] = depth_of(i);
+        }
+        if (tid < MW_FC_KEY_WORDS / 2)
+            reinterpret_cast<uint4 *>(meta + 2 + MW_FC_KEY_WORDS * victim)[tid] = reinterpret_cast<const uint4 *>(fc->key + (size_t)env * MW_FC_KEY_WORDS)[tid];
+        if (tid == 64) meta[0] = (uint64_t)(victim + 1u == (uint32_t)fc_slots ? 0u : victim + 1u);
     }
 }
 
 }  // namespace
 
-#define MWQ_FWD N, W, H, max_vis, tiles_x, n_tiles, rec_raster, rec_shade, rec_cull, nvis_arr, envhdr, texels, obs, depth, dbg, texel_bytes, prof, frame_clean
+#define MWQ_FWD N, W, H, max_vis, tiles_x, n_tiles, rec_raster, rec_shade, rec_cull, nvis_arr, envhdr, texels, obs, depth, dbg, texel_bytes, prof, frame_clean, fc, frame_source
 // each kernel and its list form over the envs of a list (int32 [0] count, [1 + i] env)
 #define MWQ_PAIR(stem, bounds, ...)                                                                          \
     extern "C" __global__ bounds void stem##_kernel(MWQ_ARGS) { rasterq_body<__VA_ARGS__, false>(MWQ_FWD); } \

@@ -17,6 +17,7 @@ extern "C" __global__ __launch_bounds__(64) void MW_RESET_KERNEL_NAME(MwArgs a, 
     if (!wave_per_env || threadIdx.x == 0) {
         if (mark_refill) a.refill_mask[env] = 1u;      // spare mode: its spare is stale now
         a.reset_pending[env] = 0;       // the new world replaces a pending next-step auto-reset
+        a.fc_epoch[env] += 1u;          // ... and no cached frame of the old one shows it (MwArgs::fc_epoch)
     }
 }
 
@@ -63,6 +64,7 @@ extern "C" __global__ __launch_bounds__(64) void MW_INSTALL_KERNEL_NAME(MwArgs a
         a.pending_remove[env] = -1;
         a.reset_pending[env] = 0;
         a.frame_clean[env] = 0;         // (K1 ran as a terminal step and may have found the finished episode's last frame unchanged)
+        a.fc_epoch[env] += 1u;          // (a world installed: MwArgs::fc_epoch)
     }
 }
 
@@ -74,6 +76,6 @@ extern "C" __global__ __launch_bounds__(64) void mw_take_spare_kernel(MwArgs a, 
     if (env >= a.N) return;
     if (!force_all && !mask[env]) return;
     mw::take_spare(a, env, (int)threadIdx.x);
-    if (threadIdx.x == 0) { a.refill_mask[env] = 1u; a.reset_pending[env] = 0; }
+    if (threadIdx.x == 0) { a.refill_mask[env] = 1u; a.reset_pending[env] = 0; a.fc_epoch[env] += 1u; }
 }
 #endif

@@ -26,6 +26,22 @@ __device__ inline double uni(double v)
 
 __device__ inline bool same_bits(double x, double y) { return __double_as_longlong(x) == __double_as_longlong(y); }
 
+// The key of the frame this call leaves behind (MwArgs::fc_key), stored by the env's writer lane as five 16-byte quads: what a plain
+// agent-view frame shows of a world that stays installed — the agent's pose, the carried slot and that entity's pose — and the env's
+// epoch, which K1 has advanced by then if this call changed anything else (step_env).
+__device__ inline void store_frame_key(const MwArgs &a, int env, double px, double py, double pz, double dir, int carry, uint32_t epoch,
+                                       double cx, double cy, double cz, double cdir)
+{
+    ulonglong2 *k = reinterpret_cast<ulonglong2 *>(a.fc_key + (size_t)env * MW_FC_KEY_WORDS);
+    auto bits = [](double v) { return (unsigned long long)__double_as_longlong(v); };
+    const bool c = carry >= 0;
+    k[0] = make_ulonglong2(bits(px), bits(py));
+    k[1] = make_ulonglong2(bits(pz), bits(dir));
+    k[2] = make_ulonglong2((unsigned long long)(uint32_t)carry | ((unsigned long long)epoch << 32), c ? bits(cx) : 0ull);
+    k[3] = make_ulonglong2(c ? bits(cy) : 0ull, c ? bits(cz) : 0ull);
+    k[4] = make_ulonglong2(c ? bits(cdir) : 0ull, 1ull);
+}
+
 // ---------------------------------------------------------------- dynamics (f64)
 
 struct StepCtx {
@@ -241,6 +257,8 @@ __device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writ
     // the state as loaded, for the frame_clean byte: what the frame shows of an env is its agent's pose and its entities'
     const double o_px = c.px, o_py = c.py, o_pz = c.pz, o_dir = c.dir, o_cpos[3] = {c.cpos[0], c.cpos[1], c.cpos[2]}, o_cdir = c.cdir;
     const int o_carry = c.carry;
+    const int o_pending = a.pending_remove[env];        // (what the last step left; -1: nothing left or has just left the list)
+    const uint32_t o_epoch = a.fc_epoch[env];
     bool same = false;              // the state this step stores is the state it loaded, bit for bit
     int remove_slot = -1;
     int tm = 0, tr = 0;             // terminated / truncated, uniform over the env's lanes
@@ -409,8 +427,14 @@ __device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writ
         // left it behind the last one (the geometry kernel applied that removal after the last frame was drawn: MW_REMOVE_APPLIED;
         // a slot still pending was never applied), not on a next-step reset, not when a world was installed.  CollectHealth never:
         // its respawn kernel moves entities behind this kernel's back.
-        const bool clean = same && !pend && !installed && remove_slot < 0 && a.pending_remove[env] == -1 && a.task != MW_TASK_COLLECT;
-        if (REPEAT) clean_out = clean; else a.frame_clean[env] = clean ? 1 : 0;
+        const bool clean = same && !pend && !installed && remove_slot < 0 && o_pending == -1 && a.task != MW_TASK_COLLECT;
+        if (REPEAT) clean_out = clean; else { a.frame_clean[env] = clean ? 1 : 0; a.fc_source[env] = 0; }
+        // the frame cache's epoch: everything that forces clean = 0 whatever the poses say also parts the frames before it from the
+        // frames after it — a world installed, a removal the geometry kernel applied behind the last frame (the frame of the step
+        // that removes still shows the entity), a change of the carried slot (a dropped entity stays where it was put)
+        const bool parted = pend || installed || o_pending != -1 || c.carry != o_carry;
+        if (parted) a.fc_epoch[env] = o_epoch + 1u;
+        if (!REPEAT) store_frame_key(a, env, c.px, c.py, c.pz, c.dir, c.carry, o_epoch + (parted ? 1u : 0u), c.cpos[0], c.cpos[1], c.cpos[2], c.cdir);
         a.pending_remove[env] = remove_slot;
     }
     return SubStep{rew_out, tm, tr, remove_slot, !pend, clean_out};
@@ -468,6 +492,12 @@ __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool 
         trunc[env] = (uint8_t)tr;
         if (nsteps) nsteps[env] = n;
         a.frame_clean[env] = n > 0 && clean ? 1 : 0;
+        a.fc_source[env] = 0;
+        // the key of the state the last sub-step left, once per call, from the writer's own stores: the slot the frame shows as
+        // carried is the one that leaves the list behind it, if any (step_env: remove_slot), else the carried one
+        const int pr = a.pending_remove[env], k = pr >= 0 ? pr : a.carry[env], ks = k >= 0 ? k : 0;
+        store_frame_key(a, env, a.ax[env], a.ay[env], a.az[env], a.adir[env], k, a.fc_epoch[env], a.epos[((size_t)0 * a.E + ks) * a.N + env],
+                        a.epos[((size_t)1 * a.E + ks) * a.N + env], a.epos[((size_t)2 * a.E + ks) * a.N + env], a.edir[(size_t)ks * a.N + env]);
     }
 }
 

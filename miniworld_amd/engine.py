@@ -37,7 +37,7 @@ PATH_TILE, PATH_QUAD, PATH_QUAD_MESH, PATH_GENERIC = 0, 1, 2, 3
 EXPORTS = [
     "mw_create", "mw_destroy", "mw_last_error", "mw_upload_texture", "mw_upload_mesh",
     "mw_set_geometry", "mw_get_geometry", "mw_set_state", "mw_get_state", "mw_set_step_params", "mw_reset",
-    "mw_step", "mw_step_repeat", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
+    "mw_step", "mw_step_repeat", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_frame_cache", "mw_get_frame_source", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
     "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
     "mw_selftest_sincosf",
     "mw_set_frame_stack", "mw_stack_refresh", "mw_stack_window",
@@ -207,6 +207,8 @@ def load_library():
     L.mw_get_reset_pending.argtypes = [vp, vp, vp]
     L.mw_set_frame_reuse.argtypes = [vp, i32]
     L.mw_get_frame_clean.argtypes = [vp, vp, vp]
+    L.mw_set_frame_cache.argtypes = [vp, i32]
+    L.mw_get_frame_source.argtypes = [vp, vp, vp]
     L.mw_get_list_lengths.argtypes = [vp, i32, i32, vp, vp]
     L.mw_debug_set_mesh_frame_seq.argtypes = [vp, C.c_uint32]
     L.mw_debug_get_slow_heads.argtypes = [vp, vp, vp]
@@ -217,6 +219,14 @@ def load_library():
 def frame_reuse_allowed() -> bool:
     """MW_FRAME_REUSE=0 forces frame reuse off, whatever a caller asks for: the A/B switch of an unchanged benchmark run."""
     return os.environ.get("MW_FRAME_REUSE", "1").strip() != "0"
+
+
+MAX_FRAME_CACHE = 8     # MW_FC_MAX_SLOTS
+
+
+def frame_cache_allowed() -> bool:
+    """MW_FRAME_CACHE=0 forces the frame cache off, whatever a caller asks for: the A/B switch of an unchanged benchmark run."""
+    return os.environ.get("MW_FRAME_CACHE", "1").strip() != "0"
 
 
 def stack_slots(depth: int, push: int):
@@ -254,6 +264,7 @@ class Engine:
             raise EngineError(f"mw_create failed ({rc}): {self.lib.mw_last_error(None).decode()}")
         self.h = h
         self.frame_reuse = False
+        self.frame_cache = 0
 
     def _check(self, rc, what):
         if rc != 0:
@@ -572,6 +583,26 @@ class Engine:
         self._check(self.lib.mw_set_frame_reuse(self.h, int(on)), "mw_set_frame_reuse")
         self.frame_reuse = on
         return on
+
+    def set_frame_cache(self, slots: int):
+        """The engine keeps every env's last `slots` distinct drawn frames (0 .. MAX_FRAME_CACHE, 0 = off) and copies one instead
+        of drawing when the env is back in the state it shows (include/mwengine.h: mw_set_frame_cache; num_envs x slots x H x W x 3
+        bytes, and as many floats with depth).  MW_FRAME_CACHE=0 in the environment forces it off (the A/B switch); returns what is
+        in effect."""
+        slots = int(slots) if frame_cache_allowed() else 0
+        self._check(self.lib.mw_set_frame_cache(self.h, slots), "mw_set_frame_cache")
+        self.frame_cache = slots
+        return slots
+
+    def get_frame_source(self, out=None):
+        """uint8[N] on the device: where each env's frame of the last plain step came from — 0 drawn, 1 left alone as clean (frame
+        reuse), 2 + j copied from slot j of the frame cache.  Written into `out` when given."""
+        import torch
+        if out is None:
+            out = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (self.N,) and out.is_contiguous()
+        self._check(self.lib.mw_get_frame_source(self.h, out.data_ptr(), _stream_ptr(self.device)), "mw_get_frame_source")
+        return out
 
     def get_frame_clean(self, out=None):
         """uint8[N] on the device: 1 = the env's frame after the last step is bit for bit the frame before it (a blocked move, a

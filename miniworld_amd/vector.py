@@ -35,6 +35,15 @@ that frame (`MiniWorldVecEnv(frame_reuse=True)`, the default).  A wrapper that n
 find its own writes again in the rows of such envs — copy first (`obs.clone()`, `obs.float()`), or pass `frame_reuse=False`, which
 draws every env on every step.  `to_numpy=True` hands out host copies and is not affected.  Results are bit for bit the same
 either way; `self.vec.frame_clean()` tells a consumer which rows did not change.
+
+**`frame_cache`: on for exploration, off for a policy that never turns back.**  The engine keeps every env's last `frame_cache` (default 4)
+distinct drawn frames on the device and copies one instead of drawing when the env is back in the state it shows — a third of the steps
+of a near-uniform policy, +15 % env-steps/s on Hallway.  A policy that never returns to a state gains nothing and pays one more store
+of every frame: -3.7 % with always-turn-left.  For such a consumer:
+
+    envs = MiniWorldVectorEnv("MiniWorld-Hallway-v0", num_envs=4096, frame_cache=0)
+
+Results are bit for bit the same either way; it costs 59 MB of device memory per slot at 4096 envs of 80x60 (78 MB more with depth).
 """
 from __future__ import annotations
 
@@ -49,10 +58,11 @@ class MiniWorldVectorEnv(VectorEnvBase):
     metadata = {"autoreset_mode": AUTORESET_SAME_STEP, "render_modes": ["rgb_array"]}
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
-                 frame_reuse: bool = True, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset", **kwargs):
+                 frame_reuse: bool = True, frame_cache: int = 4, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset", **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
         False draws every env on every step, for consumers that write into the returned observation tensor (module docstring).
+        frame_cache: slots per env of the engine's cache of drawn frames (MiniWorldVecEnv's frame_cache; 0 turns it off).
         action_repeat > 1: every step() holds the action for up to that many env steps (MiniWorldVecEnv.step's `repeat`) and
         info["substeps"] (int32[N]) tells how many each env took.
         frame_stack=K, stack_pad: observations (and the observation spaces) become the stacks of the last K frames, oldest first
@@ -63,6 +73,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
             raise ValueError(f"action_repeat must be an integer in 1 .. 256, not {action_repeat!r}")
         self.action_repeat = int(action_repeat)
         kwargs["frame_reuse"] = frame_reuse
+        kwargs["frame_cache"] = frame_cache
         if frame_stack is not None:
             kwargs["frame_stack"], kwargs["stack_pad"] = frame_stack, stack_pad
         mode = str(getattr(autoreset_mode, "name", autoreset_mode)).lower().replace("_", "-")     # (an AutoresetMode: its name)
