@@ -5,6 +5,11 @@ on the device (a save kernel, a load kernel, a frame).  No state leaves the GPU 
 would have; here they diverge again because each member draws its own actions.
 
     python examples/fork_best.py --env MiniWorld-Hallway-v0 --envs 1024 --steps 200 --every 20
+    python examples/fork_best.py --frame-stack 4        # a policy input of the last 4 frames: the fork carries the frames too
+
+With `--frame-stack K` the members keep a stack of their last K frames (`vec.stack`) and the fork is `vec.fork(src, frames=True)`: the
+copy gets its source's observation and stack — what a policy that reads the stack saw in the source — through four copy kernels, and
+no frame is drawn.  The default fork redraws and starts every copy's stack over from its one new frame.
 
 `vec.save_state()` / `vec.load_state(snap)` are the other two calls: a checkpoint (`torch.save(snap.cpu().state_dict(), path)`) and
 "go back to a state seen earlier".
@@ -24,13 +29,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--every", type=int, default=20, help="steps between two selections")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--frame-stack", type=int, default=None, metavar="K", help="keep the last K frames per member; forks then carry the frames")
     args = ap.parse_args()
 
     import torch
     from miniworld_amd.vec_env import MiniWorldVecEnv
 
     n = args.envs
-    vec = MiniWorldVecEnv(args.env, n, seed=args.seed)
+    vec = MiniWorldVecEnv(args.env, n, seed=args.seed, frame_stack=args.frame_stack)
+    carry_frames = args.frame_stack is not None
     vec.reset()
     g = torch.Generator(device="cuda").manual_seed(args.seed)
     score = torch.zeros(n, device="cuda")
@@ -46,7 +53,7 @@ def main():
             order = torch.argsort(score, descending=True)
             src = torch.arange(n, device="cuda")
             src[order[n // 2:]] = order[:n - n // 2]
-            vec.fork(src)
+            vec.fork(src, frames=carry_frames)
             total += float(score.sum())
             score.zero_()
             forks += 1

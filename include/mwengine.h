@@ -480,6 +480,44 @@ int mw_snapshot_save(mw_engine *e, const int32_t *d_envs, int32_t count, uint8_t
  * next world; a record whose spare was consumed restores an env whose spare the next step's refill regenerates. */
 int mw_snapshot_load(mw_engine *e, const int32_t *d_envs, const int32_t *d_recs, int32_t count,
                      const uint8_t *d_snap, int32_t n_recs, int32_t capacity, void *stream);
+/* Frame records, the opt-in companion of the state records: what the agent SAW, in a second caller-owned device buffer, so that a load
+ * or fork can put the frames back instead of drawing them again.  A frame record holds
+ *   - the env's row of d_obs as it stands at the save, in the layout of mw_set_obs_layout — whatever the row holds: the engine cannot
+ *     know whether it is the env's current frame (after a step or render into d_obs it is);
+ *   - with MW_SNAPF_DEPTH, its row of d_depth;
+ *   - with MW_SNAPF_STACK, its `depth` stacked frames in WINDOW order, oldest first (mw_stack_window), and its stack flag byte ("rebuild
+ *     on the next push": reset and not refreshed, or a next-step reset pending).  Window order does not depend on the ring position:
+ *     a record is valid at any later push count and in another engine.
+ *   the buffer  opaque, 16-byte aligned, mw_snapshot_frames_bytes(capacity, flags) bytes.  A 64-byte header carries a key — a format
+ *               number, obs_width, obs_height, the obs layout, the bytes of a frame, flags, the stack depth, capacity —, the records
+ *               follow record-major (a frame is contiguous), each section 16-byte aligned.  Compatible between engines of the same frame
+ *               configuration in one process, whatever their num_envs.  It must not overlap d_obs, d_depth or the stack's ring.
+ * Both calls are one kernel launch, asynchronous on `stream` and ordered there like any other call: a save behind a step sees that
+ * step's frames and its push.  d_envs / d_recs as for the state records.
+ * Errors.  MW_E_INVALID before anything is launched: a null engine, d_frames or d_obs; a misaligned d_frames; count < 0,
+ * count > capacity, n_recs > capacity; count > num_envs on a load or on a save with d_envs == NULL; unknown flag bits; MW_SNAPF_DEPTH
+ * with a null d_depth; MW_SNAPF_STACK without a frame stack or under another obs layout than the stack was set under.  On the device
+ * every env and record index is tested and a load compares the key (flags included: a buffer is loaded with the flags it was saved
+ * with): an offending item writes nothing and sets the status bit that mw_check reports as MW_E_INVALID. */
+enum { MW_SNAPF_DEPTH = 1, MW_SNAPF_STACK = 2 };
+/* bytes of a buffer for `capacity` frame records under `flags` (host value, no sync; < 0 on error: capacity < 0, unknown flag bits,
+ * MW_SNAPF_STACK without a frame stack or under another obs layout than the stack was set under) */
+int64_t mw_snapshot_frames_bytes(const mw_engine *e, int32_t capacity, int32_t flags);
+/* frame record k (k < count <= capacity) := the frames of env d_envs[k]; d_envs == NULL: env k, count <= num_envs.  Writes the header.
+ * Changes nothing in the engine. */
+int mw_snapshot_save_frames(mw_engine *e, const int32_t *d_envs, int32_t count, const uint8_t *d_obs, const float *d_depth,
+                            uint8_t *d_frames, int32_t capacity, int32_t flags, void *stream);
+/* env d_envs[k]'s rows of d_obs / d_depth := frame record d_recs[k].  Targets are distinct, records may repeat.  With MW_SNAPF_STACK the
+ * env's row of the ring is written so that it is exactly the row the env would have had it pushed the record's `depth` frames itself,
+ * at the engine's current push count: window frame k goes to slot first + k (mw_stack_window's first slot) and to the mirror slot
+ * `depth` away where that lies inside 0 .. 2 * depth - 2, so this window and every later one are right and the ring position does not
+ * move; the env's flag byte := the record's (an env saved while still marked for a rebuild stays marked: its next push or
+ * mw_stack_refresh rebuilds it as ever).  The host sequence of a restore that carries its frames is mw_snapshot_load, then
+ * mw_snapshot_load_frames with the same index arrays — no mw_render, no mw_stack_refresh: the env's observation is the one its source
+ * returned (a picked-up object's last appearance included, which a redraw of the restored state does not show) and its stack is its
+ * source's.  Like every call that writes d_obs it drops the frame that frame reuse holds; the frame cache stays (no state changed). */
+int mw_snapshot_load_frames(mw_engine *e, const int32_t *d_envs, const int32_t *d_recs, int32_t count, const uint8_t *d_frames,
+                            int32_t n_recs, int32_t capacity, int32_t flags, uint8_t *d_obs, float *d_depth, void *stream);
 
 /* checks the device-side status word (capacity overflows, items a snapshot call skipped); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);

@@ -1200,6 +1200,53 @@ int snapshot_grid(mw_engine *e, const char *what, int count, int *item_chunks, u
     return MW_OK;
 }
 
+// Frame records (mw_snapshot_save_frames / mw_snapshot_load_frames; mw_snapframes.h): what of the engine's frame configuration shapes
+// one under `flags`
+MwSnapfConfig snapf_config(const mw_engine *e, int32_t flags)
+{
+    MwSnapfConfig c{};
+    c.W = e->cfg.obs_width; c.H = e->cfg.obs_height; c.layout = e->obs_layout; c.flags = flags;
+    c.stack_depth = (flags & MW_SNAPF_STACK) ? e->stack.depth : 0;
+    c.frame_bytes = obs_row_bytes(e);
+    return c;
+}
+
+// the arguments both calls share, checked before anything is launched; then the kernel's view of the call
+int snapf_args(mw_engine *e, const char *what, const void *d_frames, const void *d_obs, const void *d_depth, int32_t count, int32_t n_recs,
+               int32_t capacity, int32_t flags, bool whole_batch_limit, MwSnapfArgs *out, unsigned *grid)
+{
+    if (const int rc = snapshot_args(e, what, d_frames, count, capacity, whole_batch_limit)) return rc;
+    if (n_recs < 0 || n_recs > capacity) return fail(e, MW_E_INVALID, "%s: n_recs %d outside 0 .. capacity %d", what, (int)n_recs, (int)capacity);
+    if (!d_obs) return fail(e, MW_E_INVALID, "%s: d_obs is null", what);
+    if (flags & ~(MW_SNAPF_DEPTH | MW_SNAPF_STACK)) return fail(e, MW_E_INVALID, "%s: unknown flag bits in %d", what, (int)flags);
+    if ((flags & MW_SNAPF_DEPTH) && !d_depth) return fail(e, MW_E_INVALID, "%s: MW_SNAPF_DEPTH with a null d_depth", what);
+    if ((flags & MW_SNAPF_STACK) && !e->stack.depth) return fail(e, MW_E_INVALID, "%s: MW_SNAPF_STACK without a frame stack (mw_set_frame_stack)", what);
+    if (flags & MW_SNAPF_STACK)
+        if (const int rc = stack_check(e, what)) return rc;
+    const MwSnapfConfig c = snapf_config(e, flags);
+    const MwSnapfLayout L = mw_snapf_layout(c, capacity);
+    MwSnapfArgs a{};
+    a.key = mw_snapf_key(c, capacity);
+    for (int s = 0; s < MW_SF_COUNT; ++s) a.off[s] = L.off[s];
+    a.frame_bytes = c.frame_bytes;
+    a.depth_bytes = L.rec_bytes[MW_SF_DEPTH];
+    a.N = e->cfg.num_envs; a.count = count; a.n_recs = n_recs;
+    a.stack_depth = c.stack_depth;
+    a.first_slot = c.stack_depth ? stack_phase(e) : 0;
+    // 16-byte units: every base and every size a multiple of 16 (the sections always are: mw_snapframes.h)
+    a.wide = (((uintptr_t)d_frames | (uintptr_t)d_obs | (uintptr_t)(a.depth_bytes ? d_depth : nullptr) | (uintptr_t)(c.stack_depth ? e->stack.ring : nullptr) |
+               (uintptr_t)a.frame_bytes | (uintptr_t)a.depth_bytes) & 15u) == 0;
+    const uint64_t unit = a.wide ? 16 : 1, chunk = (uint64_t)MW_SNAPF_THREADS * MW_SNAPF_UNROLL * unit;
+    const uint64_t frame_chunks = (a.frame_bytes + chunk - 1) / chunk, depth_chunks = (a.depth_bytes + chunk - 1) / chunk;
+    const uint64_t per_item = frame_chunks * (1 + (uint64_t)c.stack_depth) + depth_chunks, blocks = per_item * (uint64_t)count;
+    if (blocks > 0x7FFFFFFFull)
+        return fail(e, MW_E_INVALID, "%s: %d items need %llu workgroups, more than one launch holds: split the call", what, (int)count, (unsigned long long)blocks);
+    a.frame_chunks = (int32_t)frame_chunks; a.depth_chunks = (int32_t)depth_chunks; a.chunks_per_item = (int32_t)per_item;
+    *out = a;
+    *grid = (unsigned)std::max<uint64_t>(blocks, 1);
+    return MW_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1749,6 +1796,45 @@ int mw_snapshot_load(mw_engine *e, const int32_t *d_envs, const int32_t *d_recs,
     return MW_OK;
 }
 
+int64_t mw_snapshot_frames_bytes(const mw_engine *e, int32_t capacity, int32_t flags)
+{
+    if (!e || capacity < 0 || (flags & ~(MW_SNAPF_DEPTH | MW_SNAPF_STACK))) return MW_E_INVALID;
+    // (stacked frames are those of the layout the stack was set under, as for the two calls: stack_check's own test, no message)
+    if ((flags & MW_SNAPF_STACK) && (!e->stack.depth || e->stack.layout != e->obs_layout || e->stack.frame_bytes != obs_row_bytes(e))) return MW_E_INVALID;
+    return (int64_t)mw_snapf_layout(snapf_config(e, flags), capacity).total;
+}
+
+int mw_snapshot_save_frames(mw_engine *e, const int32_t *d_envs, int32_t count, const uint8_t *d_obs, const float *d_depth, uint8_t *d_frames,
+                            int32_t capacity, int32_t flags, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    MwSnapfArgs a;
+    unsigned grid = 1;
+    if (const int rc = snapf_args(e, "mw_snapshot_save_frames", d_frames, d_obs, d_depth, count, capacity, capacity, flags, d_envs == nullptr, &a, &grid)) return rc;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(mw_snapshot_save_frames_kernel, dim3(grid), dim3(MW_SNAPF_THREADS), 0, (hipStream_t)stream, a, d_envs, e->args.status, d_obs,
+                       reinterpret_cast<const uint8_t *>(a.depth_bytes ? d_depth : nullptr), (const uint8_t *)(a.stack_depth ? e->stack.ring : nullptr),
+                       (const uint8_t *)(a.stack_depth ? stack_flags(e, e->stack.cur) : nullptr), d_frames);
+    HIP_TRY(e, hipGetLastError());
+    return MW_OK;
+}
+
+int mw_snapshot_load_frames(mw_engine *e, const int32_t *d_envs, const int32_t *d_recs, int32_t count, const uint8_t *d_frames, int32_t n_recs,
+                            int32_t capacity, int32_t flags, uint8_t *d_obs, float *d_depth, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    MwSnapfArgs a;
+    unsigned grid = 1;
+    if (const int rc = snapf_args(e, "mw_snapshot_load_frames", d_frames, d_obs, d_depth, count, n_recs, capacity, flags, true, &a, &grid)) return rc;
+    ON_DEVICE(e);
+    drop_held_frame(e);     // (rows of d_obs are written; the frame cache stays: no state changed)
+    hipLaunchKernelGGL(mw_snapshot_load_frames_kernel, dim3(grid), dim3(MW_SNAPF_THREADS), 0, (hipStream_t)stream, a, d_envs, e->args.status, d_recs, d_frames,
+                       d_obs, reinterpret_cast<uint8_t *>(a.depth_bytes ? d_depth : nullptr), a.stack_depth ? e->stack.ring : nullptr,
+                       a.stack_depth ? stack_flags(e, e->stack.cur) : nullptr);
+    HIP_TRY(e, hipGetLastError());
+    return MW_OK;
+}
+
 int mw_check(mw_engine *e, void *stream)
 {
     if (!e) return MW_E_INVALID;
@@ -1759,7 +1845,8 @@ int mw_check(mw_engine *e, void *stream)
     if (st & MW_ST_VIS_OVERFLOW) return fail(e, MW_E_OVERFLOW, "more than max_visible=%d visible primitives in some env", e->cfg.max_visible);
     if (st & MW_ST_PLACEMENT_FAIL) return fail(e, MW_E_OVERFLOW, "device-side placement did not converge in some env");
     if (st & MW_ST_SNAPSHOT_BAD)
-        return fail(e, MW_E_INVALID, "mw_snapshot_save / mw_snapshot_load skipped an item: an env or record index out of range, or a record buffer of another layout (key mismatch)");
+        return fail(e, MW_E_INVALID, "mw_snapshot_save / mw_snapshot_load / mw_snapshot_save_frames / mw_snapshot_load_frames skipped an item: an env or record index out of range, or a record "
+                    "buffer of another layout (key mismatch)");
     return MW_OK;
 }
 

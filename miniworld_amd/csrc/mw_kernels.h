@@ -4,6 +4,7 @@
 #pragma once
 #include "mw_device.h"
 #include "mw_snapshot.h"
+#include "mw_snapframes.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine.hip)
@@ -153,6 +154,19 @@ extern "C" __global__ void mw_snapshot_save_kernel(MW_SNAP_ARGS, uint8_t *__rest
 //   frame_clean, occ_valid, stack_flags  what a load resets for every env it writes (the last two may be null)
 extern "C" __global__ void mw_snapshot_load_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap, const int32_t *__restrict__ d_recs, int n_recs,
                                                    uint8_t *__restrict__ frame_clean, int32_t *__restrict__ occ_valid, uint8_t *__restrict__ stack_flags);
+
+// frame records (mw_snapframes.hip; the layout and MwSnapfArgs: mw_snapframes.h): one launch per call, a 1-D grid of MW_SNAPF_THREADS
+// lanes, workgroup (item, chunk of the record: its obs row, its depth row, its K window frames).  Items and their index tests as for
+// the state records; a load compares the key first.  The frame buffer does not alias obs, depth or the ring (the caller's contract).
+//   obs, depth, ring, stack_flags  the caller's rows, the stack's ring and the CURRENT half of its flag bytes (depth / the last two:
+//                                  null without MW_SNAPF_DEPTH / MW_SNAPF_STACK)
+#define MW_SNAPF_ARGS MwSnapfArgs a, const int32_t *__restrict__ d_envs, uint32_t *__restrict__ status
+extern "C" __global__ void mw_snapshot_save_frames_kernel(MW_SNAPF_ARGS, const uint8_t *__restrict__ obs, const uint8_t *__restrict__ depth,
+                                                          const uint8_t *__restrict__ ring, const uint8_t *__restrict__ stack_flags,
+                                                          uint8_t *__restrict__ frames);
+extern "C" __global__ void mw_snapshot_load_frames_kernel(MW_SNAPF_ARGS, const int32_t *__restrict__ d_recs, const uint8_t *__restrict__ frames,
+                                                          uint8_t *__restrict__ obs, uint8_t *__restrict__ depth, uint8_t *__restrict__ ring,
+                                                          uint8_t *__restrict__ stack_flags);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -21,6 +21,7 @@ ABI_VERSION = 4
 MAX_REPEAT = 256            # MW_MAX_REPEAT
 MAX_STACK = 16              # MW_MAX_STACK
 STACK_PAD_RESET, STACK_PAD_ZERO = 0, 1
+SNAPF_DEPTH, SNAPF_STACK = 1, 2     # MW_SNAPF_*
 ENT_NONE, ENT_BOX, ENT_MESH, ENT_FRAME = 0, 1, 2, 3
 POLY_ENTITY = 0x100          # mw_poly.nv flag: quad of a static entity, not a room
 POLY_XF = 0x200              # ... drawn under its own glTranslatef / glRotatef (mw_poly.xf)
@@ -42,6 +43,7 @@ EXPORTS = [
     "mw_selftest_sincosf",
     "mw_set_frame_stack", "mw_stack_refresh", "mw_stack_window",
     "mw_snapshot_bytes", "mw_snapshot_save", "mw_snapshot_load",
+    "mw_snapshot_frames_bytes", "mw_snapshot_save_frames", "mw_snapshot_load_frames",
 ]
 
 
@@ -198,6 +200,10 @@ def load_library():
     L.mw_snapshot_bytes.restype = C.c_int64
     L.mw_snapshot_save.argtypes = [vp, vp, i32, vp, i32, vp]
     L.mw_snapshot_load.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp]
+    L.mw_snapshot_frames_bytes.argtypes = [vp, i32, i32]
+    L.mw_snapshot_frames_bytes.restype = C.c_int64
+    L.mw_snapshot_save_frames.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp]
+    L.mw_snapshot_load_frames.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]
     L.mw_pcg64_draws.argtypes = [C.c_uint64, i32, vp, vp]
     L.mw_check.argtypes = [vp, vp]
     L.mw_kernel_time_ms.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -496,6 +502,66 @@ class Engine:
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         self._check(self.lib.mw_snapshot_load(self.h, ptr(envs), ptr(records), int(count), C.c_void_p(buf.data_ptr()), int(n_recs), int(capacity),
                                               _stream_ptr(self.device)), "mw_snapshot_load")
+
+    def snapshot_frames_bytes(self, capacity: int, flags: int = 0) -> int:
+        """Bytes of a device buffer that holds `capacity` frame records under `flags` (SNAPF_DEPTH | SNAPF_STACK;
+        include/mwengine.h: mw_snapshot_frames_bytes)."""
+        n = int(self.lib.mw_snapshot_frames_bytes(self.h, int(capacity), int(flags)))
+        if n < 0:
+            raise EngineError(f"mw_snapshot_frames_bytes failed ({n}): capacity {capacity!r}, flags {flags!r}")
+        return n
+
+    def _frames_buffer(self, buf, capacity, flags):
+        import torch
+        need = self.snapshot_frames_bytes(capacity, flags)
+        if buf.device != self.device or buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.numel() < need:
+            raise EngineError(f"frame record buffer: need a contiguous uint8 tensor of at least {need} bytes on {self.device} for {capacity} records "
+                              f"(flags {flags}), got {buf.dtype} {tuple(buf.shape)} on {buf.device}")
+
+    def _frame_rows(self, obs, depth, flags):
+        """The kernels index `obs` / `depth` by env through raw pointers: they must be the step's buffers (obs_buffer()'s dtype and
+        size in the current layout, float32 [N, H, W] depth), and SNAPF_DEPTH needs a depth tensor."""
+        import torch
+        grey = self.obs_layout == OBS_GREY_F64
+        if obs is None:
+            raise EngineError("frame records: obs is None")
+        self._dev_tensor(obs, "obs", torch.float64 if grey else torch.uint8, self.N * self.H * self.W * (1 if grey else 3))
+        if (flags & SNAPF_DEPTH) and depth is None:
+            raise EngineError("frame records: SNAPF_DEPTH without a depth tensor")
+        self._dev_tensor(depth, "depth", torch.float32, self.N * self.H * self.W)
+
+    def snapshot_save_frames(self, buf, capacity: int, obs, depth=None, flags: int = 0, envs=None, count: int | None = None):
+        """Frame record k of `buf` := env envs[k]'s row of `obs`, with SNAPF_DEPTH its row of `depth`, with SNAPF_STACK its stacked
+        frames and stack flag (envs=None: env k, for k < count, default all envs); `buf` is a uint8 device tensor of
+        snapshot_frames_bytes(capacity, flags) bytes that overlaps none of them.  Asynchronous on the current stream, one kernel;
+        returns the number of records written (mw_snapshot_save_frames)."""
+        envs = self._index_tensor(envs, "envs")
+        count = (self.N if envs is None else envs.numel()) if count is None else int(count)
+        self._frames_buffer(buf, capacity, flags)
+        self._frame_rows(obs, depth, flags)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.mw_snapshot_save_frames(self.h, ptr(envs), count, ptr(obs), ptr(depth), C.c_void_p(buf.data_ptr()), int(capacity),
+                                                     int(flags), _stream_ptr(self.device)), "mw_snapshot_save_frames")
+        return count
+
+    def snapshot_load_frames(self, buf, n_recs: int, capacity: int, obs, depth=None, flags: int = 0, envs=None, records=None,
+                             count: int | None = None):
+        """Env envs[k]'s rows of `obs` / `depth` (and with SNAPF_STACK its frame stack and stack flag) := frame record records[k] of
+        `buf`, saved under the same `flags`.  Called behind snapshot_load() with the same indices it replaces render() and
+        stack_refresh(): the frames are the ones the records' sources returned.  Asynchronous on the current stream, one kernel
+        (mw_snapshot_load_frames)."""
+        envs, records = self._index_tensor(envs, "envs"), self._index_tensor(records, "records")
+        if count is None:
+            count = envs.numel() if envs is not None else records.numel() if records is not None else min(int(n_recs), self.N)
+        for t, name in ((envs, "envs"), (records, "records")):
+            if t is not None and t.numel() != count:
+                raise EngineError(f"{name}: {t.numel()} indices for {count} items")
+        self._frames_buffer(buf, capacity, flags)
+        self._frame_rows(obs, depth, flags)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.mw_snapshot_load_frames(self.h, ptr(envs), ptr(records), int(count), C.c_void_p(buf.data_ptr()), int(n_recs),
+                                                     int(capacity), int(flags), ptr(obs), ptr(depth), _stream_ptr(self.device)),
+                    "mw_snapshot_load_frames")
 
     def render(self, obs, depth=None):
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())

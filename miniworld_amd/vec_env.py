@@ -57,27 +57,39 @@ _KIND = {
 class EnvSnapshot:
     """Records of MiniWorldVecEnv.save_state(): `data`, the engine's opaque uint8 record buffer (a torch tensor; its header carries
     the layout key of the configuration it was taken under), `count`, the valid records, and `capacity`, the records the buffer was
-    laid out for.  `.cpu()` / `.to(device)` move it, so `torch.save(snap.cpu().state_dict(), path)` and
-    `EnvSnapshot.from_state_dict(torch.load(path))` write a checkpoint and read it back."""
+    laid out for.  A snapshot taken with frames=True also holds `frames`, the engine's frame record buffer (the observation, depth
+    and stacked frames each env had at the save), `frame_flags`, the engine.SNAPF_* bits it was saved under, and `frame_stack`, the
+    stack depth K of its stacks (0: none); without frames they are None, 0 and 0.  `.cpu()` / `.to(device)` move it, so
+    `torch.save(snap.cpu().state_dict(), path)` and `EnvSnapshot.from_state_dict(torch.load(path))` write a checkpoint and read it
+    back."""
 
-    def __init__(self, data, count: int, capacity: int):
+    def __init__(self, data, count: int, capacity: int, frames=None, frame_flags: int = 0, frame_stack: int = 0):
         self.data, self.count, self.capacity = data, int(count), int(capacity)
+        self.frames = frames
+        self.frame_flags, self.frame_stack = (int(frame_flags), int(frame_stack)) if frames is not None else (0, 0)
+
+    def _with(self, move):
+        return EnvSnapshot(move(self.data), self.count, self.capacity, None if self.frames is None else move(self.frames),
+                           self.frame_flags, self.frame_stack)
 
     def to(self, device):
-        return EnvSnapshot(self.data.to(device), self.count, self.capacity)
+        return self._with(lambda t: t.to(device))
 
     def cpu(self):
         return self.to("cpu")
 
     def clone(self):
-        return EnvSnapshot(self.data.clone(), self.count, self.capacity)
+        return self._with(lambda t: t.clone())
 
     def state_dict(self):
-        return {"data": self.data, "count": self.count, "capacity": self.capacity}
+        d = {"data": self.data, "count": self.count, "capacity": self.capacity}
+        if self.frames is not None:
+            d.update(frames=self.frames, frame_flags=self.frame_flags, frame_stack=self.frame_stack)
+        return d
 
     @classmethod
     def from_state_dict(cls, d):
-        return cls(d["data"], d["count"], d["capacity"])
+        return cls(d["data"], d["count"], d["capacity"], d.get("frames"), d.get("frame_flags", 0), d.get("frame_stack", 0))
 
     def __len__(self):
         return self.count
@@ -302,6 +314,7 @@ class MiniWorldVecEnv:
         self._info_buf = None
         self._final_info_buf = None
         self._fork_buf = None           # fork()'s scratch records, made on first use
+        self._fork_frames = None        # ... and its scratch frame records (fork(src, frames=True))
 
     # ------------------------------------------------------------------ assets / worlds
     def _upload_assets(self, sc):
@@ -387,14 +400,17 @@ class MiniWorldVecEnv:
         return self.obs, self.reward, self.terminated, self.truncated
 
     # ------------------------------------------------------------------ save / restore / fork
-    def save_state(self, envs=None, capacity: int | None = None):
+    def save_state(self, envs=None, capacity: int | None = None, frames: bool = False):
         """The complete state of the envs `envs` (an integer sequence or tensor; None: all of them, in order) as an EnvSnapshot on
         the device: everything that decides their future — poses, entities, step counts, the random stream, pending removals and
         resets, the Maze's own geometry, the pre-generated next world — but no frames (include/mwengine.h: mw_snapshot_save).  One
         kernel on the current stream; nothing in this env changes.
         capacity: the records the buffer is laid out for (default: the number saved).  One load_state call moves at most that many
         envs, so a snapshot of ONE state that is to be loaded into many envs at once ("reset all of them to this cell") is taken
-        with capacity=num_envs: `vec.load_state(vec.save_state([i], capacity=n), records=torch.zeros(n, dtype=torch.int32))`."""
+        with capacity=num_envs: `vec.load_state(vec.save_state([i], capacity=n), records=torch.zeros(n, dtype=torch.int32))`.
+        frames=True: a second kernel also saves what the agent saw — the envs' rows of `self.obs`, of `self.depth` with want_depth,
+        and their frame stacks with frame_stack (mw_snapshot_save_frames) — into `snap.frames`; load_state() then puts those
+        frames back instead of drawing new ones."""
         torch = self.torch
         envs = None if envs is None else torch.as_tensor(envs)
         count = self.num_envs if envs is None else int(envs.numel())
@@ -403,30 +419,76 @@ class MiniWorldVecEnv:
             raise ValueError(f"capacity {capacity} < the {count} records to save")
         data = torch.zeros(self.engine.snapshot_bytes(capacity), dtype=torch.uint8, device=self.engine.device)
         self.engine.snapshot_save(data, capacity, envs)
-        return EnvSnapshot(data, count, capacity)
+        if not frames:
+            return EnvSnapshot(data, count, capacity)
+        flags = self._frame_flags()
+        fdata = torch.zeros(self.engine.snapshot_frames_bytes(capacity, flags), dtype=torch.uint8, device=self.engine.device)
+        self.engine.snapshot_save_frames(fdata, capacity, self.obs, self.depth, flags, envs)
+        return EnvSnapshot(data, count, capacity, fdata, flags, self.frame_stack or 0)
 
-    def load_state(self, snap, envs=None, records=None):
+    def _frame_flags(self):
+        """the engine.SNAPF_* bits of this env's frame records: depth with want_depth, the stacks with frame_stack"""
+        return (eng.SNAPF_DEPTH if self.depth is not None else 0) | (eng.SNAPF_STACK if self.frame_stack else 0)
+
+    def load_state(self, snap, envs=None, records=None, frames: bool | None = None):
         """Env envs[k] becomes record records[k] of `snap` (envs=None: env k; records=None: record k; the envs must be distinct,
         records may repeat; one call moves at most `snap.capacity` envs) and continues bit for bit as the env the record was taken from would have — on this env or on another
         one of the same configuration, whatever its num_envs.  Draws the new frames (and rebuilds the loaded envs' frame stacks as
-        reset() does) and returns `self.obs`; rewards and flags are left alone."""
+        reset() does) and returns `self.obs`; rewards and flags are left alone.
+        frames: None uses the snapshot's frame records if it has any (save_state(frames=True)), False never does, True insists
+        (ValueError without them).  With them nothing is drawn and no stack is rebuilt: the loaded envs' rows of `self.obs` /
+        `self.depth` and their stacks are copied back (mw_snapshot_load, mw_snapshot_load_frames).  What differs from the redraw:
+        the observation is the one the record's source RETURNED — a picked-up object's last appearance included, which a frame of
+        the restored state does not show — and `self.stack` is the source's stack, not a new episode's.  The snapshot's frame flags
+        and stack depth must be this env's (want_depth, frame_stack): ValueError otherwise, before anything is launched."""
+        if frames is None:
+            frames = snap.frames is not None
+        if frames:
+            if snap.frames is None:
+                raise ValueError("load_state(frames=True): the snapshot holds no frame records (save_state(frames=True))")
+            if snap.frame_flags != self._frame_flags() or snap.frame_stack != (self.frame_stack or 0):
+                raise ValueError(f"load_state: the snapshot's frame records (flags {snap.frame_flags}, frame_stack {snap.frame_stack}) are not this "
+                                 f"env's (flags {self._frame_flags()}, frame_stack {self.frame_stack or 0}: want_depth / frame_stack differ)")
         data = snap.data
         if data.device != self.engine.device:
             data = data.to(self.engine.device)
+        if not frames:
+            self.engine.snapshot_load(data, snap.count, snap.capacity, envs, records)
+            return self._redraw()
+        fdata = snap.frames
+        if fdata.device != self.engine.device:
+            fdata = fdata.to(self.engine.device)
+        envs, records = self.engine._index_tensor(envs, "envs"), self.engine._index_tensor(records, "records")
         self.engine.snapshot_load(data, snap.count, snap.capacity, envs, records)
-        return self._redraw()
+        self.engine.snapshot_load_frames(fdata, snap.count, snap.capacity, self.obs, self.depth, snap.frame_flags, envs, records)
+        return self.obs
 
-    def fork(self, src):
+    def fork(self, src, frames: bool = False):
         """src: integer tensor [N].  Env j becomes a copy of env src[j] (its stream included: copies given the same actions stay
         identical) — a whole-batch save into scratch records of this env's own and a load through `src`, two kernels and a frame;
-        returns `self.obs`."""
+        returns `self.obs`.
+        frames=True: no frame is drawn.  Env j's frame after the fork IS env src[j]'s, and it is already on the device: the frames
+        are saved and loaded through `src` like the states — save, save_frames, load, load_frames, four copy kernels.  What differs
+        from the redraw: env j's observation (and depth) is the one env src[j]'s last step returned — a picked-up object's last
+        appearance included — and its frame stack is env src[j]'s, so a policy that reads `self.stack` sees in the copy what it saw
+        in the source."""
         eng_ = self.engine
+        n = self.num_envs
         if self._fork_buf is None:
-            self._fork_buf = self.torch.empty(eng_.snapshot_bytes(self.num_envs), dtype=self.torch.uint8, device=eng_.device)
-        src = eng_._index_tensor(src, "src", self.num_envs)
-        eng_.snapshot_save(self._fork_buf, self.num_envs)
-        eng_.snapshot_load(self._fork_buf, self.num_envs, self.num_envs, None, src)
-        return self._redraw()
+            self._fork_buf = self.torch.empty(eng_.snapshot_bytes(n), dtype=self.torch.uint8, device=eng_.device)
+        src = eng_._index_tensor(src, "src", n)
+        if not frames:
+            eng_.snapshot_save(self._fork_buf, n)
+            eng_.snapshot_load(self._fork_buf, n, n, None, src)
+            return self._redraw()
+        flags = self._frame_flags()
+        if self._fork_frames is None:
+            self._fork_frames = self.torch.empty(eng_.snapshot_frames_bytes(n, flags), dtype=self.torch.uint8, device=eng_.device)
+        eng_.snapshot_save(self._fork_buf, n)
+        eng_.snapshot_save_frames(self._fork_frames, n, self.obs, self.depth, flags)
+        eng_.snapshot_load(self._fork_buf, n, n, None, src)
+        eng_.snapshot_load_frames(self._fork_frames, n, n, self.obs, self.depth, flags, None, src)
+        return self.obs
 
     def _redraw(self):
         self.engine.render(self.obs, self.depth)

@@ -1,18 +1,23 @@
-"""What saving, restoring and forking environments costs (mw_snapshot_save / mw_snapshot_load; MiniWorldVecEnv.save_state / load_state /
-fork), for Hallway x 4096, Maze x 1024 and PickupObjects (domain randomisation) x 2048.
+"""What saving, restoring and forking environments costs (mw_snapshot_save / mw_snapshot_load and their frame records,
+mw_snapshot_save_frames / mw_snapshot_load_frames; MiniWorldVecEnv.save_state / load_state / fork), for Hallway x 4096 (also with
+frame_stack=4), Maze x 1024 and PickupObjects (domain randomisation) x 2048.
 
     python tools/perf/snapshot_cost.py                        # wall time per call, alternating windows, one JSON line per config
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o snap -- python tools/perf/snapshot_cost.py --profile maze --op fork
                                                               # a run of its own, no counters: the two kernels' durations.  --op save_load:
                                                               # whole-batch save and whole-batch load; --op fork: whole-batch save and a
                                                               # load through a random index (the gather)
+                                                              # --op fork_frames: the four kernels of fork(src, frames=True)
     python tools/perf/snapshot_cost.py --bench <parent checkout>   # `python bench.py --windows 5` alternately in a built checkout of
                                                               # the parent commit and in this tree
+    python tools/perf/snapshot_cost.py --fork-vs <parent checkout> # fork(src) of the parent commit against fork(src, frames=True) of
+                                                              # this tree: alternating windows, a process each, one JSON line per config
 
 Wall time: per config one env; the timed windows alternate between save_state(), load_state(snap), fork(random src), a render alone (what
 load_state and fork end with) and the only thing a user could do before: engine.get_state() + engine.set_state() through the host —
 which does NOT carry the random stream, the spare worlds, pending removals and resets, health, the kept final info or the Maze's
-geometry, so it is the price of less.  Every window is preceded and ended by a device synchronisation.  Reported beside them: the bytes
+geometry, so it is the price of less.  Since the frame records: fork(src, frames=True) and load_state(snap_with_frames) — four and two
+copy kernels, no frame — and the two engine calls alone.  Every window is preceded and ended by a device synchronisation.  Reported beside them: the bytes
 of the records (the layout's; a save reads that much and writes it, a load the other way round); the profiled runs' kernel durations
 turn them into a rate (profiles/r10/README.md)."""
 import argparse
@@ -27,6 +32,7 @@ sys.path.insert(0, ROOT)
 
 CONFIGS = {
     "hallway": ("MiniWorld-Hallway-v0", 4096, 3, {}),
+    "hallway_stack4": ("MiniWorld-Hallway-v0", 4096, 3, {"frame_stack": 4}),
     "maze": ("MiniWorld-Maze-v0", 1024, 3, {}),
     "pickup_dr": ("MiniWorld-PickupObjects-v0", 2048, 5, {"domain_rand": True}),
 }
@@ -52,8 +58,11 @@ def profile(name, op, reps, warmup):
     buf = torch.zeros(e.snapshot_bytes(n), dtype=torch.uint8, device="cuda")
     src = torch.randint(0, n, (n,), generator=g, device="cuda", dtype=torch.int32)
     for _ in range(reps):
-        e.snapshot_save(buf, n)
-        e.snapshot_load(buf, n, n, None, src if op == "fork" else None)
+        if op == "fork_frames":
+            vec.fork(src, frames=True)
+        else:
+            e.snapshot_save(buf, n)
+            e.snapshot_load(buf, n, n, None, src if op == "fork" else None)
         # (a step in between: the next save reads worlds the engine has touched, as in a search loop)
         vec.step(torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32))
     torch.cuda.synchronize()
@@ -67,7 +76,8 @@ def wall(name, windows, reps, warmup):
     for _ in range(warmup):
         vec.step(torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32))
     e = vec.engine
-    snap = vec.save_state()
+    snap, snapf = vec.save_state(), vec.save_state(frames=True)
+    fflags = snapf.frame_flags
     src = torch.randint(0, n, (n,), generator=g, device="cuda", dtype=torch.int32)
 
     def host_round_trip():
@@ -76,9 +86,13 @@ def wall(name, windows, reps, warmup):
         "save_state": (lambda: vec.save_state(), reps),
         "load_state": (lambda: vec.load_state(snap), reps),
         "fork": (lambda: vec.fork(src), reps),
+        "load_state_frames": (lambda: vec.load_state(snapf), reps),
+        "fork_frames": (lambda: vec.fork(src, frames=True), reps),
         "render_alone": (lambda: e.render(vec.obs, vec.depth), reps),
         "engine_save_kernel_call": (lambda: e.snapshot_save(snap.data, n), reps),
         "engine_load_kernel_call": (lambda: e.snapshot_load(snap.data, n, n), reps),
+        "engine_save_frames_kernel_call": (lambda: e.snapshot_save_frames(snapf.frames, n, vec.obs, vec.depth, fflags), reps),
+        "engine_load_frames_kernel_call": (lambda: e.snapshot_load_frames(snapf.frames, n, n, vec.obs, vec.depth, fflags), reps),
         "host_get_state_set_state": (host_round_trip, max(1, reps // 10)),
     }
     us = {k: [] for k in variants}
@@ -105,6 +119,7 @@ def wall(name, windows, reps, warmup):
     med = {k: sorted(v)[len(v) // 2] for k, v in us.items()}
     out = {"config": name, "env_id": CONFIGS[name][0], "num_envs": n, "record_bytes": round(record_bytes, 1),
            "batch_bytes": int(e.snapshot_bytes(n)), "geometry": geometry, "calls_per_window": reps,
+           "frame_flags": fflags, "frame_stack": snapf.frame_stack, "frame_batch_bytes": int(e.snapshot_frames_bytes(n, fflags)),
            "wall_us_per_call": {k: round(v, 1) for k, v in med.items()},
            "windows_us": {k: [round(x, 1) for x in v] for k, v in us.items()},
            "host_alternative_lacks": "rng stream, spare world, pending_remove, reset_pending, health, final info, per-env geometry"}
@@ -127,17 +142,66 @@ def bench_alternation(parent, rounds, windows):
             print(json.dumps({"tree": tag, "round": r, "result": res}), flush=True)
 
 
+def fork_window(name, frames, reps, warmup):
+    """one window of forks in a process of its own (fork_vs); without `frames` it runs on a tree that has no frame records"""
+    import torch
+    vec, n, n_act, g = make(name)
+    for _ in range(warmup):
+        vec.step(torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32))
+    src = torch.randint(0, n, (n,), generator=g, device="cuda", dtype=torch.int32)
+    fork = (lambda: vec.fork(src, frames=True)) if frames else (lambda: vec.fork(src))
+    for _ in range(5):
+        fork()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fork()
+    torch.cuda.synchronize()
+    us = 1e6 * (time.perf_counter() - t0) / reps
+    vec.engine.check()
+    vec.close()
+    print(json.dumps({"us": round(us, 1)}), flush=True)
+
+
+def fork_vs(parent, names, windows, reps, warmup):
+    """fork(src) in a built checkout of the parent commit against fork(src, frames=True) in this tree: alternating windows, every
+    window a process of its own that runs this very file on its tree (--root)"""
+    for name in names:
+        us = {"parent_fork": [], "fork_frames": []}
+        for _ in range(windows):
+            for tag, root, extra in (("parent_fork", parent, []), ("fork_frames", ROOT, ["--frames"])):
+                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--root", root, "--fork-window", name, "--reps", str(reps),
+                                    "--warmup", str(warmup)] + extra, cwd=root, capture_output=True, text=True, timeout=600)
+                line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+                if p.returncode != 0 or not line:
+                    print(json.dumps({"config": name, "tree": tag, "error": (p.stdout + p.stderr)[-2000:]}), flush=True)
+                    raise SystemExit(1)
+                us[tag].append(json.loads(line[-1])["us"])
+        print(json.dumps({"config": name, "calls_per_window": reps, "windows_us": us,
+                          "every_frames_window_below_every_parent_window": max(us["fork_frames"]) < min(us["parent_fork"])}), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--configs", default="hallway,maze,pickup_dr")
+    p.add_argument("--configs", default="hallway,hallway_stack4,maze,pickup_dr")
     p.add_argument("--windows", type=int, default=5)
     p.add_argument("--reps", type=int, default=50, help="calls per timed window (the host round trip: a tenth)")
     p.add_argument("--warmup", type=int, default=100, help="steps before anything is measured")
     p.add_argument("--profile", choices=sorted(CONFIGS), help="one config, untimed: the run a profiler wraps")
-    p.add_argument("--op", choices=["save_load", "fork"], default="save_load")
+    p.add_argument("--op", choices=["save_load", "fork", "fork_frames"], default="save_load")
     p.add_argument("--bench", metavar="PARENT", help="a built checkout of the parent commit: alternate bench.py between it and this tree")
     p.add_argument("--rounds", type=int, default=2)
+    p.add_argument("--fork-vs", metavar="PARENT", help="a built checkout of the parent commit: its fork(src) against this tree's fork(src, frames=True)")
+    p.add_argument("--fork-window", choices=sorted(CONFIGS), help=argparse.SUPPRESS)
+    p.add_argument("--frames", action="store_true", help=argparse.SUPPRESS)
+    p.add_argument("--root", help=argparse.SUPPRESS)
     args = p.parse_args()
+    if args.root:               # (a window of fork_vs: the package of that tree)
+        sys.path.insert(0, os.path.abspath(args.root))
+    if args.fork_window:
+        return fork_window(args.fork_window, args.frames, args.reps, args.warmup)
+    if args.fork_vs:
+        return fork_vs(os.path.abspath(args.fork_vs), [c for c in args.configs.split(",") if c in CONFIGS], args.windows, args.reps, args.warmup)
     if args.bench:
         return bench_alternation(os.path.abspath(args.bench), args.rounds, args.windows)
     if args.profile:
