@@ -341,6 +341,40 @@ int mw_step(mw_engine *e, const int32_t *d_actions, uint8_t *d_obs, float *d_dep
 #define MW_MAX_REPEAT 256       /* keeps one launch bounded */
 int mw_step_repeat(mw_engine *e, const int32_t *d_actions, int32_t repeat, uint8_t *d_obs, float *d_depth,
                    float *d_reward, uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, void *stream);
+/* Open-loop rollouts (the inner loop of CEM, MPPI, random shooting, a tree search's rollout phase): up to `horizon` consecutive
+ * MiniWorldEnv.step(plan[k]) per env in ONE step-kernel launch, and one frame at the end or none at all — the reference's
+ * step() / render_obs() split (miniworld.py:670-730 / :1177-1221), T times step() without the T render_obs().  Arguments as
+ * mw_step_repeat's, and
+ *   d_plans        int32[horizon][N], sub-step-major: sub-step k of env i takes d_plans[k][i]
+ *   horizon        1 .. MW_MAX_PLAN; anything else is MW_E_INVALID: nothing is launched, no state is touched
+ *   d_step_reward  float[horizon][N] or NULL: the reward a single mw_step would have returned for sub-step k; 0 for every sub-step
+ *                  the env did not execute (what a planner discounts from)
+ *   d_obs          NULL: a FRAMELESS call (d_depth must be NULL too, else MW_E_INVALID)
+ * Per env and call: `for k in range(horizon): step(d_plans[k][env]); if done: break`, then the auto-reset of the engine's mode — every
+ * clause of mw_step_repeat's contract above with "the action" read as "row k's action": the env stops at the first sub-step that sets
+ * term | trunc, flags are that sub-step's, d_reward is the executed sub-steps' sum (in double, in order, rounded once), d_nsteps
+ * their count; max_episode_steps counts sub-steps and every executed one takes its three domain-randomisation draws; the auto-reset
+ * runs once, behind the last executed sub-step; a next-step env that enters with reset_pending executes 0 sub-steps and installs its
+ * world; the env's stream is consumed as sub-step 1's draws, what follows it, sub-step 2's draws, ..., then the reset's.
+ * A DRAWN call (d_obs != NULL) is mw_step_repeat behind the step kernel: one frame, the frame's tail, frame reuse and the frame cache,
+ * the two passes with final buffers, one stack push.  A plan whose rows are all equal returns, bit for bit, what
+ * mw_step_repeat(repeat = horizon) returns, and horizon = 1 what mw_step returns.
+ * A FRAMELESS call launches the step kernel (in the engine's own auto-reset mode, final buffers or not) and nothing that draws: no
+ * geometry, raster or respawn kernel, no push, no final-buffer pass.  The step kernel applies, behind the last executed sub-step, what
+ * the frame's tail of a drawn call would have: a picked-up object leaves the list (pickupobjects.py:86-88), MW_TASK_COLLECT's consumed
+ * kit respawns with its draws from the env's stream (collecthealth.py:79-98) — also on a next-step terminal sub-step, where the
+ * reference's loop draws the respawn before reset(); not when that sub-step installed a world (same-step drops it, as mw_step does).
+ * Afterwards the state, the stream, mw_get_info / mw_get_final_info / mw_get_reset_pending are those of `horizon` mw_steps with a host
+ * that reads no frame, and mw_render draws that state.  d_obs, d_depth, the final buffers and the stack's ring keep what they held:
+ * mw_get_frame_clean reports 0 for every env, the frame that frame reuse holds is dropped (the next drawn call draws every env),
+ * the frame cache is neither read nor filled and stays valid.  mw_kernel_time_ms does not sample frameless calls.
+ * Frame stack: a frameless call pushes nothing and the ring position stays.  The first push after any number of frameless calls
+ * rebuilds the stack of exactly those envs that began a new episode since their last push; every other env's window gains that
+ * call's frame as usual. */
+#define MW_MAX_PLAN MW_MAX_REPEAT
+int mw_step_plan(mw_engine *e, const int32_t *d_plans /* [horizon][N] */, int32_t horizon,
+                 uint8_t *d_obs, float *d_depth, float *d_reward, float *d_step_reward /* [horizon][N] or NULL */,
+                 uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, void *stream);
 /* Final observations of a MW_AUTORESET_SAME_STEP engine (Gymnasium's info["final_obs"] of a same-step vector env, SB3's
  * info["terminal_observation"]): d_final_obs and d_final_depth are device buffers shaped like mw_step's d_obs / d_depth (N rows in
  * the layout of mw_set_obs_layout at the time of the step).  With d_final_obs non-null, every later mw_step writes the TERMINAL

@@ -319,6 +319,14 @@ auto k1_repeat_of(const mw_engine *e, int lanes) -> decltype(&mw_step_repeat_ker
     return pcg ? mw_step_repeat_pcg_kernel : mw_step_repeat_kernel;
 }
 
+// ... and mw_step_plan's (the loop with one action per sub-step)
+auto k1_plan_of(const mw_engine *e, int lanes) -> decltype(&mw_step_plan_kernel)
+{
+    const bool pcg = e->cfg.rng_mode == MW_RNG_PCG64;
+    if (lanes) return pcg ? mw_step_plan_dense_pcg_kernel : mw_step_plan_dense_kernel;
+    return pcg ? mw_step_plan_pcg_kernel : mw_step_plan_kernel;
+}
+
 // a kernel and its list form (mw_kernels.h: MW_KERNEL_PAIR)
 template <typename... A>
 struct KernelPair {
@@ -738,24 +746,43 @@ struct Frame {
     MeshFrame mf;               // p.mesh only
 };
 
+// Which step kernels a call runs: mw_step's (repeat = horizon = 0), mw_step_repeat's (repeat > 0: up to `repeat` sub-steps per env with
+// its action, the executed count into nsteps) or mw_step_plan's (horizon > 0: d_actions is the plans, [horizon][N], and each sub-step's
+// own reward goes to step_reward) — the same launch shape for all three.
+struct StepCall {
+    int repeat = 0;
+    int32_t *nsteps = nullptr;
+    int horizon = 0;
+    float *step_reward = nullptr;
+};
+
+// the step kernel (frameless: of an mw_step_plan that no frame follows)
+void launch_k1(mw_engine *e, const MwArgs &ak, hipStream_t st, bool async_refill, const int32_t *d_actions, float *d_reward, uint8_t *d_term,
+               uint8_t *d_trunc, const StepCall &c, bool frameless = false)
+{
+    const int N = e->cfg.num_envs;
+    // spare mode: blocks appended to the grid regenerate the spare worlds consumed in earlier steps, beside the step itself
+    // (the Maze's go to the side stream: launch_side_refill)
+    const int refill_blocks = (e->spare_mode && !async_refill) ? (N + 63) / 64 : 0;
+    const int lanes = k1_dense_lanes(e), epw = lanes ? 64 / lanes : 1;      // envs per workgroup
+    const dim3 grid((N + epw - 1) / epw + refill_blocks);
+    float *reward = d_reward ? d_reward : e->d_reward_scratch;
+    uint8_t *term = d_term ? d_term : e->d_flag_scratch, *trunc = d_trunc ? d_trunc : e->d_flag_scratch + N;
+    if (c.horizon > 0)
+        hipLaunchKernelGGL(k1_plan_of(e, lanes), grid, dim3(64), 0, st, ak, lanes, d_actions, reward, term, trunc, c.horizon, c.nsteps, c.step_reward, frameless ? 1 : 0);
+    else if (c.repeat > 0) hipLaunchKernelGGL(k1_repeat_of(e, lanes), grid, dim3(64), 0, st, ak, lanes, d_actions, reward, term, trunc, c.repeat, c.nsteps);
+    else hipLaunchKernelGGL(k1_of(e, lanes), grid, dim3(64), 0, st, ak, lanes, d_actions, reward, term, trunc);
+}
+
 // the step (a render-only frame has none), the list of a FRAME_TERMINAL step's finished envs, the frame's vertex half, CollectHealth's respawns
-// (repeat > 0: mw_step_repeat's step kernel, the same launch shape, up to `repeat` sub-steps per env, the executed count into d_nsteps)
 void launch_step_and_geometry(mw_engine *e, const Frame &f, bool do_step, int frame, bool async_refill, const int32_t *d_actions,
-                              float *d_reward, uint8_t *d_term, uint8_t *d_trunc, int repeat, int32_t *d_nsteps)
+                              float *d_reward, uint8_t *d_term, uint8_t *d_trunc, const StepCall &c)
 {
     const MwArgs &a = f.a; const int N = e->cfg.num_envs;
     if (do_step) {
-        // spare mode: blocks appended to the grid regenerate the spare worlds consumed in earlier steps, beside the step itself
-        // (the Maze's go to the side stream: launch_side_refill)
-        const int refill_blocks = (e->spare_mode && !async_refill) ? (N + 63) / 64 : 0;
         MwArgs ak = a;          // the step kernel's arguments: the first pass of a final-observation step runs as a next-step terminal step
         if (frame == FRAME_TERMINAL) ak.autoreset = MW_AUTORESET_NEXT_STEP;
-        const int lanes = k1_dense_lanes(e), epw = lanes ? 64 / lanes : 1;      // envs per workgroup
-        const dim3 grid((N + epw - 1) / epw + refill_blocks);
-        float *reward = d_reward ? d_reward : e->d_reward_scratch;
-        uint8_t *term = d_term ? d_term : e->d_flag_scratch, *trunc = d_trunc ? d_trunc : e->d_flag_scratch + N;
-        if (repeat > 0) hipLaunchKernelGGL(k1_repeat_of(e, lanes), grid, dim3(64), 0, f.st, ak, lanes, d_actions, reward, term, trunc, repeat, d_nsteps);
-        else hipLaunchKernelGGL(k1_of(e, lanes), grid, dim3(64), 0, f.st, ak, lanes, d_actions, reward, term, trunc);
+        launch_k1(e, ak, f.st, async_refill, d_actions, d_reward, d_term, d_trunc, c);
     }
     if (frame == FRAME_TERMINAL)
         hipLaunchKernelGGL(mw_final_list_kernel, dim3(1), dim3(1024), 0, f.st, N, (const uint8_t *)a.reset_pending, a.pending_remove, e->d_final_list);
@@ -880,8 +907,7 @@ int launch_mesh_chain(mw_engine *e, const Frame &f, hipStream_t st)
 }
 
 int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_actions, uint8_t *d_obs, float *d_depth,
-                 float *d_reward, uint8_t *d_term, uint8_t *d_trunc, hipStream_t st, int frame = FRAME_ALL, int repeat = 0,
-                 int32_t *d_nsteps = nullptr)
+                 float *d_reward, uint8_t *d_term, uint8_t *d_trunc, hipStream_t st, int frame = FRAME_ALL, const StepCall &call = {})
 {
     if (!d_obs) return fail(e, MW_E_INVALID, "d_obs is null");
     // Frame reuse: a plain step of the whole batch into the buffers that hold the frame before it leaves the envs K1 marks clean
@@ -937,7 +963,7 @@ int launch_frame(mw_engine *e, bool do_step, int view_flags, const int32_t *d_ac
         (void)hipEventRecord(ev.a.get(), st);
     }
     const bool async_refill = e->spare_mode && do_step && e->cfg.generator == MW_GEN_MAZE;
-    launch_step_and_geometry(e, f, do_step, frame, async_refill, d_actions, d_reward, d_term, d_trunc, repeat, d_nsteps);
+    launch_step_and_geometry(e, f, do_step, frame, async_refill, d_actions, d_reward, d_term, d_trunc, call);
     if (timed) (void)hipEventRecord(ev.b.get(), st);
     int rc = MW_OK;
     if (async_refill && (rc = launch_side_refill(e, st))) return rc;
@@ -1563,17 +1589,17 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
 }
 
 // the frames of one call: one, or the two passes of a same-step step with final observations
-static int step_passes(mw_engine *e, const int32_t *d_actions, int repeat, uint8_t *d_obs, float *d_depth, float *d_reward,
-                       uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, hipStream_t st)
+static int step_passes(mw_engine *e, const int32_t *d_actions, const StepCall &call, uint8_t *d_obs, float *d_depth, float *d_reward,
+                       uint8_t *d_term, uint8_t *d_trunc, hipStream_t st)
 {
     if (!e->final_obs)
-        return launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, st, FRAME_ALL, repeat, d_nsteps);
+        return launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, st, FRAME_ALL, call);
     // Same-step auto-reset with final observations, in two passes.  1: the step as the next-step mode's terminal step — physics,
     // rule, reward, flags, final info, per-step draws; the finished envs keep their terminal state — and the frame of every env.
     // The finished envs' rows go to the final buffers.  2: they install their next world (the same install code and stream order
     // as the plain same-step step: the step's draws, then the reset's), and the frame of those envs alone overwrites their rows.
     const int N = e->cfg.num_envs;
-    int rc = launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, st, FRAME_TERMINAL, repeat, d_nsteps);
+    int rc = launch_frame(e, true, 0, d_actions, d_obs, d_depth, d_reward, d_term, d_trunc, st, FRAME_TERMINAL, call);
     if (rc != MW_OK) return rc;
     const size_t row_bytes = obs_row_bytes(e);
     hipLaunchKernelGGL(mw_final_copy_kernel, dim3(N), dim3(256), 0, st, (const int32_t *)e->d_final_list, (const uint8_t *)d_obs, e->final_obs,
@@ -1583,16 +1609,42 @@ static int step_passes(mw_engine *e, const int32_t *d_actions, int repeat, uint8
     return launch_frame(e, false, 0, e->d_action_scratch, d_obs, d_depth, nullptr, nullptr, nullptr, st, FRAME_LIST);
 }
 
-// mw_step (repeat = 0: the plain step kernels) and mw_step_repeat (1 .. MW_MAX_REPEAT: the repeat kernels)
-static int step_frames(mw_engine *e, const int32_t *d_actions, int repeat, uint8_t *d_obs, float *d_depth, float *d_reward,
-                uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, void *stream)
+// A frameless mw_step_plan: the step kernel in the engine's own auto-reset mode — it applies the frame's tail behind the last executed
+// sub-step itself —, the Maze's side-stream refill where a drawn call has one, and the stack's flag bytes.  No geometry kernel, no
+// raster, no respawn kernel, no push, no final-buffer pass; nothing is timed.  The buffers that frame reuse holds no longer show the
+// envs' states; the frame cache is neither read nor filled and stays valid (the epochs part what the call changed).
+static int step_frameless(mw_engine *e, const int32_t *d_plans, const StepCall &call, float *d_reward, uint8_t *d_term, uint8_t *d_trunc, hipStream_t st)
+{
+    drop_held_frame(e);
+    const int N = e->cfg.num_envs;
+    MwArgs a = e->args;
+    a.step_override = e->use_step_override ? e->d_step_override : nullptr;
+    uint8_t *term = d_term ? d_term : e->d_flag_scratch, *trunc = d_trunc ? d_trunc : e->d_flag_scratch + N;
+    const bool async_refill = e->spare_mode && e->cfg.generator == MW_GEN_MAZE;
+    launch_k1(e, a, st, async_refill, d_plans, d_reward, term, trunc, call, true);
+    if (async_refill)
+        if (const int rc = launch_side_refill(e, st)) return rc;
+    if (e->stack.depth) {
+        const bool installs = e->cfg.generator != MW_GEN_NONE;
+        const bool same = installs && e->cfg.autoreset == MW_AUTORESET_SAME_STEP, next = installs && e->cfg.autoreset == MW_AUTORESET_NEXT_STEP;
+        hipLaunchKernelGGL(mw_stack_plan_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, same ? (const uint8_t *)term : nullptr,
+                           same ? (const uint8_t *)trunc : nullptr, next ? (const uint8_t *)e->args.reset_pending : nullptr, stack_flags(e, e->stack.cur));
+    }
+    HIP_TRY(e, hipGetLastError());
+    return MW_OK;
+}
+
+// mw_step (the plain step kernels), mw_step_repeat (the repeat kernels) and mw_step_plan (the plan kernels; d_actions: the plans)
+static int step_frames(mw_engine *e, const char *what, const int32_t *d_actions, const StepCall &call, uint8_t *d_obs, float *d_depth, float *d_reward,
+                uint8_t *d_term, uint8_t *d_trunc, void *stream)
 {
     ON_DEVICE(e);
-    if (!d_actions) return fail(e, MW_E_INVALID, "d_actions is null");
+    if (!d_actions) return fail(e, MW_E_INVALID, "%s: %s is null", what, call.horizon ? "d_plans" : "d_actions");
     if ((e->cfg.generator == MW_GEN_PROGRAM || e->cfg.task >= MW_TASK_SIDEWALK) && !e->args.prog)
         return fail(e, MW_E_INVALID, "no placement program installed (mw_set_gen_program)");
-    if (const int rc = stack_check(e, repeat ? "mw_step_repeat" : "mw_step")) return rc;
-    const int rc = step_passes(e, d_actions, repeat, d_obs, d_depth, d_reward, d_term, d_trunc, d_nsteps, (hipStream_t)stream);
+    if (call.horizon && !d_obs) return step_frameless(e, d_actions, call, d_reward, d_term, d_trunc, (hipStream_t)stream);
+    if (const int rc = stack_check(e, what)) return rc;
+    const int rc = step_passes(e, d_actions, call, d_obs, d_depth, d_reward, d_term, d_trunc, (hipStream_t)stream);
     if (rc != MW_OK || !e->stack.depth) return rc;
     // the call's one push, behind its last raster kernel; the flags are where the step kernel wrote them (launch_step_and_geometry)
     return launch_stack(e, true, d_obs, d_term ? d_term : e->d_flag_scratch, d_trunc ? d_trunc : e->d_flag_scratch + e->cfg.num_envs, (hipStream_t)stream);
@@ -1602,7 +1654,7 @@ int mw_step(mw_engine *e, const int32_t *d_actions, uint8_t *d_obs, float *d_dep
             uint8_t *d_term, uint8_t *d_trunc, void *stream)
 {
     if (!e) return MW_E_INVALID;
-    return step_frames(e, d_actions, 0, d_obs, d_depth, d_reward, d_term, d_trunc, nullptr, stream);
+    return step_frames(e, "mw_step", d_actions, StepCall{}, d_obs, d_depth, d_reward, d_term, d_trunc, stream);
 }
 
 int mw_step_repeat(mw_engine *e, const int32_t *d_actions, int32_t repeat, uint8_t *d_obs, float *d_depth, float *d_reward,
@@ -1610,7 +1662,16 @@ int mw_step_repeat(mw_engine *e, const int32_t *d_actions, int32_t repeat, uint8
 {
     if (!e) return MW_E_INVALID;
     if (repeat < 1 || repeat > MW_MAX_REPEAT) return fail(e, MW_E_INVALID, "mw_step_repeat: repeat %d outside 1 .. %d", (int)repeat, MW_MAX_REPEAT);
-    return step_frames(e, d_actions, repeat, d_obs, d_depth, d_reward, d_term, d_trunc, d_nsteps, stream);
+    return step_frames(e, "mw_step_repeat", d_actions, StepCall{repeat, d_nsteps}, d_obs, d_depth, d_reward, d_term, d_trunc, stream);
+}
+
+int mw_step_plan(mw_engine *e, const int32_t *d_plans, int32_t horizon, uint8_t *d_obs, float *d_depth, float *d_reward,
+                 float *d_step_reward, uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (horizon < 1 || horizon > MW_MAX_PLAN) return fail(e, MW_E_INVALID, "mw_step_plan: horizon %d outside 1 .. %d", (int)horizon, MW_MAX_PLAN);
+    if (d_depth && !d_obs) return fail(e, MW_E_INVALID, "mw_step_plan: d_depth without d_obs (a frameless call draws nothing)");
+    return step_frames(e, "mw_step_plan", d_plans, StepCall{0, d_nsteps, horizon, d_step_reward}, d_obs, d_depth, d_reward, d_term, d_trunc, stream);
 }
 
 int mw_set_final_obs(mw_engine *e, uint8_t *d_final_obs, float *d_final_depth)

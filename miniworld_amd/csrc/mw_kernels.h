@@ -26,6 +26,14 @@ extern "C" __global__ void mw_step_repeat_kernel(MW_K1_REPEAT_ARGS);
 extern "C" __global__ void mw_step_repeat_pcg_kernel(MW_K1_REPEAT_ARGS);
 extern "C" __global__ void mw_step_repeat_dense_kernel(MW_K1_REPEAT_ARGS);
 extern "C" __global__ void mw_step_repeat_dense_pcg_kernel(MW_K1_REPEAT_ARGS);
+// ... and mw_step_plan's (mw_setup_plan*.hip; step_env_repeat with PLAN): `actions` is the plans, int32 [horizon][N], sub-step k of
+// every env reads row k; step_reward, float [horizon][N] or null, gets each sub-step's own reward; frameless != 0: no frame follows,
+// the kernel applies the frame's tail behind the last executed sub-step itself
+#define MW_K1_PLAN_ARGS MW_K1_ARGS, int horizon, int32_t *__restrict__ nsteps, float *__restrict__ step_reward, int frameless
+extern "C" __global__ void mw_step_plan_kernel(MW_K1_PLAN_ARGS);
+extern "C" __global__ void mw_step_plan_pcg_kernel(MW_K1_PLAN_ARGS);
+extern "C" __global__ void mw_step_plan_dense_kernel(MW_K1_PLAN_ARGS);
+extern "C" __global__ void mw_step_plan_dense_pcg_kernel(MW_K1_PLAN_ARGS);
 
 // reset, spare refill, CollectHealth respawn, same-step install, spare take-over (mw_reset.hip, mw_reset_pcg.hip)
 extern "C" __global__ void mw_reset_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all, int mark_refill);
@@ -141,6 +149,11 @@ extern "C" __global__ void mw_stack_push_kernel(MW_STACK_ARGS, const uint8_t *__
                                                 uint8_t *__restrict__ final_stack);
 extern "C" __global__ void mw_stack_refresh_kernel(MW_STACK_ARGS);
 extern "C" __global__ void mw_stack_mark_kernel(int N, const uint8_t *__restrict__ mask, int force_all, uint8_t *__restrict__ flags);
+// behind the step kernel of a frameless mw_step_plan, which pushes nothing: the current flag bytes follow the episodes that began and
+// ended inside the call (term, trunc: the call's flags where it installs worlds on the sub-step that ends an episode, else null;
+// pending: reset_pending where the env's next call installs one, else null).  One thread per env.
+extern "C" __global__ void mw_stack_plan_kernel(int N, const uint8_t *__restrict__ term, const uint8_t *__restrict__ trunc,
+                                                const uint8_t *__restrict__ pending, uint8_t *__restrict__ flags);
 
 // snapshot records (mw_snapshot.hip; the layout: mw_snapshot.h): one launch per save, one per load.  A 1-D grid of MW_SNAP_THREADS
 // lanes: first the component blocks — (row of a component, 256 consecutive items), a lane per item —, then, with per-env geometry

@@ -450,26 +450,38 @@ __device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writ
 // one left the state as it was.
 // The envs of a dense wavefront stop at different sub-steps: the trip count is the wavefront's — the loop ends when none of its
 // envs is active — and an env that has stopped is predicated off, its lanes stay in the loop.
-template <bool PER_LANE>
+//
+// PLAN: mw_step_plan's step of one env — the same loop with the action of sub-step k read from row k of `actions` ([repeat][N],
+// sub-step-major: the envs of a dense wavefront read consecutive words) and the float reward a single mw_step would have returned for
+// sub-step k stored to step_reward[k][env] (may be null), 0 for every sub-step the env did not execute.  `frameless`: no frame follows
+// the call, so the writer lane applies the frame's tail behind the LAST executed sub-step too — whatever the geometry kernel and
+// the respawn kernel of a drawn call would have found in pending_remove: nothing where that sub-step installed a world (step_env
+// leaves -1 there), the removal or the respawn on a terminal sub-step that installed none — and frame_clean is 0.  Both arguments are
+// compile-time constants of the repeat kernels, whose code they leave as it was.
+template <bool PER_LANE, bool PLAN = false>
 __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool writer, const int32_t *__restrict__ actions, int repeat,
                                        float *__restrict__ reward, uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
-                                       int32_t *__restrict__ nsteps, unsigned char *gen_ws, int *s_claim)
+                                       int32_t *__restrict__ nsteps, float *__restrict__ step_reward, bool frameless, unsigned char *gen_ws,
+                                       int *s_claim)
 {
     double sum = 0.0;
     int n = 0, tm = 0, tr = 0;
     bool clean = true, active = true;
+    int rows = 0;           // PLAN: the rows of step_reward the loop has written (the wavefront's trip count)
     for (int k = 0; k < repeat; ++k) {
         if (!ballot(active)) break;
+        float rew_k = 0.0f;
         if (active) {
-            const SubStep s = step_env<PER_LANE, true>(a, env, lane, writer, actions, reward, term, trunc, gen_ws, s_claim);
+            const SubStep s = step_env<PER_LANE, true>(a, env, lane, writer, PLAN ? actions + (size_t)k * a.N : actions, reward, term, trunc, gen_ws, s_claim);
             if (s.ran) {
                 sum += s.rew;
                 ++n;
                 tm = s.tm; tr = s.tr;
                 clean = clean && s.clean;
+                if (PLAN) rew_k = (float)s.rew;
             }
             active = s.ran && !(tm | tr) && k + 1 < repeat;
-            if (active && writer && s.remove_slot >= 0) {
+            if ((active || (PLAN && frameless)) && writer && s.remove_slot >= 0) {
                 if (a.task == MW_TASK_COLLECT) {
                     mw::collect_respawn(a, env, a.shared_geom ? 0 : env, s.remove_slot, a.ax[env], a.az[env]);
                     a.pending_remove[env] = -1;
@@ -479,6 +491,10 @@ __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool 
                 }
             }
         }
+        if (PLAN) {
+            if (writer && step_reward) step_reward[(size_t)k * a.N + env] = rew_k;
+            rows = k + 1;
+        }
         // the env's lanes reload its state for the next sub-step: after the writer's stores (the install site's pattern, at
         // workgroup scope: the lanes that reload are the writer's own wavefront, which is the whole workgroup in both forms.  The
         // device-scope __threadfence() here, an L2 write-back and invalidate per sub-step, made the dense kernel 118 us at
@@ -487,11 +503,13 @@ __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool 
         __builtin_amdgcn_wave_barrier();
     }
     if (writer) {
+        if (PLAN && step_reward)
+            for (int k = rows; k < repeat; ++k) step_reward[(size_t)k * a.N + env] = 0.0f;
         reward[env] = (float)sum;
         term[env] = (uint8_t)tm;
         trunc[env] = (uint8_t)tr;
         if (nsteps) nsteps[env] = n;
-        a.frame_clean[env] = n > 0 && clean ? 1 : 0;
+        a.frame_clean[env] = !(PLAN && frameless) && n > 0 && clean ? 1 : 0;
         a.fc_source[env] = 0;
         // the key of the state the last sub-step left, once per call, from the writer's own stores: the slot the frame shows as
         // carried is the one that leaves the list behind it, if any (step_env: remove_slot), else the carried one
@@ -506,10 +524,15 @@ __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool 
 // The two K1 sources (mw_setup.hip, mw_setup_dense.hip) compile as the plain step or, with MW_K1_REPEAT defined by the unit that
 // re-includes them (mw_setup_repeat*.hip), as mw_step_repeat's kernels: the same grid mapping and refill blocks around the
 // sub-step loop, `repeat` and `nsteps` as two more kernel parameters (mw_kernels.h).
-#ifdef MW_K1_REPEAT
+// With MW_K1_PLAN (mw_setup_plan*.hip) they compile as mw_step_plan's: the loop with PLAN set, `actions` the [horizon][N] plans.
+#if defined(MW_K1_PLAN)
+#define MW_K1_PARAMS MW_K1_PLAN_ARGS
+#define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) \
+    step_env_repeat<PER_LANE, true>(a, env, lane, writer, actions, horizon, reward, term, trunc, nsteps, step_reward, frameless != 0, ws, claim)
+#elif defined(MW_K1_REPEAT)
 #define MW_K1_PARAMS MW_K1_REPEAT_ARGS
 #define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) \
-    step_env_repeat<PER_LANE>(a, env, lane, writer, actions, repeat, reward, term, trunc, nsteps, ws, claim)
+    step_env_repeat<PER_LANE>(a, env, lane, writer, actions, repeat, reward, term, trunc, nsteps, nullptr, false, ws, claim)
 #else
 #define MW_K1_PARAMS MW_K1_ARGS
 #define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) step_env<PER_LANE>(a, env, lane, writer, actions, reward, term, trunc, ws, claim)

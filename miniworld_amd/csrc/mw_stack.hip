@@ -108,3 +108,22 @@ extern "C" __global__ void mw_stack_mark_kernel(int N, const uint8_t *__restrict
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < N && (force_all || mask[i])) flags[i] = MW_STACK_FRESH;
 }
+
+// A frameless mw_step_plan: no push, but episodes begin and end inside the call.  The env's next push rebuilds its stack iff the env
+// began an episode since its last push: MW_STACK_FRESH where the call installed a world — same-step: it set term | trunc; next-step:
+// the env entered with reset_pending, which its flag byte says (MW_STACK_PENDING: the push, the snapshot loads and this kernel keep
+// it in step with reset_pending) —, MW_STACK_PENDING where the call left reset_pending set.  In place: one thread reads and writes
+// an env's byte.
+extern "C" __global__ void mw_stack_plan_kernel(int N, const uint8_t *__restrict__ term, const uint8_t *__restrict__ trunc,
+                                                const uint8_t *__restrict__ pending, uint8_t *__restrict__ flags)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    uint8_t fl = flags[i];
+    if (term && (term[i] | trunc[i]) != 0) fl = MW_STACK_FRESH;
+    if (pending) {
+        if (fl & MW_STACK_PENDING) fl = MW_STACK_FRESH;
+        if (pending[i]) fl |= MW_STACK_PENDING;
+    }
+    flags[i] = fl;
+}

@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("MW_ENGINE_LIB") or os.path.join(_CSRC, "libmwengine.s
 
 ABI_VERSION = 4
 MAX_REPEAT = 256            # MW_MAX_REPEAT
+MAX_PLAN = MAX_REPEAT        # MW_MAX_PLAN
 MAX_STACK = 16              # MW_MAX_STACK
 STACK_PAD_RESET, STACK_PAD_ZERO = 0, 1
 SNAPF_DEPTH, SNAPF_STACK = 1, 2     # MW_SNAPF_*
@@ -38,7 +39,7 @@ PATH_TILE, PATH_QUAD, PATH_QUAD_MESH, PATH_GENERIC = 0, 1, 2, 3
 EXPORTS = [
     "mw_create", "mw_destroy", "mw_last_error", "mw_upload_texture", "mw_upload_mesh",
     "mw_set_geometry", "mw_get_geometry", "mw_set_state", "mw_get_state", "mw_set_step_params", "mw_reset",
-    "mw_step", "mw_step_repeat", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_frame_cache", "mw_get_frame_source", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
+    "mw_step", "mw_step_repeat", "mw_step_plan", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_frame_cache", "mw_get_frame_source", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
     "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
     "mw_selftest_sincosf",
     "mw_set_frame_stack", "mw_stack_refresh", "mw_stack_window",
@@ -187,6 +188,7 @@ def load_library():
     L.mw_reset.argtypes = [vp, vp, vp, vp]
     L.mw_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.mw_step_repeat.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.mw_step_plan.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mw_render.argtypes = [vp, vp, vp, vp]
     L.mw_render_top.argtypes = [vp, vp, vp, i32, vp]
     L.mw_render_view.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
@@ -408,6 +410,29 @@ class Engine:
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         self._check(self.lib.mw_step_repeat(self.h, ptr(actions), int(repeat), ptr(obs), ptr(depth), ptr(reward), ptr(term),
                                             ptr(trunc), ptr(nsteps), _stream_ptr(self.device)), "mw_step_repeat")
+
+    def step_plan(self, plans, obs, depth=None, reward=None, step_reward=None, term=None, trunc=None, nsteps=None):
+        """Open-loop rollout (include/mwengine.h: mw_step_plan): `plans` is an integer tensor [T, N], env i takes plans[0, i],
+        plans[1, i], ... until its episode ends, in one step-kernel launch.  It is converted to contiguous int32 on the device if
+        needed; the outputs are checked as for step_repeat(), `step_reward` (float32, at least T * N elements: rows 0 .. T - 1 of a
+        [*, N] buffer) receives every sub-step's own reward.  obs=None is the frameless call: nothing is drawn, `depth` must be None.
+        A wrong shape or T outside 1 .. MAX_PLAN raises before the library is called."""
+        import torch
+        if plans.dim() != 2 or plans.shape[1] != self.N or not 1 <= plans.shape[0] <= MAX_PLAN:
+            raise EngineError(f"plans: need an integer tensor [T, {self.N}] with T in 1 .. {MAX_PLAN}, got {tuple(plans.shape)}")
+        horizon = int(plans.shape[0])
+        if obs is None and depth is not None:
+            raise EngineError("step_plan: depth without obs (a frameless call draws nothing)")
+        if plans.device != self.device or plans.dtype != torch.int32 or not plans.is_contiguous():
+            plans = plans.to(device=self.device, dtype=torch.int32).contiguous()
+        self._step_tensors(plans[0], obs, depth, reward, term, trunc)       # (the output checks; row 0 stands in for step()'s actions)
+        self._dev_tensor(nsteps, "nsteps", torch.int32, self.N)
+        if step_reward is not None and (step_reward.device != self.device or step_reward.dtype != torch.float32 or
+                                        not step_reward.is_contiguous() or step_reward.numel() < horizon * self.N):
+            raise EngineError(f"step_reward: need a contiguous float32 tensor of at least {horizon * self.N} elements on {self.device}")
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.mw_step_plan(self.h, ptr(plans), horizon, ptr(obs), ptr(depth), ptr(reward), ptr(step_reward), ptr(term),
+                                          ptr(trunc), ptr(nsteps), _stream_ptr(self.device)), "mw_step_plan")
 
     def set_final_obs(self, obs=None, depth=None):
         """Same-step auto-reset: every later step writes the terminal frame (and depth) of each env whose episode ended in it into

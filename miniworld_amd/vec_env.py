@@ -289,6 +289,7 @@ class MiniWorldVecEnv:
         self.terminated = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
         self.truncated = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
         self.substeps = None            # int32[N], made by the first step(actions, repeat > 1)
+        self.step_rewards = self._step_rewards = None       # float32[T, N] of the last rollout(), a view of the buffer behind it
         self.final_obs = self.final_depth = None
         if final_obs:
             self.final_obs = self.engine.obs_buffer()
@@ -398,6 +399,31 @@ class MiniWorldVecEnv:
             self.substeps = self.torch.zeros(self.num_envs, dtype=self.torch.int32, device=self.engine.device)
         self.engine.step_repeat(actions, repeat, self.obs, self.depth, self.reward, self.terminated, self.truncated, self.substeps)
         return self.obs, self.reward, self.terminated, self.truncated
+
+    def rollout(self, plans, render: bool = True):
+        """Open-loop rollout: plans is an integer torch tensor [T, N] (converted to contiguous int32 on the engine's device if
+        needed), T in 1 .. engine.MAX_PLAN.  Env i takes plans[0, i], plans[1, i], ... in one kernel launch and stops at the step
+        that ends its episode, exactly as T calls of step() would with a host that breaks on done (then the auto-reset, once).
+        Returns (obs or None, reward, terminated, truncated): the reward is the sum, the flags the last executed step's;
+        `self.substeps` (int32[N]) holds the executed counts and `self.step_rewards` (float32[T, N], a view of a buffer grown on
+        demand) every step's own reward, 0 where the env did not execute it — what a planner discounts from.
+        render=False is the frameless call, for planners that read no frames: nothing is drawn or pushed.  `self.obs`,
+        `self.depth`, `self.stack` and the final buffers keep what they held and are STALE until the next drawn call (step(),
+        rollout(render=True)), load_state(..., frames) or reset()."""
+        torch = self.torch
+        if plans.dim() != 2 or plans.shape[1] != self.num_envs:
+            raise ValueError(f"plans: need an integer tensor [T, {self.num_envs}], got {tuple(plans.shape)}")
+        T = int(plans.shape[0])
+        if not 1 <= T <= eng.MAX_PLAN:
+            raise ValueError(f"plans: T = {T} outside 1 .. {eng.MAX_PLAN}")
+        if self.substeps is None:
+            self.substeps = torch.zeros(self.num_envs, dtype=torch.int32, device=self.engine.device)
+        if self._step_rewards is None or self._step_rewards.shape[0] < T:
+            self._step_rewards = torch.zeros((T, self.num_envs), dtype=torch.float32, device=self.engine.device)
+        self.step_rewards = self._step_rewards[:T]
+        obs, depth = (self.obs, self.depth) if render else (None, None)
+        self.engine.step_plan(plans, obs, depth, self.reward, self._step_rewards, self.terminated, self.truncated, self.substeps)
+        return obs, self.reward, self.terminated, self.truncated
 
     # ------------------------------------------------------------------ save / restore / fork
     def save_state(self, envs=None, capacity: int | None = None, frames: bool = False):
