@@ -25,7 +25,7 @@ MW_HD int mul24i(int a, int b)
 #endif
 }
 
-// integer edges of a front-facing triangle in 32 bits (frames up to 128 x 96: mw_engine.hip::tile_kernels_exact), the
+// integer edges of a front-facing triangle in 32 bits (frames up to 128 x 96: mw_policy.h::tile_kernels_exact), the
 // snapped vertices' bounds and the depth plane: mw_glmath.h::setup_triangle_pos for a multisampled target.
 struct Edges {
     int dcdx[3], dcdy[3], c[3];

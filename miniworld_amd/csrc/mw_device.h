@@ -1,8 +1,9 @@
-// mwengine internal types shared by the host runtime (mw_engine.hip) and the kernels.
+// mwengine internal types shared by the host runtime (mw_engine*.hip) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mwengine.h"
+#include "mw_shape.h"            // MW_TILE_W, MW_TILE_H, MW_LDS_RECS, MW_LDS_SHADE_Q, MW_LDS_CULL_Q
 #include "mw_asset_types.h"      // MwTexDesc, MwMeshDesc, MW_MAX_LEVELS, MW_MESH_VCAP, MW_MESH_POS_STRIDE
 
 #define MW_MAX_TEX 64
@@ -10,11 +11,6 @@
 #define MW_RASTER_REC 64     // dwords per raster record
 #define MW_SHADE_REC 32      // dwords per shade record (attribute planes, colour, tex, depth plane)
 #define MW_CULL_REC 24       // a[4] b[4] c[4] tmin[4] tmax[4] flags pad[3]
-#define MW_LDS_RECS 32       // triangle records a small-scene raster wave stages in LDS ...
-#define MW_LDS_SHADE_Q 7      // ... as the quads K2 reads of each: 7 of the shade record's 8,
-#define MW_LDS_CULL_Q 5       //     5 of the classification record's 6 (192 B per triangle: 7.5 KB + 192 B per wave, 5 waves per SIMD)
-#define MW_TILE_W 16
-#define MW_TILE_H 4
 #define MW_SKY_PID 0xFFFFu
 #define MW_ENVHDR 640         // floats per env: sky, light colours, mesh-entity table (geometry kernel -> raster kernels)
 #define MW_MAX_MESH_ENTS 21   // mesh entities drawn per env

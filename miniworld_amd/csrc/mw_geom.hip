@@ -212,7 +212,7 @@ __device__ inline bool occluded_rmq(const float *rmq, const mwgl::Vert v[4], flo
 // small scenes' kernel, whose workgroups then fit four to a CU.
 // SFIX: the target's samples per pixel when fixed at compile time (8: the observation path — a quarter of the record
 // writer's code, 36 registers less), 0: taken from the launch
-// SUB: the frame of a subset of the batch (same-step auto-reset with final observations, mw_engine.hip): group g of the grid
+// SUB: the frame of a subset of the batch (same-step auto-reset with final observations, mw_engine_frame.hip): group g of the grid
 // draws env list[1 + g] while g < list[0]; the grid stays N-sized (the host does not know the count) and a workgroup without a
 // listed env exits at once
 template <bool BIG, int SFIX, bool SUB = false>

@@ -1,4 +1,4 @@
-// The kernel interface: every kernel the host runtime (mw_engine.hip) launches, declared once.  The engine includes this header to
+// The kernel interface: every kernel the host runtime (mw_engine*.hip) launches, declared once.  The engine includes this header to
 // launch them and every translation unit that defines one includes it too, so a definition that drifts from its declaration does
 // not compile.
 #pragma once
@@ -7,7 +7,7 @@
 #include "mw_snapframes.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
-// whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine.hip)
+// whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
 #define MW_KERNEL_PAIR(stem, ...)                          \
     extern "C" __global__ void stem##_kernel(__VA_ARGS__); \
     extern "C" __global__ void stem##_sub_kernel(__VA_ARGS__, const int32_t *list)
@@ -53,16 +53,16 @@ MW_KERNEL_PAIR(mw_geom_big, MW_GEOM_ARGS);
 MW_KERNEL_PAIR(mw_geom_any, MW_GEOM_ARGS);
 MW_KERNEL_PAIR(mw_geom_big_any, MW_GEOM_ARGS);
 
-// Bit of the raster kernels' flag word (mw_engine.hip::raster_flags): the observation buffer still holds every env's last frame, so
-// an env whose frame_clean byte is set (MwArgs) is not drawn — the quad kernel's workgroup and the plain tile kernels' wavefronts
-// of that env leave at once.  Only frames without mesh entities carry it: the bit is the lowest of the field that holds the
-// slow-fragment stamp of a frame with meshes, and such a frame is always drawn in full.  The list forms never honour it.
-#define MW_RASTER_REUSE 0x10000
+// MW_RASTER_REUSE (mw_shape.h), a bit of the raster kernels' flag word (mw_policy.h::raster_flags): the observation buffer still
+// holds every env's last frame, so an env whose frame_clean byte is set (MwArgs) is not drawn — the quad kernel's workgroup and the
+// plain tile kernels' wavefronts of that env leave at once.  Only frames without mesh entities carry it: the bit is the lowest of the
+// field that holds the slow-fragment stamp of a frame with meshes, and such a frame is always drawn in full.  The list forms never
+// honour it.
 
 // the tile kernels (mw_raster.hip)
 // (the frame kernels take parameter lists, not one struct: only __restrict__ on a kernel parameter tells the compiler that the
 // buffers do not overlap, and a by-value struct's pointers lose it — measured, tools/experiments/README.md)
-// (texd == texels: the descriptor table is the head of the texel block, mw_engine.hip::upload_textures; the kernels
+// (texd == texels: the descriptor table is the head of the texel block, mw_engine.hip: upload_textures; the kernels
 // use `texels` for both)
 #define MW_RASTER_ARGS \
     int N, int W, int H, int max_vis, int tiles_x, int n_tiles, int waves_per_env, int tiles_per_wave, \
@@ -133,12 +133,10 @@ MW_KERNEL_PAIR(mw_view_raster, MW_VIEW_RASTER_ARGS);
 MW_KERNEL_PAIR(mw_view_raster_any, MW_VIEW_RASTER_ARGS);
 
 // frame stacking (mw_stack.hip): the push behind a step's last raster kernel, mw_stack_refresh's form of the same body, mw_reset's marks.
-// Grid (N, chunks of MW_STACK_THREADS * MW_STACK_UNROLL units); a unit is 16 bytes (`wide`: obs, ring, the final buffers and the frame
+// Grid (N, chunks of MW_STACK_THREADS * MW_STACK_UNROLL units: mw_shape.h); a unit is 16 bytes (`wide`: obs, ring, the final buffers and the frame
 // size are all multiples of 16) or one byte.  The per-env flag byte: MW_STACK_FRESH — reset by the host or never pushed, the stack is
 // rebuilt by mw_stack_refresh or the next push; MW_STACK_PENDING — the env's next call installs a world (next-step auto-reset), the
 // push of that call rebuilds.
-#define MW_STACK_THREADS 256
-#define MW_STACK_UNROLL 4
 #define MW_STACK_FRESH 1
 #define MW_STACK_PENDING 2
 #define MW_STACK_ARGS \
@@ -180,6 +178,13 @@ extern "C" __global__ void mw_snapshot_save_frames_kernel(MW_SNAPF_ARGS, const u
 extern "C" __global__ void mw_snapshot_load_frames_kernel(MW_SNAPF_ARGS, const int32_t *__restrict__ d_recs, const uint8_t *__restrict__ frames,
                                                           uint8_t *__restrict__ obs, uint8_t *__restrict__ depth, uint8_t *__restrict__ ring,
                                                           uint8_t *__restrict__ stack_flags);
+
+// the host runtime's own small kernels (mw_engine_kernels.hip): mw_get_info's gather; behind the first pass of a same-step step with
+// final observations, the list of the envs that finished and the copy of their rows into the final buffers
+extern "C" __global__ void mw_info_kernel(int N, int E, const int32_t *health, const double *epos, int slot, int32_t *out_health, double *out_pos);
+extern "C" __global__ void mw_final_list_kernel(int N, const uint8_t *__restrict__ pending, int32_t *__restrict__ pending_remove, int32_t *__restrict__ list);
+extern "C" __global__ void mw_final_copy_kernel(const int32_t *__restrict__ list, const uint8_t *__restrict__ obs, uint8_t *__restrict__ final_obs,
+                                                unsigned long long row_bytes, const float *__restrict__ depth, float *__restrict__ final_depth, int depth_row);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -1,0 +1,243 @@
+// The launch policy of the host runtime: which kernels draw a frame, with how many lanes, waves and workgroups, and what a frame may
+// reuse, cache or hold.  Pure arithmetic over integers and switches — plain C++17, no HIP, no engine: the runtime (mw_engine*.hip)
+// takes every such decision from here and keeps no second copy; tests/hostcheck/policy.cpp compiles it for the host.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/mwengine.h"
+#include "mw_shape.h"
+#include "mw_snapframes.h"      // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
+#include "mw_snapshot.h"        // MW_SNAP_THREADS
+
+namespace mwpolicy {
+
+// The tile / quad / mesh-scatter kernels keep edge values in 32 bits: |c_k| = |dcdx X - dcdy Y| <= 2 W H 2^16 has to stay below
+// 2^31, i.e. W H < 16384 — 128 x 96 passes, 128 x 128 does not (a wall across the whole frame lost its triangle there);
+// larger frames take the generic-resolution kernels (64-bit edge values).
+inline bool tile_kernels_exact(int W, int H) { return W <= 128 && H <= 128 && W * H <= 128 * 96; }
+
+// The frame is W x H, the size the caller asked for: the viewport, the projection and every output stride.  The raster grid is
+// the frame rounded up to whole 16 x 4 tiles, ceil16(W) x ceil4(H): tiles_x, tiles_y, n_tiles.  A frame that is not the grid
+// ("ragged": padding pixels right of column W - 1 or below row H - 1) takes, at 8 samples without mesh entities, with an even H
+// and a grid inside the tile kernels' edge bound, the ragged tile kernels (mw_raster.hip, FMT -2: padding masked, per-pixel stores); any
+// other ragged frame the generic-resolution kernels, which mask the padding per pixel too.  The quad kernel and the fixed-layout
+// tile kernels take frames on the grid only ("Frame sizes").
+inline int tiles_across(int W) { return (W + MW_TILE_W - 1) / MW_TILE_W; }
+inline int tiles_down(int H) { return (H + MW_TILE_H - 1) / MW_TILE_H; }
+inline bool frame_on_grid(int W, int H) { return W % MW_TILE_W == 0 && H % MW_TILE_H == 0; }
+inline bool tile_path_ok(int W, int H) { return frame_on_grid(W, H) && tile_kernels_exact(W, H); }
+// sizes mw_create and mw_render_view accept: at least one pixel, at most 255 tiles of grid in each direction (8-bit tile
+// coordinates of the records' bounding boxes)
+inline bool frame_size_ok(int W, int H) { return W >= 1 && H >= 1 && W <= 255 * MW_TILE_W && H <= 255 * MW_TILE_H; }
+
+// big scenes: the geometry kernel leaves a visiting order for the tile kernels (MwArgs::rec_order) exactly then
+inline bool has_visiting_order(int max_visible) { return max_visible > 64; }
+
+// lanes per env of the geometry kernel: the power of two that holds an env's triangles (two per polygon and box face, the
+// agent marker), 8 .. 64 — except that the smallest scenes get 16 lanes for their up to 32 triangles: an env's lanes go over
+// its triangles in rounds, and four envs per wavefront fill the chip with half the wavefronts of this one-wave-per-SIMD kernel
+// (measured, 4096 Hallway envs: 64 lanes 117 us, 32: 86, 16: 79, 8: 101)
+inline int geom_lanes(int max_polys, int max_ents, bool order)
+{
+    const int items = 2 * (max_polys + 6 * max_ents + 1);      // one triangle per lane
+    int L = 8;
+    while (L < items && L < 64) L <<= 1;
+    if (L == 32) L = 16;
+    // mid-sized scenes (PickupObjects: 6 polygons + 5 entity slots = 74 triangles; no visiting order, no sifting): two envs per
+    // wavefront — 2 048 envs are ONE round of this one-wave-per-SIMD kernel instead of two (K1 + KG 103 -> 71 us)
+    if (L == 64 && !order && max_polys <= 64) L = 32;
+    return L;
+}
+
+// Lanes per env of the dense K1 (mw_setup_dense.hip), or 0 when the step has to go through the wave-per-env kernel: big
+// scenes, CollectHealth, or too many slots to pack two envs into a wavefront.  (max_ents: at least one, as the engine keeps it.)
+inline int k1_dense_lanes(int max_polys, int max_ents, int max_visible, int task)
+{
+    if (has_visiting_order(max_visible) || task == MW_TASK_COLLECT) return 0;
+    // at least two envs per wavefront: with one, every lane repeats the env's scalar work for nothing and the wave-per-env
+    // kernel's lane-cooperative collision tests win (PickupObjects, 35 slots: 62 us dense against 47 us)
+    const int lanes = max_polys + 6 * max_ents;
+    return lanes <= 32 ? lanes : 0;
+}
+
+// workgroups of one wavefront over N envs at `lanes` lanes per env (0: a wavefront per env) — K1 and the geometry kernel
+inline int env_blocks(int N, int lanes)
+{
+    const int epw = lanes ? 64 / lanes : 1;
+    return (N + epw - 1) / epw;
+}
+
+// wavefronts per env of the tile kernels: enough to fill 256 CUs x 4 SIMDs x 7 resident waves several times over (measured:
+// 15-25 waves per env beat 5 by ~7 % at 4096 envs), in divisors of n_tiles
+inline int pick_waves_per_env(int n_tiles, int num_envs)
+{
+    for (int w = 1; w <= n_tiles; ++w)
+        if (n_tiles % w == 0 && (long long)num_envs * w >= 49152) return w;
+    return n_tiles;
+}
+
+// the quad kernel (mw_rasterq.hip) keeps an env's frame, quad lists and triangle records in LDS: frames up to 8192 pixels whose plan
+// (lds_bytes: mw_rasterq_lds_bytes at 4 samples for msaa = 4, else 8, with depth) fits 64 KB
+inline bool k2q_ok(int msaa, int W, int H, int lds_bytes)
+{
+    return (msaa == 8 || msaa == 4) && frame_on_grid(W, H) && W <= 128 && H <= 128 && W * H <= 8192 && lds_bytes <= 64 * 1024;
+}
+
+// Which kernels draw a frame of the engine's size (mw_raster_path), and the forms of them the launches pick: the one statement
+// of these conditions — launch_frame, the frame's mesh lists and ensure_mesh_buffers take their answer from here.
+struct RasterFacts {
+    int msaa, W, H;
+    bool meshes, order;             // meshes resident; a visiting order exists
+    bool use_k2q, generic_raster;   // the MW_K2Q / MW_GENERIC_RASTER switches
+    bool k2q_ok;                    // (k2q_ok above, worked out once by mw_create)
+    int layout, dbg_flags;
+};
+struct RasterPath {
+    int path;           // MW_PATH_TILE, MW_PATH_QUAD, MW_PATH_QUAD_MESH, MW_PATH_GENERIC
+    bool mesh;          // mesh entities through the tile / quad kernels: the frame runs the mesh chain (launch_mesh_chain) on the mesh path's lists
+    bool quad4;         // the quad kernel at 4 samples
+    // big scene: a visiting order exists; an output layout other than HWC or debug flags; a frame off the 16 x 4 grid; depth asked for
+    bool big, general, ragged, depth;
+};
+inline RasterPath raster_path(const RasterFacts &f, bool depth)
+{
+    const int S = f.msaa;
+    RasterPath p{MW_PATH_GENERIC, false, false, f.order, f.layout != MW_OBS_HWC_U8 || f.dbg_flags != 0, !frame_on_grid(f.W, f.H), depth};
+    // the quad kernel (mw_rasterq.hip): small scenes without a visiting order, frames that fit its LDS plan — 8 samples (the
+    // hot path) and 4 (llvmpipe's GL_MAX_SAMPLES: the reference's own frames run through the same code); with mesh entities
+    // it draws the tiles no mesh can touch (8 samples only)
+    // (big scenes — a visiting order exists — keep the tile kernels: their near-to-far order with its early exit is the better fit
+    // for deep scenes; the quad kernel on the Maze was measured and lost, tools/experiments/README.md)
+    const bool k2q = f.use_k2q && f.k2q_ok && !p.big && !(S == 4 && (f.meshes || f.generic_raster));
+    // a ragged frame the ragged tile kernels draw (frame_on_grid).  The even H: the tile kernels' 2x2 quads (texture lod) pair image rows from
+    // the top, GL pairs window rows from the bottom (mw_frag.h), and the two agree only then.  Odd heights take the generic-resolution kernels.
+    const bool ragged_tiles = !f.meshes && p.ragged && f.H % 2 == 0 && tile_kernels_exact(tiles_across(f.W) * MW_TILE_W, tiles_down(f.H) * MW_TILE_H);
+    p.quad4 = k2q && S == 4;
+    // FrameBuffer's fallback sample counts (opengl.py:229-231: a driver that clamps GL_MAX_SAMPLES gets 4 or 1
+    // samples), observations beyond 128 x 128 (the tile kernels' 24-bit edge arithmetic) and frames off the 16 x 4 grid:
+    // the generic-resolution kernels, 64-bit edge values, exact packed-key resolution, every output layout, the whole
+    // batch in one grid (blockIdx.y = env)
+    const bool generic = S != 8 || (!tile_path_ok(f.W, f.H) && !ragged_tiles);
+    p.mesh = !p.quad4 && !generic && f.meshes;
+    p.path = p.quad4 ? MW_PATH_QUAD : generic ? MW_PATH_GENERIC : !k2q ? MW_PATH_TILE : p.mesh ? MW_PATH_QUAD_MESH : MW_PATH_QUAD;
+    return p;
+}
+
+// The tile and quad kernels' flag word (`dbg`): the MW_DEBUG_FLAGS experiment bits, the output layout (bits 8-9,
+// mw_set_obs_layout), the part of a frame with mesh entities the launch draws (bits 4-5: 0 every tile, 1 those no mesh can touch,
+// 2 those a mesh can, 3 the same from the geometry kernel's tile list) and the frame stamp of the slow-fragment chains (bits
+// 16-31; 0 for the quad kernel, which reads bits 13-15 as experiment bits).  mw_create keeps only MW_DEBUG_BITS of MW_DEBUG_FLAGS,
+// so that no experiment flag lands in the fields beside it.
+#define MW_DEBUG_BITS 0xFCCF
+// `reuse`: MW_RASTER_REUSE (mw_kernels.h), frames without mesh entities only — it shares the stamp's field.
+inline int raster_flags(int dbg_flags, int layout, int part, uint32_t stamp, bool reuse)
+{
+    return dbg_flags | layout << 8 | part << 4 | (int)(stamp << 16) | (reuse && stamp == 0u ? MW_RASTER_REUSE : 0);
+}
+
+// bytes of one env's row of d_obs in an output layout
+inline size_t obs_row_bytes(int W, int H, int layout) { return (size_t)W * H * (layout == MW_OBS_GREY_F64 ? 8 : 3); }
+
+// Frame stacking (mw_set_frame_stack; kernels: mw_stack.hip).  phase of the last push: the window starts there (before the first push
+// every slot a refresh wrote is valid, and the same formula gives depth - 1).
+inline int stack_phase(int64_t pushes, int depth) { return (int)((pushes + depth - 1) % depth); }
+
+// Auto-reset: does it install worlds (none with MW_GEN_NONE), and on the step that ends the episode or on the env's next call
+struct ResetMode { bool installs, same, next; };
+inline ResetMode reset_mode(int generator, int autoreset)
+{
+    const bool installs = generator != MW_GEN_NONE;
+    return {installs, installs && autoreset == MW_AUTORESET_SAME_STEP, installs && autoreset == MW_AUTORESET_NEXT_STEP};
+}
+
+// What a launch_frame call is.  CALL_RENDER: no step, every env's frame.  CALL_STEP: the step kernel, then every env's frame.  The two
+// passes of a same-step step with final observations (mw_set_final_obs): CALL_TERMINAL_STEP — the step kernel runs as the next-step
+// mode's terminal step (no install; reset_pending marks the finished envs), the list of those envs is built behind it, and the frame
+// shows every env's state after the step (terminal states for the finished envs); CALL_LIST_PASS — no step, the frame of the listed
+// envs only (their new worlds), through the list forms of the geometry and raster kernels.
+enum CallKind { CALL_RENDER = 0, CALL_STEP = 1, CALL_TERMINAL_STEP = 2, CALL_LIST_PASS = 3 };
+inline bool call_steps(CallKind k) { return k == CALL_STEP || k == CALL_TERMINAL_STEP; }
+
+// The frame's policy.  Frame reuse: a plain step of the whole batch into the buffers that hold the frame before it leaves the envs K1
+// marks clean undrawn.  Any other frame — the first one, a render, a top view, the passes of a final-observation step, frames with mesh
+// entities (their sample keys and fragment lists have a protocol of their own), other buffers or another layout, experiment
+// flags — draws every env; a whole plain agent-view frame then makes its buffers the held ones, anything else leaves none.
+// The frame cache: consulted and filled by a plain step of the whole batch through the quad kernel, in the layout it was
+// allocated for, without mesh entities or experiment flags; whose buffers the frame goes to does not matter.  Every other frame
+// neither reads nor writes it.  CollectHealth never: its respawn kernel moves entities behind K1's back (as for frame_clean).
+struct FrameFacts {
+    CallKind kind;
+    int view_flags;
+    bool frame_reuse, held_match;   // mw_set_frame_reuse is on; the held buffers are valid and are this call's, in this layout
+    bool meshes;
+    int dbg_flags, layout, task;
+    bool cache_allocated;           // mw_set_frame_cache: slots > 0 and their frames exist
+    int path;                       // RasterPath::path
+};
+struct FramePolicy {
+    bool reuse;         // clean envs may stay undrawn
+    bool source;        // the quad kernel writes the per-env source byte
+    bool cache;         // ... and consults and fills the frame cache
+    bool hold;          // afterwards the call's buffers are the held ones
+};
+inline FramePolicy frame_policy(const FrameFacts &f)
+{
+    const bool plain = (f.kind == CALL_RENDER || f.kind == CALL_STEP) && f.view_flags == 0;
+    const bool plain_step = plain && f.kind == CALL_STEP, bare = !f.meshes && f.dbg_flags == 0;
+    const bool source = plain_step && f.path == MW_PATH_QUAD;
+    return {f.frame_reuse && plain_step && bare && f.held_match, source,
+            source && f.cache_allocated && bare && f.layout == MW_OBS_HWC_U8 && f.task != MW_TASK_COLLECT, plain};
+}
+
+// The tile kernels' launch (mw_raster.hip) for a part of the frame (raster_flags).  big scenes (a visiting order exists): records
+// read in place, near to far; otherwise the env's records are staged in LDS when there are at most MW_LDS_RECS of them (a wave whose
+// env holds more reads them in place).  The second part (the tiles a mesh can touch: few, slow, clustered) with a tile list:
+// persistent wavefronts over the geometry kernel's list (part 3).
+struct TileLaunch { int part, waves_per_env, tiles_per_wave, grid; size_t lds; };
+inline TileLaunch tile_launch(int part, bool tile_list, bool big, int max_vis, int n_tiles, int wpe, int N, int mesh_tile_waves)
+{
+    const int lds_recs = max_vis < MW_LDS_RECS ? max_vis : MW_LDS_RECS;
+    const size_t lds = big ? 192 : (size_t)lds_recs * (MW_LDS_SHADE_Q + MW_LDS_CULL_Q) * 16 + 192;
+    const bool listed = part == 2 && tile_list;
+    if (listed) part = 3;
+    const int wpe2 = part == 2 ? n_tiles : wpe, tpw2 = part == 2 ? 1 : (n_tiles + wpe - 1) / wpe;
+    const int all = N * n_tiles;
+    return {part, wpe2, tpw2, listed ? (mesh_tile_waves < all ? mesh_tile_waves : all) : (N + 7) / 8 * 8 * wpe2, lds};
+}
+
+// 16-byte units where every base and size of a copy is a multiple of 16 (`bits`: the addresses and byte counts, or'ed), else bytes
+inline bool wide_units(uintptr_t bits) { return (bits & 15u) == 0; }
+
+// the frame stack's push / refresh: grid (N, chunks) over the units of one frame
+struct StackLaunch { bool wide; unsigned chunks; };
+inline StackLaunch stack_launch(uintptr_t address_bits, size_t frame_bytes)
+{
+    const bool wide = wide_units(address_bits | (uintptr_t)frame_bytes);
+    const size_t units = frame_bytes / (wide ? 16 : 1), chunk = (size_t)MW_STACK_THREADS * MW_STACK_UNROLL;
+    return {wide, (unsigned)((units + chunk - 1) / chunk)};
+}
+
+// more workgroups than one 1-D launch holds
+inline bool grid_too_large(unsigned long long blocks) { return blocks > 0x7FFFFFFFull; }
+
+// the grid of a state-record call over `count` items: component blocks, then blob blocks (mw_snapshot.hip)
+struct SnapshotGrid { int item_chunks; long long blocks; };
+inline SnapshotGrid snapshot_grid(int count, int total_rows, int chunks_per_item)
+{
+    const int item_chunks = (count + MW_SNAP_THREADS - 1) / MW_SNAP_THREADS;
+    return {item_chunks, (long long)item_chunks * total_rows + (long long)count * chunks_per_item};
+}
+
+// ... and of a frame-record call (mw_snapframes.hip): per item the chunks of its obs row and of each window frame, then its depth row
+struct SnapfGrid { bool wide; uint64_t frame_chunks, depth_chunks, per_item, blocks; };
+inline SnapfGrid snapf_grid(uintptr_t address_bits, uint64_t frame_bytes, uint64_t depth_bytes, int stack_depth, int count)
+{
+    const bool wide = wide_units(address_bits | (uintptr_t)frame_bytes | (uintptr_t)depth_bytes);
+    const uint64_t chunk = (uint64_t)MW_SNAPF_THREADS * MW_SNAPF_UNROLL * (wide ? 16 : 1);
+    const uint64_t frame_chunks = (frame_bytes + chunk - 1) / chunk, depth_chunks = (depth_bytes + chunk - 1) / chunk;
+    const uint64_t per_item = frame_chunks * (1 + (uint64_t)stack_depth) + depth_chunks;
+    return {wide, frame_chunks, depth_chunks, per_item, per_item * (uint64_t)count};
+}
+
+}  // namespace mwpolicy

@@ -169,7 +169,7 @@ __device__ __attribute__((always_inline)) inline void raster_env_tiles(
 // persistent wavefronts drawing (env, tile) items from the list the geometry kernel left (mw_geom.hip: the union of the
 // entities' tile rectangles; a grid of one wavefront per tile of every env spent most of its time starting wavefronts that
 // found no mesh in their env).
-// SUB: the frame of a subset of the batch (mw_engine.hip, same-step auto-reset with final observations): the block's env slot e
+// SUB: the frame of a subset of the batch (mw_engine_frame.hip, same-step auto-reset with final observations): the block's env slot e
 // draws env list[1 + e] while e < list[0], and exits otherwise (the listed mesh tiles come from the geometry kernel's list, which
 // held the listed envs only).
 template <bool LDS_RECS, int FMT, int HOT = 0, int MESHAWARE = 0, bool SUB = false>
@@ -224,12 +224,12 @@ __device__ __attribute__((always_inline)) inline void raster_kernel_body(
 #define MW_RASTER_FWD N, W, H, max_vis, tiles_x, n_tiles, waves_per_env, tiles_per_wave, rec_raster, rec_shade, rec_cull, \
     nvis_arr, envhdr, texd, texels, obs, depth, dbg, texel_bytes, rec_order, mesh_pos, mesh_nrm, mesh_rgb, mesh_uv, mesh_keys, plane_cache, plane_cap, slow_frags, slow_head, tile_list, tile_n, tile_list_cap, n_xcc, frame_clean
 // each kernel and its list form over the envs of a list (int32 [0] count, [1 + i] env): the second pass of a same-step auto-reset
-// step with final observations (mw_engine.hip)
+// step with final observations (mw_engine_frame.hip)
 #define MW_RASTER_PAIR(stem, bounds, ...)                                                                                           \
     extern "C" __global__ bounds void stem##_kernel(MW_RASTER_ARGS) { raster_kernel_body<__VA_ARGS__, false>(MW_RASTER_FWD); } \
     extern "C" __global__ bounds void stem##_sub_kernel(MW_RASTER_ARGS, const int32_t *__restrict__ list) { raster_kernel_body<__VA_ARGS__, true>(MW_RASTER_FWD, list); }
 
-// the production kernels of small scenes: no debug flags (mw_engine.hip launches the general kernel below when
+// the production kernels of small scenes: no debug flags (mw_engine_frame.hip launches the general kernel below when
 // MW_DEBUG_FLAGS asks for any), RGB only / RGB + depth
 MW_RASTER_PAIR(mw_raster, __launch_bounds__(64), true, 0, 1, 0)
 MW_RASTER_PAIR(mw_raster_depth, __launch_bounds__(64), true, 0, 2, 0)

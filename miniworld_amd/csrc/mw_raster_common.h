@@ -414,7 +414,7 @@ __device__ inline int mesh_entry_of(const TileCtx &cx, uint32_t id, int &rec)
 }
 
 // FMT: output layout fixed at compile time (0: the plain observation) or -1: read from the launch flags; -2: the same for a
-// frame off the 16 x 4 grid ("ragged": W or H not a multiple of the tile, mw_engine.hip).  The tiles cover the grid
+// frame off the 16 x 4 grid ("ragged": W or H not a multiple of the tile, mw_policy.h).  The tiles cover the grid
 // ceil16(W) x ceil4(H); the lanes of padding pixels (px >= W, or py >= H: GL rows below 0) have their coverage masked and store
 // nothing, and the real pixels store byte by byte (a 48-byte tile row would straddle output rows, and rows start at any address).
 // SORTED: the env's triangles come with a visiting order by ascending depth bound (big scenes).

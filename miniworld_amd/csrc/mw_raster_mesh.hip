@@ -413,7 +413,7 @@ __device__ inline void view_mesh_body(int W, int H, const float *hdr, const floa
 }
 
 // grid (x, count): blockIdx.y = env first_env + y of the batch, its keys at keys + y * W * H * S.  SUB (first_env = 0, the whole
-// batch's keys): y draws env list[1 + y] while y < list[0] (same-step auto-reset with final observations, mw_engine.hip).
+// batch's keys): y draws env list[1 + y] while y < list[0] (same-step auto-reset with final observations, mw_engine_frame.hip).
 template <bool SUB>
 __device__ __attribute__((always_inline)) inline void view_mesh_kernel_body(int W, int H, int S, int first_env, const float *__restrict__ envhdr,
                                              const float *__restrict__ mesh_pos, uint32_t *keys, const int32_t *__restrict__ list)

@@ -545,7 +545,7 @@ __device__ inline void batch_exact(const QCtx &cx, int kmax, Tri tri, RecOf recp
 }
 
 // ---- the kernel -------------------------------------------------------------------------------------------------------------
-// SUB: the frame of a subset of the batch (mw_engine.hip, same-step auto-reset with final observations): workgroup e draws env
+// SUB: the frame of a subset of the batch (mw_engine_frame.hip, same-step auto-reset with final observations): workgroup e draws env
 // list[1 + e] while e < list[0] and exits at once otherwise (before any barrier: the whole workgroup)
 template <int S, bool SUB = false>
 __device__ inline void rasterq_body(
@@ -1052,7 +1052,7 @@ __device__ inline void rasterq_body(
 MWQ_PAIR(mw_rasterq, __launch_bounds__(MWQ_THREADS, MWQ_OCC), 8)
 MWQ_PAIR(mw_rasterq4, __launch_bounds__(MWQ_THREADS), 4)
 
-// bytes of dynamic LDS a launch needs (mw_engine.hip)
+// bytes of dynamic LDS a launch needs (mw_engine_frame.hip: launch_quad; mw_policy.h: k2q_ok)
 extern "C" int mw_rasterq_lds_bytes(int S, int W, int H, int n_tiles, int depth) { return q_plan(S, W, H, n_tiles, depth != 0).total; }
 // the longest display list the quad path draws (longer ones: the tile code)
 extern "C" int mw_rasterq_cap(int depth) { return q_cap(depth != 0); }

@@ -49,7 +49,7 @@ extern "C" __global__ __launch_bounds__(64) void MW_RESPAWN_KERNEL_NAME(MwArgs a
 #ifndef MW_INSTALL_KERNEL_NAME
 #define MW_INSTALL_KERNEL_NAME mw_final_install_kernel
 #endif
-// Same-step auto-reset with final observations, between the two passes of the step (mw_engine.hip): the listed envs (int32
+// Same-step auto-reset with final observations, between the two passes of the step (mw_engine_frame.hip): the listed envs (int32
 // [0] count, [1 + i] env: the ones whose episode ended with this step, whose terminal frame was drawn) install their next world
 // through the same install code as the step kernel's, and leave nothing of the finished episode behind: no pending removal (a
 // picked object, CollectHealth's consumed kit), no pending next-step reset, no frame_clean byte.  One wavefront per list slot; grid N.

@@ -352,7 +352,7 @@ __device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writ
             }
         }
         if (a.task >= MW_TASK_SIDEWALK) program_rules(c, action, step_count, rew, tm);
-        // CollectHealth (collecthealth.py:79-98) never takes the dense form (the engine's k1_dense_lanes)
+        // CollectHealth (collecthealth.py:79-98) never takes the dense form (mw_policy.h: k1_dense_lanes)
         int health = 0;
         if (!PER_LANE && a.task == MW_TASK_COLLECT) {
             health = a.health[env] - 2;

@@ -1,5 +1,5 @@
 // Frame records (mw_snapshot_save_frames / mw_snapshot_load_frames): where everything lies in the caller's second buffer, the companion
-// of the state records (mw_snapshot.h).  Shared by the host runtime (mw_engine.hip), the copy kernels (mw_snapframes.hip) and the CPU
+// of the state records (mw_snapshot.h).  Shared by the host runtime (mw_engine_snapshot.hip), the copy kernels (mw_snapframes.hip) and the CPU
 // check of the layout (tests/hostcheck/snapframes_layout.cpp).
 //
 // A buffer for `capacity` records is a 64-byte header and then up to four sections.  Unlike the state records they are RECORD-major: a

@@ -1,5 +1,5 @@
 // Snapshot records (mw_snapshot_save / mw_snapshot_load): where everything lies in the caller's buffer.  Shared by the host runtime
-// (mw_engine.hip), the copy kernels (mw_snapshot.hip) and the CPU check of the layout (tests/hostcheck/snapshot_layout.cpp).
+// (mw_engine.hip, mw_engine_snapshot.hip), the copy kernels (mw_snapshot.hip) and the CPU check of the layout (tests/hostcheck/snapshot_layout.cpp).
 //
 // A buffer for `capacity` records is a 64-byte header and then sections, each Structure-of-Arrays over the records like the engine's
 // state is over the envs, so that consecutive lanes of the copy kernels take consecutive records of one component:

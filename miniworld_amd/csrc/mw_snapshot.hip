@@ -17,7 +17,7 @@
 // The header's key (a load) is compared by every workgroup before anything else: all of them leave on a mismatch.
 //
 // Between launches refill_mask is 0 (spare ready) or 1 (consumed, refill pending) only: the transient states 2 and 3 exist inside a
-// step kernel or a refill kernel, and both calls are ordered behind those (mw_engine.hip: snapshot_order).  The word is copied as it is.
+// step kernel or a refill kernel, and both calls are ordered behind those (mw_engine_snapshot.hip: snapshot_order).  The word is copied as it is.
 #include <hip/hip_runtime.h>
 
 #include "mw_kernels.h"

@@ -365,3 +365,39 @@ def test_errors_leave_the_stack_alone():
     for v in (vec, ref, off):
         v.engine.check()
         v.close()
+
+
+@pytest.mark.parametrize("mode", ["same_step", "next_step"])
+def test_steps_without_reward_and_flag_outputs_equal_steps_with_them(mode):
+    """reward, terminated and truncated are optional in mw_step, mw_step_repeat and mw_step_plan: the engine's scratch stands in.  Twin
+    A passes its three tensors, twin B passes None for all of them, through every kind of call (a step, a repeat of 3, a drawn plan of 3
+    and a frameless one), always moving forward so that envs reach their boxes and worlds are installed — where the stack's push
+    and the frameless call's flag kernel read the flags the step kernel wrote.  obs, the stack view and the whole state must stay equal
+    bit for bit after every call, and at least one episode of A must have terminated."""
+    import torch
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    n, calls, forward = 8, 120, 2
+    A, B = (MiniWorldVecEnv("MiniWorld-Hallway-v0", n, seed=3, autoreset=mode, frame_stack=2) for _ in range(2))
+    assert torch.equal(A.reset(), B.reset()) and torch.equal(A.stack, B.stack)
+    act = torch.full((n,), forward, dtype=torch.int32, device="cuda")
+    plans = torch.full((3, n), forward, dtype=torch.int32, device="cuda")
+    terminated = 0
+    for j in range(calls):
+        kind = j % 4
+        for v, outs in ((A, (A.reward, A.terminated, A.truncated)), (B, (None, None, None))):
+            if kind == 0:
+                v.engine.step(act, v.obs, None, *outs)
+            elif kind == 1:
+                v.engine.step_repeat(act, 3, v.obs, None, *outs)
+            else:
+                v.engine.step_plan(plans, v.obs if kind == 2 else None, None, outs[0], None, outs[1], outs[2])
+        terminated += int(A.terminated.sum())
+        assert torch.equal(A.obs, B.obs), (j, "obs")
+        assert torch.equal(A.stack, B.stack), (j, "stack")
+        sa, sb = A.engine.get_state(), B.engine.get_state()
+        assert sa.keys() == sb.keys()
+        for k in sa:
+            assert np.array_equal(sa[k], sb[k]), (j, k)
+    print(f"{mode}: {terminated} terminated flags over {calls} calls")
+    A.engine.check(); B.engine.check()
+    assert terminated >= 1, "no episode terminated: lengthen the run"
