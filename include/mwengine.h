@@ -552,6 +552,47 @@ int mw_snapshot_save_frames(mw_engine *e, const int32_t *d_envs, int32_t count, 
  * source's.  Like every call that writes d_obs it drops the frame that frame reuse holds; the frame cache stays (no state changed). */
 int mw_snapshot_load_frames(mw_engine *e, const int32_t *d_envs, const int32_t *d_recs, int32_t count, const uint8_t *d_frames,
                             int32_t n_recs, int32_t capacity, int32_t flags, uint8_t *d_obs, float *d_depth, void *stream);
+/* Level sets: a bank of records a step loop restarts finished envs from.  The reference has one way to choose the world an env plays
+ * next, env.reset(seed=s) between episodes (miniworld.py:544-668; Procgen's num_levels / start_level and Prioritized Level Replay are
+ * built on exactly that); here a level is a record of a freshly reset env — state, stream and spare in the state record, first
+ * observation, depth and stack in the frame record — and restarting an env from it is two copies and no draw.  Four calls beside the
+ * four above, which they leave as they are.
+ * mw_snapshot_save_at / mw_snapshot_save_frames_at stand in for the append of a level or an archive cell to a Python list: a bank
+ * larger than the engine is filled in chunks, and a running loop adds the states it reaches. */
+/* record d_recs[k] := the complete state of env d_envs[k], k < count.  d_recs == NULL: record k (mw_snapshot_save);
+ * d_envs == NULL: env k.  The records named must be distinct (caller's contract); every other record of the buffer
+ * keeps what it held.  Writes the header. */
+int mw_snapshot_save_at(mw_engine *e, const int32_t *d_envs, const int32_t *d_recs, int32_t count,
+                        uint8_t *d_snap, int32_t capacity, void *stream);
+int mw_snapshot_save_frames_at(mw_engine *e, const int32_t *d_envs, const int32_t *d_recs, int32_t count,
+                               const uint8_t *d_obs, const float *d_depth, uint8_t *d_frames,
+                               int32_t capacity, int32_t flags, void *stream);
+/* mw_snapshot_load_where / mw_snapshot_load_frames_where stand in for the reference loop's "if done: env.reset(seed=next_level)"
+ * (scripts/benchmark.py:36-37), for every env at once and without the host learning which envs finished. */
+/* for every env i < num_envs with d_mask[i] != 0: env i := record d_recs[i].  d_mask uint8[N], d_recs int32[N], both on
+ * the device; d_recs[i] is not read where d_mask[i] == 0.  No count, no host value, no synchronisation.
+ * One kernel launch each, asynchronous on `stream`, ordered behind the Maze's side-stream refills as mw_snapshot_load is; the key is
+ * compared as a load compares it.  The grid is over all num_envs envs whatever the mask holds (a workgroup whose items are all
+ * unmasked leaves after reading the mask), and num_envs may exceed capacity: records repeat, the list form's count <= capacity rule does
+ * not apply.  A masked env whose record index is outside 0 .. n_recs - 1 is skipped — it writes nothing — and sets the status bit that
+ * mw_check reports as MW_E_INVALID; an index under a zero mask byte is never an error.  MW_E_INVALID before anything is launched: a null
+ * engine, mask, index array (record i for env i is what the list form is for) or buffer; a misaligned buffer; n_recs outside
+ * 0 .. capacity; the frame twin's flag rules (mw_snapshot_load_frames).
+ * For every env it writes mw_snapshot_load_where owes what mw_snapshot_load owes — the frame-clean byte cleared, the occlusion cache
+ * of its geometry set invalidated, its stack flag byte marked as after mw_reset (plus the record's pending next-step reset) — and
+ * nothing to any other env: it leaves the other envs' cached frames alone (mw_set_frame_cache).  Where mw_snapshot_load clears the
+ * frame cache of every env, this call advances the cache epoch of each env it writes, on the device; the epoch is part of a cached
+ * frame's key and of no record, so none of that env's cached frames can match again, and every other env keeps its cache.
+ * Both _where calls drop the held frame of frame reuse (mw_set_frame_reuse), as mw_snapshot_load_frames does: the engine cannot know
+ * that a record's frame shows the record's state.  The next step therefore draws every env it cannot serve from the frame cache; with
+ * the cache on, a clean env is an ordinary cache hit.
+ * mw_snapshot_load_frames_where writes the masked envs' rows of d_obs, of d_depth with MW_SNAPF_DEPTH, and their ring rows and flag
+ * bytes with MW_SNAPF_STACK exactly as mw_snapshot_load_frames would, and touches no byte of any other env's rows. */
+int mw_snapshot_load_where(mw_engine *e, const uint8_t *d_mask, const int32_t *d_recs, const uint8_t *d_snap,
+                           int32_t n_recs, int32_t capacity, void *stream);
+int mw_snapshot_load_frames_where(mw_engine *e, const uint8_t *d_mask, const int32_t *d_recs, const uint8_t *d_frames,
+                                  int32_t n_recs, int32_t capacity, int32_t flags, uint8_t *d_obs, float *d_depth,
+                                  void *stream);
 
 /* checks the device-side status word (capacity overflows, items a snapshot call skipped); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);

@@ -676,7 +676,7 @@ int mw_check(mw_engine *e, void *stream)
     if (st & MW_ST_VIS_OVERFLOW) return fail(e, MW_E_OVERFLOW, "more than max_visible=%d visible primitives in some env", e->cfg.max_visible);
     if (st & MW_ST_PLACEMENT_FAIL) return fail(e, MW_E_OVERFLOW, "device-side placement did not converge in some env");
     if (st & MW_ST_SNAPSHOT_BAD)
-        return fail(e, MW_E_INVALID, "mw_snapshot_save / mw_snapshot_load / mw_snapshot_save_frames / mw_snapshot_load_frames skipped an item: an env or record index out of range, or a record "
+        return fail(e, MW_E_INVALID, "mw_snapshot_save / mw_snapshot_load / mw_snapshot_save_frames / mw_snapshot_load_frames (or an _at / _where form of them) skipped an item: an env or record index out of range, or a record "
                     "buffer of another layout (key mismatch)");
     return MW_OK;
 }

@@ -165,6 +165,14 @@ extern "C" __global__ void mw_snapshot_save_kernel(MW_SNAP_ARGS, uint8_t *__rest
 //   frame_clean, occ_valid, stack_flags  what a load resets for every env it writes (the last two may be null)
 extern "C" __global__ void mw_snapshot_load_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap, const int32_t *__restrict__ d_recs, int n_recs,
                                                    uint8_t *__restrict__ frame_clean, int32_t *__restrict__ occ_valid, uint8_t *__restrict__ stack_flags);
+// the same bodies, items named otherwise.  mw_snapshot_save_at: item k is (env d_envs[k] or k, record d_recs[k] or k) — a save into chosen
+// records.  mw_snapshot_load_where: count = N, item k is env k where mask[k] != 0 and its record d_recs[k] (not read elsewhere; d_envs is
+// not read); a workgroup whose items are all unmasked leaves after reading the mask.  fc_epoch: advanced for every env written
+// (MwArgs::fc_epoch), which stands in for the host's cache-wide invalidation.
+extern "C" __global__ void mw_snapshot_save_at_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap, const int32_t *__restrict__ d_recs);
+extern "C" __global__ void mw_snapshot_load_where_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap, const int32_t *__restrict__ d_recs, int n_recs,
+                                                         uint8_t *__restrict__ frame_clean, int32_t *__restrict__ occ_valid, uint8_t *__restrict__ stack_flags,
+                                                         const uint8_t *__restrict__ mask, uint32_t *__restrict__ fc_epoch);
 
 // frame records (mw_snapframes.hip; the layout and MwSnapfArgs: mw_snapframes.h): one launch per call, a 1-D grid of MW_SNAPF_THREADS
 // lanes, workgroup (item, chunk of the record: its obs row, its depth row, its K window frames).  Items and their index tests as for
@@ -178,6 +186,13 @@ extern "C" __global__ void mw_snapshot_save_frames_kernel(MW_SNAPF_ARGS, const u
 extern "C" __global__ void mw_snapshot_load_frames_kernel(MW_SNAPF_ARGS, const int32_t *__restrict__ d_recs, const uint8_t *__restrict__ frames,
                                                           uint8_t *__restrict__ obs, uint8_t *__restrict__ depth, uint8_t *__restrict__ ring,
                                                           uint8_t *__restrict__ stack_flags);
+// ... and their forms with chosen records (a save) and with a mask over all N envs (a load; a.count = N), as for the state records
+extern "C" __global__ void mw_snapshot_save_frames_at_kernel(MW_SNAPF_ARGS, const uint8_t *__restrict__ obs, const uint8_t *__restrict__ depth,
+                                                             const uint8_t *__restrict__ ring, const uint8_t *__restrict__ stack_flags,
+                                                             uint8_t *__restrict__ frames, const int32_t *__restrict__ d_recs);
+extern "C" __global__ void mw_snapshot_load_frames_where_kernel(MW_SNAPF_ARGS, const int32_t *__restrict__ d_recs, const uint8_t *__restrict__ frames,
+                                                                uint8_t *__restrict__ obs, uint8_t *__restrict__ depth, uint8_t *__restrict__ ring,
+                                                                uint8_t *__restrict__ stack_flags, const uint8_t *__restrict__ mask);
 
 // the host runtime's own small kernels (mw_engine_kernels.hip): mw_get_info's gather; behind the first pass of a same-step step with
 // final observations, the list of the envs that finished and the copy of their rows into the final buffers

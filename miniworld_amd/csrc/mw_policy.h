@@ -229,6 +229,19 @@ inline SnapshotGrid snapshot_grid(int count, int total_rows, int chunks_per_item
     return {item_chunks, (long long)item_chunks * total_rows + (long long)count * chunks_per_item};
 }
 
+// The masked loads (mw_snapshot_load_where, mw_snapshot_load_frames_where): the grid is the list form's for count = N, whatever the mask
+// holds and however few records the buffer has — records repeat, so N may exceed the capacity.
+inline SnapshotGrid snapshot_where_grid(int N, int total_rows, int chunks_per_item) { return snapshot_grid(N, total_rows, chunks_per_item); }
+
+// What a load of state records invalidates on the host.  The held frame (frame reuse) always: the caller's buffers no longer show the
+// envs.  The frame cache of EVERY env only for the list form, whose kernel leaves the epochs alone; the masked form runs behind every
+// step of a loop and must not cost the other envs their cached frames, so its kernel advances fc_epoch of each env it writes instead
+// (the epoch is part of a frame's key and of no record: none of that env's cached frames can match again).
+struct LoadInvalidation { bool held, cache; };
+inline LoadInvalidation snapshot_load_invalidation(bool where) { return {true, !where}; }
+// ... and of frame records, either form: rows of d_obs are written, no state changes
+inline LoadInvalidation snapshot_load_frames_invalidation(bool /*where*/) { return {true, false}; }
+
 // ... and of a frame-record call (mw_snapframes.hip): per item the chunks of its obs row and of each window frame, then its depth row
 struct SnapfGrid { bool wide; uint64_t frame_chunks, depth_chunks, per_item, blocks; };
 inline SnapfGrid snapf_grid(uintptr_t address_bits, uint64_t frame_bytes, uint64_t depth_bytes, int stack_depth, int count)
@@ -238,6 +251,10 @@ inline SnapfGrid snapf_grid(uintptr_t address_bits, uint64_t frame_bytes, uint64
     const uint64_t frame_chunks = (frame_bytes + chunk - 1) / chunk, depth_chunks = (depth_bytes + chunk - 1) / chunk;
     const uint64_t per_item = frame_chunks * (1 + (uint64_t)stack_depth) + depth_chunks;
     return {wide, frame_chunks, depth_chunks, per_item, per_item * (uint64_t)count};
+}
+inline SnapfGrid snapf_where_grid(uintptr_t address_bits, uint64_t frame_bytes, uint64_t depth_bytes, int stack_depth, int N)
+{
+    return snapf_grid(address_bits, frame_bytes, depth_bytes, stack_depth, N);
 }
 
 }  // namespace mwpolicy

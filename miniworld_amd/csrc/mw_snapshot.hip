@@ -1,6 +1,8 @@
 // Snapshot records (mw_snapshot_save / mw_snapshot_load): the complete state of an env out of the engine's arrays into a caller's
 // buffer and back — the hot path of a fork loop (tree search, particle resampling: save the batch, load it back through an index).
 // A pure copy: no arithmetic, nothing but loads, stores and index tests.  The layout of the buffer: mw_snapshot.h.
+// mw_snapshot_save_at and mw_snapshot_load_where are the same body with the items named otherwise (Form): a level bank filled in chunks,
+// and the envs a step finished — known on the device alone — restarted from it.
 //
 // One launch per call, a 1-D grid of two kinds of workgroups, told apart by blockIdx alone:
 //   component blocks  (row r of the state, 256 consecutive items): the engine's state is component-major over the envs and the
@@ -26,13 +28,18 @@ namespace {
 
 struct Item { int env, rec; bool ok; };
 
+// How a call names its items.  LIST: item k is (env d_envs[k] or k, record d_recs[k] or k — a save: always k), k < count.  AT
+// (mw_snapshot_save_at): a save honours d_recs too.  WHERE (mw_snapshot_load_where): item k is env k, k < N, present where mask[k] != 0,
+// and its record is d_recs[k] — not read under a zero mask byte.
+enum Form { LIST = 0, AT = 1, WHERE = 2 };
+
 // item k of the call: the env and the record, each tested against its limit
-template <bool LOAD>
+template <bool LOAD, Form FORM>
 __device__ __forceinline__ Item item_of(int k, int N, int n_recs, const int32_t *__restrict__ d_envs, const int32_t *__restrict__ d_recs)
 {
     Item it;
-    it.env = d_envs ? d_envs[k] : k;
-    it.rec = LOAD && d_recs ? d_recs[k] : k;       // (a save: record k, k < count <= capacity)
+    it.env = FORM != WHERE && d_envs ? d_envs[k] : k;
+    it.rec = FORM == WHERE ? d_recs[k] : (LOAD || FORM == AT) && d_recs ? d_recs[k] : k;       // (a plain save: record k, k < count <= capacity)
     it.ok = (unsigned)it.env < (unsigned)N && (unsigned)it.rec < (unsigned)n_recs;
     return it;
 }
@@ -40,11 +47,13 @@ __device__ __forceinline__ Item item_of(int k, int N, int n_recs, const int32_t 
 template <typename T>
 __device__ __forceinline__ void move(void *dst, const void *src) { *static_cast<T *>(dst) = *static_cast<const T *>(src); }
 
-template <bool LOAD>
+// (mask, fc_epoch: the WHERE form alone — which envs are items, and the frame-cache epoch a written env advances)
+template <bool LOAD, Form FORM = LIST>
 __device__ __forceinline__ void snapshot_block(const MwSnapTable *__restrict__ tab, int N, int capacity, int count, int item_chunks,
                                                const int32_t *__restrict__ d_envs, const int32_t *__restrict__ d_recs, int n_recs,
                                                uint32_t *__restrict__ status, uint8_t *snap, uint8_t *__restrict__ frame_clean,
-                                               int32_t *__restrict__ occ_valid, uint8_t *__restrict__ stack_flags)
+                                               int32_t *__restrict__ occ_valid, uint8_t *__restrict__ stack_flags,
+                                               const uint8_t *__restrict__ mask = nullptr, uint32_t *__restrict__ fc_epoch = nullptr)
 {
     const int tid = (int)threadIdx.x;
     const int total_rows = tab->total_rows;
@@ -56,7 +65,8 @@ __device__ __forceinline__ void snapshot_block(const MwSnapTable *__restrict__ t
         const MwSnapRow comp = tab->comp[tab->row_comp[row]];
         const int k = chunk * MW_SNAP_THREADS + tid;
         if (k >= count) return;
-        const Item it = item_of<LOAD>(k, N, n_recs, d_envs, d_recs);
+        if (FORM == WHERE && !mask[k]) return;
+        const Item it = item_of<LOAD, FORM>(k, N, n_recs, d_envs, d_recs);
         if (!it.ok) {
             if (row == 0) atomicOr(status, MW_ST_SNAPSHOT_BAD);
             return;
@@ -79,6 +89,9 @@ __device__ __forceinline__ void snapshot_block(const MwSnapTable *__restrict__ t
                 const uint8_t pending = snap[MW_SNAP_HEADER_BYTES + cap * tab->reset_pending_unit + (size_t)it.rec];
                 stack_flags[it.env] = (uint8_t)(MW_STACK_FRESH | (pending ? MW_STACK_PENDING : 0));
             }
+            // ... and the WHERE form, which leaves the host's cache-wide invalidation out: no cached frame of the env matches again
+            // (the epoch is part of the key and of no record, MwArgs::fc_epoch)
+            if (FORM == WHERE) fc_epoch[it.env] += 1u;
         }
         return;
     }
@@ -89,7 +102,8 @@ __device__ __forceinline__ void snapshot_block(const MwSnapTable *__restrict__ t
     const long long g = (long long)blockIdx.x - comp_blocks;
     const int k = (int)(g / per_item), within = (int)(g % per_item);
     if (k >= count) return;
-    const Item it = item_of<LOAD>(k, N, n_recs, d_envs, d_recs);
+    if (FORM == WHERE && !mask[k]) return;
+    const Item it = item_of<LOAD, FORM>(k, N, n_recs, d_envs, d_recs);
     if (!it.ok) return;         // (the status bit: the item's component block of row 0)
     const int set = within / per_set, part = within % per_set;
     const bool polys = part < poly_chunks;
@@ -122,16 +136,32 @@ __device__ __forceinline__ void snapshot_block(const MwSnapTable *__restrict__ t
     if (u3 < units) dst[u3] = v3;
 }
 
-}  // namespace
-
-extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_save_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap)
+// the header: the key, then zeros, by one lane of the first workgroup (every save writes it, an empty one too)
+__device__ __forceinline__ void write_header(const MwSnapKey &key, uint8_t *snap)
 {
-    // the header: the key, then zeros, by one lane of the first workgroup (every save writes it, an empty one too)
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         uint32_t *head = reinterpret_cast<uint32_t *>(snap);
 #pragma unroll
         for (int i = 0; i < MW_SNAP_HEADER_BYTES / 4; ++i) head[i] = i < MW_SNAP_KEY_WORDS ? key.w[i < MW_SNAP_KEY_WORDS ? i : 0] : 0u;
     }
+}
+
+// a buffer of another layout (or no snapshot at all): nothing of it is read beyond its first words, nothing is written
+__device__ __forceinline__ bool key_matches(const MwSnapKey &key, const uint8_t *snap, uint32_t *__restrict__ status)
+{
+    const uint32_t *head = reinterpret_cast<const uint32_t *>(snap);
+    bool same = true;
+#pragma unroll
+    for (int i = 0; i < MW_SNAP_KEY_WORDS; ++i) same = same && head[i] == key.w[i];
+    if (!same && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(status, MW_ST_SNAPSHOT_BAD);
+    return same;
+}
+
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_save_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap)
+{
+    write_header(key, snap);
     snapshot_block<false>(tab, N, capacity, count, item_chunks, d_envs, nullptr, capacity, status, snap, nullptr, nullptr, nullptr);
 }
 
@@ -140,14 +170,25 @@ extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_load_k
                                                                                      uint8_t *__restrict__ frame_clean, int32_t *__restrict__ occ_valid,
                                                                                      uint8_t *__restrict__ stack_flags)
 {
-    // a buffer of another layout (or no snapshot at all): nothing of it is read beyond its first words, nothing is written
-    const uint32_t *head = reinterpret_cast<const uint32_t *>(snap);
-    bool same = true;
-#pragma unroll
-    for (int i = 0; i < MW_SNAP_KEY_WORDS; ++i) same = same && head[i] == key.w[i];
-    if (!same) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(status, MW_ST_SNAPSHOT_BAD);
-        return;
-    }
+    if (!key_matches(key, snap, status)) return;
     snapshot_block<true>(tab, N, capacity, count, item_chunks, d_envs, d_recs, n_recs, status, const_cast<uint8_t *>(snap), frame_clean, occ_valid, stack_flags);
+}
+
+extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_save_at_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap,
+                                                                                        const int32_t *__restrict__ d_recs)
+{
+    write_header(key, snap);
+    snapshot_block<false, AT>(tab, N, capacity, count, item_chunks, d_envs, d_recs, capacity, status, snap, nullptr, nullptr, nullptr);
+}
+
+// (count = N: the grid is over every env; d_envs is not read)
+extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_load_where_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap,
+                                                                                           const int32_t *__restrict__ d_recs, int n_recs,
+                                                                                           uint8_t *__restrict__ frame_clean, int32_t *__restrict__ occ_valid,
+                                                                                           uint8_t *__restrict__ stack_flags, const uint8_t *__restrict__ mask,
+                                                                                           uint32_t *__restrict__ fc_epoch)
+{
+    if (!key_matches(key, snap, status)) return;
+    snapshot_block<true, WHERE>(tab, N, capacity, count, item_chunks, nullptr, d_recs, n_recs, status, const_cast<uint8_t *>(snap), frame_clean, occ_valid,
+                                stack_flags, mask, fc_epoch);
 }

@@ -45,6 +45,7 @@ EXPORTS = [
     "mw_set_frame_stack", "mw_stack_refresh", "mw_stack_window",
     "mw_snapshot_bytes", "mw_snapshot_save", "mw_snapshot_load",
     "mw_snapshot_frames_bytes", "mw_snapshot_save_frames", "mw_snapshot_load_frames",
+    "mw_snapshot_save_at", "mw_snapshot_save_frames_at", "mw_snapshot_load_where", "mw_snapshot_load_frames_where",
 ]
 
 
@@ -206,6 +207,10 @@ def load_library():
     L.mw_snapshot_frames_bytes.restype = C.c_int64
     L.mw_snapshot_save_frames.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp]
     L.mw_snapshot_load_frames.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]
+    L.mw_snapshot_save_at.argtypes = [vp, vp, vp, i32, vp, i32, vp]
+    L.mw_snapshot_save_frames_at.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, vp]
+    L.mw_snapshot_load_where.argtypes = [vp, vp, vp, vp, i32, i32, vp]
+    L.mw_snapshot_load_frames_where.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.mw_pcg64_draws.argtypes = [C.c_uint64, i32, vp, vp]
     L.mw_check.argtypes = [vp, vp]
     L.mw_kernel_time_ms.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -587,6 +592,73 @@ class Engine:
         self._check(self.lib.mw_snapshot_load_frames(self.h, ptr(envs), ptr(records), int(count), C.c_void_p(buf.data_ptr()), int(n_recs),
                                                      int(capacity), int(flags), ptr(obs), ptr(depth), _stream_ptr(self.device)),
                     "mw_snapshot_load_frames")
+
+    def _at_items(self, envs, records, count):
+        """The index tensors and the item count of a save into chosen records."""
+        envs, records = self._index_tensor(envs, "envs"), self._index_tensor(records, "records")
+        if count is None:
+            count = envs.numel() if envs is not None else records.numel() if records is not None else self.N
+        for t, name in ((envs, "envs"), (records, "records")):
+            if t is not None and t.numel() != count:
+                raise EngineError(f"{name}: {t.numel()} indices for {count} items")
+        return envs, records, int(count)
+
+    def snapshot_save_at(self, buf, capacity: int, envs=None, records=None, count: int | None = None):
+        """Record records[k] of `buf` := the complete state of env envs[k] (envs=None: env k; records=None: record k).  The records
+        named must be distinct; every other record of `buf` keeps what it held, so a bank of more records than the engine has envs
+        is filled in chunks and a running loop adds to it.  Asynchronous on the current stream, one kernel; returns the number of
+        records written (mw_snapshot_save_at)."""
+        envs, records, count = self._at_items(envs, records, count)
+        self._snapshot_buffer(buf, capacity)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.mw_snapshot_save_at(self.h, ptr(envs), ptr(records), count, C.c_void_p(buf.data_ptr()), int(capacity),
+                                                 _stream_ptr(self.device)), "mw_snapshot_save_at")
+        return count
+
+    def snapshot_save_frames_at(self, buf, capacity: int, obs, depth=None, flags: int = 0, envs=None, records=None, count: int | None = None):
+        """Frame record records[k] of `buf` := env envs[k]'s frames, as snapshot_save_frames() takes them; the other records keep
+        what they held (mw_snapshot_save_frames_at).  Asynchronous on the current stream, one kernel; returns the number written."""
+        envs, records, count = self._at_items(envs, records, count)
+        self._frames_buffer(buf, capacity, flags)
+        self._frame_rows(obs, depth, flags)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.mw_snapshot_save_frames_at(self.h, ptr(envs), ptr(records), count, ptr(obs), ptr(depth), C.c_void_p(buf.data_ptr()),
+                                                        int(capacity), int(flags), _stream_ptr(self.device)), "mw_snapshot_save_frames_at")
+        return count
+
+    def _mask_tensor(self, mask):
+        """The mask of a _where call: a contiguous uint8[N] tensor on the engine's device (nothing is converted: a conversion
+        would be a kernel and an allocation in every step of the loop this call exists for)."""
+        import torch
+        if mask is None:
+            raise EngineError("mask: None")
+        return self._dev_tensor(mask, "mask", torch.uint8, self.N)
+
+    def snapshot_load_where(self, buf, n_recs: int, capacity: int, mask, records):
+        """For every env i with mask[i] != 0: env i := record records[i] of `buf`, whose first n_recs records are valid.  mask uint8[N]
+        and records int32[N] are device tensors; nothing is read on the host, so the call sits behind a step with no
+        synchronisation.  records[i] is not read under a zero mask byte; N may exceed `capacity` (records repeat).  The other
+        envs keep their cached frames (mw_snapshot_load_where).  Asynchronous on the current stream, one kernel."""
+        mask, records = self._mask_tensor(mask), self._index_tensor(records, "records", self.N)
+        if records is None:
+            raise EngineError("records: None (record i for env i: snapshot_load)")
+        self._snapshot_buffer(buf, capacity)
+        self._check(self.lib.mw_snapshot_load_where(self.h, C.c_void_p(mask.data_ptr()), C.c_void_p(records.data_ptr()), C.c_void_p(buf.data_ptr()),
+                                                    int(n_recs), int(capacity), _stream_ptr(self.device)), "mw_snapshot_load_where")
+
+    def snapshot_load_frames_where(self, buf, n_recs: int, capacity: int, mask, records, obs, depth=None, flags: int = 0):
+        """For every env i with mask[i] != 0: env i's rows of `obs` / `depth` (and with SNAPF_STACK its frame stack and stack flag) :=
+        frame record records[i] of `buf`; no byte of any other env's rows is touched.  Called behind snapshot_load_where() with the
+        same mask and records (mw_snapshot_load_frames_where).  Asynchronous on the current stream, one kernel."""
+        mask, records = self._mask_tensor(mask), self._index_tensor(records, "records", self.N)
+        if records is None:
+            raise EngineError("records: None (record i for env i: snapshot_load_frames)")
+        self._frames_buffer(buf, capacity, flags)
+        self._frame_rows(obs, depth, flags)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(self.lib.mw_snapshot_load_frames_where(self.h, ptr(mask), ptr(records), C.c_void_p(buf.data_ptr()), int(n_recs), int(capacity),
+                                                           int(flags), ptr(obs), ptr(depth), _stream_ptr(self.device)),
+                    "mw_snapshot_load_frames_where")
 
     def render(self, obs, depth=None):
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())

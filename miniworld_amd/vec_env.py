@@ -8,6 +8,8 @@ with ``terminated|truncated`` is the first one of the next episode.  ``autoreset
 episode returns its terminal frame, reward and flags, and the env's next step ignores its action and returns the next
 episode's first frame with reward 0 and no flags — the reference's own "step; if done: reset()" (it leaves the reset to the
 caller, scripts/benchmark.py:36-37), on the same random stream.  ``autoreset=False``: the caller resets.
+``autoreset="levels"``: a finished env restarts, in the same step and without the host learning that it finished, from a
+record of a bank of levels the caller chose (``make_levels``, ``set_levels``, ``next_level``).
 
 All 23 env ids are generated, ruled and auto-reset on the device, on the reference's own numpy PCG64 stream: Hallway,
 OneRoom*, Maze* and PickupObjects through their own generators, the fixed-floorplan families through placement programs
@@ -61,16 +63,18 @@ class EnvSnapshot:
     and stacked frames each env had at the save), `frame_flags`, the engine.SNAPF_* bits it was saved under, and `frame_stack`, the
     stack depth K of its stacks (0: none); without frames they are None, 0 and 0.  `.cpu()` / `.to(device)` move it, so
     `torch.save(snap.cpu().state_dict(), path)` and `EnvSnapshot.from_state_dict(torch.load(path))` write a checkpoint and read it
-    back."""
+    back.  A bank of levels (MiniWorldVecEnv.make_levels) also carries `seeds`, the int64 tensor of the seed each record was reset
+    with; None otherwise."""
 
-    def __init__(self, data, count: int, capacity: int, frames=None, frame_flags: int = 0, frame_stack: int = 0):
+    def __init__(self, data, count: int, capacity: int, frames=None, frame_flags: int = 0, frame_stack: int = 0, seeds=None):
         self.data, self.count, self.capacity = data, int(count), int(capacity)
         self.frames = frames
         self.frame_flags, self.frame_stack = (int(frame_flags), int(frame_stack)) if frames is not None else (0, 0)
+        self.seeds = seeds
 
     def _with(self, move):
         return EnvSnapshot(move(self.data), self.count, self.capacity, None if self.frames is None else move(self.frames),
-                           self.frame_flags, self.frame_stack)
+                           self.frame_flags, self.frame_stack, None if self.seeds is None else move(self.seeds))
 
     def to(self, device):
         return self._with(lambda t: t.to(device))
@@ -85,11 +89,13 @@ class EnvSnapshot:
         d = {"data": self.data, "count": self.count, "capacity": self.capacity}
         if self.frames is not None:
             d.update(frames=self.frames, frame_flags=self.frame_flags, frame_stack=self.frame_stack)
+        if self.seeds is not None:
+            d.update(seeds=self.seeds)
         return d
 
     @classmethod
     def from_state_dict(cls, d):
-        return cls(d["data"], d["count"], d["capacity"], d.get("frames"), d.get("frame_flags", 0), d.get("frame_stack", 0))
+        return cls(d["data"], d["count"], d["capacity"], d.get("frames"), d.get("frame_flags", 0), d.get("frame_stack", 0), d.get("seeds"))
 
     def __len__(self):
         return self.count
@@ -110,7 +116,11 @@ class MiniWorldVecEnv:
         continue like env.reset(), per-step domain-randomisation draws included (every device generator);
         "philox" = the engine's counter-based stream; "auto" = pcg64 where implemented.
         autoreset: True or "same_step", "next_step", False (see the module's docstring); the mode is `autoreset_mode`
-        ("same_step", "next_step" or "off").
+        ("same_step", "next_step" or "off").  "levels" (`autoreset_mode` "levels"): the engine itself resets nothing; after
+        set_levels(bank) every step() restarts the envs whose episode it ended from record `next_level[i]` of the bank — two
+        masked copy kernels behind the step, no draw and no host synchronisation.  What the caller sees is the same-step
+        auto-reset: the observation (and `self.stack`) returned with terminated | truncated is the first one of the env's next
+        level, reward and flags are the finished episode's last.
         final_obs (same-step auto-reset only): every step also writes the terminal frame of each env whose episode ended in it
         into that env's row of `self.final_obs` (and its depth into `self.final_depth` with want_depth); the other rows keep
         what they held.  Costs a second, small frame of the finished envs in every step.
@@ -139,13 +149,16 @@ class MiniWorldVecEnv:
             raise ValueError(f"stack_pad must be 'reset' or 'zero', not {stack_pad!r}")
         self.frame_stack = None if frame_stack is None else int(frame_stack)
         self.stack_pad = stack_pad
-        modes = {True: "same_step", False: "off", "same_step": "same_step", "next_step": "next_step"}
+        modes = {True: "same_step", False: "off", "same_step": "same_step", "next_step": "next_step", "levels": "levels"}
         if not isinstance(autoreset, (bool, str)) or autoreset not in modes:
-            raise ValueError(f"autoreset must be True, False, 'same_step' or 'next_step', not {autoreset!r}")
+            raise ValueError(f"autoreset must be True, False, 'same_step', 'next_step' or 'levels', not {autoreset!r}")
         self.autoreset_mode = modes[autoreset]
         if final_obs and self.autoreset_mode != "same_step":
-            raise ValueError(f"final_obs needs the same-step auto-reset (autoreset={autoreset!r}: "
-                             + ("the terminal step returns the terminal frame itself)" if self.autoreset_mode == "next_step" else "nothing is auto-reset)"))
+            why = {"next_step": "the terminal step returns the terminal frame itself",
+                   "levels": "the terminal frame is in self.obs only between the engine's step and the level loads, and nothing copies the "
+                             "finished envs' rows out yet",
+                   "off": "nothing is auto-reset"}[self.autoreset_mode]
+            raise ValueError(f"final_obs needs the same-step auto-reset (autoreset={autoreset!r}: {why})")
         if obs_layout not in ("hwc", "cwh", "grey"):
             raise ValueError(f"obs_layout must be 'hwc', 'cwh' or 'grey', not {obs_layout!r}")
         self.obs_layout = obs_layout
@@ -199,7 +212,8 @@ class MiniWorldVecEnv:
         cfg.max_episode_steps = int(min(float(self.template.max_episode_steps), 2 ** 30))
         cfg.domain_rand = int(domain_rand)
         cfg.generator = generator
-        cfg.autoreset = {"same_step": eng.AUTORESET_SAME_STEP, "next_step": eng.AUTORESET_NEXT_STEP, "off": eng.AUTORESET_OFF}[self.autoreset_mode]
+        cfg.autoreset = {"same_step": eng.AUTORESET_SAME_STEP, "next_step": eng.AUTORESET_NEXT_STEP, "off": eng.AUTORESET_OFF,
+                         "levels": eng.AUTORESET_OFF}[self.autoreset_mode]      # (levels: the loads behind the step restart the envs)
         self.autoreset = self.autoreset_mode != "off"
         cfg.agent_radius = float(self.template.agent.radius)
         if generator in (eng.GEN_HALLWAY, eng.GEN_ONEROOM):
@@ -316,6 +330,9 @@ class MiniWorldVecEnv:
         self._final_info_buf = None
         self._fork_buf = None           # fork()'s scratch records, made on first use
         self._fork_frames = None        # ... and its scratch frame records (fork(src, frames=True))
+        # autoreset="levels": the bank (set_levels), the level each env plays and the one it gets when its episode ends
+        self.levels = self.level = self.next_level = self.played_level = None
+        self._level_gen = self._done = self._done_b = self._ones = None
 
     # ------------------------------------------------------------------ assets / worlds
     def _upload_assets(self, sc):
@@ -364,7 +381,15 @@ class MiniWorldVecEnv:
 
     # ------------------------------------------------------------------ API
     def reset(self, seed: int | None = None):
-        """Reset every env (env i is seeded with seed + i); returns the observation tensor."""
+        """Reset every env (env i is seeded with seed + i); returns the observation tensor.
+        autoreset="levels": every env starts level next_level[i] of the bank instead — the two masked loads with a mask of ones,
+        nothing is generated or drawn, `seed` is not used — and next_level is refilled."""
+        if self.autoreset_mode == "levels":
+            self._need_levels("reset")
+            self.terminated.zero_()
+            self.truncated.zero_()
+            self._start_levels(self._ones, frames=True)
+            return self.obs
         if seed is not None:
             self._next_seed = seed
         seeds = np.arange(self.num_envs, dtype=np.uint64) + np.uint64(self._next_seed)
@@ -392,12 +417,17 @@ class MiniWorldVecEnv:
         auto-reset, as for a single step), the reward their sum, the flags the last one's, and `self.substeps` (int32[N] on
         the device) the number each env took — 0 for the reset step of autoreset="next_step".  max_episode_steps counts them.
         With frame_stack every call pushes its one frame; read `self.stack` afterwards."""
+        levels = self.autoreset_mode == "levels"
+        if levels:
+            self._need_levels("step")
         if repeat == 1:
             self.engine.step(actions, self.obs, self.depth, self.reward, self.terminated, self.truncated)
-            return self.obs, self.reward, self.terminated, self.truncated
-        if self.substeps is None:
-            self.substeps = self.torch.zeros(self.num_envs, dtype=self.torch.int32, device=self.engine.device)
-        self.engine.step_repeat(actions, repeat, self.obs, self.depth, self.reward, self.terminated, self.truncated, self.substeps)
+        else:
+            if self.substeps is None:
+                self.substeps = self.torch.zeros(self.num_envs, dtype=self.torch.int32, device=self.engine.device)
+            self.engine.step_repeat(actions, repeat, self.obs, self.depth, self.reward, self.terminated, self.truncated, self.substeps)
+        if levels:
+            self._finished_to_levels(frames=True)
         return self.obs, self.reward, self.terminated, self.truncated
 
     def rollout(self, plans, render: bool = True):
@@ -409,7 +439,10 @@ class MiniWorldVecEnv:
         demand) every step's own reward, 0 where the env did not execute it — what a planner discounts from.
         render=False is the frameless call, for planners that read no frames: nothing is drawn or pushed.  `self.obs`,
         `self.depth`, `self.stack` and the final buffers keep what they held and are STALE until the next drawn call (step(),
-        rollout(render=True)), load_state(..., frames) or reset()."""
+        rollout(render=True)), load_state(..., frames) or reset().
+        autoreset="levels": the envs whose episode ended in the call restart from their next level behind it, as in step();
+        render=False loads their states alone (the frames are stale by this call's contract; the state load marks the loaded
+        envs' stacks, so their next push rebuilds them)."""
         torch = self.torch
         if plans.dim() != 2 or plans.shape[1] != self.num_envs:
             raise ValueError(f"plans: need an integer tensor [T, {self.num_envs}], got {tuple(plans.shape)}")
@@ -422,11 +455,120 @@ class MiniWorldVecEnv:
             self._step_rewards = torch.zeros((T, self.num_envs), dtype=torch.float32, device=self.engine.device)
         self.step_rewards = self._step_rewards[:T]
         obs, depth = (self.obs, self.depth) if render else (None, None)
+        if self.autoreset_mode == "levels":
+            self._need_levels("rollout")
         self.engine.step_plan(plans, obs, depth, self.reward, self._step_rewards, self.terminated, self.truncated, self.substeps)
+        if self.autoreset_mode == "levels":
+            self._finished_to_levels(frames=render)
         return obs, self.reward, self.terminated, self.truncated
 
+    # ------------------------------------------------------------------ level sets
+    def make_levels(self, seeds):
+        """A bank of levels: record l of the returned EnvSnapshot IS the reference's env.reset(seed=seeds[l]) on the PCG64 stream —
+        world, agent, random stream, pre-generated next world — together with its first observation (depth, frame stack) as frame
+        records under this env's frame flags.  `seeds` is an integer sequence or tensor of any length L, more than num_envs too: the
+        bank is built num_envs levels at a time (engine.reset with the seeds, a render, a stack refresh, then mw_snapshot_save_at /
+        mw_snapshot_save_frames_at into records base .. base + m - 1).  `snap.seeds` keeps the seeds (int64).
+        Afterwards this env's own state is the last chunk's: call reset() or set_levels() next.
+        A record carries the env's random stream, so under domain randomisation every replay of a level draws the same per-step
+        noise; a bank that keeps the level but not the stream is not built here."""
+        torch = self.torch
+        if isinstance(seeds, torch.Tensor):
+            seeds_np = seeds.detach().cpu().numpy()
+        else:
+            seeds_np = np.asarray(seeds)
+        if seeds_np.ndim != 1 or seeds_np.size == 0 or seeds_np.dtype.kind not in "iu":
+            raise ValueError(f"seeds: need a non-empty 1-D integer sequence, got {seeds_np.dtype} {seeds_np.shape}")
+        if seeds_np.dtype.kind == "i" and (seeds_np < 0).any():
+            raise ValueError("seeds: negative seed")
+        seeds_np = seeds_np.astype(np.uint64)
+        L, N, dev = int(seeds_np.size), self.num_envs, self.engine.device
+        flags = self._frame_flags()
+        data = torch.zeros(self.engine.snapshot_bytes(L), dtype=torch.uint8, device=dev)
+        fdata = torch.zeros(self.engine.snapshot_frames_bytes(L, flags), dtype=torch.uint8, device=dev)
+        for base in range(0, L, N):
+            m = min(N, L - base)
+            mask, full = np.zeros(N, np.uint8), np.zeros(N, np.uint64)
+            mask[:m], full[:m] = 1, seeds_np[base:base + m]
+            self.engine.reset(mask, full)
+            self.engine.render(self.obs, self.depth)
+            if self.frame_stack:
+                self.engine.stack_refresh(self.obs)
+            recs = torch.arange(base, base + m, dtype=torch.int32, device=dev)     # (envs None: env k is item k, k < m)
+            self.engine.snapshot_save_at(data, L, None, recs)
+            self.engine.snapshot_save_frames_at(fdata, L, self.obs, self.depth, flags, None, recs)
+        return EnvSnapshot(data, L, L, fdata, flags, self.frame_stack or 0, torch.from_numpy(seeds_np.astype(np.int64)).to(dev))
+
+    def _check_frame_config(self, snap, what):
+        if snap.frames is None:
+            raise ValueError(f"{what}: the snapshot holds no frame records (make_levels, save_state(frames=True))")
+        if snap.frame_flags != self._frame_flags() or snap.frame_stack != (self.frame_stack or 0):
+            raise ValueError(f"{what}: the snapshot's frame records (flags {snap.frame_flags}, frame_stack {snap.frame_stack}) are not this "
+                             f"env's (flags {self._frame_flags()}, frame_stack {self.frame_stack or 0}: want_depth / frame_stack differ)")
+
+    def set_levels(self, snap, generator=None):
+        """autoreset="levels": `snap` (make_levels, or any snapshot with frame records of this env's frame configuration) becomes the
+        bank finished envs restart from; its buffers are moved to the device once.  Creates `self.level` and `self.next_level`, int32[N]
+        on the device: level[i] is the record env i is playing (`self.played_level`: the one it played in the step that just ended,
+        which differs for the envs that step finished), next_level[i] the one it gets when its episode ends — drawn uniformly
+        from 0 .. len(snap) - 1 with torch.randint(generator=generator) behind every step, and the caller's to overwrite between
+        steps (a level-replay sampler writes its choice there, on the device).  Call reset() next."""
+        torch = self.torch
+        if self.autoreset_mode != "levels":
+            raise RuntimeError(f"set_levels needs autoreset='levels' (this env: {self.autoreset_mode!r})")
+        self._check_frame_config(snap, "set_levels")
+        if snap.count < 1:
+            raise ValueError("set_levels: the snapshot holds no records")
+        dev, N = self.engine.device, self.num_envs
+        self.levels = snap if snap.data.device == dev and snap.frames.device == dev else snap.to(dev)
+        self._level_gen = generator
+        self.level = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.next_level = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.played_level = torch.zeros(N, dtype=torch.int32, device=dev)
+        self._done = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._done_b = torch.zeros(N, dtype=torch.bool, device=dev)
+        self._ones = torch.ones(N, dtype=torch.uint8, device=dev)
+        self._draw_next_levels()
+
+    def _need_levels(self, what):
+        if self.levels is None:
+            raise RuntimeError(f"{what}() with autoreset='levels' before set_levels(): there is no bank to restart finished envs from")
+
+    def _draw_next_levels(self):
+        self.torch.randint(0, self.levels.count, (self.num_envs,), generator=self._level_gen, out=self.next_level)
+
+    def _start_levels(self, mask, frames):
+        """the envs under `mask` (uint8[N], device) start level next_level[i]: states, then frames; then the bookkeeping"""
+        torch, bank = self.torch, self.levels
+        self.engine.snapshot_load_where(bank.data, bank.count, bank.capacity, mask, self.next_level)
+        if frames:
+            self.engine.snapshot_load_frames_where(bank.frames, bank.count, bank.capacity, mask, self.next_level, self.obs, self.depth, bank.frame_flags)
+        torch.ne(mask, 0, out=self._done_b)
+        self.played_level.copy_(self.level)
+        torch.where(self._done_b, self.next_level, self.level, out=self.level)
+        self._draw_next_levels()
+
+    def _finished_to_levels(self, frames):
+        """behind a step in level mode, with no host synchronisation: done, the terminal infos, the two loads, level, next_level"""
+        torch = self.torch
+        torch.bitwise_or(self.terminated, self.truncated, out=self._done)
+        if self._info_kind is not None:
+            # the finished episodes' own values, before the loads replace the states they are read from (final_infos)
+            now = self.infos()[self._info_kind]
+            self._level_final_info()
+            done = self._done.bool()
+            torch.where(done if now.dim() == 1 else done[:, None], now, self._final_info_buf, out=self._final_info_buf)
+        self._start_levels(self._done, frames)
+
+    def _level_final_info(self):
+        if self._final_info_buf is None:
+            dev = self.engine.device
+            self._final_info_buf = (self.torch.zeros(self.num_envs, dtype=self.torch.int32, device=dev) if self._info_kind == "health"
+                                    else self.torch.zeros((self.num_envs, 3), dtype=self.torch.float64, device=dev))
+        return self._final_info_buf
+
     # ------------------------------------------------------------------ save / restore / fork
-    def save_state(self, envs=None, capacity: int | None = None, frames: bool = False):
+    def save_state(self, envs=None, capacity: int | None = None, frames: bool = False, into=None, records=None):
         """The complete state of the envs `envs` (an integer sequence or tensor; None: all of them, in order) as an EnvSnapshot on
         the device: everything that decides their future — poses, entities, step counts, the random stream, pending removals and
         resets, the Maze's own geometry, the pre-generated next world — but no frames (include/mwengine.h: mw_snapshot_save).  One
@@ -436,8 +578,17 @@ class MiniWorldVecEnv:
         with capacity=num_envs: `vec.load_state(vec.save_state([i], capacity=n), records=torch.zeros(n, dtype=torch.int32))`.
         frames=True: a second kernel also saves what the agent saw — the envs' rows of `self.obs`, of `self.depth` with want_depth,
         and their frame stacks with frame_stack (mw_snapshot_save_frames) — into `snap.frames`; load_state() then puts those
-        frames back instead of drawing new ones."""
+        frames back instead of drawing new ones.
+        into=snap, records=idx: the envs are saved into the records idx[k] (distinct) of an EXISTING snapshot on this env's device
+        instead (mw_snapshot_save_at), their frames too when `snap` has frame records — they must be of this env's frame
+        configuration —, and `snap` is returned; its other records keep what they held and its count grows to cover the highest
+        record named.  A running loop adds states to a bank this way: an archive of cells, a curriculum of reached states.
+        ValueError for a snapshot of another frame configuration, for indices of the wrong length, and for `into` with `capacity`."""
         torch = self.torch
+        if into is not None:
+            return self._save_into(into, envs, records, capacity)
+        if records is not None:
+            raise ValueError("save_state: records needs into=<snapshot>")
         envs = None if envs is None else torch.as_tensor(envs)
         count = self.num_envs if envs is None else int(envs.numel())
         capacity = count if capacity is None else int(capacity)
@@ -451,6 +602,30 @@ class MiniWorldVecEnv:
         fdata = torch.zeros(self.engine.snapshot_frames_bytes(capacity, flags), dtype=torch.uint8, device=self.engine.device)
         self.engine.snapshot_save_frames(fdata, capacity, self.obs, self.depth, flags, envs)
         return EnvSnapshot(data, count, capacity, fdata, flags, self.frame_stack or 0)
+
+    def _save_into(self, snap, envs, records, capacity):
+        torch = self.torch
+        if capacity is not None:
+            raise ValueError("save_state: into=<snapshot> has its own capacity; capacity cannot be given with it")
+        if records is None:
+            raise ValueError("save_state: into=<snapshot> needs records=<the record indices>")
+        if snap.frames is not None:
+            self._check_frame_config(snap, "save_state(into=...)")
+        count = self.num_envs if envs is None else int(torch.as_tensor(envs).numel())
+        rec_host = torch.as_tensor(records)
+        if rec_host.dim() != 1 or int(rec_host.numel()) != count:
+            raise ValueError(f"save_state: {tuple(rec_host.shape)} record indices for {count} envs")
+        if count > snap.capacity:
+            raise ValueError(f"save_state: {count} records into a snapshot of capacity {snap.capacity}")
+        if snap.data.device != self.engine.device or (snap.frames is not None and snap.frames.device != self.engine.device):
+            raise ValueError(f"save_state: into=<snapshot> must live on {self.engine.device} (snap.to(device))")
+        envs, recs = self.engine._index_tensor(envs, "envs"), self.engine._index_tensor(records, "records")
+        self.engine.snapshot_save_at(snap.data, snap.capacity, envs, recs)
+        if snap.frames is not None:
+            self.engine.snapshot_save_frames_at(snap.frames, snap.capacity, self.obs, self.depth, snap.frame_flags, envs, recs)
+        if rec_host.device.type == "cpu" and count:     # (device indices: the caller keeps count; nothing is read back here)
+            snap.count = max(snap.count, min(int(rec_host.max()) + 1, snap.capacity))
+        return snap
 
     def _frame_flags(self):
         """the engine.SNAPF_* bits of this env's frame records: depth with want_depth, the stacks with frame_stack"""
@@ -547,6 +722,8 @@ class MiniWorldVecEnv:
         are undefined (mask them with terminated | truncated of the step)."""
         if self._info_kind is None:
             return {}
+        if self.autoreset_mode == "levels":     # (kept by step() itself before the level loads; the engine installs nothing here)
+            return {self._info_kind: self._level_final_info()}
         torch = self.torch
         if self._final_info_buf is None:
             dev = self.engine.device

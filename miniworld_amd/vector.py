@@ -6,7 +6,7 @@
 
 follows gymnasium.vector.VectorEnv's calling convention (num_envs, single_* / batched spaces,
 reset -> (obs, infos), step -> 5-tuple, autoreset mode "same-step" by default: the observation returned with
-a finished episode is the first one of the next episode; or "next-step", below).  Observations, rewards and flags stay
+a finished episode is the first one of the next episode; or "next-step", below; `levels=` chooses the worlds, further below).  Observations, rewards and flags stay
 torch tensors on the engine's GPU by default (`to_numpy=True` copies them to the host like a
 classic VectorEnv); actions may be a torch tensor, a numpy array or a list.
 
@@ -44,6 +44,13 @@ of every frame: -3.7 % with always-turn-left.  For such a consumer:
     envs = MiniWorldVectorEnv("MiniWorld-Hallway-v0", num_envs=4096, frame_cache=0)
 
 Results are bit for bit the same either way; it costs 59 MB of device memory per slot at 4096 envs of 80x60 (78 MB more with depth).
+
+**`levels=`: a finite set of worlds.**  `levels=seeds` (an integer sequence or tensor) builds a bank with one level per seed — level l is
+the reference's `env.reset(seed=seeds[l])` with its first observation —, `levels=snapshot` takes one (MiniWorldVecEnv.make_levels /
+save_state(frames=True)).  Finished envs then restart from a record of the bank in the same step, on the device (MiniWorldVecEnv's
+autoreset="levels"): the adapter advertises same-step auto-reset, info["level"] (int32[N]) is the level each env played in the step that
+just ended, and `self.vec.next_level` (int32[N] on the device) is the caller's to write between steps — a training set and a held-out
+set are two banks, a level-replay sampler writes its choices there.  final_obs is not available in this mode.
 """
 from __future__ import annotations
 
@@ -58,7 +65,8 @@ class MiniWorldVectorEnv(VectorEnvBase):
     metadata = {"autoreset_mode": AUTORESET_SAME_STEP, "render_modes": ["rgb_array"]}
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
-                 frame_reuse: bool = True, frame_cache: int = 4, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset", **kwargs):
+                 frame_reuse: bool = True, frame_cache: int = 4, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset",
+                 levels=None, level_generator=None, **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
         False draws every env on every step, for consumers that write into the returned observation tensor (module docstring).
@@ -68,7 +76,9 @@ class MiniWorldVectorEnv(VectorEnvBase):
         frame_stack=K, stack_pad: observations (and the observation spaces) become the stacks of the last K frames, oldest first
         (MiniWorldVecEnv's frame_stack: Gymnasium's FrameStackObservation / SB3's VecFrameStack on the device) — the engine's
         view, read-only until the next step, or a host copy with to_numpy; with final_obs, info["final_obs"] holds the final
-        stacks (the old stack with the terminal frame appended)."""
+        stacks (the old stack with the terminal frame appended).
+        levels: seeds or an EnvSnapshot with frame records — finished envs restart from that bank (module docstring); same-step only,
+        without final_obs.  level_generator: the torch.Generator of the uniform draws of next_level."""
         if not isinstance(action_repeat, (int, np.integer)) or not 1 <= action_repeat <= 256:
             raise ValueError(f"action_repeat must be an integer in 1 .. 256, not {action_repeat!r}")
         self.action_repeat = int(action_repeat)
@@ -88,7 +98,14 @@ class MiniWorldVectorEnv(VectorEnvBase):
             raise ValueError("final_obs=True needs autoreset_mode='same-step' (next-step returns the terminal frame itself)")
         if final_obs:
             kwargs["final_obs"] = True
+        if levels is not None:
+            if mode != "same-step" or final_obs or kwargs.get("autoreset", True) is not True:
+                raise ValueError("levels= is the same-step auto-reset from a bank: it excludes autoreset_mode='next-step', autoreset= and final_obs=True")
+            kwargs["autoreset"] = "levels"
         self.vec = MiniWorldVecEnv(env_id, num_envs, **kwargs)
+        if levels is not None:
+            from .vec_env import EnvSnapshot
+            self.vec.set_levels(levels if isinstance(levels, EnvSnapshot) else self.vec.make_levels(levels), level_generator)
         self.num_envs = num_envs
         self.to_numpy = to_numpy
         shape, dtype = tuple(self.vec.obs.shape[1:]), {"grey": np.float64}.get(self.vec.obs_layout, np.uint8)
@@ -112,7 +129,8 @@ class MiniWorldVectorEnv(VectorEnvBase):
         return {k: self._out(v) for k, v in self.vec.infos().items()}
 
     def reset(self, *, seed: int | None = None, options: dict | None = None):
-        """Env i is seeded with seed + i (gymnasium's convention for an integer seed)."""
+        """Env i is seeded with seed + i (gymnasium's convention for an integer seed); with levels= every env starts a level of the
+        bank and the seed is not used."""
         obs = self.vec.reset(seed)
         return self._out(self._obs(obs)), {}
 
@@ -125,7 +143,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
         info = self._infos()
         if self.action_repeat > 1:
             info["substeps"] = self._out(self.vec.substeps) if self.to_numpy else self.vec.substeps.clone()
-        if self.vec.autoreset_mode == "same_step":
+        if self.vec.autoreset_mode in ("same_step", "levels"):
             # gymnasium's same-step convention: "_final_info" masks the envs whose episode ended with this step (every family); the
             # finished episodes' own info under "final_info" where the family has info keys — clones, the engine's buffers are
             # rewritten by the next step.  ("final_obs" with final_obs=True: see the module's docstring.)
@@ -139,6 +157,8 @@ class MiniWorldVectorEnv(VectorEnvBase):
                 final = {k: (self._out(v) if self.to_numpy else v.clone()) for k, v in self.vec.final_infos().items()}
                 final.update({"_" + k: done for k in list(final)})
                 info["final_info"] = final
+        if self.vec.autoreset_mode == "levels":
+            info["level"] = self._out(self.vec.played_level) if self.to_numpy else self.vec.played_level.clone()
         return self._out(self._obs(obs)), self._out(rew), self._out(term.bool()), self._out(trunc.bool()), info
 
     def render(self):

@@ -12,6 +12,14 @@ frame_stack=4), Maze x 1024 and PickupObjects (domain randomisation) x 2048.
                                                               # the parent commit and in this tree
     python tools/perf/snapshot_cost.py --fork-vs <parent checkout> # fork(src) of the parent commit against fork(src, frames=True) of
                                                               # this tree: alternating windows, a process each, one JSON line per config
+    rocprofv3 --kernel-trace --stats ... -- python tools/perf/snapshot_cost.py --profile hallway --op load_where --density 0.015625
+                                                              # the two masked loads (mw_snapshot_load_where / _frames_where) at a mask
+                                                              # density, records drawn from 256 levels, a step between the calls
+    python tools/perf/snapshot_cost.py --op level_step --level-vs <parent checkout>
+                                                              # the step loop of Hallway x 4096 over 256 levels: autoreset="levels" on this
+                                                              # tree against the host-driven loop of the parent commit (done.nonzero(),
+                                                              # load_state(envs, records, frames=True)), and — for information — this tree's
+                                                              # same-step auto-reset; alternating windows, a process each
 
 Wall time: per config one env; the timed windows alternate between save_state(), load_state(snap), fork(random src), a render alone (what
 load_state and fork end with) and the only thing a user could do before: engine.get_state() + engine.set_state() through the host —
@@ -46,6 +54,32 @@ def make(name):
     vec.reset()
     g = torch.Generator(device="cuda").manual_seed(1)
     return vec, n, n_act, g
+
+
+LEVELS = 256
+
+
+def profile_where(name, density, reps, warmup):
+    """the run a profiler wraps for the masked loads: `reps` launches of each at one mask density, a step between the calls"""
+    import torch
+    vec, n, n_act, g = make(name)
+    bank = vec.make_levels(torch.arange(LEVELS) + 1000)
+    vec.reset()
+    for _ in range(warmup):
+        vec.step(torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32))
+    e, flags = vec.engine, bank.frame_flags
+    mask = (torch.rand(n, generator=g, device="cuda") < density).to(torch.uint8)
+    recs = torch.randint(0, LEVELS, (n,), generator=g, device="cuda", dtype=torch.int32)
+    for _ in range(reps):
+        e.snapshot_load_where(bank.data, bank.count, bank.capacity, mask, recs)
+        e.snapshot_load_frames_where(bank.frames, bank.count, bank.capacity, mask, recs, vec.obs, vec.depth, flags)
+        vec.step(torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32))
+    torch.cuda.synchronize()
+    e.check()
+    print(json.dumps({"config": name, "density": density, "masked_envs": int(mask.sum()), "num_envs": n, "launches": reps,
+                      "state_record_bytes": round((e.snapshot_bytes(n) - e.snapshot_bytes(0)) / n, 1),
+                      "frame_record_bytes": round((e.snapshot_frames_bytes(n, flags) - e.snapshot_frames_bytes(0, flags)) / n, 1)}), flush=True)
+    vec.close()
 
 
 def profile(name, op, reps, warmup):
@@ -181,6 +215,77 @@ def fork_vs(parent, names, windows, reps, warmup):
                           "every_frames_window_below_every_parent_window": max(us["fork_frames"]) < min(us["parent_fork"])}), flush=True)
 
 
+def level_window(mode, steps, warmup):
+    """one window of the level step loop in a process of its own (level_vs), Hallway x 4096 over LEVELS levels, uniform-random actions,
+    default episode lengths.  "levels": autoreset="levels" of this tree.  "host": what the parent commit can do — autoreset=False, the
+    finished envs read on the host, load_state(envs, records, frames=True) —, written with the parent's calls alone.  "same_step": the
+    generator's own auto-reset, no levels."""
+    import numpy as np
+    import torch
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    env_id, n, n_act, _ = CONFIGS["hallway"]
+    g = torch.Generator(device="cuda").manual_seed(1)
+    draw = lambda: torch.randint(0, LEVELS, (n,), generator=g, device="cuda", dtype=torch.int32)     # noqa: E731
+    bank = nxt = None
+    if mode == "levels":
+        vec = MiniWorldVecEnv(env_id, n, seed=0, autoreset="levels")
+        vec.set_levels(vec.make_levels(torch.arange(LEVELS) + 1000), generator=g)
+        vec.reset()
+    elif mode == "host":
+        vec = MiniWorldVecEnv(env_id, n, seed=0, autoreset=False)
+        mask, seeds = np.zeros(n, np.uint8), np.zeros(n, np.uint64)
+        mask[:LEVELS], seeds[:LEVELS] = 1, np.arange(LEVELS) + 1000
+        vec.reset()
+        vec.engine.reset(mask, seeds)
+        vec.engine.render(vec.obs, vec.depth)
+        bank = vec.save_state(torch.arange(LEVELS), capacity=n, frames=True)      # (capacity n: one load may move every env)
+        nxt = draw()
+        vec.load_state(bank, records=nxt, frames=True)
+        nxt = draw()
+    else:
+        vec = MiniWorldVecEnv(env_id, n, seed=0)
+        vec.reset()
+
+    def step():
+        nonlocal nxt
+        act = torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32)
+        _, _, term, trunc = vec.step(act)
+        if mode == "host":
+            idx = (term | trunc).nonzero().squeeze(1)
+            if idx.numel():
+                vec.load_state(bank, envs=idx, records=nxt[idx], frames=True)
+            nxt = draw()
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    us = 1e6 * (time.perf_counter() - t0) / steps
+    vec.engine.check()
+    vec.close()
+    print(json.dumps({"us": round(us, 1)}), flush=True)
+
+
+def level_vs(parent, windows, steps, warmup):
+    """alternating windows, every window a process of its own that runs this very file on its tree (--root)"""
+    us = {"levels": [], "host_parent": [], "same_step": []}
+    for _ in range(windows):
+        for tag, root, mode in (("levels", ROOT, "levels"), ("host_parent", parent, "host"), ("same_step", ROOT, "same_step")):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--root", root, "--level-window", mode, "--reps", str(steps),
+                                "--warmup", str(warmup)], cwd=root, capture_output=True, text=True, timeout=600)
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+            if p.returncode != 0 or not line:
+                print(json.dumps({"tree": tag, "error": (p.stdout + p.stderr)[-2000:]}), flush=True)
+                raise SystemExit(1)
+            us[tag].append(json.loads(line[-1])["us"])
+    n = CONFIGS["hallway"][1]
+    print(json.dumps({"config": "hallway", "num_envs": n, "levels": LEVELS, "steps_per_window": steps, "windows_us_per_step": us,
+                      "env_steps_per_s_median": {k: round(n / sorted(v)[len(v) // 2] * 1e6) for k, v in us.items()},
+                      "every_levels_window_below_every_host_window": max(us["levels"]) < min(us["host_parent"])}), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--configs", default="hallway,hallway_stack4,maze,pickup_dr")
@@ -188,7 +293,10 @@ def main():
     p.add_argument("--reps", type=int, default=50, help="calls per timed window (the host round trip: a tenth)")
     p.add_argument("--warmup", type=int, default=100, help="steps before anything is measured")
     p.add_argument("--profile", choices=sorted(CONFIGS), help="one config, untimed: the run a profiler wraps")
-    p.add_argument("--op", choices=["save_load", "fork", "fork_frames"], default="save_load")
+    p.add_argument("--op", choices=["save_load", "fork", "fork_frames", "load_where", "level_step"], default="save_load")
+    p.add_argument("--density", type=float, default=1.0, help="--op load_where: the share of envs under the mask")
+    p.add_argument("--level-vs", metavar="PARENT", help="--op level_step: a built checkout of the parent commit for the host-driven loop")
+    p.add_argument("--level-window", choices=["levels", "host", "same_step"], help=argparse.SUPPRESS)
     p.add_argument("--bench", metavar="PARENT", help="a built checkout of the parent commit: alternate bench.py between it and this tree")
     p.add_argument("--rounds", type=int, default=2)
     p.add_argument("--fork-vs", metavar="PARENT", help="a built checkout of the parent commit: its fork(src) against this tree's fork(src, frames=True)")
@@ -198,6 +306,14 @@ def main():
     args = p.parse_args()
     if args.root:               # (a window of fork_vs: the package of that tree)
         sys.path.insert(0, os.path.abspath(args.root))
+    if args.level_window:
+        return level_window(args.level_window, args.reps, args.warmup)
+    if args.op == "level_step":
+        if not args.level_vs:
+            p.error("--op level_step needs --level-vs <parent checkout>")
+        return level_vs(os.path.abspath(args.level_vs), args.windows, 200 if args.reps == 50 else args.reps, args.warmup)
+    if args.profile and args.op == "load_where":
+        return profile_where(args.profile, args.density, args.reps, args.warmup)
     if args.fork_window:
         return fork_window(args.fork_window, args.frames, args.reps, args.warmup)
     if args.fork_vs:
