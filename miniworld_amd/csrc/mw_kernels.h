@@ -155,44 +155,38 @@ extern "C" __global__ void mw_stack_plan_kernel(int N, const uint8_t *__restrict
 
 // snapshot records (mw_snapshot.hip; the layout: mw_snapshot.h): one launch per save, one per load.  A 1-D grid of MW_SNAP_THREADS
 // lanes: first the component blocks — (row of a component, 256 consecutive items), a lane per item —, then, with per-env geometry
-// sets, the blob blocks — (item, geometry set, chunk of its polygons or segments), 16-byte units.  Item k is (env d_envs[k] or k,
-// record d_recs[k] or k); every index is tested against its limit, an offending item is skipped and sets MW_ST_SNAPSHOT_BAD.
+// sets, the blob blocks — (item, geometry set, chunk of its polygons or segments), 16-byte units.
+//
+// The items of a call, the last arguments of all four kernels.  Item k is present when k < count and (mask is null or mask[k] != 0);
+// its env is d_envs ? d_envs[k] : k, its record d_recs ? d_recs[k] : k, and neither array is read for an absent item.  Every index is
+// tested against its limit; an offending item is skipped and sets MW_ST_SNAPSHOT_BAD.  So the plain calls, the saves into chosen records
+// (_at) and the masked loads (_where: count = N, d_envs null; a workgroup whose items are all unmasked leaves after reading the mask)
+// are the same kernels.  (Separate parameters, not a struct: the note at MW_RASTER_ARGS.)
+#define MW_SNAP_ITEMS const int32_t *__restrict__ d_envs, const int32_t *__restrict__ d_recs, const uint8_t *__restrict__ mask
 #define MW_SNAP_ARGS \
-    const MwSnapTable *__restrict__ tab, MwSnapKey key, int N, int capacity, int count, int item_chunks, const int32_t *__restrict__ d_envs, \
-    uint32_t *__restrict__ status
-extern "C" __global__ void mw_snapshot_save_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap);
+    const MwSnapTable *__restrict__ tab, MwSnapKey key, int N, int capacity, int count, int item_chunks, uint32_t *__restrict__ status
+extern "C" __global__ void mw_snapshot_save_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap, MW_SNAP_ITEMS);
 //   n_recs               the records of the buffer that are valid
 //   frame_clean, occ_valid, stack_flags  what a load resets for every env it writes (the last two may be null)
-extern "C" __global__ void mw_snapshot_load_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap, const int32_t *__restrict__ d_recs, int n_recs,
-                                                   uint8_t *__restrict__ frame_clean, int32_t *__restrict__ occ_valid, uint8_t *__restrict__ stack_flags);
-// the same bodies, items named otherwise.  mw_snapshot_save_at: item k is (env d_envs[k] or k, record d_recs[k] or k) — a save into chosen
-// records.  mw_snapshot_load_where: count = N, item k is env k where mask[k] != 0 and its record d_recs[k] (not read elsewhere; d_envs is
-// not read); a workgroup whose items are all unmasked leaves after reading the mask.  fc_epoch: advanced for every env written
-// (MwArgs::fc_epoch), which stands in for the host's cache-wide invalidation.
-extern "C" __global__ void mw_snapshot_save_at_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap, const int32_t *__restrict__ d_recs);
-extern "C" __global__ void mw_snapshot_load_where_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap, const int32_t *__restrict__ d_recs, int n_recs,
-                                                         uint8_t *__restrict__ frame_clean, int32_t *__restrict__ occ_valid, uint8_t *__restrict__ stack_flags,
-                                                         const uint8_t *__restrict__ mask, uint32_t *__restrict__ fc_epoch);
+//   fc_epoch             null, or advanced for every env written (MwArgs::fc_epoch): the masked form, where it stands in for the host's
+//                        cache-wide invalidation
+extern "C" __global__ void mw_snapshot_load_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap, int n_recs, uint8_t *__restrict__ frame_clean,
+                                                   int32_t *__restrict__ occ_valid, uint8_t *__restrict__ stack_flags, uint32_t *__restrict__ fc_epoch,
+                                                   MW_SNAP_ITEMS);
 
 // frame records (mw_snapframes.hip; the layout and MwSnapfArgs: mw_snapframes.h): one launch per call, a 1-D grid of MW_SNAPF_THREADS
-// lanes, workgroup (item, chunk of the record: its obs row, its depth row, its K window frames).  Items and their index tests as for
-// the state records; a load compares the key first.  The frame buffer does not alias obs, depth or the ring (the caller's contract).
+// lanes, workgroup (item, chunk of the record: its obs row, its depth row, its K window frames).  Items (MW_SNAP_ITEMS; a.count, a.N,
+// a.n_recs) and their index tests as for the state records; a load compares the key first.  The frame buffer does not alias obs, depth
+// or the ring (the caller's contract).
 //   obs, depth, ring, stack_flags  the caller's rows, the stack's ring and the CURRENT half of its flag bytes (depth / the last two:
 //                                  null without MW_SNAPF_DEPTH / MW_SNAPF_STACK)
-#define MW_SNAPF_ARGS MwSnapfArgs a, const int32_t *__restrict__ d_envs, uint32_t *__restrict__ status
+#define MW_SNAPF_ARGS MwSnapfArgs a, uint32_t *__restrict__ status
 extern "C" __global__ void mw_snapshot_save_frames_kernel(MW_SNAPF_ARGS, const uint8_t *__restrict__ obs, const uint8_t *__restrict__ depth,
                                                           const uint8_t *__restrict__ ring, const uint8_t *__restrict__ stack_flags,
-                                                          uint8_t *__restrict__ frames);
-extern "C" __global__ void mw_snapshot_load_frames_kernel(MW_SNAPF_ARGS, const int32_t *__restrict__ d_recs, const uint8_t *__restrict__ frames,
-                                                          uint8_t *__restrict__ obs, uint8_t *__restrict__ depth, uint8_t *__restrict__ ring,
-                                                          uint8_t *__restrict__ stack_flags);
-// ... and their forms with chosen records (a save) and with a mask over all N envs (a load; a.count = N), as for the state records
-extern "C" __global__ void mw_snapshot_save_frames_at_kernel(MW_SNAPF_ARGS, const uint8_t *__restrict__ obs, const uint8_t *__restrict__ depth,
-                                                             const uint8_t *__restrict__ ring, const uint8_t *__restrict__ stack_flags,
-                                                             uint8_t *__restrict__ frames, const int32_t *__restrict__ d_recs);
-extern "C" __global__ void mw_snapshot_load_frames_where_kernel(MW_SNAPF_ARGS, const int32_t *__restrict__ d_recs, const uint8_t *__restrict__ frames,
-                                                                uint8_t *__restrict__ obs, uint8_t *__restrict__ depth, uint8_t *__restrict__ ring,
-                                                                uint8_t *__restrict__ stack_flags, const uint8_t *__restrict__ mask);
+                                                          uint8_t *__restrict__ frames, MW_SNAP_ITEMS);
+extern "C" __global__ void mw_snapshot_load_frames_kernel(MW_SNAPF_ARGS, const uint8_t *__restrict__ frames, uint8_t *__restrict__ obs,
+                                                          uint8_t *__restrict__ depth, uint8_t *__restrict__ ring, uint8_t *__restrict__ stack_flags,
+                                                          MW_SNAP_ITEMS);
 
 // the host runtime's own small kernels (mw_engine_kernels.hip): mw_get_info's gather; behind the first pass of a same-step step with
 // final observations, the list of the envs that finished and the copy of their rows into the final buffers

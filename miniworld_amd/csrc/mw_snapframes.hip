@@ -1,7 +1,8 @@
 // Frame records (mw_snapshot_save_frames / mw_snapshot_load_frames): an env's rows of the caller's observation and depth buffers and its
 // frame stack out into a caller's buffer and back — what lets a fork carry the frames it already has instead of drawing them again.
 // A pure copy: no arithmetic, nothing but loads, stores and index tests.  The layout of the buffer: mw_snapframes.h.
-// mw_snapshot_save_frames_at and mw_snapshot_load_frames_where are the same body with the items named otherwise (Form).
+// The forms with chosen records (_at) and with a device mask over all envs (_where) are the same two kernels: the items are named by
+// d_envs, d_recs and mask (MW_SNAP_ITEMS, mw_kernels.h).
 //
 // One launch per call, a 1-D grid: workgroup (item, chunk of the record), the chunks of an item being those of its obs row, of its
 // depth row and of its K window frames.  What happens to an item — index valid, key equal, which part a chunk belongs to — is uniform
@@ -51,22 +52,17 @@ __device__ __forceinline__ void copy_chunk(uint8_t *dst_bytes, uint8_t *dst2_byt
     }
 }
 
-// How a call names its items, as for the state records (mw_snapshot.hip).  LIST: item k is (env d_envs[k] or k, record d_recs[k] or k —
-// a save: always k).  AT (mw_snapshot_save_frames_at): a save honours d_recs too.  WHERE (mw_snapshot_load_frames_where): item k is env k,
-// k < N = count, present where mask[k] != 0, its record d_recs[k] — not read under a zero mask byte.
-enum Form { LIST = 0, AT = 1, WHERE = 2 };
-
 // LOAD: the engine side (obs, depth, ring, stack_flags) is written from `frames`; else the other way round
-template <bool LOAD, typename T, Form FORM = LIST>
+template <bool LOAD, typename T>
 __device__ __forceinline__ void frames_block(const MwSnapfArgs &a, const int32_t *__restrict__ d_envs, const int32_t *__restrict__ d_recs,
                                              uint8_t *obs, uint8_t *depth, uint8_t *ring, uint8_t *stack_flags, uint8_t *frames,
-                                             uint32_t *__restrict__ status, const uint8_t *__restrict__ mask = nullptr)
+                                             uint32_t *__restrict__ status, const uint8_t *__restrict__ mask)
 {
     const int k = (int)(blockIdx.x / (unsigned)a.chunks_per_item), c = (int)(blockIdx.x % (unsigned)a.chunks_per_item);
     if (k >= a.count) return;
-    if (FORM == WHERE && !mask[k]) return;
-    const int env = FORM != WHERE && d_envs ? d_envs[k] : k;
-    const int rec = FORM == WHERE ? d_recs[k] : (LOAD || FORM == AT) && d_recs ? d_recs[k] : k;        // (a plain save: record k, k < count <= capacity)
+    if (mask && !mask[k]) return;
+    const int env = d_envs ? d_envs[k] : k;
+    const int rec = d_recs ? d_recs[k] : k;
     if ((unsigned)env >= (unsigned)a.N || (unsigned)rec >= (unsigned)a.n_recs) {
         if (c == 0 && threadIdx.x == 0) atomicOr(status, MW_ST_SNAPSHOT_BAD);
         return;
@@ -102,79 +98,50 @@ __device__ __forceinline__ void frames_block(const MwSnapfArgs &a, const int32_t
     else copy_chunk<T>(in_record, nullptr, in_engine, bytes / sizeof(T), chunk);
 }
 
+// the header: the key, then zeros, by one lane of the first workgroup (every save writes it, an empty one too)
+__device__ __forceinline__ void write_header(const MwSnapfKey &key, uint8_t *frames)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        uint32_t *head = reinterpret_cast<uint32_t *>(frames);
+#pragma unroll
+        for (int i = 0; i < MW_SNAPF_KEY_WORDS; ++i) head[i] = key.w[i];
+#pragma unroll
+        for (int i = MW_SNAPF_KEY_WORDS; i < MW_SNAPF_HEADER_BYTES / 4; ++i) head[i] = 0u;
+    }
+}
+
+// a buffer of another layout (or no frame records at all): nothing of it is read beyond its first words, nothing is written
+__device__ __forceinline__ bool key_matches(const MwSnapfKey &key, const uint8_t *frames, uint32_t *__restrict__ status)
+{
+    const uint32_t *head = reinterpret_cast<const uint32_t *>(frames);
+    bool same = true;
+#pragma unroll
+    for (int i = 0; i < MW_SNAPF_KEY_WORDS; ++i) same = same && head[i] == key.w[i];
+    if (!same && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(status, MW_ST_SNAPSHOT_BAD);
+    return same;
+}
+
 }  // namespace
 
 extern "C" __global__ __launch_bounds__(MW_SNAPF_THREADS) void mw_snapshot_save_frames_kernel(MW_SNAPF_ARGS, const uint8_t *__restrict__ obs,
                                                                                              const uint8_t *__restrict__ depth, const uint8_t *__restrict__ ring,
-                                                                                             const uint8_t *__restrict__ stack_flags, uint8_t *__restrict__ frames)
+                                                                                             const uint8_t *__restrict__ stack_flags, uint8_t *__restrict__ frames,
+                                                                                             MW_SNAP_ITEMS)
 {
-    // the header: the key, then zeros, by one lane of the first workgroup (every save writes it, an empty one too)
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        uint32_t *head = reinterpret_cast<uint32_t *>(frames);
-#pragma unroll
-        for (int i = 0; i < MW_SNAPF_KEY_WORDS; ++i) head[i] = a.key.w[i];
-#pragma unroll
-        for (int i = MW_SNAPF_KEY_WORDS; i < MW_SNAPF_HEADER_BYTES / 4; ++i) head[i] = 0u;
-    }
+    write_header(a.key, frames);
     // (the engine side is only read: frames_block<false> never writes through these pointers)
     uint8_t *o = const_cast<uint8_t *>(obs), *d = const_cast<uint8_t *>(depth), *g = const_cast<uint8_t *>(ring), *f = const_cast<uint8_t *>(stack_flags);
-    if (a.wide) frames_block<false, uint4>(a, d_envs, nullptr, o, d, g, f, frames, status);
-    else frames_block<false, uint8_t>(a, d_envs, nullptr, o, d, g, f, frames, status);
+    if (a.wide) frames_block<false, uint4>(a, d_envs, d_recs, o, d, g, f, frames, status, mask);
+    else frames_block<false, uint8_t>(a, d_envs, d_recs, o, d, g, f, frames, status, mask);
 }
 
-extern "C" __global__ __launch_bounds__(MW_SNAPF_THREADS) void mw_snapshot_load_frames_kernel(MW_SNAPF_ARGS, const int32_t *__restrict__ d_recs,
-                                                                                             const uint8_t *__restrict__ frames, uint8_t *__restrict__ obs,
-                                                                                             uint8_t *__restrict__ depth, uint8_t *__restrict__ ring,
-                                                                                             uint8_t *__restrict__ stack_flags)
+extern "C" __global__ __launch_bounds__(MW_SNAPF_THREADS) void mw_snapshot_load_frames_kernel(MW_SNAPF_ARGS, const uint8_t *__restrict__ frames,
+                                                                                             uint8_t *__restrict__ obs, uint8_t *__restrict__ depth,
+                                                                                             uint8_t *__restrict__ ring, uint8_t *__restrict__ stack_flags,
+                                                                                             MW_SNAP_ITEMS)
 {
-    // a buffer of another layout (or no frame records at all): nothing of it is read beyond its first words, nothing is written
-    const uint32_t *head = reinterpret_cast<const uint32_t *>(frames);
-    bool same = true;
-#pragma unroll
-    for (int i = 0; i < MW_SNAPF_KEY_WORDS; ++i) same = same && head[i] == a.key.w[i];
-    if (!same) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(status, MW_ST_SNAPSHOT_BAD);
-        return;
-    }
+    if (!key_matches(a.key, frames, status)) return;
     uint8_t *f = const_cast<uint8_t *>(frames);
-    if (a.wide) frames_block<true, uint4>(a, d_envs, d_recs, obs, depth, ring, stack_flags, f, status);
-    else frames_block<true, uint8_t>(a, d_envs, d_recs, obs, depth, ring, stack_flags, f, status);
-}
-
-// The forms with chosen records and with a mask: the same two kernels around other instantiations of frames_block.  (Their header and
-// key lines are written out again rather than shared through a function: with one, the two kernels above came out with other registers.)
-extern "C" __global__ __launch_bounds__(MW_SNAPF_THREADS) void mw_snapshot_save_frames_at_kernel(MW_SNAPF_ARGS, const uint8_t *__restrict__ obs,
-                                                                                                const uint8_t *__restrict__ depth, const uint8_t *__restrict__ ring,
-                                                                                                const uint8_t *__restrict__ stack_flags, uint8_t *__restrict__ frames,
-                                                                                                const int32_t *__restrict__ d_recs)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        uint32_t *head = reinterpret_cast<uint32_t *>(frames);
-#pragma unroll
-        for (int i = 0; i < MW_SNAPF_KEY_WORDS; ++i) head[i] = a.key.w[i];
-#pragma unroll
-        for (int i = MW_SNAPF_KEY_WORDS; i < MW_SNAPF_HEADER_BYTES / 4; ++i) head[i] = 0u;
-    }
-    uint8_t *o = const_cast<uint8_t *>(obs), *d = const_cast<uint8_t *>(depth), *g = const_cast<uint8_t *>(ring), *f = const_cast<uint8_t *>(stack_flags);
-    if (a.wide) frames_block<false, uint4, AT>(a, d_envs, d_recs, o, d, g, f, frames, status);
-    else frames_block<false, uint8_t, AT>(a, d_envs, d_recs, o, d, g, f, frames, status);
-}
-
-// (a.count = N: the grid is over every env; d_envs is not read)
-extern "C" __global__ __launch_bounds__(MW_SNAPF_THREADS) void mw_snapshot_load_frames_where_kernel(MW_SNAPF_ARGS, const int32_t *__restrict__ d_recs,
-                                                                                                   const uint8_t *__restrict__ frames, uint8_t *__restrict__ obs,
-                                                                                                   uint8_t *__restrict__ depth, uint8_t *__restrict__ ring,
-                                                                                                   uint8_t *__restrict__ stack_flags, const uint8_t *__restrict__ mask)
-{
-    const uint32_t *head = reinterpret_cast<const uint32_t *>(frames);
-    bool same = true;
-#pragma unroll
-    for (int i = 0; i < MW_SNAPF_KEY_WORDS; ++i) same = same && head[i] == a.key.w[i];
-    if (!same) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(status, MW_ST_SNAPSHOT_BAD);
-        return;
-    }
-    uint8_t *f = const_cast<uint8_t *>(frames);
-    if (a.wide) frames_block<true, uint4, WHERE>(a, nullptr, d_recs, obs, depth, ring, stack_flags, f, status, mask);
-    else frames_block<true, uint8_t, WHERE>(a, nullptr, d_recs, obs, depth, ring, stack_flags, f, status, mask);
+    if (a.wide) frames_block<true, uint4>(a, d_envs, d_recs, obs, depth, ring, stack_flags, f, status, mask);
+    else frames_block<true, uint8_t>(a, d_envs, d_recs, obs, depth, ring, stack_flags, f, status, mask);
 }

@@ -1,8 +1,9 @@
 // Snapshot records (mw_snapshot_save / mw_snapshot_load): the complete state of an env out of the engine's arrays into a caller's
 // buffer and back — the hot path of a fork loop (tree search, particle resampling: save the batch, load it back through an index).
 // A pure copy: no arithmetic, nothing but loads, stores and index tests.  The layout of the buffer: mw_snapshot.h.
-// mw_snapshot_save_at and mw_snapshot_load_where are the same body with the items named otherwise (Form): a level bank filled in chunks,
-// and the envs a step finished — known on the device alone — restarted from it.
+// The forms with chosen records (mw_snapshot_save_at) and with a device mask over all envs (mw_snapshot_load_where) are the same two
+// kernels: which of d_envs, d_recs and mask is null names the items (MW_SNAP_ITEMS, mw_kernels.h) — a level bank filled in chunks, and
+// the envs a step finished — known on the device alone — restarted from it.
 //
 // One launch per call, a 1-D grid of two kinds of workgroups, told apart by blockIdx alone:
 //   component blocks  (row r of the state, 256 consecutive items): the engine's state is component-major over the envs and the
@@ -28,18 +29,12 @@ namespace {
 
 struct Item { int env, rec; bool ok; };
 
-// How a call names its items.  LIST: item k is (env d_envs[k] or k, record d_recs[k] or k — a save: always k), k < count.  AT
-// (mw_snapshot_save_at): a save honours d_recs too.  WHERE (mw_snapshot_load_where): item k is env k, k < N, present where mask[k] != 0,
-// and its record is d_recs[k] — not read under a zero mask byte.
-enum Form { LIST = 0, AT = 1, WHERE = 2 };
-
-// item k of the call: the env and the record, each tested against its limit
-template <bool LOAD, Form FORM>
+// item k of the call (MW_SNAP_ITEMS; the caller has seen that it is present): the env and the record, each tested against its limit
 __device__ __forceinline__ Item item_of(int k, int N, int n_recs, const int32_t *__restrict__ d_envs, const int32_t *__restrict__ d_recs)
 {
     Item it;
-    it.env = FORM != WHERE && d_envs ? d_envs[k] : k;
-    it.rec = FORM == WHERE ? d_recs[k] : (LOAD || FORM == AT) && d_recs ? d_recs[k] : k;       // (a plain save: record k, k < count <= capacity)
+    it.env = d_envs ? d_envs[k] : k;
+    it.rec = d_recs ? d_recs[k] : k;
     it.ok = (unsigned)it.env < (unsigned)N && (unsigned)it.rec < (unsigned)n_recs;
     return it;
 }
@@ -47,13 +42,13 @@ __device__ __forceinline__ Item item_of(int k, int N, int n_recs, const int32_t 
 template <typename T>
 __device__ __forceinline__ void move(void *dst, const void *src) { *static_cast<T *>(dst) = *static_cast<const T *>(src); }
 
-// (mask, fc_epoch: the WHERE form alone — which envs are items, and the frame-cache epoch a written env advances)
-template <bool LOAD, Form FORM = LIST>
+// (fc_epoch: null, or the frame-cache epoch a written env advances)
+template <bool LOAD>
 __device__ __forceinline__ void snapshot_block(const MwSnapTable *__restrict__ tab, int N, int capacity, int count, int item_chunks,
                                                const int32_t *__restrict__ d_envs, const int32_t *__restrict__ d_recs, int n_recs,
                                                uint32_t *__restrict__ status, uint8_t *snap, uint8_t *__restrict__ frame_clean,
                                                int32_t *__restrict__ occ_valid, uint8_t *__restrict__ stack_flags,
-                                               const uint8_t *__restrict__ mask = nullptr, uint32_t *__restrict__ fc_epoch = nullptr)
+                                               const uint8_t *__restrict__ mask, uint32_t *__restrict__ fc_epoch)
 {
     const int tid = (int)threadIdx.x;
     const int total_rows = tab->total_rows;
@@ -65,8 +60,8 @@ __device__ __forceinline__ void snapshot_block(const MwSnapTable *__restrict__ t
         const MwSnapRow comp = tab->comp[tab->row_comp[row]];
         const int k = chunk * MW_SNAP_THREADS + tid;
         if (k >= count) return;
-        if (FORM == WHERE && !mask[k]) return;
-        const Item it = item_of<LOAD, FORM>(k, N, n_recs, d_envs, d_recs);
+        if (mask && !mask[k]) return;
+        const Item it = item_of(k, N, n_recs, d_envs, d_recs);
         if (!it.ok) {
             if (row == 0) atomicOr(status, MW_ST_SNAPSHOT_BAD);
             return;
@@ -89,9 +84,9 @@ __device__ __forceinline__ void snapshot_block(const MwSnapTable *__restrict__ t
                 const uint8_t pending = snap[MW_SNAP_HEADER_BYTES + cap * tab->reset_pending_unit + (size_t)it.rec];
                 stack_flags[it.env] = (uint8_t)(MW_STACK_FRESH | (pending ? MW_STACK_PENDING : 0));
             }
-            // ... and the WHERE form, which leaves the host's cache-wide invalidation out: no cached frame of the env matches again
+            // ... and the masked form, which leaves the host's cache-wide invalidation out: no cached frame of the env matches again
             // (the epoch is part of the key and of no record, MwArgs::fc_epoch)
-            if (FORM == WHERE) fc_epoch[it.env] += 1u;
+            if (fc_epoch) fc_epoch[it.env] += 1u;
         }
         return;
     }
@@ -102,8 +97,8 @@ __device__ __forceinline__ void snapshot_block(const MwSnapTable *__restrict__ t
     const long long g = (long long)blockIdx.x - comp_blocks;
     const int k = (int)(g / per_item), within = (int)(g % per_item);
     if (k >= count) return;
-    if (FORM == WHERE && !mask[k]) return;
-    const Item it = item_of<LOAD, FORM>(k, N, n_recs, d_envs, d_recs);
+    if (mask && !mask[k]) return;
+    const Item it = item_of(k, N, n_recs, d_envs, d_recs);
     if (!it.ok) return;         // (the status bit: the item's component block of row 0)
     const int set = within / per_set, part = within % per_set;
     const bool polys = part < poly_chunks;
@@ -159,36 +154,19 @@ __device__ __forceinline__ bool key_matches(const MwSnapKey &key, const uint8_t 
 
 }  // namespace
 
-extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_save_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap)
+// (a save: every record of the buffer may be written, n_recs is the capacity)
+extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_save_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap, MW_SNAP_ITEMS)
 {
     write_header(key, snap);
-    snapshot_block<false>(tab, N, capacity, count, item_chunks, d_envs, nullptr, capacity, status, snap, nullptr, nullptr, nullptr);
+    snapshot_block<false>(tab, N, capacity, count, item_chunks, d_envs, d_recs, capacity, status, snap, nullptr, nullptr, nullptr, mask, nullptr);
 }
 
-extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_load_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap,
-                                                                                     const int32_t *__restrict__ d_recs, int n_recs,
+extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_load_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap, int n_recs,
                                                                                      uint8_t *__restrict__ frame_clean, int32_t *__restrict__ occ_valid,
-                                                                                     uint8_t *__restrict__ stack_flags)
+                                                                                     uint8_t *__restrict__ stack_flags, uint32_t *__restrict__ fc_epoch,
+                                                                                     MW_SNAP_ITEMS)
 {
     if (!key_matches(key, snap, status)) return;
-    snapshot_block<true>(tab, N, capacity, count, item_chunks, d_envs, d_recs, n_recs, status, const_cast<uint8_t *>(snap), frame_clean, occ_valid, stack_flags);
-}
-
-extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_save_at_kernel(MW_SNAP_ARGS, uint8_t *__restrict__ snap,
-                                                                                        const int32_t *__restrict__ d_recs)
-{
-    write_header(key, snap);
-    snapshot_block<false, AT>(tab, N, capacity, count, item_chunks, d_envs, d_recs, capacity, status, snap, nullptr, nullptr, nullptr);
-}
-
-// (count = N: the grid is over every env; d_envs is not read)
-extern "C" __global__ __launch_bounds__(MW_SNAP_THREADS) void mw_snapshot_load_where_kernel(MW_SNAP_ARGS, const uint8_t *__restrict__ snap,
-                                                                                           const int32_t *__restrict__ d_recs, int n_recs,
-                                                                                           uint8_t *__restrict__ frame_clean, int32_t *__restrict__ occ_valid,
-                                                                                           uint8_t *__restrict__ stack_flags, const uint8_t *__restrict__ mask,
-                                                                                           uint32_t *__restrict__ fc_epoch)
-{
-    if (!key_matches(key, snap, status)) return;
-    snapshot_block<true, WHERE>(tab, N, capacity, count, item_chunks, nullptr, d_recs, n_recs, status, const_cast<uint8_t *>(snap), frame_clean, occ_valid,
-                                stack_flags, mask, fc_epoch);
+    snapshot_block<true>(tab, N, capacity, count, item_chunks, d_envs, d_recs, n_recs, status, const_cast<uint8_t *>(snap), frame_clean, occ_valid,
+                         stack_flags, mask, fc_epoch);
 }

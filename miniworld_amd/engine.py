@@ -256,6 +256,11 @@ def _stream_ptr(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _ptr(t):
+    """The device pointer of a tensor for the C ABI; None stays null."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 class Engine:
     """One mw_engine: N environments resident on one GPU."""
 
@@ -399,9 +404,8 @@ class Engine:
         contiguous int32 tensor on the device if it is not one already (torch.randint / argmax / Categorical.sample
         give int64; a column of a [N, T] tensor is strided); the output tensors are checked, never converted."""
         actions = self._step_tensors(actions, obs, depth, reward, term, trunc)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_step(self.h, ptr(actions), ptr(obs), ptr(depth), ptr(reward), ptr(term),
-                                     ptr(trunc), _stream_ptr(self.device)), "mw_step")
+        self._check(self.lib.mw_step(self.h, _ptr(actions), _ptr(obs), _ptr(depth), _ptr(reward), _ptr(term),
+                                     _ptr(trunc), _stream_ptr(self.device)), "mw_step")
 
     def step_repeat(self, actions, repeat, obs, depth=None, reward=None, term=None, trunc=None, nsteps=None):
         """Action repeat (include/mwengine.h: mw_step_repeat): every env takes up to `repeat` steps with its action, stops at
@@ -412,9 +416,8 @@ class Engine:
             raise EngineError(f"repeat: need an integer in 1 .. {MAX_REPEAT}, got {repeat!r}")
         actions = self._step_tensors(actions, obs, depth, reward, term, trunc)
         self._dev_tensor(nsteps, "nsteps", torch.int32, self.N)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_step_repeat(self.h, ptr(actions), int(repeat), ptr(obs), ptr(depth), ptr(reward), ptr(term),
-                                            ptr(trunc), ptr(nsteps), _stream_ptr(self.device)), "mw_step_repeat")
+        self._check(self.lib.mw_step_repeat(self.h, _ptr(actions), int(repeat), _ptr(obs), _ptr(depth), _ptr(reward), _ptr(term),
+                                            _ptr(trunc), _ptr(nsteps), _stream_ptr(self.device)), "mw_step_repeat")
 
     def step_plan(self, plans, obs, depth=None, reward=None, step_reward=None, term=None, trunc=None, nsteps=None):
         """Open-loop rollout (include/mwengine.h: mw_step_plan): `plans` is an integer tensor [T, N], env i takes plans[0, i],
@@ -435,9 +438,8 @@ class Engine:
         if step_reward is not None and (step_reward.device != self.device or step_reward.dtype != torch.float32 or
                                         not step_reward.is_contiguous() or step_reward.numel() < horizon * self.N):
             raise EngineError(f"step_reward: need a contiguous float32 tensor of at least {horizon * self.N} elements on {self.device}")
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_step_plan(self.h, ptr(plans), horizon, ptr(obs), ptr(depth), ptr(reward), ptr(step_reward), ptr(term),
-                                          ptr(trunc), ptr(nsteps), _stream_ptr(self.device)), "mw_step_plan")
+        self._check(self.lib.mw_step_plan(self.h, _ptr(plans), horizon, _ptr(obs), _ptr(depth), _ptr(reward), _ptr(step_reward), _ptr(term),
+                                          _ptr(trunc), _ptr(nsteps), _stream_ptr(self.device)), "mw_step_plan")
 
     def set_final_obs(self, obs=None, depth=None):
         """Same-step auto-reset: every later step writes the terminal frame (and depth) of each env whose episode ended in it into
@@ -448,8 +450,7 @@ class Engine:
             obs_numel = self.N * self.H * self.W * (1 if self.obs_layout == OBS_GREY_F64 else 3)
             self._dev_tensor(obs, "final obs", torch.float64 if self.obs_layout == OBS_GREY_F64 else torch.uint8, obs_numel)
             self._dev_tensor(depth, "final depth", torch.float32, self.N * self.H * self.W)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_set_final_obs(self.h, ptr(obs), ptr(depth if obs is not None else None)), "mw_set_final_obs")
+        self._check(self.lib.mw_set_final_obs(self.h, _ptr(obs), _ptr(depth if obs is not None else None)), "mw_set_final_obs")
         self._final_bufs = (obs, depth) if obs is not None else None
 
     def set_frame_stack(self, depth: int, pad: int = STACK_PAD_RESET, ring=None, final_stack=None):
@@ -465,14 +466,13 @@ class Engine:
             self._dev_tensor(final_stack, "final stack", dtype, self.N * depth * per_frame)
         else:
             depth, ring, final_stack = 0, None, None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_set_frame_stack(self.h, int(depth), int(pad), ptr(ring), ptr(final_stack)), "mw_set_frame_stack")
+        self._check(self.lib.mw_set_frame_stack(self.h, int(depth), int(pad), _ptr(ring), _ptr(final_stack)), "mw_set_frame_stack")
         self._stack_bufs = (ring, final_stack) if depth else None
 
     def stack_refresh(self, obs):
         """The reset path of the frame stack: after reset(mask) and render(obs), rebuilds the stacks of the envs that were reset (or
         never pushed) from their rows of `obs`; the others and the ring position stay (mw_stack_refresh)."""
-        self._check(self.lib.mw_stack_refresh(self.h, C.c_void_p(obs.data_ptr()), _stream_ptr(self.device)), "mw_stack_refresh")
+        self._check(self.lib.mw_stack_refresh(self.h, _ptr(obs), _stream_ptr(self.device)), "mw_stack_refresh")
 
     def stack_window(self):
         """(first_slot, pushes): every env's ordered stack is ring[:, first_slot : first_slot + depth]; host values, no sync."""
@@ -507,30 +507,33 @@ class Engine:
             raise EngineError(f"snapshot buffer: need a contiguous uint8 tensor of at least {need} bytes on {self.device} for {capacity} records, got "
                               f"{buf.dtype} {tuple(buf.shape)} on {buf.device}")
 
+    def _items(self, envs, records, count, default):
+        """The index tensors and the item count of a list call: envs / records None or made int32 device tensors (_index_tensor), count
+        the length of whichever is given, else `default`; every array given must be that long."""
+        envs, records = self._index_tensor(envs, "envs"), self._index_tensor(records, "records")
+        if count is None:
+            count = envs.numel() if envs is not None else records.numel() if records is not None else default
+        for t, name in ((envs, "envs"), (records, "records")):
+            if t is not None and t.numel() != count:
+                raise EngineError(f"{name}: {t.numel()} indices for {count} items")
+        return envs, records, int(count)
+
     def snapshot_save(self, buf, capacity: int, envs=None, count: int | None = None):
         """Record k of `buf` := the complete state of env envs[k] (envs=None: env k, for k < count, default all envs); `buf` is a
         uint8 device tensor of snapshot_bytes(capacity) bytes.  Asynchronous on the current stream, one kernel; returns the number
         of records written (mw_snapshot_save)."""
-        envs = self._index_tensor(envs, "envs")
-        count = (self.N if envs is None else envs.numel()) if count is None else int(count)
+        envs, _, count = self._items(envs, None, count, self.N)
         self._snapshot_buffer(buf, capacity)
-        self._check(self.lib.mw_snapshot_save(self.h, None if envs is None else C.c_void_p(envs.data_ptr()), count, C.c_void_p(buf.data_ptr()),
-                                              int(capacity), _stream_ptr(self.device)), "mw_snapshot_save")
+        self._check(self.lib.mw_snapshot_save(self.h, _ptr(envs), count, _ptr(buf), int(capacity), _stream_ptr(self.device)), "mw_snapshot_save")
         return count
 
     def snapshot_load(self, buf, n_recs: int, capacity: int, envs=None, records=None, count: int | None = None):
         """Env envs[k] := record records[k] of `buf`, whose first n_recs records are valid (envs=None: env k; records=None: record
         k).  The target envs must be distinct; records may repeat — a fork.  The observation buffers are stale afterwards: render(),
         then stack_refresh() with a frame stack (mw_snapshot_load).  Asynchronous on the current stream, one kernel."""
-        envs, records = self._index_tensor(envs, "envs"), self._index_tensor(records, "records")
-        if count is None:
-            count = envs.numel() if envs is not None else records.numel() if records is not None else min(int(n_recs), self.N)
-        for t, name in ((envs, "envs"), (records, "records")):
-            if t is not None and t.numel() != count:
-                raise EngineError(f"{name}: {t.numel()} indices for {count} items")
+        envs, records, count = self._items(envs, records, count, min(int(n_recs), self.N))
         self._snapshot_buffer(buf, capacity)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_snapshot_load(self.h, ptr(envs), ptr(records), int(count), C.c_void_p(buf.data_ptr()), int(n_recs), int(capacity),
+        self._check(self.lib.mw_snapshot_load(self.h, _ptr(envs), _ptr(records), count, _ptr(buf), int(n_recs), int(capacity),
                                               _stream_ptr(self.device)), "mw_snapshot_load")
 
     def snapshot_frames_bytes(self, capacity: int, flags: int = 0) -> int:
@@ -565,12 +568,10 @@ class Engine:
         frames and stack flag (envs=None: env k, for k < count, default all envs); `buf` is a uint8 device tensor of
         snapshot_frames_bytes(capacity, flags) bytes that overlaps none of them.  Asynchronous on the current stream, one kernel;
         returns the number of records written (mw_snapshot_save_frames)."""
-        envs = self._index_tensor(envs, "envs")
-        count = (self.N if envs is None else envs.numel()) if count is None else int(count)
+        envs, _, count = self._items(envs, None, count, self.N)
         self._frames_buffer(buf, capacity, flags)
         self._frame_rows(obs, depth, flags)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_snapshot_save_frames(self.h, ptr(envs), count, ptr(obs), ptr(depth), C.c_void_p(buf.data_ptr()), int(capacity),
+        self._check(self.lib.mw_snapshot_save_frames(self.h, _ptr(envs), count, _ptr(obs), _ptr(depth), _ptr(buf), int(capacity),
                                                      int(flags), _stream_ptr(self.device)), "mw_snapshot_save_frames")
         return count
 
@@ -580,49 +581,31 @@ class Engine:
         `buf`, saved under the same `flags`.  Called behind snapshot_load() with the same indices it replaces render() and
         stack_refresh(): the frames are the ones the records' sources returned.  Asynchronous on the current stream, one kernel
         (mw_snapshot_load_frames)."""
-        envs, records = self._index_tensor(envs, "envs"), self._index_tensor(records, "records")
-        if count is None:
-            count = envs.numel() if envs is not None else records.numel() if records is not None else min(int(n_recs), self.N)
-        for t, name in ((envs, "envs"), (records, "records")):
-            if t is not None and t.numel() != count:
-                raise EngineError(f"{name}: {t.numel()} indices for {count} items")
+        envs, records, count = self._items(envs, records, count, min(int(n_recs), self.N))
         self._frames_buffer(buf, capacity, flags)
         self._frame_rows(obs, depth, flags)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_snapshot_load_frames(self.h, ptr(envs), ptr(records), int(count), C.c_void_p(buf.data_ptr()), int(n_recs),
-                                                     int(capacity), int(flags), ptr(obs), ptr(depth), _stream_ptr(self.device)),
+        self._check(self.lib.mw_snapshot_load_frames(self.h, _ptr(envs), _ptr(records), count, _ptr(buf), int(n_recs),
+                                                     int(capacity), int(flags), _ptr(obs), _ptr(depth), _stream_ptr(self.device)),
                     "mw_snapshot_load_frames")
-
-    def _at_items(self, envs, records, count):
-        """The index tensors and the item count of a save into chosen records."""
-        envs, records = self._index_tensor(envs, "envs"), self._index_tensor(records, "records")
-        if count is None:
-            count = envs.numel() if envs is not None else records.numel() if records is not None else self.N
-        for t, name in ((envs, "envs"), (records, "records")):
-            if t is not None and t.numel() != count:
-                raise EngineError(f"{name}: {t.numel()} indices for {count} items")
-        return envs, records, int(count)
 
     def snapshot_save_at(self, buf, capacity: int, envs=None, records=None, count: int | None = None):
         """Record records[k] of `buf` := the complete state of env envs[k] (envs=None: env k; records=None: record k).  The records
         named must be distinct; every other record of `buf` keeps what it held, so a bank of more records than the engine has envs
         is filled in chunks and a running loop adds to it.  Asynchronous on the current stream, one kernel; returns the number of
         records written (mw_snapshot_save_at)."""
-        envs, records, count = self._at_items(envs, records, count)
+        envs, records, count = self._items(envs, records, count, self.N)
         self._snapshot_buffer(buf, capacity)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_snapshot_save_at(self.h, ptr(envs), ptr(records), count, C.c_void_p(buf.data_ptr()), int(capacity),
-                                                 _stream_ptr(self.device)), "mw_snapshot_save_at")
+        self._check(self.lib.mw_snapshot_save_at(self.h, _ptr(envs), _ptr(records), count, _ptr(buf), int(capacity), _stream_ptr(self.device)),
+                    "mw_snapshot_save_at")
         return count
 
     def snapshot_save_frames_at(self, buf, capacity: int, obs, depth=None, flags: int = 0, envs=None, records=None, count: int | None = None):
         """Frame record records[k] of `buf` := env envs[k]'s frames, as snapshot_save_frames() takes them; the other records keep
         what they held (mw_snapshot_save_frames_at).  Asynchronous on the current stream, one kernel; returns the number written."""
-        envs, records, count = self._at_items(envs, records, count)
+        envs, records, count = self._items(envs, records, count, self.N)
         self._frames_buffer(buf, capacity, flags)
         self._frame_rows(obs, depth, flags)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_snapshot_save_frames_at(self.h, ptr(envs), ptr(records), count, ptr(obs), ptr(depth), C.c_void_p(buf.data_ptr()),
+        self._check(self.lib.mw_snapshot_save_frames_at(self.h, _ptr(envs), _ptr(records), count, _ptr(obs), _ptr(depth), _ptr(buf),
                                                         int(capacity), int(flags), _stream_ptr(self.device)), "mw_snapshot_save_frames_at")
         return count
 
@@ -643,8 +626,8 @@ class Engine:
         if records is None:
             raise EngineError("records: None (record i for env i: snapshot_load)")
         self._snapshot_buffer(buf, capacity)
-        self._check(self.lib.mw_snapshot_load_where(self.h, C.c_void_p(mask.data_ptr()), C.c_void_p(records.data_ptr()), C.c_void_p(buf.data_ptr()),
-                                                    int(n_recs), int(capacity), _stream_ptr(self.device)), "mw_snapshot_load_where")
+        self._check(self.lib.mw_snapshot_load_where(self.h, _ptr(mask), _ptr(records), _ptr(buf), int(n_recs), int(capacity),
+                                                    _stream_ptr(self.device)), "mw_snapshot_load_where")
 
     def snapshot_load_frames_where(self, buf, n_recs: int, capacity: int, mask, records, obs, depth=None, flags: int = 0):
         """For every env i with mask[i] != 0: env i's rows of `obs` / `depth` (and with SNAPF_STACK its frame stack and stack flag) :=
@@ -655,18 +638,15 @@ class Engine:
             raise EngineError("records: None (record i for env i: snapshot_load_frames)")
         self._frames_buffer(buf, capacity, flags)
         self._frame_rows(obs, depth, flags)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_snapshot_load_frames_where(self.h, ptr(mask), ptr(records), C.c_void_p(buf.data_ptr()), int(n_recs), int(capacity),
-                                                           int(flags), ptr(obs), ptr(depth), _stream_ptr(self.device)),
+        self._check(self.lib.mw_snapshot_load_frames_where(self.h, _ptr(mask), _ptr(records), _ptr(buf), int(n_recs), int(capacity),
+                                                           int(flags), _ptr(obs), _ptr(depth), _stream_ptr(self.device)),
                     "mw_snapshot_load_frames_where")
 
     def render(self, obs, depth=None):
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_render(self.h, ptr(obs), ptr(depth), _stream_ptr(self.device)), "mw_render")
+        self._check(self.lib.mw_render(self.h, _ptr(obs), _ptr(depth), _stream_ptr(self.device)), "mw_render")
 
     def render_top(self, obs, depth=None, render_agent=True):
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.mw_render_top(self.h, ptr(obs), ptr(depth), int(render_agent), _stream_ptr(self.device)), "mw_render_top")
+        self._check(self.lib.mw_render_top(self.h, _ptr(obs), _ptr(depth), int(render_agent), _stream_ptr(self.device)), "mw_render_top")
 
     def render_view(self, env: int, width: int, height: int, msaa: int = 16, top: bool = False,
                     render_agent: bool = False, want_depth: bool = False):
@@ -675,8 +655,7 @@ class Engine:
         out = torch.zeros((height, width, 3), dtype=torch.uint8, device=self.device)
         dep = torch.zeros((height, width, 1), dtype=torch.float32, device=self.device) if want_depth else None
         flags = (1 if top else 0) | (2 if render_agent else 0)
-        self._check(self.lib.mw_render_view(self.h, env, flags, width, height, msaa, C.c_void_p(out.data_ptr()),
-                                            None if dep is None else C.c_void_p(dep.data_ptr()), _stream_ptr(self.device)),
+        self._check(self.lib.mw_render_view(self.h, env, flags, width, height, msaa, _ptr(out), _ptr(dep), _stream_ptr(self.device)),
                     "mw_render_view")
         return (out, dep) if want_depth else out
 
@@ -701,42 +680,45 @@ class Engine:
         import torch
         count = self.N - first_env if count is None else count
         vis = torch.zeros((count, self.E), dtype=torch.uint8, device=self.device)
-        self._check(self.lib.mw_visible_ents(self.h, first_env, count, C.c_void_p(vis.data_ptr()), _stream_ptr(self.device)),
+        self._check(self.lib.mw_visible_ents(self.h, first_env, count, _ptr(vis), _stream_ptr(self.device)),
                     "mw_visible_ents")
         return vis
 
     def check(self):
         self._check(self.lib.mw_check(self.h, _stream_ptr(self.device)), "mw_check")
 
+    def _info_tensors(self, health, pos):
+        """what get_info and get_final_info ask of their outputs: int32[N] and float64[N, 3] device tensors, either may be None"""
+        import torch
+        for t, dt, shape in ((health, torch.int32, (self.N,)), (pos, torch.float64, (self.N, 3))):
+            if t is not None:
+                assert t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()
+
     def get_info(self, health=None, ent_pos=None, ent_slot=0):
         """Fills the caller's device tensors: health int32[N] (CollectHealth's info["health"]) and / or ent_pos float64[N, 3]
         (position of entity slot ent_slot: TMaze / YMaze info["goal_pos"])."""
-        import torch
-        for t, dt, shape in ((health, torch.int32, (self.N,)), (ent_pos, torch.float64, (self.N, 3))):
-            if t is not None:
-                assert t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()
-        self._check(self.lib.mw_get_info(self.h, health.data_ptr() if health is not None else None,
-                                         ent_pos.data_ptr() if ent_pos is not None else None, int(ent_slot), _stream_ptr(self.device)), "mw_get_info")
+        self._info_tensors(health, ent_pos)
+        self._check(self.lib.mw_get_info(self.h, _ptr(health), _ptr(ent_pos), int(ent_slot), _stream_ptr(self.device)), "mw_get_info")
 
     def get_final_info(self, health=None, goal_pos=None):
         """The `info` values of each env's last FINISHED episode (kept by the step kernel before the same-step auto-reset): health
         int32[N] (CollectHealth) and / or goal_pos float64[N, 3] (TMaze / YMaze)."""
-        import torch
-        for t, dt, shape in ((health, torch.int32, (self.N,)), (goal_pos, torch.float64, (self.N, 3))):
-            if t is not None:
-                assert t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()
-        self._check(self.lib.mw_get_final_info(self.h, health.data_ptr() if health is not None else None,
-                                               goal_pos.data_ptr() if goal_pos is not None else None, _stream_ptr(self.device)), "mw_get_final_info")
+        self._info_tensors(health, goal_pos)
+        self._check(self.lib.mw_get_final_info(self.h, _ptr(health), _ptr(goal_pos), _stream_ptr(self.device)), "mw_get_final_info")
 
-    def get_reset_pending(self, out=None):
-        """uint8[N] on the device: 1 = the env's last step ended its episode and, under AUTORESET_NEXT_STEP, its next step installs
-        the next world instead of stepping (the action is ignored; reward 0, flags 0).  Written into `out` when given."""
+    def _get_bytes(self, fn, out):
+        """a uint8[N] getter of the library into `out`, made here when None"""
         import torch
         if out is None:
             out = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
         assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (self.N,) and out.is_contiguous()
-        self._check(self.lib.mw_get_reset_pending(self.h, out.data_ptr(), _stream_ptr(self.device)), "mw_get_reset_pending")
+        self._check(getattr(self.lib, fn)(self.h, _ptr(out), _stream_ptr(self.device)), fn)
         return out
+
+    def get_reset_pending(self, out=None):
+        """uint8[N] on the device: 1 = the env's last step ended its episode and, under AUTORESET_NEXT_STEP, its next step installs
+        the next world instead of stepping (the action is ignored; reward 0, flags 0).  Written into `out` when given."""
+        return self._get_bytes("mw_get_reset_pending", out)
 
     def set_frame_reuse(self, on: bool):
         """Lets step() leave the rows of envs whose frame did not change undrawn (include/mwengine.h: mw_set_frame_reuse).  With
@@ -760,22 +742,12 @@ class Engine:
     def get_frame_source(self, out=None):
         """uint8[N] on the device: where each env's frame of the last plain step came from — 0 drawn, 1 left alone as clean (frame
         reuse), 2 + j copied from slot j of the frame cache.  Written into `out` when given."""
-        import torch
-        if out is None:
-            out = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
-        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (self.N,) and out.is_contiguous()
-        self._check(self.lib.mw_get_frame_source(self.h, out.data_ptr(), _stream_ptr(self.device)), "mw_get_frame_source")
-        return out
+        return self._get_bytes("mw_get_frame_source", out)
 
     def get_frame_clean(self, out=None):
         """uint8[N] on the device: 1 = the env's frame after the last step is bit for bit the frame before it (a blocked move, a
         pickup that found nothing ...), whether or not reuse is on.  Written into `out` when given."""
-        import torch
-        if out is None:
-            out = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
-        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (self.N,) and out.is_contiguous()
-        self._check(self.lib.mw_get_frame_clean(self.h, out.data_ptr(), _stream_ptr(self.device)), "mw_get_frame_clean")
-        return out
+        return self._get_bytes("mw_get_frame_clean", out)
 
     def list_lengths(self):
         """int32[N]: triangles in each env's display list of the last frame (after clipping and culling)."""

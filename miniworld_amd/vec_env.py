@@ -395,10 +395,7 @@ class MiniWorldVecEnv:
         seeds = np.arange(self.num_envs, dtype=np.uint64) + np.uint64(self._next_seed)
         self._next_seed += self.num_envs
         self.engine.reset(None, seeds)
-        self.engine.render(self.obs, self.depth)
-        if self.frame_stack:
-            self.engine.stack_refresh(self.obs)
-        return self.obs
+        return self._redraw()
 
     @property
     def stack(self):
@@ -491,9 +488,7 @@ class MiniWorldVecEnv:
             mask, full = np.zeros(N, np.uint8), np.zeros(N, np.uint64)
             mask[:m], full[:m] = 1, seeds_np[base:base + m]
             self.engine.reset(mask, full)
-            self.engine.render(self.obs, self.depth)
-            if self.frame_stack:
-                self.engine.stack_refresh(self.obs)
+            self._redraw()
             recs = torch.arange(base, base + m, dtype=torch.int32, device=dev)     # (envs None: env k is item k, k < m)
             self.engine.snapshot_save_at(data, L, None, recs)
             self.engine.snapshot_save_frames_at(fdata, L, self.obs, self.depth, flags, None, recs)
@@ -560,11 +555,16 @@ class MiniWorldVecEnv:
             torch.where(done if now.dim() == 1 else done[:, None], now, self._final_info_buf, out=self._final_info_buf)
         self._start_levels(self._done, frames)
 
+    def _new_info_buffer(self):
+        """what get_info / get_final_info fill for this env's `info` key: health int32[N], goal_pos float64[N, 3]"""
+        torch, dev = self.torch, self.engine.device
+        if self._info_kind == "health":
+            return torch.zeros(self.num_envs, dtype=torch.int32, device=dev)
+        return torch.zeros((self.num_envs, 3), dtype=torch.float64, device=dev)
+
     def _level_final_info(self):
         if self._final_info_buf is None:
-            dev = self.engine.device
-            self._final_info_buf = (self.torch.zeros(self.num_envs, dtype=self.torch.int32, device=dev) if self._info_kind == "health"
-                                    else self.torch.zeros((self.num_envs, 3), dtype=self.torch.float64, device=dev))
+            self._final_info_buf = self._new_info_buffer()
         return self._final_info_buf
 
     # ------------------------------------------------------------------ save / restore / fork
@@ -645,11 +645,7 @@ class MiniWorldVecEnv:
         if frames is None:
             frames = snap.frames is not None
         if frames:
-            if snap.frames is None:
-                raise ValueError("load_state(frames=True): the snapshot holds no frame records (save_state(frames=True))")
-            if snap.frame_flags != self._frame_flags() or snap.frame_stack != (self.frame_stack or 0):
-                raise ValueError(f"load_state: the snapshot's frame records (flags {snap.frame_flags}, frame_stack {snap.frame_stack}) are not this "
-                                 f"env's (flags {self._frame_flags()}, frame_stack {self.frame_stack or 0}: want_depth / frame_stack differ)")
+            self._check_frame_config(snap, "load_state")
         data = snap.data
         if data.device != self.engine.device:
             data = data.to(self.engine.device)
@@ -705,11 +701,8 @@ class MiniWorldVecEnv:
         episode's own values: final_infos —; with the next-step auto-reset it reports the finished one)."""
         if self._info_kind is None:
             return {}
-        torch = self.torch
         if self._info_buf is None:
-            dev = self.engine.device
-            self._info_buf = (torch.zeros(self.num_envs, dtype=torch.int32, device=dev) if self._info_kind == "health"
-                              else torch.zeros((self.num_envs, 3), dtype=torch.float64, device=dev))
+            self._info_buf = self._new_info_buffer()
         if self._info_kind == "health":
             self.engine.get_info(health=self._info_buf)
         else:
@@ -724,11 +717,8 @@ class MiniWorldVecEnv:
             return {}
         if self.autoreset_mode == "levels":     # (kept by step() itself before the level loads; the engine installs nothing here)
             return {self._info_kind: self._level_final_info()}
-        torch = self.torch
         if self._final_info_buf is None:
-            dev = self.engine.device
-            self._final_info_buf = (torch.zeros(self.num_envs, dtype=torch.int32, device=dev) if self._info_kind == "health"
-                                    else torch.zeros((self.num_envs, 3), dtype=torch.float64, device=dev))
+            self._final_info_buf = self._new_info_buffer()
         if self._info_kind == "health":
             self.engine.get_final_info(health=self._final_info_buf)
         else:

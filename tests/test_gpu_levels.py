@@ -195,6 +195,32 @@ def test_a_bank_is_filled_in_chunks_through_chosen_records(name, monkeypatch):
         v.close()
 
 
+@pytest.mark.parametrize("env_id, n, kw", [(HALLWAY, 70, dict(obs_width=81, obs_height=61, want_depth=True, frame_stack=2)), (MAZE, 3, dict(want_depth=True))],
+                         ids=["hallway-81x61-depth-stack2", "maze"])
+def test_a_save_at_without_records_is_the_plain_save(env_id, n, kw):
+    """records=None names record k for item k: snapshot_save_at(buf, cap, envs, None) and snapshot_save(buf, cap, envs) into zeroed
+    buffers of more records than items leave the same bytes, and so does the frames pair.  One kernel serves both calls and reads the
+    rule from its arguments, so a null record list must stay what the plain save has always meant."""
+    import torch
+    seed = 5250
+    rng = np.random.default_rng(seed)
+    V = _make(env_id, n, seed, **kw)
+    V.reset()
+    for act in _actions(rng, 3, n, 3, 0.5):
+        _step(V, act)
+    e, flags, cap = V.engine, V._frame_flags(), n + 2
+    envs = _dev(rng.permutation(n)[:max(2, n - 1)], torch.int32)
+    at, plain = (torch.zeros(e.snapshot_bytes(cap), dtype=torch.uint8, device="cuda") for _ in range(2))
+    fat, fplain = (torch.zeros(e.snapshot_frames_bytes(cap, flags), dtype=torch.uint8, device="cuda") for _ in range(2))
+    assert e.snapshot_save_at(at, cap, envs, None) == e.snapshot_save(plain, cap, envs) == envs.numel()
+    assert e.snapshot_save_frames_at(fat, cap, V.obs, V.depth, flags, envs, None) == e.snapshot_save_frames(fplain, cap, V.obs, V.depth, flags, envs)
+    e.check()
+    assert _np(plain).any() and _np(fplain).any()
+    assert np.array_equal(_np(at), _np(plain)), "state records"
+    assert np.array_equal(_np(fat), _np(fplain)), "frame records"
+    V.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------- 3. a level is a reset
 
 @pytest.mark.parametrize("name", ["hallway", "maze", "pickup-dr", "collecthealth"])

@@ -2,7 +2,7 @@
 """Compares the kernels' resource usage of two builds of the library.
 
 Each argument is the log of `make EXTRA=-Rpass-analysis=kernel-resource-usage` (a clean build, stderr included) in
-miniworld_amd/csrc: the parent commit's first, this tree's second.  Prints one line per kernel — VGPRs, AGPRs, scratch bytes
+miniworld_amd/csrc: the parent commit's first, this tree's second.  Prints one line per kernel — VGPRs, AGPRs, SGPRs, scratch bytes
 per lane, occupancy (waves per SIMD), static LDS — for both builds, the kernels only this tree has, and the number of kernels
 that differ; exit status 1 if any kernel of the parent differs or is missing.
 
@@ -11,7 +11,7 @@ that differ; exit status 1 if any kernel of the parent differs or is missing.
 import re
 import sys
 
-KEYS = (("VGPR", "VGPRs"), ("AGPR", "AGPRs"), ("scratch", r"ScratchSize \[bytes/lane\]"), ("occupancy", r"Occupancy \[waves/SIMD\]"),
+KEYS = (("VGPR", "VGPRs"), ("AGPR", "AGPRs"), ("SGPR", "TotalSGPRs"), ("scratch", r"ScratchSize \[bytes/lane\]"), ("occupancy", r"Occupancy \[waves/SIMD\]"),
         ("LDS", r"LDS Size \[bytes/block\]"))
 
 
@@ -40,7 +40,7 @@ def main():
     differ = [k for k in parent if parent[k] != this.get(k)]
     new = [k for k in this if k not in parent]
     print(f"# -Rpass-analysis=kernel-resource-usage of the library's kernels, parent commit and this tree: {len(parent)} kernels in the")
-    print(f"# parent, {len(this)} here; VGPRs, AGPRs, scratch bytes per lane, occupancy (waves per SIMD) and static LDS.")
+    print(f"# parent, {len(this)} here; VGPRs, AGPRs, SGPRs, scratch bytes per lane, occupancy (waves per SIMD) and static LDS.")
     print("# kernel | parent | this tree")
     for k in parent:
         print(f"{k} | {fmt(parent[k])} | {fmt(this[k]) if k in this else 'missing'}")
