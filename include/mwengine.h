@@ -302,6 +302,20 @@ int mw_get_state(mw_engine *e, int32_t first_env, int32_t count, mw_state_view *
  * With a frame stack (mw_set_frame_stack) the envs whose world it writes are marked: mw_stack_refresh or their next push rebuilds
  * their stacks (a MW_GEN_NONE engine's reset writes no world and marks nothing). */
 int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *stream);
+/* The device twin of mw_reset(mask, seeds): MiniWorldEnv.reset(seed=...) (miniworld.py:544-604) of the masked envs with both arrays
+ * ON THE DEVICE — what a loop that restarts finished envs from chosen seeds (Procgen's start_level / num_levels, seed-based level
+ * replay, evaluation on held-out seeds) calls behind a step without learning on the host which envs finished.
+ *   d_mask   uint8[N], device
+ *   d_seeds  uint64[N], device; d_seeds[i] is not read where d_mask[i] == 0
+ * Asynchronous on `stream`: no host synchronisation, no host value read, the stream array never leaves the device.  For every masked
+ * env: its stream is re-seeded on the device with the arithmetic the host seeds with (numpy's SeedSequence + PCG64 under MW_RNG_PCG64;
+ * key = seed, counter 0 under MW_RNG_PHILOX), the live world is generated directly from it (a pre-generated next world goes stale and
+ * is marked for regeneration), a pending next-step auto-reset is dropped, the env's frame-cache epoch advances and, with a frame stack,
+ * its stack flag is marked as after mw_reset.  Nothing of any other env is written: the call leaves the other envs' cached frames
+ * alone.  It does drop the held frame of frame reuse (the caller's buffers no longer show the masked envs): draw next (mw_render).
+ * MW_GEN_NONE: the masked envs are re-seeded only, as by mw_reset.
+ * MW_E_INVALID, before anything is launched: a null engine, mask or seeds; MW_GEN_PROGRAM without a program. */
+int mw_reset_where(mw_engine *e, const uint8_t *d_mask, const uint64_t *d_seeds, void *stream);
 
 /* ---- the hot path ------------------------------------------------------------ */
 /* MiniWorldEnv.step (miniworld.py:670-730) + env rule + render_obs (:1177-1221) for all envs.
@@ -386,6 +400,23 @@ int mw_step_plan(mw_engine *e, const int32_t *d_plans /* [horizon][N] */, int32_
  * MW_E_INVALID on MW_AUTORESET_OFF / MW_AUTORESET_NEXT_STEP engines and on MW_GEN_NONE engines (nothing is auto-reset there: the
  * frame mw_step returns is the terminal one). */
 int mw_set_final_obs(mw_engine *e, uint8_t *d_final_obs, float *d_final_depth);
+/* Seeded same-step auto-reset: d_next_seed is the caller's uint64[N] on the device (NULL turns it off again).  With it set, an env
+ * whose episode ends in a step starts, in that step, the episode MiniWorldEnv.reset(seed=d_next_seed[i]) starts (miniworld.py:544-604)
+ * instead of continuing on its own stream as the reference's benchmark loop does (scripts/benchmark.py:36-37): its stream is re-seeded
+ * on the device and its world generated from it.  d_next_seed[i] is read only for an env that finishes in a call, and at that call,
+ * on the call's stream: the caller may rewrite the array between calls on the same stream (a level sampler writes its choices there).
+ * Every drawn mw_step, mw_step_repeat and mw_step_plan then takes the two passes of a step with final buffers, whether or not final
+ * buffers are set: the step as the next-step mode's terminal step and the frame of every env; the finished envs' rows into the final
+ * buffers where set (the two compose); the listed envs seeded and generated; the frame of those envs alone.  What the call returns is
+ * the same-step contract: the observation returned with term | trunc is the first frame of the episode of d_next_seed[i], reward and
+ * flags are the finished episode's, mw_get_final_info reports it, mw_get_reset_pending stays zeros, one stack push rebuilds the
+ * finished envs' stacks.  The step's own draws (domain randomisation, MW_TASK_COLLECT) on the terminal step come from the old stream.
+ * A pre-generated next world is never used while seeds are set; it is regenerated from the new stream like any consumed one.  Frame
+ * reuse and the frame cache serve the first pass as they serve a plain step.  After NULL the envs continue as plain same-step
+ * auto-reset on their current streams.
+ * MW_E_INVALID on MW_AUTORESET_OFF / MW_AUTORESET_NEXT_STEP engines and on MW_GEN_NONE engines (mw_set_final_obs's rule).  While seeds
+ * are set a FRAMELESS mw_step_plan (d_obs == NULL) is MW_E_INVALID and touches nothing: the step kernel cannot seed. */
+int mw_set_reset_seeds(mw_engine *e, const uint64_t *d_next_seed /* [N], device; NULL = off */);
 /* Frame stacking on the device (Gymnasium's FrameStackObservation, SB3's VecFrameStack, EnvPool's stack_num around the reference env):
  * the engine keeps the last `depth` frames each env RETURNED — its rows of d_obs, in the layout of mw_set_obs_layout; depth maps are
  * not stacked — oldest first, in the caller's ring.

@@ -9,45 +9,12 @@
 #include <map>
 #include <vector>
 #include "mw_asset_types.h"
+#include "mw_rng.h"
 
 namespace mwasset {
-// numpy.random.SeedSequence(seed).generate_state(4, uint64) for a non-negative integer seed (the
-// published SeedSequence algorithm: 4-word pool, hashmix / mix with the constants below), then PCG64's
-// pcg_setseq_128_srandom_r — what gymnasium's np_random(seed) builds (miniworld.py:551).
-// pcg64_step: the stream's 128-bit state step (mw_rng.h: mw::pcg64_step, the one the kernels run).
-template <typename Step>
-void pcg64_seed(uint64_t seed, uint64_t out[4], Step pcg64_step)
-{
-    const uint32_t INIT_A = 0x43b0d7e5u, MULT_A = 0x931e8875u, INIT_B = 0x8b51f9ddu, MULT_B = 0x58f38dedu;
-    const uint32_t MIX_L = 0xca01f9ddu, MIX_R = 0x4973f715u;
-    uint32_t ent[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-    const int n_ent = ent[1] ? 2 : 1;
-    uint32_t hc = INIT_A;
-    auto hashmix = [&](uint32_t v) { v ^= hc; hc *= MULT_A; v *= hc; v ^= v >> 16; return v; };
-    auto mix = [&](uint32_t x, uint32_t y) { uint32_t r = MIX_L * x - MIX_R * y; r ^= r >> 16; return r; };
-    uint32_t pool[4];
-    for (int i = 0; i < 4; ++i) pool[i] = hashmix(i < n_ent ? ent[i] : 0u);
-    for (int s = 0; s < 4; ++s)
-        for (int d = 0; d < 4; ++d)
-            if (s != d) pool[d] = mix(pool[d], hashmix(pool[s]));
-    uint32_t hb = INIT_B, w[8];
-    for (int i = 0; i < 8; ++i) {
-        uint32_t v = pool[i & 3];
-        v ^= hb; hb *= MULT_B; v *= hb; v ^= v >> 16;
-        w[i] = v;
-    }
-    uint64_t st[4];
-    for (int i = 0; i < 4; ++i) st[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
-    // initstate = st[0]:st[1], initseq = st[2]:st[3];  inc = (initseq << 1) | 1
-    const uint64_t inc_hi = (st[2] << 1) | (st[3] >> 63), inc_lo = (st[3] << 1) | 1ull;
-    uint64_t hi = 0, lo = 0;
-    pcg64_step(hi, lo, inc_hi, inc_lo);
-    const uint64_t sl = lo + st[1];
-    hi += st[0] + (sl < lo ? 1ull : 0ull);
-    lo = sl;
-    pcg64_step(hi, lo, inc_hi, inc_lo);
-    out[0] = hi; out[1] = lo; out[2] = inc_hi; out[3] = inc_lo;
-}
+// the seed of numpy's PCG64 stream for a non-negative integer seed: state hi, lo, increment hi, lo — the arithmetic is mw_rng.h's
+// (mw::pcg64_seed), shared with the kernels that seed on the device
+inline void pcg64_seed(uint64_t seed, uint64_t out[4]) { mw::pcg64_seed(seed, out); }
 
 // Mip pyramid as glGenerateMipmap builds it on the reference's driver (llvmpipe: a GL_LINEAR blit of the previous level):
 // destination texel i of dn reads source texels i0, i1 with an 8-bit weight — 24.8 fixed-point coordinate

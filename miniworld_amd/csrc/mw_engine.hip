@@ -13,18 +13,13 @@ using namespace mwhost;
 
 namespace {
 
-// (re)seed env i in a host copy of the uint64[4][N] rng array
+// (re)seed env i in a host copy of the uint64[5][N] rng array
 void seed_env(const mw_engine *e, uint64_t *rng, int i, uint64_t seed)
 {
     const size_t N = (size_t)e->cfg.num_envs;
-    if (e->cfg.rng_mode == MW_RNG_PCG64) {
-        uint64_t s[4];
-        mwasset::pcg64_seed(seed, s, mw::pcg64_step);
-        for (int k = 0; k < 4; ++k) rng[(size_t)k * N + i] = s[k];
-        rng[4 * N + i] = 0;
-    } else {
-        rng[i] = seed; rng[N + i] = 0; rng[2 * N + i] = 0; rng[3 * N + i] = 0; rng[4 * N + i] = 0;
-    }
+    uint64_t w[5];
+    mw::rng_seed_words(e->cfg.rng_mode == MW_RNG_PCG64, seed, w);
+    for (int k = 0; k < 5; ++k) rng[(size_t)k * N + i] = w[k];
 }
 
 // One device block holds the descriptor table followed by the texels of every level: the raster kernels reach
@@ -655,11 +650,34 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
     return MW_OK;
 }
 
+int mw_reset_where(mw_engine *e, const uint8_t *d_mask, const uint64_t *d_seeds, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (!d_mask || !d_seeds) return fail(e, MW_E_INVALID, "mw_reset_where: %s is null", d_mask ? "d_seeds" : "d_mask");
+    if (e->cfg.generator == MW_GEN_PROGRAM && !e->args.prog) return fail(e, MW_E_INVALID, "MW_GEN_PROGRAM: no placement program installed (mw_set_gen_program)");
+    ON_DEVICE(e);
+    const int N = e->cfg.num_envs;
+    hipStream_t st = (hipStream_t)stream;
+    if (const int rc = refill_order(e, st)) return rc;
+    // the caller's buffers no longer show the masked envs; the other envs keep their cached frames (the kernel advances the epochs of the
+    // envs it writes)
+    invalidate(e, reset_where_invalidation());
+    const bool pcg = e->cfg.rng_mode == MW_RNG_PCG64;
+    const dim3 grid(e->cfg.generator == MW_GEN_MAZE ? N : (N + 63) / 64);
+    // spare mode: the live world comes directly from the fresh stream and the env's spare is marked stale (mw_reset's seeded path); the
+    // refill blocks of the next step, or its side-stream refill, regenerate it
+    hipLaunchKernelGGL(pcg ? mw_reset_where_pcg_kernel : mw_reset_where_kernel, grid, dim3(64), 0, st, e->args, d_mask, d_seeds);
+    if (e->stack.depth && e->cfg.generator != MW_GEN_NONE)
+        hipLaunchKernelGGL(mw_stack_mark_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, d_mask, 0, stack_flags(e, e->stack.cur));
+    HIP_TRY(e, hipGetLastError());
+    return MW_OK;
+}
+
 int mw_pcg64_draws(uint64_t seed, int32_t n, const int32_t *bounds, double *out)
 {
     if (!out || n < 0) return MW_E_INVALID;
     uint64_t s[4];
-    mwasset::pcg64_seed(seed, s, mw::pcg64_step);
+    mwasset::pcg64_seed(seed, s);
     mw::Rng r{s[0], s[1], s[2], s[3], 1, 0u, 0u};
     for (int i = 0; i < n; ++i)
         out[i] = (bounds && bounds[i] > 0) ? (double)mw::rng_below(r, (uint32_t)bounds[i]) : mw::rng_double(r);

@@ -357,7 +357,7 @@ int launch_frame(mw_engine *e, const Call &c, CallKind kind, int view_flags = 0)
     const RasterPath path = raster_path_of(e, d_depth != nullptr);
     const bool held_match = e->held.valid && e->held.obs == d_obs && e->held.depth == d_depth && e->held.layout == e->obs_layout;
     const FramePolicy pol = frame_policy({kind, view_flags, e->frame_reuse, held_match, e->have_meshes, e->dbg_flags, e->obs_layout, e->cfg.task,
-                                          e->fc.slots > 0 && e->fc.frames, path.path});
+                                          e->fc.slots > 0 && e->fc.frames, path.path, e->reset_seeds != nullptr});
     frames_stale(e);
     const int N = e->cfg.num_envs;
     Frame f{e->args, view_flags, kind == CALL_LIST_PASS ? e->d_final_list : nullptr, d_obs, d_depth, st, pol, path, {}};
@@ -419,20 +419,26 @@ int launch_frame(mw_engine *e, const Call &c, CallKind kind, int view_flags = 0)
 
 extern "C" {
 
-// the frames of one call: one, or the two passes of a same-step step with final observations
-static int step_passes(mw_engine *e, const Call &c)
+// the frames of one call: one, or the two passes of a same-step step with final observations or reset seeds (mw_policy.h: step_passes_of)
+static int step_passes(mw_engine *e, const Call &c, const StepPasses &p)
 {
-    if (!e->final_obs) return launch_frame(e, c, CALL_STEP);
-    // Same-step auto-reset with final observations, in two passes.  1: the step as the next-step mode's terminal step — physics,
-    // rule, reward, flags, final info, per-step draws; the finished envs keep their terminal state — and the frame of every env.
-    // The finished envs' rows go to the final buffers.  2: they install their next world (the same install code and stream order
-    // as the plain same-step step: the step's draws, then the reset's), and the frame of those envs alone overwrites their rows.
+    if (p.shape == STEP_ONE_PASS) return launch_frame(e, c, CALL_STEP);
+    // Same-step auto-reset in two passes.  1: the step as the next-step mode's terminal step — physics, rule, reward, flags, final
+    // info, per-step draws; the finished envs keep their terminal state — and the frame of every env.  With final buffers the finished
+    // envs' rows go there.  2: they install their next world — the same install code and stream order as the plain same-step step
+    // (the step's draws, then the reset's), or with reset seeds the world of the env's seed on a stream seeded here —, and the frame
+    // of those envs alone overwrites their rows.
     const int N = e->cfg.num_envs;
+    const bool pcg = e->cfg.rng_mode == MW_RNG_PCG64;
     if (const int rc = launch_frame(e, c, CALL_TERMINAL_STEP)) return rc;
-    hipLaunchKernelGGL(mw_final_copy_kernel, dim3(N), dim3(256), 0, c.st, (const int32_t *)e->d_final_list, (const uint8_t *)c.obs, e->final_obs,
-                       (unsigned long long)frame_bytes_of(e), (const float *)c.depth, e->final_depth, e->cfg.obs_width * e->cfg.obs_height);
-    hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_final_install_pcg_kernel : mw_final_install_kernel, dim3(N), dim3(64), 0, c.st,
-                       e->args, (const int32_t *)e->d_final_list);
+    if (p.final_copy)
+        hipLaunchKernelGGL(mw_final_copy_kernel, dim3(N), dim3(256), 0, c.st, (const int32_t *)e->d_final_list, (const uint8_t *)c.obs, e->final_obs,
+                           (unsigned long long)frame_bytes_of(e), (const float *)c.depth, e->final_depth, e->cfg.obs_width * e->cfg.obs_height);
+    if (p.seeded_install)
+        hipLaunchKernelGGL(pcg ? mw_seed_install_pcg_kernel : mw_seed_install_kernel, dim3(N), dim3(64), 0, c.st, e->args, (const int32_t *)e->d_final_list,
+                           e->reset_seeds);
+    else
+        hipLaunchKernelGGL(pcg ? mw_final_install_pcg_kernel : mw_final_install_kernel, dim3(N), dim3(64), 0, c.st, e->args, (const int32_t *)e->d_final_list);
     return launch_frame(e, c, CALL_LIST_PASS);
 }
 
@@ -465,10 +471,13 @@ static int step_frames(mw_engine *e, const char *what, Call c)
     if (!c.actions) return fail(e, MW_E_INVALID, "%s: %s is null", what, c.horizon ? "d_plans" : "d_actions");
     if ((e->cfg.generator == MW_GEN_PROGRAM || e->cfg.task >= MW_TASK_SIDEWALK) && !e->args.prog)
         return fail(e, MW_E_INVALID, "no placement program installed (mw_set_gen_program)");
+    const StepPasses p = step_passes_of(e->reset_seeds != nullptr, e->final_obs != nullptr, c.horizon && !c.obs);
+    if (p.shape == STEP_REFUSED)
+        return fail(e, MW_E_INVALID, "%s: a frameless call while reset seeds are set (mw_set_reset_seeds): the step kernel cannot seed the finished envs", what);
     resolve_outputs(e, c);
-    if (c.horizon && !c.obs) return step_frameless(e, c);
+    if (p.shape == STEP_FRAMELESS) return step_frameless(e, c);
     if (const int rc = stack_check(e, what)) return rc;
-    const int rc = step_passes(e, c);
+    const int rc = step_passes(e, c, p);
     if (rc != MW_OK || !e->stack.depth) return rc;
     return launch_stack(e, c.obs, c.st, &c);     // the call's one push, behind its last raster kernel
 }
@@ -507,6 +516,18 @@ int mw_set_final_obs(mw_engine *e, uint8_t *d_final_obs, float *d_final_depth)
     frames_stale(e);
     e->final_obs = d_final_obs;
     e->final_depth = d_final_obs ? d_final_depth : nullptr;
+    return MW_OK;
+}
+
+int mw_set_reset_seeds(mw_engine *e, const uint64_t *d_next_seed)
+{
+    if (!e) return MW_E_INVALID;
+    if (e->cfg.autoreset != MW_AUTORESET_SAME_STEP)
+        return fail(e, MW_E_INVALID, "mw_set_reset_seeds: the seeded auto-reset exists in MW_AUTORESET_SAME_STEP only");
+    if (e->cfg.generator == MW_GEN_NONE)
+        return fail(e, MW_E_INVALID, "mw_set_reset_seeds: MW_GEN_NONE engines auto-reset nothing (there is no generator to seed)");
+    frames_stale(e);        // (the step changes its shape: trust starts with the next whole frame, as for mw_set_final_obs)
+    e->reset_seeds = d_next_seed;
     return MW_OK;
 }
 

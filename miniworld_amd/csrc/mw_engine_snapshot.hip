@@ -7,20 +7,6 @@ using namespace mwhost;
 
 namespace {
 
-// mw_snapshot_save / mw_snapshot_load touch worlds that the Maze's refill kernel may still be writing on the side stream (spares and
-// their refill_mask words, read behind the live stream).  The caller's stream waits for an event recorded behind those refills:
-// the host does not block — a fork loop stays asynchronous, which ON_DEVICE_SYNC would not be — and everything the engine enqueues
-// later on the side stream is ordered behind the caller's stream by launch_side_refill's own event.  The other refills are blocks
-// of the step kernel itself, in stream order.  So between launches refill_mask is 0 or 1 (mw_snapshot.hip).
-int snapshot_order(mw_engine *e, hipStream_t st)
-{
-    if (!e->side_refill_pending || !e->side_stream) return MW_OK;
-    if (!e->ev_refill_done) HIP_TRY(e, make_event(e->ev_refill_done));
-    HIP_TRY(e, hipEventRecord(e->ev_refill_done.get(), e->side_stream.get()));
-    HIP_TRY(e, hipStreamWaitEvent(st, e->ev_refill_done.get(), 0));
-    return MW_OK;
-}
-
 // The items of a call, as its entry point's contract names them (the kernels' rule: MW_SNAP_ITEMS, mw_kernels.h): a list of `count`
 // of them, or — mask non-null, the _where forms — every env under a device mask; count is num_envs then, and the list form's limits on it
 // do not apply: records repeat.
@@ -45,7 +31,7 @@ int snapshot_args(mw_engine *e, const char *what, const void *d_snap, const Snap
     return MW_OK;
 }
 
-// What a save and a load of state records share: the arguments checked, the engine's device, the grid of the call over its items (MW_E_INVALID past the 1-D grid limit) and the order behind the refills.
+// What a save and a load of state records share: the arguments checked, the engine's device, the grid of the call over its items (MW_E_INVALID past the 1-D grid limit) and the order behind the refills (mw_engine.h: refill_order).
 int snapshot_begin(mw_engine *e, const char *what, const void *d_snap, const SnapItems &it, int32_t n_recs, int32_t capacity, hipStream_t st, SnapshotGrid *g)
 {
     if (const int rc = snapshot_args(e, what, d_snap, it, n_recs, capacity)) return rc;
@@ -55,7 +41,7 @@ int snapshot_begin(mw_engine *e, const char *what, const void *d_snap, const Sna
     if (grid_too_large((unsigned long long)g->blocks))
         return fail(e, MW_E_INVALID, "%s: %d items need %lld workgroups, more than one launch holds: split the call", what, it.count, g->blocks);
     g->blocks = std::max<long long>(g->blocks, 1);
-    return snapshot_order(e, st);
+    return refill_order(e, st);
 }
 
 int save_states(mw_engine *e, const char *what, const SnapItems &it, uint8_t *d_snap, int32_t capacity, hipStream_t st)

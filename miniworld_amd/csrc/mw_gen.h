@@ -889,4 +889,32 @@ __device__ inline void install_next_world(const MwArgs &a, int env, int lane, un
     if (!PER_LANE) __syncthreads();
 }
 
+// The next world of an env whose episode ended, from a seed the caller chose (mw_set_reset_seeds): the env's stream becomes the
+// stream of `seed` and the live world is generated in place from it — never from the spare, which holds a world of the old stream.
+// One workgroup of ONE wavefront; lane 0 writes.  In spare mode the env's stream is owned first, under the refill_mask protocol of
+// install_next_world: a consumed spare (1) is claimed (3), so that no refill block starts on the stream; a refill that runs (2) is
+// waited for; a ready spare (0) has no refill to come.  The env ends at 1: its spare is stale, and the ordinary refill regenerates
+// it from the new stream.
+__device__ inline void install_seeded_world(const MwArgs &a, int env, int lane, unsigned char *gen_ws, uint64_t seed)
+{
+    if (a.spare) {
+        if (lane == 0) {
+            const unsigned old = atomicCAS(a.refill_mask + env, 1u, 3u);
+            if (old == 2u) while (__hip_atomic_load(a.refill_mask + env, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u) __builtin_amdgcn_s_sleep(16);
+        }
+        __syncthreads();
+        __threadfence();        // acquire: the stream a refill block advanced (released with its state) is overwritten behind the claim
+    }
+    if (lane == 0) rng_seed_store(a.rng, a.N, env, seed);
+    __threadfence_block();
+    __syncthreads();            // (the Maze generator's lanes all load the stream)
+    generate_world(*a.gen_live, env, gen_ws, lane);
+    if (a.spare) {
+        __threadfence();
+        __syncthreads();
+        if (lane == 0) atomicExch(a.refill_mask + env, 1u);
+    }
+    __syncthreads();
+}
+
 }  // namespace mw

@@ -45,6 +45,11 @@ extern "C" __global__ void mw_collect_respawn_pcg_kernel(MwArgs a);
 extern "C" __global__ void mw_final_install_kernel(MwArgs a, const int32_t *__restrict__ list);
 extern "C" __global__ void mw_final_install_pcg_kernel(MwArgs a, const int32_t *__restrict__ list);
 extern "C" __global__ void mw_take_spare_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all);
+// ... and with seeds the device holds: mw_reset_where's masked seeded reset, the seeded same-step install (mw_set_reset_seeds)
+extern "C" __global__ void mw_reset_where_kernel(MwArgs a, const uint8_t *__restrict__ mask, const uint64_t *__restrict__ seeds);
+extern "C" __global__ void mw_reset_where_pcg_kernel(MwArgs a, const uint8_t *__restrict__ mask, const uint64_t *__restrict__ seeds);
+extern "C" __global__ void mw_seed_install_kernel(MwArgs a, const int32_t *__restrict__ list, const uint64_t *__restrict__ next_seed);
+extern "C" __global__ void mw_seed_install_pcg_kernel(MwArgs a, const int32_t *__restrict__ list, const uint64_t *__restrict__ next_seed);
 
 // the geometry kernel (mw_geom.hip): small / big scenes, 8 samples per pixel compiled in or any
 #define MW_GEOM_ARGS MwArgs a, int view_flags, int S, int L, int n_env

@@ -159,6 +159,20 @@ inline ResetMode reset_mode(int generator, int autoreset)
 enum CallKind { CALL_RENDER = 0, CALL_STEP = 1, CALL_TERMINAL_STEP = 2, CALL_LIST_PASS = 3 };
 inline bool call_steps(CallKind k) { return k == CALL_STEP || k == CALL_TERMINAL_STEP; }
 
+// The passes of a step call (mw_step, mw_step_repeat, mw_step_plan) of a same-step engine.  One pass: CALL_STEP, the step kernel installs
+// the next worlds itself.  Two passes — final buffers (mw_set_final_obs), reset seeds (mw_set_reset_seeds) or both: CALL_TERMINAL_STEP,
+// with final buffers the copy of the finished envs' rows, the install of the listed envs — from their seeds where seeds are set, else the
+// step kernel's own install code —, CALL_LIST_PASS.  A frameless mw_step_plan launches the step kernel alone and ignores final buffers;
+// with seeds set it is refused: the step kernel cannot seed, and no list pass follows it.
+enum StepShape { STEP_REFUSED = -1, STEP_FRAMELESS = 0, STEP_ONE_PASS = 1, STEP_TWO_PASS = 2 };
+struct StepPasses { StepShape shape; bool final_copy, seeded_install; };
+inline StepPasses step_passes_of(bool seeds, bool final_bufs, bool frameless)
+{
+    if (frameless) return {seeds ? STEP_REFUSED : STEP_FRAMELESS, false, false};
+    if (!seeds && !final_bufs) return {STEP_ONE_PASS, false, false};
+    return {STEP_TWO_PASS, final_bufs, seeds};
+}
+
 // The frame's policy.  Frame reuse: a plain step of the whole batch into the buffers that hold the frame before it leaves the envs K1
 // marks clean undrawn.  Any other frame — the first one, a render, a top view, the passes of a final-observation step, frames with mesh
 // entities (their sample keys and fragment lists have a protocol of their own), other buffers or another layout, experiment
@@ -166,6 +180,10 @@ inline bool call_steps(CallKind k) { return k == CALL_STEP || k == CALL_TERMINAL
 // The frame cache: consulted and filled by a plain step of the whole batch through the quad kernel, in the layout it was
 // allocated for, without mesh entities or experiment flags; whose buffers the frame goes to does not matter.  Every other frame
 // neither reads nor writes it.  CollectHealth never: its respawn kernel moves entities behind K1's back (as for frame_clean).
+// With reset seeds set (mw_set_reset_seeds) EVERY step takes the two passes, so there the first pass counts as the plain step it is
+// for all but the finished envs: K1 stored frame_clean and the key of every env, the frame shows every env's state after the step,
+// a finished env's row may stay or come from the cache like any other (its terminal frame; the install advances its epoch), and the
+// list pass redraws exactly the rows whose env got a new world — afterwards the call's buffers show every env and are the held ones.
 struct FrameFacts {
     CallKind kind;
     int view_flags;
@@ -174,6 +192,7 @@ struct FrameFacts {
     int dbg_flags, layout, task;
     bool cache_allocated;           // mw_set_frame_cache: slots > 0 and their frames exist
     int path;                       // RasterPath::path
+    bool seeded = false;            // reset seeds are set: the call is a pass of a seeded step
 };
 struct FramePolicy {
     bool reuse;         // clean envs may stay undrawn
@@ -184,10 +203,11 @@ struct FramePolicy {
 inline FramePolicy frame_policy(const FrameFacts &f)
 {
     const bool plain = (f.kind == CALL_RENDER || f.kind == CALL_STEP) && f.view_flags == 0;
-    const bool plain_step = plain && f.kind == CALL_STEP, bare = !f.meshes && f.dbg_flags == 0;
+    const bool seeded_pass = f.seeded && (f.kind == CALL_TERMINAL_STEP || f.kind == CALL_LIST_PASS) && f.view_flags == 0;
+    const bool plain_step = (plain && f.kind == CALL_STEP) || (seeded_pass && f.kind == CALL_TERMINAL_STEP), bare = !f.meshes && f.dbg_flags == 0;
     const bool source = plain_step && f.path == MW_PATH_QUAD;
     return {f.frame_reuse && plain_step && bare && f.held_match, source,
-            source && f.cache_allocated && bare && f.layout == MW_OBS_HWC_U8 && f.task != MW_TASK_COLLECT, plain};
+            source && f.cache_allocated && bare && f.layout == MW_OBS_HWC_U8 && f.task != MW_TASK_COLLECT, plain || seeded_pass};
 }
 
 // The tile kernels' launch (mw_raster.hip) for a part of the frame (raster_flags).  big scenes (a visiting order exists): records
@@ -239,6 +259,8 @@ inline SnapshotGrid snapshot_where_grid(int N, int total_rows, int chunks_per_it
 // (the epoch is part of a frame's key and of no record: none of that env's cached frames can match again).
 struct LoadInvalidation { bool held, cache; };
 inline LoadInvalidation snapshot_load_invalidation(bool where) { return {true, !where}; }
+// ... and mw_reset_where, the masked seeded reset on the device: as the masked load — its kernel advances the epochs of the envs it writes
+inline LoadInvalidation reset_where_invalidation() { return snapshot_load_invalidation(true); }
 // ... and of frame records, either form: rows of d_obs are written, no state changes
 inline LoadInvalidation snapshot_load_frames_invalidation(bool /*where*/) { return {true, false}; }
 

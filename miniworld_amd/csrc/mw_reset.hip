@@ -68,6 +68,53 @@ extern "C" __global__ __launch_bounds__(64) void MW_INSTALL_KERNEL_NAME(MwArgs a
     }
 }
 
+#ifndef MW_RESET_WHERE_KERNEL_NAME
+#define MW_RESET_WHERE_KERNEL_NAME mw_reset_where_kernel
+#endif
+// mw_reset_where: mw_reset(mask, seeds) with both arrays on the device — every masked env's stream becomes the stream of its seed
+// (mw_rng.h: the host's own seeding arithmetic) and its live world is generated from it, as by mw_reset_kernel with mark_refill; the
+// grid is that kernel's.  seeds[env] is not read under a zero mask byte.  MW_GEN_NONE: the stream alone.
+extern "C" __global__ __launch_bounds__(64) void MW_RESET_WHERE_KERNEL_NAME(MwArgs a, const uint8_t *__restrict__ mask, const uint64_t *__restrict__ seeds)
+{
+    __shared__ unsigned char ws[64][MW_GEN_WS_BYTES];
+    const bool wave_per_env = a.generator == MW_GEN_MAZE;
+    const int env = wave_per_env ? (int)blockIdx.x : (int)(blockIdx.x * 64 + threadIdx.x);
+    if (env >= a.N || !mask[env]) return;
+    if (!wave_per_env || threadIdx.x == 0) mw::rng_seed_store(a.rng, a.N, env, seeds[env]);
+    if (a.generator == MW_GEN_NONE) return;
+    if (wave_per_env) {         // (the env's 64 lanes all load the stream lane 0 stored; the whole workgroup is here)
+        __threadfence_block();
+        __syncthreads();
+    }
+    mw::generate_world(*a.gen_live, env, wave_per_env ? ws[0] : ws[threadIdx.x], wave_per_env ? (int)threadIdx.x : 0);
+    if (!wave_per_env || threadIdx.x == 0) {
+        if (a.refill_mask) a.refill_mask[env] = 1u;     // spare mode: its spare is stale now
+        a.reset_pending[env] = 0;
+        a.fc_epoch[env] += 1u;
+    }
+}
+
+#ifndef MW_SEED_INSTALL_KERNEL_NAME
+#define MW_SEED_INSTALL_KERNEL_NAME mw_seed_install_kernel
+#endif
+// Same-step auto-reset from chosen seeds (mw_set_reset_seeds), between the two passes of the step in mw_final_install_kernel's place:
+// the listed envs — and no other: next_seed[env] is read for them alone — start the episode of their seed, and leave behind what that
+// kernel leaves behind.  (fc_source: the list pass draws the env's row, whatever the first pass did with it.)
+extern "C" __global__ __launch_bounds__(64) void MW_SEED_INSTALL_KERNEL_NAME(MwArgs a, const int32_t *__restrict__ list, const uint64_t *__restrict__ next_seed)
+{
+    __shared__ unsigned char gen_ws[MW_GEN_WS_BYTES];
+    if ((int)blockIdx.x >= list[0]) return;
+    const int env = list[1 + blockIdx.x], lane = (int)threadIdx.x;
+    mw::install_seeded_world(a, env, lane, gen_ws, next_seed[env]);
+    if (lane == 0) {
+        a.pending_remove[env] = -1;
+        a.reset_pending[env] = 0;
+        a.frame_clean[env] = 0;
+        a.fc_epoch[env] += 1u;
+        a.fc_source[env] = 0;
+    }
+}
+
 #if MW_RNG_KIND == 0
 // mw_reset without seeds in spare mode: the masked envs take their pre-generated world (one wavefront per env)
 extern "C" __global__ __launch_bounds__(64) void mw_take_spare_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all)

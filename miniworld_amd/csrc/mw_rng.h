@@ -5,8 +5,11 @@
 // draws from np_random.uniform, params.py:99), i.e. same distribution, different stream
 // (MW_RNG_PCG64 reproduces numpy's own stream instead, for the generators that support it).
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
+#include "mw_hd.h"
 
 namespace mw {
 
@@ -22,7 +25,7 @@ struct Rng { uint64_t a, b, c, d; int kind; uint32_t has32, buf32; };   // has32
 #ifndef MW_RNG_KIND
 #define MW_RNG_KIND 0
 #endif
-__host__ __device__ inline bool rng_is_pcg(const Rng &r)
+MW_HD bool rng_is_pcg(const Rng &r)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return MW_RNG_KIND == 1;
@@ -31,7 +34,7 @@ __host__ __device__ inline bool rng_is_pcg(const Rng &r)
 #endif
 }
 
-__host__ __device__ inline void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1)
+MW_HD void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1)
 {
     const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
     const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
@@ -43,7 +46,7 @@ __host__ __device__ inline void philox_round(uint32_t c[4], uint32_t k0, uint32_
 }
 
 // state = state * 0x2360ED051FC65DA44385DF649FCCF645 + inc  (mod 2^128)
-__host__ __device__ inline void pcg64_step(uint64_t &hi, uint64_t &lo, uint64_t inc_hi, uint64_t inc_lo)
+MW_HD void pcg64_step(uint64_t &hi, uint64_t &lo, uint64_t inc_hi, uint64_t inc_lo)
 {
     const uint64_t mh = 2549297995355413924ull, ml = 4865540595714422341ull;
     const unsigned __int128 p = (unsigned __int128)lo * ml;
@@ -54,7 +57,60 @@ __host__ __device__ inline void pcg64_step(uint64_t &hi, uint64_t &lo, uint64_t 
     hi = nh; lo = sl;
 }
 
-__host__ __device__ inline uint64_t rng_next_u64(Rng &r)
+// The seed of numpy's stream: numpy.random.SeedSequence(seed).generate_state(4, uint64) for a non-negative integer seed (the
+// published SeedSequence algorithm: 4-word pool, hashmix / mix with the constants below; a seed below 2^32 is ONE entropy word,
+// a larger one two), then PCG64's pcg_setseq_128_srandom_r — what gymnasium's np_random(seed) builds (miniworld.py:551).
+// out: state hi, lo, increment hi, lo.  The one statement of this arithmetic: the host seeds through it (mw_assets.h:
+// mwasset::pcg64_seed; mw_reset, mw_pcg64_draws) and so do the kernels that seed on the device (rng_seed_store below).
+MW_HD uint32_t seedseq_hashmix(uint32_t v, uint32_t &hc)
+{
+    v ^= hc; hc *= 0x931e8875u; v *= hc; v ^= v >> 16;
+    return v;
+}
+MW_HD uint32_t seedseq_mix(uint32_t x, uint32_t y)
+{
+    uint32_t r = 0xca01f9ddu * x - 0x4973f715u * y;
+    r ^= r >> 16;
+    return r;
+}
+MW_HD void pcg64_seed(uint64_t seed, uint64_t out[4])
+{
+    const uint32_t ent[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    const int n_ent = ent[1] ? 2 : 1;
+    uint32_t hc = 0x43b0d7e5u;
+    uint32_t pool[4];
+    for (int i = 0; i < 4; ++i) pool[i] = seedseq_hashmix(i < n_ent ? ent[i] : 0u, hc);
+    for (int s = 0; s < 4; ++s)
+        for (int d = 0; d < 4; ++d)
+            if (s != d) pool[d] = seedseq_mix(pool[d], seedseq_hashmix(pool[s], hc));
+    uint32_t hb = 0x8b51f9ddu, w[8];
+    for (int i = 0; i < 8; ++i) {
+        uint32_t v = pool[i & 3];
+        v ^= hb; hb *= 0x58f38dedu; v *= hb; v ^= v >> 16;
+        w[i] = v;
+    }
+    uint64_t st[4];
+    for (int i = 0; i < 4; ++i) st[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+    // initstate = st[0]:st[1], initseq = st[2]:st[3];  inc = (initseq << 1) | 1
+    const uint64_t inc_hi = (st[2] << 1) | (st[3] >> 63), inc_lo = (st[3] << 1) | 1ull;
+    uint64_t hi = 0, lo = 0;
+    pcg64_step(hi, lo, inc_hi, inc_lo);
+    const uint64_t sl = lo + st[1];
+    hi += st[0] + (sl < lo ? 1ull : 0ull);
+    lo = sl;
+    pcg64_step(hi, lo, inc_hi, inc_lo);
+    out[0] = hi; out[1] = lo; out[2] = inc_hi; out[3] = inc_lo;
+}
+
+// The five words an env's stream holds right after it was seeded (storage order, below).  PCG64: the state and increment above,
+// nothing buffered.  Philox: the seed as the key, draw counter 0.
+MW_HD void rng_seed_words(bool pcg, uint64_t seed, uint64_t w[5])
+{
+    w[0] = seed; w[1] = w[2] = w[3] = w[4] = 0;
+    if (pcg) pcg64_seed(seed, w);
+}
+
+MW_HD uint64_t rng_next_u64(Rng &r)
 {
     if (rng_is_pcg(r)) {    // pcg64_next64: step, then XSL-RR of the new state
         pcg64_step(r.a, r.b, r.c, r.d);
@@ -74,19 +130,19 @@ __host__ __device__ inline uint64_t rng_next_u64(Rng &r)
     return ((uint64_t)c[1] << 32) | c[0];
 }
 
-__host__ __device__ inline double rng_double(Rng &r)
+MW_HD double rng_double(Rng &r)
 {
     return (double)(rng_next_u64(r) >> 11) * (1.0 / 9007199254740992.0);
 }
 
-__host__ __device__ inline double rng_uniform(Rng &r, double lo, double hi)
+MW_HD double rng_uniform(Rng &r, double lo, double hi)
 {
     return lo + (hi - lo) * rng_double(r);
 }
 
 // numpy's pcg64_next32: a 64-bit output serves two 32-bit draws, low half first; doubles never touch
 // the buffered half
-__host__ __device__ inline uint32_t rng_next_u32(Rng &r)
+MW_HD uint32_t rng_next_u32(Rng &r)
 {
     if (r.has32) { r.has32 = 0; return r.buf32; }
     const uint64_t v = rng_next_u64(r);
@@ -97,7 +153,7 @@ __host__ __device__ inline uint32_t rng_next_u32(Rng &r)
 // uniform integer in [0, n), n >= 1.  PCG64 stream: exactly Generator.integers(0, n) / Generator.choice(n)
 // for n <= 2^32 (random_bounded_uint64 -> buffered_bounded_lemire_uint32, numpy/random/src/distributions):
 // no draw at all for n == 1.  Philox stream: one 64-bit draw, multiply-shift.
-__host__ __device__ inline uint32_t rng_below(Rng &r, uint32_t n)
+MW_HD uint32_t rng_below(Rng &r, uint32_t n)
 {
     if (rng_is_pcg(r)) {
         if (n <= 1u) return 0u;
@@ -116,6 +172,7 @@ __host__ __device__ inline uint32_t rng_below(Rng &r, uint32_t n)
     return (uint32_t)(((rng_next_u64(r) >> 32) * (uint64_t)n) >> 32);
 }
 
+#ifdef __HIPCC__
 // storage: uint64[5][N] (a, b, c, d, has32 << 32 | buf32); the kind is a property of the kernel (MW_RNG_KIND)
 __device__ inline Rng rng_load(const uint64_t *p, int N, int env)
 {
@@ -132,5 +189,14 @@ __device__ inline void rng_store(uint64_t *p, int N, int env, const Rng &r)
         p[(size_t)4 * N + env] = ((uint64_t)r.has32 << 32) | r.buf32;
     }
 }
+// env's stream := the stream of `seed`, all five words (mw_reset_where, the seeded auto-reset: what mw_reset's host seeding stores)
+__device__ inline void rng_seed_store(uint64_t *p, int N, int env, uint64_t seed)
+{
+    uint64_t w[5];
+    rng_seed_words(MW_RNG_KIND == 1, seed, w);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) p[(size_t)k * N + env] = w[k];
+}
+#endif
 
 }  // namespace mw

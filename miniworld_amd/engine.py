@@ -46,6 +46,7 @@ EXPORTS = [
     "mw_snapshot_bytes", "mw_snapshot_save", "mw_snapshot_load",
     "mw_snapshot_frames_bytes", "mw_snapshot_save_frames", "mw_snapshot_load_frames",
     "mw_snapshot_save_at", "mw_snapshot_save_frames_at", "mw_snapshot_load_where", "mw_snapshot_load_frames_where",
+    "mw_reset_where", "mw_set_reset_seeds",
 ]
 
 
@@ -187,6 +188,8 @@ def load_library():
     L.mw_set_step_params.argtypes = [vp, vp]
     L.mw_set_gen_program.argtypes = [vp, C.POINTER(MwGenProgram), vp, vp, vp, vp, i32, vp, i32]
     L.mw_reset.argtypes = [vp, vp, vp, vp]
+    L.mw_reset_where.argtypes = [vp, vp, vp, vp]
+    L.mw_set_reset_seeds.argtypes = [vp, vp]
     L.mw_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.mw_step_repeat.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mw_step_plan.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -372,6 +375,33 @@ class Engine:
         s = None if seeds is None else np.ascontiguousarray(seeds, np.uint64)
         self._check(self.lib.mw_reset(self.h, None if m is None else m.ctypes.data,
                                       None if s is None else s.ctypes.data, _stream_ptr(self.device)), "mw_reset")
+
+    def _seed_tensor(self, seeds, name):
+        """Seeds the device reads: a contiguous int64[N] tensor on the engine's device, whose bits the engine takes as uint64
+        (torch's own integer type; a non-negative int64 is the same number).  Nothing is converted or read here."""
+        import torch
+        if seeds is None:
+            raise EngineError(f"{name}: None")
+        return self._dev_tensor(seeds, name, torch.int64, self.N)
+
+    def reset_where(self, mask, seeds):
+        """reset(mask, seeds) with both arrays on the device (mw_reset_where): for every env i with mask[i] != 0 the episode of
+        env.reset(seed=seeds[i]) starts — stream re-seeded and world generated on the device, no host synchronisation, no copy of the
+        stream array.  mask uint8[N], seeds int64[N] (bits as uint64; not read under a zero mask byte), device tensors, nothing is
+        converted.  The other envs, their streams and their cached frames are untouched.  Asynchronous on the current stream; draw
+        next (render)."""
+        mask, seeds = self._mask_tensor(mask), self._seed_tensor(seeds, "seeds")
+        self._check(self.lib.mw_reset_where(self.h, _ptr(mask), _ptr(seeds), _stream_ptr(self.device)), "mw_reset_where")
+
+    def set_reset_seeds(self, next_seed=None):
+        """Seeded same-step auto-reset (mw_set_reset_seeds): with `next_seed`, an int64[N] device tensor (bits as uint64), an env whose
+        episode ends in a step starts the episode of env.reset(seed=next_seed[i]) in that step.  The engine reads next_seed[i] only
+        for an env that finishes, when it finishes: write the tensor between steps, on the stream the steps run on.  None turns it
+        off.  The engine keeps a reference to the tensor while it is in use."""
+        if next_seed is not None:
+            self._seed_tensor(next_seed, "next_seed")
+        self._check(self.lib.mw_set_reset_seeds(self.h, _ptr(next_seed)), "mw_set_reset_seeds")
+        self._reset_seeds = next_seed
 
     # -- hot path ---------------------------------------------------------------------
     def _dev_tensor(self, t, name, dtype, numel):

@@ -10,6 +10,9 @@ episode's first frame with reward 0 and no flags — the reference's own "step; 
 caller, scripts/benchmark.py:36-37), on the same random stream.  ``autoreset=False``: the caller resets.
 ``autoreset="levels"``: a finished env restarts, in the same step and without the host learning that it finished, from a
 record of a bank of levels the caller chose (``make_levels``, ``set_levels``, ``next_level``).
+``autoreset="seeds"``: the same-step auto-reset from seeds the device holds — a finished env starts, in the same step, the episode
+of ``env.reset(seed=next_seed[i])``; ``next_seed`` (int64[N] on the device) is the caller's to write between steps, ``episode_seed``
+tells which seed each env is playing.  Eight bytes per level, no bank to build, any seed.
 
 All 23 env ids are generated, ruled and auto-reset on the device, on the reference's own numpy PCG64 stream: Hallway,
 OneRoom*, Maze* and PickupObjects through their own generators, the fixed-floorplan families through placement programs
@@ -121,6 +124,14 @@ class MiniWorldVecEnv:
         masked copy kernels behind the step, no draw and no host synchronisation.  What the caller sees is the same-step
         auto-reset: the observation (and `self.stack`) returned with terminated | truncated is the first one of the env's next
         level, reward and flags are the finished episode's last.
+        "seeds" (`autoreset_mode` "seeds"): the engine's same-step auto-reset, seeded (mw_set_reset_seeds) — an env whose episode
+        ends in a step starts the episode of the reference's env.reset(seed=next_seed[i]) in that step, generated on the device.
+        `self.next_seed` and `self.episode_seed` are int64[N] device tensors (the engine reads the bits as uint64: keep them
+        non-negative).  reset(seed=s) sets episode_seed[i] = s + i and next_seed[i] = s + N + i; behind every step, on the device
+        and with no host value, episode_seed = where(done, next_seed, episode_seed) and next_seed += N where done — so left alone
+        every env walks the seeds s + i, s + N + i, s + 2 N + i, ...  THE CALLER'S WRITES TO next_seed BETWEEN STEPS WIN: the engine
+        reads next_seed[i] only when env i finishes, in that step (a level-replay sampler or a held-out evaluation writes its
+        choices there).  Composes with final_obs, frame_stack, step(repeat=...) and rollout(); rollout(render=False) is refused.
         final_obs (same-step auto-reset only): every step also writes the terminal frame of each env whose episode ended in it
         into that env's row of `self.final_obs` (and its depth into `self.final_depth` with want_depth); the other rows keep
         what they held.  Costs a second, small frame of the finished envs in every step.
@@ -149,11 +160,11 @@ class MiniWorldVecEnv:
             raise ValueError(f"stack_pad must be 'reset' or 'zero', not {stack_pad!r}")
         self.frame_stack = None if frame_stack is None else int(frame_stack)
         self.stack_pad = stack_pad
-        modes = {True: "same_step", False: "off", "same_step": "same_step", "next_step": "next_step", "levels": "levels"}
+        modes = {True: "same_step", False: "off", "same_step": "same_step", "next_step": "next_step", "levels": "levels", "seeds": "seeds"}
         if not isinstance(autoreset, (bool, str)) or autoreset not in modes:
-            raise ValueError(f"autoreset must be True, False, 'same_step', 'next_step' or 'levels', not {autoreset!r}")
+            raise ValueError(f"autoreset must be True, False, 'same_step', 'next_step', 'levels' or 'seeds', not {autoreset!r}")
         self.autoreset_mode = modes[autoreset]
-        if final_obs and self.autoreset_mode != "same_step":
+        if final_obs and self.autoreset_mode not in ("same_step", "seeds"):
             why = {"next_step": "the terminal step returns the terminal frame itself",
                    "levels": "the terminal frame is in self.obs only between the engine's step and the level loads, and nothing copies the "
                              "finished envs' rows out yet",
@@ -213,7 +224,8 @@ class MiniWorldVecEnv:
         cfg.domain_rand = int(domain_rand)
         cfg.generator = generator
         cfg.autoreset = {"same_step": eng.AUTORESET_SAME_STEP, "next_step": eng.AUTORESET_NEXT_STEP, "off": eng.AUTORESET_OFF,
-                         "levels": eng.AUTORESET_OFF}[self.autoreset_mode]      # (levels: the loads behind the step restart the envs)
+                         "levels": eng.AUTORESET_OFF,       # (levels: the loads behind the step restart the envs)
+                         "seeds": eng.AUTORESET_SAME_STEP}[self.autoreset_mode]
         self.autoreset = self.autoreset_mode != "off"
         cfg.agent_radius = float(self.template.agent.radius)
         if generator in (eng.GEN_HALLWAY, eng.GEN_ONEROOM):
@@ -333,6 +345,15 @@ class MiniWorldVecEnv:
         # autoreset="levels": the bank (set_levels), the level each env plays and the one it gets when its episode ends
         self.levels = self.level = self.next_level = self.played_level = None
         self._level_gen = self._done = self._done_b = self._ones = None
+        # autoreset="seeds": the seed each env gets when its episode ends (the engine reads it: mw_set_reset_seeds) and the one it plays
+        self.next_seed = self.episode_seed = self._done_i = None
+        if self.autoreset_mode == "seeds":
+            self.next_seed = torch.arange(num_envs, 2 * num_envs, dtype=torch.int64, device=dev) + int(seed)
+            self.episode_seed = torch.arange(num_envs, dtype=torch.int64, device=dev) + int(seed)
+            self._done = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
+            self._done_b = torch.zeros(num_envs, dtype=torch.bool, device=dev)
+            self._done_i = torch.zeros(num_envs, dtype=torch.int64, device=dev)
+            self.engine.set_reset_seeds(self.next_seed)
 
     # ------------------------------------------------------------------ assets / worlds
     def _upload_assets(self, sc):
@@ -392,10 +413,49 @@ class MiniWorldVecEnv:
             return self.obs
         if seed is not None:
             self._next_seed = seed
+        if self.autoreset_mode == "seeds":
+            # (the device reads these as uint64: a negative seed would become a huge one without a word)
+            if self._next_seed < 0 or self._next_seed + 2 * self.num_envs > 2 ** 63:
+                raise ValueError(f"reset: seed {self._next_seed} outside 0 .. 2^63 - 2 num_envs")
+            self.torch.arange(self._next_seed, self._next_seed + self.num_envs, out=self.episode_seed)
+            self.torch.arange(self._next_seed + self.num_envs, self._next_seed + 2 * self.num_envs, out=self.next_seed)
         seeds = np.arange(self.num_envs, dtype=np.uint64) + np.uint64(self._next_seed)
         self._next_seed += self.num_envs
         self.engine.reset(None, seeds)
         return self._redraw()
+
+    def reset_where(self, mask, seeds):
+        """The envs under `mask` (uint8[N] or bool[N]) start the episode of env.reset(seed=seeds[i]) (int64[N]), on the device and
+        without a host synchronisation when both are device tensors (mw_reset_where); host sequences are copied over first, and a
+        negative seed among them is refused.  seeds[i] is not read where mask[i] is 0.  Then the frame and the stack refresh of
+        reset(); the other envs, their streams and their rows of `self.obs` stay as they are.  With autoreset="seeds",
+        episode_seed follows; next_seed is the caller's.  Returns the observation tensor."""
+        torch, dev = self.torch, self.engine.device
+        if not torch.is_tensor(seeds):
+            vals = [int(x) for x in np.asarray(seeds, dtype=object).ravel()]        # (Python integers: seeds up to 2^64 - 1 keep their bits)
+            if any(not 0 <= x < 2 ** 64 for x in vals):
+                raise ValueError("seeds: need non-negative integers below 2^64")
+            seeds = torch.from_numpy(np.array(vals, dtype=np.uint64).view(np.int64))
+        elif seeds.device.type == "cpu" and seeds.dtype == torch.int64 and bool((seeds < 0).any()):
+            raise ValueError("seeds: negative seed")
+        if not torch.is_tensor(mask):
+            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0).astype(np.uint8))
+        if mask.dtype == torch.bool:
+            mask = mask.to(torch.uint8)
+        mask, seeds = mask.to(dev).contiguous(), seeds.to(device=dev, dtype=torch.int64).contiguous()
+        self.engine.reset_where(mask, seeds)
+        if self.episode_seed is not None:
+            torch.where(mask != 0, seeds, self.episode_seed, out=self.episode_seed)
+        return self._redraw()
+
+    def _advance_seeds(self):
+        """behind a step in seed mode, with no host value: episode_seed follows the envs that finished, their next_seed moves N on"""
+        torch = self.torch
+        torch.bitwise_or(self.terminated, self.truncated, out=self._done)
+        torch.ne(self._done, 0, out=self._done_b)
+        torch.where(self._done_b, self.next_seed, self.episode_seed, out=self.episode_seed)
+        self._done_i.copy_(self._done_b)
+        self.next_seed.add_(self._done_i, alpha=self.num_envs)
 
     @property
     def stack(self):
@@ -425,6 +485,8 @@ class MiniWorldVecEnv:
             self.engine.step_repeat(actions, repeat, self.obs, self.depth, self.reward, self.terminated, self.truncated, self.substeps)
         if levels:
             self._finished_to_levels(frames=True)
+        elif self.next_seed is not None:
+            self._advance_seeds()
         return self.obs, self.reward, self.terminated, self.truncated
 
     def rollout(self, plans, render: bool = True):
@@ -452,11 +514,15 @@ class MiniWorldVecEnv:
             self._step_rewards = torch.zeros((T, self.num_envs), dtype=torch.float32, device=self.engine.device)
         self.step_rewards = self._step_rewards[:T]
         obs, depth = (self.obs, self.depth) if render else (None, None)
+        if self.next_seed is not None and not render:
+            raise ValueError("rollout(render=False) with autoreset='seeds': a frameless call cannot seed the envs that finish in it")
         if self.autoreset_mode == "levels":
             self._need_levels("rollout")
         self.engine.step_plan(plans, obs, depth, self.reward, self._step_rewards, self.terminated, self.truncated, self.substeps)
         if self.autoreset_mode == "levels":
             self._finished_to_levels(frames=render)
+        elif self.next_seed is not None:
+            self._advance_seeds()
         return obs, self.reward, self.terminated, self.truncated
 
     # ------------------------------------------------------------------ level sets

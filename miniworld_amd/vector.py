@@ -51,6 +51,12 @@ save_state(frames=True)).  Finished envs then restart from a record of the bank 
 autoreset="levels"): the adapter advertises same-step auto-reset, info["level"] (int32[N]) is the level each env played in the step that
 just ended, and `self.vec.next_level` (int32[N] on the device) is the caller's to write between steps — a training set and a held-out
 set are two banks, a level-replay sampler writes its choices there.  final_obs is not available in this mode.
+
+**`reset_seeds=`: worlds by seed, unbounded.**  `reset_seeds=True` (MiniWorldVecEnv's autoreset="seeds") makes the same-step auto-reset
+start the reference's `env.reset(seed=next_seed[i])` for a finished env i, generated on the device: `self.vec.next_seed` (int64[N] on the
+device) is the caller's to write between steps, `info["seed"]` (int64[N]) is the seed each env played in the step that just ended.
+`reset_seeds=tensor` (or a sequence) also writes it as the first `next_seed`.  Left alone, env i walks seed + i, seed + N + i, ...
+Eight bytes per level instead of a record; composes with final_obs.
 """
 from __future__ import annotations
 
@@ -66,7 +72,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
                  frame_reuse: bool = True, frame_cache: int = 4, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset",
-                 levels=None, level_generator=None, **kwargs):
+                 levels=None, level_generator=None, reset_seeds=None, **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
         False draws every env on every step, for consumers that write into the returned observation tensor (module docstring).
@@ -78,7 +84,9 @@ class MiniWorldVectorEnv(VectorEnvBase):
         view, read-only until the next step, or a host copy with to_numpy; with final_obs, info["final_obs"] holds the final
         stacks (the old stack with the terminal frame appended).
         levels: seeds or an EnvSnapshot with frame records — finished envs restart from that bank (module docstring); same-step only,
-        without final_obs.  level_generator: the torch.Generator of the uniform draws of next_level."""
+        without final_obs.  level_generator: the torch.Generator of the uniform draws of next_level.
+        reset_seeds: True, or the first next_seed (int64[N] tensor / sequence) — finished envs restart from `vec.next_seed` (module
+        docstring); same-step only, excludes levels= and autoreset=."""
         if not isinstance(action_repeat, (int, np.integer)) or not 1 <= action_repeat <= 256:
             raise ValueError(f"action_repeat must be an integer in 1 .. 256, not {action_repeat!r}")
         self.action_repeat = int(action_repeat)
@@ -102,7 +110,20 @@ class MiniWorldVectorEnv(VectorEnvBase):
             if mode != "same-step" or final_obs or kwargs.get("autoreset", True) is not True:
                 raise ValueError("levels= is the same-step auto-reset from a bank: it excludes autoreset_mode='next-step', autoreset= and final_obs=True")
             kwargs["autoreset"] = "levels"
+        seeded = reset_seeds is not None and reset_seeds is not False
+        if seeded:
+            if mode != "same-step" or levels is not None or kwargs.get("autoreset", True) is not True:
+                raise ValueError("reset_seeds= is the seeded same-step auto-reset: it excludes autoreset_mode='next-step', autoreset= and levels=")
+            kwargs["autoreset"] = "seeds"
         self.vec = MiniWorldVecEnv(env_id, num_envs, **kwargs)
+        self._first_next_seed = None
+        if seeded and reset_seeds is not True:
+            first = np.asarray(reset_seeds.detach().cpu().numpy() if hasattr(reset_seeds, "detach") else reset_seeds)
+            if first.shape != (num_envs,) or first.dtype.kind not in "iu" or (first < 0).any():
+                raise ValueError(f"reset_seeds: need True or {num_envs} non-negative integers")
+            self._first_next_seed = self.vec.torch.from_numpy(first.astype(np.int64)).to(self.vec.engine.device)
+            self.vec.next_seed.copy_(self._first_next_seed)
+        self._played_seed = None
         if levels is not None:
             from .vec_env import EnvSnapshot
             self.vec.set_levels(levels if isinstance(levels, EnvSnapshot) else self.vec.make_levels(levels), level_generator)
@@ -132,6 +153,8 @@ class MiniWorldVectorEnv(VectorEnvBase):
         """Env i is seeded with seed + i (gymnasium's convention for an integer seed); with levels= every env starts a level of the
         bank and the seed is not used."""
         obs = self.vec.reset(seed)
+        if self._first_next_seed is not None:       # (reset() lays out seed + N + i; the caller's first choices stand)
+            self.vec.next_seed.copy_(self._first_next_seed)
         return self._out(self._obs(obs)), {}
 
     def step(self, actions):
@@ -139,11 +162,15 @@ class MiniWorldVectorEnv(VectorEnvBase):
         if not torch.is_tensor(actions):
             actions = torch.as_tensor(np.asarray(actions), device=self.vec.engine.device)
         actions = actions.to(device=self.vec.engine.device, dtype=torch.int32)
+        if self.vec.autoreset_mode == "seeds":      # the seed each env plays in this step (the step moves episode_seed on)
+            if self._played_seed is None:
+                self._played_seed = torch.zeros_like(self.vec.episode_seed)
+            self._played_seed.copy_(self.vec.episode_seed)
         obs, rew, term, trunc = self.vec.step(actions, self.action_repeat)
         info = self._infos()
         if self.action_repeat > 1:
             info["substeps"] = self._out(self.vec.substeps) if self.to_numpy else self.vec.substeps.clone()
-        if self.vec.autoreset_mode in ("same_step", "levels"):
+        if self.vec.autoreset_mode in ("same_step", "levels", "seeds"):
             # gymnasium's same-step convention: "_final_info" masks the envs whose episode ended with this step (every family); the
             # finished episodes' own info under "final_info" where the family has info keys — clones, the engine's buffers are
             # rewritten by the next step.  ("final_obs" with final_obs=True: see the module's docstring.)
@@ -159,6 +186,8 @@ class MiniWorldVectorEnv(VectorEnvBase):
                 info["final_info"] = final
         if self.vec.autoreset_mode == "levels":
             info["level"] = self._out(self.vec.played_level) if self.to_numpy else self.vec.played_level.clone()
+        if self.vec.autoreset_mode == "seeds":
+            info["seed"] = self._out(self._played_seed) if self.to_numpy else self._played_seed.clone()
         return self._out(self._obs(obs)), self._out(rew), self._out(term.bool()), self._out(trunc.bool()), info
 
     def render(self):

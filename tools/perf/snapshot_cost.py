@@ -20,6 +20,13 @@ frame_stack=4), Maze x 1024 and PickupObjects (domain randomisation) x 2048.
                                                               # tree against the host-driven loop of the parent commit (done.nonzero(),
                                                               # load_state(envs, records, frames=True)), and — for information — this tree's
                                                               # same-step auto-reset; alternating windows, a process each
+    python tools/perf/snapshot_cost.py --op seed_step [--seed-vs <parent checkout>]
+                                                              # the step loop of Hallway x 4096 where finished envs restart from chosen
+                                                              # seeds: autoreset="seeds" on this tree against the host-driven loop the parent
+                                                              # commit offers (autoreset=False, done.nonzero(), engine.reset(mask, seeds), a
+                                                              # render; run on the parent checkout when one is given, else on this tree) and
+                                                              # this tree's same-step auto-reset on the envs' own streams; alternating
+                                                              # windows, a process each
 
 Wall time: per config one env; the timed windows alternate between save_state(), load_state(snap), fork(random src), a render alone (what
 load_state and fork end with) and the only thing a user could do before: engine.get_state() + engine.set_state() through the host —
@@ -286,6 +293,65 @@ def level_vs(parent, windows, steps, warmup):
                       "every_levels_window_below_every_host_window": max(us["levels"]) < min(us["host_parent"])}), flush=True)
 
 
+def seed_window(mode, steps, warmup):
+    """one window of the seeded step loop in a process of its own (seed_vs), Hallway x 4096, uniform-random actions, default episode
+    lengths; a finished env restarts from the seed next_seed[i], which moves on by N.  "seeds": autoreset="seeds" of this tree.
+    "host": what the parent commit can do, written with its calls alone — autoreset=False, the finished envs read on the host,
+    engine.reset(mask, seeds) from host arrays (a stream synchronisation, the whole stream array to the host and back), a render of
+    the whole batch.  "same_step": the generator's own auto-reset, no seed control."""
+    import numpy as np
+    import torch
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    env_id, n, n_act, _ = CONFIGS["hallway"]
+    g = torch.Generator(device="cuda").manual_seed(1)
+    vec = MiniWorldVecEnv(env_id, n, seed=0, autoreset={"seeds": "seeds", "host": False, "same_step": True}[mode])
+    vec.reset(seed=0)
+    next_seed = np.arange(n, 2 * n, dtype=np.uint64)
+
+    def step():
+        act = torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32)
+        _, _, term, trunc = vec.step(act)
+        if mode == "host":
+            idx = (term | trunc).nonzero().squeeze(1).cpu().numpy()
+            if idx.size:
+                mask = np.zeros(n, np.uint8)
+                mask[idx] = 1
+                vec.engine.reset(mask, next_seed)
+                vec.engine.render(vec.obs, vec.depth)
+                next_seed[idx] += np.uint64(n)
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    us = 1e6 * (time.perf_counter() - t0) / steps
+    vec.engine.check()
+    vec.close()
+    print(json.dumps({"us": round(us, 1)}), flush=True)
+
+
+def seed_vs(parent, windows, steps, warmup):
+    """alternating windows, every window a process of its own that runs this very file on its tree (--root)"""
+    us = {"seeds": [], "host_loop": [], "same_step": []}
+    for _ in range(windows):
+        for tag, root, mode in (("seeds", ROOT, "seeds"), ("host_loop", parent or ROOT, "host"), ("same_step", ROOT, "same_step")):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--root", root, "--seed-window", mode, "--reps", str(steps),
+                                "--warmup", str(warmup)], cwd=root, capture_output=True, text=True, timeout=600)
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+            if p.returncode != 0 or not line:
+                print(json.dumps({"tree": tag, "error": (p.stdout + p.stderr)[-2000:]}), flush=True)
+                raise SystemExit(1)
+            us[tag].append(json.loads(line[-1])["us"])
+    n = CONFIGS["hallway"][1]
+    med = {k: sorted(v)[len(v) // 2] for k, v in us.items()}
+    print(json.dumps({"config": "hallway", "num_envs": n, "steps_per_window": steps, "host_loop_tree": "parent" if parent else "this", "windows_us_per_step": us,
+                      "env_steps_per_s_median": {k: round(n / v * 1e6) for k, v in med.items()},
+                      "seeds_over_same_step_percent": round(100 * (med["seeds"] / med["same_step"] - 1), 1),
+                      "every_seeds_window_below_every_host_window": max(us["seeds"]) < min(us["host_loop"])}), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--configs", default="hallway,hallway_stack4,maze,pickup_dr")
@@ -293,10 +359,12 @@ def main():
     p.add_argument("--reps", type=int, default=50, help="calls per timed window (the host round trip: a tenth)")
     p.add_argument("--warmup", type=int, default=100, help="steps before anything is measured")
     p.add_argument("--profile", choices=sorted(CONFIGS), help="one config, untimed: the run a profiler wraps")
-    p.add_argument("--op", choices=["save_load", "fork", "fork_frames", "load_where", "level_step"], default="save_load")
+    p.add_argument("--op", choices=["save_load", "fork", "fork_frames", "load_where", "level_step", "seed_step"], default="save_load")
     p.add_argument("--density", type=float, default=1.0, help="--op load_where: the share of envs under the mask")
     p.add_argument("--level-vs", metavar="PARENT", help="--op level_step: a built checkout of the parent commit for the host-driven loop")
     p.add_argument("--level-window", choices=["levels", "host", "same_step"], help=argparse.SUPPRESS)
+    p.add_argument("--seed-vs", metavar="PARENT", help="--op seed_step: a built checkout of the parent commit for the host-driven loop (default: this tree, which has the same calls)")
+    p.add_argument("--seed-window", choices=["seeds", "host", "same_step"], help=argparse.SUPPRESS)
     p.add_argument("--bench", metavar="PARENT", help="a built checkout of the parent commit: alternate bench.py between it and this tree")
     p.add_argument("--rounds", type=int, default=2)
     p.add_argument("--fork-vs", metavar="PARENT", help="a built checkout of the parent commit: its fork(src) against this tree's fork(src, frames=True)")
@@ -308,6 +376,10 @@ def main():
         sys.path.insert(0, os.path.abspath(args.root))
     if args.level_window:
         return level_window(args.level_window, args.reps, args.warmup)
+    if args.seed_window:
+        return seed_window(args.seed_window, args.reps, args.warmup)
+    if args.op == "seed_step":
+        return seed_vs(os.path.abspath(args.seed_vs) if args.seed_vs else None, args.windows, 200 if args.reps == 50 else args.reps, args.warmup)
     if args.op == "level_step":
         if not args.level_vs:
             p.error("--op level_step needs --level-vs <parent checkout>")
