@@ -257,6 +257,42 @@ extern "C" int mwhost_list_length(const mwo_scene *sc)
     return (int)tris.size();
 }
 
+// The quad kernel's bookkeeping counts, per rectangle of the frame, the list's triangles that TOUCH it and those that cover
+// it in FULL — by edge functions alone, each edge on its own (mw_rasterq.hip, classify_at).  The same two counts from the
+// definition, with nothing of the kernel's thresholds in it: a triangle touches a rectangle iff every edge is positive at
+// SOME sample of some pixel of it (not necessarily the same one for the three edges), and covers it iff every edge is
+// positive at EVERY sample of every pixel.  Rectangles of rw x rh pixels (16 x 4: a tile, 2 x 2: a quad) of a frame that is
+// a whole number of them; touch, full: [H / rh][W / rw], image rows (row 0 at the top).  Returns the list length.
+extern "C" int mwhost_rect_counts(const mwo_scene *sc, int rw, int rh, int32_t *touch, int32_t *full)
+{
+    const int W = sc->width, H = sc->height, S = sc->nsamples;
+    if (W % rw || H % rh) return -1;
+    const int (*pat)[2] = S == 1 ? PAT1 : (S == 4 ? PAT4 : (S == 8 ? PAT8 : PAT16));
+    const bool ms = S > 1;
+    std::vector<Tri> tris;
+    geometry(sc, ms, tris);
+    const int nx = W / rw, ny = H / rh;
+    for (int i = 0; i < nx * ny; ++i) touch[i] = full[i] = 0;
+    for (const Tri &tr : tris)
+        for (int ry = 0; ry < ny; ++ry)
+            for (int rx = 0; rx < nx; ++rx) {
+                bool some[3] = {false, false, false}, every[3] = {true, true, true};
+                for (int y = 0; y < rh; ++y)
+                    for (int x = 0; x < rw; ++x)
+                        for (int s = 0; s < S; ++s) {
+                            const int px = rx * rw + x, gy = H - 1 - (ry * rh + y);
+                            const int32_t fx = px * 256 + (ms ? pat[s][0] * 16 : 0), fy = gy * 256 + (ms ? pat[s][1] * 16 : 0);
+                            for (int k = 0; k < 3; ++k) {
+                                const bool in = (tr.ts.c[k] + (int64_t)tr.ts.dcdy[k] * fy - (int64_t)tr.ts.dcdx[k] * fx) > 0;
+                                some[k] |= in; every[k] &= in;
+                            }
+                        }
+                touch[ry * nx + rx] += some[0] && some[1] && some[2];
+                full[ry * nx + rx] += every[0] && every[1] && every[2];
+            }
+    return (int)tris.size();
+}
+
 // glibc's sinf / cosf against the restatement the device uses (exhaustive range test in tests/)
 extern "C" void mwhost_sincosf(float x, float *s, float *c) { sincosf_glibc(x, *s, *c); }
 
