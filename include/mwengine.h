@@ -294,6 +294,35 @@ int mw_set_state(mw_engine *e, int32_t first_env, int32_t count, const mw_state_
  * NULL switches the override off. */
 int mw_set_step_params(mw_engine *e, const double *host_params);
 int mw_get_state(mw_engine *e, int32_t first_env, int32_t count, mw_state_view *host);
+/* State views on the device: what research code around the reference reads and writes as plain Python attributes — env.agent.pos and
+ * env.agent.dir, env.agent.carrying, env.entities[k].pos, env.step_count (entity.py:455-515, miniworld.py:576-578; the attributes
+ * mw_state_view lists) — for an asymmetric critic, a visitation count, a scripted expert, the cell key of an archive, a start-state
+ * curriculum, without the synchronisation, the per-component copies and the host transposition of mw_get_state / mw_set_state.  Both
+ * calls take the same struct: it stays in HOST memory, its pointers are DEVICE pointers (torch tensors), any may be NULL (= leave / do
+ * not fetch).  One kernel launch each, asynchronous on `stream`, no host value read, no synchronisation.
+ *
+ * mw_get_state_device: rows of envs first_env .. first_env + count - 1, laid out exactly as mw_get_state lays them out on the host
+ * ([count][3], [count], [count][max_ents][9], ...), bit for bit what mw_get_state would return at that point of the stream: ent_kind
+ * MW_ENT_NONE for a removed slot, a picked-up object still listed until the frame's tail removed it, the new episode's state for an env
+ * a same-step auto-reset just restarted, the terminal state under MW_AUTORESET_NEXT_STEP.  It reads live state only and changes
+ * nothing in the engine.  count == 0 is MW_OK and launches nothing.  MW_E_INVALID before anything is launched: a null engine or view,
+ * a range outside 0 .. num_envs, a view whose pointers are all NULL. */
+int mw_get_state_device(mw_engine *e, int32_t first_env, int32_t count, const mw_state_view *d_view, void *stream);
+/* mw_set_state_where: rows are [N][...] over ALL num_envs envs, d_mask is uint8[N] on the device.  For every env i with d_mask[i] != 0,
+ * row i of each non-null field is written into the engine's state: mid-episode injection with mw_set_state's meaning (and its domain of
+ * agent_dir) — no consistency is made between fields.  Row i of any field is not read where d_mask[i] == 0: garbage or NaN under a zero
+ * mask byte is never an error.  The grid covers all N envs whatever the mask holds.  `extent` may be written; it is a top-view value.
+ * What each written env is owed, on the device (the pattern of mw_snapshot_load_where): its pending next-step auto-reset is dropped
+ * and, as by mw_set_state, the rebuild of its frame stack that reset would have caused (the stacks themselves stay); its frame-clean
+ * byte is cleared; its frame-cache epoch advances, so none of its cached frames can match again.  Nothing is owed to any other env:
+ * their cached frames stay valid, where mw_set_state drops every env's.  On the host the held frame of frame reuse is dropped (the
+ * caller's buffers no longer show the masked envs): draw next (mw_render), or step — the step draws every env it cannot serve from the
+ * frame cache.
+ * Validation on the device: a masked env whose `carrying` lies outside -1 .. max_ents - 1 or one of whose `ent_kind` lies outside
+ * MW_ENT_NONE .. MW_ENT_FRAME is skipped whole — it writes nothing — and sets a status bit that the next mw_check reports as
+ * MW_E_INVALID, once, ahead of whatever else the status word holds (the check after it reports that); the other envs are written as usual.  MW_E_INVALID before anything is launched: a null engine, mask or view, a
+ * view whose pointers are all NULL. */
+int mw_set_state_where(mw_engine *e, const uint8_t *d_mask, const mw_state_view *d_view, void *stream);
 /* device-side MiniWorldEnv.reset (miniworld.py:544-604) for the configured generator.
  * mask: host uint8[num_envs] or NULL (= all); seeds: host uint64[num_envs] or NULL.
  * With MW_GEN_NONE (host-generated worlds) only the re-seeding happens: seeds[i] (masked) re-seeds env i's device
@@ -625,7 +654,8 @@ int mw_snapshot_load_frames_where(mw_engine *e, const uint8_t *d_mask, const int
                                   int32_t n_recs, int32_t capacity, int32_t flags, uint8_t *d_obs, float *d_depth,
                                   void *stream);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped); synchronises `stream` */
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where skipped — these are
+ * reported first, by one check, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 
 /* ---- measurement ------------------------------------------------------------- */

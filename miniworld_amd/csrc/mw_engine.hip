@@ -332,6 +332,13 @@ int launch_info(mw_engine *e, int E, const int32_t *health, const double *pos, i
     return MW_OK;
 }
 
+// the engine's arrays of mw_state_view's fields, for the state-view kernels (mw_state_view.h)
+MwStateArrays state_arrays_of(const mw_engine *e)
+{
+    const MwArgs &a = e->args;
+    return {a.ax, a.ay, a.az, a.adir, a.cam, a.light, a.carry, a.step, a.picked, a.ekind, a.emesh, a.estatic, a.epos, a.edir, a.egeom, a.extent};
+}
+
 // mw_get_reset_pending / mw_get_frame_source / mw_get_frame_clean: one of the engine's uint8 [N] arrays, device to device
 int get_env_bytes(mw_engine *e, const char *what, const uint8_t *src, uint8_t *d_out, void *stream)
 {
@@ -542,6 +549,43 @@ int mw_get_state(mw_engine *e, int32_t first_env, int32_t count, mw_state_view *
     return state_xfer(e, first_env, count, host, false);
 }
 
+// The two device-side state views.  Neither waits for the Maze's side-stream refills (refill_order), which mw_snapshot_load and
+// mw_reset_where do wait for: those calls read or write spares, refill_mask words or the envs' streams, the refill kernel's own data.
+// The refill kernel generates into the spare arrays through the redirected argument block (sync_gen_args: everything of the world goes
+// to the spares, carry / step / picked to a dummy) and touches the stream and refill_mask beside them — it neither reads nor writes a
+// live array of mw_state_view's fields, and these two calls touch nothing else of the world (the write's reset_pending, frame_clean,
+// fc_epoch and stack flags belong to the caller's stream alone).  So the order of either against a running refill does not matter.
+int mw_get_state_device(mw_engine *e, int32_t first_env, int32_t count, const mw_state_view *d_view, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (!d_view) return fail(e, MW_E_INVALID, "mw_get_state_device: d_view is null");
+    if (first_env < 0 || count < 0 || first_env > e->cfg.num_envs - count) return fail(e, MW_E_INVALID, "mw_get_state_device: env range out of bounds");
+    if (!mwsv::any_field(*d_view)) return fail(e, MW_E_INVALID, "mw_get_state_device: every pointer of the view is null");
+    if (count == 0) return MW_OK;
+    ON_DEVICE(e);
+    hipLaunchKernelGGL(mw_state_get_kernel, dim3((unsigned)((count + MW_SV_ENVS - 1) / MW_SV_ENVS)), dim3(MW_SV_THREADS), 0, (hipStream_t)stream,
+                       state_arrays_of(e), *d_view, e->cfg.num_envs, e->args.E, (int)first_env, (int)count);
+    HIP_TRY(e, hipGetLastError());
+    return MW_OK;
+}
+
+int mw_set_state_where(mw_engine *e, const uint8_t *d_mask, const mw_state_view *d_view, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (!d_mask || !d_view) return fail(e, MW_E_INVALID, "mw_set_state_where: %s is null", d_mask ? "d_view" : "d_mask");
+    if (!mwsv::any_field(*d_view)) return fail(e, MW_E_INVALID, "mw_set_state_where: every pointer of the view is null");
+    ON_DEVICE(e);
+    // the caller's buffers no longer show the masked envs; the other envs keep their cached frames (the kernel advances the epochs of the
+    // envs it writes)
+    invalidate(e, set_state_where_invalidation());
+    const int N = e->cfg.num_envs;
+    hipLaunchKernelGGL(mw_state_set_where_kernel, dim3((unsigned)((N + MW_SV_ENVS - 1) / MW_SV_ENVS)), dim3(MW_SV_THREADS), 0, (hipStream_t)stream,
+                       state_arrays_of(e), *d_view, d_mask, N, e->args.E, e->args.status, e->args.reset_pending, e->args.frame_clean, e->args.fc_epoch,
+                       e->stack.depth ? stack_flags(e, e->stack.cur) : nullptr);
+    HIP_TRY(e, hipGetLastError());
+    return MW_OK;
+}
+
 int mw_set_gen_program(mw_engine *e, const mw_gen_program *prog, const mw_poly *polys, const int32_t *poly_room,
                        const int32_t *poly_surf, const double *poly_m, int32_t n_polys, const double *segs, int32_t n_segs)
 {
@@ -691,6 +735,13 @@ int mw_check(mw_engine *e, void *stream)
     HIP_TRY(e, hipStreamSynchronize((hipStream_t)stream));
     uint32_t st = 0;
     HIP_TRY(e, hipMemcpy(&st, e->args.status, 4, hipMemcpyDeviceToHost));
+    if (st & MW_ST_STATE_BAD) {
+        // reported once, and ahead of the sticky bits below, which return first on every check once they are set: the bit belongs to the
+        // calls since the last check (the stream is idle here); the other bits stay as they are, for the next check to report
+        const uint32_t rest = st & ~MW_ST_STATE_BAD;
+        HIP_TRY(e, hipMemcpy(e->args.status, &rest, 4, hipMemcpyHostToDevice));
+        return fail(e, MW_E_INVALID, "mw_set_state_where skipped an env: its carrying outside -1 .. %d or an ent_kind outside %d .. %d", e->args.E - 1, MW_ENT_NONE, MW_ENT_FRAME);
+    }
     if (st & MW_ST_VIS_OVERFLOW) return fail(e, MW_E_OVERFLOW, "more than max_visible=%d visible primitives in some env", e->cfg.max_visible);
     if (st & MW_ST_PLACEMENT_FAIL) return fail(e, MW_E_OVERFLOW, "device-side placement did not converge in some env");
     if (st & MW_ST_SNAPSHOT_BAD)

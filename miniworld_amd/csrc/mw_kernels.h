@@ -5,6 +5,7 @@
 #include "mw_device.h"
 #include "mw_snapshot.h"
 #include "mw_snapframes.h"
+#include "mw_state_view.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -199,6 +200,20 @@ extern "C" __global__ void mw_info_kernel(int N, int E, const int32_t *health, c
 extern "C" __global__ void mw_final_list_kernel(int N, const uint8_t *__restrict__ pending, int32_t *__restrict__ pending_remove, int32_t *__restrict__ list);
 extern "C" __global__ void mw_final_copy_kernel(const int32_t *__restrict__ list, const uint8_t *__restrict__ obs, uint8_t *__restrict__ final_obs,
                                                 unsigned long long row_bytes, const float *__restrict__ depth, float *__restrict__ final_depth, int depth_row);
+
+// state views (mw_state_view.hip; the index arithmetic and MwStateArrays: mw_state_view.h): one launch per call, a wavefront per env,
+// MW_SV_ENVS envs per workgroup.  The view is the caller's mw_state_view by value: device pointers, null = field not asked for.
+//   get        item k < count is env first_env + k, row k of every non-null field := its state
+//   set_where  grid over all N envs; env i with mask[i] != 0: row i of every non-null field into the engine, then reset_pending,
+//              frame_clean, fc_epoch and the MW_STACK_PENDING bit of stack_flags (the current half; null without a stack) as
+//              mw_set_state_where owes them; an env whose carrying or ent_kind row is out of range writes nothing and sets MW_ST_STATE_BAD
+#define MW_SV_THREADS 256
+#define MW_SV_ENVS (MW_SV_THREADS / 64)
+extern "C" __global__ void mw_state_get_kernel(MwStateArrays a, mw_state_view v, int N, int E, int first_env, int count);
+extern "C" __global__ void mw_state_set_where_kernel(MwStateArrays a, mw_state_view v, const uint8_t *__restrict__ mask, int N, int E,
+                                                     uint32_t *__restrict__ status, uint8_t *__restrict__ reset_pending,
+                                                     uint8_t *__restrict__ frame_clean, uint32_t *__restrict__ fc_epoch,
+                                                     uint8_t *__restrict__ stack_flags);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -261,6 +261,9 @@ struct LoadInvalidation { bool held, cache; };
 inline LoadInvalidation snapshot_load_invalidation(bool where) { return {true, !where}; }
 // ... and mw_reset_where, the masked seeded reset on the device: as the masked load — its kernel advances the epochs of the envs it writes
 inline LoadInvalidation reset_where_invalidation() { return snapshot_load_invalidation(true); }
+// ... and mw_set_state_where, the masked state write on the device: the same again — where mw_set_state marks the whole cache dirty, its
+// kernel advances the epochs of the envs it writes and every other env keeps its cached frames
+inline LoadInvalidation set_state_where_invalidation() { return snapshot_load_invalidation(true); }
 // ... and of frame records, either form: rows of d_obs are written, no state changes
 inline LoadInvalidation snapshot_load_frames_invalidation(bool /*where*/) { return {true, false}; }
 

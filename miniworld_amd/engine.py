@@ -47,6 +47,7 @@ EXPORTS = [
     "mw_snapshot_frames_bytes", "mw_snapshot_save_frames", "mw_snapshot_load_frames",
     "mw_snapshot_save_at", "mw_snapshot_save_frames_at", "mw_snapshot_load_where", "mw_snapshot_load_frames_where",
     "mw_reset_where", "mw_set_reset_seeds",
+    "mw_get_state_device", "mw_set_state_where",
 ]
 
 
@@ -185,6 +186,8 @@ def load_library():
     L.mw_get_geometry.argtypes = [vp, i32, vp, C.POINTER(i32), vp, C.POINTER(i32)]
     L.mw_set_state.argtypes = [vp, i32, i32, C.POINTER(MwStateView)]
     L.mw_get_state.argtypes = [vp, i32, i32, C.POINTER(MwStateView)]
+    L.mw_get_state_device.argtypes = [vp, i32, i32, C.POINTER(MwStateView), vp]
+    L.mw_set_state_where.argtypes = [vp, vp, C.POINTER(MwStateView), vp]
     L.mw_set_step_params.argtypes = [vp, vp]
     L.mw_set_gen_program.argtypes = [vp, C.POINTER(MwGenProgram), vp, vp, vp, vp, i32, vp, i32]
     L.mw_reset.argtypes = [vp, vp, vp, vp]
@@ -352,6 +355,60 @@ class Engine:
         view, keep = self._view({}, count, alloc=True)
         self._check(self.lib.mw_get_state(self.h, first, count, C.byref(view)), "mw_get_state")
         return keep
+
+    def _state_tensor(self, t, name, rows):
+        """A field of a device-side state view: a contiguous tensor [rows, *field shape] of the field's dtype (float64 / int32) on the
+        engine's device.  Checked, never converted: the kernels read raw pointers (_dev_tensor)."""
+        import torch
+        if name not in STATE_FIELDS:
+            raise EngineError(f"{name!r} is no state field; have {sorted(STATE_FIELDS)}")
+        dt, shp = STATE_FIELDS[name]
+        dtype, shape = (torch.float64 if dt is np.float64 else torch.int32), (rows,) + shp(self.E)
+        if not torch.is_tensor(t) or tuple(t.shape) != shape:
+            raise EngineError(f"{name}: need a {dtype} tensor of shape {shape} on {self.device}, got "
+                              f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        return self._dev_tensor(t, name, dtype, int(np.prod(shape, dtype=np.int64)))
+
+    def _device_view(self, tensors: dict, rows: int):
+        view = MwStateView()
+        for name, t in tensors.items():
+            if t is None and name in STATE_FIELDS:      # (as for set_state: leave / do not fetch)
+                continue
+            setattr(view, name, self._state_tensor(t, name, rows).data_ptr())
+        if not any(getattr(view, name) for name in STATE_FIELDS):
+            raise EngineError("state view: no field named (every entry is None)")
+        return view
+
+    def get_state_device(self, out: dict | None = None, first: int = 0, count: int | None = None) -> dict:
+        """get_state() on the device (mw_get_state_device): one kernel on the current stream, no synchronisation, no host value.
+        `out` maps field names (those of get_state()) to device tensors [count, *field shape] of the field's dtype (float64 /
+        int32), which are filled and returned; only the fields named are fetched.  None: every field, into new tensors.  The rows
+        are bit for bit what get_state(first, count) would return at this point of the stream.  A tensor of another dtype,
+        device, shape or stride pattern is refused before the library is called."""
+        import torch
+        count = self.N - first if count is None else count
+        if first < 0 or count < 0 or first + count > self.N:
+            raise EngineError(f"get_state_device: envs {first} .. {first + count - 1} of {self.N}")
+        if out is None:
+            out = {name: torch.zeros((count,) + shp(self.E), dtype=torch.float64 if dt is np.float64 else torch.int32, device=self.device)
+                   for name, (dt, shp) in STATE_FIELDS.items()}
+        if not out:
+            raise EngineError("get_state_device: no field named")
+        view = self._device_view(out, count)
+        self._check(self.lib.mw_get_state_device(self.h, int(first), int(count), C.byref(view), _stream_ptr(self.device)), "mw_get_state_device")
+        return out
+
+    def set_state_where(self, mask, arrays: dict):
+        """set_state() under a device mask (mw_set_state_where): for every env i with mask[i] != 0, row i of each tensor in `arrays`
+        (field name -> device tensor [N, *field shape], float64 / int32) is written into the engine's state; rows under a zero mask
+        byte are not read.  mask is a uint8[N] device tensor.  One kernel on the current stream, no synchronisation; the envs
+        written lose their pending next-step reset, their frame-clean byte and their cached frames, every other env keeps its
+        own.  Draw next (render), or step.  Nothing is converted: a wrong tensor is refused before the library is called."""
+        mask = self._mask_tensor(mask)
+        if not arrays:
+            raise EngineError("set_state_where: no field named")
+        view = self._device_view(arrays, self.N)
+        self._check(self.lib.mw_set_state_where(self.h, _ptr(mask), C.byref(view), _stream_ptr(self.device)), "mw_set_state_where")
 
     def set_gen_program(self, prog: MwGenProgram, polys: np.ndarray, poly_room, poly_surf, poly_m, segs: np.ndarray):
         """Installs the placement program of an MW_GEN_PROGRAM engine (include/mwengine.h: mw_set_gen_program)."""

@@ -340,6 +340,7 @@ class MiniWorldVecEnv:
         self._info_slot = int(cfg.goal_ent)
         self._info_buf = None
         self._final_info_buf = None
+        self._state_bufs = {}           # state()'s tensors, one per field, made on first use
         self._fork_buf = None           # fork()'s scratch records, made on first use
         self._fork_frames = None        # ... and its scratch frame records (fork(src, frames=True))
         # autoreset="levels": the bank (set_levels), the level each env plays and the one it gets when its episode ends
@@ -752,6 +753,66 @@ class MiniWorldVecEnv:
         eng_.snapshot_load(self._fork_buf, n, n, None, src)
         eng_.snapshot_load_frames(self._fork_frames, n, n, self.obs, self.depth, flags, None, src)
         return self.obs
+
+    # ------------------------------------------------------------------ state views
+    STATE_DEFAULT = ("agent_pos", "agent_dir", "carrying", "step_count", "ent_kind", "ent_pos", "ent_dir")
+
+    def state(self, fields=None):
+        """The envs' own state as device tensors — what code around the reference reads as env.agent.pos / .dir / .carrying,
+        env.entities[k].pos, env.step_count: {"agent_pos": float64[N, 3], "agent_dir": float64[N], "carrying": int32[N] (entity slot
+        or -1), "step_count": int32[N], "ent_kind": int32[N, E] (engine.ENT_*, ENT_NONE = empty or removed), "ent_pos":
+        float64[N, E, 3], "ent_dir": float64[N, E]} by default; `fields` is any subset of the names of engine.get_state() ("cam",
+        "light", "num_picked_up", "ent_mesh", "ent_static", "ent_geom", "extent" beside those).  One gather kernel on the engine's
+        stream (mw_get_state_device), no synchronisation and no host value: an expert, a visitation count or an archive's cell key
+        is computed from it in torch behind the step.  The tensors are this env's own, reused between calls: valid until the next
+        state() call that names the field.  The values are those of the state the device holds (as for infos(): with the same-step
+        auto-reset an env that just finished reports its new episode; with the next-step auto-reset it reports the finished one
+        until its next step installs the new episode)."""
+        torch, e = self.torch, self.engine
+        names = self.STATE_DEFAULT if fields is None else tuple(fields)
+        out = {}
+        for name in names:
+            if name not in eng.STATE_FIELDS:
+                raise ValueError(f"state: {name!r} is no state field; have {sorted(eng.STATE_FIELDS)}")
+            if name not in self._state_bufs:
+                dt, shp = eng.STATE_FIELDS[name]
+                self._state_bufs[name] = torch.zeros((self.num_envs,) + shp(e.E), dtype=torch.float64 if dt is np.float64 else torch.int32,
+                                                     device=e.device)
+            out[name] = self._state_bufs[name]
+        if not out:
+            raise ValueError("state: no field named")
+        return e.get_state_device(out)
+
+    def set_state_where(self, mask, **fields):
+        """The envs under `mask` (uint8[N] or bool[N]) get row i of every field given — agent_pos=float64[N, 3], agent_dir=float64[N],
+        ent_pos=float64[N, E, 3], carrying=int32[N], ...: the names, shapes and dtypes of state() — written into their state, on the
+        device and without a host synchronisation when everything is a device tensor (mw_set_state_where); host sequences and bool
+        masks are copied over first.  Mid-episode injection, as engine.set_state(): teleporting the agents of chosen envs, a
+        start-state curriculum, goal relabelling; no consistency is made between fields, and rows where mask[i] is 0 are not read.
+        A device tensor of the wrong dtype or shape is refused, never converted.  Then the frame and the stack refresh of reset();
+        the other envs, their cached frames and their rows of `self.obs` stay as they are.  In the "seeds" and "levels" modes
+        episode_seed and level are left alone: the env is still playing that episode.  Returns the observation tensor."""
+        torch, dev = self.torch, self.engine.device
+        if not fields:
+            raise ValueError("set_state_where: no field given")
+        arrays = {}
+        for name, val in fields.items():
+            if name not in eng.STATE_FIELDS:
+                raise ValueError(f"set_state_where: {name!r} is no state field; have {sorted(eng.STATE_FIELDS)}")
+            dt, shp = eng.STATE_FIELDS[name]
+            if not torch.is_tensor(val):
+                val = torch.from_numpy(np.ascontiguousarray(np.asarray(val, dtype=dt))).to(dev)
+            arrays[name] = val
+        if not torch.is_tensor(mask):
+            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0).astype(np.uint8))
+        if mask.dtype == torch.bool:
+            mask = mask.to(torch.uint8)
+        mask = mask.to(dev).contiguous()
+        # (the tensors are checked before the first library call: a wrong one leaves the engine as it was)
+        for name, t in arrays.items():
+            self.engine._state_tensor(t, name, self.num_envs)
+        self.engine.set_state_where(mask, arrays)
+        return self._redraw()
 
     def _redraw(self):
         self.engine.render(self.obs, self.depth)

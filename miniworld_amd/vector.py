@@ -72,7 +72,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
                  frame_reuse: bool = True, frame_cache: int = 4, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset",
-                 levels=None, level_generator=None, reset_seeds=None, **kwargs):
+                 levels=None, level_generator=None, reset_seeds=None, info_state=None, **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
         False draws every env on every step, for consumers that write into the returned observation tensor (module docstring).
@@ -86,7 +86,12 @@ class MiniWorldVectorEnv(VectorEnvBase):
         levels: seeds or an EnvSnapshot with frame records — finished envs restart from that bank (module docstring); same-step only,
         without final_obs.  level_generator: the torch.Generator of the uniform draws of next_level.
         reset_seeds: True, or the first next_seed (int64[N] tensor / sequence) — finished envs restart from `vec.next_seed` (module
-        docstring); same-step only, excludes levels= and autoreset=."""
+        docstring); same-step only, excludes levels= and autoreset=.
+        info_state: names of state fields (MiniWorldVecEnv.state: "agent_pos", "agent_dir", "carrying", "ent_pos", ...) — every
+        step() and reset() adds them to info as arrays over the batch, filled by one gather kernel behind the step; None (the
+        default) adds nothing.  The rows show the state the device holds, as the other info keys do: for an env whose episode ended
+        with the step that is its next episode's first state under the same-step auto-reset, the terminal state under next-step.
+        Copies: they stay valid after the next step."""
         if not isinstance(action_repeat, (int, np.integer)) or not 1 <= action_repeat <= 256:
             raise ValueError(f"action_repeat must be an integer in 1 .. 256, not {action_repeat!r}")
         self.action_repeat = int(action_repeat)
@@ -115,6 +120,10 @@ class MiniWorldVectorEnv(VectorEnvBase):
             if mode != "same-step" or levels is not None or kwargs.get("autoreset", True) is not True:
                 raise ValueError("reset_seeds= is the seeded same-step auto-reset: it excludes autoreset_mode='next-step', autoreset= and levels=")
             kwargs["autoreset"] = "seeds"
+        from .engine import STATE_FIELDS
+        self.info_state = None if info_state is None else tuple(info_state)
+        if self.info_state is not None and (isinstance(info_state, str) or not self.info_state or any(k not in STATE_FIELDS for k in self.info_state)):
+            raise ValueError(f"info_state: need a sequence of state field names out of {sorted(STATE_FIELDS)}, not {info_state!r}")
         self.vec = MiniWorldVecEnv(env_id, num_envs, **kwargs)
         self._first_next_seed = None
         if seeded and reset_seeds is not True:
@@ -149,13 +158,20 @@ class MiniWorldVectorEnv(VectorEnvBase):
         """gymnasium's batched info convention: one array per key (health / goal_pos: MiniWorldVecEnv.infos)."""
         return {k: self._out(v) for k, v in self.vec.infos().items()}
 
+    def _state_info(self, info):
+        """info_state: the named fields of the state the device holds, one state() call; copies (state()'s tensors are reused)"""
+        if self.info_state is not None:
+            for k, v in self.vec.state(self.info_state).items():
+                info[k] = self._out(v) if self.to_numpy else v.clone()
+        return info
+
     def reset(self, *, seed: int | None = None, options: dict | None = None):
         """Env i is seeded with seed + i (gymnasium's convention for an integer seed); with levels= every env starts a level of the
         bank and the seed is not used."""
         obs = self.vec.reset(seed)
         if self._first_next_seed is not None:       # (reset() lays out seed + N + i; the caller's first choices stand)
             self.vec.next_seed.copy_(self._first_next_seed)
-        return self._out(self._obs(obs)), {}
+        return self._out(self._obs(obs)), self._state_info({})
 
     def step(self, actions):
         torch = self.vec.torch
@@ -188,6 +204,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
             info["level"] = self._out(self.vec.played_level) if self.to_numpy else self.vec.played_level.clone()
         if self.vec.autoreset_mode == "seeds":
             info["seed"] = self._out(self._played_seed) if self.to_numpy else self._played_seed.clone()
+        self._state_info(info)
         return self._out(self._obs(obs)), self._out(rew), self._out(term.bool()), self._out(trunc.bool()), info
 
     def render(self):

@@ -1,0 +1,256 @@
+"""Device-side state views (mw_get_state_device / mw_set_state_where), host side, without a GPU: the header declares the two entry
+points, the ABI version did not move, the library exports them and refuses a null engine; what the masked write invalidates on the
+host (mw_policy.h, compiled from tests/hostcheck/state_view_policy.cpp); the index arithmetic the kernels share with the host
+(mw_state_view.h) as a stand-alone program under the address and undefined-behaviour sanitizers
+(tests/hostcheck/state_view_index.cpp); and MiniWorldVecEnv.state / set_state_where and the adapter's info_state over a stub engine."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_launch_policy_cpu import policy_lib
+from test_snapshot_cpu import _stub_engine
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "miniworld_amd", "csrc")
+NAMES = ("mw_get_state_device", "mw_set_state_where")
+FIELDS = ("agent_pos", "agent_dir", "cam", "light", "carrying", "step_count", "num_picked_up", "ent_kind", "ent_mesh", "ent_static",
+          "ent_pos", "ent_dir", "ent_geom", "extent")
+
+
+# ---------------------------------------------------------------------------------------------------------------- the interface
+
+def test_header_declares_the_entry_points():
+    from miniworld_amd import engine
+    header = open(os.path.join(ROOT, "include", "mwengine.h")).read()
+    assert re.search(r"int mw_get_state_device\(mw_engine \*e, int32_t first_env, int32_t count, const mw_state_view \*d_view, void \*stream\);", header)
+    assert re.search(r"int mw_set_state_where\(mw_engine \*e, const uint8_t \*d_mask, const mw_state_view \*d_view, void \*stream\);", header)
+    assert engine.ABI_VERSION == 4 and re.search(r"#define MW_ABI_VERSION 4\b", header)
+    assert set(NAMES) <= set(engine.EXPORTS)
+    # the comments cite the reference lines the calls replace
+    text = " ".join(header.split())
+    between = text[text.index("int mw_get_state(mw_engine *e"):text.index("int mw_set_state_where(")]
+    for cite in ("entity.py:455-515", "miniworld.py:576-578", "env.agent.pos", "env.agent.dir", "env.agent.carrying", "env.entities[k].pos", "env.step_count"):
+        assert cite in between, cite
+    # the view the two calls take is the one the host calls take: the binding's field order is the header's
+    struct = header[header.index("typedef struct {\n    double *agent_pos;"):header.index("} mw_state_view;")]
+    assert tuple(re.findall(r"\*(\w+);", struct)) == FIELDS == tuple(n for n, _ in engine.MwStateView._fields_) == tuple(engine.STATE_FIELDS)
+
+
+def test_library_exports_the_entry_points_and_refuses_a_null_engine():
+    from miniworld_amd import engine
+    engine.build_library()
+    lib = engine.load_library()
+    for name in NAMES:
+        assert hasattr(lib, name), name
+    rows = (C.c_double * 8)()
+    mask = (C.c_uint8 * 8)(*([1] * 8))
+    view = engine.MwStateView()
+    view.agent_dir = C.addressof(rows)
+    assert lib.mw_get_state_device(None, 0, 8, C.byref(view), None) == -1      # no engine: MW_E_INVALID
+    assert lib.mw_set_state_where(None, C.cast(mask, C.c_void_p), C.byref(view), None) == -1
+    assert lib.mw_get_state_device(None, 0, 0, None, None) == -1
+    assert lib.mw_set_state_where(None, None, None, None) == -1
+    assert not any(rows)
+    assert lib.mw_abi_version() == 4
+
+
+def test_the_new_unit_is_built_and_declared():
+    """mw_state_view.hip is one of the Makefile's sources, its two kernels are declared in mw_kernels.h, and the fields are written
+    out by name: the by-value argument structs are never indexed at run time."""
+    make = open(os.path.join(CSRC, "Makefile")).read()
+    assert re.search(r"^SRCS = (?:.*\\\n)*.*\bmw_state_view\.hip\b", make, re.M)
+    decl = open(os.path.join(CSRC, "mw_kernels.h")).read()
+    unit = open(os.path.join(CSRC, "mw_state_view.hip")).read()
+    for k in ("mw_state_get_kernel", "mw_state_set_where_kernel"):
+        assert re.search(r'extern "C" __global__ void ' + k + r"\(", decl), k
+        assert len(re.findall(r"__global__[^;{]*\b" + k + r"\(", unit)) == 1, k
+    assert len(re.findall(r"__global__", unit)) == 2
+    assert "__shared__" not in unit
+    index = open(os.path.join(CSRC, "mw_state_view.h")).read()
+    assert "MW_HD" in index and '#include "mw_hd.h"' in index
+    for f in FIELDS:
+        assert re.search(r"\bv\." + f + r"\b", index), f
+
+
+# ---------------------------------------------------------------------------------------------------------------- the policy
+
+def test_what_the_masked_write_invalidates():
+    """The held frame goes, the cache is NOT marked dirty (the kernel advances the epochs of the envs it writes) — as for
+    mw_reset_where and the masked load, and unlike the list forms and mw_set_state."""
+    lib = policy_lib(os.path.join(HERE, "hostcheck", "state_view_policy.cpp"), os.path.join(HERE, "hostcheck", "libmwstateview.so"))
+
+    def ask(what):
+        a, out = np.zeros(1, np.int64), np.zeros(8, np.int64)
+        assert lib.mwpol(what, a.ctypes.data, out.ctypes.data) == 2
+        return out[:2].tolist()
+    assert ask(0) == [1, 0]
+    assert ask(1) == [1, 0] and ask(2) == [1, 1]
+    # ... and the runtime takes its answer from there
+    host = open(os.path.join(CSRC, "mw_engine.hip")).read()
+    body = host[host.index("int mw_set_state_where("):host.index("int mw_set_gen_program(")]
+    assert "invalidate(e, set_state_where_invalidation());" in body
+    assert "world_changed" not in body and "Synchronize" not in body and "hipMemcpy" not in body
+
+
+# ---------------------------------------------------------------------------------------------------------------- the index header
+
+def test_index_header_under_the_sanitizers(tmp_path):
+    """The MW_HD index functions the kernels inline, run on the host by a program of its own (tests/hostcheck/state_view_index.cpp):
+    N = 5, E = 3, gather against state_xfer's transposition, scatter under the mask 1 0 1 0 1.  Built with the address and
+    undefined-behaviour sanitizers (their runtimes linked statically: the program needs nothing of the process that starts it)."""
+    src = os.path.join(HERE, "hostcheck", "state_view_index.cpp")
+    exe = str(tmp_path / "state_view_index")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-static-libasan", "-static-libubsan", src, "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "state_view_index: ok" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stdout + r.stderr
+
+
+# ---------------------------------------------------------------------------------------------------------------- the vec env
+
+def _names(calls):
+    return [c[0] for c in calls]
+
+
+def _view_ptrs(view_ref):
+    v = view_ref._obj
+    return {n: getattr(v, n) for n in FIELDS}
+
+
+def test_state_is_one_call_into_the_envs_own_tensors(monkeypatch):
+    import torch
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    lib = _stub_engine(monkeypatch)
+    vec = MiniWorldVecEnv("MiniWorld-Hallway-v0", 5)
+    E = vec.engine.E
+    n0 = len(lib.calls)
+    st = vec.state()
+    assert _names(lib.calls[n0:]) == ["mw_get_state_device"]
+    assert tuple(st) == ("agent_pos", "agent_dir", "carrying", "step_count", "ent_kind", "ent_pos", "ent_dir") == MiniWorldVecEnv.STATE_DEFAULT
+    shapes = {"agent_pos": (5, 3), "agent_dir": (5,), "carrying": (5,), "step_count": (5,), "ent_kind": (5, E), "ent_pos": (5, E, 3), "ent_dir": (5, E)}
+    for k, t in st.items():
+        assert tuple(t.shape) == shapes[k] and t.dtype == (torch.int32 if k in ("carrying", "step_count", "ent_kind") else torch.float64), k
+    args = lib.calls[-1][1]
+    assert args[1:3] == (0, 5)
+    ptrs = _view_ptrs(args[3])
+    assert {k for k, p in ptrs.items() if p} == set(st) and all(ptrs[k] == st[k].data_ptr() for k in st)
+    # the buffers are reused; a subset fetches the subset; every field can be named
+    again = vec.state()
+    assert all(again[k] is st[k] for k in st)
+    one = vec.state(["agent_dir"])
+    assert list(one) == ["agent_dir"] and one["agent_dir"] is st["agent_dir"]
+    assert {k for k, p in _view_ptrs(lib.calls[-1][1][3]).items() if p} == {"agent_dir"}
+    every = vec.state(FIELDS)
+    assert tuple(every) == FIELDS and tuple(every["ent_geom"].shape) == (5, E, 9) and tuple(every["light"].shape) == (5, 12)
+    n0 = len(lib.calls)
+    with pytest.raises(ValueError, match="agent_speed"):
+        vec.state(["agent_pos", "agent_speed"])
+    with pytest.raises(ValueError):
+        vec.state([])
+    assert lib.calls[n0:] == []
+    assert "same-step" in MiniWorldVecEnv.state.__doc__ and "next-step" in MiniWorldVecEnv.state.__doc__
+
+
+def test_set_state_where_writes_then_redraws(monkeypatch):
+    import torch
+    from miniworld_amd import engine
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    lib = _stub_engine(monkeypatch)
+    vec = MiniWorldVecEnv("MiniWorld-Hallway-v0", 5)
+    n0 = len(lib.calls)
+    out = vec.set_state_where([1, 0, 1, 0, 0], agent_dir=[0.5, 0.0, 1.5, 0.0, 0.0])
+    assert out is vec.obs
+    assert _names(lib.calls[n0:]) == ["mw_set_state_where", "mw_render"]
+    args = lib.calls[n0][1]
+    assert args[1] is not None
+    assert {k for k, p in _view_ptrs(args[2]).items() if p} == {"agent_dir"}
+    # device tensors are used as they are; a bool mask is copied to uint8
+    dirs = torch.zeros(5, dtype=torch.float64)
+    mask = torch.tensor([0, 1, 0, 0, 1], dtype=torch.uint8)
+    vec.set_state_where(mask, agent_dir=dirs)
+    args = lib.calls[-2][1]
+    assert args[1].value == mask.data_ptr() and _view_ptrs(args[2])["agent_dir"] == dirs.data_ptr()
+    vec.set_state_where(torch.tensor([True, False, False, False, False]), agent_pos=torch.zeros((5, 3), dtype=torch.float64))
+    assert _names(lib.calls[-2:]) == ["mw_set_state_where", "mw_render"]
+    # with a frame stack the reset path's refresh follows the frame
+    stacked = MiniWorldVecEnv("MiniWorld-Hallway-v0", 5, frame_stack=3)
+    n0 = len(lib.calls)
+    assert stacked.set_state_where([0, 0, 0, 0, 1], agent_dir=[0.0] * 5) is stacked.obs
+    assert _names(lib.calls[n0:]) == ["mw_set_state_where", "mw_render", "mw_stack_refresh"]
+    # a float32 tensor, a wrong shape and an unknown field each raise before any library call
+    n0 = len(lib.calls)
+    with pytest.raises(engine.EngineError, match="float64"):
+        vec.set_state_where(mask, agent_dir=torch.zeros(5, dtype=torch.float32))
+    with pytest.raises(engine.EngineError, match="shape"):
+        vec.set_state_where(mask, agent_pos=torch.zeros((5, 4), dtype=torch.float64))
+    with pytest.raises(engine.EngineError, match="shape"):
+        vec.set_state_where(mask, agent_dir=torch.zeros(4, dtype=torch.float64))
+    with pytest.raises(engine.EngineError):
+        vec.set_state_where(mask, carrying=torch.zeros(5, dtype=torch.int64))
+    with pytest.raises(engine.EngineError):
+        vec.set_state_where(mask, agent_pos=torch.zeros((3, 5), dtype=torch.float64).t())      # (the right shape, strided)
+    with pytest.raises(ValueError, match="agent_speed"):
+        vec.set_state_where(mask, agent_speed=torch.zeros(5, dtype=torch.float64))
+    with pytest.raises(ValueError):
+        vec.set_state_where(mask)
+    with pytest.raises(engine.EngineError):
+        vec.set_state_where(torch.zeros(4, dtype=torch.uint8), agent_dir=dirs)
+    with pytest.raises(engine.EngineError, match="float64"):
+        vec.engine.get_state_device({"agent_dir": torch.zeros(5, dtype=torch.float32)})
+    with pytest.raises(engine.EngineError):
+        vec.engine.get_state_device({"agent_pos": torch.zeros((5, 3), dtype=torch.float64)}, first=3, count=3)
+    with pytest.raises(engine.EngineError):
+        vec.engine.set_state_where(mask, {"nonsense": dirs})
+    with pytest.raises(engine.EngineError, match="no field"):       # (None = leave, as for set_state: a view of Nones names nothing)
+        vec.engine.set_state_where(mask, {"agent_dir": None, "agent_pos": None})
+    with pytest.raises(engine.EngineError, match="no field"):
+        vec.engine.get_state_device({"agent_dir": None})
+    assert lib.calls[n0:] == []
+    # the engine's sub-range read passes the range on
+    part = vec.engine.get_state_device({"agent_pos": torch.zeros((2, 3), dtype=torch.float64)}, first=3, count=2)
+    assert lib.calls[-1][0] == "mw_get_state_device" and lib.calls[-1][1][1:3] == (3, 2) and list(part) == ["agent_pos"]
+
+
+def test_seed_and_level_modes_keep_their_bookkeeping(monkeypatch):
+    from miniworld_amd import engine
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    lib = _stub_engine(monkeypatch)
+    monkeypatch.setattr(engine.Engine, "reset", lambda self, mask=None, seeds=None: lib.calls.append(("mw_reset", ())))
+    vec = MiniWorldVecEnv("MiniWorld-Hallway-v0", 4, autoreset="seeds")
+    vec.reset(seed=10)
+    before = (vec.episode_seed.tolist(), vec.next_seed.tolist())
+    vec.set_state_where([1, 1, 0, 0], agent_dir=[0.25] * 4)
+    assert (vec.episode_seed.tolist(), vec.next_seed.tolist()) == before
+
+
+def test_the_adapter_emits_info_state_on_request(monkeypatch):
+    import torch
+    from miniworld_amd.vector import MiniWorldVectorEnv
+    lib = _stub_engine(monkeypatch)
+    plain = MiniWorldVectorEnv("MiniWorld-Hallway-v0", 3)
+    _, info0 = plain.reset(seed=1)
+    *_, info1 = plain.step(torch.zeros(3, dtype=torch.int32))
+    assert info0 == {} and set(info1) == {"_final_info"}
+    assert "mw_get_state_device" not in _names(lib.calls)
+    envs = MiniWorldVectorEnv("MiniWorld-Hallway-v0", 3, info_state=("agent_pos", "agent_dir"))
+    n0 = len(lib.calls)
+    _, info = envs.reset(seed=1)
+    assert set(info) == {"agent_pos", "agent_dir"} and _names(lib.calls[n0:]).count("mw_get_state_device") == 1
+    n0 = len(lib.calls)
+    *_, info = envs.step(torch.zeros(3, dtype=torch.int32))
+    assert set(info) == {"_final_info", "agent_pos", "agent_dir"}
+    assert _names(lib.calls[n0:]) == ["mw_step", "mw_get_state_device"]
+    assert tuple(info["agent_pos"].shape) == (3, 3) and info["agent_pos"].dtype == torch.float64 and tuple(info["agent_dir"].shape) == (3,)
+    assert info["agent_pos"].data_ptr() != envs.vec.state(["agent_pos"])["agent_pos"].data_ptr()       # a copy: valid after the next step
+    host = MiniWorldVectorEnv("MiniWorld-Hallway-v0", 3, info_state=["carrying"], to_numpy=True)
+    *_, info = host.step([0, 0, 0])
+    assert isinstance(info["carrying"], np.ndarray) and info["carrying"].dtype == np.int32
+    for bad in ("agent_pos", ("agent_speed",), ()):
+        with pytest.raises(ValueError, match="info_state"):
+            MiniWorldVectorEnv("MiniWorld-Hallway-v0", 3, info_state=bad)
