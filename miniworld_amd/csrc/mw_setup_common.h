@@ -65,13 +65,27 @@ __device__ inline double ent_geom(const MwArgs &a, int env, int slot, int k)
     return a.egeom[((size_t)k * a.E + slot) * a.N + env];
 }
 
-// MiniWorldEnv.intersect (miniworld.py:937-963): 0 none, -1 wall, 1+slot entity, 1+E agent.
+// The reference's sums of radii as they evaluate under NumPy 2's promotion rules (the fixtures record the version: meta/numpy).
+// A MeshEnt's radius (Ball, Key, MedKit, the static meshes) comes from ObjMesh.max_coords and is an np.float32 (entity.py:141-147);
+// a Box's, a frame's and the agent's are Python floats.  Where a Python float meets an np.float32 it is converted to float32
+// first, and the sum is formed in float32, left to right as the reference writes it; the comparison with the float64 distance
+// (or the product with the float64 direction vector) widens the result again.  Decided by the entity's kind, never by its value.
+__device__ inline bool is_mesh(const MwArgs &a, int env, int slot) { return a.ekind[(size_t)slot * a.N + env] == MW_ENT_MESH; }
+__device__ inline double radii_sum(double r0, double r1, bool f32) { return f32 ? (double)((float)r0 + (float)r1) : r0 + r1; }
+__device__ inline double radii_sum(double r0, double r1, double more, bool f32)
+{
+    return f32 ? (double)(((float)r0 + (float)r1) + (float)more) : r0 + r1 + more;
+}
+
+// MiniWorldEnv.intersect (miniworld.py:937-963): 0 none, -1 wall, 1+slot entity, 1+E agent.  `radius` is the agent's (self_slot
+// -1: a Python float) or the radius of the entity self_slot, which the agent carries.
 // Every lane passes the same arguments; segments / entities are spread over the lanes.
 __device__ int intersect_wave(const StepCtx &c, int self_slot, double x, double z, double radius)
 {
     const MwArgs &a = c.a;
     const double *segs = a.segs + (size_t)c.set * a.max_segs * 4;
     const int ns = a.nsegs[c.set];
+    const bool rf32 = self_slot >= 0 && is_mesh(a, c.env, self_slot);
     bool hit = false;
     for (int i = c.lane; i < ns; i += 64) {
         const double sax = segs[i * 4 + 0], saz = segs[i * 4 + 1], sbx = segs[i * 4 + 2], sbz = segs[i * 4 + 3];
@@ -89,16 +103,17 @@ __device__ int intersect_wave(const StepCtx &c, int self_slot, double x, double 
     for (int base = 0; base < a.E; base += 64) {
         const int slot = base + c.lane;
         bool h = false;
-        if (slot < a.E && slot != self_slot && a.ekind[(size_t)slot * a.N + c.env] != MW_ENT_NONE) {
+        const int kind = slot < a.E && slot != self_slot ? a.ekind[(size_t)slot * a.N + c.env] : MW_ENT_NONE;
+        if (kind != MW_ENT_NONE) {
             const double dx = ent_pos(c, slot, 0) - x, dz = ent_pos(c, slot, 2) - z;
-            h = sqrt(dx * dx + dz * dz) < radius + ent_geom(a, c.env, slot, 7);
+            h = sqrt(dx * dx + dz * dz) < radii_sum(radius, ent_geom(a, c.env, slot, 7), rf32 || kind == MW_ENT_MESH);
         }
         const uint64_t m = ballot(h);
         if (m) return 1 + base + (__ffsll((unsigned long long)m) - 1);
     }
     if (self_slot >= 0) {
         const double dx = c.px - x, dz = c.pz - z;
-        if (sqrt(dx * dx + dz * dz) < radius + a.agent_radius) return 1 + a.E;
+        if (sqrt(dx * dx + dz * dz) < radii_sum(radius, a.agent_radius, rf32)) return 1 + a.E;
     }
     return 0;
 }
@@ -110,6 +125,7 @@ __device__ int intersect_lane(const StepCtx &c, int self_slot, double x, double 
     const MwArgs &a = c.a;
     const double *segs = a.segs + (size_t)c.set * a.max_segs * 4;
     const int ns = a.nsegs[c.set];
+    const bool rf32 = self_slot >= 0 && is_mesh(a, c.env, self_slot);
     bool hit = false;
 #pragma unroll 2
     for (int i = 0; i < ns; ++i) {      // independent iterations: two divisions / square roots in flight
@@ -126,13 +142,14 @@ __device__ int intersect_lane(const StepCtx &c, int self_slot, double x, double 
     }
     if (hit) return -1;
     for (int slot = 0; slot < a.E; ++slot) {
-        if (slot == self_slot || a.ekind[(size_t)slot * a.N + c.env] == MW_ENT_NONE) continue;
+        const int kind = a.ekind[(size_t)slot * a.N + c.env];
+        if (slot == self_slot || kind == MW_ENT_NONE) continue;
         const double dx = ent_pos(c, slot, 0) - x, dz = ent_pos(c, slot, 2) - z;
-        if (sqrt(dx * dx + dz * dz) < radius + ent_geom(a, c.env, slot, 7)) return 1 + slot;
+        if (sqrt(dx * dx + dz * dz) < radii_sum(radius, ent_geom(a, c.env, slot, 7), rf32 || kind == MW_ENT_MESH)) return 1 + slot;
     }
     if (self_slot >= 0) {
         const double dx = c.px - x, dz = c.pz - z;
-        if (sqrt(dx * dx + dz * dz) < radius + a.agent_radius) return 1 + a.E;
+        if (sqrt(dx * dx + dz * dz) < radii_sum(radius, a.agent_radius, rf32)) return 1 + a.E;
     }
     return 0;
 }
@@ -143,11 +160,11 @@ __device__ inline int intersect(const StepCtx &c, int self_slot, double x, doubl
     return PER_LANE ? intersect_lane(c, self_slot, x, z, radius) : intersect_wave(c, self_slot, x, z, radius);
 }
 
-// _get_carry_pos (miniworld.py:606-618)
+// _get_carry_pos (miniworld.py:606-618): agent.radius + ent.radius + max_forward_step, in float32 for a mesh entity
 __device__ inline void carry_pos(const StepCtx &c, int slot, double ax, double ay, double az, double dvx,
                                  double dvz, double out[3])
 {
-    const double dist = c.a.agent_radius + ent_geom(c.a, c.env, slot, 7) + c.a.max_forward_step;
+    const double dist = radii_sum(c.a.agent_radius, ent_geom(c.a, c.env, slot, 7), c.a.max_forward_step, is_mesh(c.a, c.env, slot));
     out[0] = ax + dvx * 1.05 * dist;
     out[1] = ay + 0.0 * 1.05 * dist;
     out[2] = az + dvz * 1.05 * dist;
@@ -155,11 +172,13 @@ __device__ inline void carry_pos(const StepCtx &c, int slot, double ax, double a
     out[1] = out[1] + 1.0 * (y > 0.0 ? y : 0.0);
 }
 
-// near(ent) (miniworld.py:965-975): 3D distance agent - entity below the two radii + 1.1 * max_forward_step
+// near(ent) (miniworld.py:965-975): 3D distance agent - entity below ent.radius + agent.radius + 1.1 * max_forward_step (the
+// product is formed in double and, for a mesh entity, rounded to float32 before it joins the sum)
 __device__ inline bool near_agent(const StepCtx &c, int slot)
 {
     const double dx = ent_pos(c, slot, 0) - c.px, dy = ent_pos(c, slot, 1) - c.py, dz = ent_pos(c, slot, 2) - c.pz;
-    return sqrt(dx * dx + dy * dy + dz * dz) < ent_geom(c.a, c.env, slot, 7) + c.a.agent_radius + 1.1 * c.a.max_forward_step;
+    return sqrt(dx * dx + dy * dy + dz * dz) <
+           radii_sum(ent_geom(c.a, c.env, slot, 7), c.a.agent_radius, 1.1 * c.a.max_forward_step, is_mesh(c.a, c.env, slot));
 }
 
 // The env rules that live in the placement program's tables (include/mwengine.h):
@@ -325,10 +344,7 @@ __device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writ
         double rew = 0.0;
         tr = step_count >= a.max_steps ? 1 : 0;
         if (a.task == MW_TASK_GOTO) {
-            const int g = a.goal_ent;
-            const double dx = ent_pos(c, g, 0) - c.px, dy = ent_pos(c, g, 1) - c.py, dz = ent_pos(c, g, 2) - c.pz;
-            const double dist = sqrt(dx * dx + dy * dy + dz * dz);
-            if (dist < ent_geom(a, env, g, 7) + a.agent_radius + 1.1 * a.max_forward_step) {
+            if (near_agent(c, a.goal_ent)) {
                 rew += 1.0 - 0.2 * ((double)step_count / (double)a.max_steps);
                 tm = 1;
             }
@@ -338,7 +354,7 @@ __device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writ
                 const double dx = ent_pos(c, g0, 0) - ent_pos(c, g1, 0), dy = ent_pos(c, g0, 1) - ent_pos(c, g1, 1),
                              dz = ent_pos(c, g0, 2) - ent_pos(c, g1, 2);
                 const double dist = sqrt(dx * dx + dy * dy + dz * dz);
-                if (dist < ent_geom(a, env, g0, 7) + ent_geom(a, env, g1, 7) + 1.1 * a.max_forward_step) {
+                if (dist < radii_sum(ent_geom(a, env, g0, 7), ent_geom(a, env, g1, 7), 1.1 * a.max_forward_step, is_mesh(a, env, g0) || is_mesh(a, env, g1))) {
                     rew += 1.0 - 0.2 * ((double)step_count / (double)a.max_steps);
                     tm = 1;
                 }

@@ -146,6 +146,8 @@ typedef struct {            /* physical part of an entity (miniworld.py:951-961)
     double height;
     int32_t alive;          /* 0 after removal from self.entities (pickupobjects.py:87) */
     int32_t is_static;
+    int32_t is_mesh;        /* a MeshEnt (Ball, Key, MedKit, static meshes): its radius is an np.float32 (entity.py:141-147) */
+    int32_t pad;
 } mwo_phys_ent;
 
 /* One MiniWorldEnv.step(action) + the env subclass' reward/termination rule

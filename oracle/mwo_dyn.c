@@ -12,11 +12,33 @@
  *              PickupObjects (pickupobjects.py:83-95)
  * The evaluation order of every floating-point expression follows numpy's (left to
  * right, reductions over (x, y, z) with y == 0 terms kept where they matter).
+ * So does the precision of the sums of radii (radii_sum below): float32 where a mesh
+ * entity's radius is an operand, under NumPy 2's promotion rules.
  * Pinned against the reference run under GL stubs: tests/golden/dyn_*.npz.
  */
 #include "mwo.h"
 #include <math.h>
 #include <string.h>
+
+/* The reference's sums of radii as NumPy 2 (NEP 50) evaluates them.  A MeshEnt's radius (Ball, Key,
+ * MedKit, the static meshes) derives from ObjMesh.max_coords and is an np.float32 (entity.py:141-147);
+ * a Box's, a frame's and the agent's are Python floats.  `python_float + np.float32` converts the
+ * Python float to float32 and adds in float32; the sum stays an np.float32 for the operands that
+ * follow, left to right.  The comparison with the float64 distance (:960, :975) and the product with
+ * the float64 direction vector (:612) widen the result again.  Decided by the entity's kind (is_mesh),
+ * never by whether a value happens to be representable. */
+static double radii_sum(double r0, double r1, int f32)
+{
+    return f32 ? (double)(float)((float)r0 + (float)r1) : r0 + r1;
+}
+
+static double radii_sum3(double r0, double r1, double more, int f32)
+{
+    if (!f32) return r0 + r1 + more;
+    float s = (float)r0 + (float)r1;
+    s = s + (float)more;
+    return (double)s;
+}
 
 int mwo_intersect(const mwo_agent_state *ag, const mwo_phys_ent *ents, int32_t self_idx,
                   double px, double pz, double radius, const double *segs, int32_t n_segs)
@@ -35,17 +57,19 @@ int mwo_intersect(const mwo_agent_state *ag, const mwo_phys_ent *ents, int32_t s
         double dist = sqrt(dx * dx + dz * dz);
         if (dist < radius) return -1;
     }
-    /* miniworld.py:951-961 — entities in list order, skipping self */
+    /* miniworld.py:951-961 — entities in list order, skipping self; `radius` is the agent's (a Python
+     * float) or, on behalf of a carried entity, that entity's */
+    const int rf32 = self_idx >= 0 && ents[self_idx].is_mesh;
     for (int i = 0; i < ag->n_ents; ++i) {
         if (i == self_idx || !ents[i].alive) continue;
         double dx = ents[i].pos[0] - px, dz = ents[i].pos[2] - pz;
         double d = sqrt(dx * dx + dz * dz);
-        if (d < radius + ents[i].radius) return 1 + i;
+        if (d < radii_sum(radius, ents[i].radius, rf32 || ents[i].is_mesh)) return 1 + i;
     }
     if (self_idx >= 0) {
         double dx = ag->pos[0] - px, dz = ag->pos[2] - pz;
         double d = sqrt(dx * dx + dz * dz);
-        if (d < radius + ag->radius) return 1 + ag->n_ents;
+        if (d < radii_sum(radius, ag->radius, rf32)) return 1 + ag->n_ents;
     }
     return 0;
 }
@@ -54,7 +78,7 @@ static void carry_pos(const mwo_agent_state *ag, const mwo_phys_ent *e, double a
                       double apz, double dvx, double dvz, double out[3])
 {
     /* miniworld.py:606-618 */
-    double dist = ag->radius + e->radius + ag->max_forward_step;
+    double dist = radii_sum3(ag->radius, e->radius, ag->max_forward_step, e->is_mesh);
     out[0] = apx + dvx * 1.05 * dist;
     out[1] = apy + 0.0 * 1.05 * dist;
     out[2] = apz + dvz * 1.05 * dist;
@@ -154,7 +178,7 @@ int mwo_step(mwo_agent_state *ag, mwo_phys_ent *ents, mwo_phys_ent *ents_at_rend
         const mwo_phys_ent *b = &ents[ag->goal_ent];
         double dx = b->pos[0] - ag->pos[0], dy = b->pos[1] - ag->pos[1], dz = b->pos[2] - ag->pos[2];
         double dist = sqrt(dx * dx + dy * dy + dz * dz);
-        if (dist < b->radius + ag->radius + 1.1 * ag->max_forward_step) {
+        if (dist < radii_sum3(b->radius, ag->radius, 1.1 * ag->max_forward_step, b->is_mesh)) {
             rew += 1.0 - 0.2 * ((double)ag->step_count / (double)ag->max_episode_steps);
             term = 1;
         }
@@ -164,7 +188,7 @@ int mwo_step(mwo_agent_state *ag, mwo_phys_ent *ents, mwo_phys_ent *ents_at_rend
             const mwo_phys_ent *e0 = &ents[ag->goal_ent], *e1 = &ents[ag->goal_ent2];
             double dx = e0->pos[0] - e1->pos[0], dy = e0->pos[1] - e1->pos[1], dz = e0->pos[2] - e1->pos[2];
             double dist = sqrt(dx * dx + dy * dy + dz * dz);
-            if (dist < e0->radius + e1->radius + 1.1 * ag->max_forward_step) {
+            if (dist < radii_sum3(e0->radius, e1->radius, 1.1 * ag->max_forward_step, e0->is_mesh || e1->is_mesh)) {
                 rew += 1.0 - 0.2 * ((double)ag->step_count / (double)ag->max_episode_steps);
                 term = 1;
             }

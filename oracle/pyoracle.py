@@ -84,7 +84,8 @@ class AgentState(C.Structure):
 
 class PhysEnt(C.Structure):
     _fields_ = [("pos", C.c_double * 3), ("dir", C.c_double), ("radius", C.c_double),
-                ("height", C.c_double), ("alive", C.c_int32), ("is_static", C.c_int32)]
+                ("height", C.c_double), ("alive", C.c_int32), ("is_static", C.c_int32),
+                ("is_mesh", C.c_int32), ("pad", C.c_int32)]
 
 
 TASK_NONE, TASK_GOTO, TASK_PICKUP, TASK_PUTNEXT = 0, 1, 2, 3
@@ -308,6 +309,7 @@ class Dynamics:
             self.ents[i].height = float(scene["ents_height"][i])
             self.ents[i].alive = 1
             self.ents[i].is_static = int(scene["ents_static"][i])
+            self.ents[i].is_mesh = int(int(scene["ents_kind"][i]) == 2)
         self.segs = np.ascontiguousarray(scene["wall_segs"], np.float64).reshape(-1, 4)
 
     def step(self, action, fwd_step=0.15, fwd_drift=0.0, turn_step=15.0):

@@ -19,6 +19,25 @@ def load_case(name):
     return s0, tr, meta, obs
 
 
+def carry_cases(prefix=""):
+    """Names of the carried-object fixtures (tests/golden/carry/, tools/gen_carry_fixtures.py) that start with `prefix`."""
+    return sorted(f[:-4] for f in os.listdir(os.path.join(GOLDEN, "carry")) if f.endswith(".npz") and f.startswith(prefix))
+
+
+def load_carry_case(name):
+    """(s0, tr, meta, poke) of a carried-object fixture; poke: the starting states of a threshold file's single steps, else empty."""
+    d = np.load(os.path.join(GOLDEN, "carry", name + ".npz"))
+    return tuple({k[len(p):]: d[k] for k in d.files if k.startswith(p)} for p in ("s0/", "tr/", "meta/", "poke/"))
+
+
+def poked_scene(s0, poke, k):
+    """Scene s0 with the starting state of threshold case k substituted."""
+    sc = dict(s0)
+    sc["agent_pos"], sc["agent_dir"], sc["agent_carrying"] = poke["agent_pos"][k], poke["agent_dir"][k], poke["carrying"][k]
+    sc["ents_pos"], sc["ents_dir"] = poke["ents_pos"][k], poke["ents_dir"][k]
+    return sc
+
+
 def golden_meshes(scene):
     """mesh name -> arrays dict for oracle.pyoracle.render, from tests/golden/meshes.npz."""
     d = np.load(os.path.join(GOLDEN, "meshes.npz"))
@@ -215,7 +234,10 @@ class EpisodeMirror:
         from miniworld_amd.scene import scene_from_env
         h = self.h
         self.sc = scene_from_env(h)
-        self.dyn = pyoracle.Dynamics(self.sc, self.task, int(min(float(h.max_episode_steps), 2 ** 30)),
+        ents = [e for e in h.entities if e is not h.agent]
+        # PutNext's rule (putnext.py:74-78) is about two of the boxes; every other task rule is about slot 0 or about none
+        g0, g1 = (ents.index(h.red_box), ents.index(h.yellow_box)) if hasattr(h, "red_box") else (0, -1)
+        self.dyn = pyoracle.Dynamics(self.sc, self.task, int(min(float(h.max_episode_steps), 2 ** 30)), goal_ent=g0, goal_ent2=g1,
                                      num_objs=len(self.sc["ents_kind"]), max_forward_step=float(h.max_forward_step),
                                      agent_radius=float(h.agent.radius))
         self.fresh = True

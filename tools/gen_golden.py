@@ -77,8 +77,12 @@ CASES = [
 ]
 
 
-def run_case(name, cls, kwargs, seed, n_actions, steps, frames, meshes):
-    env = refshim.make_env(cls, **kwargs)
+TR_KEYS = ("action", "pos", "dir", "carrying", "ents_pos", "ents_dir", "ents_alive", "reward", "term", "trunc", "fwd_step",
+           "fwd_drift", "turn_step")
+
+
+def log_param_draws(env):
+    """Wraps env.params.sample; returns the list that receives (name, value) of every draw (the caller clears it per step)."""
     log = []
     params = env.params.copy()
     orig = params.sample
@@ -89,60 +93,31 @@ def run_case(name, cls, kwargs, seed, n_actions, steps, frames, meshes):
         return v
     params.sample = sample
     env.params = params
-    env.reset(seed=seed)
-    s0 = refscene.scene_from_ref_env(env)
-    ents0 = [e for e in env.entities if e is not env.agent]
-    for e in ents0:
-        if hasattr(e, "mesh"):
-            mname = refscene.mesh_name_of(e)
-            base = mname.split("_")[0]
-            if base not in meshes:
-                meshes[base] = refscene.ref_mesh_arrays(e.mesh)
-            meshes["kd:" + mname] = meshes.get("kd:" + mname, np.array(
-                refscene.ref_mesh_arrays(e.mesh)["colors"][0, 0], np.float64))
+    return log
+
+
+def record_step(tr, env, ents0, a, rew, term, trunc, log):
+    """Appends the reference's state after env.step(a) to the lists of `tr` (ents0: the entity list at reset without the agent;
+    log: the step's parameter draws, the first three of which are step()'s own, miniworld.py:677-680)."""
     E = len(ents0)
-    rng = np.random.default_rng(1000 + seed)
-    tr = {k: [] for k in ("action", "pos", "dir", "carrying", "ents_pos", "ents_dir", "ents_alive",
-                          "reward", "term", "trunc", "fwd_step", "fwd_drift", "turn_step")}
-    scenes = {0: s0}
-    poke = np.array([-1, 0, 0, 0, 0], np.float64)
-    for t in range(steps):
-        if name.startswith("putnext_poke") and t == 40:
-            env.red_box.pos = env.yellow_box.pos + np.array([1.0, 0.0, 0.0])
-            poke = np.array([t, ents0.index(env.red_box), *env.red_box.pos], np.float64)
-        if isinstance(n_actions, list):
-            a = int(rng.choice(len(n_actions), p=n_actions))
-        else:
-            a = int(rng.integers(0, n_actions))
-        del log[:]
-        obs, rew, term, trunc, info = env.step(a)
-        step_params = dict(log[:3])
-        tr["action"].append(a)
-        tr["pos"].append(np.array(env.agent.pos, np.float64))
-        tr["dir"].append(float(env.agent.dir))
-        tr["carrying"].append(ents0.index(env.agent.carrying) if env.agent.carrying is not None else -1)
-        tr["ents_pos"].append(np.array([e.pos for e in ents0], np.float64).reshape(E, 3))
-        tr["ents_dir"].append(np.array([e.dir for e in ents0], np.float64))
-        tr["ents_alive"].append(np.array([any(e is x for x in env.entities) for e in ents0], np.int32))
-        tr["reward"].append(float(rew))
-        tr["term"].append(bool(term))
-        tr["trunc"].append(bool(trunc))
-        tr["fwd_step"].append(float(step_params["forward_step"]))
-        tr["fwd_drift"].append(float(step_params["forward_drift"]))
-        tr["turn_step"].append(float(step_params["turn_step"]))
-        if (t + 1) in frames:
-            sc = refscene.scene_from_ref_env(env)
-            # keep the original entity indexing: dead entities get kind 0
-            full = dict(s0)
-            full.update({k: sc[k] for k in ("agent_pos", "agent_dir", "agent_carrying", "step_count")})
-            alive = tr["ents_alive"][-1]
-            full["ents_pos"] = tr["ents_pos"][-1]
-            full["ents_dir"] = tr["ents_dir"][-1]
-            full["ents_kind"] = np.where(alive > 0, s0["ents_kind"], 0).astype(np.int32)
-            # CollectHealth re-places consumed kits at the end of self.entities: keep the live order
-            scenes[t + 1] = sc if cls == "CollectHealth" else full
-        if term or trunc:
-            break
+    step_params = dict(log[:3])
+    tr["action"].append(a)
+    tr["pos"].append(np.array(env.agent.pos, np.float64))
+    tr["dir"].append(float(env.agent.dir))
+    tr["carrying"].append(ents0.index(env.agent.carrying) if env.agent.carrying is not None else -1)
+    tr["ents_pos"].append(np.array([e.pos for e in ents0], np.float64).reshape(E, 3))
+    tr["ents_dir"].append(np.array([e.dir for e in ents0], np.float64))
+    tr["ents_alive"].append(np.array([any(e is x for x in env.entities) for e in ents0], np.int32))
+    tr["reward"].append(float(rew))
+    tr["term"].append(bool(term))
+    tr["trunc"].append(bool(trunc))
+    tr["fwd_step"].append(float(step_params["forward_step"]))
+    tr["fwd_drift"].append(float(step_params["forward_drift"]))
+    tr["turn_step"].append(float(step_params["turn_step"]))
+
+
+def pack_case(s0, tr, env, ents0, cls, kwargs, seed, n_actions, poke):
+    """The s0/, tr/ and meta/ keys of a fixture file."""
     out = {}
     for k, v in s0.items():
         out["s0/" + k] = v
@@ -162,6 +137,53 @@ def run_case(name, cls, kwargs, seed, n_actions, steps, frames, meshes):
         goal, goal2 = ents0.index(env.red_box), ents0.index(env.yellow_box)
     out["meta/goal_ent"], out["meta/goal_ent2"] = np.int32(goal), np.int32(goal2)
     out["meta/agent_radius"] = np.float64(env.agent.radius)
+    return out
+
+
+def run_case(name, cls, kwargs, seed, n_actions, steps, frames, meshes):
+    env = refshim.make_env(cls, **kwargs)
+    log = log_param_draws(env)
+    env.reset(seed=seed)
+    s0 = refscene.scene_from_ref_env(env)
+    ents0 = [e for e in env.entities if e is not env.agent]
+    for e in ents0:
+        if hasattr(e, "mesh"):
+            mname = refscene.mesh_name_of(e)
+            base = mname.split("_")[0]
+            if base not in meshes:
+                meshes[base] = refscene.ref_mesh_arrays(e.mesh)
+            meshes["kd:" + mname] = meshes.get("kd:" + mname, np.array(
+                refscene.ref_mesh_arrays(e.mesh)["colors"][0, 0], np.float64))
+    E = len(ents0)
+    rng = np.random.default_rng(1000 + seed)
+    tr = {k: [] for k in TR_KEYS}
+    scenes = {0: s0}
+    poke = np.array([-1, 0, 0, 0, 0], np.float64)
+    for t in range(steps):
+        if name.startswith("putnext_poke") and t == 40:
+            env.red_box.pos = env.yellow_box.pos + np.array([1.0, 0.0, 0.0])
+            poke = np.array([t, ents0.index(env.red_box), *env.red_box.pos], np.float64)
+        if isinstance(n_actions, list):
+            a = int(rng.choice(len(n_actions), p=n_actions))
+        else:
+            a = int(rng.integers(0, n_actions))
+        del log[:]
+        obs, rew, term, trunc, info = env.step(a)
+        record_step(tr, env, ents0, a, rew, term, trunc, log)
+        if (t + 1) in frames:
+            sc = refscene.scene_from_ref_env(env)
+            # keep the original entity indexing: dead entities get kind 0
+            full = dict(s0)
+            full.update({k: sc[k] for k in ("agent_pos", "agent_dir", "agent_carrying", "step_count")})
+            alive = tr["ents_alive"][-1]
+            full["ents_pos"] = tr["ents_pos"][-1]
+            full["ents_dir"] = tr["ents_dir"][-1]
+            full["ents_kind"] = np.where(alive > 0, s0["ents_kind"], 0).astype(np.int32)
+            # CollectHealth re-places consumed kits at the end of self.entities: keep the live order
+            scenes[t + 1] = sc if cls == "CollectHealth" else full
+        if term or trunc:
+            break
+    out = pack_case(s0, tr, env, ents0, cls, kwargs, seed, n_actions, poke)
     mesh_arrays = {}
     for mname in [str(m) for m in s0["mesh_names"]]:
         base = mname.split("_")[0]
