@@ -418,6 +418,37 @@ int mw_step_repeat(mw_engine *e, const int32_t *d_actions, int32_t repeat, uint8
 int mw_step_plan(mw_engine *e, const int32_t *d_plans /* [horizon][N] */, int32_t horizon,
                  uint8_t *d_obs, float *d_depth, float *d_reward, float *d_step_reward /* [horizon][N] or NULL */,
                  uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, void *stream);
+/* Rollout traces: mw_step_plan, and where the agent was after each of its sub-steps — what a planner turns into a dense cost on the
+ * device (the distance to a goal, a visitation count, an archive's cell key) where the rewards are sparse.  The fields are those of
+ * env.agent and env.entities that step() itself writes (miniworld.py:670-730; the carried entity follows the agent, entity.py:455-515)
+ * and the frame's tail never touches.  A host struct of DEVICE pointers; any may be NULL, not all:
+ *   agent_pos  double[horizon][N][3]  env.agent.pos as step() k leaves it
+ *   agent_dir  double[horizon][N]     env.agent.dir
+ *   carrying   int32[horizon][N]      the carried slot or -1, as the step stores it: a MW_TASK_PICKUP object that leaves the list reads -1
+ *   ent_pos    double[horizon][N][3]  the position of ONE slot, ent_slot (0 .. max_ents - 1) — the goal box, or the box being carried.
+ *                                     The slot's kind is not consulted: a removed slot keeps its last position.
+ * Row k of env i is the state the env is in when its sub-step k (0-based) has run its physics and its rule, before any auto-reset: each
+ * row has mw_state_view's row layout and holds, bit for bit, what mw_get_state_device returns for that field behind a single mw_step
+ * of a MW_AUTORESET_OFF engine in the same state.  The terminal sub-step's row is the terminal state in every auto-reset mode (the world a
+ * same-step engine installs on it never shows).  Rows k >= d_nsteps[i] repeat row d_nsteps[i] - 1 — the env stays where it ended, a
+ * cost summed over the horizon needs no mask —, and all rows of an env that executed 0 sub-steps (next-step, entered with
+ * reset_pending) hold the state it entered the call with.  Exactly `horizon` rows of N columns are written, by the step kernel itself
+ * (the trace kernels, mw_setup_trace*.hip: the plan kernels with the stores added; mw_step_plan keeps its own).
+ * Everything else is mw_step_plan's contract, clause for clause — drawn or frameless, final buffers, reset seeds, the stack, frame
+ * reuse and the frame cache: state, stream, frames, rewards, flags, d_nsteps and d_step_reward are bit for bit what mw_step_plan returns.
+ * MW_E_INVALID, nothing launched and nothing touched: `trace` NULL or without a field; ent_pos with ent_slot out of range; ent_pos
+ * on a MW_TASK_COLLECT engine (a kit's respawn belongs to the frame's tail, so where it is after sub-step k would depend on whether a
+ * frame follows); whatever mw_step_plan refuses. */
+typedef struct {            /* host struct, DEVICE pointers; any may be NULL, not all */
+    double  *agent_pos;     /* [horizon][N][3] */
+    double  *agent_dir;     /* [horizon][N]    */
+    int32_t *carrying;      /* [horizon][N]    */
+    double  *ent_pos;       /* [horizon][N][3], slot ent_slot */
+    int32_t  ent_slot;
+} mw_plan_trace;
+int mw_step_plan_trace(mw_engine *e, const int32_t *d_plans, int32_t horizon, uint8_t *d_obs, float *d_depth,
+                       float *d_reward, float *d_step_reward, uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps,
+                       const mw_plan_trace *trace, void *stream);
 /* Final observations of a MW_AUTORESET_SAME_STEP engine (Gymnasium's info["final_obs"] of a same-step vector env, SB3's
  * info["terminal_observation"]): d_final_obs and d_final_depth are device buffers shaped like mw_step's d_obs / d_depth (N rows in
  * the layout of mw_set_obs_layout at the time of the step).  With d_final_obs non-null, every later mw_step writes the TERMINAL

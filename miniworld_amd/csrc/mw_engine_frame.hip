@@ -63,7 +63,8 @@ auto tile_kernel_of(bool big, bool depth, bool general, bool ragged, bool mesh, 
 
 // The buffers of one call, and which step kernels it runs: mw_step's (repeat = horizon = 0), mw_step_repeat's (repeat > 0: up to `repeat`
 // sub-steps per env with its action, the executed count into nsteps) or mw_step_plan's (horizon > 0: `actions` is the plans,
-// [horizon][N], and each sub-step's own reward goes to step_reward) — the same launch shape for all three.  A render has no actions
+// [horizon][N], and each sub-step's own reward goes to step_reward; with `trace`, mw_step_plan_trace's: the trace kernels store each
+// sub-step's row of it) — the same launch shape for all of them.  A render has no actions
 // and no outputs.  reward, term and trunc are never null behind resolve_outputs: everything downstream reads them as they stand.
 struct Call {
     const int32_t *actions = nullptr;
@@ -72,6 +73,7 @@ struct Call {
     hipStream_t st = nullptr;
     int repeat = 0; int32_t *nsteps = nullptr;
     int horizon = 0; float *step_reward = nullptr;
+    const mw_plan_trace *trace = nullptr;
 };
 // the one place where the outputs a caller did not ask for get the engine's scratch (step_frames, the entry point of every step)
 void resolve_outputs(const mw_engine *e, Call &c)
@@ -208,7 +210,10 @@ void launch_k1(mw_engine *e, const MwArgs &ak, const Call &c, bool frameless)
     const int refill_blocks = (e->spare_mode && !side_refills(e)) ? (N + 63) / 64 : 0;
     const int lanes = dense_lanes_of(e);
     const dim3 grid(env_blocks(N, lanes) + refill_blocks);
-    if (c.horizon > 0)
+    if (c.horizon > 0 && c.trace)
+        hipLaunchKernelGGL(MW_K1(e, lanes, mw_step_trace), grid, dim3(64), 0, c.st, ak, lanes, c.actions, c.reward, c.term, c.trunc, c.horizon, c.nsteps, c.step_reward,
+                           frameless ? 1 : 0, *c.trace);
+    else if (c.horizon > 0)
         hipLaunchKernelGGL(MW_K1(e, lanes, mw_step_plan), grid, dim3(64), 0, c.st, ak, lanes, c.actions, c.reward, c.term, c.trunc, c.horizon, c.nsteps, c.step_reward,
                            frameless ? 1 : 0);
     else if (c.repeat > 0) hipLaunchKernelGGL(MW_K1(e, lanes, mw_step_repeat), grid, dim3(64), 0, c.st, ak, lanes, c.actions, c.reward, c.term, c.trunc, c.repeat, c.nsteps);
@@ -464,7 +469,8 @@ static int step_frameless(mw_engine *e, const Call &c)
     return MW_OK;
 }
 
-// mw_step (the plain step kernels), mw_step_repeat (the repeat kernels) and mw_step_plan (the plan kernels; c.actions: the plans)
+// mw_step (the plain step kernels), mw_step_repeat (the repeat kernels), mw_step_plan and mw_step_plan_trace (the plan and the trace
+// kernels; c.actions: the plans)
 static int step_frames(mw_engine *e, const char *what, Call c)
 {
     ON_DEVICE(e);
@@ -504,6 +510,24 @@ int mw_step_plan(mw_engine *e, const int32_t *d_plans, int32_t horizon, uint8_t 
     if (horizon < 1 || horizon > MW_MAX_PLAN) return fail(e, MW_E_INVALID, "mw_step_plan: horizon %d outside 1 .. %d", (int)horizon, MW_MAX_PLAN);
     if (d_depth && !d_obs) return fail(e, MW_E_INVALID, "mw_step_plan: d_depth without d_obs (a frameless call draws nothing)");
     return step_frames(e, "mw_step_plan", Call{d_plans, d_obs, d_depth, d_reward, d_term, d_trunc, (hipStream_t)stream, 0, d_nsteps, horizon, d_step_reward});
+}
+
+int mw_step_plan_trace(mw_engine *e, const int32_t *d_plans, int32_t horizon, uint8_t *d_obs, float *d_depth, float *d_reward,
+                       float *d_step_reward, uint8_t *d_term, uint8_t *d_trunc, int32_t *d_nsteps, const mw_plan_trace *trace, void *stream)
+{
+    if (!e) return MW_E_INVALID;
+    if (horizon < 1 || horizon > MW_MAX_PLAN) return fail(e, MW_E_INVALID, "mw_step_plan_trace: horizon %d outside 1 .. %d", (int)horizon, MW_MAX_PLAN);
+    if (d_depth && !d_obs) return fail(e, MW_E_INVALID, "mw_step_plan_trace: d_depth without d_obs (a frameless call draws nothing)");
+    if (!trace || !(trace->agent_pos || trace->agent_dir || trace->carrying || trace->ent_pos))
+        return fail(e, MW_E_INVALID, "mw_step_plan_trace: no trace field asked for (mw_step_plan is the call without a trace)");
+    if (trace->ent_pos && (trace->ent_slot < 0 || trace->ent_slot >= e->cfg.max_ents))
+        return fail(e, MW_E_INVALID, "mw_step_plan_trace: ent_slot %d outside 0 .. %d", (int)trace->ent_slot, (int)e->cfg.max_ents - 1);
+    if (trace->ent_pos && e->cfg.task == MW_TASK_COLLECT)
+        return fail(e, MW_E_INVALID, "mw_step_plan_trace: ent_pos on a MW_TASK_COLLECT engine (a kit's respawn belongs to the frame's tail: where it is "
+                                     "after a sub-step depends on whether a frame follows)");
+    Call c{d_plans, d_obs, d_depth, d_reward, d_term, d_trunc, (hipStream_t)stream, 0, d_nsteps, horizon, d_step_reward};
+    c.trace = trace;
+    return step_frames(e, "mw_step_plan_trace", c);
 }
 
 int mw_set_final_obs(mw_engine *e, uint8_t *d_final_obs, float *d_final_depth)

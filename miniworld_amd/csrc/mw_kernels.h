@@ -35,6 +35,13 @@ extern "C" __global__ void mw_step_plan_kernel(MW_K1_PLAN_ARGS);
 extern "C" __global__ void mw_step_plan_pcg_kernel(MW_K1_PLAN_ARGS);
 extern "C" __global__ void mw_step_plan_dense_kernel(MW_K1_PLAN_ARGS);
 extern "C" __global__ void mw_step_plan_dense_pcg_kernel(MW_K1_PLAN_ARGS);
+// ... and mw_step_plan_trace's (mw_setup_trace*.hip; step_env_repeat with PLAN and TRACE): the plan kernels' arguments and the caller's
+// trace by value — device pointers, [horizon][N] rows, null = field not asked for; row k of env i := the state sub-step k left
+#define MW_K1_TRACE_ARGS MW_K1_PLAN_ARGS, mw_plan_trace trace
+extern "C" __global__ void mw_step_trace_kernel(MW_K1_TRACE_ARGS);
+extern "C" __global__ void mw_step_trace_pcg_kernel(MW_K1_TRACE_ARGS);
+extern "C" __global__ void mw_step_trace_dense_kernel(MW_K1_TRACE_ARGS);
+extern "C" __global__ void mw_step_trace_dense_pcg_kernel(MW_K1_TRACE_ARGS);
 
 // reset, spare refill, CollectHealth respawn, same-step install, spare take-over (mw_reset.hip, mw_reset_pcg.hip)
 extern "C" __global__ void mw_reset_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all, int mark_refill);

@@ -248,6 +248,48 @@ struct SubStep {
     bool clean;             // the writer lane's frame_clean value of this sub-step
 };
 
+// TRACE (mw_step_plan_trace's kernels, mw_setup_trace*.hip): row `row` of env `env` in the caller's trace arrays (mw_plan_trace,
+// mwengine.h: [horizon][N] rows in mw_state_view's row layout, any field may be null) := the agent's pose, the carried slot as the
+// step stores it and the position of slot ent_slot — from the writer lane's registers where the step has them (`live`: the slot whose
+// position is in cpos, or -1), else from the engine's arrays.
+__device__ inline void trace_store(const MwArgs &a, const mw_plan_trace &t, int row, int env, double px, double py, double pz, double dir, int carry,
+                                   int live, const double *cpos)
+{
+    const size_t r = (size_t)row * a.N + env;
+    if (t.agent_pos) { t.agent_pos[r * 3 + 0] = px; t.agent_pos[r * 3 + 1] = py; t.agent_pos[r * 3 + 2] = pz; }
+    if (t.agent_dir) t.agent_dir[r] = dir;
+    if (t.carrying) t.carrying[r] = carry;
+    if (t.ent_pos) {
+        const int s = t.ent_slot;
+        const bool held = live == s;
+        t.ent_pos[r * 3 + 0] = held ? cpos[0] : a.epos[((size_t)0 * a.E + s) * a.N + env];
+        t.ent_pos[r * 3 + 1] = held ? cpos[1] : a.epos[((size_t)1 * a.E + s) * a.N + env];
+        t.ent_pos[r * 3 + 2] = held ? cpos[2] : a.epos[((size_t)2 * a.E + s) * a.N + env];
+    }
+}
+// ... and rows k0 .. k1 - 1 := row src: the rows of the sub-steps an env did not execute repeat the state it stopped in
+__device__ inline void trace_fill(const MwArgs &a, const mw_plan_trace &t, int src, int k0, int k1, int env)
+{
+    if (k0 >= k1) return;
+    const size_t N = (size_t)a.N, s = (size_t)src * N + env;
+    if (t.agent_pos) {
+        const double x = t.agent_pos[s * 3 + 0], y = t.agent_pos[s * 3 + 1], z = t.agent_pos[s * 3 + 2];
+        for (int k = k0; k < k1; ++k) { double *d = t.agent_pos + ((size_t)k * N + env) * 3; d[0] = x; d[1] = y; d[2] = z; }
+    }
+    if (t.agent_dir) {
+        const double v = t.agent_dir[s];
+        for (int k = k0; k < k1; ++k) t.agent_dir[(size_t)k * N + env] = v;
+    }
+    if (t.carrying) {
+        const int32_t v = t.carrying[s];
+        for (int k = k0; k < k1; ++k) t.carrying[(size_t)k * N + env] = v;
+    }
+    if (t.ent_pos) {
+        const double x = t.ent_pos[s * 3 + 0], y = t.ent_pos[s * 3 + 1], z = t.ent_pos[s * 3 + 2];
+        for (int k = k0; k < k1; ++k) { double *d = t.ent_pos + ((size_t)k * N + env) * 3; d[0] = x; d[1] = y; d[2] = z; }
+    }
+}
+
 // One env's step, the body of both K1 forms (mw_setup.hip: one wavefront per env, PER_LANE = false, the 64 lanes share the
 // collision tests; mw_setup_dense.hip: several envs per wavefront, PER_LANE = true, each lane tests alone).  Every lane of the
 // env calls it with the same env and evaluates the step; `writer`, one lane of the env, writes its state and flags.
@@ -258,10 +300,13 @@ struct SubStep {
 // The frame itself — camera, transform, lighting, clipping, triangle setup — is the geometry kernel's (mw_geom.hip).
 // REPEAT: one sub-step of mw_step_repeat — the same step, except that reward, flags and the frame_clean byte are the loop's to
 // write, once per call (step_env_repeat).
-template <bool PER_LANE, bool REPEAT = false>
+// TRACE: the writer lane also stores row trace_row of the caller's trace (trace_store) beside the env's state — the state the sub-step
+// leaves, before the install site below replaces it with the next episode's; for a pending next-step reset, the state the call found.
+// A compile-time constant like REPEAT: the two arguments behind it do not exist in the kernels that leave it false.
+template <bool PER_LANE, bool REPEAT = false, bool TRACE = false>
 __device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writer, const int32_t *__restrict__ actions,
                                 float *__restrict__ reward, uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
-                                unsigned char *gen_ws, int *s_claim)
+                                unsigned char *gen_ws, int *s_claim, const mw_plan_trace *trace = nullptr, int trace_row = 0)
 {
     StepCtx c{a, env, lane, a.shared_geom ? 0 : env, 0, 0, 0, 0, 0, -1, -1, {0, 0, 0}, 0};
     c.px = a.ax[env]; c.py = a.ay[env]; c.pz = a.az[env]; c.dir = a.adir[env];
@@ -405,6 +450,7 @@ __device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writ
                 a.edir[(size_t)c.live * a.N + env] = c.cdir;
             }
             a.carry[env] = remove_slot >= 0 ? -1 : c.carry;
+            if (TRACE) trace_store(a, *trace, trace_row, env, c.px, c.py, c.pz, c.dir, remove_slot >= 0 ? -1 : c.carry, c.live, c.cpos);
             if ((tm | tr) && a.autoreset != MW_AUTORESET_OFF && a.generator != MW_GEN_NONE) {
                 mw::keep_final_info(a, env);
                 if (a.autoreset == MW_AUTORESET_NEXT_STEP) a.reset_pending[env] = 1;
@@ -414,6 +460,8 @@ __device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writ
         reward[env] = 0.0f;
         term[env] = 0;
         trunc[env] = 0;
+    } else if (TRACE && writer) {
+        trace_store(a, *trace, trace_row, env, c.px, c.py, c.pz, c.dir, c.carry, c.live, c.cpos);
     }
     // The one install site of the next world.  Same-step auto-reset: on the step that ends the episode, so that the observation
     // returned with done = 1 is the first one of the next episode.  Next-step auto-reset: on the step after it, the reference's
@@ -474,11 +522,16 @@ __device__ inline SubStep step_env(const MwArgs &a, int env, int lane, bool writ
 // the respawn kernel of a drawn call would have found in pending_remove: nothing where that sub-step installed a world (step_env
 // leaves -1 there), the removal or the respawn on a terminal sub-step that installed none — and frame_clean is 0.  Both arguments are
 // compile-time constants of the repeat kernels, whose code they leave as it was.
-template <bool PER_LANE, bool PLAN = false>
+//
+// TRACE (with PLAN): mw_step_plan_trace's — every executed sub-step stores its row of `trace` (step_env), and so does the sub-step that
+// found a pending next-step reset; the rows behind an env's last one, inside the loop where other envs of the wavefront are still
+// stepping and behind it, repeat that row (the pattern of step_reward's zero fill).  A compile-time constant of the repeat and plan
+// kernels, whose code it leaves as it was.
+template <bool PER_LANE, bool PLAN = false, bool TRACE = false>
 __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool writer, const int32_t *__restrict__ actions, int repeat,
                                        float *__restrict__ reward, uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
                                        int32_t *__restrict__ nsteps, float *__restrict__ step_reward, bool frameless, unsigned char *gen_ws,
-                                       int *s_claim)
+                                       int *s_claim, const mw_plan_trace *trace = nullptr)
 {
     double sum = 0.0;
     int n = 0, tm = 0, tr = 0;
@@ -488,7 +541,8 @@ __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool 
         if (!ballot(active)) break;
         float rew_k = 0.0f;
         if (active) {
-            const SubStep s = step_env<PER_LANE, true>(a, env, lane, writer, PLAN ? actions + (size_t)k * a.N : actions, reward, term, trunc, gen_ws, s_claim);
+            const SubStep s = step_env<PER_LANE, true, TRACE>(a, env, lane, writer, PLAN ? actions + (size_t)k * a.N : actions, reward, term, trunc, gen_ws, s_claim,
+                                                              trace, k);
             if (s.ran) {
                 sum += s.rew;
                 ++n;
@@ -506,6 +560,8 @@ __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool 
                     a.pending_remove[env] = MW_REMOVE_APPLIED;
                 }
             }
+        } else if (TRACE && writer) {
+            trace_fill(a, *trace, k - 1, k, k + 1, env);        // (an env is active at k = 0)
         }
         if (PLAN) {
             if (writer && step_reward) step_reward[(size_t)k * a.N + env] = rew_k;
@@ -521,6 +577,7 @@ __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool 
     if (writer) {
         if (PLAN && step_reward)
             for (int k = rows; k < repeat; ++k) step_reward[(size_t)k * a.N + env] = 0.0f;
+        if (TRACE) trace_fill(a, *trace, rows - 1, rows, repeat, env);
         reward[env] = (float)sum;
         term[env] = (uint8_t)tm;
         trunc[env] = (uint8_t)tr;
@@ -541,7 +598,12 @@ __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool 
 // re-includes them (mw_setup_repeat*.hip), as mw_step_repeat's kernels: the same grid mapping and refill blocks around the
 // sub-step loop, `repeat` and `nsteps` as two more kernel parameters (mw_kernels.h).
 // With MW_K1_PLAN (mw_setup_plan*.hip) they compile as mw_step_plan's: the loop with PLAN set, `actions` the [horizon][N] plans.
-#if defined(MW_K1_PLAN)
+// With MW_K1_TRACE beside it (mw_setup_trace*.hip), as mw_step_plan_trace's: TRACE set too, the caller's trace one more parameter.
+#if defined(MW_K1_PLAN) && defined(MW_K1_TRACE)
+#define MW_K1_PARAMS MW_K1_TRACE_ARGS
+#define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) \
+    step_env_repeat<PER_LANE, true, true>(a, env, lane, writer, actions, horizon, reward, term, trunc, nsteps, step_reward, frameless != 0, ws, claim, &trace)
+#elif defined(MW_K1_PLAN)
 #define MW_K1_PARAMS MW_K1_PLAN_ARGS
 #define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) \
     step_env_repeat<PER_LANE, true>(a, env, lane, writer, actions, horizon, reward, term, trunc, nsteps, step_reward, frameless != 0, ws, claim)

@@ -39,7 +39,7 @@ PATH_TILE, PATH_QUAD, PATH_QUAD_MESH, PATH_GENERIC = 0, 1, 2, 3
 EXPORTS = [
     "mw_create", "mw_destroy", "mw_last_error", "mw_upload_texture", "mw_upload_mesh",
     "mw_set_geometry", "mw_get_geometry", "mw_set_state", "mw_get_state", "mw_set_step_params", "mw_reset",
-    "mw_step", "mw_step_repeat", "mw_step_plan", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_frame_cache", "mw_get_frame_source", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
+    "mw_step", "mw_step_repeat", "mw_step_plan", "mw_step_plan_trace", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_frame_cache", "mw_get_frame_source", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
     "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
     "mw_selftest_sincosf",
     "mw_set_frame_stack", "mw_stack_refresh", "mw_stack_window",
@@ -122,6 +122,19 @@ class MwStateView(C.Structure):
         "ent_kind", "ent_mesh", "ent_static", "ent_pos", "ent_dir", "ent_geom", "extent")]
 
 
+class MwPlanTrace(C.Structure):
+    _fields_ = [("agent_pos", C.c_void_p), ("agent_dir", C.c_void_p), ("carrying", C.c_void_p), ("ent_pos", C.c_void_p), ("ent_slot", C.c_int32)]
+
+
+# the fields of a rollout trace (mw_plan_trace): name -> (dtype, per-env shape); ent_pos is ONE slot's position
+TRACE_FIELDS = {
+    "agent_pos": (np.float64, (3,)),
+    "agent_dir": (np.float64, ()),
+    "carrying": (np.int32, ()),
+    "ent_pos": (np.float64, (3,)),
+}
+
+
 # name -> (dtype, per-env shape as a function of max_ents)
 STATE_FIELDS = {
     "agent_pos": (np.float64, lambda E: (3,)),
@@ -196,6 +209,7 @@ def load_library():
     L.mw_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.mw_step_repeat.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mw_step_plan.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mw_step_plan_trace.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(MwPlanTrace), vp]
     L.mw_render.argtypes = [vp, vp, vp, vp]
     L.mw_render_top.argtypes = [vp, vp, vp, i32, vp]
     L.mw_render_view.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
@@ -512,6 +526,42 @@ class Engine:
         needed; the outputs are checked as for step_repeat(), `step_reward` (float32, at least T * N elements: rows 0 .. T - 1 of a
         [*, N] buffer) receives every sub-step's own reward.  obs=None is the frameless call: nothing is drawn, `depth` must be None.
         A wrong shape or T outside 1 .. MAX_PLAN raises before the library is called."""
+        self._step_plan(plans, obs, depth, reward, step_reward, term, trunc, nsteps, None)
+
+    def step_plan_trace(self, plans, obs, depth=None, reward=None, step_reward=None, term=None, trunc=None, nsteps=None, *, trace: dict,
+                        ent_slot: int = 0):
+        """step_plan() with a trace (include/mwengine.h: mw_step_plan_trace): `trace` maps names of TRACE_FIELDS to device tensors
+        [R, N, *field shape] with R >= T rows — "agent_pos" float64[R, N, 3], "agent_dir" float64[R, N], "carrying" int32[R, N],
+        "ent_pos" float64[R, N, 3] (the position of slot `ent_slot`) — whose row k receives every env's state after its sub-step k,
+        rows an env did not execute repeating its last one; rows T .. R - 1 are not written.  Everything else is step_plan()'s.
+        Checked like a state view's tensors (dtype, device, contiguity), never converted: an unknown name, a wrong tensor, no field
+        at all, ent_pos with a slot outside 0 .. max_ents - 1 or on a TASK_COLLECT engine raise before the library is called."""
+        import torch
+        if not trace or all(t is None for t in trace.values()):
+            raise EngineError("step_plan_trace: no trace field named")
+        view = MwPlanTrace()
+        T = int(plans.shape[0]) if plans.dim() == 2 else 0
+        for name, t in trace.items():
+            if name not in TRACE_FIELDS:
+                raise EngineError(f"{name!r} is no trace field; have {sorted(TRACE_FIELDS)}")
+            if t is None:
+                continue
+            dt, shp = TRACE_FIELDS[name]
+            dtype = torch.float64 if dt is np.float64 else torch.int32
+            if not torch.is_tensor(t) or t.dim() != 2 + len(shp) or tuple(t.shape[1:]) != (self.N,) + shp or t.shape[0] < T:
+                raise EngineError(f"trace {name}: need a {dtype} tensor of shape [>= {T}, {self.N}{''.join(', %d' % d for d in shp)}] on {self.device}, got "
+                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            setattr(view, name, self._dev_tensor(t, "trace " + name, dtype, t.numel()).data_ptr())
+        if view.ent_pos:
+            if isinstance(ent_slot, bool) or not isinstance(ent_slot, (int, np.integer)) or not 0 <= ent_slot < self.cfg.max_ents:
+                raise EngineError(f"ent_slot: need an integer in 0 .. {self.cfg.max_ents - 1}, got {ent_slot!r}")
+            if self.cfg.task == TASK_COLLECT:
+                raise EngineError("trace ent_pos on a TASK_COLLECT engine: a kit's respawn belongs to the frame's tail")
+            view.ent_slot = int(ent_slot)
+        self._step_plan(plans, obs, depth, reward, step_reward, term, trunc, nsteps, view)
+
+    def _step_plan(self, plans, obs, depth, reward, step_reward, term, trunc, nsteps, trace):
+        """step_plan() and step_plan_trace(): the checks, then the one library call (trace: the filled MwPlanTrace or None)."""
         import torch
         if plans.dim() != 2 or plans.shape[1] != self.N or not 1 <= plans.shape[0] <= MAX_PLAN:
             raise EngineError(f"plans: need an integer tensor [T, {self.N}] with T in 1 .. {MAX_PLAN}, got {tuple(plans.shape)}")
@@ -525,6 +575,10 @@ class Engine:
         if step_reward is not None and (step_reward.device != self.device or step_reward.dtype != torch.float32 or
                                         not step_reward.is_contiguous() or step_reward.numel() < horizon * self.N):
             raise EngineError(f"step_reward: need a contiguous float32 tensor of at least {horizon * self.N} elements on {self.device}")
+        if trace is not None:
+            self._check(self.lib.mw_step_plan_trace(self.h, _ptr(plans), horizon, _ptr(obs), _ptr(depth), _ptr(reward), _ptr(step_reward), _ptr(term),
+                                                    _ptr(trunc), _ptr(nsteps), C.byref(trace), _stream_ptr(self.device)), "mw_step_plan_trace")
+            return
         self._check(self.lib.mw_step_plan(self.h, _ptr(plans), horizon, _ptr(obs), _ptr(depth), _ptr(reward), _ptr(step_reward), _ptr(term),
                                           _ptr(trunc), _ptr(nsteps), _stream_ptr(self.device)), "mw_step_plan")
 

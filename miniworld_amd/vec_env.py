@@ -316,6 +316,8 @@ class MiniWorldVecEnv:
         self.truncated = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
         self.substeps = None            # int32[N], made by the first step(actions, repeat > 1)
         self.step_rewards = self._step_rewards = None       # float32[T, N] of the last rollout(), a view of the buffer behind it
+        self.trace = None               # name -> [T, N, ...] of the last rollout(trace=...), views of the buffers behind them
+        self._trace_bufs = {}
         self.final_obs = self.final_depth = None
         if final_obs:
             self.final_obs = self.engine.obs_buffer()
@@ -490,7 +492,9 @@ class MiniWorldVecEnv:
             self._advance_seeds()
         return self.obs, self.reward, self.terminated, self.truncated
 
-    def rollout(self, plans, render: bool = True):
+    TRACE_DEFAULT = ("agent_pos", "agent_dir", "carrying")
+
+    def rollout(self, plans, render: bool = True, trace=None, trace_ent=None):
         """Open-loop rollout: plans is an integer torch tensor [T, N] (converted to contiguous int32 on the engine's device if
         needed), T in 1 .. engine.MAX_PLAN.  Env i takes plans[0, i], plans[1, i], ... in one kernel launch and stops at the step
         that ends its episode, exactly as T calls of step() would with a host that breaks on done (then the auto-reset, once).
@@ -502,8 +506,32 @@ class MiniWorldVecEnv:
         rollout(render=True)), load_state(..., frames) or reset().
         autoreset="levels": the envs whose episode ended in the call restart from their next level behind it, as in step();
         render=False loads their states alone (the frames are stale by this call's contract; the state load marks the loaded
-        envs' stacks, so their next push rebuilds them)."""
+        envs' stacks, so their next push rebuilds them).
+        trace: where the agent was after every step of the plan, for a planner's dense cost (the distance to a goal, a visitation
+        count, a cell key) where the rewards are sparse.  True names ("agent_pos", "agent_dir", "carrying"); an iterable names any of
+        those and "ent_pos", the position of ONE entity slot, `trace_ent` (default: the family's goal slot, engine.cfg.goal_ent —
+        Hallway's box; a carried box moves with the agent).  `self.trace` is then a dict name -> device tensor, float64[T, N, 3] /
+        float64[T, N] / int32[T, N] / float64[T, N, 3], views of buffers grown on demand: row k is the state behind the env's step k
+        as state() would report it there — the terminal state on the step that ends an episode, in every auto-reset mode —, rows
+        an env did not execute repeat its last one, and an env that executed nothing (next-step: it installed its world) repeats
+        the state it entered with.  Written by the same one launch (mw_step_plan_trace); everything else the call returns is
+        unchanged.  None: no trace, `self.trace` is None.  An unknown name, "ent_pos" on CollectHealth (its kits respawn behind
+        the frame) or a slot outside 0 .. max_ents - 1 raises ValueError before any library call."""
         torch = self.torch
+        names = None
+        if trace is not None and trace is not False:
+            names = self.TRACE_DEFAULT if trace is True else tuple(trace)
+            if isinstance(trace, str) or not names:
+                raise ValueError(f"trace: need True or an iterable of names out of {sorted(eng.TRACE_FIELDS)}, got {trace!r}")
+            for name in names:
+                if name not in eng.TRACE_FIELDS:
+                    raise ValueError(f"trace: {name!r} is no trace field; have {sorted(eng.TRACE_FIELDS)}")
+            slot = int(self.engine.cfg.goal_ent) if trace_ent is None else trace_ent
+            if "ent_pos" in names:
+                if self.engine.cfg.task == eng.TASK_COLLECT:
+                    raise ValueError("trace: 'ent_pos' on CollectHealth (a consumed kit respawns behind the frame, not inside the step)")
+                if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.engine.cfg.max_ents:
+                    raise ValueError(f"trace_ent: need an entity slot in 0 .. {self.engine.cfg.max_ents - 1}, got {trace_ent!r}")
         if plans.dim() != 2 or plans.shape[1] != self.num_envs:
             raise ValueError(f"plans: need an integer tensor [T, {self.num_envs}], got {tuple(plans.shape)}")
         T = int(plans.shape[0])
@@ -519,7 +547,19 @@ class MiniWorldVecEnv:
             raise ValueError("rollout(render=False) with autoreset='seeds': a frameless call cannot seed the envs that finish in it")
         if self.autoreset_mode == "levels":
             self._need_levels("rollout")
-        self.engine.step_plan(plans, obs, depth, self.reward, self._step_rewards, self.terminated, self.truncated, self.substeps)
+        if names is None:
+            self.trace = None
+            self.engine.step_plan(plans, obs, depth, self.reward, self._step_rewards, self.terminated, self.truncated, self.substeps)
+        else:
+            for name in names:
+                dt, shp = eng.TRACE_FIELDS[name]
+                if name not in self._trace_bufs or self._trace_bufs[name].shape[0] < T:
+                    self._trace_bufs[name] = torch.zeros((T, self.num_envs) + shp, dtype=torch.float64 if dt is np.float64 else torch.int32,
+                                                         device=self.engine.device)
+            bufs = {name: self._trace_bufs[name] for name in names}
+            self.trace = {name: b[:T] for name, b in bufs.items()}
+            self.engine.step_plan_trace(plans, obs, depth, self.reward, self._step_rewards, self.terminated, self.truncated, self.substeps,
+                                        trace=bufs, ent_slot=int(slot) if "ent_pos" in names else 0)
         if self.autoreset_mode == "levels":
             self._finished_to_levels(frames=render)
         elif self.next_seed is not None:

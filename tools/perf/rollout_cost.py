@@ -17,7 +17,19 @@ Prints one JSON line.
 --trace T: the plan kernel against the repeat kernel, for a kernel trace.  Constant plans (every row the call's actions) through
 rollout(render=True) and the same actions through step(repeat=T), alternating windows of `calls` calls on twin engines; nothing is
 timed on the host.  --summarise reads the trace, cuts every step kernel's dispatches into the windows and prints per kernel the
-median duration of each window, their range and the overall median."""
+median duration of each window, their range and the overall median.
+
+    python tools/perf/rollout_cost.py --window traced [--root PARENT_CHECKOUT] >> cost.jsonl
+    python tools/perf/rollout_cost.py --collect cost.jsonl
+
+--window METHOD: what a rollout trace costs and buys, ONE timed window per process (a job alternates the processes: parent untraced,
+tree untraced, traced, loop, parent untraced, ...).  Hallway x 4096 (or --config), frameless, uniform-random plans, per T one window of
+`calls` x WINDOW_CALLS[method] calls behind a warm-up; prints one JSON line.  The methods:
+    untraced  rollout(plans, render=False) — with --root, of the checkout given there (the parent commit's, built), else of this tree
+    traced    rollout(plans, render=False, trace=True): the three default fields
+    loop      what a trace replaces: T x (rollout(plans[k:k + 1], render=False) + state() of the same three fields)
+--collect reads the lines of such a job and prints, per T and method, the median and the range of the windows (us per call and simulated
+env-steps/s) and the three comparisons of profiles/r19/README.md."""
 import argparse
 import csv
 import json
@@ -36,6 +48,91 @@ HORIZONS = (4, 8, 32)
 METHODS = ("frameless", "steps", "repeat")
 CALLS = {"frameless": 20, "steps": 1, "repeat": 4}      # a window is `calls` times this many calls: every window lasts a tenth of a second or more
 COUNTED = 25                                            # calls per window whose sub-steps are counted, behind the timed loop
+WINDOW_METHODS = ("untraced", "traced", "loop")
+WINDOW_CALLS = {"untraced": 20, "traced": 20, "loop": 1}
+TRACE_FIELDS = ("agent_pos", "agent_dir", "carrying")
+
+
+def window(args, env_id, n, dr, n_act):
+    """one timed window per horizon of one method, in this process"""
+    import torch
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    m = args.window
+    v = MiniWorldVecEnv(env_id, n, seed=0, domain_rand=dr)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    v.reset()
+    for _ in range(args.warmup):
+        v.step(torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32))
+
+    def run(plans, t, T, count=None):
+        if m == "untraced":
+            v.rollout(plans[t], render=False)
+        elif m == "traced":
+            v.rollout(plans[t], render=False, trace=True)
+        else:
+            for k in range(T):
+                v.rollout(plans[t, k:k + 1], render=False)
+                v.state(TRACE_FIELDS)
+                if count is not None:
+                    count += v.substeps.sum()
+            return
+        if count is not None:
+            count += v.substeps.sum()
+
+    out = {"window": m, "root": args.root or "tree", "config": args.config, "num_envs": n, "calls": args.calls, "horizons": {}}
+    for T in (int(x) for x in args.horizons.split(",")):
+        plans = torch.randint(0, n_act, (args.calls, T, n), generator=g, device="cuda", dtype=torch.int32)
+        reps = args.calls * WINDOW_CALLS[m]
+        for t in range(min(args.calls, 50)):        # (the method's kernels and buffers exist, the clocks are up)
+            run(plans, t, T)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for t in range(reps):
+            run(plans, t % args.calls, T)
+        torch.cuda.synchronize()
+        sec = time.perf_counter() - t0
+        subs = torch.zeros((), dtype=torch.int64, device="cuda")
+        for t in range(COUNTED):
+            run(plans, t, T, subs)
+        per_call = subs.item() / COUNTED
+        out["horizons"][T] = {"call_us": round(1e6 * sec / reps, 2), "sim_steps_per_s": round(per_call * reps / sec),
+                              "mean_substeps_per_env_and_call": round(per_call / n, 3)}
+    from miniworld_amd.engine import EngineError
+    try:
+        v.engine.check()
+        out["mw_check"] = "ok"
+    except EngineError as e:
+        out["mw_check"] = str(e)
+    v.close()
+    print(json.dumps(out))
+
+
+def collect(path):
+    rows = [json.loads(line) for line in open(path) if line.startswith("{")]
+    assert all(r["mw_check"] == "ok" for r in rows)
+    keys = sorted({(("parent " if r["root"] != "tree" else "") + r["window"]) for r in rows})
+    by = {}
+    for r in rows:
+        for T, h in r["horizons"].items():
+            by.setdefault((int(T), ("parent " if r["root"] != "tree" else "") + r["window"]), []).append(h)
+    med = lambda v: sorted(v)[len(v) // 2]
+    out = {}
+    for T in sorted({k[0] for k in by}):
+        o = out.setdefault(T, {})
+        for name in keys:
+            h = by.get((T, name), [])
+            if h:
+                us, rate = [x["call_us"] for x in h], [x["sim_steps_per_s"] for x in h]
+                o[name] = {"windows": len(h), "call_us": [med(us), min(us), max(us)], "sim_steps_per_s": [med(rate), min(rate), max(rate)]}
+        us = lambda name: o[name]["call_us"] if name in o else None
+        if us("untraced") and us("parent untraced"):
+            o["tree_slower_than_parent_in_every_window"] = us("untraced")[1] > us("parent untraced")[2]
+        if us("traced") and us("untraced"):
+            o["traced_over_untraced_median"] = round(us("traced")[0] / us("untraced")[0], 3)
+        if us("traced") and us("loop"):
+            o["every_traced_window_beats_every_loop_window"] = us("traced")[2] < us("loop")[1]
+            o["loop_over_traced_median"] = round(us("loop")[0] / us("traced")[0], 1)
+    print(json.dumps(out, indent=1))
 
 
 def summarise(path, windows):
@@ -88,12 +185,21 @@ def main():
     p.add_argument("--horizons", default=",".join(map(str, HORIZONS)))
     p.add_argument("--trace", type=int, default=0, metavar="T")
     p.add_argument("--summarise", metavar="KERNEL_TRACE_CSV")
+    p.add_argument("--window", choices=WINDOW_METHODS)
+    p.add_argument("--root", help="--window: the checkout whose package and library run (default: this tree)")
+    p.add_argument("--collect", metavar="JSONL")
     args = p.parse_args()
     if args.summarise:
         return summarise(args.summarise, args.windows)
+    if args.collect:
+        return collect(args.collect)
+    if args.root:
+        sys.path.insert(0, os.path.abspath(args.root))
     import torch
     from miniworld_amd.vec_env import MiniWorldVecEnv
     env_id, n, dr, n_act = CONFIGS[args.config]
+    if args.window:
+        return window(args, env_id, n, dr, n_act)
     if args.trace:
         return trace(args, env_id, n, dr, n_act)
     v = MiniWorldVecEnv(env_id, n, seed=0, domain_rand=dr)
