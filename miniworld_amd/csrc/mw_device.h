@@ -1,8 +1,10 @@
 // mwengine internal types shared by the host runtime (mw_engine*.hip) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/mwengine.h"
+#include "mw_world_fields.h"
 #include "mw_shape.h"            // MW_TILE_W, MW_TILE_H, MW_LDS_RECS, MW_LDS_SHADE_Q, MW_LDS_CULL_Q
 #include "mw_asset_types.h"      // MwTexDesc, MwMeshDesc, MW_MAX_LEVELS, MW_MESH_VCAP, MW_MESH_POS_STRIDE
 
@@ -203,3 +205,11 @@ struct MwArgs {
     int32_t n_xcc, pad_xcc;     // XCDs of the device as the engine's probe found them (1, 2, 4 or 8), mw_xcc_probe_kernel
     unsigned long long *k1_prof;   // MW_K1_PROF: [N][MW_K1_PROF_SLOTS] cycle counters of the geometry kernel's phases, start and end time of the env's wavefront (tools/perf/kgprof.py; perf experiments only), else null
 };
+
+// The world's arrays are listed once, in mw_world_fields.h: a row's member is one of MwArgs with the row's element size (MwSpare's
+// are assigned to MwArgs' by name, mw_engine.hip).  The table names the members, the struct above lays them out: it is the kernels'
+// by-value argument, and nothing of it moves.
+#define X(m, T, inner, slot, when, spare, view, vf) static_assert(sizeof(*MwArgs::m) == sizeof(T), #m);
+MW_WORLD_FIELDS(X)
+#undef X
+static_assert(sizeof(MwArgs) == 1176 && offsetof(MwArgs, ax) == 720 && offsetof(MwArgs, rng) == 872 && offsetof(MwArgs, reset_pending) == 1072, "MwArgs' layout moved");

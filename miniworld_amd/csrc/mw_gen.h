@@ -738,6 +738,7 @@ __device__ inline void keep_final_info(const MwArgs &a, int env)
 }
 
 // An episode ends in spare mode: the env's pre-generated world becomes the live one (64 lanes of one wavefront).
+// (the SP rows of MW_WORLD_FIELDS, mw_world_fields.h, written out: hand-scheduled, on the step's critical path)
 __device__ inline void take_spare(const MwArgs &a, int env, int lane)
 {
     const MwSpare &sp = *a.spare;
@@ -773,6 +774,7 @@ __device__ inline void take_spare(const MwArgs &a, int env, int lane)
 // The same by ONE lane (mw_setup_dense.hip: the env's leading lane; a wavefront holds several envs there).
 // Every group of values is loaded into registers first and stored afterwards: source and destination may alias as
 // far as the compiler knows, and a load -> store -> load chain would pay one memory round trip per value.
+// (the SP rows of MW_WORLD_FIELDS, mw_world_fields.h, written out like take_spare's)
 __device__ inline void take_spare_lane(const MwArgs &a, int env)
 {
     const MwSpare &sp = *a.spare;

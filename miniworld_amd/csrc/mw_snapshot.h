@@ -7,7 +7,7 @@
 //              spares on / off, capacity.  A load compares all of it.
 //   blobs      per-env geometry sets only: [capacity][max_polys] mw_poly and [capacity][max_segs][4] double of the live world, then
 //              the same of the spare world (spare mode) — contiguous per record, moved in 16-byte units
-//   8-byte components, then 4-byte ones, then 1-byte ones: per component [rows][capacity], in the order of the MW_SC_* list
+//   8-byte components, then 4-byte ones, then 1-byte ones: per component [rows][capacity], in the order of the MW_SC_* list (mw_world_fields.h)
 // Every section starts at header + capacity * (bytes of one record in front of it): sections of one element size follow each other
 // and the blobs are multiples of 16 bytes, so every section is aligned to its element and the blobs to 16 bytes, whatever capacity is.
 //
@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "mw_hd.h"
+#include "mw_world_fields.h"
 
 #define MW_SNAP_MAGIC 0x50414E53u       // "SNAP"
 #define MW_SNAP_FORMAT 1u
@@ -37,14 +38,16 @@ struct MwSnapConfig {
     int32_t health;     // the task keeps health / final_health (MW_TASK_COLLECT)
 };
 
+// the components: the rows of MW_WORLD_FIELDS (MW_SC_<member>), then the spare world's — the rows it has a copy of, in the same
+// order (MW_SC_SP_<member>) — and its state word
 enum {
-    MW_SC_AX = 0, MW_SC_AY, MW_SC_AZ, MW_SC_ADIR, MW_SC_CAM, MW_SC_LIGHT, MW_SC_EXTENT, MW_SC_CARRY, MW_SC_STEP, MW_SC_PICKED,
-    MW_SC_HEALTH, MW_SC_FINAL_HEALTH, MW_SC_FINAL_GOAL, MW_SC_EKIND, MW_SC_EMESH, MW_SC_ESTATIC, MW_SC_EPOS, MW_SC_EDIR, MW_SC_EGEOM,
-    MW_SC_RNG, MW_SC_PENDING_REMOVE, MW_SC_RESET_PENDING, MW_SC_NPOLYS, MW_SC_NSEGS,
-    // the spare world (MwSpare) and its state word
-    MW_SC_SP_AX, MW_SC_SP_AY, MW_SC_SP_AZ, MW_SC_SP_ADIR, MW_SC_SP_CAM, MW_SC_SP_LIGHT, MW_SC_SP_EXTENT, MW_SC_SP_EKIND, MW_SC_SP_EMESH,
-    MW_SC_SP_ESTATIC, MW_SC_SP_EPOS, MW_SC_SP_EDIR, MW_SC_SP_EGEOM, MW_SC_SP_NPOLYS, MW_SC_SP_NSEGS, MW_SC_REFILL_MASK,
-    MW_SC_COUNT
+#define X(m, T, inner, slot, when, spare, view, vf) MW_SC_##m,
+    MW_WORLD_FIELDS(X)
+#undef X
+#define X(m, T, inner, slot, when, spare, view, vf) MW_WF_SPARE_##spare(MW_SC_SP_##m,)
+    MW_WORLD_FIELDS(X)
+#undef X
+    MW_SC_REFILL_MASK, MW_SC_COUNT
 };
 enum { MW_SB_POLYS = 0, MW_SB_SEGS, MW_SB_SP_POLYS, MW_SB_SP_SEGS, MW_SB_COUNT };
 #define MW_SNAP_POLY_BYTES 128          // sizeof(mw_poly)
@@ -53,34 +56,15 @@ enum { MW_SB_POLYS = 0, MW_SB_SEGS, MW_SB_SP_POLYS, MW_SB_SP_SEGS, MW_SB_COUNT }
 // rows ([rows][N] in the engine, [rows][capacity] in the buffer; 0: the engine has no such array) and element size of a component
 MW_HD void mw_snap_shape(const MwSnapConfig &c, int id, int32_t *rows, int32_t *elem)
 {
-    const int32_t E = c.E, geo = c.shared_geom ? 0 : 1, sp = c.spares ? 1 : 0;
-    int32_t r = 0, b = 8;
-    switch (id) {
-    case MW_SC_AX: case MW_SC_AY: case MW_SC_AZ: case MW_SC_ADIR: r = 1; break;
-    case MW_SC_CAM: case MW_SC_EXTENT: r = 4; break;
-    case MW_SC_LIGHT: r = 12; break;
-    case MW_SC_CARRY: case MW_SC_STEP: case MW_SC_PICKED: case MW_SC_PENDING_REMOVE: r = 1; b = 4; break;
-    case MW_SC_HEALTH: case MW_SC_FINAL_HEALTH: r = c.health ? 1 : 0; b = 4; break;
-    case MW_SC_FINAL_GOAL: r = 3; break;
-    case MW_SC_EKIND: case MW_SC_EMESH: case MW_SC_ESTATIC: r = E; b = 4; break;
-    case MW_SC_EPOS: r = 3 * E; break;
-    case MW_SC_EDIR: r = E; break;
-    case MW_SC_EGEOM: r = 9 * E; break;
-    case MW_SC_RNG: r = 5; break;
-    case MW_SC_RESET_PENDING: r = 1; b = 1; break;
-    case MW_SC_NPOLYS: case MW_SC_NSEGS: r = geo; b = 4; break;
-    case MW_SC_SP_AX: case MW_SC_SP_AY: case MW_SC_SP_AZ: case MW_SC_SP_ADIR: r = sp; break;
-    case MW_SC_SP_CAM: case MW_SC_SP_EXTENT: r = 4 * sp; break;
-    case MW_SC_SP_LIGHT: r = 12 * sp; break;
-    case MW_SC_SP_EKIND: case MW_SC_SP_EMESH: case MW_SC_SP_ESTATIC: r = E * sp; b = 4; break;
-    case MW_SC_SP_EPOS: r = 3 * E * sp; break;
-    case MW_SC_SP_EDIR: r = E * sp; break;
-    case MW_SC_SP_EGEOM: r = 9 * E * sp; break;
-    case MW_SC_SP_NPOLYS: case MW_SC_SP_NSEGS: r = geo * sp; b = 4; break;
-    case MW_SC_REFILL_MASK: r = sp; b = 4; break;
-    default: break;
+    const int32_t sp = c.spares ? 1 : 0;
+    *rows = id == MW_SC_REFILL_MASK ? sp : 0; *elem = 4;
+#define X(m, T, inner, slot, when, spare, view, vf)                                                                          \
+    if (id == MW_SC_##m MW_WF_SPARE_##spare(|| id == MW_SC_SP_##m)) {                                                        \
+        *rows = mw_wf_rows(inner, slot, MW_WF_##when, c.E, c.health != 0, !c.shared_geom) * (id == MW_SC_##m ? 1 : sp);     \
+        *elem = (int32_t)sizeof(T);                                                                                          \
     }
-    *rows = r; *elem = b;
+    MW_WORLD_FIELDS(X)
+#undef X
 }
 
 // Capacity-independent form of the layout: `unit` = the bytes of ONE record that lie in front of a section, so that the section of a

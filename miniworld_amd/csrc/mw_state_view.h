@@ -11,23 +11,23 @@
 
 #include "../../include/mwengine.h"
 #include "mw_hd.h"
+#include "mw_world_fields.h"
 
 // The engine's arrays of the fields of mw_state_view, by name (a kernel argument: indexing a by-value struct at run time would
-// cost a private copy in scratch — the note at MwGenTables, mw_device.h).
+// cost a private copy in scratch — the note at MwGenTables, mw_device.h): the rows of MW_WORLD_FIELDS that a view reaches, so that a
+// view field cannot exist without its array.
 struct MwStateArrays {
-    double *ax, *ay, *az, *adir, *cam, *light;
-    int32_t *carry, *step, *picked;
-    int32_t *ekind, *emesh, *estatic;
-    double *epos, *edir, *egeom, *extent;
+#define X(m, T, inner, slot, when, spare, view, vf) MW_WF_INVIEW_##view(T *m;)
+    MW_WORLD_FIELDS(X)
+#undef X
 };
 
-// components per env (or per slot) of the fields: mw_state_view's comments
+// components of agent_pos, the one field that is no row of the table: [3] in a row, the arrays ax, ay, az in the engine
 #define MW_SV_POS 3
-#define MW_SV_CAM 4
-#define MW_SV_LIGHT 12
-#define MW_SV_EPOS 3
-#define MW_SV_EGEOM 9
-#define MW_SV_EXTENT 4
+// every other field of mw_state_view is a VIEW row (of the row's element type: gather_row / scatter_row take row and array as T * alike)
+#define X(m, T, inner, slot, when, spare, view, vf) MW_WF_VIEWED_##view(+1)
+static_assert(sizeof(mw_state_view) == (1 MW_WORLD_FIELDS(X)) * sizeof(void *), "mw_state_view has a field that is no row of MW_WORLD_FIELDS");
+#undef X
 
 namespace mwsv {
 
@@ -67,50 +67,29 @@ MW_HD void scatter_pos(const double *row, double *ax, double *ay, double *az, si
     for (int r = lane; r < MW_SV_POS; r += stride) (r == 0 ? ax : r == 1 ? ay : az)[env] = row[r];
 }
 
-// Every non-null field of the view, for one env: `item` is the env's row in the caller's buffers (env - first_env for a read of a
-// range, the env itself for the masked write).  The fields are written out by name.
-MW_HD void gather_env(const MwStateArrays &a, const mw_state_view &v, int E, size_t N, size_t env, size_t item, int lane, int stride)
+// Every non-null field of the view, for one env, engine -> rows (GATHER) or rows -> engine: `item` is the env's row in the caller's
+// buffers (env - first_env for a read of a range, the env itself for the masked write).  One statement per VIEW row of the table: the
+// field's and the array's names reach the compiler as names.
+template <bool GATHER>
+MW_HD void copy_env(const MwStateArrays &a, const mw_state_view &v, int E, size_t N, size_t env, size_t item, int lane, int stride)
 {
-    const size_t e = (size_t)E;
-    if (v.agent_pos) gather_pos(v.agent_pos + item * MW_SV_POS, a.ax, a.ay, a.az, env, lane, stride);
-    if (v.agent_dir) gather_row<double, 1>(v.agent_dir + item, a.adir, 1, N, env, lane, stride);
-    if (v.cam) gather_row<double, MW_SV_CAM>(v.cam + item * MW_SV_CAM, a.cam, 1, N, env, lane, stride);
-    if (v.light) gather_row<double, MW_SV_LIGHT>(v.light + item * MW_SV_LIGHT, a.light, 1, N, env, lane, stride);
-    if (v.carrying) gather_row<int32_t, 1>(v.carrying + item, a.carry, 1, N, env, lane, stride);
-    if (v.step_count) gather_row<int32_t, 1>(v.step_count + item, a.step, 1, N, env, lane, stride);
-    if (v.num_picked_up) gather_row<int32_t, 1>(v.num_picked_up + item, a.picked, 1, N, env, lane, stride);
-    if (v.ent_kind) gather_row<int32_t, 1>(v.ent_kind + item * e, a.ekind, E, N, env, lane, stride);
-    if (v.ent_mesh) gather_row<int32_t, 1>(v.ent_mesh + item * e, a.emesh, E, N, env, lane, stride);
-    if (v.ent_static) gather_row<int32_t, 1>(v.ent_static + item * e, a.estatic, E, N, env, lane, stride);
-    if (v.ent_pos) gather_row<double, MW_SV_EPOS>(v.ent_pos + item * e * MW_SV_EPOS, a.epos, E, N, env, lane, stride);
-    if (v.ent_dir) gather_row<double, 1>(v.ent_dir + item * e, a.edir, E, N, env, lane, stride);
-    if (v.ent_geom) gather_row<double, MW_SV_EGEOM>(v.ent_geom + item * e * MW_SV_EGEOM, a.egeom, E, N, env, lane, stride);
-    if (v.extent) gather_row<double, MW_SV_EXTENT>(v.extent + item * MW_SV_EXTENT, a.extent, 1, N, env, lane, stride);
+    if (v.agent_pos && GATHER) gather_pos(v.agent_pos + item * MW_SV_POS, a.ax, a.ay, a.az, env, lane, stride);
+    if (v.agent_pos && !GATHER) scatter_pos(v.agent_pos + item * MW_SV_POS, a.ax, a.ay, a.az, env, lane, stride);
+#define X(m, T, inner, slot, when, spare, view, vf)                                                                                                   \
+    MW_WF_VIEWED_##view(if (v.vf && GATHER) gather_row<T, inner>(v.vf + item * (size_t)((slot ? E : 1) * inner), a.m, slot ? E : 1, N, env, lane, stride); \
+                        if (v.vf && !GATHER) scatter_row<T, inner>(v.vf + item * (size_t)((slot ? E : 1) * inner), a.m, slot ? E : 1, N, env, lane, stride);)
+    MW_WORLD_FIELDS(X)
+#undef X
 }
-MW_HD void scatter_env(const MwStateArrays &a, const mw_state_view &v, int E, size_t N, size_t env, size_t item, int lane, int stride)
-{
-    const size_t e = (size_t)E;
-    if (v.agent_pos) scatter_pos(v.agent_pos + item * MW_SV_POS, a.ax, a.ay, a.az, env, lane, stride);
-    if (v.agent_dir) scatter_row<double, 1>(v.agent_dir + item, a.adir, 1, N, env, lane, stride);
-    if (v.cam) scatter_row<double, MW_SV_CAM>(v.cam + item * MW_SV_CAM, a.cam, 1, N, env, lane, stride);
-    if (v.light) scatter_row<double, MW_SV_LIGHT>(v.light + item * MW_SV_LIGHT, a.light, 1, N, env, lane, stride);
-    if (v.carrying) scatter_row<int32_t, 1>(v.carrying + item, a.carry, 1, N, env, lane, stride);
-    if (v.step_count) scatter_row<int32_t, 1>(v.step_count + item, a.step, 1, N, env, lane, stride);
-    if (v.num_picked_up) scatter_row<int32_t, 1>(v.num_picked_up + item, a.picked, 1, N, env, lane, stride);
-    if (v.ent_kind) scatter_row<int32_t, 1>(v.ent_kind + item * e, a.ekind, E, N, env, lane, stride);
-    if (v.ent_mesh) scatter_row<int32_t, 1>(v.ent_mesh + item * e, a.emesh, E, N, env, lane, stride);
-    if (v.ent_static) scatter_row<int32_t, 1>(v.ent_static + item * e, a.estatic, E, N, env, lane, stride);
-    if (v.ent_pos) scatter_row<double, MW_SV_EPOS>(v.ent_pos + item * e * MW_SV_EPOS, a.epos, E, N, env, lane, stride);
-    if (v.ent_dir) scatter_row<double, 1>(v.ent_dir + item * e, a.edir, E, N, env, lane, stride);
-    if (v.ent_geom) scatter_row<double, MW_SV_EGEOM>(v.ent_geom + item * e * MW_SV_EGEOM, a.egeom, E, N, env, lane, stride);
-    if (v.extent) scatter_row<double, MW_SV_EXTENT>(v.extent + item * MW_SV_EXTENT, a.extent, 1, N, env, lane, stride);
-}
+MW_HD void gather_env(const MwStateArrays &a, const mw_state_view &v, int E, size_t N, size_t env, size_t item, int lane, int stride) { copy_env<true>(a, v, E, N, env, item, lane, stride); }
+MW_HD void scatter_env(const MwStateArrays &a, const mw_state_view &v, int E, size_t N, size_t env, size_t item, int lane, int stride) { copy_env<false>(a, v, E, N, env, item, lane, stride); }
 
 // does the view name any field at all
 MW_HD bool any_field(const mw_state_view &v)
 {
-    return v.agent_pos || v.agent_dir || v.cam || v.light || v.carrying || v.step_count || v.num_picked_up || v.ent_kind || v.ent_mesh ||
-           v.ent_static || v.ent_pos || v.ent_dir || v.ent_geom || v.extent;
+#define X(m, T, inner, slot, when, spare, view, vf) MW_WF_VIEWED_##view(|| v.vf)
+    return v.agent_pos MW_WORLD_FIELDS(X);
+#undef X
 }
 
 // what the masked write tests of an env before it writes anything of it: the carried slot and every entity kind

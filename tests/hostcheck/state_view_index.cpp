@@ -38,9 +38,12 @@ struct World {
     // agent_pos is three separate arrays in the engine: its [3][N] block is ax, ay, az in a row
     MwStateArrays arrays()
     {
-        return {pos.dev.data(), pos.dev.data() + N, pos.dev.data() + 2 * N, dir.dev.data(), cam.dev.data(), light.dev.data(), carry.dev.data(),
-                step.dev.data(), picked.dev.data(), ekind.dev.data(), emesh.dev.data(), estatic.dev.data(), epos.dev.data(), edir.dev.data(),
-                egeom.dev.data(), extent.dev.data()};
+        MwStateArrays a{};
+        a.ax = pos.dev.data(); a.ay = pos.dev.data() + N; a.az = pos.dev.data() + 2 * N; a.adir = dir.dev.data(); a.cam = cam.dev.data(); a.light = light.dev.data();
+        a.carry = carry.dev.data(); a.step = step.dev.data(); a.picked = picked.dev.data();
+        a.ekind = ekind.dev.data(); a.emesh = emesh.dev.data(); a.estatic = estatic.dev.data();
+        a.epos = epos.dev.data(); a.edir = edir.dev.data(); a.egeom = egeom.dev.data(); a.extent = extent.dev.data();
+        return a;
     }
     mw_state_view view()
     {

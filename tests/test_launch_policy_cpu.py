@@ -29,7 +29,7 @@ SCENES = {"hallway": (6, 1, 16, TASK_GOTO), "pickupobjects": (6, 5, 48, TASK_PIC
 def policy_lib(src=SRC, lib=LIB):
     """tests/hostcheck/libmwpolicy.so, (re)built when a source is newer"""
     csrc = os.path.join(ROOT, "miniworld_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, h) for h in ("mw_policy.h", "mw_shape.h", "mw_snapshot.h", "mw_snapframes.h")] + [os.path.join(ROOT, "include", "mwengine.h")]
+    deps = [src] + [os.path.join(csrc, h) for h in ("mw_policy.h", "mw_shape.h", "mw_snapshot.h", "mw_world_fields.h", "mw_snapframes.h")] + [os.path.join(ROOT, "include", "mwengine.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-Wall", "-shared", src, "-o", lib])
     L = C.CDLL(lib)

@@ -22,7 +22,7 @@ GEN_HALLWAY, GEN_PICKUP, GEN_MAZE, GEN_PROGRAM = 1, 3, 4, 5
 
 def layout_lib():
     """tests/hostcheck/libmwsnapshot.so, (re)built when a source is newer (also used by tests/test_gpu_snapshot.py)."""
-    deps = [SRC] + [os.path.join(ROOT, "miniworld_amd", "csrc", h) for h in ("mw_snapshot.h", "mw_hd.h")]
+    deps = [SRC] + [os.path.join(ROOT, "miniworld_amd", "csrc", h) for h in ("mw_snapshot.h", "mw_world_fields.h", "mw_hd.h")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-Wall", "-shared", SRC, "-o", LIB])
     lib = C.CDLL(LIB)

@@ -60,8 +60,8 @@ def test_library_exports_the_entry_points_and_refuses_a_null_engine():
 
 
 def test_the_new_unit_is_built_and_declared():
-    """mw_state_view.hip is one of the Makefile's sources, its two kernels are declared in mw_kernels.h, and the fields are written
-    out by name: the by-value argument structs are never indexed at run time."""
+    """mw_state_view.hip is one of the Makefile's sources, its two kernels are declared in mw_kernels.h, and the fields reach the
+    compiler by name: the by-value argument structs are never indexed at run time."""
     make = open(os.path.join(CSRC, "Makefile")).read()
     assert re.search(r"^SRCS = (?:.*\\\n)*.*\bmw_state_view\.hip\b", make, re.M)
     decl = open(os.path.join(CSRC, "mw_kernels.h")).read()
@@ -73,8 +73,14 @@ def test_the_new_unit_is_built_and_declared():
     assert "__shared__" not in unit
     index = open(os.path.join(CSRC, "mw_state_view.h")).read()
     assert "MW_HD" in index and '#include "mw_hd.h"' in index
-    for f in FIELDS:
-        assert re.search(r"\bv\." + f + r"\b", index), f
+    # ... every field is one of the view rows of the table of world arrays, which the header expands into one member access per row
+    # (v.<field>, a.<member>); agent_pos, three arrays behind one field, is the one it writes out
+    table = open(os.path.join(CSRC, "mw_world_fields.h")).read()
+    rows = re.findall(r"^\s*X\((\w+),\s*\w+,\s*\d+,\s*[01],\s*\w+,\s*\w+,\s*(\w+),\s*(\w+)\)", table, re.M)
+    assert sorted(["agent_pos"] + [vf for _, view, vf in rows if view == "VIEW"]) == sorted(FIELDS)
+    assert [m for m, view, vf in rows if view == "POS"] == ["ax", "ay", "az"] and {vf for _, view, vf in rows if view == "POS"} == {"agent_pos"}
+    assert len(re.findall(r"\bv\.agent_pos\b", index)) >= 5 and re.search(r"\bv\.vf\b", index) and re.search(r"\ba\.m\b", index)
+    assert index.count("MW_WORLD_FIELDS(X)") >= 4 and not re.search(r"\b[av]\s*\[", index)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the policy
