@@ -770,7 +770,7 @@ int mw_get_frame_clean(mw_engine *e, uint8_t *d_out, void *stream);
  * with the cache off.  A drawn frame costs one more store of its bytes, so a policy that never revisits a state pays without gain. */
 int mw_set_frame_cache(mw_engine *e, int32_t slots);
 /* d_out uint8[N] (device): where each env's frame of the last plain mw_step came from — 0 drawn, 1 left alone as clean (frame reuse),
- * 2 + j copied from slot j of the frame cache.  The step kernel stores 0, the quad kernel the rest: zeros on the other raster paths.  Asynchronous on `stream`. */
+ * 2 + j copied from slot j of the frame cache.  The step kernel stores 0, the frame plan in front of the quad kernel the rest: zeros on the other raster paths.  Asynchronous on `stream`. */
 int mw_get_frame_source(mw_engine *e, uint8_t *d_out, void *stream);
 
 /* Diagnostic (synchronises `stream`): how many triangles the last frame's display list held per env after clipping and culling —

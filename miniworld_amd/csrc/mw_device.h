@@ -185,7 +185,7 @@ struct MwArgs {
     // change of the carried slot — so that frames from before and after it cannot match.
     uint64_t *fc_key;        // [N][MW_FC_KEY_WORDS]
     uint32_t *fc_epoch;      // [N]
-    uint8_t *fc_source;      // [N] where the env's frame of the last plain step came from (mw_get_frame_source): K1 stores 0, "drawn", the quad kernel 1 or 2 + j for an env it does not draw
+    uint8_t *fc_source;      // [N] where the env's frame of the last plain step came from (mw_get_frame_source): K1 stores 0, "drawn", the plan kernel its verdict for every env, 1 or 2 + j for an env that is not drawn (mw_frame_plan.h)
     // big scenes: what the geometry kernel's culling derives from a world's polygons alone (mw_geom.hip), kept from frame to
     // frame.  occ_valid[set]: polygon count + 1 of the world the cache belongs to, 0 after anything rewrote the polygons.
     int32_t *occ_valid;     // [sets] or null

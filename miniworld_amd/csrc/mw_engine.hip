@@ -224,12 +224,13 @@ int init_engine(mw_engine *e, const mw_config *cfg)
     ALLOC(a.nvis, N); ALLOC(a.envhdr, (size_t)MW_ENVHDR * N); ALLOC(a.status, 1);
     ALLOC(e->d_reward_scratch, N); ALLOC(e->d_flag_scratch, 2 * (size_t)N);
     ALLOC(e->d_final_list, 1 + (size_t)N);
+    ALLOC(e->d_plan[0], MW_PLAN_WORDS(N)); ALLOC(e->d_plan[1], MW_PLAN_WORDS(N));      // (zeroed: the first plan kernel counts from nothing)
     ALLOC(e->stack.flags, 2 * (size_t)N);
     ALLOC(e->d_mask, N); ALLOC(e->d_step_override, 3 * (size_t)N);
 #ifdef MW_PERF_HOOKS        // (tools/perf: make EXTRA=-DMW_PERF_HOOKS — kernel phase stamps dumped by mw_destroy; not in the product build)
     if (getenv("MW_K1_PROF")) ALLOC(a.k1_prof, MW_K1_PROF_SLOTS * (size_t)N);     // per-env cycle stamps of the geometry kernel's phases (zeroed)
     if (getenv("MW_ENT_PROF")) ALLOC(e->d_ent_prof, (size_t)16 * 2 * N * MW_MAX_MESH_ENTS * 8);
-    if (getenv("MW_K2Q_PROF")) ALLOC(e->d_k2q_prof, (size_t)N * 80);
+    if (getenv("MW_K2Q_PROF")) ALLOC(e->d_k2q_prof, (size_t)N * 96);
 #endif
 #undef LIVE_ALLOC
 #undef ALLOC
@@ -386,7 +387,7 @@ void mw_destroy(mw_engine *e)
         if (dev && hipMemcpy(h.data(), dev, count * 8, hipMemcpyDeviceToHost) == hipSuccess)
             if (FILE *f = fopen(getenv(var), "wb")) { fwrite(h.data(), 8, count, f); fclose(f); }
     };
-    dump(e->d_k2q_prof, (size_t)e->cfg.num_envs * 80, "MW_K2Q_PROF");
+    dump(e->d_k2q_prof, (size_t)e->cfg.num_envs * 96, "MW_K2Q_PROF");
     dump(e->d_ent_prof, (size_t)16 * 2 * e->cfg.num_envs * MW_MAX_MESH_ENTS * 8, "MW_ENT_PROF");
     dump(e->args.k1_prof, (size_t)e->cfg.num_envs * MW_K1_PROF_SLOTS, "MW_K1_PROF");
     if (getenv("MW_SLOW_STATS") && e->mp.slow_count) {      // perf experiments only: the last frame's slow fragments per env

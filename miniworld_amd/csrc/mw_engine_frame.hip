@@ -194,7 +194,7 @@ struct Frame {
     int view_flags;
     const int32_t *list;        // CALL_LIST_PASS: the list forms draw the listed envs only
     uint8_t *obs; float *depth; hipStream_t st;
-    FramePolicy pol;            // reuse; source: the per-env source byte is written; cache: the quad kernel consults and fills the frame cache
+    FramePolicy pol;            // reuse; cache: the frame consults and fills the frame cache (both through the frame plan on the quad path: frame_plans)
     RasterPath p;
     MeshFrame mf;               // p.mesh only
 };
@@ -274,15 +274,28 @@ int launch_generic(mw_engine *e, const MwArgs &a, int first_env, int count, int 
     return MW_OK;
 }
 
-// the quad kernel (mw_rasterq.hip); part: raster_flags
-void launch_quad(const mw_engine *e, const Frame &f, int part, hipStream_t st)
+// the quad kernel (mw_rasterq.hip); part: raster_flags.  plan: the block the plan kernel filled for this frame (launch_plan), or null —
+// then every env is drawn, and the cache is neither consulted nor filled
+void launch_quad(const mw_engine *e, const Frame &f, int part, hipStream_t st, const uint32_t *plan = nullptr)
 {
     const MwArgs &a = f.a;
     const int lds = mw_rasterq_lds_bytes(e->cfg.msaa, a.W, a.H, a.n_tiles, f.depth ? 1 : 0);
     launch(f.p.quad4 ? MW_PAIR(mw_rasterq4) : MW_PAIR(mw_rasterq), f.list, dim3(e->cfg.num_envs), dim3(MWQ_THREADS), (size_t)lds, st, a.N, a.W, a.H, a.max_vis,
            a.tiles_x, a.n_tiles, (const float *)a.rec_raster, (const float *)a.rec_shade, (const float *)a.rec_cull,
-           (const int32_t *)a.nvis, (const float *)a.envhdr, a.texels, f.obs, f.depth, raster_flags(e->dbg_flags, e->obs_layout, part, 0u, f.pol.reuse), e->texel_bytes, e->d_k2q_prof,
-           (const uint8_t *)a.frame_clean, f.pol.cache ? (const MwFcArgs *)e->fc.d_args.get() : nullptr, f.pol.source ? a.fc_source : nullptr);
+           (const int32_t *)a.nvis, (const float *)a.envhdr, a.texels, f.obs, f.depth, raster_flags(e->dbg_flags, e->obs_layout, part, 0u, false), e->texel_bytes, e->d_k2q_prof,
+           plan && f.pol.cache ? (const MwFcArgs *)e->fc.d_args.get() : nullptr, plan);
+}
+
+// The frame plan of a plain whole-batch step through the quad kernel (frame_plans), behind the geometry kernel on the caller's stream: which envs
+// the quad kernel draws, which it copies from the cache, which it leaves.  Returns the block it filled.
+const uint32_t *launch_plan(mw_engine *e, const Frame &f, hipStream_t st)
+{
+    const MwArgs &a = f.a; const int N = e->cfg.num_envs;
+    uint32_t *plan = e->d_plan[e->plan_cur], *next = e->d_plan[e->plan_cur ^ 1];
+    e->plan_cur ^= 1;
+    hipLaunchKernelGGL(mw_frame_plan_kernel, dim3((N + MW_PLAN_ENVS - 1) / MW_PLAN_ENVS), dim3(64), 0, st, N, f.pol.reuse ? 1 : 0, (const uint8_t *)a.frame_clean,
+                       (const uint64_t *)a.fc_key, f.pol.cache ? (const uint64_t *)e->fc.meta.get() : nullptr, f.pol.cache ? e->fc.slots : 0, a.fc_source, plan, next);
+    return plan;
 }
 
 // the tile kernels (mw_raster.hip); part: raster_flags
@@ -407,7 +420,7 @@ int launch_frame(mw_engine *e, const Call &c, CallKind kind, int view_flags = 0)
     if (call_steps(kind) && side_refills(e) && (rc = launch_side_refill(e, st))) return rc;
     if (f.p.path == MW_PATH_GENERIC) rc = launch_generic(e, f.a, 0, N, e->cfg.msaa, dim3(32, N), d_obs, d_depth, e->obs_layout, f.list, st);
     else if (f.p.mesh) rc = launch_mesh_chain(e, f, st);
-    else if (f.p.path == MW_PATH_QUAD) launch_quad(e, f, 0, st);
+    else if (f.p.path == MW_PATH_QUAD) launch_quad(e, f, 0, st, frame_plans(pol, f.p.path, f.list != nullptr, N) ? launch_plan(e, f, st) : nullptr);
     else launch_tiles(e, f, 0, st);
     if (rc) return rc;
     e->last_raster_path = f.p.path;

@@ -63,3 +63,52 @@ extern "C" __global__ __launch_bounds__(256) void mw_final_copy_kernel(const int
     if (depth && final_depth)
         for (int k = threadIdx.x; k < depth_row; k += blockDim.x) final_depth[env * depth_row + k] = depth[env * depth_row + k];
 }
+
+// The frame plan of a plain whole-batch step through the quad kernel (mw_policy.h: frame_plans; mw_frame_plan.h: the decision and the
+// plan block), behind the geometry kernel: per env the source byte (mw_get_frame_source) and, unless the env is left alone, an entry in
+// the draw list or the copy list.  A lane per env, MW_PLAN_ENVS = 64 envs per wavefront: the lane loads the clean byte, the key K1
+// stored for this frame, the header and the keys of all MW_FC_MAX_SLOTS slots — the slots the cache does not have re-read its last one
+// and do not count —, every load issued before the first comparison: one round trip to memory.  The appends are aggregated per
+// wavefront: two ballots, then ONE 64-bit atomic per wavefront on the two counts (one word takes ~88 atomics/us: an atomic per env,
+// or two per eight envs, cost more than the rest of the kernel — 14.6 us measured at 4096 envs against 5.4 this way).  No LDS; grid
+// ceil(N / MW_PLAN_ENVS) wavefronts.
+// reuse: MW_RASTER_REUSE applies; meta: the cache's key table, null without a cache (slots 0); next: the engine's other plan block,
+// whose counts this launch zeroes for the frame after this one.
+extern "C" __global__ __launch_bounds__(64) void mw_frame_plan_kernel(int N, int reuse, const uint8_t *__restrict__ frame_clean, const uint64_t *__restrict__ key,
+                                                                     const uint64_t *__restrict__ meta, int slots, uint8_t *__restrict__ frame_source,
+                                                                     uint32_t *__restrict__ plan, uint32_t *__restrict__ next)
+{
+    const int lane = (int)threadIdx.x, env = (int)blockIdx.x * MW_PLAN_ENVS + lane;
+    if (blockIdx.x == 0 && lane < 2) next[lane] = 0u;
+    const bool on = env < N;
+    uint32_t v = MW_SRC_CLEAN;          // (a lane without an env appends nothing)
+    if (on) {
+        const bool clean = frame_clean[env] != 0;
+        uint32_t match = 0u, header = 0u;
+        if (meta) {
+            const uint64_t *row = static_cast<const uint64_t *>(__builtin_assume_aligned(meta + (size_t)env * MW_FC_META_WORDS(slots), 16));
+            const uint64_t *cur = static_cast<const uint64_t *>(__builtin_assume_aligned(key + (size_t)env * MW_FC_KEY_WORDS, 16));
+            header = (uint32_t)row[0];
+#pragma unroll
+            for (int j = 0; j < MW_FC_MAX_SLOTS; ++j) {
+                const int jj = j < slots ? j : slots - 1;
+                match |= mw_fc_key_equal(static_cast<const uint64_t *>(__builtin_assume_aligned(row + 2 + MW_FC_KEY_WORDS * jj, 16)), cur) && j < slots ? 1u << j : 0u;
+            }
+        }
+        v = mw_frame_verdict(clean, reuse != 0, match, header, meta ? slots : 0);
+        frame_source[env] = (uint8_t)v;
+    }
+    const uint32_t src = v & 0xFFu;
+    const bool draw = on && src == MW_SRC_DRAWN, copy = on && src >= (uint32_t)MW_SRC_SLOT(0);
+    const uint64_t md = __builtin_amdgcn_ballot_w64(draw), mc = __builtin_amdgcn_ballot_w64(copy), below = (1ull << lane) - 1ull;
+    // (plan[0] and plan[1] as one 64-bit word: draw entries in the low half, copy entries in the high half; neither can carry)
+    unsigned long long base = 0ull;
+    if (lane == 0 && (md | mc))
+        base = atomicAdd(reinterpret_cast<unsigned long long *>(plan), (unsigned long long)__popcll(md) | (unsigned long long)__popcll(mc) << 32);
+    const uint32_t bd = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base), bc = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
+    const uint32_t entry = (uint32_t)env | (v >> 8) << MW_PLAN_ENV_BITS;
+    // (the counts start at zero, so a list never outgrows its N entries; the tests keep a stray count from writing past them)
+    const uint32_t id = bd + (uint32_t)__popcll(md & below), ic = bc + (uint32_t)__popcll(mc & below);
+    if (draw && id < (uint32_t)N) plan[MW_PLAN_HEAD + id] = entry;
+    if (copy && ic < (uint32_t)N) plan[MW_PLAN_HEAD + (size_t)N + ic] = entry;
+}

@@ -3,6 +3,7 @@
 // not compile.
 #pragma once
 #include "mw_device.h"
+#include "mw_frame_plan.h"
 #include "mw_snapshot.h"
 #include "mw_snapframes.h"
 #include "mw_state_view.h"
@@ -67,10 +68,10 @@ MW_KERNEL_PAIR(mw_geom_any, MW_GEOM_ARGS);
 MW_KERNEL_PAIR(mw_geom_big_any, MW_GEOM_ARGS);
 
 // MW_RASTER_REUSE (mw_shape.h), a bit of the raster kernels' flag word (mw_policy.h::raster_flags): the observation buffer still
-// holds every env's last frame, so an env whose frame_clean byte is set (MwArgs) is not drawn — the quad kernel's workgroup and the
-// plain tile kernels' wavefronts of that env leave at once.  Only frames without mesh entities carry it: the bit is the lowest of the
-// field that holds the slow-fragment stamp of a frame with meshes, and such a frame is always drawn in full.  The list forms never
-// honour it.
+// holds every env's last frame, so an env whose frame_clean byte is set (MwArgs) is not drawn — the plain tile kernels' wavefronts of
+// that env leave at once; for the quad kernel the frame plan (below) leaves the env out of its lists, and the kernel itself never
+// reads the bit or the byte.  Only frames without mesh entities carry it: the bit is the lowest of the field that holds the
+// slow-fragment stamp of a frame with meshes, and such a frame is always drawn in full.  The list forms never honour it.
 
 // the tile kernels (mw_raster.hip)
 // (the frame kernels take parameter lists, not one struct: only __restrict__ on a kernel parameter tells the compiler that the
@@ -103,18 +104,25 @@ MW_KERNEL_PAIR(mw_raster_mesh_wrap, MW_RASTER_ARGS);
 MW_KERNEL_PAIR(mw_raster_big_mesh_wrap, MW_RASTER_ARGS);
 
 // the quad kernel (mw_rasterq.hip): one workgroup of MWQ_THREADS lanes per env, 8 or 4 samples per pixel
-// The frame cache (mw_set_frame_cache), fc != null (MwFcArgs, mw_device.h) — uint8 HWC frames without mesh entities only, never the
-// list forms: the env's workgroup compares the key K1 stored for this frame (MwArgs::fc_key) with the keys of the env's slots and
-// copies the matching slot's frame and depth map instead of drawing; a frame it draws also goes to the slot the env's header names,
-// with its key.  frame_source (may be null; MwArgs::fc_source): per env 0 drawn — K1's store, a drawing workgroup writes nothing —, 1 left
-// alone as clean, 2 + j copied from slot j.
+// plan == null: workgroup b draws env b (the list forms: env list[1 + b] while b < list[0]).
+// plan != null (mw_frame_plan.h: the block mw_frame_plan_kernel filled behind the geometry kernel; plain whole-batch steps only,
+// mw_policy.h: frame_plans): the kernel decides nothing about an env itself.  Workgroup b < n_draw draws the env of draw entry b;
+// workgroup n_draw <= b < n_draw + n_copy copies the frame, and the depth map, of the slot its copy entry names from the frame cache
+// into the caller's buffers — 16-, 4- or 1-byte stores by the buffer's alignment — and leaves before any barrier; every other
+// workgroup leaves at once.  So the drawing workgroups are the first the launch dispatches and the copies fill its tail; nothing
+// waits on another workgroup, and no result depends on the order of dispatch or of the entries.
+// The frame cache (mw_set_frame_cache), fc != null (MwFcArgs, mw_device.h; only with a plan) — uint8 HWC frames without mesh entities
+// only, never the list forms: a frame the kernel draws also goes to the slot its draw entry names (the plan kernel read it from the
+// env's header: round-robin), with the key K1 stored for it (MwArgs::fc_key), and the header advances; a copy changes nothing.
+// The source byte (MwArgs::fc_source; mw_get_frame_source) — 0 drawn, 1 left alone as clean, 2 + j copied from slot j — is K1's 0
+// for every env, overwritten for every env by the plan kernel where one runs.
 #define MWQ_THREADS 512
 #define MWQ_ARGS \
     int N, int W, int H, int max_vis, int tiles_x, int n_tiles, \
     const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull, \
     const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const uint32_t *__restrict__ texels, \
     uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof, \
-    const uint8_t *__restrict__ frame_clean, const MwFcArgs *__restrict__ fc, uint8_t *__restrict__ frame_source
+    const MwFcArgs *__restrict__ fc, const uint32_t *__restrict__ plan
 MW_KERNEL_PAIR(mw_rasterq, MWQ_ARGS);
 MW_KERNEL_PAIR(mw_rasterq4, MWQ_ARGS);
 // bytes of dynamic LDS a launch needs; the longest display list the quad path draws (longer ones: the tile code)
@@ -207,6 +215,12 @@ extern "C" __global__ void mw_info_kernel(int N, int E, const int32_t *health, c
 extern "C" __global__ void mw_final_list_kernel(int N, const uint8_t *__restrict__ pending, int32_t *__restrict__ pending_remove, int32_t *__restrict__ list);
 extern "C" __global__ void mw_final_copy_kernel(const int32_t *__restrict__ list, const uint8_t *__restrict__ obs, uint8_t *__restrict__ final_obs,
                                                 unsigned long long row_bytes, const float *__restrict__ depth, float *__restrict__ final_depth, int depth_row);
+// ... and the frame plan of a plain whole-batch step through the quad kernel (mw_frame_plan.h), behind the geometry kernel: a lane per
+// env; grid ceil(N / MW_PLAN_ENVS) x 64 lanes
+#define MW_PLAN_ENVS 64
+extern "C" __global__ void mw_frame_plan_kernel(int N, int reuse, const uint8_t *__restrict__ frame_clean, const uint64_t *__restrict__ key,
+                                                const uint64_t *__restrict__ meta, int slots, uint8_t *__restrict__ frame_source,
+                                                uint32_t *__restrict__ plan, uint32_t *__restrict__ next);
 
 // state views (mw_state_view.hip; the index arithmetic and MwStateArrays: mw_state_view.h): one launch per call, a wavefront per env,
 // MW_SV_ENVS envs per workgroup.  The view is the caller's mw_state_view by value: device pointers, null = field not asked for.

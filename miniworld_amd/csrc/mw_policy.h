@@ -196,8 +196,8 @@ struct FrameFacts {
 };
 struct FramePolicy {
     bool reuse;         // clean envs may stay undrawn
-    bool source;        // the quad kernel writes the per-env source byte
-    bool cache;         // ... and consults and fills the frame cache
+    bool source;        // a plain step through the quad kernel: the per-env source byte tells of this frame (K1's zeros; the plan kernel's verdicts, frame_plans)
+    bool cache;         // ... and the frame consults and fills the frame cache
     bool hold;          // afterwards the call's buffers are the held ones
 };
 inline FramePolicy frame_policy(const FrameFacts &f)
@@ -208,6 +208,14 @@ inline FramePolicy frame_policy(const FrameFacts &f)
     const bool source = plain_step && f.path == MW_PATH_QUAD;
     return {f.frame_reuse && plain_step && bare && f.held_match, source,
             source && f.cache_allocated && bare && f.layout == MW_OBS_HWC_U8 && f.task != MW_TASK_COLLECT, plain || seeded_pass};
+}
+
+// The frame plan (mw_frame_plan_kernel, behind the geometry kernel): made exactly for the frames whose quad kernel may leave an env
+// undrawn — the whole batch (no list) through the quad kernel alone, with clean envs that may stay (reuse) or a cache to consult
+// (cache).  Its entries keep the env in 24 bits (mw_frame_plan.h); a larger batch is drawn in full, which is always right.
+inline bool frame_plans(const FramePolicy &pol, int path, bool listed, int N)
+{
+    return !listed && path == MW_PATH_QUAD && (pol.reuse || pol.cache) && N <= 0xFFFFFF;
 }
 
 // The tile kernels' launch (mw_raster.hip) for a part of the frame (raster_flags).  big scenes (a visiting order exists): records

@@ -545,6 +545,17 @@ __device__ inline void batch_exact(const QCtx &cx, int kmax, Tri tri, RecOf recp
 }
 
 // ---- the kernel -------------------------------------------------------------------------------------------------------------
+#ifdef MW_PERF_HOOKS
+// per-workgroup residency (perf builds only; tools/perf/k2qprof.py), by blockIdx in a third region of the stamps, [N][16]: [0] the
+// first instruction, [1] kind (0 drawn, 1 clean, 2 copied, 3 idle), [2 + wave] the wavefront's exit — s_memrealtime, the 100 MHz
+// clock every XCD shares (s_memtime, the phase stamps' clock, has an origin of its own on every XCD)
+#define MWQ_WG_BEGIN() const unsigned long long wg_t0 = prof ? __builtin_amdgcn_s_memrealtime() : 0ull
+#define MWQ_WG_END(kind) do { if (prof && (threadIdx.x & 63) == 0) { unsigned long long *w_ = prof + (size_t)N * (MWQ_WAVES * 8 + 16) + (size_t)blockIdx.x * 16; \
+    if (threadIdx.x == 0) { w_[0] = wg_t0; w_[1] = (kind); } w_[2 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
+#else
+#define MWQ_WG_BEGIN() do {} while (0)
+#define MWQ_WG_END(kind) do {} while (0)
+#endif
 // SUB: the frame of a subset of the batch (mw_engine_frame.hip, same-step auto-reset with final observations): workgroup e draws env
 // list[1 + e] while e < list[0] and exits at once otherwise (before any barrier: the whole workgroup)
 template <int S, bool SUB = false>
@@ -553,44 +564,34 @@ __device__ inline void rasterq_body(
     const float *__restrict__ rec_raster, const float *__restrict__ rec_shade, const float *__restrict__ rec_cull,
     const int32_t *__restrict__ nvis_arr, const float *__restrict__ envhdr, const uint32_t *__restrict__ texels,
     uint8_t *__restrict__ obs, float *__restrict__ depth, int dbg, int texel_bytes, unsigned long long *__restrict__ prof,
-    const uint8_t *__restrict__ frame_clean, const MwFcArgs *__restrict__ fc, uint8_t *__restrict__ frame_source,
-    const int32_t *__restrict__ list = nullptr)
+    const MwFcArgs *__restrict__ fc, const uint32_t *__restrict__ plan, const int32_t *__restrict__ list = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef QRec<S> R;
+    MWQ_WG_BEGIN();
     int env = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool has_depth = depth != nullptr;
+    uint32_t fc_victim = 0u;        // the slot of the frame cache this frame goes to: kept in LDS from phase 0 on (s_misc[20])
     if (SUB) {
         if (env >= list[0]) return;
         env = list[1 + env];
     } else if (env >= N) return;
-    // the buffer holds this env's frame already (MW_RASTER_REUSE, mw_kernels.h): the whole workgroup, before any barrier
-    if (!SUB && (dbg & MW_RASTER_REUSE) && frame_clean[env]) {
-        if (frame_source && threadIdx.x == 0) frame_source[env] = 1;
-        return;
-    }
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool has_depth = depth != nullptr;
-    // The frame cache (mw_kernels.h): every wavefront compares the env's key with the slots' keys, a 16-byte quad per lane, and
-    // reaches the same verdict from the same bytes — nothing writes them before phase E, behind the barriers every wavefront of a
-    // drawing workgroup passes.  A hit copies the slot's frame and leaves, the whole workgroup, before any barrier.
-    uint32_t fc_victim = 0u;        // the slot this frame goes to when it is drawn: kept in LDS from phase 0 on (s_misc[20])
-    if (!SUB && fc) {
-        const int fc_slots = fc->slots;
-        const uint64_t *meta = fc->meta + (size_t)env * MW_FC_META_WORDS(fc_slots);
-        const uint4 *cur = reinterpret_cast<const uint4 *>(fc->key + (size_t)env * MW_FC_KEY_WORDS);
-        // (lane 63 fetches the env's header beside the keys: one round trip to memory for both)
-        bool eq = false;
-        uint4 k = make_uint4(0u, 0u, 0u, 0u);
-        if (lane < fc_slots * (MW_FC_KEY_WORDS / 2)) {
-            const uint4 c = cur[lane % (MW_FC_KEY_WORDS / 2)];
-            k = reinterpret_cast<const uint4 *>(meta + 2)[lane];
-            eq = k.x == c.x && k.y == c.y && k.z == c.z && k.w == c.w;
-        } else if (lane == 63) k = reinterpret_cast<const uint4 *>(meta)[0];
-        const uint64_t m = __builtin_amdgcn_ballot_w64(eq);
-        int hit = -1;
-        for (int j = fc_slots - 1; j >= 0; --j)
-            if (((m >> (j * (MW_FC_KEY_WORDS / 2))) & 31ull) == 31ull) hit = j;
-        if (hit >= 0) {
+    else if (plan) {
+        // The frame plan (mw_frame_plan.h; mw_frame_plan_kernel ran behind the geometry kernel): the first n_draw workgroups of the
+        // launch draw the listed envs, the n_copy behind them copy a cached frame each, the rest have nothing to do.  Every decision
+        // below is the whole workgroup's, from scalar loads, before any barrier.
+        const uint32_t b = blockIdx.x, n_draw = plan[0];
+        if (b < n_draw) {
+            const uint32_t entry = plan[MW_PLAN_HEAD + b];
+            env = (int)(entry & MW_PLAN_ENV_MASK);
+            fc_victim = entry >> MW_PLAN_ENV_BITS;
+        } else {
+            if (b - n_draw >= plan[1] || !fc) { MWQ_WG_END(3); return; }
+            // a hit: the slot's frame, and its depth map, into the caller's buffers
+            const uint32_t entry = plan[MW_PLAN_HEAD + (size_t)N + (b - n_draw)];
+            env = (int)(entry & MW_PLAN_ENV_MASK);
+            const int hit = (int)(entry >> MW_PLAN_ENV_BITS), fc_slots = fc->slots;
             const int fbytes = W * H * 3;           // (a multiple of 64 bytes: the quad path draws frames on the 16x4 grid only)
             const uint8_t *src = fc->frames + ((size_t)env * fc_slots + hit) * fbytes;
             uint8_t *dst = obs + (size_t)env * fbytes;
@@ -608,10 +609,9 @@ __device__ inline void rasterq_body(
                 else
                     for (int i = tid; i < W * H; i += MWQ_THREADS) zd[i] = zs[i];
             }
-            if (frame_source && tid == 0) frame_source[env] = (uint8_t)(2 + hit);
+            MWQ_WG_END(2);
             return;
         }
-        fc_victim = min((uint32_t)__builtin_amdgcn_readlane((int)k.x, 63), (uint32_t)(fc_slots - 1));
     }
     const QPlan pl = q_plan(S, W, H, n_tiles, has_depth);
     float4 *s_rec = reinterpret_cast<float4 *>(smem + pl.rec);
@@ -1040,11 +1040,12 @@ __device__ inline void rasterq_body(
             reinterpret_cast<uint4 *>(meta + 2 + MW_FC_KEY_WORDS * victim)[tid] = reinterpret_cast<const uint4 *>(fc->key + (size_t)env * MW_FC_KEY_WORDS)[tid];
         if (tid == 64) meta[0] = (uint64_t)(victim + 1u == (uint32_t)fc_slots ? 0u : victim + 1u);
     }
+    MWQ_WG_END(0);
 }
 
 }  // namespace
 
-#define MWQ_FWD N, W, H, max_vis, tiles_x, n_tiles, rec_raster, rec_shade, rec_cull, nvis_arr, envhdr, texels, obs, depth, dbg, texel_bytes, prof, frame_clean, fc, frame_source
+#define MWQ_FWD N, W, H, max_vis, tiles_x, n_tiles, rec_raster, rec_shade, rec_cull, nvis_arr, envhdr, texels, obs, depth, dbg, texel_bytes, prof, fc, plan
 // each kernel and its list form over the envs of a list (int32 [0] count, [1 + i] env)
 #define MWQ_PAIR(stem, bounds, ...)                                                                          \
     extern "C" __global__ bounds void stem##_kernel(MWQ_ARGS) { rasterq_body<__VA_ARGS__, false>(MWQ_FWD); } \
