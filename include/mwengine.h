@@ -685,8 +685,61 @@ int mw_snapshot_load_frames_where(mw_engine *e, const uint8_t *d_mask, const int
                                   int32_t n_recs, int32_t capacity, int32_t flags, uint8_t *d_obs, float *d_depth,
                                   void *stream);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where skipped — these are
- * reported first, by one check, and then forgotten, the others by every check from then on); synchronises `stream` */
+/* ---- navigation fields ------------------------------------------------------- */
+/* The shortest-path cost from every cell of a grid over each env's floor plan to a target, with the walls in the way, and the next
+ * cell on the way down: what navigation suites around comparable simulators ship as geodesic distance and shortest-path follower.
+ * The reference has no such call; its users run Dijkstra on the host over env.wall_segs.  The two predicates are the reference's own:
+ * a cell is blocked where a circle of the agent's radius (+ margin) at its centre meets a wall, by the closest-point test of
+ * intersect_circle_segs (math.py:30-62), and the cells a slot target is reached from are those where near(ent) (miniworld.py:965-975)
+ * holds in the floor plane.
+ *
+ * The grid: gx x gz cells of side `cell`, origin (min_x, min_z) of the env's own extent; the centre of cell (j, i) is
+ * (min_x + (i + 0.5) * cell, min_z + (j + 0.5) * cell).  A cell is BLOCKED when its centre lies beyond max_x or max_z, when the
+ * distance from its centre to a collision segment is < agent_radius + margin, or — with MW_NAV_ENTITIES — when
+ * sqrt(dx*dx + dz*dz) < agent_radius + radius(slot) + margin for a slot that is not MW_ENT_NONE, not carried and not the target slot.
+ * SOURCES are the unblocked cells whose centre is closer (in x, z) than `reach` to the target: row i of d_target (double[N][3]; y is
+ * not read) with params->reach, or — d_target NULL — the position of entity slot target_slot, with that slot's near() threshold
+ * radius + agent_radius + 1.1 * max_forward_step (formed in float32 for a mesh entity, as near() forms it).  A move to one of the 8
+ * neighbours costs 5 (straight) or 7 (diagonal; both cells the move passes between must be unblocked).
+ * The field: uint16[N][gz][gx]; 0xFFFF a blocked cell, 0xFFFE an unblocked cell no path reaches (no source at all: every unblocked
+ * cell — not an error), every other value the exact cost of the cheapest path.  The result does not depend on the kernel's schedule. */
+#define MW_NAV_ENTITIES 1       /* flags: entities block cells too */
+#define MW_NAV_JACOBI 2         /* flags: relax by whole-grid passes instead of directional sweeps (measurement only: the same field) */
+#define MW_NAV_BLOCKED 0xFFFF
+#define MW_NAV_UNREACHED 0xFFFE
+#define MW_NAV_MAX_CELLS 32768  /* gx * gz: the grid lives in 64 KiB of LDS */
+typedef struct mw_nav_params {
+    double cell;            /* side of a cell, > 0 */
+    double margin;          /* added to the agent's radius, >= 0 */
+    double reach;           /* point targets only: > 0 */
+    int32_t gx, gz;         /* cells along x and z, >= 1, gx * gz <= MW_NAV_MAX_CELLS */
+    int32_t flags;          /* MW_NAV_* */
+    int32_t target_slot;    /* 0 .. max_ents - 1 (read where d_target is NULL, checked always) */
+} mw_nav_params;
+/* mw_nav_build: rows of d_field for every env i with d_mask[i] != 0 (d_mask uint8[N] on the device, NULL = all); other rows are not
+ * touched.  One kernel, one workgroup per env, asynchronous on `stream`, no host value read; it reads live arrays only and changes
+ * nothing in the engine.  An env whose extent the grid does not cover (the centre of the first cell past the grid is not beyond max_x /
+ * max_z), or one of whose costs would reach 0xFFFE, gets a row of 0xFFFF throughout and sets a status bit that the next mw_check
+ * reports as MW_E_INVALID, once.  MW_E_INVALID before anything is launched: a null engine, params or field, cell <= 0, gx or gz < 1,
+ * more than MW_NAV_MAX_CELLS cells, margin < 0, a target slot outside 0 .. max_ents - 1, reach <= 0 with point targets. */
+int mw_nav_build(mw_engine *e, const mw_nav_params *params, const uint8_t *d_mask, const double *d_target, uint16_t *d_field, void *stream);
+/* mw_nav_query: one thread per env, for the agents' positions (d_pos NULL) or row i of d_pos (double[N][3]; y is not read).  The
+ * env's cell is floor((x - min_x) / cell), floor((z - min_z) / cell), clamped to the grid; if it is blocked, the lowest-cost unblocked
+ * cell of its 3 x 3 neighbourhood stands in (0xFFFE counts as unblocked; ties: the first in the order below).  None, or a cell of
+ * 0xFFFE: cost -1, next -1, the waypoint is the position itself.  Else
+ *   d_cost[i]      int32, the cell's cost
+ *   d_next[i]      int32, j * gx + i of the admissible neighbour of strictly lower cost with the lowest cost — ties go to the first in
+ *                  the order (dj, di) = (-1,0), (1,0), (0,-1), (0,1), (-1,-1), (-1,1), (1,-1), (1,1) —, the cell itself at cost 0
+ *   d_waypoint[i]  double[2], that cell's centre x, z; at cost 0 the target's x, z (d_target as for the build that made the field)
+ * Any of the three outputs may be NULL.  The same argument checks as mw_nav_build. */
+int mw_nav_query(mw_engine *e, const mw_nav_params *params, const double *d_target, const uint16_t *d_field, const double *d_pos,
+                 int32_t *d_cost, int32_t *d_next, double *d_waypoint, void *stream);
+/* measurements: d_passes, int32[N] on the device, gets the relaxation's count of rounds of every env each later mw_nav_build builds;
+ * NULL stops that */
+int mw_debug_set_nav_passes(mw_engine *e, int32_t *d_passes);
+
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where or mw_nav_build skipped
+ * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 
 /* ---- measurement ------------------------------------------------------------- */

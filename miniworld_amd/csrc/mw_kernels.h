@@ -7,6 +7,7 @@
 #include "mw_snapshot.h"
 #include "mw_snapframes.h"
 #include "mw_state_view.h"
+#include "mw_nav.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -235,6 +236,19 @@ extern "C" __global__ void mw_state_set_where_kernel(MwStateArrays a, mw_state_v
                                                      uint32_t *__restrict__ status, uint8_t *__restrict__ reset_pending,
                                                      uint8_t *__restrict__ frame_clean, uint32_t *__restrict__ fc_epoch,
                                                      uint8_t *__restrict__ stack_flags);
+
+// navigation fields (mw_nav.hip; the arithmetic, the phases and MwNavArgs: mw_nav.h).  The parameters are the caller's mw_nav_params by
+// value; d_target null = the slot target.
+//   build  grid N workgroups of MW_NAV_THREADS lanes, 2 * gx * gz bytes of dynamic LDS; env b's row of `field` where mask is null or
+//          mask[b] != 0; passes: null, or int32[N] that gets the env's count of relaxation rounds (measurements)
+//   query  a lane per env; pos null = the agents; cost, next, waypoint: any may be null
+#define MW_NAV_THREADS 512
+#define MW_NAV_QUERY_THREADS 256
+extern "C" __global__ void mw_nav_build_kernel(MwNavArgs a, mw_nav_params p, const uint8_t *__restrict__ mask, const double *__restrict__ d_target,
+                                               uint16_t *__restrict__ field, int32_t *__restrict__ passes);
+extern "C" __global__ void mw_nav_query_kernel(MwNavArgs a, mw_nav_params p, const double *__restrict__ d_target, const uint16_t *__restrict__ field,
+                                               const double *__restrict__ pos, int32_t *__restrict__ cost, int32_t *__restrict__ next,
+                                               double *__restrict__ waypoint);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -48,6 +48,7 @@ EXPORTS = [
     "mw_snapshot_save_at", "mw_snapshot_save_frames_at", "mw_snapshot_load_where", "mw_snapshot_load_frames_where",
     "mw_reset_where", "mw_set_reset_seeds",
     "mw_get_state_device", "mw_set_state_where",
+    "mw_nav_build", "mw_nav_query", "mw_debug_set_nav_passes",
 ]
 
 
@@ -120,6 +121,16 @@ class MwStateView(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in (
         "agent_pos", "agent_dir", "cam", "light", "carrying", "step_count", "num_picked_up",
         "ent_kind", "ent_mesh", "ent_static", "ent_pos", "ent_dir", "ent_geom", "extent")]
+
+
+NAV_ENTITIES, NAV_JACOBI = 1, 2         # MW_NAV_* flags
+NAV_BLOCKED, NAV_UNREACHED = 0xFFFF, 0xFFFE
+NAV_MAX_CELLS = 32768                   # MW_NAV_MAX_CELLS
+
+
+class MwNavParams(C.Structure):
+    _fields_ = [("cell", C.c_double), ("margin", C.c_double), ("reach", C.c_double), ("gx", C.c_int32), ("gz", C.c_int32),
+                ("flags", C.c_int32), ("target_slot", C.c_int32)]
 
 
 class MwPlanTrace(C.Structure):
@@ -201,6 +212,9 @@ def load_library():
     L.mw_get_state.argtypes = [vp, i32, i32, C.POINTER(MwStateView)]
     L.mw_get_state_device.argtypes = [vp, i32, i32, C.POINTER(MwStateView), vp]
     L.mw_set_state_where.argtypes = [vp, vp, C.POINTER(MwStateView), vp]
+    L.mw_nav_build.argtypes = [vp, C.POINTER(MwNavParams), vp, vp, vp, vp]
+    L.mw_nav_query.argtypes = [vp, C.POINTER(MwNavParams), vp, vp, vp, vp, vp, vp, vp]
+    L.mw_debug_set_nav_passes.argtypes = [vp, vp]
     L.mw_set_step_params.argtypes = [vp, vp]
     L.mw_set_gen_program.argtypes = [vp, C.POINTER(MwGenProgram), vp, vp, vp, vp, i32, vp, i32]
     L.mw_reset.argtypes = [vp, vp, vp, vp]
@@ -423,6 +437,40 @@ class Engine:
             raise EngineError("set_state_where: no field named")
         view = self._device_view(arrays, self.N)
         self._check(self.lib.mw_set_state_where(self.h, _ptr(mask), C.byref(view), _stream_ptr(self.device)), "mw_set_state_where")
+
+    # -- navigation fields ---------------------------------------------------------------
+    def _nav_tensors(self, params: MwNavParams, field, target):
+        import torch
+        self._dev_tensor(field, "field", torch.uint16, self.N * params.gx * params.gz)
+        self._dev_tensor(target, "target", torch.float64, self.N * 3)
+
+    def nav_build(self, params: MwNavParams, field, mask=None, target=None):
+        """mw_nav_build: rows of `field` (uint16[N, gz, gx], device) for the envs under `mask` (uint8[N], device; None = all) := the
+        shortest-path cost to `target` (float64[N, 3], device; None = entity slot params.target_slot).  One kernel on the current
+        stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the library is called."""
+        self._nav_tensors(params, field, target)
+        if mask is not None:
+            mask = self._mask_tensor(mask)
+        self._check(self.lib.mw_nav_build(self.h, C.byref(params), _ptr(mask), _ptr(target), _ptr(field), _stream_ptr(self.device)), "mw_nav_build")
+
+    def nav_query(self, params: MwNavParams, field, target=None, pos=None, cost=None, next=None, waypoint=None):
+        """mw_nav_query: for the agents (pos None) or the rows of `pos` (float64[N, 3], device): cost int32[N], next int32[N] and
+        waypoint float64[N, 2], whichever are given.  `target` as for the nav_build that made the field."""
+        import torch
+        self._nav_tensors(params, field, target)
+        self._dev_tensor(pos, "pos", torch.float64, self.N * 3)
+        self._dev_tensor(cost, "cost", torch.int32, self.N)
+        self._dev_tensor(next, "next", torch.int32, self.N)
+        self._dev_tensor(waypoint, "waypoint", torch.float64, self.N * 2)
+        self._check(self.lib.mw_nav_query(self.h, C.byref(params), _ptr(target), _ptr(field), _ptr(pos), _ptr(cost), _ptr(next), _ptr(waypoint),
+                                          _stream_ptr(self.device)), "mw_nav_query")
+
+    def debug_set_nav_passes(self, passes):
+        """Measurements: int32[N] on the device that every later nav_build fills with its relaxation's round count per env; None stops."""
+        import torch
+        self._dev_tensor(passes, "passes", torch.int32, self.N)
+        self._nav_passes = passes       # (kept alive while the engine holds its pointer)
+        self._check(self.lib.mw_debug_set_nav_passes(self.h, _ptr(passes)), "mw_debug_set_nav_passes")
 
     def set_gen_program(self, prog: MwGenProgram, polys: np.ndarray, poly_room, poly_surf, poly_m, segs: np.ndarray):
         """Installs the placement program of an MW_GEN_PROGRAM engine (include/mwengine.h: mw_set_gen_program)."""

@@ -28,6 +28,26 @@ from . import engine as eng
 from . import envs as _envs
 from .scene import base_config, polys_array, scene_from_env, state_arrays, upload_scene_meshes
 
+class NavField:
+    """A navigation field (MiniWorldVecEnv.nav_field): `field`, the uint16[N, gz, gx] device tensor of shortest-path costs — 0xFFFF a
+    blocked cell, 0xFFFE one no path reaches, a move costs 5 straight and 7 diagonally —, the grid (`cell` metres per cell, gx x gz
+    cells from the env's own min_x, min_z), and what it leads to: `target`, an entity slot or a float64[N, 3] device tensor.  The
+    tensor is the caller's, like a level bank: the engine keeps nothing of it."""
+
+    def __init__(self, field, params, target, obstacles):
+        self.field, self.params, self.target, self.obstacles = field, params, target, obstacles
+
+    cell = property(lambda self: self.params.cell)
+    margin = property(lambda self: self.params.margin)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+
+    @property
+    def points(self):
+        """the device tensor of point targets, or None for a slot target"""
+        return None if isinstance(self.target, int) else self.target
+
+
 _KIND = {
     "MiniWorld-Hallway-v0": ("Hallway", eng.GEN_HALLWAY, eng.TASK_GOTO, 3),
     "MiniWorld-OneRoom-v0": ("OneRoom", eng.GEN_ONEROOM, eng.TASK_GOTO, 3),
@@ -343,6 +363,7 @@ class MiniWorldVecEnv:
         self._info_buf = None
         self._final_info_buf = None
         self._state_bufs = {}           # state()'s tensors, one per field, made on first use
+        self._nav_bufs = None           # nav_query()'s tensors, made on first use
         self._fork_buf = None           # fork()'s scratch records, made on first use
         self._fork_frames = None        # ... and its scratch frame records (fork(src, frames=True))
         # autoreset="levels": the bank (set_levels), the level each env plays and the one it gets when its episode ends
@@ -853,6 +874,97 @@ class MiniWorldVecEnv:
             self.engine._state_tensor(t, name, self.num_envs)
         self.engine.set_state_where(mask, arrays)
         return self._redraw()
+
+    # ------------------------------------------------------------------ navigation fields
+    NAV_OBSTACLES = {"walls": 0, "walls+entities": eng.NAV_ENTITIES}
+
+    def nav_field(self, target=None, mask=None, cell=0.25, obstacles="walls", margin=None, reach=None, into=None):
+        """The shortest-path cost to a target from every cell of a grid over each env's floor plan, walls in the way, built on the
+        device by one kernel (mw_nav_build) with no host value and no synchronisation: a NavField.
+
+        target     None: the env's goal entity (cfg.goal_ent); an int: that entity slot — the field starts from the cells where the
+                   env's own near() test would hold —; or a float64[N, 3] device tensor of points with `reach` metres around them
+        cell       metres per cell; gx, gz follow from the template world's extent, which the family's constructor arguments fix
+        obstacles  "walls", or "walls+entities": every listed entity but the target and the carried one blocks cells too
+        margin     kept from walls beyond the agent's radius; default cell / 2
+        mask       uint8[N] or bool[N] device tensor: only those envs' rows are built (the others are not touched)
+        into       a NavField of this call's parameters to rebuild in place — `nav_field(into=field, mask=done)` behind a step keeps
+                   the field current across auto-resets; without it a new tensor is allocated (unmasked rows: 0xFFFF)
+        An env whose extent the grid does not cover, or one whose costs do not fit 16 bits, gets a row of 0xFFFF and engine.check()
+        raises once.  ValueError for arguments that make no field; nothing is launched then."""
+        torch, e = self.torch, self.engine
+        if into is not None:
+            if not isinstance(into, NavField):
+                raise ValueError("nav_field: `into` must be a NavField")
+            if target is not None or margin is not None or reach is not None or (cell, obstacles) != (0.25, "walls"):
+                raise ValueError("nav_field: with `into` the field's own target and parameters are used: pass only mask")
+            field, params, target = into.field, into.params, into.target
+        else:
+            if obstacles not in self.NAV_OBSTACLES:
+                raise ValueError(f"nav_field: obstacles {obstacles!r}; have {sorted(self.NAV_OBSTACLES)}")
+            if not (isinstance(cell, (int, float)) and cell > 0 and math.isfinite(cell)):
+                raise ValueError(f"nav_field: cell {cell!r} must be a positive length")
+            margin = cell / 2 if margin is None else margin
+            if not (margin >= 0 and math.isfinite(margin)):
+                raise ValueError(f"nav_field: margin {margin!r} < 0")
+            if target is None:
+                target = int(e.cfg.goal_ent)
+                if target < 0:
+                    raise ValueError("nav_field: this env has no goal entity: name a target slot or points")
+            if torch.is_tensor(target):
+                if tuple(target.shape) != (self.num_envs, 3) or target.dtype != torch.float64 or target.device != e.device or not target.is_contiguous():
+                    raise ValueError(f"nav_field: point targets are a contiguous float64 tensor [{self.num_envs}, 3] on {e.device}")
+                if reach is None or not (reach > 0 and math.isfinite(reach)):
+                    raise ValueError(f"nav_field: point targets need reach > 0, got {reach!r}")
+            elif isinstance(target, (int, np.integer)) and not isinstance(target, bool):
+                target = int(target)
+                if not 0 <= target < e.cfg.max_ents:
+                    raise ValueError(f"nav_field: target slot {target} outside 0 .. {e.cfg.max_ents - 1}")
+                if reach is not None:
+                    raise ValueError("nav_field: a slot target's reach is the env's own near() distance: pass no reach")
+            else:
+                raise ValueError(f"nav_field: target is None, an entity slot or a float64[N, 3] device tensor, not {type(target).__name__}")
+            t = self.template
+            gx = max(1, math.ceil((float(t.max_x) - float(t.min_x)) / cell))
+            gz = max(1, math.ceil((float(t.max_z) - float(t.min_z)) / cell))
+            if gx * gz > eng.NAV_MAX_CELLS:
+                raise ValueError(f"nav_field: {gx} x {gz} cells > {eng.NAV_MAX_CELLS}: use a larger cell")
+            params = eng.MwNavParams(float(cell), float(margin), float(reach or 0.0), gx, gz, self.NAV_OBSTACLES[obstacles],
+                                     target if isinstance(target, int) else 0)
+            # (0xFFFF throughout; filled as int16: the 16-bit unsigned type has few kernels of its own)
+            field = torch.full((self.num_envs, gz, gx), -1, dtype=torch.int16, device=e.device).view(torch.uint16)
+        if mask is not None:
+            if not torch.is_tensor(mask) or tuple(mask.shape) != (self.num_envs,) or mask.dtype not in (torch.uint8, torch.bool):
+                raise ValueError(f"nav_field: mask is a uint8 or bool tensor [{self.num_envs}]")
+            if mask.dtype == torch.bool:
+                mask = mask.view(torch.uint8)       # (one byte per element, 0 / 1: no conversion kernel)
+        out = into if into is not None else NavField(field, params, target, obstacles)
+        e.nav_build(params, field, mask, out.points)
+        return out
+
+    def nav_query(self, field, pos=None):
+        """Where each env's agent — or row i of `pos`, float64[N, 3] on the device — stands in `field` (a NavField), by one small
+        kernel (mw_nav_query), no host value: {"cost": int32[N], the cell's cost, -1 where no path leads to the target; "next":
+        int32[N], the flat index j * gx + i of the neighbouring cell to go to (-1 without a path); "waypoint": float64[N, 2], that
+        cell's centre x, z — the target's own x, z once the cell is a source —; "distance": float32[N], cost * cell / 5 in metres,
+        inf where there is no path}.  The distance is the grid's metric — straight and diagonal moves of 5 and 7 — which
+        over-estimates the Euclidean geodesic by up to 8 % and is exact along the axes.  A position in a blocked cell (an agent may
+        stand closer to a wall than the field's margin) is answered from the best unblocked cell around it.  The tensors are this
+        env's own, reused between calls."""
+        torch, e = self.torch, self.engine
+        if not isinstance(field, NavField):
+            raise ValueError("nav_query: `field` must be a NavField (nav_field())")
+        if pos is not None and (not torch.is_tensor(pos) or tuple(pos.shape) != (self.num_envs, 3) or pos.dtype != torch.float64
+                                or pos.device != e.device or not pos.is_contiguous()):
+            raise ValueError(f"nav_query: pos is a contiguous float64 tensor [{self.num_envs}, 3] on {e.device}")
+        if self._nav_bufs is None:
+            n = self.num_envs
+            self._nav_bufs = {"cost": torch.zeros(n, dtype=torch.int32, device=e.device), "next": torch.zeros(n, dtype=torch.int32, device=e.device),
+                              "waypoint": torch.zeros((n, 2), dtype=torch.float64, device=e.device)}
+        b = self._nav_bufs
+        e.nav_query(field.params, field.field, field.points, pos, b["cost"], b["next"], b["waypoint"])
+        dist = torch.where(b["cost"] < 0, float("inf"), b["cost"].to(torch.float32) * (field.cell / 5.0)).to(torch.float32)
+        return {"cost": b["cost"], "next": b["next"], "waypoint": b["waypoint"], "distance": dist}
 
     def _redraw(self):
         self.engine.render(self.obs, self.depth)
