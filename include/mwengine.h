@@ -825,6 +825,16 @@ int mw_set_frame_cache(mw_engine *e, int32_t slots);
 /* d_out uint8[N] (device): where each env's frame of the last plain mw_step came from — 0 drawn, 1 left alone as clean (frame reuse),
  * 2 + j copied from slot j of the frame cache.  The step kernel stores 0, the frame plan in front of the quad kernel the rest: zeros on the other raster paths.  Asynchronous on `stream`. */
 int mw_get_frame_source(mw_engine *e, uint8_t *d_out, void *stream);
+/* Test and diagnosis call (synchronises `stream`; the step path itself never does, and stays capturable): the frame plan the last
+ * planned frame was drawn from — the plain whole-batch steps through the quad kernel with frame reuse or the frame cache on — copied
+ * to the host with the cost inputs it was built from.  host_plan: the block, uint32[words]; words must be 96 + 9 N for N <= 65535
+ * envs (an ordered plan) and 96 + 2 N beyond.  [0] draw entries, [1] copy entries, [2] 8 in an ordered plan and 0 otherwise,
+ * [32..33] and [64..65] the entries of cost classes 0..3 and 4..7, 16 bits each, the lowest class in the lowest bits; from [96] N
+ * places for copy entries env | slot << 24; from [96 + N] the draw entries env | victim slot << 24 — ordered: N places per cost
+ * class, class 0 first; else one list.  The quad kernel's workgroups take the draw entries from the highest class down, then the
+ * copies.  host_lengths: int32[N], the display-list length of every env in the last frame; an env's cost class is min(7, length / 4).
+ * MW_E_INVALID before the first planned frame. */
+int mw_get_frame_plan(mw_engine *e, uint32_t *host_plan, int64_t words, int32_t *host_lengths, void *stream);
 
 /* Diagnostic (synchronises `stream`): how many triangles the last frame's display list held per env after clipping and culling —
  * what max_visible has to pay for (6 records per unit), and what decides which raster kernel an env's frame takes.

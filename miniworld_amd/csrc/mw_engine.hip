@@ -224,7 +224,7 @@ int init_engine(mw_engine *e, const mw_config *cfg)
     ALLOC(a.nvis, N); ALLOC(a.envhdr, (size_t)MW_ENVHDR * N); ALLOC(a.status, 1);
     ALLOC(e->d_reward_scratch, N); ALLOC(e->d_flag_scratch, 2 * (size_t)N);
     ALLOC(e->d_final_list, 1 + (size_t)N);
-    ALLOC(e->d_plan[0], MW_PLAN_WORDS(N)); ALLOC(e->d_plan[1], MW_PLAN_WORDS(N));      // (zeroed: the first plan kernel counts from nothing)
+    ALLOC(e->d_plan[0], MW_PLAN_WORDS(N, frame_plan_ordered(N))); ALLOC(e->d_plan[1], MW_PLAN_WORDS(N, frame_plan_ordered(N)));      // (zeroed: the first plan kernel counts from nothing)
     ALLOC(e->stack.flags, 2 * (size_t)N);
     ALLOC(e->d_mask, N); ALLOC(e->d_step_override, 3 * (size_t)N);
 #ifdef MW_PERF_HOOKS        // (tools/perf: make EXTRA=-DMW_PERF_HOOKS — kernel phase stamps dumped by mw_destroy; not in the product build)
@@ -808,6 +808,20 @@ int mw_get_reset_pending(mw_engine *e, uint8_t *d_out, void *stream)
 int mw_get_frame_source(mw_engine *e, uint8_t *d_out, void *stream)
 {
     return e ? get_env_bytes(e, "mw_get_frame_source", e->args.fc_source, d_out, stream) : MW_E_INVALID;
+}
+
+int mw_get_frame_plan(mw_engine *e, uint32_t *host_plan, int64_t words, int32_t *host_lengths, void *stream)
+{
+    if (!e || !host_plan || !host_lengths) return fail(e, MW_E_INVALID, "mw_get_frame_plan: null argument");
+    const int N = e->cfg.num_envs;
+    const size_t want = MW_PLAN_WORDS(N, frame_plan_ordered(N));
+    if (words != (int64_t)want) return fail(e, MW_E_INVALID, "mw_get_frame_plan: %lld words given, the block has %zu", (long long)words, want);
+    if (!e->plan_made) return fail(e, MW_E_INVALID, "mw_get_frame_plan: no frame of this engine has been planned yet");
+    ON_DEVICE(e);
+    HIP_TRY(e, hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(e, hipMemcpy(host_plan, e->d_plan[e->plan_cur ^ 1], want * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(host_lengths, e->args.nvis, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    return MW_OK;
 }
 
 int mw_get_frame_clean(mw_engine *e, uint8_t *d_out, void *stream)

@@ -293,8 +293,10 @@ const uint32_t *launch_plan(mw_engine *e, const Frame &f, hipStream_t st)
     const MwArgs &a = f.a; const int N = e->cfg.num_envs;
     uint32_t *plan = e->d_plan[e->plan_cur], *next = e->d_plan[e->plan_cur ^ 1];
     e->plan_cur ^= 1;
+    e->plan_made = true;
     hipLaunchKernelGGL(mw_frame_plan_kernel, dim3((N + MW_PLAN_ENVS - 1) / MW_PLAN_ENVS), dim3(64), 0, st, N, f.pol.reuse ? 1 : 0, (const uint8_t *)a.frame_clean,
-                       (const uint64_t *)a.fc_key, f.pol.cache ? (const uint64_t *)e->fc.meta.get() : nullptr, f.pol.cache ? e->fc.slots : 0, a.fc_source, plan, next);
+                       (const uint64_t *)a.fc_key, f.pol.cache ? (const uint64_t *)e->fc.meta.get() : nullptr, f.pol.cache ? e->fc.slots : 0,
+                       frame_plan_ordered(N) ? (const int32_t *)a.nvis : nullptr, a.fc_source, plan, next);
     return plan;
 }
 

@@ -68,22 +68,33 @@ extern "C" __global__ __launch_bounds__(256) void mw_final_copy_kernel(const int
 // plan block), behind the geometry kernel: per env the source byte (mw_get_frame_source) and, unless the env is left alone, an entry in
 // the draw list or the copy list.  A lane per env, MW_PLAN_ENVS = 64 envs per wavefront: the lane loads the clean byte, the key K1
 // stored for this frame, the header and the keys of all MW_FC_MAX_SLOTS slots — the slots the cache does not have re-read its last one
-// and do not count —, every load issued before the first comparison: one round trip to memory.  The appends are aggregated per
-// wavefront: two ballots, then ONE 64-bit atomic per wavefront on the two counts (one word takes ~88 atomics/us: an atomic per env,
-// or two per eight envs, cost more than the rest of the kernel — 14.6 us measured at 4096 envs against 5.4 this way).  No LDS; grid
-// ceil(N / MW_PLAN_ENVS) wavefronts.
-// reuse: MW_RASTER_REUSE applies; meta: the cache's key table, null without a cache (slots 0); next: the engine's other plan block,
-// whose counts this launch zeroes for the frame after this one.
+// and do not count — and, for an ordered plan, the length of its display list, every load issued before the first comparison: one
+// round trip to memory.  The appends are aggregated per wavefront: ballots, then ONE atomic instruction per wavefront — lane 0 adds
+// to the two counts as one 64-bit word, and in an ordered plan lanes 1 and 2 add the wavefront's eight class counts, four 16-bit
+// fields to a word, each word on a line of its own (one line takes ~88 atomics/us: an atomic per env, or two per eight envs, cost more
+// than the rest of the kernel — 14.6 us measured at 4096 envs against 5.4 with one per wavefront).  No LDS; grid ceil(N /
+// MW_PLAN_ENVS) wavefronts.
+// reuse: MW_RASTER_REUSE applies; meta: the cache's key table, null without a cache (slots 0); nvis: the display lists' lengths for an
+// ordered plan (frame_plan_ordered), null for one unordered draw list; next: the engine's other plan block, whose counters this
+// launch zeroes for the frame after this one.
 extern "C" __global__ __launch_bounds__(64) void mw_frame_plan_kernel(int N, int reuse, const uint8_t *__restrict__ frame_clean, const uint64_t *__restrict__ key,
-                                                                     const uint64_t *__restrict__ meta, int slots, uint8_t *__restrict__ frame_source,
-                                                                     uint32_t *__restrict__ plan, uint32_t *__restrict__ next)
+                                                                     const uint64_t *__restrict__ meta, int slots, const int32_t *__restrict__ nvis,
+                                                                     uint8_t *__restrict__ frame_source, uint32_t *__restrict__ plan, uint32_t *__restrict__ next)
 {
     const int lane = (int)threadIdx.x, env = (int)blockIdx.x * MW_PLAN_ENVS + lane;
-    if (blockIdx.x == 0 && lane < 2) next[lane] = 0u;
+    const bool ordered = nvis != nullptr;
+    if (blockIdx.x == 0) {
+        if (lane < 2) next[lane] = 0u;
+        else if (lane < 4) next[MW_PLAN_CLS_LO + lane - 2] = 0u;
+        else if (lane < 6) next[MW_PLAN_CLS_HI + lane - 4] = 0u;
+        else if (lane == 6) plan[2] = ordered ? (uint32_t)MW_PLAN_CLASSES : 0u;
+    }
     const bool on = env < N;
     uint32_t v = MW_SRC_CLEAN;          // (a lane without an env appends nothing)
+    uint32_t cls = 0u;
     if (on) {
         const bool clean = frame_clean[env] != 0;
+        const int32_t len = ordered ? nvis[env] : 0;
         uint32_t match = 0u, header = 0u;
         if (meta) {
             const uint64_t *row = static_cast<const uint64_t *>(__builtin_assume_aligned(meta + (size_t)env * MW_FC_META_WORDS(slots), 16));
@@ -97,18 +108,36 @@ extern "C" __global__ __launch_bounds__(64) void mw_frame_plan_kernel(int N, int
         }
         v = mw_frame_verdict(clean, reuse != 0, match, header, meta ? slots : 0);
         frame_source[env] = (uint8_t)v;
+        cls = mw_plan_cost_class(len);
     }
     const uint32_t src = v & 0xFFu;
     const bool draw = on && src == MW_SRC_DRAWN, copy = on && src >= (uint32_t)MW_SRC_SLOT(0);
     const uint64_t md = __builtin_amdgcn_ballot_w64(draw), mc = __builtin_amdgcn_ballot_w64(copy), below = (1ull << lane) - 1ull;
-    // (plan[0] and plan[1] as one 64-bit word: draw entries in the low half, copy entries in the high half; neither can carry)
-    unsigned long long base = 0ull;
-    if (lane == 0 && (md | mc))
-        base = atomicAdd(reinterpret_cast<unsigned long long *>(plan), (unsigned long long)__popcll(md) | (unsigned long long)__popcll(mc) << 32);
-    const uint32_t bd = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base), bc = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
+    // (plan[0] and plan[1] as one 64-bit word: draw entries in the low half, copy entries in the high half; neither can carry — nor
+    // can a 16-bit class count: the counters start at zero and an ordered plan has at most MW_PLAN_ORDERED_MAX_N envs)
+    unsigned long long add = (unsigned long long)__popcll(md) | (unsigned long long)__popcll(mc) << 32, add_lo = 0ull, add_hi = 0ull;
+    uint64_t mine = md;                 // the drawn lanes this lane shares a list with
+    if (ordered) {
+#pragma unroll
+        for (uint32_t c = 0; c < MW_PLAN_CLASSES; ++c) {
+            const uint64_t m = __builtin_amdgcn_ballot_w64(draw && cls == c);
+            (c < 4u ? add_lo : add_hi) |= (unsigned long long)__popcll(m) << (16u * (c & 3u));
+            mine = cls == c ? m : mine;
+        }
+    }
+    unsigned long long old = 0ull;
+    if (lane < 3) {
+        const unsigned long long a = lane == 0 ? add : lane == 1 ? add_lo : add_hi;
+        uint32_t *at = plan + (lane == 0 ? 0 : lane == 1 ? MW_PLAN_CLS_LO : MW_PLAN_CLS_HI);
+        if (a) old = atomicAdd(reinterpret_cast<unsigned long long *>(at), a);
+    }
+    const uint32_t old_lo = (uint32_t)old, old_hi = (uint32_t)(old >> 32);
+    const uint32_t bd = (uint32_t)__builtin_amdgcn_readlane((int)old_lo, 0), bc = (uint32_t)__builtin_amdgcn_readlane((int)old_hi, 0);
+    const uint64_t base_lo = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)old_lo, 1) | (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)old_hi, 1) << 32;
+    const uint64_t base_hi = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)old_lo, 2) | (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)old_hi, 2) << 32;
     const uint32_t entry = (uint32_t)env | (v >> 8) << MW_PLAN_ENV_BITS;
     // (the counts start at zero, so a list never outgrows its N entries; the tests keep a stray count from writing past them)
-    const uint32_t id = bd + (uint32_t)__popcll(md & below), ic = bc + (uint32_t)__popcll(mc & below);
-    if (draw && id < (uint32_t)N) plan[MW_PLAN_HEAD + id] = entry;
-    if (copy && ic < (uint32_t)N) plan[MW_PLAN_HEAD + (size_t)N + ic] = entry;
+    const uint32_t id = (ordered ? mw_plan_class_count(base_lo, base_hi, cls) : bd) + (uint32_t)__popcll(mine & below), ic = bc + (uint32_t)__popcll(mc & below);
+    if (draw && id < (uint32_t)N) plan[MW_PLAN_DRAW(N, ordered ? cls : 0u) + id] = entry;
+    if (copy && ic < (uint32_t)N) plan[MW_PLAN_COPY(N) + ic] = entry;
 }

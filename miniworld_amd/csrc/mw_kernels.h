@@ -107,7 +107,8 @@ MW_KERNEL_PAIR(mw_raster_big_mesh_wrap, MW_RASTER_ARGS);
 // the quad kernel (mw_rasterq.hip): one workgroup of MWQ_THREADS lanes per env, 8 or 4 samples per pixel
 // plan == null: workgroup b draws env b (the list forms: env list[1 + b] while b < list[0]).
 // plan != null (mw_frame_plan.h: the block mw_frame_plan_kernel filled behind the geometry kernel; plain whole-batch steps only,
-// mw_policy.h: frame_plans): the kernel decides nothing about an env itself.  Workgroup b < n_draw draws the env of draw entry b;
+// mw_policy.h: frame_plans): the kernel decides nothing about an env itself.  Workgroup b < n_draw draws the env of draw entry b — in
+// an ordered plan the entry mw_plan_slot names: the cost classes from the highest down, so the longest frames start first —;
 // workgroup n_draw <= b < n_draw + n_copy copies the frame, and the depth map, of the slot its copy entry names from the frame cache
 // into the caller's buffers — 16-, 4- or 1-byte stores by the buffer's alignment — and leaves before any barrier; every other
 // workgroup leaves at once.  So the drawing workgroups are the first the launch dispatches and the copies fill its tail; nothing
@@ -220,8 +221,8 @@ extern "C" __global__ void mw_final_copy_kernel(const int32_t *__restrict__ list
 // env; grid ceil(N / MW_PLAN_ENVS) x 64 lanes
 #define MW_PLAN_ENVS 64
 extern "C" __global__ void mw_frame_plan_kernel(int N, int reuse, const uint8_t *__restrict__ frame_clean, const uint64_t *__restrict__ key,
-                                                const uint64_t *__restrict__ meta, int slots, uint8_t *__restrict__ frame_source,
-                                                uint32_t *__restrict__ plan, uint32_t *__restrict__ next);
+                                                const uint64_t *__restrict__ meta, int slots, const int32_t *__restrict__ nvis,
+                                                uint8_t *__restrict__ frame_source, uint32_t *__restrict__ plan, uint32_t *__restrict__ next);
 
 // state views (mw_state_view.hip; the index arithmetic and MwStateArrays: mw_state_view.h): one launch per call, a wavefront per env,
 // MW_SV_ENVS envs per workgroup.  The view is the caller's mw_state_view by value: device pointers, null = field not asked for.

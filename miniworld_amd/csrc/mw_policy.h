@@ -217,6 +217,12 @@ inline bool frame_plans(const FramePolicy &pol, int path, bool listed, int N)
 {
     return !listed && path == MW_PATH_QUAD && (pol.reuse || pol.cache) && N <= 0xFFFFFF;
 }
+// ... and its draw entries are filed by cost class (mw_frame_plan.h: an ordered plan, a segment of N entries per class and 16-bit
+// class counts) for the batches whose counts fit, MW_PLAN_ORDERED_MAX_N; a larger batch gets one unordered draw list, which is always right.
+inline bool frame_plan_ordered(int N)
+{
+    return N <= 0xFFFF;
+}
 
 // The tile kernels' launch (mw_raster.hip) for a part of the frame (raster_flags).  big scenes (a visiting order exists): records
 // read in place, near to far; otherwise the env's records are staged in LDS when there are at most MW_LDS_RECS of them (a wave whose

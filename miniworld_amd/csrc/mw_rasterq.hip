@@ -548,13 +548,14 @@ __device__ inline void batch_exact(const QCtx &cx, int kmax, Tri tri, RecOf recp
 #ifdef MW_PERF_HOOKS
 // per-workgroup residency (perf builds only; tools/perf/k2qprof.py), by blockIdx in a third region of the stamps, [N][16]: [0] the
 // first instruction, [1] kind (0 drawn, 1 clean, 2 copied, 3 idle), [2 + wave] the wavefront's exit — s_memrealtime, the 100 MHz
-// clock every XCD shares (s_memtime, the phase stamps' clock, has an origin of its own on every XCD)
+// clock every XCD shares (s_memtime, the phase stamps' clock, has an origin of its own on every XCD) —, [10] the env the workgroup
+// drew or copied, [11] its display-list length (tools/perf/plan_order_sim.py joins the residencies with the class counts by env)
 #define MWQ_WG_BEGIN() const unsigned long long wg_t0 = prof ? __builtin_amdgcn_s_memrealtime() : 0ull
-#define MWQ_WG_END(kind) do { if (prof && (threadIdx.x & 63) == 0) { unsigned long long *w_ = prof + (size_t)N * (MWQ_WAVES * 8 + 16) + (size_t)blockIdx.x * 16; \
-    if (threadIdx.x == 0) { w_[0] = wg_t0; w_[1] = (kind); } w_[2 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
+#define MWQ_WG_END(kind, env_, nvis_) do { if (prof && (threadIdx.x & 63) == 0) { unsigned long long *w_ = prof + (size_t)N * (MWQ_WAVES * 8 + 16) + (size_t)blockIdx.x * 16; \
+    if (threadIdx.x == 0) { w_[0] = wg_t0; w_[1] = (kind); w_[10] = (unsigned long long)(env_); w_[11] = (unsigned long long)(nvis_); } w_[2 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
 #else
 #define MWQ_WG_BEGIN() do {} while (0)
-#define MWQ_WG_END(kind) do {} while (0)
+#define MWQ_WG_END(kind, env_, nvis_) do {} while (0)
 #endif
 // SUB: the frame of a subset of the batch (mw_engine_frame.hip, same-step auto-reset with final observations): workgroup e draws env
 // list[1 + e] while e < list[0] and exits at once otherwise (before any barrier: the whole workgroup)
@@ -581,15 +582,29 @@ __device__ inline void rasterq_body(
         // The frame plan (mw_frame_plan.h; mw_frame_plan_kernel ran behind the geometry kernel): the first n_draw workgroups of the
         // launch draw the listed envs, the n_copy behind them copy a cached frame each, the rest have nothing to do.  Every decision
         // below is the whole workgroup's, from scalar loads, before any barrier.
-        const uint32_t b = blockIdx.x, n_draw = plan[0];
-        if (b < n_draw) {
-            const uint32_t entry = plan[MW_PLAN_HEAD + b];
+        // An ordered plan files the draw entries by cost class: the counters of the head in one round of scalar loads, the class
+        // and the rank of this workgroup's entry by a scalar prefix (mw_plan_slot), then the entry — one dependent load more than
+        // the unordered list takes.  Every index that comes from a counter is held below the capacity of what it indexes.
+        const uint32_t b = blockIdx.x, n_copy = plan[1], n_classes = plan[2];
+        const uint64_t c_lo = *reinterpret_cast<const uint64_t *>(plan + MW_PLAN_CLS_LO), c_hi = *reinterpret_cast<const uint64_t *>(plan + MW_PLAN_CLS_HI);
+        uint32_t n_draw = plan[0], cls = 0u, rank = b;
+        bool draws = b < n_draw;
+        if (n_classes != 0u) {
+            uint32_t count[MW_PLAN_CLASSES];
+#pragma unroll
+            for (uint32_t c = 0; c < MW_PLAN_CLASSES; ++c) count[c] = mw_plan_class_count(c_lo, c_hi, c);
+            draws = mw_plan_slot(b, count, &cls, &rank);
+            n_draw = b - rank;          // (for a workgroup that does not draw: the sum of the counts)
+        }
+        if (draws) {
+            if (rank >= (uint32_t)N) { MWQ_WG_END(3, 0, 0); return; }
+            const uint32_t entry = plan[MW_PLAN_DRAW(N, cls) + rank];
             env = (int)(entry & MW_PLAN_ENV_MASK);
             fc_victim = entry >> MW_PLAN_ENV_BITS;
         } else {
-            if (b - n_draw >= plan[1] || !fc) { MWQ_WG_END(3); return; }
+            if (b - n_draw >= n_copy || !fc) { MWQ_WG_END(3, 0, 0); return; }
             // a hit: the slot's frame, and its depth map, into the caller's buffers
-            const uint32_t entry = plan[MW_PLAN_HEAD + (size_t)N + (b - n_draw)];
+            const uint32_t entry = plan[MW_PLAN_COPY(N) + (b - n_draw)];
             env = (int)(entry & MW_PLAN_ENV_MASK);
             const int hit = (int)(entry >> MW_PLAN_ENV_BITS), fc_slots = fc->slots;
             const int fbytes = W * H * 3;           // (a multiple of 64 bytes: the quad path draws frames on the 16x4 grid only)
@@ -609,7 +624,7 @@ __device__ inline void rasterq_body(
                 else
                     for (int i = tid; i < W * H; i += MWQ_THREADS) zd[i] = zs[i];
             }
-            MWQ_WG_END(2);
+            MWQ_WG_END(2, env, 0);
             return;
         }
     }
@@ -890,6 +905,17 @@ __device__ inline void rasterq_body(
             const uint32_t size = cls == QC_TRIV ? 64u : 16u, bi = b - cfirst;
             s_btab[b] = ((cslot + bi * (size / 16u)) * 16u) | (cls << 12) | (min(size, ccnt - bi * size) << 16);      // first quad of the queue | class | quads
         }
+#ifdef MW_PERF_HOOKS
+        // (perf builds: what a cost hint from the env's drawing before this one would have known — its class sizes and partial events,
+        // 16 bits each, into words 9..11 of the env's class sizes, ahead of the barrier behind which this drawing's replace them; [12]
+        // this drawing's partial events)
+        if (prof && tid == 0) {
+            unsigned long long *c_ = prof + (size_t)N * MWQ_WAVES * 8 + (size_t)env * 16, pk[3] = {0ull, 0ull, 0ull};
+            for (int c = 0; c < QC_NCLS; ++c) pk[c >> 2] |= (c_[c] < 0xFFFFull ? c_[c] : 0xFFFFull) << (16 * (c & 3));
+            pk[2] |= (c_[12] < 0xFFFFull ? c_[12] : 0xFFFFull) << 16;
+            c_[9] = pk[0]; c_[10] = pk[1]; c_[11] = pk[2]; c_[12] = s_misc[16];
+        }
+#endif
         __syncthreads();
 
         stamp(4);
@@ -1040,7 +1066,7 @@ __device__ inline void rasterq_body(
             reinterpret_cast<uint4 *>(meta + 2 + MW_FC_KEY_WORDS * victim)[tid] = reinterpret_cast<const uint4 *>(fc->key + (size_t)env * MW_FC_KEY_WORDS)[tid];
         if (tid == 64) meta[0] = (uint64_t)(victim + 1u == (uint32_t)fc_slots ? 0u : victim + 1u);
     }
-    MWQ_WG_END(0);
+    MWQ_WG_END(0, env, nvis);
 }
 
 }  // namespace

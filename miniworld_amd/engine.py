@@ -39,7 +39,7 @@ PATH_TILE, PATH_QUAD, PATH_QUAD_MESH, PATH_GENERIC = 0, 1, 2, 3
 EXPORTS = [
     "mw_create", "mw_destroy", "mw_last_error", "mw_upload_texture", "mw_upload_mesh",
     "mw_set_geometry", "mw_get_geometry", "mw_set_state", "mw_get_state", "mw_set_step_params", "mw_reset",
-    "mw_step", "mw_step_repeat", "mw_step_plan", "mw_step_plan_trace", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_frame_cache", "mw_get_frame_source", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
+    "mw_step", "mw_step_repeat", "mw_step_plan", "mw_step_plan_trace", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_frame_cache", "mw_get_frame_source", "mw_get_frame_plan", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
     "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
     "mw_selftest_sincosf",
     "mw_set_frame_stack", "mw_stack_refresh", "mw_stack_window",
@@ -256,6 +256,7 @@ def load_library():
     L.mw_get_frame_clean.argtypes = [vp, vp, vp]
     L.mw_set_frame_cache.argtypes = [vp, i32]
     L.mw_get_frame_source.argtypes = [vp, vp, vp]
+    L.mw_get_frame_plan.argtypes = [vp, vp, C.c_int64, vp, vp]
     L.mw_get_list_lengths.argtypes = [vp, i32, i32, vp, vp]
     L.mw_debug_set_mesh_frame_seq.argtypes = [vp, C.c_uint32]
     L.mw_debug_get_slow_heads.argtypes = [vp, vp, vp]
@@ -932,6 +933,27 @@ class Engine:
         """uint8[N] on the device: where each env's frame of the last plain step came from — 0 drawn, 1 left alone as clean (frame
         reuse), 2 + j copied from slot j of the frame cache.  Written into `out` when given."""
         return self._get_bytes("mw_get_frame_source", out)
+
+    def get_frame_plan(self):
+        """Test and diagnosis call (synchronises): the plan the last planned frame was drawn from (include/mwengine.h:
+        mw_get_frame_plan), as a dict — `classes` (8 in an ordered plan, 0 in an unordered one), `class_counts` (the draw entries per
+        cost class), `draw` (uint32, the draw entries env | victim slot << 24 in the order the quad kernel's workgroups take them:
+        the highest class first), `copy` (the copy entries env | slot << 24), `lengths` (int32[N], every env's display-list length,
+        the cost input: class = min(7, length // 4)) and `block`, the raw words."""
+        N = self.N
+        ordered = N <= 0xFFFF
+        block = np.zeros(96 + N * (9 if ordered else 2), np.uint32)
+        lengths = np.zeros(N, np.int32)
+        self._check(self.lib.mw_get_frame_plan(self.h, block.ctypes.data, block.size, lengths.ctypes.data, _stream_ptr(self.device)), "mw_get_frame_plan")
+        n_draw, n_copy, classes = int(block[0]), int(block[1]), int(block[2])
+        packed = [int(block[32]) | int(block[33]) << 32, int(block[64]) | int(block[65]) << 32]
+        counts = [(packed[c >> 2] >> (16 * (c & 3))) & 0xFFFF for c in range(8)] if classes else []
+        if classes:
+            draw = np.concatenate([block[96 + N * (1 + c):96 + N * (1 + c) + min(counts[c], N)] for c in reversed(range(8))])
+        else:
+            draw = block[96 + N:96 + N + min(n_draw, N)].copy()
+        return {"n_draw": n_draw, "n_copy": n_copy, "classes": classes, "class_counts": counts, "draw": draw,
+                "copy": block[96:96 + min(n_copy, N)].copy(), "lengths": lengths, "block": block}
 
     def get_frame_clean(self, out=None):
         """uint8[N] on the device: 1 = the env's frame after the last step is bit for bit the frame before it (a blocked move, a

@@ -39,8 +39,9 @@ either way; `self.vec.frame_clean()` tells a consumer which rows did not change.
 **`frame_cache`: on for exploration, off for a policy that never turns back.**  The engine keeps every env's last `frame_cache` (default 4)
 distinct drawn frames on the device and copies one instead of drawing when the env is back in the state it shows — a third of the steps
 of a near-uniform policy, +15 % env-steps/s on Hallway.  A policy that never returns to a state gains nothing and pays one more store
-of every frame: -3.7 % with always-turn-left (against `frame_cache=0`; the step with the cache on has since become 0.9 % faster under that
-policy, 13.36 -> 13.48 M, profiles/r20).  For such a consumer:
+of every frame: -3.7 % with always-turn-left (against `frame_cache=0`; the step with the cache on has since become faster under that
+policy, 13.36 -> 13.48 M with the frame plan, profiles/r20, and 13.41 -> 14.21 M with its draw list ordered by cost, profiles/r22).  For
+such a consumer:
 
     envs = MiniWorldVectorEnv("MiniWorld-Hallway-v0", num_envs=4096, frame_cache=0)
 

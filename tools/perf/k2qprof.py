@@ -22,7 +22,7 @@ raw = np.fromfile(dump, np.uint64)
 n_env = raw.size // 96
 t = raw[:n_env * 64].reshape(-1, 8, 8).astype(np.int64)      # [env][wave][stamp]: s_memtime, the shader clock of the env's XCD
 cls = raw[n_env * 64:n_env * 80].reshape(n_env, 16)[:, :9].astype(np.int64)
-wg = raw[n_env * 80:].reshape(n_env, 16).astype(np.int64)    # [workgroup]: start, kind, the wavefronts' exits: s_memrealtime, 100 MHz, one clock for all XCDs
+wg = raw[n_env * 80:].reshape(n_env, 16).astype(np.int64)    # [workgroup]: start, kind, the wavefronts' exits: s_memrealtime, 100 MHz, one clock for all XCDs; [10] env, [11] its list length (plan_order_sim.py)
 TICKS = 100.0       # s_memrealtime ticks per us
 
 # ---- every workgroup of the launch, by blockIdx
