@@ -433,7 +433,7 @@ int mw_step_plan(mw_engine *e, const int32_t *d_plans /* [horizon][N] */, int32_
  * same-step engine installs on it never shows).  Rows k >= d_nsteps[i] repeat row d_nsteps[i] - 1 — the env stays where it ended, a
  * cost summed over the horizon needs no mask —, and all rows of an env that executed 0 sub-steps (next-step, entered with
  * reset_pending) hold the state it entered the call with.  Exactly `horizon` rows of N columns are written, by the step kernel itself
- * (the trace kernels, mw_setup_trace*.hip: the plan kernels with the stores added; mw_step_plan keeps its own).
+ * (the trace kernels, mode 3 of the step kernel's table in mw_kernels.h: the plan kernels with the stores added; mw_step_plan keeps its own).
  * Everything else is mw_step_plan's contract, clause for clause — drawn or frameless, final buffers, reset seeds, the stack, frame
  * reuse and the frame cache: state, stream, frames, rewards, flags, d_nsteps and d_step_reward are bit for bit what mw_step_plan returns.
  * MW_E_INVALID, nothing launched and nothing touched: `trace` NULL or without a field; ent_pos with ent_slot out of range; ent_pos

@@ -662,8 +662,7 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
     // domain-randomisation draws (miniworld.py:677-680); the world itself comes through mw_set_state / mw_set_geometry
     if (e->cfg.generator == MW_GEN_NONE) return MW_OK;
     if (mask) HIP_TRY(e, hipMemcpyAsync(e->d_mask, mask, N, hipMemcpyHostToDevice, st));
-    const bool pcg = e->cfg.rng_mode == MW_RNG_PCG64;
-    auto gen = pcg ? mw_reset_pcg_kernel : mw_reset_kernel;
+    auto gen = MW_BY_STREAM(e, mw_reset);
     const dim3 grid(e->cfg.generator == MW_GEN_MAZE ? N : (N + 63) / 64);
     const int all = mask ? 0 : 1;
     if (!e->spare_mode) {
@@ -672,7 +671,7 @@ int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *str
         // spare mode: a fresh seed generates the live world directly; without seeds the env's pre-generated world is
         // taken (what the same-step auto-reset does, after the pending refills have been run); either way the spare
         // of a reset env is then regenerated from its stream
-        auto refill = pcg ? mw_refill_pcg_kernel : mw_refill_kernel;
+        auto refill = MW_BY_STREAM(e, mw_refill);
         if (seeds) {
             hipLaunchKernelGGL(gen, grid, dim3(64), 0, st, e->args, (const uint8_t *)e->d_mask, all, 1);
         } else {
@@ -700,11 +699,10 @@ int mw_reset_where(mw_engine *e, const uint8_t *d_mask, const uint64_t *d_seeds,
     // the caller's buffers no longer show the masked envs; the other envs keep their cached frames (the kernel advances the epochs of the
     // envs it writes)
     invalidate(e, reset_where_invalidation());
-    const bool pcg = e->cfg.rng_mode == MW_RNG_PCG64;
     const dim3 grid(e->cfg.generator == MW_GEN_MAZE ? N : (N + 63) / 64);
     // spare mode: the live world comes directly from the fresh stream and the env's spare is marked stale (mw_reset's seeded path); the
     // refill blocks of the next step, or its side-stream refill, regenerate it
-    hipLaunchKernelGGL(pcg ? mw_reset_where_pcg_kernel : mw_reset_where_kernel, grid, dim3(64), 0, st, e->args, d_mask, d_seeds);
+    hipLaunchKernelGGL(MW_BY_STREAM(e, mw_reset_where), grid, dim3(64), 0, st, e->args, d_mask, d_seeds);
     if (e->stack.depth && e->cfg.generator != MW_GEN_NONE)
         hipLaunchKernelGGL(mw_stack_mark_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, d_mask, 0, stack_flags(e, e->stack.cur));
     HIP_TRY(e, hipGetLastError());

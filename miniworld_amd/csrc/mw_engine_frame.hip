@@ -6,16 +6,9 @@ using namespace mwhost;
 
 namespace {
 
-// K1 for the engine's random stream (the device code is compiled once per stream, mw_rng.h) out of a call's four forms (mw_step's,
-// mw_step_repeat's or mw_step_plan's): the dense form for lanes = k1_dense_lanes > 0, the wave-per-env form otherwise
-template <typename K>
-K k1_of(const mw_engine *e, int lanes, K wave, K wave_pcg, K dense, K dense_pcg)
-{
-    const bool pcg = e->cfg.rng_mode == MW_RNG_PCG64;
-    if (lanes) return pcg ? dense_pcg : dense;
-    return pcg ? wave_pcg : wave;
-}
-#define MW_K1(e, lanes, stem) k1_of(e, lanes, stem##_kernel, stem##_pcg_kernel, stem##_dense_kernel, stem##_dense_pcg_kernel)
+// K1 out of the four kernels of a mode (mw_kernels.h: the K1 table): the dense form for lanes = k1_dense_lanes > 0, the wave-per-env form
+// otherwise, then the engine's random stream
+#define MW_K1(e, lanes, stem) ((lanes) ? MW_BY_STREAM(e, stem##_dense) : MW_BY_STREAM(e, stem))
 
 // a kernel and its list form (mw_kernels.h: MW_KERNEL_PAIR)
 template <typename... A>
@@ -235,7 +228,7 @@ void launch_step_and_geometry(mw_engine *e, const Frame &f, const Call &c, CallK
     const int L = geom_lanes_of(e);
     launch(geom_kernel_of(L, e->cfg.msaa), f.list, dim3(env_blocks(N, L)), dim3(64), 0, f.st, a, f.view_flags, e->cfg.msaa, L, N);
     if (call_steps(kind) && e->cfg.task == MW_TASK_COLLECT)
-        hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_collect_respawn_pcg_kernel : mw_collect_respawn_kernel, dim3((N + 63) / 64), dim3(64), 0, f.st, a);
+        hipLaunchKernelGGL(MW_BY_STREAM(e, mw_collect_respawn), dim3((N + 63) / 64), dim3(64), 0, f.st, a);
 }
 
 // The Maze's spare worlds: regenerating one takes ~300 us on a single wave, four times a whole step of the batch, and any launch
@@ -248,7 +241,7 @@ int launch_side_refill(mw_engine *e, hipStream_t st)
     if (!e->ev_fork) HIP_TRY(e, make_event(e->ev_fork));
     HIP_TRY(e, hipEventRecord(e->ev_fork.get(), st));
     HIP_TRY(e, hipStreamWaitEvent(e->side_stream.get(), e->ev_fork.get(), 0));
-    hipLaunchKernelGGL(e->cfg.rng_mode == MW_RNG_PCG64 ? mw_refill_pcg_kernel : mw_refill_kernel, dim3(e->cfg.num_envs), dim3(64), 0, e->side_stream.get(), e->args);
+    hipLaunchKernelGGL(MW_BY_STREAM(e, mw_refill), dim3(e->cfg.num_envs), dim3(64), 0, e->side_stream.get(), e->args);
     e->side_refill_pending = true;
     return MW_OK;
 }
@@ -449,16 +442,15 @@ static int step_passes(mw_engine *e, const Call &c, const StepPasses &p)
     // (the step's draws, then the reset's), or with reset seeds the world of the env's seed on a stream seeded here —, and the frame
     // of those envs alone overwrites their rows.
     const int N = e->cfg.num_envs;
-    const bool pcg = e->cfg.rng_mode == MW_RNG_PCG64;
     if (const int rc = launch_frame(e, c, CALL_TERMINAL_STEP)) return rc;
     if (p.final_copy)
         hipLaunchKernelGGL(mw_final_copy_kernel, dim3(N), dim3(256), 0, c.st, (const int32_t *)e->d_final_list, (const uint8_t *)c.obs, e->final_obs,
                            (unsigned long long)frame_bytes_of(e), (const float *)c.depth, e->final_depth, e->cfg.obs_width * e->cfg.obs_height);
     if (p.seeded_install)
-        hipLaunchKernelGGL(pcg ? mw_seed_install_pcg_kernel : mw_seed_install_kernel, dim3(N), dim3(64), 0, c.st, e->args, (const int32_t *)e->d_final_list,
+        hipLaunchKernelGGL(MW_BY_STREAM(e, mw_seed_install), dim3(N), dim3(64), 0, c.st, e->args, (const int32_t *)e->d_final_list,
                            e->reset_seeds);
     else
-        hipLaunchKernelGGL(pcg ? mw_final_install_pcg_kernel : mw_final_install_kernel, dim3(N), dim3(64), 0, c.st, e->args, (const int32_t *)e->d_final_list);
+        hipLaunchKernelGGL(MW_BY_STREAM(e, mw_final_install), dim3(N), dim3(64), 0, c.st, e->args, (const int32_t *)e->d_final_list);
     return launch_frame(e, c, CALL_LIST_PASS);
 }
 

@@ -15,51 +15,55 @@
     extern "C" __global__ void stem##_kernel(__VA_ARGS__); \
     extern "C" __global__ void stem##_sub_kernel(__VA_ARGS__, const int32_t *list)
 
-// K1, the step (mw_setup.hip: wave per env; mw_setup_dense.hip: several envs per wavefront), per random stream (the *_pcg units)
+// a kernel compiled once per random stream (mw_rng.h: MW_RNG_KIND): the Philox form and the PCG64 form
+#define MW_RNG_PAIR(stem, ...)                             \
+    extern "C" __global__ void stem##_kernel(__VA_ARGS__); \
+    extern "C" __global__ void stem##_pcg_kernel(__VA_ARGS__)
+// ... and the name of the one a unit defines: the form of the stream the unit is compiled for
+#define MW_CAT_(a, b) a##b
+#define MW_CAT(a, b) MW_CAT_(a, b)
+#define MW_STREAM_SUFFIX_0
+#define MW_STREAM_SUFFIX_1 _pcg
+#define MW_KERNEL_NAME(stem) MW_CAT(MW_CAT(stem, MW_CAT(MW_STREAM_SUFFIX_, MW_RNG_KIND)), _kernel)
+
+// K1, the step: one row per mode, MW_K1_ROW_<mode>(X) = X(stem, parameters), and four kernels per row: the wave-per-env form
+// (mw_setup.hip) and the dense form, several envs per wavefront (mw_setup_dense.hip), each per random stream.  The Makefile compiles
+// each of the two sources once per mode and stream, with MW_K1_MODE and MW_RNG_KIND; a unit takes its kernel's name and parameters
+// from the row of its mode, and mw_setup_common.h has the mode's call of the step body.
+#define MW_K1_DECLARE(stem, ...) MW_RNG_PAIR(stem, __VA_ARGS__); MW_RNG_PAIR(stem##_dense, __VA_ARGS__)
+#define MW_K1_STEM(stem, ...) stem
+#define MW_K1_PARAMS_OF(stem, ...) __VA_ARGS__
+// mode 0, mw_step's
 #define MW_K1_ARGS MwArgs a, int lanes_per_env, const int32_t *__restrict__ actions, float *__restrict__ reward, \
                    uint8_t *__restrict__ term, uint8_t *__restrict__ trunc
-extern "C" __global__ void mw_step_setup_kernel(MW_K1_ARGS);
-extern "C" __global__ void mw_step_setup_pcg_kernel(MW_K1_ARGS);
-extern "C" __global__ void mw_step_setup_dense_kernel(MW_K1_ARGS);
-extern "C" __global__ void mw_step_setup_dense_pcg_kernel(MW_K1_ARGS);
-// ... and mw_step_repeat's: the same sources around the sub-step loop (mw_setup_repeat*.hip; mw_setup_common.h: step_env_repeat),
-// up to `repeat` sub-steps per env, the executed count into nsteps (may be null)
+#define MW_K1_ROW_0(X) X(mw_step_setup, MW_K1_ARGS)
+MW_K1_ROW_0(MW_K1_DECLARE);
+// mode 1, mw_step_repeat's: the same sources around the sub-step loop (mw_setup_common.h: step_env_repeat), up to `repeat` sub-steps
+// per env, the executed count into nsteps (may be null)
 #define MW_K1_REPEAT_ARGS MW_K1_ARGS, int repeat, int32_t *__restrict__ nsteps
-extern "C" __global__ void mw_step_repeat_kernel(MW_K1_REPEAT_ARGS);
-extern "C" __global__ void mw_step_repeat_pcg_kernel(MW_K1_REPEAT_ARGS);
-extern "C" __global__ void mw_step_repeat_dense_kernel(MW_K1_REPEAT_ARGS);
-extern "C" __global__ void mw_step_repeat_dense_pcg_kernel(MW_K1_REPEAT_ARGS);
-// ... and mw_step_plan's (mw_setup_plan*.hip; step_env_repeat with PLAN): `actions` is the plans, int32 [horizon][N], sub-step k of
+#define MW_K1_ROW_1(X) X(mw_step_repeat, MW_K1_REPEAT_ARGS)
+MW_K1_ROW_1(MW_K1_DECLARE);
+// mode 2, mw_step_plan's (step_env_repeat with PLAN): `actions` is the plans, int32 [horizon][N], sub-step k of
 // every env reads row k; step_reward, float [horizon][N] or null, gets each sub-step's own reward; frameless != 0: no frame follows,
 // the kernel applies the frame's tail behind the last executed sub-step itself
 #define MW_K1_PLAN_ARGS MW_K1_ARGS, int horizon, int32_t *__restrict__ nsteps, float *__restrict__ step_reward, int frameless
-extern "C" __global__ void mw_step_plan_kernel(MW_K1_PLAN_ARGS);
-extern "C" __global__ void mw_step_plan_pcg_kernel(MW_K1_PLAN_ARGS);
-extern "C" __global__ void mw_step_plan_dense_kernel(MW_K1_PLAN_ARGS);
-extern "C" __global__ void mw_step_plan_dense_pcg_kernel(MW_K1_PLAN_ARGS);
-// ... and mw_step_plan_trace's (mw_setup_trace*.hip; step_env_repeat with PLAN and TRACE): the plan kernels' arguments and the caller's
+#define MW_K1_ROW_2(X) X(mw_step_plan, MW_K1_PLAN_ARGS)
+MW_K1_ROW_2(MW_K1_DECLARE);
+// mode 3, mw_step_plan_trace's (step_env_repeat with PLAN and TRACE): the plan kernels' arguments and the caller's
 // trace by value — device pointers, [horizon][N] rows, null = field not asked for; row k of env i := the state sub-step k left
 #define MW_K1_TRACE_ARGS MW_K1_PLAN_ARGS, mw_plan_trace trace
-extern "C" __global__ void mw_step_trace_kernel(MW_K1_TRACE_ARGS);
-extern "C" __global__ void mw_step_trace_pcg_kernel(MW_K1_TRACE_ARGS);
-extern "C" __global__ void mw_step_trace_dense_kernel(MW_K1_TRACE_ARGS);
-extern "C" __global__ void mw_step_trace_dense_pcg_kernel(MW_K1_TRACE_ARGS);
+#define MW_K1_ROW_3(X) X(mw_step_trace, MW_K1_TRACE_ARGS)
+MW_K1_ROW_3(MW_K1_DECLARE);
 
-// reset, spare refill, CollectHealth respawn, same-step install, spare take-over (mw_reset.hip, mw_reset_pcg.hip)
-extern "C" __global__ void mw_reset_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all, int mark_refill);
-extern "C" __global__ void mw_reset_pcg_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all, int mark_refill);
-extern "C" __global__ void mw_refill_kernel(MwArgs a);
-extern "C" __global__ void mw_refill_pcg_kernel(MwArgs a);
-extern "C" __global__ void mw_collect_respawn_kernel(MwArgs a);
-extern "C" __global__ void mw_collect_respawn_pcg_kernel(MwArgs a);
-extern "C" __global__ void mw_final_install_kernel(MwArgs a, const int32_t *__restrict__ list);
-extern "C" __global__ void mw_final_install_pcg_kernel(MwArgs a, const int32_t *__restrict__ list);
+// reset, spare refill, CollectHealth respawn, same-step install, spare take-over (mw_reset.hip, compiled once per stream)
+MW_RNG_PAIR(mw_reset, MwArgs a, const uint8_t *__restrict__ mask, int force_all, int mark_refill);
+MW_RNG_PAIR(mw_refill, MwArgs a);
+MW_RNG_PAIR(mw_collect_respawn, MwArgs a);
+MW_RNG_PAIR(mw_final_install, MwArgs a, const int32_t *__restrict__ list);
 extern "C" __global__ void mw_take_spare_kernel(MwArgs a, const uint8_t *__restrict__ mask, int force_all);
 // ... and with seeds the device holds: mw_reset_where's masked seeded reset, the seeded same-step install (mw_set_reset_seeds)
-extern "C" __global__ void mw_reset_where_kernel(MwArgs a, const uint8_t *__restrict__ mask, const uint64_t *__restrict__ seeds);
-extern "C" __global__ void mw_reset_where_pcg_kernel(MwArgs a, const uint8_t *__restrict__ mask, const uint64_t *__restrict__ seeds);
-extern "C" __global__ void mw_seed_install_kernel(MwArgs a, const int32_t *__restrict__ list, const uint64_t *__restrict__ next_seed);
-extern "C" __global__ void mw_seed_install_pcg_kernel(MwArgs a, const int32_t *__restrict__ list, const uint64_t *__restrict__ next_seed);
+MW_RNG_PAIR(mw_reset_where, MwArgs a, const uint8_t *__restrict__ mask, const uint64_t *__restrict__ seeds);
+MW_RNG_PAIR(mw_seed_install, MwArgs a, const int32_t *__restrict__ list, const uint64_t *__restrict__ next_seed);
 
 // the geometry kernel (mw_geom.hip): small / big scenes, 8 samples per pixel compiled in or any
 #define MW_GEOM_ARGS MwArgs a, int view_flags, int S, int L, int n_env

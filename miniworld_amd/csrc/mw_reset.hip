@@ -3,10 +3,7 @@
 #include "mw_gen.h"
 #include "mw_kernels.h"
 
-#ifndef MW_RESET_KERNEL_NAME
-#define MW_RESET_KERNEL_NAME mw_reset_kernel
-#endif
-extern "C" __global__ __launch_bounds__(64) void MW_RESET_KERNEL_NAME(MwArgs a, const uint8_t *__restrict__ mask, int force_all, int mark_refill)
+extern "C" __global__ __launch_bounds__(64) void MW_KERNEL_NAME(mw_reset)(MwArgs a, const uint8_t *__restrict__ mask, int force_all, int mark_refill)
 {
     __shared__ unsigned char ws[64][MW_GEN_WS_BYTES];
     const bool wave_per_env = a.generator == MW_GEN_MAZE;
@@ -21,22 +18,16 @@ extern "C" __global__ __launch_bounds__(64) void MW_RESET_KERNEL_NAME(MwArgs a, 
     }
 }
 
-#ifndef MW_REFILL_KERNEL_NAME
-#define MW_REFILL_KERNEL_NAME mw_refill_kernel
-#endif
 // spare mode: regenerate every consumed spare now (mw_reset needs them current); grid like K1's refill blocks
-extern "C" __global__ __launch_bounds__(64) void MW_REFILL_KERNEL_NAME(MwArgs a)
+extern "C" __global__ __launch_bounds__(64) void MW_KERNEL_NAME(mw_refill)(MwArgs a)
 {
     __shared__ unsigned char refill_ws[MW_GEN_WS_BYTES];
     mw::refill_spares(a, (int)blockIdx.x, (int)threadIdx.x, refill_ws);
 }
 
-#ifndef MW_RESPAWN_KERNEL_NAME
-#define MW_RESPAWN_KERNEL_NAME mw_collect_respawn_kernel
-#endif
 // CollectHealth: the kit consumed by this step respawns after its frame was set up (collecthealth.py:86-90), with
 // place_entity's draws from the env's stream; one thread per env, launched behind the geometry kernel
-extern "C" __global__ __launch_bounds__(64) void MW_RESPAWN_KERNEL_NAME(MwArgs a)
+extern "C" __global__ __launch_bounds__(64) void MW_KERNEL_NAME(mw_collect_respawn)(MwArgs a)
 {
     const int env = (int)(blockIdx.x * 64 + threadIdx.x);
     if (env >= a.N) return;
@@ -46,14 +37,11 @@ extern "C" __global__ __launch_bounds__(64) void MW_RESPAWN_KERNEL_NAME(MwArgs a
     a.pending_remove[env] = -1;
 }
 
-#ifndef MW_INSTALL_KERNEL_NAME
-#define MW_INSTALL_KERNEL_NAME mw_final_install_kernel
-#endif
 // Same-step auto-reset with final observations, between the two passes of the step (mw_engine_frame.hip): the listed envs (int32
 // [0] count, [1 + i] env: the ones whose episode ended with this step, whose terminal frame was drawn) install their next world
 // through the same install code as the step kernel's, and leave nothing of the finished episode behind: no pending removal (a
 // picked object, CollectHealth's consumed kit), no pending next-step reset, no frame_clean byte.  One wavefront per list slot; grid N.
-extern "C" __global__ __launch_bounds__(64) void MW_INSTALL_KERNEL_NAME(MwArgs a, const int32_t *__restrict__ list)
+extern "C" __global__ __launch_bounds__(64) void MW_KERNEL_NAME(mw_final_install)(MwArgs a, const int32_t *__restrict__ list)
 {
     __shared__ unsigned char gen_ws[MW_GEN_WS_BYTES];
     __shared__ int s_claim;
@@ -68,13 +56,10 @@ extern "C" __global__ __launch_bounds__(64) void MW_INSTALL_KERNEL_NAME(MwArgs a
     }
 }
 
-#ifndef MW_RESET_WHERE_KERNEL_NAME
-#define MW_RESET_WHERE_KERNEL_NAME mw_reset_where_kernel
-#endif
 // mw_reset_where: mw_reset(mask, seeds) with both arrays on the device — every masked env's stream becomes the stream of its seed
 // (mw_rng.h: the host's own seeding arithmetic) and its live world is generated from it, as by mw_reset_kernel with mark_refill; the
 // grid is that kernel's.  seeds[env] is not read under a zero mask byte.  MW_GEN_NONE: the stream alone.
-extern "C" __global__ __launch_bounds__(64) void MW_RESET_WHERE_KERNEL_NAME(MwArgs a, const uint8_t *__restrict__ mask, const uint64_t *__restrict__ seeds)
+extern "C" __global__ __launch_bounds__(64) void MW_KERNEL_NAME(mw_reset_where)(MwArgs a, const uint8_t *__restrict__ mask, const uint64_t *__restrict__ seeds)
 {
     __shared__ unsigned char ws[64][MW_GEN_WS_BYTES];
     const bool wave_per_env = a.generator == MW_GEN_MAZE;
@@ -94,13 +79,10 @@ extern "C" __global__ __launch_bounds__(64) void MW_RESET_WHERE_KERNEL_NAME(MwAr
     }
 }
 
-#ifndef MW_SEED_INSTALL_KERNEL_NAME
-#define MW_SEED_INSTALL_KERNEL_NAME mw_seed_install_kernel
-#endif
 // Same-step auto-reset from chosen seeds (mw_set_reset_seeds), between the two passes of the step in mw_final_install_kernel's place:
 // the listed envs — and no other: next_seed[env] is read for them alone — start the episode of their seed, and leave behind what that
 // kernel leaves behind.  (fc_source: the list pass draws the env's row, whatever the first pass did with it.)
-extern "C" __global__ __launch_bounds__(64) void MW_SEED_INSTALL_KERNEL_NAME(MwArgs a, const int32_t *__restrict__ list, const uint64_t *__restrict__ next_seed)
+extern "C" __global__ __launch_bounds__(64) void MW_KERNEL_NAME(mw_seed_install)(MwArgs a, const int32_t *__restrict__ list, const uint64_t *__restrict__ next_seed)
 {
     __shared__ unsigned char gen_ws[MW_GEN_WS_BYTES];
     if ((int)blockIdx.x >= list[0]) return;

@@ -19,11 +19,15 @@ namespace mw {
 // device reset draws the very numbers the reference's env.reset(seed=...) draws (miniworld.py:551).
 struct Rng { uint64_t a, b, c, d; int kind; uint32_t has32, buf32; };   // has32 / buf32: PCG64's buffered upper half
 
-// Device code is compiled once per stream (MW_RNG_KIND = 0 in mw_setup.hip / mw_reset.hip, 1 in their
-// *_pcg.hip twins, which only re-include them): a kernel carries one generator, not a run-time switch
-// at each of its dozens of inlined draw sites.  Host code (seeding, the test hook) looks at r.kind.
+// Device code is compiled once per stream (the Makefile builds mw_setup.hip, mw_setup_dense.hip and mw_reset.hip
+// with MW_RNG_KIND = 0 and again with 1; mw_kernels.h: MW_KERNEL_NAME gives the second the _pcg names): a kernel
+// carries one generator, not a run-time switch at each of its dozens of inlined draw sites.  Host code (seeding,
+// the test hook) looks at r.kind.
 #ifndef MW_RNG_KIND
 #define MW_RNG_KIND 0
+#endif
+#if MW_RNG_KIND != 0 && MW_RNG_KIND != 1
+#error "MW_RNG_KIND is 0 (Philox) or 1 (PCG64)"
 #endif
 MW_HD bool rng_is_pcg(const Rng &r)
 {

@@ -6,15 +6,12 @@
 #include "mw_setup_common.h"
 #include "mw_kernels.h"
 
-#ifndef MW_SETUP_KERNEL_NAME
-#define MW_SETUP_KERNEL_NAME mw_step_setup_kernel
-#endif
 #ifndef MW_K1_OCC
 #define MW_K1_OCC 3      // waves per SIMD the register allocation aims at
 #endif
 
 // (lanes_per_env: the dense form's argument, 0 and unused here: one env per workgroup)
-extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MW_K1_OCC, 4))) void MW_SETUP_KERNEL_NAME(
+extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MW_K1_OCC, 4))) void MW_K1_NAME()(
     MW_K1_PARAMS)
 {
     __shared__ int s_claim;

@@ -248,7 +248,7 @@ struct SubStep {
     bool clean;             // the writer lane's frame_clean value of this sub-step
 };
 
-// TRACE (mw_step_plan_trace's kernels, mw_setup_trace*.hip): row `row` of env `env` in the caller's trace arrays (mw_plan_trace,
+// TRACE (mw_step_plan_trace's kernels, MW_K1_MODE 3): row `row` of env `env` in the caller's trace arrays (mw_plan_trace,
 // mwengine.h: [horizon][N] rows in mw_state_view's row layout, any field may be null) := the agent's pose, the carried slot as the
 // step stores it and the position of slot ent_slot — from the writer lane's registers where the step has them (`live`: the slot whose
 // position is in cpos, or -1), else from the engine's arrays.
@@ -594,24 +594,30 @@ __device__ inline void step_env_repeat(const MwArgs &a, int env, int lane, bool 
 
 }  // namespace
 
-// The two K1 sources (mw_setup.hip, mw_setup_dense.hip) compile as the plain step or, with MW_K1_REPEAT defined by the unit that
-// re-includes them (mw_setup_repeat*.hip), as mw_step_repeat's kernels: the same grid mapping and refill blocks around the
-// sub-step loop, `repeat` and `nsteps` as two more kernel parameters (mw_kernels.h).
-// With MW_K1_PLAN (mw_setup_plan*.hip) they compile as mw_step_plan's: the loop with PLAN set, `actions` the [horizon][N] plans.
-// With MW_K1_TRACE beside it (mw_setup_trace*.hip), as mw_step_plan_trace's: TRACE set too, the caller's trace one more parameter.
-#if defined(MW_K1_PLAN) && defined(MW_K1_TRACE)
-#define MW_K1_PARAMS MW_K1_TRACE_ARGS
-#define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) \
-    step_env_repeat<PER_LANE, true, true>(a, env, lane, writer, actions, horizon, reward, term, trunc, nsteps, step_reward, frameless != 0, ws, claim, &trace)
-#elif defined(MW_K1_PLAN)
-#define MW_K1_PARAMS MW_K1_PLAN_ARGS
-#define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) \
-    step_env_repeat<PER_LANE, true>(a, env, lane, writer, actions, horizon, reward, term, trunc, nsteps, step_reward, frameless != 0, ws, claim)
-#elif defined(MW_K1_REPEAT)
-#define MW_K1_PARAMS MW_K1_REPEAT_ARGS
+// The two K1 sources (mw_setup.hip, mw_setup_dense.hip) compile once per mode of mw_kernels.h's table, MW_K1_MODE (the Makefile sets
+// it): the row of the mode gives the kernel's stem and parameters, the branch here its call of the step body — the same grid mapping
+// and refill blocks around it in every mode.
+//   0  the plain step
+//   1  mw_step_repeat's: the sub-step loop, `repeat` and `nsteps` as two more kernel parameters
+//   2  mw_step_plan's: the loop with PLAN set, `actions` the [horizon][N] plans
+//   3  mw_step_plan_trace's: TRACE set too, the caller's trace one more parameter
+#ifndef MW_K1_MODE
+#define MW_K1_MODE 0
+#endif
+#define MW_K1_ROW MW_CAT(MW_K1_ROW_, MW_K1_MODE)
+#define MW_K1_PARAMS MW_K1_ROW(MW_K1_PARAMS_OF)
+#define MW_K1_NAME(form) MW_KERNEL_NAME(MW_CAT(MW_K1_ROW(MW_K1_STEM), form))      // form: empty (wave per env) or _dense
+#if MW_K1_MODE == 0
+#define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) step_env<PER_LANE>(a, env, lane, writer, actions, reward, term, trunc, ws, claim)
+#elif MW_K1_MODE == 1
 #define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) \
     step_env_repeat<PER_LANE>(a, env, lane, writer, actions, repeat, reward, term, trunc, nsteps, nullptr, false, ws, claim)
+#elif MW_K1_MODE == 2
+#define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) \
+    step_env_repeat<PER_LANE, true>(a, env, lane, writer, actions, horizon, reward, term, trunc, nsteps, step_reward, frameless != 0, ws, claim)
+#elif MW_K1_MODE == 3
+#define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) \
+    step_env_repeat<PER_LANE, true, true>(a, env, lane, writer, actions, horizon, reward, term, trunc, nsteps, step_reward, frameless != 0, ws, claim, &trace)
 #else
-#define MW_K1_PARAMS MW_K1_ARGS
-#define MW_K1_STEP(PER_LANE, env, lane, writer, ws, claim) step_env<PER_LANE>(a, env, lane, writer, actions, reward, term, trunc, ws, claim)
+#error "MW_K1_MODE is not a mode of mw_kernels.h's K1 table"
 #endif

@@ -8,12 +8,8 @@
 #include "mw_setup_common.h"
 #include "mw_kernels.h"
 
-#ifndef MW_DENSE_KERNEL_NAME
-#define MW_DENSE_KERNEL_NAME mw_step_setup_dense_kernel
-#endif
 
-
-extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void MW_DENSE_KERNEL_NAME(
+extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void MW_K1_NAME(_dense)(
     MW_K1_PARAMS)
 {
     __shared__ unsigned char gen_ws[MW_GEN_WS_BYTES];      // generator scratch (used by the Maze generator only)

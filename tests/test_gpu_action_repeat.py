@@ -168,6 +168,28 @@ def test_hallway_dense_same_step(spare, K, depth, monkeypatch):
         assert ((subs > 1) & (subs < K)).any()
 
 
+@pytest.mark.parametrize("spare", ["0", "1"])
+def test_hallway_dense_philox(spare, monkeypatch):
+    """The dense repeat kernel of the Philox stream (every other case here runs the PCG64 kernels), 7 envs: a full wavefront of five
+    and a ragged one of two.  Episodes of 7 steps at K = 4: truncation and the install, with its draws, land on sub-step 3 of every
+    second call."""
+    monkeypatch.setenv("MW_SPARE", spare)
+    _short_episodes(monkeypatch, "Hallway", 7)
+    subs, dones, _ = _repeat_parity("MiniWorld-Hallway-v0", 7, 4, 20, 902, 3, p_fwd=0.6, rng="philox")
+    assert dones.sum() >= 7
+    assert ((subs > 1) & (subs < 4)).any()
+
+
+def test_maze_wave_per_env_philox(monkeypatch):
+    """The wave-per-env repeat kernel of the Philox stream: MazeS3, 3 envs, episodes of 6 steps at K = 4 — every second call ends on
+    sub-step 2 and installs a world.  Without spare worlds: the kernel generates the maze itself, from its own stream's draws (with
+    them a finished env takes a world the refill kernel made, and this kernel draws nothing)."""
+    monkeypatch.setenv("MW_SPARE", "0")
+    subs, dones, _ = _repeat_parity("MiniWorld-MazeS3-v0", 3, 4, 18, 78, 3, max_episode_steps=6, rng="philox")
+    assert dones.sum() >= 6
+    assert ((subs > 1) & (subs < 4)).any()
+
+
 def test_oneroom_dense_next_step(monkeypatch):
     """Next-step mode, K = 3 on episodes of 2 steps: every real call ends on sub-step 2, every other call is a reset call that
     executes nothing."""

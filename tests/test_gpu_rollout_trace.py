@@ -174,6 +174,30 @@ def test_hallway_dense_same_step(spare, monkeypatch):
     assert (moved & dones).sum() >= 20 and not (moved & ~dones).any()
 
 
+@pytest.mark.parametrize("spare", ["0", "1"])
+def test_hallway_dense_philox(spare, monkeypatch):
+    """The dense trace kernel of the Philox stream (every other case here runs the PCG64 kernels), 7 envs: a full wavefront of five and
+    a ragged one of two.  Episodes of 7 steps at T = 4: truncation and the install, with its draws, land on sub-step 3 of every
+    second call; the rows of that sub-step are the terminal state."""
+    monkeypatch.setenv("MW_SPARE", spare)
+    _short_episodes(monkeypatch, "Hallway", 7)
+    subs, dones, moved = _trace_parity("MiniWorld-Hallway-v0", 7, 4, 20, 902, 3, p_fwd=0.6, rng="philox")
+    assert dones.sum() >= 7
+    assert ((subs > 1) & (subs < 4)).any()
+    assert (moved & dones).any() and not (moved & ~dones).any()
+
+
+def test_maze_wave_per_env_philox(monkeypatch):
+    """The wave-per-env trace kernel of the Philox stream: MazeS3, 3 envs, episodes of 6 steps at T = 4 — every second call ends on
+    sub-step 2 and installs a world.  Without spare worlds: the kernel generates the maze itself, from its own stream's draws (with
+    them a finished env takes a world the refill kernel made, and this kernel draws nothing)."""
+    monkeypatch.setenv("MW_SPARE", "0")
+    subs, dones, moved = _trace_parity("MiniWorld-MazeS3-v0", 3, 4, 18, 78, 3, max_episode_steps=6, rng="philox")
+    assert dones.sum() >= 6
+    assert ((subs > 1) & (subs < 4)).any()
+    assert (moved & dones).any()
+
+
 def test_oneroom_dense_next_step(monkeypatch):
     """Next-step mode, T = 3 on episodes of 2 steps: every second call executes 0 sub-steps and all three of its rows are the state the
     env entered the call with (compared with B.state() before the call in _trace_parity), not the world it installs."""
