@@ -738,6 +738,60 @@ int mw_nav_query(mw_engine *e, const mw_nav_params *params, const double *d_targ
  * NULL stops that */
 int mw_debug_set_nav_passes(mw_engine *e, int32_t *d_passes);
 
+/* ---- ray casts --------------------------------------------------------------- */
+/* What a ray from a point of an env's floor plan meets first, and how far away: the range sensor ("lidar"), the line-of-sight test
+ * and the free-path test of a disc that navigation suites around comparable simulators ship (Habitat's cast_ray, MuJoCo's mj_ray,
+ * PyBullet's rayTestBatch).  The reference has no ray call; its users write one in numpy over env.wall_segs.  The obstacles and the
+ * "starts inside" predicate are the reference's own: the collision segments and entity circles of
+ * MiniWorldEnv.intersect (miniworld.py:937-963), the closest-point distance of intersect_circle_segs (math.py:30-62).
+ *
+ * Ray k of env i is o + t * d, t in [0, max_t]: o row [i][k] of d_origin (x, y, z; y is not read) or, d_origin NULL, the env's agent
+ * position; d = (dx, dz) row [i][k] of d_dir, of any length, or, d_dir NULL, the fan: the angle agent_dir[i] + d_offsets[k] and
+ * d = (cos, -sin) of it — the reference's dir_vec, through the same deterministic sin / cos as the dynamics (a NaN direction for an
+ * angle of 1e6 or more in magnitude).  d_t[i][k] is the smallest such t at which the ray meets an obstacle, d_hit[i][k] says which:
+ * the segment's index for a wall, MW_RAY_ENT + slot for an entity; where it meets none, d_t = max_t and d_hit = -1.  With unit
+ * directions t is metres; with d = B - A and max_t = 1, "t < 1" says that something is in the way from A to B.  d_dir_out, if given,
+ * receives the directions used, in either mode.
+ *
+ * Obstacles: the env's collision segments; with MW_RAY_ENTITIES also every slot whose kind is not MW_ENT_NONE and which is not the
+ * carried one, as a circle of radius radius(slot) + params->radius (summed in float64) about its x, z.
+ * All arithmetic is float64, + - * / and sqrt only, uncontracted, in this order (R: a circle's radius, r = params->radius):
+ *   circle         w = o - c; A = dx*dx + dz*dz; B = wx*dx + wz*dz; C = (wx*wx + wz*wz) - R*R.  C < 0: t = 0.  Else disc = B*B - A*C;
+ *                  disc < 0: no hit; else t = (-B - sqrt(disc)) / A, which counts when t >= 0
+ *   segment a-b    e = b - a; den = dx*ez - dz*ex; den == 0 (parallel): no hit.  w = a - o; t = (wx*ez - wz*ex) / den;
+ *                  s = (wx*dz - wz*dx) / den; counts when t >= 0 and 0 <= s <= 1 (both endpoints inclusive)
+ *   wall, r == 0   the segment
+ *   wall, r > 0    a capsule.  The closest-point distance from o to the wall < r: the ray starts inside, t = 0.  Else
+ *                  len = sqrt(ex*ex + ez*ez), n = ((ez / len) * r, (-ex / len) * r), and t is the smallest of the circles of radius r
+ *                  about a and b and of the segments (a + n)-(b + n) and (a - n)-(b - n)
+ * A candidate counts only when t < best, from best = max_t (then best = t + 0.0), walls in index order, then slots in order: equal
+ * t goes to the lowest code, and the result does not depend on how the work is spread over lanes.  Garbage is no error and no test
+ * holds for a NaN: a NaN anywhere in a ray's origin or direction gives max_t and -1, a zero direction hits only what its origin is
+ * inside, origins outside the extent are ordinary. */
+#define MW_RAY_ENTITIES 1        /* flags: listed entities are obstacles too */
+#define MW_RAY_ENT 0x10000       /* d_hit: MW_RAY_ENT + slot for an entity, the segment index for a wall, -1 for nothing */
+#define MW_RAY_MAX 4096          /* rays per env and call */
+typedef struct mw_ray_params {
+    double max_t;                /* > 0, finite: rays are cut at o + max_t * d */
+    double radius;               /* >= 0, finite: 0 a ray, > 0 a disc of this radius swept along it */
+    int32_t rays;                /* R, 1 .. MW_RAY_MAX */
+    int32_t flags;               /* MW_RAY_* */
+} mw_ray_params;
+/* All pointers are device pointers.  One kernel, asynchronous on `stream`, no host value read, no synchronisation; it reads live arrays
+ * only and changes nothing in the engine.  d_mask: uint8[N] or NULL (all envs); rows of envs under a zero mask byte are neither read
+ * (origins, directions) nor written.  MW_E_INVALID before anything is launched, and nothing touched: a null engine, params or d_t,
+ * rays outside 1 .. MW_RAY_MAX, max_t not > 0 or not finite, radius < 0 or not finite, unknown flag bits, both or neither of d_dir /
+ * d_offsets; also an engine whose max_segs and max_ents need more than 64 KiB of LDS at 48 bytes per segment and 32 per slot (rays >= 64 only). */
+int mw_ray_cast(mw_engine *e, const mw_ray_params *params, const uint8_t *d_mask,
+                const double *d_origin  /* [N][R][3] (y is not read) or NULL = the env's agent position for all its rays */,
+                const double *d_dir     /* [N][R][2] = (dx, dz), any length, or NULL */,
+                const double *d_offsets /* [R], radians, shared by all envs: the fan; exactly one of d_dir / d_offsets is non-null */,
+                double *d_t /* [N][R] */, int32_t *d_hit /* [N][R] or NULL */, double *d_dir_out /* [N][R][2] or NULL */,
+                void *stream);
+/* measurements: form 1 casts every ray count with a ray per lane, 2 with an obstacle per lane (the same bits either way), 0 leaves the
+ * choice to the ray count again */
+int mw_debug_set_ray_form(mw_engine *e, int form);
+
 /* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where or mw_nav_build skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);

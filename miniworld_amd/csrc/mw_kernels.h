@@ -8,6 +8,7 @@
 #include "mw_snapframes.h"
 #include "mw_state_view.h"
 #include "mw_nav.h"
+#include "mw_ray.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -254,6 +255,19 @@ extern "C" __global__ void mw_nav_build_kernel(MwNavArgs a, mw_nav_params p, con
 extern "C" __global__ void mw_nav_query_kernel(MwNavArgs a, mw_nav_params p, const double *__restrict__ d_target, const uint16_t *__restrict__ field,
                                                const double *__restrict__ pos, int32_t *__restrict__ cost, int32_t *__restrict__ next,
                                                double *__restrict__ waypoint);
+
+// ray casts (mw_ray.hip; the arithmetic, MwRayArgs and the launch constants: mw_ray.h; the choice of form: mwpolicy::ray_launch).  The
+// parameters are the caller's mw_ray_params by value; origin null = the agents, exactly one of dir / offsets (the fan) non-null; hit
+// and dir_out may be null; an env under a zero mask byte is skipped.
+//   lanes  grid N workgroups of 64 .. MW_RAY_THREADS lanes, a ray per lane, max_segs * MW_RAY_WALL_BYTES + E * MW_RAY_DISC_BYTES bytes
+//          of dynamic LDS
+//   waves  grid ceil(N * R / MW_RAY_WAVES) workgroups of MW_RAY_WAVES wavefronts, a wavefront per ray, an obstacle per lane
+extern "C" __global__ void mw_ray_lanes_kernel(MwRayArgs a, mw_ray_params p, const uint8_t *__restrict__ mask, const double *__restrict__ origin,
+                                               const double *__restrict__ dir, const double *__restrict__ offsets, double *__restrict__ t_out,
+                                               int32_t *__restrict__ hit_out, double *__restrict__ dir_out);
+extern "C" __global__ void mw_ray_waves_kernel(MwRayArgs a, mw_ray_params p, const uint8_t *__restrict__ mask, const double *__restrict__ origin,
+                                               const double *__restrict__ dir, const double *__restrict__ offsets, double *__restrict__ t_out,
+                                               int32_t *__restrict__ hit_out, double *__restrict__ dir_out);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

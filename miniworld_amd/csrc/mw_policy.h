@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/mwengine.h"
+#include "mw_ray.h"             // MW_RAY_THREADS, MW_RAY_WAVES, MW_RAY_WALL_BYTES, MW_RAY_DISC_BYTES
 #include "mw_shape.h"
 #include "mw_snapframes.h"      // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -294,6 +295,26 @@ inline SnapfGrid snapf_grid(uintptr_t address_bits, uint64_t frame_bytes, uint64
 inline SnapfGrid snapf_where_grid(uintptr_t address_bits, uint64_t frame_bytes, uint64_t depth_bytes, int stack_depth, int N)
 {
     return snapf_grid(address_bits, frame_bytes, depth_bytes, stack_depth, N);
+}
+
+// Ray casts (mw_ray_cast; kernels: mw_ray.hip).  The form follows from the rays per env alone: from kRayPerLaneFrom rays on, a
+// workgroup per env with a ray per lane and the obstacles staged in LDS; below it a wavefront per ray with an obstacle per lane.
+// Both produce the same bits.  The ray-per-lane form takes as many whole wavefronts as hold the rays, MW_RAY_THREADS lanes at most;
+// its LDS is sized from the engine's capacities (fits: at most 64 KiB — the caller refuses what does not).
+// Measured (profiles/r24, us per call, a disc of the agent's radius, ray per lane / obstacle per lane): Maze x 1024, 256 segments:
+// R = 16: 216 / 47, 64: 227 / 167, 256: 567 / 647; Hallway x 4096, 4 segments: R = 1: 16 / 11, 4: 16 / 17, 16: 13 / 55, 64: 14 / 207.
+// The crossover moves with the segment count — below 4 rays in the Hallway, between 64 and 256 in the Maze —; 64 keeps the range
+// sensor on the form that is flat in R and the few-ray queries on the one that is flat in the segment count.
+constexpr int kRayPerLaneFrom = 64;
+struct RayLaunch { bool per_lane; unsigned long long grid; int threads; size_t lds; bool fits; };
+inline RayLaunch ray_launch(int N, int R, int max_segs, int max_ents, int forced = 0 /* measurements: 1 a ray per lane, 2 an obstacle per lane */)
+{
+    if (forced ? forced == 1 : R >= kRayPerLaneFrom) {
+        const int waves = (R + 63) / 64;
+        const size_t lds = ((size_t)max_segs * MW_RAY_WALL_BYTES + (size_t)max_ents * MW_RAY_DISC_BYTES + 15) / 16 * 16;
+        return {true, (unsigned long long)N, 64 * (waves < MW_RAY_THREADS / 64 ? waves : MW_RAY_THREADS / 64), lds, lds <= 64 * 1024};
+    }
+    return {false, ((unsigned long long)N * (unsigned long long)R + MW_RAY_WAVES - 1) / MW_RAY_WAVES, MW_RAY_WAVES * 64, 0, true};
 }
 
 }  // namespace mwpolicy

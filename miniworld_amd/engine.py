@@ -49,6 +49,7 @@ EXPORTS = [
     "mw_reset_where", "mw_set_reset_seeds",
     "mw_get_state_device", "mw_set_state_where",
     "mw_nav_build", "mw_nav_query", "mw_debug_set_nav_passes",
+    "mw_ray_cast", "mw_debug_set_ray_form",
 ]
 
 
@@ -133,6 +134,15 @@ class MwNavParams(C.Structure):
                 ("flags", C.c_int32), ("target_slot", C.c_int32)]
 
 
+RAY_ENTITIES = 1                        # MW_RAY_ENTITIES
+RAY_ENT = 0x10000                       # MW_RAY_ENT: hit = RAY_ENT + slot for an entity
+RAY_MAX = 4096                          # MW_RAY_MAX
+
+
+class MwRayParams(C.Structure):
+    _fields_ = [("max_t", C.c_double), ("radius", C.c_double), ("rays", C.c_int32), ("flags", C.c_int32)]
+
+
 class MwPlanTrace(C.Structure):
     _fields_ = [("agent_pos", C.c_void_p), ("agent_dir", C.c_void_p), ("carrying", C.c_void_p), ("ent_pos", C.c_void_p), ("ent_slot", C.c_int32)]
 
@@ -215,6 +225,8 @@ def load_library():
     L.mw_nav_build.argtypes = [vp, C.POINTER(MwNavParams), vp, vp, vp, vp]
     L.mw_nav_query.argtypes = [vp, C.POINTER(MwNavParams), vp, vp, vp, vp, vp, vp, vp]
     L.mw_debug_set_nav_passes.argtypes = [vp, vp]
+    L.mw_ray_cast.argtypes = [vp, C.POINTER(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mw_debug_set_ray_form.argtypes = [vp, i32]
     L.mw_set_step_params.argtypes = [vp, vp]
     L.mw_set_gen_program.argtypes = [vp, C.POINTER(MwGenProgram), vp, vp, vp, vp, i32, vp, i32]
     L.mw_reset.argtypes = [vp, vp, vp, vp]
@@ -472,6 +484,31 @@ class Engine:
         self._dev_tensor(passes, "passes", torch.int32, self.N)
         self._nav_passes = passes       # (kept alive while the engine holds its pointer)
         self._check(self.lib.mw_debug_set_nav_passes(self.h, _ptr(passes)), "mw_debug_set_nav_passes")
+
+    # -- ray casts -----------------------------------------------------------------------
+    def ray_cast(self, params: MwRayParams, t, hit=None, dir_out=None, mask=None, origin=None, direction=None, offsets=None):
+        """mw_ray_cast: R = params.rays rays per env under `mask` (uint8[N], device; None = all) from `origin` (float64[N, R, 3],
+        device; None = the agents) along `direction` (float64[N, R, 2]) or the fan `offsets` (float64[R], radians from each agent's
+        heading) into t (float64[N, R]), hit (int32[N, R]) and dir_out (float64[N, R, 2]), the last two optional.  One kernel on the
+        current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the library is called."""
+        import torch
+        n = self.N * int(params.rays)
+        if t is None:
+            raise EngineError("t: None")
+        self._dev_tensor(t, "t", torch.float64, n)
+        self._dev_tensor(hit, "hit", torch.int32, n)
+        self._dev_tensor(dir_out, "dir_out", torch.float64, n * 2)
+        self._dev_tensor(origin, "origin", torch.float64, n * 3)
+        self._dev_tensor(direction, "direction", torch.float64, n * 2)
+        self._dev_tensor(offsets, "offsets", torch.float64, int(params.rays))
+        if mask is not None:
+            mask = self._mask_tensor(mask)
+        self._check(self.lib.mw_ray_cast(self.h, C.byref(params), _ptr(mask), _ptr(origin), _ptr(direction), _ptr(offsets), _ptr(t), _ptr(hit), _ptr(dir_out),
+                                         _stream_ptr(self.device)), "mw_ray_cast")
+
+    def debug_set_ray_form(self, form: int):
+        """Measurements: 1 casts every ray count with a ray per lane, 2 with an obstacle per lane, 0 by the ray count again."""
+        self._check(self.lib.mw_debug_set_ray_form(self.h, int(form)), "mw_debug_set_ray_form")
 
     def set_gen_program(self, prog: MwGenProgram, polys: np.ndarray, poly_room, poly_surf, poly_m, segs: np.ndarray):
         """Installs the placement program of an MW_GEN_PROGRAM engine (include/mwengine.h: mw_set_gen_program)."""

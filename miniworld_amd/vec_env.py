@@ -364,6 +364,7 @@ class MiniWorldVecEnv:
         self._final_info_buf = None
         self._state_bufs = {}           # state()'s tensors, one per field, made on first use
         self._nav_bufs = None           # nav_query()'s tensors, made on first use
+        self._lidar_bufs = {}           # lidar()'s offsets and result per (rays, fov), made on first use
         self._fork_buf = None           # fork()'s scratch records, made on first use
         self._fork_frames = None        # ... and its scratch frame records (fork(src, frames=True))
         # autoreset="levels": the bank (set_levels), the level each env plays and the one it gets when its episode ends
@@ -965,6 +966,103 @@ class MiniWorldVecEnv:
         e.nav_query(field.params, field.field, field.points, pos, b["cost"], b["next"], b["waypoint"])
         dist = torch.where(b["cost"] < 0, float("inf"), b["cost"].to(torch.float32) * (field.cell / 5.0)).to(torch.float32)
         return {"cost": b["cost"], "next": b["next"], "waypoint": b["waypoint"], "distance": dist}
+
+    # ------------------------------------------------------------------ ray casts
+    RAY_OBSTACLES = {"walls": 0, "walls+entities": eng.RAY_ENTITIES}
+
+    def raycast(self, direction=None, origin=None, offsets=None, max_t=1.0, radius=0.0, obstacles="walls", mask=None, into=None):
+        """What R rays per env meet first in the env's collision world, by one kernel (mw_ray_cast) with no host value and no
+        synchronisation: {"t": float64[N, R], "hit": int32[N, R]} and, with `offsets`, "dir": float64[N, R, 2].
+
+        Ray k of env i is origin + t * direction, t in 0 .. max_t; "t" is the smallest t at which it meets an obstacle and "hit" which
+        one — a wall's segment index, engine.RAY_ENT + slot for an entity —, max_t and -1 where it meets none.  With unit directions t
+        is metres; with direction = B - A and max_t = 1, t < 1 says that something is in the way from A to B.
+        direction  float64[N, R, 2] device tensor of (dx, dz), any length; or
+        offsets    float64[R] device tensor of angles in radians added to each agent's heading (a fan; "dir" returns the directions)
+        origin     float64[N, R, 3] device tensor (y is not read); None: each env's agent position for all its rays
+        radius     0 a ray; > 0 a disc of that radius swept along it (a wall is a capsule, an entity's circle grows by it)
+        obstacles  "walls", or "walls+entities": every listed entity but the carried one too
+        mask       uint8[N] or bool[N] device tensor: only those envs' rows are read and written
+        into       a previous result of the same R (and mode) to write into; without it new tensors are allocated (unmasked rows:
+                   t = max_t, hit = -1, dir = 0)
+        A NaN in a ray gives max_t and -1; nothing raises on the device.  ValueError for arguments that make no cast; nothing is
+        launched then."""
+        torch, e = self.torch, self.engine
+        n = self.num_envs
+        if (direction is None) == (offsets is None):
+            raise ValueError("raycast: give exactly one of direction (float64[N, R, 2]) and offsets (float64[R])")
+
+        def ok(t, shape):
+            return torch.is_tensor(t) and t.dtype == torch.float64 and t.device == e.device and t.is_contiguous() and (
+                len(t.shape) == len(shape) and all(s is None or s == d for s, d in zip(shape, t.shape)))
+        if offsets is not None:
+            if not ok(offsets, (None,)):
+                raise ValueError(f"raycast: offsets is a contiguous float64 tensor [R] on {e.device}")
+            rays = int(offsets.shape[0])
+        else:
+            if not ok(direction, (n, None, 2)):
+                raise ValueError(f"raycast: direction is a contiguous float64 tensor [{n}, R, 2] on {e.device}")
+            rays = int(direction.shape[1])
+        if not 1 <= rays <= eng.RAY_MAX:
+            raise ValueError(f"raycast: {rays} rays per env outside 1 .. {eng.RAY_MAX}")
+        if origin is not None and not ok(origin, (n, rays, 3)):
+            raise ValueError(f"raycast: origin is a contiguous float64 tensor [{n}, {rays}, 3] on {e.device}")
+        if not (isinstance(max_t, (int, float)) and not isinstance(max_t, bool) and max_t > 0 and math.isfinite(max_t)):
+            raise ValueError(f"raycast: max_t {max_t!r} must be a positive finite number")
+        if not (isinstance(radius, (int, float)) and not isinstance(radius, bool) and radius >= 0 and math.isfinite(radius)):
+            raise ValueError(f"raycast: radius {radius!r} must be a finite number >= 0")
+        if obstacles not in self.RAY_OBSTACLES:
+            raise ValueError(f"raycast: obstacles {obstacles!r}; have {sorted(self.RAY_OBSTACLES)}")
+        if mask is not None:
+            if not torch.is_tensor(mask) or tuple(mask.shape) != (n,) or mask.dtype not in (torch.uint8, torch.bool) or mask.device != e.device:
+                raise ValueError(f"raycast: mask is a uint8 or bool tensor [{n}] on {e.device}")
+            if mask.dtype == torch.bool:
+                mask = mask.view(torch.uint8)       # (one byte per element, 0 / 1: no conversion kernel)
+        keys = ("t", "hit", "dir") if offsets is not None else ("t", "hit")
+        if into is not None:
+            if not isinstance(into, dict) or set(into) != set(keys):
+                raise ValueError(f"raycast: `into` is a previous result with the keys {keys}")
+            want = {"t": (torch.float64, (n, rays)), "hit": (torch.int32, (n, rays)), "dir": (torch.float64, (n, rays, 2))}
+            for k in keys:
+                t = into[k]
+                if not torch.is_tensor(t) or t.dtype != want[k][0] or tuple(t.shape) != want[k][1] or t.device != e.device or not t.is_contiguous():
+                    raise ValueError(f"raycast: into[{k!r}] is a contiguous {want[k][0]} tensor {list(want[k][1])} on {e.device}")
+            out = into
+        else:
+            out = {"t": torch.full((n, rays), float(max_t), dtype=torch.float64, device=e.device),
+                   "hit": torch.full((n, rays), -1, dtype=torch.int32, device=e.device)}
+            if offsets is not None:
+                out["dir"] = torch.zeros((n, rays, 2), dtype=torch.float64, device=e.device)
+        params = eng.MwRayParams(float(max_t), float(radius), rays, self.RAY_OBSTACLES[obstacles])
+        e.ray_cast(params, out["t"], out["hit"], out.get("dir"), mask, origin, direction, offsets)
+        return out
+
+    def lidar(self, rays=64, fov=2 * math.pi, max_range=10.0, radius=0.0, obstacles="walls+entities"):
+        """A range sensor: `rays` distances in a fan around each agent's heading, by one kernel — raycast() with evenly spaced
+        offsets, built once per (rays, fov) and kept on the device, unit directions and max_t = max_range.  Returns {"t":
+        float64[N, rays], the range in metres (max_range where nothing is hit); "hit": int32[N, rays]; "dir": float64[N, rays, 2], the
+        rays' unit directions (x, z), so that agent_pos + t * dir is the point hit}; the tensors are this env's own, reused between
+        calls of the same (rays, fov).
+
+        For fov < 2 pi offset k = -fov / 2 + k * fov / (rays - 1) (a single ray looks straight ahead); for the full circle offset
+        k = k * 2 pi / rays.  A positive offset turns the ray the way `turn_left` turns the agent: the heading grows, and the agent
+        looks along (cos dir, -sin dir) in (x, z) — ray 0 of a fov < 2 pi is the rightmost one, the last the leftmost."""
+        torch, e = self.torch, self.engine
+        if not (isinstance(rays, (int, np.integer)) and not isinstance(rays, bool) and 1 <= rays <= eng.RAY_MAX):
+            raise ValueError(f"lidar: rays {rays!r} outside 1 .. {eng.RAY_MAX}")
+        if not (isinstance(fov, (int, float)) and not isinstance(fov, bool) and 0 < fov <= 2 * math.pi):
+            raise ValueError(f"lidar: fov {fov!r} outside 0 .. 2 pi radians")
+        rays = int(rays)
+        key = (rays, float(fov))
+        if key not in self._lidar_bufs:
+            if fov < 2 * math.pi:
+                off = [0.0] if rays == 1 else [-fov / 2 + k * fov / (rays - 1) for k in range(rays)]
+            else:
+                off = [k * 2 * math.pi / rays for k in range(rays)]
+            self._lidar_bufs[key] = [torch.tensor(off, dtype=torch.float64, device=e.device), None]
+        buf = self._lidar_bufs[key]
+        buf[1] = self.raycast(offsets=buf[0], max_t=max_range, radius=radius, obstacles=obstacles, into=buf[1])
+        return buf[1]
 
     def _redraw(self):
         self.engine.render(self.obs, self.depth)

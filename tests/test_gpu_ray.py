@@ -1,0 +1,399 @@
+"""Ray casts on the GPU (mw_ray_cast; MiniWorldVecEnv.raycast / lidar) against the restatement of tests/ray_reference.py — numpy in
+the documented order of operations, fed by engine.get_geometry(env) and engine.get_state() — bit for bit: t, hit and the fan's
+directions, in both launch forms (a ray per lane from the policy's threshold on, an obstacle per lane below it)."""
+import math
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+import nav_reference as nav
+import ray_reference as ref
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "..", "examples"))
+
+pytestmark = pytest.mark.gpu
+THR = int(re.search(r"constexpr int kRayPerLaneFrom = (\d+);", open(os.path.join(HERE, "..", "miniworld_amd", "csrc", "mw_policy.h")).read()).group(1))
+
+
+def _vec(env_id, n, **kw):
+    from miniworld_amd.vec_env import MiniWorldVecEnv
+    kw.setdefault("seed", 0)
+    vec = MiniWorldVecEnv(env_id, n, **kw)
+    vec.reset()
+    return vec
+
+
+def _worlds(vec, envs=None):
+    st = vec.engine.get_state()
+    return {i: nav.world_of_engine(vec.engine, st, i) for i in (range(vec.num_envs) if envs is None else envs)}, st
+
+
+def _full(rays):
+    return ref.lidar_offsets(rays, 2 * math.pi)
+
+
+def _assert_fan(vec, worlds, st, offsets, max_t, radius, obstacles, envs=None):
+    """casts the fan and compares every env's row with the restatement; returns the result as numpy"""
+    import torch
+    out = vec.raycast(offsets=torch.tensor(offsets, dtype=torch.float64, device="cuda"), max_t=max_t, radius=radius, obstacles=obstacles)
+    t, hit, d = out["t"].cpu().numpy(), out["hit"].cpu().numpy(), out["dir"].cpu().numpy()
+    for i in worlds if envs is None else envs:
+        w = worlds[i]
+        dirs = ref.fan_directions(st["agent_dir"][i], offsets)
+        o = np.tile(st["agent_pos"][i][[0, 2]][None], (len(offsets), 1))
+        wt, wh = ref.cast(w, o, dirs, max_t, radius, obstacles == "walls+entities")
+        assert np.array_equal(d[i], dirs, equal_nan=True), (i, "directions")
+        assert np.array_equal(hit[i], wh), (i, "hits that differ", np.nonzero(hit[i] != wh)[0][:8].tolist())
+        assert np.array_equal(t[i], wt), (i, "t that differ", np.nonzero(t[i] != wt)[0][:8].tolist())
+    return t, hit, d
+
+
+@pytest.fixture(scope="module")
+def maze67():
+    vec = _vec("MiniWorld-MazeS2-v0", 67)       # per-env geometry: one full group of 64 envs and a partial one
+    worlds, st = _worlds(vec)
+    yield vec, worlds, st
+    vec.engine.check()
+    vec.close()
+
+
+@pytest.mark.parametrize("rays", [1, 3, THR - 1, THR, THR + 1, 257])
+def test_fan_equals_the_restatement_in_both_forms(maze67, rays):
+    vec, worlds, st = maze67
+    t0, hit0, _ = _assert_fan(vec, worlds, st, _full(rays), 10.0, 0.0, "walls")
+    t1, hit1, _ = _assert_fan(vec, worlds, st, _full(rays), 10.0, 0.4, "walls+entities")
+    assert (hit0 >= 0).all() and (t1 <= t0).all() and (t1 < t0).any()
+    _assert_fan(vec, worlds, st, _full(rays), 0.75, 0.0, "walls", envs=range(0, 67, 8))        # a short max_t: misses
+    offs, excused = _full(rays), 0
+    for i in range(0, 67, 4):
+        o = np.tile(st["agent_pos"][i][[0, 2]][None], (rays, 1))
+        excused += ref.check_property(worlds[i], o, ref.fan_directions(st["agent_dir"][i], offs), t1[i], hit1[i], 0.4, True)[1]
+    assert excused <= ref.EXCUSED_SHARE * rays * 17
+
+
+def test_both_forms_give_the_same_bits_at_any_ray_count(maze67):
+    import torch
+    vec, worlds, st = maze67
+    try:
+        for rays in (2, 70):
+            offs = torch.tensor(_full(rays), dtype=torch.float64, device="cuda")
+            got = []
+            for form in (1, 2):
+                vec.engine.debug_set_ray_form(form)
+                got.append({k: v.clone() for k, v in vec.raycast(offsets=offs, max_t=10.0, radius=0.3, obstacles="walls+entities").items()})
+            for k in got[0]:
+                assert torch.equal(got[0][k], got[1][k]), (rays, k)
+    finally:
+        vec.engine.debug_set_ray_form(0)
+    with pytest.raises(Exception):
+        vec.engine.debug_set_ray_form(3)
+
+
+@pytest.mark.parametrize("env_id,n,rays", [("MiniWorld-FourRooms-v0", 5, 65),      # shared geometry
+                                           ("MiniWorld-YMaze-v0", 3, 65),          # walls off the axes
+                                           ("MiniWorld-Maze-v0", 3, 65),           # the largest segment list: the LDS staging at capacity
+                                           ("MiniWorld-Maze-v0", 3, 2)])
+def test_other_geometries(env_id, n, rays):
+    vec = _vec(env_id, n)
+    worlds, st = _worlds(vec)
+    for radius in (0.0, 0.4):
+        t, hit, _ = _assert_fan(vec, worlds, st, _full(rays), 30.0, radius, "walls")
+        assert (hit >= 0).all()
+    vec.engine.check()
+    vec.close()
+
+
+@pytest.mark.parametrize("env_id", ["MiniWorld-ThreeRooms-v0", "MiniWorld-PutNext-v0"])
+def test_entities_are_hit(env_id):
+    vec = _vec(env_id, 4)
+    worlds, st = _worlds(vec)
+    seen = 0
+    for rays in (129, 16):
+        for radius in (0.0, 0.2):
+            tw, hw, _ = _assert_fan(vec, worlds, st, _full(rays), 30.0, radius, "walls")
+            te, he, _ = _assert_fan(vec, worlds, st, _full(rays), 30.0, radius, "walls+entities")
+            assert (hw < ref.RAY_ENT).all() and (te <= tw).all()
+            ent = he >= ref.RAY_ENT
+            seen += int(ent.sum())
+            slots = he[ent] - ref.RAY_ENT
+            assert (slots < st["ent_kind"].shape[1]).all()
+            for i, s in zip(np.nonzero(ent)[0], slots):
+                assert st["ent_kind"][i][s] != 0
+    assert seen, "no ray reported MW_RAY_ENT + slot"
+    vec.engine.check()
+    vec.close()
+
+
+def test_a_removed_object_is_not_hit():
+    import torch
+    from test_gpu_nav import _fetch
+    vec = _vec("MiniWorld-PickupObjects-v0", 4, autoreset=False)
+    got = _fetch(vec, 0, torch)
+    vec.step(torch.full((4,), 1, dtype=torch.int32, device="cuda"))       # (the frame's tail has taken the slot out of the list)
+    worlds, st = _worlds(vec)
+    assert (st["ent_kind"][got, 0] == 0).all()
+    for rays in (THR + 1, 8):
+        t, hit, _ = _assert_fan(vec, worlds, st, _full(rays), 30.0, 0.1, "walls+entities")
+        assert not (hit[got] == ref.RAY_ENT).any()
+    # ... and the comparison would have seen it: with the slot still listed the restatement's rows are others
+    offs = _full(THR + 1)
+    for i in np.nonzero(got)[0]:
+        w = dict(worlds[int(i)])
+        w["kind"] = w["kind"].copy()
+        w["kind"][0] = 1
+        o = np.tile(st["agent_pos"][i][[0, 2]][None], (len(offs), 1))
+        wt, wh = ref.cast(w, o, ref.fan_directions(st["agent_dir"][i], offs), 30.0, 0.1, True)
+        assert not np.array_equal(wh, hit[i]) or not np.array_equal(wt, t[i])
+    vec.engine.check()
+    vec.close()
+
+
+def test_a_carried_object_is_not_hit():
+    import torch
+    from test_gpu_nav import _fetch
+    vec = _vec("MiniWorld-PutNext-v0", 4, autoreset=False)
+    got = _fetch(vec, 0, torch)
+    worlds, st = _worlds(vec)
+    assert (st["carrying"][got] == 0).all()
+    offs = _full(THR + 1)
+    t, hit, _ = _assert_fan(vec, worlds, st, offs, 30.0, 0.1, "walls+entities")
+    assert not (hit[got] == ref.RAY_ENT).any() and (hit >= ref.RAY_ENT).any()       # the others are still hit
+    for i in np.nonzero(got)[0]:        # (with the carried slot an obstacle, the restatement's rows are others)
+        w = dict(worlds[int(i)])
+        w["carry"] = -1
+        o = np.tile(st["agent_pos"][i][[0, 2]][None], (len(offs), 1))
+        wt, wh = ref.cast(w, o, ref.fan_directions(st["agent_dir"][i], offs), 30.0, 0.1, True)
+        assert not np.array_equal(wh, hit[i])
+    vec.engine.check()
+    vec.close()
+
+
+def _explicit(rng, w, rays):
+    ext = w["extent"]
+    span = max(ext[1] - ext[0], ext[3] - ext[2])
+    o = np.zeros((rays, 3))
+    o[:, 0], o[:, 1], o[:, 2] = rng.uniform(ext[0], ext[1], rays), rng.uniform(0, 1, rays), rng.uniform(ext[2], ext[3], rays)
+    ang, ln = rng.uniform(0, 2 * math.pi, rays), np.exp(rng.uniform(math.log(0.01), math.log(30.0), rays))
+    d = np.stack([np.cos(ang) * ln, np.sin(ang) * ln], axis=1)
+    o[0, [0, 2]] = ext[0] - span, ext[2] - 0.5 * span              # outside the extent
+    s = w["segs"][rng.integers(0, len(w["segs"]))]
+    o[1, [0, 2]] = (s[0] + s[2]) / 2, (s[1] + s[3]) / 2             # on a wall
+    d[2] = 0.0                                                      # a zero direction
+    d[3, 0] = np.nan                                                # NaN rows
+    o[4, 2] = np.nan
+    if rays > 5:
+        d[5] = 0.0
+        o[5, [0, 2]] = (s[0] + s[2]) / 2, (s[1] + s[3]) / 2         # a zero direction inside a wall's capsule
+    return o, d
+
+
+@pytest.mark.parametrize("rays", [7, THR + 6])
+def test_explicit_rays(rays):
+    import torch
+    n = 5
+    vec = _vec("MiniWorld-MazeS2-v0", n)
+    worlds, st = _worlds(vec)
+    rng = np.random.default_rng(2410 + rays)
+    rays_o, rays_d = zip(*(_explicit(rng, worlds[i], rays) for i in range(n)))
+    o, d = np.stack(rays_o), np.stack(rays_d)
+    to, td = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
+    for radius, obstacles, max_t in ((0.0, "walls", 1.0), (0.4, "walls+entities", 1.0), (0.2, "walls", 200.0)):
+        out = vec.raycast(direction=td, origin=to, max_t=max_t, radius=radius, obstacles=obstacles)
+        assert set(out) == {"t", "hit"}
+        t, hit = out["t"].cpu().numpy(), out["hit"].cpu().numpy()
+        excused = 0
+        for i in range(n):
+            wt, wh = ref.cast(worlds[i], o[i][:, [0, 2]], d[i], max_t, radius, obstacles == "walls+entities")
+            assert np.array_equal(hit[i], wh) and np.array_equal(t[i], wt), (i, radius)
+            excused += ref.check_property(worlds[i], o[i][:, [0, 2]], d[i], t[i], hit[i], radius, obstacles == "walls+entities")[1]
+        assert excused <= ref.EXCUSED_SHARE * n * rays
+        assert (t[:, 3:5] == max_t).all() and (hit[:, 3:5] == -1).all()
+        assert ((hit[:, 2] == -1) | (t[:, 2] == 0.0)).all()
+        if radius > 0:
+            assert (t[:, 1] == 0.0).all() and (hit[:, 1] >= 0).all()        # starts inside the capsule
+            if rays > 5:
+                assert (t[:, 5] == 0.0).all()
+    # the agents' origins with explicit directions
+    out = vec.raycast(direction=td, max_t=3.0)
+    t, hit = out["t"].cpu().numpy(), out["hit"].cpu().numpy()
+    for i in range(n):
+        wt, wh = ref.cast(worlds[i], np.tile(st["agent_pos"][i][[0, 2]][None], (rays, 1)), d[i], 3.0, 0.0, False)
+        assert np.array_equal(hit[i], wh) and np.array_equal(t[i], wt)
+    vec.engine.check()          # garbage raised nothing
+    vec.close()
+
+
+def test_a_masked_call_writes_the_masked_rows_only():
+    import torch
+    n = 9
+    vec = _vec("MiniWorld-MazeS2-v0", n)
+    for rays in (5, THR + 1):
+        offs = torch.tensor(_full(rays), dtype=torch.float64, device="cuda")
+        full = {k: v.clone() for k, v in vec.raycast(offsets=offs, max_t=10.0, radius=0.1).items()}
+        out = vec.raycast(offsets=offs, max_t=10.0, radius=0.1)
+        # garbage origins under a zero mask byte are never read: NaN everywhere but in the masked rows
+        good = vec.state(("agent_pos",))["agent_pos"][:, None, :].expand(n, rays, 3)
+        for mask in ([1, 0, 0, 1, 0, 0, 0, 0, 1], [0] * 9, [1] * 9):
+            m = torch.tensor(mask, dtype=torch.uint8, device="cuda")
+            origin = torch.where(m.bool()[:, None, None], good, float("nan")).contiguous()
+            for mm in (m, m.bool()):
+                out["t"].fill_(-7.0), out["hit"].fill_(-7), out["dir"].fill_(-7.0)
+                vec.raycast(offsets=offs, origin=origin, max_t=10.0, radius=0.1, mask=mm, into=out)
+                for i in range(n):
+                    for k in out:
+                        assert torch.equal(out[k][i], full[k][i] if mask[i] else torch.full_like(out[k][i], -7)), (mask, i, k)
+    vec.engine.check()
+    vec.close()
+
+
+def test_rays_see_the_new_worlds_under_auto_reset():
+    import torch
+    from expert_nav import expert
+    n = 8
+    vec = _vec("MiniWorld-MazeS2-v0", n)
+    worlds, st = _worlds(vec)
+    offs = _full(THR + 1)
+    first, _, _ = _assert_fan(vec, worlds, st, offs, 30.0, 0.0, "walls")
+    g = torch.Generator(device="cuda").manual_seed(7)
+    for _ in range(30):
+        vec.step(torch.randint(0, 3, (n,), generator=g, device="cuda", dtype=torch.int32))
+    worlds, st = _worlds(vec)
+    # the fan's directions are (cos, -sin)(agent_dir + offset) through the engine's sin / cos, bit for bit (inside _assert_fan)
+    _assert_fan(vec, worlds, st, offs, 30.0, 0.0, "walls")
+    _assert_fan(vec, worlds, st, _full(4), 30.0, 0.2, "walls+entities")
+    fld = vec.nav_field()
+    done_any = torch.zeros(n, dtype=torch.bool, device="cuda")
+    turn = math.radians(float(vec.engine.cfg.turn_step.default))
+    for _ in range(800):
+        if bool(done_any.any()):
+            break
+        s = vec.state(("agent_pos", "agent_dir"))
+        _, _, term, trunc = vec.step(expert(s["agent_pos"], s["agent_dir"], vec.nav_query(fld)["waypoint"], turn))
+        done = (term | trunc) != 0
+        vec.nav_field(into=fld, mask=done)
+        done_any |= done
+    assert bool(done_any.any()), "no env finished an episode"
+    worlds2, st2 = _worlds(vec)
+    i = int(done_any.nonzero()[0])
+    # (a new episode: a 2 x 2 maze may draw the floor plan it had, the box and the agent are placed anew)
+    assert not np.array_equal(worlds2[i]["segs"], worlds[i]["segs"]) or not np.array_equal(worlds2[i]["pos"], worlds[i]["pos"])
+    second, _, _ = _assert_fan(vec, worlds2, st2, offs, 30.0, 0.0, "walls")
+    _assert_fan(vec, worlds2, st2, _full(4), 30.0, 0.0, "walls")
+    assert not np.array_equal(first[i], second[i])
+    vec.engine.check()
+    vec.close()
+
+
+def test_lidar():
+    import torch
+    vec = _vec("MiniWorld-FourRooms-v0", 3)
+    worlds, st = _worlds(vec)
+    s = vec.lidar()
+    t, hit, d = s["t"].cpu().numpy(), s["hit"].cpu().numpy(), s["dir"].cpu().numpy()
+    for i in range(3):
+        dirs = ref.fan_directions(st["agent_dir"][i], _full(64))
+        wt, wh = ref.cast(worlds[i], np.tile(st["agent_pos"][i][[0, 2]][None], (64, 1)), dirs, 10.0, 0.0, True)
+        assert np.array_equal(d[i], dirs) and np.array_equal(t[i], wt) and np.array_equal(hit[i], wh)
+    # positive offsets turn the way turn_left does: after one turn_left, ray 0 looks where the ray one turn step to the left looked
+    turn = math.radians(float(vec.engine.cfg.turn_step.default))
+    offs = torch.tensor([0.0, turn], dtype=torch.float64, device="cuda")
+    before = vec.raycast(offsets=offs, max_t=50.0)["t"].clone()
+    vec.step(torch.zeros(3, dtype=torch.int32, device="cuda"))       # turn_left
+    after = vec.raycast(offsets=offs, max_t=50.0)["t"]
+    assert torch.allclose(after[:, 0], before[:, 1], rtol=0, atol=1e-9)
+    assert vec.lidar() is s
+    vec.engine.check()
+    vec.close()
+
+
+def test_refusals():
+    import torch
+    from miniworld_amd import engine
+    vec = _vec("MiniWorld-FourRooms-v0", 3)
+    e = vec.engine
+
+    def bufs(rays):
+        return (torch.zeros((3, rays), dtype=torch.float64, device="cuda"), torch.zeros((3, rays), dtype=torch.int32, device="cuda"),
+                torch.zeros((3, rays, 2), dtype=torch.float64, device="cuda"), torch.zeros(rays, dtype=torch.float64, device="cuda"))
+    t, hit, d, offs = bufs(4)
+    P = engine.MwRayParams
+    for p in (P(0.0, 0.0, 4, 0), P(-1.0, 0.0, 4, 0), P(float("inf"), 0.0, 4, 0), P(float("nan"), 0.0, 4, 0), P(1.0, -0.1, 4, 0), P(1.0, float("inf"), 4, 0),
+              P(1.0, float("nan"), 4, 0), P(1.0, 0.0, 4, 2), P(1.0, 0.0, 4, -1)):
+        with pytest.raises(engine.EngineError):
+            e.ray_cast(p, t, hit, offsets=offs)
+    with pytest.raises(engine.EngineError):     # both, neither
+        e.ray_cast(P(1.0, 0.0, 4, 0), t, hit, direction=d, offsets=offs)
+    with pytest.raises(engine.EngineError):
+        e.ray_cast(P(1.0, 0.0, 4, 0), t, hit)
+    with pytest.raises(engine.EngineError):
+        e.ray_cast(P(1.0, 0.0, 4, 0), None, hit, offsets=offs)
+    lib, sp = e.lib, engine._stream_ptr(e.device)
+    for rays in (0, -1, engine.RAY_MAX + 1):    # (past the binding's tensor checks: the library's own)
+        p = P(1.0, 0.0, rays, 0)
+        assert lib.mw_ray_cast(e.h, p, None, None, None, offs.data_ptr(), t.data_ptr(), None, None, sp) == -1
+    assert lib.mw_ray_cast(e.h, None, None, None, None, offs.data_ptr(), t.data_ptr(), None, None, sp) == -1
+    assert lib.mw_ray_cast(e.h, P(1.0, 0.0, 4, 0), None, None, None, offs.data_ptr(), None, None, None, sp) == -1
+    assert (t == 0).all() and (hit == 0).all()      # nothing was touched
+    with pytest.raises(ValueError):
+        vec.raycast(offsets=offs, max_t=0.0)
+    e.check()
+    # the limit itself is served
+    t, hit, d, offs = bufs(engine.RAY_MAX)
+    e.ray_cast(P(50.0, 0.0, engine.RAY_MAX, 0), t, hit, offsets=offs)
+    assert bool((t[:, 0:1] == t).all()) and bool((hit >= 0).all())       # all offsets 0: one ray, 4096 times
+    e.check()
+    vec.close()
+
+
+def test_the_engine_is_left_as_it_was():
+    """a twin that never casts returns identical observations, rewards, flags and state over 20 steps"""
+    import torch
+    n = 6
+    a, b = _vec("MiniWorld-MazeS2-v0", n), _vec("MiniWorld-MazeS2-v0", n)
+    g = torch.Generator(device="cuda").manual_seed(11)
+    for _ in range(20):
+        act = torch.randint(0, 3, (n,), generator=g, device="cuda", dtype=torch.int32)
+        a.lidar()
+        a.lidar(rays=7, fov=1.0, radius=0.2)
+        ra, rb = a.step(act), b.step(act)
+        for x, y in zip(ra, rb):
+            assert torch.equal(x, y)
+    sa, sb = a.engine.get_state(), b.engine.get_state()
+    for k in sa:
+        assert np.array_equal(sa[k], sb[k]), k
+    a.engine.check()
+    a.close()
+    b.close()
+
+
+def test_the_smoothed_expert_reaches_the_box_in_every_maze():
+    """MazeS3 x 16, seed 0, no domain randomisation, no auto-reset: the expert of examples/expert_smooth.py for max_episode_steps
+    steps; every env terminates with a positive reward (on the oracle's dynamics: tests/test_ray_cpu.py)"""
+    import torch
+    from expert_nav import expert
+    from expert_smooth import Smoother
+    n = 16
+    vec = _vec("MiniWorld-MazeS3-v0", n, autoreset=False, domain_rand=False)
+    fld = vec.nav_field()
+    sm = Smoother(vec, fld)
+    turn = math.radians(float(vec.engine.cfg.turn_step.default))
+    won = torch.zeros(n, dtype=torch.bool, device="cuda")
+    over = torch.zeros(n, dtype=torch.bool, device="cuda")
+    for _ in range(int(vec.engine.cfg.max_episode_steps)):
+        st = vec.state(("agent_pos", "agent_dir"))
+        pos, heading = st["agent_pos"].clone(), st["agent_dir"].clone()
+        target, _ = sm.aim(pos)
+        act = torch.where(over, 1, expert(pos, heading, target, turn)).to(torch.int32)
+        _, rew, term, trunc = vec.step(act)
+        sm.moved(vec.state(("agent_pos",))["agent_pos"], act, torch.zeros_like(over))
+        won |= ~over & (term != 0) & (rew > 0)
+        over |= (term | trunc) != 0
+        if bool(over.all()):
+            break
+    assert bool(won.all()), won.tolist()
+    vec.engine.check()
+    vec.close()
