@@ -327,7 +327,8 @@ int mw_set_state_where(mw_engine *e, const uint8_t *d_mask, const mw_state_view 
  * mask: host uint8[num_envs] or NULL (= all); seeds: host uint64[num_envs] or NULL.
  * With MW_GEN_NONE (host-generated worlds) only the re-seeding happens: seeds[i] (masked) re-seeds env i's device
  * stream, which serves the per-step domain-randomisation draws (miniworld.py:677-680); seeds == NULL is an error.
- * A pending next-step auto-reset of a reset env is dropped (the env's next step is an ordinary one).
+ * A pending next-step auto-reset of a reset env is dropped (the env's next step is an ordinary one), and so is the mark that an
+ * entity has just left its list (mw_get_frame_clean): nothing of the old episode's last pickup reaches the new world's first step.
  * With a frame stack (mw_set_frame_stack) the envs whose world it writes are marked: mw_stack_refresh or their next push rebuilds
  * their stacks (a MW_GEN_NONE engine's reset writes no world and marks nothing). */
 int mw_reset(mw_engine *e, const uint8_t *mask, const uint64_t *seeds, void *stream);

@@ -14,6 +14,7 @@ extern "C" __global__ __launch_bounds__(64) void MW_KERNEL_NAME(mw_reset)(MwArgs
     if (!wave_per_env || threadIdx.x == 0) {
         if (mark_refill) a.refill_mask[env] = 1u;      // spare mode: its spare is stale now
         a.reset_pending[env] = 0;       // the new world replaces a pending next-step auto-reset
+        a.pending_remove[env] = -1;     // ... and nothing has "just left" its entity list (the old episode's last pickup, K1's frame_clean)
         a.fc_epoch[env] += 1u;          // ... and no cached frame of the old one shows it (MwArgs::fc_epoch)
     }
 }
@@ -75,6 +76,7 @@ extern "C" __global__ __launch_bounds__(64) void MW_KERNEL_NAME(mw_reset_where)(
     if (!wave_per_env || threadIdx.x == 0) {
         if (a.refill_mask) a.refill_mask[env] = 1u;     // spare mode: its spare is stale now
         a.reset_pending[env] = 0;
+        a.pending_remove[env] = -1;     // (as mw_reset_kernel: the old episode's removal is not the new world's)
         a.fc_epoch[env] += 1u;
     }
 }
@@ -105,6 +107,6 @@ extern "C" __global__ __launch_bounds__(64) void mw_take_spare_kernel(MwArgs a, 
     if (env >= a.N) return;
     if (!force_all && !mask[env]) return;
     mw::take_spare(a, env, (int)threadIdx.x);
-    if (threadIdx.x == 0) { a.refill_mask[env] = 1u; a.reset_pending[env] = 0; a.fc_epoch[env] += 1u; }
+    if (threadIdx.x == 0) { a.refill_mask[env] = 1u; a.reset_pending[env] = 0; a.pending_remove[env] = -1; a.fc_epoch[env] += 1u; }
 }
 #endif

@@ -3,6 +3,8 @@ import os
 
 import numpy as np
 
+from engine_model import ModelEnv
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
@@ -215,70 +217,14 @@ def scene_of_vec_env(vec, st, i, row=None):
     return sc
 
 
-class EpisodeMirror:
-    """One environment of a device batch replayed on the CPU from the same seed, with nothing of the engine in it:
-    worlds come from the host world generator (seed-exact with the reference's reset(), tests/test_host_logic_cpu.py),
-    steps from the C oracle's dynamics (pyoracle.Dynamics, pinned on the reference's trajectories), the three per-step
-    domain-randomisation draws from the env's own numpy stream in the reference's order (miniworld.py:677-680), and an
-    episode's end continues that stream with reset() exactly like the device's same-step auto-reset."""
-
-    def __init__(self, cls, seed, domain_rand, task, **env_kwargs):
-        self.h = cls(host_only=True, domain_rand=domain_rand, **env_kwargs)
-        self.h.reset(seed=int(seed))
-        self.dr, self.task = domain_rand, task
-        self.episodes = 0
-        self._new_episode()
-
-    def _new_episode(self):
-        import pyoracle
-        from miniworld_amd.scene import scene_from_env
-        h = self.h
-        self.sc = scene_from_env(h)
-        ents = [e for e in h.entities if e is not h.agent]
-        # PutNext's rule (putnext.py:74-78) is about two of the boxes; every other task rule is about slot 0 or about none
-        g0, g1 = (ents.index(h.red_box), ents.index(h.yellow_box)) if hasattr(h, "red_box") else (0, -1)
-        self.dyn = pyoracle.Dynamics(self.sc, self.task, int(min(float(h.max_episode_steps), 2 ** 30)), goal_ent=g0, goal_ent2=g1,
-                                     num_objs=len(self.sc["ents_kind"]), max_forward_step=float(h.max_forward_step),
-                                     agent_radius=float(h.agent.radius))
-        self.fresh = True
-        self.episodes += 1
+class EpisodeMirror(ModelEnv):
+    """One environment of a device batch replayed on the CPU from the same seed, with nothing of the engine in it: engine_model.ModelEnv
+    (host world generator, the C oracle's dynamics, the per-step domain-randomisation draws from the env's own numpy stream) with
+    the same-step auto-reset folded into step(): an episode's end continues that stream with reset() exactly like the device's
+    same-step auto-reset."""
 
     def step(self, action):
-        h = self.h
-        rand = h.np_random if self.dr else None
-        p = [h.params.sample(rand, k) for k in ("forward_step", "forward_drift", "turn_step")]
-        r, te, tr = self.dyn.step(int(action), *p)
-        self.fresh = False
+        r, te, tr = self.substep(action)
         if te or tr:
-            h.reset()
-            self._new_episode()
+            self.reset()
         return r, te, tr
-
-    def state(self):
-        """(agent_pos, agent_dir, carrying, step_count, alive[E], ent_pos[E,3], ent_dir[E]) after the last step."""
-        E = len(self.sc["ents_kind"])
-        ag, ents = self.dyn.ag, self.dyn.ents
-        return (np.array(ag.pos[:]), float(ag.dir), int(ag.carrying), int(ag.step_count),
-                np.array([bool(ents[k].alive) for k in range(E)]),
-                np.array([ents[k].pos[:] for k in range(E)]).reshape(E, 3), np.array([ents[k].dir for k in range(E)]))
-
-    def frame_scene(self):
-        """The scene the observation returned by the last step shows: a fresh episode's initial world, or the state
-        at render time — rendering happens before PickupObjects removes what was picked up (pickupobjects.py:86-88)."""
-        sc = dict(self.sc)
-        if not self.fresh:
-            E = len(sc["ents_kind"])
-            ag, ents = self.dyn.ag, self.dyn.render_ents
-            sc["agent_pos"], sc["agent_dir"] = np.array(ag.pos[:]), np.float64(ag.dir)
-            sc["ents_pos"] = np.array([ents[k].pos[:] for k in range(E)]).reshape(E, 3)
-            sc["ents_dir"] = np.array([ents[k].dir for k in range(E)])
-            sc["ents_kind"] = np.where([bool(ents[k].alive) for k in range(E)], sc["ents_kind"], 0).astype(np.int32)
-        return sc
-
-    def meshes(self):
-        from miniworld_amd.objmesh import ObjMesh
-        out = {}
-        for name in [str(m) for m in self.sc["mesh_names"]]:
-            m = ObjMesh.get(name)
-            out[name] = {"verts": m.verts, "norms": m.norms, "texcs": m.texcs, "colors": m.colors}
-        return out
