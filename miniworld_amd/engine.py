@@ -10,12 +10,14 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # (MW_ENGINE_LIB: a variant build of the library for A/B measurements — tools/perf; the product is csrc/libmwengine.so)
-LIB_PATH = os.environ.get("MW_ENGINE_LIB") or os.path.join(_CSRC, "libmwengine.so")
+PRODUCT_PATH = os.path.join(_CSRC, "libmwengine.so")
+LIB_PATH = os.environ.get("MW_ENGINE_LIB") or PRODUCT_PATH
 
 ABI_VERSION = 4
 MAX_REPEAT = 256            # MW_MAX_REPEAT
@@ -35,23 +37,6 @@ AUTORESET_OFF, AUTORESET_SAME_STEP, AUTORESET_NEXT_STEP = 0, 1, 2
 OBS_HWC_U8, OBS_CWH_U8, OBS_GREY_F64 = 0, 1, 2
 RNG_PHILOX, RNG_PCG64 = 0, 1
 PATH_TILE, PATH_QUAD, PATH_QUAD_MESH, PATH_GENERIC = 0, 1, 2, 3
-
-EXPORTS = [
-    "mw_create", "mw_destroy", "mw_last_error", "mw_upload_texture", "mw_upload_mesh",
-    "mw_set_geometry", "mw_get_geometry", "mw_set_state", "mw_get_state", "mw_set_step_params", "mw_reset",
-    "mw_step", "mw_step_repeat", "mw_step_plan", "mw_step_plan_trace", "mw_render", "mw_render_top", "mw_render_view", "mw_visible_ents", "mw_set_obs_layout", "mw_pcg64_draws", "mw_check", "mw_kernel_time_ms", "mw_raster_path", "mw_get_info", "mw_get_final_info", "mw_get_reset_pending", "mw_set_frame_reuse", "mw_get_frame_clean", "mw_set_frame_cache", "mw_get_frame_source", "mw_get_frame_plan", "mw_set_final_obs", "mw_get_list_lengths", "mw_debug_set_mesh_frame_seq", "mw_debug_get_slow_heads",
-    "mw_set_gen_program", "mw_selftest_rcp", "mw_selftest_div", "mw_selftest_sort", "mw_selftest_q",
-    "mw_selftest_sincosf",
-    "mw_set_frame_stack", "mw_stack_refresh", "mw_stack_window",
-    "mw_snapshot_bytes", "mw_snapshot_save", "mw_snapshot_load",
-    "mw_snapshot_frames_bytes", "mw_snapshot_save_frames", "mw_snapshot_load_frames",
-    "mw_snapshot_save_at", "mw_snapshot_save_frames_at", "mw_snapshot_load_where", "mw_snapshot_load_frames_where",
-    "mw_reset_where", "mw_set_reset_seeds",
-    "mw_get_state_device", "mw_set_state_where",
-    "mw_nav_build", "mw_nav_query", "mw_debug_set_nav_passes",
-    "mw_ray_cast", "mw_debug_set_ray_form",
-]
-
 
 class MwRange(C.Structure):
     _fields_ = [("default", C.c_double), ("lo", C.c_double), ("hi", C.c_double)]
@@ -179,8 +164,99 @@ class EngineError(RuntimeError):
     pass
 
 
+def torch_dtype(dt):
+    """the torch dtype of a field table's numpy type (STATE_FIELDS, TRACE_FIELDS)"""
+    import torch
+    return getattr(torch, np.dtype(dt).name)
+
+
+def _sig(*argtypes, ret=C.c_int):
+    return list(argtypes), ret
+
+
+# The functions of include/mwengine.h: name -> (argtypes, restype), applied by load_library().  Handles and buffers are void pointers
+# (the binding passes raw addresses), structs and host out-values are typed (tests/test_abi_mirror_cpu.py compares the table with the
+# header: the names, each parameter's class, the return type).
+vp, i32, i64, P = C.c_void_p, C.c_int32, C.c_int64, C.POINTER
+SIGNATURES = {
+    "mw_create": _sig(P(MwConfig), P(vp)),
+    "mw_destroy": _sig(vp, ret=None),
+    "mw_last_error": _sig(vp, ret=C.c_char_p),
+    "mw_upload_texture": _sig(vp, i32, vp, i32, i32),
+    "mw_upload_mesh": _sig(vp, i32, vp, vp, vp, vp, i32, i32),
+    "mw_set_geometry": _sig(vp, i32, vp, i32, vp, i32),
+    "mw_get_geometry": _sig(vp, i32, vp, P(i32), vp, P(i32)),
+    "mw_set_state": _sig(vp, i32, i32, P(MwStateView)),
+    "mw_get_state": _sig(vp, i32, i32, P(MwStateView)),
+    "mw_get_state_device": _sig(vp, i32, i32, P(MwStateView), vp),
+    "mw_set_state_where": _sig(vp, vp, P(MwStateView), vp),
+    "mw_set_step_params": _sig(vp, vp),
+    "mw_set_gen_program": _sig(vp, P(MwGenProgram), vp, vp, vp, vp, i32, vp, i32),
+    "mw_reset": _sig(vp, vp, vp, vp),
+    "mw_reset_where": _sig(vp, vp, vp, vp),
+    "mw_set_reset_seeds": _sig(vp, vp),
+    "mw_step": _sig(vp, vp, vp, vp, vp, vp, vp, vp),
+    "mw_step_repeat": _sig(vp, vp, i32, vp, vp, vp, vp, vp, vp, vp),
+    "mw_step_plan": _sig(vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp),
+    "mw_step_plan_trace": _sig(vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, P(MwPlanTrace), vp),
+    "mw_render": _sig(vp, vp, vp, vp),
+    "mw_render_top": _sig(vp, vp, vp, i32, vp),
+    "mw_render_view": _sig(vp, i32, i32, i32, i32, i32, vp, vp, vp),
+    "mw_visible_ents": _sig(vp, i32, i32, vp, vp),
+    "mw_set_obs_layout": _sig(vp, i32),
+    "mw_set_final_obs": _sig(vp, vp, vp),
+    "mw_set_frame_stack": _sig(vp, i32, i32, vp, vp),
+    "mw_stack_refresh": _sig(vp, vp, vp),
+    "mw_stack_window": _sig(vp, P(i32), P(i64)),
+    "mw_snapshot_bytes": _sig(vp, i32, ret=i64),
+    "mw_snapshot_save": _sig(vp, vp, i32, vp, i32, vp),
+    "mw_snapshot_load": _sig(vp, vp, vp, i32, vp, i32, i32, vp),
+    "mw_snapshot_frames_bytes": _sig(vp, i32, i32, ret=i64),
+    "mw_snapshot_save_frames": _sig(vp, vp, i32, vp, vp, vp, i32, i32, vp),
+    "mw_snapshot_load_frames": _sig(vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp),
+    "mw_snapshot_save_at": _sig(vp, vp, vp, i32, vp, i32, vp),
+    "mw_snapshot_save_frames_at": _sig(vp, vp, vp, i32, vp, vp, vp, i32, i32, vp),
+    "mw_snapshot_load_where": _sig(vp, vp, vp, vp, i32, i32, vp),
+    "mw_snapshot_load_frames_where": _sig(vp, vp, vp, vp, i32, i32, i32, vp, vp, vp),
+    "mw_nav_build": _sig(vp, P(MwNavParams), vp, vp, vp, vp),
+    "mw_nav_query": _sig(vp, P(MwNavParams), vp, vp, vp, vp, vp, vp, vp),
+    "mw_debug_set_nav_passes": _sig(vp, vp),
+    "mw_ray_cast": _sig(vp, P(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp),
+    "mw_debug_set_ray_form": _sig(vp, C.c_int),
+    "mw_pcg64_draws": _sig(C.c_uint64, i32, vp, vp),
+    "mw_selftest_rcp": _sig(vp, vp, vp),
+    "mw_selftest_div": _sig(vp, vp),
+    "mw_selftest_sort": _sig(vp, vp, i32, vp),
+    "mw_selftest_q": _sig(vp, vp),
+    "mw_selftest_sincosf": _sig(vp, C.c_uint64, vp),
+    "mw_check": _sig(vp, vp),
+    "mw_kernel_time_ms": _sig(vp, i32, P(C.c_double), P(C.c_double), P(i64)),
+    "mw_raster_path": _sig(vp),
+    "mw_get_info": _sig(vp, vp, vp, i32, vp),
+    "mw_get_final_info": _sig(vp, vp, vp, vp),
+    "mw_get_reset_pending": _sig(vp, vp, vp),
+    "mw_set_frame_reuse": _sig(vp, i32),
+    "mw_get_frame_clean": _sig(vp, vp, vp),
+    "mw_set_frame_cache": _sig(vp, i32),
+    "mw_get_frame_source": _sig(vp, vp, vp),
+    "mw_get_frame_plan": _sig(vp, vp, i64, vp, vp),
+    "mw_get_list_lengths": _sig(vp, i32, i32, vp, vp),
+    "mw_debug_set_mesh_frame_seq": _sig(vp, C.c_uint32),
+    "mw_debug_get_slow_heads": _sig(vp, vp, vp),
+}
+EXPORTS = list(SIGNATURES)      # what a built library must export (__graft_entry__.build)
+
+_said = set()
+
+
 def build_library(force: bool = False) -> str:
-    """Compile libmwengine.so for gfx950 with hipcc (in-tree); returns its path."""
+    """Compile libmwengine.so for gfx950 with hipcc (in-tree); returns its path.  With MW_ENGINE_LIB set nothing is built: that file
+    is what load_library() opens (a variant build made elsewhere; the in-tree sources say nothing about its age), said once."""
+    if LIB_PATH != PRODUCT_PATH:
+        if LIB_PATH not in _said:
+            _said.add(LIB_PATH)
+            print(f"miniworld_amd: MW_ENGINE_LIB is set: loading {LIB_PATH} as it is, not building {PRODUCT_PATH}", file=sys.stderr)
+        return LIB_PATH
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".h"))]
     srcs.append(os.path.join(_CSRC, "..", "..", "include", "mwengine.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -208,70 +284,9 @@ def load_library():
             f"{LIB_PATH} not found: the HIP engine is not built (run `python -c 'import __graft_entry__ as g; "
             "g.build()'` or miniworld_amd/csrc/build.sh).  There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, i32 = C.c_void_p, C.c_int32
-    L.mw_create.argtypes = [C.POINTER(MwConfig), C.POINTER(vp)]
-    L.mw_destroy.argtypes = [vp]
-    L.mw_destroy.restype = None
-    L.mw_last_error.argtypes = [vp]
-    L.mw_last_error.restype = C.c_char_p
-    L.mw_upload_texture.argtypes = [vp, i32, vp, i32, i32]
-    L.mw_upload_mesh.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32]
-    L.mw_set_geometry.argtypes = [vp, i32, vp, i32, vp, i32]
-    L.mw_get_geometry.argtypes = [vp, i32, vp, C.POINTER(i32), vp, C.POINTER(i32)]
-    L.mw_set_state.argtypes = [vp, i32, i32, C.POINTER(MwStateView)]
-    L.mw_get_state.argtypes = [vp, i32, i32, C.POINTER(MwStateView)]
-    L.mw_get_state_device.argtypes = [vp, i32, i32, C.POINTER(MwStateView), vp]
-    L.mw_set_state_where.argtypes = [vp, vp, C.POINTER(MwStateView), vp]
-    L.mw_nav_build.argtypes = [vp, C.POINTER(MwNavParams), vp, vp, vp, vp]
-    L.mw_nav_query.argtypes = [vp, C.POINTER(MwNavParams), vp, vp, vp, vp, vp, vp, vp]
-    L.mw_debug_set_nav_passes.argtypes = [vp, vp]
-    L.mw_ray_cast.argtypes = [vp, C.POINTER(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mw_debug_set_ray_form.argtypes = [vp, i32]
-    L.mw_set_step_params.argtypes = [vp, vp]
-    L.mw_set_gen_program.argtypes = [vp, C.POINTER(MwGenProgram), vp, vp, vp, vp, i32, vp, i32]
-    L.mw_reset.argtypes = [vp, vp, vp, vp]
-    L.mw_reset_where.argtypes = [vp, vp, vp, vp]
-    L.mw_set_reset_seeds.argtypes = [vp, vp]
-    L.mw_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mw_step_repeat.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    L.mw_step_plan.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mw_step_plan_trace.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(MwPlanTrace), vp]
-    L.mw_render.argtypes = [vp, vp, vp, vp]
-    L.mw_render_top.argtypes = [vp, vp, vp, i32, vp]
-    L.mw_render_view.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    L.mw_visible_ents.argtypes = [vp, i32, i32, vp, vp]
-    L.mw_set_obs_layout.argtypes = [vp, i32]
-    L.mw_set_final_obs.argtypes = [vp, vp, vp]
-    L.mw_set_frame_stack.argtypes = [vp, i32, i32, vp, vp]
-    L.mw_stack_refresh.argtypes = [vp, vp, vp]
-    L.mw_stack_window.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_int64)]
-    L.mw_snapshot_bytes.argtypes = [vp, i32]
-    L.mw_snapshot_bytes.restype = C.c_int64
-    L.mw_snapshot_save.argtypes = [vp, vp, i32, vp, i32, vp]
-    L.mw_snapshot_load.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp]
-    L.mw_snapshot_frames_bytes.argtypes = [vp, i32, i32]
-    L.mw_snapshot_frames_bytes.restype = C.c_int64
-    L.mw_snapshot_save_frames.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp]
-    L.mw_snapshot_load_frames.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]
-    L.mw_snapshot_save_at.argtypes = [vp, vp, vp, i32, vp, i32, vp]
-    L.mw_snapshot_save_frames_at.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, vp]
-    L.mw_snapshot_load_where.argtypes = [vp, vp, vp, vp, i32, i32, vp]
-    L.mw_snapshot_load_frames_where.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-    L.mw_pcg64_draws.argtypes = [C.c_uint64, i32, vp, vp]
-    L.mw_check.argtypes = [vp, vp]
-    L.mw_kernel_time_ms.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    L.mw_raster_path.argtypes = [vp]
-    L.mw_get_info.argtypes = [vp, vp, vp, i32, vp]
-    L.mw_get_final_info.argtypes = [vp, vp, vp, vp]
-    L.mw_get_reset_pending.argtypes = [vp, vp, vp]
-    L.mw_set_frame_reuse.argtypes = [vp, i32]
-    L.mw_get_frame_clean.argtypes = [vp, vp, vp]
-    L.mw_set_frame_cache.argtypes = [vp, i32]
-    L.mw_get_frame_source.argtypes = [vp, vp, vp]
-    L.mw_get_frame_plan.argtypes = [vp, vp, C.c_int64, vp, vp]
-    L.mw_get_list_lengths.argtypes = [vp, i32, i32, vp, vp]
-    L.mw_debug_set_mesh_frame_seq.argtypes = [vp, C.c_uint32]
-    L.mw_debug_get_slow_heads.argtypes = [vp, vp, vp]
+    for name, (argtypes, restype) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = argtypes, restype
     _lib = L
     return L
 
@@ -312,24 +327,33 @@ class Engine:
     """One mw_engine: N environments resident on one GPU."""
 
     def __init__(self, cfg: MwConfig):
-        import torch
-        if not torch.cuda.is_available():
-            raise EngineError("no ROCm device visible: the mwengine HIP path cannot run (no CPU fallback exists)")
-        self.lib = load_library()
+        self._init_host(cfg)
+        self._open()
+
+    def _init_host(self, cfg):
+        """Every attribute the class reads that needs no device (a test without one replaces _open() alone)."""
         cfg.abi_version = ABI_VERSION
         self.cfg = cfg
         self.N = cfg.num_envs
         self.E = max(cfg.max_ents, 1)
         self.W, self.H = cfg.obs_width, cfg.obs_height
-        self.obs_layout = OBS_HWC_U8
-        self.device = torch.device("cuda", cfg.device_id)
+        self._set_layout(OBS_HWC_U8)
+        self.frame_reuse = False
+        self.frame_cache = 0
+        self.lib = self.h = self.device = None
+
+    def _open(self):
+        """Where the engine lives: the library, the torch device and the mw_engine handle."""
+        import torch
+        if not torch.cuda.is_available():
+            raise EngineError("no ROCm device visible: the mwengine HIP path cannot run (no CPU fallback exists)")
+        self.lib = load_library()
+        self.device = torch.device("cuda", self.cfg.device_id)
         h = C.c_void_p()
-        rc = self.lib.mw_create(C.byref(cfg), C.byref(h))
+        rc = self.lib.mw_create(C.byref(self.cfg), C.byref(h))
         if rc != 0:
             raise EngineError(f"mw_create failed ({rc}): {self.lib.mw_last_error(None).decode()}")
         self.h = h
-        self.frame_reuse = False
-        self.frame_cache = 0
 
     def _check(self, rc, what):
         if rc != 0:
@@ -400,15 +424,18 @@ class Engine:
     def _state_tensor(self, t, name, rows):
         """A field of a device-side state view: a contiguous tensor [rows, *field shape] of the field's dtype (float64 / int32) on the
         engine's device.  Checked, never converted: the kernels read raw pointers (_dev_tensor)."""
-        import torch
         if name not in STATE_FIELDS:
             raise EngineError(f"{name!r} is no state field; have {sorted(STATE_FIELDS)}")
         dt, shp = STATE_FIELDS[name]
-        dtype, shape = (torch.float64 if dt is np.float64 else torch.int32), (rows,) + shp(self.E)
-        if not torch.is_tensor(t) or tuple(t.shape) != shape:
-            raise EngineError(f"{name}: need a {dtype} tensor of shape {shape} on {self.device}, got "
+        return self._shaped_tensor(t, name, torch_dtype(dt), (rows,) + shp(self.E))
+
+    def _shaped_tensor(self, t, name, dtype, shape, more_rows=False):
+        """A tensor whose shape matters beside its size: `shape` exactly (more_rows: shape[0] rows or more), then _dev_tensor's check."""
+        import torch
+        if not torch.is_tensor(t) or t.dim() != len(shape) or tuple(t.shape[1:]) != shape[1:] or (t.shape[0] < shape[0] if more_rows else t.shape[0] != shape[0]):
+            raise EngineError(f"{name}: need a {dtype} tensor of shape {shape}{' or more rows' if more_rows else ''} on {self.device}, got "
                               f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-        return self._dev_tensor(t, name, dtype, int(np.prod(shape, dtype=np.int64)))
+        return self._dev_tensor(t, name, dtype, t.numel())
 
     def _device_view(self, tensors: dict, rows: int):
         view = MwStateView()
@@ -431,7 +458,7 @@ class Engine:
         if first < 0 or count < 0 or first + count > self.N:
             raise EngineError(f"get_state_device: envs {first} .. {first + count - 1} of {self.N}")
         if out is None:
-            out = {name: torch.zeros((count,) + shp(self.E), dtype=torch.float64 if dt is np.float64 else torch.int32, device=self.device)
+            out = {name: torch.zeros((count,) + shp(self.E), dtype=torch_dtype(dt), device=self.device)
                    for name, (dt, shp) in STATE_FIELDS.items()}
         if not out:
             raise EngineError("get_state_device: no field named")
@@ -462,8 +489,7 @@ class Engine:
         shortest-path cost to `target` (float64[N, 3], device; None = entity slot params.target_slot).  One kernel on the current
         stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the library is called."""
         self._nav_tensors(params, field, target)
-        if mask is not None:
-            mask = self._mask_tensor(mask)
+        mask = self._mask_tensor(mask, optional=True)
         self._check(self.lib.mw_nav_build(self.h, C.byref(params), _ptr(mask), _ptr(target), _ptr(field), _stream_ptr(self.device)), "mw_nav_build")
 
     def nav_query(self, params: MwNavParams, field, target=None, pos=None, cost=None, next=None, waypoint=None):
@@ -501,8 +527,7 @@ class Engine:
         self._dev_tensor(origin, "origin", torch.float64, n * 3)
         self._dev_tensor(direction, "direction", torch.float64, n * 2)
         self._dev_tensor(offsets, "offsets", torch.float64, int(params.rays))
-        if mask is not None:
-            mask = self._mask_tensor(mask)
+        mask = self._mask_tensor(mask, optional=True)
         self._check(self.lib.mw_ray_cast(self.h, C.byref(params), _ptr(mask), _ptr(origin), _ptr(direction), _ptr(offsets), _ptr(t), _ptr(hit), _ptr(dir_out),
                                          _stream_ptr(self.device)), "mw_ray_cast")
 
@@ -521,11 +546,8 @@ class Engine:
                                                 m.ctypes.data, len(p), sg.ctypes.data, len(sg)), "mw_set_gen_program")
 
     def set_step_params(self, params: np.ndarray | None):
-        if params is None:
-            self._check(self.lib.mw_set_step_params(self.h, None), "mw_set_step_params")
-        else:
-            p = np.ascontiguousarray(params, np.float64).reshape(self.N, 3)
-            self._check(self.lib.mw_set_step_params(self.h, p.ctypes.data), "mw_set_step_params")
+        p = None if params is None else np.ascontiguousarray(params, np.float64).reshape(self.N, 3)
+        self._check(self.lib.mw_set_step_params(self.h, None if p is None else p.ctypes.data), "mw_set_step_params")
 
     def reset(self, mask: np.ndarray | None = None, seeds: np.ndarray | None = None):
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
@@ -561,15 +583,32 @@ class Engine:
         self._reset_seeds = next_seed
 
     # -- hot path ---------------------------------------------------------------------
-    def _dev_tensor(self, t, name, dtype, numel):
+    def _dev_tensor(self, t, name, dtype, numel, at_least=False):
         """The kernels read raw pointers: a tensor of another dtype / device / stride pattern would be read as garbage
-        (an int64 action tensor as int32 pairs, a CPU tensor as a fault).  Outputs must already be right; see step()."""
+        (an int64 action tensor as int32 pairs, a CPU tensor as a fault).  Outputs must already be right; see step().
+        at_least: a buffer that may be larger than what is written (record buffers, the rows of step_reward)."""
         if t is None:
             return None
-        if t.device != self.device or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel:
-            raise EngineError(f"{name}: need a contiguous {dtype} tensor of {numel} elements on {self.device}, got "
+        if t.device != self.device or t.dtype != dtype or not t.is_contiguous() or (t.numel() < numel if at_least else t.numel() != numel):
+            raise EngineError(f"{name}: need a contiguous {dtype} tensor of {'at least ' if at_least else ''}{numel} elements on {self.device}, got "
                               f"{t.dtype} {tuple(t.shape)} on {t.device}{'' if t.is_contiguous() else ' (non-contiguous)'}")
         return t
+
+    def _set_layout(self, layout):
+        """obs_layout, and with it obs_spec: the (dtype, elements per frame) of an observation in that layout — the one place"""
+        import torch
+        self.obs_layout = int(layout)
+        self.obs_spec = (torch.float64, self.H * self.W) if self.obs_layout == OBS_GREY_F64 else (torch.uint8, self.H * self.W * 3)
+
+    def _obs_tensor(self, obs, name="obs"):
+        """a buffer of N frames in the current layout (obs_buffer()'s dtype and size), or None"""
+        dtype, per_frame = self.obs_spec
+        return self._dev_tensor(obs, name, dtype, self.N * per_frame)
+
+    def _depth_tensor(self, depth, name="depth"):
+        """float32 [N, H, W] depth, or None"""
+        import torch
+        return self._dev_tensor(depth, name, torch.float32, self.N * self.H * self.W)
 
     def _step_tensors(self, actions, obs, depth, reward, term, trunc):
         """The checks step() and step_repeat() share; returns the int32 actions."""
@@ -578,8 +617,8 @@ class Engine:
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
         if actions.numel() != self.N:
             raise EngineError(f"actions: {actions.numel()} elements for {self.N} envs")
-        obs_numel = self.N * self.H * self.W * (1 if self.obs_layout == OBS_GREY_F64 else 3)
-        self._dev_tensor(obs, "obs", torch.float64 if self.obs_layout == OBS_GREY_F64 else torch.uint8, obs_numel)
+        dtype, per_frame = self.obs_spec        # (_obs_tensor and _depth_tensor, written out: this is every step's path)
+        self._dev_tensor(obs, "obs", dtype, self.N * per_frame)
         self._dev_tensor(depth, "depth", torch.float32, self.N * self.H * self.W)
         self._dev_tensor(reward, "reward", torch.float32, self.N)
         self._dev_tensor(term, "terminated", torch.uint8, self.N)
@@ -622,7 +661,6 @@ class Engine:
         rows an env did not execute repeating its last one; rows T .. R - 1 are not written.  Everything else is step_plan()'s.
         Checked like a state view's tensors (dtype, device, contiguity), never converted: an unknown name, a wrong tensor, no field
         at all, ent_pos with a slot outside 0 .. max_ents - 1 or on a TASK_COLLECT engine raise before the library is called."""
-        import torch
         if not trace or all(t is None for t in trace.values()):
             raise EngineError("step_plan_trace: no trace field named")
         view = MwPlanTrace()
@@ -633,11 +671,7 @@ class Engine:
             if t is None:
                 continue
             dt, shp = TRACE_FIELDS[name]
-            dtype = torch.float64 if dt is np.float64 else torch.int32
-            if not torch.is_tensor(t) or t.dim() != 2 + len(shp) or tuple(t.shape[1:]) != (self.N,) + shp or t.shape[0] < T:
-                raise EngineError(f"trace {name}: need a {dtype} tensor of shape [>= {T}, {self.N}{''.join(', %d' % d for d in shp)}] on {self.device}, got "
-                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-            setattr(view, name, self._dev_tensor(t, "trace " + name, dtype, t.numel()).data_ptr())
+            setattr(view, name, self._shaped_tensor(t, "trace " + name, torch_dtype(dt), (T, self.N) + shp, more_rows=True).data_ptr())
         if view.ent_pos:
             if isinstance(ent_slot, bool) or not isinstance(ent_slot, (int, np.integer)) or not 0 <= ent_slot < self.cfg.max_ents:
                 raise EngineError(f"ent_slot: need an integer in 0 .. {self.cfg.max_ents - 1}, got {ent_slot!r}")
@@ -658,25 +692,18 @@ class Engine:
             plans = plans.to(device=self.device, dtype=torch.int32).contiguous()
         self._step_tensors(plans[0], obs, depth, reward, term, trunc)       # (the output checks; row 0 stands in for step()'s actions)
         self._dev_tensor(nsteps, "nsteps", torch.int32, self.N)
-        if step_reward is not None and (step_reward.device != self.device or step_reward.dtype != torch.float32 or
-                                        not step_reward.is_contiguous() or step_reward.numel() < horizon * self.N):
-            raise EngineError(f"step_reward: need a contiguous float32 tensor of at least {horizon * self.N} elements on {self.device}")
-        if trace is not None:
-            self._check(self.lib.mw_step_plan_trace(self.h, _ptr(plans), horizon, _ptr(obs), _ptr(depth), _ptr(reward), _ptr(step_reward), _ptr(term),
-                                                    _ptr(trunc), _ptr(nsteps), C.byref(trace), _stream_ptr(self.device)), "mw_step_plan_trace")
-            return
-        self._check(self.lib.mw_step_plan(self.h, _ptr(plans), horizon, _ptr(obs), _ptr(depth), _ptr(reward), _ptr(step_reward), _ptr(term),
-                                          _ptr(trunc), _ptr(nsteps), _stream_ptr(self.device)), "mw_step_plan")
+        self._dev_tensor(step_reward, "step_reward", torch.float32, horizon * self.N, at_least=True)
+        fn, tail = ("mw_step_plan", ()) if trace is None else ("mw_step_plan_trace", (C.byref(trace),))
+        self._check(getattr(self.lib, fn)(self.h, _ptr(plans), horizon, _ptr(obs), _ptr(depth), _ptr(reward), _ptr(step_reward), _ptr(term),
+                                          _ptr(trunc), _ptr(nsteps), *tail, _stream_ptr(self.device)), fn)
 
     def set_final_obs(self, obs=None, depth=None):
         """Same-step auto-reset: every later step writes the terminal frame (and depth) of each env whose episode ended in it into
         that env's row of `obs` (`depth`); the other rows are left alone.  Device tensors shaped like the step's obs / depth
         (obs_buffer()); obs=None turns it off.  The engine keeps references to them while they are in use."""
-        import torch
         if obs is not None:
-            obs_numel = self.N * self.H * self.W * (1 if self.obs_layout == OBS_GREY_F64 else 3)
-            self._dev_tensor(obs, "final obs", torch.float64 if self.obs_layout == OBS_GREY_F64 else torch.uint8, obs_numel)
-            self._dev_tensor(depth, "final depth", torch.float32, self.N * self.H * self.W)
+            self._obs_tensor(obs, "final obs")
+            self._depth_tensor(depth, "final depth")
         self._check(self.lib.mw_set_final_obs(self.h, _ptr(obs), _ptr(depth if obs is not None else None)), "mw_set_final_obs")
         self._final_bufs = (obs, depth) if obs is not None else None
 
@@ -685,10 +712,8 @@ class Engine:
         frame into `ring`, a device tensor of [N, 2 * depth - 1, *frame] elements in the obs dtype, and — on an engine with final
         buffers — completes the rows of `final_stack` ([N, depth, *frame]) of the envs whose episode ended.  depth = 0 or
         ring=None turns it off.  The engine keeps references to the tensors while they are in use."""
-        import torch
         if depth and ring is not None:
-            per_frame = self.H * self.W * (1 if self.obs_layout == OBS_GREY_F64 else 3)
-            dtype = torch.float64 if self.obs_layout == OBS_GREY_F64 else torch.uint8
+            dtype, per_frame = self.obs_spec
             self._dev_tensor(ring, "stack ring", dtype, self.N * (2 * depth - 1) * per_frame)
             self._dev_tensor(final_stack, "final stack", dtype, self.N * depth * per_frame)
         else:
@@ -727,13 +752,6 @@ class Engine:
             raise EngineError(f"{name}: need a 1-D index tensor" + (f" of {count} elements" if count is not None else "") + f", got shape {tuple(t.shape)}")
         return t
 
-    def _snapshot_buffer(self, buf, capacity):
-        import torch
-        need = self.snapshot_bytes(capacity)
-        if buf.device != self.device or buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.numel() < need:
-            raise EngineError(f"snapshot buffer: need a contiguous uint8 tensor of at least {need} bytes on {self.device} for {capacity} records, got "
-                              f"{buf.dtype} {tuple(buf.shape)} on {buf.device}")
-
     def _items(self, envs, records, count, default):
         """The index tensors and the item count of a list call: envs / records None or made int32 device tensors (_index_tensor), count
         the length of whichever is given, else `default`; every array given must be that long."""
@@ -745,13 +763,32 @@ class Engine:
                 raise EngineError(f"{name}: {t.numel()} indices for {count} items")
         return envs, records, int(count)
 
+    def _where_items(self, mask, records, instead):
+        """The mask and the record indices of a _where call: uint8[N] as given, int32[N] made a device tensor."""
+        mask, records = self._mask_tensor(mask), self._index_tensor(records, "records", self.N)
+        if records is None:
+            raise EngineError(f"records: None (record i for env i: {instead})")
+        return mask, records
+
+    def _records_call(self, fn, buf, capacity, frames, *args):
+        """What the snapshot calls share behind their indices: the record buffer's check — with `frames` = (obs, depth, flags), a
+        frame record call, the frame rows' too —, then the library call fn(handle, *args, stream)."""
+        import torch
+        if frames is None:
+            self._dev_tensor(buf, f"snapshot buffer for {capacity} records", torch.uint8, self.snapshot_bytes(capacity), at_least=True)
+        else:
+            obs, depth, flags = frames
+            self._dev_tensor(buf, f"frame record buffer for {capacity} records (flags {flags})", torch.uint8,
+                             self.snapshot_frames_bytes(capacity, flags), at_least=True)
+            self._frame_rows(obs, depth, flags)
+        self._check(getattr(self.lib, fn)(self.h, *args, _stream_ptr(self.device)), fn)
+
     def snapshot_save(self, buf, capacity: int, envs=None, count: int | None = None):
         """Record k of `buf` := the complete state of env envs[k] (envs=None: env k, for k < count, default all envs); `buf` is a
         uint8 device tensor of snapshot_bytes(capacity) bytes.  Asynchronous on the current stream, one kernel; returns the number
         of records written (mw_snapshot_save)."""
         envs, _, count = self._items(envs, None, count, self.N)
-        self._snapshot_buffer(buf, capacity)
-        self._check(self.lib.mw_snapshot_save(self.h, _ptr(envs), count, _ptr(buf), int(capacity), _stream_ptr(self.device)), "mw_snapshot_save")
+        self._records_call("mw_snapshot_save", buf, capacity, None, _ptr(envs), count, _ptr(buf), int(capacity))
         return count
 
     def snapshot_load(self, buf, n_recs: int, capacity: int, envs=None, records=None, count: int | None = None):
@@ -759,9 +796,7 @@ class Engine:
         k).  The target envs must be distinct; records may repeat — a fork.  The observation buffers are stale afterwards: render(),
         then stack_refresh() with a frame stack (mw_snapshot_load).  Asynchronous on the current stream, one kernel."""
         envs, records, count = self._items(envs, records, count, min(int(n_recs), self.N))
-        self._snapshot_buffer(buf, capacity)
-        self._check(self.lib.mw_snapshot_load(self.h, _ptr(envs), _ptr(records), count, _ptr(buf), int(n_recs), int(capacity),
-                                              _stream_ptr(self.device)), "mw_snapshot_load")
+        self._records_call("mw_snapshot_load", buf, capacity, None, _ptr(envs), _ptr(records), count, _ptr(buf), int(n_recs), int(capacity))
 
     def snapshot_frames_bytes(self, capacity: int, flags: int = 0) -> int:
         """Bytes of a device buffer that holds `capacity` frame records under `flags` (SNAPF_DEPTH | SNAPF_STACK;
@@ -771,24 +806,15 @@ class Engine:
             raise EngineError(f"mw_snapshot_frames_bytes failed ({n}): capacity {capacity!r}, flags {flags!r}")
         return n
 
-    def _frames_buffer(self, buf, capacity, flags):
-        import torch
-        need = self.snapshot_frames_bytes(capacity, flags)
-        if buf.device != self.device or buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.numel() < need:
-            raise EngineError(f"frame record buffer: need a contiguous uint8 tensor of at least {need} bytes on {self.device} for {capacity} records "
-                              f"(flags {flags}), got {buf.dtype} {tuple(buf.shape)} on {buf.device}")
-
     def _frame_rows(self, obs, depth, flags):
         """The kernels index `obs` / `depth` by env through raw pointers: they must be the step's buffers (obs_buffer()'s dtype and
         size in the current layout, float32 [N, H, W] depth), and SNAPF_DEPTH needs a depth tensor."""
-        import torch
-        grey = self.obs_layout == OBS_GREY_F64
         if obs is None:
             raise EngineError("frame records: obs is None")
-        self._dev_tensor(obs, "obs", torch.float64 if grey else torch.uint8, self.N * self.H * self.W * (1 if grey else 3))
+        self._obs_tensor(obs)
         if (flags & SNAPF_DEPTH) and depth is None:
             raise EngineError("frame records: SNAPF_DEPTH without a depth tensor")
-        self._dev_tensor(depth, "depth", torch.float32, self.N * self.H * self.W)
+        self._depth_tensor(depth)
 
     def snapshot_save_frames(self, buf, capacity: int, obs, depth=None, flags: int = 0, envs=None, count: int | None = None):
         """Frame record k of `buf` := env envs[k]'s row of `obs`, with SNAPF_DEPTH its row of `depth`, with SNAPF_STACK its stacked
@@ -796,10 +822,8 @@ class Engine:
         snapshot_frames_bytes(capacity, flags) bytes that overlaps none of them.  Asynchronous on the current stream, one kernel;
         returns the number of records written (mw_snapshot_save_frames)."""
         envs, _, count = self._items(envs, None, count, self.N)
-        self._frames_buffer(buf, capacity, flags)
-        self._frame_rows(obs, depth, flags)
-        self._check(self.lib.mw_snapshot_save_frames(self.h, _ptr(envs), count, _ptr(obs), _ptr(depth), _ptr(buf), int(capacity),
-                                                     int(flags), _stream_ptr(self.device)), "mw_snapshot_save_frames")
+        self._records_call("mw_snapshot_save_frames", buf, capacity, (obs, depth, flags),
+                           _ptr(envs), count, _ptr(obs), _ptr(depth), _ptr(buf), int(capacity), int(flags))
         return count
 
     def snapshot_load_frames(self, buf, n_recs: int, capacity: int, obs, depth=None, flags: int = 0, envs=None, records=None,
@@ -809,11 +833,8 @@ class Engine:
         stack_refresh(): the frames are the ones the records' sources returned.  Asynchronous on the current stream, one kernel
         (mw_snapshot_load_frames)."""
         envs, records, count = self._items(envs, records, count, min(int(n_recs), self.N))
-        self._frames_buffer(buf, capacity, flags)
-        self._frame_rows(obs, depth, flags)
-        self._check(self.lib.mw_snapshot_load_frames(self.h, _ptr(envs), _ptr(records), count, _ptr(buf), int(n_recs),
-                                                     int(capacity), int(flags), _ptr(obs), _ptr(depth), _stream_ptr(self.device)),
-                    "mw_snapshot_load_frames")
+        self._records_call("mw_snapshot_load_frames", buf, capacity, (obs, depth, flags),
+                           _ptr(envs), _ptr(records), count, _ptr(buf), int(n_recs), int(capacity), int(flags), _ptr(obs), _ptr(depth))
 
     def snapshot_save_at(self, buf, capacity: int, envs=None, records=None, count: int | None = None):
         """Record records[k] of `buf` := the complete state of env envs[k] (envs=None: env k; records=None: record k).  The records
@@ -821,26 +842,22 @@ class Engine:
         is filled in chunks and a running loop adds to it.  Asynchronous on the current stream, one kernel; returns the number of
         records written (mw_snapshot_save_at)."""
         envs, records, count = self._items(envs, records, count, self.N)
-        self._snapshot_buffer(buf, capacity)
-        self._check(self.lib.mw_snapshot_save_at(self.h, _ptr(envs), _ptr(records), count, _ptr(buf), int(capacity), _stream_ptr(self.device)),
-                    "mw_snapshot_save_at")
+        self._records_call("mw_snapshot_save_at", buf, capacity, None, _ptr(envs), _ptr(records), count, _ptr(buf), int(capacity))
         return count
 
     def snapshot_save_frames_at(self, buf, capacity: int, obs, depth=None, flags: int = 0, envs=None, records=None, count: int | None = None):
         """Frame record records[k] of `buf` := env envs[k]'s frames, as snapshot_save_frames() takes them; the other records keep
         what they held (mw_snapshot_save_frames_at).  Asynchronous on the current stream, one kernel; returns the number written."""
         envs, records, count = self._items(envs, records, count, self.N)
-        self._frames_buffer(buf, capacity, flags)
-        self._frame_rows(obs, depth, flags)
-        self._check(self.lib.mw_snapshot_save_frames_at(self.h, _ptr(envs), _ptr(records), count, _ptr(obs), _ptr(depth), _ptr(buf),
-                                                        int(capacity), int(flags), _stream_ptr(self.device)), "mw_snapshot_save_frames_at")
+        self._records_call("mw_snapshot_save_frames_at", buf, capacity, (obs, depth, flags),
+                           _ptr(envs), _ptr(records), count, _ptr(obs), _ptr(depth), _ptr(buf), int(capacity), int(flags))
         return count
 
-    def _mask_tensor(self, mask):
+    def _mask_tensor(self, mask, optional=False):
         """The mask of a _where call: a contiguous uint8[N] tensor on the engine's device (nothing is converted: a conversion
-        would be a kernel and an allocation in every step of the loop this call exists for)."""
+        would be a kernel and an allocation in every step of the loop this call exists for); None only where it means every env."""
         import torch
-        if mask is None:
+        if mask is None and not optional:
             raise EngineError("mask: None")
         return self._dev_tensor(mask, "mask", torch.uint8, self.N)
 
@@ -849,25 +866,16 @@ class Engine:
         and records int32[N] are device tensors; nothing is read on the host, so the call sits behind a step with no
         synchronisation.  records[i] is not read under a zero mask byte; N may exceed `capacity` (records repeat).  The other
         envs keep their cached frames (mw_snapshot_load_where).  Asynchronous on the current stream, one kernel."""
-        mask, records = self._mask_tensor(mask), self._index_tensor(records, "records", self.N)
-        if records is None:
-            raise EngineError("records: None (record i for env i: snapshot_load)")
-        self._snapshot_buffer(buf, capacity)
-        self._check(self.lib.mw_snapshot_load_where(self.h, _ptr(mask), _ptr(records), _ptr(buf), int(n_recs), int(capacity),
-                                                    _stream_ptr(self.device)), "mw_snapshot_load_where")
+        mask, records = self._where_items(mask, records, "snapshot_load")
+        self._records_call("mw_snapshot_load_where", buf, capacity, None, _ptr(mask), _ptr(records), _ptr(buf), int(n_recs), int(capacity))
 
     def snapshot_load_frames_where(self, buf, n_recs: int, capacity: int, mask, records, obs, depth=None, flags: int = 0):
         """For every env i with mask[i] != 0: env i's rows of `obs` / `depth` (and with SNAPF_STACK its frame stack and stack flag) :=
         frame record records[i] of `buf`; no byte of any other env's rows is touched.  Called behind snapshot_load_where() with the
         same mask and records (mw_snapshot_load_frames_where).  Asynchronous on the current stream, one kernel."""
-        mask, records = self._mask_tensor(mask), self._index_tensor(records, "records", self.N)
-        if records is None:
-            raise EngineError("records: None (record i for env i: snapshot_load_frames)")
-        self._frames_buffer(buf, capacity, flags)
-        self._frame_rows(obs, depth, flags)
-        self._check(self.lib.mw_snapshot_load_frames_where(self.h, _ptr(mask), _ptr(records), _ptr(buf), int(n_recs), int(capacity),
-                                                           int(flags), _ptr(obs), _ptr(depth), _stream_ptr(self.device)),
-                    "mw_snapshot_load_frames_where")
+        mask, records = self._where_items(mask, records, "snapshot_load_frames")
+        self._records_call("mw_snapshot_load_frames_where", buf, capacity, (obs, depth, flags),
+                           _ptr(mask), _ptr(records), _ptr(buf), int(n_recs), int(capacity), int(flags), _ptr(obs), _ptr(depth))
 
     def render(self, obs, depth=None):
         self._check(self.lib.mw_render(self.h, _ptr(obs), _ptr(depth), _stream_ptr(self.device)), "mw_render")
@@ -889,18 +897,13 @@ class Engine:
     def set_obs_layout(self, layout: int):
         """Layout of the obs buffer the raster kernel writes: OBS_HWC_U8 | OBS_CWH_U8 | OBS_GREY_F64."""
         self._check(self.lib.mw_set_obs_layout(self.h, int(layout)), "mw_set_obs_layout")
-        self.obs_layout = int(layout)
+        self._set_layout(layout)
 
     def obs_buffer(self, count: int | None = None):
         """A device tensor of the right shape / dtype for the current obs layout."""
         import torch
-        n = self.N if count is None else count
-        layout = self.obs_layout
-        if layout == OBS_CWH_U8:
-            return torch.zeros((n, 3, self.W, self.H), dtype=torch.uint8, device=self.device)
-        if layout == OBS_GREY_F64:
-            return torch.zeros((n, self.H, self.W, 1), dtype=torch.float64, device=self.device)
-        return torch.zeros((n, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
+        frame = {OBS_CWH_U8: (3, self.W, self.H), OBS_GREY_F64: (self.H, self.W, 1)}.get(self.obs_layout, (self.H, self.W, 3))
+        return torch.zeros((self.N if count is None else count,) + frame, dtype=self.obs_spec[0], device=self.device)
 
     def visible_ents(self, first_env: int = 0, count: int | None = None):
         """get_visible_ents (miniworld.py:1238-1333): uint8[count, max_ents] on the device, 1 = visible."""
@@ -917,9 +920,8 @@ class Engine:
     def _info_tensors(self, health, pos):
         """what get_info and get_final_info ask of their outputs: int32[N] and float64[N, 3] device tensors, either may be None"""
         import torch
-        for t, dt, shape in ((health, torch.int32, (self.N,)), (pos, torch.float64, (self.N, 3))):
-            if t is not None:
-                assert t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()
+        self._dev_tensor(health, "health", torch.int32, self.N)
+        self._dev_tensor(pos, "position", torch.float64, self.N * 3)
 
     def get_info(self, health=None, ent_pos=None, ent_slot=0):
         """Fills the caller's device tensors: health int32[N] (CollectHealth's info["health"]) and / or ent_pos float64[N, 3]
@@ -938,7 +940,7 @@ class Engine:
         import torch
         if out is None:
             out = torch.zeros(self.N, dtype=torch.uint8, device=self.device)
-        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (self.N,) and out.is_contiguous()
+        self._dev_tensor(out, fn, torch.uint8, self.N)
         self._check(getattr(self.lib, fn)(self.h, _ptr(out), _stream_ptr(self.device)), fn)
         return out
 

@@ -21,6 +21,7 @@ OneRoom*, Maze* and PickupObjects through their own generators, the fixed-floorp
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import numpy as np
 
@@ -77,6 +78,145 @@ _KIND = {
     # collecthealth.py:79-98) are a K1 task rule too
     "MiniWorld-CollectHealth-v0": ("CollectHealth", eng.GEN_PROGRAM, eng.TASK_COLLECT, 8),
 }
+
+
+AUTORESET_MODES = {True: "same_step", False: "off", "same_step": "same_step", "next_step": "next_step", "levels": "levels", "seeds": "seeds"}
+_ENGINE_AUTORESET = {"same_step": eng.AUTORESET_SAME_STEP, "next_step": eng.AUTORESET_NEXT_STEP, "off": eng.AUTORESET_OFF,
+                     "levels": eng.AUTORESET_OFF,       # (levels: the loads behind the step restart the envs)
+                     "seeds": eng.AUTORESET_SAME_STEP}
+_INFO_KIND = {"CollectHealth": "health", "TMaze": "goal_pos", "TMazeLeft": "goal_pos", "TMazeRight": "goal_pos",
+              "YMaze": "goal_pos", "YMazeLeft": "goal_pos", "YMazeRight": "goal_pos"}
+
+
+# ------------------------------------------------------------------ the engine's configuration (no torch, no engine)
+
+class EnvConfig(NamedTuple):
+    """What build_config() decides: the mw_config the engine is created with, the resident texture names in id order, whether they
+    are domain-randomisation variants (beyond the template scene's own), and the mesh names to upload ahead of the scene's."""
+    cfg: eng.MwConfig
+    textures: list
+    tex_dr: bool
+    meshes: list
+
+
+def _ball_key_meshes():
+    """all 12 ball / key meshes: ids ball_<colour> = 0..5, key_<colour> = 6..11 in sorted colour order"""
+    from .entity import COLOR_NAMES
+    return [f"ball_{c}" for c in COLOR_NAMES] + [f"key_{c}" for c in COLOR_NAMES]
+
+
+def _entity_slots(template):
+    """the template's entities in slot order (the agent has none)"""
+    return [e for e in template.entities if e is not template.agent]
+
+
+def _fill(array, values):
+    for i, v in enumerate(values):
+        array[i] = float(v)
+
+
+def _room_args(cfg, template, sc):
+    """GEN_HALLWAY / GEN_ONEROOM: the room's extent, where the box and the agent may be, the agent's heading range, the box size"""
+    room = template.rooms[0]
+    if cfg.generator == eng.GEN_HALLWAY:
+        rest = [room.max_x - 2, room.max_x - 2, math.pi / 4, 0.8]
+    else:
+        rest = [room.min_x, room.max_x, math.pi, 0.8]
+    _fill(cfg.gen_args, [room.min_x, room.max_x, room.min_z, room.max_z] + rest)
+
+
+def _maze_tables(cfg, template, sc):
+    """GEN_MAZE: rows, columns, room and gap size, wall height, the three texture ids; TEX_DENSITY / size of each texture"""
+    r0 = template.rooms[0]
+    texs = [r0.floor_tex, r0.ceil_tex, r0.wall_tex]
+    names = [str(v) for v in sc["tex_names"]]
+    _fill(cfg.gen_tab, [template.num_rows, template.num_cols, template.room_size, template.gap_size, r0.wall_height]
+          + [names.index(x.variant) for x in texs])
+    _fill(cfg.gen_colors, [512 / d for x in texs for d in (x.width, x.height)])
+
+
+def _pickup_tables(cfg, template, sc):
+    """GEN_PICKUP: the room, per kind (Ball, Box, Key) radius, height, scale and first mesh id, and the six colours' RGB"""
+    from .entity import COLOR_NAMES, COLORS, Ball, Box, Key
+    room = template.rooms[0]
+    _fill(cfg.gen_args, [room.min_x, room.max_x, room.min_z, room.max_z])
+    protos = (Ball(COLOR_NAMES[0], size=0.9), Box(COLOR_NAMES[0], size=0.9), Key(COLOR_NAMES[0]))
+    _fill(cfg.gen_tab, [v for proto, first_mesh in zip(protos, (0, -1, 6))
+                        for v in (proto.radius, proto.height, getattr(proto, "scale", 1.0), first_mesh)])
+    _fill(cfg.gen_colors, [COLORS[c][j] for c in COLOR_NAMES for j in range(3)])
+
+
+_GENERATOR_TABLES = {eng.GEN_HALLWAY: _room_args, eng.GEN_ONEROOM: _room_args, eng.GEN_MAZE: _maze_tables, eng.GEN_PICKUP: _pickup_tables}
+
+
+def _room_variants(cfg, template, sc):
+    """Texture domain randomisation of a generated single-room world: the variant tables of its wall, floor and ceiling (ids,
+    TEX_DENSITY / size) and the room's shape go into cfg; returns the resident names, or None when no slot has a choice."""
+    from . import assets
+    room0 = template.rooms[0]
+    variants = [assets.texture_variants(t) for t in (room0.wall_tex_name, room0.floor_tex_name, room0.ceil_tex_name)]
+    if not any(len(v) > 1 for v in variants):
+        return None
+    names = [str(v) for v in sc["tex_names"]]
+    for k, vs in enumerate(variants):
+        cfg.tex_nvar[k] = len(vs)
+        for j, v in enumerate(vs):
+            if v not in names:
+                names.append(v)
+            cfg.tex_var_id[k][j] = names.index(v)
+            w, h = assets.texture_size(v)
+            cfg.tex_var_scale[k][j][0], cfg.tex_var_scale[k][j][1] = 512 / w, 512 / h
+    cfg.room_wall_height = float(room0.wall_height)
+    cfg.room_no_ceiling = int(bool(room0.no_ceiling))
+    return names
+
+
+def _program_variants(template, sc):
+    """Texture domain randomisation of a placement program, whose rooms may each name their own textures: every variant of every room
+    texture is resident (the program's tables name them); returns the names, or None when no texture has a choice."""
+    from . import assets
+    room_names = sorted({n for r in template.rooms for n in (r.wall_tex_name, r.floor_tex_name, r.ceil_tex_name)})
+    if not any(len(assets.texture_variants(n)) > 1 for n in room_names):
+        return None
+    names = [str(v) for v in sc["tex_names"]]
+    for n in room_names:
+        names += [v for v in assets.texture_variants(n) if v not in names]
+    return names
+
+
+def build_config(env_id, template, sc, num_envs, device_id=0, domain_rand=False, msaa=8, autoreset_mode="same_step", rng="auto"):
+    """The engine configuration of a family: `template` is its host world after reset(seed), `sc` that world's scene
+    (scene_from_env), the rest the constructor's choices.  Returns an EnvConfig; nothing is uploaded or created here."""
+    cls_name, generator, task, _ = _KIND[env_id]
+    P, S, E = len(sc["polys_nv"]), len(sc["wall_segs"]), max(1, len(sc["ents_kind"]))
+    if cls_name == "PickupObjects":
+        E = max(E, template.num_objs)
+    cfg = base_config(num_envs, template.obs_width, template.obs_height, E, P, S,
+                      max_visible=-(-(P + 6 * E) // 16) * 16,
+                      params_ranges=template.params.as_ranges(), device_id=device_id)
+    cfg.msaa = int(msaa)
+    cfg.task, cfg.goal_ent, cfg.num_objs = task, 0, len(sc["ents_kind"])
+    ents = _entity_slots(template)
+    if task in (eng.TASK_GOTO, eng.TASK_SIDEWALK) and hasattr(template, "box"):
+        cfg.goal_ent = ents.index(template.box)
+    if task == eng.TASK_PUTNEXT:
+        cfg.goal_ent, cfg.goal_ent2 = ents.index(template.red_box), ents.index(template.yellow_box)
+    cfg.max_episode_steps = int(min(float(template.max_episode_steps), 2 ** 30))
+    cfg.domain_rand = int(domain_rand)
+    cfg.generator = generator
+    cfg.autoreset = _ENGINE_AUTORESET[autoreset_mode]
+    cfg.agent_radius = float(template.agent.radius)
+    cfg.rng_mode = eng.RNG_PHILOX if rng == "philox" else eng.RNG_PCG64     # (every device generator draws numpy's PCG64 stream)
+    if generator in _GENERATOR_TABLES:
+        _GENERATOR_TABLES[generator](cfg, template, sc)
+    # texture domain randomisation needs one geometry set per env (texcoords depend on the variant)
+    variants = None
+    if domain_rand:
+        variants = _program_variants(template, sc) if generator == eng.GEN_PROGRAM else _room_variants(cfg, template, sc)
+    cfg.shared_geometry = int(generator != eng.GEN_MAZE and variants is None)
+    # PickupObjects, RoomObjects: any mix of kinds and colours can be generated on the device, so all twelve meshes are resident
+    meshes = _ball_key_meshes() if cls_name in ("PickupObjects", "RoomObjects") else []
+    return EnvConfig(cfg, variants or [str(v) for v in sc["tex_names"]], variants is not None, meshes)
 
 
 class EnvSnapshot:
@@ -173,6 +313,28 @@ class MiniWorldVecEnv:
         all-zero frames, then the frame).  One push per step() call, whatever `repeat` is; reset() rebuilds every stack."""
         import torch
         self.torch = torch
+        self._check_arguments(env_id, autoreset, final_obs, obs_layout, rng, domain_rand, frame_stack, stack_pad)
+        cls_name, self.generator, _, self.n_actions = _KIND[env_id]
+        if cls_name == "Sign":
+            domain_rand = False             # sign.py:92-98 fixes it
+        self.env_id, self.num_envs = env_id, num_envs
+        self.domain_rand, self.want_depth = domain_rand, want_depth
+        self._make_template(cls_name, seed, env_kwargs)
+        sc = scene_from_env(self.template)
+        setup = build_config(env_id, self.template, sc, num_envs, device_id, domain_rand, msaa, self.autoreset_mode, rng)
+        self.rng_mode = "pcg64" if setup.cfg.rng_mode == eng.RNG_PCG64 else "philox"
+        self.engine = eng.Engine(setup.cfg)
+        self._upload_assets(sc, setup)
+        if self.generator == eng.GEN_PROGRAM:
+            self._install_program(cls_name, sc)
+        self._make_buffers(final_obs)
+        self._set_frame_options(frame_reuse, frame_cache, final_obs)
+        self._init_modes(cls_name, seed)
+
+    host_autoreset = False      # every registered id is generated, ruled and auto-reset on the device
+
+    def _check_arguments(self, env_id, autoreset, final_obs, obs_layout, rng, domain_rand, frame_stack, stack_pad):
+        """The constructor's choices that need no world: refused before anything is made, kept as attributes otherwise."""
         if frame_stack is not None and (not isinstance(frame_stack, (int, np.integer)) or isinstance(frame_stack, bool)
                                         or not 2 <= frame_stack <= eng.MAX_STACK):
             raise ValueError(f"frame_stack must be an integer in 2 .. {eng.MAX_STACK} (or None), not {frame_stack!r}")
@@ -180,10 +342,10 @@ class MiniWorldVecEnv:
             raise ValueError(f"stack_pad must be 'reset' or 'zero', not {stack_pad!r}")
         self.frame_stack = None if frame_stack is None else int(frame_stack)
         self.stack_pad = stack_pad
-        modes = {True: "same_step", False: "off", "same_step": "same_step", "next_step": "next_step", "levels": "levels", "seeds": "seeds"}
-        if not isinstance(autoreset, (bool, str)) or autoreset not in modes:
+        if not isinstance(autoreset, (bool, str)) or autoreset not in AUTORESET_MODES:
             raise ValueError(f"autoreset must be True, False, 'same_step', 'next_step', 'levels' or 'seeds', not {autoreset!r}")
-        self.autoreset_mode = modes[autoreset]
+        self.autoreset_mode = AUTORESET_MODES[autoreset]
+        self.autoreset = self.autoreset_mode != "off"
         if final_obs and self.autoreset_mode not in ("same_step", "seeds"):
             why = {"next_step": "the terminal step returns the terminal frame itself",
                    "levels": "the terminal frame is in self.obs only between the engine's step and the level loads, and nothing copies the "
@@ -195,145 +357,55 @@ class MiniWorldVecEnv:
         self.obs_layout = obs_layout
         if env_id not in _KIND:
             raise KeyError(f"{env_id!r} is not available in the batched engine yet; have {sorted(_KIND)}")
-        cls_name, generator, task, n_actions = _KIND[env_id]
-        if cls_name == "Sign":
-            domain_rand = False             # sign.py:92-98 fixes it
-        self.env_id, self.num_envs, self.n_actions = env_id, num_envs, n_actions
-        self.domain_rand, self.want_depth = domain_rand, want_depth
-        self.generator = generator
+        if rng not in ("auto", "pcg64", "philox"):
+            raise ValueError(f"rng={rng!r} is not available for {env_id} (domain_rand={domain_rand})")
+
+    def _make_template(self, cls_name, seed, env_kwargs):
+        """template world: geometry, textures, capacities (host-side world generation only)"""
         cls = getattr(_envs, cls_name)
-        # template world: geometry, textures, capacities (host-side world generation only)
         # (Sign fixes domain_rand=False itself and does not take the argument, sign.py:92-98)
         self._dr_kw = (lambda dr: {}) if cls_name == "Sign" else (lambda dr: {"domain_rand": dr})
         self.template = cls(host_only=True, **self._dr_kw(False), **env_kwargs)
         self.template.reset(seed=seed)
         self._cls, self._env_kwargs = cls, env_kwargs
-        sc = scene_from_env(self.template)
-        # texture domain randomisation needs one geometry set per env (texcoords depend on the variant)
-        from . import assets as _assets
-        room0 = self.template.rooms[0]
-        tex_slots = [room0.wall_tex_name, room0.floor_tex_name, room0.ceil_tex_name]
-        variants = [_assets.texture_variants(t) for t in tex_slots]
-        tex_dr = bool(domain_rand) and generator in (eng.GEN_HALLWAY, eng.GEN_ONEROOM, eng.GEN_PICKUP, eng.GEN_MAZE) and any(len(v) > 1 for v in variants)
-        # placement programs: every room may name its own textures
-        prog_names = sorted({n for r in self.template.rooms for n in (r.wall_tex_name, r.floor_tex_name, r.ceil_tex_name)})
-        prog_tex_dr = bool(domain_rand) and generator == eng.GEN_PROGRAM and any(len(_assets.texture_variants(n)) > 1 for n in prog_names)
-        shared = generator != eng.GEN_MAZE and not tex_dr and not prog_tex_dr
-        P, S, E = len(sc["polys_nv"]), len(sc["wall_segs"]), max(1, len(sc["ents_kind"]))
-        pickup_meshes = None
-        if cls_name == "PickupObjects":
-            # any mix of kinds can be generated on the device: all 12 ball / key meshes are resident,
-            # ids ball_<colour> = 0..5, key_<colour> = 6..11 in sorted colour order
-            from .entity import COLOR_NAMES, COLORS, Ball, Box, Key
-            E = max(E, self.template.num_objs)
-            pickup_meshes = [f"ball_{c}" for c in COLOR_NAMES] + [f"key_{c}" for c in COLOR_NAMES]
-            protos = (Ball(COLOR_NAMES[0], size=0.9), Box(COLOR_NAMES[0], size=0.9), Key(COLOR_NAMES[0]))
-            first_mesh = (0, -1, 6)
-        cfg = base_config(num_envs, self.template.obs_width, self.template.obs_height, E, P, S,
-                          max_visible=-(-(P + 6 * E) // 16) * 16,
-                          params_ranges=self.template.params.as_ranges(), device_id=device_id)
-        cfg.shared_geometry = int(shared)
-        cfg.msaa = int(msaa)
-        cfg.task, cfg.goal_ent, cfg.num_objs = task, 0, len(sc["ents_kind"])
-        ents = [e for e in self.template.entities if e is not self.template.agent]
-        if task in (eng.TASK_GOTO, eng.TASK_SIDEWALK) and hasattr(self.template, "box"):
-            cfg.goal_ent = ents.index(self.template.box)
-        if task == eng.TASK_PUTNEXT:
-            cfg.goal_ent, cfg.goal_ent2 = ents.index(self.template.red_box), ents.index(self.template.yellow_box)
-        cfg.max_episode_steps = int(min(float(self.template.max_episode_steps), 2 ** 30))
-        cfg.domain_rand = int(domain_rand)
-        cfg.generator = generator
-        cfg.autoreset = {"same_step": eng.AUTORESET_SAME_STEP, "next_step": eng.AUTORESET_NEXT_STEP, "off": eng.AUTORESET_OFF,
-                         "levels": eng.AUTORESET_OFF,       # (levels: the loads behind the step restart the envs)
-                         "seeds": eng.AUTORESET_SAME_STEP}[self.autoreset_mode]
-        self.autoreset = self.autoreset_mode != "off"
-        cfg.agent_radius = float(self.template.agent.radius)
-        if generator in (eng.GEN_HALLWAY, eng.GEN_ONEROOM):
-            room = self.template.rooms[0]
-            args = [room.min_x, room.max_x, room.min_z, room.max_z]
-            if generator == eng.GEN_HALLWAY:
-                args += [room.max_x - 2, room.max_x - 2, math.pi / 4, 0.8]
-            else:
-                args += [room.min_x, room.max_x, math.pi, 0.8]
-            for i, v in enumerate(args):
-                cfg.gen_args[i] = float(v)
-        if generator == eng.GEN_MAZE:
-            t = self.template
-            r0 = t.rooms[0]
-            texs = [r0.floor_tex, r0.ceil_tex, r0.wall_tex]
-            names = [str(v) for v in sc["tex_names"]]
-            vals = [t.num_rows, t.num_cols, t.room_size, t.gap_size, r0.wall_height] + [names.index(x.variant) for x in texs]
-            for i, v in enumerate(vals):
-                cfg.gen_tab[i] = float(v)
-            for k, x in enumerate(texs):
-                cfg.gen_colors[2 * k] = 512 / x.width
-                cfg.gen_colors[2 * k + 1] = 512 / x.height
-        if generator == eng.GEN_PICKUP:
-            room = self.template.rooms[0]
-            for i, v in enumerate([room.min_x, room.max_x, room.min_z, room.max_z]):
-                cfg.gen_args[i] = float(v)
-            for k, (proto, fm) in enumerate(zip(protos, first_mesh)):
-                scale = float(getattr(proto, "scale", 1.0))
-                for j, v in enumerate([float(proto.radius), float(proto.height), scale, float(fm)]):
-                    cfg.gen_tab[k * 4 + j] = v
-            for ci, cname in enumerate(COLOR_NAMES):
-                for j in range(3):
-                    cfg.gen_colors[ci * 3 + j] = float(COLORS[cname][j])
-        self._tex_dr_variants = None
-        if prog_tex_dr:     # every variant of every room texture is resident; the program's tables name them
-            names = [str(v) for v in sc["tex_names"]]
-            for n in prog_names:
-                names += [v for v in _assets.texture_variants(n) if v not in names]
-            self._tex_dr_variants = names
-        if tex_dr:
-            order, nid = [], len(sc["tex_names"])
-            names = [str(v) for v in sc["tex_names"]]
-            for k, vs in enumerate(variants):
-                cfg.tex_nvar[k] = len(vs)
-                for j, v in enumerate(vs):
-                    if v not in names:
-                        names.append(v)
-                    cfg.tex_var_id[k][j] = names.index(v)
-                    w, h = _assets.texture_size(v)
-                    cfg.tex_var_scale[k][j][0], cfg.tex_var_scale[k][j][1] = 512 / w, 512 / h
-            self._tex_dr_variants = names
-            cfg.room_wall_height = float(room0.wall_height)
-            cfg.room_no_ceiling = int(bool(room0.no_ceiling))
-        pcg_ok = True       # every device generator draws numpy's PCG64 stream
-        if rng not in ("auto", "pcg64", "philox") or (rng == "pcg64" and not pcg_ok):
-            raise ValueError(f"rng={rng!r} is not available for {env_id} (domain_rand={domain_rand})")
-        cfg.rng_mode = eng.RNG_PCG64 if (pcg_ok and rng != "philox") else eng.RNG_PHILOX
-        self.rng_mode = "pcg64" if cfg.rng_mode == eng.RNG_PCG64 else "philox"
-        self.engine = eng.Engine(cfg)
-        self.host_autoreset = False         # every registered id is generated, ruled and auto-reset on the device
-        self._upload_assets(sc)
-        if cls_name == "RoomObjects":       # any colour of ball / key can be drawn: all twelve meshes are resident
-            from .entity import COLOR_NAMES
-            pickup_meshes = [f"ball_{c}" for c in COLOR_NAMES] + [f"key_{c}" for c in COLOR_NAMES]
-        if pickup_meshes:
-            from .objmesh import ObjMesh
-            for name in pickup_meshes:
-                self.mesh_ids[name] = len(self.mesh_ids)
-                m = ObjMesh.get(name)
-                self.engine.upload_mesh(self.mesh_ids[name], m.verts, m.norms, m.texcs, m.colors)
-        if generator == eng.GEN_PROGRAM:
-            from . import genprog
-            mesh_map = upload_scene_meshes(self.engine, sc, self.mesh_ids, self.tex_ids)
-            slot_of = lambda e: ents.index(e)                       # noqa: E731
-            room_of = lambda r: self.template.rooms.index(r)        # noqa: E731
-            if cls_name == "RoomObjects":
-                ops = genprog.room_objects_ops(0, 1, 2, self.mesh_ids["ball_" + COLOR_NAMES[0]], self.mesh_ids["key_" + COLOR_NAMES[0]])
-            else:
-                ops = genprog.family_ops(self.template, slot_of, room_of)
-            self.engine.set_gen_program(*genprog.compile_program(self.template, sc, self.tex_ids, mesh_map, ops))
-        dev = self.engine.device
+
+    def _upload_assets(self, sc, setup):
+        """the resident textures, the shared geometry set, the meshes the generator may draw"""
+        from . import assets
+        from .objmesh import ObjMesh
+        self._tex_dr_variants = setup.textures if setup.tex_dr else None
+        self.tex_ids, self.mesh_ids = {}, {}
+        for i, variant in enumerate(setup.textures):
+            self.tex_ids[variant] = i
+            self.engine.upload_texture(i, assets.texture_rgb_bottom_up(variant))
+        if setup.cfg.shared_geometry:
+            self.engine.set_geometry(-1, polys_array(sc), sc["wall_segs"])
+        for name in setup.meshes:
+            self.mesh_ids[name] = len(self.mesh_ids)
+            m = ObjMesh.get(name)
+            self.engine.upload_mesh(self.mesh_ids[name], m.verts, m.norms, m.texcs, m.colors)
+
+    def _install_program(self, cls_name, sc):
+        """GEN_PROGRAM: the scene's own meshes, then the family's _gen_world as a placement program (genprog.py)"""
+        from . import genprog
+        mesh_map = upload_scene_meshes(self.engine, sc, self.mesh_ids, self.tex_ids)
+        if cls_name == "RoomObjects":
+            names = _ball_key_meshes()
+            ops = genprog.room_objects_ops(0, 1, 2, self.mesh_ids[names[0]], self.mesh_ids[names[6]])
+        else:
+            ops = genprog.family_ops(self.template, _entity_slots(self.template).index, self.template.rooms.index)
+        self.engine.set_gen_program(*genprog.compile_program(self.template, sc, self.tex_ids, mesh_map, ops))
+
+    def _make_buffers(self, final_obs):
+        """what a step writes: obs in the chosen layout, depth, reward, flags; with final_obs the terminal frames' own buffers"""
+        torch, dev, n = self.torch, self.engine.device, self.num_envs
         H, W = self.template.obs_height, self.template.obs_width
-        self.engine.set_obs_layout({"hwc": eng.OBS_HWC_U8, "cwh": eng.OBS_CWH_U8, "grey": eng.OBS_GREY_F64}[obs_layout])
+        self.engine.set_obs_layout({"hwc": eng.OBS_HWC_U8, "cwh": eng.OBS_CWH_U8, "grey": eng.OBS_GREY_F64}[self.obs_layout])
         self.obs = self.engine.obs_buffer()
-        self.depth = torch.zeros((num_envs, H, W, 1), dtype=torch.float32, device=dev) if want_depth else None
-        self.reward = torch.zeros(num_envs, dtype=torch.float32, device=dev)
-        self.terminated = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
-        self.truncated = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
+        self.depth = torch.zeros((n, H, W, 1), dtype=torch.float32, device=dev) if self.want_depth else None
+        self.reward = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.terminated = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.truncated = torch.zeros(n, dtype=torch.uint8, device=dev)
         self.substeps = None            # int32[N], made by the first step(actions, repeat > 1)
         self.step_rewards = self._step_rewards = None       # float32[T, N] of the last rollout(), a view of the buffer behind it
         self.trace = None               # name -> [T, N, ...] of the last rollout(trace=...), views of the buffers behind them
@@ -341,8 +413,19 @@ class MiniWorldVecEnv:
         self.final_obs = self.final_depth = None
         if final_obs:
             self.final_obs = self.engine.obs_buffer()
-            self.final_depth = torch.zeros_like(self.depth) if want_depth else None
+            self.final_depth = torch.zeros_like(self.depth) if self.want_depth else None
             self.engine.set_final_obs(self.final_obs, self.final_depth)
+        self._info_buf = self._final_info_buf = None
+        self._state_bufs = {}           # state()'s tensors, one per field, made on first use
+        self._nav_bufs = {}             # nav_query()'s tensors, made on first use
+        self._lidar_bufs = {}           # lidar()'s offsets and result per (rays, fov), made on first use
+        self._fork_buf = None           # fork()'s scratch records, made on first use
+        self._fork_frames = None        # ... and its scratch frame records (fork(src, frames=True))
+        self._done = self._done_b = self._done_i = None     # the finished envs of a step as uint8 / bool / int64 ("levels", "seeds")
+
+    def _set_frame_options(self, frame_reuse, frame_cache, final_obs):
+        """frame reuse, the frame cache and the frame stack, in that order"""
+        torch, n = self.torch, self.num_envs
         self.frame_reuse = self.engine.set_frame_reuse(frame_reuse)
         if isinstance(frame_cache, bool) or not isinstance(frame_cache, (int, np.integer)) or not 0 <= frame_cache <= eng.MAX_FRAME_CACHE:
             raise ValueError(f"frame_cache must be an integer in 0 .. {eng.MAX_FRAME_CACHE}, not {frame_cache!r}")
@@ -350,50 +433,77 @@ class MiniWorldVecEnv:
         self._ring = self.final_stack = None
         if self.frame_stack:
             K, frame = self.frame_stack, tuple(self.obs.shape[1:])
-            self._ring = torch.zeros((num_envs, 2 * K - 1) + frame, dtype=self.obs.dtype, device=dev)
+            self._ring = torch.zeros((n, 2 * K - 1) + frame, dtype=self.obs.dtype, device=self.engine.device)
             if final_obs:
-                self.final_stack = torch.zeros((num_envs, K) + frame, dtype=self.obs.dtype, device=dev)
-            self.engine.set_frame_stack(K, {"reset": eng.STACK_PAD_RESET, "zero": eng.STACK_PAD_ZERO}[stack_pad], self._ring, self.final_stack)
+                self.final_stack = torch.zeros((n, K) + frame, dtype=self.obs.dtype, device=self.engine.device)
+            self.engine.set_frame_stack(K, {"reset": eng.STACK_PAD_RESET, "zero": eng.STACK_PAD_ZERO}[self.stack_pad], self._ring, self.final_stack)
+
+    def _init_modes(self, cls_name, seed):
+        """the seeds reset() hands out, the family's `info`, and what the "levels" and "seeds" auto-resets keep"""
+        torch, n = self.torch, self.num_envs
         self._host_envs = None
         self._next_seed = seed
         # what the env's step() reports in `info` beside the observation (collecthealth.py:100, tmaze.py:89, ymaze.py:125)
-        self._info_kind = {"CollectHealth": "health", "TMaze": "goal_pos", "TMazeLeft": "goal_pos", "TMazeRight": "goal_pos",
-                           "YMaze": "goal_pos", "YMazeLeft": "goal_pos", "YMazeRight": "goal_pos"}.get(cls_name)
-        self._info_slot = int(cfg.goal_ent)
-        self._info_buf = None
-        self._final_info_buf = None
-        self._state_bufs = {}           # state()'s tensors, one per field, made on first use
-        self._nav_bufs = None           # nav_query()'s tensors, made on first use
-        self._lidar_bufs = {}           # lidar()'s offsets and result per (rays, fov), made on first use
-        self._fork_buf = None           # fork()'s scratch records, made on first use
-        self._fork_frames = None        # ... and its scratch frame records (fork(src, frames=True))
+        self._info_kind = _INFO_KIND.get(cls_name)
+        self._info_slot = int(self.engine.cfg.goal_ent)
         # autoreset="levels": the bank (set_levels), the level each env plays and the one it gets when its episode ends
         self.levels = self.level = self.next_level = self.played_level = None
-        self._level_gen = self._done = self._done_b = self._ones = None
+        self._level_gen = self._ones = None
         # autoreset="seeds": the seed each env gets when its episode ends (the engine reads it: mw_set_reset_seeds) and the one it plays
-        self.next_seed = self.episode_seed = self._done_i = None
+        self.next_seed = self.episode_seed = None
         if self.autoreset_mode == "seeds":
-            self.next_seed = torch.arange(num_envs, 2 * num_envs, dtype=torch.int64, device=dev) + int(seed)
-            self.episode_seed = torch.arange(num_envs, dtype=torch.int64, device=dev) + int(seed)
-            self._done = torch.zeros(num_envs, dtype=torch.uint8, device=dev)
-            self._done_b = torch.zeros(num_envs, dtype=torch.bool, device=dev)
-            self._done_i = torch.zeros(num_envs, dtype=torch.int64, device=dev)
+            self.next_seed = torch.arange(n, 2 * n, dtype=torch.int64, device=self.engine.device) + int(seed)
+            self.episode_seed = torch.arange(n, dtype=torch.int64, device=self.engine.device) + int(seed)
+            self._done_scratch()
+            self._buffer("_done_i", (n,), torch.int64)
             self.engine.set_reset_seeds(self.next_seed)
 
-    # ------------------------------------------------------------------ assets / worlds
-    def _upload_assets(self, sc):
-        from . import assets
-        self.tex_ids, self.mesh_ids = {}, {}
-        for i, variant in enumerate(self._tex_dr_variants or [str(v) for v in sc["tex_names"]]):
-            self.tex_ids[variant] = i
-            self.engine.upload_texture(i, assets.texture_rgb_bottom_up(variant))
-        if self.engine.cfg.shared_geometry:
-            self.engine.set_geometry(-1, polys_array(sc), sc["wall_segs"])
+    # ------------------------------------------------------------------ buffers and argument checks
+    def _buffer(self, name, shape, dtype, store=None):
+        """This env's own zeroed device tensor `name` — an attribute, or an entry of the dict `store` —, made on first use and made
+        anew when `shape` asks for more rows than it has."""
+        have = getattr(self, name) if store is None else store.get(name)
+        if have is None or have.shape[0] < shape[0]:
+            have = self.torch.zeros(shape, dtype=dtype, device=self.engine.device)
+            if store is None:
+                setattr(self, name, have)
+            else:
+                store[name] = have
+        return have
 
+    def _done_scratch(self):
+        """the finished envs of a step as bytes and as booleans, behind a step of the "levels" and "seeds" modes"""
+        self._buffer("_done", (self.num_envs,), self.torch.uint8)
+        self._buffer("_done_b", (self.num_envs,), self.torch.bool)
+
+    def _is_tensor(self, t, shape, dtype=None):
+        """whether `t` is a contiguous tensor of `dtype` (default float64) and `shape` (None: any size there) on the engine's device"""
+        torch = self.torch
+        return (torch.is_tensor(t) and t.dtype == (dtype or torch.float64) and t.device == self.engine.device and t.is_contiguous()
+                and len(t.shape) == len(shape) and all(s is None or s == d for s, d in zip(shape, t.shape)))
+
+    def _copied_mask(self, mask):
+        """reset_where / set_state_where: a host sequence or a uint8 / bool tensor anywhere, copied over as uint8[N] on the device"""
+        torch = self.torch
+        if not torch.is_tensor(mask):
+            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0).astype(np.uint8))
+        if mask.dtype == torch.bool:
+            mask = mask.to(torch.uint8)
+        return mask.to(self.engine.device).contiguous()
+
+    def _device_mask(self, mask, what):
+        """nav_field / raycast: None, or a uint8 / bool [N] tensor already on the device; a bool is viewed as bytes (one byte per
+        element, 0 / 1: no conversion kernel)"""
+        torch = self.torch
+        if mask is None:
+            return None
+        if (not torch.is_tensor(mask) or tuple(mask.shape) != (self.num_envs,) or mask.dtype not in (torch.uint8, torch.bool)
+                or mask.device != self.engine.device):
+            raise ValueError(f"{what}: mask is a uint8 or bool tensor [{self.num_envs}] on {self.engine.device}")
+        return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+    # ------------------------------------------------------------------ worlds from the host
     def host_generate(self, indices, seeds):
-        return self._host_generate(indices, seeds)
-
-    def _host_generate(self, indices, seeds):
         """Host world generation (reference-compatible stream) for envs without a device generator."""
         if self._host_envs is None:
             self._host_envs = [None] * self.num_envs
@@ -463,11 +573,7 @@ class MiniWorldVecEnv:
             seeds = torch.from_numpy(np.array(vals, dtype=np.uint64).view(np.int64))
         elif seeds.device.type == "cpu" and seeds.dtype == torch.int64 and bool((seeds < 0).any()):
             raise ValueError("seeds: negative seed")
-        if not torch.is_tensor(mask):
-            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0).astype(np.uint8))
-        if mask.dtype == torch.bool:
-            mask = mask.to(torch.uint8)
-        mask, seeds = mask.to(dev).contiguous(), seeds.to(device=dev, dtype=torch.int64).contiguous()
+        mask, seeds = self._copied_mask(mask), seeds.to(device=dev, dtype=torch.int64).contiguous()
         self.engine.reset_where(mask, seeds)
         if self.episode_seed is not None:
             torch.where(mask != 0, seeds, self.episode_seed, out=self.episode_seed)
@@ -506,7 +612,7 @@ class MiniWorldVecEnv:
             self.engine.step(actions, self.obs, self.depth, self.reward, self.terminated, self.truncated)
         else:
             if self.substeps is None:
-                self.substeps = self.torch.zeros(self.num_envs, dtype=self.torch.int32, device=self.engine.device)
+                self._buffer("substeps", (self.num_envs,), self.torch.int32)
             self.engine.step_repeat(actions, repeat, self.obs, self.depth, self.reward, self.terminated, self.truncated, self.substeps)
         if levels:
             self._finished_to_levels(frames=True)
@@ -560,9 +666,9 @@ class MiniWorldVecEnv:
         if not 1 <= T <= eng.MAX_PLAN:
             raise ValueError(f"plans: T = {T} outside 1 .. {eng.MAX_PLAN}")
         if self.substeps is None:
-            self.substeps = torch.zeros(self.num_envs, dtype=torch.int32, device=self.engine.device)
-        if self._step_rewards is None or self._step_rewards.shape[0] < T:
-            self._step_rewards = torch.zeros((T, self.num_envs), dtype=torch.float32, device=self.engine.device)
+            self._buffer("substeps", (self.num_envs,), torch.int32)
+        if self._step_rewards is None or self._step_rewards.shape[0] < T:     # (_buffer's own rule, asked here first: every rollout's path)
+            self._buffer("_step_rewards", (T, self.num_envs), torch.float32)
         self.step_rewards = self._step_rewards[:T]
         obs, depth = (self.obs, self.depth) if render else (None, None)
         if self.next_seed is not None and not render:
@@ -573,12 +679,8 @@ class MiniWorldVecEnv:
             self.trace = None
             self.engine.step_plan(plans, obs, depth, self.reward, self._step_rewards, self.terminated, self.truncated, self.substeps)
         else:
-            for name in names:
-                dt, shp = eng.TRACE_FIELDS[name]
-                if name not in self._trace_bufs or self._trace_bufs[name].shape[0] < T:
-                    self._trace_bufs[name] = torch.zeros((T, self.num_envs) + shp, dtype=torch.float64 if dt is np.float64 else torch.int32,
-                                                         device=self.engine.device)
-            bufs = {name: self._trace_bufs[name] for name in names}
+            bufs = {name: self._buffer(name, (T, self.num_envs) + eng.TRACE_FIELDS[name][1], eng.torch_dtype(eng.TRACE_FIELDS[name][0]), self._trace_bufs)
+                    for name in names}
             self.trace = {name: b[:T] for name, b in bufs.items()}
             self.engine.step_plan_trace(plans, obs, depth, self.reward, self._step_rewards, self.terminated, self.truncated, self.substeps,
                                         trace=bufs, ent_slot=int(slot) if "ent_pos" in names else 0)
@@ -646,11 +748,8 @@ class MiniWorldVecEnv:
         dev, N = self.engine.device, self.num_envs
         self.levels = snap if snap.data.device == dev and snap.frames.device == dev else snap.to(dev)
         self._level_gen = generator
-        self.level = torch.zeros(N, dtype=torch.int32, device=dev)
-        self.next_level = torch.zeros(N, dtype=torch.int32, device=dev)
-        self.played_level = torch.zeros(N, dtype=torch.int32, device=dev)
-        self._done = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._done_b = torch.zeros(N, dtype=torch.bool, device=dev)
+        self.level, self.next_level, self.played_level = (torch.zeros(N, dtype=torch.int32, device=dev) for _ in range(3))
+        self._done_scratch()
         self._ones = torch.ones(N, dtype=torch.uint8, device=dev)
         self._draw_next_levels()
 
@@ -679,22 +778,16 @@ class MiniWorldVecEnv:
         if self._info_kind is not None:
             # the finished episodes' own values, before the loads replace the states they are read from (final_infos)
             now = self.infos()[self._info_kind]
-            self._level_final_info()
+            kept = self._info_buffer("_final_info_buf")
             done = self._done.bool()
-            torch.where(done if now.dim() == 1 else done[:, None], now, self._final_info_buf, out=self._final_info_buf)
+            torch.where(done if now.dim() == 1 else done[:, None], now, kept, out=kept)
         self._start_levels(self._done, frames)
 
-    def _new_info_buffer(self):
-        """what get_info / get_final_info fill for this env's `info` key: health int32[N], goal_pos float64[N, 3]"""
-        torch, dev = self.torch, self.engine.device
+    def _info_buffer(self, name):
+        """what get_info / get_final_info fill for this env's `info` key, made on first use: health int32[N], goal_pos float64[N, 3]"""
         if self._info_kind == "health":
-            return torch.zeros(self.num_envs, dtype=torch.int32, device=dev)
-        return torch.zeros((self.num_envs, 3), dtype=torch.float64, device=dev)
-
-    def _level_final_info(self):
-        if self._final_info_buf is None:
-            self._final_info_buf = self._new_info_buffer()
-        return self._final_info_buf
+            return self._buffer(name, (self.num_envs,), self.torch.int32)
+        return self._buffer(name, (self.num_envs, 3), self.torch.float64)
 
     # ------------------------------------------------------------------ save / restore / fork
     def save_state(self, envs=None, capacity: int | None = None, frames: bool = False, into=None, records=None):
@@ -718,8 +811,7 @@ class MiniWorldVecEnv:
             return self._save_into(into, envs, records, capacity)
         if records is not None:
             raise ValueError("save_state: records needs into=<snapshot>")
-        envs = None if envs is None else torch.as_tensor(envs)
-        count = self.num_envs if envs is None else int(envs.numel())
+        envs, count = self._named_envs(envs)
         capacity = count if capacity is None else int(capacity)
         if capacity < count:
             raise ValueError(f"capacity {capacity} < the {count} records to save")
@@ -732,6 +824,11 @@ class MiniWorldVecEnv:
         self.engine.snapshot_save_frames(fdata, capacity, self.obs, self.depth, flags, envs)
         return EnvSnapshot(data, count, capacity, fdata, flags, self.frame_stack or 0)
 
+    def _named_envs(self, envs):
+        """(the envs a save names, as a tensor or None for all of them in order; how many they are)"""
+        envs = None if envs is None else self.torch.as_tensor(envs)
+        return envs, self.num_envs if envs is None else int(envs.numel())
+
     def _save_into(self, snap, envs, records, capacity):
         torch = self.torch
         if capacity is not None:
@@ -740,7 +837,7 @@ class MiniWorldVecEnv:
             raise ValueError("save_state: into=<snapshot> needs records=<the record indices>")
         if snap.frames is not None:
             self._check_frame_config(snap, "save_state(into=...)")
-        count = self.num_envs if envs is None else int(torch.as_tensor(envs).numel())
+        envs, count = self._named_envs(envs)
         rec_host = torch.as_tensor(records)
         if rec_host.dim() != 1 or int(rec_host.numel()) != count:
             raise ValueError(f"save_state: {tuple(rec_host.shape)} record indices for {count} envs")
@@ -775,17 +872,14 @@ class MiniWorldVecEnv:
             frames = snap.frames is not None
         if frames:
             self._check_frame_config(snap, "load_state")
-        data = snap.data
-        if data.device != self.engine.device:
-            data = data.to(self.engine.device)
-        if not frames:
-            self.engine.snapshot_load(data, snap.count, snap.capacity, envs, records)
-            return self._redraw()
-        fdata = snap.frames
-        if fdata.device != self.engine.device:
-            fdata = fdata.to(self.engine.device)
-        envs, records = self.engine._index_tensor(envs, "envs"), self.engine._index_tensor(records, "records")
+        dev = self.engine.device
+        data = snap.data if snap.data.device == dev else snap.data.to(dev)
+        if frames:      # (both loads take the same indices: made device tensors once)
+            fdata = snap.frames if snap.frames.device == dev else snap.frames.to(dev)
+            envs, records = self.engine._index_tensor(envs, "envs"), self.engine._index_tensor(records, "records")
         self.engine.snapshot_load(data, snap.count, snap.capacity, envs, records)
+        if not frames:
+            return self._redraw()
         self.engine.snapshot_load_frames(fdata, snap.count, snap.capacity, self.obs, self.depth, snap.frame_flags, envs, records)
         return self.obs
 
@@ -803,16 +897,15 @@ class MiniWorldVecEnv:
         if self._fork_buf is None:
             self._fork_buf = self.torch.empty(eng_.snapshot_bytes(n), dtype=self.torch.uint8, device=eng_.device)
         src = eng_._index_tensor(src, "src", n)
-        if not frames:
-            eng_.snapshot_save(self._fork_buf, n)
-            eng_.snapshot_load(self._fork_buf, n, n, None, src)
-            return self._redraw()
         flags = self._frame_flags()
-        if self._fork_frames is None:
+        if frames and self._fork_frames is None:
             self._fork_frames = self.torch.empty(eng_.snapshot_frames_bytes(n, flags), dtype=self.torch.uint8, device=eng_.device)
         eng_.snapshot_save(self._fork_buf, n)
-        eng_.snapshot_save_frames(self._fork_frames, n, self.obs, self.depth, flags)
+        if frames:
+            eng_.snapshot_save_frames(self._fork_frames, n, self.obs, self.depth, flags)
         eng_.snapshot_load(self._fork_buf, n, n, None, src)
+        if not frames:
+            return self._redraw()
         eng_.snapshot_load_frames(self._fork_frames, n, n, self.obs, self.depth, flags, None, src)
         return self.obs
 
@@ -830,17 +923,14 @@ class MiniWorldVecEnv:
         state() call that names the field.  The values are those of the state the device holds (as for infos(): with the same-step
         auto-reset an env that just finished reports its new episode; with the next-step auto-reset it reports the finished one
         until its next step installs the new episode)."""
-        torch, e = self.torch, self.engine
+        e = self.engine
         names = self.STATE_DEFAULT if fields is None else tuple(fields)
         out = {}
         for name in names:
             if name not in eng.STATE_FIELDS:
                 raise ValueError(f"state: {name!r} is no state field; have {sorted(eng.STATE_FIELDS)}")
-            if name not in self._state_bufs:
-                dt, shp = eng.STATE_FIELDS[name]
-                self._state_bufs[name] = torch.zeros((self.num_envs,) + shp(e.E), dtype=torch.float64 if dt is np.float64 else torch.int32,
-                                                     device=e.device)
-            out[name] = self._state_bufs[name]
+            dt, shp = eng.STATE_FIELDS[name]
+            out[name] = self._buffer(name, (self.num_envs,) + shp(e.E), eng.torch_dtype(dt), self._state_bufs)
         if not out:
             raise ValueError("state: no field named")
         return e.get_state_device(out)
@@ -865,11 +955,7 @@ class MiniWorldVecEnv:
             if not torch.is_tensor(val):
                 val = torch.from_numpy(np.ascontiguousarray(np.asarray(val, dtype=dt))).to(dev)
             arrays[name] = val
-        if not torch.is_tensor(mask):
-            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0).astype(np.uint8))
-        if mask.dtype == torch.bool:
-            mask = mask.to(torch.uint8)
-        mask = mask.to(dev).contiguous()
+        mask = self._copied_mask(mask)
         # (the tensors are checked before the first library call: a wrong one leaves the engine as it was)
         for name, t in arrays.items():
             self.engine._state_tensor(t, name, self.num_envs)
@@ -913,7 +999,7 @@ class MiniWorldVecEnv:
                 if target < 0:
                     raise ValueError("nav_field: this env has no goal entity: name a target slot or points")
             if torch.is_tensor(target):
-                if tuple(target.shape) != (self.num_envs, 3) or target.dtype != torch.float64 or target.device != e.device or not target.is_contiguous():
+                if not self._is_tensor(target, (self.num_envs, 3)):
                     raise ValueError(f"nav_field: point targets are a contiguous float64 tensor [{self.num_envs}, 3] on {e.device}")
                 if reach is None or not (reach > 0 and math.isfinite(reach)):
                     raise ValueError(f"nav_field: point targets need reach > 0, got {reach!r}")
@@ -934,11 +1020,7 @@ class MiniWorldVecEnv:
                                      target if isinstance(target, int) else 0)
             # (0xFFFF throughout; filled as int16: the 16-bit unsigned type has few kernels of its own)
             field = torch.full((self.num_envs, gz, gx), -1, dtype=torch.int16, device=e.device).view(torch.uint16)
-        if mask is not None:
-            if not torch.is_tensor(mask) or tuple(mask.shape) != (self.num_envs,) or mask.dtype not in (torch.uint8, torch.bool):
-                raise ValueError(f"nav_field: mask is a uint8 or bool tensor [{self.num_envs}]")
-            if mask.dtype == torch.bool:
-                mask = mask.view(torch.uint8)       # (one byte per element, 0 / 1: no conversion kernel)
+        mask = self._device_mask(mask, "nav_field")
         out = into if into is not None else NavField(field, params, target, obstacles)
         e.nav_build(params, field, mask, out.points)
         return out
@@ -955,14 +1037,11 @@ class MiniWorldVecEnv:
         torch, e = self.torch, self.engine
         if not isinstance(field, NavField):
             raise ValueError("nav_query: `field` must be a NavField (nav_field())")
-        if pos is not None and (not torch.is_tensor(pos) or tuple(pos.shape) != (self.num_envs, 3) or pos.dtype != torch.float64
-                                or pos.device != e.device or not pos.is_contiguous()):
+        if pos is not None and not self._is_tensor(pos, (self.num_envs, 3)):
             raise ValueError(f"nav_query: pos is a contiguous float64 tensor [{self.num_envs}, 3] on {e.device}")
-        if self._nav_bufs is None:
-            n = self.num_envs
-            self._nav_bufs = {"cost": torch.zeros(n, dtype=torch.int32, device=e.device), "next": torch.zeros(n, dtype=torch.int32, device=e.device),
-                              "waypoint": torch.zeros((n, 2), dtype=torch.float64, device=e.device)}
-        b = self._nav_bufs
+        n = self.num_envs
+        b = {name: self._buffer(name, shape, dtype, self._nav_bufs)
+             for name, shape, dtype in (("cost", (n,), torch.int32), ("next", (n,), torch.int32), ("waypoint", (n, 2), torch.float64))}
         e.nav_query(field.params, field.field, field.points, pos, b["cost"], b["next"], b["waypoint"])
         dist = torch.where(b["cost"] < 0, float("inf"), b["cost"].to(torch.float32) * (field.cell / 5.0)).to(torch.float32)
         return {"cost": b["cost"], "next": b["next"], "waypoint": b["waypoint"], "distance": dist}
@@ -991,10 +1070,7 @@ class MiniWorldVecEnv:
         n = self.num_envs
         if (direction is None) == (offsets is None):
             raise ValueError("raycast: give exactly one of direction (float64[N, R, 2]) and offsets (float64[R])")
-
-        def ok(t, shape):
-            return torch.is_tensor(t) and t.dtype == torch.float64 and t.device == e.device and t.is_contiguous() and (
-                len(t.shape) == len(shape) and all(s is None or s == d for s, d in zip(shape, t.shape)))
+        ok = self._is_tensor
         if offsets is not None:
             if not ok(offsets, (None,)):
                 raise ValueError(f"raycast: offsets is a contiguous float64 tensor [R] on {e.device}")
@@ -1013,26 +1089,19 @@ class MiniWorldVecEnv:
             raise ValueError(f"raycast: radius {radius!r} must be a finite number >= 0")
         if obstacles not in self.RAY_OBSTACLES:
             raise ValueError(f"raycast: obstacles {obstacles!r}; have {sorted(self.RAY_OBSTACLES)}")
-        if mask is not None:
-            if not torch.is_tensor(mask) or tuple(mask.shape) != (n,) or mask.dtype not in (torch.uint8, torch.bool) or mask.device != e.device:
-                raise ValueError(f"raycast: mask is a uint8 or bool tensor [{n}] on {e.device}")
-            if mask.dtype == torch.bool:
-                mask = mask.view(torch.uint8)       # (one byte per element, 0 / 1: no conversion kernel)
-        keys = ("t", "hit", "dir") if offsets is not None else ("t", "hit")
+        mask = self._device_mask(mask, "raycast")
+        # the result's tensors: name -> (dtype, shape, what an unmasked row holds)
+        want = {"t": (torch.float64, (n, rays), float(max_t)), "hit": (torch.int32, (n, rays), -1)}
+        if offsets is not None:
+            want["dir"] = (torch.float64, (n, rays, 2), 0.0)
+        keys = tuple(want)
         if into is not None:
             if not isinstance(into, dict) or set(into) != set(keys):
                 raise ValueError(f"raycast: `into` is a previous result with the keys {keys}")
-            want = {"t": (torch.float64, (n, rays)), "hit": (torch.int32, (n, rays)), "dir": (torch.float64, (n, rays, 2))}
-            for k in keys:
-                t = into[k]
-                if not torch.is_tensor(t) or t.dtype != want[k][0] or tuple(t.shape) != want[k][1] or t.device != e.device or not t.is_contiguous():
-                    raise ValueError(f"raycast: into[{k!r}] is a contiguous {want[k][0]} tensor {list(want[k][1])} on {e.device}")
-            out = into
-        else:
-            out = {"t": torch.full((n, rays), float(max_t), dtype=torch.float64, device=e.device),
-                   "hit": torch.full((n, rays), -1, dtype=torch.int32, device=e.device)}
-            if offsets is not None:
-                out["dir"] = torch.zeros((n, rays, 2), dtype=torch.float64, device=e.device)
+            for k, (dtype, shape, _) in want.items():
+                if not ok(into[k], shape, dtype):
+                    raise ValueError(f"raycast: into[{k!r}] is a contiguous {dtype} tensor {list(shape)} on {e.device}")
+        out = into or {k: torch.full(shape, fill, dtype=dtype, device=e.device) for k, (dtype, shape, fill) in want.items()}
         params = eng.MwRayParams(float(max_t), float(radius), rays, self.RAY_OBSTACLES[obstacles])
         e.ray_cast(params, out["t"], out["hit"], out.get("dir"), mask, origin, direction, offsets)
         return out
@@ -1076,31 +1145,27 @@ class MiniWorldVecEnv:
         (miniworld.py:730 returns an empty dict).  One small gather kernel on the engine's stream; the values are those of the
         state the device holds (with the same-step auto-reset an env that just finished reports its new episode — the finished
         episode's own values: final_infos —; with the next-step auto-reset it reports the finished one)."""
-        if self._info_kind is None:
-            return {}
-        if self._info_buf is None:
-            self._info_buf = self._new_info_buffer()
-        if self._info_kind == "health":
-            self.engine.get_info(health=self._info_buf)
-        else:
-            self.engine.get_info(ent_pos=self._info_buf, ent_slot=self._info_slot)
-        return {self._info_kind: self._info_buf}
+        return self._fill_info("_info_buf", self.engine.get_info, self._info_slot)
 
     def final_infos(self):
         """The `info` each env's last FINISHED episode ended with ({"health": …} / {"goal_pos": …} / {}), as the step kernel kept it
         before the same-step auto-reset installed the next world (mw_get_final_info); rows of envs that have not finished an episode yet
         are undefined (mask them with terminated | truncated of the step)."""
+        if self._info_kind is not None and self.autoreset_mode == "levels":
+            # (kept by step() itself before the level loads; the engine installs nothing here)
+            return {self._info_kind: self._info_buffer("_final_info_buf")}
+        return self._fill_info("_final_info_buf", self.engine.get_final_info)
+
+    def _fill_info(self, name, get, *slot):
+        """infos() and final_infos(): the family's buffer `name` filled by the engine's getter — get(health, position, *slot)"""
         if self._info_kind is None:
             return {}
-        if self.autoreset_mode == "levels":     # (kept by step() itself before the level loads; the engine installs nothing here)
-            return {self._info_kind: self._level_final_info()}
-        if self._final_info_buf is None:
-            self._final_info_buf = self._new_info_buffer()
+        buf = self._info_buffer(name)
         if self._info_kind == "health":
-            self.engine.get_final_info(health=self._final_info_buf)
+            get(buf)
         else:
-            self.engine.get_final_info(goal_pos=self._final_info_buf)
-        return {self._info_kind: self._final_info_buf}
+            get(None, buf, *slot)
+        return {self._info_kind: buf}
 
     def reset_pending(self):
         """uint8[N] device tensor: 1 = the env's last step ended its episode and its next step (autoreset="next_step") installs

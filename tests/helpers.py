@@ -86,6 +86,42 @@ def goals_of(meta):
     return int(meta.get("goal_ent", 0)), int(meta.get("goal_ent2", -1))
 
 
+# ------------------------------------------------------------------ the engine without a device (CPU tests)
+
+class RecordingLib:
+    """Stands in for libmwengine.so: every entry point succeeds and is written down — `calls`, (name, args) in order; `returns` maps an
+    entry point's name to what it returns instead of 0 (mw_snapshot_bytes -> 4096); `engines` are the Engines opened on it."""
+
+    def __init__(self, returns=None):
+        self.calls, self.engines, self.returns = [], [], dict(returns or {})
+
+    def __getattr__(self, name):
+        if not name.startswith("mw_"):
+            raise AttributeError(name)
+        rc = self.returns.get(name, 0)
+
+        def call(*args):
+            self.calls.append((name, args))
+            return rc
+        return call
+
+
+def stub_engine(monkeypatch, returns=None):
+    """engine.Engine without a device: the real class over a RecordingLib, tensors on the CPU.  Only Engine._open() is replaced (the
+    library, the device, the handle); every host attribute is the real __init__'s.  Returns the library."""
+    import torch
+    from miniworld_amd import engine
+    lib = RecordingLib(returns)
+
+    def open_(self):
+        lib.engines.append(self)
+        self.lib, self.device, self.h = lib, torch.device("cpu"), 1
+    monkeypatch.setattr(engine.Engine, "_open", open_)
+    monkeypatch.setattr(engine.Engine, "close", lambda self: None)
+    monkeypatch.setattr(engine, "_stream_ptr", lambda device=None: None)       # (no HIP stream without a device)
+    return lib
+
+
 # ------------------------------------------------------------------ engine glue (GPU tests)
 
 def make_engine_for_scene(s0, n_envs, task=1, max_episode_steps=None, domain_rand=False, max_visible=None,

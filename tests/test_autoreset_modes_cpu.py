@@ -17,8 +17,6 @@ def test_header_enum_matches_the_python_constants():
     assert values == {"MW_AUTORESET_OFF": engine.AUTORESET_OFF, "MW_AUTORESET_SAME_STEP": engine.AUTORESET_SAME_STEP,
                       "MW_AUTORESET_NEXT_STEP": engine.AUTORESET_NEXT_STEP}
     assert engine.AUTORESET_NEXT_STEP == 2 and engine.ABI_VERSION == 4
-    assert "mw_get_reset_pending" in engine.EXPORTS
-    assert re.search(r"int mw_get_reset_pending\(mw_engine \*e, uint8_t \*d_out, void \*stream\);", header)
 
 
 def test_create_rejects_an_unknown_autoreset_mode():

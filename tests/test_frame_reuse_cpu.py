@@ -5,16 +5,15 @@ import re
 
 import pytest
 
+from helpers import stub_engine
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_header_declares_the_entry_points():
-    from miniworld_amd import engine
     header = open(os.path.join(ROOT, "include", "mwengine.h")).read()
     assert re.search(r"int mw_set_frame_reuse\(mw_engine \*e, int32_t on\);", header)
     assert re.search(r"int mw_get_frame_clean\(mw_engine \*e, uint8_t \*d_out, void \*stream\);", header)
-    assert engine.ABI_VERSION == 4 and re.search(r"#define MW_ABI_VERSION 4\b", header)
-    assert "mw_set_frame_reuse" in engine.EXPORTS and "mw_get_frame_clean" in engine.EXPORTS
 
 
 def test_library_exports_the_entry_points():
@@ -24,40 +23,6 @@ def test_library_exports_the_entry_points():
     assert hasattr(lib, "mw_set_frame_reuse") and hasattr(lib, "mw_get_frame_clean")
     assert lib.mw_set_frame_reuse(None, 1) == -1 and lib.mw_get_frame_clean(None, None, None) == -1      # no engine: MW_E_INVALID
     assert lib.mw_abi_version() == 4
-
-
-class _RecordingLib:
-    """Stands in for libmwengine.so: every entry point succeeds and is written down."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("mw_"):
-            raise AttributeError(name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return 0
-        return call
-
-
-def _stub_engine(monkeypatch):
-    """engine.Engine without a device: the real methods over a recording library, tensors on the CPU."""
-    import torch
-    from miniworld_amd import engine
-    lib = _RecordingLib()
-
-    def init(self, cfg):
-        self.lib, self.cfg, self.h = lib, cfg, 1
-        self.N, self.E = cfg.num_envs, max(cfg.max_ents, 1)
-        self.W, self.H = cfg.obs_width, cfg.obs_height
-        self.obs_layout = engine.OBS_HWC_U8
-        self.device = torch.device("cpu")
-        self.frame_reuse = False
-    monkeypatch.setattr(engine.Engine, "__init__", init)
-    monkeypatch.setattr(engine.Engine, "close", lambda self: None)
-    return lib
 
 
 def _reuse_calls(lib):
@@ -78,7 +43,7 @@ def test_vec_env_switch_and_environment_reach_the_engine(kwargs, env, want, monk
         monkeypatch.delenv("MW_FRAME_REUSE", raising=False)
     else:
         monkeypatch.setenv("MW_FRAME_REUSE", env)
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
     vec = MiniWorldVecEnv("MiniWorld-Hallway-v0", 2, **kwargs)
     assert _reuse_calls(lib) == [want]
     assert vec.frame_reuse == bool(want) and vec.engine.frame_reuse == bool(want)
@@ -87,7 +52,7 @@ def test_vec_env_switch_and_environment_reach_the_engine(kwargs, env, want, monk
 def test_engine_reports_what_is_in_effect(monkeypatch):
     from miniworld_amd import engine
     from miniworld_amd.scene import base_config
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
     e = engine.Engine(base_config(4, 80, 60, 1, 6, 4, 16))
     monkeypatch.delenv("MW_FRAME_REUSE", raising=False)
     assert e.set_frame_reuse(True) is True and e.set_frame_reuse(False) is False

