@@ -890,11 +890,19 @@ int mw_get_frame_source(mw_engine *e, uint8_t *d_out, void *stream);
  * copies.  host_lengths: int32[N], the display-list length of every env in the last frame; an env's cost class is min(7, length / 4).
  * MW_E_INVALID before the first planned frame. */
 int mw_get_frame_plan(mw_engine *e, uint32_t *host_plan, int64_t words, int32_t *host_lengths, void *stream);
+/* Test and diagnosis call (synchronises `stream`): host_out uint8[N], 1 where the geometry kernel of the last planned frame built the
+ * env's display list, 0 where it left it alone.  In front of a frame plan the geometry kernel of a small scene builds only the envs
+ * the plan will have drawn, and those whose picked-up entity still has to leave the list, and deals them evenly over its wavefronts;
+ * every env whose source byte says drawn was built.  An engine created with MW_GEOM_DEAL=0 in the environment builds every env on
+ * every frame and never writes these bytes (zeros); they tell nothing of frames without a plan, which build every env. */
+int mw_get_geom_built(mw_engine *e, uint8_t *host_out, void *stream);
 
 /* Diagnostic (synchronises `stream`): how many triangles the last frame's display list held per env after clipping and culling —
  * what max_visible has to pay for (6 records per unit), and what decides which raster kernel an env's frame takes.
  * The stored length is clamped to the list's capacity (6 x max_visible): a value EQUAL to the capacity means "at least this
- * many" — raise max_visible and look again (mw_check reports the overflow itself as MW_E_CAPACITY). */
+ * many" — raise max_visible and look again (mw_check reports the overflow itself as MW_E_CAPACITY).
+ * An env that a planned frame did not build (mw_get_geom_built: 0) keeps the length — like the header and the records — of its last
+ * build: the length of the frame that is on display only where that frame was drawn. */
 int mw_get_list_lengths(mw_engine *e, int32_t first_env, int32_t count, int32_t *host_out, void *stream);
 
 /* Test hook: the sequence number of the next frame with mesh entities.  Its low 16 bits stamp the per-pixel chains of the

@@ -226,6 +226,7 @@ int init_engine(mw_engine *e, const mw_config *cfg)
     ALLOC(e->d_final_list, 1 + (size_t)N);
     ALLOC(e->d_plan[0], MW_PLAN_WORDS(N, frame_plan_ordered(N))); ALLOC(e->d_plan[1], MW_PLAN_WORDS(N, frame_plan_ordered(N)));      // (zeroed: the first plan kernel counts from nothing)
     ALLOC(e->stack.flags, 2 * (size_t)N);
+    ALLOC(e->d_geom_built, (size_t)N);
     ALLOC(e->d_mask, N); ALLOC(e->d_step_override, 3 * (size_t)N);
 #ifdef MW_PERF_HOOKS        // (tools/perf: make EXTRA=-DMW_PERF_HOOKS — kernel phase stamps dumped by mw_destroy; not in the product build)
     if (getenv("MW_K1_PROF")) ALLOC(a.k1_prof, MW_K1_PROF_SLOTS * (size_t)N);     // per-env cycle stamps of the geometry kernel's phases (zeroed)
@@ -270,6 +271,7 @@ int init_engine(mw_engine *e, const mw_config *cfg)
     if (const char *s = getenv("MW_DEBUG_FLAGS")) e->dbg_flags = atoi(s) & MW_DEBUG_BITS;
     if (const char *s = getenv("MW_K2Q")) e->use_k2q = atoi(s) != 0;
     if (const char *s = getenv("MW_GENERIC_RASTER")) e->generic_raster = atoi(s) != 0;
+    if (const char *s = getenv("MW_GEOM_DEAL")) e->geom_deal = atoi(s) != 0;
     e->k2q_ok = k2q_ok(cfg->msaa, a.W, a.H, mw_rasterq_lds_bytes(cfg->msaa == 4 ? 4 : 8, a.W, a.H, a.n_tiles, 1));
     {
         // snapshot records: the components this engine has, each with its array and its place in a record (mw_snapshot.h)
@@ -819,6 +821,15 @@ int mw_get_frame_plan(mw_engine *e, uint32_t *host_plan, int64_t words, int32_t 
     HIP_TRY(e, hipStreamSynchronize((hipStream_t)stream));
     HIP_TRY(e, hipMemcpy(host_plan, e->d_plan[e->plan_cur ^ 1], want * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIP_TRY(e, hipMemcpy(host_lengths, e->args.nvis, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    return MW_OK;
+}
+
+int mw_get_geom_built(mw_engine *e, uint8_t *host_out, void *stream)
+{
+    if (!e || !host_out) return fail(e, MW_E_INVALID, "mw_get_geom_built: null argument");
+    ON_DEVICE(e);
+    HIP_TRY(e, hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(e, hipMemcpy(host_out, e->d_geom_built, (size_t)e->cfg.num_envs, hipMemcpyDeviceToHost));
     return MW_OK;
 }
 

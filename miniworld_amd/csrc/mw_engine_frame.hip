@@ -188,6 +188,7 @@ struct Frame {
     const int32_t *list;        // CALL_LIST_PASS: the list forms draw the listed envs only
     uint8_t *obs; float *depth; hipStream_t st;
     FramePolicy pol;            // reuse; cache: the frame consults and fills the frame cache (both through the frame plan on the quad path: frame_plans)
+    bool plans;                 // the plan kernel runs behind the geometry kernel (frame_plans)
     RasterPath p;
     MeshFrame mf;               // p.mesh only
 };
@@ -225,8 +226,12 @@ void launch_step_and_geometry(mw_engine *e, const Frame &f, const Call &c, CallK
     if (kind == CALL_TERMINAL_STEP)
         hipLaunchKernelGGL(mw_final_list_kernel, dim3(1), dim3(1024), 0, f.st, N, (const uint8_t *)a.reset_pending, a.pending_remove, e->d_final_list);
     // the frame's vertex half: camera, lighting, transform, clipping, triangle setup (mw_geom.hip)
+    // ... of the envs the plan will have drawn only, dealt evenly over the wavefronts, where a plan kernel follows (mw_kernels.h: MW_GEOM_DEAL)
     const int L = geom_lanes_of(e);
-    launch(geom_kernel_of(L, e->cfg.msaa), f.list, dim3(env_blocks(N, L)), dim3(64), 0, f.st, a, f.view_flags, e->cfg.msaa, L, N);
+    const bool deals = geom_deals(f.plans, e->geom_deal, L);
+    const int flags = f.view_flags | (deals ? MW_GEOM_DEAL | (f.pol.reuse ? MW_GEOM_REUSE : 0) : 0);
+    launch(geom_kernel_of(L, e->cfg.msaa), f.list, dim3(env_blocks(N, L)), dim3(64), 0, f.st, a, flags, e->cfg.msaa, L, N,
+           deals && f.pol.cache ? (const uint64_t *)e->fc.meta.get() : nullptr, deals && f.pol.cache ? e->fc.slots : 0, e->d_geom_built);
     if (call_steps(kind) && e->cfg.task == MW_TASK_COLLECT)
         hipLaunchKernelGGL(MW_BY_STREAM(e, mw_collect_respawn), dim3((N + 63) / 64), dim3(64), 0, f.st, a);
 }
@@ -373,7 +378,8 @@ int launch_frame(mw_engine *e, const Call &c, CallKind kind, int view_flags = 0)
                                           e->fc.slots > 0 && e->fc.frames, path.path, e->reset_seeds != nullptr});
     frames_stale(e);
     const int N = e->cfg.num_envs;
-    Frame f{e->args, view_flags, kind == CALL_LIST_PASS ? e->d_final_list : nullptr, d_obs, d_depth, st, pol, path, {}};
+    Frame f{e->args, view_flags, kind == CALL_LIST_PASS ? e->d_final_list : nullptr, d_obs, d_depth, st, pol, false, path, {}};
+    f.plans = frame_plans(pol, path.path, f.list != nullptr, N);
     if (pol.cache) {
         if (d_depth && !e->fc.depth) {
             if (const int rc = dev_alloc(e, e->fc.depth, (size_t)N * e->fc.slots * f.a.W * f.a.H, false)) return rc;
@@ -415,7 +421,7 @@ int launch_frame(mw_engine *e, const Call &c, CallKind kind, int view_flags = 0)
     if (call_steps(kind) && side_refills(e) && (rc = launch_side_refill(e, st))) return rc;
     if (f.p.path == MW_PATH_GENERIC) rc = launch_generic(e, f.a, 0, N, e->cfg.msaa, dim3(32, N), d_obs, d_depth, e->obs_layout, f.list, st);
     else if (f.p.mesh) rc = launch_mesh_chain(e, f, st);
-    else if (f.p.path == MW_PATH_QUAD) launch_quad(e, f, 0, st, frame_plans(pol, f.p.path, f.list != nullptr, N) ? launch_plan(e, f, st) : nullptr);
+    else if (f.p.path == MW_PATH_QUAD) launch_quad(e, f, 0, st, f.plans ? launch_plan(e, f, st) : nullptr);
     else launch_tiles(e, f, 0, st);
     if (rc) return rc;
     e->last_raster_path = f.p.path;
@@ -634,7 +640,7 @@ int mw_render_view(mw_engine *e, int32_t env, int32_t view_flags, int32_t width,
     b.W = width; b.H = height;
     b.tiles_x = tiles_across(width); b.tiles_y = tiles_down(height); b.n_tiles = b.tiles_x * b.tiles_y;
     b.env_base = env;
-    hipLaunchKernelGGL(geom_kernel_of(64, msaa).plain, dim3(1), dim3(64), 0, st, b, view_flags, msaa, 64, 1);
+    hipLaunchKernelGGL(geom_kernel_of(64, msaa).plain, dim3(1), dim3(64), 0, st, b, view_flags, msaa, 64, 1, (const uint64_t *)nullptr, 0, (uint8_t *)nullptr);
     if (const int rc = e->have_meshes ? grow(e, e->mp.view_keys, e->mp.view_keys_bytes, (size_t)width * height * msaa * 4, 1) : MW_OK) return rc;
     if (const int rc = launch_generic(e, b, env, 1, msaa, dim3(128), d_out, d_depth, MW_OBS_HWC_U8, nullptr, st)) return rc;
     HIP_TRY(e, hipGetLastError());
@@ -664,7 +670,7 @@ int mw_visible_ents(mw_engine *e, int32_t first_env, int32_t count, uint8_t *d_v
     // the geometry kernel in proxy mode (view_flags bit 2): room polygons + one tagged proxy box per entity
     {
         const int L = geom_lanes_of(e);
-        hipLaunchKernelGGL(geom_kernel_of(L, e->cfg.msaa).plain, dim3(env_blocks(count, L)), dim3(64), 0, st, b, 4, e->cfg.msaa, L, count);
+        hipLaunchKernelGGL(geom_kernel_of(L, e->cfg.msaa).plain, dim3(env_blocks(count, L)), dim3(64), 0, st, b, 4, e->cfg.msaa, L, count, (const uint64_t *)nullptr, 0, (uint8_t *)nullptr);
     }
     if (!e->visible_attr_set) {
         HIP_TRY(e, hipFuncSetAttribute((const void *)mw_visible_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -17,6 +17,8 @@
 //
 // Lanes: a wavefront serves 64 / L envs, L lanes each (L: the power of two that holds an env's triangles — two per polygon
 // and box face, the agent marker — or 64, with several rounds).  One triangle per lane and round.
+// Small scenes: which envs — a wavefront takes its slots' envs from the mask of its group of 64 (mw_geom_deal.h): every env of the
+// launch, or, in front of a frame plan (MW_GEOM_DEAL), only the envs the plan will have drawn, dealt evenly over the group's wavefronts.
 // A round runs twice over its triangles: pass 1 counts what survives clipping and culling (the snapped-area test only), a
 // segmented scan turns the counts into list positions, pass 2 sets the survivors up and writes the records.  A triangle
 // that crosses a frustum plane goes through one of kClipSlots work lists in LDS, eight lanes to a list: an edge of the
@@ -27,6 +29,7 @@
 #include "mw_setup_common.h"
 #include "mw_records.h"
 #include "mw_kernels.h"
+#include "mw_geom_deal.h"
 
 namespace {
 
@@ -40,6 +43,64 @@ __device__ inline void wave_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// Dealing (mw_kernels.h: MW_GEOM_DEAL): the mask of a group of up to 64 envs, env0 .. env0 + n - 1, a lane per env — does this launch
+// build the env: will the plan kernel behind it have the env drawn, or is there a removal to apply at the kernel's end?  The plan
+// kernel's own decision on the same bytes, with the plan kernel's functions (mw_frame_plan.h: mw_fc_key_equal, mw_frame_verdict; the
+// victim slot does not matter here, so the rows' headers go unused).  Every slot's key is requested before any is compared: the loop
+// of mw_frame_verdict_of, the same decision with the loads in program order, waits a round trip to memory per slot — at one
+// wavefront per SIMD a microsecond each.  And the L wavefronts of a group all want the same 64 rows of the key table, 16 + 80 bytes
+// per slot each: read a lane per env, every 16-byte load of a wavefront touches 64 cache lines, 1 344 of them for four slots, and
+// the four wavefronts of a CU queue at its one L1.  Up to kDealStageSlots slots the group's rows — contiguous in memory — are
+// fetched 1 KB per load into the clipper's work lists (idle until the rounds), 168 lines, and a lane reads its row from there.
+// Scalars in, the ballot out: nothing of the keys lives beyond the call.
+constexpr int kDealStageSlots = 4;
+constexpr int kDealStageQuads = 64 * (MW_FC_META_WORDS(kDealStageSlots) / 2);
+__device__ inline uint64_t deal_mask(const uint8_t *__restrict__ frame_clean, const int32_t *__restrict__ pending_remove, const uint64_t *__restrict__ fc_key,
+                                     const uint64_t *__restrict__ meta, int slots, bool reuse, int env0, int n, int lane, uint4 *stage)
+{
+    const bool on = lane < n;
+    const int env = env0 + (on ? lane : 0);
+    const bool clean = frame_clean[env] != 0;
+    const int rs = pending_remove[env];
+    if (!meta) slots = 0;
+    uint32_t match = 0u;
+    if (slots > 0) {
+        const uint64_t *cur = static_cast<const uint64_t *>(__builtin_assume_aligned(fc_key + (size_t)env * MW_FC_KEY_WORDS, 16));
+        uint64_t key[MW_FC_KEY_WORDS];
+#pragma unroll
+        for (int w = 0; w < MW_FC_KEY_WORDS; ++w) key[w] = cur[w];
+        if (slots <= kDealStageSlots) {
+            const int rq = MW_FC_META_WORDS(slots) / 2;         // 16-byte quads per row
+            const uint4 *src = static_cast<const uint4 *>(__builtin_assume_aligned(meta + (size_t)env0 * MW_FC_META_WORDS(slots), 16));
+            const int nq = (n < 64 ? n : 64) * rq;
+            constexpr int kTurns = kDealStageQuads / 64;
+            // (a place past the rows repeats the last quad: every load and every store unconditional, all loads in flight at once)
+            uint4 q[kTurns];
+#pragma unroll
+            for (int t = 0; t < kTurns; ++t) q[t] = src[min(lane + 64 * t, nq - 1)];
+#pragma unroll
+            for (int t = 0; t < kTurns; ++t) stage[min(lane + 64 * t, nq - 1)] = q[t];
+            wave_lds_sync();
+            const uint4 *row = stage + (size_t)(on ? lane : 0) * rq;
+#pragma unroll
+            for (int j = 0; j < kDealStageSlots; ++j) {
+                const int jj = j < slots ? j : slots - 1;
+                match |= mw_fc_key_equal(reinterpret_cast<const uint64_t *>(row + 1 + (MW_FC_KEY_WORDS / 2) * jj), key) && j < slots ? 1u << j : 0u;
+            }
+            wave_lds_sync();        // (the lists are the clipper's again)
+        } else {
+            const uint64_t *row = static_cast<const uint64_t *>(__builtin_assume_aligned(meta + (size_t)env * MW_FC_META_WORDS(slots), 16));
+#pragma unroll
+            for (int j = 0; j < MW_FC_MAX_SLOTS; ++j) {
+                const int jj = j < slots ? j : slots - 1;
+                match |= mw_fc_key_equal(static_cast<const uint64_t *>(__builtin_assume_aligned(row + 2 + MW_FC_KEY_WORDS * jj, 16)), key) && j < slots ? 1u << j : 0u;
+            }
+        }
+    }
+    const uint32_t v = mw_frame_verdict(clean, reuse, match, 0u, slots);
+    return __ballot(on && ((v & 0xFFu) == (uint32_t)MW_SRC_DRAWN || rs >= 0));
 }
 
 // exclusive scan inside the env's L-lane group; total: the group's sum
@@ -216,12 +277,13 @@ __device__ inline bool occluded_rmq(const float *rmq, const mwgl::Vert v[4], flo
 // draws env list[1 + g] while g < list[0]; the grid stays N-sized (the host does not know the count) and a workgroup without a
 // listed env exits at once
 template <bool BIG, int SFIX, bool SUB = false>
-__device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L, int n_env, const int32_t *__restrict__ list = nullptr)
+__device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L, int n_env, const uint64_t *fc_meta, int fc_slots, uint8_t *built, const int32_t *__restrict__ list = nullptr)
 {
     const int S = SFIX ? SFIX : S_;
     // (244 dwords per slot: consecutive slots start in different LDS banks)
     struct ClipSlot { mwgl::ClipVert l[2][MWGL_MAX_CLIP_VERTS]; float pad[4]; };
-    __shared__ ClipSlot s_clip[kClipSlots];
+    __shared__ ClipSlot s_clip[kClipSlots];     // (small scenes: the dealing prologue stages 16-byte quads in it first, deal_mask)
+    static_assert(BIG || (alignof(ClipSlot) >= 16 && sizeof(ClipSlot) * kClipSlots >= kDealStageQuads * sizeof(uint4)), "the dealing prologue borrows the clipper's LDS");
     __shared__ int s_pos[BIG ? 1 : 8][66];       // (the big scenes' kernel serves one env per wavefront: its LDS must stay within a quarter of a CU's)
     __shared__ uint32_t s_meta[64], s_res[64];      // per work list: owner lane | clip planes << 8; vertices | list << 4 | front-facing fan triangles << 8
     __shared__ float s_occ_z[BIG ? MW_OCC_BINS + MW_OCC_BINS / 16 : 1];      // occlusion culling: farthest depth of the nearest wall per column bin, group maxima
@@ -243,14 +305,58 @@ __device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L,
     [[maybe_unused]] unsigned long long kp_clip = 0, kp_emit = 0, kp_e_shfl = 0, kp_e_setup = 0, kp_e_write = 0;
     const int lane = threadIdx.x;
     const int epw = 64 / L, sub = lane & (L - 1), grp = lane / L;
-    if (SUB) {
-        n_env = list[0];
-        if ((int)blockIdx.x * epw >= n_env) return;     // (uniform over the workgroup: one wavefront)
+    const bool deal = !BIG && !SUB && (view_flags & MW_GEOM_DEAL) != 0;
+    int rel, env;
+    bool live;
+    // Small scenes' plain kernels: what the camera prologue wants of the env — pose, light, camera — is requested before the env is
+    // known, lane k for env k of the group, beside the mask's loads, and handed to the slot's lanes by shuffles: one round trip to
+    // memory in front of the prologue, not the mask's and then the pose's.
+    constexpr bool kPoseAhead = !BIG && !SUB;
+    constexpr int kPoseWords = 17;       // x, y, z, dir; light rows 3 .. 11; cam rows 0 .. 3
+    [[maybe_unused]] double ahead[kPoseWords];
+    [[maybe_unused]] int ahead_lane = 0;
+    if constexpr (BIG) {
+        if (SUB) {
+            n_env = list[0];
+            if ((int)blockIdx.x * epw >= n_env) return;     // (uniform over the workgroup: one wavefront)
+        }
+        rel = (int)blockIdx.x * epw + grp;
+        live = rel < n_env;
+        // a padding group recomputes the last env and writes nothing
+        env = SUB ? list[1 + (live ? rel : n_env - 1)] : a.env_base + (live ? rel : n_env - 1);
+    } else {
+        // Small scenes: the wavefront takes its envs from the mask of its group of 64 (mw_geom_deal.h) — lane k answers for the
+        // group's env k: in range, and, dealing, built at all —, slot grp the env of rank i + grp * waves.  A slot without an env
+        // brings no work: no polygons, no entities, no marker, no store — it idles through its neighbours' rounds (no lane leaves:
+        // the clipper's lists are served by all 64).  A wavefront without any env leaves whole.
+        if (SUB) n_env = list[0];
+        const int lg = __ffs(L) - 1, g = (int)blockIdx.x >> lg, i = (int)blockIdx.x & (L - 1);
+        const int waves = min(L, (int)gridDim.x - (g << lg));
+        const int mine = 64 * g + lane;
+        if (kPoseAhead) {
+            const int ge = a.env_base + min(mine, n_env - 1);
+            ahead[0] = a.ax[ge]; ahead[1] = a.ay[ge]; ahead[2] = a.az[ge]; ahead[3] = a.adir[ge];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) ahead[4 + i] = a.light[(size_t)(3 + i) * a.N + ge];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ahead[13 + i] = a.cam[(size_t)i * a.N + ge];
+        }
+        uint64_t mask;
+        if (deal) mask = deal_mask(a.frame_clean, a.pending_remove, a.fc_key, fc_meta, fc_slots, (view_flags & MW_GEOM_REUSE) != 0, a.env_base + 64 * g, n_env - 64 * g, lane, reinterpret_cast<uint4 *>(&s_clip[0]));
+        else mask = __ballot(mine < n_env);
+        const bool want = ((mask >> lane) & 1ull) != 0ull;
+        if (deal && i == 0 && mine < n_env && !want) built[a.env_base + mine] = 0;      // (a built env's byte: its slot's first lane, at the end)
+        if ((int)__popcll((unsigned long long)mask) <= i) return;       // (uniform over the workgroup: one wavefront)
+        const int bit = mw_geom_deal(mask, waves, i, grp);
+        live = bit >= 0;
+        rel = 64 * g + (live ? bit : mw_geom_deal(mask, waves, i, 0));      // (an empty slot reads the env of slot 0 and does nothing with it)
+        env = SUB ? list[1 + rel] : a.env_base + rel;
+        ahead_lane = rel - 64 * g;
     }
-    const int rel = (int)blockIdx.x * epw + grp;
-    const bool live = rel < n_env;
-    // a padding group recomputes the last env and writes nothing
-    const int env = SUB ? list[1 + (live ? rel : n_env - 1)] : a.env_base + (live ? rel : n_env - 1);
+    if (kPoseAhead) {
+#pragma unroll
+        for (int i = 0; i < kPoseWords; ++i) ahead[i] = __shfl(ahead[i], ahead_lane);
+    }
     const int set = a.shared_geom ? 0 : env;
     const bool top = (view_flags & 1) != 0, proxy = (view_flags & 4) != 0, ms = S > 1;
     // big scenes: the per-world culling data (occ_cache: full-height walls, boxes of eight polygons) lives in HBM, one to two
@@ -282,24 +388,24 @@ __device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L,
     // the env's entity table, one slot per lane of its group (the walks below ask for slot after slot: a chain of dependent
     // global loads otherwise — with five slots and two passes, a quarter of PickupObjects' kernel)
     const bool ent_pre = a.E <= L;
-    const int my_ekind = (ent_pre && sub < a.E) ? a.ekind[(size_t)sub * a.N + env] : 0;
+    const int my_ekind = (ent_pre && sub < a.E && (BIG || live)) ? a.ekind[(size_t)sub * a.N + env] : 0;
     const int my_estatic = (ent_pre && sub < a.E) ? a.estatic[(size_t)sub * a.N + env] : 0;
     const int my_emesh = (ent_pre && sub < a.E && my_ekind == MW_ENT_MESH) ? a.emesh[(size_t)sub * a.N + env] : 0;
     const int my_mesh_ntris = (ent_pre && sub < a.E && my_ekind == MW_ENT_MESH) ? (int)a.mesh[my_emesh].ntris : 0;
-    auto ent_kind = [&](int s0) { return ent_pre ? __shfl(my_ekind, s0, L) : a.ekind[(size_t)s0 * a.N + env]; };
+    auto ent_kind = [&](int s0) { return ent_pre ? __shfl(my_ekind, s0, L) : (BIG || live) ? a.ekind[(size_t)s0 * a.N + env] : (int)MW_ENT_NONE; };
     auto ent_static = [&](int s0) { return ent_pre ? __shfl(my_estatic, s0, L) : a.estatic[(size_t)s0 * a.N + env]; };
     auto ent_mesh_ntris = [&](int s0) { return ent_pre ? __shfl(my_mesh_ntris, s0, L) : (int)a.mesh[a.emesh[(size_t)s0 * a.N + env]].ntris; };
     // ---- the frame's GL state (every lane of the group evaluates it: same instruction stream)
     mwgl::Frame f;
-    const double px = a.ax[env], py = a.ay[env], pz = a.az[env], dir = a.adir[env];
+    const double px = kPoseAhead ? ahead[0] : a.ax[env], py = kPoseAhead ? ahead[1] : a.ay[env], pz = kPoseAhead ? ahead[2] : a.az[env], dir = kPoseAhead ? ahead[3] : a.adir[env];
     float eye_x = 0.0f, eye_y = 0.0f, eye_z = 0.0f;
     {
         double lpos[3], lcol[3], lamb[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            lpos[i] = a.light[(size_t)(3 + i) * a.N + env];
-            lcol[i] = a.light[(size_t)(6 + i) * a.N + env];
-            lamb[i] = a.light[(size_t)(9 + i) * a.N + env];
+            lpos[i] = kPoseAhead ? ahead[4 + i] : a.light[(size_t)(3 + i) * a.N + env];
+            lcol[i] = kPoseAhead ? ahead[7 + i] : a.light[(size_t)(6 + i) * a.N + env];
+            lamb[i] = kPoseAhead ? ahead[10 + i] : a.light[(size_t)(9 + i) * a.N + env];
         }
         if (top) {
             double min_x = a.extent[(size_t)0 * a.N + env] - 1, max_x = a.extent[(size_t)1 * a.N + env] + 1;
@@ -316,8 +422,8 @@ __device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L,
             mwgl::frame_top(f, min_x, max_x, min_z, max_z);
         } else {
             // Agent.cam_pos / cam_dir via gen_rot_matrix (math.py:11-27, entity.py:476-503) as numpy evaluates them
-            const double cam_height = a.cam[(size_t)0 * a.N + env], fwd_disp = a.cam[(size_t)1 * a.N + env];
-            const double pitch_deg = a.cam[(size_t)2 * a.N + env], fov_y = a.cam[(size_t)3 * a.N + env];
+            const double cam_height = kPoseAhead ? ahead[13] : a.cam[(size_t)0 * a.N + env], fwd_disp = kPoseAhead ? ahead[14] : a.cam[(size_t)1 * a.N + env];
+            const double pitch_deg = kPoseAhead ? ahead[15] : a.cam[(size_t)2 * a.N + env], fov_y = kPoseAhead ? ahead[16] : a.cam[(size_t)3 * a.N + env];
             const mw::SinCos hd = mw::sincos_det(dir / 2.0);
             const double ya = hd.c, yc = -1.0 * hd.s;
             const double ry00 = ya * ya - yc * yc, ry02 = 2.0 * (ya * yc), ry11 = ya * ya + yc * yc;
@@ -342,7 +448,7 @@ __device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L,
     if (KGP_ON) tp[0] = __builtin_readcyclecounter();
 
     const mw_poly *polys = a.polys + (size_t)set * a.max_polys;
-    const int np = a.npolys[set];
+    const int np = (BIG || live) ? a.npolys[set] : 0;
     float *hdr = a.envhdr + (size_t)env * MW_ENVHDR;
 
     // ---- the env's draw list behind the polygons: boxes in drawing order (static entities first, inside display list 1,
@@ -797,7 +903,7 @@ __device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L,
     if (KGP_ON) tp[1] = tprev = __builtin_readcyclecounter();
     int count = 0;          // the env's list length so far (uniform in the group)
     float stale_n[3] = {0.0f, 1.0f, 0.0f};
-    const int marker = (view_flags & 2) ? 1 : 0;
+    const int marker = ((view_flags & 2) && (BIG || live)) ? 1 : 0;
     if (marker && np > 0) { stale_n[0] = polys[np - 1].n[0]; stale_n[1] = polys[np - 1].n[1]; stale_n[2] = polys[np - 1].n[2]; }      // (only the marker is lit by it)
     if (total_boxes > 0) { stale_n[0] = 0.0f; stale_n[1] = -1.0f; stale_n[2] = 0.0f; }     // drawBox ends with glNormal3f(0, -1, 0)
     const float white[3] = {1.0f, 1.0f, 1.0f};
@@ -1249,6 +1355,7 @@ __device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L,
         hdr[MW_HDR_MESH + MW_HDR_MESH_STRIDE * my_mesh_j + 1] = __int_as_float(p0 + my_tris_before);
     }
     if (sub == 0 && live) {
+        if (deal) built[env] = 1;
         a.nvis[env] = count < a.max_vis ? count : a.max_vis;
         hdr[0] = (float)a.light[(size_t)0 * a.N + env]; hdr[1] = (float)a.light[(size_t)1 * a.N + env]; hdr[2] = (float)a.light[(size_t)2 * a.N + env];
         hdr[3] = __int_as_float(total_meshes);
@@ -1306,8 +1413,8 @@ __device__ inline void geom_body(const MwArgs &a, int view_flags, int S_, int L,
 #endif
 // each kernel and its list form over the envs of a list (int32 [0] count, [1 + i] env; n_env unused)
 #define MW_GEOM_PAIR(stem, bounds, ...)                                                                                        \
-    extern "C" __global__ bounds void stem##_kernel(MW_GEOM_ARGS) { geom_body<__VA_ARGS__, false>(a, view_flags, S, L, n_env); } \
-    extern "C" __global__ bounds void stem##_sub_kernel(MW_GEOM_ARGS, const int32_t *list) { geom_body<__VA_ARGS__, true>(a, view_flags, S, L, n_env, list); }
+    extern "C" __global__ bounds void stem##_kernel(MW_GEOM_ARGS) { geom_body<__VA_ARGS__, false>(a, view_flags, S, L, n_env, fc_meta, fc_slots, built); } \
+    extern "C" __global__ bounds void stem##_sub_kernel(MW_GEOM_ARGS, const int32_t *list) { geom_body<__VA_ARGS__, true>(a, view_flags, S, L, n_env, fc_meta, fc_slots, built, list); }
 MW_GEOM_PAIR(mw_geom, __launch_bounds__(64) MW_GEOM_OCC, false, 8)
 MW_GEOM_PAIR(mw_geom_big, __launch_bounds__(64) MW_GEOM_OCC, true, 8)
 // ... for frame buffers with 1, 4 or 16 samples per pixel

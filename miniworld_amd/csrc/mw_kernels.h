@@ -67,7 +67,16 @@ MW_RNG_PAIR(mw_reset_where, MwArgs a, const uint8_t *__restrict__ mask, const ui
 MW_RNG_PAIR(mw_seed_install, MwArgs a, const int32_t *__restrict__ list, const uint64_t *__restrict__ next_seed);
 
 // the geometry kernel (mw_geom.hip): small / big scenes, 8 samples per pixel compiled in or any
-#define MW_GEOM_ARGS MwArgs a, int view_flags, int S, int L, int n_env
+// view_flags beyond the view's own bits 0-2 (mw_geom.hip), small scenes' plain kernels only — set exactly where the plan kernel runs
+// behind the launch (mw_policy.h: geom_deals): MW_GEOM_DEAL — the kernel builds only the envs the plan will have drawn, or whose
+// pending removal it must still apply, and deals them evenly over the wavefronts (mw_geom_deal.h); every wavefront of a group takes
+// each env's verdict from the plan kernel's functions (mw_frame_plan.h) on the bytes the plan kernel reads — K1's frame_clean and
+// fc_key, the cache's key table fc_meta with fc_slots slots (the plan kernel's own arguments; null: no cache) —, and nothing writes
+// them between the two, so built is a superset of drawn.  MW_GEOM_REUSE: the plan kernel's `reuse`.  built: uint8 [N], 1 where the launch built env's list, 0
+// where it left the list, nvis and the header of an earlier frame (mw_get_geom_built); written in deal mode only.
+#define MW_GEOM_DEAL 8
+#define MW_GEOM_REUSE 16
+#define MW_GEOM_ARGS MwArgs a, int view_flags, int S, int L, int n_env, const uint64_t *fc_meta, int fc_slots, uint8_t *built
 MW_KERNEL_PAIR(mw_geom, MW_GEOM_ARGS);
 MW_KERNEL_PAIR(mw_geom_big, MW_GEOM_ARGS);
 MW_KERNEL_PAIR(mw_geom_any, MW_GEOM_ARGS);

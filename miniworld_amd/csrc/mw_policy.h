@@ -218,6 +218,13 @@ inline bool frame_plans(const FramePolicy &pol, int path, bool listed, int N)
 {
     return !listed && path == MW_PATH_QUAD && (pol.reuse || pol.cache) && N <= 0xFFFFFF;
 }
+// ... and the small-scene geometry kernel in front of it builds only the envs that plan will have drawn, dealt evenly over its wavefronts
+// (mw_geom_deal.h), exactly then — unless the engine was created with MW_GEOM_DEAL=0 (enabled).  Big scenes (64 lanes: one env per
+// wavefront) have nothing to deal.
+inline bool geom_deals(bool plans, bool enabled, int lanes)
+{
+    return plans && enabled && lanes < 64;
+}
 // ... and its draw entries are filed by cost class (mw_frame_plan.h: an ordered plan, a segment of N entries per class and 16-bit
 // class counts) for the batches whose counts fit, MW_PLAN_ORDERED_MAX_N; a larger batch gets one unordered draw list, which is always right.
 inline bool frame_plan_ordered(int N)

@@ -240,6 +240,7 @@ SIGNATURES = {
     "mw_set_frame_cache": _sig(vp, i32),
     "mw_get_frame_source": _sig(vp, vp, vp),
     "mw_get_frame_plan": _sig(vp, vp, i64, vp, vp),
+    "mw_get_geom_built": _sig(vp, vp, vp),
     "mw_get_list_lengths": _sig(vp, i32, i32, vp, vp),
     "mw_debug_set_mesh_frame_seq": _sig(vp, C.c_uint32),
     "mw_debug_get_slow_heads": _sig(vp, vp, vp),
@@ -994,13 +995,21 @@ class Engine:
         return {"n_draw": n_draw, "n_copy": n_copy, "classes": classes, "class_counts": counts, "draw": draw,
                 "copy": block[96:96 + min(n_copy, N)].copy(), "lengths": lengths, "block": block}
 
+    def get_geom_built(self):
+        """Test and diagnosis call (synchronises): uint8[N], 1 where the geometry kernel of the last planned frame built the env's
+        display list, 0 where it left the list, its length and the header of an earlier frame (include/mwengine.h: mw_get_geom_built)."""
+        out = np.zeros(self.N, np.uint8)
+        self._check(self.lib.mw_get_geom_built(self.h, out.ctypes.data, _stream_ptr(self.device)), "mw_get_geom_built")
+        return out
+
     def get_frame_clean(self, out=None):
         """uint8[N] on the device: 1 = the env's frame after the last step is bit for bit the frame before it (a blocked move, a
         pickup that found nothing ...), whether or not reuse is on.  Written into `out` when given."""
         return self._get_bytes("mw_get_frame_clean", out)
 
     def list_lengths(self):
-        """int32[N]: triangles in each env's display list of the last frame (after clipping and culling)."""
+        """int32[N]: triangles in each env's display list of the last frame (after clipping and culling); of its last build for an
+        env that a planned frame did not build (get_geom_built)."""
         out = np.zeros(self.N, np.int32)
         self._check(self.lib.mw_get_list_lengths(self.h, 0, self.N, out.ctypes.data, _stream_ptr(self.device)), "mw_get_list_lengths")
         return out

@@ -14,8 +14,14 @@ g = torch.Generator(device="cuda").manual_seed(1)
 for t in range(40):
     vec.step(torch.randint(0, n_act, (n,), generator=g, device="cuda", dtype=torch.int32))
 torch.cuda.synchronize()
+# a dealing launch (MW_GEOM_DEAL) stamps only the envs it built: the others' rows are those of an earlier frame
+built = vec.engine.get_geom_built() if hasattr(vec.engine, "get_geom_built") else np.zeros(n, np.uint8)
 vec.close()
 raw = np.fromfile(out, np.uint64).reshape(n, 32)
+if built.any():
+    print("dealt launch: %d of %d envs built; the rows below are theirs (a wavefront counts once per env it built)" % (int(built.sum()), n))
+    raw = raw[built == 1]
+    n = len(raw)
 d = raw[:, :8].astype(np.float64)
 names = ["xform", "walk/occ/sift", "vertex stage", "pass1 setups", "pass1 clip", "scan", "pass2", "tail"]
 print(cfg, "cycles per phase (mean over envs, the rounds' phases summed over the rounds, last frame):")
