@@ -6,6 +6,7 @@
 // PCG64 stream is reproduced host-side only).  Executed by ONE lane.
 #pragma once
 #include "mw_device.h"
+#include "mw_radii.h"
 #include "mw_rng.h"
 
 namespace mw {
@@ -52,8 +53,9 @@ __device__ inline bool gen_hits_wall_wave(const MwArgs &a, int set, double x, do
 }
 
 // place_entity in the rectangular room gen_args[0..3] (miniworld.py:872-905); lx/hx narrow
-// the sampled x range like the min_x / max_x keyword arguments do.
-__device__ inline bool gen_place(const MwArgs &a, int env, int set, Rng &r, double radius, int n_placed,
+// the sampled x range like the min_x / max_x keyword arguments do.  `mesh`: the entity being placed is a MeshEnt — its
+// radius is an np.float32, and so is every sum of radii it takes part in (intersect, miniworld.py:960; radii_sum).
+__device__ inline bool gen_place(const MwArgs &a, int env, int set, Rng &r, double radius, bool mesh, int n_placed,
                                  double lx, double hx, double &ox, double &oz)
 {
     const double rx0 = a.gen_args[0], rx1 = a.gen_args[1], rz0 = a.gen_args[2], rz1 = a.gen_args[3];
@@ -71,7 +73,8 @@ __device__ inline bool gen_place(const MwArgs &a, int env, int set, Rng &r, doub
         for (int s = 0; s < n_placed; ++s) {
             const double dx = a.epos[((size_t)0 * a.E + s) * a.N + env] - x;
             const double dz = a.epos[((size_t)2 * a.E + s) * a.N + env] - z;
-            hit |= sqrt(dx * dx + dz * dz) < radius + a.egeom[((size_t)7 * a.E + s) * a.N + env];
+            const bool f32 = mesh || a.ekind[(size_t)s * a.N + env] == MW_ENT_MESH;
+            hit |= sqrt(dx * dx + dz * dz) < radii_sum(radius, a.egeom[((size_t)7 * a.E + s) * a.N + env], f32);
         }
         if (hit) continue;
         ox = x; oz = z;
@@ -384,20 +387,22 @@ __device__ inline bool prog_point_inside(const mw_prog_room &rm, double x, doubl
     return in;
 }
 
-// MiniWorldEnv.intersect as place_entity uses it (miniworld.py:937-963): walls, then every entity already in the list
+// MiniWorldEnv.intersect as place_entity uses it (miniworld.py:937-963): walls, then every entity already in the list.
+// `mesh`: the entity being placed is a MeshEnt (sums of radii in float32: radii_sum).
 __device__ inline bool prog_blocked(const MwArgs &a, int env, int set, unsigned long long placed, bool agent_placed,
-                                    double agent_x, double agent_z, double x, double z, double radius)
+                                    double agent_x, double agent_z, double x, double z, double radius, bool mesh)
 {
     if (gen_hits_wall(a, set, x, z, radius)) return true;
     for (int s = 0; s < a.E; ++s) {
         if (!((placed >> s) & 1ull)) continue;
         const double dx = a.epos[((size_t)0 * a.E + s) * a.N + env] - x;
         const double dz = a.epos[((size_t)2 * a.E + s) * a.N + env] - z;
-        if (sqrt(dx * dx + dz * dz) < radius + a.egeom[((size_t)7 * a.E + s) * a.N + env]) return true;
+        const bool f32 = mesh || a.ekind[(size_t)s * a.N + env] == MW_ENT_MESH;
+        if (sqrt(dx * dx + dz * dz) < radii_sum(radius, a.egeom[((size_t)7 * a.E + s) * a.N + env], f32)) return true;
     }
     if (agent_placed) {
         const double dx = agent_x - x, dz = agent_z - z;
-        if (sqrt(dx * dx + dz * dz) < radius + a.agent_radius) return true;
+        if (sqrt(dx * dx + dz * dz) < radii_sum(radius, a.agent_radius, mesh)) return true;
     }
     return false;
 }
@@ -444,7 +449,7 @@ __device__ inline void prog_static_data(const MwArgs &a, int env, int set, Rng &
 
 // place_entity's rejection sampling (miniworld.py:872-905) for one PLACE op: room (given or drawn by area), a 3-vector
 // draw whose y is thrown away, Room.point_inside, MiniWorldEnv.intersect against walls and the entities in the list
-__device__ inline void prog_sample_position(const MwArgs &a, int env, int set, Rng &r, const mw_prog_op &op, double rad,
+__device__ inline void prog_sample_position(const MwArgs &a, int env, int set, Rng &r, const mw_prog_op &op, double rad, bool mesh,
                                             unsigned long long placed, bool agent_placed, double agent_x, double agent_z,
                                             double &x, double &z)
 {
@@ -465,7 +470,7 @@ __device__ inline void prog_sample_position(const MwArgs &a, int env, int set, R
         if (rng_is_pcg(r)) (void)rng_uniform(r, 0.0, 0.0);        // the y component of the 3-vector draw
         z = rng_uniform(r, lz - rad, hz + rad);
         if (!prog_point_inside(rm, x, z)) continue;
-        if (prog_blocked(a, env, set, placed, agent_placed, agent_x, agent_z, x, z, rad)) continue;
+        if (prog_blocked(a, env, set, placed, agent_placed, agent_x, agent_z, x, z, rad, mesh)) continue;
         return;
     }
     atomicOr(a.status, MW_ST_PLACEMENT_FAIL);
@@ -519,7 +524,8 @@ __device__ inline void gen_program(const MwArgs &a, int env, int set, Rng &r, do
             if (op.op == MW_OP_FIXED) {
                 y = op.a;
             } else {
-                prog_sample_position(a, env, set, r, op, rad, placed, agent_placed, ax, az, x, z);
+                const bool mesh = !agent && a.ekind[(size_t)op.slot * N + env] == MW_ENT_MESH;
+                prog_sample_position(a, env, set, r, op, rad, mesh, placed, agent_placed, ax, az, x, z);
             }
             const double dir = op.dir_mode == 1 ? op.dir : (op.dir_mode == 2 ? dir_reg : rng_uniform(r, -kGenPi, kGenPi));
             if (agent) {
@@ -567,7 +573,7 @@ __device__ inline void collect_respawn(const MwArgs &a, int env, int set, int k,
     for (int s = 0; s < last; ++s)
         if (a.ekind[(size_t)s * N + env] != MW_ENT_NONE) placed |= 1ull << s;
     double x = 0.0, z = 0.0;
-    prog_sample_position(a, env, set, r, op, geom[7], placed, true, agent_x, agent_z, x, z);
+    prog_sample_position(a, env, set, r, op, geom[7], kind == MW_ENT_MESH, placed, true, agent_x, agent_z, x, z);
     a.epos[((size_t)0 * E + last) * N + env] = x;
     a.epos[((size_t)1 * E + last) * N + env] = 0.0;
     a.epos[((size_t)2 * E + last) * N + env] = z;
@@ -622,7 +628,7 @@ __device__ inline void generate_world(const MwArgs &a, int env, unsigned char *w
         } else {
             const double brad = sqrt(size * size + size * size) / 2.0;
             double bx, bz;
-            gen_place(a, env, set, r, brad, 0, a.gen_args[4], a.gen_args[1], bx, bz);
+            gen_place(a, env, set, r, brad, false, 0, a.gen_args[4], a.gen_args[1], bx, bz);
             const double bdir = rng_uniform(r, -kGenPi, kGenPi);
             // written first so that the agent's placement sees it; colour bias applied below
             gen_store_box(a, env, 0, bx, bz, bdir, size, col);
@@ -631,7 +637,7 @@ __device__ inline void generate_world(const MwArgs &a, int env, unsigned char *w
             // The Philox stream keeps its historical order (direction first) for both.
             const bool dir_last = rng_is_pcg(r) && a.generator == MW_GEN_ONEROOM;
             if (!dir_last) adir = rng_uniform(r, -a.gen_args[6], a.gen_args[6]);
-            gen_place(a, env, set, r, a.agent_radius, 1, a.gen_args[0], a.gen_args[5], ax, az);
+            gen_place(a, env, set, r, a.agent_radius, false, 1, a.gen_args[0], a.gen_args[5], ax, az);
             if (dir_last) adir = rng_uniform(r, -a.gen_args[6], a.gen_args[6]);
         }
         // per-episode parameters (miniworld.py:576-578), then entity randomisation (:584-585)
@@ -678,7 +684,7 @@ __device__ inline void generate_world(const MwArgs &a, int env, unsigned char *w
             if (tex_late && s == 0) pick_textures();
             const double radius = a.gt->gen_tab[kind * 4 + 0], height = a.gt->gen_tab[kind * 4 + 1];
             double x, z;
-            gen_place(a, env, set, r, radius, s, a.gen_args[0], a.gen_args[1], x, z);
+            gen_place(a, env, set, r, radius, kind != 1, s, a.gen_args[0], a.gen_args[1], x, z);
             const double dir = rng_uniform(r, -kGenPi, kGenPi);
             const size_t E = a.E;
             a.ekind[(size_t)s * N + env] = kind == 1 ? MW_ENT_BOX : MW_ENT_MESH;
@@ -695,7 +701,7 @@ __device__ inline void generate_world(const MwArgs &a, int env, unsigned char *w
             a.egeom[((size_t)7 * E + s) * N + env] = radius;
             a.egeom[((size_t)8 * E + s) * N + env] = height;
         }
-        gen_place(a, env, set, r, a.agent_radius, n < a.E ? n : a.E, a.gen_args[0], a.gen_args[1], ax, az);
+        gen_place(a, env, set, r, a.agent_radius, false, n < a.E ? n : a.E, a.gen_args[0], a.gen_args[1], ax, az);
         adir = rng_uniform(r, -kGenPi, kGenPi);
         for (int k = 0; k < 3; ++k) a.light[(size_t)(0 + k) * N + env] = gen_param(r, a.sky[k], dr);
         for (int k = 0; k < 3; ++k) a.light[(size_t)(3 + k) * N + env] = gen_param(r, a.light_pos[k], dr);

@@ -65,17 +65,10 @@ __device__ inline double ent_geom(const MwArgs &a, int env, int slot, int k)
     return a.egeom[((size_t)k * a.E + slot) * a.N + env];
 }
 
-// The reference's sums of radii as they evaluate under NumPy 2's promotion rules (the fixtures record the version: meta/numpy).
-// A MeshEnt's radius (Ball, Key, MedKit, the static meshes) comes from ObjMesh.max_coords and is an np.float32 (entity.py:141-147);
-// a Box's, a frame's and the agent's are Python floats.  Where a Python float meets an np.float32 it is converted to float32
-// first, and the sum is formed in float32, left to right as the reference writes it; the comparison with the float64 distance
-// (or the product with the float64 direction vector) widens the result again.  Decided by the entity's kind, never by its value.
+// The reference's sums of radii (radii_sum, mw_radii.h: float32 where a mesh entity takes part), decided by the entity's kind, never
+// by its value.
+using mw::radii_sum;
 __device__ inline bool is_mesh(const MwArgs &a, int env, int slot) { return a.ekind[(size_t)slot * a.N + env] == MW_ENT_MESH; }
-__device__ inline double radii_sum(double r0, double r1, bool f32) { return f32 ? (double)((float)r0 + (float)r1) : r0 + r1; }
-__device__ inline double radii_sum(double r0, double r1, double more, bool f32)
-{
-    return f32 ? (double)(((float)r0 + (float)r1) + (float)more) : r0 + r1 + more;
-}
 
 // MiniWorldEnv.intersect (miniworld.py:937-963): 0 none, -1 wall, 1+slot entity, 1+E agent.  `radius` is the agent's (self_slot
 // -1: a Python float) or the radius of the entity self_slot, which the agent carries.

@@ -32,6 +32,44 @@ def load_carry_case(name):
     return tuple({k[len(p):]: d[k] for k in d.files if k.startswith(p)} for p in ("s0/", "tr/", "meta/", "poke/"))
 
 
+def placement_cases(prefix=""):
+    """Names of the placement fixtures (tests/golden/placement/, tools/gen_placement_fixtures.py) that start with `prefix`."""
+    return sorted(f[:-4] for f in os.listdir(os.path.join(GOLDEN, "placement")) if f.endswith(".npz") and f.startswith(prefix))
+
+
+def load_placement_case(name):
+    """(world, case, meta, poke) of a placement fixture; poke: the state before the respawn case's one step, else empty."""
+    d = np.load(os.path.join(GOLDEN, "placement", name + ".npz"))
+    return tuple({k[len(p):]: d[k] for k in d.files if k.startswith(p)} for p in ("w/", "case/", "meta/", "poke/"))
+
+
+def world_of_scene(sc):
+    """The w/ arrays of a placement fixture from a neutral scene (scene.scene_from_env of a host env, scene_of_vec_env of a
+    device env): what test_gpu_env_api._assert_same_world compares — poses, kinds, mesh names, a box's size and colour, a
+    mesh's scale and radius, the per-episode parameters — and the texture variant of every room polygon."""
+    live = np.asarray(sc["ents_kind"]) != 0
+    box = (np.asarray(sc["ents_kind"])[live] == 1)[:, None]
+    names = [str(n) for n in sc["mesh_names"]]
+    room = [i for i in range(len(sc["polys_nv"])) if not sc["polys_nv"][i] & 0x100]
+    return {
+        "agent_pos": np.asarray(sc["agent_pos"], np.float64), "agent_dir": np.float64(sc["agent_dir"]),
+        "cam": np.array([sc["cam_height"], sc["cam_fwd_disp"], sc["cam_pitch"], sc["cam_fov_y"]], np.float64),
+        "light": np.concatenate([sc["sky"], sc["light_pos"], sc["light_color"], sc["light_ambient"]]).astype(np.float64),
+        "ents_kind": np.asarray(sc["ents_kind"])[live], "ents_pos": np.asarray(sc["ents_pos"])[live], "ents_dir": np.asarray(sc["ents_dir"])[live],
+        "ents_size": np.where(box, np.asarray(sc["ents_size"])[live], 0.0), "ents_color": np.where(box, np.asarray(sc["ents_color"])[live], 1.0),
+        "ents_scale": np.asarray(sc["ents_scale"])[live], "ents_radius": np.asarray(sc["ents_radius"])[live],
+        "ents_mesh_name": np.array([names[m] if m >= 0 else "" for m in np.asarray(sc["ents_mesh"])[live]]),
+        "polys_tex_name": np.array([str(sc["tex_names"][sc["polys_tex"][i]]) for i in room]),
+    }
+
+
+def assert_world_equal(got, want, tag):
+    """Exact equality, field by field."""
+    assert sorted(got) == sorted(want), (tag, sorted(got), sorted(want))
+    for k in want:
+        assert np.array_equal(np.asarray(got[k]), np.asarray(want[k])), (tag, k, got[k], want[k])
+
+
 def poked_scene(s0, poke, k):
     """Scene s0 with the starting state of threshold case k substituted."""
     sc = dict(s0)
