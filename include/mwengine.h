@@ -793,6 +793,17 @@ int mw_ray_cast(mw_engine *e, const mw_ray_params *params, const uint8_t *d_mask
  * choice to the ray count again */
 int mw_debug_set_ray_form(mw_engine *e, int form);
 
+/* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
+ * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
+ * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.
+ *   waves_per_env    wavefronts per env of the tile kernels; must divide the raster grid's tile count (ceil(W / 16) * ceil(H / 4))
+ *   mesh_tile_waves  wavefronts of the listed mesh tiles' launch, at least 8 (each draws the list of class b % n_xcc, n_xcc <= 8)
+ *   ent_blocks       persistent workgroups of the mesh entity kernel, at least 8 (the same)
+ *   slow_waves       wavefronts of the mesh slow-path kernel, at least 1
+ * MW_E_INVALID, and nothing changed: a null engine, a negative value, a waves_per_env that does not divide the tile count,
+ * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
+int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
+
 /* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where or mw_nav_build skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);

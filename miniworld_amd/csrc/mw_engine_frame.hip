@@ -716,4 +716,24 @@ int mw_set_frame_cache(mw_engine *e, int32_t slots)
     return MW_OK;
 }
 
+// The launch shape for tests and measurements.  None of the three worker kinds waits for another — the entity kernel's workgroups draw
+// items from a cursor, the listed tile wavefronts and the slow kernel's stride over their lists —, so any count draws the same frame as
+// long as every class b % n_xcc of the entity and tile lists has a worker: 8, the most classes the engine knows.
+int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves)
+{
+    if (!e) return MW_E_INVALID;
+    if (waves_per_env < 0 || mesh_tile_waves < 0 || ent_blocks < 0 || slow_waves < 0)
+        return fail(e, MW_E_INVALID, "mw_debug_set_launch_shape: negative value (%d, %d, %d, %d)", waves_per_env, mesh_tile_waves, ent_blocks, slow_waves);
+    if (waves_per_env && e->args.n_tiles % waves_per_env != 0)
+        return fail(e, MW_E_INVALID, "mw_debug_set_launch_shape: waves_per_env %d does not divide the %d tiles of the frame", waves_per_env, e->args.n_tiles);
+    if ((mesh_tile_waves && mesh_tile_waves < 8) || (ent_blocks && ent_blocks < 8))
+        return fail(e, MW_E_INVALID, "mw_debug_set_launch_shape: mesh_tile_waves %d, ent_blocks %d: fewer than 8 leave whole lists undrawn", mesh_tile_waves, ent_blocks);
+    frames_stale(e);
+    if (waves_per_env) e->waves_per_env = waves_per_env;
+    if (mesh_tile_waves) e->mp.mesh_tile_waves = mesh_tile_waves;
+    if (ent_blocks) e->mp.ent_blocks = ent_blocks;
+    if (slow_waves) e->mp.slow_waves = slow_waves;      // (0 keeps the value, so a value below 1 cannot be set)
+    return MW_OK;
+}
+
 }  // extern "C"

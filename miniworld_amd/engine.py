@@ -223,6 +223,7 @@ SIGNATURES = {
     "mw_debug_set_nav_passes": _sig(vp, vp),
     "mw_ray_cast": _sig(vp, P(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_ray_form": _sig(vp, C.c_int),
+    "mw_debug_set_launch_shape": _sig(vp, C.c_int, C.c_int, C.c_int, C.c_int),
     "mw_pcg64_draws": _sig(C.c_uint64, i32, vp, vp),
     "mw_selftest_rcp": _sig(vp, vp, vp),
     "mw_selftest_div": _sig(vp, vp),
@@ -535,6 +536,13 @@ class Engine:
     def debug_set_ray_form(self, form: int):
         """Measurements: 1 casts every ray count with a ray per lane, 2 with an obstacle per lane, 0 by the ray count again."""
         self._check(self.lib.mw_debug_set_ray_form(self.h, int(form)), "mw_debug_set_ray_form")
+
+    def debug_set_launch_shape(self, waves_per_env: int = 0, mesh_tile_waves: int = 0, ent_blocks: int = 0, slow_waves: int = 0):
+        """Tests and measurements: wavefronts per env of the tile kernels (a divisor of the frame's tile count) and the persistent
+        workers of the mesh tiles (>= 8), the mesh entity kernel (>= 8) and the mesh slow path (>= 1); 0 keeps a value.  Every
+        frame is the same bits under every shape."""
+        self._check(self.lib.mw_debug_set_launch_shape(self.h, int(waves_per_env), int(mesh_tile_waves), int(ent_blocks), int(slow_waves)),
+                    "mw_debug_set_launch_shape")
 
     def set_gen_program(self, prog: MwGenProgram, polys: np.ndarray, poly_room, poly_surf, poly_m, segs: np.ndarray):
         """Installs the placement program of an MW_GEN_PROGRAM engine (include/mwengine.h: mw_set_gen_program)."""

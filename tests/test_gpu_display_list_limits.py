@@ -34,12 +34,15 @@ def wanted(name, ns, width, height):
     return [pyoracle.render(sc, width=width, height=height, nsamples=ns, meshes=meshes) for sc in scenes]
 
 
-def draw_and_compare(name, want_path, msaa=8, with_depth=True, max_visible=64, width=80, height=60, lengths=None):
+def draw_and_compare(name, want_path, msaa=8, with_depth=True, max_visible=64, width=80, height=60, lengths=None, shape=None):
+    """shape: keyword arguments of Engine.debug_set_launch_shape, applied to the new engine (tests/test_gpu_launch_shapes.py)"""
     import torch
     world, scenes, names, pinned, _ = batch(name)
     lengths = pinned if lengths is None else lengths
     assert len(scenes) <= 80
     eng = helpers.make_engine_for_scene(world, len(scenes), msaa=msaa, max_visible=max_visible, width=width, height=height)
+    if shape is not None:
+        eng.debug_set_launch_shape(**shape)
     eng.set_state(helpers.scene_state_arrays(scenes))
     rgb = torch.zeros((len(scenes), height, width, 3), dtype=torch.uint8, device="cuda")
     depth = torch.zeros((len(scenes), height, width, 1), dtype=torch.float32, device="cuda") if with_depth else None
@@ -76,12 +79,12 @@ CONFIGS = {
 }
 
 
-def run_config(name, config, monkeypatch):
+def run_config(name, config, monkeypatch, shape=None):
     from miniworld_amd import engine as E
     msaa, env, with_depth, max_visible, path = CONFIGS[config]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    draw_and_compare(name, getattr(E, path), msaa=msaa, with_depth=with_depth, max_visible=max_visible)
+    draw_and_compare(name, getattr(E, path), msaa=msaa, with_depth=with_depth, max_visible=max_visible, shape=shape)
 
 
 @pytest.mark.parametrize("config", CONFIGS)

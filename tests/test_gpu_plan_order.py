@@ -84,26 +84,37 @@ def _check_frames(tag, v, family, samples, st):
     return src
 
 
-def _check_plan(tag, v, src, slot_of=None):
-    """The block against the source bytes (and the model's slots); returns the classes along the draw list."""
-    n = len(src)
-    p = v.engine.get_frame_plan()
+def _check_plan(tag, v, src, slot_of=None, ordered=True, slots=SLOTS):
+    """The block against the source bytes (and the model's slots); returns the classes along the draw list.  v: a MiniWorldVecEnv or
+    an Engine.  ordered=False (tests/test_gpu_launch_shapes.py: 65536 envs and more): one draw list, no classes; returns its envs."""
+    p =getattr(v, "engine", v).get_frame_plan()
+    if not ordered:
+        assert p["classes"] == 0 and p["class_counts"] == [], (tag, "a batch this large gets one unordered draw list", p["classes"])
+        assert not p["block"][[32, 33, 64, 65]].any(), (tag, "class counts in the head of an unordered plan")
+        return _check_lists(tag, p, src, slot_of, slots)
     assert p["classes"] == CLASSES, (tag, "a batch this small gets an ordered plan")
+    denv = _check_lists(tag, p, src, slot_of, slots)
+    assert p["n_draw"] == sum(p["class_counts"]), (tag, p["n_draw"], p["class_counts"])
+    cls = np.minimum(CLASSES - 1, np.maximum(p["lengths"], 0) // 4)[denv]
+    assert (np.diff(cls) <= 0).all(), (tag, "the classes along the draw list increase somewhere", cls.tolist()[:64])
+    assert [int((cls == c).sum()) for c in range(CLASSES)] == p["class_counts"], (tag, "the head's class counts", p["class_counts"])
+    return cls
+
+
+def _check_lists(tag, p, src, slot_of, slots):
+    """the draw and copy entries of a plan block against the source bytes; returns the envs along the draw list"""
     denv, dslot = (p["draw"] & 0xFFFFFF).astype(np.int64), (p["draw"] >> 24).astype(np.int64)
     cenv, cslot = (p["copy"] & 0xFFFFFF).astype(np.int64), (p["copy"] >> 24).astype(np.int64)
-    assert p["n_draw"] == sum(p["class_counts"]) == denv.size == int((src == 0).sum()), (tag, p["n_draw"], p["class_counts"], int((src == 0).sum()))
+    assert p["n_draw"] == denv.size == int((src == 0).sum()), (tag, p["n_draw"], p["class_counts"], int((src == 0).sum()))
     assert p["n_copy"] == cenv.size == int((src >= 2).sum()), (tag, p["n_copy"], int((src >= 2).sum()))
-    assert sorted(denv.tolist()) == np.flatnonzero(src == 0).tolist(), (tag, "the draw entries are not the drawn envs, each once")
-    assert sorted(cenv.tolist()) == np.flatnonzero(src >= 2).tolist(), (tag, "the copy entries are not the hits, each once")
+    assert np.array_equal(np.sort(denv), np.flatnonzero(src == 0)), (tag, "the draw entries are not the drawn envs, each once")
+    assert np.array_equal(np.sort(cenv), np.flatnonzero(src >= 2)), (tag, "the copy entries are not the hits, each once")
     assert (cslot == src[cenv].astype(np.int64) - 2).all(), (tag, "a copy entry names another slot than the source byte")
     if slot_of is not None:
         assert (dslot == slot_of[denv]).all(), (tag, "a draw entry names another victim slot than the rule's", denv[dslot != slot_of[denv]][:8].tolist())
     else:
-        assert (dslot < SLOTS).all()
-    cls = np.minimum(CLASSES - 1, np.maximum(p["lengths"], 0) // 4)[denv]
-    assert (np.diff(cls) <= 0).all(), (tag, "the classes along the draw list increase somewhere", cls.tolist())
-    assert [int((cls == c).sum()) for c in range(CLASSES)] == p["class_counts"], (tag, "the head's class counts", p["class_counts"])
-    return cls
+        assert (dslot < slots).all()
+    return denv
 
 
 CASES = [("MiniWorld-Hallway-v0", "Hallway", False, 8, n) for n in (1, 65, 130)] + [("MiniWorld-Hallway-v0", "Hallway", False, 4, n) for n in (1, 65, 130)] + \
