@@ -310,14 +310,16 @@ __device__ inline bool scatter_tri_wave(const MeshEnt &e, int tri, const float4 
     return __any(any) != 0;
 }
 
-// Attribute planes of mesh triangle (e, tri) for the pixel (px, gy): the triangle is taken through the vertex stage again
-// (lighting per vertex: Gouraud), clipped if it has to be — then the part of the fan that covers the pixel — and set up.
+// Attribute planes of mesh triangle (e, tri) for sample `smp` of the pixel (px, gy): the triangle is taken through the vertex stage
+// again (lighting per vertex: Gouraud), clipped if it has to be — then the piece of the fan that holds the sample, which GL shades
+// on its own — and set up.  cover: the pixel's samples the colour stands for (all of them for a triangle that is not clipped).
 // (out of line with scalar arguments, like raster_tri: the tile context and the table entry by reference were 500 B of scratch)
 template <int S>
 __device__ __attribute__((noinline)) RGB shade_mesh_tri(const float *hdr, int W, int H, int j, int tri, int px, int gy, const float *mesh_pos,
                                                         const float *mesh_nrm, const float *mesh_rgb, const float *mesh_uv, rsrc_t tex_rsrc,
-                                                        int flat, mwgl::Vert *clipbuf)
+                                                        int flat, mwgl::Vert *clipbuf, int smp, uint32_t &cover)
 {
+    cover = ~0u;
     mwgl::Frame f;
     frame_lite(hdr, W, H, f);
     const MeshEnt e = load_ment(hdr + MW_HDR_MESH, j);
@@ -348,20 +350,22 @@ __device__ __attribute__((noinline)) RGB shade_mesh_tri(const float *hdr, int W,
         if (!((pend >> lane) & 1ull) || rank >= MW_CLIP_TURN) continue;
         mwgl::Vert *buf = clipbuf + rank * 2 * MWGL_MAX_CLIP_VERTS, *r;
         const int n = mwgl::clip_triangle<true>(f, v[0], v[1], v[2], buf, buf + MWGL_MAX_CLIP_VERTS, &r);
-        // the first triangle of the fan with a sample of this pixel inside
-        for (int i = 2; i < n && !have; ++i) {
+        // the triangle of the fan with the sample inside (else, as a key without a piece cannot happen, the first with any)
+        bool exact = false;
+        for (int i = 2; i < n && !exact; ++i) {
             mwgl::TriSetup t2;
             if (!mwgl::setup_triangle(r[i - 1], r[i], r[0], S > 1, e.tex >= 0, t2)) continue;
-            bool any = false;
+            uint32_t any = 0u;
             for (int s = 0; s < S; ++s) {
                 int sx, sy;
                 mwrec::sample_offset(S, s, sx, sy);
                 const int64_t fx = (int64_t)px * 256 + sx, fy = (int64_t)gy * 256 + sy;
                 bool in = true;
                 for (int k = 0; k < 3; ++k) in &= (t2.c[k] + (int64_t)t2.dcdy[k] * fy - (int64_t)t2.dcdx[k] * fx) > 0;
-                any |= in;
+                any |= in ? 1u << s : 0u;
             }
-            if (any) { ts = t2; have = true; }
+            exact = (any >> smp) & 1u;
+            if (exact || (any && !have)) { ts = t2; have = true; cover = exact ? any : ~0u; }
         }
     }
     if (!have) return RGB{0.0f, 0.0f, 0.0f};
@@ -384,8 +388,9 @@ __device__ __attribute__((noinline)) RGB shade_frag_view(const float4 *sr, rsrc_
 // draw id -> fragment colour: ids inside a mesh entity's range are triangles, the others index the record list once the
 // mesh triangles drawn before them are subtracted
 template <int S>
-__device__ inline RGB shade_by_draw_id_s(const TileCtx &cx, uint32_t id, int px, int gy)
+__device__ inline RGB shade_by_draw_id_s(const TileCtx &cx, uint32_t id, int px, int gy, int smp, uint32_t &cover)
 {
+    cover = ~0u;
     const int n_mesh = __float_as_int(cx.hdr[3]);
     int vis = (int)id;
     for (int j = 0; j < n_mesh; ++j) {
@@ -395,32 +400,36 @@ __device__ inline RGB shade_by_draw_id_s(const TileCtx &cx, uint32_t id, int px,
             vis -= nt;
         } else if ((int)id >= start) {
             return shade_mesh_tri<S>(cx.hdr, cx.W, cx.H, j, (int)id - start, px, gy, cx.mesh_pos, cx.mesh_nrm, cx.mesh_rgb, cx.mesh_uv, cx.te.tx,
-                                     cx.te.flat, cx.clipbuf);
+                                     cx.te.flat, cx.clipbuf, smp, cover);
         }
     }
     return shade_frag_view(cx.s_shade + vis * (MW_SHADE_REC / 4), cx.te.tx, cx.te.flat, px, gy, S > 1 ? 0.5f : 0.0f);
 }
 
-// the tile kernels (obs path): mesh triangle `id` of table entry mj from the plane cache (raster_tri_obs)
-__device__ inline RGB shade_mesh_winner(const TileCtx &cx, int mj, uint32_t id, int px, int gy)
+// the tile kernels (obs path): mesh triangle `id` of table entry mj from the plane cache (raster_tri_obs).  want: the pixel's
+// samples that still wait for the triangle's colour; cover: those of them the returned colour is for — all, but for a clipped
+// triangle, whose fan GL shades piece by piece: then the samples of the first piece that holds one of `want`
+__device__ inline RGB shade_mesh_winner(const TileCtx &cx, int mj, uint32_t id, int px, int gy, uint32_t want, uint32_t &cover)
 {
+    cover = 0xFFu;
     const int start = __float_as_int(cx.ment[MW_HDR_MESH_STRIDE * mj + 1]);
     const size_t slot = (size_t)__float_as_int(cx.ment[MW_HDR_MESH_STRIDE * mj + 25]) + (size_t)((int)id - start);
     const float4 *q = reinterpret_cast<const float4 *>(cx.planes + slot * MW_PLANE_REC);
     const float4 *q4p = reinterpret_cast<const float4 *>(cx.planes_xtra + slot * MW_PLANE_XTRA);
     if (__float_as_int(q[1].w) == MW_PLANE_SLOW) {
         // a triangle that crosses a frustum plane: mw_mesh_slow_kernel clipped it and left, per pixel, a chain of the pieces
-        // of its fan that cover a sample there, and the pieces' planes (of the entries for this id the first piece's counts)
+        // of its fan that cover a sample there with the masks of those samples, and the pieces' planes (of the entries for this id
+        // that hold a wanted sample the first piece's counts)
         const uint32_t h0 = cx.slow_head[(cx.H - 1 - gy) * cx.W + px];
         uint32_t k = (h0 >> 16) == cx.slow_stamp ? (h0 & 0xFFFFu) : 0u;        // a head of an earlier frame is empty
         uint32_t best = 8u, piece = 0xFFFFFFFFu;
         for (int guard = 0; k != 0u && k <= MW_SLOW_FRAGS && guard < MW_SLOW_FRAGS; ++guard) {
             const float4 fr = cx.slow_frags[k - 1u];
             const uint32_t w = __float_as_uint(fr.x), pc = (w >> 13) & 7u;
-            if ((w >> 16) == id && pc < best) { piece = __float_as_uint(fr.y); best = pc; }
+            if ((w >> 16) == id && pc < best && (__float_as_uint(fr.z) & want)) { piece = __float_as_uint(fr.y); best = pc; cover = __float_as_uint(fr.z); }
             k = w & 0x1FFFu;
         }
-        if (piece >= (uint32_t)MW_SLOW_PIECES) return RGB{0.0f, 0.0f, 0.0f};
+        if (piece >= (uint32_t)MW_SLOW_PIECES) { cover = 0xFFu; return RGB{0.0f, 0.0f, 0.0f}; }
         q = cx.slow_frags + (MW_SLOW_FRAGS + 1) + (size_t)piece * (MW_PIECE_REC / 4);
         q4p = q + 4;
     }

@@ -265,7 +265,7 @@ __device__ unsigned long long g_k2prof[K2P_SLOTS][16];
 
 struct TileCtx;
 // colour of mesh triangle `id` (entry mj of the env's mesh table) at the lane's pixel: defined by the kernels that see meshes
-__device__ inline RGB shade_mesh_winner(const TileCtx &cx, int mj, uint32_t id, int px, int gy);
+__device__ inline RGB shade_mesh_winner(const TileCtx &cx, int mj, uint32_t id, int px, int gy, uint32_t want, uint32_t &cover);
 
 // Everything a wavefront needs to produce one 16x4 tile of one env.
 struct TileCtx {
@@ -659,7 +659,7 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
             ++kp_win;
             int rec = (int)id;
             const int mj = MESH ? mesh_entry_of(cx, id, rec) : -1;
-            uint32_t sel = id;
+            uint32_t sel = id, cover = 0xFFu;         // (cover: the samples the colour is for — a clipped mesh triangle's come piece by piece)
             RGB c;
             if (MESH && mj >= 0) {
                 // every lane whose next winner belongs to this mesh entity shades its own triangle
@@ -667,7 +667,10 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
                 const bool on = (int)mine < start + nt;      // mine >= id >= start
                 sel = on ? mine : 0x20000u;
                 [[maybe_unused]] const unsigned long long km0 = K2P_NOW();
-                c = shade_mesh_winner(cx, mj, on ? mine : id, px, gy);
+                uint32_t want = 0u;
+#pragma unroll
+                for (int s = 0; s < 8; ++s) want |= pid[s] == sel ? 1u << s : 0u;
+                c = shade_mesh_winner(cx, mj, on ? mine : id, px, gy, want, cover);
 #ifdef MW_PERF_HOOKS
                 kp_mesh_cyc += K2P_NOW() - km0; ++kp_mesh_n;
 #endif
@@ -676,7 +679,7 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
             }
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-                const bool eq = pid[s] == sel;
+                const bool eq = pid[s] == sel && ((cover >> s) & 1u);
                 smp.r[s] = eq ? c.r : smp.r[s]; smp.g[s] = eq ? c.g : smp.g[s]; smp.b[s] = eq ? c.b : smp.b[s];
                 pid[s] = eq ? 0x10000u : pid[s];
             }

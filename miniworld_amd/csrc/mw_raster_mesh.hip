@@ -198,11 +198,11 @@ struct SlowPiece {       // what the pixel loop needs of one set-up piece
     uint32_t rec;       // the piece's record (attribute planes) in the env's piece table
 };
 
-// the piece's samples in pixel (px, gy): keys scattered; true if any
-__device__ inline bool slow_cover(const SlowPiece &p, int px, int gy, int W, int H, uint32_t *keys)
+// the piece's samples in pixel (px, gy): keys scattered; the mask of the samples inside
+__device__ inline uint32_t slow_cover(const SlowPiece &p, int px, int gy, int W, int H, uint32_t *keys)
 {
     uint32_t *kp = keys + ((size_t)(H - 1 - gy) * W + px) * 8;
-    bool any = false;
+    uint32_t any = 0u;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         const int fx = px * 256 + (int)mwrec::kPat[2][s][0] * 16, fy = gy * 256 + (int)mwrec::kPat[2][s][1] * 16;
@@ -212,25 +212,27 @@ __device__ inline bool slow_cover(const SlowPiece &p, int px, int gy, int W, int
         if (in) {
             const float xs = (float)px + samp_fx<8>(s), ys = (float)gy + samp_fy<8>(s);
             atomicMin(kp + s, (mwgl::z_to_unorm16(mwgl::plane_at(p.z, xs, ys)) << 16) | (p.id >> 16));
-            any = true;
+            any |= 1u << s;
         }
     }
     return any;
 }
 
-// the piece covers a sample of pixel (px, gy): entry k of the env's list, chained to the pixel (K2 shades it from the
-// piece's record if it wins)
+// the piece covers a sample of pixel (px, gy): entry k of the env's list, chained to the pixel with the mask of the samples it
+// covers (K2 shades those of them its triangle wins from the piece's record: GL shades every piece of a clipped triangle's fan
+// on its own)
 // (a pixel's chain head is (frame stamp << 16) | index + 1: heads of earlier frames read as empty, nothing is cleared)
 __device__ inline void slow_pixel(const SlowPiece &p, int px, int gy, int W, int H, uint32_t *keys, int32_t *frag_count,
                                   float4 *frags, uint32_t stamp, uint32_t *head, uint32_t *status)
 {
-    if (!slow_cover(p, px, gy, W, H, keys)) return;
+    const uint32_t cover = slow_cover(p, px, gy, W, H, keys);
+    if (!cover) return;
     const int k = atomicAdd(frag_count, 1);
     if (k >= MW_SLOW_FRAGS) { atomicOr(status, MW_ST_VIS_OVERFLOW); return; }
     const uint32_t pix = (uint32_t)((H - 1 - gy) * W + px);
     const uint32_t old = atomicExch(head + pix, (stamp << 16) | ((uint32_t)k + 1u));
     const uint32_t next = (old >> 16) == stamp ? (old & 0xFFFFu) : 0u;
-    frags[k] = make_float4(__uint_as_float(p.id | next), __uint_as_float(p.rec), 0.0f, 0.0f);
+    frags[k] = make_float4(__uint_as_float(p.id | next), __uint_as_float(p.rec), __uint_as_float(cover), 0.0f);
 }
 
 }  // namespace
@@ -493,17 +495,19 @@ __device__ inline void view_tile_body(TileCtx &cx, int tiles_x, const uint32_t *
     const uint32_t z16 = key[0] >> 16;
     // resolve: the samples' colours summed in sample order; a sample whose winner is the previous sample's reuses its colour
     const RGB sky = {cx.sky_r, cx.sky_g, cx.sky_b};
+    // (... and lies in the part of it that was shaded: the pieces of a clipped mesh triangle's fan are shaded one by one)
     RGB acc = {0.0f, 0.0f, 0.0f}, last = sky;
-    uint32_t last_id = MW_SKY_PID;
+    uint32_t last_id = MW_SKY_PID, last_cover = ~0u;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const uint32_t w = key[s] & 0xFFFFu;
-        const bool need = w != last_id && w != MW_SKY_PID;
+        const bool need = (w != last_id || !((last_cover >> s) & 1u)) && w != MW_SKY_PID;
         if (__any(need)) {
-            const RGB c = shade_by_draw_id_s<S>(cx, need ? w : 0u, px, gy);
-            if (need) { last = c; last_id = w; }
+            uint32_t cover;
+            const RGB c = shade_by_draw_id_s<S>(cx, need ? w : 0u, px, gy, s, cover);
+            if (need) { last = c; last_id = w; last_cover = cover; }
         }
-        if (w == MW_SKY_PID) { last = sky; last_id = MW_SKY_PID; }
+        if (w == MW_SKY_PID) { last = sky; last_id = MW_SKY_PID; last_cover = ~0u; }
         if (s == 0) acc = last;
         else { acc.r = acc.r + last.r; acc.g = acc.g + last.g; acc.b = acc.b + last.b; }
     }

@@ -859,7 +859,8 @@ def test_maze_with_domain_rand_draws_a_texture_variant_per_room(env_id, cls_name
 
 
 _DEVICE_FAMILIES = {"Hallway": "MiniWorld-Hallway-v0", "OneRoom": "MiniWorld-OneRoom-v0", "Maze": "MiniWorld-Maze-v0",
-                    "MazeS3": "MiniWorld-MazeS3-v0", "PickupObjects": "MiniWorld-PickupObjects-v0"}
+                    "MazeS3": "MiniWorld-MazeS3-v0", "PickupObjects": "MiniWorld-PickupObjects-v0", "OneRoomS6": "MiniWorld-OneRoomS6-v0",
+                    "OneRoomS6Fast": "MiniWorld-OneRoomS6Fast-v0", "MazeS2": "MiniWorld-MazeS2-v0", "MazeS3Fast": "MiniWorld-MazeS3Fast-v0"}
 _DEVICE_FAMILIES.update({c: f"MiniWorld-{c}-v0" for c in _PROGRAM_FAMILIES})
 
 
@@ -1120,7 +1121,9 @@ def test_two_engines_are_independent():
         v.close()
 
 
-@pytest.mark.parametrize("case", ["sidewalk_s0", "sidewalk_s3", "sign_s0", "sign_green_key_s1", "collecthealth_s13"])
+@pytest.mark.parametrize("case", ["sidewalk_s0", "sidewalk_s3", "sign_s0", "sign_green_key_s1", "collecthealth_s13",
+                                  "out_sidewalk_s0", "out_sidewalk_street_box", "out_sign_box_s0", "out_sign_key_s1",
+                                  "out_collecthealth_none_s0", "out_collecthealth_kits_s1"])
 def test_vec_env_host_rule_families_follow_reference_trajectory(case):
     """Sidewalk, Sign and CollectHealth in the batched API: Sidewalk's forbidden street, Sign's touch table / extra
     end-of-episode action and CollectHealth's health bookkeeping with kits respawning through the env's own numpy
