@@ -793,6 +793,45 @@ int mw_ray_cast(mw_engine *e, const mw_ray_params *params, const uint8_t *d_mask
  * choice to the ray count again */
 int mw_debug_set_ray_form(mw_engine *e, int form);
 
+/* ---- explored-area maps ------------------------------------------------------ */
+/* Which cells of its floor plan each agent has seen so far, and how many of them are new: the coverage reward, the top-down map with
+ * fog of war (Habitat's), the occupancy input of Active Neural SLAM style policies, the frontier of frontier exploration.  The
+ * reference has no such call.  The map accumulates in the caller's tensor, like a nav field; the engine keeps nothing of it.
+ *
+ * The grid: a seen map is uint8[N][gz][gx], 0 unseen and 1 seen, on the grid of a nav field of the same cell, gx, gz — origin
+ * (min_x, min_z) of the env's own extent, the centre of cell (j, i) at (min_x + (i + 0.5) * cell, min_z + (j + 0.5) * cell) — so that
+ * map and field line up cell for cell.
+ *
+ * Sight: cell (j, i) of env e is VISIBLE in a call iff all of the following hold; all arithmetic is float64, + - * / and sqrt only,
+ * uncontracted, in this order:
+ *   1  its centre c is not beyond the extent (c.x > max_x or c.z > max_z, as a nav field's blocked border)
+ *   2  with v = (cx - ox, cz - oz) from the agent's position o: dist = sqrt(vx*vx + vz*vz), and dist <= range
+ *   3  cos_half == -1.0 (all round), or dist == 0.0, or vx*hx + vz*hz >= cos_half * dist, where h = (cos, -sin) of agent_dir — the
+ *      reference's dir_vec, through the same deterministic sin / cos as the dynamics, as the fan of mw_ray_cast forms it for offset 0
+ *   4  the line of sight is free: the ray with origin o, direction v, max_t = 1 and radius 0 meets nothing under exactly mw_ray_cast's
+ *      arithmetic and rules, t == 1 and hit == -1.  The obstacles are the collision segments and, with MW_SEEN_ENTITIES, every slot
+ *      whose kind is not MW_ENT_NONE and which is not the carried one, as its circle; a candidate counts only when t < 1, both endpoints
+ *      of a segment are inclusive.
+ * No test holds for a NaN: a NaN agent pose marks nothing.
+ *
+ * One call, for every env i with d_mask[i] != 0 (d_mask uint8[N] on the device, NULL = all): if d_clear[i] != 0 (uint8[N], NULL = none)
+ * its row is zeroed and its count set to 0 first; then every visible cell is set to 1.  d_new[i] gets the number of cells that went
+ * 0 -> 1 in this call, d_count[i] becomes (cleared ? 0 : d_count[i]) + d_new[i]: the count is carried, never recounted over the grid.
+ * Rows, counts and d_new of envs under a zero mask byte are neither read nor written: the mask wins over clear.  Every cell has one
+ * owner and the counts are integer sums, so the result does not depend on the kernel's schedule.  An env whose extent the grid does not
+ * cover (as for mw_nav_build) gets its row zeroed, count 0 and new 0, and sets a status bit that the next mw_check reports as
+ * MW_E_INVALID, once. */
+#define MW_SEEN_ENTITIES 1       /* flags: listed entities block the line of sight too, as discs of full height */
+/* One kernel, one workgroup per env, asynchronous on `stream`; it reads no host value except host_sight (during the call), reads live
+ * arrays only and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched: a null engine, grid,
+ * host_sight, d_seen or d_count; cell <= 0, gx or gz < 1, more than MW_NAV_MAX_CELLS cells; a range that is not > 0 or not finite; a
+ * cos_half outside -1 .. 1 or NaN; unknown flag bits; more workgroups than a launch holds; an engine whose max_segs and max_ents need
+ * more than 64 KiB of LDS at 48 bytes per segment and 32 per slot beside the kernel's own 2064. */
+int mw_seen_update(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */,
+                   const double *host_sight /* [2] on the host, read during the call: range in metres, cos(fov / 2) or -1 */,
+                   int32_t flags, const uint8_t *d_mask, const uint8_t *d_clear,
+                   uint8_t *d_seen, int32_t *d_count, int32_t *d_new /* or NULL */, void *stream);
+
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.
@@ -804,7 +843,7 @@ int mw_debug_set_ray_form(mw_engine *e, int form);
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where or mw_nav_build skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build or mw_seen_update skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

@@ -9,6 +9,7 @@
 #include "mw_state_view.h"
 #include "mw_nav.h"
 #include "mw_ray.h"
+#include "mw_seen.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -277,6 +278,13 @@ extern "C" __global__ void mw_ray_lanes_kernel(MwRayArgs a, mw_ray_params p, con
 extern "C" __global__ void mw_ray_waves_kernel(MwRayArgs a, mw_ray_params p, const uint8_t *__restrict__ mask, const double *__restrict__ origin,
                                                const double *__restrict__ dir, const double *__restrict__ offsets, double *__restrict__ t_out,
                                                int32_t *__restrict__ hit_out, double *__restrict__ dir_out);
+
+// explored-area maps (mw_seen.hip; the tests, the phases and the launch constants: mw_seen.h; the launch: mwpolicy::seen_launch).  The
+// grid is the caller's mw_nav_params by value (cell, gx, gz are read), the sight its range, cos(fov / 2) and flags.  Grid N workgroups
+// of MW_SEEN_THREADS lanes, max_segs * MW_RAY_WALL_BYTES + E * MW_RAY_DISC_BYTES (rounded up to 16) + MW_SEEN_TAIL_BYTES bytes of
+// dynamic LDS; env b's row of `seen`, count[b] and newly[b] where mask is null or mask[b] != 0; clear and newly may be null.
+extern "C" __global__ void mw_seen_kernel(MwRayArgs a, mw_nav_params p, mwseen::Sight s, const uint8_t *__restrict__ mask, const uint8_t *__restrict__ clear,
+                                          uint8_t *seen, int32_t *__restrict__ count, int32_t *__restrict__ newly);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -7,6 +7,7 @@
 
 #include "../../include/mwengine.h"
 #include "mw_ray.h"             // MW_RAY_THREADS, MW_RAY_WAVES, MW_RAY_WALL_BYTES, MW_RAY_DISC_BYTES
+#include "mw_seen.h"            // MW_SEEN_THREADS, MW_SEEN_TAIL_BYTES
 #include "mw_shape.h"
 #include "mw_snapframes.h"      // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -322,6 +323,16 @@ inline RayLaunch ray_launch(int N, int R, int max_segs, int max_ents, int forced
         return {true, (unsigned long long)N, 64 * (waves < MW_RAY_THREADS / 64 ? waves : MW_RAY_THREADS / 64), lds, lds <= 64 * 1024};
     }
     return {false, ((unsigned long long)N * (unsigned long long)R + MW_RAY_WAVES - 1) / MW_RAY_WAVES, MW_RAY_WAVES * 64, 0, true};
+}
+
+// Explored-area maps (mw_seen_update; kernel: mw_seen.hip): a workgroup of MW_SEEN_THREADS lanes per env.  Its LDS is the ray-per-lane
+// form's staged obstacles, sized from the engine's capacities, and behind them the candidate list and its words (MW_SEEN_TAIL_BYTES);
+// fits: at most 64 KiB, the rule of ray_launch — the caller refuses what does not.
+struct SeenLaunch { unsigned long long grid; int threads; size_t lds; bool fits; };
+inline SeenLaunch seen_launch(int N, int max_segs, int max_ents)
+{
+    const size_t lds = ((size_t)max_segs * MW_RAY_WALL_BYTES + (size_t)max_ents * MW_RAY_DISC_BYTES + 15) / 16 * 16 + MW_SEEN_TAIL_BYTES;
+    return {(unsigned long long)N, MW_SEEN_THREADS, lds, lds <= 64 * 1024};
 }
 
 }  // namespace mwpolicy

@@ -128,6 +128,9 @@ class MwRayParams(C.Structure):
     _fields_ = [("max_t", C.c_double), ("radius", C.c_double), ("rays", C.c_int32), ("flags", C.c_int32)]
 
 
+SEEN_ENTITIES = 1                       # MW_SEEN_ENTITIES
+
+
 class MwPlanTrace(C.Structure):
     _fields_ = [("agent_pos", C.c_void_p), ("agent_dir", C.c_void_p), ("carrying", C.c_void_p), ("ent_pos", C.c_void_p), ("ent_slot", C.c_int32)]
 
@@ -223,6 +226,7 @@ SIGNATURES = {
     "mw_debug_set_nav_passes": _sig(vp, vp),
     "mw_ray_cast": _sig(vp, P(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_ray_form": _sig(vp, C.c_int),
+    "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_launch_shape": _sig(vp, C.c_int, C.c_int, C.c_int, C.c_int),
     "mw_pcg64_draws": _sig(C.c_uint64, i32, vp, vp),
     "mw_selftest_rcp": _sig(vp, vp, vp),
@@ -536,6 +540,25 @@ class Engine:
     def debug_set_ray_form(self, form: int):
         """Measurements: 1 casts every ray count with a ray per lane, 2 with an obstacle per lane, 0 by the ray count again."""
         self._check(self.lib.mw_debug_set_ray_form(self.h, int(form)), "mw_debug_set_ray_form")
+
+    # -- explored-area maps --------------------------------------------------------------
+    def seen_update(self, params: MwNavParams, max_range: float, cos_half: float, flags: int, seen, count, new=None, mask=None, clear=None):
+        """mw_seen_update: for the envs under `mask` (uint8[N], device; None = all) the cells of `seen` (uint8[N, gz, gx], device) each
+        agent sees within `max_range` metres and the cone of cos(fov / 2) = `cos_half` (-1: all round) are set to 1, behind a zeroing
+        of the rows under `clear` (uint8[N], device; None = none); new (int32[N], optional) gets the cells that went 0 -> 1, count
+        (int32[N]) carries their sum.  One kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong
+        tensor is refused before the library is called."""
+        import torch
+        if seen is None or count is None:
+            raise EngineError(f"{'seen' if seen is None else 'count'}: None")
+        self._shaped_tensor(seen, "seen", torch.uint8, (self.N, int(params.gz), int(params.gx)))
+        self._dev_tensor(count, "count", torch.int32, self.N)
+        self._dev_tensor(new, "new", torch.int32, self.N)
+        self._dev_tensor(clear, "clear", torch.uint8, self.N)
+        mask = self._mask_tensor(mask, optional=True)
+        sight = (C.c_double * 2)(float(max_range), float(cos_half))
+        self._check(self.lib.mw_seen_update(self.h, C.byref(params), sight, int(flags), _ptr(mask), _ptr(clear), _ptr(seen), _ptr(count), _ptr(new),
+                                            _stream_ptr(self.device)), "mw_seen_update")
 
     def debug_set_launch_shape(self, waves_per_env: int = 0, mesh_tile_waves: int = 0, ent_blocks: int = 0, slow_waves: int = 0):
         """Tests and measurements: wavefronts per env of the tile kernels (a divisor of the frame's tile count) and the persistent

@@ -49,6 +49,22 @@ class NavField:
         return None if isinstance(self.target, int) else self.target
 
 
+class SeenMap:
+    """An explored-area map (MiniWorldVecEnv.seen_map): `seen`, the uint8[N, gz, gx] device tensor — 1 where the env's agent has had
+    the cell's centre in sight since the row was last cleared —, `count`, int32[N], the cells seen so far, `new`, int32[N], those the
+    last seen_update() added, and the grid (`cell` metres per cell, gx x gz cells from the env's own min_x, min_z: a nav field's).
+    `max_range` (metres), `cos_half` (cos(fov / 2); -1: all round) and `obstacles` say what sight is.  The tensors are the caller's,
+    like a nav field's: the engine keeps nothing of them, and a fork indexes them with its own `src`."""
+
+    def __init__(self, seen, count, new, params, max_range, cos_half, obstacles):
+        self.seen, self.count, self.new, self.params = seen, count, new, params
+        self.max_range, self.cos_half, self.obstacles = max_range, cos_half, obstacles
+
+    cell = property(lambda self: self.params.cell)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+
+
 _KIND = {
     "MiniWorld-Hallway-v0": ("Hallway", eng.GEN_HALLWAY, eng.TASK_GOTO, 3),
     "MiniWorld-OneRoom-v0": ("OneRoom", eng.GEN_ONEROOM, eng.TASK_GOTO, 3),
@@ -1045,6 +1061,83 @@ class MiniWorldVecEnv:
         e.nav_query(field.params, field.field, field.points, pos, b["cost"], b["next"], b["waypoint"])
         dist = torch.where(b["cost"] < 0, float("inf"), b["cost"].to(torch.float32) * (field.cell / 5.0)).to(torch.float32)
         return {"cost": b["cost"], "next": b["next"], "waypoint": b["waypoint"], "distance": dist}
+
+    # ------------------------------------------------------------------ explored-area maps
+    SEEN_OBSTACLES = {"walls": 0, "walls+entities": eng.SEEN_ENTITIES}
+
+    def default_fov(self):
+        """The horizontal field of view of the default camera in radians: 2 atan(tan(fov_y / 2) * width / height) from the vertical
+        field of view the env's parameters default to (cam_fov_y, 60 degrees) and the observation's aspect."""
+        cfg = self.engine.cfg
+        return 2.0 * math.atan(math.tan(math.radians(float(cfg.cam_fov_y.default)) / 2.0) * float(cfg.obs_width) / float(cfg.obs_height))
+
+    def seen_map(self, cell=0.25, max_range=10.0, fov=None, obstacles="walls", like=None):
+        """An empty explored-area map over each env's floor plan: a SeenMap, which seen_update() fills.
+
+        cell       metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
+        like       a NavField whose grid (cell, gx, gz) the map adopts, so that map and field line up cell for cell; pass no cell then
+        max_range  how far the agent sees, in metres
+        fov        the horizontal opening angle of sight in radians, 0 < fov <= 2 pi, about the agent's heading; None: default_fov(),
+                   the horizontal field of view of the default camera — the vertical field of view the parameters default to and
+                   the observation's aspect, so that a cell is seen when the frame could show its floor point.  2 pi: all round.
+        obstacles  "walls", or "walls+entities": every listed entity but the carried one blocks the line of sight too, as a disc of
+                   full height
+        A cell counts as seen once its centre is within max_range and the cone and the straight line from the agent to it meets no
+        obstacle (include/mwengine.h, "explored-area maps").  ValueError for arguments that make no map; nothing is launched."""
+        torch, e = self.torch, self.engine
+        if obstacles not in self.SEEN_OBSTACLES:
+            raise ValueError(f"seen_map: obstacles {obstacles!r}; have {sorted(self.SEEN_OBSTACLES)}")
+        if not (isinstance(max_range, (int, float)) and not isinstance(max_range, bool) and max_range > 0 and math.isfinite(max_range)):
+            raise ValueError(f"seen_map: max_range {max_range!r} must be a positive finite length")
+        fov = self.default_fov() if fov is None else fov
+        if not (isinstance(fov, (int, float)) and not isinstance(fov, bool) and 0 < fov <= 2 * math.pi):
+            raise ValueError(f"seen_map: fov {fov!r} outside 0 .. 2 pi radians")
+        cos_half = -1.0 if fov == 2 * math.pi else math.cos(fov / 2)
+        if like is not None:
+            if not isinstance(like, NavField):
+                raise ValueError("seen_map: `like` must be a NavField")
+            if cell != 0.25:
+                raise ValueError("seen_map: with `like` the field's own grid is used: pass no cell")
+            cell, gx, gz = like.cell, like.gx, like.gz
+        else:
+            if not (isinstance(cell, (int, float)) and not isinstance(cell, bool) and cell > 0 and math.isfinite(cell)):
+                raise ValueError(f"seen_map: cell {cell!r} must be a positive length")
+            t = self.template
+            gx = max(1, math.ceil((float(t.max_x) - float(t.min_x)) / cell))
+            gz = max(1, math.ceil((float(t.max_z) - float(t.min_z)) / cell))
+            if gx * gz > eng.NAV_MAX_CELLS:
+                raise ValueError(f"seen_map: {gx} x {gz} cells > {eng.NAV_MAX_CELLS}: use a larger cell")
+        params = eng.MwNavParams(float(cell), 0.0, 0.0, int(gx), int(gz), 0, 0)
+        n = self.num_envs
+        return SeenMap(torch.zeros((n, int(gz), int(gx)), dtype=torch.uint8, device=e.device), torch.zeros(n, dtype=torch.int32, device=e.device),
+                       torch.zeros(n, dtype=torch.int32, device=e.device), params, float(max_range), float(cos_half), obstacles)
+
+    def _seen_flags(self, t, what):
+        """seen_update's clear and mask: None, or a uint8 / bool [N] tensor on the device; a bool is copied over as bytes"""
+        torch = self.torch
+        if t is None:
+            return None
+        if (not torch.is_tensor(t) or tuple(t.shape) != (self.num_envs,) or t.dtype not in (torch.uint8, torch.bool) or t.device != self.engine.device):
+            raise ValueError(f"seen_update: {what} is a uint8 or bool tensor [{self.num_envs}] on {self.engine.device}")
+        return self._copied_mask(t) if t.dtype == torch.bool else t
+
+    def seen_update(self, seen, clear=None, mask=None):
+        """Marks the cells each env's agent sees from where it stands now in `seen` (a SeenMap), by one kernel (mw_seen_update) with no
+        host value and no synchronisation; returns seen.new, int32[N], the cells that became seen in this call, while seen.count
+        carries the total.
+
+        clear  uint8[N] or bool[N] device tensor: those envs' rows are zeroed and their counts restarted first.  Behind a step of the
+               same-step auto-reset `seen_update(m, clear=terminated | truncated)` starts the map of every new episode with the
+               first pose of its world.
+        mask   uint8[N] or bool[N] device tensor: only those envs are updated; the rows, counts and `new` of the others are neither
+               read nor written, whatever `clear` says.
+        An env whose extent the grid does not cover gets its row zeroed and engine.check() raises once.  Tensors are checked, never
+        converted: a SeenMap whose tensors were replaced by ones of another shape, dtype or device is refused (EngineError)."""
+        if not isinstance(seen, SeenMap):
+            raise ValueError("seen_update: `seen` must be a SeenMap (seen_map())")
+        clear, mask = self._seen_flags(clear, "clear"), self._seen_flags(mask, "mask")
+        self.engine.seen_update(seen.params, seen.max_range, seen.cos_half, self.SEEN_OBSTACLES[seen.obstacles], seen.seen, seen.count, seen.new, mask, clear)
+        return seen.new
 
     # ------------------------------------------------------------------ ray casts
     RAY_OBSTACLES = {"walls": 0, "walls+entities": eng.RAY_ENTITIES}

@@ -74,7 +74,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
                  frame_reuse: bool = True, frame_cache: int = 4, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset",
-                 levels=None, level_generator=None, reset_seeds=None, info_state=None, **kwargs):
+                 levels=None, level_generator=None, reset_seeds=None, info_state=None, seen_map=None, **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
         False draws every env on every step, for consumers that write into the returned observation tensor (module docstring).
@@ -93,7 +93,14 @@ class MiniWorldVectorEnv(VectorEnvBase):
         step() and reset() adds them to info as arrays over the batch, filled by one gather kernel behind the step; None (the
         default) adds nothing.  The rows show the state the device holds, as the other info keys do: for an env whose episode ended
         with the step that is its next episode's first state under the same-step auto-reset, the terminal state under next-step.
-        Copies: they stay valid after the next step."""
+        Copies: they stay valid after the next step.
+        seen_map: a dict of MiniWorldVecEnv.seen_map()'s arguments (an empty one for its defaults) — every step() marks what each agent
+        sees from its new pose in an explored-area map on the device (`self.seen`, a SeenMap) and adds info["seen_new"] (int32[N], the
+        cells that became seen with this step: a coverage reward) and info["seen_count"] (int32[N], the cells seen so far in the
+        episode); the map of an env whose episode ended restarts with the first pose of its next one (under next-step with the reset
+        step), and reset() restarts every map.  None (the default) adds nothing and calls nothing."""
+        if seen_map is not None and not isinstance(seen_map, dict):
+            raise ValueError(f"seen_map: need a dict of MiniWorldVecEnv.seen_map()'s arguments or None, not {seen_map!r}")
         if not isinstance(action_repeat, (int, np.integer)) or not 1 <= action_repeat <= 256:
             raise ValueError(f"action_repeat must be an integer in 1 .. 256, not {action_repeat!r}")
         self.action_repeat = int(action_repeat)
@@ -135,6 +142,8 @@ class MiniWorldVectorEnv(VectorEnvBase):
             self._first_next_seed = self.vec.torch.from_numpy(first.astype(np.int64)).to(self.vec.engine.device)
             self.vec.next_seed.copy_(self._first_next_seed)
         self._played_seed = None
+        self.seen = None if seen_map is None else self.vec.seen_map(**seen_map)
+        self._seen_clear = None         # next-step: the envs whose next step is their reset step
         if levels is not None:
             from .vec_env import EnvSnapshot
             self.vec.set_levels(levels if isinstance(levels, EnvSnapshot) else self.vec.make_levels(levels), level_generator)
@@ -167,13 +176,29 @@ class MiniWorldVectorEnv(VectorEnvBase):
                 info[k] = self._out(v) if self.to_numpy else v.clone()
         return info
 
+    def _seen_info(self, info, done, all_new):
+        """seen_map: one seen_update() behind the step or reset; copies of the map's counters (they are rewritten by the next step)"""
+        if self.seen is not None:
+            torch = self.vec.torch
+            if all_new:
+                clear = torch.ones(self.num_envs, dtype=torch.uint8, device=self.vec.engine.device)
+            elif self.vec.autoreset_mode == "next_step":
+                clear = self._seen_clear
+            else:
+                clear = done.to(torch.uint8) if self.vec.autoreset_mode != "off" else None
+            self._seen_clear = None if all_new else done.to(torch.uint8)
+            self.vec.seen_update(self.seen, clear=clear)
+            info["seen_new"] = self._out(self.seen.new) if self.to_numpy else self.seen.new.clone()
+            info["seen_count"] = self._out(self.seen.count) if self.to_numpy else self.seen.count.clone()
+        return info
+
     def reset(self, *, seed: int | None = None, options: dict | None = None):
         """Env i is seeded with seed + i (gymnasium's convention for an integer seed); with levels= every env starts a level of the
         bank and the seed is not used."""
         obs = self.vec.reset(seed)
         if self._first_next_seed is not None:       # (reset() lays out seed + N + i; the caller's first choices stand)
             self.vec.next_seed.copy_(self._first_next_seed)
-        return self._out(self._obs(obs)), self._state_info({})
+        return self._out(self._obs(obs)), self._state_info(self._seen_info({}, None, True))
 
     def step(self, actions):
         torch = self.vec.torch
@@ -206,6 +231,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
             info["level"] = self._out(self.vec.played_level) if self.to_numpy else self.vec.played_level.clone()
         if self.vec.autoreset_mode == "seeds":
             info["seed"] = self._out(self._played_seed) if self.to_numpy else self._played_seed.clone()
+        self._seen_info(info, term | trunc, False)
         self._state_info(info)
         return self._out(self._obs(obs)), self._out(rew), self._out(term.bool()), self._out(trunc.bool()), info
 
