@@ -672,10 +672,7 @@ int mw_visible_ents(mw_engine *e, int32_t first_env, int32_t count, uint8_t *d_v
         const int L = geom_lanes_of(e);
         hipLaunchKernelGGL(geom_kernel_of(L, e->cfg.msaa).plain, dim3(env_blocks(count, L)), dim3(64), 0, st, b, 4, e->cfg.msaa, L, count, (const uint64_t *)nullptr, 0, (uint8_t *)nullptr);
     }
-    if (!e->visible_attr_set) {
-        HIP_TRY(e, hipFuncSetAttribute((const void *)mw_visible_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        e->visible_attr_set = true;
-    }
+    if (const int rc = allow_dynamic_lds(e, mw_visible_kernel, e->visible_lds_set, lds)) return rc;
     hipLaunchKernelGGL(mw_visible_kernel, dim3(count), dim3(256), lds, st, first_env, e->cfg.obs_width, e->cfg.obs_height,
                        e->cfg.msaa, b.max_vis, e->cfg.max_ents, (const float *)b.rec_raster, (const float *)b.rec_cull, (const int32_t *)b.nvis, d_vis);
     HIP_TRY(e, hipGetLastError());

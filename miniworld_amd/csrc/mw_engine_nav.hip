@@ -1,10 +1,6 @@
 // mwengine host runtime: navigation fields (mw_nav_build, mw_nav_query; kernels: mw_nav.hip, arithmetic: mw_nav.h).
 //
-// Neither call waits for the Maze's side-stream refills (refill_order), for the reason given at mw_get_state_device (mw_engine.hip):
-// the refill kernel generates into the spare arrays — the spare's own segs / nsegs, extent and entity slabs among them — and touches
-// the env's random stream and refill_mask beside them; the live segs, nsegs, extent, ekind, epos, egeom, carry and agent position that
-// these kernels read are written on the caller's stream alone (K1's take-over of a spare, the resets, the state writes), behind which
-// the call is ordered by being on that stream.
+// Neither call waits for the Maze's side-stream refills: mw_engine.h, at world_view().
 #include "mw_engine.h"
 
 using namespace mwhost;
@@ -14,20 +10,11 @@ namespace {
 int nav_args(mw_engine *e, const char *what, const mw_nav_params *p, const double *d_target, const void *d_field)
 {
     if (!p || !d_field) return fail(e, MW_E_INVALID, "%s: %s is null", what, p ? "d_field" : "params");
-    if (!(p->cell > 0.0)) return fail(e, MW_E_INVALID, "%s: cell %g <= 0", what, p->cell);
-    if (p->gx < 1 || p->gz < 1) return fail(e, MW_E_INVALID, "%s: a grid of %d x %d cells", what, (int)p->gx, (int)p->gz);
-    if ((long long)p->gx * (long long)p->gz > MW_NAV_MAX_CELLS)
-        return fail(e, MW_E_INVALID, "%s: %d x %d cells > %d (the grid lives in LDS): use a larger cell", what, (int)p->gx, (int)p->gz, MW_NAV_MAX_CELLS);
+    if (const int rc = grid_check(e, what, p, " (the grid lives in LDS)")) return rc;
     if (!(p->margin >= 0.0)) return fail(e, MW_E_INVALID, "%s: margin %g < 0", what, p->margin);
     if (p->target_slot < 0 || p->target_slot >= e->cfg.max_ents) return fail(e, MW_E_INVALID, "%s: target slot %d outside 0 .. %d", what, (int)p->target_slot, e->cfg.max_ents - 1);
     if (d_target && !(p->reach > 0.0)) return fail(e, MW_E_INVALID, "%s: reach %g <= 0 with point targets", what, p->reach);
     return MW_OK;
-}
-
-MwNavArgs nav_args_of(const mw_engine *e)
-{
-    const MwArgs &a = e->args;
-    return {a.segs, a.nsegs, a.extent, a.ekind, a.epos, a.egeom, a.carry, a.ax, a.az, a.status, a.N, a.E, a.max_segs, a.shared_geom, a.agent_radius, a.max_forward_step};
 }
 
 }  // namespace
@@ -40,11 +27,8 @@ int mw_nav_build(mw_engine *e, const mw_nav_params *params, const uint8_t *d_mas
     if (const int rc = nav_args(e, "mw_nav_build", params, d_target, d_field)) return rc;
     ON_DEVICE(e);
     const int lds = (int)((size_t)params->gx * params->gz * sizeof(uint16_t) + 15) / 16 * 16;
-    if (lds > e->nav_lds_set) {
-        HIP_TRY(e, hipFuncSetAttribute((const void *)mw_nav_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        e->nav_lds_set = lds;
-    }
-    hipLaunchKernelGGL(mw_nav_build_kernel, dim3((unsigned)e->cfg.num_envs), dim3(MW_NAV_THREADS), (size_t)lds, (hipStream_t)stream, nav_args_of(e), *params,
+    if (const int rc = allow_dynamic_lds(e, mw_nav_build_kernel, e->nav_lds_set, lds)) return rc;
+    hipLaunchKernelGGL(mw_nav_build_kernel, dim3((unsigned)e->cfg.num_envs), dim3(MW_NAV_THREADS), (size_t)lds, (hipStream_t)stream, world_view(e), *params,
                        d_mask, d_target, d_field, e->nav_passes);
     HIP_TRY(e, hipGetLastError());
     return MW_OK;
@@ -58,7 +42,7 @@ int mw_nav_query(mw_engine *e, const mw_nav_params *params, const double *d_targ
     ON_DEVICE(e);
     const int N = e->cfg.num_envs;
     hipLaunchKernelGGL(mw_nav_query_kernel, dim3((unsigned)((N + MW_NAV_QUERY_THREADS - 1) / MW_NAV_QUERY_THREADS)), dim3(MW_NAV_QUERY_THREADS), 0,
-                       (hipStream_t)stream, nav_args_of(e), *params, d_target, d_field, d_pos, d_cost, d_next, d_waypoint);
+                       (hipStream_t)stream, world_view(e), *params, d_target, d_field, d_pos, d_cost, d_next, d_waypoint);
     HIP_TRY(e, hipGetLastError());
     return MW_OK;
 }

@@ -1,10 +1,6 @@
 // mwengine host runtime: ray casts (mw_ray_cast; kernels: mw_ray.hip, arithmetic: mw_ray.h, launch form: mw_policy.h).
 //
-// Like the nav calls (mw_engine_nav.hip), and for the reason given there word for word, the call does not wait for the Maze's
-// side-stream refills: the refill kernel generates into the spare arrays — the spare's own segs / nsegs, extent and entity slabs among
-// them — and touches the env's random stream and refill_mask beside them; the live segs, nsegs, ekind, epos, egeom, carry and agent pose
-// that these kernels read are written on the caller's stream alone (K1's take-over of a spare, the resets, the state writes), behind
-// which the call is ordered by being on that stream.
+// The call does not wait for the Maze's side-stream refills: mw_engine.h, at world_view().
 #include <math.h>
 
 #include "mw_engine.h"
@@ -30,14 +26,9 @@ int mw_ray_cast(mw_engine *e, const mw_ray_params *params, const uint8_t *d_mask
     if (!l.fits) return fail(e, MW_E_INVALID, "%s: %d segments and %d slots need %zu bytes of LDS > 64 KiB", what, a.max_segs, a.E, l.lds);
     if (mwpolicy::grid_too_large(l.grid)) return fail(e, MW_E_INVALID, "%s: %llu workgroups", what, l.grid);
     ON_DEVICE(e);
-    const MwRayArgs ra{{a.segs, a.nsegs, a.extent, a.ekind, a.epos, a.egeom, a.carry, a.ax, a.az, a.status, a.N, a.E, a.max_segs, a.shared_geom, a.agent_radius,
-                        a.max_forward_step},
-                       a.adir};
+    const MwRayArgs ra = ray_view(e);
     if (l.per_lane) {
-        if ((int)l.lds > e->ray_lds_set) {
-            HIP_TRY(e, hipFuncSetAttribute((const void *)mw_ray_lanes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
-            e->ray_lds_set = (int)l.lds;
-        }
+        if (const int rc = allow_dynamic_lds(e, mw_ray_lanes_kernel, e->ray_lds_set, l.lds)) return rc;
         hipLaunchKernelGGL(mw_ray_lanes_kernel, dim3((unsigned)l.grid), dim3((unsigned)l.threads), l.lds, (hipStream_t)stream, ra, *params, d_mask, d_origin, d_dir,
                            d_offsets, d_t, d_hit, d_dir_out);
     } else {

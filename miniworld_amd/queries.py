@@ -1,0 +1,270 @@
+"""The world queries of the batched env — navigation fields, explored-area maps, ray casts —, each one kernel on the device with no
+host value: their value classes (NavField, SeenMap) and `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import engine as eng
+from ._args import integer, real
+
+
+class NavField:
+    """A navigation field (MiniWorldVecEnv.nav_field): `field`, the uint16[N, gz, gx] device tensor of shortest-path costs — 0xFFFF a
+    blocked cell, 0xFFFE one no path reaches, a move costs 5 straight and 7 diagonally —, the grid (`cell` metres per cell, gx x gz
+    cells from the env's own min_x, min_z), and what it leads to: `target`, an entity slot or a float64[N, 3] device tensor.  The
+    tensor is the caller's, like a level bank: the engine keeps nothing of it."""
+
+    def __init__(self, field, params, target, obstacles):
+        self.field, self.params, self.target, self.obstacles = field, params, target, obstacles
+
+    cell = property(lambda self: self.params.cell)
+    margin = property(lambda self: self.params.margin)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+
+    @property
+    def points(self):
+        """the device tensor of point targets, or None for a slot target"""
+        return None if isinstance(self.target, int) else self.target
+
+
+class SeenMap:
+    """An explored-area map (MiniWorldVecEnv.seen_map): `seen`, the uint8[N, gz, gx] device tensor — 1 where the env's agent has had
+    the cell's centre in sight since the row was last cleared —, `count`, int32[N], the cells seen so far, `new`, int32[N], those the
+    last seen_update() added, and the grid (`cell` metres per cell, gx x gz cells from the env's own min_x, min_z: a nav field's).
+    `max_range` (metres), `cos_half` (cos(fov / 2); -1: all round) and `obstacles` say what sight is.  The tensors are the caller's,
+    like a nav field's: the engine keeps nothing of them, and a fork indexes them with its own `src`."""
+
+    def __init__(self, seen, count, new, params, max_range, cos_half, obstacles):
+        self.seen, self.count, self.new, self.params = seen, count, new, params
+        self.max_range, self.cos_half, self.obstacles = max_range, cos_half, obstacles
+
+    cell = property(lambda self: self.params.cell)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+
+
+assert eng.NAV_ENTITIES == eng.RAY_ENTITIES == eng.SEEN_ENTITIES      # (one table serves the three calls)
+
+
+class WorldQueries:
+    OBSTACLES = {"walls": 0, "walls+entities": eng.NAV_ENTITIES}
+
+    def _obstacle_flags(self, where, obstacles):
+        """the engine's flag bits of an `obstacles` name"""
+        if obstacles not in self.OBSTACLES:
+            raise ValueError(f"{where}: obstacles {obstacles!r}; have {sorted(self.OBSTACLES)}")
+        return self.OBSTACLES[obstacles]
+
+    def _grid(self, where, cell):
+        """(cell, gx, gz): the grid of `cell` metres per cell over the template world's extent, which the family's constructor arguments fix"""
+        cell, t = real(where, "cell", cell), self.template
+        gx = max(1, math.ceil((float(t.max_x) - float(t.min_x)) / cell))
+        gz = max(1, math.ceil((float(t.max_z) - float(t.min_z)) / cell))
+        if gx * gz > eng.NAV_MAX_CELLS:
+            raise ValueError(f"{where}: {gx} x {gz} cells > {eng.NAV_MAX_CELLS}: use a larger cell")
+        return cell, gx, gz
+
+    def nav_field(self, target=None, mask=None, cell=0.25, obstacles="walls", margin=None, reach=None, into=None):
+        """The shortest-path cost to a target from every cell of a grid over each env's floor plan, walls in the way, built on the
+        device by one kernel (mw_nav_build) with no host value and no synchronisation: a NavField.
+
+        target     None: the env's goal entity (cfg.goal_ent); an int: that entity slot — the field starts from the cells where the
+                   env's own near() test would hold —; or a float64[N, 3] device tensor of points with `reach` metres around them
+        cell       metres per cell; gx, gz follow from the template world's extent, which the family's constructor arguments fix
+        obstacles  "walls", or "walls+entities": every listed entity but the target and the carried one blocks cells too
+        margin     kept from walls beyond the agent's radius; default cell / 2
+        mask       uint8[N] or bool[N] device tensor: only those envs' rows are built (the others are not touched)
+        into       a NavField of this call's parameters to rebuild in place — `nav_field(into=field, mask=done)` behind a step keeps
+                   the field current across auto-resets; without it a new tensor is allocated (unmasked rows: 0xFFFF)
+        An env whose extent the grid does not cover, or one whose costs do not fit 16 bits, gets a row of 0xFFFF and engine.check()
+        raises once.  ValueError for arguments that make no field; nothing is launched then."""
+        torch, e = self.torch, self.engine
+        if into is not None:
+            if not isinstance(into, NavField):
+                raise ValueError("nav_field: `into` must be a NavField")
+            if target is not None or margin is not None or reach is not None or (cell, obstacles) != (0.25, "walls"):
+                raise ValueError("nav_field: with `into` the field's own target and parameters are used: pass only mask")
+            field, params, target = into.field, into.params, into.target
+        else:
+            flags = self._obstacle_flags("nav_field", obstacles)
+            cell, gx, gz = self._grid("nav_field", cell)
+            margin = cell / 2 if margin is None else real("nav_field", "margin", margin, lo_open=False)
+            if target is None:
+                target = int(e.cfg.goal_ent)
+                if target < 0:
+                    raise ValueError("nav_field: this env has no goal entity: name a target slot or points")
+            if torch.is_tensor(target):
+                if not self._is_tensor(target, (self.num_envs, 3)):
+                    raise ValueError(f"nav_field: point targets are a contiguous float64 tensor [{self.num_envs}, 3] on {e.device}")
+                reach = real("nav_field", "reach (point targets need one)", reach)
+            elif isinstance(target, (int, np.integer)) and not isinstance(target, bool):
+                target = integer("nav_field", "target slot", target, 0, e.cfg.max_ents - 1)
+                if reach is not None:
+                    raise ValueError("nav_field: a slot target's reach is the env's own near() distance: pass no reach")
+            else:
+                raise ValueError(f"nav_field: target is None, an entity slot or a float64[N, 3] device tensor, not {type(target).__name__}")
+            params = eng.MwNavParams(cell, margin, reach or 0.0, gx, gz, flags, target if isinstance(target, int) else 0)
+            # (0xFFFF throughout; filled as int16: the 16-bit unsigned type has few kernels of its own)
+            field = torch.full((self.num_envs, gz, gx), -1, dtype=torch.int16, device=e.device).view(torch.uint16)
+        mask = self._device_mask(mask, "nav_field")
+        out = into if into is not None else NavField(field, params, target, obstacles)
+        e.nav_build(params, field, mask, out.points)
+        return out
+
+    def nav_query(self, field, pos=None):
+        """Where each env's agent — or row i of `pos`, float64[N, 3] on the device — stands in `field` (a NavField), by one small
+        kernel (mw_nav_query), no host value: {"cost": int32[N], the cell's cost, -1 where no path leads to the target; "next":
+        int32[N], the flat index j * gx + i of the neighbouring cell to go to (-1 without a path); "waypoint": float64[N, 2], that
+        cell's centre x, z — the target's own x, z once the cell is a source —; "distance": float32[N], cost * cell / 5 in metres,
+        inf where there is no path}.  The distance is the grid's metric — straight and diagonal moves of 5 and 7 — which
+        over-estimates the Euclidean geodesic by up to 8 % and is exact along the axes.  A position in a blocked cell (an agent may
+        stand closer to a wall than the field's margin) is answered from the best unblocked cell around it.  The tensors are this
+        env's own, reused between calls."""
+        torch, e = self.torch, self.engine
+        if not isinstance(field, NavField):
+            raise ValueError("nav_query: `field` must be a NavField (nav_field())")
+        if pos is not None and not self._is_tensor(pos, (self.num_envs, 3)):
+            raise ValueError(f"nav_query: pos is a contiguous float64 tensor [{self.num_envs}, 3] on {e.device}")
+        n = self.num_envs
+        b = {name: self._buffer(name, shape, dtype, self._nav_bufs)
+             for name, shape, dtype in (("cost", (n,), torch.int32), ("next", (n,), torch.int32), ("waypoint", (n, 2), torch.float64))}
+        e.nav_query(field.params, field.field, field.points, pos, b["cost"], b["next"], b["waypoint"])
+        dist = torch.where(b["cost"] < 0, float("inf"), b["cost"].to(torch.float32) * (field.cell / 5.0)).to(torch.float32)
+        return {"cost": b["cost"], "next": b["next"], "waypoint": b["waypoint"], "distance": dist}
+
+    # ------------------------------------------------------------------ explored-area maps
+    def default_fov(self):
+        """The horizontal field of view of the default camera in radians: 2 atan(tan(fov_y / 2) * width / height) from the vertical
+        field of view the env's parameters default to (cam_fov_y, 60 degrees) and the observation's aspect."""
+        cfg = self.engine.cfg
+        return 2.0 * math.atan(math.tan(math.radians(float(cfg.cam_fov_y.default)) / 2.0) * float(cfg.obs_width) / float(cfg.obs_height))
+
+    def seen_map(self, cell=0.25, max_range=10.0, fov=None, obstacles="walls", like=None):
+        """An empty explored-area map over each env's floor plan: a SeenMap, which seen_update() fills.
+
+        cell       metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
+        like       a NavField whose grid (cell, gx, gz) the map adopts, so that map and field line up cell for cell; pass no cell then
+        max_range  how far the agent sees, in metres
+        fov        the horizontal opening angle of sight in radians, 0 < fov <= 2 pi, about the agent's heading; None: default_fov(),
+                   the horizontal field of view of the default camera — the vertical field of view the parameters default to and
+                   the observation's aspect, so that a cell is seen when the frame could show its floor point.  2 pi: all round.
+        obstacles  "walls", or "walls+entities": every listed entity but the carried one blocks the line of sight too, as a disc of
+                   full height
+        A cell counts as seen once its centre is within max_range and the cone and the straight line from the agent to it meets no
+        obstacle (include/mwengine.h, "explored-area maps").  ValueError for arguments that make no map; nothing is launched."""
+        torch, e = self.torch, self.engine
+        self._obstacle_flags("seen_map", obstacles)
+        max_range = real("seen_map", "max_range", max_range)
+        fov = self.default_fov() if fov is None else real("seen_map", "fov", fov, hi=2 * math.pi)
+        cos_half = -1.0 if fov == 2 * math.pi else math.cos(fov / 2)
+        if like is not None:
+            if not isinstance(like, NavField):
+                raise ValueError("seen_map: `like` must be a NavField")
+            if cell != 0.25:
+                raise ValueError("seen_map: with `like` the field's own grid is used: pass no cell")
+            cell, gx, gz = like.cell, like.gx, like.gz
+        else:
+            cell, gx, gz = self._grid("seen_map", cell)
+        params = eng.MwNavParams(float(cell), 0.0, 0.0, int(gx), int(gz), 0, 0)
+        n = self.num_envs
+        return SeenMap(torch.zeros((n, int(gz), int(gx)), dtype=torch.uint8, device=e.device), torch.zeros(n, dtype=torch.int32, device=e.device),
+                       torch.zeros(n, dtype=torch.int32, device=e.device), params, max_range, float(cos_half), obstacles)
+
+    def seen_update(self, seen, clear=None, mask=None):
+        """Marks the cells each env's agent sees from where it stands now in `seen` (a SeenMap), by one kernel (mw_seen_update) with no
+        host value and no synchronisation; returns seen.new, int32[N], the cells that became seen in this call, while seen.count
+        carries the total.
+
+        clear  uint8[N] or bool[N] device tensor: those envs' rows are zeroed and their counts restarted first.  Behind a step of the
+               same-step auto-reset `seen_update(m, clear=terminated | truncated)` starts the map of every new episode with the
+               first pose of its world.
+        mask   uint8[N] or bool[N] device tensor: only those envs are updated; the rows, counts and `new` of the others are neither
+               read nor written, whatever `clear` says.
+        An env whose extent the grid does not cover gets its row zeroed and engine.check() raises once.  Tensors are checked, never
+        converted: a SeenMap whose tensors were replaced by ones of another shape, dtype or device is refused (EngineError)."""
+        if not isinstance(seen, SeenMap):
+            raise ValueError("seen_update: `seen` must be a SeenMap (seen_map())")
+        clear, mask = self._device_mask(clear, "seen_update", "clear"), self._device_mask(mask, "seen_update")
+        self.engine.seen_update(seen.params, seen.max_range, seen.cos_half, self.OBSTACLES[seen.obstacles], seen.seen, seen.count, seen.new, mask, clear)
+        return seen.new
+
+    # ------------------------------------------------------------------ ray casts
+    def raycast(self, direction=None, origin=None, offsets=None, max_t=1.0, radius=0.0, obstacles="walls", mask=None, into=None):
+        """What R rays per env meet first in the env's collision world, by one kernel (mw_ray_cast) with no host value and no
+        synchronisation: {"t": float64[N, R], "hit": int32[N, R]} and, with `offsets`, "dir": float64[N, R, 2].
+
+        Ray k of env i is origin + t * direction, t in 0 .. max_t; "t" is the smallest t at which it meets an obstacle and "hit" which
+        one — a wall's segment index, engine.RAY_ENT + slot for an entity —, max_t and -1 where it meets none.  With unit directions t
+        is metres; with direction = B - A and max_t = 1, t < 1 says that something is in the way from A to B.
+        direction  float64[N, R, 2] device tensor of (dx, dz), any length; or
+        offsets    float64[R] device tensor of angles in radians added to each agent's heading (a fan; "dir" returns the directions)
+        origin     float64[N, R, 3] device tensor (y is not read); None: each env's agent position for all its rays
+        radius     0 a ray; > 0 a disc of that radius swept along it (a wall is a capsule, an entity's circle grows by it)
+        obstacles  "walls", or "walls+entities": every listed entity but the carried one too
+        mask       uint8[N] or bool[N] device tensor: only those envs' rows are read and written
+        into       a previous result of the same R (and mode) to write into; without it new tensors are allocated (unmasked rows:
+                   t = max_t, hit = -1, dir = 0)
+        A NaN in a ray gives max_t and -1; nothing raises on the device.  ValueError for arguments that make no cast; nothing is
+        launched then."""
+        torch, e = self.torch, self.engine
+        n = self.num_envs
+        if (direction is None) == (offsets is None):
+            raise ValueError("raycast: give exactly one of direction (float64[N, R, 2]) and offsets (float64[R])")
+        ok = self._is_tensor
+        if offsets is not None:
+            if not ok(offsets, (None,)):
+                raise ValueError(f"raycast: offsets is a contiguous float64 tensor [R] on {e.device}")
+            rays = int(offsets.shape[0])
+        else:
+            if not ok(direction, (n, None, 2)):
+                raise ValueError(f"raycast: direction is a contiguous float64 tensor [{n}, R, 2] on {e.device}")
+            rays = int(direction.shape[1])
+        if not 1 <= rays <= eng.RAY_MAX:
+            raise ValueError(f"raycast: {rays} rays per env outside 1 .. {eng.RAY_MAX}")
+        if origin is not None and not ok(origin, (n, rays, 3)):
+            raise ValueError(f"raycast: origin is a contiguous float64 tensor [{n}, {rays}, 3] on {e.device}")
+        max_t, radius = real("raycast", "max_t", max_t), real("raycast", "radius", radius, lo_open=False)
+        flags = self._obstacle_flags("raycast", obstacles)
+        mask = self._device_mask(mask, "raycast")
+        # the result's tensors: name -> (dtype, shape, what an unmasked row holds)
+        want = {"t": (torch.float64, (n, rays), max_t), "hit": (torch.int32, (n, rays), -1)}
+        if offsets is not None:
+            want["dir"] = (torch.float64, (n, rays, 2), 0.0)
+        keys = tuple(want)
+        if into is not None:
+            if not isinstance(into, dict) or set(into) != set(keys):
+                raise ValueError(f"raycast: `into` is a previous result with the keys {keys}")
+            for k, (dtype, shape, _) in want.items():
+                if not ok(into[k], shape, dtype):
+                    raise ValueError(f"raycast: into[{k!r}] is a contiguous {dtype} tensor {list(shape)} on {e.device}")
+        out = into or {k: torch.full(shape, fill, dtype=dtype, device=e.device) for k, (dtype, shape, fill) in want.items()}
+        params = eng.MwRayParams(max_t, radius, rays, flags)
+        e.ray_cast(params, out["t"], out["hit"], out.get("dir"), mask, origin, direction, offsets)
+        return out
+
+    def lidar(self, rays=64, fov=2 * math.pi, max_range=10.0, radius=0.0, obstacles="walls+entities"):
+        """A range sensor: `rays` distances in a fan around each agent's heading, by one kernel — raycast() with evenly spaced
+        offsets, built once per (rays, fov) and kept on the device, unit directions and max_t = max_range.  Returns {"t":
+        float64[N, rays], the range in metres (max_range where nothing is hit); "hit": int32[N, rays]; "dir": float64[N, rays, 2], the
+        rays' unit directions (x, z), so that agent_pos + t * dir is the point hit}; the tensors are this env's own, reused between
+        calls of the same (rays, fov).
+
+        For fov < 2 pi offset k = -fov / 2 + k * fov / (rays - 1) (a single ray looks straight ahead); for the full circle offset
+        k = k * 2 pi / rays.  A positive offset turns the ray the way `turn_left` turns the agent: the heading grows, and the agent
+        looks along (cos dir, -sin dir) in (x, z) — ray 0 of a fov < 2 pi is the rightmost one, the last the leftmost."""
+        torch, e = self.torch, self.engine
+        rays, fov = integer("lidar", "rays", rays, 1, eng.RAY_MAX), real("lidar", "fov", fov, hi=2 * math.pi)
+        key = (rays, fov)
+        if key not in self._lidar_bufs:
+            if fov < 2 * math.pi:
+                off = [0.0] if rays == 1 else [-fov / 2 + k * fov / (rays - 1) for k in range(rays)]
+            else:
+                off = [k * 2 * math.pi / rays for k in range(rays)]
+            self._lidar_bufs[key] = [torch.tensor(off, dtype=torch.float64, device=e.device), None]
+        buf = self._lidar_bufs[key]
+        buf[1] = self.raycast(offsets=buf[0], max_t=max_range, radius=radius, obstacles=obstacles, into=buf[1])
+        return buf[1]
+

@@ -201,6 +201,12 @@ def run_session(install, env_id, domain_rand, mode_kwargs, blobs):
     do("raycast into", lambda: vec.raycast(direction=torch.ones((N, 5, 2), dtype=torch.float64), into=rays))
     do("lidar", lambda: vec.lidar(rays=8))
     do("lidar again", lambda: vec.lidar(rays=8))
+    do("default_fov", lambda: vec.default_fov())
+    seen = do("seen_map", lambda: vec.seen_map(cell=0.5, max_range=6.0, fov=2.0, obstacles="walls+entities"))
+    seen_like = do("seen_map like", lambda: vec.seen_map(like=field))
+    do("seen_update", lambda: vec.seen_update(seen))
+    do("seen_update clear", lambda: vec.seen_update(seen, clear=torch.tensor([1, 0, 0, 1], dtype=torch.uint8)))
+    do("seen_update bool mask", lambda: vec.seen_update(seen_like, mask=torch.tensor([True, False, True, False])))
     do("infos", lambda: vec.infos())
     do("final_infos", lambda: vec.final_infos())
     do("reset_pending", lambda: vec.reset_pending())
