@@ -832,6 +832,59 @@ int mw_seen_update(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are r
                    int32_t flags, const uint8_t *d_mask, const uint8_t *d_clear,
                    uint8_t *d_seen, int32_t *d_count, int32_t *d_new /* or NULL */, void *stream);
 
+/* ---- egocentric map windows -------------------------------------------------- */
+/* A small window of points centred on each agent and turned so that "up" is its heading: where walls and entities are, which points
+ * the agent sees right now, and what a grid over the floor plan — a seen map, a nav field, the caller's own — holds there.  MiniGrid's
+ * partial view, Habitat's ego_map sensor, the local map of Active Neural SLAM style policies and of local planners.  The reference
+ * has no such call.
+ *
+ * The window: size = S, 1 .. MW_EGO_MAX_SIZE; row r = 0 is the farthest ahead, column c grows to the agent's right.  All arithmetic is
+ * float64, + - * / floor and sqrt only, uncontracted, in this order:
+ *   lat = (((double)c + 0.5) - (double)S * 0.5) * cell
+ *   fwd = (((double)S * 0.5 - ((double)r + 0.5)) + back) * cell      back in cells: 0 the agent at the window's centre, S / 2 on the
+ *                                                                    middle of its bottom edge
+ *   the axes: f = (hx, hz) = (cos, -sin) of agent_dir — the reference's dir_vec through the same deterministic sin / cos as the dynamics,
+ *   as the fan of mw_ray_cast forms it for offset 0 — and rt = (-hz, hx), the reference's right_vec; with MW_EGO_NORTH the constants
+ *   f = (0, -1), rt = (1, 0): rows then grow with z and columns with x, like every grid here
+ *   px = ox + (fwd * fx + lat * rtx), pz = oz + (fwd * fz + lat * rtz), o the agent's position or row i of d_pos (the heading is
+ *   always the agent's)
+ * The planes at point p, one uint8 each; every test is written so that a NaN fails it:
+ *   MW_EGO_WALL     0 iff px >= min_x && px <= max_x && pz >= min_z && pz <= max_z (the env's extent) and the closest-point distance
+ *                   from p to a collision segment (mw_nav_build's) is < wall_radius for no segment of the env; else 1.  A NaN pose: 1.
+ *   MW_EGO_ENTITY   0, or 1 + the lowest slot whose kind is not MW_ENT_NONE, which is not the carried one and for which
+ *                   dx*dx + dz*dz < R*R with d = p - its (x, z) and R = radius(slot) + entity_pad (summed in float64: mw_ray_cast's
+ *                   circle under radius = entity_pad)
+ *   MW_EGO_VISIBLE  tests 2 - 4 of mw_seen_update with p in the cell centre's place: v = p - o, dist <= range, the cone about the
+ *                   agent's heading (with MW_EGO_NORTH too), the line of sight free under exactly mw_ray_cast's arithmetic with
+ *                   max_t = 1 and radius 0 — walls, and with MW_EGO_ENTITIES the listed slots' circles
+ * The sample (d_src given): fi = floor((px - min_x) / src_grid->cell), fj = floor((pz - min_z) / src_grid->cell); the point is inside
+ * iff fi >= 0.0 && fi < (double)gx && fj >= 0.0 && fj < (double)gz, compared as doubles before any conversion; inside,
+ * d_sample[i][r][c] = d_src[i][(int)fj][(int)fi], otherwise fill truncated to src_bytes.  No clamping, no status bit.  Elements are 1
+ * byte (a seen map, the caller's own uint8 grid) or 2 (a nav field).
+ * Rows of envs under a zero mask byte are neither read (d_pos) nor written.  Every cell has one owner, so the result does not depend
+ * on the kernel's schedule. */
+#define MW_EGO_ENTITIES 1        /* flags: listed entities block the line of sight of MW_EGO_VISIBLE too */
+#define MW_EGO_NORTH 2           /* flags: the window keeps the world's axes instead of turning with the agent */
+#define MW_EGO_WALL 1            /* planes */
+#define MW_EGO_ENTITY 2
+#define MW_EGO_VISIBLE 4
+#define MW_EGO_MAX_SIZE 128
+/* One kernel, one workgroup per env, asynchronous on `stream`; it reads no host value except host_window (during the call), reads live
+ * arrays only and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched: a null engine or
+ * host_window; size outside 1 .. MW_EGO_MAX_SIZE; a cell that is not > 0 and finite; a back that is not finite; a wall_radius or
+ * entity_pad < 0 or not finite; with MW_EGO_VISIBLE a range that is not > 0 or not finite, a cos_half outside -1 .. 1 or NaN; unknown
+ * plane or flag bits; planes == 0 without a source; d_planes null while planes != 0; MW_EGO_ENTITY on an engine of more than 255 slots;
+ * a source without src_grid, d_sample or src_bytes in {1, 2}, or whose grid mw_nav_build would refuse (cell <= 0, gx or gz < 1, more
+ * than MW_NAV_MAX_CELLS cells); src_grid, d_sample or src_bytes != 0 without d_src is no error, they are ignored; more workgroups than
+ * a launch holds; an engine whose max_segs and max_ents need more than 64 KiB of LDS for the asked planes (VISIBLE 48 bytes per
+ * segment and 32 per slot, WALL 32 per segment, ENTITY 32 per slot). */
+int mw_ego_map(mw_engine *e, const double *host_window /* [6] on the host: cell, back, wall_radius, entity_pad, range, cos_half */,
+               int32_t size, int32_t planes, int32_t flags, const uint8_t *d_mask,
+               const double *d_pos /* [N][3] (y is not read) or NULL = the agents */,
+               uint8_t *d_planes /* [N][P][size][size]: P = popcount(planes) planes in bit order; NULL iff planes == 0 */,
+               const mw_nav_params *src_grid /* cell, gx, gz are read */, const void *d_src /* [N][gz][gx] of src_bytes each or NULL */,
+               int32_t src_bytes /* 1 or 2 with d_src */, uint32_t fill, void *d_sample /* [N][size][size] of src_bytes each */, void *stream);
+
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.

@@ -10,6 +10,7 @@
 #include "mw_nav.h"
 #include "mw_ray.h"
 #include "mw_seen.h"
+#include "mw_ego.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -285,6 +286,14 @@ extern "C" __global__ void mw_ray_waves_kernel(MwRayArgs a, mw_ray_params p, con
 // dynamic LDS; env b's row of `seen`, count[b] and newly[b] where mask is null or mask[b] != 0; clear and newly may be null.
 extern "C" __global__ void mw_seen_kernel(MwRayArgs a, mw_nav_params p, mwseen::Sight s, const uint8_t *__restrict__ mask, const uint8_t *__restrict__ clear,
                                           uint8_t *seen, int32_t *__restrict__ count, int32_t *__restrict__ newly);
+
+// egocentric map windows (mw_ego.hip; the point, the tests, the phases and the launch constant: mw_ego.h; the launch: mwpolicy::ego_launch).
+// The window, the sight (range, cos(fov / 2), flags) and the sampled grid travel by value.  Grid N workgroups of MW_EGO_THREADS lanes,
+// mwego::staged_bytes(max_segs, E, planes) bytes of dynamic LDS; env b's [P][size][size] bytes of `planes` and its row of `sample` where
+// mask is null or mask[b] != 0; pos null = the agents; planes null iff no plane is asked for; src and sample both null = no sample.
+extern "C" __global__ void mw_ego_kernel(MwRayArgs a, mwego::Window w, mwseen::Sight s, mwego::Source q, const uint8_t *__restrict__ mask,
+                                         const double *__restrict__ pos, uint8_t *__restrict__ planes, const void *__restrict__ src,
+                                         void *__restrict__ sample);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

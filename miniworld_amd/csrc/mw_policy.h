@@ -8,6 +8,7 @@
 #include "../../include/mwengine.h"
 #include "mw_ray.h"             // MW_RAY_THREADS, MW_RAY_WAVES, MW_RAY_WALL_BYTES, MW_RAY_DISC_BYTES
 #include "mw_seen.h"            // MW_SEEN_THREADS, MW_SEEN_TAIL_BYTES
+#include "mw_ego.h"             // MW_EGO_THREADS, mwego::staged_bytes
 #include "mw_shape.h"
 #include "mw_snapframes.h"      // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -333,6 +334,17 @@ inline SeenLaunch seen_launch(int N, int max_segs, int max_ents)
 {
     const size_t lds = ((size_t)max_segs * MW_RAY_WALL_BYTES + (size_t)max_ents * MW_RAY_DISC_BYTES + 15) / 16 * 16 + MW_SEEN_TAIL_BYTES;
     return {(unsigned long long)N, MW_SEEN_THREADS, lds, lds <= 64 * 1024};
+}
+
+// Egocentric map windows (mw_ego_map; kernel: mw_ego.hip): a workgroup of MW_EGO_THREADS lanes per env.  Its LDS is the staged
+// obstacles of the asked planes, sized from the engine's capacities (mwego::staged_bytes: 48 bytes per segment and 32 per slot for
+// VISIBLE, 32 per segment for WALL, 32 per slot for ENTITY, rounded up to 16; nothing without planes); fits: at most 64 KiB — the caller
+// refuses what does not.
+struct EgoLaunch { unsigned long long grid; int threads; size_t lds; bool fits; };
+inline EgoLaunch ego_launch(int N, int max_segs, int max_ents, int planes)
+{
+    const size_t lds = mwego::staged_bytes(max_segs, max_ents, planes);
+    return {(unsigned long long)N, MW_EGO_THREADS, lds, lds <= 64 * 1024};
 }
 
 }  // namespace mwpolicy

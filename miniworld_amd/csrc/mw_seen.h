@@ -53,14 +53,19 @@ MW_HD mwray::Ray ray_to(const mwnav::Grid &g, const View &v, int j, int i)
 {
     return {v.ox, v.oz, mwnav::centre(g.min_x, i, g.cell) - v.ox, mwnav::centre(g.min_z, j, g.cell) - v.oz};
 }
+// tests 2 - 3 of the ray r from the agent to a point: within range and inside the cone about the heading (mw_ego.h asks it of its
+// window points too)
+MW_HD bool in_cone(const View &v, const Sight &s, const mwray::Ray &r)
+{
+    const double dist = sqrt(r.dx * r.dx + r.dz * r.dz);
+    if (!(dist <= s.range)) return false;
+    return s.cos_half == -1.0 || dist == 0.0 || r.dx * v.hx + r.dz * v.hz >= s.cos_half * dist;
+}
 // tests 1 - 3: no division, no obstacle
 MW_HD bool in_sight(const mwnav::Grid &g, const View &v, const Sight &s, int j, int i)
 {
     if (mwnav::beyond(g, j, i)) return false;
-    const mwray::Ray r = ray_to(g, v, j, i);
-    const double dist = sqrt(r.dx * r.dx + r.dz * r.dz);
-    if (!(dist <= s.range)) return false;
-    return s.cos_half == -1.0 || dist == 0.0 || r.dx * v.hx + r.dz * v.hz >= s.cos_half * dist;
+    return in_cone(v, s, ray_to(g, v, j, i));
 }
 // test 4 on staged obstacles.  mw_ray_cast's result is h = (1, -1) exactly when no candidate was taken, and a taken candidate is never
 // given back: the walk may stop at the first one.

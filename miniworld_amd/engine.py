@@ -130,6 +130,10 @@ class MwRayParams(C.Structure):
 
 SEEN_ENTITIES = 1                       # MW_SEEN_ENTITIES
 
+EGO_ENTITIES, EGO_NORTH = 1, 2          # MW_EGO_* flags
+EGO_WALL, EGO_ENTITY, EGO_VISIBLE = 1, 2, 4     # MW_EGO_* planes
+EGO_MAX_SIZE = 128                      # MW_EGO_MAX_SIZE
+
 
 class MwPlanTrace(C.Structure):
     _fields_ = [("agent_pos", C.c_void_p), ("agent_dir", C.c_void_p), ("carrying", C.c_void_p), ("ent_pos", C.c_void_p), ("ent_slot", C.c_int32)]
@@ -227,6 +231,7 @@ SIGNATURES = {
     "mw_ray_cast": _sig(vp, P(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_ray_form": _sig(vp, C.c_int),
     "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
+    "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
     "mw_debug_set_launch_shape": _sig(vp, C.c_int, C.c_int, C.c_int, C.c_int),
     "mw_pcg64_draws": _sig(C.c_uint64, i32, vp, vp),
     "mw_selftest_rcp": _sig(vp, vp, vp),
@@ -559,6 +564,40 @@ class Engine:
         sight = (C.c_double * 2)(float(max_range), float(cos_half))
         self._check(self.lib.mw_seen_update(self.h, C.byref(params), sight, int(flags), _ptr(mask), _ptr(clear), _ptr(seen), _ptr(count), _ptr(new),
                                             _stream_ptr(self.device)), "mw_seen_update")
+
+    # -- egocentric map windows ----------------------------------------------------------
+    def ego_map(self, size: int, cell: float, back: float, wall_radius: float, entity_pad: float, max_range: float, cos_half: float, planes: int,
+                flags: int, out=None, mask=None, pos=None, src_params: MwNavParams | None = None, src=None, fill: int = 0, sample=None):
+        """mw_ego_map: for the envs under `mask` (uint8[N], device; None = all) the `size` x `size` window of points `cell` metres apart
+        around each agent — or row i of `pos` (float64[N, 3], device) —, turned with its heading (EGO_NORTH in `flags`: not turned), `back`
+        cells behind the centre: the planes named by the bits of `planes` (EGO_WALL, EGO_ENTITY, EGO_VISIBLE) into `out` (uint8[N, P, size,
+        size], device; None iff planes == 0) and, with `src` (uint8 or uint16 [N, gz, gx] on the grid `src_params`), the source's element
+        under every point, `fill` outside the grid, into `sample` ([N, size, size] of src's dtype).  One kernel on the current stream, no
+        synchronisation, nothing of the engine changes.  A wrong tensor is refused before the library is called."""
+        import torch
+        size, planes = int(size), int(planes)
+        count = bin(planes & (EGO_WALL | EGO_ENTITY | EGO_VISIBLE)).count("1")
+        if (out is None) != (count == 0):
+            raise EngineError("out: None" if out is None else "out: a tensor without planes to write")
+        if out is not None:
+            self._shaped_tensor(out, "out", torch.uint8, (self.N, count, size, size))
+        self._dev_tensor(pos, "pos", torch.float64, self.N * 3)
+        mask = self._mask_tensor(mask, optional=True)
+        src_bytes = 0
+        if src is not None:
+            if src_params is None or sample is None:
+                raise EngineError(f"{'src_params' if src_params is None else 'sample'}: None")
+            if not torch.is_tensor(src) or src.dtype not in (torch.uint8, torch.uint16):
+                raise EngineError(f"src: need a uint8 or uint16 tensor, got {src.dtype if torch.is_tensor(src) else type(src).__name__}")
+            self._shaped_tensor(src, "src", src.dtype, (self.N, int(src_params.gz), int(src_params.gx)))
+            self._shaped_tensor(sample, "sample", src.dtype, (self.N, size, size))
+            src_bytes = src.element_size()
+        elif sample is not None:
+            raise EngineError("sample: a tensor without a source")
+        window = (C.c_double * 6)(float(cell), float(back), float(wall_radius), float(entity_pad), float(max_range), float(cos_half))
+        self._check(self.lib.mw_ego_map(self.h, window, size, planes, int(flags), _ptr(mask), _ptr(pos), _ptr(out),
+                                        None if src is None else C.byref(src_params), _ptr(src), src_bytes, int(fill) & 0xFFFFFFFF, _ptr(sample),
+                                        _stream_ptr(self.device)), "mw_ego_map")
 
     def debug_set_launch_shape(self, waves_per_env: int = 0, mesh_tile_waves: int = 0, ent_blocks: int = 0, slow_waves: int = 0):
         """Tests and measurements: wavefronts per env of the tile kernels (a divisor of the frame's tile count) and the persistent

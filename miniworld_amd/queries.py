@@ -1,5 +1,6 @@
-"""The world queries of the batched env — navigation fields, explored-area maps, ray casts —, each one kernel on the device with no
-host value: their value classes (NavField, SeenMap) and `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
+"""The world queries of the batched env — navigation fields, explored-area maps, egocentric map windows, ray casts —, each one kernel on
+the device with no host value: their value classes (NavField, SeenMap, EgoWindow) and `WorldQueries`, a mixin of MiniWorldVecEnv
+(vec_env.py)."""
 from __future__ import annotations
 
 import math
@@ -46,7 +47,30 @@ class SeenMap:
     gz = property(lambda self: self.params.gz)
 
 
-assert eng.NAV_ENTITIES == eng.RAY_ENTITIES == eng.SEEN_ENTITIES      # (one table serves the three calls)
+class EgoWindow:
+    """An egocentric map window (MiniWorldVecEnv.ego_window): `planes`, the uint8[N, P, S, S] device tensor that ego_update() fills —
+    row 0 the farthest ahead, columns growing to the agent's right, points `cell` metres apart —, `names`, its planes in order out of
+    ("wall", "entity", "visible"), and the views `wall` (1 in a wall or outside the extent), `entity` (1 + the slot of the entity
+    there, 0 for none) and `visible` (1 where the agent sees the point now), each uint8[N, S, S] or None when not asked for.  `back`
+    is the anchor in cells behind the window's centre, `frame` "heading" or "north"; `wall_radius`, `entity_pad`, `max_range`,
+    `cos_half` and `obstacles` say what the planes mean.  The tensor is the caller's: the engine keeps nothing of it."""
+    PLANES = {"wall": eng.EGO_WALL, "entity": eng.EGO_ENTITY, "visible": eng.EGO_VISIBLE}
+
+    def __init__(self, planes, names, size, cell, back, frame, wall_radius, entity_pad, max_range, cos_half, obstacles):
+        self.planes, self.names, self.size, self.cell, self.back, self.frame = planes, tuple(names), size, cell, back, frame
+        self.wall_radius, self.entity_pad, self.max_range, self.cos_half, self.obstacles = wall_radius, entity_pad, max_range, cos_half, obstacles
+
+    bits = property(lambda self: sum(self.PLANES[n] for n in self.names))
+
+    def _plane(self, name):
+        return self.planes[:, self.names.index(name)] if name in self.names else None
+
+    wall = property(lambda self: self._plane("wall"))
+    entity = property(lambda self: self._plane("entity"))
+    visible = property(lambda self: self._plane("visible"))
+
+
+assert eng.NAV_ENTITIES == eng.RAY_ENTITIES == eng.SEEN_ENTITIES == eng.EGO_ENTITIES      # (one table serves the four calls)
 
 
 class WorldQueries:
@@ -190,6 +214,83 @@ class WorldQueries:
         clear, mask = self._device_mask(clear, "seen_update", "clear"), self._device_mask(mask, "seen_update")
         self.engine.seen_update(seen.params, seen.max_range, seen.cos_half, self.OBSTACLES[seen.obstacles], seen.seen, seen.count, seen.new, mask, clear)
         return seen.new
+
+    # ------------------------------------------------------------------ egocentric map windows
+    def ego_window(self, size=33, cell=0.25, anchor="centre", frame="heading", planes=("wall", "entity", "visible"), wall_radius=None,
+                   entity_pad=None, max_range=10.0, fov=None, obstacles="walls"):
+        """An empty egocentric map window: an EgoWindow, which ego_update() fills.  Nothing is launched.
+
+        size         S: the window is S x S points, 1 .. engine.EGO_MAX_SIZE
+        cell         metres between neighbouring points
+        anchor       "centre": the agent stands in the window's centre; "bottom": on the middle of its bottom edge, all of it ahead
+        frame        "heading": row 0 is the farthest ahead and columns grow to the agent's right; "north": the window keeps the
+                     world's axes, rows grow with z and columns with x like every grid here
+        planes       which of "wall", "entity", "visible" to compute (kept in that order); () for a window that only samples a source
+        wall_radius  a point counts as wall when it is closer than this to a collision segment, or outside the extent; default cell / 2
+        entity_pad   added to an entity's radius; default cell / 2
+        max_range, fov, obstacles  what "visible" means, exactly as for seen_map()
+        ValueError for arguments that make no window."""
+        torch, e = self.torch, self.engine
+        size = integer("ego_window", "size", size, 1, eng.EGO_MAX_SIZE)
+        cell = real("ego_window", "cell", cell)
+        if anchor not in ("centre", "bottom"):
+            raise ValueError(f"ego_window: anchor {anchor!r}; have 'centre' and 'bottom'")
+        if frame not in ("heading", "north"):
+            raise ValueError(f"ego_window: frame {frame!r}; have 'heading' and 'north'")
+        if isinstance(planes, str) or not isinstance(planes, (tuple, list)) or len(set(planes)) != len(planes) or any(
+                not isinstance(p, str) or p not in EgoWindow.PLANES for p in planes):
+            raise ValueError(f"ego_window: planes {planes!r}: a sequence of distinct names out of {tuple(EgoWindow.PLANES)}")
+        names = tuple(n for n in EgoWindow.PLANES if n in planes)
+        if "entity" in names and e.cfg.max_ents > 255:
+            raise ValueError(f"ego_window: {e.cfg.max_ents} entity slots do not fit the entity plane's byte")
+        wall_radius = cell / 2 if wall_radius is None else real("ego_window", "wall_radius", wall_radius, lo_open=False)
+        entity_pad = cell / 2 if entity_pad is None else real("ego_window", "entity_pad", entity_pad, lo_open=False)
+        self._obstacle_flags("ego_window", obstacles)
+        max_range = real("ego_window", "max_range", max_range)
+        fov = self.default_fov() if fov is None else real("ego_window", "fov", fov, hi=2 * math.pi)
+        cos_half = -1.0 if fov == 2 * math.pi else math.cos(fov / 2)
+        out = torch.zeros((self.num_envs, len(names), size, size), dtype=torch.uint8, device=e.device) if names else None
+        return EgoWindow(out, names, size, cell, size / 2 if anchor == "bottom" else 0.0, frame, wall_radius, entity_pad, max_range, float(cos_half), obstacles)
+
+    def ego_update(self, w, source=None, fill=None, mask=None, pos=None):
+        """Fills `w` (an EgoWindow) for where each env's agent stands and looks now, by one kernel (mw_ego_map) with no host value and
+        no synchronisation; returns w.planes, or (w.planes, sample) with a source.
+
+        source  a SeenMap or a NavField: `sample`, [N, S, S] of the source's dtype (uint8 / uint16), holds the source's cell under
+                every point of the window — with the engine's own rounding, so that window and map agree at cell borders.  The
+                tensor is this env's own, reused between calls of the same size and dtype.
+        fill    what a point outside the source's grid samples; default 0 for a seen map, 0xFFFF (blocked) for a nav field
+        mask    uint8[N] or bool[N] device tensor: only those envs' rows are read and written
+        pos     float64[N, 3] device tensor: the window's origin instead of the agent's position (y is not read); the heading stays
+                the agent's
+        Tensors are checked, never converted (EngineError); ValueError for arguments that make no call; nothing is launched then."""
+        torch, e = self.torch, self.engine
+        if not isinstance(w, EgoWindow):
+            raise ValueError("ego_update: `w` must be an EgoWindow (ego_window())")
+        src = params = sample = None
+        if source is not None:
+            if isinstance(source, SeenMap):
+                src, limit, default = source.seen, 0xFF, 0
+            elif isinstance(source, NavField):
+                src, limit, default = source.field, 0xFFFF, eng.NAV_BLOCKED
+            else:
+                raise ValueError(f"ego_update: source is None, a SeenMap or a NavField, not {type(source).__name__}")
+            params = source.params
+            fill = default if fill is None else integer("ego_update", "fill", fill, 0, limit)
+            if not torch.is_tensor(src):
+                raise eng.EngineError(f"ego_update: the source's tensor is {type(src).__name__}")
+            sample = self._buffer((w.size, src.dtype), (self.num_envs, w.size, w.size), src.dtype, self._ego_bufs)
+        elif fill is not None:
+            raise ValueError("ego_update: fill without a source")
+        elif not w.names:
+            raise ValueError("ego_update: a window without planes needs a source")
+        if pos is not None and not self._is_tensor(pos, (self.num_envs, 3)):
+            raise ValueError(f"ego_update: pos is a contiguous float64 tensor [{self.num_envs}, 3] on {e.device}")
+        mask = self._device_mask(mask, "ego_update")
+        flags = self.OBSTACLES[w.obstacles] | (eng.EGO_NORTH if w.frame == "north" else 0)
+        e.ego_map(w.size, w.cell, w.back, w.wall_radius, w.entity_pad, w.max_range, w.cos_half, w.bits, flags, w.planes, mask, pos, params, src,
+                  fill or 0, sample)
+        return w.planes if source is None else (w.planes, sample)
 
     # ------------------------------------------------------------------ ray casts
     def raycast(self, direction=None, origin=None, offsets=None, max_t=1.0, radius=0.0, obstacles="walls", mask=None, into=None):

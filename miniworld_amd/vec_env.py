@@ -30,7 +30,7 @@ from . import engine as eng
 from . import envs as _envs
 from ._args import integer, seeds_u64
 from .env_config import _INFO_KIND, _KIND, AUTORESET_MODES, EnvConfig, _ball_key_meshes, _entity_slots, build_config   # noqa: F401 (re-exported)
-from .queries import NavField, SeenMap, WorldQueries    # noqa: F401
+from .queries import EgoWindow, NavField, SeenMap, WorldQueries     # noqa: F401
 from .restarts import Restarts
 from .scene import polys_array, scene_from_env, state_arrays, upload_scene_meshes
 from .snapshots import EnvSnapshot, Snapshots           # noqa: F401
@@ -188,6 +188,7 @@ class MiniWorldVecEnv(Snapshots, Restarts, WorldQueries):
         self._state_bufs = {}           # state()'s tensors, one per field, made on first use
         self._nav_bufs = {}             # nav_query()'s tensors, made on first use
         self._lidar_bufs = {}           # lidar()'s offsets and result per (rays, fov), made on first use
+        self._ego_bufs = {}             # ego_update()'s samples per (size, dtype), made on first use
         self._fork_buf = None           # fork()'s scratch records, made on first use
         self._fork_frames = None        # ... and its scratch frame records (fork(src, frames=True))
         self._done = self._done_b = self._done_i = None     # the finished envs of a step as uint8 / bool / int64 ("levels", "seeds")

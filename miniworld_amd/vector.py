@@ -74,7 +74,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
                  frame_reuse: bool = True, frame_cache: int = 4, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset",
-                 levels=None, level_generator=None, reset_seeds=None, info_state=None, seen_map=None, **kwargs):
+                 levels=None, level_generator=None, reset_seeds=None, info_state=None, seen_map=None, ego_map=None, **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
         False draws every env on every step, for consumers that write into the returned observation tensor (module docstring).
@@ -98,9 +98,16 @@ class MiniWorldVectorEnv(VectorEnvBase):
         sees from its new pose in an explored-area map on the device (`self.seen`, a SeenMap) and adds info["seen_new"] (int32[N], the
         cells that became seen with this step: a coverage reward) and info["seen_count"] (int32[N], the cells seen so far in the
         episode); the map of an env whose episode ended restarts with the first pose of its next one (under next-step with the reset
-        step), and reset() restarts every map.  None (the default) adds nothing and calls nothing."""
+        step), and reset() restarts every map.  None (the default) adds nothing and calls nothing.
+        ego_map: a dict of MiniWorldVecEnv.ego_window()'s arguments (an empty one for its defaults) — reset() and every step() fill an
+        egocentric map window around each agent's new pose on the device (`self.ego`, an EgoWindow; one kernel) and add info["ego_map"],
+        uint8[N, P, S, S]: its planes, a cheap symbolic observation.  For an env whose episode ended with the step the window shows what the
+        device holds: its next episode's world under the same-step auto-reset.  A copy: it stays valid after the next step.  None (the
+        default) adds nothing and calls nothing."""
         if seen_map is not None and not isinstance(seen_map, dict):
             raise ValueError(f"seen_map: need a dict of MiniWorldVecEnv.seen_map()'s arguments or None, not {seen_map!r}")
+        if ego_map is not None and (not isinstance(ego_map, dict) or ego_map.get("planes", True) in ((), [])):
+            raise ValueError(f"ego_map: need a dict of MiniWorldVecEnv.ego_window()'s arguments with at least one plane, or None, not {ego_map!r}")
         if not isinstance(action_repeat, (int, np.integer)) or not 1 <= action_repeat <= 256:
             raise ValueError(f"action_repeat must be an integer in 1 .. 256, not {action_repeat!r}")
         self.action_repeat = int(action_repeat)
@@ -144,6 +151,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
         self._played_seed = None
         self.seen = None if seen_map is None else self.vec.seen_map(**seen_map)
         self._seen_clear = None         # next-step: the envs whose next step is their reset step
+        self.ego = None if ego_map is None else self.vec.ego_window(**ego_map)
         if levels is not None:
             from .vec_env import EnvSnapshot
             self.vec.set_levels(levels if isinstance(levels, EnvSnapshot) else self.vec.make_levels(levels), level_generator)
@@ -192,13 +200,20 @@ class MiniWorldVectorEnv(VectorEnvBase):
             info["seen_count"] = self._out(self.seen.count) if self.to_numpy else self.seen.count.clone()
         return info
 
+    def _ego_info(self, info):
+        """ego_map: one ego_update() behind the step or reset; a copy of the window's planes (they are rewritten by the next step)"""
+        if self.ego is not None:
+            planes = self.vec.ego_update(self.ego)
+            info["ego_map"] = self._out(planes) if self.to_numpy else planes.clone()
+        return info
+
     def reset(self, *, seed: int | None = None, options: dict | None = None):
         """Env i is seeded with seed + i (gymnasium's convention for an integer seed); with levels= every env starts a level of the
         bank and the seed is not used."""
         obs = self.vec.reset(seed)
         if self._first_next_seed is not None:       # (reset() lays out seed + N + i; the caller's first choices stand)
             self.vec.next_seed.copy_(self._first_next_seed)
-        return self._out(self._obs(obs)), self._state_info(self._seen_info({}, None, True))
+        return self._out(self._obs(obs)), self._state_info(self._ego_info(self._seen_info({}, None, True)))
 
     def step(self, actions):
         torch = self.vec.torch
@@ -232,6 +247,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
         if self.vec.autoreset_mode == "seeds":
             info["seed"] = self._out(self._played_seed) if self.to_numpy else self._played_seed.clone()
         self._seen_info(info, term | trunc, False)
+        self._ego_info(info)
         self._state_info(info)
         return self._out(self._obs(obs)), self._out(rew), self._out(term.bool()), self._out(trunc.bool()), info
 
