@@ -885,6 +885,69 @@ int mw_ego_map(mw_engine *e, const double *host_window /* [6] on the host: cell,
                const mw_nav_params *src_grid /* cell, gx, gz are read */, const void *d_src /* [N][gz][gx] of src_bytes each or NULL */,
                int32_t src_bytes /* 1 or 2 with d_src */, uint32_t fill, void *d_sample /* [N][size][size] of src_bytes each */, void *stream);
 
+/* ---- depth projection -------------------------------------------------------- */
+/* The map a depth sensor gives: every pixel of each env's depth map — float32 [N][H][W], eye depth in metres, row 0 the top, what mw_step
+ * and mw_render write with want-depth buffers: the reference's get_depth_map(0.04, 100), opengl.py:400-435 — is unprojected with the env's
+ * own camera (cam_height, cam_fwd_disp, cam_pitch, cam_fov_y; miniworld.py:1200-1222, entity.py:477-503) and the pose the device holds
+ * now, classed by its height as floor, obstacle or neither, and counted into a cell of an egocentric window laid out as mw_ego_map's or of
+ * a grid over the floor plan laid out as mw_nav_build's.  Active Neural SLAM's mapper, Habitat's ego_map from depth, every "local map from
+ * RGB-D" planner.  The privileged counterparts are mw_ego_map and mw_seen_update, computed from the collision segments: they are the labels
+ * and the check of this one, which is what a policy without simulator state may consume.  The reference has no such call.
+ *
+ * All arithmetic is float64, only + - * /, floor and the engine's deterministic sin / cos (the one of the dynamics, mw_ray_cast's fan),
+ * uncontracted, in exactly this order.  W x H is the engine's frame, pixel row v counts from the top, column u from the left.
+ * Per env:
+ *   o = the agent's (x, z); f = (hx, hz) = (cos, -sin) of agent_dir and rt = (-hz, hx), exactly mw_ego_map's axes
+ *   (sp, cp) = sincos(pitch_deg * M_PI / 180.0); (sh, ch) = sincos(fov_deg * 0.5 * M_PI / 180.0); th = sh / ch
+ *   aspect = (double)W / (double)H; tx = th * aspect
+ * Per pixel:
+ *   d = (double)depth[v][u]; the pixel is dropped unless d >= min_range && d <= max_range (so a NaN is dropped)
+ *   xn = (((double)u + sub_x) * 2.0) / (double)W - 1.0
+ *   yn = 1.0 - (((double)v + sub_y) * 2.0) / (double)H
+ *   lat = (xn * tx) * d
+ *   yc = (yn * th) * d
+ *   fwd = fwd_disp + (d * cp - yc * sp)
+ *   up = height + (d * sp + yc * cp)                 the height above the agent's own pos.y
+ *   floor iff up >= -floor_tol && up <= floor_tol; obstacle iff up > floor_tol && up <= top; otherwise dropped (ceiling, sky)
+ *   px = ox + (fwd * fx + lat * rtx); pz = oz + (fwd * fz + lat * rtz)
+ * (sub_x, sub_y) is where in the pixel the engine took the depth: sample 0 of its multisample pattern, (sx, sy) / 16 in GL space with y up
+ * — (9, 5) at 8 samples, (6, 2) at 4, (8, 8) at 1 —, so sub_x = sx / 16.0 and sub_y = 1.0 - sy / 16.0: not the pixel's centre.
+ * The window target (grid == NULL; size = S, cell, back and MW_EGO_NORTH as in mw_ego_map, whose point (r, c) is the centre of cell (r, c)):
+ *   a = lat, b = fwd; with MW_EGO_NORTH a = px - ox, b = -(pz - oz)
+ *   c = floor(a / cell + (double)S * 0.5); r = floor(((double)S * 0.5 + back) - b / cell)
+ *   the point is kept iff c >= 0.0 && c < (double)S && r >= 0.0 && r < (double)S, compared as doubles before any conversion
+ *   d_planes[i][0][r][c] = min(255, the floor points of the cell), d_planes[i][1][r][c] = min(255, its obstacle points); both planes are
+ *   written in full by every call.
+ * The map target (grid != NULL: cell, gx, gz are read; min_x, min_z the env's own extent):
+ *   fi = floor((px - min_x) / cell), fj = floor((pz - min_z) / cell); kept iff fi >= 0.0 && fi < (double)gx && fj >= 0.0 && fj < (double)gz
+ *   (mw_ego_map's sample test); the cell is [(int)fj][(int)fi]
+ *   d_map is uint8[N][2][gz][gx], plane 0 free (floor points), plane 1 obstacle.  For every env i with d_mask[i] != 0: if d_clear[i] != 0 its
+ *   two planes are zeroed and its counts set to 0 first; then a byte that is 0 becomes 1 when the call's count for the cell reaches
+ *   min_points; no call ever clears a byte except through d_clear.  d_new[i][k] gets the cells of plane k that went 0 -> 1 in this call,
+ *   d_count[i][k] becomes (cleared ? 0 : d_count[i][k]) + d_new[i][k].  An env whose extent the grid does not cover (as for mw_nav_build) gets
+ *   its planes zeroed, counts 0 and new 0, and sets a status bit that the next mw_check reports as MW_E_INVALID, once.
+ * Rows of envs under a zero mask byte are neither read nor written: the mask wins over clear.  A count is a sum of ones, so the result
+ * does not depend on the kernel's schedule.  Every test is written so that a NaN fails it.
+ *
+ * What the sensor cannot do.  The depth map is a function of a 16-bit depth value; one step of that value at eye depth z is
+ * z * z * (far - near) / (far * near * 65535) metres with near = 0.04, far = 100: 3.8 mm at 3 m, 3.8 cm at 10 m.  Choose max_range well below the
+ * far plane: at 8 m a step is 2.4 cm, a tenth of a 0.25 m cell.  The sky reads 100.0 and is dropped by any such max_range. */
+#define MW_DEPTH_MAX_PIXELS 65535       /* W * H of the engine's frame: a cell's floor and obstacle counts share one 32-bit word in the kernel */
+/* One kernel, one workgroup per env, asynchronous on `stream`; it reads no host value except host_params (during the call), reads live
+ * arrays only and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched: a null engine, host_params
+ * or d_depth; a frame of more than MW_DEPTH_MAX_PIXELS pixels (a cell's two 16-bit counts could carry into each other); a min_range or
+ * max_range that is not > 0 and finite, min_range > max_range; a floor_tol < 0 or not finite; a top < floor_tol or not finite; for a window
+ * a size outside 1 .. MW_EGO_MAX_SIZE, a cell that is not > 0 and finite, a back that is not finite, flags other than MW_EGO_NORTH, a null
+ * d_planes; for a map a null d_map or d_count, flags != 0, min_points outside 1 .. 255, a grid mw_nav_build would refuse (cell <= 0 or not
+ * finite, gx or gz < 1, more than MW_NAV_MAX_CELLS cells) or one of more than 16384 cells (4 bytes of LDS per cell, 64 KiB: use a larger
+ * cell); more workgroups than a launch holds. */
+int mw_depth_project(mw_engine *e, const double *host_params /* [6] on the host: min_range, max_range, floor_tol, top, cell, back (the last two: window) */,
+                     const float *d_depth /* [N][H][W] */, const uint8_t *d_mask,
+                     int32_t size, int32_t flags, uint8_t *d_planes /* [N][2][size][size]; read with grid == NULL */,
+                     const mw_nav_params *grid /* NULL = the window target; else cell, gx, gz are read */, int32_t min_points,
+                     const uint8_t *d_clear /* or NULL */, uint8_t *d_map /* [N][2][gz][gx] */, int32_t *d_count /* [N][2] */,
+                     int32_t *d_new /* [N][2] or NULL */, void *stream);
+
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.
@@ -896,7 +959,7 @@ int mw_ego_map(mw_engine *e, const double *host_window /* [6] on the host: cell,
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build or mw_seen_update skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update or mw_depth_project skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

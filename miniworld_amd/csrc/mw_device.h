@@ -56,6 +56,7 @@
 #define MW_ST_STATE_BAD 8u          // mw_set_state_where skipped an env: its carrying outside -1 .. max_ents - 1 or an ent_kind outside MW_ENT_NONE .. MW_ENT_FRAME
 #define MW_ST_NAV_BAD 16u           // mw_nav_build refused an env (its row is all 0xFFFF): the grid does not cover its extent, a cost would reach 0xFFFE, or the relaxation hit its bound on passes
 #define MW_ST_SEEN_BAD 32u          // mw_seen_update refused an env (its row is zeroed, its count 0): the grid does not cover its extent
+#define MW_ST_DEPTH_BAD 64u         // mw_depth_project refused an env (its rows of the map are zeroed, its counts 0): the grid does not cover its extent
 
 // Generator tables; kept in device memory because dynamic indexing into a by-value kernarg
 // struct would force a private (scratch) copy of the whole argument block.

@@ -1,0 +1,66 @@
+// mwengine host runtime: depth projection (mw_depth_project; kernel: mw_depth.hip, arithmetic and phases: mw_depth.h, launch: mw_policy.h).
+//
+// The call does not wait for the Maze's side-stream refills: mw_engine.h, at world_view().
+#include <math.h>
+
+#include "mw_engine.h"
+#include "mw_policy.h"
+
+using namespace mwhost;
+
+extern "C" {
+
+int mw_depth_project(mw_engine *e, const double *host_params, const float *d_depth, const uint8_t *d_mask, int32_t size, int32_t flags, uint8_t *d_planes,
+                     const mw_nav_params *grid, int32_t min_points, const uint8_t *d_clear, uint8_t *d_map, int32_t *d_count, int32_t *d_new, void *stream)
+{
+    const char *what = "mw_depth_project";
+    if (!e) return MW_E_INVALID;
+    if (!host_params) return fail(e, MW_E_INVALID, "%s: host_params is null", what);
+    if (!d_depth) return fail(e, MW_E_INVALID, "%s: d_depth is null", what);
+    const MwArgs &a = e->args;
+    // the kernel counts a cell's floor and obstacle points in the two halves of one 32-bit word: more pixels could carry from one into the other
+    if ((long long)a.W * (long long)a.H > MW_DEPTH_MAX_PIXELS)
+        return fail(e, MW_E_INVALID, "%s: a frame of %d x %d pixels > %d (a cell's two counts share a 32-bit word)", what, a.W, a.H, MW_DEPTH_MAX_PIXELS);
+    mwdepth::Sensor s{host_params[0], host_params[1], host_params[2], host_params[3], 0.0, 0.0, a.W, a.H};
+    mwdepth::subpixel_of(e->cfg.msaa, s.sub_x, s.sub_y);
+    if (!(s.min_range > 0.0) || !isfinite(s.min_range)) return fail(e, MW_E_INVALID, "%s: min_range %g is not a positive finite number", what, s.min_range);
+    if (!(s.max_range > 0.0) || !isfinite(s.max_range)) return fail(e, MW_E_INVALID, "%s: max_range %g is not a positive finite number", what, s.max_range);
+    if (s.min_range > s.max_range) return fail(e, MW_E_INVALID, "%s: min_range %g > max_range %g", what, s.min_range, s.max_range);
+    if (!(s.floor_tol >= 0.0) || !isfinite(s.floor_tol)) return fail(e, MW_E_INVALID, "%s: floor_tol %g is not a finite number >= 0", what, s.floor_tol);
+    if (!(s.top >= s.floor_tol) || !isfinite(s.top)) return fail(e, MW_E_INVALID, "%s: top %g is not a finite number >= floor_tol %g", what, s.top, s.floor_tol);
+    mwdepth::Window w{1.0, 0.0, 1, 0};
+    mw_nav_params p{1.0, 0.0, 0.0, 1, 1, 0, 0};
+    long long cells;
+    if (!grid) {        // the window target
+        w = {host_params[4], host_params[5], size, flags};
+        if (size < 1 || size > MW_EGO_MAX_SIZE) return fail(e, MW_E_INVALID, "%s: size %d outside 1 .. %d", what, (int)size, MW_EGO_MAX_SIZE);
+        if (!(w.cell > 0.0) || !isfinite(w.cell)) return fail(e, MW_E_INVALID, "%s: cell %g is not a positive finite number", what, w.cell);
+        if (!isfinite(w.back)) return fail(e, MW_E_INVALID, "%s: back %g is not finite", what, w.back);
+        if (flags & ~MW_EGO_NORTH) return fail(e, MW_E_INVALID, "%s: unknown flags 0x%x", what, (unsigned)flags);
+        if (!d_planes) return fail(e, MW_E_INVALID, "%s: d_planes is null", what);
+        cells = (long long)size * size;
+    } else {            // the map target
+        if (!d_map || !d_count) return fail(e, MW_E_INVALID, "%s: %s is null", what, !d_map ? "d_map" : "d_count");
+        if (flags) return fail(e, MW_E_INVALID, "%s: unknown flags 0x%x (a map has none)", what, (unsigned)flags);
+        if (min_points < 1 || min_points > 255) return fail(e, MW_E_INVALID, "%s: min_points %d outside 1 .. 255", what, (int)min_points);
+        if (const int rc = grid_check(e, what, grid)) return rc;
+        if (!isfinite(grid->cell)) return fail(e, MW_E_INVALID, "%s: cell %g is not finite", what, grid->cell);
+        p = *grid;
+        cells = (long long)p.gx * p.gz;
+    }
+    const mwpolicy::DepthLaunch l = mwpolicy::depth_launch(a.N, cells);
+    if (!l.fits)
+        return fail(e, MW_E_INVALID, "%s: %lld cells need %zu bytes of LDS > 64 KiB (at most %d cells): use a larger cell", what, cells, l.lds, MW_DEPTH_MAX_CELLS);
+    if (mwpolicy::grid_too_large(l.grid)) return fail(e, MW_E_INVALID, "%s: %llu workgroups", what, l.grid);
+    ON_DEVICE(e);
+    const MwRayArgs ra = ray_view(e);
+    if (const int rc = allow_dynamic_lds(e, mw_depth_kernel, e->depth_lds_set, l.lds)) return rc;
+    const int wide = (a.W * a.H) % 4 == 0 && mwpolicy::wide_units((uintptr_t)d_depth) ? 1 : 0;
+    hipLaunchKernelGGL(mw_depth_kernel, dim3((unsigned)l.grid), dim3((unsigned)l.threads), l.lds, (hipStream_t)stream, ra, a.cam, s, w, p, grid ? min_points : 1,
+                       wide, d_depth, d_mask, grid ? d_clear : nullptr, grid ? nullptr : d_planes, grid ? d_map : nullptr, grid ? d_count : nullptr,
+                       grid ? d_new : nullptr);
+    HIP_TRY(e, hipGetLastError());
+    return MW_OK;
+}
+
+}  // extern "C"

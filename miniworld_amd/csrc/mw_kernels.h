@@ -11,6 +11,7 @@
 #include "mw_ray.h"
 #include "mw_seen.h"
 #include "mw_ego.h"
+#include "mw_depth.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -294,6 +295,15 @@ extern "C" __global__ void mw_seen_kernel(MwRayArgs a, mw_nav_params p, mwseen::
 extern "C" __global__ void mw_ego_kernel(MwRayArgs a, mwego::Window w, mwseen::Sight s, mwego::Source q, const uint8_t *__restrict__ mask,
                                          const double *__restrict__ pos, uint8_t *__restrict__ planes, const void *__restrict__ src,
                                          void *__restrict__ sample);
+
+// depth projection (mw_depth.hip; the arithmetic, the phases and the launch constants: mw_depth.h; the launch: mwpolicy::depth_launch).  The
+// sensor, the window and the grid (cell, gx, gz are read) travel by value; cam is the world's [4][N] camera rows.  Grid N workgroups of
+// MW_DEPTH_THREADS lanes, MW_DEPTH_CELL_BYTES of dynamic LDS per cell of the target; exactly one of planes ([N][2][size][size]) and map
+// ([N][2][gz][gx], with count [N][2]) is non-null; env b's rows where mask is null or mask[b] != 0; clear and newly may be null; wide != 0:
+// W * H is a multiple of 4 and depth 16-byte aligned.
+extern "C" __global__ void mw_depth_kernel(MwRayArgs a, const double *__restrict__ cam, mwdepth::Sensor s, mwdepth::Window w, mw_nav_params p, int min_points,
+                                           int wide, const float *__restrict__ depth, const uint8_t *__restrict__ mask, const uint8_t *__restrict__ clear,
+                                           uint8_t *__restrict__ planes, uint8_t *__restrict__ map, int32_t *__restrict__ count, int32_t *__restrict__ newly);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

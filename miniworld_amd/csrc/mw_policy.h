@@ -9,6 +9,7 @@
 #include "mw_ray.h"             // MW_RAY_THREADS, MW_RAY_WAVES, MW_RAY_WALL_BYTES, MW_RAY_DISC_BYTES
 #include "mw_seen.h"            // MW_SEEN_THREADS, MW_SEEN_TAIL_BYTES
 #include "mw_ego.h"             // MW_EGO_THREADS, mwego::staged_bytes
+#include "mw_depth.h"           // MW_DEPTH_THREADS, MW_DEPTH_CELL_BYTES, MW_DEPTH_MAX_CELLS
 #include "mw_shape.h"
 #include "mw_snapframes.h"      // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -345,6 +346,18 @@ inline EgoLaunch ego_launch(int N, int max_segs, int max_ents, int planes)
 {
     const size_t lds = mwego::staged_bytes(max_segs, max_ents, planes);
     return {(unsigned long long)N, MW_EGO_THREADS, lds, lds <= 64 * 1024};
+}
+
+// Depth projection (mw_depth_project; kernel: mw_depth.hip): a workgroup of MW_DEPTH_THREADS lanes per env.  Its LDS is one uint32 per
+// cell of the target — size * size of a window, gx * gz of a map —, never less than the two words per wavefront the map's reduction
+// reuses, rounded up to 16; fits: at most 64 KiB, i.e. MW_DEPTH_MAX_CELLS = 16384 cells (a window of MW_EGO_MAX_SIZE = 128; the Maze at
+// 0.25 m has 10 609) — the caller refuses what does not.
+struct DepthLaunch { unsigned long long grid; int threads; size_t lds; bool fits; };
+inline DepthLaunch depth_launch(int N, long long cells)
+{
+    const long long least = 2 * (MW_DEPTH_THREADS / 64);
+    const size_t lds = ((size_t)(cells > least ? cells : least) * MW_DEPTH_CELL_BYTES + 15) / 16 * 16;
+    return {(unsigned long long)N, MW_DEPTH_THREADS, lds, lds <= 64 * 1024};
 }
 
 }  // namespace mwpolicy

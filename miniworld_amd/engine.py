@@ -134,6 +134,9 @@ EGO_ENTITIES, EGO_NORTH = 1, 2          # MW_EGO_* flags
 EGO_WALL, EGO_ENTITY, EGO_VISIBLE = 1, 2, 4     # MW_EGO_* planes
 EGO_MAX_SIZE = 128                      # MW_EGO_MAX_SIZE
 
+DEPTH_MAX_PIXELS = 65535                # MW_DEPTH_MAX_PIXELS
+DEPTH_MAX_CELLS = 16384                 # the cells of a depth window or map: 4 bytes of LDS each (csrc/mw_depth.h)
+
 
 class MwPlanTrace(C.Structure):
     _fields_ = [("agent_pos", C.c_void_p), ("agent_dir", C.c_void_p), ("carrying", C.c_void_p), ("ent_pos", C.c_void_p), ("ent_slot", C.c_int32)]
@@ -232,6 +235,7 @@ SIGNATURES = {
     "mw_debug_set_ray_form": _sig(vp, C.c_int),
     "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
     "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
+    "mw_depth_project": _sig(vp, P(C.c_double), vp, vp, i32, i32, vp, P(MwNavParams), i32, vp, vp, vp, vp, vp),
     "mw_debug_set_launch_shape": _sig(vp, C.c_int, C.c_int, C.c_int, C.c_int),
     "mw_pcg64_draws": _sig(C.c_uint64, i32, vp, vp),
     "mw_selftest_rcp": _sig(vp, vp, vp),
@@ -598,6 +602,43 @@ class Engine:
         self._check(self.lib.mw_ego_map(self.h, window, size, planes, int(flags), _ptr(mask), _ptr(pos), _ptr(out),
                                         None if src is None else C.byref(src_params), _ptr(src), src_bytes, int(fill) & 0xFFFFFFFF, _ptr(sample),
                                         _stream_ptr(self.device)), "mw_ego_map")
+
+    # -- depth projection ----------------------------------------------------------------
+    def depth_project(self, depth, min_range: float, max_range: float, floor_tol: float, top: float, mask=None, size: int = 0, cell: float = 0.0,
+                      back: float = 0.0, flags: int = 0, planes=None, params: MwNavParams | None = None, min_points: int = 1, map=None, count=None,
+                      new=None, clear=None):
+        """mw_depth_project: for the envs under `mask` (uint8[N], device; None = all) every pixel of `depth` (float32[N, H, W] or
+        [N, H, W, 1], device) with min_range <= depth <= max_range is unprojected with the env's camera and the pose the device holds,
+        classed as floor (|up| <= floor_tol) or obstacle (floor_tol < up <= top) and counted.  Window target (`planes`, uint8[N, 2, size,
+        size]: the counts per cell of mw_ego_map's window of `size`, `cell`, `back`, EGO_NORTH in `flags`, clamped to 255) or map target
+        (`params` with `map`, uint8[N, 2, gz, gx], `count` and optionally `new`, int32[N, 2]: a byte becomes 1 once the call's count reaches
+        `min_points`, behind a zeroing of the rows under `clear`, uint8[N]).  One kernel on the current stream, no synchronisation, nothing
+        of the engine changes.  A wrong tensor is refused before the library is called."""
+        import torch
+        H, W = self.H, self.W
+        if not torch.is_tensor(depth) or tuple(depth.shape) not in ((self.N, H, W), (self.N, H, W, 1)):
+            raise EngineError(f"depth: need a float32 tensor [{self.N}, {H}, {W}] or [{self.N}, {H}, {W}, 1], got "
+                              f"{tuple(depth.shape) if torch.is_tensor(depth) else type(depth).__name__}")
+        self._dev_tensor(depth, "depth", torch.float32, self.N * H * W)
+        mask = self._mask_tensor(mask, optional=True)
+        if (planes is None) == (params is None):
+            raise EngineError("depth_project: exactly one target, planes (a window) or params with map (a map)")
+        if params is None:
+            self._shaped_tensor(planes, "planes", torch.uint8, (self.N, 2, int(size), int(size)))
+            if map is not None or count is not None or new is not None or clear is not None:
+                raise EngineError("depth_project: map, count, new and clear belong to the map target")
+        else:
+            if map is None or count is None:
+                raise EngineError(f"{'map' if map is None else 'count'}: None")
+            self._shaped_tensor(map, "map", torch.uint8, (self.N, 2, int(params.gz), int(params.gx)))
+            self._shaped_tensor(count, "count", torch.int32, (self.N, 2))
+            if new is not None:
+                self._shaped_tensor(new, "new", torch.int32, (self.N, 2))
+            self._dev_tensor(clear, "clear", torch.uint8, self.N)
+        host = (C.c_double * 6)(float(min_range), float(max_range), float(floor_tol), float(top), float(cell), float(back))
+        self._check(self.lib.mw_depth_project(self.h, host, _ptr(depth), _ptr(mask), int(size), int(flags), _ptr(planes),
+                                              None if params is None else C.byref(params), int(min_points), _ptr(clear), _ptr(map), _ptr(count), _ptr(new),
+                                              _stream_ptr(self.device)), "mw_depth_project")
 
     def debug_set_launch_shape(self, waves_per_env: int = 0, mesh_tile_waves: int = 0, ent_blocks: int = 0, slow_waves: int = 0):
         """Tests and measurements: wavefronts per env of the tile kernels (a divisor of the frame's tile count) and the persistent

@@ -1,6 +1,6 @@
-"""The world queries of the batched env — navigation fields, explored-area maps, egocentric map windows, ray casts —, each one kernel on
-the device with no host value: their value classes (NavField, SeenMap, EgoWindow) and `WorldQueries`, a mixin of MiniWorldVecEnv
-(vec_env.py)."""
+"""The world queries of the batched env — navigation fields, explored-area maps, egocentric map windows, depth projection, ray casts —,
+each one kernel on the device with no host value: their value classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap) and
+`WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
 from __future__ import annotations
 
 import math
@@ -68,6 +68,39 @@ class EgoWindow:
     wall = property(lambda self: self._plane("wall"))
     entity = property(lambda self: self._plane("entity"))
     visible = property(lambda self: self._plane("visible"))
+
+
+class DepthWindow:
+    """A depth-projected egocentric window (MiniWorldVecEnv.depth_window): `planes`, the uint8[N, 2, S, S] device tensor that
+    depth_update() fills, laid out cell for cell like an EgoWindow of the same size, cell, anchor and frame — row 0 the farthest ahead,
+    columns growing to the agent's right —, and its views `floor` (how many pixels of the depth map showed floor in the cell, at most
+    255) and `obstacle` (how many showed something between `floor_tol` and `top` above the floor), each uint8[N, S, S].  `min_range`
+    and `max_range` bound the eye depth of the pixels that count.  The tensor is the caller's: the engine keeps nothing of it."""
+
+    def __init__(self, planes, size, cell, back, frame, min_range, max_range, floor_tol, top):
+        self.planes, self.size, self.cell, self.back, self.frame = planes, size, cell, back, frame
+        self.min_range, self.max_range, self.floor_tol, self.top = min_range, max_range, floor_tol, top
+
+    floor = property(lambda self: self.planes[:, 0])
+    obstacle = property(lambda self: self.planes[:, 1])
+
+
+class DepthMap:
+    """A depth-built floor-plan map (MiniWorldVecEnv.depth_map): `map`, the uint8[N, 2, gz, gx] device tensor that depth_map_update()
+    accumulates on a nav field's grid (`params`: `cell` metres per cell, gx x gz cells from the env's own min_x, min_z), with the views
+    `free` (1 once `min_points` pixels of one depth map showed floor in the cell) and `obstacle` (the same for points between `floor_tol`
+    and `top` above the floor) — a cell may be both, or neither: never seen —, `count`, int32[N, 2], the cells set so far in each, and
+    `new`, int32[N, 2], those the last update added.  The tensors are the caller's, like a SeenMap's."""
+
+    def __init__(self, map, count, new, params, min_points, min_range, max_range, floor_tol, top):
+        self.map, self.count, self.new, self.params, self.min_points = map, count, new, params, min_points
+        self.min_range, self.max_range, self.floor_tol, self.top = min_range, max_range, floor_tol, top
+
+    cell = property(lambda self: self.params.cell)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+    free = property(lambda self: self.map[:, 0])
+    obstacle = property(lambda self: self.map[:, 1])
 
 
 assert eng.NAV_ENTITIES == eng.RAY_ENTITIES == eng.SEEN_ENTITIES == eng.EGO_ENTITIES      # (one table serves the four calls)
@@ -291,6 +324,118 @@ class WorldQueries:
         e.ego_map(w.size, w.cell, w.back, w.wall_radius, w.entity_pad, w.max_range, w.cos_half, w.bits, flags, w.planes, mask, pos, params, src,
                   fill or 0, sample)
         return w.planes if source is None else (w.planes, sample)
+
+    # ------------------------------------------------------------------ depth projection
+    def _depth_sensor(self, where, min_range, max_range, floor_tol, top):
+        """(min_range, max_range, floor_tol, top) of a depth window or map, checked"""
+        min_range, max_range = real(where, "min_range", min_range), real(where, "max_range", max_range)
+        if min_range > max_range:
+            raise ValueError(f"{where}: min_range {min_range!r} > max_range {max_range!r}")
+        floor_tol = real(where, "floor_tol", floor_tol, lo_open=False)
+        top = float(self.engine.cfg.agent_height) if top is None else real(where, "top", top, lo_open=False)
+        if top < floor_tol:
+            raise ValueError(f"{where}: top {top!r} < floor_tol {floor_tol!r}")
+        return min_range, max_range, floor_tol, top
+
+    def _depth_input(self, where, depth):
+        """the depth tensor of a projection: the env's own, or the caller's contiguous float32[N, H, W, 1] / [N, H, W] on the device"""
+        torch, e = self.torch, self.engine
+        if depth is None:
+            if self.depth is None:
+                raise ValueError(f"{where}: this env draws no depth map: make it with want_depth=True, or pass depth=")
+            return self.depth
+        n, H, W = self.num_envs, int(e.cfg.obs_height), int(e.cfg.obs_width)
+        if not (self._is_tensor(depth, (n, H, W, 1), torch.float32) or self._is_tensor(depth, (n, H, W), torch.float32)):
+            raise ValueError(f"{where}: depth is a contiguous float32 tensor [{n}, {H}, {W}, 1] or [{n}, {H}, {W}] on {e.device}")
+        return depth
+
+    def depth_window(self, size=33, cell=0.25, anchor="centre", frame="heading", min_range=0.05, max_range=8.0, floor_tol=0.1, top=None):
+        """An empty depth-projected egocentric window: a DepthWindow, which depth_update() fills.  Nothing is launched.
+
+        size, cell, anchor, frame  exactly as for ego_window(): the two windows line up cell for cell
+        min_range, max_range       the eye depths in metres whose pixels count.  The depth map steps by z * z * 3.8e-4 metres at depth z
+                                   (a 16-bit depth value): 2.4 cm at the default 8 m, a tenth of the default cell; the sky reads 100 and
+                                   never counts
+        floor_tol                  a point within this of the height of the agent's feet is floor
+        top                        a point above floor_tol and up to this height is an obstacle; None: the agent's height — the ceiling
+                                   is neither
+        ValueError for arguments that make no window."""
+        torch, e = self.torch, self.engine
+        size = integer("depth_window", "size", size, 1, eng.EGO_MAX_SIZE)
+        cell = real("depth_window", "cell", cell)
+        if anchor not in ("centre", "bottom"):
+            raise ValueError(f"depth_window: anchor {anchor!r}; have 'centre' and 'bottom'")
+        if frame not in ("heading", "north"):
+            raise ValueError(f"depth_window: frame {frame!r}; have 'heading' and 'north'")
+        sensor = self._depth_sensor("depth_window", min_range, max_range, floor_tol, top)
+        if int(e.cfg.obs_width) * int(e.cfg.obs_height) > eng.DEPTH_MAX_PIXELS:
+            raise ValueError(f"depth_window: frames of {e.cfg.obs_width} x {e.cfg.obs_height} pixels > {eng.DEPTH_MAX_PIXELS}")
+        out = torch.zeros((self.num_envs, 2, size, size), dtype=torch.uint8, device=e.device)
+        return DepthWindow(out, size, cell, size / 2 if anchor == "bottom" else 0.0, frame, *sensor)
+
+    def depth_update(self, w, depth=None, mask=None):
+        """Fills `w` (a DepthWindow) from a depth map, by one kernel (mw_depth_project) with no host value and no synchronisation;
+        returns w.planes.  Every pixel is unprojected with its env's own camera — height, forward displacement, pitch and field of
+        view, per env under domain randomisation — at the place inside the pixel where the engine sampled the depth, and with the pose
+        the device holds NOW.  That is the pose `self.depth` was drawn for after step(), reset(), a drawn rollout() and the terminal
+        step of the next-step mode; it is NOT after a frameless rollout(render=False), whose depth is stale until the next drawn call.
+
+        depth  None: `self.depth` (ValueError without want_depth=True); or a contiguous float32[N, H, W, 1] / [N, H, W] device tensor
+        mask   uint8[N] or bool[N] device tensor: only those envs' rows are read and written
+        Tensors are checked, never converted (EngineError); ValueError for arguments that make no call; nothing is launched then."""
+        if not isinstance(w, DepthWindow):
+            raise ValueError("depth_update: `w` must be a DepthWindow (depth_window())")
+        depth = self._depth_input("depth_update", depth)
+        mask = self._device_mask(mask, "depth_update")
+        self.engine.depth_project(depth, w.min_range, w.max_range, w.floor_tol, w.top, mask, size=w.size, cell=w.cell, back=w.back,
+                                  flags=eng.EGO_NORTH if w.frame == "north" else 0, planes=w.planes)
+        return w.planes
+
+    def depth_map(self, cell=0.25, like=None, min_points=1, min_range=0.05, max_range=8.0, floor_tol=0.1, top=None):
+        """An empty depth-built map over each env's floor plan: a DepthMap, which depth_map_update() accumulates.  Nothing is launched.
+
+        cell        metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
+        like        a NavField or SeenMap whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass no cell then
+        min_points  how many pixels of ONE depth map must fall into a cell to set it, 1 .. 255
+        min_range, max_range, floor_tol, top  as for depth_window()
+        At most 16384 cells (the kernel counts in 64 KiB of LDS): ValueError says "use a larger cell" otherwise."""
+        torch, e = self.torch, self.engine
+        if like is not None:
+            if not isinstance(like, (NavField, SeenMap)):
+                raise ValueError("depth_map: `like` must be a NavField or a SeenMap")
+            if cell != 0.25:
+                raise ValueError("depth_map: with `like` its own grid is used: pass no cell")
+            cell, gx, gz = like.cell, like.gx, like.gz
+        else:
+            cell, gx, gz = self._grid("depth_map", cell)
+        if gx * gz > eng.DEPTH_MAX_CELLS:
+            raise ValueError(f"depth_map: {gx} x {gz} cells > {eng.DEPTH_MAX_CELLS}: use a larger cell")
+        min_points = integer("depth_map", "min_points", min_points, 1, 255)
+        sensor = self._depth_sensor("depth_map", min_range, max_range, floor_tol, top)
+        if int(e.cfg.obs_width) * int(e.cfg.obs_height) > eng.DEPTH_MAX_PIXELS:
+            raise ValueError(f"depth_map: frames of {e.cfg.obs_width} x {e.cfg.obs_height} pixels > {eng.DEPTH_MAX_PIXELS}")
+        params = eng.MwNavParams(float(cell), 0.0, 0.0, int(gx), int(gz), 0, 0)
+        n = self.num_envs
+        return DepthMap(torch.zeros((n, 2, int(gz), int(gx)), dtype=torch.uint8, device=e.device), torch.zeros((n, 2), dtype=torch.int32, device=e.device),
+                        torch.zeros((n, 2), dtype=torch.int32, device=e.device), params, min_points, *sensor)
+
+    def depth_map_update(self, m, depth=None, clear=None, mask=None):
+        """Accumulates a depth map's points in `m` (a DepthMap), by one kernel (mw_depth_project) with no host value and no
+        synchronisation; returns m.new, int32[N, 2], the free and obstacle cells that were set by this call, while m.count carries the
+        totals.  The pose is the one the device holds now, as for depth_update() — not the one a frameless rollout left `self.depth` at.
+
+        depth  None: `self.depth`; or a contiguous float32[N, H, W, 1] / [N, H, W] device tensor
+        clear  uint8[N] or bool[N] device tensor: those envs' maps are zeroed and their counts restarted first — behind a step of the
+               same-step auto-reset, `depth_map_update(m, clear=terminated | truncated)` starts every new episode's map
+        mask   uint8[N] or bool[N] device tensor: only those envs are updated; the mask wins over clear
+        An env whose extent the grid does not cover gets its map zeroed and engine.check() raises once."""
+        if not isinstance(m, DepthMap):
+            raise ValueError("depth_map_update: `m` must be a DepthMap (depth_map())")
+        depth = self._depth_input("depth_map_update", depth)
+        clear, mask = self._device_mask(clear, "depth_map_update", "clear"), self._device_mask(mask, "depth_map_update")
+        self.engine.depth_project(depth, m.min_range, m.max_range, m.floor_tol, m.top, mask, params=m.params, min_points=m.min_points, map=m.map,
+                                  count=m.count, new=m.new, clear=clear)
+        return m.new
 
     # ------------------------------------------------------------------ ray casts
     def raycast(self, direction=None, origin=None, offsets=None, max_t=1.0, radius=0.0, obstacles="walls", mask=None, into=None):
