@@ -27,6 +27,7 @@
 // GL_MAX_SAMPLES, opengl.py:229-231: the reference's own frames in tests/golden/gl_*.npz run through this very code).
 #include "mw_mesh.h"
 #include "mw_kernels.h"
+#include "mw_quad_bin.h"
 
 #define MWQ_WAVES (MWQ_THREADS / 64)
 #define MWQ_CAP_MAX 48        // triangle records staged per env: 48, or 40 with a depth channel (three workgroups per CU either way)
@@ -34,6 +35,18 @@
 #define MWQ_EMPTY 63u
 #ifndef MWQ_TILE_FALLBACK
 #define MWQ_TILE_FALLBACK 1
+#endif
+// binning (phases A and B): 0 steps the edge values along a tile row / a row of quads (mw_quad_bin.h), 1 keeps the flat loops — a lane
+// per (tile, triangle) and per (event, quad) — for variant builds; MWQ_BIN_LANES lanes share a partial event (4 or 2); MWQ_BIN_BOX 1
+// walks a triangle's bounding tiles only
+#ifndef MWQ_BIN_FLAT
+#define MWQ_BIN_FLAT 0
+#endif
+#ifndef MWQ_BIN_LANES
+#define MWQ_BIN_LANES 4
+#endif
+#ifndef MWQ_BIN_BOX
+#define MWQ_BIN_BOX 1
 #endif
 #ifndef MWQ_OCC
 #define MWQ_OCC 6           // wavefronts per SIMD the register allocation aims at (3 workgroups per CU)
@@ -754,6 +767,16 @@ __device__ inline void rasterq_body(
         // (the texture's level-0 geometry follows during phase A: a dependent load that need not hold the copy up)
         // (two loops, so that the copied quads and the computed ones do not share a wavefront's instruction stream: plain copies
         // by source-index arithmetic, then the three threshold quads of every record on their own few lanes)
+#if !MWQ_BIN_FLAT
+        const int tiles_y = H / MW_TILE_H;
+        const uint32_t m_ty = (uint32_t)__builtin_amdgcn_readfirstlane((int)mw_magic16((uint32_t)tiles_y));
+#if MWQ_BIN_BOX
+        // (the tile box of the triangle this lane bins first in phase A — most envs' only trip —, requested ahead of the staging: the
+        // cull records stay in memory, and the load's round trip would stand at the head of the phase)
+        uint32_t box_ahead = 0x00ff00ffu;
+        if (tid < nvis * tiles_y) box_ahead = __float_as_uint(g_cull[(size_t)mw_div16((uint32_t)tid, m_ty) * (MW_CULL_REC / 4)].w);
+#endif
+#endif
         for (int i = tid; i < nvis * R::CT; i += MWQ_THREADS) {
             const int p = i / R::CT, q = i - p * R::CT;
             const int kq = q - 4, k = kq / R::TQ, j = kq - k * R::TQ;                    // thresholds: edge k, quad j of it
@@ -777,6 +800,7 @@ __device__ inline void rasterq_body(
             my_tex = __float_as_int(s_rec[tid * R::NQ + R::SH].w);
             if (my_tex >= 0) { my_w = texd[my_tex].w; my_h = texd[my_tex].h; my_nl = texd[my_tex].nlevels; }
         }
+#if MWQ_BIN_FLAT
         const uint32_t m_nvis = (uint32_t)__builtin_amdgcn_readfirstlane((int)mw_magic16((uint32_t)max(nvis, 1)));
         for (int i = tid; i < n_tiles * nvis; i += MWQ_THREADS) {
             const int t = (int)mw_div16((uint32_t)i, m_nvis), p = i - t * nvis;
@@ -797,6 +821,45 @@ __device__ inline void rasterq_body(
                 }
             }
         }
+#else
+        // a lane per (triangle, tile row): the record and the tile thresholds once, the edge triple at the row's first tile, then one add
+        // per edge and tile column (the lanes of a triangle are neighbours: they read the same record, and file into different tiles)
+        for (int i = tid; i < nvis * tiles_y; i += MWQ_THREADS) {
+            const int p = (int)mw_div16((uint32_t)i, m_ty), ty = i - p * tiles_y;
+            const float4 *rec = s_rec + p * R::NQ;
+            const float4 a0 = rec[0], a1 = rec[1], a2 = rec[2], c0 = rec[R::CT], c1 = rec[R::CT + 1];
+            const int32_t A[3] = {__float_as_int(a0.x), __float_as_int(a0.y), __float_as_int(a0.z)}, B[3] = {__float_as_int(a0.w), __float_as_int(a1.x), __float_as_int(a1.y)};
+            const int32_t C[3] = {__float_as_int(a1.z), __float_as_int(a1.w), __float_as_int(a2.x)};
+            const int32_t T[3] = {__float_as_int(c0.x), __float_as_int(c0.y), __float_as_int(c0.z)}, F[3] = {__float_as_int(c0.w), __float_as_int(c1.x), __float_as_int(c1.y)};
+            int tx0 = 0, tx1 = tiles_x - 1;
+#if MWQ_BIN_BOX
+            // (the cull record's tile box holds every pixel whose samples the triangle can cover: the edge test alone also lists tiles
+            // beyond the vertex bounds, where the triangle owns no sample)
+            const MwTileBox box = mw_qb_box(i == tid ? box_ahead : __float_as_uint(g_cull[(size_t)p * (MW_CULL_REC / 4)].w), tiles_x, tiles_y);
+            if (!mw_qb_box_row(box, ty)) continue;
+            tx0 = box.x0; tx1 = box.x1;
+#endif
+            MwEdge3 ev = mw_qb_start(A, B, C, tx0 * MW_TILE_W, H - MW_TILE_H - ty * MW_TILE_H);
+            const MwEdge3 dx = mw_qb_delta(A, B, MW_TILE_W, 0);
+            for (int tx = tx0, t = ty * tiles_x + tx0; tx <= tx1; ++tx, ++t, mw_qb_step(ev, dx)) {
+                bool touch, full;
+                mw_qb_verdict(ev, T, F, touch, full);
+                if (touch) {
+                    const uint32_t slot = atomicAdd(&s_tcnt[t], 1u);
+                    if (slot < MWQ_SLOTS) {
+                        const uint32_t e = (uint32_t)t * MWQ_SLOTS + slot;
+                        s_tlist[e] = (uint8_t)p;
+                        if (full) s_tmask[e] = 0xFFFFFFFFu;
+                        else s_pe[atomicAdd(&s_misc[16], 1u)] = e | ((uint32_t)p << 16);
+                    }
+                    if (full) {
+                        const uint32_t f = atomicAdd(&s_tfull[t], 1u) & 255u;
+                        if (f < 3u) atomicOr(&s_tfull[t], (uint32_t)p << (8u + 8u * f));
+                    }
+                }
+            }
+        }
+#endif
         if (tid < nvis) {
             float *r = reinterpret_cast<float *>(s_rec + tid * R::NQ + R::SH);
             const uint32_t pot = ((my_w & (my_w - 1u)) | (my_h & (my_h - 1u))) == 0u ? 1u : 0u;
@@ -811,6 +874,7 @@ __device__ inline void rasterq_body(
         if ((dbg >> 13) == 2) return;
         // ---- B: (quad, triangle) pairs of the tiles a triangle crosses -----------------------------------------------------
         const int npe = __builtin_amdgcn_readfirstlane((int)s_misc[16]);
+#if MWQ_BIN_FLAT
         for (int i = tid; i < ((npe * 16 + 63) & ~63); i += MWQ_THREADS) {
             const int j = i >> 4, qi = i & 15;
             bool touch = false, full = false;
@@ -834,6 +898,55 @@ __device__ inline void rasterq_body(
             const int sh = lane & 48;
             if (j < npe && qi == 0) s_tmask[e] = (uint32_t)((tm >> sh) & 0xFFFFull) | ((uint32_t)((fm >> sh) & 0xFFFFull) << 16);
         }
+#else
+        // MWQ_BIN_LANES lanes per event, each over BQ neighbouring quads of one row of the tile (bits q0 .. q0 + BQ - 1 of the masks): the
+        // edge triple at the first of them, one add per edge and quad; the masks are built in registers and joined inside the lane group
+        // by DPP moves.  A lane's atomics go out together: BQ counters first, then the ids.
+        constexpr int BL = MWQ_BIN_LANES, BQ = 16 / BL;
+        static_assert(BL == 4 || BL == 2, "lanes per partial event");
+        for (int i = tid; i < ((npe * BL + 63) & ~63); i += MWQ_THREADS) {
+            const int j = i / BL, q0 = (i & (BL - 1)) * BQ;
+            uint32_t word = 0u, e = 0u;
+            if (j < npe) {
+                const uint32_t ep = s_pe[j];
+                e = ep & 0xFFFFu;
+                const int t = (int)(e / MWQ_SLOTS), p = (int)(ep >> 16);
+                const int ty = (int)mw_div16((uint32_t)t, m_tx), tx = t - ty * tiles_x;
+                const int qx = tx * 8 + (q0 & 7), qy = ty * 2 + (q0 >> 3);
+                const float4 *rec = s_rec + p * R::NQ;
+                const float4 a0 = rec[0], a1 = rec[1], a2 = rec[2], c1 = rec[R::CT + 1], c2 = rec[R::CT + 2];
+                const int32_t A[3] = {__float_as_int(a0.x), __float_as_int(a0.y), __float_as_int(a0.z)}, B[3] = {__float_as_int(a0.w), __float_as_int(a1.x), __float_as_int(a1.y)};
+                const int32_t C[3] = {__float_as_int(a1.z), __float_as_int(a1.w), __float_as_int(a2.x)};
+                const int32_t T[3] = {__float_as_int(c1.z), __float_as_int(c1.w), __float_as_int(c2.x)}, F[3] = {__float_as_int(c2.y), __float_as_int(c2.z), __float_as_int(c2.w)};
+                MwEdge3 ev = mw_qb_start(A, B, C, qx * 2, H - 2 - qy * 2);
+                const MwEdge3 dx = mw_qb_delta(A, B, 2, 0);
+                uint32_t tb = 0u, fb = 0u;
+#pragma unroll
+                for (int k = 0; k < BQ; ++k, mw_qb_step(ev, dx)) {
+                    bool touch, full;
+                    mw_qb_verdict(ev, T, F, touch, full);
+                    tb |= (touch ? 1u : 0u) << k;
+                    fb |= (full ? 1u : 0u) << k;
+                }
+                // the quad's own list: a place by the counter in bits 24-30, the id into it (four 6-bit places), bit 31 = covered by some triangle
+                uint32_t *qd = s_qids + qy * QW + qx;
+                uint32_t was[BQ];
+#pragma unroll
+                for (int k = 0; k < BQ; ++k) was[k] = (tb >> k) & 1u ? atomicAdd(qd + k, 1u << 24) : 0u;
+#pragma unroll
+                for (int k = 0; k < BQ; ++k) {
+                    const uint32_t slot = (was[k] >> 24) & 127u;
+                    const uint32_t v = ((fb >> k) & 1u ? 0x80000000u : 0u) | (slot < 4u ? (uint32_t)p << (6u * slot) : 0u);
+                    if (((tb >> k) & 1u) && v) atomicOr(qd + k, v);
+                }
+                word = (tb << q0) | (fb << (16 + q0));
+            }
+            // (every lane of a group is in the loop, with a zero word where there is no event: quad_perm [1 0 3 2], then [2 3 0 1])
+            word |= (uint32_t)__builtin_amdgcn_mov_dpp((int)word, 0xB1, 0xF, 0xF, true);
+            if (BL == 4) word |= (uint32_t)__builtin_amdgcn_mov_dpp((int)word, 0x4E, 0xF, 0xF, true);
+            if (j < npe && q0 == 0) s_tmask[e] = word;
+        }
+#endif
         __syncthreads();
 
         stamp(3);
