@@ -948,6 +948,76 @@ int mw_depth_project(mw_engine *e, const double *host_params /* [6] on the host:
                      const uint8_t *d_clear /* or NULL */, uint8_t *d_map /* [N][2][gz][gx] */, int32_t *d_count /* [N][2] */,
                      int32_t *d_new /* [N][2] or NULL */, void *stream);
 
+/* ---- label frames ----------------------------------------------------------------------------------------------------------------
+ * What every pixel of an env's observation shows — the third sensor image beside colour and depth (a semantic / instance image) —, cast
+ * on the device from the live world: the label of pixel (u, v) is what the ray from the env's camera through the pixel's depth sample
+ * meets first.  The reference has no such call; it stands in for what its users write against env.entities and the GL matrices
+ * (miniworld.py:1197-1221 gluPerspective and gluLookAt, entity.py:150-161 MeshEnt.render, entity.py:409-432 Box.render, entity.py:205-207
+ * the frames' transform, objmesh.py:280-292, miniworld.py:512 GL_CULL_FACE).  The ray is parametrised by eye depth t, so t is directly
+ * comparable with the depth output of mw_step / mw_render, whose own 16-bit steps it is free of.
+ *
+ * All arithmetic is float64, only + - * /, sqrt and the engine's deterministic sin / cos, uncontracted, in exactly this order (W x H the
+ * engine's frame, pixel row v from the top, column u; the camera terms o, f, rt, sp, cp, th, tx and the sample (sub_x, sub_y) are
+ * mw_depth_project's; a float is widened first):
+ *   eye       ex = ox + fwd_disp * fx;  ey = agent_y + height;  ez = oz + fwd_disp * fz
+ *   ray       xn = (((double)u + sub_x) * 2.0) / (double)W - 1.0;  yn = 1.0 - (((double)v + sub_y) * 2.0) / (double)H
+ *             lat = xn * tx;  yt = yn * th;  up = sp + yt * cp;  fwd = cp - yt * sp
+ *             dx = fwd * fx + lat * rtx;  dy = up;  dz = fwd * fz + lat * rtz;  the point at eye depth t is eye + t * d
+ *             a NaN in the eye or in d: the pixel shows nothing
+ * Candidates, in this order; a candidate t counts when near <= t && t <= far && t < best, from best = +infinity, and then best = t + 0.0:
+ * equal t goes to the lowest code, a NaN fails every test.
+ *   1. the static polygons of the env's geometry set in index order, code = the index.  A vertex is (x, y, z) = v[i]; under MW_POLY_XF,
+ *      with (s, c) = sincos((double)xf[3] * M_PI / 180.0), it is ((c * x + s * z) + xf[0], y + xf[1], (c * z - s * x) + xf[2]).
+ *        plane   a = V1 - V0, b = V2 - V0;  n = (ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx)
+ *                k = ((nx * (V0x - ex) + ny * (V0y - ey)) + nz * (V0z - ez))
+ *                den = ((nx * dx + ny * dy) + nz * dz); none unless den < 0 or den > 0;  t = k / den
+ *        inside  p = (ex + t * dx, ey + t * dy, ez + t * dz); for every edge V_i -> V_(i + 1 mod nv), e = V_(i + 1) - V_i,
+ *                m = (ny * ez - nz * ey, nz * ex - nx * ez, nx * ey - ny * ex), mc = ((mx * V_ix + my * V_iy) + mz * V_iz):
+ *                ((mx * px + my * py) + mz * pz) - mc >= 0.0 — the edge itself counts, so two polygons that share it leave no hole
+ *   2. the slots of kind MW_ENT_BOX in slot order, code = MW_RAY_ENT + slot: the oriented box of Box.render.  (s, c) = sincos(dir);
+ *      q = eye - pos;  o = (c * qx - s * qz, qy, s * qx + c * qz);  l = (c * dx - s * dz, dy, s * dx + c * dz); per axis with lo .. hi =
+ *      -sx / 2 .. sx / 2, 0 .. sy, -sz / 2 .. sz / 2:  l == 0: none unless o >= lo && o <= hi; else t1 = (lo - o) / l, t2 = (hi - o) / l,
+ *      tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1, none unless tn <= tf; enter = the largest tn, leave = the smallest tf; a hit
+ *      iff enter <= leave, and t = enter: the entry point.  (|dir| >= 1e6 or NaN, outside sincos' domain: the slot shows nothing.)
+ *   3. the slots of kind MW_ENT_MESH in slot order, code = MW_RAY_ENT + slot:
+ *      MW_LABEL_MESH_BOUNDS  the upright cylinder of the slot's radius R and height on its pos, side and caps: w = (ex - pos.x, ez - pos.z);
+ *                A = dx * dx + dz * dz; B = wx * dx + wz * dz; C = (wx * wx + wz * wz) - R * R;  A == 0: none unless C <= 0; else
+ *                disc = B * B - A * C, none unless disc >= 0, q = sqrt(disc), enter = (-B - q) / A, leave = (-B + q) / A; then the y axis
+ *                as a box's with o = ey - pos.y, lo .. hi = 0 .. height; t = enter
+ *      MW_LABEL_MESH_EXACT   the triangles of the slot's uploaded mesh: vertex (x, y, z) becomes, with (s, c) = sincos(dir), rx = c * x +
+ *                s * z, rz = c * z - s * x, the point (pos.x + scale * rx, pos.y + scale * y, pos.z + scale * rz); plane and inside test
+ *                as for a polygon of three vertices, but none unless den < 0: the reference draws with GL_CULL_FACE, a triangle seen from
+ *                behind is not there.  The slot's t is the smallest of its triangles'.
+ * Every slot whose kind is not MW_ENT_NONE counts, the carried one included: it is drawn, so it is labelled.  MW_ENT_FRAME slots are
+ * drawn through the polygon list and labelled there.
+ *
+ * The outputs, device pointers, every one but d_class may be NULL:
+ *   d_class       uint8[N][H][W]   MW_LABEL_NOTHING (sky), _FLOOR, _CEILING, _WALL, _FRAME, _BOX, _MESH.  A static polygon is a _FRAME with
+ *                                  MW_POLY_ENTITY, else a _WALL with MW_POLY_QUAD, else a _FLOOR when the normal of its own vertices
+ *                                  (az * bx - ax * bz above, before any transform) points up, > 0, else a _CEILING
+ *   d_code        int32[N][H][W]   the code above, -1 for nothing
+ *   d_depth       float32[N][H][W] the winning t rounded once, (float)far for nothing; mw_depth_project takes it
+ *   d_ent_pixels  int32[N][E]      the pixels that show each slot
+ *   d_ent_box     int32[N][E][4]   their bounding box u0, v0, u1, v1, inclusive; W, H, -1, -1 for a slot without a pixel
+ * The result of a pixel is the minimum of (t, place in the order above) over all candidates: it does not depend on the kernel's schedule.
+ * Rows of envs under a zero mask byte are neither read nor written. */
+enum { MW_LABEL_NOTHING = 0, MW_LABEL_FLOOR = 1, MW_LABEL_CEILING = 2, MW_LABEL_WALL = 3, MW_LABEL_FRAME = 4, MW_LABEL_BOX = 5, MW_LABEL_MESH = 6 };
+#define MW_LABEL_MESH_EXACT  0          /* flags: mesh slots as their own triangles */
+#define MW_LABEL_MESH_BOUNDS 1          /* flags: mesh slots as their bounding cylinders */
+#define MW_LABEL_UNPRUNED    2          /* flags, tests and measurements: every triangle against every pixel — the same bits, slower */
+struct mw_label_params {
+    double near, far;           /* the eye depths a hit may have: the frame's are 0.04 and 100 */
+    int32_t flags, pad;         /* MW_LABEL_MESH_* */
+};
+typedef struct mw_label_params mw_label_params;
+/* One kernel, one workgroup per env, asynchronous on `stream`; it reads no host value except params (during the call), reads live arrays
+ * only and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched: a null engine, params or d_class;
+ * flags other than MW_LABEL_MESH_BOUNDS and MW_LABEL_UNPRUNED; a near or far that is not finite, near < 0 (the kernel orders t by its bits) or near >= far; a
+ * frame so wide that not one row of it fits the kernel's 64 KiB of LDS beside the staged scene, or a scene of more than 61440 polygons per
+ * set or 4095 entity slots (a pixel's code is kept in 16 bits there); more workgroups than a launch holds. */
+int mw_label_frame(mw_engine *e, const mw_label_params *params, const uint8_t *d_mask, uint8_t *d_class, int32_t *d_code, float *d_depth,
+                   int32_t *d_ent_pixels, int32_t *d_ent_box, void *stream);
+
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.

@@ -12,6 +12,7 @@
 #include "mw_seen.h"
 #include "mw_ego.h"
 #include "mw_depth.h"
+#include "mw_label.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -304,6 +305,14 @@ extern "C" __global__ void mw_ego_kernel(MwRayArgs a, mwego::Window w, mwseen::S
 extern "C" __global__ void mw_depth_kernel(MwRayArgs a, const double *__restrict__ cam, mwdepth::Sensor s, mwdepth::Window w, mw_nav_params p, int min_points,
                                            int wide, const float *__restrict__ depth, const uint8_t *__restrict__ mask, const uint8_t *__restrict__ clear,
                                            uint8_t *__restrict__ planes, uint8_t *__restrict__ map, int32_t *__restrict__ count, int32_t *__restrict__ newly);
+
+// label frames (mw_label.hip; the arithmetic, the phases, MwLabelArgs and the launch constants: mw_label.h; the launch: mwpolicy::label_launch).
+// The parameters are the caller's mw_label_params by value.  Grid N workgroups of MW_LABEL_THREADS lanes, mwlabel::plan_bytes(band_rows * W,
+// chunk, E) bytes of dynamic LDS; env b's rows of the outputs where mask is null or mask[b] != 0; every output but cls may be null;
+// prune == 0: the mesh phase without its pruning rectangle (MW_LABEL_UNPRUNED).
+extern "C" __global__ void mw_label_kernel(MwLabelArgs a, mw_label_params p, int band_rows, int chunk, int prune, const uint8_t *__restrict__ mask,
+                                           uint8_t *__restrict__ cls, int32_t *__restrict__ code, float *__restrict__ depth,
+                                           int32_t *__restrict__ ent_pixels, int32_t *__restrict__ ent_box);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -10,6 +10,7 @@
 #include "mw_seen.h"            // MW_SEEN_THREADS, MW_SEEN_TAIL_BYTES
 #include "mw_ego.h"             // MW_EGO_THREADS, mwego::staged_bytes
 #include "mw_depth.h"           // MW_DEPTH_THREADS, MW_DEPTH_CELL_BYTES, MW_DEPTH_MAX_CELLS
+#include "mw_label.h"           // MW_LABEL_THREADS, MW_LABEL_CHUNK, MW_LABEL_MAX_POLYS, MW_LABEL_MAX_ENTS, mwlabel::plan_bytes
 #include "mw_shape.h"
 #include "mw_snapframes.h"      // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -358,6 +359,26 @@ inline DepthLaunch depth_launch(int N, long long cells)
     const long long least = 2 * (MW_DEPTH_THREADS / 64);
     const size_t lds = ((size_t)(cells > least ? cells : least) * MW_DEPTH_CELL_BYTES + 15) / 16 * 16;
     return {(unsigned long long)N, MW_DEPTH_THREADS, lds, lds <= 64 * 1024};
+}
+
+// Label frames (mw_label_frame; kernel: mw_label.hip): a workgroup of MW_LABEL_THREADS lanes per env.  Its LDS (mwlabel::plan_bytes)
+// holds the staged scene — min(max_polys, MW_LABEL_CHUNK) polygons of 160 bytes at a time, 72 + 20 bytes per entity slot — and 10 bytes
+// per pixel of a band of whole rows, the bits of t and a 16-bit code; the frame is labelled band by band, band_rows rows at a time: as
+// many as fit 64 KiB, the whole frame where it does (80 x 60: one band of 48 000 bytes; 84 x 84: two; 160 x 120: four).  fits: a row
+// fits, and a 16-bit code can name every polygon and slot — the caller refuses what does not.
+struct LabelLaunch { unsigned long long grid; int threads; size_t lds; int band_rows, chunk; bool fits; };
+inline LabelLaunch label_launch(int N, int W, int H, int max_polys, int max_ents)
+{
+    const int chunk = max_polys < 1 ? 1 : (max_polys < MW_LABEL_CHUNK ? max_polys : MW_LABEL_CHUNK);
+    LabelLaunch l{(unsigned long long)N, MW_LABEL_THREADS, 0, 0, chunk, false};
+    if (W < 1 || H < 1 || max_polys > MW_LABEL_MAX_POLYS || max_ents < 0 || max_ents > MW_LABEL_MAX_ENTS) return l;
+    const size_t scene = mwlabel::plan_bytes(0, chunk, max_ents) + 16;       // (+ 16: the sum is rounded up once more with the pixels)
+    if (scene >= 64 * 1024) return l;
+    const long long rows = (long long)((64 * 1024 - scene) / ((size_t)W * MW_LABEL_PIXEL_BYTES));
+    l.band_rows = (int)(rows < (long long)H ? rows : (long long)H);
+    l.fits = l.band_rows >= 1;
+    l.lds = l.fits ? mwlabel::plan_bytes(l.band_rows * W, chunk, max_ents) : 0;
+    return l;
 }
 
 }  // namespace mwpolicy

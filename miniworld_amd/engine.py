@@ -137,6 +137,13 @@ EGO_MAX_SIZE = 128                      # MW_EGO_MAX_SIZE
 DEPTH_MAX_PIXELS = 65535                # MW_DEPTH_MAX_PIXELS
 DEPTH_MAX_CELLS = 16384                 # the cells of a depth window or map: 4 bytes of LDS each (csrc/mw_depth.h)
 
+LABEL_NOTHING, LABEL_FLOOR, LABEL_CEILING, LABEL_WALL, LABEL_FRAME, LABEL_BOX, LABEL_MESH = range(7)       # MW_LABEL_* classes
+LABEL_MESH_EXACT, LABEL_MESH_BOUNDS, LABEL_UNPRUNED = 0, 1, 2           # MW_LABEL_* flags
+
+
+class MwLabelParams(C.Structure):
+    _fields_ = [("near", C.c_double), ("far", C.c_double), ("flags", C.c_int32), ("pad", C.c_int32)]
+
 
 class MwPlanTrace(C.Structure):
     _fields_ = [("agent_pos", C.c_void_p), ("agent_dir", C.c_void_p), ("carrying", C.c_void_p), ("ent_pos", C.c_void_p), ("ent_slot", C.c_int32)]
@@ -236,6 +243,7 @@ SIGNATURES = {
     "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
     "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
     "mw_depth_project": _sig(vp, P(C.c_double), vp, vp, i32, i32, vp, P(MwNavParams), i32, vp, vp, vp, vp, vp),
+    "mw_label_frame": _sig(vp, vp, vp, vp, vp, vp, vp, vp, vp),        # (params: an MwLabelParams by reference)
     "mw_debug_set_launch_shape": _sig(vp, C.c_int, C.c_int, C.c_int, C.c_int),
     "mw_pcg64_draws": _sig(C.c_uint64, i32, vp, vp),
     "mw_selftest_rcp": _sig(vp, vp, vp),
@@ -639,6 +647,27 @@ class Engine:
         self._check(self.lib.mw_depth_project(self.h, host, _ptr(depth), _ptr(mask), int(size), int(flags), _ptr(planes),
                                               None if params is None else C.byref(params), int(min_points), _ptr(clear), _ptr(map), _ptr(count), _ptr(new),
                                               _stream_ptr(self.device)), "mw_depth_project")
+
+    # -- label frames --------------------------------------------------------------------
+    def label_frame(self, params: MwLabelParams, cls, code=None, depth=None, ent_pixels=None, ent_box=None, mask=None):
+        """mw_label_frame: for the envs under `mask` (uint8[N], device; None = all) what every pixel of the env's observation shows — the
+        first thing the ray through the pixel's depth sample meets among the static polygons, the Box slots and the mesh slots (their
+        triangles, or with LABEL_MESH_BOUNDS in params.flags their cylinders) within params.near .. params.far of eye depth: `cls`
+        (uint8[N, H, W], LABEL_*), `code` (int32[N, H, W]: a polygon's index, RAY_ENT + slot, -1), `depth` (float32[N, H, W]: the eye
+        depth, far for nothing), `ent_pixels` (int32[N, E]) and `ent_box` (int32[N, E, 4]: u0, v0, u1, v1); every output but `cls` may be
+        None.  One kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before
+        the library is called."""
+        import torch
+        if cls is None:
+            raise EngineError("cls: None")
+        mask = self._mask_tensor(mask, optional=True)
+        for t, name, dtype, shape in ((cls, "cls", torch.uint8, (self.N, self.H, self.W)), (code, "code", torch.int32, (self.N, self.H, self.W)),
+                                      (depth, "depth", torch.float32, (self.N, self.H, self.W)), (ent_pixels, "ent_pixels", torch.int32, (self.N, self.E)),
+                                      (ent_box, "ent_box", torch.int32, (self.N, self.E, 4))):
+            if t is not None:
+                self._shaped_tensor(t, name, dtype, shape)
+        self._check(self.lib.mw_label_frame(self.h, C.byref(params), _ptr(mask), _ptr(cls), _ptr(code), _ptr(depth), _ptr(ent_pixels), _ptr(ent_box),
+                                            _stream_ptr(self.device)), "mw_label_frame")
 
     def debug_set_launch_shape(self, waves_per_env: int = 0, mesh_tile_waves: int = 0, ent_blocks: int = 0, slow_waves: int = 0):
         """Tests and measurements: wavefronts per env of the tile kernels (a divisor of the frame's tile count) and the persistent

@@ -1,5 +1,6 @@
-"""The world queries of the batched env — navigation fields, explored-area maps, egocentric map windows, depth projection, ray casts —,
-each one kernel on the device with no host value: their value classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap) and
+"""The world queries of the batched env — navigation fields, explored-area maps, egocentric map windows, depth projection, label frames,
+ray casts —, each one kernel on the device with no host value: their value classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap,
+LabelFrame) and
 `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
 from __future__ import annotations
 
@@ -101,6 +102,28 @@ class DepthMap:
     gz = property(lambda self: self.params.gz)
     free = property(lambda self: self.map[:, 0])
     obstacle = property(lambda self: self.map[:, 1])
+
+
+class LabelFrame:
+    """A label frame (MiniWorldVecEnv.label_frame): what every pixel of `vec.obs` shows, as label_update() casts it.  `cls`, uint8[N, H, W]:
+    0 nothing (sky), 1 floor, 2 ceiling, 3 wall, 4 a static frame (ImageFrame, TextFrame), 5 a Box, 6 a mesh object (engine.LABEL_*);
+    `code`, int32[N, H, W]: the static polygon's index, engine.RAY_ENT + slot for an entity, -1 for nothing; `slot`, a view computed
+    from it: the entity slot, -1 off entities; `depth`, float32[N, H, W]: the eye depth in metres, `far` for nothing — vec.depth without
+    its 16-bit steps, and depth_update(w, depth=f.depth) takes it; `ent_pixels`, int32[N, E]: the pixels that show each slot;
+    `ent_box`, int32[N, E, 4]: their box u0, v0, u1, v1 inclusive, (W, H, -1, -1) for a slot out of view.  The tensors not asked for are
+    None.  `meshes` ("exact": a mesh object's own triangles; "bounds": its bounding cylinder), `near` and `far` say what was cast.
+    The tensors are the caller's: the engine keeps nothing of them."""
+
+    def __init__(self, cls, code, depth, ent_pixels, ent_box, meshes, near, far):
+        self.cls, self.code, self.depth, self.ent_pixels, self.ent_box = cls, code, depth, ent_pixels, ent_box
+        self.meshes, self.near, self.far = meshes, near, far
+
+    @property
+    def slot(self):
+        """int32[N, H, W]: the entity slot each pixel shows, -1 off entities (a new tensor); None without `code`"""
+        if self.code is None:
+            return None
+        return (self.code - eng.RAY_ENT).masked_fill_(self.code < eng.RAY_ENT, -1)
 
 
 assert eng.NAV_ENTITIES == eng.RAY_ENTITIES == eng.SEEN_ENTITIES == eng.EGO_ENTITIES      # (one table serves the four calls)
@@ -436,6 +459,52 @@ class WorldQueries:
         self.engine.depth_project(depth, m.min_range, m.max_range, m.floor_tol, m.top, mask, params=m.params, min_points=m.min_points, map=m.map,
                                   count=m.count, new=m.new, clear=clear)
         return m.new
+
+    # ------------------------------------------------------------------ label frames
+    MESHES = {"exact": eng.LABEL_MESH_EXACT, "bounds": eng.LABEL_MESH_BOUNDS}
+
+    def label_frame(self, meshes="exact", code=True, depth=False, stats=False, near=0.04, far=100.0):
+        """An empty label frame: a LabelFrame, which label_update() fills.  Nothing is launched.
+
+        meshes     "exact": a mesh object (ball, key, ...) is labelled where its own triangles show; "bounds": where its bounding cylinder
+                   does — cheaper, and a little wider than the object
+        code       with the per-pixel codes (and `slot`); False: the class plane alone
+        depth      with the per-pixel eye depth
+        stats      with the per-slot pixel counts and boxes (detection targets)
+        near, far  the eye depths a hit may have; the defaults are the frame's own planes
+        ValueError for arguments that make no frame."""
+        torch, e = self.torch, self.engine
+        if not isinstance(meshes, str) or meshes not in self.MESHES:
+            raise ValueError(f"label_frame: meshes {meshes!r}; have {sorted(self.MESHES)}")
+        for name, v in (("code", code), ("depth", depth), ("stats", stats)):
+            if not isinstance(v, bool):
+                raise ValueError(f"label_frame: {name} must be True or False, not {v!r}")
+        near, far = real("label_frame", "near", near, lo_open=False), real("label_frame", "far", far)
+        if near >= far:
+            raise ValueError(f"label_frame: near {near!r} >= far {far!r}")
+        n, H, W, E = self.num_envs, int(e.cfg.obs_height), int(e.cfg.obs_width), int(e.E)
+        new = lambda shape, dtype, fill: torch.full(shape, fill, dtype=dtype, device=e.device)
+        box = None
+        if stats:
+            box = torch.tensor([W, H, -1, -1], dtype=torch.int32, device=e.device).repeat(n, E, 1)
+        return LabelFrame(new((n, H, W), torch.uint8, 0), new((n, H, W), torch.int32, -1) if code else None,
+                          new((n, H, W), torch.float32, far) if depth else None, new((n, E), torch.int32, 0) if stats else None, box, meshes, near, far)
+
+    def label_update(self, f, mask=None):
+        """Fills `f` (a LabelFrame) with what every pixel of the current observation shows, by one kernel (mw_label_frame) with no host
+        value and no synchronisation; returns f.cls.  The label of a pixel is the first thing the ray through the pixel's depth sample
+        meets — a static polygon as drawn, a Box, a mesh object —, cast in float64 with each env's own camera and the pose the device
+        holds NOW (the one `vec.obs` was drawn for after step(), reset() and a drawn rollout()).  The carried object is drawn, so it is
+        labelled.  Nothing of the engine changes.
+
+        mask   uint8[N] or bool[N] device tensor: only those envs' rows are read and written
+        Tensors are checked, never converted (EngineError); ValueError for arguments that make no call; nothing is launched then."""
+        if not isinstance(f, LabelFrame):
+            raise ValueError("label_update: `f` must be a LabelFrame (label_frame())")
+        mask = self._device_mask(mask, "label_update")
+        params = eng.MwLabelParams(f.near, f.far, self.MESHES[f.meshes], 0)
+        self.engine.label_frame(params, f.cls, f.code, f.depth, f.ent_pixels, f.ent_box, mask)
+        return f.cls
 
     # ------------------------------------------------------------------ ray casts
     def raycast(self, direction=None, origin=None, offsets=None, max_t=1.0, radius=0.0, obstacles="walls", mask=None, into=None):

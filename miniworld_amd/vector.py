@@ -74,7 +74,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
                  frame_reuse: bool = True, frame_cache: int = 4, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset",
-                 levels=None, level_generator=None, reset_seeds=None, info_state=None, seen_map=None, ego_map=None, depth_map=None, **kwargs):
+                 levels=None, level_generator=None, reset_seeds=None, info_state=None, seen_map=None, ego_map=None, depth_map=None, label_frame=None, **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
         False draws every env on every step, for consumers that write into the returned observation tensor (module docstring).
@@ -108,7 +108,14 @@ class MiniWorldVectorEnv(VectorEnvBase):
         (want_depth is switched on; want_depth=False beside it is refused), reset() and every step() project the new depth map into an
         egocentric window on the device (`self.depth_win`, a DepthWindow; one kernel) and add info["depth_map"], uint8[N, 2, S, S]: the
         floor and obstacle points per cell, the map a policy without simulator state may have — laid out like ego_map's planes, which
-        are its labels.  A copy: it stays valid after the next step.  None (the default) adds nothing and calls nothing."""
+        are its labels.  A copy: it stays valid after the next step.  None (the default) adds nothing and calls nothing.
+        label_frame: a dict of MiniWorldVecEnv.label_frame()'s arguments (an empty one for its defaults) — reset() and every step() cast
+        what each pixel of the new observation shows on the device (`self.label`, a LabelFrame; one kernel) and add info["label"]: that
+        LabelFrame itself, whose tensors the next step rewrites (clone what must outlive it).  For an env whose episode ended with the
+        step the labels show what the device holds, like the observation under the same-step auto-reset.  None (the default) adds
+        nothing and calls nothing."""
+        if label_frame is not None and not isinstance(label_frame, dict):
+            raise ValueError(f"label_frame: need a dict of MiniWorldVecEnv.label_frame()'s arguments or None, not {label_frame!r}")
         if depth_map is not None:
             if not isinstance(depth_map, dict):
                 raise ValueError(f"depth_map: need a dict of MiniWorldVecEnv.depth_window()'s arguments or None, not {depth_map!r}")
@@ -164,6 +171,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
         self._seen_clear = None         # next-step: the envs whose next step is their reset step
         self.ego = None if ego_map is None else self.vec.ego_window(**ego_map)
         self.depth_win = None if depth_map is None else self.vec.depth_window(**depth_map)
+        self.label = None if label_frame is None else self.vec.label_frame(**label_frame)
         if levels is not None:
             from .vec_env import EnvSnapshot
             self.vec.set_levels(levels if isinstance(levels, EnvSnapshot) else self.vec.make_levels(levels), level_generator)
@@ -226,13 +234,20 @@ class MiniWorldVectorEnv(VectorEnvBase):
             info["depth_map"] = self._out(planes) if self.to_numpy else planes.clone()
         return info
 
+    def _label_info(self, info):
+        """label_frame: one label_update() behind the step or reset; the LabelFrame itself (its tensors are rewritten by the next step)"""
+        if self.label is not None:
+            self.vec.label_update(self.label)
+            info["label"] = self.label
+        return info
+
     def reset(self, *, seed: int | None = None, options: dict | None = None):
         """Env i is seeded with seed + i (gymnasium's convention for an integer seed); with levels= every env starts a level of the
         bank and the seed is not used."""
         obs = self.vec.reset(seed)
         if self._first_next_seed is not None:       # (reset() lays out seed + N + i; the caller's first choices stand)
             self.vec.next_seed.copy_(self._first_next_seed)
-        return self._out(self._obs(obs)), self._state_info(self._depth_info(self._ego_info(self._seen_info({}, None, True))))
+        return self._out(self._obs(obs)), self._state_info(self._label_info(self._depth_info(self._ego_info(self._seen_info({}, None, True)))))
 
     def step(self, actions):
         torch = self.vec.torch
@@ -268,6 +283,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
         self._seen_info(info, term | trunc, False)
         self._ego_info(info)
         self._depth_info(info)
+        self._label_info(info)
         self._state_info(info)
         return self._out(self._obs(obs)), self._out(rew), self._out(term.bool()), self._out(trunc.bool()), info
 
