@@ -23,10 +23,10 @@ int mw_depth_project(mw_engine *e, const double *host_params, const float *d_dep
         return fail(e, MW_E_INVALID, "%s: a frame of %d x %d pixels > %d (a cell's two counts share a 32-bit word)", what, a.W, a.H, MW_DEPTH_MAX_PIXELS);
     mwdepth::Sensor s{host_params[0], host_params[1], host_params[2], host_params[3], 0.0, 0.0, a.W, a.H};
     mwdepth::subpixel_of(e->cfg.msaa, s.sub_x, s.sub_y);
-    if (!(s.min_range > 0.0) || !isfinite(s.min_range)) return fail(e, MW_E_INVALID, "%s: min_range %g is not a positive finite number", what, s.min_range);
-    if (!(s.max_range > 0.0) || !isfinite(s.max_range)) return fail(e, MW_E_INVALID, "%s: max_range %g is not a positive finite number", what, s.max_range);
+    if (const int rc = positive_check(e, what, "min_range", s.min_range)) return rc;
+    if (const int rc = positive_check(e, what, "max_range", s.max_range)) return rc;
     if (s.min_range > s.max_range) return fail(e, MW_E_INVALID, "%s: min_range %g > max_range %g", what, s.min_range, s.max_range);
-    if (!(s.floor_tol >= 0.0) || !isfinite(s.floor_tol)) return fail(e, MW_E_INVALID, "%s: floor_tol %g is not a finite number >= 0", what, s.floor_tol);
+    if (const int rc = nonnegative_check(e, what, "floor_tol", s.floor_tol)) return rc;
     if (!(s.top >= s.floor_tol) || !isfinite(s.top)) return fail(e, MW_E_INVALID, "%s: top %g is not a finite number >= floor_tol %g", what, s.top, s.floor_tol);
     mwdepth::Window w{1.0, 0.0, 1, 0};
     mw_nav_params p{1.0, 0.0, 0.0, 1, 1, 0, 0};
@@ -34,7 +34,7 @@ int mw_depth_project(mw_engine *e, const double *host_params, const float *d_dep
     if (!grid) {        // the window target
         w = {host_params[4], host_params[5], size, flags};
         if (size < 1 || size > MW_EGO_MAX_SIZE) return fail(e, MW_E_INVALID, "%s: size %d outside 1 .. %d", what, (int)size, MW_EGO_MAX_SIZE);
-        if (!(w.cell > 0.0) || !isfinite(w.cell)) return fail(e, MW_E_INVALID, "%s: cell %g is not a positive finite number", what, w.cell);
+        if (const int rc = positive_check(e, what, "cell", w.cell)) return rc;
         if (!isfinite(w.back)) return fail(e, MW_E_INVALID, "%s: back %g is not finite", what, w.back);
         if (flags & ~MW_EGO_NORTH) return fail(e, MW_E_INVALID, "%s: unknown flags 0x%x", what, (unsigned)flags);
         if (!d_planes) return fail(e, MW_E_INVALID, "%s: d_planes is null", what);
@@ -48,19 +48,12 @@ int mw_depth_project(mw_engine *e, const double *host_params, const float *d_dep
         p = *grid;
         cells = (long long)p.gx * p.gz;
     }
-    const mwpolicy::DepthLaunch l = mwpolicy::depth_launch(a.N, cells);
+    const mwpolicy::Launch l = mwpolicy::depth_launch(a.N, cells);
     if (!l.fits)
         return fail(e, MW_E_INVALID, "%s: %lld cells need %zu bytes of LDS > 64 KiB (at most %d cells): use a larger cell", what, cells, l.lds, MW_DEPTH_MAX_CELLS);
-    if (mwpolicy::grid_too_large(l.grid)) return fail(e, MW_E_INVALID, "%s: %llu workgroups", what, l.grid);
-    ON_DEVICE(e);
-    const MwRayArgs ra = ray_view(e);
-    if (const int rc = allow_dynamic_lds(e, mw_depth_kernel, e->depth_lds_set, l.lds)) return rc;
     const int wide = (a.W * a.H) % 4 == 0 && mwpolicy::wide_units((uintptr_t)d_depth) ? 1 : 0;
-    hipLaunchKernelGGL(mw_depth_kernel, dim3((unsigned)l.grid), dim3((unsigned)l.threads), l.lds, (hipStream_t)stream, ra, a.cam, s, w, p, grid ? min_points : 1,
-                       wide, d_depth, d_mask, grid ? d_clear : nullptr, grid ? nullptr : d_planes, grid ? d_map : nullptr, grid ? d_count : nullptr,
-                       grid ? d_new : nullptr);
-    HIP_TRY(e, hipGetLastError());
-    return MW_OK;
+    return launch_query(e, what, mw_depth_kernel, ray_view, l.grid, l.threads, l.lds, &e->depth_lds_set, stream, a.cam, s, w, p, grid ? min_points : 1, wide, d_depth,
+                        d_mask, grid ? d_clear : nullptr, grid ? nullptr : d_planes, grid ? d_map : nullptr, grid ? d_count : nullptr, grid ? d_new : nullptr);
 }
 
 }  // extern "C"

@@ -19,14 +19,14 @@ int mw_ego_map(mw_engine *e, const double *host_window, int32_t size, int32_t pl
     const mwego::Window w{host_window[0], host_window[1], host_window[2], host_window[3], size, planes, flags};
     const mwseen::Sight s = mwego::sight_of(w, host_window[4], host_window[5]);
     if (size < 1 || size > MW_EGO_MAX_SIZE) return fail(e, MW_E_INVALID, "%s: size %d outside 1 .. %d", what, (int)size, MW_EGO_MAX_SIZE);
-    if (!(w.cell > 0.0) || !isfinite(w.cell)) return fail(e, MW_E_INVALID, "%s: cell %g is not a positive finite number", what, w.cell);
+    if (const int rc = positive_check(e, what, "cell", w.cell)) return rc;
     if (!isfinite(w.back)) return fail(e, MW_E_INVALID, "%s: back %g is not finite", what, w.back);
-    if (!(w.wall_radius >= 0.0) || !isfinite(w.wall_radius)) return fail(e, MW_E_INVALID, "%s: wall_radius %g is not a finite number >= 0", what, w.wall_radius);
-    if (!(w.entity_pad >= 0.0) || !isfinite(w.entity_pad)) return fail(e, MW_E_INVALID, "%s: entity_pad %g is not a finite number >= 0", what, w.entity_pad);
+    if (const int rc = nonnegative_check(e, what, "wall_radius", w.wall_radius)) return rc;
+    if (const int rc = nonnegative_check(e, what, "entity_pad", w.entity_pad)) return rc;
     if (planes & ~(MW_EGO_WALL | MW_EGO_ENTITY | MW_EGO_VISIBLE)) return fail(e, MW_E_INVALID, "%s: unknown planes 0x%x", what, (unsigned)planes);
     if (flags & ~(MW_EGO_ENTITIES | MW_EGO_NORTH)) return fail(e, MW_E_INVALID, "%s: unknown flags 0x%x", what, (unsigned)flags);
     if (planes & MW_EGO_VISIBLE) {
-        if (!(s.range > 0.0) || !isfinite(s.range)) return fail(e, MW_E_INVALID, "%s: range %g is not a positive finite number", what, s.range);
+        if (const int rc = positive_check(e, what, "range", s.range)) return rc;
         if (!(s.cos_half >= -1.0 && s.cos_half <= 1.0)) return fail(e, MW_E_INVALID, "%s: cos_half %g outside -1 .. 1", what, s.cos_half);
     }
     if (!planes && !d_src) return fail(e, MW_E_INVALID, "%s: neither a plane nor a source is asked for", what);
@@ -40,16 +40,10 @@ int mw_ego_map(mw_engine *e, const double *host_window, int32_t size, int32_t pl
     }
     const MwArgs &a = e->args;
     if ((planes & MW_EGO_ENTITY) && a.E > 255) return fail(e, MW_E_INVALID, "%s: %d slots do not fit the entity plane's byte", what, a.E);
-    const mwpolicy::EgoLaunch l = mwpolicy::ego_launch(a.N, a.max_segs, a.E, planes);
+    const mwpolicy::Launch l = mwpolicy::ego_launch(a.N, a.max_segs, a.E, planes);
     if (!l.fits) return fail(e, MW_E_INVALID, "%s: %d segments and %d slots need %zu bytes of LDS > 64 KiB", what, a.max_segs, a.E, l.lds);
-    if (mwpolicy::grid_too_large(l.grid)) return fail(e, MW_E_INVALID, "%s: %llu workgroups", what, l.grid);
-    ON_DEVICE(e);
-    const MwRayArgs ra = ray_view(e);
-    if (const int rc = allow_dynamic_lds(e, mw_ego_kernel, e->ego_lds_set, l.lds)) return rc;
-    hipLaunchKernelGGL(mw_ego_kernel, dim3((unsigned)l.grid), dim3((unsigned)l.threads), l.lds, (hipStream_t)stream, ra, w, s, q, d_mask, d_pos,
-                       planes ? d_planes : nullptr, d_src, d_src ? d_sample : nullptr);
-    HIP_TRY(e, hipGetLastError());
-    return MW_OK;
+    return launch_query(e, what, mw_ego_kernel, ray_view, l.grid, l.threads, l.lds, &e->ego_lds_set, stream, w, s, q, d_mask, d_pos, planes ? d_planes : nullptr, d_src,
+                        d_src ? d_sample : nullptr);
 }
 
 }  // extern "C"

@@ -10,6 +10,23 @@
 
 using namespace mwhost;
 
+namespace {
+
+// the queries' view and what the frame needs beside it
+MwLabelArgs label_view(const mw_engine *e)
+{
+    const MwArgs &a = e->args;
+    MwLabelArgs la{};
+    la.r = ray_view(e);
+    la.ay = a.ay; la.cam = a.cam; la.edir = a.edir; la.emesh = a.emesh; la.polys = a.polys; la.npolys = a.npolys;
+    la.mesh = e->have_meshes ? a.mesh : nullptr;
+    la.mesh_pos = e->have_meshes ? a.mesh_pos : nullptr;
+    la.max_polys = a.max_polys; la.n_mesh = MW_MAX_MESH; la.W = a.W; la.H = a.H; la.msaa = e->cfg.msaa;
+    return la;
+}
+
+}  // namespace
+
 extern "C" {
 
 int mw_label_frame(mw_engine *e, const mw_label_params *params, const uint8_t *d_mask, uint8_t *d_class, int32_t *d_code, float *d_depth, int32_t *d_ent_pixels,
@@ -29,19 +46,8 @@ int mw_label_frame(mw_engine *e, const mw_label_params *params, const uint8_t *d
     if (!l.fits)
         return fail(e, MW_E_INVALID, "%s: a frame %d pixels wide over a scene of %d polygons and %d slots does not fit the kernel's LDS plan (64 KiB; at most %d polygons, %d slots)",
                     what, a.W, a.max_polys, a.E, MW_LABEL_MAX_POLYS, MW_LABEL_MAX_ENTS);
-    if (mwpolicy::grid_too_large(l.grid)) return fail(e, MW_E_INVALID, "%s: %llu workgroups", what, l.grid);
-    ON_DEVICE(e);
-    MwLabelArgs la{};
-    la.r = ray_view(e);
-    la.ay = a.ay; la.cam = a.cam; la.edir = a.edir; la.emesh = a.emesh; la.polys = a.polys; la.npolys = a.npolys;
-    la.mesh = e->have_meshes ? a.mesh : nullptr;
-    la.mesh_pos = e->have_meshes ? a.mesh_pos : nullptr;
-    la.max_polys = a.max_polys; la.n_mesh = MW_MAX_MESH; la.W = a.W; la.H = a.H; la.msaa = e->cfg.msaa;
-    if (const int rc = allow_dynamic_lds(e, mw_label_kernel, e->label_lds_set, l.lds)) return rc;
-    hipLaunchKernelGGL(mw_label_kernel, dim3((unsigned)l.grid), dim3((unsigned)l.threads), l.lds, (hipStream_t)stream, la, p, l.band_rows, l.chunk,
-                       (p.flags & MW_LABEL_UNPRUNED) ? 0 : 1, d_mask, d_class, d_code, d_depth, d_ent_pixels, d_ent_box);
-    HIP_TRY(e, hipGetLastError());
-    return MW_OK;
+    return launch_query(e, what, mw_label_kernel, label_view, l.grid, l.threads, l.lds, &e->label_lds_set, stream, p, l.band_rows, l.chunk,
+                        (p.flags & MW_LABEL_UNPRUNED) ? 0 : 1, d_mask, d_class, d_code, d_depth, d_ent_pixels, d_ent_box);
 }
 
 }  // extern "C"

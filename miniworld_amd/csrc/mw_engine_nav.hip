@@ -25,13 +25,9 @@ int mw_nav_build(mw_engine *e, const mw_nav_params *params, const uint8_t *d_mas
 {
     if (!e) return MW_E_INVALID;
     if (const int rc = nav_args(e, "mw_nav_build", params, d_target, d_field)) return rc;
-    ON_DEVICE(e);
     const int lds = (int)((size_t)params->gx * params->gz * sizeof(uint16_t) + 15) / 16 * 16;
-    if (const int rc = allow_dynamic_lds(e, mw_nav_build_kernel, e->nav_lds_set, lds)) return rc;
-    hipLaunchKernelGGL(mw_nav_build_kernel, dim3((unsigned)e->cfg.num_envs), dim3(MW_NAV_THREADS), (size_t)lds, (hipStream_t)stream, world_view(e), *params,
-                       d_mask, d_target, d_field, e->nav_passes);
-    HIP_TRY(e, hipGetLastError());
-    return MW_OK;
+    return launch_query(e, "mw_nav_build", mw_nav_build_kernel, world_view, e->cfg.num_envs, MW_NAV_THREADS, lds, &e->nav_lds_set, stream, *params, d_mask, d_target,
+                        d_field, e->nav_passes);
 }
 
 int mw_nav_query(mw_engine *e, const mw_nav_params *params, const double *d_target, const uint16_t *d_field, const double *d_pos, int32_t *d_cost,
@@ -39,12 +35,9 @@ int mw_nav_query(mw_engine *e, const mw_nav_params *params, const double *d_targ
 {
     if (!e) return MW_E_INVALID;
     if (const int rc = nav_args(e, "mw_nav_query", params, d_target, d_field)) return rc;
-    ON_DEVICE(e);
     const int N = e->cfg.num_envs;
-    hipLaunchKernelGGL(mw_nav_query_kernel, dim3((unsigned)((N + MW_NAV_QUERY_THREADS - 1) / MW_NAV_QUERY_THREADS)), dim3(MW_NAV_QUERY_THREADS), 0,
-                       (hipStream_t)stream, world_view(e), *params, d_target, d_field, d_pos, d_cost, d_next, d_waypoint);
-    HIP_TRY(e, hipGetLastError());
-    return MW_OK;
+    return launch_query(e, "mw_nav_query", mw_nav_query_kernel, world_view, (N + MW_NAV_QUERY_THREADS - 1) / MW_NAV_QUERY_THREADS, MW_NAV_QUERY_THREADS, 0, nullptr, stream,
+                        *params, d_target, d_field, d_pos, d_cost, d_next, d_waypoint);
 }
 
 int mw_debug_set_nav_passes(mw_engine *e, int32_t *d_passes)

@@ -1,8 +1,6 @@
 // mwengine host runtime: explored-area maps (mw_seen_update; kernel: mw_seen.hip, tests and phases: mw_seen.h, launch: mw_policy.h).
 //
 // The call does not wait for the Maze's side-stream refills: mw_engine.h, at world_view().
-#include <math.h>
-
 #include "mw_engine.h"
 #include "mw_policy.h"
 
@@ -19,20 +17,13 @@ int mw_seen_update(mw_engine *e, const mw_nav_params *grid, const double *host_s
         return fail(e, MW_E_INVALID, "%s: %s is null", what, !grid ? "grid" : !host_sight ? "host_sight" : !d_seen ? "d_seen" : "d_count");
     if (const int rc = grid_check(e, what, grid)) return rc;      // (every seen grid is a valid nav grid)
     const mwseen::Sight s{host_sight[0], host_sight[1], flags};
-    if (!(s.range > 0.0) || !isfinite(s.range)) return fail(e, MW_E_INVALID, "%s: range %g is not a positive finite number", what, s.range);
+    if (const int rc = positive_check(e, what, "range", s.range)) return rc;
     if (!(s.cos_half >= -1.0 && s.cos_half <= 1.0)) return fail(e, MW_E_INVALID, "%s: cos_half %g outside -1 .. 1", what, s.cos_half);
     if (flags & ~MW_SEEN_ENTITIES) return fail(e, MW_E_INVALID, "%s: unknown flags 0x%x", what, (unsigned)flags);
     const MwArgs &a = e->args;
-    const mwpolicy::SeenLaunch l = mwpolicy::seen_launch(a.N, a.max_segs, a.E);
+    const mwpolicy::Launch l = mwpolicy::seen_launch(a.N, a.max_segs, a.E);
     if (!l.fits) return fail(e, MW_E_INVALID, "%s: %d segments and %d slots need %zu bytes of LDS > 64 KiB", what, a.max_segs, a.E, l.lds);
-    if (mwpolicy::grid_too_large(l.grid)) return fail(e, MW_E_INVALID, "%s: %llu workgroups", what, l.grid);
-    ON_DEVICE(e);
-    const MwRayArgs ra = ray_view(e);
-    if (const int rc = allow_dynamic_lds(e, mw_seen_kernel, e->seen_lds_set, l.lds)) return rc;
-    hipLaunchKernelGGL(mw_seen_kernel, dim3((unsigned)l.grid), dim3((unsigned)l.threads), l.lds, (hipStream_t)stream, ra, *grid, s, d_mask, d_clear, d_seen, d_count,
-                       d_new);
-    HIP_TRY(e, hipGetLastError());
-    return MW_OK;
+    return launch_query(e, what, mw_seen_kernel, ray_view, l.grid, l.threads, l.lds, &e->seen_lds_set, stream, *grid, s, d_mask, d_clear, d_seen, d_count, d_new);
 }
 
 }  // extern "C"

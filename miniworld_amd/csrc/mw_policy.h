@@ -308,6 +308,13 @@ inline SnapfGrid snapf_where_grid(uintptr_t address_bits, uint64_t frame_bytes, 
     return snapf_grid(address_bits, frame_bytes, depth_bytes, stack_depth, N);
 }
 
+// The launch of a world query whose kernel takes a workgroup per env (seen_launch, ego_launch, depth_launch): the grid, the lanes of a
+// workgroup, its dynamic LDS in bytes, and whether that fits.  (ray_launch and label_launch return more: RayLaunch, LabelLaunch.)
+struct Launch { unsigned long long grid; int threads; size_t lds; bool fits; };
+using SeenLaunch = Launch;      // (the names the three had while each declared the same four fields)
+using EgoLaunch = Launch;
+using DepthLaunch = Launch;
+
 // Ray casts (mw_ray_cast; kernels: mw_ray.hip).  The form follows from the rays per env alone: from kRayPerLaneFrom rays on, a
 // workgroup per env with a ray per lane and the obstacles staged in LDS; below it a wavefront per ray with an obstacle per lane.
 // Both produce the same bits.  The ray-per-lane form takes as many whole wavefronts as hold the rays, MW_RAY_THREADS lanes at most;
@@ -331,8 +338,7 @@ inline RayLaunch ray_launch(int N, int R, int max_segs, int max_ents, int forced
 // Explored-area maps (mw_seen_update; kernel: mw_seen.hip): a workgroup of MW_SEEN_THREADS lanes per env.  Its LDS is the ray-per-lane
 // form's staged obstacles, sized from the engine's capacities, and behind them the candidate list and its words (MW_SEEN_TAIL_BYTES);
 // fits: at most 64 KiB, the rule of ray_launch — the caller refuses what does not.
-struct SeenLaunch { unsigned long long grid; int threads; size_t lds; bool fits; };
-inline SeenLaunch seen_launch(int N, int max_segs, int max_ents)
+inline Launch seen_launch(int N, int max_segs, int max_ents)
 {
     const size_t lds = ((size_t)max_segs * MW_RAY_WALL_BYTES + (size_t)max_ents * MW_RAY_DISC_BYTES + 15) / 16 * 16 + MW_SEEN_TAIL_BYTES;
     return {(unsigned long long)N, MW_SEEN_THREADS, lds, lds <= 64 * 1024};
@@ -342,8 +348,7 @@ inline SeenLaunch seen_launch(int N, int max_segs, int max_ents)
 // obstacles of the asked planes, sized from the engine's capacities (mwego::staged_bytes: 48 bytes per segment and 32 per slot for
 // VISIBLE, 32 per segment for WALL, 32 per slot for ENTITY, rounded up to 16; nothing without planes); fits: at most 64 KiB — the caller
 // refuses what does not.
-struct EgoLaunch { unsigned long long grid; int threads; size_t lds; bool fits; };
-inline EgoLaunch ego_launch(int N, int max_segs, int max_ents, int planes)
+inline Launch ego_launch(int N, int max_segs, int max_ents, int planes)
 {
     const size_t lds = mwego::staged_bytes(max_segs, max_ents, planes);
     return {(unsigned long long)N, MW_EGO_THREADS, lds, lds <= 64 * 1024};
@@ -353,8 +358,7 @@ inline EgoLaunch ego_launch(int N, int max_segs, int max_ents, int planes)
 // cell of the target — size * size of a window, gx * gz of a map —, never less than the two words per wavefront the map's reduction
 // reuses, rounded up to 16; fits: at most 64 KiB, i.e. MW_DEPTH_MAX_CELLS = 16384 cells (a window of MW_EGO_MAX_SIZE = 128; the Maze at
 // 0.25 m has 10 609) — the caller refuses what does not.
-struct DepthLaunch { unsigned long long grid; int threads; size_t lds; bool fits; };
-inline DepthLaunch depth_launch(int N, long long cells)
+inline Launch depth_launch(int N, long long cells)
 {
     const long long least = 2 * (MW_DEPTH_THREADS / 64);
     const size_t lds = ((size_t)(cells > least ? cells : least) * MW_DEPTH_CELL_BYTES + 15) / 16 * 16;

@@ -147,6 +147,34 @@ class WorldQueries:
             raise ValueError(f"{where}: {gx} x {gz} cells > {eng.NAV_MAX_CELLS}: use a larger cell")
         return cell, gx, gz
 
+    def _map_grid(self, where, cell, like, kinds, own):
+        """the bare grid (MwNavParams: no margin, reach, flags or target) of a map: `like`'s — one of `kinds`; `own` is how the message
+        names its grid — or _grid()'s for `cell`"""
+        if like is not None:
+            if not isinstance(like, kinds):
+                raise ValueError(f"{where}: `like` must be {' or '.join('a ' + k.__name__ for k in kinds)}")
+            if cell != 0.25:
+                raise ValueError(f"{where}: with `like` {own} grid is used: pass no cell")
+            cell, gx, gz = like.cell, like.gx, like.gz
+        else:
+            cell, gx, gz = self._grid(where, cell)
+        return eng.MwNavParams(float(cell), 0.0, 0.0, int(gx), int(gz), 0, 0)
+
+    def _window_shape(self, where, size, cell, anchor, frame):
+        """(size, cell, back, frame) of an egocentric window, checked; `back` is the anchor in cells behind the window's centre"""
+        size = integer(where, "size", size, 1, eng.EGO_MAX_SIZE)
+        cell = real(where, "cell", cell)
+        if anchor not in ("centre", "bottom"):
+            raise ValueError(f"{where}: anchor {anchor!r}; have 'centre' and 'bottom'")
+        if frame not in ("heading", "north"):
+            raise ValueError(f"{where}: frame {frame!r}; have 'heading' and 'north'")
+        return size, cell, size / 2 if anchor == "bottom" else 0.0, frame
+
+    def _cos_half(self, where, fov):
+        """cos(fov / 2) of a horizontal opening angle in radians, checked; None: default_fov(); 2 pi: -1.0, all round"""
+        fov = self.default_fov() if fov is None else real(where, "fov", fov, hi=2 * math.pi)
+        return -1.0 if fov == 2 * math.pi else float(math.cos(fov / 2))
+
     def nav_field(self, target=None, mask=None, cell=0.25, obstacles="walls", margin=None, reach=None, into=None):
         """The shortest-path cost to a target from every cell of a grid over each env's floor plan, walls in the way, built on the
         device by one kernel (mw_nav_build) with no host value and no synchronisation: a NavField.
@@ -238,20 +266,11 @@ class WorldQueries:
         torch, e = self.torch, self.engine
         self._obstacle_flags("seen_map", obstacles)
         max_range = real("seen_map", "max_range", max_range)
-        fov = self.default_fov() if fov is None else real("seen_map", "fov", fov, hi=2 * math.pi)
-        cos_half = -1.0 if fov == 2 * math.pi else math.cos(fov / 2)
-        if like is not None:
-            if not isinstance(like, NavField):
-                raise ValueError("seen_map: `like` must be a NavField")
-            if cell != 0.25:
-                raise ValueError("seen_map: with `like` the field's own grid is used: pass no cell")
-            cell, gx, gz = like.cell, like.gx, like.gz
-        else:
-            cell, gx, gz = self._grid("seen_map", cell)
-        params = eng.MwNavParams(float(cell), 0.0, 0.0, int(gx), int(gz), 0, 0)
+        cos_half = self._cos_half("seen_map", fov)
+        params = self._map_grid("seen_map", cell, like, (NavField,), "the field's own")
         n = self.num_envs
-        return SeenMap(torch.zeros((n, int(gz), int(gx)), dtype=torch.uint8, device=e.device), torch.zeros(n, dtype=torch.int32, device=e.device),
-                       torch.zeros(n, dtype=torch.int32, device=e.device), params, max_range, float(cos_half), obstacles)
+        return SeenMap(torch.zeros((n, params.gz, params.gx), dtype=torch.uint8, device=e.device), torch.zeros(n, dtype=torch.int32, device=e.device),
+                       torch.zeros(n, dtype=torch.int32, device=e.device), params, max_range, cos_half, obstacles)
 
     def seen_update(self, seen, clear=None, mask=None):
         """Marks the cells each env's agent sees from where it stands now in `seen` (a SeenMap), by one kernel (mw_seen_update) with no
@@ -287,12 +306,7 @@ class WorldQueries:
         max_range, fov, obstacles  what "visible" means, exactly as for seen_map()
         ValueError for arguments that make no window."""
         torch, e = self.torch, self.engine
-        size = integer("ego_window", "size", size, 1, eng.EGO_MAX_SIZE)
-        cell = real("ego_window", "cell", cell)
-        if anchor not in ("centre", "bottom"):
-            raise ValueError(f"ego_window: anchor {anchor!r}; have 'centre' and 'bottom'")
-        if frame not in ("heading", "north"):
-            raise ValueError(f"ego_window: frame {frame!r}; have 'heading' and 'north'")
+        size, cell, back, frame = self._window_shape("ego_window", size, cell, anchor, frame)
         if isinstance(planes, str) or not isinstance(planes, (tuple, list)) or len(set(planes)) != len(planes) or any(
                 not isinstance(p, str) or p not in EgoWindow.PLANES for p in planes):
             raise ValueError(f"ego_window: planes {planes!r}: a sequence of distinct names out of {tuple(EgoWindow.PLANES)}")
@@ -303,10 +317,9 @@ class WorldQueries:
         entity_pad = cell / 2 if entity_pad is None else real("ego_window", "entity_pad", entity_pad, lo_open=False)
         self._obstacle_flags("ego_window", obstacles)
         max_range = real("ego_window", "max_range", max_range)
-        fov = self.default_fov() if fov is None else real("ego_window", "fov", fov, hi=2 * math.pi)
-        cos_half = -1.0 if fov == 2 * math.pi else math.cos(fov / 2)
+        cos_half = self._cos_half("ego_window", fov)
         out = torch.zeros((self.num_envs, len(names), size, size), dtype=torch.uint8, device=e.device) if names else None
-        return EgoWindow(out, names, size, cell, size / 2 if anchor == "bottom" else 0.0, frame, wall_radius, entity_pad, max_range, float(cos_half), obstacles)
+        return EgoWindow(out, names, size, cell, back, frame, wall_radius, entity_pad, max_range, cos_half, obstacles)
 
     def ego_update(self, w, source=None, fill=None, mask=None, pos=None):
         """Fills `w` (an EgoWindow) for where each env's agent stands and looks now, by one kernel (mw_ego_map) with no host value and
@@ -372,6 +385,12 @@ class WorldQueries:
             raise ValueError(f"{where}: depth is a contiguous float32 tensor [{n}, {H}, {W}, 1] or [{n}, {H}, {W}] on {e.device}")
         return depth
 
+    def _depth_pixel_cap(self, where):
+        """a cell's two counts share a 32-bit word in the kernel: frames of more pixels are refused"""
+        cfg = self.engine.cfg
+        if int(cfg.obs_width) * int(cfg.obs_height) > eng.DEPTH_MAX_PIXELS:
+            raise ValueError(f"{where}: frames of {cfg.obs_width} x {cfg.obs_height} pixels > {eng.DEPTH_MAX_PIXELS}")
+
     def depth_window(self, size=33, cell=0.25, anchor="centre", frame="heading", min_range=0.05, max_range=8.0, floor_tol=0.1, top=None):
         """An empty depth-projected egocentric window: a DepthWindow, which depth_update() fills.  Nothing is launched.
 
@@ -384,17 +403,11 @@ class WorldQueries:
                                    is neither
         ValueError for arguments that make no window."""
         torch, e = self.torch, self.engine
-        size = integer("depth_window", "size", size, 1, eng.EGO_MAX_SIZE)
-        cell = real("depth_window", "cell", cell)
-        if anchor not in ("centre", "bottom"):
-            raise ValueError(f"depth_window: anchor {anchor!r}; have 'centre' and 'bottom'")
-        if frame not in ("heading", "north"):
-            raise ValueError(f"depth_window: frame {frame!r}; have 'heading' and 'north'")
+        size, cell, back, frame = self._window_shape("depth_window", size, cell, anchor, frame)
         sensor = self._depth_sensor("depth_window", min_range, max_range, floor_tol, top)
-        if int(e.cfg.obs_width) * int(e.cfg.obs_height) > eng.DEPTH_MAX_PIXELS:
-            raise ValueError(f"depth_window: frames of {e.cfg.obs_width} x {e.cfg.obs_height} pixels > {eng.DEPTH_MAX_PIXELS}")
+        self._depth_pixel_cap("depth_window")
         out = torch.zeros((self.num_envs, 2, size, size), dtype=torch.uint8, device=e.device)
-        return DepthWindow(out, size, cell, size / 2 if anchor == "bottom" else 0.0, frame, *sensor)
+        return DepthWindow(out, size, cell, back, frame, *sensor)
 
     def depth_update(self, w, depth=None, mask=None):
         """Fills `w` (a DepthWindow) from a depth map, by one kernel (mw_depth_project) with no host value and no synchronisation;
@@ -423,23 +436,15 @@ class WorldQueries:
         min_range, max_range, floor_tol, top  as for depth_window()
         At most 16384 cells (the kernel counts in 64 KiB of LDS): ValueError says "use a larger cell" otherwise."""
         torch, e = self.torch, self.engine
-        if like is not None:
-            if not isinstance(like, (NavField, SeenMap)):
-                raise ValueError("depth_map: `like` must be a NavField or a SeenMap")
-            if cell != 0.25:
-                raise ValueError("depth_map: with `like` its own grid is used: pass no cell")
-            cell, gx, gz = like.cell, like.gx, like.gz
-        else:
-            cell, gx, gz = self._grid("depth_map", cell)
+        params = self._map_grid("depth_map", cell, like, (NavField, SeenMap), "its own")
+        gx, gz = params.gx, params.gz
         if gx * gz > eng.DEPTH_MAX_CELLS:
             raise ValueError(f"depth_map: {gx} x {gz} cells > {eng.DEPTH_MAX_CELLS}: use a larger cell")
         min_points = integer("depth_map", "min_points", min_points, 1, 255)
         sensor = self._depth_sensor("depth_map", min_range, max_range, floor_tol, top)
-        if int(e.cfg.obs_width) * int(e.cfg.obs_height) > eng.DEPTH_MAX_PIXELS:
-            raise ValueError(f"depth_map: frames of {e.cfg.obs_width} x {e.cfg.obs_height} pixels > {eng.DEPTH_MAX_PIXELS}")
-        params = eng.MwNavParams(float(cell), 0.0, 0.0, int(gx), int(gz), 0, 0)
+        self._depth_pixel_cap("depth_map")
         n = self.num_envs
-        return DepthMap(torch.zeros((n, 2, int(gz), int(gx)), dtype=torch.uint8, device=e.device), torch.zeros((n, 2), dtype=torch.int32, device=e.device),
+        return DepthMap(torch.zeros((n, 2, gz, gx), dtype=torch.uint8, device=e.device), torch.zeros((n, 2), dtype=torch.int32, device=e.device),
                         torch.zeros((n, 2), dtype=torch.int32, device=e.device), params, min_points, *sensor)
 
     def depth_map_update(self, m, depth=None, clear=None, mask=None):

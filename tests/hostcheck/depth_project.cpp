@@ -3,52 +3,28 @@
 // clear byte and a depth map per step —, each step one mwdepth::window_one or map_one into the same buffers (a step under a zero mask
 // byte is skipped, as the kernel skips the env).
 //
-// The file, whitespace-separated (doubles as Python's repr, which round-trips; depth values as the hexadecimal bits of their float32,
-// so that a NaN, an infinity and a negative zero arrive as they are):
+// The file (hostcheck.h: the tokens, the world block; depth values as the hexadecimal bits of their float32):
 //   W H msaa
 //   min_range max_range floor_tol top
 //   target                     0: then size cell back flags;  1: then cell gx gz min_points
 //   garbage                    (the byte the planes, the map and the counts' bytes hold before the first step)
-//   min_x max_x min_z max_z
+//   the world: EXTENT alone (the projection reads neither segments nor slots)
 //   nsteps, then per step: x z dir  cam_height cam_fwd_disp cam_pitch cam_fov_y  mask clear, then H * W depth words
 // The answer, per step: a line with the 2 * cells bytes of the planes or the map; for a map a second line "count0 count1 new0 new1".
 // `depth_project --policy N cells` prints mwpolicy::depth_launch instead: "grid threads lds fits"; `depth_project --pattern msaa` prints
 // mwdepth::sample0_of: "sx sy".
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#define HOSTCHECK_PROGRAM "depth_project"
+#include "hostcheck.h"
 
 #include "../../miniworld_amd/csrc/mw_depth.h"
 #include "../../miniworld_amd/csrc/mw_policy.h"
 
-static double rd(FILE *f)
-{
-    double v;
-    if (fscanf(f, "%lf", &v) != 1) { fprintf(stderr, "depth_project: short file\n"); exit(2); }
-    return v;
-}
-static int ri(FILE *f)
-{
-    int v;
-    if (fscanf(f, "%d", &v) != 1) { fprintf(stderr, "depth_project: short file\n"); exit(2); }
-    return v;
-}
-static float rbits(FILE *f)
-{
-    unsigned v;
-    if (fscanf(f, "%x", &v) != 1) { fprintf(stderr, "depth_project: short file\n"); exit(2); }
-    const uint32_t u = v;
-    float x;
-    memcpy(&x, &u, 4);
-    return x;
-}
+using namespace hostcheck;
 
 int main(int argc, char **argv)
 {
     if (argc == 4 && !strcmp(argv[1], "--policy")) {
-        const mwpolicy::DepthLaunch l = mwpolicy::depth_launch(atoi(argv[2]), atoll(argv[3]));
-        printf("%llu %d %zu %d\n", l.grid, l.threads, l.lds, l.fits ? 1 : 0);
+        print_launch(mwpolicy::depth_launch(atoi(argv[2]), atoll(argv[3])));
         return 0;
     }
     if (argc == 3 && !strcmp(argv[1], "--pattern")) {
@@ -79,20 +55,13 @@ int main(int argc, char **argv)
         !(s.top >= s.floor_tol) || (msaa != 1 && msaa != 4 && msaa != 8) ||
         (to_map ? (!(p.cell > 0.0) || p.gx < 1 || p.gz < 1 || min_points < 1 || min_points > 255)
                 : (w.size < 1 || w.size > MW_EGO_MAX_SIZE || !(w.cell > 0.0) || (w.flags & ~MW_EGO_NORTH))) ||
-        !mwpolicy::depth_launch(1, cells).fits) {
-        fprintf(stderr, "depth_project: parameters the engine refuses\n");
-        return 2;
-    }
+        !mwpolicy::depth_launch(1, cells).fits)
+        return refused();
     const int garbage = ri(f);
-    std::vector<double> extent(4);
-    for (double &v : extent) v = rd(f);
-    MwRayArgs a{};
-    uint32_t status = 0;
-    int32_t carry = -1, nsegs = 0;
-    double ax = 0.0, az = 0.0, adir = 0.0, cam[4] = {0.0, 0.0, 0.0, 0.0};
-    a.w.nsegs = &nsegs; a.w.extent = extent.data(); a.w.carry = &carry; a.w.ax = &ax; a.w.az = &az; a.w.status = &status;
-    a.w.N = 1; a.w.E = 0; a.w.max_segs = 0; a.w.shared_geom = 1;
-    a.adir = &adir;
+    World world;
+    world.read(f, EXTENT);
+    const MwRayArgs a = world.ray();
+    double cam[4] = {0.0, 0.0, 0.0, 0.0};
     // exactly as many elements as the call may touch: the sanitizer sees a step past any of them
     std::vector<uint8_t> out(2 * (size_t)cells, (uint8_t)garbage);
     std::vector<uint32_t> scratch((size_t)cells);
@@ -102,7 +71,7 @@ int main(int argc, char **argv)
     memset(newly, garbage, sizeof newly);
     const int nsteps = ri(f);
     for (int t = 0; t < nsteps; ++t) {
-        ax = rd(f); az = rd(f); adir = rd(f);
+        world.ax = rd(f); world.az = rd(f); world.adir = rd(f);
         for (double &v : cam) v = rd(f);
         const bool mask = ri(f) != 0, clear = ri(f) != 0;
         for (float &v : depth) v = rbits(f);

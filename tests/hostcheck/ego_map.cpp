@@ -3,45 +3,28 @@
 // mask byte and an optional origin per step —, each step one mwego::window_one into the same buffers (a step under a zero mask byte
 // is skipped, as the kernel skips the env).
 //
-// The file, whitespace-separated (doubles as Python's repr, which round-trips; nan is read as a NaN):
+// The file (hostcheck.h: the tokens, the world block):
 //   size cell back wall_radius entity_pad planes flags
 //   range cos_half
 //   src_bytes src_cell gx gz fill, then — src_bytes != 0 — the gz * gx elements of the source
 //   garbage                    (the byte the planes and the sample hold before the first step)
-//   agent_radius max_forward_step
-//   min_x max_x min_z max_z
-//   nsegs, then ax az bx bz per segment
-//   E, then kind x y z radius per slot
+//   the world: AGENT, EXTENT, SEGS, SLOTS
 //   nsteps, then x z dir carry mask has_pos pos_x pos_z per step
 // The answer, per step: a line with the P * size * size bytes of the planes ("-" without planes), a line with the size * size
 // elements of the sample ("-" without a source).
 // `ego_map --policy N max_segs max_ents planes` prints mwpolicy::ego_launch instead: "grid threads lds fits".
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#define HOSTCHECK_PROGRAM "ego_map"
+#include "hostcheck.h"
 
 #include "../../miniworld_amd/csrc/mw_ego.h"
 #include "../../miniworld_amd/csrc/mw_policy.h"
 
-static double rd(FILE *f)
-{
-    double v;
-    if (fscanf(f, "%lf", &v) != 1) { fprintf(stderr, "ego_map: short file\n"); exit(2); }
-    return v;
-}
-static int ri(FILE *f)
-{
-    int v;
-    if (fscanf(f, "%d", &v) != 1) { fprintf(stderr, "ego_map: short file\n"); exit(2); }
-    return v;
-}
+using namespace hostcheck;
 
 int main(int argc, char **argv)
 {
     if (argc == 6 && !strcmp(argv[1], "--policy")) {
-        const mwpolicy::EgoLaunch l = mwpolicy::ego_launch(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]));
-        printf("%llu %d %zu %d\n", l.grid, l.threads, l.lds, l.fits ? 1 : 0);
+        print_launch(mwpolicy::ego_launch(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5])));
         return 0;
     }
     if (argc != 2) { fprintf(stderr, "usage: ego_map WORLD | ego_map --policy N max_segs max_ents planes\n"); return 2; }
@@ -57,10 +40,8 @@ int main(int argc, char **argv)
     if (w.size < 1 || w.size > MW_EGO_MAX_SIZE || !(w.cell > 0.0) || !(w.wall_radius >= 0.0) || !(w.entity_pad >= 0.0) ||
         (w.planes & ~(MW_EGO_WALL | MW_EGO_ENTITY | MW_EGO_VISIBLE)) || (w.flags & ~(MW_EGO_ENTITIES | MW_EGO_NORTH)) || (!w.planes && !sampled) ||
         ((w.planes & MW_EGO_VISIBLE) && (!(range > 0.0) || !(cos_half >= -1.0 && cos_half <= 1.0))) ||
-        (sampled && ((q.bytes != 1 && q.bytes != 2) || !(q.cell > 0.0) || q.gx < 1 || q.gz < 1 || (long long)q.gx * q.gz > MW_NAV_MAX_CELLS))) {
-        fprintf(stderr, "ego_map: parameters the engine refuses\n");
-        return 2;
-    }
+        (sampled && ((q.bytes != 1 && q.bytes != 2) || !(q.cell > 0.0) || q.gx < 1 || q.gz < 1 || (long long)q.gx * q.gz > MW_NAV_MAX_CELLS)))
+        return refused();
     const size_t src_cells = sampled ? (size_t)q.gx * q.gz : 0;
     std::vector<uint8_t> src8(q.bytes == 1 ? src_cells : 0);
     std::vector<uint16_t> src16(q.bytes == 2 ? src_cells : 0);
@@ -70,40 +51,20 @@ int main(int argc, char **argv)
         else src16[c] = (uint16_t)v;
     }
     const int garbage = ri(f);
-    MwRayArgs a{};
-    a.w.agent_radius = rd(f); a.w.max_forward_step = rd(f);
-    std::vector<double> extent(4);
-    for (double &v : extent) v = rd(f);
-    int32_t nsegs = ri(f);
-    std::vector<double> segs((size_t)nsegs * 4 + 1);
-    for (int i = 0; i < nsegs * 4; ++i) segs[i] = rd(f);
-    const int E = ri(f);
-    if ((w.planes & MW_EGO_ENTITY) && E > 255) { fprintf(stderr, "ego_map: parameters the engine refuses\n"); return 2; }
-    std::vector<int32_t> kind((size_t)E + 1);
-    std::vector<double> pos((size_t)E * 3 + 1), geom((size_t)E * 9 + 1);
-    for (int k = 0; k < E; ++k) {       // (the engine's layouts with N = 1: [3][E], [9][E])
-        kind[k] = ri(f);
-        for (int c = 0; c < 3; ++c) pos[(size_t)c * E + k] = rd(f);
-        geom[(size_t)7 * E + k] = rd(f);
-    }
-    uint32_t status = 0;
-    int32_t carry = -1;
-    double ax = 0.0, az = 0.0, adir = 0.0;
-    a.w.segs = segs.data(); a.w.nsegs = &nsegs; a.w.extent = extent.data(); a.w.ekind = kind.data(); a.w.epos = pos.data(); a.w.egeom = geom.data();
-    a.w.carry = &carry; a.w.ax = &ax; a.w.az = &az; a.w.status = &status;
-    a.w.N = 1; a.w.E = E; a.w.max_segs = nsegs; a.w.shared_geom = 1;
-    a.adir = &adir;
+    World world;
+    if (!world.read(f, AGENT | EXTENT | SEGS | SLOTS, (w.planes & MW_EGO_ENTITY) ? 255 : 1 << 20)) return refused();
+    const MwRayArgs a = world.ray();
     const int P = mwego::plane_count(w.planes);
     const size_t cells = (size_t)w.size * w.size;
     // exactly as many bytes as the call may touch: the sanitizer sees a step past any of them
     std::vector<uint8_t> planes(P * cells, (uint8_t)garbage);
     std::vector<uint8_t> out8(q.bytes == 1 ? cells : 0, (uint8_t)garbage);
     std::vector<uint16_t> out16(q.bytes == 2 ? cells : 0, (uint16_t)(garbage * 0x101));
-    std::vector<double> scratch(mwego::staged_bytes(nsegs, E, w.planes) / sizeof(double) + 1);
+    std::vector<double> scratch((mwego::staged_bytes(world.nsegs, world.E, w.planes) + sizeof(double) - 1) / sizeof(double));
     const int nsteps = ri(f);
     for (int t = 0; t < nsteps; ++t) {
-        ax = rd(f); az = rd(f); adir = rd(f);
-        carry = ri(f);
+        world.ax = rd(f); world.az = rd(f); world.adir = rd(f);
+        world.carry = ri(f);
         const bool mask = ri(f) != 0, has_pos = ri(f) != 0;
         const double origin[3] = {rd(f), 0.0, rd(f)};
         const void *src_row = q.bytes == 1 ? (const void *)src8.data() : q.bytes == 2 ? (const void *)src16.data() : nullptr;

@@ -3,35 +3,22 @@
 // mwlabel::frame_env<HostOps> with (lane, stride) = (0, 1) into the same buffers — the kernel's phases, pruning rectangle and bands
 // included (a step under a zero mask byte is skipped, as the kernel skips the env).
 //
-// The file, whitespace-separated (doubles as Python's repr, which round-trips; floats as the hexadecimal bits of their float32):
+// The file (hostcheck.h: the tokens, the world block; floats as the hexadecimal bits of their float32):
 //   W H msaa  near far flags  band_rows chunk          (band_rows, chunk 0: mwpolicy::label_launch's)
 //   npolys, then per polygon: nv (with its MW_POLY_* flags), 12 words v, 4 words xf
-//   E, then per slot: kind mesh  pos[3] dir geom[9]
+//   the world: SLOTS in their WIDE form alone
 //   nmesh, then per mesh: ntris and 9 * ntris words
 //   garbage                    (the byte every output holds before the first step)
 //   nsteps, then per step: x y z dir  cam_height cam_fwd_disp cam_pitch cam_fov_y  mask
 // The answer, per step, five lines: H * W classes, H * W codes, the H * W depths as hexadecimal bits, E pixel counts, 4 * E box words.
 // `label_frame --policy N W H max_polys max_ents` prints mwpolicy::label_launch instead: "grid threads lds band_rows chunk fits".
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#define HOSTCHECK_PROGRAM "label_frame"
+#include "hostcheck.h"
 
 #include "../../miniworld_amd/csrc/mw_label.h"
 #include "../../miniworld_amd/csrc/mw_policy.h"
 
-static void shortfile() { fprintf(stderr, "label_frame: short file\n"); exit(2); }
-static double rd(FILE *f) { double v; if (fscanf(f, "%lf", &v) != 1) shortfile(); return v; }
-static int ri(FILE *f) { int v; if (fscanf(f, "%d", &v) != 1) shortfile(); return v; }
-static float rbits(FILE *f)
-{
-    unsigned v;
-    if (fscanf(f, "%x", &v) != 1) shortfile();
-    const uint32_t u = v;
-    float x;
-    memcpy(&x, &u, 4);
-    return x;
-}
+using namespace hostcheck;
 
 int main(int argc, char **argv)
 {
@@ -49,10 +36,8 @@ int main(int argc, char **argv)
     int band_rows = ri(f), chunk = ri(f);
     const int npolys = ri(f);
     if (W < 1 || H < 1 || (msaa != 1 && msaa != 4 && msaa != 8) || !(p.near >= 0.0) || !(p.near < p.far) || (p.flags & ~(MW_LABEL_MESH_BOUNDS | MW_LABEL_UNPRUNED)) ||
-        npolys < 0 || npolys > MW_LABEL_MAX_POLYS) {
-        fprintf(stderr, "label_frame: parameters the engine refuses\n");
-        return 2;
-    }
+        npolys < 0 || npolys > MW_LABEL_MAX_POLYS)
+        return refused();
     std::vector<mw_poly> polys((size_t)npolys);
     for (mw_poly &q : polys) {
         memset(&q, 0, sizeof q);
@@ -60,17 +45,9 @@ int main(int argc, char **argv)
         for (int i = 0; i < 4; ++i) for (int k = 0; k < 3; ++k) q.v[i][k] = rbits(f);
         for (int k = 0; k < 4; ++k) q.xf[k] = rbits(f);
     }
-    const int E = ri(f);
-    if (E < 0 || E > MW_LABEL_MAX_ENTS) { fprintf(stderr, "label_frame: parameters the engine refuses\n"); return 2; }
-    // the engine's layout with N = 1: [E], [3][E], [9][E]; exactly as many elements as the call may touch
-    std::vector<int32_t> ekind((size_t)E), emesh((size_t)E);
-    std::vector<double> epos((size_t)E * 3), edir((size_t)E), egeom((size_t)E * 9);
-    for (int s = 0; s < E; ++s) {
-        ekind[s] = ri(f); emesh[s] = ri(f);
-        for (int k = 0; k < 3; ++k) epos[(size_t)k * E + s] = rd(f);
-        edir[s] = rd(f);
-        for (int k = 0; k < 9; ++k) egeom[(size_t)k * E + s] = rd(f);
-    }
+    World world;
+    if (!world.read(f, SLOTS | WIDE, MW_LABEL_MAX_ENTS)) return refused();
+    const int E = world.E;
     const int nmesh = ri(f);
     std::vector<MwMeshDesc> descs((size_t)(nmesh > 0 ? nmesh : 0));
     std::vector<float> pool;
@@ -89,15 +66,11 @@ int main(int argc, char **argv)
     if (!l.fits) { fprintf(stderr, "label_frame: a frame or scene the engine refuses\n"); return 2; }
     if (band_rows < 1) band_rows = l.band_rows;
     if (chunk < 1) chunk = l.chunk;
-    int32_t np = npolys, carry = -1, nsegs = 0;
-    uint32_t status = 0;
-    double ax = 0.0, ay = 0.0, az = 0.0, adir = 0.0, cam[4] = {0.0, 0.0, 0.0, 0.0}, extent[4] = {0.0, 0.0, 0.0, 0.0};
+    int32_t np = npolys;
+    double ay = 0.0, cam[4] = {0.0, 0.0, 0.0, 0.0};
     MwLabelArgs a{};
-    a.r.w.nsegs = &nsegs; a.r.w.extent = extent; a.r.w.ekind = ekind.data(); a.r.w.epos = epos.data(); a.r.w.egeom = egeom.data(); a.r.w.carry = &carry;
-    a.r.w.ax = &ax; a.r.w.az = &az; a.r.w.status = &status;
-    a.r.w.N = 1; a.r.w.E = E; a.r.w.max_segs = 0; a.r.w.shared_geom = 1;
-    a.r.adir = &adir;
-    a.ay = &ay; a.cam = cam; a.edir = edir.data(); a.emesh = emesh.data(); a.polys = polys.data(); a.npolys = &np;
+    a.r = world.ray();
+    a.ay = &ay; a.cam = cam; a.edir = world.edir.data(); a.emesh = world.emesh.data(); a.polys = polys.data(); a.npolys = &np;
     a.mesh = nmesh > 0 ? descs.data() : nullptr; a.mesh_pos = nmesh > 0 ? pool.data() : nullptr;
     a.max_polys = npolys; a.n_mesh = nmesh; a.W = W; a.H = H; a.msaa = msaa;
     const size_t pixels = (size_t)W * H;
@@ -113,7 +86,7 @@ int main(int argc, char **argv)
     const mwlabel::Out out{cls.data(), code.data(), depth.data(), pix.data(), box.data()};
     const int nsteps = ri(f);
     for (int t = 0; t < nsteps; ++t) {
-        ax = rd(f); ay = rd(f); az = rd(f); adir = rd(f);
+        world.ax = rd(f); ay = rd(f); world.az = rd(f); world.adir = rd(f);
         for (double &v : cam) v = rd(f);
         if (ri(f) != 0) mwlabel::frame_env<mwlabel::HostOps>(a, p, 0, lds, band_rows, chunk, !(p.flags & MW_LABEL_UNPRUNED), out, 0, 1);
         for (size_t k = 0; k < pixels; ++k) printf("%u%s", (unsigned)cls[k], k + 1 == pixels ? "" : " ");

@@ -2,33 +2,18 @@
 // undefined-behaviour sanitizers): one env's world from a file, the field by whole-grid passes and again by directional sweeps — the
 // two must agree —, then the query at the file's positions.
 //
-// The file, whitespace-separated (doubles as Python's repr, which round-trips):
+// The file (hostcheck.h: the tokens, the world block):
 //   cell margin reach gx gz flags target_slot
-//   agent_radius max_forward_step carry
-//   min_x max_x min_z max_z
-//   nsegs, then ax az bx bz per segment
-//   E, then kind x y z radius per slot
+//   the world: AGENT with CARRY, EXTENT, SEGS, SLOTS
 //   has_target [x y z]
 //   nq, then x z per position
 // The answer: "field <ok> <passes> <sweep rounds>", the gz * gx cells, then "cost next wx wz" per position (%a).
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#define HOSTCHECK_PROGRAM "nav_field"
+#include "hostcheck.h"
 
 #include "../../miniworld_amd/csrc/mw_nav.h"
 
-static double rd(FILE *f)
-{
-    double v;
-    if (fscanf(f, "%lf", &v) != 1) { fprintf(stderr, "nav_field: short file\n"); exit(2); }
-    return v;
-}
-static int ri(FILE *f)
-{
-    int v;
-    if (fscanf(f, "%d", &v) != 1) { fprintf(stderr, "nav_field: short file\n"); exit(2); }
-    return v;
-}
+using namespace hostcheck;
 
 int main(int argc, char **argv)
 {
@@ -38,37 +23,19 @@ int main(int argc, char **argv)
     mw_nav_params p{};
     p.cell = rd(f); p.margin = rd(f); p.reach = rd(f);
     p.gx = ri(f); p.gz = ri(f); p.flags = ri(f); p.target_slot = ri(f);
-    MwNavArgs a{};
-    a.agent_radius = rd(f); a.max_forward_step = rd(f);
-    int32_t carry = ri(f);
-    std::vector<double> extent(4);
-    for (double &v : extent) v = rd(f);
-    int32_t nsegs = ri(f);
-    std::vector<double> segs((size_t)nsegs * 4 + 1);
-    for (int i = 0; i < nsegs * 4; ++i) segs[i] = rd(f);
-    const int E = ri(f);
-    std::vector<int32_t> kind((size_t)E + 1);
-    std::vector<double> pos((size_t)E * 3 + 1), geom((size_t)E * 9 + 1);
-    for (int s = 0; s < E; ++s) {       // (the engine's layouts with N = 1: [3][E], [9][E])
-        kind[s] = ri(f);
-        for (int k = 0; k < 3; ++k) pos[(size_t)k * E + s] = rd(f);
-        geom[(size_t)7 * E + s] = rd(f);
-    }
+    World world;
+    if (!world.read(f, AGENT | CARRY | EXTENT | SEGS | SLOTS)) return refused();
+    const int E = world.E;
     double target[3];
     const bool has_target = ri(f) != 0;
     if (has_target) for (double &v : target) v = rd(f);
     const int nq = ri(f);
-    std::vector<double> q((size_t)nq * 2 + 1);
-    for (int i = 0; i < nq * 2; ++i) q[i] = rd(f);
+    std::vector<double> q((size_t)(nq > 0 ? nq : 0) * 2);
+    for (double &v : q) v = rd(f);
     fclose(f);
-    if (p.gx < 1 || p.gz < 1 || (long long)p.gx * p.gz > MW_NAV_MAX_CELLS || p.target_slot < 0 || p.target_slot >= (E > 0 ? E : 1)) {
-        fprintf(stderr, "nav_field: parameters the engine refuses\n");
-        return 2;
-    }
-    uint32_t status = 0;
-    a.segs = segs.data(); a.nsegs = &nsegs; a.extent = extent.data(); a.ekind = kind.data(); a.epos = pos.data(); a.egeom = geom.data();
-    a.carry = &carry; a.ax = nullptr; a.az = nullptr; a.status = &status;
-    a.N = 1; a.E = E; a.max_segs = nsegs; a.shared_geom = 1;
+    if (p.gx < 1 || p.gz < 1 || (long long)p.gx * p.gz > MW_NAV_MAX_CELLS || p.target_slot < 0 || p.target_slot >= (E > 0 ? E : 1))
+        return refused();
+    const MwNavArgs a = world.nav();
 
     const size_t cells = (size_t)p.gx * p.gz;
     std::vector<uint16_t> field(cells), swept(cells);

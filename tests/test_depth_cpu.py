@@ -19,10 +19,9 @@ import depth_reference as ref
 import nav_reference as nav
 import ray_reference as ray
 from helpers import stub_engine
+from query_checks import (CSRC, ROOT, build, check_does_not_wait, check_kernel, check_refuses_null_engine, check_units_built, pose_of as _pose_of, run,
+                          scene as _scene, scene_walk)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "miniworld_amd", "csrc")
 CELL = 0.25
 NORTH = 2
 SENSOR = ref.SENSOR
@@ -35,27 +34,10 @@ FRAMES = [(8, 80, 60), (4, 80, 60), (1, 80, 60), (8, 21, 13), (1, 21, 13)]
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("depth_project") / "depth_project")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", os.path.join(HERE, "hostcheck", "depth_project.cpp"), "-o", exe])
-    return exe
+    return build("depth_project", tmp_path_factory.mktemp("depth_project"))
 
 
-_scenes, _frames = {}, {}
-
-
-def _scene(cls_name, seed=0):
-    if (cls_name, seed) not in _scenes:
-        from miniworld_amd import envs
-        from miniworld_amd.scene import scene_from_env
-        env = getattr(envs, cls_name)(host_only=True)
-        env.reset(seed=seed)
-        _scenes[(cls_name, seed)] = scene_from_env(env)
-    return _scenes[(cls_name, seed)]
-
-
-def _pose_of(sc):
-    return (float(sc["agent_pos"][0]), float(sc["agent_pos"][2]), float(sc["agent_dir"]))
+_frames = {}
 
 
 def _render(cls_name, pose, cam, msaa, W, H, seed=0):
@@ -76,24 +58,9 @@ def _render(cls_name, pose, cam, msaa, W, H, seed=0):
     return _frames[key]
 
 
-def _walk(cls_name, steps, seed=0):
+def _poses(cls_name, steps, seed=0):
     """poses (x, z, dir) from the world's own first one: turns and forward moves of the env's sizes, kept inside the extent"""
-    sc = _scene(cls_name, seed)
-    ext = [float(v) for v in sc["extent"]]
-    x, z, d = _pose_of(sc)
-    out = [(x, z, d)]
-    rng = np.random.default_rng(3400 + seed)
-    for _ in range(steps - 1):
-        a = rng.integers(0, 3)
-        if a == 0:
-            d += math.radians(15)
-        elif a == 1:
-            d -= math.radians(15)
-        else:
-            x = min(max(x + 0.15 * math.cos(d), ext[0] + 0.5), ext[1] - 0.5)
-            z = min(max(z - 0.15 * math.sin(d), ext[2] + 0.5), ext[3] - 0.5)
-        out.append((x, z, d))
-    return out
+    return scene_walk(cls_name, steps, seed, 3400 + seed, 15)
 
 
 def _bits(depth):
@@ -115,11 +82,7 @@ def _run(program, tmp_path, msaa, W, H, target, extent, steps, sensor=SENSOR, ga
     for pose, cam, mask, clear, depth in steps:
         lines.append(" ".join(repr(float(v)) for v in tuple(pose) + tuple(cam)) + f" {int(mask)} {int(clear)}")
         lines.append(_bits(depth))
-    path = tmp_path / "walk.txt"
-    path.write_text("\n".join(lines) + "\n")
-    r = subprocess.run([program, str(path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-300:], r.stderr[-2000:])
-    rows = r.stdout.split("\n")[:-1]
+    rows = run(program, tmp_path / "walk.txt", lines, blank=True)
     per = 2 if to_map else 1
     assert len(rows) == per * len(steps)
     out = []
@@ -176,7 +139,7 @@ FEW_SHAPES = [_window(33), _window(9, anchor="bottom", north=True), _window(2, n
 @pytest.mark.parametrize("cls_name", ["Hallway", "OneRoom", "FourRooms", "MazeS3"])
 def test_walk_equals_the_restatement(program, tmp_path, cls_name):
     extent = [float(v) for v in _scene(cls_name)["extent"]]
-    poses = _walk(cls_name, 4)
+    poses = _poses(cls_name, 4)
     seen = {"floor": 0, "obstacle": 0, "clamped": 0, "new_later": 0, "dropped_far": 0}
     for f, (msaa, W, H) in enumerate(FRAMES):
         # a camera per step, another start per frame format; the first step clears the map's garbage, the third is masked off, the last clears again
@@ -253,7 +216,7 @@ def test_synthetic_depth_edges(program, tmp_path):
 def test_map_accumulates_clears_and_obeys_the_mask(program, tmp_path):
     sc = _scene("OneRoom")
     extent = [float(v) for v in sc["extent"]]
-    poses = _walk("OneRoom", 6)
+    poses = _poses("OneRoom", 6)
     cam = CAMERAS[0]
     frames = [_render("OneRoom", p, cam, 8, 80, 60)[0] for p in poses]
     for min_points in (1, 3):
@@ -286,7 +249,7 @@ def _geometry_poses(cls_name):
     """The walk's poses.  In FourRooms turned by 270 degrees: a doorway's lintel (the wall between 2.2 m and the ceiling) is drawn but
     is no collision segment, and from the world's own first heading it fills more than the cap allows of a 21 x 13 frame."""
     turn = math.radians(270) if cls_name == "FourRooms" else 0.0
-    return [(x, z, d + turn) for x, z, d in _walk(cls_name, 3)]
+    return [(x, z, d + turn) for x, z, d in _poses(cls_name, 3)]
 
 
 GEOMETRY = [(c, m, W, H) for c in ("Hallway", "OneRoom", "FourRooms", "MazeS3") for (m, W, H) in ((8, 80, 60), (4, 80, 60), (1, 80, 60), (8, 21, 13))]
@@ -307,7 +270,7 @@ def test_every_pixel_lies_on_the_world_the_renderer_drew(cls_name, msaa, W, H):
 
 def test_a_wrong_sample_offset_or_sign_fails_the_geometry():
     """the check above is sharp: the pixel's centre in the place of sample 0, or a flipped pitch, leaves far more pixels off the world"""
-    pose, cam = _walk("OneRoom", 1)[0], CAMERAS[2]
+    pose, cam = _poses("OneRoom", 1)[0], CAMERAS[2]
     depth, z16 = _render("OneRoom", pose, cam, 8, 80, 60)
     good, _ = ref.unclassified(depth, z16, pose, cam, 8, ref.solids_of_scene(_scene("OneRoom")))
     centre, _ = ref.unclassified(depth, z16, pose, cam, 1, ref.solids_of_scene(_scene("OneRoom")))         # (1 sample: the centre)
@@ -342,28 +305,19 @@ def test_header_declares_the_entry_point_and_the_build_has_the_units():
     for cited in ("opengl.py:400-435", "miniworld.py:1200-1222", "entity.py:477-503", "z * z * (far - near) / (far * near * 65535)"):
         assert cited in header, cited
     assert "mw_depth_project" in engine.SIGNATURES and engine.EXPORTS == list(engine.SIGNATURES)
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    for unit in ("mw_depth.hip", "mw_engine_depth.hip"):
-        assert re.search(r"^SRCS = (?:.*\\\n)*.*\b" + re.escape(unit), make, re.M), unit
-    decl = open(os.path.join(CSRC, "mw_kernels.h")).read()
-    unit = open(os.path.join(CSRC, "mw_depth.hip")).read()
-    assert len(re.findall(r'extern "C" __global__ void mw_depth_kernel\(', decl)) == 1
-    assert len(re.findall(r"__global__[^;{]*\bmw_depth_kernel\(", unit)) == 1
+    check_units_built("mw_depth.hip", "mw_engine_depth.hip")
+    check_kernel("mw_depth_kernel", "mw_depth.hip")
     depth_h = open(os.path.join(CSRC, "mw_depth.h")).read()
     for shared in ("mwego::frame_of", "mwnav::grid_of", "mwnav::covers", "mw::sincos_det"):
         assert shared in depth_h, shared
     code = re.sub(r"//[^\n]*", "", depth_h)
     for own in ("sqrt", "sin(", "cos(", "tan(", "atan"):
         assert own not in code.replace("sincos_det(", ""), own
-    assert "does not wait for the Maze's" in " ".join(open(os.path.join(CSRC, "mw_engine_depth.hip")).read().replace("//", " ").split())
+    check_does_not_wait("mw_engine_depth.hip")
 
 
 def test_library_exports_the_entry_point_and_refuses_a_null_engine():
-    from miniworld_amd import engine
-    engine.build_library()
-    lib = engine.load_library()
-    assert hasattr(lib, "mw_depth_project")
-    assert lib.mw_depth_project(None, None, None, None, 9, 0, None, None, 1, None, None, None, None, None) == -1
+    check_refuses_null_engine("mw_depth_project", None, None, None, 9, 0, None, None, 1, None, None, None, None, None)
 
 
 def test_vec_env_refusals_and_the_recorded_call(monkeypatch):

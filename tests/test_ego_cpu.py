@@ -8,7 +8,6 @@ stub engine and the library call of one ego_update."""
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,10 +16,9 @@ import ego_reference as ref
 import nav_reference as nav
 import seen_reference as seen_ref
 from helpers import stub_engine
+from query_checks import (CSRC, ROOT, build, check_does_not_wait, check_kernel, check_refuses_null_engine, check_units_built, host_world, launch_of as _policy,
+                          run, walk as _walk, world_lines)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "miniworld_amd", "csrc")
 CELL = 0.25
 FOV = 2.0 * math.atan(math.tan(math.radians(60.0) / 2.0) * 80.0 / 60.0)        # the default camera's horizontal field of view
 ENTITIES, NORTH = 1, 2
@@ -29,39 +27,7 @@ ALL = ref.WALL | ref.ENTITY | ref.VISIBLE
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("ego_map") / "ego_map")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", os.path.join(HERE, "hostcheck", "ego_map.cpp"), "-o", exe])
-    return exe
-
-
-def _host_world(cls_name, seed):
-    from miniworld_amd import envs
-    from miniworld_amd.scene import scene_from_env
-    env = getattr(envs, cls_name)(host_only=True)
-    env.reset(seed=seed)
-    sc = scene_from_env(env)
-    w = nav.world_of_scene(sc)
-    w["agent"] = (float(sc["agent_pos"][0]), float(sc["agent_pos"][2]), float(sc["agent_dir"]))
-    return w
-
-
-def _walk(w, rng, steps):
-    """poses (x, z, dir): from the agent's own, forward moves and turns of the env's sizes, kept inside the extent"""
-    ext = w["extent"]
-    x, z, d = w["agent"]
-    out = [(x, z, d)]
-    for _ in range(steps - 1):
-        a = rng.integers(0, 3)
-        if a == 0:
-            d += math.radians(15)
-        elif a == 1:
-            d -= math.radians(15)
-        else:
-            x = min(max(x + 0.45 * math.cos(d), ext[0] + 0.1), ext[1] - 0.1)
-            z = min(max(z - 0.45 * math.sin(d), ext[2] + 0.1), ext[3] - 0.1)
-        out.append((x, z, d))
-    return out
+    return build("ego_map", tmp_path_factory.mktemp("ego_map"))
 
 
 def _window(size=9, cell=CELL, anchor="centre", north=False, planes=ALL, wall_radius=CELL / 2, entity_pad=CELL / 2, max_range=10.0, cos_half=None,
@@ -85,20 +51,12 @@ def _run(program, tmp_path, w, win, steps, src=None, src_cell=CELL, fill=0, garb
     else:
         lines.append(f"{src.dtype.itemsize} {float(src_cell)!r} {src.shape[1]} {src.shape[0]} {int(fill)}")
         lines.append(" ".join(str(int(v)) for v in src.ravel()))
-    lines += [str(garbage), f"{w['agent_radius']!r} {w['max_forward_step']!r}", " ".join(repr(float(v)) for v in w["extent"]), str(len(w["segs"]))]
-    lines += [" ".join(repr(float(v)) for v in s) for s in w["segs"]]
-    lines.append(str(len(w["kind"])))
-    for s in range(len(w["kind"])):
-        lines.append(f"{int(w['kind'][s])} " + " ".join(repr(float(v)) for v in w["pos"][s]) + f" {float(w['radius'][s])!r}")
+    lines += [str(garbage)] + world_lines(w)
     lines.append(str(len(steps)))
     for x, z, d, carry, mask, origin in steps:
         ox, oz = origin if origin is not None else (0.0, 0.0)
         lines.append(f"{float(x)!r} {float(z)!r} {float(d)!r} {int(carry)} {int(mask)} {int(origin is not None)} {float(ox)!r} {float(oz)!r}")
-    path = tmp_path / "world.txt"
-    path.write_text("\n".join(lines) + "\n")
-    r = subprocess.run([program, str(path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-300:], r.stderr[-2000:])
-    rows = r.stdout.split("\n")[:-1]
+    rows = run(program, tmp_path / "world.txt", lines, blank=True)
     assert len(rows) == 2 * len(steps)
     out = []
     for k in range(len(steps)):
@@ -151,7 +109,7 @@ def test_walk_equals_the_restatement(program, tmp_path, cls_name, seeds, entitie
     rng = np.random.default_rng(3300)
     seen = {"wall": set(), "visible": set(), "outside_wall": 0, "fill": 0, "entity": 0, "carried": 0, "entity_blocks": 0}
     for seed in seeds:
-        w = _host_world(cls_name, seed)
+        w = host_world(cls_name, seed)[2]
         ext = w["extent"]
         poses = _walk(w, rng, 11)
         # one slot carried for part of the walk, a masked-off step, an origin that is not the agent's, a pose in the extent's corner
@@ -201,7 +159,7 @@ def test_walk_equals_the_restatement(program, tmp_path, cls_name, seeds, entitie
 
 
 def test_a_nan_pose_and_a_masked_env(program, tmp_path):
-    w = _host_world("PickupObjects", 0)
+    w = host_world("PickupObjects", 0)[2]
     rng = np.random.default_rng(3301)
     nan = float("nan")
     for dtype, fill in ((np.uint8, 0x5A), (np.uint16, 0xFFFF)):
@@ -225,7 +183,7 @@ def test_a_nan_pose_and_a_masked_env(program, tmp_path):
 @pytest.mark.parametrize("S", [9, 8])
 def test_a_north_window_on_the_grid_is_the_plain_crop(program, tmp_path, S):
     """cell == the source's cell, the origin on a cell's centre (odd S) or corner (even S): the window's points are cell centres"""
-    w = _host_world("FourRooms", 0)
+    w = host_world("FourRooms", 0)[2]
     rng = np.random.default_rng(3302)
     ext = w["extent"]
     gx, gz = nav.grid_shape(ext, CELL)
@@ -264,7 +222,7 @@ def test_heading_zero_is_the_north_window_turned(program, tmp_path):
     import pyoracle
     s, c = pyoracle.sincos(0.0)
     assert (c, s) == (1.0, 0.0)         # the engine's deterministic sin / cos at 0: the heading is exactly (1, -0)
-    w = _host_world("PickupObjects", 0)
+    w = host_world("PickupObjects", 0)[2]
     x, z, _ = w["agent"]
     for S in (17, 8):          # (half a metre between points: the window reaches past the range and the cone)
         steps = [_step((x, z, 0.0)), _step((x + 0.3, z - 0.7, 0.0))]
@@ -292,13 +250,8 @@ def test_header_declares_the_entry_point_and_the_build_has_the_units():
     assert re.search(r"#define MW_ABI_VERSION 4\b", header)
     assert header.index("---- explored-area maps") < header.index("---- egocentric map windows") < header.index("int mw_ego_map(")
     assert "mw_ego_map" in engine.SIGNATURES
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    for unit in ("mw_ego.hip", "mw_engine_ego.hip"):
-        assert re.search(r"^SRCS = (?:.*\\\n)*.*\b" + re.escape(unit), make, re.M), unit
-    decl = open(os.path.join(CSRC, "mw_kernels.h")).read()
-    unit = open(os.path.join(CSRC, "mw_ego.hip")).read()
-    assert len(re.findall(r'extern "C" __global__ void mw_ego_kernel\(', decl)) == 1
-    assert len(re.findall(r"__global__[^;{]*\bmw_ego_kernel\(", unit)) == 1
+    check_units_built("mw_ego.hip", "mw_engine_ego.hip")
+    check_kernel("mw_ego_kernel", "mw_ego.hip")
     # the arithmetic is the shared one: the ego header defines no ray, wall or cone formula of its own
     ego_h = open(os.path.join(CSRC, "mw_ego.h")).read()
     for shared in ("mwnav::grid_of", "mwnav::seg_dist", "mwnav::segs_of", "mwnav::nsegs_of", "mwray::disc_of", "mwray::ray_of", "mwray::wall_of",
@@ -307,20 +260,11 @@ def test_header_declares_the_entry_point_and_the_build_has_the_units():
     code = re.sub(r"//[^\n]*", "", ego_h)
     for own in ("ray_seg", "ray_circle", "sincos", "cos_half *"):
         assert own not in code, own
-    assert "does not wait for the Maze's" in " ".join(open(os.path.join(CSRC, "mw_engine_ego.hip")).read().replace("//", " ").split())
+    check_does_not_wait("mw_engine_ego.hip")
 
 
 def test_library_exports_the_entry_point_and_refuses_a_null_engine():
-    from miniworld_amd import engine
-    engine.build_library()
-    lib = engine.load_library()
-    assert hasattr(lib, "mw_ego_map")
-    assert lib.mw_ego_map(None, None, 9, 1, 0, None, None, None, None, None, 0, 0, None, None) == -1
-
-
-def _policy(program, n, max_segs, max_ents, planes):
-    out = subprocess.run([program, "--policy", str(n), str(max_segs), str(max_ents), str(planes)], capture_output=True, text=True, check=True).stdout.split()
-    return dict(zip(("grid", "threads", "lds", "fits"), map(int, out)))
+    check_refuses_null_engine("mw_ego_map", None, 9, 1, 0, None, None, None, None, None, 0, 0, None, None)
 
 
 def test_ego_launch_is_a_workgroup_per_env_and_refuses_what_lds_does_not_hold(program):

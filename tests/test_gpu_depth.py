@@ -10,6 +10,7 @@ import pytest
 
 import depth_reference as ref
 import nav_reference as nav
+from query_checks import dev as _dev, vec_env
 
 pytestmark = pytest.mark.gpu
 N = 4
@@ -17,12 +18,8 @@ SENSOR = ref.SENSOR
 
 
 def _vec(env_id, n=N, **kw):
-    from miniworld_amd.vec_env import MiniWorldVecEnv
-    kw.setdefault("seed", 0)
     kw.setdefault("want_depth", True)
-    vec = MiniWorldVecEnv(env_id, n, **kw)
-    vec.reset()
-    return vec
+    return vec_env(env_id, n, **kw)
 
 
 def _state(vec):
@@ -34,11 +31,6 @@ def _state(vec):
 
 def _sensor(o):
     return dict(min_range=o.min_range, max_range=o.max_range, floor_tol=o.floor_tol, top=o.top)
-
-
-def _dev(a, dtype=None):
-    import torch
-    return None if a is None else torch.as_tensor(np.asarray(a), device="cuda", dtype=dtype)
 
 
 def _window_both(vec, w, depth=None, mask=None):

@@ -10,6 +10,7 @@ import pytest
 
 import ego_reference as ref
 import nav_reference as nav
+from query_checks import dev as _dev, host as _host, poses as _poses, teleport as _teleport, vec_env, worlds as _worlds
 
 pytestmark = pytest.mark.gpu
 N = 8
@@ -17,28 +18,7 @@ CELL = 0.25
 
 
 def _vec(env_id, n=N, **kw):
-    from miniworld_amd.vec_env import MiniWorldVecEnv
-    kw.setdefault("seed", 0)
-    vec = MiniWorldVecEnv(env_id, n, **kw)
-    vec.reset()
-    return vec
-
-
-def _worlds(vec):
-    st = vec.engine.get_state()
-    return [nav.world_of_engine(vec.engine, st, i) for i in range(vec.num_envs)]
-
-
-def _poses(vec):
-    st = vec.state(("agent_pos", "agent_dir"))
-    pos, d = st["agent_pos"].cpu().numpy(), st["agent_dir"].cpu().numpy()
-    return [(pos[i, 0], pos[i, 2], d[i]) for i in range(vec.num_envs)]
-
-
-def _host(t):
-    """a device tensor as numpy; uint16 through its bits"""
-    import torch
-    return t.view(torch.int16).cpu().numpy().view(np.uint16) if t.dtype == torch.uint16 else t.cpu().numpy()
+    return vec_env(env_id, n, **kw)
 
 
 def _random_field(vec, rng):
@@ -50,11 +30,6 @@ def _random_field(vec, rng):
     gx, gz = nav.grid_shape((t.min_x, t.max_x, t.min_z, t.max_z), CELL)
     cells = rng.integers(0, 0xFFFE, (vec.num_envs, gz, gx)).astype(np.uint16)
     return NavField(torch.from_numpy(cells.view(np.int16)).cuda().view(torch.uint16), engine.MwNavParams(CELL, 0.0, 0.0, gx, gz, 0, 0), 0, "walls")
-
-
-def _dev(a):
-    import torch
-    return None if a is None else torch.as_tensor(np.asarray(a), device="cuda")
 
 
 def _update_both(vec, w, source=None, fill=None, mask=None, pos=None):
@@ -94,16 +69,6 @@ def _update_both(vec, w, source=None, fill=None, mask=None, pos=None):
             assert np.array_equal(sample[i], ws), (i, "sample", np.argwhere(sample[i] != ws)[:8].tolist())
         out.append((wp, ws))
     return out
-
-
-def _teleport(vec, xz, direction=None):
-    import torch
-    pos = vec.state(("agent_pos",))["agent_pos"].clone()
-    pos[:, 0], pos[:, 2] = torch.as_tensor(xz[0], dtype=torch.float64, device="cuda"), torch.as_tensor(xz[1], dtype=torch.float64, device="cuda")
-    fields = {"agent_pos": pos}
-    if direction is not None:
-        fields["agent_dir"] = torch.as_tensor(direction, dtype=torch.float64, device="cuda").expand(vec.num_envs).contiguous()
-    vec.set_state_where(torch.ones(vec.num_envs, dtype=torch.uint8, device="cuda"), **fields)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the reference

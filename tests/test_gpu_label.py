@@ -9,6 +9,7 @@ import pytest
 import label_reference as ref
 from depth_reference import z16_of
 from helpers import scene_of_vec_env, vec_env_meshes
+from query_checks import vec_env
 
 pytestmark = pytest.mark.gpu
 N = 8
@@ -16,11 +17,7 @@ MISS_CAP, INTERIOR_FLOOR = 0.005, 0.70         # tests/test_label_cpu.py's caps
 
 
 def _vec(env_id, n=N, **kw):
-    from miniworld_amd.vec_env import MiniWorldVecEnv
-    kw.setdefault("seed", 0)
-    vec = MiniWorldVecEnv(env_id, n, **kw)
-    vec.reset()
-    return vec
+    return vec_env(env_id, n, **kw)
 
 
 def _walk(vec, steps, seed):

@@ -10,19 +10,12 @@ import numpy as np
 import pytest
 
 import nav_reference as ref
+from query_checks import vec_env as _vec
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "examples"))
 
 pytestmark = pytest.mark.gpu
 PICKUP = 4
-
-
-def _vec(env_id, n, **kw):
-    from miniworld_amd.vec_env import MiniWorldVecEnv
-    kw.setdefault("seed", 0)
-    vec = MiniWorldVecEnv(env_id, n, **kw)
-    vec.reset()
-    return vec
 
 
 def _want(vec, fld, envs=None, reach=None):

@@ -11,20 +11,13 @@ import pytest
 
 import nav_reference as nav
 import ray_reference as ref
+from query_checks import vec_env as _vec
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "examples"))
 
 pytestmark = pytest.mark.gpu
 THR = int(re.search(r"constexpr int kRayPerLaneFrom = (\d+);", open(os.path.join(HERE, "..", "miniworld_amd", "csrc", "mw_policy.h")).read()).group(1))
-
-
-def _vec(env_id, n, **kw):
-    from miniworld_amd.vec_env import MiniWorldVecEnv
-    kw.setdefault("seed", 0)
-    vec = MiniWorldVecEnv(env_id, n, **kw)
-    vec.reset()
-    return vec
 
 
 def _worlds(vec, envs=None):

@@ -10,8 +10,8 @@ import re
 import numpy as np
 import pytest
 
-import nav_reference as nav
 import seen_reference as ref
+from query_checks import dev, poses as _poses, teleport as _teleport, vec_env, worlds as _worlds
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 pytestmark = pytest.mark.gpu
@@ -22,22 +22,7 @@ CANDS = int(re.search(r"#define MW_SEEN_CANDS (\d+)", _SEEN_H).group(1))
 
 
 def _vec(env_id, n=N, **kw):
-    from miniworld_amd.vec_env import MiniWorldVecEnv
-    kw.setdefault("seed", 0)
-    vec = MiniWorldVecEnv(env_id, n, **kw)
-    vec.reset()
-    return vec
-
-
-def _worlds(vec):
-    st = vec.engine.get_state()
-    return [nav.world_of_engine(vec.engine, st, i) for i in range(vec.num_envs)]
-
-
-def _poses(vec):
-    st = vec.state(("agent_pos", "agent_dir"))
-    pos, d = st["agent_pos"].cpu().numpy(), st["agent_dir"].cpu().numpy()
-    return [(pos[i, 0], pos[i, 2], d[i]) for i in range(vec.num_envs)]
+    return vec_env(env_id, n, **kw)
 
 
 def _maps(m):
@@ -58,23 +43,12 @@ def _update_both(vec, m, maps, clear=None, mask=None):
     entities = m.obstacles == "walls+entities"
     cands = [ref.update(maps[i], worlds[i], m.cell, poses[i], m.max_range, m.cos_half, entities,
                         clear=bool(clear is not None and clear[i]), mask=bool(mask is None or mask[i])) for i in range(vec.num_envs)]
-    dev = lambda a: None if a is None else torch.as_tensor(np.asarray(a), device="cuda")      # (uint8 or bool, as the caller made it)
     assert vec.seen_update(m, clear=dev(clear), mask=dev(mask)) is m.new
     seen, count, new = m.seen.cpu().numpy(), m.count.cpu().numpy(), m.new.cpu().numpy()
     for i in range(vec.num_envs):
         assert np.array_equal(seen[i], maps[i].seen), (i, "cells that differ", np.argwhere(seen[i] != maps[i].seen)[:8].tolist())
         assert (int(new[i]), int(count[i])) == (maps[i].new, maps[i].count), (i, "new, count")
     return cands
-
-
-def _teleport(vec, xz, direction=None):
-    import torch
-    pos = vec.state(("agent_pos",))["agent_pos"].clone()
-    pos[:, 0], pos[:, 2] = torch.as_tensor(xz[0], dtype=torch.float64, device="cuda"), torch.as_tensor(xz[1], dtype=torch.float64, device="cuda")
-    fields = {"agent_pos": pos}
-    if direction is not None:
-        fields["agent_dir"] = torch.as_tensor(direction, dtype=torch.float64, device="cuda").expand(vec.num_envs).contiguous()
-    vec.set_state_where(torch.ones(vec.num_envs, dtype=torch.uint8, device="cuda"), **fields)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the reference

@@ -11,18 +11,16 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import label_reference as ref
 from helpers import golden_meshes, stub_engine
+from query_checks import (CSRC, ROOT, build, check_does_not_wait, check_kernel, check_refuses_null_engine, check_units_built, launch_of, run,
+                          scene as _scene, scene_walk)
 from test_depth_cpu import CAMERAS
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "miniworld_amd", "csrc")
 FAMILIES = ["Hallway", "OneRoom", "MazeS3", "FourRooms", "Sign", "PickupObjects", "Sidewalk", "CollectHealth"]
 BOUNDS, UNPRUNED = 1, 2
 # the caps of the renderer check (the issue's): misses among a frame's interior pixels, and interior pixels of a frame
@@ -31,44 +29,16 @@ MISS_CAP, INTERIOR_FLOOR = 0.005, 0.70
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("label_frame") / "label_frame")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", os.path.join(HERE, "hostcheck", "label_frame.cpp"), "-o", exe])
-    return exe
+    return build("label_frame", tmp_path_factory.mktemp("label_frame"))
 
 
-_scenes, _frames, _labels = {}, {}, {}
+_frames, _labels = {}, {}
 
 
-def _scene(cls_name, seed=0):
-    if (cls_name, seed) not in _scenes:
-        from miniworld_amd import envs
-        from miniworld_amd.scene import scene_from_env
-        env = getattr(envs, cls_name)(host_only=True)
-        env.reset(seed=seed)
-        _scenes[(cls_name, seed)] = scene_from_env(env)
-    return _scenes[(cls_name, seed)]
-
-
-def _walk(cls_name, steps, seed=0):
+def _poses(cls_name, steps, seed=0):
     """poses (x, y, z, dir) from the world's own first one: turns of 40 degrees and forward moves, kept inside the extent"""
-    sc = _scene(cls_name, seed)
-    ext = [float(v) for v in sc["extent"]]
-    x, y, z = (float(v) for v in sc["agent_pos"])
-    d = float(sc["agent_dir"])
-    out = [(x, y, z, d)]
-    rng = np.random.default_rng(3500 + seed)
-    for _ in range(steps - 1):
-        a = rng.integers(0, 3)
-        if a == 0:
-            d += math.radians(40)
-        elif a == 1:
-            d -= math.radians(40)
-        else:
-            x = min(max(x + 0.15 * math.cos(d), ext[0] + 0.5), ext[1] - 0.5)
-            z = min(max(z - 0.15 * math.sin(d), ext[2] + 0.5), ext[3] - 0.5)
-        out.append((x, y, z, d))
-    return out
+    y = float(_scene(cls_name, seed)["agent_pos"][1])
+    return [(x, y, z, d) for x, z, d in scene_walk(cls_name, steps, seed, 3500 + seed, 40)]
 
 
 def _posed(sc, pose, cam):
@@ -123,11 +93,7 @@ def _run(program, tmp_path, sc, W, H, msaa, steps, flags=0, near=ref.NEAR, far=r
     lines += [str(garbage), str(len(steps))]
     for pose, cam, mask in steps:
         lines.append(" ".join(repr(float(v)) for v in tuple(pose) + tuple(cam)) + f" {int(mask)}")
-    path = tmp_path / "scene.txt"
-    path.write_text("\n".join(lines) + "\n")
-    r = subprocess.run([program, str(path)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stdout[-300:], r.stderr[-2000:])
-    rows = r.stdout.split("\n")[:-1]
+    rows = run(program, tmp_path / "scene.txt", lines, timeout=600, blank=True)
     assert len(rows) == 5 * len(steps)
     out = []
     for k in range(len(steps)):
@@ -151,7 +117,7 @@ FORMATS = [(8, 80, 60, 0), (4, 81, 61, 0), (1, 21, 13, 0), (8, 81, 61, 17), (4, 
 @pytest.mark.parametrize("cls_name", FAMILIES)
 def test_program_equals_the_restatement(program, tmp_path, cls_name):
     sc = _scene(cls_name)
-    poses = _walk(cls_name, 6)
+    poses = _poses(cls_name, 6)
     has_mesh = any(int(k) == ref.ENT_MESH for k in sc["ents_kind"])
     seen = set()
     for k, pose in enumerate(poses):
@@ -170,7 +136,7 @@ def test_program_equals_the_restatement(program, tmp_path, cls_name):
 
 def test_masked_step_keeps_every_byte_and_other_ranges(program, tmp_path):
     sc = _scene("PickupObjects")
-    pose, cam = _walk("PickupObjects", 1)[0], CAMERAS[0]
+    pose, cam = _poses("PickupObjects", 1)[0], CAMERAS[0]
     got = _run(program, tmp_path, sc, 21, 13, 8, [(pose, cam, 0), (pose, cam, 1)], garbage=0x5A)
     assert (got[0]["cls"] == 0x5A).all() and (got[0]["code"] == 0x5A5A5A5A).all() and (got[0]["ent_box"] == 0x5A5A5A5A).all()
     _same(got[1], _label(sc, "PickupObjects", pose, cam, 8, 21, 13), "after the mask")
@@ -237,7 +203,7 @@ RENDERED = [("Hallway", 0, 0, 8, 80, 60), ("OneRoom", 1, 1, 4, 80, 60), ("MazeS3
 
 def _renderer_check(cls_name, k, cam, msaa, W, H, label_of=None):
     sc = _scene(cls_name)
-    pose = k if isinstance(k, tuple) else _walk(cls_name, 6)[k]
+    pose = k if isinstance(k, tuple) else _poses(cls_name, 6)[k]
     z16 = _render(sc, cls_name, pose, cam, msaa, W, H)
     label = label_of(sc, pose, cam) if label_of else _label(sc, cls_name, pose, cam, msaa, W, H)
     return ref.against_frame(label, z16) + (label,)
@@ -303,7 +269,7 @@ def test_bounds_contain_exact_and_the_stats_are_the_codes():
     for cls_name in ("PickupObjects", "Sidewalk", "CollectHealth"):
         sc = _scene(cls_name)
         for k in (0, 3):
-            pose = _walk(cls_name, 6)[k]
+            pose = _poses(cls_name, 6)[k]
             exact = _label(sc, cls_name, pose, CAMERAS[0], 8, 80, 60)
             bounds = _label(sc, cls_name, pose, CAMERAS[0], 8, 80, 60, "bounds")
             on_mesh = exact["cls"] == ref.MESH
@@ -342,34 +308,24 @@ def test_header_declares_the_entry_point_and_the_build_has_the_units():
     for cited in ("miniworld.py:1197-1221", "entity.py:150-161", "entity.py:409-432", "miniworld.py:512"):
         assert cited in header, cited
     assert "mw_label_frame" in engine.SIGNATURES and engine.EXPORTS == list(engine.SIGNATURES)
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    for unit in ("mw_label.hip", "mw_engine_label.hip"):
-        assert re.search(r"^SRCS = (?:.*\\\n)*.*\b" + re.escape(unit), make, re.M), unit
-    decl = open(os.path.join(CSRC, "mw_kernels.h")).read()
-    unit = open(os.path.join(CSRC, "mw_label.hip")).read()
-    assert len(re.findall(r'extern "C" __global__ void mw_label_kernel\(', decl)) == 1
-    assert len(re.findall(r"__global__[^;{]*\bmw_label_kernel\(", unit)) == 1
+    check_units_built("mw_label.hip", "mw_engine_label.hip")
+    check_kernel("mw_label_kernel", "mw_label.hip")
     label_h = open(os.path.join(CSRC, "mw_label.h")).read()
     for shared in ("mwdepth::camera_of", "mwdepth::subpixel_of", "mw::sincos_det"):
         assert shared in label_h, shared
     code = re.sub(r"//[^\n]*", "", label_h)
     for own in ("sin(", "cos(", "tan(", "atan", "fma("):
         assert own not in code.replace("sincos_det(", ""), own
-    assert "does not wait for the Maze's" in " ".join(open(os.path.join(CSRC, "mw_engine_label.hip")).read().replace("//", " ").split())
+    check_does_not_wait("mw_engine_label.hip")
 
 
 def test_library_exports_the_entry_point_and_refuses_a_null_engine():
-    from miniworld_amd import engine
-    engine.build_library()
-    lib = engine.load_library()
-    assert hasattr(lib, "mw_label_frame")
-    assert lib.mw_label_frame(None, None, None, None, None, None, None, None, None) == -1
+    check_refuses_null_engine("mw_label_frame", None, None, None, None, None, None, None, None)
 
 
 def test_label_launch(program):
     def launch(*args):
-        out = subprocess.run([program, "--policy"] + [str(a) for a in args], capture_output=True, text=True, check=True).stdout.split()
-        return dict(zip(("grid", "threads", "lds", "band_rows", "chunk", "fits"), map(int, out)))
+        return launch_of(program, *args, names=("grid", "threads", "lds", "band_rows", "chunk", "fits"))
 
     def bytes_of(pixels, chunk, ents):
         return (pixels * 10 + chunk * 160 + ents * 92 + 15) // 16 * 16

@@ -8,57 +8,35 @@ dynamics."""
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import nav_reference as ref
 from helpers import stub_engine
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "miniworld_amd", "csrc")
-NAMES = ("mw_nav_build", "mw_nav_query")
+from query_checks import ROOT, build, check_kernel, check_refuses_null_engine, check_units_built, host_world, run, world_lines
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("nav_field") / "nav_field")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", os.path.join(HERE, "hostcheck", "nav_field.cpp"), "-o", exe])
-    return exe
+    return build("nav_field", tmp_path_factory.mktemp("nav_field"))
 
 
 def _host_world(cls_name, seed):
-    from miniworld_amd import envs
-    from miniworld_amd.scene import scene_from_env
-    env = getattr(envs, cls_name)(host_only=True)
-    env.reset(seed=seed)
-    sc = scene_from_env(env)
+    """... and the slot of the box to go to"""
+    env, sc, w = host_world(cls_name, seed)
     ents = [e for e in env.entities if e is not env.agent]
-    goal = ents.index(env.box) if hasattr(env, "box") else 0
-    return env, sc, ref.world_of_scene(sc), goal
+    return env, sc, w, ents.index(env.box) if hasattr(env, "box") else 0
 
 
 def _run(program, tmp_path, w, cell, margin, flags, target, reach, shape, positions):
     gx, gz = shape
     slot = isinstance(target, int)
-    lines = [f"{cell!r} {margin!r} {float(reach or 0.0)!r} {gx} {gz} {flags} {target if slot else 0}",
-             f"{w['agent_radius']!r} {w['max_forward_step']!r} {w['carry']}",
-             " ".join(repr(float(v)) for v in w["extent"]),
-             str(len(w["segs"]))] + [" ".join(repr(float(v)) for v in s) for s in w["segs"]]
-    lines.append(str(len(w["kind"])))
-    for s in range(len(w["kind"])):
-        lines.append(f"{int(w['kind'][s])} " + " ".join(repr(float(v)) for v in w["pos"][s]) + f" {float(w['radius'][s])!r}")
+    lines = [f"{cell!r} {margin!r} {float(reach or 0.0)!r} {gx} {gz} {flags} {target if slot else 0}"] + world_lines(w, carry=True)
     lines.append("1 " + " ".join(repr(float(v)) for v in target) if not slot else "0")
     lines.append(str(len(positions)))
     lines += [f"{float(x)!r} {float(z)!r}" for x, z in positions]
-    path = tmp_path / "world.txt"
-    path.write_text("\n".join(lines) + "\n")
-    r = subprocess.run([program, str(path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-300:], r.stderr[-2000:])
-    out = r.stdout.split("\n")
+    out = run(program, tmp_path / "world.txt", lines)
     head = out[0].split()
     assert head[0] == "field"
     f = np.array(out[1].split(), np.int64).astype(np.uint16).reshape(gz, gx)
@@ -179,24 +157,16 @@ def test_header_declares_the_entry_points():
     assert (engine.NAV_BLOCKED, engine.NAV_UNREACHED, engine.NAV_MAX_CELLS) == (0xFFFF, 0xFFFE, 32768)
     for k, v in (("MW_NAV_ENTITIES", engine.NAV_ENTITIES), ("MW_NAV_BLOCKED", "0xFFFF"), ("MW_NAV_UNREACHED", "0xFFFE"), ("MW_NAV_MAX_CELLS", 32768)):
         assert re.search(rf"#define {k} {v}\b", header), k
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SRCS = (?:.*\\\n)*.*\bmw_nav\.hip\b", make, re.M)
-    decl = open(os.path.join(CSRC, "mw_kernels.h")).read()
-    unit = open(os.path.join(CSRC, "mw_nav.hip")).read()
+    check_units_built("mw_nav.hip")
     for k in ("mw_nav_build_kernel", "mw_nav_query_kernel"):
-        assert re.search(r'extern "C" __global__ void ' + k + r"\(", decl), k
-        assert len(re.findall(r"__global__[^;{]*\b" + k + r"\(", unit)) == 1, k
+        check_kernel(k, "mw_nav.hip")
 
 
 def test_library_exports_the_entry_points_and_refuses_a_null_engine():
     from miniworld_amd import engine
-    engine.build_library()
-    lib = engine.load_library()
-    for name in NAMES:
-        assert hasattr(lib, name), name
     p = engine.MwNavParams(0.25, 0.125, 0.0, 4, 4, 0, 0)
-    assert lib.mw_nav_build(None, p, None, None, None, None) == -1
-    assert lib.mw_nav_query(None, p, None, None, None, None, None, None, None) == -1
+    check_refuses_null_engine("mw_nav_build", p, None, None, None, None)
+    check_refuses_null_engine("mw_nav_query", p, None, None, None, None, None, None, None)
 
 
 def test_vec_env_argument_errors_and_calls(monkeypatch):

@@ -8,7 +8,6 @@ a stub engine, and the smoothed follower of examples/expert_smooth.py on the ora
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,47 +15,22 @@ import pytest
 import nav_reference as nav
 import ray_reference as ref
 from helpers import stub_engine
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "miniworld_amd", "csrc")
+from query_checks import (CSRC, ROOT, build, check_does_not_wait, check_kernel, check_refuses_null_engine, check_units_built, host_world as _host_world,
+                          launch_of, run, world_lines)
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("ray_cast") / "ray_cast")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", os.path.join(HERE, "hostcheck", "ray_cast.cpp"), "-o", exe])
-    return exe
-
-
-def _host_world(cls_name, seed):
-    from miniworld_amd import envs
-    from miniworld_amd.scene import scene_from_env
-    env = getattr(envs, cls_name)(host_only=True)
-    env.reset(seed=seed)
-    sc = scene_from_env(env)
-    w = nav.world_of_scene(sc)
-    w["agent"] = (float(sc["agent_pos"][0]), float(sc["agent_pos"][2]), float(sc["agent_dir"]))
-    return env, sc, w
+    return build("ray_cast", tmp_path_factory.mktemp("ray_cast"))
 
 
 def _run(program, tmp_path, w, max_t, radius, flags, offsets, origins, dirs):
-    lines = [f"{float(max_t)!r} {float(radius)!r} {flags}", f"{w['agent_radius']!r} {w['max_forward_step']!r} {w['carry']}",
-             " ".join(repr(float(v)) for v in w["agent"]), str(len(w["segs"]))]
-    lines += [" ".join(repr(float(v)) for v in s) for s in w["segs"]]
-    lines.append(str(len(w["kind"])))
-    for s in range(len(w["kind"])):
-        lines.append(f"{int(w['kind'][s])} " + " ".join(repr(float(v)) for v in w["pos"][s]) + f" {float(w['radius'][s])!r}")
+    lines = [f"{float(max_t)!r} {float(radius)!r} {flags}"] + world_lines(w, carry=True, pose=True, extent=False)
     lines.append(str(len(offsets)))
     lines.append(" ".join(repr(float(v)) for v in offsets))
     lines.append(str(len(origins)))
     lines += [" ".join(repr(float(v)) for v in (*o, *d)) for o, d in zip(origins, dirs)]
-    path = tmp_path / "world.txt"
-    path.write_text("\n".join(lines) + "\n")
-    r = subprocess.run([program, str(path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-300:], r.stderr[-2000:])
-    rows = [line.split() for line in r.stdout.split("\n") if line]
+    rows = [line.split() for line in run(program, tmp_path / "world.txt", lines)]
     assert len(rows) == len(offsets) + len(origins)
     t = np.array([float.fromhex(x[0]) for x in rows])
     hit = np.array([int(x[1]) for x in rows], np.int32)
@@ -166,30 +140,19 @@ def test_header_declares_the_entry_point():
     assert (engine.RAY_ENTITIES, engine.RAY_ENT, engine.RAY_MAX) == (1, 0x10000, 4096)
     for k, v in (("MW_RAY_ENTITIES", 1), ("MW_RAY_ENT", "0x10000"), ("MW_RAY_MAX", 4096)):
         assert re.search(rf"#define {k} {v}\b", header), k
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    for unit in ("mw_ray.hip", "mw_engine_ray.hip"):
-        assert re.search(r"^SRCS = (?:.*\\\n)*.*\b" + re.escape(unit), make, re.M), unit
-    decl = open(os.path.join(CSRC, "mw_kernels.h")).read()
-    unit = open(os.path.join(CSRC, "mw_ray.hip")).read()
+    check_units_built("mw_ray.hip", "mw_engine_ray.hip")
     for k in ("mw_ray_lanes_kernel", "mw_ray_waves_kernel"):
-        assert re.search(r'extern "C" __global__ void ' + k + r"\(", decl), k
-        assert len(re.findall(r"__global__[^;{]*\b" + k + r"\(", unit)) == 1, k
-    # the new runtime file says why it does not wait for the side-stream refills
-    assert "does not wait for the Maze's" in " ".join(open(os.path.join(CSRC, "mw_engine_ray.hip")).read().replace("//", " ").split())
+        check_kernel(k, "mw_ray.hip")
+    check_does_not_wait("mw_engine_ray.hip")
 
 
 def test_library_exports_the_entry_point_and_refuses_a_null_engine():
     from miniworld_amd import engine
-    engine.build_library()
-    lib = engine.load_library()
-    assert hasattr(lib, "mw_ray_cast")
-    p = engine.MwRayParams(1.0, 0.0, 4, 0)
-    assert lib.mw_ray_cast(None, p, None, None, None, None, None, None, None, None) == -1
+    check_refuses_null_engine("mw_ray_cast", engine.MwRayParams(1.0, 0.0, 4, 0), None, None, None, None, None, None, None, None)
 
 
 def _policy(program, n, r, max_segs, max_ents):
-    out = subprocess.run([program, "--policy", str(n), str(r), str(max_segs), str(max_ents)], capture_output=True, text=True, check=True).stdout.split()
-    return dict(zip(("per_lane", "grid", "threads", "lds", "fits", "threshold"), map(int, out)))
+    return launch_of(program, n, r, max_segs, max_ents, names=("per_lane", "grid", "threads", "lds", "fits", "threshold"))
 
 
 def test_policy_chooses_the_form_from_the_ray_count(program):

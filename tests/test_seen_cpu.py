@@ -8,7 +8,6 @@ binding over a stub engine and the library call of one seen_update."""
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,66 +15,24 @@ import pytest
 import nav_reference as nav
 import seen_reference as ref
 from helpers import stub_engine
+from query_checks import (CSRC, ROOT, build, check_does_not_wait, check_kernel, check_refuses_null_engine, check_units_built, host_world, launch_of as _policy,
+                          run, walk as _walk, world_lines)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "miniworld_amd", "csrc")
 CELL = 0.25
 FOV = 2.0 * math.atan(math.tan(math.radians(60.0) / 2.0) * 80.0 / 60.0)        # the default camera's horizontal field of view
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("seen_map") / "seen_map")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", os.path.join(HERE, "hostcheck", "seen_map.cpp"), "-o", exe])
-    return exe
-
-
-def _host_world(cls_name, seed):
-    from miniworld_amd import envs
-    from miniworld_amd.scene import scene_from_env
-    env = getattr(envs, cls_name)(host_only=True)
-    env.reset(seed=seed)
-    sc = scene_from_env(env)
-    w = nav.world_of_scene(sc)
-    w["agent"] = (float(sc["agent_pos"][0]), float(sc["agent_pos"][2]), float(sc["agent_dir"]))
-    return w
-
-
-def _walk(w, rng, steps):
-    """poses (x, z, dir): from the agent's own, forward moves and turns of the env's sizes, kept inside the extent"""
-    ext = w["extent"]
-    x, z, d = w["agent"]
-    out = [(x, z, d)]
-    for _ in range(steps - 1):
-        a = rng.integers(0, 3)
-        if a == 0:
-            d += math.radians(15)
-        elif a == 1:
-            d -= math.radians(15)
-        else:
-            x = min(max(x + 0.45 * math.cos(d), ext[0] + 0.1), ext[1] - 0.1)
-            z = min(max(z - 0.45 * math.sin(d), ext[2] + 0.1), ext[3] - 0.1)
-        out.append((x, z, d))
-    return out
+    return build("seen_map", tmp_path_factory.mktemp("seen_map"))
 
 
 def _run(program, tmp_path, w, gx, gz, max_range, cos_half, flags, steps, fill=0, count=0, new=0, cell=CELL):
     """steps: (x, z, dir, carry, clear, mask) -> per step (covered, new, count, uint8[gz, gx])"""
-    lines = [f"{float(cell)!r} {gx} {gz}", f"{float(max_range)!r} {float(cos_half)!r} {flags}", f"{fill} {count} {new}",
-             f"{w['agent_radius']!r} {w['max_forward_step']!r}", " ".join(repr(float(v)) for v in w["extent"]), str(len(w["segs"]))]
-    lines += [" ".join(repr(float(v)) for v in s) for s in w["segs"]]
-    lines.append(str(len(w["kind"])))
-    for s in range(len(w["kind"])):
-        lines.append(f"{int(w['kind'][s])} " + " ".join(repr(float(v)) for v in w["pos"][s]) + f" {float(w['radius'][s])!r}")
+    lines = [f"{float(cell)!r} {gx} {gz}", f"{float(max_range)!r} {float(cos_half)!r} {flags}", f"{fill} {count} {new}"] + world_lines(w)
     lines.append(str(len(steps)))
     lines += [f"{float(x)!r} {float(z)!r} {float(d)!r} {int(carry)} {int(clear)} {int(mask)}" for x, z, d, carry, clear, mask in steps]
-    path = tmp_path / "world.txt"
-    path.write_text("\n".join(lines) + "\n")
-    r = subprocess.run([program, str(path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-300:], r.stderr[-2000:])
-    rows = [line.split() for line in r.stdout.split("\n") if line]
+    rows = [line.split() for line in run(program, tmp_path / "world.txt", lines)]
     assert len(rows) == 2 * len(steps)
     return [(int(rows[2 * k][0]), int(rows[2 * k][1]), int(rows[2 * k][2]), np.array(rows[2 * k + 1], np.uint8).reshape(gz, gx)) for k in range(len(steps))]
 
@@ -98,7 +55,7 @@ def test_walk_equals_the_restatement(program, tmp_path, cls_name, seeds, entitie
     rng = np.random.default_rng(3100)
     blocked_by_entity = 0
     for seed in seeds:
-        w = _host_world(cls_name, seed)
+        w = host_world(cls_name, seed)[2]
         gx, gz = ref.grid_shape(w["extent"], CELL)
         poses = _walk(w, rng, 12)
         # a clear in the middle, a masked-off step (with a clear that must not happen), a pose on a cell's centre (dist == 0)
@@ -129,7 +86,7 @@ def _both(program, tmp_path, w, gx, gz, max_range, cos_half, entities, steps, **
 
 def test_properties_hold_on_the_restatement_and_the_host_build(program, tmp_path):
     rng = np.random.default_rng(3101)
-    w = _host_world("FourRooms", 0)
+    w = host_world("FourRooms", 0)[2]
     gx, gz = ref.grid_shape(w["extent"], CELL)
     poses = _walk(w, rng, 10)
     plain = [(x, z, d, -1, 0, 1) for x, z, d in poses]
@@ -173,7 +130,7 @@ def test_properties_hold_on_the_restatement_and_the_host_build(program, tmp_path
 
 
 def test_a_grid_that_does_not_cover_the_extent_is_refused(program, tmp_path):
-    w = _host_world("Hallway", 0)
+    w = host_world("Hallway", 0)[2]
     gx, gz = ref.grid_shape(w["extent"], CELL)
     step = [w["agent"] + (-1, 0, 1)]
     got = _run(program, tmp_path, w, gx - 2, gz, 5.0, -1.0, 0, step, fill=1, count=9, new=9)
@@ -194,33 +151,19 @@ def test_header_declares_the_entry_point_and_the_build_has_the_units():
     assert proto in text
     assert re.search(r"#define MW_SEEN_ENTITIES 1\b", header) and engine.SEEN_ENTITIES == 1
     assert re.search(r"#define MW_ABI_VERSION 4\b", header)
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    for unit in ("mw_seen.hip", "mw_engine_seen.hip"):
-        assert re.search(r"^SRCS = (?:.*\\\n)*.*\b" + re.escape(unit), make, re.M), unit
-    decl = open(os.path.join(CSRC, "mw_kernels.h")).read()
-    unit = open(os.path.join(CSRC, "mw_seen.hip")).read()
-    assert re.search(r'extern "C" __global__ void mw_seen_kernel\(', decl)
-    assert len(re.findall(r"__global__[^;{]*\bmw_seen_kernel\(", unit)) == 1
+    check_units_built("mw_seen.hip", "mw_engine_seen.hip")
+    check_kernel("mw_seen_kernel", "mw_seen.hip")
     # the arithmetic is the shared one: the seen header defines no ray or grid formula of its own
     seen_h = open(os.path.join(CSRC, "mw_seen.h")).read()
     for shared in ("mwray::ray_of", "mwray::wall_of", "mwray::disc_of", "mwray::ray_wall", "mwray::ray_circle", "mwray::take", "mwnav::grid_of",
                    "mwnav::centre", "mwnav::beyond", "mwnav::covers", "mwnav::box_of"):
         assert shared in seen_h, shared
-    assert "does not wait for the Maze's" in " ".join(open(os.path.join(CSRC, "mw_engine_seen.hip")).read().replace("//", " ").split())
+    check_does_not_wait("mw_engine_seen.hip")
 
 
 def test_library_exports_the_entry_point_and_refuses_a_null_engine():
     from miniworld_amd import engine
-    engine.build_library()
-    lib = engine.load_library()
-    assert hasattr(lib, "mw_seen_update")
-    p = engine.MwNavParams(0.25, 0.0, 0.0, 4, 4, 0, 0)
-    assert lib.mw_seen_update(None, p, None, 0, None, None, None, None, None, None) == -1
-
-
-def _policy(program, n, max_segs, max_ents):
-    out = subprocess.run([program, "--policy", str(n), str(max_segs), str(max_ents)], capture_output=True, text=True, check=True).stdout.split()
-    return dict(zip(("grid", "threads", "lds", "fits"), map(int, out)))
+    check_refuses_null_engine("mw_seen_update", engine.MwNavParams(0.25, 0.0, 0.0, 4, 4, 0, 0), None, 0, None, None, None, None, None, None)
 
 
 def test_seen_launch_is_a_workgroup_per_env_and_refuses_what_lds_does_not_hold(program):
