@@ -1045,7 +1045,8 @@ int mw_kernel_time_ms(mw_engine *e, int32_t reset, double *raster_ms, double *se
  * which code its fixtures exercised: MW_PATH_QUAD the quad kernel (mw_rasterq.hip: small scenes, 8 or 4 samples),
  * MW_PATH_QUAD_MESH the same for every tile no mesh entity can touch + the mesh-aware tile kernel for the others,
  * MW_PATH_TILE the tile kernels (mw_raster.hip: big scenes, MW_K2Q=0), MW_PATH_GENERIC the generic-resolution kernels
- * (other sample counts, frames beyond 128 x 96 pixels (W H > 12 288: the tile kernels' 32-bit edge sums), frames off the 16 x 4 grid
+ * (other sample counts, frames 128 pixels wide or high and wider or higher (the tile and quad kernels' 24-bit edge coefficients), frames
+ * beyond 128 x 96 pixels (W H > 12 288: their 32-bit edge sums), frames off the 16 x 4 grid
  * other than the ragged tile kernels' (8 samples, even H, no meshes), MW_GENERIC_RASTER=1); -1 before the first frame.  Frames off
  * the grid that the tile kernels draw report MW_PATH_TILE. */
 /* The `info` dict of the envs' step() as device arrays, asynchronous on `stream` (either pointer may be NULL):

@@ -8,6 +8,7 @@
 // candidates instead of 8 samples x 1-4 pixels x 3 edges.
 #pragma once
 #include "mw_glmath.h"
+#include "mw_quad_bin.h"
 
 namespace mwcov {
 
@@ -16,16 +17,12 @@ namespace mwcov {
 constexpr uint32_t kColSample = 5u | (4u << 3) | (3u << 6) | (1u << 9) | (0u << 12) | (6u << 15) | (2u << 18) | (7u << 21);
 constexpr uint32_t kColY = 7u | (13u << 4) | (3u << 8) | (11u << 12) | (5u << 16) | (15u << 20) | (9u << 24) | (1u << 28);
 
-MW_HD int mul24i(int a, int b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __mul24(a, b);
-#else
-    return a * b;
-#endif
-}
+// the device's 24-bit multiply, modelled on the host (mw_quad_bin.h): tests/hostcheck/mwhost.cpp sees what the kernel computes.  The
+// operands here are dcdx, dcdy (at most 256 H, 256 W) and 24.8 sample coordinates (below 256 W, 256 H): 24 bits hold both for every
+// frame size the engine accepts — unlike the raster records' coefficients, which carry another factor of 256 (mw_edge_rec.h)
+MW_HD int mul24i(int a, int b) { return mw_qb_mul24(a, b); }
 
-// integer edges of a front-facing triangle in 32 bits (frames up to 128 x 96: mw_policy.h::tile_kernels_exact), the
+// integer edges of a front-facing triangle in 32 bits (frames up to 128 x 96: mw_policy.h::edge_sums_fit), the
 // snapped vertices' bounds and the depth plane: mw_glmath.h::setup_triangle_pos for a multisampled target.
 struct Edges {
     int dcdx[3], dcdy[3], c[3];

@@ -17,15 +17,28 @@
 
 namespace mwpolicy {
 
-// The tile / quad / mesh-scatter kernels keep edge values in 32 bits: |c_k| = |dcdx X - dcdy Y| <= 2 W H 2^16 has to stay below
-// 2^31, i.e. W H < 16384 — 128 x 96 passes, 128 x 128 does not (a wall across the whole frame lost its triangle there);
-// larger frames take the generic-resolution kernels (64-bit edge values).
-inline bool tile_kernels_exact(int W, int H) { return W <= 128 && H <= 128 && W * H <= 128 * 96; }
+// The tile / quad / mesh-scatter kernels evaluate an edge at a pixel as mul24(A_k, px) + mul24(B_k, gy) + C_k in 32 bits that wrap
+// (mw_edge_rec.h).  Two bounds, both pinned at their boundary by tests/hostcheck/edge_limits.cpp against 64-bit edge functions:
+//   edge_coeffs_fit   the multiply reads 24 signed bits of A_k = -256 dcdx_k and B_k = 256 dcdy_k.  Vertices are snapped inside
+//                     [0, W] x [0, H] of the FRAME (the viewport: the vertex range), so |B| <= 2^16 W and |A| <= 2^16 H: W and H have
+//                     to stay below 128 — at 128 an edge over the whole width (height) has B (A) = +2^23, which the multiply reads
+//                     as -2^23.  This is the bound that binds first: 128 x 48 and 48 x 128 already draw wrong frames without it.
+//   edge_sums_fit     the sum is compared as a signed 32-bit value.  The stated bound is the edge constant's, |c_k| = |dcdx X - dcdy Y| <=
+//                     2 W H 2^16 < 2^31, i.e. W H <= 128 x 96, taken on the raster GRID (the frame rounded up to whole tiles: the
+//                     padding pixels are evaluated too).  It is on the safe side: the sums wrap, so only the edge VALUE has to fit, and
+//                     on the grid |E| <= W H 2^16 or little more (twice a triangle's area in 24.8 units) — the model finds the exact
+//                     value inside 32 bits and, with exact multiplies, no wrong verdict up to 144 x 132.  The wall triangle that 128 x
+//                     128 once lost was the multiply's operand, not this sum.  The bound stays as stated all the same.
+// Larger frames take the generic-resolution kernels (64-bit edge values).
+inline bool edge_coeffs_fit(int W, int H) { return W < 128 && H < 128; }
+inline bool edge_sums_fit(int W, int H) { return W <= 128 && H <= 128 && W * H <= 128 * 96; }
+// ... of a frame that is its own grid
+inline bool tile_kernels_exact(int W, int H) { return edge_coeffs_fit(W, H) && edge_sums_fit(W, H); }
 
 // The frame is W x H, the size the caller asked for: the viewport, the projection and every output stride.  The raster grid is
 // the frame rounded up to whole 16 x 4 tiles, ceil16(W) x ceil4(H): tiles_x, tiles_y, n_tiles.  A frame that is not the grid
 // ("ragged": padding pixels right of column W - 1 or below row H - 1) takes, at 8 samples without mesh entities, with an even H
-// and a grid inside the tile kernels' edge bound, the ragged tile kernels (mw_raster.hip, FMT -2: padding masked, per-pixel stores); any
+// sides below 128 and a grid inside the edge sums' bound (above), the ragged tile kernels (mw_raster.hip, FMT -2: padding masked, per-pixel stores); any
 // other ragged frame the generic-resolution kernels, which mask the padding per pixel too.  The quad kernel and the fixed-layout
 // tile kernels take frames on the grid only ("Frame sizes").
 inline int tiles_across(int W) { return (W + MW_TILE_W - 1) / MW_TILE_W; }
@@ -86,7 +99,7 @@ inline int pick_waves_per_env(int n_tiles, int num_envs)
 // (lds_bytes: mw_rasterq_lds_bytes at 4 samples for msaa = 4, else 8, with depth) fits 64 KB
 inline bool k2q_ok(int msaa, int W, int H, int lds_bytes)
 {
-    return (msaa == 8 || msaa == 4) && frame_on_grid(W, H) && W <= 128 && H <= 128 && W * H <= 8192 && lds_bytes <= 64 * 1024;
+    return (msaa == 8 || msaa == 4) && frame_on_grid(W, H) && edge_coeffs_fit(W, H) && W * H <= 8192 && lds_bytes <= 64 * 1024;
 }
 
 // Which kernels draw a frame of the engine's size (mw_raster_path), and the forms of them the launches pick: the one statement
@@ -117,10 +130,10 @@ inline RasterPath raster_path(const RasterFacts &f, bool depth)
     const bool k2q = f.use_k2q && f.k2q_ok && !p.big && !(S == 4 && (f.meshes || f.generic_raster));
     // a ragged frame the ragged tile kernels draw (frame_on_grid).  The even H: the tile kernels' 2x2 quads (texture lod) pair image rows from
     // the top, GL pairs window rows from the bottom (mw_frag.h), and the two agree only then.  Odd heights take the generic-resolution kernels.
-    const bool ragged_tiles = !f.meshes && p.ragged && f.H % 2 == 0 && tile_kernels_exact(tiles_across(f.W) * MW_TILE_W, tiles_down(f.H) * MW_TILE_H);
+    const bool ragged_tiles = !f.meshes && p.ragged && f.H % 2 == 0 && edge_coeffs_fit(f.W, f.H) && edge_sums_fit(tiles_across(f.W) * MW_TILE_W, tiles_down(f.H) * MW_TILE_H);
     p.quad4 = k2q && S == 4;
     // FrameBuffer's fallback sample counts (opengl.py:229-231: a driver that clamps GL_MAX_SAMPLES gets 4 or 1
-    // samples), observations beyond 128 x 128 (the tile kernels' 24-bit edge arithmetic) and frames off the 16 x 4 grid:
+    // samples), observations 128 pixels wide or high and beyond (the tile kernels' 24-bit edge coefficients) and frames off the 16 x 4 grid:
     // the generic-resolution kernels, 64-bit edge values, exact packed-key resolution, every output layout, the whole
     // batch in one grid (blockIdx.y = env)
     const bool generic = S != 8 || (!tile_path_ok(f.W, f.H) && !ragged_tiles);

@@ -311,8 +311,8 @@ __device__ inline void classify_prim(const float4 *cr, int pxlo, int pxhi, int g
     touch = true; full = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int emax = ea[k] * (ea[k] > 0 ? pxhi : pxlo) + eb[k] * (eb[k] > 0 ? gyhi : gylo) + ec[k];
-        const int emin = ea[k] * (ea[k] > 0 ? pxlo : pxhi) + eb[k] * (eb[k] > 0 ? gylo : gyhi) + ec[k];
+        int emax, emin;
+        mwrec::edge_extremes(ea[k], eb[k], ec[k], pxlo, pxhi, gylo, gyhi, emax, emin);
         touch &= emax > tmn[k];
         const bool inside = emin > tmx[k];
         full &= inside;
@@ -495,7 +495,7 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
                         if (PRE == 1 && !((cx.pre_edges >> (16 * k + (bit & 15))) & 1ull)) continue;   // known from the classification
-                        const int E = __mul24(rr[k], px) + __mul24(rr[3 + k], gy) + rr[6 + k];
+                        const int E = mwrec::edge_at(rr[k], rr[3 + k], rr[6 + k], px, gy);
                         if (__all(E > rr[13 + k])) continue;        // tile strictly inside edge k
 #pragma unroll
                         for (int s = 0; s < 8; ++s) in_m[s] &= __ballot(E > rr[16 + k * 16 + s]);
@@ -586,7 +586,7 @@ __device__ inline void raster_tile_fmt(const TileCtx &cx, int tx, int ty, const 
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     if (PRE == 1 && !((cx.pre_edges >> (16 * k + (bit & 15))) & 1ull)) continue;
-                    const int E = __mul24(rr[k], px) + __mul24(rr[3 + k], gy) + rr[6 + k];
+                    const int E = mwrec::edge_at(rr[k], rr[3 + k], rr[6 + k], px, gy);
                     if (__all(E > rr[13 + k])) continue;
 #pragma unroll
                     for (int s = 0; s < 8; ++s) in_m[s] &= __ballot(E > rr[16 + k * 16 + s]);

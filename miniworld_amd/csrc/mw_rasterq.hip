@@ -127,7 +127,7 @@ __device__ inline void classify_at(const float4 &a0, const float4 &a1, const flo
     touch = true; full = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int E = __mul24(ea[k], pxlo) + __mul24(eb[k], gylo) + ec[k];
+        const int E = mwrec::edge_at(ea[k], eb[k], ec[k], pxlo, gylo);
         touch &= E > T[k];
         full &= E > F[k];
     }
@@ -160,7 +160,7 @@ __device__ inline void cover_lane(const float4 *rec, int px, int gy, uint64_t va
     for (int s = 0; s < S; ++s) in_m[s] = valid_m;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int E = __mul24(A[k], px) + __mul24(B[k], gy) + C[k];
+        const int E = mwrec::edge_at(A[k], B[k], C[k], px, gy);
         if (wave_all(E > TM[k])) continue;                 // every lane's pixel strictly inside its triangle's edge k
         int thr[S];
 #pragma unroll
@@ -704,11 +704,8 @@ __device__ inline void rasterq_body(
             int c[12];
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                const int ap = max(A[k], 0), an = min(A[k], 0), bp = max(B[k], 0), bn = min(B[k], 0);
-                c[k] = tmn[k] - ap * (MW_TILE_W - 1) - bp * (MW_TILE_H - 1);
-                c[3 + k] = tmx[k] - an * (MW_TILE_W - 1) - bn * (MW_TILE_H - 1);
-                c[6 + k] = tmn[k] - ap - bp;
-                c[9 + k] = tmx[k] - an - bn;
+                mwrec::rect_thresholds(A[k], B[k], tmn[k], tmx[k], MW_TILE_W, MW_TILE_H, c[k], c[3 + k]);
+                mwrec::rect_thresholds(A[k], B[k], tmn[k], tmx[k], 2, 2, c[6 + k], c[9 + k]);
             }
             const int j = q - R::CT;
             v = make_float4(__int_as_float(j == 0 ? c[0] : (j == 1 ? c[4] : c[8])), __int_as_float(j == 0 ? c[1] : (j == 1 ? c[5] : c[9])),

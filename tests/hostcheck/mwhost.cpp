@@ -257,6 +257,23 @@ extern "C" int mwhost_list_length(const mwo_scene *sc)
     return (int)tris.size();
 }
 
+// the signed extremes of the edge slopes over the scene's display list, out = {min dcdx, max dcdx, min dcdy, max dcdy} (24.8 units:
+// dcdy = +256 W is an edge across the whole frame, dcdx = -256 H one over its whole height — the raster records' coefficients B = 256
+// dcdy and A = -256 dcdx are then +2^23 at W = 128, H = 128: mw_edge_rec.h).  Returns the list length (0: out untouched).
+extern "C" int mwhost_edge_extremes(const mwo_scene *sc, int32_t *out)
+{
+    std::vector<Tri> tris;
+    geometry(sc, sc->nsamples > 1, tris);
+    if (tris.empty()) return 0;
+    out[0] = out[2] = INT32_MAX; out[1] = out[3] = INT32_MIN;
+    for (const Tri &tr : tris)
+        for (int k = 0; k < 3; ++k) {
+            out[0] = std::min(out[0], tr.ts.dcdx[k]); out[1] = std::max(out[1], tr.ts.dcdx[k]);
+            out[2] = std::min(out[2], tr.ts.dcdy[k]); out[3] = std::max(out[3], tr.ts.dcdy[k]);
+        }
+    return (int)tris.size();
+}
+
 // The quad kernel's bookkeeping counts, per rectangle of the frame, the list's triangles that TOUCH it and those that cover
 // it in FULL — by edge functions alone, each edge on its own (mw_rasterq.hip, classify_at).  The same two counts from the
 // definition, with nothing of the kernel's thresholds in it: a triangle touches a rectangle iff every edge is positive at

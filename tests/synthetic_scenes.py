@@ -180,6 +180,36 @@ def overlap_world(base, tex=None):
     return _world(base, tex, items)
 
 
+FILLING_PARTS = ("cover", "upper", "lower", "right", "left", "floor")
+
+
+def frame_filling_world(base, aspect=80 / 60, tex=None):
+    """Stations whose polygons reach past the frustum, so that clipping leaves their vertices ON the frame's borders and corners: the
+    edges with the largest slopes a frame of `aspect` = W / H can hold (a full-width edge has dcdy = +-256 W, a full-height one dcdx =
+    +-256 H, the diagonals both; miniworld_amd/csrc/mw_edge_rec.h).
+      cover   a quad three times the frustum at 1 m, its sides in the frame's proportion: clipped, its two triangles meet along the
+              frame's diagonal and their other edges are the frame's borders, each in one direction
+      upper, lower   the halves of the same quad above and below the diagonal from bottom left to top right, one alone per station
+      right, left    the halves beside the other diagonal: every corner-to-corner edge is drawn in both windings
+      floor   a wide horizontal quad below the eye that the bottom, left and right planes clip, and its mirror image above as ceiling
+    The room is part of the world, no station sees it."""
+    ty = np.tan(np.radians(float(base["cam_fov_y"])) / 2.0)
+    tx = ty * aspect
+
+    def corners(e, f, r):
+        return quad(e + f * 1.0, r, UP, 3.0 * tx, 3.0 * ty)          # bottom left, bottom right, top right, top left
+
+    def level(e, f, r):
+        # 0.2 .. 3.2 m ahead, 8 m to each side (past the side planes of a 128 x 48 frame there, 84 degrees off a neighbour's axis), 0.5 m below / above the eye
+        return [quad(e + f * 1.7 - UP * 0.5, r, f, 8.0, 1.5), quad(e + f * 1.7 + UP * 0.5, r, -f, 8.0, 1.5)]
+    halves = {"upper": (0, 2, 3), "lower": (0, 1, 2), "right": (1, 2, 3), "left": (0, 1, 3)}
+    items = [("cover", _station(0), lambda e, f, r: [corners(e, f, r)])]
+    items += [(name, _station(1 + k), lambda e, f, r, ids=ids: [corners(e, f, r)[list(ids)]]) for k, (name, ids) in enumerate(halves.items())]
+    items.append(("floor", _station(1 + len(halves)), level))
+    assert tuple(name for name, _, _ in items) == FILLING_PARTS
+    return _world(base, tex, items)
+
+
 def only(world, part):
     """the world's polygons of one part alone (a slice of them)"""
     sc = dict(world)

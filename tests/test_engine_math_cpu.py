@@ -23,7 +23,7 @@ def build_host():
     """tests/hostcheck/libmwhost.so, (re)built when a source is newer; also used by the -m gpu selftests."""
     deps = [SRC, os.path.join(ROOT, "oracle", "mwo_math.c")] + [
         os.path.join(ROOT, "miniworld_amd", "csrc", h)
-        for h in ("mw_glmath.h", "mw_frag.h", "mw_cover.h", "mw_math.h", "mw_selftest.h", "mw_hd.h", "mw_assets.h", "mw_asset_types.h")]
+        for h in ("mw_glmath.h", "mw_frag.h", "mw_cover.h", "mw_quad_bin.h", "mw_math.h", "mw_selftest.h", "mw_hd.h", "mw_assets.h", "mw_asset_types.h")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         fma = ["-mfma"] if " fma " in open("/proc/cpuinfo").read() else []
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", *fma, "-pthread", "-shared", SRC,

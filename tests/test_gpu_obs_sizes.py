@@ -21,7 +21,8 @@ def expected_path(w, h, msaa, meshes):
     """DESIGN.md's path table for a frame off the 16 x 4 grid (MW_K2Q and MW_GENERIC_RASTER do not change it)."""
     from miniworld_amd import engine as E
     gw, gh = -(-w // 16) * 16, -(-h // 4) * 4
-    exact = gw <= 128 and gh <= 128 and gw * gh <= 128 * 96
+    # (the frame's own sides below 128: the 24-bit coefficients; the grid's area: the 32-bit sums — mw_policy.h, edge_coeffs_fit / edge_sums_fit)
+    exact = w < 128 and h < 128 and gw <= 128 and gh <= 128 and gw * gh <= 128 * 96
     return E.PATH_TILE if (msaa == 8 and not meshes and exact and h % 2 == 0) else E.PATH_GENERIC
 
 

@@ -5,10 +5,11 @@ the same size and sample count: RGB and the depth map bit for bit, mw_check clea
 
 Shapes: one tile column (W = 16), one tile row (H = 4), a single tile, 32 x 8, 80 x 60, seven tile columns (112 x 48) and the largest
 frame of the quad kernel, 96 x 64 — its LDS plan (q_plan) must fit 64 KB beside W H <= 8192, and at 128 x 64 it does not (80 KB with
-a depth channel): that size is drawn and compared all the same, through the kernels the policy gives it.  (128 x 48 fits the plan,
-but at W = 128 an edge across the whole frame has the coefficient 2^23, one past the signed 24 bits of the kernels' multiplies —
-FourRooms' frame 150 has one; the flat loops and the stepped ones see the same wrong value there, mw_quad_bin.h — so no 128-wide frame
-is asked of the quad kernel here.)  8 and 4 samples, with and without a depth output (40 / 48 staged records).  Scenes: fixture frames (Hallway, OneRoom, FourRooms; PickupObjects: the mesh part mode) and
+a depth channel).  No frame 128 pixels wide or high is the quad kernel's, or the tile kernels': an edge across the whole frame has
+the coefficient 2^23 there, one past the signed 24 bits of the kernels' multiplies (miniworld_amd/csrc/mw_edge_rec.h,
+tests/test_edge_limits_cpu.py; FourRooms' frame 150 at 128 x 48 holds one), so the launch policy gives 128 x 64, 128 x 48 and their like to
+the generic-resolution kernels: 128 x 64 is drawn and compared here all the same, the others with scenes that sit on that limit in
+tests/test_gpu_edge_limits.py.  8 and 4 samples, with and without a depth output (40 / 48 staged records).  Scenes: fixture frames (Hallway, OneRoom, FourRooms; PickupObjects: the mesh part mode) and
 tests/synthetic_scenes.py — a list of one triangle, lists at capacity, slats and slivers (more than 16 triangles on a tile: the
 fallback class; many partial events per tile), a quad whose edges lie exactly on a tile's borders —, the experiment flags that force
 the exact, fallback and over-capacity paths, and the list form of the kernel (final observations)."""
@@ -52,7 +53,13 @@ def one_triangle_world():
 
 @functools.lru_cache(maxsize=None)
 def batch(name):
-    """(world, scenes, meshes for the oracle) — at most 8 envs"""
+    """(world, scenes, meshes for the oracle) — at most 8 envs.  "filling/WxH": synthetic_scenes.frame_filling_world for that frame's
+    proportion, every part"""
+    if name.startswith("filling/"):
+        W, H = map(int, name[len("filling/"):].split("x"))
+        base = cpu.hallway_frame()
+        world, poses, parts = syn.frame_filling_world(base, aspect=W / H, tex=cpu.wall_texture(base))
+        return world, [syn.posed(world, poses[part]) for part in syn.FILLING_PARTS], None
     if name in ("crowded", "overlaps"):
         world, scenes = cpu.shape_batch(name)
         return world, list(scenes.values())[:8], None
@@ -68,6 +75,12 @@ def batch(name):
 
 
 SYNTHETIC = ("crowded", "overlaps", "only", "border")
+
+
+def synthetic(name):
+    return name in SYNTHETIC or name.startswith("filling/")
+
+
 MAX_VISIBLE = 64                # of the synthetic worlds' engines (at most 64 polygons): a small scene, no visiting order
 
 
@@ -76,7 +89,7 @@ def sized_batch(name, msaa, width, height):
     """the batch's scenes whose display list the engine holds at this size (a synthetic world seen through a frame of another
     shape can list more than MAX_VISIBLE triangles: by the host's own count, not by anything the kernels give)"""
     world, scenes, meshes = batch(name)
-    if name in SYNTHETIC:
+    if synthetic(name):
         scenes = [sc for sc in scenes if cpu.list_length(cpu.host_library(), sc, msaa, width, height) <= MAX_VISIBLE]
     assert scenes
     return world, scenes, meshes
@@ -95,7 +108,7 @@ def draw_and_compare(name, width, height, msaa, with_depth, want_path):
     from miniworld_amd import engine as E
     world, scenes, _ = sized_batch(name, msaa, width, height)
     assert len(scenes) <= 8
-    eng = helpers.make_engine_for_scene(world, len(scenes), msaa=msaa, width=width, height=height, max_visible=MAX_VISIBLE if name in SYNTHETIC else None)
+    eng = helpers.make_engine_for_scene(world, len(scenes), msaa=msaa, width=width, height=height, max_visible=MAX_VISIBLE if synthetic(name) else None)
     eng.set_state(helpers.scene_state_arrays(scenes))
     rgb = torch.zeros((len(scenes), height, width, 3), dtype=torch.uint8, device="cuda")
     depth = torch.zeros((len(scenes), height, width, 1), dtype=torch.float32, device="cuda") if with_depth else None
@@ -128,11 +141,12 @@ def test_frames_of_every_shape_equal_the_oracle(size, msaa, with_depth):
 @pytest.mark.parametrize("with_depth", [True, False])
 @pytest.mark.parametrize("msaa", [8, 4])
 def test_the_frame_past_the_lds_plan_takes_other_kernels(msaa, with_depth):
-    """128 x 64 is W H = 8192, but the workgroup's plan needs 80 KB of LDS (66 KB without depth; the engine asks with): mw_create
-    gives the frame to the tile kernels (8 samples) or the generic-resolution kernels (4) — the same frames"""
+    """128 x 64 is W H = 8192, but the workgroup's plan needs 80 KB of LDS (66 KB without depth; the engine asks with), and a frame 128
+    pixels wide can hold an edge coefficient past the tile kernels' 24-bit multiplies too: mw_create gives the frame to the
+    generic-resolution kernels at either sample count — the same frames"""
     W, H = PAST_THE_LDS_PLAN
     for name in ("hallway", "crowded"):
-        draw_and_compare(name, W, H, msaa, with_depth, "PATH_TILE" if msaa == 8 else "PATH_GENERIC")
+        draw_and_compare(name, W, H, msaa, with_depth, "PATH_GENERIC")
 
 
 @pytest.mark.parametrize("with_depth", [True, False])

@@ -158,9 +158,11 @@ def test_display_list_of_one_triangle(msaa):
 @pytest.mark.parametrize("size", [(16, 12), (16, 60), (32, 4), (128, 128)])
 @pytest.mark.parametrize("msaa", [8, 4])
 def test_observation_sizes_at_the_edges_of_the_tile_kernels(size, msaa):
-    """mw_create accepts any multiple of the 16 x 4 tile; up to 128 x 96 pixels the tile / quad kernels draw it: one tile column
-    (16 pixels wide: the tile index arithmetic divides by tiles_x = 1), one tile row; 128 x 128 is past their 32-bit edge sums
-    (|c| <= 2 W H 2^16: a wall across the whole frame lost a triangle there) and takes the generic-resolution kernels."""
+    """mw_create accepts any multiple of the 16 x 4 tile; frames with both sides below 128 pixels and at most 128 x 96 of them are
+    drawn by the tile / quad kernels: one tile column (16 pixels wide: the tile index arithmetic divides by tiles_x = 1), one tile
+    row; 128 x 128 is past their 24-bit edge coefficients (|B| <= 2^16 W: a wall across the whole frame lost a triangle there —
+    tests/test_edge_limits_cpu.py shows that it is the multiply's operand, not the 32-bit sum, that gives way first) and takes the
+    generic-resolution kernels, like every frame 128 wide or high (tests/test_gpu_edge_limits.py)."""
     import torch
     import pyoracle
     W, H = size
