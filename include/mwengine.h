@@ -709,9 +709,12 @@ int mw_snapshot_load_frames_where(mw_engine *e, const uint8_t *d_mask, const int
 #define MW_NAV_BLOCKED 0xFFFF
 #define MW_NAV_UNREACHED 0xFFFE
 #define MW_NAV_MAX_CELLS 32768  /* gx * gz: the grid lives in 64 KiB of LDS */
+#define MW_NAV_GRID 4           /* flags: the field is mw_nav_build_grid's; mw_nav_query's waypoint at cost 0 is the cell's own centre */
+#define MW_NAV_MAX_INFLATE 16   /* mw_nav_build_grid: the largest inflation radius in cells */
 typedef struct mw_nav_params {
     double cell;            /* side of a cell, > 0 */
-    double margin;          /* added to the agent's radius, >= 0 */
+    double margin;          /* added to the agent's radius, >= 0.  For mw_nav_build_grid the WHOLE inflation radius in metres: the agent's
+                             * radius is not added there (the caller's grid may already hold it) */
     double reach;           /* point targets only: > 0 */
     int32_t gx, gz;         /* cells along x and z, >= 1, gx * gz <= MW_NAV_MAX_CELLS */
     int32_t flags;          /* MW_NAV_* */
@@ -732,11 +735,44 @@ int mw_nav_build(mw_engine *e, const mw_nav_params *params, const uint8_t *d_mas
  *   d_next[i]      int32, j * gx + i of the admissible neighbour of strictly lower cost with the lowest cost — ties go to the first in
  *                  the order (dj, di) = (-1,0), (1,0), (0,-1), (0,1), (-1,-1), (-1,1), (1,-1), (1,1) —, the cell itself at cost 0
  *   d_waypoint[i]  double[2], that cell's centre x, z; at cost 0 the target's x, z (d_target as for the build that made the field)
- * Any of the three outputs may be NULL.  The same argument checks as mw_nav_build. */
+ * Any of the three outputs may be NULL.  The same argument checks as mw_nav_build.
+ * With MW_NAV_GRID in params->flags (a field of mw_nav_build_grid) the waypoint at cost 0 is the centre of the cell itself, and neither
+ * d_target nor target_slot is read; everything else is as above.  The descent ends on such a field too: with extra costs a cell's cost
+ * still exceeds that of the neighbour it came through.  Without the flag the answers are what they were, bit for bit. */
 int mw_nav_query(mw_engine *e, const mw_nav_params *params, const double *d_target, const uint16_t *d_field, const double *d_pos,
                  int32_t *d_cost, int32_t *d_next, double *d_waypoint, void *stream);
-/* measurements: d_passes, int32[N] on the device, gets the relaxation's count of rounds of every env each later mw_nav_build builds;
- * NULL stops that */
+/* mw_nav_build_grid: the same field over the caller's own maps — a planner for a map an agent built from what it perceived (mw_depth_project's
+ * obstacle plane, a seen map, anything rasterised by the caller), with several sources at once (the field is the cost to the nearest)
+ * and a cost per cell.  It follows mw_nav_build where nothing else is said: one kernel, one workgroup per env, asynchronous on `stream`,
+ * no host value read, nothing in the engine changes, rows of envs with d_mask[i] == 0 are not touched.  It reads only the caller's
+ * tensors, and — with d_target alone — the env's extent for min_x, min_z.  Every grid is uint8[N][gz][gx] on the device, row-major like
+ * the field, gx * gz bytes per env with no padding.  params: cell, gx, gz as before; reach for d_target; flags: MW_NAV_JACOBI is
+ * honoured, MW_NAV_GRID accepted and ignored, MW_NAV_ENTITIES refused (this call reads no entities); target_slot is not read; margin
+ * is the whole inflation radius in metres — the agent's radius is NOT added.
+ *   BLOCKED   cell c is blocked when d_blocked[c] != 0 (a raw obstacle cell), and when some raw obstacle cell o at offset
+ *             (dj, di) != (0, 0) from c has sqrt((double)(di*di + dj*dj)) * cell < margin: float64, in that order, strict, no
+ *             contraction.  margin == 0 blocks the raw cells only.  The offsets run over |di|, |dj| <= R, R the smallest integer with
+ *             R * cell >= margin.  Cells outside the grid hold no obstacle.  Nothing is blocked on account of the env's extent:
+ *             the grid is the caller's, and mw_nav_build's refusal of a grid that does not cover the extent does not apply.
+ *   SOURCES   an unblocked cell with d_sources[c] != 0, and — with d_target — the unblocked cells whose centre is closer than
+ *             params->reach to row i of d_target (double[N][3], y not read), centres on the env's own min_x, min_z exactly as for
+ *             mw_nav_build.  Either or both may be given, both give the union.  An env without any source: every unblocked cell
+ *             0xFFFE, no error.
+ *   COSTS     a source is 0, whatever d_extra says.  Every other unblocked cell c costs d_extra[c] (NULL: 0) plus the minimum over its
+ *             admissible neighbours d of cost(d) + 5 (straight) or + 7 (diagonal, both cells the move passes between unblocked).
+ *             The fixed point is unique; 0xFFFF and 0xFFFE mean what they mean above.
+ * An env one of whose costs would reach 0xFFFE gets a row of 0xFFFF throughout and sets the status bit mw_nav_build sets: the next
+ * mw_check reports MW_E_INVALID, once.  MW_E_INVALID before anything is launched: a null engine, params, d_blocked or d_field; both
+ * d_sources and d_target null; cell <= 0, gx or gz < 1, more than MW_NAV_MAX_CELLS cells; margin < 0 or not finite, or R above
+ * MW_NAV_MAX_INFLATE; MW_NAV_ENTITIES in flags; reach <= 0 with d_target.  With d_extra the kernel holds a byte per cell more in LDS
+ * (at most 64 + 32 KiB). */
+int mw_nav_build_grid(mw_engine *e, const mw_nav_params *params, const uint8_t *d_mask,
+                      const uint8_t *d_blocked /* uint8[N][gz][gx]: != 0 a raw obstacle cell */,
+                      const uint8_t *d_sources /* uint8[N][gz][gx] or NULL: != 0 a source cell */,
+                      const double *d_target /* double[N][3] or NULL: point sources with params->reach */,
+                      const uint8_t *d_extra /* uint8[N][gz][gx] or NULL: the extra cost of a cell */, uint16_t *d_field, void *stream);
+/* measurements: d_passes, int32[N] on the device, gets the relaxation's count of rounds of every env each later mw_nav_build or
+ * mw_nav_build_grid builds; NULL stops that */
 int mw_debug_set_nav_passes(mw_engine *e, int32_t *d_passes);
 
 /* ---- ray casts --------------------------------------------------------------- */

@@ -8,6 +8,7 @@
 #include "mw_snapframes.h"
 #include "mw_state_view.h"
 #include "mw_nav.h"
+#include "mw_nav_grid.h"
 #include "mw_ray.h"
 #include "mw_seen.h"
 #include "mw_ego.h"
@@ -268,6 +269,12 @@ extern "C" __global__ void mw_nav_build_kernel(MwNavArgs a, mw_nav_params p, con
 extern "C" __global__ void mw_nav_query_kernel(MwNavArgs a, mw_nav_params p, const double *__restrict__ d_target, const uint16_t *__restrict__ field,
                                                const double *__restrict__ pos, int32_t *__restrict__ cost, int32_t *__restrict__ next,
                                                double *__restrict__ waypoint);
+// grid navigation fields (mw_nav_grid.hip; the phases: mw_nav_grid.h): the build over the caller's own rows — blocked, and sources,
+// d_target (at least one of the two) and extra, each uint8[N][gz][gx] or null.  R: mwnav::inflate_radius of the parameters.  Grid,
+// lanes, mask and passes as for the build above; mwpolicy::nav_grid_launch gives the dynamic LDS.
+extern "C" __global__ void mw_nav_grid_kernel(MwNavArgs a, mw_nav_params p, int R, const uint8_t *__restrict__ mask, const uint8_t *__restrict__ blocked,
+                                              const uint8_t *__restrict__ sources, const double *__restrict__ d_target, const uint8_t *__restrict__ extra,
+                                              uint16_t *__restrict__ field, int32_t *__restrict__ passes);
 
 // ray casts (mw_ray.hip; the arithmetic, MwRayArgs and the launch constants: mw_ray.h; the choice of form: mwpolicy::ray_launch).  The
 // parameters are the caller's mw_ray_params by value; origin null = the agents, exactly one of dir / offsets (the fan) non-null; hit

@@ -65,7 +65,7 @@ extern "C" __global__ __launch_bounds__(MW_NAV_THREADS) __attribute__((amdgpu_wa
     }
 }
 
-// mw_nav_query: a lane per env; reads the field, the extent, the target and the position, writes the three outputs that are asked for
+// mw_nav_query: a lane per env; reads the field, the extent, the target (not with MW_NAV_GRID) and the position, writes the three outputs that are asked for
 extern "C" __global__ __launch_bounds__(MW_NAV_QUERY_THREADS) void mw_nav_query_kernel(MwNavArgs a, mw_nav_params p, const double *__restrict__ d_target,
                                                                                        const uint16_t *__restrict__ field, const double *__restrict__ pos,
                                                                                        int32_t *__restrict__ cost, int32_t *__restrict__ next,
@@ -75,7 +75,9 @@ extern "C" __global__ __launch_bounds__(MW_NAV_QUERY_THREADS) void mw_nav_query_
     if (env >= (size_t)a.N) return;
     const mwnav::Grid g = mwnav::grid_of(a, p, env);
     const double x = pos ? pos[env * 3] : a.ax[env], z = pos ? pos[env * 3 + 2] : a.az[env];
-    const mwnav::Answer r = mwnav::query(g, field + env * (size_t)(g.gx * g.gz), mwnav::target_of(a, p, d_target, env), x, z);
+    const uint16_t *f = field + env * (size_t)(g.gx * g.gz);
+    // (a grid field, mw_nav_build_grid's, has no target to read: at cost 0 the cell's own centre)
+    const mwnav::Answer r = (p.flags & MW_NAV_GRID) ? mwnav::query_grid(g, f, x, z) : mwnav::query(g, f, mwnav::target_of(a, p, d_target, env), x, z);
     if (cost) cost[env] = r.cost;
     if (next) next[env] = r.next;
     if (waypoint) { waypoint[env * 2] = r.wx; waypoint[env * 2 + 1] = r.wz; }

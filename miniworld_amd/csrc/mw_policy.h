@@ -10,6 +10,7 @@
 #include "mw_seen.h"            // MW_SEEN_THREADS, MW_SEEN_TAIL_BYTES
 #include "mw_ego.h"             // MW_EGO_THREADS, mwego::staged_bytes
 #include "mw_depth.h"           // MW_DEPTH_THREADS, MW_DEPTH_CELL_BYTES, MW_DEPTH_MAX_CELLS
+#include "mw_nav_grid.h"        // MW_NAV_GRID_THREADS, mwnav::grid_field_bytes, mwnav::grid_extra_bytes
 #include "mw_label.h"           // MW_LABEL_THREADS, MW_LABEL_CHUNK, MW_LABEL_MAX_POLYS, MW_LABEL_MAX_ENTS, mwlabel::plan_bytes
 #include "mw_shape.h"
 #include "mw_snapframes.h"      // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
@@ -376,6 +377,16 @@ inline Launch depth_launch(int N, long long cells)
     const long long least = 2 * (MW_DEPTH_THREADS / 64);
     const size_t lds = ((size_t)(cells > least ? cells : least) * MW_DEPTH_CELL_BYTES + 15) / 16 * 16;
     return {(unsigned long long)N, MW_DEPTH_THREADS, lds, lds <= 64 * 1024};
+}
+
+// Grid navigation fields (mw_nav_build_grid; kernel: mw_nav_grid.hip): a workgroup of MW_NAV_GRID_THREADS lanes per env.  Its LDS is the
+// uint16 cost grid, rounded up to 16 — mw_nav_build's —, and with extra costs a byte per cell behind it, rounded up to 16: at most
+// 64 + 32 KiB at MW_NAV_MAX_CELLS, which one workgroup may hold (a CU has 160 KiB).  fits: no more cells than that, and a positive count.
+inline Launch nav_grid_launch(int N, long long cells, bool weighted)
+{
+    const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS;
+    const size_t lds = fits ? mwnav::grid_field_bytes(cells) + mwnav::grid_extra_bytes(cells, weighted) : 0;
+    return {(unsigned long long)N, MW_NAV_GRID_THREADS, lds, fits};
 }
 
 // Label frames (mw_label_frame; kernel: mw_label.hip): a workgroup of MW_LABEL_THREADS lanes per env.  Its LDS (mwlabel::plan_bytes)

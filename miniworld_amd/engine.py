@@ -109,9 +109,10 @@ class MwStateView(C.Structure):
         "ent_kind", "ent_mesh", "ent_static", "ent_pos", "ent_dir", "ent_geom", "extent")]
 
 
-NAV_ENTITIES, NAV_JACOBI = 1, 2         # MW_NAV_* flags
+NAV_ENTITIES, NAV_JACOBI, NAV_GRID = 1, 2, 4     # MW_NAV_* flags
 NAV_BLOCKED, NAV_UNREACHED = 0xFFFF, 0xFFFE
 NAV_MAX_CELLS = 32768                   # MW_NAV_MAX_CELLS
+NAV_MAX_INFLATE = 16                    # MW_NAV_MAX_INFLATE: mw_nav_build_grid's largest inflation radius in cells
 
 
 class MwNavParams(C.Structure):
@@ -236,6 +237,7 @@ SIGNATURES = {
     "mw_snapshot_load_where": _sig(vp, vp, vp, vp, i32, i32, vp),
     "mw_snapshot_load_frames_where": _sig(vp, vp, vp, vp, i32, i32, i32, vp, vp, vp),
     "mw_nav_build": _sig(vp, P(MwNavParams), vp, vp, vp, vp),
+    "mw_nav_build_grid": _sig(vp, P(MwNavParams), vp, vp, vp, vp, vp, vp, vp),
     "mw_nav_query": _sig(vp, P(MwNavParams), vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_nav_passes": _sig(vp, vp),
     "mw_ray_cast": _sig(vp, P(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp),
@@ -515,6 +517,23 @@ class Engine:
         mask = self._mask_tensor(mask, optional=True)
         self._check(self.lib.mw_nav_build(self.h, C.byref(params), _ptr(mask), _ptr(target), _ptr(field), _stream_ptr(self.device)), "mw_nav_build")
 
+    def nav_build_grid(self, params: MwNavParams, field, blocked, sources=None, target=None, extra=None, mask=None):
+        """mw_nav_build_grid: rows of `field` (uint16[N, gz, gx], device) for the envs under `mask` := the shortest-path cost over the
+        caller's own grids, each uint8[N, gz, gx] on the device: `blocked` (!= 0 a raw obstacle cell, inflated by params.margin metres),
+        `sources` (!= 0 a source cell) and / or `target` (float64[N, 3] with params.reach), `extra` (a cost per cell; None = zeros).
+        One kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the
+        library is called."""
+        import torch
+        self._nav_tensors(params, field, target)
+        cells = self.N * params.gx * params.gz
+        for name, t in (("blocked", blocked), ("sources", sources), ("extra", extra)):
+            self._dev_tensor(t, name, torch.uint8, cells)
+        if blocked is None:
+            raise EngineError("blocked: None")
+        mask = self._mask_tensor(mask, optional=True)
+        self._check(self.lib.mw_nav_build_grid(self.h, C.byref(params), _ptr(mask), _ptr(blocked), _ptr(sources), _ptr(target), _ptr(extra), _ptr(field),
+                                               _stream_ptr(self.device)), "mw_nav_build_grid")
+
     def nav_query(self, params: MwNavParams, field, target=None, pos=None, cost=None, next=None, waypoint=None):
         """mw_nav_query: for the agents (pos None) or the rows of `pos` (float64[N, 3], device): cost int32[N], next int32[N] and
         waypoint float64[N, 2], whichever are given.  `target` as for the nav_build that made the field."""
@@ -528,7 +547,7 @@ class Engine:
                                           _stream_ptr(self.device)), "mw_nav_query")
 
     def debug_set_nav_passes(self, passes):
-        """Measurements: int32[N] on the device that every later nav_build fills with its relaxation's round count per env; None stops."""
+        """Measurements: int32[N] on the device that every later nav_build or nav_build_grid fills with its relaxation's round count per env; None stops."""
         import torch
         self._dev_tensor(passes, "passes", torch.int32, self.N)
         self._nav_passes = passes       # (kept alive while the engine holds its pointer)

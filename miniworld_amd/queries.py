@@ -16,7 +16,8 @@ class NavField:
     """A navigation field (MiniWorldVecEnv.nav_field): `field`, the uint16[N, gz, gx] device tensor of shortest-path costs — 0xFFFF a
     blocked cell, 0xFFFE one no path reaches, a move costs 5 straight and 7 diagonally —, the grid (`cell` metres per cell, gx x gz
     cells from the env's own min_x, min_z), and what it leads to: `target`, an entity slot or a float64[N, 3] device tensor.  The
-    tensor is the caller's, like a level bank: the engine keeps nothing of it."""
+    tensor is the caller's, like a level bank: the engine keeps nothing of it.  A field of grid_field() — built over the caller's own
+    maps — has `obstacles` "grid", `target` None or the tensor of points, and `margin` is its whole inflation radius."""
 
     def __init__(self, field, params, target, obstacles):
         self.field, self.params, self.target, self.obstacles = field, params, target, obstacles
@@ -193,6 +194,8 @@ class WorldQueries:
         if into is not None:
             if not isinstance(into, NavField):
                 raise ValueError("nav_field: `into` must be a NavField")
+            if into.obstacles == "grid":
+                raise ValueError("nav_field: `into` is a grid field: grid_field(into=) rebuilds it")
             if target is not None or margin is not None or reach is not None or (cell, obstacles) != (0.25, "walls"):
                 raise ValueError("nav_field: with `into` the field's own target and parameters are used: pass only mask")
             field, params, target = into.field, into.params, into.target
@@ -220,6 +223,70 @@ class WorldQueries:
         mask = self._device_mask(mask, "nav_field")
         out = into if into is not None else NavField(field, params, target, obstacles)
         e.nav_build(params, field, mask, out.points)
+        return out
+
+    def _cell_grid(self, where, name, t, gz, gx, optional=True):
+        """a grid of bytes of grid_field: None where that may be, or a contiguous uint8 / bool [N, gz, gx] tensor already on the
+        device; a bool is viewed as bytes (0 / 1: no conversion kernel)"""
+        torch = self.torch
+        if t is None and optional:
+            return None
+        if not any(self._is_tensor(t, (self.num_envs, gz, gx), dt) for dt in (torch.uint8, torch.bool)):
+            raise ValueError(f"{where}: {name} is a contiguous uint8 or bool tensor [{self.num_envs}, {gz}, {gx}] on {self.engine.device}")
+        return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+    def grid_field(self, blocked, sources=None, target=None, reach=None, extra=None, inflate=None, like=None, cell=0.25, mask=None, into=None):
+        """The shortest-path cost to the nearest source over the caller's OWN maps — the planner for a map the agent built from what
+        it perceived, where nav_field() reads the simulator's walls —, built on the device by one kernel (mw_nav_build_grid) with no
+        host value and no synchronisation: a NavField whose `obstacles` is "grid".  nav_query(), ego_update(source=) and
+        seen_map(like=) take it like any other; nav_query's waypoint at cost 0 is the centre of the source cell itself.
+
+        blocked   uint8 or bool [N, gz, gx] device tensor: != 0 a raw obstacle cell (a DepthMap's `obstacle` plane made contiguous, a
+                  SeenMap, the caller's own raster)
+        sources   the same kind of tensor: != 0 a source cell (a frontier mask: one build gives the way to the nearest frontier)
+        target    a float64[N, 3] device tensor of points with `reach` metres around them, as in nav_field(); with `sources` the
+                  union of both.  At least one of the two.
+        extra     the same kind of tensor as `blocked`: a cost 0 .. 255 added to every path through the cell (sources stay 0)
+        inflate   metres: a cell is blocked too when a raw obstacle cell's centre is closer than this to its own.  None:
+                  agent_radius + cell / 2, nav_field()'s default clearance.  0: the raw cells only.  At most
+                  engine.NAV_MAX_INFLATE cells.  The agent's radius is NOT added: the caller's grid may already hold it.
+        like      a NavField, SeenMap or DepthMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell` metres
+                  per cell as in nav_field().
+        mask      uint8[N] or bool[N] device tensor: only those envs' rows are built (the others are not touched)
+        into      a grid field to rebuild in place: the grids are passed again, the grid's parameters are the field's own
+        The tensors are checked and never converted.  An env whose costs do not fit 16 bits gets a row of 0xFFFF and engine.check()
+        raises once.  ValueError for arguments that make no field; nothing is launched then."""
+        torch, e = self.torch, self.engine
+        if into is not None:
+            if not isinstance(into, NavField) or into.obstacles != "grid":
+                raise ValueError("grid_field: `into` must be a NavField of grid_field()")
+            if target is not None or reach is not None or inflate is not None or like is not None or cell != 0.25:
+                raise ValueError("grid_field: with `into` the field's own points and parameters are used: pass only the grids and mask")
+            field, params, target = into.field, into.params, into.target
+        else:
+            g = self._map_grid("grid_field", cell, like, (NavField, SeenMap, DepthMap), "its own")
+            cell, gx, gz = g.cell, g.gx, g.gz
+            inflate = float(e.cfg.agent_radius) + cell / 2 if inflate is None else real("grid_field", "inflate", inflate, lo_open=False)
+            if inflate > eng.NAV_MAX_INFLATE * cell:
+                raise ValueError(f"grid_field: inflate {inflate!r} is more than {eng.NAV_MAX_INFLATE} cells of {cell!r}")
+            if target is not None:
+                if not self._is_tensor(target, (self.num_envs, 3)):
+                    raise ValueError(f"grid_field: point targets are a contiguous float64 tensor [{self.num_envs}, 3] on {e.device}")
+                reach = real("grid_field", "reach (point targets need one)", reach)
+            elif reach is not None:
+                raise ValueError("grid_field: reach without point targets")
+            params = eng.MwNavParams(cell, inflate, reach or 0.0, gx, gz, eng.NAV_GRID, 0)
+        if sources is None and target is None:
+            raise ValueError("grid_field: no sources: pass a mask of source cells, point targets, or both")
+        blocked = self._cell_grid("grid_field", "blocked", blocked, params.gz, params.gx, optional=False)
+        sources = self._cell_grid("grid_field", "sources", sources, params.gz, params.gx)
+        extra = self._cell_grid("grid_field", "extra", extra, params.gz, params.gx)
+        mask = self._device_mask(mask, "grid_field")
+        if into is None:
+            # (0xFFFF throughout, as nav_field fills it)
+            field = torch.full((self.num_envs, params.gz, params.gx), -1, dtype=torch.int16, device=e.device).view(torch.uint16)
+        out = into if into is not None else NavField(field, params, target, "grid")
+        e.nav_build_grid(params, field, blocked, sources, target, extra, mask)
         return out
 
     def nav_query(self, field, pos=None):
