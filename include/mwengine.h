@@ -1054,6 +1054,51 @@ typedef struct mw_label_params mw_label_params;
 int mw_label_frame(mw_engine *e, const mw_label_params *params, const uint8_t *d_mask, uint8_t *d_class, int32_t *d_code, float *d_depth,
                    int32_t *d_ent_pixels, int32_t *d_ent_box, void *stream);
 
+/* ---- object maps ---------------------------------------------------------------------------------------------------------------------
+ * Labelled pixels projected onto the maps a depth sensor gives: the semantic map of an ObjectNav stack (SemExp's category channels,
+ * Habitat's semantic top-down map).  Every pixel of an env's label image — int32 [N][H][W], mw_label_frame's d_code or the caller's own
+ * category image — is unprojected with its depth exactly as mw_depth_project unprojects it and carries its id into the cell it falls in, of
+ * an egocentric window laid out as mw_ego_map's (cell for cell an entity plane's, and a depth window's) or of a grid over the floor plan laid
+ * out as mw_nav_build's.  With mw_depth_project's map and mw_nav_build_grid a policy can find, reach and recognise a goal from sensor
+ * images alone.  The reference has no such call.
+ *
+ * All arithmetic is float64, only + - * /, floor and the engine's deterministic sin / cos, uncontracted, in exactly mw_depth_project's
+ * order: the camera terms and the sample position (sub_x, sub_y), the range test and the height classes, px / pz, the window bin and the
+ * map bin are the ones defined there, by name.  Every test is written so that a NaN fails it.  Per pixel k:
+ *   the pixel counts iff mw_depth_project would count it as floor or as obstacle and its bin lies inside the target
+ *   id = code[k] - base, valid iff code[k] >= base && code[k] - base <= 254 (compared before the subtraction: nothing overflows)
+ *   key = id where valid, else 0xFFFE: "seen, no object"
+ *   a cell's key is the minimum of its pixels' keys, from 0xFFFF: "not seen by this frame".  The lowest id wins a shared cell; the result
+ *   does not depend on the kernel's schedule.
+ * base = MW_RAY_ENT makes ids the entity slots of mw_label_frame's d_code; base = 0 takes the caller's own image, negative values for none.
+ * The window target (grid == NULL; size, cell, back and MW_EGO_NORTH as in mw_depth_project):
+ *   d_plane[i][r][c] = 1 + key where key <= 254, else 0; the plane is written in full by every call.
+ * The map target (grid != NULL: cell, gx, gz are read; min_x, min_z the env's own extent).  The last observation wins — objects here are
+ * picked up, carried, dropped, and a health kit respawns.  For an env i under the mask:
+ *   d_clear[i] != 0: every byte d_map[i][j][c] is rewritten, 1 + key where key <= 254, else 0
+ *   otherwise a cell whose key is 0xFFFF keeps its byte and every other cell gets key <= 254 ? 1 + key : 0: a cell seen empty now forgets
+ *   the object it held, a cell out of view keeps what it knew.
+ * The per-object outputs, for every id q < ids over the whole map of the env after the update:
+ *   n = the cells whose byte is 1 + q; si, sj = the integer sums of their column and row indices (exact, order-free, below 2^28)
+ *   d_obj_cells[i][q] = n
+ *   d_obj_pos[i][q] = (min_x + ((double)si / (double)n + 0.5) * cell, 0.0, min_z + ((double)sj / (double)n + 0.5) * cell), three quiet
+ *   NaNs when n == 0.  Row q of [N][K][3], made contiguous, serves as the points of mw_nav_build, mw_nav_build_grid or mw_nav_query.
+ * Rows of envs under a zero mask byte are neither read nor written: the mask wins over clear.  An env whose extent the grid does not cover
+ * (as for mw_nav_build) gets its map zeroed, its cells 0 and its positions NaN, and sets a status bit that the next mw_check reports as
+ * MW_E_INVALID, "mw_label_project refused an env", once.
+ *
+ * One kernel, one workgroup per env, asynchronous on `stream`; it reads no host value except host_params (during the call), reads live
+ * arrays only and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched: everything
+ * mw_depth_project refuses for the same host_params, d_depth, size, flags and grid, a frame of more than MW_DEPTH_MAX_PIXELS pixels
+ * included; a null d_code; a base < 0; ids outside 0 .. 255; a window with a null d_plane or ids > 0; a map with a null d_map, or with
+ * ids > 0 and both per-object outputs null; a map of more than 16384 cells (a key of LDS per cell: use a larger cell). */
+int mw_label_project(mw_engine *e, const double *host_params /* [6], mw_depth_project's */,
+                     const float *d_depth /* [N][H][W] */, const int32_t *d_code /* [N][H][W] */, int32_t base,
+                     const uint8_t *d_mask, int32_t size, int32_t flags, uint8_t *d_plane /* [N][size][size], window target */,
+                     const mw_nav_params *grid /* NULL = window */, const uint8_t *d_clear, uint8_t *d_map /* [N][gz][gx] */,
+                     int32_t ids /* K: 0 .. 255 */, int32_t *d_obj_cells /* [N][K] or NULL */, double *d_obj_pos /* [N][K][3] or NULL */,
+                     void *stream);
+
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.
@@ -1065,7 +1110,7 @@ int mw_label_frame(mw_engine *e, const mw_label_params *params, const uint8_t *d
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update or mw_depth_project skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_depth_project or mw_label_project skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

@@ -57,6 +57,7 @@
 #define MW_ST_NAV_BAD 16u           // mw_nav_build refused an env (its row is all 0xFFFF): the grid does not cover its extent, a cost would reach 0xFFFE, or the relaxation hit its bound on passes
 #define MW_ST_SEEN_BAD 32u          // mw_seen_update refused an env (its row is zeroed, its count 0): the grid does not cover its extent
 #define MW_ST_DEPTH_BAD 64u         // mw_depth_project refused an env (its rows of the map are zeroed, its counts 0): the grid does not cover its extent
+#define MW_ST_LABELMAP_BAD 128u     // mw_label_project refused an env (its map is zeroed, its cells 0, its positions NaN): the grid does not cover its extent
 
 // Generator tables; kept in device memory because dynamic indexing into a by-value kernarg
 // struct would force a private (scratch) copy of the whole argument block.

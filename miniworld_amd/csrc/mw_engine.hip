@@ -751,6 +751,11 @@ int mw_check(mw_engine *e, void *stream)
         HIP_TRY(e, hipMemcpy(e->args.status, &rest, 4, hipMemcpyHostToDevice));
         return fail(e, MW_E_INVALID, "mw_depth_project refused an env (its rows of the map are zeroed, its counts 0): the grid does not cover the env's extent");
     }
+    if (st & MW_ST_LABELMAP_BAD) {  // and again
+        const uint32_t rest = st & ~MW_ST_LABELMAP_BAD;
+        HIP_TRY(e, hipMemcpy(e->args.status, &rest, 4, hipMemcpyHostToDevice));
+        return fail(e, MW_E_INVALID, "mw_label_project refused an env (its map is zeroed, its cells 0, its positions NaN): the grid does not cover the env's extent");
+    }
     if (st & MW_ST_VIS_OVERFLOW) return fail(e, MW_E_OVERFLOW, "more than max_visible=%d visible primitives in some env", e->cfg.max_visible);
     if (st & MW_ST_PLACEMENT_FAIL) return fail(e, MW_E_OVERFLOW, "device-side placement did not converge in some env");
     if (st & MW_ST_SNAPSHOT_BAD)

@@ -14,6 +14,7 @@
 #include "mw_ego.h"
 #include "mw_depth.h"
 #include "mw_label.h"
+#include "mw_labelmap.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -320,6 +321,17 @@ extern "C" __global__ void mw_depth_kernel(MwRayArgs a, const double *__restrict
 extern "C" __global__ void mw_label_kernel(MwLabelArgs a, mw_label_params p, int band_rows, int chunk, int prune, const uint8_t *__restrict__ mask,
                                            uint8_t *__restrict__ cls, int32_t *__restrict__ code, float *__restrict__ depth,
                                            int32_t *__restrict__ ent_pixels, int32_t *__restrict__ ent_box);
+
+// object maps (mw_labelmap.hip; the arithmetic, the phases and the launch constants: mw_labelmap.h; the launch: mwpolicy::labelmap_launch).
+// The sensor, the window and the grid travel by value as for mw_depth_kernel, whose cam it reads too.  Grid N workgroups of
+// MW_LABELMAP_THREADS lanes, MW_LABELMAP_WORD_BYTES of dynamic LDS per cell of the target and three times that per id; exactly one of plane
+// ([N][size][size]) and map ([N][gz][gx]) is non-null; env b's rows where mask is null or mask[b] != 0; clear may be null; K ids (0 with a
+// plane) with obj_cells ([N][K]) and obj_pos ([N][K][3]), either of which may be null; wide != 0: W * H is a multiple of 4 and depth and
+// code 16-byte aligned.
+extern "C" __global__ void mw_labelmap_kernel(MwRayArgs a, const double *__restrict__ cam, mwdepth::Sensor s, mwdepth::Window w, mw_nav_params p, int wide,
+                                              const float *__restrict__ depth, const int32_t *__restrict__ code, int32_t base, const uint8_t *__restrict__ mask,
+                                              const uint8_t *__restrict__ clear, uint8_t *__restrict__ plane, uint8_t *__restrict__ map, int K,
+                                              int32_t *__restrict__ obj_cells, double *__restrict__ obj_pos);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

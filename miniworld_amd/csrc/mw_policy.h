@@ -12,6 +12,7 @@
 #include "mw_depth.h"           // MW_DEPTH_THREADS, MW_DEPTH_CELL_BYTES, MW_DEPTH_MAX_CELLS
 #include "mw_nav_grid.h"        // MW_NAV_GRID_THREADS, mwnav::grid_field_bytes, mwnav::grid_extra_bytes
 #include "mw_label.h"           // MW_LABEL_THREADS, MW_LABEL_CHUNK, MW_LABEL_MAX_POLYS, MW_LABEL_MAX_ENTS, mwlabel::plan_bytes
+#include "mw_labelmap.h"        // MW_LABELMAP_THREADS, MW_LABELMAP_WORD_BYTES, MW_LABELMAP_MAX_CELLS, MW_LABELMAP_MAX_IDS
 #include "mw_shape.h"
 #include "mw_snapframes.h"      // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -322,7 +323,7 @@ inline SnapfGrid snapf_where_grid(uintptr_t address_bits, uint64_t frame_bytes, 
     return snapf_grid(address_bits, frame_bytes, depth_bytes, stack_depth, N);
 }
 
-// The launch of a world query whose kernel takes a workgroup per env (seen_launch, ego_launch, depth_launch): the grid, the lanes of a
+// The launch of a world query whose kernel takes a workgroup per env (seen_launch, ego_launch, depth_launch, labelmap_launch): the grid, the lanes of a
 // workgroup, its dynamic LDS in bytes, and whether that fits.  (ray_launch and label_launch return more: RayLaunch, LabelLaunch.)
 struct Launch { unsigned long long grid; int threads; size_t lds; bool fits; };
 using SeenLaunch = Launch;      // (the names the three had while each declared the same four fields)
@@ -407,6 +408,18 @@ inline LabelLaunch label_launch(int N, int W, int H, int max_polys, int max_ents
     l.fits = l.band_rows >= 1;
     l.lds = l.fits ? mwlabel::plan_bytes(l.band_rows * W, chunk, max_ents) : 0;
     return l;
+}
+
+// Object maps (mw_label_project; kernel: mw_labelmap.hip): a workgroup of MW_LABELMAP_THREADS lanes per env.  Its LDS is one uint32 key per
+// cell of the target — size * size of a window, gx * gz of a map — and behind the keys three words per id (n, si, sj): 68 596 bytes at
+// MW_LABELMAP_MAX_CELLS = 16384 cells and MW_LABELMAP_MAX_IDS = 255 ids, above 64 KiB, which one workgroup may hold (a CU has 160 KiB; the
+// engine asks for it as for mw_nav_grid_kernel).  fits: a positive count of no more cells than that, and 0 .. 255 ids — the caller
+// refuses what does not.
+inline Launch labelmap_launch(int N, long long cells, int ids)
+{
+    const bool fits = cells >= 1 && cells <= MW_LABELMAP_MAX_CELLS && ids >= 0 && ids <= MW_LABELMAP_MAX_IDS;
+    const size_t lds = fits ? ((size_t)cells + 3 * (size_t)ids) * MW_LABELMAP_WORD_BYTES : 0;
+    return {(unsigned long long)N, MW_LABELMAP_THREADS, lds, fits};
 }
 
 }  // namespace mwpolicy

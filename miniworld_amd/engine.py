@@ -138,6 +138,9 @@ EGO_MAX_SIZE = 128                      # MW_EGO_MAX_SIZE
 DEPTH_MAX_PIXELS = 65535                # MW_DEPTH_MAX_PIXELS
 DEPTH_MAX_CELLS = 16384                 # the cells of a depth window or map: 4 bytes of LDS each (csrc/mw_depth.h)
 
+LABELMAP_MAX_CELLS = 16384              # the cells of an object window or map: a key of LDS each (csrc/mw_labelmap.h)
+LABELMAP_MAX_IDS = 255                  # the ids of an object map's per-object outputs; an id is 0 .. 254, a byte 1 + id
+
 LABEL_NOTHING, LABEL_FLOOR, LABEL_CEILING, LABEL_WALL, LABEL_FRAME, LABEL_BOX, LABEL_MESH = range(7)       # MW_LABEL_* classes
 LABEL_MESH_EXACT, LABEL_MESH_BOUNDS, LABEL_UNPRUNED = 0, 1, 2           # MW_LABEL_* flags
 
@@ -246,6 +249,7 @@ SIGNATURES = {
     "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
     "mw_depth_project": _sig(vp, P(C.c_double), vp, vp, i32, i32, vp, P(MwNavParams), i32, vp, vp, vp, vp, vp),
     "mw_label_frame": _sig(vp, vp, vp, vp, vp, vp, vp, vp, vp),        # (params: an MwLabelParams by reference)
+    "mw_label_project": _sig(vp, P(C.c_double), vp, vp, i32, vp, i32, i32, vp, P(MwNavParams), vp, vp, i32, vp, vp, vp),
     "mw_debug_set_launch_shape": _sig(vp, C.c_int, C.c_int, C.c_int, C.c_int),
     "mw_pcg64_draws": _sig(C.c_uint64, i32, vp, vp),
     "mw_selftest_rcp": _sig(vp, vp, vp),
@@ -687,6 +691,46 @@ class Engine:
                 self._shaped_tensor(t, name, dtype, shape)
         self._check(self.lib.mw_label_frame(self.h, C.byref(params), _ptr(mask), _ptr(cls), _ptr(code), _ptr(depth), _ptr(ent_pixels), _ptr(ent_box),
                                             _stream_ptr(self.device)), "mw_label_frame")
+
+    # -- object maps ---------------------------------------------------------------------
+    def label_project(self, depth, code, base: int, min_range: float, max_range: float, floor_tol: float, top: float, mask=None, size: int = 0,
+                      cell: float = 0.0, back: float = 0.0, flags: int = 0, plane=None, params: MwNavParams | None = None, map=None, clear=None, ids: int = 0,
+                      cells=None, pos=None):
+        """mw_label_project: for the envs under `mask` (uint8[N], device; None = all) every pixel of `depth` (float32[N, H, W] or
+        [N, H, W, 1], device) that depth_project() would count carries the id `code - base` of `code` (int32[N, H, W], device) — 0 .. 254,
+        anything else "no object" — into its cell, which keeps the lowest id.  Window target (`plane`, uint8[N, size, size]: 1 + id, 0 for
+        none, of mw_ego_map's window of `size`, `cell`, `back`, EGO_NORTH in `flags`) or map target (`params` with `map`, uint8[N, gz, gx]:
+        a cell the frame saw is rewritten, the others keep their byte, behind a rewrite of every byte of the rows under `clear`, uint8[N];
+        with `ids` > 0 `cells`, int32[N, ids], and `pos`, float64[N, ids, 3], at least one of them: how many cells of the map hold each id
+        and their centroid, NaN for none).  One kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong
+        tensor is refused before the library is called."""
+        import torch
+        H, W = self.H, self.W
+        if not torch.is_tensor(depth) or tuple(depth.shape) not in ((self.N, H, W), (self.N, H, W, 1)):
+            raise EngineError(f"depth: need a float32 tensor [{self.N}, {H}, {W}] or [{self.N}, {H}, {W}, 1], got "
+                              f"{tuple(depth.shape) if torch.is_tensor(depth) else type(depth).__name__}")
+        self._dev_tensor(depth, "depth", torch.float32, self.N * H * W)
+        self._shaped_tensor(code, "code", torch.int32, (self.N, H, W))
+        mask = self._mask_tensor(mask, optional=True)
+        if (plane is None) == (params is None):
+            raise EngineError("label_project: exactly one target, plane (a window) or params with map (a map)")
+        if params is None:
+            self._shaped_tensor(plane, "plane", torch.uint8, (self.N, int(size), int(size)))
+            if map is not None or clear is not None or cells is not None or pos is not None:
+                raise EngineError("label_project: map, clear, cells and pos belong to the map target")
+        else:
+            if map is None:
+                raise EngineError("map: None")
+            self._shaped_tensor(map, "map", torch.uint8, (self.N, int(params.gz), int(params.gx)))
+            if cells is not None:
+                self._shaped_tensor(cells, "cells", torch.int32, (self.N, int(ids)))
+            if pos is not None:
+                self._shaped_tensor(pos, "pos", torch.float64, (self.N, int(ids), 3))
+            self._dev_tensor(clear, "clear", torch.uint8, self.N)
+        host = (C.c_double * 6)(float(min_range), float(max_range), float(floor_tol), float(top), float(cell), float(back))
+        self._check(self.lib.mw_label_project(self.h, host, _ptr(depth), _ptr(code), int(base), _ptr(mask), int(size), int(flags), _ptr(plane),
+                                              None if params is None else C.byref(params), _ptr(clear), _ptr(map), int(ids), _ptr(cells), _ptr(pos),
+                                              _stream_ptr(self.device)), "mw_label_project")
 
     def debug_set_launch_shape(self, waves_per_env: int = 0, mesh_tile_waves: int = 0, ent_blocks: int = 0, slow_waves: int = 0):
         """Tests and measurements: wavefronts per env of the tile kernels (a divisor of the frame's tile count) and the persistent

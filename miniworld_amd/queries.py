@@ -1,6 +1,6 @@
 """The world queries of the batched env — navigation fields, explored-area maps, egocentric map windows, depth projection, label frames,
-ray casts —, each one kernel on the device with no host value: their value classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap,
-LabelFrame) and
+object maps, ray casts —, each one kernel on the device with no host value: their value classes (NavField, SeenMap, EgoWindow, DepthWindow,
+DepthMap, LabelFrame, ObjectWindow, ObjectMap) and
 `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
 from __future__ import annotations
 
@@ -127,6 +127,34 @@ class LabelFrame:
         return (self.code - eng.RAY_ENT).masked_fill_(self.code < eng.RAY_ENT, -1)
 
 
+class ObjectWindow:
+    """A sensed object window (MiniWorldVecEnv.object_window): `plane`, the uint8[N, S, S] device tensor that object_update() fills, laid
+    out cell for cell like an EgoWindow's `entity` plane and like a DepthWindow of the same size, cell, anchor and frame: 1 + the id of
+    the object whose labelled pixels fell into the cell — the lowest id where several did —, 0 for none.  `min_range`, `max_range`,
+    `floor_tol` and `top` say which pixels count, exactly as for a DepthWindow.  The tensor is the caller's: the engine keeps nothing of it."""
+
+    def __init__(self, plane, size, cell, back, frame, min_range, max_range, floor_tol, top):
+        self.plane, self.size, self.cell, self.back, self.frame = plane, size, cell, back, frame
+        self.min_range, self.max_range, self.floor_tol, self.top = min_range, max_range, floor_tol, top
+
+
+class ObjectMap:
+    """A sensed object map (MiniWorldVecEnv.object_map): `map`, the uint8[N, gz, gx] device tensor that object_map_update() keeps on a nav
+    field's grid (`params`: `cell` metres per cell, gx x gz cells from the env's own min_x, min_z) — 1 + the id of the object last seen in
+    the cell, 0 for none or never seen; the last observation wins: a cell seen empty forgets its object, a cell out of view keeps it —,
+    `cells`, int32[N, ids], how many cells of the map hold each id, and `pos`, float64[N, ids, 3], their centroid (x, 0, z), NaN where
+    there are none: `pos[:, q].contiguous()` is a target of grid_field() and nav_field() and a `pos` of nav_query().  The tensors are
+    the caller's, like a DepthMap's."""
+
+    def __init__(self, map, cells, pos, params, ids, min_range, max_range, floor_tol, top):
+        self.map, self.cells, self.pos, self.params, self.ids = map, cells, pos, params, ids
+        self.min_range, self.max_range, self.floor_tol, self.top = min_range, max_range, floor_tol, top
+
+    cell = property(lambda self: self.params.cell)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+
+
 assert eng.NAV_ENTITIES == eng.RAY_ENTITIES == eng.SEEN_ENTITIES == eng.EGO_ENTITIES      # (one table serves the four calls)
 
 
@@ -250,7 +278,7 @@ class WorldQueries:
         inflate   metres: a cell is blocked too when a raw obstacle cell's centre is closer than this to its own.  None:
                   agent_radius + cell / 2, nav_field()'s default clearance.  0: the raw cells only.  At most
                   engine.NAV_MAX_INFLATE cells.  The agent's radius is NOT added: the caller's grid may already hold it.
-        like      a NavField, SeenMap or DepthMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell` metres
+        like      a NavField, SeenMap, DepthMap or ObjectMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell` metres
                   per cell as in nav_field().
         mask      uint8[N] or bool[N] device tensor: only those envs' rows are built (the others are not touched)
         into      a grid field to rebuild in place: the grids are passed again, the grid's parameters are the field's own
@@ -264,7 +292,7 @@ class WorldQueries:
                 raise ValueError("grid_field: with `into` the field's own points and parameters are used: pass only the grids and mask")
             field, params, target = into.field, into.params, into.target
         else:
-            g = self._map_grid("grid_field", cell, like, (NavField, SeenMap, DepthMap), "its own")
+            g = self._map_grid("grid_field", cell, like, (NavField, SeenMap, DepthMap, ObjectMap), "its own")
             cell, gx, gz = g.cell, g.gx, g.gz
             inflate = float(e.cfg.agent_radius) + cell / 2 if inflate is None else real("grid_field", "inflate", inflate, lo_open=False)
             if inflate > eng.NAV_MAX_INFLATE * cell:
@@ -321,7 +349,8 @@ class WorldQueries:
         """An empty explored-area map over each env's floor plan: a SeenMap, which seen_update() fills.
 
         cell       metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
-        like       a NavField whose grid (cell, gx, gz) the map adopts, so that map and field line up cell for cell; pass no cell then
+        like       a NavField (or an ObjectMap) whose grid (cell, gx, gz) the map adopts, so that map and field line up cell for cell; pass
+                   no cell then
         max_range  how far the agent sees, in metres
         fov        the horizontal opening angle of sight in radians, 0 < fov <= 2 pi, about the agent's heading; None: default_fov(),
                    the horizontal field of view of the default camera — the vertical field of view the parameters default to and
@@ -334,7 +363,7 @@ class WorldQueries:
         self._obstacle_flags("seen_map", obstacles)
         max_range = real("seen_map", "max_range", max_range)
         cos_half = self._cos_half("seen_map", fov)
-        params = self._map_grid("seen_map", cell, like, (NavField,), "the field's own")
+        params = self._map_grid("seen_map", cell, like, (NavField, ObjectMap), "the field's own")
         n = self.num_envs
         return SeenMap(torch.zeros((n, params.gz, params.gx), dtype=torch.uint8, device=e.device), torch.zeros(n, dtype=torch.int32, device=e.device),
                        torch.zeros(n, dtype=torch.int32, device=e.device), params, max_range, cos_half, obstacles)
@@ -498,12 +527,13 @@ class WorldQueries:
         """An empty depth-built map over each env's floor plan: a DepthMap, which depth_map_update() accumulates.  Nothing is launched.
 
         cell        metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
-        like        a NavField or SeenMap whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass no cell then
+        like        a NavField, SeenMap or ObjectMap whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass no
+                    cell then
         min_points  how many pixels of ONE depth map must fall into a cell to set it, 1 .. 255
         min_range, max_range, floor_tol, top  as for depth_window()
         At most 16384 cells (the kernel counts in 64 KiB of LDS): ValueError says "use a larger cell" otherwise."""
         torch, e = self.torch, self.engine
-        params = self._map_grid("depth_map", cell, like, (NavField, SeenMap), "its own")
+        params = self._map_grid("depth_map", cell, like, (NavField, SeenMap, ObjectMap), "its own")
         gx, gz = params.gx, params.gz
         if gx * gz > eng.DEPTH_MAX_CELLS:
             raise ValueError(f"depth_map: {gx} x {gz} cells > {eng.DEPTH_MAX_CELLS}: use a larger cell")
@@ -577,6 +607,97 @@ class WorldQueries:
         params = eng.MwLabelParams(f.near, f.far, self.MESHES[f.meshes], 0)
         self.engine.label_frame(params, f.cls, f.code, f.depth, f.ent_pixels, f.ent_box, mask)
         return f.cls
+
+    # ------------------------------------------------------------------ object maps
+    def _label_input(self, where, labels, depth):
+        """(code, base, depth) of an object projection: a LabelFrame with `code` — ids are its entity slots, and its own depth serves where
+        it has one — or the caller's contiguous int32[N, H, W] category image on the device — ids are its values"""
+        torch, e = self.torch, self.engine
+        n, H, W = self.num_envs, int(e.cfg.obs_height), int(e.cfg.obs_width)
+        if isinstance(labels, LabelFrame):
+            if labels.code is None:
+                raise ValueError(f"{where}: the label frame has no `code`: make it with label_frame(code=True)")
+            code, base = labels.code, eng.RAY_ENT
+            if depth is None and labels.depth is not None:
+                depth = labels.depth
+        elif torch.is_tensor(labels):
+            code, base = labels, 0
+        else:
+            raise ValueError(f"{where}: labels is a LabelFrame or an int32 tensor [{n}, {H}, {W}] on {e.device}, not {type(labels).__name__}")
+        if not self._is_tensor(code, (n, H, W), torch.int32):
+            raise ValueError(f"{where}: the labels are a contiguous int32 tensor [{n}, {H}, {W}] on {e.device}")
+        return code, base, self._depth_input(where, depth)
+
+    def object_window(self, size=33, cell=0.25, anchor="centre", frame="heading", min_range=0.05, max_range=8.0, floor_tol=0.1, top=None):
+        """An empty sensed object window: an ObjectWindow, which object_update() fills.  Nothing is launched.  Every argument is
+        depth_window()'s: the two windows, and an ego_window()'s entity plane, line up cell for cell.
+        ValueError for arguments that make no window."""
+        torch, e = self.torch, self.engine
+        size, cell, back, frame = self._window_shape("object_window", size, cell, anchor, frame)
+        sensor = self._depth_sensor("object_window", min_range, max_range, floor_tol, top)
+        self._depth_pixel_cap("object_window")
+        return ObjectWindow(torch.zeros((self.num_envs, size, size), dtype=torch.uint8, device=e.device), size, cell, back, frame, *sensor)
+
+    def object_update(self, w, labels, depth=None, mask=None):
+        """Fills `w` (an ObjectWindow) from a label image and a depth map, by one kernel (mw_label_project) with no host value and no
+        synchronisation; returns w.plane.  Every pixel that depth_update() would count — unprojected with its env's own camera and the pose
+        the device holds NOW — writes its id into the cell it falls in; the lowest id wins a shared cell.
+
+        labels  a LabelFrame with `code` (label_update() filled it): ids are entity slots, 0 .. 254; or a contiguous int32[N, H, W] device
+                tensor, the caller's own category image (a segmenter's arg-max): ids are its values 0 .. 254, anything else is no object
+        depth   None: the label frame's own `depth` where it has one, else `self.depth`; or a contiguous float32[N, H, W, 1] / [N, H, W]
+                device tensor
+        mask    uint8[N] or bool[N] device tensor: only those envs' rows are read and written
+        Tensors are checked, never converted (EngineError); ValueError for arguments that make no call; nothing is launched then."""
+        if not isinstance(w, ObjectWindow):
+            raise ValueError("object_update: `w` must be an ObjectWindow (object_window())")
+        code, base, depth = self._label_input("object_update", labels, depth)
+        mask = self._device_mask(mask, "object_update")
+        self.engine.label_project(depth, code, base, w.min_range, w.max_range, w.floor_tol, w.top, mask, size=w.size, cell=w.cell, back=w.back,
+                                  flags=eng.EGO_NORTH if w.frame == "north" else 0, plane=w.plane)
+        return w.plane
+
+    def object_map(self, cell=0.25, like=None, ids=None, min_range=0.05, max_range=8.0, floor_tol=0.1, top=None):
+        """An empty sensed object map over each env's floor plan: an ObjectMap, which object_map_update() keeps.  Nothing is launched.
+
+        cell   metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
+        like   a NavField, SeenMap, DepthMap or ObjectMap whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass
+               no cell then
+        ids    K, 0 .. 255: `cells` and `pos` have a row for each id below it (an id from K on is mapped, not counted); None: the env's
+               entity slots, at most 255.  0: the map alone
+        min_range, max_range, floor_tol, top  as for depth_window()
+        At most 16384 cells (the kernel keeps a key per cell in LDS): ValueError says "use a larger cell" otherwise."""
+        torch, e = self.torch, self.engine
+        params = self._map_grid("object_map", cell, like, (NavField, SeenMap, DepthMap, ObjectMap), "its own")
+        gx, gz = params.gx, params.gz
+        if gx * gz > eng.LABELMAP_MAX_CELLS:
+            raise ValueError(f"object_map: {gx} x {gz} cells > {eng.LABELMAP_MAX_CELLS}: use a larger cell")
+        ids = min(int(e.cfg.max_ents), eng.LABELMAP_MAX_IDS) if ids is None else integer("object_map", "ids", ids, 0, eng.LABELMAP_MAX_IDS)
+        sensor = self._depth_sensor("object_map", min_range, max_range, floor_tol, top)
+        self._depth_pixel_cap("object_map")
+        n = self.num_envs
+        return ObjectMap(torch.zeros((n, gz, gx), dtype=torch.uint8, device=e.device), torch.zeros((n, ids), dtype=torch.int32, device=e.device),
+                         torch.full((n, ids, 3), float("nan"), dtype=torch.float64, device=e.device), params, ids, *sensor)
+
+    def object_map_update(self, m, labels, depth=None, clear=None, mask=None):
+        """Writes what a label image and a depth map show into `m` (an ObjectMap), by one kernel (mw_label_project) with no host value and
+        no synchronisation; returns m.cells, int32[N, ids], while m.pos carries each id's centroid.  The last observation wins: a cell
+        this frame saw gets the lowest id of its pixels or 0, every other cell keeps its byte.  The pose is the one the device holds
+        now, as for depth_map_update().
+
+        labels, depth  as for object_update()
+        clear  uint8[N] or bool[N] device tensor: those envs' maps are rewritten whole — behind a step of the same-step auto-reset,
+               `object_map_update(m, labels, clear=terminated | truncated)` starts every new episode's map
+        mask   uint8[N] or bool[N] device tensor: only those envs are updated; the mask wins over clear
+        An env whose extent the grid does not cover gets its map zeroed, its cells 0 and its positions NaN, and engine.check() raises once."""
+        if not isinstance(m, ObjectMap):
+            raise ValueError("object_map_update: `m` must be an ObjectMap (object_map())")
+        code, base, depth = self._label_input("object_map_update", labels, depth)
+        clear, mask = self._device_mask(clear, "object_map_update", "clear"), self._device_mask(mask, "object_map_update")
+        ids = int(m.ids)
+        self.engine.label_project(depth, code, base, m.min_range, m.max_range, m.floor_tol, m.top, mask, params=m.params, map=m.map, clear=clear, ids=ids,
+                                  cells=m.cells if ids else None, pos=m.pos if ids else None)
+        return m.cells
 
     # ------------------------------------------------------------------ ray casts
     def raycast(self, direction=None, origin=None, offsets=None, max_t=1.0, radius=0.0, obstacles="walls", mask=None, into=None):

@@ -30,7 +30,7 @@ from . import engine as eng
 from . import envs as _envs
 from ._args import integer, seeds_u64
 from .env_config import _INFO_KIND, _KIND, AUTORESET_MODES, EnvConfig, _ball_key_meshes, _entity_slots, build_config   # noqa: F401 (re-exported)
-from .queries import DepthMap, DepthWindow, EgoWindow, LabelFrame, NavField, SeenMap, WorldQueries     # noqa: F401
+from .queries import DepthMap, DepthWindow, EgoWindow, LabelFrame, NavField, ObjectMap, ObjectWindow, SeenMap, WorldQueries     # noqa: F401
 from .restarts import Restarts
 from .scene import polys_array, scene_from_env, state_arrays, upload_scene_meshes
 from .snapshots import EnvSnapshot, Snapshots           # noqa: F401

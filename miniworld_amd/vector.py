@@ -74,7 +74,8 @@ class MiniWorldVectorEnv(VectorEnvBase):
 
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
                  frame_reuse: bool = True, frame_cache: int = 4, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset",
-                 levels=None, level_generator=None, reset_seeds=None, info_state=None, seen_map=None, ego_map=None, depth_map=None, label_frame=None, **kwargs):
+                 levels=None, level_generator=None, reset_seeds=None, info_state=None, seen_map=None, ego_map=None, depth_map=None, label_frame=None, object_map=None,
+                 **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
         False draws every env on every step, for consumers that write into the returned observation tensor (module docstring).
@@ -113,7 +114,22 @@ class MiniWorldVectorEnv(VectorEnvBase):
         what each pixel of the new observation shows on the device (`self.label`, a LabelFrame; one kernel) and add info["label"]: that
         LabelFrame itself, whose tensors the next step rewrites (clone what must outlive it).  For an env whose episode ended with the
         step the labels show what the device holds, like the observation under the same-step auto-reset.  None (the default) adds
-        nothing and calls nothing."""
+        nothing and calls nothing.
+        object_map: a dict of MiniWorldVecEnv.object_window()'s arguments (an empty one for its defaults) — needs label_frame= with `code`
+        (ValueError otherwise); reset() and every step() project the new labels into an egocentric window on the device behind the label
+        update (`self.object_win`, an ObjectWindow; one kernel; the label frame's own depth where it has one, else the env's, for which
+        want_depth is switched on) and add info["object_map"], uint8[N, S, S]: 1 + the entity slot sensed in each cell, 0 for none —
+        laid out like ego_map's entity plane, which is its label.  A copy: it stays valid after the next step.  None (the default)
+        adds nothing and calls nothing."""
+        if object_map is not None:
+            if not isinstance(object_map, dict):
+                raise ValueError(f"object_map: need a dict of MiniWorldVecEnv.object_window()'s arguments or None, not {object_map!r}")
+            if not isinstance(label_frame, dict) or label_frame.get("code", True) is not True:
+                raise ValueError("object_map= projects the label frame's codes: it needs label_frame= (a dict) with code=True")
+            if label_frame.get("depth", False) is not True:
+                if kwargs.get("want_depth", True) is not True:
+                    raise ValueError("object_map= needs a depth map: label_frame=dict(depth=True), or the env's own (it excludes want_depth=False)")
+                kwargs["want_depth"] = True
         if label_frame is not None and not isinstance(label_frame, dict):
             raise ValueError(f"label_frame: need a dict of MiniWorldVecEnv.label_frame()'s arguments or None, not {label_frame!r}")
         if depth_map is not None:
@@ -172,6 +188,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
         self.ego = None if ego_map is None else self.vec.ego_window(**ego_map)
         self.depth_win = None if depth_map is None else self.vec.depth_window(**depth_map)
         self.label = None if label_frame is None else self.vec.label_frame(**label_frame)
+        self.object_win = None if object_map is None else self.vec.object_window(**object_map)
         if levels is not None:
             from .vec_env import EnvSnapshot
             self.vec.set_levels(levels if isinstance(levels, EnvSnapshot) else self.vec.make_levels(levels), level_generator)
@@ -241,13 +258,20 @@ class MiniWorldVectorEnv(VectorEnvBase):
             info["label"] = self.label
         return info
 
+    def _object_info(self, info):
+        """object_map: one object_update() behind the label update; a copy of the window's plane (it is rewritten by the next step)"""
+        if self.object_win is not None:
+            plane = self.vec.object_update(self.object_win, self.label)
+            info["object_map"] = self._out(plane) if self.to_numpy else plane.clone()
+        return info
+
     def reset(self, *, seed: int | None = None, options: dict | None = None):
         """Env i is seeded with seed + i (gymnasium's convention for an integer seed); with levels= every env starts a level of the
         bank and the seed is not used."""
         obs = self.vec.reset(seed)
         if self._first_next_seed is not None:       # (reset() lays out seed + N + i; the caller's first choices stand)
             self.vec.next_seed.copy_(self._first_next_seed)
-        return self._out(self._obs(obs)), self._state_info(self._label_info(self._depth_info(self._ego_info(self._seen_info({}, None, True)))))
+        return self._out(self._obs(obs)), self._state_info(self._object_info(self._label_info(self._depth_info(self._ego_info(self._seen_info({}, None, True))))))
 
     def step(self, actions):
         torch = self.vec.torch
@@ -284,6 +308,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
         self._ego_info(info)
         self._depth_info(info)
         self._label_info(info)
+        self._object_info(info)
         self._state_info(info)
         return self._out(self._obs(obs)), self._out(rew), self._out(term.bool()), self._out(trunc.bool()), info
 
