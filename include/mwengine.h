@@ -1099,6 +1099,48 @@ int mw_label_project(mw_engine *e, const double *host_params /* [6], mw_depth_pr
                      int32_t ids /* K: 0 .. 255 */, int32_t *d_obj_cells /* [N][K] or NULL */, double *d_obj_pos /* [N][K][3] or NULL */,
                      void *stream);
 
+/* ---- grid sight -------------------------------------------------------------- */
+/* What a pose would see on the caller's OWN map: line of sight over a uint8 grid of the caller's — a depth map's obstacle plane, its
+ * own raster —, from many candidate cells per env, summed against a weight plane: the gain term of frontier-based exploration and of
+ * Active Neural SLAM's global policy ("standing there, how much of what I do not know would I see?"), a visibility polygon on an
+ * occupancy grid.  The twin of mw_seen_update, which reads the simulator's walls from the agent's true position, as mw_nav_build_grid
+ * is mw_nav_build's.  The reference has no such call.
+ *
+ * The rule.  All of it is defined on cells of a nav grid (cell, gx, gz) and is integer except the cone.
+ *   A viewpoint is a cell A = (ja, ia), a target a cell B = (jb, ib); dx = ib - ia, dz = jb - ja.
+ *   Occlusion: cell Q = (j, i) HIDES B from A iff opaque[Q] != 0, Q != A and Q != B, Q lies in the bounding box of A and B, and
+ *       2 * |dx * (j - ja) - dz * (i - ia)| <= |dx| + |dz|
+ *     — the segment between the two centres meets Q's closed square.  Closed on purpose: a line through a corner is blocked, so two
+ *     opaque cells that touch only at a corner seal (with < in place of <=, (0, 0) sees (7, 7) through an anti-diagonal wall of single
+ *     cells).  The rule is symmetric in A and B.  Per step along the major axis at most 3 cells satisfy it, so a walk costs at most
+ *     3 * max(|dx|, |dz|) probes.
+ *   Range and cone, float64, + - * and sqrt only, uncontracted, in this order: vx = (double)dx * cell, vz = (double)dz * cell;
+ *     dist = sqrt(vx*vx + vz*vz); dist <= range; cos_half == -1.0 || dist == 0.0 || vx*hx + vz*hz >= cos_half*dist, where (hx, hz) is
+ *     the heading mw_ray_cast's fan forms for the viewpoint's angle at offset 0 — test 2 and 3 of mw_seen_update with the viewpoint at
+ *     a cell centre.  The grid's origin does not enter.
+ *   B is SEEN from A iff range and cone hold and no Q hides it.  A sees itself; an opaque B is seen (its face is).
+ * gain[env][v] is the sum over the seen B of weight[B], or their count without a weight plane, as int32; seen[env][B] = 1 for every B
+ * that any viewpoint of the env sees — the call never clears it.  Counts are integer sums and the stores are idempotent, so nothing
+ * depends on the kernel's schedule.
+ *
+ * The viewpoints.  With d_cells: `views` flat cell indices j * gx + i per env; a value outside 0 .. gx*gz - 1 is "no viewpoint": its
+ * gain is 0 and it marks nothing.  Their headings are d_dirs, radians like agent_dir; d_dirs == NULL requires cos_half == -1.  With
+ * d_cells == NULL, views must be 1: the viewpoint is the agent's own cell on the env's grid (origin min_x, min_z; a position outside
+ * is clamped to the border, as mw_nav_query clamps it) and the heading is the agent's; a NaN pose is no viewpoint, and an env whose
+ * extent the grid does not cover gets gain 0 and the status bit, exactly as in mw_seen_update.  Rows of envs under a zero mask byte
+ * are neither read nor written. */
+#define MW_SIGHT_MAX_VIEWS 256   /* viewpoints per env and call */
+/* One kernel, one workgroup per env, asynchronous on `stream`; it reads no host value except host_sight (during the call), reads live
+ * arrays only and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched: a null engine, grid,
+ * host_sight, d_opaque or d_gain; cell <= 0, gx or gz < 1, more than MW_NAV_MAX_CELLS cells; a range that is not > 0 or not finite; a
+ * cos_half outside -1 .. 1 or NaN; views outside 1 .. MW_SIGHT_MAX_VIEWS; without d_cells, views != 1 or a d_dirs; with d_cells and
+ * without d_dirs, a cos_half other than -1; more workgroups than a launch holds. */
+int mw_grid_sight(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */,
+                  const double *host_sight /* [2] on the host, read during the call: range in metres, cos(fov / 2) or -1 */,
+                  int32_t views, const uint8_t *d_mask, const uint8_t *d_opaque /* [N][gz][gx] */, const uint8_t *d_weight /* or NULL */,
+                  const int32_t *d_cells /* [N][views] flat j*gx+i, or NULL */, const double *d_dirs /* [N][views] or NULL */,
+                  int32_t *d_gain /* [N][views] */, uint8_t *d_seen /* [N][gz][gx] or NULL */, void *stream);
+
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.
@@ -1110,7 +1152,7 @@ int mw_label_project(mw_engine *e, const double *host_params /* [6], mw_depth_pr
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_depth_project or mw_label_project skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project or mw_label_project skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

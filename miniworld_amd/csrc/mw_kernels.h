@@ -15,6 +15,7 @@
 #include "mw_depth.h"
 #include "mw_label.h"
 #include "mw_labelmap.h"
+#include "mw_sight.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -332,6 +333,15 @@ extern "C" __global__ void mw_labelmap_kernel(MwRayArgs a, const double *__restr
                                               const float *__restrict__ depth, const int32_t *__restrict__ code, int32_t base, const uint8_t *__restrict__ mask,
                                               const uint8_t *__restrict__ clear, uint8_t *__restrict__ plane, uint8_t *__restrict__ map, int K,
                                               int32_t *__restrict__ obj_cells, double *__restrict__ obj_pos);
+
+// grid sight (mw_sight.hip; the rule, the walk, the phases and the launch constant: mw_sight.h; the launch: mwpolicy::sight_launch).  The grid
+// (cell, gx, gz are read) and the sight (range, cos(fov / 2); no flags) travel by value; R = mwsight::reach_cells, chunks =
+// mwsight::chunks_of of them.  Grid N workgroups of MW_SIGHT_THREADS lanes; opaque and weight (or null) uint8[N][gz][gx]; cells
+// int32[N][views] with dirs float64[N][views] or null, or cells null (views = 1): the agents; env b's row of gain ([N][views]) and its
+// cells of seen (or null) where mask is null or mask[b] != 0.
+extern "C" __global__ void mw_sight_kernel(MwRayArgs a, mw_nav_params p, mwseen::Sight s, int views, int R, int chunks, const uint8_t *__restrict__ mask,
+                                           const uint8_t *__restrict__ opaque, const uint8_t *__restrict__ weight, const int32_t *__restrict__ cells,
+                                           const double *__restrict__ dirs, int32_t *__restrict__ gain, uint8_t *seen);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -13,8 +13,9 @@
 #include "mw_nav_grid.h"        // MW_NAV_GRID_THREADS, mwnav::grid_field_bytes, mwnav::grid_extra_bytes
 #include "mw_label.h"           // MW_LABEL_THREADS, MW_LABEL_CHUNK, MW_LABEL_MAX_POLYS, MW_LABEL_MAX_ENTS, mwlabel::plan_bytes
 #include "mw_labelmap.h"        // MW_LABELMAP_THREADS, MW_LABELMAP_WORD_BYTES, MW_LABELMAP_MAX_CELLS, MW_LABELMAP_MAX_IDS
+#include "mw_sight.h"           // MW_SIGHT_THREADS, mwsight::bits_bytes, weight_bytes, gain_bytes
 #include "mw_shape.h"
-#include "mw_snapframes.h"      // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
+#include "mw_snapframes.h"     // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
 
 namespace mwpolicy {
@@ -420,6 +421,17 @@ inline Launch labelmap_launch(int N, long long cells, int ids)
     const bool fits = cells >= 1 && cells <= MW_LABELMAP_MAX_CELLS && ids >= 0 && ids <= MW_LABELMAP_MAX_IDS;
     const size_t lds = fits ? ((size_t)cells + 3 * (size_t)ids) * MW_LABELMAP_WORD_BYTES : 0;
     return {(unsigned long long)N, MW_LABELMAP_THREADS, lds, fits};
+}
+
+// Grid sight (mw_grid_sight; kernel: mw_sight.hip): a workgroup of MW_SIGHT_THREADS lanes per env.  Its LDS is a bit per cell of the
+// opaque row in 32-bit words, with weights a byte per cell behind it, then a gain word per viewpoint, each rounded up to 16: 4 + 32 + 1
+// KiB at MW_NAV_MAX_CELLS and MW_SIGHT_MAX_VIEWS.  fits: a positive count of no more cells than that and 1 .. MW_SIGHT_MAX_VIEWS
+// viewpoints — the caller refuses what does not.
+inline Launch sight_launch(int N, long long cells, bool weighted, int views)
+{
+    const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS && views >= 1 && views <= MW_SIGHT_MAX_VIEWS;
+    const size_t lds = fits ? mwsight::bits_bytes(cells) + mwsight::weight_bytes(cells, weighted) + mwsight::gain_bytes(views) : 0;
+    return {(unsigned long long)N, MW_SIGHT_THREADS, lds, fits};
 }
 
 }  // namespace mwpolicy

@@ -130,6 +130,7 @@ class MwRayParams(C.Structure):
 
 
 SEEN_ENTITIES = 1                       # MW_SEEN_ENTITIES
+SIGHT_MAX_VIEWS = 256                   # MW_SIGHT_MAX_VIEWS: mw_grid_sight's viewpoints per env and call
 
 EGO_ENTITIES, EGO_NORTH = 1, 2          # MW_EGO_* flags
 EGO_WALL, EGO_ENTITY, EGO_VISIBLE = 1, 2, 4     # MW_EGO_* planes
@@ -246,6 +247,7 @@ SIGNATURES = {
     "mw_ray_cast": _sig(vp, P(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_ray_form": _sig(vp, C.c_int),
     "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
+    "mw_grid_sight": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
     "mw_depth_project": _sig(vp, P(C.c_double), vp, vp, i32, i32, vp, P(MwNavParams), i32, vp, vp, vp, vp, vp),
     "mw_label_frame": _sig(vp, vp, vp, vp, vp, vp, vp, vp, vp),        # (params: an MwLabelParams by reference)
@@ -599,6 +601,32 @@ class Engine:
         sight = (C.c_double * 2)(float(max_range), float(cos_half))
         self._check(self.lib.mw_seen_update(self.h, C.byref(params), sight, int(flags), _ptr(mask), _ptr(clear), _ptr(seen), _ptr(count), _ptr(new),
                                             _stream_ptr(self.device)), "mw_seen_update")
+
+    # -- grid sight ----------------------------------------------------------------------
+    def grid_sight(self, params: MwNavParams, max_range: float, cos_half: float, views: int, opaque, gain, weight=None, cells=None, dirs=None, seen=None,
+                   mask=None):
+        """mw_grid_sight: for the envs under `mask` (uint8[N], device; None = all) and each of `views` viewpoint cells — `cells`
+        (int32[N, views], flat j * gx + i, device) with headings `dirs` (float64[N, views]; None: all round), or None: the agent's own
+        cell and heading, views = 1 — gain (int32[N, views]) := the sum of `weight` (uint8[N, gz, gx]; None: the count) over the cells
+        seen over `opaque` (uint8[N, gz, gx]) within `max_range` metres and the cone of cos(fov / 2) = `cos_half`; every seen cell of
+        `seen` (uint8[N, gz, gx], optional) is set to 1.  One kernel on the current stream, no synchronisation, nothing of the engine
+        changes.  A wrong tensor is refused before the library is called."""
+        import torch
+        if opaque is None or gain is None:
+            raise EngineError(f"{'opaque' if opaque is None else 'gain'}: None")
+        shape, views = (self.N, int(params.gz), int(params.gx)), int(views)
+        self._shaped_tensor(opaque, "opaque", torch.uint8, shape)
+        if weight is not None:
+            self._shaped_tensor(weight, "weight", torch.uint8, shape)
+        if seen is not None:
+            self._shaped_tensor(seen, "seen", torch.uint8, shape)
+        self._dev_tensor(gain, "gain", torch.int32, self.N * views)
+        self._dev_tensor(cells, "cells", torch.int32, self.N * views)
+        self._dev_tensor(dirs, "dirs", torch.float64, self.N * views)
+        mask = self._mask_tensor(mask, optional=True)
+        sight = (C.c_double * 2)(float(max_range), float(cos_half))
+        self._check(self.lib.mw_grid_sight(self.h, C.byref(params), sight, views, _ptr(mask), _ptr(opaque), _ptr(weight), _ptr(cells), _ptr(dirs), _ptr(gain),
+                                           _ptr(seen), _stream_ptr(self.device)), "mw_grid_sight")
 
     # -- egocentric map windows ----------------------------------------------------------
     def ego_map(self, size: int, cell: float, back: float, wall_radius: float, entity_pad: float, max_range: float, cos_half: float, planes: int,

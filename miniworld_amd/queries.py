@@ -1,4 +1,4 @@
-"""The world queries of the batched env — navigation fields, explored-area maps, egocentric map windows, depth projection, label frames,
+"""The world queries of the batched env — navigation fields, explored-area maps, grid sight, egocentric map windows, depth projection, label frames,
 object maps, ray casts —, each one kernel on the device with no host value: their value classes (NavField, SeenMap, EgoWindow, DepthWindow,
 DepthMap, LabelFrame, ObjectWindow, ObjectMap) and
 `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
@@ -385,6 +385,58 @@ class WorldQueries:
         clear, mask = self._device_mask(clear, "seen_update", "clear"), self._device_mask(mask, "seen_update")
         self.engine.seen_update(seen.params, seen.max_range, seen.cos_half, self.OBSTACLES[seen.obstacles], seen.seen, seen.count, seen.new, mask, clear)
         return seen.new
+
+    # ------------------------------------------------------------------ grid sight
+    def grid_sight(self, opaque, cells=None, dirs=None, weight=None, max_range=3.0, fov=None, like=None, cell=0.25, mask=None, seen=None):
+        """What each of V candidate cells per env would see on the caller's OWN map — the gain of a next-best-view planner, where
+        seen_update() reads the simulator's walls from the agent's true position —, by one kernel (mw_grid_sight) with no host value and
+        no synchronisation: `gain`, int32[N, V], the sum of `weight` over the cells seen from each viewpoint.
+
+        opaque     uint8 or bool [N, gz, gx] device tensor: != 0 a cell that blocks the line of sight (a DepthMap's obstacle plane made
+                   contiguous, `field.field == 0xFFFF`, the caller's own raster)
+        cells      int32[N, V] device tensor of flat cell indices j * gx + i, 1 <= V <= engine.SIGHT_MAX_VIEWS; a value outside
+                   0 .. gx * gz - 1 is no viewpoint: gain 0.  None: V = 1, the agent's own cell and heading
+        dirs       float64[N, V] device tensor of headings in radians (as agent_dir), with `cells`; None: every viewpoint looks all round
+        weight     the same kind of tensor as `opaque`: what a seen cell is worth, 0 .. 255 (the unknown cells: how much of them each
+                   viewpoint would uncover).  None: the count of seen cells
+        max_range  how far a viewpoint sees, in metres, centre to centre
+        fov        the horizontal opening angle in radians about the heading, 0 < fov <= 2 pi.  None: default_fov() for the agent and
+                   with `dirs`; with `cells` and no `dirs` the cone is all round and only None or 2 pi is accepted
+        like       a NavField, SeenMap, DepthMap or ObjectMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
+                   metres per cell as in nav_field()
+        mask       uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
+        seen       uint8 or bool [N, gz, gx] device tensor: every cell any viewpoint of the env sees is set to 1; never cleared here
+        A cell is seen when its centre is within max_range and the cone of the viewpoint's centre and no opaque cell's closed square
+        meets the segment between the two (include/mwengine.h, "grid sight"): a viewpoint sees itself, and an opaque cell's face.
+        The tensors are checked and never converted.  ValueError for arguments that make no call; nothing is launched then."""
+        torch, e = self.torch, self.engine
+        params = self._map_grid("grid_sight", cell, like, (NavField, SeenMap, DepthMap, ObjectMap), "its own")
+        max_range = real("grid_sight", "max_range", max_range)
+        n = self.num_envs
+        if cells is None:
+            if dirs is not None:
+                raise ValueError("grid_sight: dirs without cells: the agent's heading is its own")
+            views = 1
+            cos_half = self._cos_half("grid_sight", fov)
+        else:
+            if not self._is_tensor(cells, (n, None), torch.int32) or not 1 <= cells.shape[1] <= eng.SIGHT_MAX_VIEWS:
+                raise ValueError(f"grid_sight: cells is a contiguous int32 tensor [{n}, 1 .. {eng.SIGHT_MAX_VIEWS}] on {e.device}")
+            views = int(cells.shape[1])
+            if dirs is None:
+                if fov is not None and fov != 2 * math.pi:
+                    raise ValueError("grid_sight: a fov needs headings: pass dirs, or no fov (viewpoints without headings look all round)")
+                cos_half = -1.0
+            else:
+                if not self._is_tensor(dirs, (n, views)):
+                    raise ValueError(f"grid_sight: dirs is a contiguous float64 tensor [{n}, {views}] on {e.device}")
+                cos_half = self._cos_half("grid_sight", fov)
+        opaque = self._cell_grid("grid_sight", "opaque", opaque, params.gz, params.gx, optional=False)
+        weight = self._cell_grid("grid_sight", "weight", weight, params.gz, params.gx)
+        seen = self._cell_grid("grid_sight", "seen", seen, params.gz, params.gx)
+        mask = self._device_mask(mask, "grid_sight")
+        gain = torch.zeros((n, views), dtype=torch.int32, device=e.device)
+        e.grid_sight(params, max_range, cos_half, views, opaque, gain, weight, cells, dirs, seen, mask)
+        return gain
 
     # ------------------------------------------------------------------ egocentric map windows
     def ego_window(self, size=33, cell=0.25, anchor="centre", frame="heading", planes=("wall", "entity", "visible"), wall_radius=None,
