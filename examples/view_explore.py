@@ -38,7 +38,8 @@ def sample_cells(mask, views, generator):
     return torch.where(top >= 0, idx, -1).to(torch.int32).contiguous()
 
 
-def run(args):
+def run(args, candidates=None):
+    """`candidates(vec, m, frontier)`: int32[N, V] flat cells (-1: none) in place of the sampled ones (examples/cluster_explore.py)"""
     import torch
     from miniworld_amd.vec_env import MiniWorldVecEnv
     n = args.envs
@@ -68,7 +69,7 @@ def run(args):
         frontier, unknown = frontier_of(m)
         opaque = m.obstacle != 0
         # the candidates, what each would see, and what the way there costs
-        cells = sample_cells(frontier, args.views, gen)
+        cells = candidates(vec, m, frontier) if candidates else sample_cells(frontier, args.views, gen)
         gain = vec.grid_sight(opaque, cells, weight=unknown, max_range=args.sight, like=m)
         pos = st["agent_pos"].clone()
         if here is None:

@@ -1141,6 +1141,41 @@ int mw_grid_sight(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are re
                   const int32_t *d_cells /* [N][views] flat j*gx+i, or NULL */, const double *d_dirs /* [N][views] or NULL */,
                   int32_t *d_gain /* [N][views] */, uint8_t *d_seen /* [N][gz][gx] or NULL */, void *stream);
 
+/* ---- grid regions ------------------------------------------------------------ */
+/* The connected regions of a byte mask on the caller's OWN map, each with its size, its centroid's sums and one cell of its own to go
+ * to: what turns a mask of frontier cells into frontiers (Yamauchi's explorer, Active Neural SLAM's planner, explore_lite), the cells a
+ * nav field can reach at all (its moves never cut a corner, so what it reaches is a 4-connected region), the specks of an obstacle
+ * plane.  It reads nothing of the simulator.  The reference has no such call.
+ *
+ * The rule.  All of it is integer and defined on cells of a nav grid (gx, gz), flat index j * gx + i.
+ *   A cell of d_member with a byte != 0 BELONGS to the mask.  Two member cells are JOINED when they are neighbours: with connectivity 4
+ *     the four cells that share an edge; with connectivity 8 also the four that share a corner, unconditionally (no "both cells between
+ *     free" rule as in a nav field's diagonal move).
+ *   A REGION is a maximal joined set; its ROOT is its lowest flat index.  The regions of at least min_cells cells are QUALIFIED and are
+ *     taken in the order of their roots (scan order, like OpenCV's connectedComponentsWithStats); the first K = max_regions of them are
+ *     LISTED.
+ *   count[env]      the number of qualified regions.  It may exceed K: then the caller knows the list is cut.
+ *   size[env][k]    the cells of the k-th qualified region, 0 for k >= count.
+ *   sum[env][k]     the sum of the rows j and the sum of the columns i of its cells, (0, 0) for none; each is at most 2^30.
+ *   cell[env][k]    its REPRESENTATIVE, -1 for none: the cell of the region that minimises
+ *                       (size * j - sum_j)^2 + (size * i - sum_i)^2
+ *                   in 64-bit integers (each term is at most 2^60); ties go to the lowest flat index.  It is always a cell OF the region:
+ *                   a frontier's centroid may lie in a wall, its representative is a frontier cell.  A row of cell is, unchanged, a row
+ *                   of mw_grid_sight's d_cells (-1 is no viewpoint there): hence MW_REGION_MAX == MW_SIGHT_MAX_VIEWS.
+ *   label[env][j][i]  0 for a cell outside the mask, k + 1 for a cell of the k-th listed region, -1 for a member cell of a region that is
+ *                   not listed (too small, or beyond K).  int16, a type torch compares.
+ * Every element of every given output row of an env under the mask is written; nothing of an env under a zero mask byte is read or
+ * written.  The results are integers the rule defines, so nothing depends on the kernel's schedule. */
+#define MW_REGION_MAX 256        /* listed regions per env and call (== MW_SIGHT_MAX_VIEWS) */
+/* One kernel, one workgroup per env, asynchronous on `stream`; it reads no host value, nothing of the world, and changes nothing in the
+ * engine.  MW_E_INVALID before anything is launched, and nothing touched: a null engine, grid, d_member, d_count, d_size or d_cell;
+ * cell <= 0, gx or gz < 1, more than MW_NAV_MAX_CELLS cells; a connectivity other than 4 or 8; min_cells < 1; max_regions outside
+ * 1 .. MW_REGION_MAX; more workgroups than a launch holds. */
+int mw_grid_regions(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */,
+                    int32_t connectivity /* 4 or 8 */, int32_t min_cells, int32_t max_regions /* K */, const uint8_t *d_mask,
+                    const uint8_t *d_member /* [N][gz][gx] */, int32_t *d_count /* [N] */, int32_t *d_size /* [N][K] */,
+                    int32_t *d_cell /* [N][K] */, int32_t *d_sum /* [N][K][2] or NULL */, int16_t *d_label /* [N][gz][gx] or NULL */,
+                    void *stream);
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.

@@ -16,6 +16,7 @@
 #include "mw_label.h"
 #include "mw_labelmap.h"
 #include "mw_sight.h"
+#include "mw_regions.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -342,6 +343,14 @@ extern "C" __global__ void mw_labelmap_kernel(MwRayArgs a, const double *__restr
 extern "C" __global__ void mw_sight_kernel(MwRayArgs a, mw_nav_params p, mwseen::Sight s, int views, int R, int chunks, const uint8_t *__restrict__ mask,
                                            const uint8_t *__restrict__ opaque, const uint8_t *__restrict__ weight, const int32_t *__restrict__ cells,
                                            const double *__restrict__ dirs, int32_t *__restrict__ gain, uint8_t *seen);
+
+// grid regions (mw_regions.hip; the rule, the arrays, the phases and the launch constant: mw_regions.h; the launch: mwpolicy::regions_launch).
+// The view is not read.  Grid N workgroups of MW_REGIONS_THREADS lanes; member uint8[N][gz][gx]; diag != 0: connectivity 8; K listed
+// regions at most; env b's element of count ([N]), its rows of size and cell ([N][K]), of sum
+// ([N][K][2], or null) and of out (int16[N][gz][gx], or null) where mask is null or mask[b] != 0.
+extern "C" __global__ void mw_regions_kernel(MwNavArgs a, int gx, int gz, int diag, int min_cells, int K, const uint8_t *__restrict__ mask,
+                                             const uint8_t *__restrict__ member, int32_t *__restrict__ count, int32_t *__restrict__ size,
+                                             int32_t *__restrict__ cell, int32_t *__restrict__ sum, int16_t *__restrict__ out);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -14,6 +14,7 @@
 #include "mw_label.h"           // MW_LABEL_THREADS, MW_LABEL_CHUNK, MW_LABEL_MAX_POLYS, MW_LABEL_MAX_ENTS, mwlabel::plan_bytes
 #include "mw_labelmap.h"        // MW_LABELMAP_THREADS, MW_LABELMAP_WORD_BYTES, MW_LABELMAP_MAX_CELLS, MW_LABELMAP_MAX_IDS
 #include "mw_sight.h"           // MW_SIGHT_THREADS, mwsight::bits_bytes, weight_bytes, gain_bytes
+#include "mw_regions.h"         // MW_REGIONS_THREADS, mwregions::label_bytes, table_bytes, scan_bytes
 #include "mw_shape.h"
 #include "mw_snapframes.h"     // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -432,6 +433,18 @@ inline Launch sight_launch(int N, long long cells, bool weighted, int views)
     const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS && views >= 1 && views <= MW_SIGHT_MAX_VIEWS;
     const size_t lds = fits ? mwsight::bits_bytes(cells) + mwsight::weight_bytes(cells, weighted) + mwsight::gain_bytes(views) : 0;
     return {(unsigned long long)N, MW_SIGHT_THREADS, lds, fits};
+}
+
+// Grid regions (mw_grid_regions; kernel: mw_regions.hip): a workgroup of MW_REGIONS_THREADS lanes per env.  Its LDS is a uint16 label and
+// a uint16 size per cell, an entry of 24 bytes per listed region and a word per lane, each rounded up to 16: 64 + 64 + 6 + 1 KiB at
+// MW_NAV_MAX_CELLS and MW_REGION_MAX, which one workgroup may hold (a CU has 160 KiB); sized by the actual cell count, so that the Maze's
+// 103 x 103 cells take 48 KiB and three workgroups share a CU.  fits: a positive count of no more cells than that and 1 .. MW_REGION_MAX
+// regions — the caller refuses what does not.
+inline Launch regions_launch(int N, long long cells, int max_regions)
+{
+    const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS && max_regions >= 1 && max_regions <= MW_REGION_MAX;
+    const size_t lds = fits ? 2 * mwregions::label_bytes(cells) + mwregions::table_bytes(max_regions) + mwregions::scan_bytes() : 0;
+    return {(unsigned long long)N, MW_REGIONS_THREADS, lds, fits};
 }
 
 }  // namespace mwpolicy

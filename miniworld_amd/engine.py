@@ -131,6 +131,7 @@ class MwRayParams(C.Structure):
 
 SEEN_ENTITIES = 1                       # MW_SEEN_ENTITIES
 SIGHT_MAX_VIEWS = 256                   # MW_SIGHT_MAX_VIEWS: mw_grid_sight's viewpoints per env and call
+REGION_MAX = 256                        # MW_REGION_MAX: mw_grid_regions' listed regions per env and call (== SIGHT_MAX_VIEWS)
 
 EGO_ENTITIES, EGO_NORTH = 1, 2          # MW_EGO_* flags
 EGO_WALL, EGO_ENTITY, EGO_VISIBLE = 1, 2, 4     # MW_EGO_* planes
@@ -246,6 +247,7 @@ SIGNATURES = {
     "mw_debug_set_nav_passes": _sig(vp, vp),
     "mw_ray_cast": _sig(vp, P(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_ray_form": _sig(vp, C.c_int),
+    "mw_grid_regions": _sig(vp, P(MwNavParams), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
     "mw_grid_sight": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
@@ -627,6 +629,31 @@ class Engine:
         sight = (C.c_double * 2)(float(max_range), float(cos_half))
         self._check(self.lib.mw_grid_sight(self.h, C.byref(params), sight, views, _ptr(mask), _ptr(opaque), _ptr(weight), _ptr(cells), _ptr(dirs), _ptr(gain),
                                            _ptr(seen), _stream_ptr(self.device)), "mw_grid_sight")
+
+    # -- grid regions --------------------------------------------------------------------
+    def grid_regions(self, params: MwNavParams, connectivity: int, min_cells: int, max_regions: int, member, count, size, cell, sum=None, label=None,
+                     mask=None):
+        """mw_grid_regions: for the envs under `mask` (uint8[N], device; None = all) the connected regions (`connectivity` 4 or 8) of
+        the bytes != 0 of `member` (uint8[N, gz, gx]): count (int32[N]) := the regions of at least `min_cells` cells, and for the first
+        K = `max_regions` of them in the order of their lowest cells size (int32[N, K]), cell (int32[N, K]: the representative, flat
+        j * gx + i, -1 for none), sum (int32[N, K, 2]: rows, columns; optional) and label (int16[N, gz, gx]: 0, k + 1 or -1; optional).
+        One kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the
+        library is called."""
+        import torch
+        for name, t in (("member", member), ("count", count), ("size", size), ("cell", cell)):
+            if t is None:
+                raise EngineError(f"{name}: None")
+        shape, K = (self.N, int(params.gz), int(params.gx)), int(max_regions)
+        self._shaped_tensor(member, "member", torch.uint8, shape)
+        if label is not None:
+            self._shaped_tensor(label, "label", torch.int16, shape)
+        self._dev_tensor(count, "count", torch.int32, self.N)
+        self._dev_tensor(size, "size", torch.int32, self.N * K)
+        self._dev_tensor(cell, "cell", torch.int32, self.N * K)
+        self._dev_tensor(sum, "sum", torch.int32, self.N * K * 2)
+        mask = self._mask_tensor(mask, optional=True)
+        self._check(self.lib.mw_grid_regions(self.h, C.byref(params), int(connectivity), int(min_cells), K, _ptr(mask), _ptr(member), _ptr(count), _ptr(size),
+                                             _ptr(cell), _ptr(sum), _ptr(label), _stream_ptr(self.device)), "mw_grid_regions")
 
     # -- egocentric map windows ----------------------------------------------------------
     def ego_map(self, size: int, cell: float, back: float, wall_radius: float, entity_pad: float, max_range: float, cos_half: float, planes: int,

@@ -1,6 +1,6 @@
-"""The world queries of the batched env — navigation fields, explored-area maps, grid sight, egocentric map windows, depth projection, label frames,
-object maps, ray casts —, each one kernel on the device with no host value: their value classes (NavField, SeenMap, EgoWindow, DepthWindow,
-DepthMap, LabelFrame, ObjectWindow, ObjectMap) and
+"""The world queries of the batched env — navigation fields, explored-area maps, grid sight, grid regions, egocentric map windows, depth projection,
+label frames, object maps, ray casts —, each one kernel on the device with no host value: their value classes (NavField, SeenMap, EgoWindow,
+DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions) and
 `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
 from __future__ import annotations
 
@@ -155,6 +155,33 @@ class ObjectMap:
     gz = property(lambda self: self.params.gz)
 
 
+class GridRegions:
+    """The connected regions of a byte mask (MiniWorldVecEnv.grid_regions), K = max_regions listed per env in the order of their lowest
+    cells: `count`, int32[N], the regions of at least min_cells cells — above K when the list is cut —, `size`, int32[N, K], their cells (0
+    for none), `cell`, int32[N, K], each one's representative as a flat index j * gx + i (-1 for none) — a cell of the region itself, and
+    a row of it is a `cells` of grid_sight() as it stands —, `sum`, int32[N, K, 2], the sums of its cells' rows and columns, and `label`,
+    int16[N, gz, gx]: 0 off the mask, k + 1 in the k-th listed region, -1 in a region that is not listed.  `sum` and `label` are None
+    when not asked for.  `params` is the grid; `connectivity` and `min_cells` say what a region is.  The tensors are the caller's."""
+
+    def __init__(self, count, size, cell, sum, label, params, connectivity, min_cells):
+        self.count, self.size, self.cell, self.sum, self.label, self.params = count, size, cell, sum, label, params
+        self.connectivity, self.min_cells = connectivity, min_cells
+
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+    max_regions = property(lambda self: int(self.size.shape[1]))
+
+    @property
+    def centroid(self):
+        """float64[N, K, 2]: each listed region's centroid (row, column) in cells, sum / size, NaN for none (a new tensor, made on the
+        device); None without `sum`"""
+        if self.sum is None:
+            return None
+        size = self.size.double().unsqueeze(-1)
+        return (self.sum.double() / size).masked_fill_(size == 0, float("nan"))
+
+
+assert eng.SIGHT_MAX_VIEWS == eng.REGION_MAX        # (a row of GridRegions.cell is a row of grid_sight's cells)
 assert eng.NAV_ENTITIES == eng.RAY_ENTITIES == eng.SEEN_ENTITIES == eng.EGO_ENTITIES      # (one table serves the four calls)
 
 
@@ -437,6 +464,52 @@ class WorldQueries:
         gain = torch.zeros((n, views), dtype=torch.int32, device=e.device)
         e.grid_sight(params, max_range, cos_half, views, opaque, gain, weight, cells, dirs, seen, mask)
         return gain
+
+    # ------------------------------------------------------------------ grid regions
+    def grid_regions(self, member, connectivity=4, min_cells=1, max_regions=32, like=None, cell=0.25, mask=None, labels=False, sums=True, into=None):
+        """The connected regions of a byte mask on the caller's OWN map — a frontier mask's clusters, the cells a field reaches, an
+        obstacle plane's specks —, each with its size and one cell of its own to go to, by one kernel (mw_grid_regions) with no host
+        value and no synchronisation: a GridRegions.
+
+        member        uint8 or bool [N, gz, gx] device tensor: != 0 a cell of the mask
+        connectivity  4: cells that share an edge are joined; 8: cells that share a corner too
+        min_cells     regions of fewer cells are not counted and not listed (their cells' label is -1)
+        max_regions   K, 1 .. engine.REGION_MAX: the regions listed per env, in the order of their lowest cells; `count` may exceed it
+        like          a NavField, SeenMap, DepthMap or ObjectMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
+                      metres per cell as in nav_field()
+        mask          uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
+        labels        with the per-cell `label` plane
+        sums          with the per-region `sum` (and `centroid`)
+        into          a GridRegions of an earlier call to write into: its grid, connectivity, min_cells, max_regions and optional
+                      tensors are used; pass only member and mask
+        The representative is the region's cell nearest its centroid, ties to the lowest index (include/mwengine.h, "grid regions").
+        The tensors are checked and never converted.  ValueError for arguments that make no call; nothing is launched then."""
+        torch, e = self.torch, self.engine
+        n = self.num_envs
+        if into is not None:
+            if not isinstance(into, GridRegions):
+                raise ValueError("grid_regions: `into` must be a GridRegions")
+            if like is not None or labels is not False or sums is not True or (connectivity, min_cells, max_regions, cell) != (4, 1, 32, 0.25):
+                raise ValueError("grid_regions: with `into` the record's own grid and parameters are used: pass only member and mask")
+            out, params = into, into.params
+        else:
+            params = self._map_grid("grid_regions", cell, like, (NavField, SeenMap, DepthMap, ObjectMap), "its own")
+            if connectivity not in (4, 8) or isinstance(connectivity, bool):
+                raise ValueError(f"grid_regions: connectivity {connectivity!r}; have 4 and 8")
+            min_cells = integer("grid_regions", "min_cells", min_cells, 1, eng.NAV_MAX_CELLS)
+            K = integer("grid_regions", "max_regions", max_regions, 1, eng.REGION_MAX)
+            for name, v in (("labels", labels), ("sums", sums)):
+                if not isinstance(v, bool):
+                    raise ValueError(f"grid_regions: {name} must be True or False, not {v!r}")
+        member = self._cell_grid("grid_regions", "member", member, params.gz, params.gx, optional=False)
+        mask = self._device_mask(mask, "grid_regions")
+        if into is None:
+            new = lambda shape, dtype, fill: torch.full(shape, fill, dtype=dtype, device=e.device)
+            out = GridRegions(new((n,), torch.int32, 0), new((n, K), torch.int32, 0), new((n, K), torch.int32, -1),
+                              new((n, K, 2), torch.int32, 0) if sums else None, new((n, params.gz, params.gx), torch.int16, 0) if labels else None,
+                              params, int(connectivity), min_cells)
+        e.grid_regions(params, out.connectivity, out.min_cells, out.max_regions, member, out.count, out.size, out.cell, out.sum, out.label, mask)
+        return out
 
     # ------------------------------------------------------------------ egocentric map windows
     def ego_window(self, size=33, cell=0.25, anchor="centre", frame="heading", planes=("wall", "entity", "visible"), wall_radius=None,
