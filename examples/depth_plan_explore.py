@@ -24,7 +24,7 @@ import time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from expert_nav import TURN_LEFT, expert  # noqa: E402
+from expert_nav import FORWARD, TURN_LEFT, expert  # noqa: E402
 from explore_frontier import unblocked_of  # noqa: E402
 
 
@@ -40,7 +40,9 @@ def frontier_of(m):
     return (m.free == 1) & beside, unknown
 
 
-def run(args):
+def run(args, ramp=None, moves=None):
+    """`ramp(vec, m)`: a uint8[N, gz, gx] cost plane that goes to grid_field as `extra` in place of the unknown cells' (examples/
+    clear_plan_explore.py); `moves`: a dict that gets "forward", the forward moves of live envs, and "blocked", those that moved nothing"""
     import torch
     from miniworld_amd.vec_env import MiniWorldVecEnv
     n = args.envs
@@ -63,13 +65,18 @@ def run(args):
     for t in range(args.steps):
         st = vec.state(("agent_pos", "agent_dir"))
         frontier, unknown = frontier_of(m)
-        extra = unknown.to(torch.uint8) * args.unknown if args.unknown else None
+        extra = ramp(vec, m) if ramp else unknown.to(torch.uint8) * args.unknown if args.unknown else None
         plan = vec.grid_field(m.obstacle != 0, frontier, extra=extra, like=m) if plan is None else vec.grid_field(m.obstacle != 0, frontier, extra=extra, into=plan)
         q = vec.nav_query(plan)
         act = expert(st["agent_pos"], st["agent_dir"], q["waypoint"], turn_step)
         act = torch.where(q["cost"] > 0, act, TURN_LEFT).to(torch.int32)
+        before = st["agent_pos"].clone() if moves is not None else None      # (a state view is the live array)
         _, _, term, trunc = vec.step(act)
         done = (term | trunc) != 0
+        if moves is not None:
+            ahead = (act == FORWARD) & ~done
+            stuck = ahead & (vec.state(("agent_pos",))["agent_pos"] == before).all(dim=1)
+            moves["forward"], moves["blocked"] = moves.get("forward", 0) + ahead.sum(), moves.get("blocked", 0) + stuck.sum()
         free = unblocked_of(yard)
         share = ((score.seen == 1) & free).sum((1, 2)).to(torch.float64) / free.sum((1, 2)).clamp(min=1).to(torch.float64)
         early = done & ~counted

@@ -1176,6 +1176,45 @@ int mw_grid_regions(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are 
                     const uint8_t *d_member /* [N][gz][gx] */, int32_t *d_count /* [N] */, int32_t *d_size /* [N][K] */,
                     int32_t *d_cell /* [N][K] */, int32_t *d_sum /* [N][K][2] or NULL */, int16_t *d_label /* [N][gz][gx] or NULL */,
                     void *stream);
+
+/* ---- grid clearance ---------------------------------------------------------- */
+/* How far every cell of the caller's OWN map is from the nearest marked cell — the exact Euclidean distance transform of a byte mask,
+ * squared and in cells: the inflation layer of a costmap (ROS costmap_2d), the speed map of a fast-marching planner (Active Neural
+ * SLAM), the repulsive term of a potential field, the ESDF a map-based MPC reads; of other masks the distance to the nearest frontier,
+ * seen or object cell.  mw_nav_build_grid's margin knows one radius, blocked or not, up to MW_NAV_MAX_INFLATE cells; this call gives the
+ * distance itself and, through cost bands, a row of that call's d_extra.  It reads nothing of the simulator.  The reference has no
+ * such call.
+ *
+ * The rule.  All of it is integer and defined on cells of a nav grid (gx, gz), flat index j * gx + i.
+ *   A cell of d_marked with a byte != 0 is MARKED.
+ *   dist2[env][j][i]    the least (j - j')^2 + (i - i')^2 over the marked cells (j', i') of the env: 0 on a marked cell; MW_CLEAR_NONE
+ *                       everywhere in an env with no marked cell, whatever the limit.  The largest real value is
+ *                       (gz - 1)^2 + (gx - 1)^2 < 2^30.
+ *   nearest[env][j][i]  the flat index j' * gx + i' of a marked cell at that distance; ties go to the lowest flat index; -1 where dist2
+ *                       holds a sentinel.
+ *   limit = L > 0       a cell whose dist2 > L^2 holds MW_CLEAR_FAR and nearest -1; every other cell holds its exact value.  This is
+ *                       what bounds the work on a nearly empty map.  0: no limit.
+ *   cost[env][j][i]     with B = bands pairs (thr_b, cost_b) in host_bands, thr strictly ascending: cost_b of the first band with
+ *                       dist2 <= thr_b, 0 where no band applies — the sentinels are above every threshold.  A row of it is a row of
+ *                       mw_nav_build_grid's d_extra as it stands.
+ * Metres are the caller's: the threshold of a radius r is the largest integer t with sqrt((double)t) * cell < r (-1: none), which is
+ * mw_nav_build_grid's own inflation test, so that dist2 == 0 || dist2 <= t are bit for bit the cells that call blocks at margin r.
+ * Thresholds ascend strictly here, so a caller that starts from radii leaves out a radius whose threshold is -1 or is not above the
+ * one before: no distance lies in such a band (vec.grid_clearance does so).
+ * Every element of every given output row of an env under the mask is written; nothing of an env under a zero mask byte is read or
+ * written.  The results are integers the rule defines, so nothing depends on the kernel's schedule. */
+#define MW_CLEAR_NONE 0x7FFFFFFF /* dist2 in an env without a marked cell */
+#define MW_CLEAR_FAR 0x7FFFFFFE  /* dist2 of a cell beyond the limit */
+#define MW_CLEAR_MAX_BANDS 8     /* cost bands per call */
+/* One kernel, one workgroup per env, asynchronous on `stream`; host_bands is read during the call and passed by value; it reads no other
+ * host value, nothing of the world, and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched:
+ * a null engine, grid, d_marked or d_dist2; cell <= 0, gx or gz < 1, more than MW_NAV_MAX_CELLS cells; limit < 0; bands outside
+ * 0 .. MW_CLEAR_MAX_BANDS, or bands > 0 and a null host_bands; a threshold that is negative or not above the one before; a cost outside
+ * 0 .. 255; d_cost without bands or bands without d_cost; more workgroups than a launch holds. */
+int mw_grid_clearance(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */, int32_t limit /* cells; 0: none */,
+                      const int32_t *host_bands /* [bands][2]: thr, cost; NULL with bands == 0 */, int32_t bands, const uint8_t *d_mask,
+                      const uint8_t *d_marked /* [N][gz][gx] */, int32_t *d_dist2 /* [N][gz][gx] */, int32_t *d_nearest /* [N][gz][gx] or NULL */,
+                      uint8_t *d_cost /* [N][gz][gx]: with bands > 0, else NULL */, void *stream);
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.

@@ -17,6 +17,7 @@
 #include "mw_labelmap.h"
 #include "mw_sight.h"
 #include "mw_regions.h"
+#include "mw_clear.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -351,6 +352,14 @@ extern "C" __global__ void mw_sight_kernel(MwRayArgs a, mw_nav_params p, mwseen:
 extern "C" __global__ void mw_regions_kernel(MwNavArgs a, int gx, int gz, int diag, int min_cells, int K, const uint8_t *__restrict__ mask,
                                              const uint8_t *__restrict__ member, int32_t *__restrict__ count, int32_t *__restrict__ size,
                                              int32_t *__restrict__ cell, int32_t *__restrict__ sum, int16_t *__restrict__ out);
+
+// grid clearance (mw_clear.hip; the rule, the array, the phases, the launch constant and the bands' struct MwClearBands: mw_clear.h; the
+// launch: mwpolicy::clear_launch).  The view is not read.  Grid N workgroups of MW_CLEAR_THREADS lanes; marked uint8[N][gz][gx]; limit
+// 0 .. 32767 cells, 0: none; env b's rows of dist2 (int32[N][gz][gx]), of nearest (the same, or null) and of cost (uint8[N][gz][gx], or
+// null) where mask is null or mask[b] != 0.
+extern "C" __global__ void mw_clear_kernel(MwNavArgs a, int gx, int gz, int limit, MwClearBands bands, const uint8_t *__restrict__ mask,
+                                           const uint8_t *__restrict__ marked, int32_t *__restrict__ dist2, int32_t *__restrict__ nearest,
+                                           uint8_t *__restrict__ cost);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -15,6 +15,7 @@
 #include "mw_labelmap.h"        // MW_LABELMAP_THREADS, MW_LABELMAP_WORD_BYTES, MW_LABELMAP_MAX_CELLS, MW_LABELMAP_MAX_IDS
 #include "mw_sight.h"           // MW_SIGHT_THREADS, mwsight::bits_bytes, weight_bytes, gain_bytes
 #include "mw_regions.h"         // MW_REGIONS_THREADS, mwregions::label_bytes, table_bytes, scan_bytes
+#include "mw_clear.h"           // MW_CLEAR_THREADS, mwclear::off_bytes
 #include "mw_shape.h"
 #include "mw_snapframes.h"     // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -445,6 +446,15 @@ inline Launch regions_launch(int N, long long cells, int max_regions)
     const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS && max_regions >= 1 && max_regions <= MW_REGION_MAX;
     const size_t lds = fits ? 2 * mwregions::label_bytes(cells) + mwregions::table_bytes(max_regions) + mwregions::scan_bytes() : 0;
     return {(unsigned long long)N, MW_REGIONS_THREADS, lds, fits};
+}
+
+// Grid clearance (mw_grid_clearance; kernel: mw_clear.hip): a workgroup of MW_CLEAR_THREADS lanes per env.  Its LDS is one int16 per cell,
+// rounded up to 16: 64 KiB at MW_NAV_MAX_CELLS; sized by the actual cell count, so that the Maze's 103 x 103 cells take 21 KiB and seven
+// workgroups share a CU's 160 KiB.  fits: a positive count of no more cells than that — the caller refuses what does not.
+inline Launch clear_launch(int N, long long cells)
+{
+    const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS;
+    return {(unsigned long long)N, MW_CLEAR_THREADS, fits ? mwclear::off_bytes(cells) : 0, fits};
 }
 
 }  // namespace mwpolicy

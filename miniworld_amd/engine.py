@@ -132,6 +132,8 @@ class MwRayParams(C.Structure):
 SEEN_ENTITIES = 1                       # MW_SEEN_ENTITIES
 SIGHT_MAX_VIEWS = 256                   # MW_SIGHT_MAX_VIEWS: mw_grid_sight's viewpoints per env and call
 REGION_MAX = 256                        # MW_REGION_MAX: mw_grid_regions' listed regions per env and call (== SIGHT_MAX_VIEWS)
+CLEAR_NONE, CLEAR_FAR = 0x7FFFFFFF, 0x7FFFFFFE      # MW_CLEAR_NONE, MW_CLEAR_FAR: mw_grid_clearance's dist2 without a marked cell, beyond the limit
+CLEAR_MAX_BANDS = 8                     # MW_CLEAR_MAX_BANDS: mw_grid_clearance's cost bands per call
 
 EGO_ENTITIES, EGO_NORTH = 1, 2          # MW_EGO_* flags
 EGO_WALL, EGO_ENTITY, EGO_VISIBLE = 1, 2, 4     # MW_EGO_* planes
@@ -248,6 +250,7 @@ SIGNATURES = {
     "mw_ray_cast": _sig(vp, P(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_ray_form": _sig(vp, C.c_int),
     "mw_grid_regions": _sig(vp, P(MwNavParams), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp),
+    "mw_grid_clearance": _sig(vp, P(MwNavParams), i32, P(i32), i32, vp, vp, vp, vp, vp, vp),
     "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
     "mw_grid_sight": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
@@ -654,6 +657,30 @@ class Engine:
         mask = self._mask_tensor(mask, optional=True)
         self._check(self.lib.mw_grid_regions(self.h, C.byref(params), int(connectivity), int(min_cells), K, _ptr(mask), _ptr(member), _ptr(count), _ptr(size),
                                              _ptr(cell), _ptr(sum), _ptr(label), _stream_ptr(self.device)), "mw_grid_regions")
+
+    # -- grid clearance ------------------------------------------------------------------
+    def grid_clearance(self, params: MwNavParams, limit: int, bands, marked, dist2, nearest=None, cost=None, mask=None):
+        """mw_grid_clearance: for the envs under `mask` (uint8[N], device; None = all) dist2 (int32[N, gz, gx]) := every cell's least
+        squared distance in cells to a byte != 0 of `marked` (uint8[N, gz, gx]) — CLEAR_NONE in an env without one, CLEAR_FAR beyond
+        `limit` cells (0: no limit) —, nearest (int32[N, gz, gx], optional) := that cell's flat index j * gx + i, the lowest at a tie, -1
+        at a sentinel, and cost (uint8[N, gz, gx]: with bands, and only then) := the cost of the first of `bands`, a sequence of
+        (threshold, cost) integer pairs with ascending thresholds, whose threshold is at least dist2, 0 with none.  One kernel on the
+        current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the library is called."""
+        import torch
+        if marked is None or dist2 is None:
+            raise EngineError(f"{'marked' if marked is None else 'dist2'}: None")
+        shape = (self.N, int(params.gz), int(params.gx))
+        self._shaped_tensor(marked, "marked", torch.uint8, shape)
+        self._shaped_tensor(dist2, "dist2", torch.int32, shape)
+        if nearest is not None:
+            self._shaped_tensor(nearest, "nearest", torch.int32, shape)
+        if cost is not None:
+            self._shaped_tensor(cost, "cost", torch.uint8, shape)
+        mask = self._mask_tensor(mask, optional=True)
+        flat = [int(v) for pair in bands for v in pair]
+        pairs = (C.c_int32 * len(flat))(*flat) if flat else None
+        self._check(self.lib.mw_grid_clearance(self.h, C.byref(params), int(limit), pairs, len(flat) // 2, _ptr(mask), _ptr(marked), _ptr(dist2),
+                                               _ptr(nearest), _ptr(cost), _stream_ptr(self.device)), "mw_grid_clearance")
 
     # -- egocentric map windows ----------------------------------------------------------
     def ego_map(self, size: int, cell: float, back: float, wall_radius: float, entity_pad: float, max_range: float, cos_half: float, planes: int,

@@ -1,6 +1,6 @@
-"""The world queries of the batched env — navigation fields, explored-area maps, grid sight, grid regions, egocentric map windows, depth projection,
-label frames, object maps, ray casts —, each one kernel on the device with no host value: their value classes (NavField, SeenMap, EgoWindow,
-DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions) and
+"""The world queries of the batched env — navigation fields, explored-area maps, grid sight, grid regions, grid clearance, egocentric map windows,
+depth projection, label frames, object maps, ray casts —, each one kernel on the device with no host value: their value classes (NavField, SeenMap,
+EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance) and
 `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
 from __future__ import annotations
 
@@ -181,6 +181,40 @@ class GridRegions:
         return (self.sum.double() / size).masked_fill_(size == 0, float("nan"))
 
 
+class GridClearance:
+    """Every cell's distance to the nearest marked cell of a byte mask (MiniWorldVecEnv.grid_clearance): `dist2`, int32[N, gz, gx], the
+    squared distance in cells — 0 on a marked cell, engine.CLEAR_NONE throughout an env without one, engine.CLEAR_FAR beyond the limit —,
+    `nearest`, int32[N, gz, gx], that marked cell's flat index j * gx + i, the lowest at a tie, -1 at a sentinel, and `cost`,
+    uint8[N, gz, gx], the cost of the first of `bands` — (threshold, cost) integer pairs, thresholds ascending — whose threshold is at
+    least dist2, 0 with none: a row of it is an `extra` of grid_field() as it stands.  `nearest` and `cost` are None when not asked for.
+    `params` is the grid, `limit` the limit in cells (0: none).  The tensors are the caller's."""
+
+    def __init__(self, dist2, nearest, cost, params, bands, limit):
+        self.dist2, self.nearest, self.cost, self.params, self.bands, self.limit = dist2, nearest, cost, params, bands, limit
+
+    cell = property(lambda self: self.params.cell)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+
+    def metres(self):
+        """float64[N, gz, gx]: sqrt(dist2) * cell, inf at the sentinels (a new tensor, made on the device)"""
+        return (self.dist2.double().sqrt() * self.cell).masked_fill_(self.dist2 >= eng.CLEAR_FAR, math.inf)
+
+    @staticmethod
+    def threshold(r, cell=0.25):
+        """the largest integer t with sqrt(float64(t)) * cell < r, -1 if there is none: grid_field's inflation test, strict and in
+        float64, so that (dist2 == 0) | (dist2 <= threshold(r)) are the cells grid_field(inflate=r) blocks.  At most 2^30, which is
+        above every dist2 of a grid."""
+        r, cell = real("GridClearance.threshold", "r", r, lo_open=False), real("GridClearance.threshold", "cell", cell)
+        inside = lambda t: math.sqrt(float(t)) * cell < r
+        t = int(min(r / cell, 32768.0) ** 2)        # (clamped first: the square of a huge ratio is no float)
+        while t >= 0 and not inside(t):
+            t -= 1
+        while t < 2 ** 30 and inside(t + 1):
+            t += 1
+        return t
+
+
 assert eng.SIGHT_MAX_VIEWS == eng.REGION_MAX        # (a row of GridRegions.cell is a row of grid_sight's cells)
 assert eng.NAV_ENTITIES == eng.RAY_ENTITIES == eng.SEEN_ENTITIES == eng.EGO_ENTITIES      # (one table serves the four calls)
 
@@ -211,7 +245,7 @@ class WorldQueries:
                 raise ValueError(f"{where}: `like` must be {' or '.join('a ' + k.__name__ for k in kinds)}")
             if cell != 0.25:
                 raise ValueError(f"{where}: with `like` {own} grid is used: pass no cell")
-            cell, gx, gz = like.cell, like.gx, like.gz
+            cell, gx, gz = like.params.cell, like.gx, like.gz       # (a GridRegions' `cell` is its representatives)
         else:
             cell, gx, gz = self._grid(where, cell)
         return eng.MwNavParams(float(cell), 0.0, 0.0, int(gx), int(gz), 0, 0)
@@ -509,6 +543,72 @@ class WorldQueries:
                               new((n, K, 2), torch.int32, 0) if sums else None, new((n, params.gz, params.gx), torch.int16, 0) if labels else None,
                               params, int(connectivity), min_cells)
         e.grid_regions(params, out.connectivity, out.min_cells, out.max_regions, member, out.count, out.size, out.cell, out.sum, out.label, mask)
+        return out
+
+    # ------------------------------------------------------------------ grid clearance
+    def grid_clearance(self, marked, radii=None, costs=None, limit=None, nearest=False, like=None, cell=0.25, mask=None, into=None):
+        """How far every cell of the caller's OWN map is from the nearest marked cell — the exact Euclidean distance transform of an
+        obstacle plane, a frontier mask, a seen map —, by one kernel (mw_grid_clearance) with no host value and no synchronisation: a
+        GridClearance.
+
+        marked   uint8 or bool [N, gz, gx] device tensor: != 0 a marked cell
+        radii    metres, ascending, at most engine.CLEAR_MAX_BANDS, with `costs`, as many integers 0 .. 255: a cell closer than radii[b]
+                 to a marked cell's centre, and not closer than radii[b - 1], gets costs[b] in `cost`; 0 from the last radius on.  A
+                 radius becomes GridClearance.threshold(radius, cell); a band that holds no distance — its threshold is -1, or not
+                 above the one before — is dropped from `bands`.  If that leaves none, `cost` is a plane of zeros the call does not
+                 write.
+        limit    metres: cells farther than the smallest L cells with L * cell >= limit hold engine.CLEAR_FAR, nearest -1, cost 0, and
+                 no scan goes farther: what bounds the work on a nearly empty map.  None: no limit.
+        nearest  with the per-cell `nearest` plane
+        like     a NavField, SeenMap, DepthMap, ObjectMap or GridRegions whose grid (cell, gx, gz) is adopted; pass no cell then.  Else
+                 `cell` metres per cell as in nav_field()
+        mask     uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
+        into     a GridClearance of an earlier call to write into: its grid, bands, limit and optional tensors are used; pass only
+                 marked and mask
+        The rule in full: include/mwengine.h, "grid clearance".  The tensors are checked and never converted.  ValueError for arguments
+        that make no call; nothing is launched then."""
+        torch, e = self.torch, self.engine
+        where = "grid_clearance"
+        if into is not None:
+            if not isinstance(into, GridClearance):
+                raise ValueError(f"{where}: `into` must be a GridClearance")
+            if radii is not None or costs is not None or limit is not None or nearest is not False or like is not None or cell != 0.25:
+                raise ValueError(f"{where}: with `into` the record's own grid and parameters are used: pass only marked and mask")
+            out, params = into, into.params
+        else:
+            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions), "its own")
+            if not isinstance(nearest, bool):
+                raise ValueError(f"{where}: nearest must be True or False, not {nearest!r}")
+            if (radii is None) != (costs is None):
+                raise ValueError(f"{where}: radii and costs go together")
+            bands = []
+            if radii is not None:
+                if isinstance(radii, (str, bytes)) or isinstance(costs, (str, bytes)) or not all(hasattr(v, "__len__") for v in (radii, costs)):
+                    raise ValueError(f"{where}: radii and costs are sequences")
+                if len(radii) != len(costs) or not 1 <= len(radii) <= eng.CLEAR_MAX_BANDS:
+                    raise ValueError(f"{where}: {len(radii)} radii and {len(costs)} costs: as many of each, 1 .. {eng.CLEAR_MAX_BANDS}")
+                radii = [real(where, "a radius", r, lo_open=False) for r in radii]
+                if any(b <= a for a, b in zip(radii, radii[1:])):
+                    raise ValueError(f"{where}: radii {radii!r} do not ascend")
+                for r, c in zip(radii, costs):
+                    t, c = GridClearance.threshold(r, params.cell), integer(where, "a cost", c, 0, 255)
+                    if t > (bands[-1][0] if bands else -1):         # (else: no distance lies in the band)
+                        bands.append((t, c))
+            cells = 0
+            if limit is not None:
+                limit = real(where, "limit", limit)
+                cells = int(min(math.ceil(limit / params.cell), 32768.0))       # (from 32768 cells on the call knows no limit: no search)
+                while cells < 32768 and cells * params.cell < limit:
+                    cells += 1
+                while 1 < cells < 32768 and (cells - 1) * params.cell >= limit:
+                    cells -= 1
+        marked = self._cell_grid(where, "marked", marked, params.gz, params.gx, optional=False)
+        mask = self._device_mask(mask, where)
+        if into is None:
+            new = lambda dtype, fill: torch.full((self.num_envs, params.gz, params.gx), fill, dtype=dtype, device=e.device)
+            out = GridClearance(new(torch.int32, eng.CLEAR_NONE), new(torch.int32, -1) if nearest else None, new(torch.uint8, 0) if radii is not None else None,
+                                params, tuple(bands), cells)
+        e.grid_clearance(params, out.limit, out.bands, marked, out.dist2, out.nearest, out.cost if out.bands else None, mask)
         return out
 
     # ------------------------------------------------------------------ egocentric map windows
