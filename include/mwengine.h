@@ -1215,6 +1215,51 @@ int mw_grid_clearance(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz ar
                       const int32_t *host_bands /* [bands][2]: thr, cost; NULL with bands == 0 */, int32_t bands, const uint8_t *d_mask,
                       const uint8_t *d_marked /* [N][gz][gx] */, int32_t *d_dist2 /* [N][gz][gx] */, int32_t *d_nearest /* [N][gz][gx] or NULL */,
                       uint8_t *d_cost /* [N][gz][gx]: with bands > 0, else NULL */, void *stream);
+
+/* ---- scan maps --------------------------------------------------------------- */
+/* The map a range scanner gives — the classic occupancy-grid mapper (gmapping, Hector, Cartographer 2D, a "lidar to costmap" layer): the
+ * cells a beam passes through become free, the cell it ends in becomes an obstacle.  The beams are mw_ray_cast's d_t and d_dir_out as
+ * they stand (vec.lidar()), or the caller's own: with noise, with dropped beams, from a pose estimate instead of the true pose — which
+ * the privileged mw_seen_update cannot express.  It needs no frame: a policy that never draws one can map, plan on its own map
+ * (mw_nav_build_grid: the obstacle plane is a d_blocked; mw_grid_sight: a d_opaque; mw_grid_clearance: a d_marked) and explore.  The
+ * reference has no such call.
+ *
+ * The rule.  All arithmetic is float64, only + - * / and floor, uncontracted, in exactly this order.  Per env: (ox, oz) = d_origin's x and
+ * z (y is not read) or, with a null d_origin, the agent's position the device holds now; min_x, min_z the env's own extent, cell, gx, gz
+ * the grid's, as for mw_depth_project's map; max_range = host_range[0].  Per beam k with t = d_t[i][k], (dx, dz) = d_dir[i][k], of any length:
+ *   u0 = (ox - min_x) / cell;  w0 = (oz - min_z) / cell;  gu = dx / cell;  gw = dz / cell
+ *   hit = t < max_range;  e = hit ? t : max_range
+ *   u1 = u0 + e * gu;  w1 = w0 + e * gw
+ *   the beam is dropped unless t >= 0 (a NaN fails) and u0, w0, u1, w1 are all finite and below 2^30 in magnitude
+ * The cells of a kept beam, in closed form — nothing walks along it:
+ *   the start cell (floor(w0), floor(u0)), as (row, column)
+ *   for every x line L the beam crosses — gu > 0: L = floor(u0) + 1 .. floor(u1); gu < 0: L = floor(u1) + 1 .. floor(u0); gu == 0: none;
+ *   L clipped to the grid's own lines 0 .. gx first — the cell entered there: column gu > 0 ? L : L - 1, row
+ *   floor(w0 + ((double)L - u0) / gu * gw)
+ *   the mirrored cells for the z lines: L from w0, w1 and gw, clipped to 0 .. gz; row gw > 0 ? L : L - 1, column
+ *   floor(u0 + ((double)L - w0) / gw * gu)
+ *   so a beam has at most gx + gz + 3 cells.  A cell counts only if row >= 0 && row < gz && column >= 0 && column < gx, compared as
+ *   doubles before any conversion.
+ * The end cell of a kept beam is (floor(w1), floor(u1)), under the same test.  The call's OBSTACLE set is the end cells of its kept beams
+ * with hit; its FREE set is every cell of every kept beam that is not in that obstacle set.  A beam that passes exactly through a corner
+ * contributes what the formulas give, one or both of the neighbouring cells.
+ * d_map is uint8[N][2][gz][gx], plane 0 free, plane 1 obstacle, and the target follows mw_depth_project's map word for word: for every env i
+ * with d_mask[i] != 0 (or a null d_mask): if d_clear[i] != 0 its two planes are zeroed and its counts set to 0 first; then a byte that is 0
+ * becomes 1 where the call's set holds the cell; no call ever clears a byte except through d_clear — an obstacle byte a later scan sees
+ * through stays.  d_new[i][k] gets the cells of plane k that went 0 -> 1 in this call, d_count[i][k] becomes (cleared ? 0 : d_count[i][k]) +
+ * d_new[i][k].  An env whose extent the grid does not cover (as for mw_nav_build) gets its planes zeroed, counts 0 and new 0, and sets
+ * the status bit mw_depth_project sets: the next mw_check reports it as MW_E_INVALID, once.  Rows of envs under a zero mask byte are
+ * neither read nor written: the mask wins over clear.  Both sets are unions, so nothing depends on the kernel's schedule.
+ *
+ * One kernel, one workgroup per env, asynchronous on `stream`; it reads no host value except host_range (during the call), reads live arrays only
+ * and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched: a null engine, grid, host_range, d_t,
+ * d_dir, d_map or d_count; a grid mw_nav_build would refuse (cell <= 0 or not finite, gx or gz < 1, more than MW_NAV_MAX_CELLS cells); R outside
+ * 1 .. MW_RAY_MAX; a max_range that is not > 0 and finite; more workgroups than a launch holds. */
+int mw_scan_project(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */,
+                    const double *host_range /* [1] on the host: max_range */, int32_t R,
+                    const double *d_t /* [N][R] */, const double *d_dir /* [N][R][2]: dx, dz */, const double *d_origin /* [N][3] or NULL = the agents */,
+                    const uint8_t *d_mask, const uint8_t *d_clear /* or NULL */, uint8_t *d_map /* [N][2][gz][gx] */, int32_t *d_count /* [N][2] */,
+                    int32_t *d_new /* [N][2] or NULL */, void *stream);
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.
@@ -1226,7 +1271,7 @@ int mw_grid_clearance(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz ar
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project or mw_label_project skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project or mw_label_project skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

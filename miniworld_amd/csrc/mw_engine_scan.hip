@@ -1,0 +1,30 @@
+// mwengine host runtime: scan maps (mw_scan_project; kernel: mw_scan.hip, rule, arrays and phases: mw_scan.h, launch: mw_policy.h).
+//
+// The call does not wait for the Maze's side-stream refills: mw_engine.h, at world_view().  (Of the world it reads each env's extent
+// and, without d_origin, the agent's position.)
+#include "mw_engine.h"
+#include "mw_policy.h"
+
+using namespace mwhost;
+
+extern "C" {
+
+int mw_scan_project(mw_engine *e, const mw_nav_params *grid, const double *host_range, int32_t R, const double *d_t, const double *d_dir, const double *d_origin,
+                    const uint8_t *d_mask, const uint8_t *d_clear, uint8_t *d_map, int32_t *d_count, int32_t *d_new, void *stream)
+{
+    const char *what = "mw_scan_project";
+    if (!e) return MW_E_INVALID;
+    if (!grid || !host_range || !d_t || !d_dir || !d_map || !d_count)
+        return fail(e, MW_E_INVALID, "%s: %s is null", what, !grid ? "grid" : !host_range ? "host_range" : !d_t ? "d_t" : !d_dir ? "d_dir" : !d_map ? "d_map" : "d_count");
+    const double max_range = host_range[0];
+    if (const int rc = grid_check(e, what, grid)) return rc;
+    if (!std::isfinite(grid->cell)) return fail(e, MW_E_INVALID, "%s: cell %g is not finite", what, grid->cell);
+    if (R < 1 || R > MW_RAY_MAX) return fail(e, MW_E_INVALID, "%s: %d beams per env outside 1 .. %d", what, (int)R, MW_RAY_MAX);
+    if (const int rc = positive_check(e, what, "max_range", max_range)) return rc;
+    const mwpolicy::Launch l = mwpolicy::scan_launch(e->cfg.num_envs, (long long)grid->gx * grid->gz, R);
+    if (!l.fits) return fail(e, MW_E_INVALID, "%s: %d x %d cells and %d beams do not fit", what, (int)grid->gx, (int)grid->gz, (int)R);
+    return launch_query(e, what, mw_scan_kernel, world_view, l.grid, l.threads, l.lds, &e->scan_lds_set, stream, *grid, max_range, (int)R, d_t, d_dir, d_origin,
+                        d_mask, d_clear, d_map, d_count, d_new);
+}
+
+}  // extern "C"

@@ -18,6 +18,7 @@
 #include "mw_sight.h"
 #include "mw_regions.h"
 #include "mw_clear.h"
+#include "mw_scan.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -360,6 +361,15 @@ extern "C" __global__ void mw_regions_kernel(MwNavArgs a, int gx, int gz, int di
 extern "C" __global__ void mw_clear_kernel(MwNavArgs a, int gx, int gz, int limit, MwClearBands bands, const uint8_t *__restrict__ mask,
                                            const uint8_t *__restrict__ marked, int32_t *__restrict__ dist2, int32_t *__restrict__ nearest,
                                            uint8_t *__restrict__ cost);
+
+// scan maps (mw_scan.hip; the rule, the arrays, the phases and the launch constant: mw_scan.h; the launch: mwpolicy::scan_launch).  Of the
+// view the extent and, with a null origin, ax / az are read.  Grid N workgroups of MW_SCAN_THREADS lanes; t double[N][R], dir
+// double[N][R][2], origin double[N][3] or null; env b's rows of map (uint8[N][2][gz][gx]), count and newly (int32[N][2]; newly may be
+// null) where mask is null or mask[b] != 0; clear uint8[N] or null.
+extern "C" __global__ void mw_scan_kernel(MwNavArgs a, mw_nav_params p, double max_range, int R, const double *__restrict__ t,
+                                          const double *__restrict__ dir, const double *__restrict__ origin, const uint8_t *__restrict__ mask,
+                                          const uint8_t *__restrict__ clear, uint8_t *__restrict__ map, int32_t *__restrict__ count,
+                                          int32_t *__restrict__ newly);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -16,6 +16,7 @@
 #include "mw_sight.h"           // MW_SIGHT_THREADS, mwsight::bits_bytes, weight_bytes, gain_bytes
 #include "mw_regions.h"         // MW_REGIONS_THREADS, mwregions::label_bytes, table_bytes, scan_bytes
 #include "mw_clear.h"           // MW_CLEAR_THREADS, mwclear::off_bytes
+#include "mw_scan.h"            // MW_SCAN_THREADS, mwscan::plane_bytes, prefix_bytes
 #include "mw_shape.h"
 #include "mw_snapframes.h"     // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -455,6 +456,16 @@ inline Launch clear_launch(int N, long long cells)
 {
     const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS;
     return {(unsigned long long)N, MW_CLEAR_THREADS, fits ? mwclear::off_bytes(cells) : 0, fits};
+}
+
+// Scan maps (mw_scan_project; kernel: mw_scan.hip): a workgroup of MW_SCAN_THREADS lanes per env.  Its LDS is two bit planes, a bit per
+// cell in 32-bit words, then a prefix word per beam and one, the two sums and a word per wavefront behind them, each rounded up to 16:
+// 4 + 4 + 16 KiB and 32 bytes at MW_NAV_MAX_CELLS and MW_RAY_MAX; sized by the actual counts, so that the Maze's 103 x 103 cells with
+// 256 beams take under 4 KiB.  fits: a positive count of no more cells than that and 1 .. MW_RAY_MAX beams — the caller refuses what does not.
+inline Launch scan_launch(int N, long long cells, int rays)
+{
+    const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS && rays >= 1 && rays <= MW_RAY_MAX;
+    return {(unsigned long long)N, MW_SCAN_THREADS, fits ? 2 * mwscan::plane_bytes(cells) + mwscan::prefix_bytes(rays) : 0, fits};
 }
 
 }  // namespace mwpolicy

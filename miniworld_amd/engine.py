@@ -251,6 +251,7 @@ SIGNATURES = {
     "mw_debug_set_ray_form": _sig(vp, C.c_int),
     "mw_grid_regions": _sig(vp, P(MwNavParams), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_grid_clearance": _sig(vp, P(MwNavParams), i32, P(i32), i32, vp, vp, vp, vp, vp, vp),
+    "mw_scan_project": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
     "mw_grid_sight": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
@@ -681,6 +682,35 @@ class Engine:
         pairs = (C.c_int32 * len(flat))(*flat) if flat else None
         self._check(self.lib.mw_grid_clearance(self.h, C.byref(params), int(limit), pairs, len(flat) // 2, _ptr(mask), _ptr(marked), _ptr(dist2),
                                                _ptr(nearest), _ptr(cost), _stream_ptr(self.device)), "mw_grid_clearance")
+
+    # -- scan maps -----------------------------------------------------------------------
+    def scan_project(self, params: MwNavParams, max_range: float, t, dir, map, count, new=None, origin=None, mask=None, clear=None):
+        """mw_scan_project: for the envs under `mask` (uint8[N], device; None = all) the beams `t` (float64[N, R]) along `dir`
+        (float64[N, R, 2]: dx, dz of any length) from `origin` (float64[N, 3], y not read; None = the agents) are traced into `map`
+        (uint8[N, 2, gz, gx]): the cells a beam passes through up to min(t, max_range) become free in plane 0, the cell a beam with
+        t < max_range ends in an obstacle in plane 1 and not free; bytes only go 0 -> 1, behind a zeroing of the rows under `clear`
+        (uint8[N]); `new` (int32[N, 2], optional) gets the cells set by this call, `count` (int32[N, 2]) carries their sum.  One kernel
+        on the current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the library is called."""
+        import torch
+        for name, v in (("t", t), ("dir", dir), ("map", map), ("count", count)):
+            if v is None:
+                raise EngineError(f"{name}: None")
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise EngineError(f"t: need a float64 tensor [{self.N}, R], got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        R = int(t.shape[1])
+        self._shaped_tensor(t, "t", torch.float64, (self.N, R))
+        self._shaped_tensor(dir, "dir", torch.float64, (self.N, R, 2))
+        self._shaped_tensor(map, "map", torch.uint8, (self.N, 2, int(params.gz), int(params.gx)))
+        self._shaped_tensor(count, "count", torch.int32, (self.N, 2))
+        if new is not None:
+            self._shaped_tensor(new, "new", torch.int32, (self.N, 2))
+        if origin is not None:
+            self._shaped_tensor(origin, "origin", torch.float64, (self.N, 3))
+        self._dev_tensor(clear, "clear", torch.uint8, self.N)
+        mask = self._mask_tensor(mask, optional=True)
+        host = (C.c_double * 1)(float(max_range))
+        self._check(self.lib.mw_scan_project(self.h, C.byref(params), host, R, _ptr(t), _ptr(dir), _ptr(origin), _ptr(mask), _ptr(clear),
+                                             _ptr(map), _ptr(count), _ptr(new), _stream_ptr(self.device)), "mw_scan_project")
 
     # -- egocentric map windows ----------------------------------------------------------
     def ego_map(self, size: int, cell: float, back: float, wall_radius: float, entity_pad: float, max_range: float, cos_half: float, planes: int,

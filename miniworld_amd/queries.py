@@ -1,6 +1,6 @@
 """The world queries of the batched env — navigation fields, explored-area maps, grid sight, grid regions, grid clearance, egocentric map windows,
-depth projection, label frames, object maps, ray casts —, each one kernel on the device with no host value: their value classes (NavField, SeenMap,
-EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance) and
+depth projection, label frames, object maps, ray casts, scan maps —, each one kernel on the device with no host value: their value classes (NavField,
+SeenMap, EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance, ScanMap) and
 `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
 from __future__ import annotations
 
@@ -97,6 +97,25 @@ class DepthMap:
     def __init__(self, map, count, new, params, min_points, min_range, max_range, floor_tol, top):
         self.map, self.count, self.new, self.params, self.min_points = map, count, new, params, min_points
         self.min_range, self.max_range, self.floor_tol, self.top = min_range, max_range, floor_tol, top
+
+    cell = property(lambda self: self.params.cell)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+    free = property(lambda self: self.map[:, 0])
+    obstacle = property(lambda self: self.map[:, 1])
+
+
+class ScanMap:
+    """A scan-built floor-plan map (MiniWorldVecEnv.scan_map): `map`, the uint8[N, 2, gz, gx] device tensor that scan_map_update()
+    accumulates on a nav field's grid (`params`: `cell` metres per cell, gx x gz cells from the env's own min_x, min_z), laid out like a
+    DepthMap's, with the views `free` (1 once a beam passed through the cell) and `obstacle` (1 once a beam that hit something ended in
+    it) — a cell may be both over several calls, or neither: never scanned —, `count`, int32[N, 2], the cells set so far in each, and
+    `new`, int32[N, 2], those the last update added.  `rays`, `fov`, `max_range` and `obstacles` are the lidar() scan_map_update() casts
+    when it is given none; `max_range` also cuts a given scan's beams.  The tensors are the caller's, like a SeenMap's."""
+
+    def __init__(self, map, count, new, params, rays, fov, max_range, obstacles):
+        self.map, self.count, self.new, self.params = map, count, new, params
+        self.rays, self.fov, self.max_range, self.obstacles = rays, fov, max_range, obstacles
 
     cell = property(lambda self: self.params.cell)
     gx = property(lambda self: self.params.gx)
@@ -339,7 +358,7 @@ class WorldQueries:
         inflate   metres: a cell is blocked too when a raw obstacle cell's centre is closer than this to its own.  None:
                   agent_radius + cell / 2, nav_field()'s default clearance.  0: the raw cells only.  At most
                   engine.NAV_MAX_INFLATE cells.  The agent's radius is NOT added: the caller's grid may already hold it.
-        like      a NavField, SeenMap, DepthMap or ObjectMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell` metres
+        like      a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell` metres
                   per cell as in nav_field().
         mask      uint8[N] or bool[N] device tensor: only those envs' rows are built (the others are not touched)
         into      a grid field to rebuild in place: the grids are passed again, the grid's parameters are the field's own
@@ -353,7 +372,7 @@ class WorldQueries:
                 raise ValueError("grid_field: with `into` the field's own points and parameters are used: pass only the grids and mask")
             field, params, target = into.field, into.params, into.target
         else:
-            g = self._map_grid("grid_field", cell, like, (NavField, SeenMap, DepthMap, ObjectMap), "its own")
+            g = self._map_grid("grid_field", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
             cell, gx, gz = g.cell, g.gx, g.gz
             inflate = float(e.cfg.agent_radius) + cell / 2 if inflate is None else real("grid_field", "inflate", inflate, lo_open=False)
             if inflate > eng.NAV_MAX_INFLATE * cell:
@@ -463,7 +482,7 @@ class WorldQueries:
         max_range  how far a viewpoint sees, in metres, centre to centre
         fov        the horizontal opening angle in radians about the heading, 0 < fov <= 2 pi.  None: default_fov() for the agent and
                    with `dirs`; with `cells` and no `dirs` the cone is all round and only None or 2 pi is accepted
-        like       a NavField, SeenMap, DepthMap or ObjectMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
+        like       a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
                    metres per cell as in nav_field()
         mask       uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
         seen       uint8 or bool [N, gz, gx] device tensor: every cell any viewpoint of the env sees is set to 1; never cleared here
@@ -471,7 +490,7 @@ class WorldQueries:
         meets the segment between the two (include/mwengine.h, "grid sight"): a viewpoint sees itself, and an opaque cell's face.
         The tensors are checked and never converted.  ValueError for arguments that make no call; nothing is launched then."""
         torch, e = self.torch, self.engine
-        params = self._map_grid("grid_sight", cell, like, (NavField, SeenMap, DepthMap, ObjectMap), "its own")
+        params = self._map_grid("grid_sight", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
         max_range = real("grid_sight", "max_range", max_range)
         n = self.num_envs
         if cells is None:
@@ -509,7 +528,7 @@ class WorldQueries:
         connectivity  4: cells that share an edge are joined; 8: cells that share a corner too
         min_cells     regions of fewer cells are not counted and not listed (their cells' label is -1)
         max_regions   K, 1 .. engine.REGION_MAX: the regions listed per env, in the order of their lowest cells; `count` may exceed it
-        like          a NavField, SeenMap, DepthMap or ObjectMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
+        like          a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
                       metres per cell as in nav_field()
         mask          uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
         labels        with the per-cell `label` plane
@@ -527,7 +546,7 @@ class WorldQueries:
                 raise ValueError("grid_regions: with `into` the record's own grid and parameters are used: pass only member and mask")
             out, params = into, into.params
         else:
-            params = self._map_grid("grid_regions", cell, like, (NavField, SeenMap, DepthMap, ObjectMap), "its own")
+            params = self._map_grid("grid_regions", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
             if connectivity not in (4, 8) or isinstance(connectivity, bool):
                 raise ValueError(f"grid_regions: connectivity {connectivity!r}; have 4 and 8")
             min_cells = integer("grid_regions", "min_cells", min_cells, 1, eng.NAV_MAX_CELLS)
@@ -560,7 +579,7 @@ class WorldQueries:
         limit    metres: cells farther than the smallest L cells with L * cell >= limit hold engine.CLEAR_FAR, nearest -1, cost 0, and
                  no scan goes farther: what bounds the work on a nearly empty map.  None: no limit.
         nearest  with the per-cell `nearest` plane
-        like     a NavField, SeenMap, DepthMap, ObjectMap or GridRegions whose grid (cell, gx, gz) is adopted; pass no cell then.  Else
+        like     a NavField, SeenMap, DepthMap, ObjectMap, GridRegions or ScanMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else
                  `cell` metres per cell as in nav_field()
         mask     uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
         into     a GridClearance of an earlier call to write into: its grid, bands, limit and optional tensors are used; pass only
@@ -576,7 +595,7 @@ class WorldQueries:
                 raise ValueError(f"{where}: with `into` the record's own grid and parameters are used: pass only marked and mask")
             out, params = into, into.params
         else:
-            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions), "its own")
+            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions, ScanMap), "its own")
             if not isinstance(nearest, bool):
                 raise ValueError(f"{where}: nearest must be True or False, not {nearest!r}")
             if (radii is None) != (costs is None):
@@ -752,13 +771,13 @@ class WorldQueries:
         """An empty depth-built map over each env's floor plan: a DepthMap, which depth_map_update() accumulates.  Nothing is launched.
 
         cell        metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
-        like        a NavField, SeenMap or ObjectMap whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass no
+        like        a NavField, SeenMap, ObjectMap or ScanMap whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass no
                     cell then
         min_points  how many pixels of ONE depth map must fall into a cell to set it, 1 .. 255
         min_range, max_range, floor_tol, top  as for depth_window()
         At most 16384 cells (the kernel counts in 64 KiB of LDS): ValueError says "use a larger cell" otherwise."""
         torch, e = self.torch, self.engine
-        params = self._map_grid("depth_map", cell, like, (NavField, SeenMap, ObjectMap), "its own")
+        params = self._map_grid("depth_map", cell, like, (NavField, SeenMap, ObjectMap, ScanMap), "its own")
         gx, gz = params.gx, params.gz
         if gx * gz > eng.DEPTH_MAX_CELLS:
             raise ValueError(f"depth_map: {gx} x {gz} cells > {eng.DEPTH_MAX_CELLS}: use a larger cell")
@@ -785,6 +804,57 @@ class WorldQueries:
         clear, mask = self._device_mask(clear, "depth_map_update", "clear"), self._device_mask(mask, "depth_map_update")
         self.engine.depth_project(depth, m.min_range, m.max_range, m.floor_tol, m.top, mask, params=m.params, min_points=m.min_points, map=m.map,
                                   count=m.count, new=m.new, clear=clear)
+        return m.new
+
+    # ------------------------------------------------------------------ scan maps
+    def scan_map(self, cell=0.25, like=None, rays=256, fov=2 * math.pi, max_range=10.0, obstacles="walls+entities"):
+        """An empty scan-built map over each env's floor plan: a ScanMap, which scan_map_update() accumulates.  Nothing is launched.
+
+        cell       metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
+        like       a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) the map adopts, so that they line up
+                   cell for cell; pass no cell then
+        rays, fov, obstacles  the lidar() that scan_map_update() casts when it is given no scan
+        max_range  metres: a beam is traced up to there, and one that reaches it marks no obstacle"""
+        torch, e = self.torch, self.engine
+        params = self._map_grid("scan_map", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
+        rays, fov = integer("scan_map", "rays", rays, 1, eng.RAY_MAX), real("scan_map", "fov", fov, hi=2 * math.pi)
+        max_range = real("scan_map", "max_range", max_range)
+        self._obstacle_flags("scan_map", obstacles)
+        n = self.num_envs
+        return ScanMap(torch.zeros((n, 2, params.gz, params.gx), dtype=torch.uint8, device=e.device), torch.zeros((n, 2), dtype=torch.int32, device=e.device),
+                       torch.zeros((n, 2), dtype=torch.int32, device=e.device), params, rays, fov, max_range, obstacles)
+
+    def scan_map_update(self, m, scan=None, origin=None, clear=None, mask=None):
+        """Traces a range scan's beams into `m` (a ScanMap), by one kernel (mw_scan_project) with no host value and no synchronisation:
+        the cells a beam passes through become free, the cell a beam shorter than m.max_range ends in becomes an obstacle (and is not
+        free in this call); returns m.new, int32[N, 2], the free and obstacle cells that were set by this call, while m.count carries
+        the totals.  It needs no frame: behind rollout(render=False) the map is as current as the pose.
+
+        scan    None: `self.lidar(m.rays, m.fov, m.max_range, obstacles=m.obstacles)`, cast now; or a raycast() / lidar() result, or any
+                dict with contiguous float64 "t" [N, R] and "dir" [N, R, 2] (dx, dz, any length) on the device — the caller's own
+                beams: with noise, with dropped ones (a NaN or a negative t), R up to engine.RAY_MAX.  Checked, never converted
+        origin  float64[N, 3] device tensor (y is not read), the beams' origin per env — a pose estimate; None: the agents' positions
+                the device holds now
+        clear   uint8[N] or bool[N] device tensor: those envs' maps are zeroed and their counts restarted first
+        mask    uint8[N] or bool[N] device tensor: only those envs are updated; the mask wins over clear
+        The rule in full: include/mwengine.h, "scan maps".  An env whose extent the grid does not cover gets its map zeroed and
+        engine.check() raises once.  ValueError for arguments that make no call; nothing is launched then."""
+        e, n = self.engine, self.num_envs
+        if not isinstance(m, ScanMap):
+            raise ValueError("scan_map_update: `m` must be a ScanMap (scan_map())")
+        if scan is not None:
+            if not isinstance(scan, dict) or "t" not in scan or "dir" not in scan:
+                raise ValueError('scan_map_update: `scan` is a dict with "t" and "dir" (a lidar() result, or raycast()\'s with the directions beside it)')
+            if not self._is_tensor(scan["t"], (n, None)) or not 1 <= scan["t"].shape[1] <= eng.RAY_MAX:
+                raise ValueError(f'scan_map_update: scan["t"] is a contiguous float64 tensor [{n}, R] on {e.device}, R in 1 .. {eng.RAY_MAX}')
+            if not self._is_tensor(scan["dir"], (n, int(scan["t"].shape[1]), 2)):
+                raise ValueError(f'scan_map_update: scan["dir"] is a contiguous float64 tensor [{n}, {int(scan["t"].shape[1])}, 2] on {e.device}')
+        if origin is not None and not self._is_tensor(origin, (n, 3)):
+            raise ValueError(f"scan_map_update: origin is a contiguous float64 tensor [{n}, 3] on {e.device}")
+        clear, mask = self._device_mask(clear, "scan_map_update", "clear"), self._device_mask(mask, "scan_map_update")
+        if scan is None:
+            scan = self.lidar(m.rays, m.fov, m.max_range, obstacles=m.obstacles)
+        e.scan_project(m.params, m.max_range, scan["t"], scan["dir"], m.map, m.count, m.new, origin, mask, clear)
         return m.new
 
     # ------------------------------------------------------------------ label frames
@@ -886,14 +956,14 @@ class WorldQueries:
         """An empty sensed object map over each env's floor plan: an ObjectMap, which object_map_update() keeps.  Nothing is launched.
 
         cell   metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
-        like   a NavField, SeenMap, DepthMap or ObjectMap whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass
+        like   a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass
                no cell then
         ids    K, 0 .. 255: `cells` and `pos` have a row for each id below it (an id from K on is mapped, not counted); None: the env's
                entity slots, at most 255.  0: the map alone
         min_range, max_range, floor_tol, top  as for depth_window()
         At most 16384 cells (the kernel keeps a key per cell in LDS): ValueError says "use a larger cell" otherwise."""
         torch, e = self.torch, self.engine
-        params = self._map_grid("object_map", cell, like, (NavField, SeenMap, DepthMap, ObjectMap), "its own")
+        params = self._map_grid("object_map", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
         gx, gz = params.gx, params.gz
         if gx * gz > eng.LABELMAP_MAX_CELLS:
             raise ValueError(f"object_map: {gx} x {gz} cells > {eng.LABELMAP_MAX_CELLS}: use a larger cell")

@@ -75,6 +75,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
     def __init__(self, env_id: str, num_envs: int, to_numpy: bool = False, autoreset_mode="same-step", final_obs: bool = False,
                  frame_reuse: bool = True, frame_cache: int = 4, action_repeat: int = 1, frame_stack: int | None = None, stack_pad: str = "reset",
                  levels=None, level_generator=None, reset_seeds=None, info_state=None, seen_map=None, ego_map=None, depth_map=None, label_frame=None, object_map=None,
+                 scan_map=None,
                  **kwargs):
         """autoreset_mode: "same-step" (the class's metadata) or "next-step" (module docstring); gymnasium's AutoresetMode values
         are accepted too.  final_obs (same-step only): info["final_obs"] / info["_final_obs"] (module docstring).  frame_reuse:
@@ -120,7 +121,14 @@ class MiniWorldVectorEnv(VectorEnvBase):
         update (`self.object_win`, an ObjectWindow; one kernel; the label frame's own depth where it has one, else the env's, for which
         want_depth is switched on) and add info["object_map"], uint8[N, S, S]: 1 + the entity slot sensed in each cell, 0 for none —
         laid out like ego_map's entity plane, which is its label.  A copy: it stays valid after the next step.  None (the default)
-        adds nothing and calls nothing."""
+        adds nothing and calls nothing.
+        scan_map: a dict of MiniWorldVecEnv.scan_map()'s arguments (an empty one for its defaults) — reset() and every step() cast the
+        map's lidar from each agent's new pose and trace its beams into a map on the device (`self.scan`, a ScanMap; two kernels, no
+        frame needed) and add info["scan_map"], uint8[N, 2, gz, gx]: the free and the obstacle plane so far in the episode; the map of an
+        env whose episode ended restarts as a seen_map's does.  A copy: it stays valid after the next step.  None (the default) adds
+        nothing and calls nothing."""
+        if scan_map is not None and not isinstance(scan_map, dict):
+            raise ValueError(f"scan_map: need a dict of MiniWorldVecEnv.scan_map()'s arguments or None, not {scan_map!r}")
         if object_map is not None:
             if not isinstance(object_map, dict):
                 raise ValueError(f"object_map: need a dict of MiniWorldVecEnv.object_window()'s arguments or None, not {object_map!r}")
@@ -184,6 +192,7 @@ class MiniWorldVectorEnv(VectorEnvBase):
             self.vec.next_seed.copy_(self._first_next_seed)
         self._played_seed = None
         self.seen = None if seen_map is None else self.vec.seen_map(**seen_map)
+        self.scan = None if scan_map is None else self.vec.scan_map(**scan_map)
         self._seen_clear = None         # next-step: the envs whose next step is their reset step
         self.ego = None if ego_map is None else self.vec.ego_window(**ego_map)
         self.depth_win = None if depth_map is None else self.vec.depth_window(**depth_map)
@@ -222,8 +231,9 @@ class MiniWorldVectorEnv(VectorEnvBase):
         return info
 
     def _seen_info(self, info, done, all_new):
-        """seen_map: one seen_update() behind the step or reset; copies of the map's counters (they are rewritten by the next step)"""
-        if self.seen is not None:
+        """seen_map: one seen_update() behind the step or reset; copies of the map's counters (they are rewritten by the next step).
+        scan_map: one lidar() and one scan_map_update() there, under the same `clear`; a copy of the map."""
+        if self.seen is not None or self.scan is not None:
             torch = self.vec.torch
             if all_new:
                 clear = torch.ones(self.num_envs, dtype=torch.uint8, device=self.vec.engine.device)
@@ -232,9 +242,13 @@ class MiniWorldVectorEnv(VectorEnvBase):
             else:
                 clear = done.to(torch.uint8) if self.vec.autoreset_mode != "off" else None
             self._seen_clear = None if all_new else done.to(torch.uint8)
+        if self.seen is not None:
             self.vec.seen_update(self.seen, clear=clear)
             info["seen_new"] = self._out(self.seen.new) if self.to_numpy else self.seen.new.clone()
             info["seen_count"] = self._out(self.seen.count) if self.to_numpy else self.seen.count.clone()
+        if self.scan is not None:
+            self.vec.scan_map_update(self.scan, clear=clear)
+            info["scan_map"] = self._out(self.scan.map) if self.to_numpy else self.scan.map.clone()
         return info
 
     def _ego_info(self, info):
