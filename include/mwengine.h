@@ -1260,6 +1260,50 @@ int mw_scan_project(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are 
                     const double *d_t /* [N][R] */, const double *d_dir /* [N][R][2]: dx, dz */, const double *d_origin /* [N][3] or NULL = the agents */,
                     const uint8_t *d_mask, const uint8_t *d_clear /* or NULL */, uint8_t *d_map /* [N][2][gz][gx] */, int32_t *d_count /* [N][2] */,
                     int32_t *d_new /* [N][2] or NULL */, void *stream);
+
+/* ---- scan matching ----------------------------------------------------------- */
+/* The other half of a scan mapper: where a scan fits the map.  mw_scan_project takes d_origin as "a pose estimate"; this call corrects one.
+ * It is Olson's brute-force correlative scan matcher (the matcher of gmapping's, Hector's and Cartographer 2D's front ends) on the map's own
+ * lattice: every rotation of a list and every translation by whole cells inside a window is scored by the sum of the likelihood bytes under
+ * the scan's end cells, and the best candidate is returned — with, if asked, the whole score volume, which a particle filter or a covariance
+ * estimate reads.  The reference has no such call.
+ *
+ * The rule.  All arithmetic is float64, only + - * / and floor, uncontracted, in exactly this order.  Per env: (ox, oz), min_x, min_z, cell,
+ * gx, gz and max_range = host_range[0] as for mw_scan_project, and per beam k with t = d_t[i][k], (dx, dz) = d_dir[i][k], of any length:
+ *   u0 = (ox - min_x) / cell;  w0 = (oz - min_z) / cell;  gu = dx / cell;  gw = dz / cell            (mw_scan_project's, bit for bit)
+ * Per rotation r = 0 .. K - 1 with (c, s) = host_rot[r] — the caller's cosine and sine: no trigonometry runs on the device, and the pair is
+ * not normalised —:
+ *   ru = c * gu + s * gw;  rw = c * gw - s * gu
+ *   u1 = u0 + t * ru;  w1 = w0 + t * rw
+ * which is the sense in which agent_dir grows for dir_vec = (cos, 0, -sin); (1, 0) leaves the beam unchanged bit for bit.
+ * Beam k COUNTS for rotation r iff t >= 0 && t < max_range (a NaN fails; a beam that reached max_range has no end point) and u0, w0, u1,
+ * w1 are all strictly inside -2^30 .. 2^30.  Its end cell is (row, col) = (floor(w1), floor(u1)): with (1, 0) mw_scan_project's end cell of
+ * a kept beam with hit.  With the window W, translations are whole cells (a, b), a along the columns and b along the rows, each in -W .. W:
+ *   score(r, b, a) = the sum over the counting beams of rotation r of d_score[i][row + b][col + a]
+ * where a term is 0 unless 0 <= row + b < gz and 0 <= col + a < gx, tested before any index is formed.  An int32: at most 4096 * 255.
+ * d_score is uint8[N][gz][gx], the caller's likelihood plane as it stands: an obstacle plane (bytes 0 / 1), or a banded likelihood field
+ * such as mw_grid_clearance's d_cost (0 .. 255).
+ * The best candidate is the one of the highest score; among equal scores the one of the least a^2 + b^2, then of the lowest r, then of the
+ * lowest b, then of the lowest a.  On a featureless plane, and for an env without a counting beam, that is (0, 0, 0) with the score of it.
+ * For every env i with d_mask[i] != 0 (or a null d_mask): d_best[i] = (r, a, b), d_best_score[i] = its score, and with a d_volume
+ * d_volume[i][r][b + W][a + W] = score(r, b, a) for every candidate.  An env whose extent the grid does not cover (as for mw_nav_build)
+ * gets best (0, 0, 0), score 0, its volume row zeroed, and sets the status bit mw_scan_project sets there: the next mw_check reports it as
+ * MW_E_INVALID, once.  Rows of envs under a zero mask byte are neither read nor written.  Every result is an integer the rule defines, so
+ * nothing depends on the kernel's schedule.
+ *
+ * One kernel, one workgroup per env, asynchronous on `stream`; host_range and host_rot are read during the call and passed by value; it
+ * reads no other host value, reads live arrays only and changes nothing in the engine.  MW_E_INVALID before anything is launched, and
+ * nothing touched: a null engine, grid, host_range, host_rot, d_score, d_t, d_dir, d_best or d_best_score; a grid mw_nav_build would refuse;
+ * R outside 1 .. MW_RAY_MAX; K outside 1 .. MW_MATCH_MAX_ROT; window outside 0 .. MW_MATCH_MAX_WINDOW; a (c, s) that is not finite; a
+ * max_range that is not > 0 and finite; more workgroups than a launch holds. */
+#define MW_MATCH_MAX_ROT 64      /* rotations per call */
+#define MW_MATCH_MAX_WINDOW 32   /* cells either way */
+int mw_scan_match(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */,
+                  const double *host_range /* [1] on the host: max_range */, const double *host_rot /* [K][2] on the host: c, s */, int32_t K,
+                  int32_t window, int32_t R, const uint8_t *d_score /* [N][gz][gx] */, const double *d_t /* [N][R] */,
+                  const double *d_dir /* [N][R][2]: dx, dz */, const double *d_origin /* [N][3] or NULL = the agents */, const uint8_t *d_mask,
+                  int32_t *d_best /* [N][3]: r, a, b */, int32_t *d_best_score /* [N] */, int32_t *d_volume /* [N][K][2W+1][2W+1] or NULL */,
+                  void *stream);
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.
@@ -1271,7 +1315,7 @@ int mw_scan_project(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are 
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project or mw_label_project skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match or mw_label_project skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

@@ -19,6 +19,7 @@
 #include "mw_regions.h"
 #include "mw_clear.h"
 #include "mw_scan.h"
+#include "mw_match.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -370,6 +371,15 @@ extern "C" __global__ void mw_scan_kernel(MwNavArgs a, mw_nav_params p, double m
                                           const double *__restrict__ dir, const double *__restrict__ origin, const uint8_t *__restrict__ mask,
                                           const uint8_t *__restrict__ clear, uint8_t *__restrict__ map, int32_t *__restrict__ count,
                                           int32_t *__restrict__ newly);
+
+// scan matching (mw_match.hip; the rule, the arrays, the phases and the launch constant: mw_match.h; the launch: mwpolicy::match_launch).
+// Of the view the extent and, with a null origin, ax / az are read.  Grid N workgroups of MW_MATCH_THREADS lanes; rot: the K rotations by
+// value; batch, quad: the launch's (rotations per pass, the form); score uint8[N][gz][gx]; t, dir, origin as for mw_scan_kernel; env b's rows of best (int32[N][3]), best_score (int32[N]) and volume
+// (int32[N][K][2 W + 1][2 W + 1] or null) where mask is null or mask[b] != 0.
+extern "C" __global__ void mw_match_kernel(MwNavArgs a, mw_nav_params p, double max_range, int R, MwMatchRot rot, int W, int batch, int quad,
+                                           const uint8_t *__restrict__ score, const double *__restrict__ t, const double *__restrict__ dir,
+                                           const double *__restrict__ origin, const uint8_t *__restrict__ mask, int32_t *__restrict__ best,
+                                           int32_t *__restrict__ best_score, int32_t *__restrict__ volume);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -17,6 +17,7 @@
 #include "mw_regions.h"         // MW_REGIONS_THREADS, mwregions::label_bytes, table_bytes, scan_bytes
 #include "mw_clear.h"           // MW_CLEAR_THREADS, mwclear::off_bytes
 #include "mw_scan.h"            // MW_SCAN_THREADS, mwscan::plane_bytes, prefix_bytes
+#include "mw_match.h"           // MW_MATCH_THREADS, mwmatch::plane_bytes, ends_bytes, fill_bytes
 #include "mw_shape.h"
 #include "mw_snapframes.h"     // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -466,6 +467,37 @@ inline Launch scan_launch(int N, long long cells, int rays)
 {
     const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS && rays >= 1 && rays <= MW_RAY_MAX;
     return {(unsigned long long)N, MW_SCAN_THREADS, fits ? 2 * mwscan::plane_bytes(cells) + mwscan::prefix_bytes(rays) : 0, fits};
+}
+
+// Scan matching (mw_scan_match; kernel: mw_match.hip): a workgroup of MW_MATCH_THREADS lanes per env.  Its LDS is the score plane, a byte
+// per cell (the quad form: and 144 bytes of pads), then two buffers of `batch` end-cell lists of a word per beam, then a fill word per
+// rotation slot and the 64-bit key, each rounded up to 16: 32 + 32 KiB and 272 bytes at MW_NAV_MAX_CELLS and MW_RAY_MAX, which one
+// workgroup may hold (a CU has 160 KiB; the engine asks for it as for mw_nav_grid_kernel); sized by the actual counts, so that the Maze's
+// 103 x 103 cells with 256 beams take under 15 KiB.  The window changes the work, not the plane.
+// quad: the form — four adjacent columns per lane where the window has more candidates than the workgroup has lanes, a translation per
+// lane where it has not.  Measured (profiles/r44, device us per call, byte / quad form): W = 10, 441 candidates, 21 rotations, 256 beams:
+// Hallway x 4096 3 136 .. 3 149 / 1 641 .. 1 652, Maze x 1024 1 205 .. 1 211 / 623 .. 626; W = 4, 81 candidates, one rotation: 94 / 124 and
+// 42 / 55.  Between 81 and 441 candidates nothing was measured: the threshold is a supposition there.  (MW_MATCH_FORM 1 / 2 builds a
+// library with one form for every window, for such measurements.)
+// batch: the rotations whose candidates are dealt over the lanes together, so that a small window fills the workgroup: as many as the
+// lanes hold whole, at most 8, and no more than keep both list buffers within 32 KiB (MW_RAY_MAX / rays).
+// fits: a positive count of no more cells than that, 1 .. MW_RAY_MAX beams and a window of 0 .. MW_MATCH_MAX_WINDOW — the caller refuses
+// what does not.
+#ifndef MW_MATCH_FORM
+#define MW_MATCH_FORM 0
+#endif
+struct MatchLaunch { unsigned long long grid; int threads; size_t lds; bool fits; bool quad; int batch; };
+inline MatchLaunch match_launch(int N, int gz, int gx, int rays, int window, int forced = MW_MATCH_FORM)
+{
+    const long long cells = (long long)gz * gx;
+    const bool fits = gz >= 1 && gx >= 1 && cells <= MW_NAV_MAX_CELLS && rays >= 1 && rays <= MW_RAY_MAX && window >= 0 && window <= MW_MATCH_MAX_WINDOW;
+    if (!fits) return {(unsigned long long)N, MW_MATCH_THREADS, 0, false, false, 1};
+    const int side = 2 * window + 1;
+    const bool quad = forced ? forced == 2 : side * side > MW_MATCH_THREADS;
+    const int per = quad ? side * ((side + 3) / 4) : side * side, most = MW_RAY_MAX / rays < 8 ? MW_RAY_MAX / rays : 8;
+    int batch = MW_MATCH_THREADS / per;
+    batch = batch > most ? most : batch < 1 ? 1 : batch;
+    return {(unsigned long long)N, MW_MATCH_THREADS, mwmatch::plane_bytes(cells, quad) + mwmatch::ends_bytes(rays, batch) + mwmatch::fill_bytes(), true, quad, batch};
 }
 
 }  // namespace mwpolicy

@@ -134,6 +134,7 @@ SIGHT_MAX_VIEWS = 256                   # MW_SIGHT_MAX_VIEWS: mw_grid_sight's vi
 REGION_MAX = 256                        # MW_REGION_MAX: mw_grid_regions' listed regions per env and call (== SIGHT_MAX_VIEWS)
 CLEAR_NONE, CLEAR_FAR = 0x7FFFFFFF, 0x7FFFFFFE      # MW_CLEAR_NONE, MW_CLEAR_FAR: mw_grid_clearance's dist2 without a marked cell, beyond the limit
 CLEAR_MAX_BANDS = 8                     # MW_CLEAR_MAX_BANDS: mw_grid_clearance's cost bands per call
+MATCH_MAX_ROT, MATCH_MAX_WINDOW = 64, 32        # MW_MATCH_MAX_ROT, MW_MATCH_MAX_WINDOW: mw_scan_match's rotations per call, cells either way
 
 EGO_ENTITIES, EGO_NORTH = 1, 2          # MW_EGO_* flags
 EGO_WALL, EGO_ENTITY, EGO_VISIBLE = 1, 2, 4     # MW_EGO_* planes
@@ -252,6 +253,7 @@ SIGNATURES = {
     "mw_grid_regions": _sig(vp, P(MwNavParams), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_grid_clearance": _sig(vp, P(MwNavParams), i32, P(i32), i32, vp, vp, vp, vp, vp, vp),
     "mw_scan_project": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+    "mw_scan_match": _sig(vp, P(MwNavParams), P(C.c_double), P(C.c_double), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
     "mw_grid_sight": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
@@ -711,6 +713,37 @@ class Engine:
         host = (C.c_double * 1)(float(max_range))
         self._check(self.lib.mw_scan_project(self.h, C.byref(params), host, R, _ptr(t), _ptr(dir), _ptr(origin), _ptr(mask), _ptr(clear),
                                              _ptr(map), _ptr(count), _ptr(new), _stream_ptr(self.device)), "mw_scan_project")
+
+    # -- scan matching -------------------------------------------------------------------
+    def scan_match(self, params: MwNavParams, max_range: float, rot, window: int, score, t, dir, best, best_score, volume=None, origin=None, mask=None):
+        """mw_scan_match: for the envs under `mask` (uint8[N], device; None = all) the beams `t` (float64[N, R]) along `dir`
+        (float64[N, R, 2]) from `origin` (float64[N, 3]; None = the agents), turned by each (c, s) of `rot` (K host pairs) and shifted by
+        every whole-cell (a, b) within `window` cells, are scored on `score` (uint8[N, gz, gx]): the sum of the bytes under the end cells
+        of the beams with 0 <= t < max_range.  `best` (int32[N, 3]) gets (rotation index, a, b) of the highest score, ties to the
+        smallest shift, `best_score` (int32[N]) its score, `volume` (int32[N, K, 2 window + 1, 2 window + 1], optional) every score.
+        One kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the
+        library is called."""
+        import torch
+        for name, v in (("score", score), ("t", t), ("dir", dir), ("best", best), ("best_score", best_score)):
+            if v is None:
+                raise EngineError(f"{name}: None")
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise EngineError(f"t: need a float64 tensor [{self.N}, R], got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        R, K, side = int(t.shape[1]), len(rot), 2 * int(window) + 1
+        self._shaped_tensor(t, "t", torch.float64, (self.N, R))
+        self._shaped_tensor(dir, "dir", torch.float64, (self.N, R, 2))
+        self._shaped_tensor(score, "score", torch.uint8, (self.N, int(params.gz), int(params.gx)))
+        self._shaped_tensor(best, "best", torch.int32, (self.N, 3))
+        self._shaped_tensor(best_score, "best_score", torch.int32, (self.N,))
+        if volume is not None:
+            self._shaped_tensor(volume, "volume", torch.int32, (self.N, K, side, side))
+        if origin is not None:
+            self._shaped_tensor(origin, "origin", torch.float64, (self.N, 3))
+        mask = self._mask_tensor(mask, optional=True)
+        host = (C.c_double * 1)(float(max_range))
+        pairs = (C.c_double * (2 * max(K, 1)))(*[float(v) for cs in rot for v in cs])
+        self._check(self.lib.mw_scan_match(self.h, C.byref(params), host, pairs, K, int(window), R, _ptr(score), _ptr(t), _ptr(dir), _ptr(origin), _ptr(mask),
+                                           _ptr(best), _ptr(best_score), _ptr(volume), _stream_ptr(self.device)), "mw_scan_match")
 
     # -- egocentric map windows ----------------------------------------------------------
     def ego_map(self, size: int, cell: float, back: float, wall_radius: float, entity_pad: float, max_range: float, cos_half: float, planes: int,

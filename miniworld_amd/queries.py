@@ -1,6 +1,6 @@
 """The world queries of the batched env — navigation fields, explored-area maps, grid sight, grid regions, grid clearance, egocentric map windows,
-depth projection, label frames, object maps, ray casts, scan maps —, each one kernel on the device with no host value: their value classes (NavField,
-SeenMap, EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance, ScanMap) and
+depth projection, label frames, object maps, ray casts, scan maps, scan matching —, each one kernel on the device with no host value: their value
+classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance, ScanMap, ScanMatch) and
 `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
 from __future__ import annotations
 
@@ -122,6 +122,42 @@ class ScanMap:
     gz = property(lambda self: self.params.gz)
     free = property(lambda self: self.map[:, 0])
     obstacle = property(lambda self: self.map[:, 1])
+
+
+class ScanMatch:
+    """Where a scan fits a map (MiniWorldVecEnv.scan_match): `best`, int32[N, 3], the best candidate's (rotation index, a, b) — a whole
+    cells along x (columns), b along z (rows) —, `score`, int32[N], its score, and `volume`, int32[N, K, 2 W + 1, 2 W + 1] indexed
+    [rotation, b + W, a + W], every candidate's score (None when not asked for).  `angles`, float64[K] on the device, are the rotations in
+    radians, centre first: 0, +d, -d, +2d, ...; `rot`, float64[K, 2], their (cos, sin) as the kernel got them; `window` is W, `params` the
+    grid, `max_range` the cut.  The tensors are the caller's."""
+
+    def __init__(self, best, score, volume, angles, rot, pairs, window, params, max_range):
+        self.best, self.score, self.volume, self.angles, self.rot = best, score, volume, angles, rot
+        self.pairs, self.window, self.params, self.max_range = pairs, window, params, max_range     # (pairs: rot's values on the host)
+
+    cell = property(lambda self: self.params.cell)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+
+    def offset(self):
+        """float64[N, 3]: the correction (a * cell, b * cell, the best rotation's angle) in metres and radians — added to a pose estimate's
+        (x, z, dir) —, a new tensor made on the device"""
+        import torch
+        k = self.best[:, 0].long()
+        return torch.stack([self.best[:, 1].double() * self.cell, self.best[:, 2].double() * self.cell, self.angles[k]], 1)
+
+    def apply(self, scan, origin):
+        """(scan', origin'): the scan's directions turned by the best rotation — with the kernel's own (cos, sin) — and the origin
+        (float64[N, 3]) shifted by the best translation, new tensors made on the device, so that scan_map_update(m, scan', origin') is
+        the next line of a mapping loop.  `t` is shared, not copied."""
+        import torch
+        cs, d = self.rot[self.best[:, 0].long()], scan["dir"]
+        c, s = cs[:, None, 0], cs[:, None, 1]
+        turned = torch.stack([c * d[..., 0] + s * d[..., 1], c * d[..., 1] - s * d[..., 0]], -1).contiguous()
+        moved = origin.clone()
+        moved[:, 0] += self.best[:, 1].double() * self.cell
+        moved[:, 2] += self.best[:, 2].double() * self.cell
+        return dict(scan, dir=turned), moved
 
 
 class LabelFrame:
@@ -856,6 +892,69 @@ class WorldQueries:
             scan = self.lidar(m.rays, m.fov, m.max_range, obstacles=m.obstacles)
         e.scan_project(m.params, m.max_range, scan["t"], scan["dir"], m.map, m.count, m.new, origin, mask, clear)
         return m.new
+
+    # ------------------------------------------------------------------ scan matching
+    def scan_match(self, score, scan, origin=None, window=8, turn=0.0, turns=1, max_range=10.0, like=None, cell=0.25, mask=None, volume=False, into=None):
+        """Aligns a range scan to the caller's OWN map — Olson's brute-force correlative scan matcher, what corrects the pose estimate
+        that scan_map_update(origin=) takes —, by one kernel (mw_scan_match) with no host value and no synchronisation: a ScanMatch.
+        Every candidate (rotation, a, b) is scored by the sum of `score`'s bytes under the end cells of the scan's beams, turned by the
+        rotation about `origin` and shifted by (a, b) whole cells; the highest score wins, ties go to the smallest shift, then turn.
+
+        score      uint8[N, gz, gx] contiguous device tensor, the likelihood plane: an obstacle plane made contiguous (bytes 0 / 1), or
+                   better a banded field around it, grid_clearance(m.obstacle != 0, radii, costs).cost.  Checked, never converted
+        scan       a raycast() / lidar() result, or any dict with contiguous float64 "t" [N, R] and "dir" [N, R, 2] on the device, as
+                   for scan_map_update(); only beams with 0 <= t < max_range count
+        origin     float64[N, 3] device tensor (y is not read): the pose estimate's position; None: the agents' positions
+        window     W, 0 .. engine.MATCH_MAX_WINDOW: shifts of -W .. W cells either way
+        turn, turns  the rotations: `turns` of them, an odd number up to engine.MATCH_MAX_ROT, evenly over -turn .. +turn radians
+                   about the scan as given (cos and sin are taken on the host); turns = 1: no rotation, and turn must be 0
+        max_range  metres: a beam that reached it has no end point
+        like       a map or field whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell` metres per cell as in nav_field()
+        mask       uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
+        volume     with the score of every candidate, int32[N, turns, 2 W + 1, 2 W + 1]
+        into       a ScanMatch of an earlier call to write into: its grid, window, rotations, max_range and volume are used; pass only
+                   score, scan, origin and mask
+        The rule in full: include/mwengine.h, "scan matching".  An env whose extent the grid does not cover gets zeros and
+        engine.check() raises once.  ValueError for arguments that make no call; nothing is launched then."""
+        torch, e, n, where = self.torch, self.engine, self.num_envs, "scan_match"
+        if into is not None:
+            if not isinstance(into, ScanMatch):
+                raise ValueError(f"{where}: `into` must be a ScanMatch")
+            if (window, turn, turns, max_range, like, cell, volume) != (8, 0.0, 1, 10.0, None, 0.25, False):
+                raise ValueError(f"{where}: with `into` the record's own grid and parameters are used: pass only score, scan, origin and mask")
+            out = into
+        else:
+            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions, GridClearance, ScanMap), "its own")
+            window = integer(where, "window", window, 0, eng.MATCH_MAX_WINDOW)
+            turns = integer(where, "turns", turns, 1, eng.MATCH_MAX_ROT)
+            turn = real(where, "turn", turn, hi=math.pi, lo_open=False)
+            if turns % 2 == 0 or (turns == 1) != (turn == 0.0):
+                raise ValueError(f"{where}: turns {turns} and turn {turn!r}: an odd count, and 1 exactly with turn = 0")
+            max_range = real(where, "max_range", max_range)
+            if not isinstance(volume, bool):
+                raise ValueError(f"{where}: volume must be True or False, not {volume!r}")
+            d = turn / (turns // 2) if turns > 1 else 0.0
+            angles = [0.0] + [sign * k * d for k in range(1, turns // 2 + 1) for sign in (1.0, -1.0)]
+            rot = [(math.cos(a), math.sin(a)) for a in angles]
+        gz, gx = (out.gz, out.gx) if into is not None else (params.gz, params.gx)
+        if not self._is_tensor(score, (n, gz, gx), torch.uint8):
+            raise ValueError(f"{where}: score is a contiguous uint8 tensor [{n}, {gz}, {gx}] on {e.device}")
+        if not isinstance(scan, dict) or "t" not in scan or "dir" not in scan:
+            raise ValueError(f'{where}: `scan` is a dict with "t" and "dir" (a lidar() result, or raycast()\'s with the directions beside it)')
+        if not self._is_tensor(scan["t"], (n, None)) or not 1 <= scan["t"].shape[1] <= eng.RAY_MAX:
+            raise ValueError(f'{where}: scan["t"] is a contiguous float64 tensor [{n}, R] on {e.device}, R in 1 .. {eng.RAY_MAX}')
+        if not self._is_tensor(scan["dir"], (n, int(scan["t"].shape[1]), 2)):
+            raise ValueError(f'{where}: scan["dir"] is a contiguous float64 tensor [{n}, {int(scan["t"].shape[1])}, 2] on {e.device}')
+        if origin is not None and not self._is_tensor(origin, (n, 3)):
+            raise ValueError(f"{where}: origin is a contiguous float64 tensor [{n}, 3] on {e.device}")
+        mask = self._device_mask(mask, where)
+        if into is None:
+            side = 2 * window + 1
+            out = ScanMatch(torch.zeros((n, 3), dtype=torch.int32, device=e.device), torch.zeros(n, dtype=torch.int32, device=e.device),
+                            torch.zeros((n, turns, side, side), dtype=torch.int32, device=e.device) if volume else None,
+                            torch.tensor(angles, dtype=torch.float64, device=e.device), torch.tensor(rot, dtype=torch.float64, device=e.device), rot, window, params, max_range)
+        e.scan_match(out.params, out.max_range, out.pairs, out.window, score, scan["t"], scan["dir"], out.best, out.score, out.volume, origin, mask)
+        return out
 
     # ------------------------------------------------------------------ label frames
     MESHES = {"exact": eng.LABEL_MESH_EXACT, "bounds": eng.LABEL_MESH_BOUNDS}
