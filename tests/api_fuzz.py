@@ -236,7 +236,7 @@ def apply_model(mv, bank, op):
     elif kind == "step":
         mv.step(op["actions"], repeat=op["repeat"])
     elif kind == "rollout":
-        mv.rollout(np.array(op["plans"]), trace=op["trace"])
+        mv.rollout(np.array(op["plans"]), render=op.get("render", True), trace=op["trace"])
     elif kind == "reset_where":
         mv.reset_where(op["mask"], op["seeds"])
     elif kind == "next_seed":

@@ -6,10 +6,13 @@ domain-randomisation draws from the env's own numpy stream in the reference's or
 frames.  `ModelVec` is a batch of them behind the method names of MiniWorldVecEnv, written from the contracts of include/mwengine.h,
 the MiniWorldVecEnv docstrings and DESIGN §5 — what a call MEANS, in the plainest Python that says it: lists of frames for the stacks,
 field-by-field copies for the snapshot records, a loop over the envs for every call.  tests/test_engine_model_cpu.py checks it here;
-tests/test_gpu_api_fuzz.py drives the engine and this model with the same op sequences.
+tests/test_gpu_api_fuzz.py drives the engine and this model with the same op sequences, tests/test_gpu_query_fuzz.py does so with
+frameless rollouts and world queries between them.
 
-Out of scope: CollectHealth (its respawn draws are pinned through the env API only), navigation fields and ray casts (read-only, each
-has a numpy reference of its own), autoreset="levels" (its loads are the masked loads modelled here), rollout(render=False)."""
+In scope since the query fuzzer: rollout(render=False), the frameless call.  The world queries (navigation fields, ray casts, maps and
+windows) are read-only and not modelled here: tests/query_fuzz.py asks them behind this model's ops, each through its own numpy
+restatement.  Out of scope: CollectHealth (its respawn draws are pinned through the env API only), autoreset="levels" (its loads are
+the masked loads modelled here)."""
 import copy
 import ctypes as C
 import itertools
@@ -183,7 +186,8 @@ class ModelEnv:
 
 
 class ModelSnapshot:
-    """save_state()'s records: `records[k]` a ModelEnv.record() (None: never written), `frames[k]` None or (obs, depth, stack)."""
+    """save_state()'s records: `records[k]` a ModelEnv.record() (None: never written), `frames[k]` None or (obs, depth, stack, and
+    whether the stack is due a rebuild)."""
 
     def __init__(self, capacity, with_frames):
         self.capacity, self.count, self.with_frames = int(capacity), 0, bool(with_frames)
@@ -229,6 +233,8 @@ class ModelVec:
         self.clean, self.clean_known, self._left = np.zeros(N, np.uint8), np.ones(N, bool), np.zeros(N, bool)
         self._last_key = [None] * N
         self._recent = [[] for _ in range(N)]
+        # the env began an episode in a frameless call since its last push: its next push, or the next refresh, rebuilds its stack
+        self._stack_fresh = np.zeros(N, bool)
 
     # ------------------------------------------------------------------ frames
     def _render(self, env, scene, key):
@@ -248,20 +254,23 @@ class ModelVec:
 
     def _rebuild(self, i):
         """a new episode's stack: K copies of its first frame, or K - 1 all-zero frames and the frame"""
+        self._stack_fresh[i] = False
         if self.K:
             f = self.obs[i].copy()
             self.stack[i] = [f if self.pad == "reset" else np.zeros_like(f)] * (self.K - 1) + [f]
 
     def _push(self, i):
-        if self.K:
+        if self._stack_fresh[i]:
+            self._rebuild(i)
+        elif self.K:
             self.stack[i] = self.stack[i][1:] + [self.obs[i].copy()]
 
     def _redraw(self, rebuilt=()):
         """mw_render + mw_stack_refresh: every env's frame drawn from its state as it is now; the stacks of the envs whose world a
-        reset or a load wrote since their last push rebuilt, every other stack left alone"""
+        reset or a load wrote since their last push rebuilt — or a frameless call installed —, every other stack left alone"""
         for i, e in enumerate(self.envs):
             self._show(i, self._render(e, e.scene_now(), e.key()))
-        for i in rebuilt:
+        for i in sorted(set(rebuilt) | set(np.flatnonzero(self._stack_fresh).tolist())):
             self._rebuild(i)
         return self.obs
 
@@ -302,9 +311,14 @@ class ModelVec:
 
     TRACE_DEFAULT = ("agent_pos", "agent_dir", "carrying")
 
-    def rollout(self, plans, trace=None, trace_ent=None):
+    def rollout(self, plans, render=True, trace=None, trace_ent=None):
         names = None if trace in (None, False) else self.TRACE_DEFAULT if trace is True else tuple(trace)
         slot = self.envs[0].dyn_kw["goal_ent"] if trace_ent is None else trace_ent
+        if not render:
+            if self.mode == "seeds":
+                raise ValueError("rollout(render=False) with autoreset='seeds': a frameless call cannot seed the envs that finish in it")
+            self._advance_frameless(np.asarray(plans), names, slot)
+            return None, self.reward, self.terminated, self.truncated
         self._advance(np.asarray(plans), names, slot)
         return self.obs, self.reward, self.terminated, self.truncated
 
@@ -386,6 +400,51 @@ class ModelVec:
             self._push(i)
         self.trace = None if names is None else {name: np.array([[rows[k][i][name] for i in range(N)] for k in range(T)]) for name in names}
 
+    def _advance_frameless(self, plans, names, slot):
+        """mw_step_plan with d_obs == NULL: the sub-steps, rewards, flags, traces and the auto-reset of a drawn rollout and nothing that
+        draws — obs, depth, the stacks and the final rows keep what they held.  Behind the last executed sub-step what the frame's
+        tail would have done is done: the picked-up object has left the list (the state IS what a frame drawn now shows).  The clean
+        byte promises nothing afterwards, and the next push rebuilds the stack of an env that began an episode in here."""
+        T, N = plans.shape
+        self.step_rewards = np.zeros((T, N), np.float32)
+        rows = [[None] * N for _ in range(T)]
+        for i, e in enumerate(self.envs):
+            self._after_pickup[i] = False
+            if self.mode == "next_step" and self.pending[i]:
+                for k in range(T):
+                    rows[k][i] = self._trace_row(e, slot)
+                e.reset()
+                self.pending[i], self._left[i], self._stack_fresh[i] = 0, False, True
+                self.reward[i], self.terminated[i], self.truncated[i], self.substeps[i] = 0.0, 0, 0, 0
+                continue
+            total, te, tr, n = 0.0, False, False, 0
+            for k in range(T):
+                alive0 = sum(bool(e.dyn.ents[j].alive) for j in range(e.E))
+                r, te, tr = e.substep(int(plans[k, i]))
+                self._after_pickup[i] = sum(bool(e.dyn.ents[j].alive) for j in range(e.E)) < alive0
+                self._left[i] = self._after_pickup[i]
+                total += r
+                self.step_rewards[k, i] = np.float32(r)
+                rows[k][i] = self._trace_row(e, slot)
+                n += 1
+                if te or tr:
+                    break
+            for k in range(n, T):
+                rows[k][i] = rows[n - 1][i]
+            self.reward[i], self.terminated[i], self.truncated[i], self.substeps[i] = np.float32(total), te, tr, n
+            C.memmove(e.dyn.render_ents, e.dyn.ents, C.sizeof(e.dyn.ents))        # the tail: nothing is left to be shown one last time
+            if te or tr:
+                self.cov["ends"] += 1
+                self.cov["early_ends"] += n < T
+                self._after_pickup[i] = False
+                if self.mode == "same_step":
+                    e.reset()
+                    self._left[i], self._stack_fresh[i] = False, True
+                elif self.mode == "next_step":
+                    self.pending[i] = 1
+        self.clean[:], self.clean_known[:] = 0, False
+        self.trace = None if names is None else {name: np.array([[rows[k][i][name] for i in range(N)] for k in range(T)]) for name in names}
+
     @staticmethod
     def _clean_key(e):
         ag = e.dyn.ag
@@ -416,7 +475,8 @@ class ModelVec:
 
     # ------------------------------------------------------------------ save / load / fork
     def _frame_record(self, i):
-        return (self.obs[i].copy(), None if self.depth is None else self.depth[i].copy(), None if not self.K else list(self.stack[i]))
+        return (self.obs[i].copy(), None if self.depth is None else self.depth[i].copy(), None if not self.K else list(self.stack[i]),
+                bool(self._stack_fresh[i]))
 
     def save_state(self, envs=None, capacity=None, frames=False, into=None, records=None):
         envs = list(range(self.N)) if envs is None else [int(i) for i in envs]
@@ -447,7 +507,7 @@ class ModelVec:
             self.pending[i], self._left[i] = rec["pending"], rec["left"]
             self.clean[i], self.clean_known[i] = 0, True
             if frames:
-                obs, depth, stack = snap.frames[k]
+                obs, depth, stack, self._stack_fresh[i] = snap.frames[k]
                 self.obs[i] = obs
                 if self.depth is not None:
                     self.depth[i] = depth

@@ -48,7 +48,7 @@ def apply_engine(vec, bank, op):
     elif kind == "step":
         vec.step(_dev(op["actions"], torch.int32), repeat=op["repeat"])
     elif kind == "rollout":
-        vec.rollout(_dev(op["plans"], torch.int32), trace=op["trace"])
+        vec.rollout(_dev(op["plans"], torch.int32), render=op.get("render", True), trace=op["trace"])
     elif kind == "reset_where":
         vec.reset_where(op["mask"], op["seeds"])
     elif kind == "next_seed":
