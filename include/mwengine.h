@@ -826,7 +826,7 @@ int mw_ray_cast(mw_engine *e, const mw_ray_params *params, const uint8_t *d_mask
                 double *d_t /* [N][R] */, int32_t *d_hit /* [N][R] or NULL */, double *d_dir_out /* [N][R][2] or NULL */,
                 void *stream);
 /* measurements: form 1 casts every ray count with a ray per lane, 2 with an obstacle per lane (the same bits either way), 0 leaves the
- * choice to the ray count again */
+ * choice to the ray count again.  mw_grid_ray_cast follows the same switch: 1 its staged form, 2 its unstaged one. */
 int mw_debug_set_ray_form(mw_engine *e, int form);
 
 /* ---- explored-area maps ------------------------------------------------------ */
@@ -1304,6 +1304,49 @@ int mw_scan_match(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are re
                   const double *d_dir /* [N][R][2]: dx, dz */, const double *d_origin /* [N][3] or NULL = the agents */, const uint8_t *d_mask,
                   int32_t *d_best /* [N][3]: r, a, b */, int32_t *d_best_score /* [N] */, int32_t *d_volume /* [N][K][2W+1][2W+1] or NULL */,
                   void *stream);
+/* ---- grid ray casts ---------------------------------------------------------- */
+/* mw_ray_cast on the caller's OWN map: what a ray from a pose meets first among the opaque cells of a uint8 grid, and how far away — the
+ * predicted scan of a beam-model localiser or a scan-to-map residual, string pulling and pose-to-pose free-path tests on a sensed map
+ * (mw_grid_sight sees from cell centre to cell centre only).  It is the inverse of mw_scan_project on the same arithmetic: that call
+ * marks the cells a beam crosses, this one returns the first of those cells that is opaque and the parameter at which the ray enters it.
+ * The reference has no such call.
+ *
+ * The rule.  All arithmetic is float64, only + - * / and floor, uncontracted, in exactly this order.  Per env: min_x, min_z the env's own
+ * extent, cell, gx, gz the grid's, word for word as for mw_scan_project; E = max_t = host_range[0].  Per ray k: (ox, oz) = d_origin[i][k]'s
+ * x and z (y is not read) or, with a null d_origin, the agent's position the device holds now; (dx, dz) = d_dir[i][k], of any length, or,
+ * with a null d_dir, mw_ray_cast's fan: ang = heading + d_offsets[k], (dx, dz) = (cos, -sin) through the engine's deterministic sin / cos
+ * (|ang| >= 1e6 or NaN: a NaN direction), where heading = d_heading[i] if given — a pose estimate's — and agent_dir[i] else.
+ *   u0 = (ox - min_x) / cell;  w0 = (oz - min_z) / cell;  gu = dx / cell;  gw = dz / cell
+ *   u1 = u0 + E * gu;          w1 = w0 + E * gw
+ *   the ray is dropped (t = max_t, hit = -1) unless u0, w0, u1, w1 are all finite and below 2^30 in magnitude (a NaN fails)
+ * The candidates of a kept ray are pairs (s, cell), in closed form — nothing is accumulated along the ray:
+ *   the start cell (floor(w0), floor(u0)), as (row, column), with s = 0
+ *   for every x line L the ray crosses — gu > 0: L = floor(u0) + 1 .. floor(u1); gu < 0: L = floor(u1) + 1 .. floor(u0); gu == 0: none;
+ *   L clipped to the grid's own lines 0 .. gx first —: s = ((double)L - u0) / gu + 0.0, column gu > 0 ? L : L - 1, row floor(w0 + s * gw)
+ *   (the bits of mw_scan_project's row: its ((double)L - u0) / gu * gw is this s * gw; the + 0.0 makes the -0 of a ray that starts on a
+ *   line and leaves it backwards the +0 of its start cell)
+ *   the mirrored candidates for the z lines: L from w0, w1 and gw, clipped to 0 .. gz; s = ((double)L - w0) / gw + 0.0, row gw > 0 ? L :
+ *   L - 1, column floor(u0 + s * gu)
+ * A candidate COUNTS only if row >= 0 && row < gz && column >= 0 && column < gx, compared as doubles before any conversion, and
+ * d_opaque[i][row][column] != 0: cells outside the grid are never opaque, and a ray that starts outside may enter.  The hit is the
+ * counting candidate of least s; equal s goes to the lowest flat index row * gx + column.  d_hit = that index, d_t = s < max_t ? s :
+ * max_t (an s the rounding put past max_t still names its cell); with no counting candidate d_t = max_t and d_hit = -1.  A zero direction
+ * hits only an opaque start cell, at 0.  d_dir_out, if given, gets the (dx, dz) used, for dropped rays too.
+ * An env whose extent the grid does not cover (as for mw_nav_build) gets max_t / -1 rows (and its directions) and sets the status bit
+ * mw_scan_project sets there: the next mw_check reports it as MW_E_INVALID, once.  Rows of envs under a zero mask byte are neither read nor
+ * written.  Every result is a value the rule defines: the least (s, index) of a set, so nothing depends on the kernel's schedule.
+ *
+ * One kernel (of two forms with the same bits, chosen by R), asynchronous on `stream`; it reads no host value except host_range (during
+ * the call), reads live arrays only and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched: a
+ * null engine, grid, host_range, d_opaque or d_t; a grid mw_nav_build would refuse (cell <= 0 or not finite, gx or gz < 1, more than
+ * MW_NAV_MAX_CELLS cells); R outside 1 .. MW_RAY_MAX; a max_t that is not > 0 and finite; both or neither of d_dir / d_offsets; d_heading
+ * with d_dir; more workgroups than a launch holds. */
+int mw_grid_ray_cast(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */,
+                     const double *host_range /* [1] on the host: max_t */, int32_t R, const uint8_t *d_mask,
+                     const uint8_t *d_opaque /* [N][gz][gx] */, const double *d_origin /* [N][R][3] or NULL = the agents */,
+                     const double *d_dir /* [N][R][2]: dx, dz, or NULL */, const double *d_offsets /* [R], radians: the fan, or NULL */,
+                     const double *d_heading /* [N], with d_offsets, or NULL = the agents' */, double *d_t /* [N][R] */,
+                     int32_t *d_hit /* [N][R] or NULL */, double *d_dir_out /* [N][R][2] or NULL */, void *stream);
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.
@@ -1315,7 +1358,7 @@ int mw_scan_match(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are re
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match or mw_label_project skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match, mw_grid_ray_cast or mw_label_project skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

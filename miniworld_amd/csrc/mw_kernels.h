@@ -20,6 +20,7 @@
 #include "mw_clear.h"
 #include "mw_scan.h"
 #include "mw_match.h"
+#include "mw_gridray.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -380,6 +381,22 @@ extern "C" __global__ void mw_match_kernel(MwNavArgs a, mw_nav_params p, double 
                                            const uint8_t *__restrict__ score, const double *__restrict__ t, const double *__restrict__ dir,
                                            const double *__restrict__ origin, const uint8_t *__restrict__ mask, int32_t *__restrict__ best,
                                            int32_t *__restrict__ best_score, int32_t *__restrict__ volume);
+
+// grid ray casts (mw_gridray.hip; the rule, the half-rays, the walks and the launch constants: mw_gridray.h; the choice of form:
+// mwpolicy::gridray_launch).  The grid (cell, gx, gz are read) and max_t travel by value; of the view the extent, with a null origin ax / az
+// and in fan mode adir (heading, double[N], in its place where given) are read.  opaque uint8[N][gz][gx]; origin double[N][R][3] or null
+// = the agents; exactly one of dir (double[N][R][2]) and offsets (double[R], the fan) non-null; hit and dir_out may be null; an env under
+// a zero mask byte is skipped.
+//   bits   grid N workgroups of MW_GRIDRAY_THREADS lanes, a half-ray per lane, mwgray::staged_bytes(cells) bytes of dynamic LDS
+//   waves  grid N * ceil(R / 2) workgroups of MW_GRIDRAY_THREADS lanes, a wavefront per half-ray, no dynamic LDS
+extern "C" __global__ void mw_gridray_bits_kernel(MwRayArgs a, mw_nav_params p, double max_t, int R, const uint8_t *__restrict__ mask,
+                                                  const uint8_t *__restrict__ opaque, const double *__restrict__ origin, const double *__restrict__ dir,
+                                                  const double *__restrict__ offsets, const double *__restrict__ heading, double *__restrict__ t_out,
+                                                  int32_t *__restrict__ hit_out, double *__restrict__ dir_out);
+extern "C" __global__ void mw_gridray_waves_kernel(MwRayArgs a, mw_nav_params p, double max_t, int R, const uint8_t *__restrict__ mask,
+                                                   const uint8_t *__restrict__ opaque, const double *__restrict__ origin, const double *__restrict__ dir,
+                                                   const double *__restrict__ offsets, const double *__restrict__ heading, double *__restrict__ t_out,
+                                                   int32_t *__restrict__ hit_out, double *__restrict__ dir_out);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -18,6 +18,7 @@
 #include "mw_clear.h"           // MW_CLEAR_THREADS, mwclear::off_bytes
 #include "mw_scan.h"            // MW_SCAN_THREADS, mwscan::plane_bytes, prefix_bytes
 #include "mw_match.h"           // MW_MATCH_THREADS, mwmatch::plane_bytes, ends_bytes, fill_bytes
+#include "mw_gridray.h"         // MW_GRIDRAY_THREADS, mwgray::staged_bytes
 #include "mw_shape.h"
 #include "mw_snapframes.h"     // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -498,6 +499,27 @@ inline MatchLaunch match_launch(int N, int gz, int gx, int rays, int window, int
     int batch = MW_MATCH_THREADS / per;
     batch = batch > most ? most : batch < 1 ? 1 : batch;
     return {(unsigned long long)N, MW_MATCH_THREADS, mwmatch::plane_bytes(cells, quad) + mwmatch::ends_bytes(rays, batch) + mwmatch::fill_bytes(), true, quad, batch};
+}
+
+// Grid ray casts (mw_grid_ray_cast; kernels: mw_gridray.hip).  The form follows from the rays per env alone, as ray_launch's: from
+// kGridRayStagedFrom rays on, a workgroup per env with the opaque row staged as bits in LDS and a half-ray per lane (its LDS: a key per
+// pair of lanes and the bits, 1 + 4 KiB at MW_NAV_MAX_CELLS); below it a wavefront per half-ray that probes the bytes where they lie, two
+// rays per workgroup, each workgroup inside one env.  Both produce the same bits.
+// Measured (profiles/r45, device us per grid_lidar call on a DepthMap after 40 steps, staged / unstaged, three windows): Hallway x 4096:
+// R = 1: 28 / 19, 4: 34 / 25, 8: 35 / 46, 16: 35 / 87, 64: 45 / 340; FourRooms x 4096: 1: 31 / 19, 4: 40 / 25, 8: 41 / 46, 16: 41 / 89,
+// 64: 54 / 341; Maze x 1024: 1: 21 / 19, 8: 25 / 18, 16: 23 / 25, 64: 23 / 88.  The unstaged form doubles with R, the staged one is flat
+// up to a round of 128 rays: they cross between 4 and 8 rays at 4096 envs and between 8 and 16 at 1024, so 8 — mw_ray_cast's 64, where
+// this started, left 16 .. 63 rays up to 6 x behind.  String pulling's 6 and a free-path test's 1 stay unstaged.
+// forced: mw_debug_set_ray_form's value — 1 the staged form, 2 the unstaged one for every ray count.  fits: a positive count of no more
+// cells than MW_NAV_MAX_CELLS and 1 .. MW_RAY_MAX rays — the caller refuses what does not.
+constexpr int kGridRayStagedFrom = 8;
+struct GridRayLaunch { bool staged; unsigned long long grid; int threads; size_t lds; bool fits; };
+inline GridRayLaunch gridray_launch(int N, long long cells, int R, int forced = 0)
+{
+    const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS && R >= 1 && R <= MW_RAY_MAX;
+    if (!fits) return {false, (unsigned long long)N, MW_GRIDRAY_THREADS, 0, false};
+    if (forced ? forced == 1 : R >= kGridRayStagedFrom) return {true, (unsigned long long)N, MW_GRIDRAY_THREADS, mwgray::staged_bytes(cells), true};
+    return {false, (unsigned long long)N * (unsigned long long)((R + 1) / 2), MW_GRIDRAY_THREADS, 0, true};
 }
 
 }  // namespace mwpolicy

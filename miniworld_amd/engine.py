@@ -250,6 +250,7 @@ SIGNATURES = {
     "mw_debug_set_nav_passes": _sig(vp, vp),
     "mw_ray_cast": _sig(vp, P(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_ray_form": _sig(vp, C.c_int),
+    "mw_grid_ray_cast": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_grid_regions": _sig(vp, P(MwNavParams), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_grid_clearance": _sig(vp, P(MwNavParams), i32, P(i32), i32, vp, vp, vp, vp, vp, vp),
     "mw_scan_project": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
@@ -588,8 +589,35 @@ class Engine:
                                          _stream_ptr(self.device)), "mw_ray_cast")
 
     def debug_set_ray_form(self, form: int):
-        """Measurements: 1 casts every ray count with a ray per lane, 2 with an obstacle per lane, 0 by the ray count again."""
+        """Measurements: 1 casts every ray count with a ray per lane, 2 with an obstacle per lane, 0 by the ray count again.
+        grid_ray_cast follows the same switch: 1 its staged form, 2 its unstaged one."""
         self._check(self.lib.mw_debug_set_ray_form(self.h, int(form)), "mw_debug_set_ray_form")
+
+    # -- grid ray casts ------------------------------------------------------------------
+    def grid_ray_cast(self, params: MwNavParams, max_t: float, rays: int, opaque, t, hit=None, dir_out=None, mask=None, origin=None, direction=None,
+                      offsets=None, heading=None):
+        """mw_grid_ray_cast: `rays` rays per env under `mask` (uint8[N], device; None = all) over `opaque` (uint8[N, gz, gx]) from `origin`
+        (float64[N, R, 3], device; None = the agents) along `direction` (float64[N, R, 2]) or the fan `offsets` (float64[R], radians from
+        `heading`, float64[N], or from each agent's own) into t (float64[N, R]: the parameter at which the ray enters its first opaque
+        cell, max_t for none), hit (int32[N, R]: that cell's flat index, -1) and dir_out (float64[N, R, 2]), the last two optional.  One
+        kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the library
+        is called."""
+        import torch
+        n = self.N * int(rays)
+        if opaque is None or t is None:
+            raise EngineError(f"{'opaque' if opaque is None else 't'}: None")
+        self._shaped_tensor(opaque, "opaque", torch.uint8, (self.N, int(params.gz), int(params.gx)))
+        self._dev_tensor(t, "t", torch.float64, n)
+        self._dev_tensor(hit, "hit", torch.int32, n)
+        self._dev_tensor(dir_out, "dir_out", torch.float64, n * 2)
+        self._dev_tensor(origin, "origin", torch.float64, n * 3)
+        self._dev_tensor(direction, "direction", torch.float64, n * 2)
+        self._dev_tensor(offsets, "offsets", torch.float64, int(rays))
+        self._dev_tensor(heading, "heading", torch.float64, self.N)
+        mask = self._mask_tensor(mask, optional=True)
+        host = (C.c_double * 1)(float(max_t))
+        self._check(self.lib.mw_grid_ray_cast(self.h, C.byref(params), host, int(rays), _ptr(mask), _ptr(opaque), _ptr(origin), _ptr(direction), _ptr(offsets),
+                                              _ptr(heading), _ptr(t), _ptr(hit), _ptr(dir_out), _stream_ptr(self.device)), "mw_grid_ray_cast")
 
     # -- explored-area maps --------------------------------------------------------------
     def seen_update(self, params: MwNavParams, max_range: float, cos_half: float, flags: int, seen, count, new=None, mask=None, clear=None):

@@ -1170,3 +1170,84 @@ class WorldQueries:
         buf[1] = self.raycast(offsets=buf[0], max_t=max_range, radius=radius, obstacles=obstacles, into=buf[1])
         return buf[1]
 
+    # ------------------------------------------------------------------ grid ray casts
+    def grid_raycast(self, opaque, direction=None, origin=None, offsets=None, heading=None, max_t=1.0, like=None, cell=0.25, mask=None, into=None):
+        """raycast() on the caller's OWN map: what R rays per env meet first among the opaque cells of a grid, by one kernel
+        (mw_grid_ray_cast) with no host value and no synchronisation: {"t": float64[N, R], "hit": int32[N, R], "dir": float64[N, R, 2]}.
+
+        Ray k of env i is origin + t * direction, t in 0 .. max_t; "t" is the parameter at which it enters the first opaque cell — 0
+        when it starts in one —, "hit" that cell's flat index row * gx + column; max_t and -1 where it meets none.  With unit
+        directions t is metres; with direction = B - A and max_t = 1, hit == -1 says that the way from A to B is free on this map.
+        opaque     uint8 or bool [N, gz, gx] device tensor: != 0 a cell that stops a ray (a DepthMap's or ScanMap's obstacle plane made
+                   contiguous, grid_clearance's inflated plane for a disc, the caller's own raster).  Cells outside the grid stop nothing
+        direction  float64[N, R, 2] device tensor of (dx, dz), any length; or
+        offsets    float64[R] device tensor of angles in radians added to a heading (raycast()'s fan), with
+        heading    float64[N] device tensor, a pose estimate's heading per env; None: each agent's own
+        origin     float64[N, R, 3] device tensor (y is not read); None: each env's agent position for all its rays
+        like       a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
+                   metres per cell as in nav_field()
+        mask       uint8[N] or bool[N] device tensor: only those envs' rows are read and written
+        into       a previous result of the same R to write into; without it new tensors are allocated (unmasked rows: t = max_t,
+                   hit = -1, dir = 0)
+        "dir" holds the directions used, so that the result is a `scan` of scan_map_update() and scan_match() as a lidar() one is.  The
+        rule in full: include/mwengine.h, "grid ray casts"; a NaN in a ray gives max_t and -1.  The tensors are checked and never
+        converted.  ValueError for arguments that make no cast; nothing is launched then."""
+        torch, e, n, ok = self.torch, self.engine, self.num_envs, self._is_tensor
+        params = self._map_grid("grid_raycast", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
+        if (direction is None) == (offsets is None):
+            raise ValueError("grid_raycast: give exactly one of direction (float64[N, R, 2]) and offsets (float64[R])")
+        if offsets is not None:
+            if not ok(offsets, (None,)):
+                raise ValueError(f"grid_raycast: offsets is a contiguous float64 tensor [R] on {e.device}")
+            rays = int(offsets.shape[0])
+            if heading is not None and not ok(heading, (n,)):
+                raise ValueError(f"grid_raycast: heading is a contiguous float64 tensor [{n}] on {e.device}")
+        else:
+            if heading is not None:
+                raise ValueError("grid_raycast: heading without offsets: a heading turns the fan")
+            if not ok(direction, (n, None, 2)):
+                raise ValueError(f"grid_raycast: direction is a contiguous float64 tensor [{n}, R, 2] on {e.device}")
+            rays = int(direction.shape[1])
+        if not 1 <= rays <= eng.RAY_MAX:
+            raise ValueError(f"grid_raycast: {rays} rays per env outside 1 .. {eng.RAY_MAX}")
+        if origin is not None and not ok(origin, (n, rays, 3)):
+            raise ValueError(f"grid_raycast: origin is a contiguous float64 tensor [{n}, {rays}, 3] on {e.device}")
+        max_t = real("grid_raycast", "max_t", max_t)
+        opaque = self._cell_grid("grid_raycast", "opaque", opaque, params.gz, params.gx, optional=False)
+        mask = self._device_mask(mask, "grid_raycast")
+        want = {"t": (torch.float64, (n, rays), max_t), "hit": (torch.int32, (n, rays), -1), "dir": (torch.float64, (n, rays, 2), 0.0)}
+        if into is not None:
+            if not isinstance(into, dict) or set(into) != set(want):
+                raise ValueError(f"grid_raycast: `into` is a previous result with the keys {tuple(want)}")
+            for k, (dtype, shape, _) in want.items():
+                if not ok(into[k], shape, dtype):
+                    raise ValueError(f"grid_raycast: into[{k!r}] is a contiguous {dtype} tensor {list(shape)} on {e.device}")
+        out = into or {k: torch.full(shape, fill, dtype=dtype, device=e.device) for k, (dtype, shape, fill) in want.items()}
+        e.grid_ray_cast(params, max_t, rays, opaque, out["t"], out["hit"], out["dir"], mask, origin, direction, offsets, heading)
+        return out
+
+    def grid_lidar(self, opaque, rays=64, fov=2 * math.pi, max_range=10.0, heading=None, origin=None, like=None, cell=0.25):
+        """The scan a pose would give on the caller's OWN map — lidar() predicted from a map and a pose estimate: grid_raycast() with
+        lidar()'s evenly spaced offsets, unit directions and max_t = max_range.  Returns {"t", "hit", "dir"} as lidar() does, "hit" a flat
+        cell index; the tensors are this env's own, reused between calls of the same (rays, fov).
+        heading  float64[N] device tensor: the estimate's heading; None: each agent's own
+        origin   float64[N, 3] device tensor (y is not read): the estimate's position, for all the env's rays; None: each agent's own"""
+        torch, e, n = self.torch, self.engine, self.num_envs
+        rays, fov = integer("grid_lidar", "rays", rays, 1, eng.RAY_MAX), real("grid_lidar", "fov", fov, hi=2 * math.pi)
+        if origin is not None and not self._is_tensor(origin, (n, 3)):
+            raise ValueError(f"grid_lidar: origin is a contiguous float64 tensor [{n}, 3] on {e.device}")
+        key = (rays, fov, "grid")       # (lidar()'s offsets, in a slot of its own: offsets, the result, the origin per ray)
+        if key not in self._lidar_bufs:
+            if fov < 2 * math.pi:
+                off = [0.0] if rays == 1 else [-fov / 2 + k * fov / (rays - 1) for k in range(rays)]
+            else:
+                off = [k * 2 * math.pi / rays for k in range(rays)]
+            self._lidar_bufs[key] = [torch.tensor(off, dtype=torch.float64, device=e.device), None, None]
+        buf = self._lidar_bufs[key]
+        if origin is not None:
+            if buf[2] is None:
+                buf[2] = torch.empty((n, rays, 3), dtype=torch.float64, device=e.device)
+            buf[2].copy_(origin[:, None, :].expand(-1, rays, -1))      # (one copy kernel into a kept buffer: no allocation per call)
+        buf[1] = self.grid_raycast(opaque, origin=buf[2] if origin is not None else None, offsets=buf[0], heading=heading, max_t=max_range, like=like, cell=cell,
+                                   into=buf[1])
+        return buf[1]
