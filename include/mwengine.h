@@ -1304,6 +1304,63 @@ int mw_scan_match(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are re
                   const double *d_dir /* [N][R][2]: dx, dz */, const double *d_origin /* [N][3] or NULL = the agents */, const uint8_t *d_mask,
                   int32_t *d_best /* [N][3]: r, a, b */, int32_t *d_best_score /* [N] */, int32_t *d_volume /* [N][K][2W+1][2W+1] or NULL */,
                   void *stream);
+/* ---- scan weighing and resampling -------------------------------------------- */
+/* The localiser that holds more than one hypothesis: the likelihood-field measurement update of Monte Carlo localisation and its
+ * resampling step.  mw_scan_match scores whole-cell shifts inside a window around one estimate; mw_scan_weigh scores P free poses
+ * (x, z, turn) per env anywhere on the map — global localisation, a kidnapped agent — on the same arithmetic, and mw_resample draws the
+ * next generation from the weights without a visit to the host.  The reference has no such calls.
+ *
+ * The weighing rule.  All arithmetic is float64, only + - * / and floor, uncontracted, in exactly this order.  Per env: min_x, min_z, cell,
+ * gx, gz and max_range = host_range[0] as for mw_scan_project, and per beam k with t = d_t[i][k], (dx, dz) = d_dir[i][k], of any length:
+ *   gu = dx / cell;  gw = dz / cell                                                               (mw_scan_match's, bit for bit)
+ * Per particle p with (x, z, c, s) = d_pose[i][p] — (c, s) the caller's cosine and sine: no trigonometry runs on the device, and the pair
+ * is not normalised, as for host_rot —:
+ *   u0 = (x - min_x) / cell;  w0 = (z - min_z) / cell
+ *   ru = c * gu + s * gw;  rw = c * gw - s * gu
+ *   u1 = u0 + t * ru;  w1 = w0 + t * rw
+ * Beam k COUNTS for particle p iff t >= 0 && t < max_range and u0, w0, u1, w1 are all strictly inside -2^30 .. 2^30.  A NaN anywhere
+ * fails: a NaN pose counts no beam and scores 0.  The end cell of a counting beam is (row, col) = (floor(w1), floor(u1)); it is INSIDE iff
+ * 0 <= row < gz and 0 <= col < gx, tested before any index is formed.
+ *   d_out[i][p]     the sum over p's counting beams of d_score[i][row][col] of the inside end cells.  An int32: at most 4096 * 255.
+ *   d_inside[i][p]  how many counting beams of p ended inside (if given)
+ *   d_best[i]       (p, score) of the particle of the highest score, the lowest p on ties (if given)
+ * With (x, z) = mw_scan_match's d_origin x and z and (c, s) = host_rot[r], d_out is mw_scan_match's score(r, 0, 0), bit for bit.
+ * For every env i with d_mask[i] != 0 (or a null d_mask).  An env whose extent the grid does not cover (as for mw_nav_build) gets zeros,
+ * best (0, 0), and sets the status bit mw_scan_project sets there: the next mw_check reports it as MW_E_INVALID, once.  Rows of envs under
+ * a zero mask byte are neither read nor written.  Every result is an integer the rule defines, so nothing depends on the kernel's
+ * schedule.
+ *
+ * One kernel (of two forms with the same bits, chosen by P), one workgroup per env, asynchronous on `stream`; host_range is read during the
+ * call; it reads no other host value, reads live arrays only and changes nothing in the engine.  MW_E_INVALID before anything is
+ * launched, and nothing touched: a null engine, grid, host_range, d_score, d_t, d_dir, d_pose or d_out; a grid mw_nav_build would refuse;
+ * R outside 1 .. MW_RAY_MAX; P outside 1 .. MW_WEIGH_MAX_PARTICLES; a max_range that is not > 0 and finite; more workgroups than a launch
+ * holds. */
+#define MW_WEIGH_MAX_PARTICLES 4096     /* particles per env and call */
+int mw_scan_weigh(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */,
+                  const double *host_range /* [1] on the host: max_range */, int32_t R, int32_t P, const uint8_t *d_score /* [N][gz][gx] */,
+                  const double *d_t /* [N][R] */, const double *d_dir /* [N][R][2]: dx, dz */, const double *d_pose /* [N][P][4]: x, z, c, s */,
+                  const uint8_t *d_mask, int32_t *d_out /* [N][P]: score */, int32_t *d_inside /* [N][P] or NULL */,
+                  int32_t *d_best /* [N][2]: p, score; or NULL */, void *stream);
+/* tests and measurements: 0 lets P choose mw_scan_weigh's form again, 1 weighs every count with a particle per lane, 2 with a wavefront
+ * per particle.  The results are the same bits.  MW_E_INVALID: a null engine, a form outside 0 .. 2. */
+int mw_debug_set_weigh_form(mw_engine *e, int form);
+/* The resampling rule: systematic (low-variance) resampling, all in unsigned 64-bit integers.  Per env i with the weights w_p =
+ * d_weight[i][p], p = 0 .. P - 1:
+ *   S = the sum of the weights
+ *   S == 0:  d_ancestor[i][j] = j
+ *   else:    o = d_offset[i] % S;  C_p = w_0 + ... + w_p;  T_j = (j * S + o) / P  (floor; j * S + o < P * S <= 2^56)
+ *            d_ancestor[i][j] = the least p with C_p > T_j
+ * so the ancestors are non-decreasing in j and particle p is drawn floor(P * w_p / S) or ceil(P * w_p / S) times; a particle of weight 0
+ * is never drawn.  With d_pose, d_pose_out[i][j] = d_pose[i][d_ancestor[i][j]], four doubles as they are; the two buffers may not overlap.
+ * For every env i with d_mask[i] != 0 (or a null d_mask); rows of envs under a zero mask byte are neither read nor written.  The call
+ * takes no grid and reads nothing of the world: there is no uncovered-extent case.
+ *
+ * One kernel, one workgroup per env, asynchronous on `stream`; it reads no host value and changes nothing in the engine.  MW_E_INVALID
+ * before anything is launched, and nothing touched: a null engine, d_weight, d_offset or d_ancestor; P outside 1 ..
+ * MW_WEIGH_MAX_PARTICLES; only one of d_pose / d_pose_out; more workgroups than a launch holds. */
+int mw_resample(mw_engine *e, int32_t P, const uint32_t *d_weight /* [N][P] */, const uint64_t *d_offset /* [N] */, const uint8_t *d_mask,
+                int32_t *d_ancestor /* [N][P] */, const double *d_pose /* [N][P][4] or NULL */, double *d_pose_out /* [N][P][4], with d_pose */,
+                void *stream);
 /* ---- grid ray casts ---------------------------------------------------------- */
 /* mw_ray_cast on the caller's OWN map: what a ray from a pose meets first among the opaque cells of a uint8 grid, and how far away — the
  * predicted scan of a beam-model localiser or a scan-to-map residual, string pulling and pose-to-pose free-path tests on a sensed map
@@ -1358,7 +1415,7 @@ int mw_grid_ray_cast(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match, mw_grid_ray_cast or mw_label_project skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match, mw_scan_weigh, mw_grid_ray_cast or mw_label_project skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

@@ -21,6 +21,7 @@
 #include "mw_scan.h"
 #include "mw_match.h"
 #include "mw_gridray.h"
+#include "mw_weigh.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -397,6 +398,21 @@ extern "C" __global__ void mw_gridray_waves_kernel(MwRayArgs a, mw_nav_params p,
                                                    const uint8_t *__restrict__ opaque, const double *__restrict__ origin, const double *__restrict__ dir,
                                                    const double *__restrict__ offsets, const double *__restrict__ heading, double *__restrict__ t_out,
                                                    int32_t *__restrict__ hit_out, double *__restrict__ dir_out);
+
+// scan weighing and resampling (mw_weigh.hip; the rules, the arrays, the phases and the launch constant: mw_weigh.h; the launches:
+// mwpolicy::weigh_launch, resample_launch).  Grid N workgroups of MW_WEIGH_THREADS lanes each.
+//   weigh     of the view the extent is read.  waves != 0: a wavefront per particle, else a particle per lane; score uint8[N][gz][gx]; t,
+//             dir as for mw_scan_kernel; pose double[N][P][4]: x, z, c, s; env b's rows of out (int32[N][P]), inside (the same, or null) and
+//             best (int32[N][2], or null) where mask is null or mask[b] != 0.
+//   resample  the view is not read.  weight uint32[N][P], offset uint64[N]; env b's rows of ancestor (int32[N][P]) and, with pose
+//             (double[N][P][4]), of pose_out (the same, no overlap) where mask is null or mask[b] != 0.
+extern "C" __global__ void mw_weigh_kernel(MwNavArgs a, mw_nav_params p, double max_range, int R, int P, int waves, const uint8_t *__restrict__ score,
+                                           const double *__restrict__ t, const double *__restrict__ dir, const double *__restrict__ pose,
+                                           const uint8_t *__restrict__ mask, int32_t *__restrict__ out, int32_t *__restrict__ inside,
+                                           int32_t *__restrict__ best);
+extern "C" __global__ void mw_resample_kernel(MwNavArgs a, int P, const uint32_t *__restrict__ weight, const uint64_t *__restrict__ offset,
+                                              const uint8_t *__restrict__ mask, int32_t *__restrict__ ancestor, const double *__restrict__ pose,
+                                              double *__restrict__ pose_out);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

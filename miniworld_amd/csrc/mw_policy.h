@@ -19,6 +19,7 @@
 #include "mw_scan.h"            // MW_SCAN_THREADS, mwscan::plane_bytes, prefix_bytes
 #include "mw_match.h"           // MW_MATCH_THREADS, mwmatch::plane_bytes, ends_bytes, fill_bytes
 #include "mw_gridray.h"         // MW_GRIDRAY_THREADS, mwgray::staged_bytes
+#include "mw_weigh.h"           // MW_WEIGH_THREADS, mwweigh::plane_bytes, beams_bytes, prefix_bytes
 #include "mw_shape.h"
 #include "mw_snapframes.h"     // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -520,6 +521,35 @@ inline GridRayLaunch gridray_launch(int N, long long cells, int R, int forced = 
     if (!fits) return {false, (unsigned long long)N, MW_GRIDRAY_THREADS, 0, false};
     if (forced ? forced == 1 : R >= kGridRayStagedFrom) return {true, (unsigned long long)N, MW_GRIDRAY_THREADS, mwgray::staged_bytes(cells), true};
     return {false, (unsigned long long)N * (unsigned long long)((R + 1) / 2), MW_GRIDRAY_THREADS, 0, true};
+}
+
+// Scan weighing (mw_scan_weigh; kernel: mw_weigh.hip): a workgroup of MW_WEIGH_THREADS lanes per env.  Its LDS is the score plane, a byte
+// per cell, then the env's beams that pass the t test, 24 bytes each, then the fill word and the key: 32 + 96 KiB and 16 bytes at
+// MW_NAV_MAX_CELLS and MW_RAY_MAX, which one workgroup may hold (a CU has 160 KiB; the engine asks for it as for mw_match_kernel); sized by
+// the actual counts, so that the Maze's 103 x 103 cells with 256 beams take under 17 KiB.
+// waves: the form — a wavefront per particle below kWeighLanesFrom particles, where a particle per lane leaves most lanes of the workgroup
+// idle; a particle per lane from there on.  Measured (profiles/r46, Maze x 1024, 103 x 103 cells, device us per call, lanes / waves, three
+// windows): R = 64: P = 16 .. 64 42 .. 44 / 41 .. 44, 128: 42 / 65, 256: 46 / 103, 4096: 392 / 1 245; R = 256: P = 16: 69 / 41, 64: 64 / 54,
+// 128: 69 / 84, 256: 90 / 144, 4096: 1 051 / 1 909; R = 1024: P = 16: 204 / 47, 64: 184 / 104, 128: 195 / 178, 256: 256 / 321, 4096:
+// 3 704 / 4 744.  They cross between 64 and 128 particles at 64 and 256 beams and between 128 and 256 at 1024 beams, so 128: at 128
+// particles and 1024 beams the lanes' form pays 10 % for it.
+// forced: mw_debug_set_weigh_form's value — 1 a particle per lane, 2 a wavefront per particle for every count.  fits: a positive count of
+// no more cells than MW_NAV_MAX_CELLS, 1 .. MW_RAY_MAX beams and 1 .. MW_WEIGH_MAX_PARTICLES particles — the caller refuses what does not.
+constexpr int kWeighLanesFrom = 128;
+struct WeighLaunch { unsigned long long grid; int threads; size_t lds; bool fits; bool waves; };
+inline WeighLaunch weigh_launch(int N, long long cells, int rays, int particles, int forced = 0)
+{
+    const bool fits = cells >= 1 && cells <= MW_NAV_MAX_CELLS && rays >= 1 && rays <= MW_RAY_MAX && particles >= 1 && particles <= MW_WEIGH_MAX_PARTICLES;
+    if (!fits) return {(unsigned long long)N, MW_WEIGH_THREADS, 0, false, false};
+    const bool waves = forced ? forced == 2 : particles < kWeighLanesFrom;
+    return {(unsigned long long)N, MW_WEIGH_THREADS, mwweigh::plane_bytes(cells) + mwweigh::beams_bytes(rays) + mwweigh::kTailBytes, true, waves};
+}
+// Resampling (mw_resample; kernel: mw_weigh.hip): a workgroup of MW_WEIGH_THREADS lanes per env; its LDS a 64-bit prefix sum per particle
+// and a word per wavefront: 32 KiB and 32 bytes at MW_WEIGH_MAX_PARTICLES.  fits: 1 .. MW_WEIGH_MAX_PARTICLES particles.
+inline Launch resample_launch(int N, int particles)
+{
+    const bool fits = particles >= 1 && particles <= MW_WEIGH_MAX_PARTICLES;
+    return {(unsigned long long)N, MW_WEIGH_THREADS, fits ? mwweigh::prefix_bytes(particles) : 0, fits};
 }
 
 }  // namespace mwpolicy

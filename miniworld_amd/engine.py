@@ -135,6 +135,7 @@ REGION_MAX = 256                        # MW_REGION_MAX: mw_grid_regions' listed
 CLEAR_NONE, CLEAR_FAR = 0x7FFFFFFF, 0x7FFFFFFE      # MW_CLEAR_NONE, MW_CLEAR_FAR: mw_grid_clearance's dist2 without a marked cell, beyond the limit
 CLEAR_MAX_BANDS = 8                     # MW_CLEAR_MAX_BANDS: mw_grid_clearance's cost bands per call
 MATCH_MAX_ROT, MATCH_MAX_WINDOW = 64, 32        # MW_MATCH_MAX_ROT, MW_MATCH_MAX_WINDOW: mw_scan_match's rotations per call, cells either way
+WEIGH_MAX_PARTICLES = 4096              # MW_WEIGH_MAX_PARTICLES: mw_scan_weigh's and mw_resample's particles per env and call
 
 EGO_ENTITIES, EGO_NORTH = 1, 2          # MW_EGO_* flags
 EGO_WALL, EGO_ENTITY, EGO_VISIBLE = 1, 2, 4     # MW_EGO_* planes
@@ -255,6 +256,9 @@ SIGNATURES = {
     "mw_grid_clearance": _sig(vp, P(MwNavParams), i32, P(i32), i32, vp, vp, vp, vp, vp, vp),
     "mw_scan_project": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_scan_match": _sig(vp, P(MwNavParams), P(C.c_double), P(C.c_double), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+    "mw_scan_weigh": _sig(vp, P(MwNavParams), P(C.c_double), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+    "mw_debug_set_weigh_form": _sig(vp, C.c_int),
+    "mw_resample": _sig(vp, i32, vp, vp, vp, vp, vp, vp, vp),
     "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
     "mw_grid_sight": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
@@ -772,6 +776,67 @@ class Engine:
         pairs = (C.c_double * (2 * max(K, 1)))(*[float(v) for cs in rot for v in cs])
         self._check(self.lib.mw_scan_match(self.h, C.byref(params), host, pairs, K, int(window), R, _ptr(score), _ptr(t), _ptr(dir), _ptr(origin), _ptr(mask),
                                            _ptr(best), _ptr(best_score), _ptr(volume), _stream_ptr(self.device)), "mw_scan_match")
+
+    # -- scan weighing and resampling ----------------------------------------------------
+    def scan_weigh(self, params: MwNavParams, max_range: float, score, t, dir, pose, out, inside=None, best=None, mask=None):
+        """mw_scan_weigh: for the envs under `mask` (uint8[N], device; None = all) the beams `t` (float64[N, R]) along `dir`
+        (float64[N, R, 2]), placed at each particle of `pose` (float64[N, P, 4]: x, z, cos, sin), are scored on `score` (uint8[N, gz, gx]):
+        `out` (int32[N, P]) gets the sum of the bytes under the end cells of the beams with 0 <= t < max_range, `inside` (int32[N, P],
+        optional) how many of them ended in the grid, `best` (int32[N, 2], optional) the (particle, score) of the highest score, the
+        lowest particle on ties.  One kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong tensor
+        is refused before the library is called."""
+        import torch
+        for name, v in (("score", score), ("t", t), ("dir", dir), ("pose", pose), ("out", out)):
+            if v is None:
+                raise EngineError(f"{name}: None")
+        for name, v, dims in (("t", t, 2), ("pose", pose, 3)):
+            if not torch.is_tensor(v) or v.dim() != dims:
+                raise EngineError(f"{name}: need a float64 tensor of {dims} dimensions, got {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}")
+        R, particles = int(t.shape[1]), int(pose.shape[1])
+        self._shaped_tensor(t, "t", torch.float64, (self.N, R))
+        self._shaped_tensor(dir, "dir", torch.float64, (self.N, R, 2))
+        self._shaped_tensor(score, "score", torch.uint8, (self.N, int(params.gz), int(params.gx)))
+        self._shaped_tensor(pose, "pose", torch.float64, (self.N, particles, 4))
+        self._shaped_tensor(out, "out", torch.int32, (self.N, particles))
+        if inside is not None:
+            self._shaped_tensor(inside, "inside", torch.int32, (self.N, particles))
+        if best is not None:
+            self._shaped_tensor(best, "best", torch.int32, (self.N, 2))
+        mask = self._mask_tensor(mask, optional=True)
+        host = (C.c_double * 1)(float(max_range))
+        self._check(self.lib.mw_scan_weigh(self.h, C.byref(params), host, R, particles, _ptr(score), _ptr(t), _ptr(dir), _ptr(pose), _ptr(mask), _ptr(out),
+                                           _ptr(inside), _ptr(best), _stream_ptr(self.device)), "mw_scan_weigh")
+
+    def debug_set_weigh_form(self, form: int):
+        """Measurements: 1 weighs every particle count with a particle per lane, 2 with a wavefront per particle, 0 by the count again."""
+        self._check(self.lib.mw_debug_set_weigh_form(self.h, int(form)), "mw_debug_set_weigh_form")
+
+    def resample(self, weight, offset, ancestor, pose=None, pose_out=None, mask=None):
+        """mw_resample: for the envs under `mask` (uint8[N], device; None = all) systematic resampling of the particles by `weight`
+        (int32[N, P], read as unsigned 32-bit) from `offset` (int64[N], read as unsigned 64-bit): `ancestor` (int32[N, P]) gets the
+        particle each new one descends from, non-decreasing, and with `pose` (float64[N, P, 4]) `pose_out` (the same, no overlap) the
+        ancestors' rows.  One kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is
+        refused before the library is called."""
+        import torch
+        for name, v in (("weight", weight), ("offset", offset), ("ancestor", ancestor)):
+            if v is None:
+                raise EngineError(f"{name}: None")
+        if not torch.is_tensor(weight) or weight.dim() != 2:
+            raise EngineError(f"weight: need an int32 tensor [{self.N}, P], got {tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
+        particles = int(weight.shape[1])
+        self._shaped_tensor(weight, "weight", torch.int32, (self.N, particles))
+        self._shaped_tensor(offset, "offset", torch.int64, (self.N,))
+        self._shaped_tensor(ancestor, "ancestor", torch.int32, (self.N, particles))
+        if (pose is None) != (pose_out is None):
+            raise EngineError(f"{'pose_out' if pose is not None else 'pose'}: None beside the other")
+        if pose is not None:
+            self._shaped_tensor(pose, "pose", torch.float64, (self.N, particles, 4))
+            self._shaped_tensor(pose_out, "pose_out", torch.float64, (self.N, particles, 4))
+            if pose.data_ptr() == pose_out.data_ptr():
+                raise EngineError("pose_out: the same buffer as pose")
+        mask = self._mask_tensor(mask, optional=True)
+        self._check(self.lib.mw_resample(self.h, particles, _ptr(weight), _ptr(offset), _ptr(mask), _ptr(ancestor), _ptr(pose), _ptr(pose_out),
+                                         _stream_ptr(self.device)), "mw_resample")
 
     # -- egocentric map windows ----------------------------------------------------------
     def ego_map(self, size: int, cell: float, back: float, wall_radius: float, entity_pad: float, max_range: float, cos_half: float, planes: int,

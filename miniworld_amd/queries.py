@@ -1,6 +1,6 @@
 """The world queries of the batched env — navigation fields, explored-area maps, grid sight, grid regions, grid clearance, egocentric map windows,
-depth projection, label frames, object maps, ray casts, scan maps, scan matching —, each one kernel on the device with no host value: their value
-classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance, ScanMap, ScanMatch) and
+depth projection, label frames, object maps, ray casts, scan maps, scan matching, scan weighing and resampling —, each one kernel on the device with no host value: their value
+classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance, ScanMap, ScanMatch, ScanWeights) and
 `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
 from __future__ import annotations
 
@@ -158,6 +158,20 @@ class ScanMatch:
         moved[:, 0] += self.best[:, 1].double() * self.cell
         moved[:, 2] += self.best[:, 2].double() * self.cell
         return dict(scan, dir=turned), moved
+
+
+class ScanWeights:
+    """How well a scan fits a map from each of P poses (MiniWorldVecEnv.scan_weigh): `score`, int32[N, P], the sum of the likelihood bytes
+    under the end cells of the scan placed at each particle; `inside`, int32[N, P], how many of its beams ended in the grid; `best`,
+    int32[N, 2], the (particle, score) of the highest score, the lowest particle on ties; `pose`, float64[N, P, 4], the rows (x, z, cos,
+    sin) exactly as the kernel got them.  `params` is the grid, `max_range` the cut.  The tensors are the caller's."""
+
+    def __init__(self, score, inside, best, pose, params, max_range):
+        self.score, self.inside, self.best, self.pose, self.params, self.max_range = score, inside, best, pose, params, max_range
+
+    cell = property(lambda self: self.params.cell)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
 
 
 class LabelFrame:
@@ -955,6 +969,100 @@ class WorldQueries:
                             torch.tensor(angles, dtype=torch.float64, device=e.device), torch.tensor(rot, dtype=torch.float64, device=e.device), rot, window, params, max_range)
         e.scan_match(out.params, out.max_range, out.pairs, out.window, score, scan["t"], scan["dir"], out.best, out.score, out.volume, origin, mask)
         return out
+
+    # ------------------------------------------------------------------ scan weighing and resampling
+    def scan_weigh(self, score, scan, poses, max_range=10.0, like=None, cell=0.25, mask=None, into=None):
+        """Scores a range scan on the caller's OWN map from P free poses per env — the likelihood-field measurement update of Monte Carlo
+        localisation —, by one kernel (mw_scan_weigh) with no host value and no synchronisation: a ScanWeights.  A particle's score is
+        the sum of `score`'s bytes under the end cells of the scan's beams, turned by the particle's angle about its position.
+
+        score      uint8[N, gz, gx] contiguous device tensor, the likelihood plane, as for scan_match().  Checked, never converted
+        scan       a raycast() / lidar() result, or any dict with contiguous float64 "t" [N, R] and "dir" [N, R, 2] on the device; only
+                   beams with 0 <= t < max_range count
+        poses      float64[N, P, 3] device tensor of (x, z, turn), P in 1 .. engine.WEIGH_MAX_PARTICLES; turn in radians in the sense of
+                   scan_match()'s rotations (torch takes cos and sin on the device); a NaN pose scores 0.  [N, P, 4] is taken too: the
+                   fourth column is the caller's own and is not read, so that resample() moves the same rows
+        max_range  metres: a beam that reached it has no end point
+        like       a map or field whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell` metres per cell as in nav_field()
+        mask       uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
+        into       a ScanWeights of an earlier call with as many particles to write into: its grid and max_range are used
+        The rule in full: include/mwengine.h, "scan weighing and resampling".  An env whose extent the grid does not cover gets zeros
+        and engine.check() raises once.  ValueError for arguments that make no call; nothing is launched then."""
+        torch, e, n, where = self.torch, self.engine, self.num_envs, "scan_weigh"
+        if into is not None:
+            if not isinstance(into, ScanWeights):
+                raise ValueError(f"{where}: `into` must be a ScanWeights")
+            if (max_range, like, cell) != (10.0, None, 0.25):
+                raise ValueError(f"{where}: with `into` the record's own grid and max_range are used: pass only score, scan, poses and mask")
+            params, max_range = into.params, into.max_range
+        else:
+            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions, GridClearance, ScanMap, ScanMatch, ScanWeights), "its own")
+            max_range = real(where, "max_range", max_range)
+        if not self._is_tensor(score, (n, params.gz, params.gx), torch.uint8):
+            raise ValueError(f"{where}: score is a contiguous uint8 tensor [{n}, {params.gz}, {params.gx}] on {e.device}")
+        if not isinstance(scan, dict) or "t" not in scan or "dir" not in scan:
+            raise ValueError(f'{where}: `scan` is a dict with "t" and "dir" (a lidar() result, or raycast()\'s with the directions beside it)')
+        if not self._is_tensor(scan["t"], (n, None)) or not 1 <= scan["t"].shape[1] <= eng.RAY_MAX:
+            raise ValueError(f'{where}: scan["t"] is a contiguous float64 tensor [{n}, R] on {e.device}, R in 1 .. {eng.RAY_MAX}')
+        if not self._is_tensor(scan["dir"], (n, int(scan["t"].shape[1]), 2)):
+            raise ValueError(f'{where}: scan["dir"] is a contiguous float64 tensor [{n}, {int(scan["t"].shape[1])}, 2] on {e.device}')
+        if not (self._is_tensor(poses, (n, None, 3)) or self._is_tensor(poses, (n, None, 4))) or not 1 <= poses.shape[1] <= eng.WEIGH_MAX_PARTICLES:
+            raise ValueError(f"{where}: poses is a contiguous float64 tensor [{n}, P, 3] (or 4) on {e.device}, P in 1 .. {eng.WEIGH_MAX_PARTICLES}")
+        particles = int(poses.shape[1])
+        if into is not None and into.pose.shape[1] != particles:
+            raise ValueError(f"{where}: `into` holds {int(into.pose.shape[1])} particles per env, poses {particles}")
+        mask = self._device_mask(mask, where)
+        if into is None:
+            zeros = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=e.device)      # noqa: E731
+            into = ScanWeights(zeros(n, particles), zeros(n, particles), zeros(n, 2), torch.empty((n, particles, 4), dtype=torch.float64, device=e.device),
+                               params, max_range)
+        into.pose[..., :2] = poses[..., :2]
+        torch.cos(poses[..., 2], out=into.pose[..., 2])
+        torch.sin(poses[..., 2], out=into.pose[..., 3])
+        e.scan_weigh(into.params, into.max_range, score, scan["t"], scan["dir"], into.pose, into.score, into.inside, into.best, mask)
+        return into
+
+    def resample(self, weights, offset=None, poses=None, mask=None, into=None):
+        """Draws the next generation of particles from their weights — systematic (low-variance) resampling in integers —, by one kernel
+        (mw_resample) with no host value and no synchronisation: {"ancestor": int32[N, P], the particle each new one descends from,
+        non-decreasing; "pose": the ancestors' rows of `poses`, or None}.  Particle p is drawn floor or ceil of P w_p / sum(w) times; a
+        row of zero weights keeps every particle.
+
+        weights    int64[N, P] or int32[N, P] contiguous device tensor, P in 1 .. engine.WEIGH_MAX_PARTICLES, of integers in 0 .. 2^32 - 1:
+                   the dtype and shape are checked, the values are brought into that range on the device (no value is read on the
+                   host) and converted to the kernel's unsigned words once
+        offset     int64[N] device tensor, read as unsigned: where in the first stratum the comb starts (taken modulo the sum); None:
+                   drawn with torch's generator on the device
+        poses      float64[N, P, 4] contiguous device tensor: the rows to move, four doubles each as they are — scan_weigh()'s `poses` in
+                   its four-column form (x, z, turn and a column of the caller's own), or a ScanWeights.pose
+        mask       uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
+        into       the dict of an earlier call of the same shapes to write into
+        The rule in full: include/mwengine.h, "scan weighing and resampling".  ValueError for arguments that make no call."""
+        torch, e, n, where = self.torch, self.engine, self.num_envs, "resample"
+        if not (self._is_tensor(weights, (n, None), torch.int64) or self._is_tensor(weights, (n, None), torch.int32)) or not 1 <= weights.shape[1] <= eng.WEIGH_MAX_PARTICLES:
+            raise ValueError(f"{where}: weights is a contiguous int64 or int32 tensor [{n}, P] on {e.device}, P in 1 .. {eng.WEIGH_MAX_PARTICLES}")
+        particles = int(weights.shape[1])
+        if offset is not None and not self._is_tensor(offset, (n,), torch.int64):
+            raise ValueError(f"{where}: offset is a contiguous int64 tensor [{n}] on {e.device}")
+        if poses is not None and not self._is_tensor(poses, (n, particles, 4)):
+            raise ValueError(f"{where}: poses is a contiguous float64 tensor [{n}, {particles}, 4] on {e.device}")
+        mask = self._device_mask(mask, where)
+        if into is not None:
+            if (not isinstance(into, dict) or not self._is_tensor(into.get("ancestor"), (n, particles), torch.int32)
+                    or (into.get("pose") is None) != (poses is None) or (poses is not None and not self._is_tensor(into["pose"], (n, particles, 4)))):
+                raise ValueError(f"{where}: `into` is the result of an earlier call with weights and poses of these shapes")
+            if poses is not None and into["pose"].data_ptr() == poses.data_ptr():
+                raise ValueError(f"{where}: `into` holds `poses` itself: the rows move between two buffers")
+        else:
+            into = {"ancestor": torch.zeros((n, particles), dtype=torch.int32, device=e.device), "pose": None if poses is None else torch.zeros_like(poses)}
+        if weights.dtype == torch.int64:        # (the low words of the clamped values: the unsigned 32 bits the kernel reads)
+            words = weights.clamp(0, 2 ** 32 - 1).view(torch.int32)[:, 0::2].contiguous()
+        else:
+            words = weights.clamp(min=0)
+        if offset is None:
+            offset = torch.randint(0, 2 ** 63 - 1, (n,), dtype=torch.int64, device=e.device)
+        e.resample(words, offset, into["ancestor"], poses, into["pose"], mask)
+        return into
 
     # ------------------------------------------------------------------ label frames
     MESHES = {"exact": eng.LABEL_MESH_EXACT, "bounds": eng.LABEL_MESH_BOUNDS}
