@@ -1304,6 +1304,36 @@ int mw_scan_match(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are re
                   const double *d_dir /* [N][R][2]: dx, dz */, const double *d_origin /* [N][3] or NULL = the agents */, const uint8_t *d_mask,
                   int32_t *d_best /* [N][3]: r, a, b */, int32_t *d_best_score /* [N] */, int32_t *d_volume /* [N][K][2W+1][2W+1] or NULL */,
                   void *stream);
+/* ---- scan search ------------------------------------------------------------- */
+/* mw_scan_match over a wide window: closing a loop after drift, finding an agent again after a lost track.  The rule is "scan matching"
+ * above, unchanged: the same beam arithmetic, the same counting test, the same zero terms outside the grid, the same best — the highest
+ * score, then the least a^2 + b^2, the lowest r, the lowest b, the lowest a.  For the same inputs d_best and d_best_score are
+ * mw_scan_match's, bit for bit; the window is 0 .. MW_SEARCH_MAX_WINDOW, K stays 1 .. MW_MATCH_MAX_ROT, and there is no volume.  The mask
+ * rule and the uncovered-extent rule are mw_scan_match's: rows of envs under a zero mask byte are neither read nor written; an env whose
+ * extent the grid does not cover gets best (0, 0, 0), score 0 — and stats (0, 0) — and sets the same status bit.
+ *
+ * It is Olson's multi-resolution search, Cartographer's branch and bound, with one coarse level: a rotation's translations are cut into
+ * blocks of 8 x 8, anchored at (-W + 8 j, -W + 8 i); a block's bound — the sum over the end cells of the plane's maximum over the 8 x 8
+ * cells the block's translations read — is at least every score in it, and a block whose bound lies below the best score found so far
+ * is skipped: it provably holds no winner, so the result does not depend on the kernel's schedule.
+ * d_stats[i][1] = K * ceil((2 W + 1) / 8)^2, the blocks in all.  d_stats[i][0], the blocks refined, DOES depend on the schedule: it
+ * lies in 1 .. d_stats[i][1] (but for the (0, 0) of an uncovered env), and equals d_stats[i][1] with pruning off.  On an all-zero or constant plane, and for an env without a
+ * counting beam, every candidate ties, nothing is pruned, and the cost is brute force plus the bounds.
+ *
+ * One kernel, one workgroup per env, asynchronous on `stream`, as mw_scan_match.  MW_E_INVALID before anything is launched, and nothing
+ * touched: mw_scan_match's refusals, with window outside 0 .. MW_SEARCH_MAX_WINDOW; and a grid whose planes, lists and bound words exceed the
+ * 160 KiB of local memory one workgroup may hold — the bound plane takes (gz + 7) x (gx + 7) bytes, so a thin grid of more than some
+ * 16 000 cells (1 x 32768, 2 x 16384), which mw_scan_match takes, is refused here. */
+#define MW_SEARCH_MAX_WINDOW 128 /* cells either way */
+int mw_scan_search(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */,
+                   const double *host_range /* [1] on the host: max_range */, const double *host_rot /* [K][2] on the host: c, s */, int32_t K,
+                   int32_t window, int32_t R, const uint8_t *d_score /* [N][gz][gx] */, const double *d_t /* [N][R] */,
+                   const double *d_dir /* [N][R][2]: dx, dz */, const double *d_origin /* [N][3] or NULL = the agents */, const uint8_t *d_mask,
+                   int32_t *d_best /* [N][3]: r, a, b */, int32_t *d_best_score /* [N] */,
+                   int32_t *d_stats /* [N][2]: blocks refined, blocks in all; or NULL */, void *stream);
+/* tests and measurements: 0 refines every block, 1 prunes again.  The results are the same bits.  MW_E_INVALID: a null engine, a value
+ * outside 0 .. 1. */
+int mw_debug_set_search_prune(mw_engine *e, int on);
 /* ---- scan weighing and resampling -------------------------------------------- */
 /* The localiser that holds more than one hypothesis: the likelihood-field measurement update of Monte Carlo localisation and its
  * resampling step.  mw_scan_match scores whole-cell shifts inside a window around one estimate; mw_scan_weigh scores P free poses
@@ -1415,7 +1445,7 @@ int mw_grid_ray_cast(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match, mw_scan_weigh, mw_grid_ray_cast or mw_label_project skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match, mw_scan_search, mw_scan_weigh, mw_grid_ray_cast or mw_label_project skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

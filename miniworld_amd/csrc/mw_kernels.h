@@ -20,6 +20,7 @@
 #include "mw_clear.h"
 #include "mw_scan.h"
 #include "mw_match.h"
+#include "mw_search.h"
 #include "mw_gridray.h"
 #include "mw_weigh.h"
 
@@ -382,6 +383,15 @@ extern "C" __global__ void mw_match_kernel(MwNavArgs a, mw_nav_params p, double 
                                            const uint8_t *__restrict__ score, const double *__restrict__ t, const double *__restrict__ dir,
                                            const double *__restrict__ origin, const uint8_t *__restrict__ mask, int32_t *__restrict__ best,
                                            int32_t *__restrict__ best_score, int32_t *__restrict__ volume);
+
+// scan search (mw_search.hip; the arrays, the key, the phases and the launch constant: mw_search.h; the rule: mw_match.h; the launch:
+// mwpolicy::search_launch).  Of the view the extent and, with a null origin, ax / az are read.  Grid N workgroups of MW_SEARCH_THREADS
+// lanes; rot, score, t, dir, origin as for mw_match_kernel; batch: the launch's (rotations per task list); prune: 0 refines every block;
+// env b's rows of best (int32[N][3]), best_score (int32[N]) and stats (int32[N][2] or null) where mask is null or mask[b] != 0.
+extern "C" __global__ void mw_search_kernel(MwNavArgs a, mw_nav_params p, double max_range, int R, MwMatchRot rot, int W, int batch, int prune,
+                                            const uint8_t *__restrict__ score, const double *__restrict__ t, const double *__restrict__ dir,
+                                            const double *__restrict__ origin, const uint8_t *__restrict__ mask, int32_t *__restrict__ best,
+                                            int32_t *__restrict__ best_score, int32_t *__restrict__ stats);
 
 // grid ray casts (mw_gridray.hip; the rule, the half-rays, the walks and the launch constants: mw_gridray.h; the choice of form:
 // mwpolicy::gridray_launch).  The grid (cell, gx, gz are read) and max_t travel by value; of the view the extent, with a null origin ax / az

@@ -18,6 +18,7 @@
 #include "mw_clear.h"           // MW_CLEAR_THREADS, mwclear::off_bytes
 #include "mw_scan.h"            // MW_SCAN_THREADS, mwscan::plane_bytes, prefix_bytes
 #include "mw_match.h"           // MW_MATCH_THREADS, mwmatch::plane_bytes, ends_bytes, fill_bytes
+#include "mw_search.h"          // MW_SEARCH_THREADS, mwsearch::plane_bytes, bound_bytes, ends_bytes, words_bytes, fill_bytes
 #include "mw_gridray.h"         // MW_GRIDRAY_THREADS, mwgray::staged_bytes
 #include "mw_weigh.h"           // MW_WEIGH_THREADS, mwweigh::plane_bytes, beams_bytes, prefix_bytes
 #include "mw_shape.h"
@@ -500,6 +501,33 @@ inline MatchLaunch match_launch(int N, int gz, int gx, int rays, int window, int
     int batch = MW_MATCH_THREADS / per;
     batch = batch > most ? most : batch < 1 ? 1 : batch;
     return {(unsigned long long)N, MW_MATCH_THREADS, mwmatch::plane_bytes(cells, quad) + mwmatch::ends_bytes(rays, batch) + mwmatch::fill_bytes(), true, quad, batch};
+}
+
+// Scan search (mw_scan_search; kernel: mw_search.hip): a workgroup of MW_SEARCH_THREADS lanes per env.  Its LDS is the score plane, a byte
+// per cell; the bound plane, (gz + 7) x (gx + 7) bytes; `batch` end-cell lists of a word per beam; a bound word per block of the batch; a
+// fill word per rotation slot and the tail, each rounded up to 16: 32 KiB + 34.7 KiB + 16 KiB + 4.3 KiB + 288 bytes, 89 328 bytes in all, at
+// 128 x 256 cells, MW_RAY_MAX and MW_SEARCH_MAX_WINDOW; sized by the actual counts, so that the Maze's 103 x 103 cells with 256 beams and a
+// window of 64 take 37 KiB.  That is not the worst case: the bound plane grows with the grid's perimeter, not its area — 1 x 32768 cells
+// would need 262 200 bytes for it alone —, so the sum is held against kSearchMaxLds, the 160 KiB of a CU that one workgroup may ask for
+// (the engine asks as for mw_match_kernel): a thin grid of more than some 16 000 cells, which mw_scan_match takes, does not fit here.
+// batch: the rotations whose blocks are one task list, so that a small window's few blocks still fill the four wavefronts: at most 8,
+// no more than keep the lists within 16 KiB (MW_RAY_MAX / rays) and the bound words within 8 KiB (kBoundWords / blocks), at least 1.
+// Not measured: the batch is a supposition.
+// fits: a positive count of no more cells than MW_NAV_MAX_CELLS, 1 .. MW_RAY_MAX beams, a window of 0 .. MW_SEARCH_MAX_WINDOW and no more
+// than kSearchMaxLds bytes in all — the caller refuses what does not.
+constexpr size_t kSearchMaxLds = 160 * 1024;
+struct SearchLaunch { unsigned long long grid; int threads; size_t lds; bool fits; int batch; };
+inline SearchLaunch search_launch(int N, int gz, int gx, int rays, int window)
+{
+    const long long cells = (long long)gz * gx;
+    const bool in_range = gz >= 1 && gx >= 1 && cells <= MW_NAV_MAX_CELLS && rays >= 1 && rays <= MW_RAY_MAX && window >= 0 && window <= MW_SEARCH_MAX_WINDOW;
+    if (!in_range) return {(unsigned long long)N, MW_SEARCH_THREADS, 0, false, 1};
+    int batch = MW_RAY_MAX / rays < 8 ? MW_RAY_MAX / rays : 8;
+    const int held = mwsearch::kBoundWords / mwsearch::blocks(window);
+    batch = batch > held ? held : batch;
+    batch = batch < 1 ? 1 : batch;
+    const size_t lds = mwsearch::plane_bytes(cells) + mwsearch::bound_bytes(gz, gx) + mwsearch::ends_bytes(rays, batch) + mwsearch::words_bytes(window, batch) + mwsearch::fill_bytes();
+    return {(unsigned long long)N, MW_SEARCH_THREADS, lds, lds <= kSearchMaxLds, batch};
 }
 
 // Grid ray casts (mw_grid_ray_cast; kernels: mw_gridray.hip).  The form follows from the rays per env alone, as ray_launch's: from

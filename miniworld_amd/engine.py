@@ -135,6 +135,7 @@ REGION_MAX = 256                        # MW_REGION_MAX: mw_grid_regions' listed
 CLEAR_NONE, CLEAR_FAR = 0x7FFFFFFF, 0x7FFFFFFE      # MW_CLEAR_NONE, MW_CLEAR_FAR: mw_grid_clearance's dist2 without a marked cell, beyond the limit
 CLEAR_MAX_BANDS = 8                     # MW_CLEAR_MAX_BANDS: mw_grid_clearance's cost bands per call
 MATCH_MAX_ROT, MATCH_MAX_WINDOW = 64, 32        # MW_MATCH_MAX_ROT, MW_MATCH_MAX_WINDOW: mw_scan_match's rotations per call, cells either way
+SEARCH_MAX_WINDOW = 128                 # MW_SEARCH_MAX_WINDOW: mw_scan_search's cells either way
 WEIGH_MAX_PARTICLES = 4096              # MW_WEIGH_MAX_PARTICLES: mw_scan_weigh's and mw_resample's particles per env and call
 
 EGO_ENTITIES, EGO_NORTH = 1, 2          # MW_EGO_* flags
@@ -256,6 +257,8 @@ SIGNATURES = {
     "mw_grid_clearance": _sig(vp, P(MwNavParams), i32, P(i32), i32, vp, vp, vp, vp, vp, vp),
     "mw_scan_project": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_scan_match": _sig(vp, P(MwNavParams), P(C.c_double), P(C.c_double), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+    "mw_scan_search": _sig(vp, P(MwNavParams), P(C.c_double), P(C.c_double), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+    "mw_debug_set_search_prune": _sig(vp, C.c_int),
     "mw_scan_weigh": _sig(vp, P(MwNavParams), P(C.c_double), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_weigh_form": _sig(vp, C.c_int),
     "mw_resample": _sig(vp, i32, vp, vp, vp, vp, vp, vp, vp),
@@ -755,27 +758,46 @@ class Engine:
         smallest shift, `best_score` (int32[N]) its score, `volume` (int32[N, K, 2 window + 1, 2 window + 1], optional) every score.
         One kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the
         library is called."""
+        R, K, host, pairs, mask = self._match_tensors(params, max_range, rot, score, t, dir, best, best_score, origin, mask, volume, "volume",
+                                                      lambda K: (K, 2 * int(window) + 1, 2 * int(window) + 1))
+        self._check(self.lib.mw_scan_match(self.h, C.byref(params), host, pairs, K, int(window), R, _ptr(score), _ptr(t), _ptr(dir), _ptr(origin), _ptr(mask),
+                                           _ptr(best), _ptr(best_score), _ptr(volume), _stream_ptr(self.device)), "mw_scan_match")
+
+    def _match_tensors(self, params, max_range, rot, score, t, dir, best, best_score, origin, mask, extra, extra_name, extra_shape):
+        """what mw_scan_match and mw_scan_search check alike, in mw_scan_match's order — `extra`, the optional last output (int32[N, *extra_shape(K)]),
+        behind best_score —: (R, K, max_range and the pairs as host arrays, the mask)"""
         import torch
         for name, v in (("score", score), ("t", t), ("dir", dir), ("best", best), ("best_score", best_score)):
             if v is None:
                 raise EngineError(f"{name}: None")
         if not torch.is_tensor(t) or t.dim() != 2:
             raise EngineError(f"t: need a float64 tensor [{self.N}, R], got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-        R, K, side = int(t.shape[1]), len(rot), 2 * int(window) + 1
+        R, K = int(t.shape[1]), len(rot)
         self._shaped_tensor(t, "t", torch.float64, (self.N, R))
         self._shaped_tensor(dir, "dir", torch.float64, (self.N, R, 2))
         self._shaped_tensor(score, "score", torch.uint8, (self.N, int(params.gz), int(params.gx)))
         self._shaped_tensor(best, "best", torch.int32, (self.N, 3))
         self._shaped_tensor(best_score, "best_score", torch.int32, (self.N,))
-        if volume is not None:
-            self._shaped_tensor(volume, "volume", torch.int32, (self.N, K, side, side))
+        if extra is not None:
+            self._shaped_tensor(extra, extra_name, torch.int32, (self.N,) + tuple(extra_shape(K)))
         if origin is not None:
             self._shaped_tensor(origin, "origin", torch.float64, (self.N, 3))
         mask = self._mask_tensor(mask, optional=True)
-        host = (C.c_double * 1)(float(max_range))
-        pairs = (C.c_double * (2 * max(K, 1)))(*[float(v) for cs in rot for v in cs])
-        self._check(self.lib.mw_scan_match(self.h, C.byref(params), host, pairs, K, int(window), R, _ptr(score), _ptr(t), _ptr(dir), _ptr(origin), _ptr(mask),
-                                           _ptr(best), _ptr(best_score), _ptr(volume), _stream_ptr(self.device)), "mw_scan_match")
+        return R, K, (C.c_double * 1)(float(max_range)), (C.c_double * (2 * max(K, 1)))(*[float(v) for cs in rot for v in cs]), mask
+
+    # -- scan search ---------------------------------------------------------------------
+    def scan_search(self, params: MwNavParams, max_range: float, rot, window: int, score, t, dir, best, best_score, stats=None, origin=None, mask=None):
+        """mw_scan_search: mw_scan_match's `best` and `best_score` for the same arguments, bit for bit, over a `window` of up to
+        SEARCH_MAX_WINDOW cells either way, by pruned bounds; no volume.  `stats` (int32[N, 2], optional) gets the blocks of 8 x 8
+        translations the kernel refined — a number that depends on its schedule — and the blocks in all.  One kernel on the current
+        stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused before the library is called."""
+        R, K, host, pairs, mask = self._match_tensors(params, max_range, rot, score, t, dir, best, best_score, origin, mask, stats, "stats", lambda K: (2,))
+        self._check(self.lib.mw_scan_search(self.h, C.byref(params), host, pairs, K, int(window), R, _ptr(score), _ptr(t), _ptr(dir), _ptr(origin), _ptr(mask),
+                                            _ptr(best), _ptr(best_score), _ptr(stats), _stream_ptr(self.device)), "mw_scan_search")
+
+    def debug_set_search_prune(self, on: bool):
+        """Tests and measurements: False makes mw_scan_search refine every block, True prunes again.  The results are the same bits."""
+        self._check(self.lib.mw_debug_set_search_prune(self.h, int(bool(on))), "mw_debug_set_search_prune")
 
     # -- scan weighing and resampling ----------------------------------------------------
     def scan_weigh(self, params: MwNavParams, max_range: float, score, t, dir, pose, out, inside=None, best=None, mask=None):

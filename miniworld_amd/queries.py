@@ -930,23 +930,34 @@ class WorldQueries:
                    score, scan, origin and mask
         The rule in full: include/mwengine.h, "scan matching".  An env whose extent the grid does not cover gets zeros and
         engine.check() raises once.  ValueError for arguments that make no call; nothing is launched then."""
-        torch, e, n, where = self.torch, self.engine, self.num_envs, "scan_match"
+        out, origin, mask = self._scan_align("scan_match", eng.MATCH_MAX_WINDOW, (8, False), "volume", score, scan, origin, window, turn, turns, max_range, like, cell,
+                                             mask, volume, into)
+        self.engine.scan_match(out.params, out.max_range, out.pairs, out.window, score, scan["t"], scan["dir"], out.best, out.score, out.volume, origin, mask)
+        return out
+
+    def _scan_align(self, where, max_window, defaults, extra_name, score, scan, origin, window, turn, turns, max_range, like, cell, mask, extra, into):
+        """scan_match's and scan_search's argument rules, which differ in the window's limit and in the one extra tensor (`extra`, a
+        bool: the volume, the stats): (the ScanMatch to fill — `into`, or a new one, with the extra tensor where asked —, origin, mask)"""
+        torch, e, n = self.torch, self.engine, self.num_envs
+        searched = extra_name == "stats"
         if into is not None:
             if not isinstance(into, ScanMatch):
                 raise ValueError(f"{where}: `into` must be a ScanMatch")
-            if (window, turn, turns, max_range, like, cell, volume) != (8, 0.0, 1, 10.0, None, 0.25, False):
+            if hasattr(into, "stats") != searched:
+                raise ValueError(f"{where}: `into` must be a ScanMatch of {where}, not of " + ("scan_match" if searched else "scan_search"))
+            if (window, turn, turns, max_range, like, cell, extra) != (defaults[0], 0.0, 1, 10.0, None, 0.25, defaults[1]):
                 raise ValueError(f"{where}: with `into` the record's own grid and parameters are used: pass only score, scan, origin and mask")
             out = into
         else:
             params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions, GridClearance, ScanMap), "its own")
-            window = integer(where, "window", window, 0, eng.MATCH_MAX_WINDOW)
+            window = integer(where, "window", window, 0, max_window)
             turns = integer(where, "turns", turns, 1, eng.MATCH_MAX_ROT)
             turn = real(where, "turn", turn, hi=math.pi, lo_open=False)
             if turns % 2 == 0 or (turns == 1) != (turn == 0.0):
                 raise ValueError(f"{where}: turns {turns} and turn {turn!r}: an odd count, and 1 exactly with turn = 0")
             max_range = real(where, "max_range", max_range)
-            if not isinstance(volume, bool):
-                raise ValueError(f"{where}: volume must be True or False, not {volume!r}")
+            if not isinstance(extra, bool):
+                raise ValueError(f"{where}: {extra_name} must be True or False, not {extra!r}")
             d = turn / (turns // 2) if turns > 1 else 0.0
             angles = [0.0] + [sign * k * d for k in range(1, turns // 2 + 1) for sign in (1.0, -1.0)]
             rot = [(math.cos(a), math.sin(a)) for a in angles]
@@ -965,9 +976,30 @@ class WorldQueries:
         if into is None:
             side = 2 * window + 1
             out = ScanMatch(torch.zeros((n, 3), dtype=torch.int32, device=e.device), torch.zeros(n, dtype=torch.int32, device=e.device),
-                            torch.zeros((n, turns, side, side), dtype=torch.int32, device=e.device) if volume else None,
+                            torch.zeros((n, turns, side, side), dtype=torch.int32, device=e.device) if extra and not searched else None,
                             torch.tensor(angles, dtype=torch.float64, device=e.device), torch.tensor(rot, dtype=torch.float64, device=e.device), rot, window, params, max_range)
-        e.scan_match(out.params, out.max_range, out.pairs, out.window, score, scan["t"], scan["dir"], out.best, out.score, out.volume, origin, mask)
+            if searched:
+                out.stats = torch.zeros((n, 2), dtype=torch.int32, device=e.device) if extra else None
+        return out, origin, mask
+
+    # ------------------------------------------------------------------ scan search
+    def scan_search(self, score, scan, origin=None, window=64, turn=0.0, turns=1, max_range=10.0, like=None, cell=0.25, mask=None, stats=False, into=None):
+        """scan_match() over a wide window — closing a loop after drift, finding an agent again after a teleport or a lost track, matching
+        over the whole turn — by one kernel (mw_scan_search) with no host value and no synchronisation: a ScanMatch with `best` and
+        `score` exactly as scan_match() would give them for the same arguments, and `volume` None, so offset() and apply() work as they
+        are.  Instead of scoring every candidate, the kernel bounds blocks of 8 x 8 translations from above and scores only the blocks
+        that can still win (Olson's multi-resolution search, Cartographer's branch and bound); a skipped block provably holds no winner.
+
+        score, scan, origin, turn, turns, max_range, like, cell, mask    as for scan_match()
+        window     W, 0 .. engine.SEARCH_MAX_WINDOW: shifts of -W .. W cells either way
+        stats      with `stats`, int32[N, 2], an attribute of the result: the blocks the kernel scored — this number depends on its
+                   schedule, nothing else does — and the blocks in all, turns * ceil((2 W + 1) / 8)^2
+        into       a ScanMatch of an earlier scan_search() to write into; pass only score, scan, origin and mask
+        On a constant plane every candidate ties and nothing is skipped: the cost is scan_match()'s and the bounds on top.  More than
+        engine.MATCH_MAX_ROT rotations: chain calls and compare the scores.  The rule: include/mwengine.h, "scan search"."""
+        out, origin, mask = self._scan_align("scan_search", eng.SEARCH_MAX_WINDOW, (64, False), "stats", score, scan, origin, window, turn, turns, max_range, like, cell,
+                                             mask, stats, into)
+        self.engine.scan_search(out.params, out.max_range, out.pairs, out.window, score, scan["t"], scan["dir"], out.best, out.score, out.stats, origin, mask)
         return out
 
     # ------------------------------------------------------------------ scan weighing and resampling
