@@ -12,7 +12,11 @@ in its own frame, so expressed along the ESTIMATED heading — goes into a scan 
 
 runs both and reports, over the envs whose episode did not end: the final position and heading error of the estimate, and the share of
 the obstacle cells of the estimate-built map that the map built from the true poses also holds.  Results, not thresholds: see README.md,
-"Scan matching".
+"Scan matching".  With `--evidence` each is run a second time on an evidence map, which takes back what a later scan contradicts:
+
+    m = vec.scan_evidence(rays=R, max_range=E)              # hit 3, miss 1, a vote per scan and cell, clamped to -20 .. 20
+    r = vec.scan_match(m.score, scan, origin=estimate, ...) # its own likelihood plane, no clearance call
+    vec.scan_evidence_update(m, scan, origin=estimate)
 """
 import argparse
 import math
@@ -32,7 +36,7 @@ def turned(d, delta):
     return torch.stack([c * d[..., 0] + s * d[..., 1], c * d[..., 1] - s * d[..., 0]], -1).contiguous()
 
 
-def run(args, match):
+def run(args, match, evidence=False):
     import torch
     from miniworld_amd.vec_env import MiniWorldVecEnv
     n = args.envs
@@ -40,14 +44,16 @@ def run(args, match):
     dev = vec.engine.device
     vec.reset()
     g = torch.Generator(device=dev).manual_seed(args.seed + 1)
-    truth, m = vec.scan_map(rays=args.rays, max_range=args.range), vec.scan_map(rays=args.rays, max_range=args.range)
+    truth = vec.scan_map(rays=args.rays, max_range=args.range)
+    m = vec.scan_evidence(rays=args.rays, max_range=args.range) if evidence else vec.scan_map(rays=args.rays, max_range=args.range)
+    update = vec.scan_evidence_update if evidence else vec.scan_map_update
     st = vec.state(("agent_pos", "agent_dir"))
     pos, heading = st["agent_pos"].clone(), st["agent_dir"].clone()
     est, est_dir = pos.clone(), heading.clone()
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     scan = vec.lidar(args.rays, truth.fov, args.range)
     vec.scan_map_update(truth, scan)
-    vec.scan_map_update(m, scan, origin=est)
+    update(m, scan, origin=est)
     field = r = None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -71,13 +77,14 @@ def run(args, match):
         vec.scan_map_update(truth, scan)
         mine = dict(scan, dir=turned(scan["dir"], est_dir - heading))          # the same beams along the estimated heading
         if match:
-            marked = m.obstacle != 0
-            field = vec.grid_clearance(marked, radii=RADII, costs=COSTS, like=m) if field is None else vec.grid_clearance(marked, into=field)
+            if not evidence:
+                marked = m.obstacle != 0
+                field = vec.grid_clearance(marked, radii=RADII, costs=COSTS, like=m) if field is None else vec.grid_clearance(marked, into=field)
             kw = dict(window=args.window, turn=math.radians(args.turn), turns=args.turns, max_range=args.range, like=m) if r is None else dict(into=r)
-            r = vec.scan_match(field.cost, mine, origin=est, **kw)
+            r = vec.scan_match(m.score if evidence else field.cost, mine, origin=est, **kw)
             mine, est = r.apply(mine, est)
             est_dir += r.offset()[:, 2]
-        vec.scan_map_update(m, mine, origin=est)
+        update(m, mine, origin=est)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     k = alive.sum().clamp(min=1)
@@ -103,9 +110,13 @@ def main():
     ap.add_argument("--turn", type=float, default=6.0, help="degrees either way")
     ap.add_argument("--turns", type=int, default=13)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--evidence", action="store_true", help="run each once more on a ScanEvidence, matched on its own score plane")
     args = ap.parse_args()
-    for name, match in (("dead reckoning", False), ("dead reckoning + scan_match", True)):
-        err, turn_err, share, alive, dt = run(args, match)
+    runs = [("dead reckoning", False, False), ("dead reckoning + scan_match", True, False)]
+    if args.evidence:
+        runs += [("dead reckoning, evidence map", False, True), ("dead reckoning + scan_match on the evidence map", True, True)]
+    for name, match, evidence in runs:
+        err, turn_err, share, alive, dt = run(args, match, evidence)
         print(f"{args.env} x {args.envs}, {args.steps} steps: {name}: position error {err:.3f} m, heading error {turn_err:.2f} deg, "
               f"{share:.3f} of the map's obstacle cells are the true-pose map's, over {alive} envs ({dt / args.steps * 1e6:.0f} us per step)")
 

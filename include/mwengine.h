@@ -1434,6 +1434,48 @@ int mw_grid_ray_cast(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are
                      const double *d_dir /* [N][R][2]: dx, dz, or NULL */, const double *d_offsets /* [R], radians: the fan, or NULL */,
                      const double *d_heading /* [N], with d_offsets, or NULL = the agents' */, double *d_t /* [N][R] */,
                      int32_t *d_hit /* [N][R] or NULL */, double *d_dir_out /* [N][R][2] or NULL */, void *stream);
+
+/* ---- scan evidence ----------------------------------------------------------- */
+/* The map a range scanner gives when a scan may be wrong.  A mw_scan_project byte only goes 0 -> 1: an obstacle cell drawn from a wrong
+ * pose estimate stays, and a cell can be both free and obstacle.  Every mapper that call is modelled on keeps evidence per cell instead
+ * (Cartographer's hit / miss odds, gmapping's hit and visit counts, OctoMap's clamped log-odds), so that a later miss can outvote an
+ * old hit.  This call keeps a signed byte per cell: the cell a beam ends in gains evidence, the cells it passes through lose some, the
+ * sum is clamped, and the thresholded planes — laid out as mw_scan_project's map — and a likelihood plane for mw_scan_match come out of the
+ * same launch.  The reference has no such call.
+ *
+ * The rule.  Beams, kept beams, a kept beam's cells, its end cell and `hit` are exactly those of "scan maps" above, from the same d_t,
+ * d_dir, d_origin, grid and host_range, bit for bit.  For a cell c of an updated env, all in int32:
+ *   hits(c)    the number of kept beams with hit whose end cell is c
+ *   passes(c)  the number of kept beams that have c among their cells.  A beam counts at most once per cell: at an exact corner one beam
+ *              names the same cell through an x-line crossing and through a z-line crossing, and still passes it once
+ *   delta(c) = hits(c) > 0 ? hit * min(hits(c), cap) : -miss * min(passes(c), cap)         a hit wins the cell, as in "scan maps"
+ *   ev'(c)   = min(max(ev(c) + delta(c), lo), hi);  under d_clear[i] != 0, ev(c) is taken as 0
+ * With cap = 1 a scan votes once per cell (Cartographer's form), with a larger cap it votes per beam.  The clamp holds for every cell
+ * of an updated env, also where delta is 0.  The seven integers and their ranges:
+ *   hit, miss  0 .. 127        cap  1 .. MW_RAY_MAX        lo  -127 .. -1        hi  1 .. 127        free_at  lo .. -1        occ_at  1 .. hi
+ * Per env i with d_mask[i] != 0 (or a null d_mask):
+ *   d_ev      int8[N][gz][gx], updated in place: ev -> ev'
+ *   d_map     uint8[N][2][gz][gx] or NULL, rewritten whole: plane 0 free = ev' <= free_at, plane 1 obstacle = ev' >= occ_at, 0 / 1; laid
+ *             out as mw_scan_project's map, so every grid call takes its planes; free_at < 0 < occ_at, so a cell is never both
+ *   d_score   uint8[N][gz][gx] or NULL, rewritten whole: max(ev', 0) — a d_score of mw_scan_match, mw_scan_search and mw_scan_weigh as it stands
+ *   d_count   int32[N][2]: the cells of the free and of the obstacle plane after the update
+ *   d_changed int32[N][2] or NULL: the cells whose membership of each plane differs between ev and ev'; under d_clear against 0
+ * An env whose extent the grid does not cover (as for mw_nav_build) gets its ev, map and score rows zeroed, count and changed 0, and sets
+ * the status bit mw_scan_project sets there: the next mw_check reports it as MW_E_INVALID, once.  Rows of envs under a zero mask byte are
+ * neither read nor written: the mask wins over clear.  Every result is an integer the rule defines: nothing depends on the kernel's schedule.
+ *
+ * One kernel, one workgroup per env, asynchronous on `stream`; it reads no host value except host_range (during the call), reads live arrays
+ * only and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched: a null engine, grid, host_range,
+ * d_t, d_dir, d_ev or d_count; a grid mw_nav_build would refuse (cell <= 0 or not finite, gx or gz < 1, more than MW_NAV_MAX_CELLS cells);
+ * R outside 1 .. MW_RAY_MAX; a max_range that is not > 0 and finite; one of the seven integers outside its range; more LDS than one
+ * workgroup may hold (none within the limits above); more workgroups than a launch holds. */
+int mw_scan_evidence(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */,
+                     const double *host_range /* [1] on the host: max_range */, int32_t R,
+                     const double *d_t /* [N][R] */, const double *d_dir /* [N][R][2]: dx, dz */, const double *d_origin /* [N][3] or NULL = the agents */,
+                     const uint8_t *d_mask, const uint8_t *d_clear /* or NULL */, int32_t hit, int32_t miss, int32_t cap, int32_t lo, int32_t hi,
+                     int32_t free_at, int32_t occ_at, int8_t *d_ev /* [N][gz][gx] */, uint8_t *d_map /* [N][2][gz][gx] or NULL */,
+                     uint8_t *d_score /* [N][gz][gx] or NULL */, int32_t *d_count /* [N][2] */, int32_t *d_changed /* [N][2] or NULL */, void *stream);
+
 /* tests and measurements: the launch shape of the tile and mesh kernels, which the engine otherwise takes from the batch size and from
  * constants — so that a small batch runs the loops that only a large one reaches (several tiles per wavefront, several items per
  * persistent worker).  Every frame is the same bits under every shape.  0 keeps a value as it is at the moment.
@@ -1445,7 +1487,7 @@ int mw_grid_ray_cast(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match, mw_scan_search, mw_scan_weigh, mw_grid_ray_cast or mw_label_project skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match, mw_scan_search, mw_scan_weigh, mw_grid_ray_cast, mw_scan_evidence or mw_label_project skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

@@ -23,6 +23,7 @@
 #include "mw_search.h"
 #include "mw_gridray.h"
 #include "mw_weigh.h"
+#include "mw_evidence.h"
 
 // a kernel and its list form: the same arguments, then the envs of a list (int32 [0] count, [1 + i] env) it draws instead of the
 // whole batch — the second pass of a same-step auto-reset step with final observations (mw_engine_frame.hip)
@@ -423,6 +424,16 @@ extern "C" __global__ void mw_weigh_kernel(MwNavArgs a, mw_nav_params p, double 
 extern "C" __global__ void mw_resample_kernel(MwNavArgs a, int P, const uint32_t *__restrict__ weight, const uint64_t *__restrict__ offset,
                                               const uint8_t *__restrict__ mask, int32_t *__restrict__ ancestor, const double *__restrict__ pose,
                                               double *__restrict__ pose_out);
+
+// scan evidence (mw_evidence.hip; the rule, the arrays, the phases and the launch constant: mw_evidence.h; the launch:
+// mwpolicy::evidence_launch).  Of the view the extent and, with a null origin, ax / az are read.  Grid N workgroups of MW_EVIDENCE_THREADS
+// lanes; rule: the call's seven integers by value; t, dir, origin, mask, clear as for mw_scan_kernel; env b's rows of ev (int8[N][gz][gx]),
+// map (uint8[N][2][gz][gx] or null), score (uint8[N][gz][gx] or null), count and changed (int32[N][2]; changed may be null) where mask is
+// null or mask[b] != 0.
+extern "C" __global__ void mw_evidence_kernel(MwNavArgs a, mw_nav_params p, double max_range, int R, mwevid::Rule rule, const double *__restrict__ t,
+                                              const double *__restrict__ dir, const double *__restrict__ origin, const uint8_t *__restrict__ mask,
+                                              const uint8_t *__restrict__ clear, int8_t *__restrict__ ev, uint8_t *__restrict__ map,
+                                              uint8_t *__restrict__ score, int32_t *__restrict__ count, int32_t *__restrict__ changed);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

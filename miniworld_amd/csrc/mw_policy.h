@@ -21,6 +21,7 @@
 #include "mw_search.h"          // MW_SEARCH_THREADS, mwsearch::plane_bytes, bound_bytes, ends_bytes, words_bytes, fill_bytes
 #include "mw_gridray.h"         // MW_GRIDRAY_THREADS, mwgray::staged_bytes
 #include "mw_weigh.h"           // MW_WEIGH_THREADS, mwweigh::plane_bytes, beams_bytes, prefix_bytes
+#include "mw_evidence.h"        // MW_EVIDENCE_THREADS, mwevid::count_bytes, prefix_bytes
 #include "mw_shape.h"
 #include "mw_snapframes.h"     // MW_SNAPF_THREADS, MW_SNAPF_UNROLL
 #include "mw_snapshot.h"        // MW_SNAP_THREADS
@@ -578,6 +579,20 @@ inline Launch resample_launch(int N, int particles)
 {
     const bool fits = particles >= 1 && particles <= MW_WEIGH_MAX_PARTICLES;
     return {(unsigned long long)N, MW_WEIGH_THREADS, fits ? mwweigh::prefix_bytes(particles) : 0, fits};
+}
+
+// Scan evidence (mw_scan_evidence; kernel: mw_evidence.hip): a workgroup of MW_EVIDENCE_THREADS lanes per env.  Its LDS is the counting
+// plane, a 32-bit word per cell, then a prefix word per beam and one, the four sums, the kept beams and a word per wavefront behind them,
+// each rounded up to 16: 128 KiB + 16 KiB and 64 bytes, 147 520 bytes in all, at MW_NAV_MAX_CELLS and MW_RAY_MAX, which one workgroup
+// may hold (a CU has 160 KiB; the engine asks for it as for mw_search_kernel); sized by the actual counts, so that the Maze's 103 x 103
+// cells with 256 beams take under 44 KiB and three workgroups share a CU.  fits: a positive count of no more cells than that, 1 ..
+// MW_RAY_MAX beams and no more than kSearchMaxLds bytes in all (a smaller workgroup or a larger limit cannot slip past it) — the caller
+// refuses what does not.
+inline Launch evidence_launch(int N, long long cells, int rays)
+{
+    const bool in_range = cells >= 1 && cells <= MW_NAV_MAX_CELLS && rays >= 1 && rays <= MW_RAY_MAX;
+    const size_t lds = in_range ? mwevid::count_bytes(cells) + mwevid::prefix_bytes(rays) : 0;
+    return {(unsigned long long)N, MW_EVIDENCE_THREADS, lds, in_range && lds <= kSearchMaxLds};
 }
 
 }  // namespace mwpolicy

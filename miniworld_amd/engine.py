@@ -262,6 +262,7 @@ SIGNATURES = {
     "mw_scan_weigh": _sig(vp, P(MwNavParams), P(C.c_double), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_weigh_form": _sig(vp, C.c_int),
     "mw_resample": _sig(vp, i32, vp, vp, vp, vp, vp, vp, vp),
+    "mw_scan_evidence": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp),
     "mw_seen_update": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp),
     "mw_grid_sight": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_ego_map": _sig(vp, P(C.c_double), i32, i32, i32, vp, vp, vp, P(MwNavParams), vp, i32, C.c_uint32, vp, vp),
@@ -292,6 +293,24 @@ SIGNATURES = {
     "mw_debug_get_slow_heads": _sig(vp, vp, vp),
 }
 EXPORTS = list(SIGNATURES)      # what a built library must export (__graft_entry__.build)
+
+# mw_scan_evidence's seven integers in the call's order, each with its range; a bound that is a name is that parameter's value
+EVIDENCE_RANGES = (("hit", 0, 127), ("miss", 0, 127), ("cap", 1, RAY_MAX), ("lo", -127, -1), ("hi", 1, 127), ("free_at", "lo", -1), ("occ_at", 1, "hi"))
+
+
+def evidence_rule(rule):
+    """`rule` as the tuple mw_scan_evidence takes: seven integers, never a bool, each inside its range of EVIDENCE_RANGES — an
+    EngineError that names the parameter otherwise.  No library is needed for it."""
+    rule = tuple(rule)
+    if len(rule) != 7 or not all(isinstance(v, int) and not isinstance(v, bool) for v in rule):
+        raise EngineError(f"rule: need the seven integers hit, miss, cap, lo, hi, free_at, occ_at, got {rule!r}")
+    named = dict(zip((r[0] for r in EVIDENCE_RANGES), rule))
+    for name, lo, hi in EVIDENCE_RANGES:
+        lo, hi = named.get(lo, lo), named.get(hi, hi)
+        if not lo <= named[name] <= hi:
+            raise EngineError(f"{name}: {named[name]} outside {lo} .. {hi}")
+    return rule
+
 
 _said = set()
 
@@ -748,6 +767,42 @@ class Engine:
         host = (C.c_double * 1)(float(max_range))
         self._check(self.lib.mw_scan_project(self.h, C.byref(params), host, R, _ptr(t), _ptr(dir), _ptr(origin), _ptr(mask), _ptr(clear),
                                              _ptr(map), _ptr(count), _ptr(new), _stream_ptr(self.device)), "mw_scan_project")
+
+    # -- scan evidence -------------------------------------------------------------------
+    def scan_evidence(self, params: MwNavParams, max_range: float, rule, t, dir, ev, count, map=None, score=None, changed=None, origin=None, mask=None, clear=None):
+        """mw_scan_evidence: for the envs under `mask` (uint8[N], device; None = all) the beams `t` (float64[N, R]) along `dir`
+        (float64[N, R, 2]) from `origin` (float64[N, 3]; None = the agents), mw_scan_project's beams and cells, are counted into `ev`
+        (int8[N, gz, gx], in place): a cell where beams with t < max_range end gains hit * min(their number, cap), any other cell
+        loses miss * min(the beams that pass it, cap), clamped to lo .. hi, from 0 under `clear` (uint8[N]).  `rule` is the seven
+        integers (hit, miss, cap, lo, hi, free_at, occ_at), checked by evidence_rule() before the library is called.  `map`
+        (uint8[N, 2, gz, gx], optional) is rewritten: free = ev <= free_at, obstacle = ev >= occ_at; `score` (uint8[N, gz, gx], optional):
+        max(ev, 0); `count` (int32[N, 2]): the cells of each plane; `changed` (int32[N, 2], optional): the cells that joined or left each.
+        One kernel on the current stream, no synchronisation, nothing of the engine changes.  A wrong tensor is refused, never converted."""
+        import torch
+        for name, v in (("t", t), ("dir", dir), ("ev", ev), ("count", count)):
+            if v is None:
+                raise EngineError(f"{name}: None")
+        rule = evidence_rule(rule)
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise EngineError(f"t: need a float64 tensor [{self.N}, R], got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        R, gz, gx = int(t.shape[1]), int(params.gz), int(params.gx)
+        self._shaped_tensor(t, "t", torch.float64, (self.N, R))
+        self._shaped_tensor(dir, "dir", torch.float64, (self.N, R, 2))
+        self._shaped_tensor(ev, "ev", torch.int8, (self.N, gz, gx))
+        self._shaped_tensor(count, "count", torch.int32, (self.N, 2))
+        if map is not None:
+            self._shaped_tensor(map, "map", torch.uint8, (self.N, 2, gz, gx))
+        if score is not None:
+            self._shaped_tensor(score, "score", torch.uint8, (self.N, gz, gx))
+        if changed is not None:
+            self._shaped_tensor(changed, "changed", torch.int32, (self.N, 2))
+        if origin is not None:
+            self._shaped_tensor(origin, "origin", torch.float64, (self.N, 3))
+        self._dev_tensor(clear, "clear", torch.uint8, self.N)
+        mask = self._mask_tensor(mask, optional=True)
+        host = (C.c_double * 1)(float(max_range))
+        self._check(self.lib.mw_scan_evidence(self.h, C.byref(params), host, R, _ptr(t), _ptr(dir), _ptr(origin), _ptr(mask), _ptr(clear), *rule,
+                                              _ptr(ev), _ptr(map), _ptr(score), _ptr(count), _ptr(changed), _stream_ptr(self.device)), "mw_scan_evidence")
 
     # -- scan matching -------------------------------------------------------------------
     def scan_match(self, params: MwNavParams, max_range: float, rot, window: int, score, t, dir, best, best_score, volume=None, origin=None, mask=None):

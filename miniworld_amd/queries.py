@@ -1,6 +1,6 @@
 """The world queries of the batched env — navigation fields, explored-area maps, grid sight, grid regions, grid clearance, egocentric map windows,
-depth projection, label frames, object maps, ray casts, scan maps, scan matching, scan weighing and resampling —, each one kernel on the device with no host value: their value
-classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance, ScanMap, ScanMatch, ScanWeights) and
+depth projection, label frames, object maps, ray casts, scan maps, scan evidence, scan matching, scan weighing and resampling —, each one kernel on the device with no host value: their value
+classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance, ScanMap, ScanEvidence, ScanMatch, ScanWeights) and
 `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
 from __future__ import annotations
 
@@ -116,6 +116,27 @@ class ScanMap:
     def __init__(self, map, count, new, params, rays, fov, max_range, obstacles):
         self.map, self.count, self.new, self.params = map, count, new, params
         self.rays, self.fov, self.max_range, self.obstacles = rays, fov, max_range, obstacles
+
+    cell = property(lambda self: self.params.cell)
+    gx = property(lambda self: self.params.gx)
+    gz = property(lambda self: self.params.gz)
+    free = property(lambda self: self.map[:, 0])
+    obstacle = property(lambda self: self.map[:, 1])
+
+
+class ScanEvidence:
+    """A scan-built evidence map (MiniWorldVecEnv.scan_evidence): `ev`, the int8[N, gz, gx] device tensor that scan_evidence_update()
+    accumulates on a ScanMap's grid (`params`) — up by `hit` per beam that ends in a cell, down by `miss` per beam that passes through
+    it, at most `cap` beams a scan, clamped to `lo` .. `hi` —, and what each update rewrites from it: `map`, uint8[N, 2, gz, gx], laid out
+    as a ScanMap's with the views `free` (ev <= `free_at`) and `obstacle` (ev >= `occ_at`) — a cell is never both —, `score`,
+    uint8[N, gz, gx] = max(ev, 0), a `score` of scan_match(), scan_search() and scan_weigh() as it stands, `count`, int32[N, 2], the
+    cells of each plane, and `changed`, int32[N, 2], those the last update moved into or out of each.  `rule` is the seven integers in the
+    call's order; `rays`, `fov`, `max_range` and `obstacles` are a ScanMap's.  The tensors are the caller's."""
+
+    def __init__(self, ev, map, score, count, changed, params, rays, fov, max_range, obstacles, rule):
+        self.ev, self.map, self.score, self.count, self.changed, self.params = ev, map, score, count, changed, params
+        self.rays, self.fov, self.max_range, self.obstacles, self.rule = rays, fov, max_range, obstacles, tuple(rule)
+        self.hit, self.miss, self.cap, self.lo, self.hi, self.free_at, self.occ_at = self.rule
 
     cell = property(lambda self: self.params.cell)
     gx = property(lambda self: self.params.gx)
@@ -408,7 +429,7 @@ class WorldQueries:
         inflate   metres: a cell is blocked too when a raw obstacle cell's centre is closer than this to its own.  None:
                   agent_radius + cell / 2, nav_field()'s default clearance.  0: the raw cells only.  At most
                   engine.NAV_MAX_INFLATE cells.  The agent's radius is NOT added: the caller's grid may already hold it.
-        like      a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell` metres
+        like      a NavField, SeenMap, DepthMap, ObjectMap, ScanMap or ScanEvidence whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell` metres
                   per cell as in nav_field().
         mask      uint8[N] or bool[N] device tensor: only those envs' rows are built (the others are not touched)
         into      a grid field to rebuild in place: the grids are passed again, the grid's parameters are the field's own
@@ -422,7 +443,7 @@ class WorldQueries:
                 raise ValueError("grid_field: with `into` the field's own points and parameters are used: pass only the grids and mask")
             field, params, target = into.field, into.params, into.target
         else:
-            g = self._map_grid("grid_field", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
+            g = self._map_grid("grid_field", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap, ScanEvidence), "its own")
             cell, gx, gz = g.cell, g.gx, g.gz
             inflate = float(e.cfg.agent_radius) + cell / 2 if inflate is None else real("grid_field", "inflate", inflate, lo_open=False)
             if inflate > eng.NAV_MAX_INFLATE * cell:
@@ -532,7 +553,7 @@ class WorldQueries:
         max_range  how far a viewpoint sees, in metres, centre to centre
         fov        the horizontal opening angle in radians about the heading, 0 < fov <= 2 pi.  None: default_fov() for the agent and
                    with `dirs`; with `cells` and no `dirs` the cone is all round and only None or 2 pi is accepted
-        like       a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
+        like       a NavField, SeenMap, DepthMap, ObjectMap, ScanMap or ScanEvidence whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
                    metres per cell as in nav_field()
         mask       uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
         seen       uint8 or bool [N, gz, gx] device tensor: every cell any viewpoint of the env sees is set to 1; never cleared here
@@ -540,7 +561,7 @@ class WorldQueries:
         meets the segment between the two (include/mwengine.h, "grid sight"): a viewpoint sees itself, and an opaque cell's face.
         The tensors are checked and never converted.  ValueError for arguments that make no call; nothing is launched then."""
         torch, e = self.torch, self.engine
-        params = self._map_grid("grid_sight", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
+        params = self._map_grid("grid_sight", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap, ScanEvidence), "its own")
         max_range = real("grid_sight", "max_range", max_range)
         n = self.num_envs
         if cells is None:
@@ -578,7 +599,7 @@ class WorldQueries:
         connectivity  4: cells that share an edge are joined; 8: cells that share a corner too
         min_cells     regions of fewer cells are not counted and not listed (their cells' label is -1)
         max_regions   K, 1 .. engine.REGION_MAX: the regions listed per env, in the order of their lowest cells; `count` may exceed it
-        like          a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
+        like          a NavField, SeenMap, DepthMap, ObjectMap, ScanMap or ScanEvidence whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
                       metres per cell as in nav_field()
         mask          uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
         labels        with the per-cell `label` plane
@@ -596,7 +617,7 @@ class WorldQueries:
                 raise ValueError("grid_regions: with `into` the record's own grid and parameters are used: pass only member and mask")
             out, params = into, into.params
         else:
-            params = self._map_grid("grid_regions", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
+            params = self._map_grid("grid_regions", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap, ScanEvidence), "its own")
             if connectivity not in (4, 8) or isinstance(connectivity, bool):
                 raise ValueError(f"grid_regions: connectivity {connectivity!r}; have 4 and 8")
             min_cells = integer("grid_regions", "min_cells", min_cells, 1, eng.NAV_MAX_CELLS)
@@ -629,7 +650,7 @@ class WorldQueries:
         limit    metres: cells farther than the smallest L cells with L * cell >= limit hold engine.CLEAR_FAR, nearest -1, cost 0, and
                  no scan goes farther: what bounds the work on a nearly empty map.  None: no limit.
         nearest  with the per-cell `nearest` plane
-        like     a NavField, SeenMap, DepthMap, ObjectMap, GridRegions or ScanMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else
+        like     a NavField, SeenMap, DepthMap, ObjectMap, GridRegions, ScanMap or ScanEvidence whose grid (cell, gx, gz) is adopted; pass no cell then.  Else
                  `cell` metres per cell as in nav_field()
         mask     uint8[N] or bool[N] device tensor: only those envs' rows are computed (the others are neither read nor written)
         into     a GridClearance of an earlier call to write into: its grid, bands, limit and optional tensors are used; pass only
@@ -645,7 +666,7 @@ class WorldQueries:
                 raise ValueError(f"{where}: with `into` the record's own grid and parameters are used: pass only marked and mask")
             out, params = into, into.params
         else:
-            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions, ScanMap), "its own")
+            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions, ScanMap, ScanEvidence), "its own")
             if not isinstance(nearest, bool):
                 raise ValueError(f"{where}: nearest must be True or False, not {nearest!r}")
             if (radii is None) != (costs is None):
@@ -821,13 +842,13 @@ class WorldQueries:
         """An empty depth-built map over each env's floor plan: a DepthMap, which depth_map_update() accumulates.  Nothing is launched.
 
         cell        metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
-        like        a NavField, SeenMap, ObjectMap or ScanMap whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass no
+        like        a NavField, SeenMap, ObjectMap, ScanMap or ScanEvidence whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass no
                     cell then
         min_points  how many pixels of ONE depth map must fall into a cell to set it, 1 .. 255
         min_range, max_range, floor_tol, top  as for depth_window()
         At most 16384 cells (the kernel counts in 64 KiB of LDS): ValueError says "use a larger cell" otherwise."""
         torch, e = self.torch, self.engine
-        params = self._map_grid("depth_map", cell, like, (NavField, SeenMap, ObjectMap, ScanMap), "its own")
+        params = self._map_grid("depth_map", cell, like, (NavField, SeenMap, ObjectMap, ScanMap, ScanEvidence), "its own")
         gx, gz = params.gx, params.gz
         if gx * gz > eng.DEPTH_MAX_CELLS:
             raise ValueError(f"depth_map: {gx} x {gz} cells > {eng.DEPTH_MAX_CELLS}: use a larger cell")
@@ -861,12 +882,12 @@ class WorldQueries:
         """An empty scan-built map over each env's floor plan: a ScanMap, which scan_map_update() accumulates.  Nothing is launched.
 
         cell       metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
-        like       a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) the map adopts, so that they line up
+        like       a NavField, SeenMap, DepthMap, ObjectMap, ScanMap or ScanEvidence whose grid (cell, gx, gz) the map adopts, so that they line up
                    cell for cell; pass no cell then
         rays, fov, obstacles  the lidar() that scan_map_update() casts when it is given no scan
         max_range  metres: a beam is traced up to there, and one that reaches it marks no obstacle"""
         torch, e = self.torch, self.engine
-        params = self._map_grid("scan_map", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
+        params = self._map_grid("scan_map", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap, ScanEvidence), "its own")
         rays, fov = integer("scan_map", "rays", rays, 1, eng.RAY_MAX), real("scan_map", "fov", fov, hi=2 * math.pi)
         max_range = real("scan_map", "max_range", max_range)
         self._obstacle_flags("scan_map", obstacles)
@@ -889,23 +910,67 @@ class WorldQueries:
         mask    uint8[N] or bool[N] device tensor: only those envs are updated; the mask wins over clear
         The rule in full: include/mwengine.h, "scan maps".  An env whose extent the grid does not cover gets its map zeroed and
         engine.check() raises once.  ValueError for arguments that make no call; nothing is launched then."""
-        e, n = self.engine, self.num_envs
         if not isinstance(m, ScanMap):
             raise ValueError("scan_map_update: `m` must be a ScanMap (scan_map())")
+        scan, clear, mask = self._scan_update_args("scan_map_update", m, scan, origin, clear, mask)
+        self.engine.scan_project(m.params, m.max_range, scan["t"], scan["dir"], m.map, m.count, m.new, origin, mask, clear)
+        return m.new
+
+    def _scan_update_args(self, where, m, scan, origin, clear, mask):
+        """(scan, clear, mask) of scan_map_update() and scan_evidence_update(), checked and never converted; a None scan is `m`'s own
+        lidar(), cast once everything else is known to be right"""
+        e, n = self.engine, self.num_envs
         if scan is not None:
             if not isinstance(scan, dict) or "t" not in scan or "dir" not in scan:
-                raise ValueError('scan_map_update: `scan` is a dict with "t" and "dir" (a lidar() result, or raycast()\'s with the directions beside it)')
+                raise ValueError(f'{where}: `scan` is a dict with "t" and "dir" (a lidar() result, or raycast()\'s with the directions beside it)')
             if not self._is_tensor(scan["t"], (n, None)) or not 1 <= scan["t"].shape[1] <= eng.RAY_MAX:
-                raise ValueError(f'scan_map_update: scan["t"] is a contiguous float64 tensor [{n}, R] on {e.device}, R in 1 .. {eng.RAY_MAX}')
+                raise ValueError(f'{where}: scan["t"] is a contiguous float64 tensor [{n}, R] on {e.device}, R in 1 .. {eng.RAY_MAX}')
             if not self._is_tensor(scan["dir"], (n, int(scan["t"].shape[1]), 2)):
-                raise ValueError(f'scan_map_update: scan["dir"] is a contiguous float64 tensor [{n}, {int(scan["t"].shape[1])}, 2] on {e.device}')
+                raise ValueError(f'{where}: scan["dir"] is a contiguous float64 tensor [{n}, {int(scan["t"].shape[1])}, 2] on {e.device}')
         if origin is not None and not self._is_tensor(origin, (n, 3)):
-            raise ValueError(f"scan_map_update: origin is a contiguous float64 tensor [{n}, 3] on {e.device}")
-        clear, mask = self._device_mask(clear, "scan_map_update", "clear"), self._device_mask(mask, "scan_map_update")
+            raise ValueError(f"{where}: origin is a contiguous float64 tensor [{n}, 3] on {e.device}")
+        clear, mask = self._device_mask(clear, where, "clear"), self._device_mask(mask, where)
         if scan is None:
             scan = self.lidar(m.rays, m.fov, m.max_range, obstacles=m.obstacles)
-        e.scan_project(m.params, m.max_range, scan["t"], scan["dir"], m.map, m.count, m.new, origin, mask, clear)
-        return m.new
+        return scan, clear, mask
+
+    # ------------------------------------------------------------------ scan evidence
+    def scan_evidence(self, cell=0.25, like=None, rays=256, fov=2 * math.pi, max_range=10.0, obstacles="walls+entities", hit=3, miss=1, cap=1, lo=-20, hi=20,
+                      free_at=-1, occ_at=1):
+        """An empty evidence map over each env's floor plan: a ScanEvidence, which scan_evidence_update() accumulates.  Nothing is launched.
+
+        cell, like, rays, fov, max_range, obstacles  as for scan_map(); `like` may also be a ScanEvidence
+        hit, miss  0 .. 127: what a cell gains per beam that ends in it, loses per beam that passes through it
+        cap        1 .. engine.RAY_MAX: the beams of one scan that count per cell — 1: a scan votes once per cell
+        lo, hi     -127 .. -1 and 1 .. 127: the clamp; with the defaults seven clean misses retract a cell twenty hits built
+        free_at, occ_at  lo .. -1 and 1 .. hi: a cell is free at or below the first, an obstacle at or above the second"""
+        torch, e, where = self.torch, self.engine, "scan_evidence"
+        params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap, ScanEvidence), "its own")
+        rays, fov = integer(where, "rays", rays, 1, eng.RAY_MAX), real(where, "fov", fov, hi=2 * math.pi)
+        max_range = real(where, "max_range", max_range)
+        self._obstacle_flags(where, obstacles)
+        hit, miss, cap = integer(where, "hit", hit, 0, 127), integer(where, "miss", miss, 0, 127), integer(where, "cap", cap, 1, eng.RAY_MAX)
+        lo, hi = integer(where, "lo", lo, -127, -1), integer(where, "hi", hi, 1, 127)
+        free_at, occ_at = integer(where, "free_at", free_at, lo, -1), integer(where, "occ_at", occ_at, 1, hi)
+        n, zeros = self.num_envs, lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=e.device)      # noqa: E731
+        return ScanEvidence(zeros((n, params.gz, params.gx), torch.int8), zeros((n, 2, params.gz, params.gx), torch.uint8), zeros((n, params.gz, params.gx), torch.uint8),
+                            zeros((n, 2), torch.int32), zeros((n, 2), torch.int32), params, rays, fov, max_range, obstacles, (hit, miss, cap, lo, hi, free_at, occ_at))
+
+    def scan_evidence_update(self, m, scan=None, origin=None, clear=None, mask=None):
+        """Counts a range scan's beams into `m` (a ScanEvidence), by one kernel (mw_scan_evidence) with no host value and no
+        synchronisation: a cell where beams shorter than m.max_range end gains m.hit per beam, any other cell loses m.miss per beam
+        that passes through it, either for at most m.cap beams, and m.ev is clamped to m.lo .. m.hi; m.map, m.score and m.count are
+        rewritten from it.  Returns m.changed, int32[N, 2]: the cells that joined or left the free and the obstacle plane.  Unlike a
+        ScanMap, a later scan takes back what an earlier one got wrong.
+
+        scan, origin, clear, mask  as for scan_map_update(): the same checks; under `clear` the evidence restarts from 0
+        The rule in full: include/mwengine.h, "scan evidence".  An env whose extent the grid does not cover gets its planes zeroed and
+        engine.check() raises once.  ValueError for arguments that make no call; nothing is launched then."""
+        if not isinstance(m, ScanEvidence):
+            raise ValueError("scan_evidence_update: `m` must be a ScanEvidence (scan_evidence())")
+        scan, clear, mask = self._scan_update_args("scan_evidence_update", m, scan, origin, clear, mask)
+        self.engine.scan_evidence(m.params, m.max_range, m.rule, scan["t"], scan["dir"], m.ev, m.count, m.map, m.score, m.changed, origin, mask, clear)
+        return m.changed
 
     # ------------------------------------------------------------------ scan matching
     def scan_match(self, score, scan, origin=None, window=8, turn=0.0, turns=1, max_range=10.0, like=None, cell=0.25, mask=None, volume=False, into=None):
@@ -949,7 +1014,7 @@ class WorldQueries:
                 raise ValueError(f"{where}: with `into` the record's own grid and parameters are used: pass only score, scan, origin and mask")
             out = into
         else:
-            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions, GridClearance, ScanMap), "its own")
+            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions, GridClearance, ScanMap, ScanEvidence), "its own")
             window = integer(where, "window", window, 0, max_window)
             turns = integer(where, "turns", turns, 1, eng.MATCH_MAX_ROT)
             turn = real(where, "turn", turn, hi=math.pi, lo_open=False)
@@ -1028,7 +1093,7 @@ class WorldQueries:
                 raise ValueError(f"{where}: with `into` the record's own grid and max_range are used: pass only score, scan, poses and mask")
             params, max_range = into.params, into.max_range
         else:
-            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions, GridClearance, ScanMap, ScanMatch, ScanWeights), "its own")
+            params = self._map_grid(where, cell, like, (NavField, SeenMap, DepthMap, ObjectMap, GridRegions, GridClearance, ScanMap, ScanEvidence, ScanMatch, ScanWeights), "its own")
             max_range = real(where, "max_range", max_range)
         if not self._is_tensor(score, (n, params.gz, params.gx), torch.uint8):
             raise ValueError(f"{where}: score is a contiguous uint8 tensor [{n}, {params.gz}, {params.gx}] on {e.device}")
@@ -1195,14 +1260,14 @@ class WorldQueries:
         """An empty sensed object map over each env's floor plan: an ObjectMap, which object_map_update() keeps.  Nothing is launched.
 
         cell   metres per cell; gx, gz follow from the template world's extent exactly as in nav_field()
-        like   a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass
+        like   a NavField, SeenMap, DepthMap, ObjectMap, ScanMap or ScanEvidence whose grid (cell, gx, gz) the map adopts, so that they line up cell for cell; pass
                no cell then
         ids    K, 0 .. 255: `cells` and `pos` have a row for each id below it (an id from K on is mapped, not counted); None: the env's
                entity slots, at most 255.  0: the map alone
         min_range, max_range, floor_tol, top  as for depth_window()
         At most 16384 cells (the kernel keeps a key per cell in LDS): ValueError says "use a larger cell" otherwise."""
         torch, e = self.torch, self.engine
-        params = self._map_grid("object_map", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
+        params = self._map_grid("object_map", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap, ScanEvidence), "its own")
         gx, gz = params.gx, params.gz
         if gx * gz > eng.LABELMAP_MAX_CELLS:
             raise ValueError(f"object_map: {gx} x {gz} cells > {eng.LABELMAP_MAX_CELLS}: use a larger cell")
@@ -1324,7 +1389,7 @@ class WorldQueries:
         offsets    float64[R] device tensor of angles in radians added to a heading (raycast()'s fan), with
         heading    float64[N] device tensor, a pose estimate's heading per env; None: each agent's own
         origin     float64[N, R, 3] device tensor (y is not read); None: each env's agent position for all its rays
-        like       a NavField, SeenMap, DepthMap, ObjectMap or ScanMap whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
+        like       a NavField, SeenMap, DepthMap, ObjectMap, ScanMap or ScanEvidence whose grid (cell, gx, gz) is adopted; pass no cell then.  Else `cell`
                    metres per cell as in nav_field()
         mask       uint8[N] or bool[N] device tensor: only those envs' rows are read and written
         into       a previous result of the same R to write into; without it new tensors are allocated (unmasked rows: t = max_t,
@@ -1333,7 +1398,7 @@ class WorldQueries:
         rule in full: include/mwengine.h, "grid ray casts"; a NaN in a ray gives max_t and -1.  The tensors are checked and never
         converted.  ValueError for arguments that make no cast; nothing is launched then."""
         torch, e, n, ok = self.torch, self.engine, self.num_envs, self._is_tensor
-        params = self._map_grid("grid_raycast", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap), "its own")
+        params = self._map_grid("grid_raycast", cell, like, (NavField, SeenMap, DepthMap, ObjectMap, ScanMap, ScanEvidence), "its own")
         if (direction is None) == (offsets is None):
             raise ValueError("grid_raycast: give exactly one of direction (float64[N, R, 2]) and offsets (float64[R])")
         if offsets is not None:
