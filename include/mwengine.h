@@ -1435,6 +1435,56 @@ int mw_grid_ray_cast(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are
                      const double *d_heading /* [N], with d_offsets, or NULL = the agents' */, double *d_t /* [N][R] */,
                      int32_t *d_hit /* [N][R] or NULL */, double *d_dir_out /* [N][R][2] or NULL */, void *stream);
 
+/* ---- grid rollouts ----------------------------------------------------------- */
+/* mw_step_plan's trace on the caller's OWN map: P candidate plans of T actions per env run through the agent's kinematics against a
+ * uint8 obstacle plane, each scored against a nav field and a cost plane — the inner loop of random shooting, CEM and MPPI for a policy
+ * that knows only the map it built and the pose it estimated.  No env per candidate, nothing of the simulator's walls.  The reference
+ * has no such call.
+ *
+ * The rule.  All arithmetic is float64, uncontracted, in exactly this order.  Per env: min_x, min_z the env's own extent, cell, gx, gz
+ * the grid's, word for word as for mw_scan_project; rc = radius / cell, r2 = rc * rc, radius = host_radius[0].  The start pose (x, z, dir)
+ * is d_pose[i] or, with a null d_pose, the pose the device holds now; it does not have to be free.  (fwd, drift, turn) is d_step[i] or the
+ * config's forward_step, forward_drift and turn_step defaults (under domain randomisation the engine draws these per step; a planner's
+ * model takes what it is given).  Step k of plan p executes a = d_plans[k][i][p]:
+ *   a == 0 / 1:  dir = dir + turn * (pi / 180.0), resp. with -turn (the engine's own turn)
+ *   a == 2 / 3:  with f = +fwd, resp. -fwd:  (s, c) = the engine's deterministic sin / cos of dir (|dir| >= 1e6 or NaN: NaNs);
+ *                nx = x + c * f + s * drift;  nz = z + (-s) * f + c * drift  (the engine's own move); the move is refused iff
+ *                blocked(nx, nz), otherwise (x, z) = (nx, nz)
+ *   anything else: nothing happens (pickup, drop and done do not move a pose; carrying is not modelled)
+ * blocked(px, pz):  u = (px - min_x) / cell, w = (pz - min_z) / cell; not finite, or 2^30 or more in magnitude: blocked.  The box is
+ *   columns floor(u - rc) .. floor(u + rc) and rows floor(w - rc) .. floor(w + rc).  A cell of the box inside the grid is opaque iff
+ *   d_opaque[i][row][column] != 0, one outside iff MW_GPLAN_OUTSIDE_BLOCKS.  For an opaque cell (row j, column c):
+ *     dx = max(max((double)c - u, u - (double)(c + 1)), 0.0);  dz likewise with j and w;  d2 = dx * dx + dz * dz
+ *   blocked iff some opaque cell of the box has d2 < r2 or is the cell (floor(w), floor(u)) itself — the point's own, so radius = 0 is the
+ *   plain cell test for a plane the caller inflated already.  An OR over a set: nothing depends on the kernel's schedule.
+ * After every executed step, with (floor(w), floor(u)) the cell of the pose: cost += d_extra there (0 outside the grid or with a null
+ * d_extra); v = d_field there (0xFFFF outside the grid or with a null d_field); if v < reach: reach = v, reach_step = k + 1; a refused
+ * move adds 1 to bumps.  Before step 0 reach is the start cell's v and reach_step = 0.  With stop_at >= 0 a plan stops as soon as reach
+ * <= stop_at — at step 0 if the start already is —; steps is the number of steps it executed, T if it never stopped, and nothing is
+ * added after the stop.
+ * d_stats[i][p] = (reach, reach_step, steps, bumps, cost); d_pose_out[i][p] = the final (x, z, dir); d_trace[k][i][p], if given, = the
+ * pose behind step k, and the rows a stopped plan did not execute repeat its last pose, as mw_plan_trace's rows do.
+ * An env whose extent the grid does not cover (as for mw_nav_build) gets stats (0xFFFF, 0, 0, 0, 0) and its start pose in every row, and
+ * sets the status bit mw_scan_project sets there: the next mw_check reports it as MW_E_INVALID, once.  Rows of envs under a zero mask byte
+ * are neither read nor written.
+ *
+ * One kernel, a plan per lane, asynchronous on `stream`; it reads no host value except host_radius (during the call), reads live arrays
+ * only and changes nothing in the engine.  MW_E_INVALID before anything is launched, and nothing touched: a null engine, grid,
+ * host_radius, d_opaque, d_plans, d_pose_out or d_stats; a grid mw_nav_build would refuse; T outside 1 .. MW_MAX_PLAN; P outside 1 ..
+ * MW_GPLAN_MAX_PLANS; a radius that is negative or not finite, or above MW_GPLAN_MAX_RADIUS * cell; unknown flag bits; stop_at outside
+ * -1 .. 0xFFFF, or stop_at >= 0 with a null d_field; more workgroups than a launch holds. */
+#define MW_GPLAN_MAX_PLANS 4096     /* plans per env and call */
+#define MW_GPLAN_MAX_RADIUS 8       /* the disc's radius in cells */
+#define MW_GPLAN_OUTSIDE_BLOCKS 1   /* flags: cells outside the grid are opaque */
+#define MW_GPLAN_BYTE_PLANS 2       /* flags: d_plans is uint8, else int32 */
+int mw_grid_plan(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are read; the rest is ignored */,
+                 const double *host_radius /* [1] on the host: metres */, int32_t flags, int32_t T, int32_t P, int32_t stop_at /* -1: never */,
+                 const uint8_t *d_mask, const uint8_t *d_opaque /* [N][gz][gx] */, const void *d_plans /* [T][N][P] */,
+                 const double *d_pose /* [N][3]: x, z, dir; NULL = the agents */,
+                 const double *d_step /* [N][3]: forward, drift, turn (degrees); NULL = the config's defaults */,
+                 const uint16_t *d_field /* [N][gz][gx] or NULL */, const uint8_t *d_extra /* [N][gz][gx] or NULL */,
+                 double *d_pose_out /* [N][P][3] */, int32_t *d_stats /* [N][P][5] */, double *d_trace /* [T][N][P][3] or NULL */, void *stream);
+
 /* ---- scan evidence ----------------------------------------------------------- */
 /* The map a range scanner gives when a scan may be wrong.  A mw_scan_project byte only goes 0 -> 1: an obstacle cell drawn from a wrong
  * pose estimate stays, and a cell can be both free and obstacle.  Every mapper that call is modelled on keeps evidence per cell instead
@@ -1487,7 +1537,7 @@ int mw_scan_evidence(mw_engine *e, const mw_nav_params *grid /* cell, gx, gz are
  * mesh_tile_waves or ent_blocks of 1 .. 7.  Afterwards the next frame is drawn whole (no frame reuse across the call). */
 int mw_debug_set_launch_shape(mw_engine *e, int waves_per_env, int mesh_tile_waves, int ent_blocks, int slow_waves);
 
-/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match, mw_scan_search, mw_scan_weigh, mw_grid_ray_cast, mw_scan_evidence or mw_label_project skipped
+/* checks the device-side status word (capacity overflows, items a snapshot call skipped; envs mw_set_state_where, mw_nav_build, mw_seen_update, mw_grid_sight, mw_depth_project, mw_scan_project, mw_scan_match, mw_scan_search, mw_scan_weigh, mw_grid_ray_cast, mw_grid_plan, mw_scan_evidence or mw_label_project skipped
  * — these are reported first, by one check each, and then forgotten, the others by every check from then on); synchronises `stream` */
 int mw_check(mw_engine *e, void *stream);
 

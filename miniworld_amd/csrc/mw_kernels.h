@@ -22,6 +22,7 @@
 #include "mw_match.h"
 #include "mw_search.h"
 #include "mw_gridray.h"
+#include "mw_gridplan.h"
 #include "mw_weigh.h"
 #include "mw_evidence.h"
 
@@ -434,6 +435,17 @@ extern "C" __global__ void mw_evidence_kernel(MwNavArgs a, mw_nav_params p, doub
                                               const double *__restrict__ dir, const double *__restrict__ origin, const uint8_t *__restrict__ mask,
                                               const uint8_t *__restrict__ clear, int8_t *__restrict__ ev, uint8_t *__restrict__ map,
                                               uint8_t *__restrict__ score, int32_t *__restrict__ count, int32_t *__restrict__ changed);
+
+// grid rollouts (mw_gridplan.hip; the rule, the bit plane and the plan's loop: mw_gridplan.h; the launch: mwpolicy::gridplan_launch).  The
+// grid (cell, gx, gz are read) and the call's scalars travel by value; of the view the extent and, with a null pose, ax / az / adir are
+// read.  opaque uint8[N][gz][gx]; plans int32 or uint8 (MW_GPLAN_BYTE_PLANS) [T][N][P]; pose and step double[N][3] or null; field
+// uint16[N][gz][gx] or null; extra uint8[N][gz][gx] or null; pose_out double[N][P][3]; stats int32[N][P][5]; trace double[T][N][P][3] or
+// null; an env under a zero mask byte is skipped.  Grid N * ceil(P / threads) workgroups of threads = min(MW_GPLAN_THREADS, P rounded
+// up to 64) lanes, a plan per lane, mwgplan::plane_bytes(gx, gz) bytes of dynamic LDS.
+extern "C" __global__ void mw_gridplan_kernel(MwRayArgs a, mw_nav_params p, mwgplan::Call q, const uint8_t *__restrict__ mask,
+                                              const uint8_t *__restrict__ opaque, const void *__restrict__ plans, const double *__restrict__ pose,
+                                              const double *__restrict__ step, const uint16_t *__restrict__ field, const uint8_t *__restrict__ extra,
+                                              double *__restrict__ pose_out, int32_t *__restrict__ stats, double *__restrict__ trace);
 
 // the occlusion queries of mw_visible_ents (mw_visible.hip)
 extern "C" __global__ void mw_visible_kernel(int env_base, int W, int H, int S, int max_vis, int E, const float *__restrict__ rec_raster,

@@ -20,6 +20,7 @@
 #include "mw_match.h"           // MW_MATCH_THREADS, mwmatch::plane_bytes, ends_bytes, fill_bytes
 #include "mw_search.h"          // MW_SEARCH_THREADS, mwsearch::plane_bytes, bound_bytes, ends_bytes, words_bytes, fill_bytes
 #include "mw_gridray.h"         // MW_GRIDRAY_THREADS, mwgray::staged_bytes
+#include "mw_gridplan.h"        // MW_GPLAN_THREADS, mwgplan::plane_bytes
 #include "mw_weigh.h"           // MW_WEIGH_THREADS, mwweigh::plane_bytes, beams_bytes, prefix_bytes
 #include "mw_evidence.h"        // MW_EVIDENCE_THREADS, mwevid::count_bytes, prefix_bytes
 #include "mw_shape.h"
@@ -593,6 +594,20 @@ inline Launch evidence_launch(int N, long long cells, int rays)
     const bool in_range = cells >= 1 && cells <= MW_NAV_MAX_CELLS && rays >= 1 && rays <= MW_RAY_MAX;
     const size_t lds = in_range ? mwevid::count_bytes(cells) + mwevid::prefix_bytes(rays) : 0;
     return {(unsigned long long)N, MW_EVIDENCE_THREADS, lds, in_range && lds <= kSearchMaxLds};
+}
+
+// Grid rollouts (mw_grid_plan; kernel: mw_gridplan.hip): a plan per lane, a workgroup per (env, block of plans) of min(MW_GPLAN_THREADS,
+// P rounded up to 64) lanes — 32 plans are one wavefront per env; 4096 are 16 workgroups per env, each of which stages the env's plane
+// again and reads it from L2.  Its LDS is the obstacle plane as bits inside its ring: 16 bytes for one cell, 4 208 for 128 x 256 cells,
+// 12 304 for the 1 x 32768 grid.  One form: the field and the cost plane are read in global memory, once per accepted move (staging them
+// beside the bits, 64 + 32 KiB more, was not built).  Not measured: other lane counts, MW_GPLAN_AHEAD other than 8.
+// fits: gx, gz >= 1 with no more than MW_NAV_MAX_CELLS cells and 1 .. MW_GPLAN_MAX_PLANS plans — the caller refuses what does not.
+inline Launch gridplan_launch(int N, int gx, int gz, int plans)
+{
+    const bool fits = gx >= 1 && gz >= 1 && (long long)gx * gz <= MW_NAV_MAX_CELLS && plans >= 1 && plans <= MW_GPLAN_MAX_PLANS;
+    if (!fits) return {(unsigned long long)N, MW_GPLAN_THREADS, 0, false};
+    const int rounded = (plans + 63) / 64 * 64, threads = rounded < MW_GPLAN_THREADS ? rounded : MW_GPLAN_THREADS;
+    return {(unsigned long long)N * (unsigned long long)((plans + threads - 1) / threads), threads, mwgplan::plane_bytes(gx, gz), true};
 }
 
 }  // namespace mwpolicy

@@ -137,6 +137,8 @@ CLEAR_MAX_BANDS = 8                     # MW_CLEAR_MAX_BANDS: mw_grid_clearance'
 MATCH_MAX_ROT, MATCH_MAX_WINDOW = 64, 32        # MW_MATCH_MAX_ROT, MW_MATCH_MAX_WINDOW: mw_scan_match's rotations per call, cells either way
 SEARCH_MAX_WINDOW = 128                 # MW_SEARCH_MAX_WINDOW: mw_scan_search's cells either way
 WEIGH_MAX_PARTICLES = 4096              # MW_WEIGH_MAX_PARTICLES: mw_scan_weigh's and mw_resample's particles per env and call
+GPLAN_MAX_PLANS, GPLAN_MAX_RADIUS = 4096, 8     # MW_GPLAN_MAX_PLANS, MW_GPLAN_MAX_RADIUS: mw_grid_plan's plans per env and call, its disc's radius in cells
+GPLAN_OUTSIDE_BLOCKS, GPLAN_BYTE_PLANS = 1, 2   # MW_GPLAN_* flags
 
 EGO_ENTITIES, EGO_NORTH = 1, 2          # MW_EGO_* flags
 EGO_WALL, EGO_ENTITY, EGO_VISIBLE = 1, 2, 4     # MW_EGO_* planes
@@ -253,6 +255,7 @@ SIGNATURES = {
     "mw_ray_cast": _sig(vp, P(MwRayParams), vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_debug_set_ray_form": _sig(vp, C.c_int),
     "mw_grid_ray_cast": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+    "mw_grid_plan": _sig(vp, P(MwNavParams), P(C.c_double), i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_grid_regions": _sig(vp, P(MwNavParams), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "mw_grid_clearance": _sig(vp, P(MwNavParams), i32, P(i32), i32, vp, vp, vp, vp, vp, vp),
     "mw_scan_project": _sig(vp, P(MwNavParams), P(C.c_double), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp),
@@ -644,6 +647,46 @@ class Engine:
         host = (C.c_double * 1)(float(max_t))
         self._check(self.lib.mw_grid_ray_cast(self.h, C.byref(params), host, int(rays), _ptr(mask), _ptr(opaque), _ptr(origin), _ptr(direction), _ptr(offsets),
                                               _ptr(heading), _ptr(t), _ptr(hit), _ptr(dir_out), _stream_ptr(self.device)), "mw_grid_ray_cast")
+
+    # -- grid rollouts -------------------------------------------------------------------
+    def grid_plan(self, params: MwNavParams, radius: float, flags: int, stop_at: int, opaque, plans, pose_out, stats, trace=None, field=None, extra=None, pose=None,
+                  step=None, mask=None):
+        """mw_grid_plan: the P plans of T actions per env in `plans` (int32 or uint8 [T, N, P], device) under `mask` (uint8[N], device;
+        None = all) run over `opaque` (uint8[N, gz, gx]) from `pose` (float64[N, 3]: x, z, dir; None = the agents) with the step sizes
+        `step` (float64[N, 3]: forward, drift, turn in degrees; None = the config's defaults) and a disc of `radius` metres, scored
+        against `field` (uint16[N, gz, gx]) and `extra` (uint8[N, gz, gx]), both optional, into pose_out (float64[N, P, 3]), stats
+        (int32[N, P, 5]: reach, reach_step, steps, bumps, cost) and trace (float64[T, N, P, 3], optional).  `flags`: GPLAN_OUTSIDE_BLOCKS;
+        GPLAN_BYTE_PLANS follows from the plans' dtype.  stop_at -1: never.  One kernel on the current stream, no synchronisation,
+        nothing of the engine changes.  A wrong tensor is refused before the library is called."""
+        import torch
+        for name, t in (("opaque", opaque), ("plans", plans), ("pose_out", pose_out), ("stats", stats)):
+            if t is None:
+                raise EngineError(f"{name}: None")
+        if not torch.is_tensor(plans) or plans.dim() != 3 or plans.shape[1] != self.N or plans.dtype not in (torch.int32, torch.uint8):
+            raise EngineError(f"plans: need an int32 or uint8 tensor [T, {self.N}, P] on {self.device}, got "
+                              f"{(plans.dtype, tuple(plans.shape)) if torch.is_tensor(plans) else type(plans).__name__}")
+        T, P = int(plans.shape[0]), int(plans.shape[2])
+        if not 1 <= T <= MAX_PLAN or not 1 <= P <= GPLAN_MAX_PLANS:
+            raise EngineError(f"plans: T = {T} outside 1 .. {MAX_PLAN} or P = {P} outside 1 .. {GPLAN_MAX_PLANS}")
+        if int(flags) & ~GPLAN_OUTSIDE_BLOCKS:
+            raise EngineError(f"flags: {int(flags):#x}: only GPLAN_OUTSIDE_BLOCKS is the caller's")
+        grid = (self.N, int(params.gz), int(params.gx))
+        self._dev_tensor(plans, "plans", plans.dtype, T * self.N * P)
+        self._shaped_tensor(opaque, "opaque", torch.uint8, grid)
+        if field is not None:
+            self._shaped_tensor(field, "field", torch.uint16, grid)
+        if extra is not None:
+            self._shaped_tensor(extra, "extra", torch.uint8, grid)
+        self._dev_tensor(pose, "pose", torch.float64, self.N * 3)
+        self._dev_tensor(step, "step", torch.float64, self.N * 3)
+        self._dev_tensor(pose_out, "pose_out", torch.float64, self.N * P * 3)
+        self._dev_tensor(stats, "stats", torch.int32, self.N * P * 5)
+        self._dev_tensor(trace, "trace", torch.float64, T * self.N * P * 3)
+        mask = self._mask_tensor(mask, optional=True)
+        flags = int(flags) | (GPLAN_BYTE_PLANS if plans.dtype == torch.uint8 else 0)
+        host = (C.c_double * 1)(float(radius))
+        self._check(self.lib.mw_grid_plan(self.h, C.byref(params), host, flags, T, P, int(stop_at), _ptr(mask), _ptr(opaque), _ptr(plans), _ptr(pose), _ptr(step),
+                                          _ptr(field), _ptr(extra), _ptr(pose_out), _ptr(stats), _ptr(trace), _stream_ptr(self.device)), "mw_grid_plan")
 
     # -- explored-area maps --------------------------------------------------------------
     def seen_update(self, params: MwNavParams, max_range: float, cos_half: float, flags: int, seen, count, new=None, mask=None, clear=None):

@@ -1,6 +1,6 @@
 """The world queries of the batched env — navigation fields, explored-area maps, grid sight, grid regions, grid clearance, egocentric map windows,
-depth projection, label frames, object maps, ray casts, scan maps, scan evidence, scan matching, scan weighing and resampling —, each one kernel on the device with no host value: their value
-classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance, ScanMap, ScanEvidence, ScanMatch, ScanWeights) and
+depth projection, label frames, object maps, ray casts, scan maps, scan evidence, scan matching, scan weighing and resampling, grid rollouts —, each one kernel on the device with no host value: their value
+classes (NavField, SeenMap, EgoWindow, DepthWindow, DepthMap, LabelFrame, ObjectWindow, ObjectMap, GridRegions, GridClearance, ScanMap, ScanEvidence, ScanMatch, ScanWeights, GridRollout) and
 `WorldQueries`, a mixin of MiniWorldVecEnv (vec_env.py)."""
 from __future__ import annotations
 
@@ -303,6 +303,24 @@ class GridClearance:
         while t < 2 ** 30 and inside(t + 1):
             t += 1
         return t
+
+
+class GridRollout:
+    """What candidate plans would do on the caller's own map (MiniWorldVecEnv.grid_rollout): `pose`, float64[N, P, 3], the final
+    (x, z, dir) of each plan; `stats`, int32[N, P, 5], whose columns are the views `reach` — the least field value the plan's poses
+    met, the start's included, 0xFFFF without a field —, `reach_step` — the number of steps after which it was first met —, `steps` —
+    the steps executed: T unless stop_at ended the plan —, `bumps` — the moves the map refused — and `cost` — the sum of `extra` over
+    the poses behind every executed step —; and `trace`, float64[T, N, P, 3], the pose behind every step, or None.  `params` is the
+    grid.  The tensors are the caller's."""
+
+    def __init__(self, pose, stats, trace, params):
+        self.pose, self.stats, self.trace, self.params = pose, stats, trace, params
+
+    reach = property(lambda self: self.stats[..., 0])
+    reach_step = property(lambda self: self.stats[..., 1])
+    steps = property(lambda self: self.stats[..., 2])
+    bumps = property(lambda self: self.stats[..., 3])
+    cost = property(lambda self: self.stats[..., 4])
 
 
 assert eng.SIGHT_MAX_VIEWS == eng.REGION_MAX        # (a row of GridRegions.cell is a row of grid_sight's cells)
@@ -1456,3 +1474,80 @@ class WorldQueries:
         buf[1] = self.grid_raycast(opaque, origin=buf[2] if origin is not None else None, offsets=buf[0], heading=heading, max_t=max_range, like=like, cell=cell,
                                    into=buf[1])
         return buf[1]
+
+    # ------------------------------------------------------------------ grid rollouts
+    def grid_rollout(self, blocked, plans, field=None, extra=None, pose=None, step=None, radius=None, outside="blocked", stop_at=None, trace=False, like=None,
+                     cell=0.25, mask=None, into=None):
+        """rollout(render=False, trace=...) on the caller's OWN map: where P candidate plans of T actions per env would take the agent
+        on the map it believes in, and what each is worth, by one kernel (mw_grid_plan) with no host value, no synchronisation and no
+        env per candidate: a GridRollout.  The inner loop of random shooting, CEM and MPPI for a map-only policy.
+
+        blocked   uint8 or bool [N, gz, gx] device tensor: != 0 an obstacle cell (a ScanMap's or DepthMap's obstacle plane made
+                  contiguous).  A move is refused when a disc of `radius` around the new position touches one, or lies in one
+        plans     int32 or uint8 [T, N, P] device tensor of actions, time-major as rollout()'s: 0 / 1 turn left / right, 2 / 3 move
+                  forward / back, anything else leaves the pose as it is
+        field     a NavField — its grid is the call's, as `like=` elsewhere; pass no like or cell then — or a uint16[N, gz, gx] device
+                  tensor: `reach` is the least of its values along the plan
+        extra     the same kind of tensor as `blocked`: a cost 0 .. 255 summed over the poses behind every step (grid_clearance's cost)
+        pose      float64[N, 3] device tensor of (x, z, dir), a pose estimate per env; None: each agent's own
+        step      float64[N, 3] device tensor of (forward, drift, turn in degrees) per env; None: the config's defaults
+        radius    metres, at most engine.GPLAN_MAX_RADIUS cells; None: the engine's agent_radius; 0: the cell test alone, for a plane
+                  that is inflated already
+        outside   "blocked": cells outside the grid are obstacles; "open": they are free
+        stop_at   a plan stops as soon as its `reach` is <= this (0: at the field's sources); needs a field.  None: never
+        trace     with the pose behind every step
+        like      a NavField, SeenMap, DepthMap, ObjectMap, ScanMap or ScanEvidence whose grid (cell, gx, gz) is adopted; pass no cell
+                  then.  Else `cell` metres per cell as in nav_field()
+        mask      uint8[N] or bool[N] device tensor: only those envs' rows are read and written
+        into      a GridRollout of the same T, P and trace to write into; without it new tensors are allocated (unmasked rows: 0)
+        Where nothing is in the way the poses are, bit for bit, those of rollout()'s trace.  The rule in full: include/mwengine.h,
+        "grid rollouts".  The tensors are checked and never converted.  ValueError for arguments that make no call; nothing is
+        launched then."""
+        torch, e, n, where = self.torch, self.engine, self.num_envs, "grid_rollout"
+        kinds = (NavField, SeenMap, DepthMap, ObjectMap, ScanMap, ScanEvidence)
+        if isinstance(field, NavField):
+            if like is not None or cell != 0.25:
+                raise ValueError(f"{where}: a NavField's grid is the call's: pass no like or cell")
+            like = field
+        params = self._map_grid(where, cell, like, kinds, "its own")
+        if isinstance(field, NavField):
+            field = field.field
+        if field is not None and not self._is_tensor(field, (n, params.gz, params.gx), torch.uint16):
+            raise ValueError(f"{where}: field is a NavField or a contiguous uint16 tensor [{n}, {params.gz}, {params.gx}] on {e.device}")
+        if not any(self._is_tensor(plans, (None, n, None), dt) for dt in (torch.int32, torch.uint8)):
+            raise ValueError(f"{where}: plans is a contiguous int32 or uint8 tensor [T, {n}, P] on {e.device}")
+        T, P = int(plans.shape[0]), int(plans.shape[2])
+        if not 1 <= T <= eng.MAX_PLAN:
+            raise ValueError(f"{where}: T = {T} outside 1 .. {eng.MAX_PLAN}")
+        if not 1 <= P <= eng.GPLAN_MAX_PLANS:
+            raise ValueError(f"{where}: {P} plans per env outside 1 .. {eng.GPLAN_MAX_PLANS}")
+        for name, t in (("pose", pose), ("step", step)):
+            if t is not None and not self._is_tensor(t, (n, 3)):
+                raise ValueError(f"{where}: {name} is a contiguous float64 tensor [{n}, 3] on {e.device}")
+        radius = float(e.cfg.agent_radius) if radius is None else real(where, "radius", radius, lo_open=False)
+        if radius > eng.GPLAN_MAX_RADIUS * params.cell:
+            raise ValueError(f"{where}: radius {radius!r} is more than {eng.GPLAN_MAX_RADIUS} cells of {params.cell!r}")
+        if outside not in ("blocked", "open"):
+            raise ValueError(f"{where}: outside {outside!r}; have 'blocked' and 'open'")
+        if stop_at is not None:
+            stop_at = integer(where, "stop_at", stop_at, 0, 0xFFFF)
+            if field is None:
+                raise ValueError(f"{where}: stop_at without a field: there is nothing to reach")
+        if not isinstance(trace, bool):
+            raise ValueError(f"{where}: trace must be True or False, not {trace!r}")
+        blocked = self._cell_grid(where, "blocked", blocked, params.gz, params.gx, optional=False)
+        extra = self._cell_grid(where, "extra", extra, params.gz, params.gx)
+        mask = self._device_mask(mask, where)
+        if into is not None:
+            if not isinstance(into, GridRollout):
+                raise ValueError(f"{where}: `into` must be a GridRollout")
+            if (not self._is_tensor(into.pose, (n, P, 3)) or not self._is_tensor(into.stats, (n, P, 5), torch.int32)
+                    or (into.trace is not None) != trace or (trace and not self._is_tensor(into.trace, (T, n, P, 3)))):
+                raise ValueError(f"{where}: `into` is a GridRollout of T = {T}, P = {P} and trace = {trace} on {e.device}")
+            out = into
+        else:
+            out = GridRollout(torch.zeros((n, P, 3), dtype=torch.float64, device=e.device), torch.zeros((n, P, 5), dtype=torch.int32, device=e.device),
+                              torch.zeros((T, n, P, 3), dtype=torch.float64, device=e.device) if trace else None, params)
+        e.grid_plan(params, radius, eng.GPLAN_OUTSIDE_BLOCKS if outside == "blocked" else 0, -1 if stop_at is None else stop_at, blocked, plans, out.pose, out.stats,
+                    out.trace, field, extra, pose, step, mask)
+        return out
